@@ -10,6 +10,13 @@ independent, test_kitti_pose.py:134-145); after the timed region the ranks' pose
 RCCL all-gather (davo_amd/comm.py), reported separately and not part of `value`.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--settle S] [--batch B] [--height H --width W] [--force-comm]
+                    [--dump-outputs DIR] [--full]
+
+A plain run sets up, runs the untimed steps, times the K steps, writes the last timed step's poses if `--dump-outputs DIR`
+is given (DIR/pose.npy on rank 0, DIR/pose_rank<r>.npy on rank r > 0: float32 [B,2,6]; the inputs are seeded, so equal
+arguments give equal inputs run to run) and prints the headline line.  `--full` adds everything else the line has carried:
+the event-bracketed dominant launch and `timing`, the per-kernel pass, the roofline blocks, the other arithmetic, the
+two-in-flight leg, the pose all-gather, the parity check against the CPU oracle and the CPU baseline.
 
 Untimed before the timed region: W warm-up steps, then S settle steps (default: whatever brings W + S to 100) — the
 chip's clock needs ~25 steps (30 ms) of this load to settle after idle.  The JSON's `warmup` is the number of untimed
@@ -125,6 +132,11 @@ def parse_args():
     ap.add_argument("--options", default="", help="davo_set_option pairs applied before the first step, k=v,k=v (A/B of launch plans under the profiler)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-sample", type=int, default=8, help="triplets per CPU-baseline pass")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the poses of the last timed step as DIR/pose.npy (float32 [B,2,6]; rank r > 0: pose_rank<r>.npy)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beyond the headline figure (event-bracketed timing, per-kernel pass, "
+                         "rooflines, the other arithmetic, two in flight, all-gather, oracle parity, CPU baseline)")
     return ap.parse_args()
 
 
@@ -199,6 +211,52 @@ def main():
         eng.forward_device(B, *sets[i % nset])
     eng.synchronize()
 
+    def finish(res):
+        """print the line on rank 0, then release the communicator, the buffers and the context"""
+        if rank == 0:
+            print(json.dumps(res), flush=True)
+        if comm is not None:
+            comm.barrier()
+            comm.close()
+        for st in sets:
+            for b in st:
+                b.free()
+        eng.close()
+
+    dtype = ("f32 (v_mfma_f32_32x32x2_f32: the reference's arithmetic, slim.conv2d in float32)" if args.precision == "f32"
+             else "f16x3 (fp16 hi/lo split operands, 3 MFMA products, f32 accumulate)")
+
+    def headline(elapsed):
+        return {
+            "metric": "pose-net triplets/sec (128x416x3-frame)" if (H, W) == (128, 416)
+                      else "pose-net triplets/sec (%dx%dx3-frame)" % (H, W),
+            "value": round(world * B * args.steps / elapsed, 2), "unit": "triplets/s", "n_gpus": world, "steps": args.steps,
+            "warmup": args.warmup + settle, "warmup_arg": args.warmup, "settle_steps": settle,
+            "ms_per_step": round(elapsed / args.steps * 1e3, 4),
+            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": dtype,
+            "data": "synthetic (splitmix64 seed 8964; random-init He-uniform weights; no KITTI/ckpt offline)",
+            "config": {"workload": workload_name(B, H, W, world),
+                       "version": FLAGSHIP_VERSION, "batch_per_gpu": B, "height": H, "width": W,
+                       "parallelism": "window-sharded replicas x%d" % world, "batches_in_flight": nset,
+                       **({"options": args.options} if args.options else {})},
+            "full": bool(args.full),
+        }
+
+    def dump_outputs():
+        """the poses the last timed step wrote (slot (K-1) % n of the in-flight buffer sets), before any later pass"""
+        if not args.dump_outputs:
+            return
+        out = sets[(args.steps - 1) % nset][3].download((B, 2, 6))
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "pose.npy" if rank == 0 else "pose_rank%d.npy" % rank), out.astype(np.float32))
+
+    if not args.full:
+        # a plain run: the timed K steps with nothing bracketed inside them, the outputs, the headline line
+        elapsed_max = timed(lambda k: [eng.forward_device(B, *sets[i % nset]) for i in range(k)], args.steps)
+        dump_outputs()
+        finish(headline(elapsed_max))
+        return
+
     # timed region: K steps; only the dominant kernel (main cnv6 launch) is bracketed by HIP events
     # on the launch stream, so the event records do not perturb the other launches
     # (every 4th step: an event pair puts two ~6 us bubbles around the launch it brackets - 1 % of the step if every launch is timed)
@@ -207,6 +265,7 @@ def main():
     eng.set_option("profile_stride", stride)
     eng.profile_reset()
     elapsed_max = timed(lambda k: [eng.forward_device(B, *sets[i % nset]) for i in range(k)], args.steps)
+    dump_outputs()
     dominant = eng.profile_entries()
     dom_dur, dom_period = eng.profile_samples("cnv6")
 
@@ -383,8 +442,8 @@ def main():
                   "collective_ms": round(coll_ms, 4), "wall_ms_incl_staging": round(wall_ms, 3),
                   "distinct_shards": n_distinct, "forced_at_world_1": bool(args.force_comm and world == 1)}
 
+    res = None
     if rank == 0:
-        value = world * B * args.steps / elapsed_max
         kern_ms = {k: round(v[1] / max(v[0], 1), 4) for k, v in kernels.items()}
         whole = flops_per_triplet * B * args.steps / elapsed_max / 1e12
         roof = roofline_block(args.precision, dominant, plan6)
@@ -396,8 +455,6 @@ def main():
                          tag + "_frac": other_block["roofline"]["frac"], tag + "_mfma_busy": other_block["roofline"]["mfma_busy"],
                          tag + "_whole_path_frac_of_mfma_peak": other_block["whole_path_frac_of_mfma_peak"],
                          tag + "_dtype": other, tag + "_max_abs_diff_vs_top_level": other_block["max_abs_diff_f16x3_vs_f32"]})
-        dtype = ("f32 (v_mfma_f32_32x32x2_f32: the reference's arithmetic, slim.conv2d in float32)" if args.precision == "f32"
-                 else "f16x3 (fp16 hi/lo split operands, 3 MFMA products, f32 accumulate)")
         # the HBM-bound front of the path: algorithmic bytes / kernel time from the per-kernel breakdown pass
         sq_ms, mp_ms = kern_ms.get("se_squeeze_partial", 0.0), kern_ms.get("mask_pack", 0.0)
         pro_bytes = (SQUEEZE_BYTES_128x416 + PACK_BYTES_128x416) * scale_px * B
@@ -413,18 +470,8 @@ def main():
                                            "GB/s": round(PACK_BYTES_128x416 * scale_px * B / (mp_ms * 1e-3) / 1e9, 1)}},
                    "note": "algorithmic bytes: flow planes 0,1 (squeeze); u8 strip + 2 flow + 2 seg planes in, packed "
                            "[2B,H,W,8] float32 (f16x3: 8 hi | 8 lo halves, the same 32 B per pixel) out (mask_pack); peak = 8 TB/s HBM3E spec"}
-        res = {
-            "metric": "pose-net triplets/sec (128x416x3-frame)" if (H, W) == (128, 416)
-                      else "pose-net triplets/sec (%dx%dx3-frame)" % (H, W),
-            "value": round(value, 2), "unit": "triplets/s", "n_gpus": world, "steps": args.steps,
-            "warmup": args.warmup + settle, "warmup_arg": args.warmup, "settle_steps": settle,
-            "ms_per_step": round(elapsed_max / args.steps * 1e3, 4),
-            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": dtype,
-            "data": "synthetic (splitmix64 seed 8964; random-init He-uniform weights; no KITTI/ckpt offline)",
-            "config": {"workload": workload_name(B, H, W, world),
-                       "version": FLAGSHIP_VERSION, "batch_per_gpu": B, "height": H, "width": W,
-                       "parallelism": "window-sharded replicas x%d" % world, "batches_in_flight": nset,
-                       **({"options": args.options} if args.options else {})},
+        res = headline(elapsed_max)
+        res.update({
             "roofline": roof,
             ("fast_mode" if other == "f16x3" else "reference_arithmetic"): other_block,
             "timing": timing,
@@ -435,7 +482,7 @@ def main():
             "range_recovery": eng.range_stats(),
             "pipelined": pipelined,
             "gather": gather,
-        }
+        })
         # parity on the bench's own batch (bounded: the first 2 windows) + CPU baseline beside it
         from oracle import c_oracle
         ns = min(2, B)
@@ -471,15 +518,7 @@ def main():
                                              % (passes, nb, H, W)}
         else:
             res["cpu_baseline"] = None
-        print(json.dumps(res), flush=True)
-
-    if comm is not None:
-        comm.barrier()
-        comm.close()
-    for st in sets:
-        for b in st:
-            b.free()
-    eng.close()
+    finish(res)
 
 
 if __name__ == "__main__":

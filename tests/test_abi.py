@@ -37,9 +37,14 @@ def test_variant_struct_layout():
 
 
 def test_no_gpu_fails_loudly(built):
-    """Without a GPU the product path raises; it never falls back to a CPU implementation."""
-    import torch
-    if torch.cuda.is_available():
+    """Without a GPU the product path raises; it never falls back to a CPU implementation.  torch looks for the GPU in a
+    child process: torch brings a HIP runtime of its own, which must not start beside the library's in this one (conftest.py)."""
+    import subprocess
+    import sys
+    probe = subprocess.run([sys.executable, "-c", "import torch; print(int(torch.cuda.is_available()))"],
+                           capture_output=True, text=True, timeout=300)
+    assert probe.returncode == 0, probe.stderr[-2000:]
+    if probe.stdout.split()[-1] == "1":
         pytest.skip("GPU present")
     from davo_amd import DAVO, FLAGSHIP_VERSION, DavoError
     d = DAVO(FLAGSHIP_VERSION)

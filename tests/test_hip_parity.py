@@ -1317,7 +1317,7 @@ def test_bench_multi_gpu_code_path_on_one_gpu(tmp_path):
     out = tmp_path / "bench.out"
     with open(out, "wb") as f:
         rc = spawn_ranks([os.path.join(root, "bench.py"), "--gpus", "1", "--force-comm", "--steps", "3", "--warmup", "1", "--settle", "2",
-                          "--batch", "4", "--no-cpu-baseline", "--no-f32", "--no-pipelined"], 1, stdout=f, timeout=600)
+                          "--batch", "4", "--full", "--no-cpu-baseline", "--no-f32", "--no-pipelined"], 1, stdout=f, timeout=600)
     assert rc == 0
     res = json.loads(open(out).read().strip().splitlines()[-1])
     g = res["gather"]
@@ -1326,6 +1326,32 @@ def test_bench_multi_gpu_code_path_on_one_gpu(tmp_path):
     assert res["timing"]["dominant_launch_ms"]["n"] == 3 and res["timing"]["step_ms_on_stream"]["n"] == 2
     assert res["max_abs_err_vs_oracle"] <= 1e-4 * res["max_abs_ref"]
     assert res["config"]["workload"].startswith("none of BASELINE.json's configs")
+
+
+def test_bench_plain_run_dumps_the_last_steps_poses(tmp_path):
+    """A plain bench run (no --full): exactly --steps timed steps, the headline line only, and --dump-outputs writes the
+    poses of the last timed step - the float32 path's bits, which the CPU oracle must agree with."""
+    import json
+    import subprocess
+    import sys
+    from oracle import c_oracle
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    B = 4
+    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "3", "--warmup", "1", "--settle", "2",
+                          "--batch", str(B), "--dump-outputs", str(tmp_path / "dump")],
+                         capture_output=True, text=True, timeout=600)
+    assert out.returncode == 0, out.stderr[-2000:]
+    res = json.loads(out.stdout.strip().splitlines()[-1])
+    assert res["steps"] == 3 and res["warmup"] == 3 and res["value"] > 0 and res["ms_per_step"] > 0
+    assert res["unit"] == "triplets/s" and res["higher_is_better"] is True and res["dtype"].startswith("f32")
+    assert res["full"] is False and "roofline" not in res and "cpu_baseline" not in res
+    assert abs(res["value"] - B * 1e3 / res["ms_per_step"]) <= 1e-3 * res["value"]
+    got = np.load(str(tmp_path / "dump" / "pose.npy"))
+    assert got.dtype == np.float32 and got.shape == (B, 2, 6)
+    cfg = parse_version(FLAGSHIP_VERSION)
+    img, flow, seg = synth.make_inputs(B, 128, 416)
+    want = c_oracle.forward(cfg, img[:2], flow[:2], seg[:2], synth.make_weights(cfg))
+    assert_pose_close(got[:2], want, "bench --dump-outputs")
 
 
 @pytest.mark.parametrize("B,H,W", [(32, 128, 416), (5, 128, 416), (3, 64, 96), (1, 128, 416)])

@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 
 from davo_amd import DAVO, Engine, synth, parse_version, FLAGSHIP_VERSION
+from davo_amd import _lib
 from davo_amd import sequence as S
 
 from helpers import assert_pose_close
@@ -190,10 +191,12 @@ def test_inference_from_an_iterator_runs_one_batch_ahead(c_oracle):
 
 # ---- davo_set_stream ---------------------------------------------------------------------------------------------------
 class _Hip:
-    """the three HIP calls a test needs to own a stream (tests only: the product binds HIP through libdavo_hip.so)"""
+    """the three HIP calls a test needs to own a stream (tests only: the product binds HIP through libdavo_hip.so).  They are
+    looked up through the library's own handle, which searches its dependencies: the stream must belong to the HIP runtime
+    the library runs on, and a process that has imported torch also holds torch's copy of the runtime under the same name."""
 
     def __init__(self):
-        self.L = ctypes.CDLL("libamdhip64.so")
+        self.L = ctypes.CDLL(_lib.LIB_PATH)
         self.L.hipStreamCreate.argtypes = [ctypes.POINTER(ctypes.c_void_p)]
         self.L.hipStreamDestroy.argtypes = [ctypes.c_void_p]
         self.L.hipStreamSynchronize.argtypes = [ctypes.c_void_p]

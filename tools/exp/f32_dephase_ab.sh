@@ -7,7 +7,7 @@ O=gpurun_out
 : > $O/r05dd_f32_dephase_ab.log
 for rnd in 1 2 3; do
 for v in "" _dp71 _dp36; do
-  DAVO_LIB_SUFFIX=$v python bench.py --steps 100 --warmup 5 --no-cpu-baseline --no-pipelined --no-f32 > $O/_dp.json 2>>$O/r05dd.err || exit 1
+  DAVO_LIB_SUFFIX=$v python bench.py --full --steps 100 --warmup 5 --no-cpu-baseline --no-pipelined --no-f32 > $O/_dp.json 2>>$O/r05dd.err || exit 1
   python - "$v" $rnd >> $O/r05dd_f32_dephase_ab.log <<'P'
 import json,sys
 d=json.load(open('gpurun_out/_dp.json'))

@@ -6,7 +6,7 @@ O=gpurun_out
 : > $O/$TAG.log
 for rnd in 1 2 3; do
 for v in "" "$@"; do
-  DAVO_LIB_SUFFIX=$v python bench.py --steps 100 --warmup 5 --no-pipelined --no-f32 --no-cpu-baseline > $O/_v.json 2>>$O/$TAG.err || exit 1
+  DAVO_LIB_SUFFIX=$v python bench.py --full --steps 100 --warmup 5 --no-pipelined --no-f32 --no-cpu-baseline > $O/_v.json 2>>$O/$TAG.err || exit 1
   python - "$v" $rnd >> $O/$TAG.log <<'P'
 import json,sys
 d=json.load(open('gpurun_out/_v.json'))
