@@ -40,10 +40,12 @@ int alloc_slot(davo_ctx* c, Slot* s) {
     for (int i = 0; i < 7; ++i)
         HIP_TRY(c, hipMalloc(reinterpret_cast<void**>(&s->d_act[i]), NB * c->act_floats_per_img[i] * sizeof(float)));
     HIP_TRY(c, hipMalloc(reinterpret_cast<void**>(&s->d_packed), NB * (size_t)c->H * c->W * 10 * sizeof(float)));
-    HIP_TRY(c, hipMalloc(reinterpret_cast<void**>(&s->d_partial), (size_t)c->max_batch * 2 * SQ_CHUNKS * 2 * sizeof(float)));
+    // squeeze partials: se_flow [B][2 sources][SQ_CHUNKS][2] floats, the class-table sources [B][3 frames][SQ_CHUNKS][SQ_REC] words
+    const size_t partial_bytes = (size_t)c->max_batch * SQ_CHUNKS * (att_class_table(c->v.att_source) ? 3 * SQ_REC : 2 * 2) * sizeof(float);
+    HIP_TRY(c, hipMalloc(reinterpret_cast<void**>(&s->d_partial), partial_bytes));
     HIP_TRY(c, hipMalloc(reinterpret_cast<void**>(&s->d_tab), (size_t)c->max_batch * 3 * NCLS * sizeof(float)));
     HIP_TRY(c, hipMalloc(reinterpret_cast<void**>(&s->d_pose_partial), NB * 2 * PH_SPLIT * 3 * sizeof(float)));
-    { int rc = zero_now(c, s->d_partial, (size_t)c->max_batch * 2 * SQ_CHUNKS * 2 * sizeof(float)); if (rc) return rc; }
+    { int rc = zero_now(c, s->d_partial, partial_bytes); if (rc) return rc; }
     HIP_TRY(c, hipMalloc(reinterpret_cast<void**>(&s->d_counters), ((size_t)c->max_batch + 1 + SK_TILE_COUNTERS) * sizeof(unsigned)));
     { int rc = zero_now(c, s->d_counters, ((size_t)c->max_batch + 1 + SK_TILE_COUNTERS) * sizeof(unsigned)); if (rc) return rc; }
     return DAVO_OK;
@@ -66,7 +68,7 @@ int davo_create(davo_ctx** out, int device, int H, int W, int max_batch, const d
     if (max_batch < 1) return fail(c, DAVO_ERR_INVALID, "max_batch must be >= 1");
     if (v->cin_per_frame != 5 && v->cin_per_frame != 3) return fail(c, DAVO_ERR_INVALID, "cin_per_frame must be 3 or 5");
     if (ilog2_exact(v->cnv6_out) < 5 || v->cnv6_out > 256) return fail(c, DAVO_ERR_INVALID, "cnv6_out must be 32, 64, 128 or 256");
-    if (v->se_act < 0 || v->se_act > 2 || v->abs_mode < 0 || v->abs_mode > 3 || v->att_source < 0 || v->att_source > 3)
+    if (v->se_act < 0 || v->se_act > 2 || v->abs_mode < 0 || v->abs_mode > 3 || v->att_source < 0 || v->att_source > 10)
         return fail(c, DAVO_ERR_INVALID, "variant field out of range");
     int ndev = 0;
     HIP_TRY(c, hipGetDeviceCount(&ndev));
@@ -135,7 +137,7 @@ int davo_load_weight(davo_ctx* c, const char* tf_name, const float* data, const 
     // the convolution tensors are re-laid-out at the first forward (weights.hip) and their raw device copy is only the test hook's
     // (impl 1: uploaded on demand, forward.hip) - 20 hipMalloc + copies less in front of a rank's first batch
     const std::string nm = tf_name;
-    const bool dense = nm.find("se_flow") != std::string::npos || nm.find("seg_channel_weight") != std::string::npos;
+    const bool dense = is_dense_weight(nm);
     if (t.dev) { (void)hipFree(t.dev); t.dev = nullptr; }
     if (dense) { int rc = upload(c, t.data, &t.dev); if (rc) return rc; }
     c->packed_ready = false;
@@ -591,12 +593,12 @@ int davo_submit(davo_ctx* c, int B, const uint8_t* img, const float* flow, const
     hipStream_t s = c->stream;
     const size_t nb_img = img_bytes(c), nb_flow = flow_bytes(c), nb_seg = seg_bytes(c);
     // H2D on the slot's stream, in order behind the forward that last read this staging set.  Only what the path reads crosses PCIe:
-    // flow planes 0,1 (davo.py:978-982) and, unless the variant reads the target frame's label map too (-segmask_all-static),
-    // the two source frames' maps (davo.py:998-1004, 1408-1412).
+    // flow planes 0,1 (davo.py:978-982) and, unless the variant reads the target frame's label map too (-segmask_all-static, the
+    // with-target class-table sources), the two source frames' maps (davo.py:998-1004, 1408-1412).
     HIP_TRY(c, hipMemcpyAsync(c->st_img[slot], img, nb_img * B, hipMemcpyHostToDevice, s));
     if (B == 1) HIP_TRY(c, hipMemcpyAsync(c->st_flow[slot], flow, nb_flow / 2, hipMemcpyHostToDevice, s));
     else HIP_TRY(c, hipMemcpy2DAsync(c->st_flow[slot], nb_flow, flow, nb_flow, nb_flow / 2, B, hipMemcpyHostToDevice, s));
-    if (c->v.att_source == 3 || B < 4) HIP_TRY(c, hipMemcpyAsync(c->st_seg[slot], seg, nb_seg * B, hipMemcpyHostToDevice, s));
+    if (att_tgt_attended(c->v.att_source) || B < 4) HIP_TRY(c, hipMemcpyAsync(c->st_seg[slot], seg, nb_seg * B, hipMemcpyHostToDevice, s));
     else
         for (int plane = 0; plane < 3; plane += 2)
             HIP_TRY(c, hipMemcpy2DAsync((uint8_t*)c->st_seg[slot] + plane * (nb_seg / 3), nb_seg, (const uint8_t*)seg + plane * (nb_seg / 3), nb_seg,

@@ -161,7 +161,7 @@ __global__ __launch_bounds__(cp1::THREADS, 3) void conv_patch_cnv1_h3(ConvPatchP
                     const size_t pix = (size_t)iy * p.W + ix;
                     float as = 1.f, at = 1.f;
                     if (v.att_source != 0) as = att_lookup(tab_s, p.seg[((size_t)b * 3 + (s ? 2 : 0)) * HW + pix]);
-                    if (v.att_source == 3) at = att_lookup(tab_t, p.seg[((size_t)b * 3 + 1) * HW + pix]);
+                    if (att_tgt_attended(v.att_source)) at = att_lookup(tab_t, p.seg[((size_t)b * 3 + 1) * HW + pix]);
                     r[0] = u8_to_unit(pt[0]); r[1] = u8_to_unit(pt[1]); r[2] = u8_to_unit(pt[2]);
                     r[3] = u8_to_unit(ps[0]); r[4] = u8_to_unit(ps[1]); r[5] = u8_to_unit(ps[2]);
                     if (v.mask_rgb) {

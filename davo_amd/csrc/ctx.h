@@ -278,6 +278,11 @@ int sync_all_slots(davo_ctx* c);
 // ---- weights.hip ----------------------------------------------------------------------------
 void init_layer(ConvLayer& L, const char* label, int KS, int stride, int rate, int cin, int cout, int groups);
 std::vector<std::string> needed_names(const Variant& v);
+// TF name of an SE dense tensor of the variant's scope (k: 0 bottleneck_fc/kernel, 1 its bias, 2 recover_fc/kernel, 3 its bias);
+// the se_flow scope's for the variants without SE layers (the kernels do not read them there)
+const char* se_weight_name(int att_source, int k);
+// the SE layers' scope is a dense tensor the kernels read in the reference's [in,out] layout (not re-laid-out like a convolution)
+bool is_dense_weight(const std::string& name);
 bool expected_shape(const davo_ctx* c, const std::string& name, std::vector<int64_t>* sh);
 int upload(davo_ctx* c, const std::vector<float>& host, float** dev);
 int build_packed_weights(davo_ctx* c);

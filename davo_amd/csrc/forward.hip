@@ -1,6 +1,6 @@
 // forward.hip — the forward plan of the pose path on one context:
 //
-//   se_squeeze_partial -> se_excite -> mask_pack -> cnv1..cnv5 -> cnv6 (rotation|translation
+//   se_squeeze_partial (se_class_squeeze for the class-table sources) -> se_excite -> mask_pack -> cnv1..cnv5 -> cnv6 (rotation|translation
 //   fused into one N = 2*cnv6_out GEMM, both read cnv5: nets/posenn.py:222-238)
 //   -> cnv7 (grouped x2) -> pose head.
 //
@@ -638,14 +638,26 @@ int forward_device(davo_ctx* c, int B, const void* d_img, const void* d_flow, co
     // folded into its neighbour at less than that, small batches do it (measured per batch: profiles/):
     //   the excitation MLP in the squeeze launch's last workgroup (costs two memory-side round trips per workgroup: +2 us at
     //   B = 1, +18 us at B = 32), mask + pack inside cnv1's patch fill (level at B = 32).
-    const bool fold_excite = v.att_source == 1 && (c->opt_fold_tails >= 1 || (c->opt_fold_tails < 0 && B <= FOLD_EXCITE_MAX_BATCH));
+    const bool class_table = att_class_table(v.att_source);
+    const bool fold_excite = (v.att_source == 1 || class_table) &&
+                             (c->opt_fold_tails >= 1 || (c->opt_fold_tails < 0 && B <= FOLD_EXCITE_MAX_BATCH));
     const bool fold_pose = c->opt_fold_tails == 1;
-    if (fold_excite) {
+    const float* se_w1 = wdev(se_weight_name(v.att_source, 0));
+    const float* se_b1 = wdev(se_weight_name(v.att_source, 1));
+    const float* se_w2 = wdev(se_weight_name(v.att_source, 2));
+    const float* se_b2 = wdev(se_weight_name(v.att_source, 3));
+    if (class_table) {
+        // segmentation / rgb / seg+flow sources: per-frame histogram, byte or flow sums, then (or, folded, in the same launch) the
+        // excitation
+        ProfScope ps(c, "se_class_squeeze");
+        HIP_TRY(c, launch_se_class_squeeze(fold_excite, static_cast<const uint8_t*>(d_img), static_cast<const float*>(d_flow),
+                                           static_cast<const float*>(d_seg), B, H, W, v, reinterpret_cast<unsigned*>(c->d_partial),
+                                           c->d_counters + 1, se_w1, se_b1, se_w2, se_b2, c->d_tab, range_reset, s));
+    } else if (fold_excite) {
         // squeeze + excitation in one launch: the workgroup that delivers a triplet's last partial sum evaluates its tables
         ProfScope ps(c, "se_squeeze_partial");
         HIP_TRY(c, launch_se_squeeze_excite(static_cast<const float*>(d_flow), B, HW, v, c->d_partial, c->d_counters + 1,
-                                            wdev("pose_exp_net/se_flow/bottleneck_fc/kernel"), wdev("pose_exp_net/se_flow/bottleneck_fc/bias"),
-                                            wdev("pose_exp_net/se_flow/recover_fc/kernel"), wdev("pose_exp_net/se_flow/recover_fc/bias"),
+                                            se_w1, se_b1, se_w2, se_b2,
                                             wdev("pose_exp_net/pose_exp_net/seg_channel_weight/weight"), c->d_tab, range_reset, s));
     } else if (v.att_source == 1) {
         ProfScope ps(c, "se_squeeze_partial");
@@ -653,9 +665,7 @@ int forward_device(davo_ctx* c, int B, const void* d_img, const void* d_flow, co
     }
     if (!fold_excite) {
         ProfScope ps(c, "se_excite");
-        HIP_TRY(c, launch_se_excite(c->d_partial, B, HW, v,
-                                    wdev("pose_exp_net/se_flow/bottleneck_fc/kernel"), wdev("pose_exp_net/se_flow/bottleneck_fc/bias"),
-                                    wdev("pose_exp_net/se_flow/recover_fc/kernel"), wdev("pose_exp_net/se_flow/recover_fc/bias"),
+        HIP_TRY(c, launch_se_excite(c->d_partial, B, HW, v, se_w1, se_b1, se_w2, se_b2,
                                     wdev("pose_exp_net/pose_exp_net/seg_channel_weight/weight"), c->d_tab, range_reset, s));
     }
     // f16x3, fuse_pack: cnv1 builds its input patch straight from the raw inputs (mask + pack fused in,

@@ -1,10 +1,12 @@
 // prologue.h — the HBM-bound front of the pose path: SE squeeze, the 2->8->19 excitation
-// MLP, and the mask + pack pass that builds the PoseNN input.
+// MLP (se_flow), the class-table squeeze / excitation of the segmentation, rgb and seg+flow
+// sources, and the mask + pack pass that builds the PoseNN input.
 //
 // Reference (all under /root/reference): davo.py:1519-1522 (u8 -> f32 * (1/255) * 2 - 1),
 // data_loader.py:537-557 (strip = src0 | tgt | src1), davo.py:978-982 / 998-1004 (flow planes
 // 0,1; seg file planes src0,tgt,src1), davo.py:1088-1102 (SE input transform),
-// nets/attention_module.py:54-103 (se, mode 'gp'), davo.py:1115,1178 (one_hot . weights ==
+// nets/attention_module.py:9-52 (se_block), :54-103 (se, mode 'gp'), davo.py:1274-1374
+// (class-table sources), davo.py:1115,1178 (one_hot . weights ==
 // 19-entry LUT gather, out-of-range id -> 0), nets/posenn.py:380-394 (static weights),
 // davo.py:1404-1442 (masking, concat).
 #pragma once
@@ -58,6 +60,83 @@ __global__ __launch_bounds__(256) void se_squeeze_partial(const float* __restric
     }
 }
 
+__device__ __forceinline__ unsigned agent_load_u32(const unsigned* p) {
+    return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// The SE flow transform of one component (davo.py:1088-1102): c = 0 horizontal, 1 vertical.
+__device__ __forceinline__ float se_flow_transform(float f, int c, const Variant& v) {
+    if (v.norm_flow) f = (f - 0.32140523f) / 15.384229f;
+    return (v.abs_mode & (1 << c)) ? fabsf(f) : f;
+}
+
+// Class-table excitation (att_source 4..10), one wave: tab[b][frame][19].  The descriptor's element c is lane c's: the sum of word c
+// of the frame's SQ_CHUNKS squeeze records in chunk order (integers for the histogram and the rgb sums, so their order does not
+// matter at all; the flow sums in a fixed order), turned into the mean once.  Then one lane per bottleneck unit, its inputs
+// broadcast by shuffles, then one lane per class.  A `_wo_tgt' source's target table is ones (davo.py:1283,1310,1349,1366).
+template <bool AGENT>
+__device__ __forceinline__ void se_class_excite_wave(const unsigned* __restrict__ partial, int HW, const Variant& v, int b, int frame,
+                                                     int lane, const float* __restrict__ w1, const float* __restrict__ b1,
+                                                     const float* __restrict__ w2, const float* __restrict__ b2, float* __restrict__ tab) {
+    float* t = tab + ((size_t)b * 3 + frame) * NCLS;
+    const int a = v.att_source;
+    if (frame == 0 && !att_tgt_attended(a)) {
+        if (lane < NCLS) t[lane] = 1.0f;
+        return;
+    }
+    const int nin = att_se_in(a), nh = att_se_hidden(a);
+    // the lane's weights first, in fixed-length loops: all of them in flight at once, ahead of the descriptor's loads (a loop over
+    // nin dependent round trips took 15 us at B = 32)
+    constexpr int MAX_IN = NCLS + 2;
+    const int j = min(lane, nh - 1), k = min(lane, NCLS - 1);
+    float w1c[MAX_IN], w2c[NCLS];
+#pragma unroll
+    for (int c = 0; c < MAX_IN; ++c) w1c[c] = w1[min(c, nin - 1) * nh + j];
+#pragma unroll
+    for (int c = 0; c < NCLS; ++c) w2c[c] = w2[min(c, nh - 1) * NCLS + k];
+    const float b1j = b1[j], b2k = b2[k];
+    const unsigned* rec = partial + ((size_t)b * 3 + frame) * SQ_CHUNKS * SQ_REC;
+    float d = 0.f;
+    if (lane < nin) {
+        if (att_desc_flow(a) && lane >= NCLS) {
+            const int c = lane - NCLS;
+            if (frame == 0) {
+                d = se_flow_transform(0.f, c, v);               // the target's flow is zeros_like (davo.py:978)
+            } else {
+                float sum = 0.f;
+                for (int ch = 0; ch < SQ_CHUNKS; ++ch) {
+                    const unsigned* q = rec + ch * SQ_REC + lane;
+                    sum += __uint_as_float(AGENT ? agent_load_u32(q) : *q);
+                }
+                d = sum * (1.0f / (float)HW);
+            }
+        } else {
+            unsigned long long sum = 0;
+            for (int ch = 0; ch < SQ_CHUNKS; ++ch) {
+                const unsigned* q = rec + ch * SQ_REC + lane;
+                sum += AGENT ? agent_load_u32(q) : *q;
+            }
+            // histogram: mean of one_hot = count / HW; rgb: mean of u8 * (1/255) * 2 - 1 over the frame (davo.py:1521-1522)
+            d = att_desc_rgb(a) ? (float)((double)sum / ((double)HW * 255.0) * 2.0 - 1.0) : (float)((double)sum / (double)HW);
+        }
+    }
+    float z = b1j;
+#pragma unroll
+    for (int c = 0; c < MAX_IN; ++c) {                                                  // dense [nin, nh]
+        const float dc = __shfl(d, c, 64);
+        if (c < nin) z += dc * w1c[c];
+    }
+    const float e = v.se_act == 1 ? tanhf(z) : v.se_act == 2 ? (z > 0.f ? z : 0.2f * z) : fmaxf(z, 0.f);
+    float y = b2k;
+#pragma unroll
+    for (int c = 0; c < NCLS; ++c) {                                                    // dense [nh, 19]
+        const float ec = __shfl(e, c, 64);
+        if (c < nh) y += ec * w2c[c];
+    }
+    // the static table's expression: zero kernels and recover_fc/bias = the static weights give its table to the bit
+    if (lane < NCLS) t[lane] = 1.0f / (1.0f + expf(-y));
+}
+
 // One wave's share of the excitation: tab[b][frame][19] for frame = (tgt, src0, src1).
 // Lanes 0..31 fetch the squeeze partials (fixed butterfly: bitwise reproducible), every lane evaluates the 8 bottleneck
 // units, lane c < 19 the class c of the recovery layer — the three dependent steps of the MLP cost three memory round
@@ -68,6 +147,10 @@ __device__ __forceinline__ void se_excite_wave(const float* __restrict__ partial
                                                const float* __restrict__ w1, const float* __restrict__ b1,
                                                const float* __restrict__ w2, const float* __restrict__ b2,
                                                const float* __restrict__ wstatic, float* __restrict__ tab) {
+    if (att_class_table(v.att_source)) {
+        se_class_excite_wave<AGENT>(reinterpret_cast<const unsigned*>(partial), HW, v, b, frame, lane, w1, b1, w2, b2, tab);
+        return;
+    }
     float* t = tab + ((size_t)b * 3 + frame) * NCLS;
     if (v.att_source == 1 && frame >= 1) {
         const float* pp = partial + ((size_t)b * 2 + (frame - 1)) * SQ_CHUNKS * 2;
@@ -157,6 +240,118 @@ __global__ __launch_bounds__(256) void se_squeeze_excite(const float* __restrict
     if (threadIdx.x == 0) __hip_atomic_store(counters + b, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
+// Class-table SE squeeze (att_source 4..10): one workgroup per (chunk, frame, triplet), grid (SQ_CHUNKS, att_se_frames, B); frame =
+// blockIdx.y + 3 - att_se_frames (the `_wo_tgt' sources skip the target).  It writes partial[b][frame][chunk][SQ_REC] words:
+//   histogram sources: [0, 19) label counts of the chunk (the att_lookup rule: finite values in (-1, 19), truncated; anything else
+//                      counts in no bin but in the HW denominator, davo.py:1115), SegFlow: [19, 21) float sums of the SE-transformed
+//                      flow (src frames; the target's flow is zeros and has no sums);
+//   rgb sources:       [0, 3) sums of the frame's u8 channel bytes.
+// A thread takes 4 horizontally adjacent pixels per step (one float4 of labels, 12 strip bytes, two float4 of flow).  Label counts:
+// per class one 64-bit ballot per pixel slot and a scalar popcount - wave-uniform sums with no LDS atomics on a hot bin (the labels
+// come in 8x8 blocks of one class).  The loop's trip count is uniform, so every lane sees every ballot.  The counts and byte sums
+// are exact integers and the flow sums use a fixed tree: bitwise reproducible.  FOLD: the workgroup that delivers the triplet's
+// last record evaluates its three tables (se_squeeze_excite's protocol, pose_tail.h).
+template <bool FOLD>
+__global__ __launch_bounds__(256) void se_class_squeeze(const uint8_t* __restrict__ img, const float* __restrict__ flow,
+                                                        const float* __restrict__ seg, int H, int W, Variant v,
+                                                        unsigned* __restrict__ partial, unsigned* __restrict__ counters,
+                                                        const float* __restrict__ w1, const float* __restrict__ b1,
+                                                        const float* __restrict__ w2, const float* __restrict__ b2,
+                                                        float* __restrict__ tab, unsigned* __restrict__ range_reset) {
+    const int a = v.att_source, nf = att_se_frames(a);
+    const int chunk = blockIdx.x, frame = blockIdx.y + 3 - nf, b = blockIdx.z;
+    if (FOLD && range_reset && chunk == 0 && blockIdx.y == 0 && b == 0 && threadIdx.x == 0) range_reset[RANGE_SNAP] = 0u;   // as se_excite
+    const int HW = H * W;
+    const int nunits = HW >> 2;                                // 4-pixel units; W is a multiple of 4, so a unit never wraps a row
+    const int per = (nunits + SQ_CHUNKS - 1) / SQ_CHUNKS;
+    const int beg = chunk * per, end = min(beg + per, nunits);
+    const bool hist = att_desc_hist(a), rgb = att_desc_rgb(a), fl = att_desc_flow(a) && frame >= 1;
+    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+    // strip slot / seg file plane of the frame: (tgt, src0, src1) -> strip src0|tgt|src1 (data_loader.py:537-557), seg file
+    // order src0, tgt, src1 (davo.py:998-1004)
+    const int slot = frame == 0 ? 1 : frame == 1 ? 0 : 2;
+    const float4* lab = reinterpret_cast<const float4*>(seg + ((size_t)b * 3 + slot) * HW);
+    const float4* fv = reinterpret_cast<const float4*>(flow + ((size_t)b * 4 + (frame >= 1 ? frame - 1 : 0)) * HW * 2);
+    unsigned cnt[NCLS];
+#pragma unroll
+    for (int c = 0; c < NCLS; ++c) cnt[c] = 0u;
+    unsigned sr = 0u, sg = 0u, sb = 0u;
+    float sx = 0.f, sy = 0.f;
+    for (int base = beg; base < end; base += 256) {            // uniform trip count
+        const int i = base + threadIdx.x;
+        const bool ok = i < end;
+        if (hist) {
+            int id[4] = {-1, -1, -1, -1};
+            if (ok) {
+                const float4 q = lab[i];
+                const float l[4] = {q.x, q.y, q.z, q.w};
+#pragma unroll
+                for (int k = 0; k < 4; ++k) id[k] = (l[k] > -1.0f && l[k] < (float)NCLS) ? (int)l[k] : -1;
+            }
+#pragma unroll
+            for (int c = 0; c < NCLS; ++c)
+                cnt[c] += (unsigned)(__popcll(__ballot(id[0] == c)) + __popcll(__ballot(id[1] == c)) +
+                                     __popcll(__ballot(id[2] == c)) + __popcll(__ballot(id[3] == c)));
+        }
+        if (rgb && ok) {
+            const int p = i << 2, y = p / W, x = p - y * W;
+            const uint32_t* q = reinterpret_cast<const uint32_t*>(img + ((size_t)b * H + y) * (size_t)(9 * W) + (size_t)(slot * W + x) * 3);
+            const uint32_t q0 = q[0], q1 = q[1], q2 = q[2];         // r0 g0 b0 r1 | g1 b1 r2 g2 | b2 r3 g3 b3
+            sr += (q0 & 255u) + (q0 >> 24) + ((q1 >> 16) & 255u) + ((q2 >> 8) & 255u);
+            sg += ((q0 >> 8) & 255u) + (q1 & 255u) + (q1 >> 24) + ((q2 >> 16) & 255u);
+            sb += ((q0 >> 16) & 255u) + ((q1 >> 8) & 255u) + (q2 & 255u) + (q2 >> 24);
+        }
+        if (fl && ok) {
+            const float4 f0 = fv[2 * i], f1 = fv[2 * i + 1];
+            sx += (se_flow_transform(f0.x, 0, v) + se_flow_transform(f0.z, 0, v)) + (se_flow_transform(f1.x, 0, v) + se_flow_transform(f1.z, 0, v));
+            sy += (se_flow_transform(f0.y, 1, v) + se_flow_transform(f0.w, 1, v)) + (se_flow_transform(f1.y, 1, v) + se_flow_transform(f1.w, 1, v));
+        }
+    }
+    __shared__ unsigned red_u[4][NCLS];
+    __shared__ float red_f[2][4];
+    __shared__ unsigned ticket;
+    if (hist && lane == 0) {
+#pragma unroll
+        for (int c = 0; c < NCLS; ++c) red_u[wid][c] = cnt[c];     // wave-uniform
+    }
+    if (rgb) {
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            sr += __shfl_xor(sr, o, 64); sg += __shfl_xor(sg, o, 64); sb += __shfl_xor(sb, o, 64);
+        }
+        if (lane == 0) { red_u[wid][0] = sr; red_u[wid][1] = sg; red_u[wid][2] = sb; }
+    }
+    if (fl) {
+        sx = wave_sum(sx);
+        sy = wave_sum(sy);
+        if (lane == 0) { red_f[0][wid] = sx; red_f[1][wid] = sy; }
+    }
+    __syncthreads();
+    if (wid == 0) {
+        unsigned* o = partial + (((size_t)b * 3 + frame) * SQ_CHUNKS + chunk) * SQ_REC;
+        const int nu = hist ? NCLS : rgb ? 3 : 0;
+        unsigned w = 0u;
+        bool store = false;
+        if (lane < nu) {
+            w = (red_u[0][lane] + red_u[1][lane]) + (red_u[2][lane] + red_u[3][lane]);
+            store = true;
+        } else if (fl && (lane == NCLS || lane == NCLS + 1)) {
+            const int c = lane - NCLS;
+            w = __float_as_uint((red_f[c][0] + red_f[c][1]) + (red_f[c][2] + red_f[c][3]));
+            store = true;
+        }
+        if (store) {
+            if (FOLD) __hip_atomic_store(o + lane, w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            else o[lane] = w;
+        }
+        if (FOLD) agent_stores_done();
+    }
+    if (!FOLD) return;
+    if (!last_workgroup(counters + b, (unsigned)(nf * SQ_CHUNKS), &ticket)) return;
+    if (wid < 3) se_class_excite_wave<true>(partial, HW, v, b, wid, lane, w1, b1, w2, b2, tab);
+    if (threadIdx.x == 0) __hip_atomic_store(counters + b, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
 __device__ __forceinline__ float att_lookup(const float* tab19, float seg) {
     // tf.cast(float -> int32) truncates toward zero; one_hot of an out-of-range id is a zero row.  NaN / inf /
     // beyond-int32 labels are platform-defined in the cast (x86: INT_MIN, GPUs: 0 or saturation) and pinned to
@@ -213,7 +408,7 @@ __global__ __launch_bounds__(256) void mask_pack(const uint8_t* __restrict__ img
         as[2] = att_lookup(tab_s, sg.z); as[3] = att_lookup(tab_s, sg.w);
     }
     float at[4] = {1.f, 1.f, 1.f, 1.f};
-    if (v.att_source == 3) {                                   // static_all: tgt frame is masked too
+    if (att_tgt_attended(v.att_source)) {                     // static_all / a with-target class table: tgt frame is masked too
         const float4 tg = *reinterpret_cast<const float4*>(seg + ((size_t)b * 3 + 1) * H * W + pix);
         const float* tab_t = tab + (size_t)b * 3 * NCLS;
         at[0] = att_lookup(tab_t, tg.x); at[1] = att_lookup(tab_t, tg.y);

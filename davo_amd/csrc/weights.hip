@@ -1,5 +1,5 @@
 // weights.hip — weight tensors of the pose path: the TF variable names and shapes a variant needs
-// (SURVEY.md table W), and their one-time re-layout into the kernels' operand formats:
+// (the SE scopes se_flow / se_seg / se_rgb / se_segflow), and their one-time re-layout into the kernels' operand formats:
 //   f32 path    HWIO [KS,KS,Cin,Cout] -> Wp[Cout_pad][K_pad] floats, k = tap * Cin_packed + c
 //   f16x3 path  HWIO -> [Cout_pad][chunk][32 hi | 32 lo] halves, channel-block major / tap minor,
 //               pre-multiplied by a power of two so the fp16 residuals of small weights stay normal
@@ -65,6 +65,26 @@ void pack_conv_weights(const float* w_tf, int KS, int cin_tf, int cout, const in
 }
 
 // ---- weights ----------------------------------------------------------------------------
+const char* se_weight_name(int att_source, int k) {
+    static const char* const names[4][4] = {
+        {"pose_exp_net/se_flow/bottleneck_fc/kernel", "pose_exp_net/se_flow/bottleneck_fc/bias",
+         "pose_exp_net/se_flow/recover_fc/kernel", "pose_exp_net/se_flow/recover_fc/bias"},
+        {"pose_exp_net/se_seg/bottleneck_fc/kernel", "pose_exp_net/se_seg/bottleneck_fc/bias",              // davo.py:1304-1310
+         "pose_exp_net/se_seg/recover_fc/kernel", "pose_exp_net/se_seg/recover_fc/bias"},
+        {"pose_exp_net/se_rgb/bottleneck_fc/kernel", "pose_exp_net/se_rgb/bottleneck_fc/bias",              // :1274-1292
+         "pose_exp_net/se_rgb/recover_fc/kernel", "pose_exp_net/se_rgb/recover_fc/bias"},
+        {"pose_exp_net/se_segflow/bottleneck_fc/kernel", "pose_exp_net/se_segflow/bottleneck_fc/bias",      // :1341-1374
+         "pose_exp_net/se_segflow/recover_fc/kernel", "pose_exp_net/se_segflow/recover_fc/bias"}};
+    const int scope = att_source == 4 ? 1 : att_desc_rgb(att_source) ? 2 : att_source >= 7 ? 3 : 0;
+    return names[scope][k & 3];
+}
+
+bool is_dense_weight(const std::string& nm) {
+    for (const char* s : {"/se_flow/", "/se_seg/", "/se_rgb/", "/se_segflow/", "seg_channel_weight"})
+        if (nm.find(s) != std::string::npos) return true;
+    return false;
+}
+
 std::vector<std::string> needed_names(const Variant& v) {
     std::vector<std::string> n;
     const char* trunk[] = {"cnv1", "cnv2", "cnv3", "cnv4", "cnv5"};
@@ -79,11 +99,8 @@ std::vector<std::string> needed_names(const Variant& v) {
             n.push_back(std::string("pose_exp_net/pose/") + h + "/" + l + "/weights");
             n.push_back(std::string("pose_exp_net/pose/") + h + "/" + l + "/biases");
         }
-    if (v.att_source == 1) {
-        n.push_back("pose_exp_net/se_flow/bottleneck_fc/kernel");
-        n.push_back("pose_exp_net/se_flow/bottleneck_fc/bias");
-        n.push_back("pose_exp_net/se_flow/recover_fc/kernel");
-        n.push_back("pose_exp_net/se_flow/recover_fc/bias");
+    if (v.att_source == 1 || att_class_table(v.att_source)) {
+        for (int k = 0; k < 4; ++k) n.push_back(se_weight_name(v.att_source, k));
     } else if (v.att_source == 2 || v.att_source == 3) {
         n.push_back("pose_exp_net/pose_exp_net/seg_channel_weight/weight");
     }
@@ -118,6 +135,15 @@ bool expected_shape(const davo_ctx* c, const std::string& name, std::vector<int6
     else if (is("pose_exp_net/se_flow/recover_fc/kernel")) *sh = {8, NCLS};
     else if (is("pose_exp_net/se_flow/recover_fc/bias")) *sh = {NCLS};
     else if (is("pose_exp_net/pose_exp_net/seg_channel_weight/weight")) *sh = {NCLS};
+    else if (att_class_table(c->v.att_source) && name.compare(0, 16, "pose_exp_net/se_") == 0) {
+        // the class-table sources' scope (se_seg / se_rgb / se_segflow): [in, hidden] -> [hidden, 19]
+        const int a = c->v.att_source, nin = att_se_in(a), nh = att_se_hidden(a);
+        if (name == se_weight_name(a, 0)) *sh = {nin, nh};
+        else if (name == se_weight_name(a, 1)) *sh = {nh};
+        else if (name == se_weight_name(a, 2)) *sh = {nh, NCLS};
+        else if (name == se_weight_name(a, 3)) *sh = {NCLS};
+        else return false;
+    }
     else return false;
     return true;
 }

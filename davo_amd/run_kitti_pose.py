@@ -44,6 +44,12 @@ def _process_start_time():
         return None
 
 
+def loader_seg_planes(cfg):
+    """Label planes the window loader decodes: the source frames' only (its default, None), unless the variant masks the
+    target frame by its own table (-segmask_all-static, the with-target class-table sources), which reads all three."""
+    return (0, 1, 2) if cfg.tgt_attended else None
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch_size", type=int, default=1)          # test_kitti_pose.py:21
@@ -131,12 +137,12 @@ def main(argv=None):
                 pass
             procs = max(1, min(16, cores - 2))
         from .version import parse_version
-        static_all = parse_version(a.version).att_source == "static_all"   # only -segmask_all-static reads the target frame's label map
+        tgt_planes = loader_seg_planes(parse_version(a.version))
         load = S.kitti_window_loader(a.concat_img_dir, a.test_seq, n_frames, H, W,
                                      alloc=lambda shape, dtype: pinned_empty(shape, dtype, device_index),
                                      workers=a.loader_threads, decode_procs=a.decode_procs, procs=procs,
                                      pin=lambda arr: (gpu_ready.wait(), pin_array(arr, device_index)), unpin=unpin_array,
-                                     seg_planes=(0, 1, 2) if static_all else None, hold=0 if a.sync_driver else 1)
+                                     seg_planes=tgt_planes, hold=0 if a.sync_driver else 1)
         # the loader's buffers are created and its workers start filling them on a thread of its own, before anything else: the
         # workers need no GPU.  Page-locking the buffers (1.4 GB at batch 64: 0.3 s) follows on the loader's own thread, entry by
         # entry, once the context below exists: HIP serialises hipHostRegister with the context's own allocations, and pinning

@@ -91,7 +91,8 @@ def make_weights(version_or_cfg, seed=SEED):
     conv ~ U(+-sqrt(6/fan_in)) (He-uniform keeps activations O(1) through eight ReLU
     layers, so the 6-DoF outputs are large enough for the 1e-4 absolute bar to bite),
     conv biases U(+-0.05), SE kernels variance-scaling as nets/attention_module.py:60,
-    SE biases U(+-0.5), static seg weights stddev 0.05 as nets/posenn.py:387-388."""
+    SE biases U(+-0.5) (every SE scope: se_flow, se_seg, se_rgb, se_segflow), static seg weights stddev 0.05 as
+    nets/posenn.py:387-388."""
     cfg = parse_version(version_or_cfg) if isinstance(version_or_cfg, str) else version_or_cfg
     out = {}
     for name, shape in weight_shapes(cfg).items():

@@ -22,7 +22,11 @@ NUM_SEG_CLASSES = 19            # utils/seg_utils/labels.py:64-101 (train ids 0.
 # enums shared with include/davo_hip.h (davo_variant)
 SE_ACT = {"relu": 0, "tanh": 1, "lrelu": 2}
 ABS_MODE = {"none": 0, "h": 1, "v": 2, "all": 3}
-ATT_SOURCE = {"ones": 0, "se_flow": 1, "static_src": 2, "static_all": 3}
+ATT_SOURCE = {"ones": 0, "se_flow": 1, "static_src": 2, "static_all": 3,
+              # class-table SE sources (davo.py:1274-1292, 1304-1310, 1341-1374): sigmoid table of 19 classes per frame
+              "se_seg_wo_tgt": 4, "se_rgb_wo_tgt_to_seg": 5, "se_rgb_to_seg": 6,
+              "se_SegFlow_to_seg_wo_tgt": 7, "se_SegFlow_to_seg": 8,
+              "se_SegFlow_to_seg_8_wo_tgt": 9, "se_SegFlow_to_seg_8": 10}
 MASK_INFO = {"none": 0, "att": 1}
 
 
@@ -39,13 +43,23 @@ class VariantConfig:
     se_act: str              # relu | tanh | lrelu  (davo.py:1077-1085)
     norm_flow: bool          # (f-0.32140523)/15.384229 before abs (davo.py:1089-1091)
     abs_mode: str            # none | h | v | all  (davo.py:1094-1102)
-    att_source: str          # ones | se_flow | static_src | static_all
+    att_source: str          # a key of ATT_SOURCE
     mask_rgb: bool           # rgb_k *= att_k          (davo.py:1419-1423 / 1447-1450)
     mask_info: bool          # flow_k *= att_k         (davo.py:1430-1434)
 
     @property
     def cin_per_frame(self):
         return 5 if self.use_flow_info else 3
+
+    @property
+    def tgt_attended(self):
+        """The target frame's rgb is masked by its own class table, looked up through its own label map."""
+        return self.att_source in _TGT_ATTENDED
+
+    @property
+    def se_scope(self):
+        """TF variable scope of the SE dense layers under pose_exp_net/, None without them."""
+        return _SE_SCOPE.get(self.att_source)
 
     def as_c_ints(self):
         """Field order of ``davo_variant`` in include/davo_hip.h."""
@@ -58,7 +72,8 @@ class VariantConfig:
 # chain: if one of these matches, the reference never reaches the se_flow branch.
 _BEFORE_SE_FLOW = ("-se_flow_on_depthseg_sharedlayers", "-se_flow_on_depthseg_seplayers",
                    "-se_flow_on_depthseg", "-se_mixDepthFlow", "-se_mixDispFlow")
-# branches AFTER "-se_flow" and before "-no_segmask" (all need depth / rgb / SPP / se_block)
+# branches AFTER "-se_flow" and before "-no_segmask", in the reference's order; the ones in _CLASS_TABLE_SOURCES run here,
+# the rest need depth / SPP / gp2x2 pooling or an se_block whose map is not a class table
 _AFTER_SE_FLOW = ("-se_gp2x2_flow_nobottle", "-se_gp2x2_flow", "-se_spp21_flow", "-se_spp2_flow",
                   "-se_spp_flow", "-se_spp864_flow", "-se_depth_wo_tgt_to_seg", "-se_depth_to_seg",
                   "-se_depth_wo_tgt", "-se_depth", "-se_disp_wo_tgt_to_seg", "-se_disp_to_seg",
@@ -67,6 +82,25 @@ _AFTER_SE_FLOW = ("-se_gp2x2_flow_nobottle", "-se_gp2x2_flow", "-se_spp21_flow",
                   "-se_spp21_seg", "-se_spp_seg_21", "-se_spp2_seg", "-se_spp_seg", "-se_spp864_seg",
                   "-se_SegFlow_to_seg_8_wo_tgt", "-se_SegFlow_to_seg_8", "-se_SegFlow_to_seg_wo_tgt",
                   "-se_SegFlow_to_seg", "-se_mixSegFlow", "-se_spp21_mixSegFlow")
+# (substring, att_source) of the attention branches that run: a global-average-pooled descriptor, two dense layers and a
+# 19-class sigmoid table looked up per pixel through the label map.  None of them creates the se_flow scope, so the second
+# pair's target map is the target map (davo.py:1404-1414): ones for `_wo_tgt', the frame's own table otherwise.
+_CLASS_TABLE_SOURCES = {"-se_seg_wo_tgt": "se_seg_wo_tgt",                          # davo.py:1304-1310, se_block ratio 1
+                        "-se_rgb_wo_tgt_to_seg": "se_rgb_wo_tgt_to_seg",            # :1274-1283
+                        "-se_rgb_to_seg": "se_rgb_to_seg",                          # :1284-1292
+                        "-se_SegFlow_to_seg_8_wo_tgt": "se_SegFlow_to_seg_8_wo_tgt",  # :1341-1349
+                        "-se_SegFlow_to_seg_8": "se_SegFlow_to_seg_8",              # :1350-1356
+                        "-se_SegFlow_to_seg_wo_tgt": "se_SegFlow_to_seg_wo_tgt",    # :1358-1366
+                        "-se_SegFlow_to_seg": "se_SegFlow_to_seg"}                  # :1367-1374
+_TGT_ATTENDED = ("static_all", "se_rgb_to_seg", "se_SegFlow_to_seg", "se_SegFlow_to_seg_8")
+_SE_SCOPE = {"se_flow": "se_flow", "se_seg_wo_tgt": "se_seg", "se_rgb_wo_tgt_to_seg": "se_rgb", "se_rgb_to_seg": "se_rgb",
+             "se_SegFlow_to_seg_wo_tgt": "se_segflow", "se_SegFlow_to_seg": "se_segflow",
+             "se_SegFlow_to_seg_8_wo_tgt": "se_segflow", "se_SegFlow_to_seg_8": "se_segflow"}
+# SE dense layer widths (in, hidden); the recovery layer always has the 19 classes
+_SE_WIDTHS = {"se_flow": (2, 8), "se_seg_wo_tgt": (NUM_SEG_CLASSES, NUM_SEG_CLASSES), "se_rgb_wo_tgt_to_seg": (3, 8),
+              "se_rgb_to_seg": (3, 8), "se_SegFlow_to_seg_wo_tgt": (NUM_SEG_CLASSES + 2, NUM_SEG_CLASSES),
+              "se_SegFlow_to_seg": (NUM_SEG_CLASSES + 2, NUM_SEG_CLASSES),
+              "se_SegFlow_to_seg_8_wo_tgt": (NUM_SEG_CLASSES + 2, 8), "se_SegFlow_to_seg_8": (NUM_SEG_CLASSES + 2, 8)}
 
 
 def parse_version(version):
@@ -144,12 +178,14 @@ def parse_version(version):
     for s in _BEFORE_SE_FLOW:
         if s in v:
             raise UnsupportedVariantError("version `%s': `%s' attention is not supported." % (v, s))
+    after = next((s for s in _AFTER_SE_FLOW if s in v), None)     # the first branch of the chain that matches
     if "-se_flow" in v:
         att_source = "se_flow"
+    elif after in _CLASS_TABLE_SOURCES:
+        att_source = _CLASS_TABLE_SOURCES[after]
+    elif after is not None:
+        raise UnsupportedVariantError("version `%s': `%s' attention is not supported." % (v, after))
     else:
-        for s in _AFTER_SE_FLOW:
-            if s in v:
-                raise UnsupportedVariantError("version `%s': `%s' attention is not supported." % (v, s))
         if "-no_segmask" in v:
             att_source = "ones"
         elif "-segmask_" in v and "-static" in v:
@@ -191,11 +227,13 @@ def weight_shapes(cfg):
         sh[p + "cnv7/biases"] = (256,)
         sh[p + "pred/weights"] = (1, 1, 256, 3)
         sh[p + "pred/biases"] = (3,)
-    if cfg.att_source == "se_flow":
-        sh["pose_exp_net/se_flow/bottleneck_fc/kernel"] = (2, 8)
-        sh["pose_exp_net/se_flow/bottleneck_fc/bias"] = (8,)
-        sh["pose_exp_net/se_flow/recover_fc/kernel"] = (8, NUM_SEG_CLASSES)
-        sh["pose_exp_net/se_flow/recover_fc/bias"] = (NUM_SEG_CLASSES,)
+    if cfg.se_scope is not None:
+        nin, nh = _SE_WIDTHS[cfg.att_source]
+        p = "pose_exp_net/%s/" % cfg.se_scope
+        sh[p + "bottleneck_fc/kernel"] = (nin, nh)
+        sh[p + "bottleneck_fc/bias"] = (nh,)
+        sh[p + "recover_fc/kernel"] = (nh, NUM_SEG_CLASSES)
+        sh[p + "recover_fc/bias"] = (NUM_SEG_CLASSES,)
     elif cfg.att_source in ("static_src", "static_all"):
         sh["pose_exp_net/pose_exp_net/seg_channel_weight/weight"] = (NUM_SEG_CLASSES,)
     return sh

@@ -41,7 +41,16 @@ typedef struct {
     int32_t se_act;         /* 0 relu | 1 tanh | 2 leaky_relu(0.2)   (davo.py:1077-1085)          */
     int32_t norm_flow;      /* (f-0.32140523)/15.384229 on the SE input (davo.py:1089-1091)       */
     int32_t abs_mode;       /* 0 none | 1 |f_x| | 2 |f_y| | 3 |f|      (davo.py:1094-1102)        */
-    int32_t att_source;     /* 0 ones (-no_segmask) | 1 se_flow | 2 static, tgt=1 | 3 static, all */
+    int32_t att_source;     /* 0 ones (-no_segmask) | 1 se_flow | 2 static, tgt=1 | 3 static, all  (davo.py:1385-1400)
+                             * class tables, a per-frame SE descriptor -> dense -> dense -> sigmoid over 19 classes
+                             * (davo.py:1274-1374; "tgt=1": target map ones, otherwise the target's own table):
+                             *   4 -se_seg_wo_tgt               label histogram 19 -> 19 -> 19, tgt=1   (scope se_seg)
+                             *   5 -se_rgb_wo_tgt_to_seg        rgb mean 3 -> 8 -> 19, tgt=1            (scope se_rgb)
+                             *   6 -se_rgb_to_seg               rgb mean 3 -> 8 -> 19                   (scope se_rgb)
+                             *   7 -se_SegFlow_to_seg_wo_tgt    histogram + flow mean 21 -> 19 -> 19, tgt=1 (scope se_segflow)
+                             *   8 -se_SegFlow_to_seg           21 -> 19 -> 19                          (scope se_segflow)
+                             *   9 -se_SegFlow_to_seg_8_wo_tgt  21 -> 8 -> 19, tgt=1                    (scope se_segflow)
+                             *  10 -se_SegFlow_to_seg_8         21 -> 8 -> 19                           (scope se_segflow) */
     int32_t mask_rgb;       /* rgb_k *= att_k                          (davo.py:1419-1423)        */
     int32_t mask_info;      /* flow_k *= att_k  (-segmask_all)         (davo.py:1430-1434)        */
 } davo_variant;
@@ -55,7 +64,7 @@ int davo_create(davo_ctx** out, int device, int H, int W, int max_batch, const d
 /* Replaces tf.train.Saver(tf.trainable_variables()).restore(sess, ckpt)
  * (test_kitti_pose.py:129-131), one tensor at a time, keyed by the TF variable name
  * (e.g. "pose_exp_net/cnv1/weights", "pose_exp_net/pose/rotation/cnv6/biases",
- * "pose_exp_net/se_flow/bottleneck_fc/kernel").  `data` is a host pointer; the context keeps
+ * "pose_exp_net/se_flow/bottleneck_fc/kernel", "pose_exp_net/se_segflow/recover_fc/bias").  `data` is a host pointer; the context keeps
  * its own (re-laid-out) device copy. */
 int davo_load_weight(davo_ctx* ctx, const char* tf_name, const float* data,
                      const int64_t* shape, int ndim);

@@ -1,0 +1,65 @@
+"""Step time of any runnable variant on one GPU (bench.py measures the flagship only): synthetic inputs resident in HBM,
+`--warmup` untimed then `--steps` timed davo_forward_device calls, one JSON line per version.  Versions are run in
+alternating rounds (`--rounds`) so that a drift of the card's clocks does not favour one of them.
+
+    python tools/variant_step.py --precision f16x3 --batch 32 <version> [<version> ...]
+
+Under `rocprofv3 --kernel-trace --stats -- python3 tools/variant_step.py ...` it gives the per-kernel table of a variant."""
+import argparse
+import json
+import os
+import sys
+import time
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+import numpy as np  # noqa: E402
+
+from davo_amd import Engine, synth, parse_version  # noqa: E402
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("versions", nargs="+")
+    ap.add_argument("--batch", type=int, default=32)
+    ap.add_argument("--height", type=int, default=128)
+    ap.add_argument("--width", type=int, default=416)
+    ap.add_argument("--precision", choices=["f16x3", "f32"], default="f16x3")
+    ap.add_argument("--steps", type=int, default=100)
+    ap.add_argument("--warmup", type=int, default=30)
+    ap.add_argument("--rounds", type=int, default=1)
+    a = ap.parse_args()
+    B, H, W = a.batch, a.height, a.width
+    img, flow, seg = synth.make_inputs(B, H, W)
+    runs = []
+    for v in a.versions:
+        cfg = parse_version(v)
+        e = Engine(cfg, H, W, B)
+        e.load_weights(synth.make_weights(cfg))
+        e.set_precision(a.precision)
+        bufs = [e.alloc(x.nbytes).upload(x) for x in (img, flow, seg)] + [e.alloc(B * 12 * 4)]
+        for _ in range(a.warmup):
+            e.forward_device(B, *bufs)
+        e.synchronize()
+        runs.append((v, e, bufs, []))
+    for _ in range(a.rounds):
+        for v, e, bufs, ms in runs:
+            e.synchronize()
+            t = time.perf_counter()
+            for _ in range(a.steps):
+                e.forward_device(B, *bufs)
+            e.synchronize()
+            ms.append((time.perf_counter() - t) * 1e3 / a.steps)
+    for v, e, bufs, ms in runs:
+        pose = bufs[3].download((B, 2, 6))
+        best = min(ms)
+        print(json.dumps({"version": v, "precision": a.precision, "batch": B, "height": H, "width": W, "steps": a.steps,
+                          "ms_per_step": round(best, 4), "ms_per_round": [round(x, 4) for x in ms],
+                          "triplets_per_s": round(B / best * 1e3, 1), "finite": bool(np.isfinite(pose).all())}), flush=True)
+        for buf in bufs:
+            buf.free()
+        e.close()
+
+
+if __name__ == "__main__":
+    main()
