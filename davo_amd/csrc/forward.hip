@@ -89,7 +89,8 @@ void activate_slot(davo_ctx* c, int i) {
 
 // f16x3 only.  Stored activations (fp16 hi/lo pairs) are float32-grade while the layer's largest stored value is
 // below the fp16 maximum (above it values were clamped) and not so small that the pairs lose their low bits
-// (tools/exp_activation_scale.py: the 1e-4 bar holds down to ~2^-16 of O(1) activations; 2^-11 is the guard).
+// (tools/exp_activation_scale.py: with ONE layer off its scale the 1e-4 bar holds down to ~2^-16 of O(1) activations; with
+// all six stored layers at the floor the errors add up, so the guard is 2^-6: docs/F16X3_NUMERICS.md, "The guard's floor").
 int check_range(davo_ctx* c, const unsigned* raw, const int* shifts) {
     static const char* names[6] = {"cnv1", "cnv2", "cnv3", "cnv4", "cnv5", "cnv6"};
     if (!shifts) shifts = c->act_shift;              // the scales the judged batch was issued under

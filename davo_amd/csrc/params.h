@@ -304,7 +304,8 @@ struct ConvPatchParams {
 constexpr int RANGE_WORDS = 8, RANGE_SNAP = 6, RANGE_SEQ = 7;
 // the verdict on one layer's maximum, shared by the host (forward.hip: check_range) and the kernel that keeps the inputs when it will fail
 __host__ __device__ inline bool range_value_fails(float vmax) {
-    return !(vmax < 65504.f) || (vmax > 0.f && vmax < 0x1p-11f);      // clamped / inf, or too small for the fp16 pairs' low halves
+    return !(vmax < 65504.f) || (vmax > 0.f && vmax < 0x1p-6f);       // clamped / inf, or too small for the fp16 pairs' low halves
+                                                                        // (2^-6: docs/F16X3_NUMERICS.md, "The guard's floor")
 }
 // a storing epilogue's note in the record: vmax = the wave's largest stored magnitude, leader = one lane of the wave
 // (compiler builtins only, so that this header still needs no HIP header)

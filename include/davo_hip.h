@@ -198,7 +198,7 @@ int davo_last_plan(davo_ctx* ctx, int layer, int launch, int* mtiles, int* bn);
 int davo_set_precision(davo_ctx* ctx, int precision);
 
 /* f16x3 range management.  Activations between layers are stored as fp16 (hi, lo) pairs; a layer's values must
- * stay below 65504 (they are clamped there) and its largest value above ~2^-11 for the pairs to carry float32-grade
+ * stay below 65504 (they are clamped there) and its largest value at or above 2^-6 for the pairs to carry float32-grade
  * precision.  Each storing kernel records the largest value it wrote (running maxima: a clamped value is caught in the very call
  * that stores it, "too small" on what has been stored since the record was last zeroed - by a recovery, a change of scales, and for
  * every 256th call / batch); davo_forward judges the record at the end of its call.

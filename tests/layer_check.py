@@ -11,6 +11,10 @@ Two bars per layer:
       the stored output and once for the split bias.  So floor = STORE_FLOOR * 2^-shift in f16x3 (shift: the layer's log2
       storage scale) and 0 in float32.  An output that is its bias alone (a 7x7 window of fully masked input) shows it:
       5.3e-4 off by 1.2e-8, 2.3e-5 of its L1 mass.
+      Bar (a) takes the same floor only where asked (a_floor=True: the storage-scale edge sets of
+      tests/test_scaled_layers_gpu.py).  With the layer's stored maximum in the guard's lowest binade [GUARD_FLOOR,
+      2 GUARD_FLOOR), that floor is STORE_FLOOR * 2^-shift <= STORE_FLOOR / GUARD_FLOOR = 2^-18 of max|ref| in rounding
+      alone, beside REL_MAX = 5e-6 (2^-17.6) for everything else: so (a) becomes max|got - ref| <= REL_MAX * max|ref| + floor.
 The network's inputs: `packed' against the oracle's packing and `att_table' against its class tables, at 2e-6.  The pose:
 0.01 * mean(pred(cnv7)) in float64 from the GPU's cnv7 when it is stored, else from cnv7(GPU cnv6) (fused pose head)."""
 import numpy as np
@@ -44,6 +48,16 @@ TAU = {
             "cnv6": 2.0 ** -19,     # 3.7e-7
             "cnv7": 2.0 ** -19},    # 4.6e-7
 }
+
+# The f16x3 range guard's window on a layer's stored maximum: [GUARD_FLOOR, GUARD_CEIL).  GUARD_FLOOR must equal the
+# "too small" threshold of range_value_fails in davo_amd/csrc/params.h (tests/test_storage_scale_emulation.py derives it,
+# tests/test_scaled_layers_gpu.py shows the library trips exactly there).
+GUARD_FLOOR_LOG2 = -6
+GUARD_FLOOR = 2.0 ** GUARD_FLOOR_LOG2
+GUARD_CEIL = 65504.0
+CEIL_BINADE_LOG2 = 15           # the highest binade below GUARD_CEIL: [2^15, 65504)
+EDGE_BAND = 2.0 ** -10          # edge_shifts keeps a stored maximum this far (relative) inside the window
+STORED = ("cnv1", "cnv2", "cnv3", "cnv4", "cnv5", "cnv6")     # the layers with a storage scale and a range record
 
 # the packed tensor of the MFMA path drops the target's flow channels 3, 4 (always zero): 10 -> 8 channels
 PACK8 = [0, 1, 2, 5, 6, 7, 8, 9]
@@ -93,24 +107,24 @@ def layers(cfg, weights):
     return out
 
 
-def layer_ratios(got, ref, mass, floor=0.0):
-    """-> (bar (a) ratio max|got - ref| / max|ref|, bar (b) ratio max (|got - ref| - floor) / mass, index of the worst (b)
-    element)."""
+def layer_ratios(got, ref, mass, floor=0.0, a_floor=False):
+    """-> (bar (a) ratio max|got - ref| / max|ref| (max|got - ref| - floor with a_floor), bar (b) ratio
+    max (|got - ref| - floor) / mass, index of the worst (b) element)."""
     d = np.abs(np.asarray(got, np.float64) - ref)
-    a = float(d.max() / max(np.abs(ref).max(), 1e-30))
+    a = float(max(d.max() - (floor if a_floor else 0.0), 0.0) / max(np.abs(ref).max(), 1e-30))
     r = np.maximum(d - floor, 0.0) / np.maximum(mass, 1e-300)
     i = np.unravel_index(int(np.argmax(r)), r.shape)
     return a, float(r[i]), i
 
 
-def check_layer(name, got, x, groups, stride, rate, tau, what="", floor=0.0):
+def check_layer(name, got, x, groups, stride, rate, tau, what="", floor=0.0, a_floor=False):
     """got [N,Ho,Wo,C] against the float64 conv of x [N,H,W,Cin] under both bars; -> (ratio a, ratio b)."""
     ref = np.empty(got.shape)
     mass = np.empty(got.shape)
     for w, b, cin, cout in groups:
         ref[..., cout] = conv64(x[..., cin], w, b, stride, rate)
         mass[..., cout] = l1_mass(x[..., cin], w, b, stride, rate)
-    a, rb, i = layer_ratios(got, ref, mass, floor)
+    a, rb, i = layer_ratios(got, ref, mass, floor, a_floor)
     assert a <= REL_MAX, "%s %s: bar (a) max|err| = %.3g of max|ref| > %.1g" % (what, name, a, REL_MAX)
     assert rb <= tau, "%s %s: bar (b) |err| = %.3g of the L1 mass at %s (got %.9g, ref %.9g, mass %.3g, floor %.3g) > tau %.3g" % (
         what, name, rb, i, got[i], ref[i], mass[i], floor, tau)
@@ -196,12 +210,12 @@ def forward(e, img, flow, seg):
     return got
 
 
-def plan_images(e, cfg, B, H, W):
-    """Pair images a subset check must hold: the first two, the last two, and those holding the first and last row of
-    every launch of the last forward's plan (last_plan: launch 0 covers rows [0, 128 m0), launch 1 the rest)."""
+def plan_images(e, cfg, B, H, W, ends=2):
+    """Pair images a subset check must hold: the first `ends' and the last `ends', and those holding the first and last
+    row of every launch of the last forward's plan (last_plan: launch 0 covers rows [0, 128 m0), launch 1 the rest)."""
     NB = 2 * B
     sh = shapes(cfg, H, W)
-    keep = {0, 1, NB - 2, NB - 1}
+    keep = set(range(ends)) | set(range(NB - ends, NB))
     for li, name in enumerate(("cnv1", "cnv2", "cnv3", "cnv4", "cnv5", "cnv6", "cnv7")):
         per = sh[name][0] * sh[name][1]
         row = 0
@@ -215,9 +229,13 @@ def plan_images(e, cfg, B, H, W):
 FULL_IMAGES = 64                # pair images checked in full (B <= 32); above that, plan_images
 
 
-def check_forward(e, cfg, weights, img, flow, seg, poses, precision, images=None, what="", stop_after=None, chunk=8):
+def check_forward(e, cfg, weights, img, flow, seg, poses, precision, images=None, what="", stop_after=None, chunk=8,
+                  a_floor=False, checked=None):
     """Check the last forward of engine `e` (run through forward() above) layer by layer.  images: pair-image indices to
-    check (None = all up to FULL_IMAGES pair images, else "plan" = plan_images).  stop_after: last tensor to check ("packed", "cnv1", ...).
+    check (None = all up to FULL_IMAGES pair images, else "plan" = plan_images, "bounds" = plan_images with one image at
+    each end).  stop_after: last tensor to check ("packed", "cnv1", ...).
+    a_floor: bar (a) takes the storage floor too (module docstring).  checked: a dict kept across calls on the same inputs
+    and images: a layer whose tensor AND input are bit-identical to the ones checked before is not convolved again.
     -> {layer: (ratio a, ratio b)}; the worst (b) ratios also go to WORST."""
     B, H, W3, _ = img.shape
     W = W3 // 3
@@ -230,6 +248,8 @@ def check_forward(e, cfg, weights, img, flow, seg, poses, precision, images=None
         images = list(range(NB)) if NB <= FULL_IMAGES else "plan"
     if isinstance(images, str) and images == "plan":
         images = plan_images(e, cfg, B, H, W)
+    elif isinstance(images, str) and images == "bounds":
+        images = plan_images(e, cfg, B, H, W, ends=1)
     images = np.asarray(images)
     trip = sorted(set(int(i) // 2 for i in images))
     want_p = ref_packed(cfg, img[trip], flow[trip], seg[trip], weights)
@@ -251,11 +271,18 @@ def check_forward(e, cfg, weights, img, flow, seg, poses, precision, images=None
             break                                   # the pose head ran fused: cnv7 was never stored
         if name == "cnv7":
             fused = False
-        worst = (0.0, 0.0)
-        for c0 in range(0, len(images), chunk):
-            s = slice(c0, c0 + chunk)
-            a, b = check_layer(name, acts[name][s], acts[prev][s], groups, stride, rate, TAU[precision][name], what, floor)
-            worst = (max(worst[0], a), max(worst[1], b))
+        seen = checked.get(name) if checked is not None else None
+        if seen is not None and np.array_equal(seen[0], acts[name]) and np.array_equal(seen[1], acts[prev]) and seen[2] == floor:
+            worst = seen[3]
+        else:
+            worst = (0.0, 0.0)
+            for c0 in range(0, len(images), chunk):
+                s = slice(c0, c0 + chunk)
+                a, b = check_layer(name, acts[name][s], acts[prev][s], groups, stride, rate, TAU[precision][name], what, floor,
+                                   a_floor)
+                worst = (max(worst[0], a), max(worst[1], b))
+            if checked is not None:
+                checked[name] = (acts[name], acts[prev], floor, worst)
         stats[name] = worst
         key = (precision, name)
         WORST[key] = max(WORST.get(key, 0.0), worst[1])
@@ -269,3 +296,87 @@ def check_forward(e, cfg, weights, img, flow, seg, poses, precision, images=None
     else:
         stats["pose"] = check_pose(got, pose_from_cnv7(acts["cnv7"], weights), what + " pose head")
     return stats
+
+
+# ---- storage scales at the edges of the range guard's window (f16x3) ---------------------------------------------------
+def binade_shift(vmax, lo_log2):
+    """The power-of-two storage shift that puts a layer's largest |activation| vmax into [2^lo_log2, 2^(lo_log2 + 1))."""
+    return int(lo_log2 - np.floor(np.log2(float(vmax))))
+
+
+def edge_shifts(maxima, where):
+    """Per-layer storage shifts at the edges of the guard's window.  maxima: {layer: largest |activation|, unscaled}
+    (Engine.activation_range()[0] of a run at any scales); where: "floor", "ceiling", or {layer: "floor" | "ceiling" |
+    None (shift 0)}.  "floor": the stored maximum in [GUARD_FLOOR, 2 GUARD_FLOOR); "ceiling": in [2^15, GUARD_CEIL (1 - 2^-10)).
+    A maximum in the guard band (within EDGE_BAND of the window's edge: a rounding away from tripping the guard) steps one
+    binade inwards - down at the ceiling, up at the floor.  -> {layer: shift}."""
+    out = {}
+    for k, m in maxima.items():
+        w = where if isinstance(where, str) else where.get(k)
+        if w is None:
+            out[k] = 0
+            continue
+        assert m > 0, (k, m)
+        if w == "floor":
+            s = binade_shift(m, GUARD_FLOOR_LOG2)
+            if m * 2.0 ** s < GUARD_FLOOR * (1.0 + EDGE_BAND):
+                s += 1
+        elif w == "ceiling":
+            s = binade_shift(m, CEIL_BINADE_LOG2)
+            if m * 2.0 ** s >= GUARD_CEIL * (1.0 - EDGE_BAND):
+                s -= 1
+        else:
+            raise ValueError(w)
+        out[k] = s
+    return out
+
+
+def pair_store(x, shift=0, flush_lo=False, clamp=GUARD_CEIL):
+    """What an f16x3 epilogue stores, decoded: x' = min(f32(x 2^shift), clamp), hi = fp16(x'), lo = fp16(x' - hi),
+    -> (hi + lo) 2^-shift in float64.  numpy's float16 keeps subnormals; flush_lo: lo halves below the smallest normal fp16
+    are stored as 0 (a kernel that flushes denormals)."""
+    xs = np.minimum(np.asarray(x, np.float64) * 2.0 ** shift, clamp).astype(np.float32)
+    hi = xs.astype(np.float16)
+    lo = (xs - hi.astype(np.float32)).astype(np.float16)
+    if flush_lo:
+        lo = np.where(np.abs(lo) < np.float16(2.0 ** -14), np.float16(0), lo)
+    return (hi.astype(np.float64) + lo.astype(np.float64)) * 2.0 ** -shift
+
+
+RECORD_REL = 2.0 ** -22         # the range record against max|debug_read|: the pair rounding, relative ...
+RECORD_ABS = 2.0 ** -25         # ... plus the subnormal grid of lo, in stored units
+
+
+def range_record_forward(e, img, flow, seg, shifts=None):
+    """One forward(), with the range record started afresh: shifts installed (None = none; the next host call then
+    starts from a zeroed record) and the host's maxima reset.  -> (poses, record {layer: max |stored|, unscaled})."""
+    e.set_activation_shifts(shifts)
+    e.activation_range(reset=True)
+    poses = forward(e, img, flow, seg)
+    return poses, e.activation_range()[0]
+
+
+def check_range_record(e, cfg, B, H, W, record, what=""):
+    """The range record of the last forward against what its kernels stored: record[layer] == max |debug_read(layer)| over
+    the whole batch, within the pair rounding (RECORD_REL * max + RECORD_ABS * 2^-shift).  Catches an epilogue that skips
+    range_note, notes before out_scale or notes rows outside the tensor.  -> {layer: (row of the maximum in the layer's
+    GEMM, [(first row, rows) of each launch of last_plan])}."""
+    sh = shapes(cfg, H, W)
+    shifts = e.activation_range()[1]
+    where = {}
+    for li, name in enumerate(STORED):
+        t = e.debug_read(name, (2 * B,) + sh[name])
+        a = np.abs(t.reshape(-1, t.shape[-1])).max(axis=1)
+        row = int(np.argmax(a))
+        m = float(a[row])
+        bar = RECORD_REL * m + RECORD_ABS * 2.0 ** -shifts[name]
+        assert abs(record[name] - m) <= bar, "%s %s: range record %.9g, stored maximum %.9g (shift %d)" % (
+            what, name, record[name], m, shifts[name])
+        launches, r0 = [], 0
+        for mt, _ in e.last_plan(li):
+            n = min(128 * mt, a.size - r0)
+            launches.append((r0, n))
+            r0 += n
+        where[name] = (row, launches)
+    return where
+

@@ -175,3 +175,77 @@ def test_subset_of_pair_images():
             return [(533, 5), (507, 4)] if layer == 4 else []
 
     assert LC.plan_images(Q(), cfg, 20, 128, 416) == [0, 1, 20, 38, 39]   # row 533 * 128 is in image 20 (3328 rows each)
+
+
+# ---- storage scales at the edges of the range guard's window ------------------------------------------------------------
+def test_guard_floor_is_the_librarys():
+    """layer_check.GUARD_FLOOR is range_value_fails' "too small" threshold in csrc/params.h."""
+    import os
+    import re
+    src = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "davo_amd", "csrc", "params.h")).read()
+    body = src[src.index("inline bool range_value_fails"):]
+    body = body[:body.index("}")]
+    assert re.search(r"vmax < 0x1p%df" % LC.GUARD_FLOOR_LOG2, body), body
+    assert "vmax < 65504.f" in body and LC.GUARD_CEIL == 65504.0
+
+
+def test_edge_shifts():
+    m = {"cnv1": 28.06, "cnv2": 1.0, "cnv3": 2.0 ** -40 * 1.5, "cnv4": 65504.0 / 2 ** 3, "cnv5": 2.0 ** -6 * (1 + 2 ** -12),
+         "cnv6": 0.3}
+    fl = LC.edge_shifts(m, "floor")
+    ce = LC.edge_shifts(m, "ceiling")
+    for k, v in m.items():
+        lo = v * 2.0 ** fl[k]
+        hi = v * 2.0 ** ce[k]
+        assert LC.GUARD_FLOOR * (1 + LC.EDGE_BAND) <= lo < 4 * LC.GUARD_FLOOR, (k, lo)
+        assert 2.0 ** 14 <= hi < LC.GUARD_CEIL * (1 - LC.EDGE_BAND), (k, hi)
+    assert fl["cnv2"] == -5 and fl["cnv5"] == 1 and ce["cnv4"] == 2 and ce["cnv2"] == 15      # the guard bands step inwards
+    assert m["cnv1"] * 2.0 ** fl["cnv1"] < 2 * LC.GUARD_FLOOR and m["cnv1"] * 2.0 ** ce["cnv1"] >= 2.0 ** 15
+    mixed = LC.edge_shifts(m, {"cnv1": "floor", "cnv2": "ceiling"})
+    assert mixed == dict({k: 0 for k in m}, cnv1=fl["cnv1"], cnv2=ce["cnv2"])
+
+
+def _edge_layer(cfg, weights, keep, name, lo_log2):
+    """cnv`name' of the oracle on its float64 input, stored at the shift that puts its maximum at 2^lo_log2's binade."""
+    prev, stride, rate, groups = _spec(cfg, weights, name)
+    w, b, _, _ = groups[0]
+    ref = LC.conv64(keep[prev], w, b, stride, rate)
+    where = "floor" if lo_log2 == LC.GUARD_FLOOR_LOG2 else "ceiling"
+    return prev, stride, rate, groups, ref, LC.edge_shifts({name: np.abs(ref).max()}, where)[name]
+
+
+def _flags_at(cfg, weights, keep, name, got, shift):
+    prev, stride, rate, groups = _spec(cfg, weights, name)
+    return _flags(lambda: LC.check_layer(name, got, keep[prev], groups, stride, rate, LC.TAU["f16x3"][name],
+                                         floor=LC.STORE_FLOOR * 2.0 ** -shift, a_floor=True))
+
+
+@pytest.mark.parametrize("name", ["cnv2", "cnv5"])
+def test_pair_storage_at_the_floor(net, name):
+    """Exact pair storage with the layer's maximum in the guard's lowest binade passes both bars (with the bar-(a) floor
+    term); the same layer with its subnormal lo halves flushed to zero, or computed from an input whose subnormal lo halves
+    were dropped (an MFMA that flushes fp16 denormals), is flagged."""
+    cfg, weights, _, keep, _ = net
+    prev, stride, rate, groups, ref, s = _edge_layer(cfg, weights, keep, name, LC.GUARD_FLOOR_LOG2)
+    assert LC.GUARD_FLOOR <= np.abs(ref).max() * 2.0 ** s < 2 * LC.GUARD_FLOOR
+    assert not _flags_at(cfg, weights, keep, name, LC.pair_store(ref, s), s)
+    assert _flags_at(cfg, weights, keep, name, LC.pair_store(ref, s, flush_lo=True), s)
+    # the input stored at ITS floor scale, decoded exactly for the checker, but convolved without its subnormal lo halves
+    s_in = LC.edge_shifts({prev: np.abs(keep[prev]).max()}, "floor")[prev]
+    x = LC.pair_store(keep[prev], s_in)
+    x_flushed = LC.pair_store(keep[prev], s_in, flush_lo=True)
+    w, b, _, _ = groups[0]
+    keep_in = dict(keep, **{prev: x})
+    assert not _flags_at(cfg, weights, keep_in, name, LC.pair_store(LC.conv64(x, w, b, stride, rate), s), s)
+    assert _flags_at(cfg, weights, keep_in, name, LC.pair_store(LC.conv64(x_flushed, w, b, stride, rate), s), s)
+
+
+@pytest.mark.parametrize("name", ["cnv2", "cnv5"])
+def test_pair_storage_at_the_ceiling(net, name):
+    """Exact pair storage with the maximum in [2^15, 65504) passes; an epilogue that clamps at 2^15 instead of 65504 is
+    flagged."""
+    cfg, weights, _, keep, _ = net
+    _, _, _, _, ref, s = _edge_layer(cfg, weights, keep, name, LC.CEIL_BINADE_LOG2)
+    assert 2.0 ** 15 <= np.abs(ref).max() * 2.0 ** s < LC.GUARD_CEIL
+    assert not _flags_at(cfg, weights, keep, name, LC.pair_store(ref, s), s)
+    assert _flags_at(cfg, weights, keep, name, LC.pair_store(ref, s, clamp=2.0 ** 15), s)

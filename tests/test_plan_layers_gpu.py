@@ -61,9 +61,12 @@ def _run(e, cfg, inputs, precision, what, images=None, stop_after=None, plan_che
 
 
 # ---- default plans -------------------------------------------------------------------------------------------------
+DEFAULT_PLANS = [(128, 416, 1), (128, 416, 3), (128, 416, 32), (128, 416, 128), (256, 832, 2),
+                 (36, 100, 2), (52, 172, 1), (20, 48, 5), (16, 16, 1)]
+
+
 @pytest.mark.parametrize("precision", PRECISIONS)
-@pytest.mark.parametrize("H,W,B", [(128, 416, 1), (128, 416, 3), (128, 416, 32), (128, 416, 128), (256, 832, 2),
-                                   (36, 100, 2), (52, 172, 1), (20, 48, 5), (16, 16, 1)])
+@pytest.mark.parametrize("H,W,B", DEFAULT_PLANS)
 def test_default_plan(H, W, B, precision):
     """The plan the library picks by itself: stored cnv7 (fuse_pose 0) with every pair image up to B = 32, then the fused
     pose head on the images a plan's launches start and end in (frames whose cnv7 map is under one 128-row tile per image
