@@ -39,6 +39,7 @@ LIB_PATH = lib_path()
 
 EXPORTS = (
     "davo_create", "davo_load_weight", "davo_weights_missing", "davo_forward", "davo_forward_device", "davo_submit", "davo_wait", "davo_pending",
+    "davo_forward_depth", "davo_forward_device_depth", "davo_submit_depth", "davo_calibrate_depth",
     "davo_last_error", "davo_destroy", "davo_device_malloc", "davo_device_free", "davo_memcpy_h2d",
     "davo_memcpy_d2h", "davo_synchronize", "davo_set_stream", "davo_set_inflight", "davo_profile_enable",
     "davo_profile_reset", "davo_profile_entry", "davo_profile_samples", "davo_last_plan", "davo_set_option", "davo_set_precision", "davo_set_impl", "davo_debug_read", "davo_conv2d_same",
@@ -168,6 +169,10 @@ def _load():
     L.davo_forward.argtypes = [vp, i, vp, vp, vp, vp]
     L.davo_forward_device.argtypes = [vp, i, vp, vp, vp, vp, ctypes.POINTER(ctypes.c_float)]
     L.davo_submit.argtypes = [vp, i, vp, vp, vp, vp, i]
+    L.davo_forward_depth.argtypes = [vp, i, vp, vp, vp, vp, vp]
+    L.davo_forward_device_depth.argtypes = [vp, i, vp, vp, vp, vp, vp, ctypes.POINTER(ctypes.c_float)]
+    L.davo_submit_depth.argtypes = [vp, i, vp, vp, vp, vp, vp, i]
+    L.davo_calibrate_depth.argtypes = [vp, i, vp, vp, vp, vp, ctypes.POINTER(i)]
     L.davo_wait.argtypes = [vp, i]
     L.davo_pending.argtypes = [vp]
     L.davo_last_error.argtypes = [vp]

@@ -68,7 +68,7 @@ int davo_create(davo_ctx** out, int device, int H, int W, int max_batch, const d
     if (max_batch < 1) return fail(c, DAVO_ERR_INVALID, "max_batch must be >= 1");
     if (v->cin_per_frame != 5 && v->cin_per_frame != 3) return fail(c, DAVO_ERR_INVALID, "cin_per_frame must be 3 or 5");
     if (ilog2_exact(v->cnv6_out) < 5 || v->cnv6_out > 256) return fail(c, DAVO_ERR_INVALID, "cnv6_out must be 32, 64, 128 or 256");
-    if (v->se_act < 0 || v->se_act > 2 || v->abs_mode < 0 || v->abs_mode > 3 || v->att_source < 0 || v->att_source > 10)
+    if (v->se_act < 0 || v->se_act > 2 || v->abs_mode < 0 || v->abs_mode > 3 || v->att_source < 0 || v->att_source > 12)
         return fail(c, DAVO_ERR_INVALID, "variant field out of range");
     int ndev = 0;
     HIP_TRY(c, hipGetDeviceCount(&ndev));
@@ -178,6 +178,17 @@ constexpr int FRESH_EVERY = 256;
 size_t img_bytes(const davo_ctx* c) { return (size_t)c->H * c->W * 9; }
 size_t flow_bytes(const davo_ctx* c) { return (size_t)c->H * c->W * 8 * sizeof(float); }
 size_t seg_bytes(const davo_ctx* c) { return (size_t)c->H * c->W * 3 * sizeof(float); }
+size_t depth_bytes(const davo_ctx* c) { return (size_t)c->H * c->W * 3 * sizeof(float); }      // [3,H,W,1] float32 like the label maps (davo.py:991-996)
+bool needs_depth(const davo_ctx* c) { return att_desc_depth(c->v.att_source); }
+
+// The depth argument of an entry point.  A depth-source variant (att_source 11, 12) must be called through the `_depth' form with
+// the planes; every other variant reads no depth: the `_depth' forms accept a pointer (or null) and ignore it.
+int resolve_depth(davo_ctx* c, const char* fn, bool depth_form, const void** depth) {
+    if (!needs_depth(c)) { *depth = nullptr; return DAVO_OK; }
+    if (!depth_form) return fail(c, DAVO_ERR_INVALID, "%s: this variant reads depth planes (att_source %d): call %s_depth", fn, c->v.att_source, fn);
+    if (!*depth) return fail(c, DAVO_ERR_INVALID, "%s_depth: null depth pointer", fn);
+    return DAVO_OK;
+}
 
 int ensure_ring(davo_ctx* c, bool snapshots) {
     if (!c->read_stream) {
@@ -191,6 +202,7 @@ int ensure_ring(davo_ctx* c, bool snapshots) {
             HIP_TRY(c, hipMalloc(&c->snap_img[r], img_bytes(c) * c->max_batch));
             HIP_TRY(c, hipMalloc(&c->snap_flow[r], flow_bytes(c) * c->max_batch));
             HIP_TRY(c, hipMalloc(&c->snap_seg[r], seg_bytes(c) * c->max_batch));
+            if (needs_depth(c)) HIP_TRY(c, hipMalloc(&c->snap_depth[r], depth_bytes(c) * c->max_batch));
         }
     }
     return DAVO_OK;
@@ -244,14 +256,14 @@ int freeze_pending_and_reset_ring(davo_ctx* c) {
 // value into [512, 1024).  A layer computed from badly ranged inputs still has about the right magnitude, so each
 // pass fixes at least the first badly ranged layer exactly and the later ones to within a few powers of two.
 // Runs on the base record; every stream must be idle.
-int calibrate_on(davo_ctx* c, int B, const void* d_img, const void* d_flow, const void* d_seg, void* d_pose) {
+int calibrate_on(davo_ctx* c, int B, const void* d_img, const void* d_flow, const void* d_seg, const void* d_depth, void* d_pose) {
     int rc = DAVO_OK;
     const int save_precision = c->precision, save_impl = c->impl;
     c->precision = 1; c->impl = 0;
     c->d_range = c->d_range_base;
     for (int pass = 0; pass < 8 && rc == DAVO_OK; ++pass) {
         if ((rc = zero_base_record(c, c->stream))) break;
-        rc = forward_device(c, B, d_img, d_flow, d_seg, d_pose);
+        rc = forward_device(c, B, d_img, d_flow, d_seg, d_depth, d_pose);
         if (rc) break;
         if (hipStreamSynchronize(c->stream) != hipSuccess) { rc = fail(c, DAVO_ERR_HIP, "hipStreamSynchronize failed"); break; }
         unsigned raw[RANGE_WORDS];
@@ -278,7 +290,7 @@ int calibrate_on(davo_ctx* c, int B, const void* d_img, const void* d_flow, cons
 int run_judged(davo_ctx* c, const Ticket& b) {
     c->d_range = c->d_range_base;
     { int rc = zero_base_record(c, c->stream); if (rc) return rc; }
-    int rc = forward_device(c, b.B, b.img, b.flow, b.seg, b.pose);
+    int rc = forward_device(c, b.B, b.img, b.flow, b.seg, b.depth, b.pose);
     if (rc) return rc;
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     if (c->last_precision != 1) return DAVO_OK;
@@ -312,7 +324,7 @@ int recover_batch(davo_ctx* c, const Ticket& orig) {
     activate_slot(c, 0);
     int rc = run_judged(c, b);
     if (rc == DAVO_ERR_RANGE) {
-        if ((rc = calibrate_on(c, b.B, b.img, b.flow, b.seg, b.pose))) return rc;
+        if ((rc = calibrate_on(c, b.B, b.img, b.flow, b.seg, b.depth, b.pose))) return rc;
         ++c->n_recalibrations;
         rc = run_judged(c, b);
         c->range_report = "re-calibrated: " + verdict;
@@ -320,7 +332,7 @@ int recover_batch(davo_ctx* c, const Ticket& orig) {
     if (rc == DAVO_ERR_RANGE) {
         const int save = c->precision;
         c->precision = 0;
-        rc = forward_device(c, b.B, b.img, b.flow, b.seg, b.pose);
+        rc = forward_device(c, b.B, b.img, b.flow, b.seg, b.depth, b.pose);
         c->precision = save;
         if (rc == DAVO_OK && hipStreamSynchronize(c->stream) != hipSuccess) rc = fail(c, DAVO_ERR_HIP, "hipStreamSynchronize failed");
         ++c->n_f32_batches;
@@ -421,11 +433,11 @@ int ticket_reserve(davo_ctx* c) {
 }
 
 // ... the batch's kernels record into the slot's record; its last kernel keeps the inputs there if the record fails
-int ticket_begin(davo_ctx* c, int B, const void* d_img, const void* d_flow, const void* d_seg, bool* snap, bool own_inputs = false) {
+int ticket_begin(davo_ctx* c, int B, const void* d_img, const void* d_flow, const void* d_seg, const void* d_depth, bool* snap, bool own_inputs = false) {
     const int r = c->ring_next;
     // own_inputs: the batch reads a staging set of the context (davo_submit), which the next batches overwrite whatever the caller declared
     *snap = c->opt_auto_range && (!c->opt_stable_inputs || own_inputs);
-    if (*snap && (((uintptr_t)d_img | (uintptr_t)d_flow | (uintptr_t)d_seg) & 15)) return fail(c, DAVO_ERR_INVALID, "device input buffers must be 16-byte aligned");
+    if (*snap && (((uintptr_t)d_img | (uintptr_t)d_flow | (uintptr_t)d_seg | (uintptr_t)d_depth) & 15)) return fail(c, DAVO_ERR_INVALID, "device input buffers must be 16-byte aligned");
     { int rc = ensure_ring(c, *snap); if (rc) return rc; }
     c->d_range = ring_record(c, r);
     c->range_zero = true;
@@ -443,11 +455,12 @@ int ticket_begin(davo_ctx* c, int B, const void* d_img, const void* d_flow, cons
                        static_cast<const uint8_t*>(d_img), static_cast<const uint8_t*>(d_flow), static_cast<const uint8_t*>(d_seg),
                        *snap ? static_cast<uint8_t*>(c->snap_img[r]) : nullptr, *snap ? static_cast<uint8_t*>(c->snap_flow[r]) : nullptr,
                        *snap ? static_cast<uint8_t*>(c->snap_seg[r]) : nullptr,
-                       (unsigned)(img_bytes(c) / 16), (unsigned)(flow_bytes(c) / 32), (unsigned)(flow_bytes(c) / 16), (unsigned)(seg_bytes(c) / 16), B};
+                       (unsigned)(img_bytes(c) / 16), (unsigned)(flow_bytes(c) / 32), (unsigned)(flow_bytes(c) / 16), (unsigned)(seg_bytes(c) / 16), B,
+                       static_cast<const uint8_t*>(d_depth), (*snap && d_depth) ? static_cast<uint8_t*>(c->snap_depth[r]) : nullptr};
     return DAVO_OK;
 }
 
-int ticket_end(davo_ctx* c, int rc, int B, const void* d_img, const void* d_flow, const void* d_seg, void* d_pose, bool snap, float* h_pose = nullptr) {
+int ticket_end(davo_ctx* c, int rc, int B, const void* d_img, const void* d_flow, const void* d_seg, const void* d_depth, void* d_pose, bool snap, float* h_pose = nullptr) {
     const int r = c->ring_next;
     c->d_range = c->d_range_base;
     c->range_zero = false;
@@ -457,6 +470,7 @@ int ticket_end(davo_ctx* c, int rc, int B, const void* d_img, const void* d_flow
     if (c->last_precision != 1) return DAVO_OK;                                  // float32 kernels (weight guard): no record, no verdict
     Ticket t{};
     t.B = B; t.img = snap ? c->snap_img[r] : d_img; t.flow = snap ? c->snap_flow[r] : d_flow; t.seg = snap ? c->snap_seg[r] : d_seg;
+    t.depth = (snap && d_depth) ? c->snap_depth[r] : d_depth;
     t.pose = d_pose; t.ring = r; t.snap = snap; t.seq = c->snap_seq_issued; t.stream = c->stream; t.h_pose = h_pose; t.issue = c->n_issued;
     for (int i = 0; i < 6; ++i) t.shifts[i] = c->act_shift[i];
     c->tickets.push_back(t);
@@ -467,11 +481,13 @@ int ticket_end(davo_ctx* c, int rc, int B, const void* d_img, const void* d_flow
 
 }  // namespace
 
-int davo_forward_device(davo_ctx* c, int B, const void* d_img, const void* d_flow, const void* d_seg,
-                        void* d_pose, float* elapsed_ms) {
+// the body of davo_forward_device / davo_forward_device_depth (depth_form)
+static int forward_device_entry(davo_ctx* c, int B, const void* d_img, const void* d_flow, const void* d_seg, const void* d_depth,
+                                void* d_pose, float* elapsed_ms, bool depth_form) {
     if (!c) return DAVO_ERR_INVALID;
     if (B < 1 || B > c->max_batch) return fail(c, DAVO_ERR_INVALID, "batch %d outside [1,%d]", B, c->max_batch);
     if (!d_img || !d_flow || !d_seg || !d_pose) return fail(c, DAVO_ERR_INVALID, "null device pointer");
+    { int rc = resolve_depth(c, "davo_forward_device", depth_form, &d_depth); if (rc) return rc; }
     HIP_TRY(c, hipSetDevice(c->device));
     const bool ticketed = c->impl == 0 && c->precision == 1;      // f16x3: the batch gets a record (and a copy of its inputs) of its own
     if (ticketed) { int rc = ticket_reserve(c); if (rc) return rc; }
@@ -479,7 +495,7 @@ int davo_forward_device(davo_ctx* c, int B, const void* d_img, const void* d_flo
     activate_slot(c, c->next_slot);
     c->next_slot = (c->next_slot + 1) % c->inflight;
     bool snap = false;
-    if (ticketed) { int rc = ticket_begin(c, B, d_img, d_flow, d_seg, &snap); if (rc) return rc; }
+    if (ticketed) { int rc = ticket_begin(c, B, d_img, d_flow, d_seg, d_depth, &snap); if (rc) return rc; }
     if (!ticketed && c->pose_spans.size() > 64) {          // float32 batches behind pending f16x3 tickets: bounded
         const int rc = judge_all(c);
         if (rc == DAVO_ERR_RANGE) { c->sticky_range_rc = rc; c->sticky_range_err = c->err; }       // "auto_range" 0: reported by the next davo_synchronize
@@ -487,8 +503,8 @@ int davo_forward_device(davo_ctx* c, int B, const void* d_img, const void* d_flo
     }
     note_pose_span(c, d_pose, B);
     if (!elapsed_ms) {
-        int rc = forward_device(c, B, d_img, d_flow, d_seg, d_pose);
-        if (ticketed) rc = ticket_end(c, rc, B, d_img, d_flow, d_seg, d_pose, snap);
+        int rc = forward_device(c, B, d_img, d_flow, d_seg, d_depth, d_pose);
+        if (ticketed) rc = ticket_end(c, rc, B, d_img, d_flow, d_seg, d_depth, d_pose, snap);
         else if (rc == DAVO_OK && c->f32_fallback) ++c->n_f32_batches;
         return rc;
     }
@@ -500,17 +516,27 @@ int davo_forward_device(davo_ctx* c, int B, const void* d_img, const void* d_flo
     };
     if (hip_ok(hipEventCreate(&e0), "hipEventCreate") && hip_ok(hipEventCreate(&e1), "hipEventCreate") &&
         hip_ok(hipEventRecord(e0, c->stream), "hipEventRecord")) {
-        rc = forward_device(c, B, d_img, d_flow, d_seg, d_pose);
+        rc = forward_device(c, B, d_img, d_flow, d_seg, d_depth, d_pose);
         if (rc == DAVO_OK && hip_ok(hipEventRecord(e1, c->stream), "hipEventRecord") &&
             hip_ok(hipEventSynchronize(e1), "hipEventSynchronize"))
             hip_ok(hipEventElapsedTime(elapsed_ms, e0, e1), "hipEventElapsedTime");
     }
     if (e0) (void)hipEventDestroy(e0);
     if (e1) (void)hipEventDestroy(e1);
-    if (ticketed) rc = ticket_end(c, rc, B, d_img, d_flow, d_seg, d_pose, snap);
+    if (ticketed) rc = ticket_end(c, rc, B, d_img, d_flow, d_seg, d_depth, d_pose, snap);
     // the timed form is synchronous, so it can judge (and, if need be, re-issue) its own batch; elapsed_ms is the first issue's
     if (rc == DAVO_OK && c->inflight == 1) rc = judge_all(c);
     return rc;
+}
+
+int davo_forward_device(davo_ctx* c, int B, const void* d_img, const void* d_flow, const void* d_seg,
+                        void* d_pose, float* elapsed_ms) {
+    return forward_device_entry(c, B, d_img, d_flow, d_seg, nullptr, d_pose, elapsed_ms, false);
+}
+
+int davo_forward_device_depth(davo_ctx* c, int B, const void* d_img, const void* d_flow, const void* d_seg, const void* d_depth,
+                              void* d_pose, float* elapsed_ms) {
+    return forward_device_entry(c, B, d_img, d_flow, d_seg, d_depth, d_pose, elapsed_ms, true);
 }
 
 
@@ -542,6 +568,7 @@ int ensure_stream_state(davo_ctx* c, int slot) {
         // planes the path never reads (flow 2,3; the target frame's label map) are never copied either: defined contents all the same
         { int rc = zero_now(c, c->st_flow[slot], flow_bytes(c) * c->max_batch); if (rc) return rc; }
         { int rc = zero_now(c, c->st_seg[slot], seg_bytes(c) * c->max_batch); if (rc) return rc; }
+        if (needs_depth(c)) HIP_TRY(c, hipMalloc(&c->st_depth[slot], depth_bytes(c) * c->max_batch));      // copied whole by every submit
     }
     return DAVO_OK;
 }
@@ -573,9 +600,13 @@ int deliver_all(davo_ctx* c) {
 
 }  // namespace
 
-int davo_submit(davo_ctx* c, int B, const uint8_t* img, const float* flow, const float* seg, float* pose_out, int hold) {
+// the body of davo_submit / davo_submit_depth (depth_form)
+static int submit_entry(davo_ctx* c, int B, const uint8_t* img, const float* flow, const float* seg, const float* depth_in, float* pose_out,
+                        int hold, bool depth_form) {
     if (!c) return DAVO_ERR_INVALID;
     if (!img || !flow || !seg || !pose_out) return fail(c, DAVO_ERR_INVALID, "null host pointer");
+    const void* depth = depth_in;
+    { int rc = resolve_depth(c, "davo_submit", depth_form, &depth); if (rc) return rc; }
     if (B < 1 || B > c->max_batch) return fail(c, DAVO_ERR_INVALID, "batch %d outside [1,%d]", B, c->max_batch);
     if (hold < 0) return fail(c, DAVO_ERR_INVALID, "hold must be >= 0");
     HIP_TRY(c, hipSetDevice(c->device));
@@ -603,20 +634,23 @@ int davo_submit(davo_ctx* c, int B, const uint8_t* img, const float* flow, const
         for (int plane = 0; plane < 3; plane += 2)
             HIP_TRY(c, hipMemcpy2DAsync((uint8_t*)c->st_seg[slot] + plane * (nb_seg / 3), nb_seg, (const uint8_t*)seg + plane * (nb_seg / 3), nb_seg,
                                         nb_seg / 3, B, hipMemcpyHostToDevice, s));
+    // depth sources: all three planes are read (the target's depth enters every frame's descriptor, davo.py:1109)
+    void* const st_depth = depth ? c->st_depth[slot] : nullptr;
+    if (depth) HIP_TRY(c, hipMemcpyAsync(st_depth, depth, depth_bytes(c) * B, hipMemcpyHostToDevice, s));
     // the caller keeps a batch's inputs unchanged for `hold` more submits.  With hold >= STREAM_POSES the pose ring already implies it
     // (a batch is delivered - so its copies are long done - before the eighth submit after it returns): no event then
     const bool track_copy = hold < STREAM_POSES;
     if (track_copy) HIP_TRY(c, hipEventRecord(c->st_copied[pr], s));
 
     bool snap = false;
-    if (ticketed) { int rc = ticket_begin(c, B, c->st_img[slot], c->st_flow[slot], c->st_seg[slot], &snap, true); if (rc) return rc; }
+    if (ticketed) { int rc = ticket_begin(c, B, c->st_img[slot], c->st_flow[slot], c->st_seg[slot], st_depth, &snap, true); if (rc) return rc; }
     ++c->n_issued;                    // (no pose span: a pose ring entry is not reused before its batch has been delivered)
-    int rc = forward_device(c, B, c->st_img[slot], c->st_flow[slot], c->st_seg[slot], c->d_pose_ring[pr]);
+    int rc = forward_device(c, B, c->st_img[slot], c->st_flow[slot], c->st_seg[slot], st_depth, c->d_pose_ring[pr]);
     const unsigned seq = c->snap_seq_issued;
     bool has_ticket = false;
     if (ticketed) {
         const size_t before = c->tickets.size();
-        rc = ticket_end(c, rc, B, c->st_img[slot], c->st_flow[slot], c->st_seg[slot], c->d_pose_ring[pr], snap, c->h_pose_ring[pr]);
+        rc = ticket_end(c, rc, B, c->st_img[slot], c->st_flow[slot], c->st_seg[slot], st_depth, c->d_pose_ring[pr], snap, c->h_pose_ring[pr]);
         has_ticket = c->tickets.size() > before;            // (the weight guard's float32 batches get no ticket)
     } else if (rc == DAVO_OK && c->f32_fallback) ++c->n_f32_batches;
     if (rc) return rc;
@@ -634,6 +668,14 @@ int davo_submit(davo_ctx* c, int B, const uint8_t* img, const float* flow, const
     return DAVO_OK;
 }
 
+int davo_submit(davo_ctx* c, int B, const uint8_t* img, const float* flow, const float* seg, float* pose_out, int hold) {
+    return submit_entry(c, B, img, flow, seg, nullptr, pose_out, hold, false);
+}
+
+int davo_submit_depth(davo_ctx* c, int B, const uint8_t* img, const float* flow, const float* seg, const float* depth, float* pose_out, int hold) {
+    return submit_entry(c, B, img, flow, seg, depth, pose_out, hold, true);
+}
+
 int davo_wait(davo_ctx* c, int leave_pending) {
     if (!c) return DAVO_ERR_INVALID;
     if (leave_pending < 0) return fail(c, DAVO_ERR_INVALID, "leave_pending must be >= 0");
@@ -644,9 +686,13 @@ int davo_wait(davo_ctx* c, int leave_pending) {
 
 int davo_pending(davo_ctx* c) { return c ? (int)c->jobs.size() : DAVO_ERR_INVALID; }
 
-int davo_forward(davo_ctx* c, int B, const uint8_t* img, const float* flow, const float* seg, float* pose_out) {
+// the body of davo_forward / davo_forward_depth (depth_form)
+static int forward_entry(davo_ctx* c, int B, const uint8_t* img, const float* flow, const float* seg, const float* depth_in, float* pose_out,
+                         bool depth_form) {
     if (!c) return DAVO_ERR_INVALID;
     if (!img || !flow || !seg || !pose_out) return fail(c, DAVO_ERR_INVALID, "null host pointer");
+    const void* depth = depth_in;
+    { int rc = resolve_depth(c, "davo_forward", depth_form, &depth); if (rc) return rc; }
     if (B < 1 || B > c->max_batch) return fail(c, DAVO_ERR_INVALID, "batch %d outside [1,%d]", B, c->max_batch);
     HIP_TRY(c, hipSetDevice(c->device));
     { int rc = deliver_all(c); if (rc) return rc; }          // davo_submit batches still under way: delivered first
@@ -659,6 +705,7 @@ int davo_forward(davo_ctx* c, int B, const uint8_t* img, const float* flow, cons
         HIP_TRY(c, hipMalloc(&c->s_flow, nb_flow * c->max_batch));
         HIP_TRY(c, hipMalloc(&c->s_seg, nb_seg * c->max_batch));
         HIP_TRY(c, hipMalloc(&c->s_pose, (size_t)c->max_batch * 12 * sizeof(float)));
+        if (needs_depth(c)) HIP_TRY(c, hipMalloc(&c->s_depth, depth_bytes(c) * c->max_batch));
     }
     if (!c->copy_stream) HIP_TRY(c, hipStreamCreateWithFlags(&c->copy_stream, hipStreamNonBlocking));
     { int rc = judge_all(c); if (rc) return rc; }               // device-path batches issued before this call
@@ -703,6 +750,8 @@ int davo_forward(davo_ctx* c, int B, const uint8_t* img, const float* flow, cons
         if (nb == 1) HIP_TRY(c, hipMemcpyAsync(df, (const uint8_t*)flow + nb_flow * b0, nb_flow / 2, hipMemcpyHostToDevice, cs));
         else HIP_TRY(c, hipMemcpy2DAsync(df, nb_flow, (const uint8_t*)flow + nb_flow * b0, nb_flow, nb_flow / 2, nb, hipMemcpyHostToDevice, cs));
         HIP_TRY(c, hipMemcpyAsync(ds, (const uint8_t*)seg + nb_seg * b0, nb_seg * nb, hipMemcpyHostToDevice, cs));
+        uint8_t* dd = depth ? (uint8_t*)c->s_depth + nb_seg * b0 : nullptr;          // depth planes: the label maps' size
+        if (depth) HIP_TRY(c, hipMemcpyAsync(dd, (const uint8_t*)depth + nb_seg * b0, nb_seg * nb, hipMemcpyHostToDevice, cs));
         if (nchunks > 1) {
             HIP_TRY(c, hipEventRecord(c->copy_done[i], c->copy_stream));
             HIP_TRY(c, hipStreamWaitEvent(c->stream, c->copy_done[i], 0));
@@ -713,7 +762,7 @@ int davo_forward(davo_ctx* c, int B, const uint8_t* img, const float* flow, cons
             c->snap = SnapArgs{};
             c->snap.record = c->d_range_base; c->snap.host_mirror = c->h_range_dev; c->snap.seq = seq; c->snap.B = nb;
         }
-        int rc = forward_device(c, nb, di, (const float*)df, (const float*)ds, (float*)c->s_pose + (size_t)b0 * 12);
+        int rc = forward_device(c, nb, di, (const float*)df, (const float*)ds, dd, (float*)c->s_pose + (size_t)b0 * 12);
         c->snap = SnapArgs{};
         if (rc) return rc;
         f32_fallback |= c->f32_fallback;
@@ -732,10 +781,18 @@ int davo_forward(davo_ctx* c, int B, const uint8_t* img, const float* flow, cons
     if (rc == DAVO_OK) note_seen(c, raw, c->act_shift);
     if (rc == DAVO_ERR_RANGE && c->opt_auto_range) {
         // the staged copy of the batch is still in HBM: re-issue it whole (recalibrated, or on the float32 kernels)
-        rc = recover_batch(c, [&] { Ticket t{}; t.B = B; t.img = c->s_img; t.flow = c->s_flow; t.seg = c->s_seg; t.pose = c->s_pose; t.ring = -1; t.stream = c->stream; t.issue = ~0ull; return t; }());
+        rc = recover_batch(c, [&] { Ticket t{}; t.B = B; t.img = c->s_img; t.flow = c->s_flow; t.seg = c->s_seg; t.depth = depth ? c->s_depth : nullptr; t.pose = c->s_pose; t.ring = -1; t.stream = c->stream; t.issue = ~0ull; return t; }());
         if (rc == DAVO_OK) HIP_TRY(c, hipMemcpy(pose_out, c->s_pose, (size_t)B * 12 * sizeof(float), hipMemcpyDeviceToHost));
     }
     return rc;
+}
+
+int davo_forward(davo_ctx* c, int B, const uint8_t* img, const float* flow, const float* seg, float* pose_out) {
+    return forward_entry(c, B, img, flow, seg, nullptr, pose_out, false);
+}
+
+int davo_forward_depth(davo_ctx* c, int B, const uint8_t* img, const float* flow, const float* seg, const float* depth, float* pose_out) {
+    return forward_entry(c, B, img, flow, seg, depth, pose_out, true);
 }
 
 int davo_range_stats(davo_ctx* c, long long* recalibrations, long long* f32_batches, long long* reissued) {
@@ -773,20 +830,31 @@ int davo_set_activation_shifts(davo_ctx* c, const int* shifts) {
     return DAVO_OK;
 }
 
-int davo_calibrate(davo_ctx* c, int B, const void* d_img, const void* d_flow, const void* d_seg, int* shifts_out) {
+// the body of davo_calibrate / davo_calibrate_depth (depth_form)
+static int calibrate_entry(davo_ctx* c, int B, const void* d_img, const void* d_flow, const void* d_seg, const void* d_depth, int* shifts_out,
+                           bool depth_form) {
     if (!c) return DAVO_ERR_INVALID;
     if (B < 1 || B > c->max_batch) return fail(c, DAVO_ERR_INVALID, "batch %d outside [1,%d]", B, c->max_batch);
     if (!d_img || !d_flow || !d_seg) return fail(c, DAVO_ERR_INVALID, "null device pointer");
+    { int rc = resolve_depth(c, "davo_calibrate", depth_form, &d_depth); if (rc) return rc; }
     HIP_TRY(c, hipSetDevice(c->device));
     { int rc = judge_all(c); if (rc) return rc; }             // batches issued under the old scales get their verdict first
     { int rc = freeze_pending_and_reset_ring(c); if (rc) return rc; }
     activate_slot(c, 0);
     float* d_pose = nullptr;
     HIP_TRY(c, hipMalloc(reinterpret_cast<void**>(&d_pose), (size_t)B * 12 * sizeof(float)));
-    const int rc = calibrate_on(c, B, d_img, d_flow, d_seg, d_pose);
+    const int rc = calibrate_on(c, B, d_img, d_flow, d_seg, d_depth, d_pose);
     (void)hipFree(d_pose);
     if (rc == DAVO_OK && shifts_out) for (int i = 0; i < 6; ++i) shifts_out[i] = c->act_shift[i];
     return rc;
+}
+
+int davo_calibrate(davo_ctx* c, int B, const void* d_img, const void* d_flow, const void* d_seg, int* shifts_out) {
+    return calibrate_entry(c, B, d_img, d_flow, d_seg, nullptr, shifts_out, false);
+}
+
+int davo_calibrate_depth(davo_ctx* c, int B, const void* d_img, const void* d_flow, const void* d_seg, const void* d_depth, int* shifts_out) {
+    return calibrate_entry(c, B, d_img, d_flow, d_seg, d_depth, shifts_out, true);
 }
 
 const char* davo_last_error(const davo_ctx* c) { return c ? c->err.c_str() : "null context"; }
@@ -806,7 +874,12 @@ void davo_destroy(davo_ctx* c) {
     for (auto e : c->copy_done) (void)hipEventDestroy(e);
     if (c->copy_stream) { (void)hipStreamSynchronize(c->copy_stream); (void)hipStreamDestroy(c->copy_stream); }
     for (int k = 0; k < STREAM_SETS; ++k)
-        for (void* q : {c->st_img[k], c->st_flow[k], c->st_seg[k]}) if (q) (void)hipFree(q);
+        for (void* q : {c->st_img[k], c->st_flow[k], c->st_seg[k], c->st_depth[k]}) if (q) (void)hipFree(q);
+    // the range-recovery ring: the input snapshots (depth planes included), the records' host mirror and the stream that reads them
+    for (int r = 0; r < RANGE_RING; ++r)
+        for (void* q : {c->snap_img[r], c->snap_flow[r], c->snap_seg[r], c->snap_depth[r]}) if (q) (void)hipFree(q);
+    if (c->read_stream) { (void)hipStreamSynchronize(c->read_stream); (void)hipStreamDestroy(c->read_stream); }
+    if (c->h_range) (void)hipHostFree(c->h_range);
     for (int k = 0; k < STREAM_POSES; ++k) {
         if (c->d_pose_ring[k]) (void)hipFree(c->d_pose_ring[k]);
         if (c->h_pose_ring[k]) (void)hipHostFree(c->h_pose_ring[k]);
@@ -814,7 +887,7 @@ void davo_destroy(davo_ctx* c) {
         if (c->st_copied[k]) (void)hipEventDestroy(c->st_copied[k]);
     }
     if (c->h_sync_pose) (void)hipHostFree(c->h_sync_pose);
-    void* misc[] = {c->d_reissue_pose, c->d_range_base, c->d_splitk, c->d_pose_tiles, c->d_w1patch, c->d_w2patch, c->d_w3patch, c->d_w1patch_f32, c->d_w2patch_f32, c->d_w3patch_f32, c->d_zeros, c->d_wpred, c->d_bpred, c->s_img, c->s_flow, c->s_seg, c->s_pose};
+    void* misc[] = {c->d_reissue_pose, c->d_range_base, c->d_splitk, c->d_pose_tiles, c->d_w1patch, c->d_w2patch, c->d_w3patch, c->d_w1patch_f32, c->d_w2patch_f32, c->d_w3patch_f32, c->d_zeros, c->d_wpred, c->d_bpred, c->s_img, c->s_flow, c->s_seg, c->s_depth, c->s_pose};
     for (auto p : misc) if (p) (void)hipFree(p);
     for (auto& kv : c->tile_orders) if (kv.second) (void)hipFree(kv.second);
     for (auto& pe : c->prof_entries)

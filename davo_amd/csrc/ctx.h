@@ -76,6 +76,7 @@ constexpr int SK_TILE_COUNTERS = 256;            // tiles of a split-K launch wh
 struct Ticket {
     int B;
     const void *img, *flow, *seg;              // what a re-issue reads: the ring slot's snapshot, or the caller's buffers ("stable_inputs")
+    const void* depth;                         // ... and the depth planes of a depth-source variant (else null)
     void* pose;
     int ring;
     bool snap;                                 // img / flow / seg are the ring slot's copy
@@ -174,6 +175,7 @@ struct davo_ctx {
     int last_plan[7][2] = {};                  // per layer, per launch: 128-row M tiles * 1000 + tile id / BN (reported by the bench)
     // host-API staging
     void *s_img = nullptr, *s_flow = nullptr, *s_seg = nullptr, *s_pose = nullptr;
+    void* s_depth = nullptr;                   // depth-source variants only
     float* h_sync_pose = nullptr;              // davo_forward: page-locked bounce buffer of the poses
     hipStream_t copy_stream = nullptr;         // H2D of the next sub-batch runs here while the previous one computes
     std::vector<hipEvent_t> copy_done;
@@ -192,6 +194,7 @@ struct davo_ctx {
     bool ring_busy[davo::RANGE_RING] = {};
     int ring_next = 0;
     void *snap_img[davo::RANGE_RING] = {}, *snap_flow[davo::RANGE_RING] = {}, *snap_seg[davo::RANGE_RING] = {};
+    void* snap_depth[davo::RANGE_RING] = {};   // depth-source variants only: the depth planes travel with the other three
     davo::SnapArgs snap{};                     // set around a ticketed batch: its last kernel copies the inputs if the record fails (prologue.h)
     hipStream_t read_stream = nullptr;
     unsigned batch_seq = 0, snap_seq_issued = 0;   // sequence number of the last ticketed batch (never 0 for a batch)
@@ -206,6 +209,7 @@ struct davo_ctx {
     int host_chunk = 8;                        // davo_forward: windows per sub-batch (davo_set_option "host_chunk"; 0 = whole batch)
     // streaming host entry (davo_submit / davo_wait): staging input sets, pose ring, undelivered batches in issue order
     void *st_img[davo::STREAM_SETS] = {}, *st_flow[davo::STREAM_SETS] = {}, *st_seg[davo::STREAM_SETS] = {};     // one staging set per in-flight slot
+    void* st_depth[davo::STREAM_SETS] = {};    // ... with the depth planes for a depth-source variant
     hipEvent_t st_copied[davo::STREAM_POSES] = {};             // "the H2D copies of the batch in pose ring entry k are done" (recorded only for hold < STREAM_POSES)
     bool copy_tracked[davo::STREAM_POSES] = {};
     float *d_pose_ring[davo::STREAM_POSES] = {}, *h_pose_ring[davo::STREAM_POSES] = {};
@@ -302,7 +306,9 @@ inline void split_f16(float v, _Float16* hi, _Float16* lo) {
 
 // ---- forward.hip ----------------------------------------------------------------------------
 void activate_slot(davo_ctx* c, int i);
-int forward_device(davo_ctx* c, int B, const void* d_img, const void* d_flow, const void* d_seg, void* d_pose);
+// d_depth: [B][3][H][W] float32 depth planes in file order (src0, tgt, src1), read by the depth sources only (att_source 11, 12;
+// null otherwise)
+int forward_device(davo_ctx* c, int B, const void* d_img, const void* d_flow, const void* d_seg, const void* d_depth, void* d_pose);
 // f16x3: verdict on the range record (d_range) read back from the device; DAVO_ERR_RANGE names the layer
 int check_range(davo_ctx* c, const unsigned* raw /*[RANGE_WORDS]*/, const int* shifts = nullptr);
 

@@ -599,9 +599,11 @@ int run_direct(davo_ctx* c, const char* label, const float* x, int N, int Hin, i
 
 }  // namespace
 
-int forward_device(davo_ctx* c, int B, const void* d_img, const void* d_flow, const void* d_seg, void* d_pose) {
+int forward_device(davo_ctx* c, int B, const void* d_img, const void* d_flow, const void* d_seg, const void* d_depth, void* d_pose) {
     if (B < 1 || B > c->max_batch) return fail(c, DAVO_ERR_INVALID, "batch %d outside [1,%d]", B, c->max_batch);
     if (!d_img || !d_flow || !d_seg || !d_pose) return fail(c, DAVO_ERR_INVALID, "null device pointer");
+    if (att_desc_depth(c->v.att_source) && (!d_depth || ((uintptr_t)d_depth & 15)))
+        return fail(c, DAVO_ERR_INVALID, "this variant reads depth planes: a 16-byte aligned device pointer is required");
     {
         std::string names;
         if (missing_weights(c, &names)) return fail(c, DAVO_ERR_NOT_READY, "weights not loaded: %s", names.c_str());
@@ -647,7 +649,12 @@ int forward_device(davo_ctx* c, int B, const void* d_img, const void* d_flow, co
     const float* se_b1 = wdev(se_weight_name(v.att_source, 1));
     const float* se_w2 = wdev(se_weight_name(v.att_source, 2));
     const float* se_b2 = wdev(se_weight_name(v.att_source, 3));
-    if (class_table) {
+    if (att_desc_depth(v.att_source)) {
+        // depth sources: one float32 sum per depth plane and chunk, then (or, folded, in the same launch) the excitation
+        ProfScope ps(c, "se_depth_squeeze");
+        HIP_TRY(c, launch_se_depth_squeeze(fold_excite, static_cast<const float*>(d_depth), B, HW, v, reinterpret_cast<unsigned*>(c->d_partial),
+                                           c->d_counters + 1, se_w1, se_b1, se_w2, se_b2, c->d_tab, range_reset, s));
+    } else if (class_table) {
         // segmentation / rgb / seg+flow sources: per-frame histogram, byte or flow sums, then (or, folded, in the same launch) the
         // excitation
         ProfScope ps(c, "se_class_squeeze");

@@ -51,11 +51,16 @@ hipError_t xcd_round_robin_probe(hipStream_t s, int* ok);
 hipError_t launch_se_squeeze_excite(const float* d_flow, int B, int HW, const Variant& v, float* d_partial, unsigned* d_counters,
                                     const float* w1, const float* b1, const float* w2, const float* b2, const float* wstatic,
                                     float* d_tab, unsigned* d_range_reset, hipStream_t s);
-// class-table sources (att_source 4..10): per-frame descriptor records into d_partial (max_batch x 3 x SQ_CHUNKS x SQ_REC words);
+// segmentation / rgb / seg+flow class-table sources (att_source 4..10): per-frame descriptor records into d_partial (max_batch x 3 x SQ_CHUNKS x SQ_REC words);
 // fold: the triplet's last workgroup evaluates its tables too (d_counters as above), otherwise launch_se_excite follows
 hipError_t launch_se_class_squeeze(bool fold, const uint8_t* d_img, const float* d_flow, const float* d_seg, int B, int H, int W,
                                   const Variant& v, unsigned* d_partial, unsigned* d_counters, const float* w1, const float* b1,
                                   const float* w2, const float* b2, float* d_tab, unsigned* d_range_reset, hipStream_t s);
+// depth sources (att_source 11, 12): one float32 sum per (triplet, frame, chunk) into word 0 of the same records; d_depth is
+// [B][3][H][W] float32 in file order (src0, tgt, src1), 16-byte aligned; fold as above
+hipError_t launch_se_depth_squeeze(bool fold, const float* d_depth, int B, int HW, const Variant& v, unsigned* d_partial,
+                                   unsigned* d_counters, const float* w1, const float* b1, const float* w2, const float* b2,
+                                   float* d_tab, unsigned* d_range_reset, hipStream_t s);
 // ld: 16 = split-fp16 8-channel layout (f16x3), 8 = float32 8-channel, 10 = the reference's 10-channel layout
 hipError_t launch_mask_pack(int ld, const uint8_t* d_img, const float* d_flow, const float* d_seg, const float* d_tab,
                             const Variant& v, int B, int H, int W, float* d_packed, hipStream_t s);

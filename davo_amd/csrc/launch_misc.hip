@@ -57,6 +57,20 @@ hipError_t launch_se_class_squeeze(bool fold, const uint8_t* d_img, const float*
     return hipGetLastError();
 }
 
+hipError_t launch_se_depth_squeeze(bool fold, const float* d_depth, int B, int HW, const Variant& v, unsigned* d_partial,
+                                   unsigned* d_counters, const float* w1, const float* b1, const float* w2, const float* b2,
+                                   float* d_tab, unsigned* d_range_reset, hipStream_t s) {
+    if (!att_desc_depth(v.att_source) || !d_depth || HW % 16) return hipErrorInvalidValue;
+    const dim3 grid(SQ_CHUNKS, 3, B);
+    if (fold)
+        hipLaunchKernelGGL(se_depth_squeeze<true>, grid, dim3(256), 0, s, d_depth, HW, v, d_partial, d_counters, w1, b1, w2, b2, d_tab,
+                           d_range_reset);
+    else
+        hipLaunchKernelGGL(se_depth_squeeze<false>, grid, dim3(256), 0, s, d_depth, HW, v, d_partial, d_counters, w1, b1, w2, b2, d_tab,
+                           d_range_reset);
+    return hipGetLastError();
+}
+
 hipError_t launch_mask_pack(int ld, const uint8_t* d_img, const float* d_flow, const float* d_seg, const float* d_tab,
                             const Variant& v, int B, int H, int W, float* d_packed, hipStream_t s) {
     const long nthreads = (long)2 * B * H * (W / 4);

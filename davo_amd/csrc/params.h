@@ -30,17 +30,21 @@ struct Variant {
 // ---- attention sources (davo_variant.att_source, include/davo_hip.h) ----------------------------------------------------------
 // 4..10 are the class-table SE sources (davo.py:1274-1292, 1304-1310, 1341-1374): a per-frame descriptor (label histogram,
 // rgb mean, or histogram + SE-transformed flow mean), two dense layers, a 19-class sigmoid table looked up per pixel.
-constexpr int SQ_REC = 24;          // class-table squeeze: words per (triplet, frame, chunk): 19 counts | 2 flow sums (or 3 rgb sums)
-__host__ __device__ inline bool att_class_table(int a) { return a >= 4 && a <= 10; }
+// 11, 12 are the depth-source class tables (davo.py:1109, 1211-1227): the descriptor is the mean of depth_frame + depth_tgt over
+// the frame (one value), dense 1 -> 8 -> 19; they read a fourth input, the depth planes.
+constexpr int SQ_REC = 24;          // class-table squeeze: words per (triplet, frame, chunk): 19 counts | 2 flow sums (or 3 rgb sums, or 1 depth sum)
+__host__ __device__ inline bool att_class_table(int a) { return a >= 4 && a <= 12; }
 // the target frame's rgb is masked by its own table (static_all and the with-target class-table sources)
-__host__ __device__ inline bool att_tgt_attended(int a) { return a == 3 || a == 6 || a == 8 || a == 10; }
-__host__ __device__ inline bool att_desc_hist(int a) { return a == 4 || a >= 7; }          // descriptor holds the label histogram
+__host__ __device__ inline bool att_tgt_attended(int a) { return a == 3 || a == 6 || a == 8 || a == 10 || a == 12; }
+__host__ __device__ inline bool att_desc_depth(int a) { return a == 11 || a == 12; }       // descriptor is the depth mean (needs the depth input)
+__host__ __device__ inline bool att_desc_hist(int a) { return a == 4 || (a >= 7 && a <= 10); }   // descriptor holds the label histogram
 __host__ __device__ inline bool att_desc_rgb(int a) { return a == 5 || a == 6; }           // ... the rgb mean
-__host__ __device__ inline bool att_desc_flow(int a) { return a >= 7; }                    // ... the transformed flow mean
-__host__ __device__ inline int att_se_in(int a) { return a == 1 ? 2 : att_desc_rgb(a) ? 3 : a == 4 ? NCLS : NCLS + 2; }
+__host__ __device__ inline bool att_desc_flow(int a) { return a >= 7 && a <= 10; }         // ... the transformed flow mean
+__host__ __device__ inline int att_se_in(int a) { return a == 1 ? 2 : att_desc_depth(a) ? 1 : att_desc_rgb(a) ? 3 : a == 4 ? NCLS : NCLS + 2; }
 __host__ __device__ inline int att_se_hidden(int a) { return (a == 4 || a == 7 || a == 8) ? NCLS : 8; }
-// frames (0 tgt, 1 src0, 2 src1) the squeeze covers: the target's table is ones for the `_wo_tgt' sources
-__host__ __device__ inline int att_se_frames(int a) { return att_tgt_attended(a) ? 3 : 2; }
+// frames (0 tgt, 1 src0, 2 src1) the squeeze covers: the target's table is ones for the `_wo_tgt' sources.  The depth sources sum
+// every plane once, the target's included: its sum enters both source frames' descriptors (davo.py:1109)
+__host__ __device__ inline int att_se_frames(int a) { return (att_tgt_attended(a) || att_desc_depth(a)) ? 3 : 2; }
 
 // ---- filter rows that only see padding ------------------------------------------------------
 // 3x3 layers: the filter rows ky that land inside the image for at least one output pixel of the flattened pixel range
@@ -325,6 +329,8 @@ struct SnapArgs {
     uint8_t *s_img, *s_flow, *s_seg;        // the ring slot's
     unsigned img_vec, flow_vec_half, flow_vec, seg_vec;      // per window, in 16-byte units: strip, flow planes 0-1, whole flow block, seg
     int B;
+    const uint8_t* depth;                   // depth sources only (else null): the caller's depth planes, seg_vec units per window ...
+    uint8_t* s_depth;                       // ... and the ring slot's copy of them
 };
 
 }  // namespace davo

@@ -1,6 +1,6 @@
 // prologue.h — the HBM-bound front of the pose path: SE squeeze, the 2->8->19 excitation
-// MLP (se_flow), the class-table squeeze / excitation of the segmentation, rgb and seg+flow
-// sources, and the mask + pack pass that builds the PoseNN input.
+// MLP (se_flow), the class-table squeeze / excitation of the segmentation, rgb, seg+flow and
+// depth sources, and the mask + pack pass that builds the PoseNN input.
 //
 // Reference (all under /root/reference): davo.py:1519-1522 (u8 -> f32 * (1/255) * 2 - 1),
 // data_loader.py:537-557 (strip = src0 | tgt | src1), davo.py:978-982 / 998-1004 (flow planes
@@ -70,10 +70,13 @@ __device__ __forceinline__ float se_flow_transform(float f, int c, const Variant
     return (v.abs_mode & (1 << c)) ? fabsf(f) : f;
 }
 
-// Class-table excitation (att_source 4..10), one wave: tab[b][frame][19].  The descriptor's element c is lane c's: the sum of word c
+// Class-table excitation (att_source 4..12), one wave: tab[b][frame][19].  The descriptor's element c is lane c's: the sum of word c
 // of the frame's SQ_CHUNKS squeeze records in chunk order (integers for the histogram and the rgb sums, so their order does not
 // matter at all; the flow sums in a fixed order), turned into the mean once.  Then one lane per bottleneck unit, its inputs
-// broadcast by shuffles, then one lane per class.  A `_wo_tgt' source's target table is ones (davo.py:1283,1310,1349,1366).
+// broadcast by shuffles, then one lane per class.  A `_wo_tgt' source's target table is ones (davo.py:1283,1310,1349,1366,1219).
+// Depth sources (11, 12): the one input is the mean of depth_frame + depth_tgt (davo.py:1109: `list + tensor' broadcasts the
+// target's depth onto every frame).  se_depth_squeeze sums each plane once; lane 0 adds the frame's SQ_CHUNKS records in chunk
+// order, lane 1 the target's, their sum is divided by H*W once.
 template <bool AGENT>
 __device__ __forceinline__ void se_class_excite_wave(const unsigned* __restrict__ partial, int HW, const Variant& v, int b, int frame,
                                                      int lane, const float* __restrict__ w1, const float* __restrict__ b1,
@@ -97,7 +100,14 @@ __device__ __forceinline__ void se_class_excite_wave(const unsigned* __restrict_
     const float b1j = b1[j], b2k = b2[k];
     const unsigned* rec = partial + ((size_t)b * 3 + frame) * SQ_CHUNKS * SQ_REC;
     float d = 0.f;
-    if (lane < nin) {
+    if (att_desc_depth(a)) {
+        float sum = 0.f;
+        if (lane < 2) {
+            const unsigned* q = partial + ((size_t)b * 3 + (lane == 0 ? frame : 0)) * SQ_CHUNKS * SQ_REC;
+            for (int ch = 0; ch < SQ_CHUNKS; ++ch) sum += __uint_as_float(AGENT ? agent_load_u32(q + ch * SQ_REC) : q[ch * SQ_REC]);
+        }
+        d = (__shfl(sum, 0, 64) + __shfl(sum, 1, 64)) * (1.0f / (float)HW);
+    } else if (lane < nin) {
         if (att_desc_flow(a) && lane >= NCLS) {
             const int c = lane - NCLS;
             if (frame == 0) {
@@ -352,6 +362,54 @@ __global__ __launch_bounds__(256) void se_class_squeeze(const uint8_t* __restric
     if (threadIdx.x == 0) __hip_atomic_store(counters + b, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
+// Depth-source SE squeeze (att_source 11, 12; davo.py:1109, 1211-1227): grid (SQ_CHUNKS, 3 frames, B), one workgroup per (chunk,
+// frame, triplet).  The SUMMED-PLANES form: each of the three depth planes is summed once (12 B per pixel and triplet) and the
+// excitation adds S_frame + S_tgt (se_class_excite_wave), instead of summing depth_frame + depth_tgt per pixel; the two differ by
+// float32 rounding only.  A thread takes four horizontally adjacent pixels (one 16-byte load) per step and adds them as
+// (x + y) + (z + w); then the fixed wave butterfly and a fixed tree over the four waves: one float32 word per record
+// (partial[b][frame][chunk][0]), bitwise the same run after run, no atomics on the sums.  depth is [B][3 file planes: src0, tgt,
+// src1][H][W] float32, 16-byte aligned; H*W is a multiple of 16.  FOLD: the workgroup that delivers the triplet's last record
+// evaluates its three tables (se_squeeze_excite's protocol, pose_tail.h).
+template <bool FOLD>
+__global__ __launch_bounds__(256) void se_depth_squeeze(const float* __restrict__ depth, int HW, Variant v,
+                                                        unsigned* __restrict__ partial, unsigned* __restrict__ counters,
+                                                        const float* __restrict__ w1, const float* __restrict__ b1,
+                                                        const float* __restrict__ w2, const float* __restrict__ b2,
+                                                        float* __restrict__ tab, unsigned* __restrict__ range_reset) {
+    const int chunk = blockIdx.x, frame = blockIdx.y, b = blockIdx.z;
+    if (FOLD && range_reset && chunk == 0 && frame == 0 && b == 0 && threadIdx.x == 0) range_reset[RANGE_SNAP] = 0u;   // as se_excite
+    const int plane = frame == 0 ? 1 : frame == 1 ? 0 : 2;     // (tgt, src0, src1) -> file order src0, tgt, src1 (davo.py:991-996)
+    const float4* dp = reinterpret_cast<const float4*>(depth + ((size_t)b * 3 + plane) * HW);
+    const int nunits = HW >> 2;
+    const int per = (nunits + SQ_CHUNKS - 1) / SQ_CHUNKS;
+    const int beg = chunk * per, end = min(beg + per, nunits);
+    float sum = 0.f;
+    for (int i = beg + threadIdx.x; i < end; i += 256) {
+        const float4 q = dp[i];
+        sum += (q.x + q.y) + (q.z + q.w);
+    }
+    __shared__ float red[4];
+    __shared__ unsigned ticket;
+    sum = wave_sum(sum);
+    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+    if (lane == 0) red[wid] = sum;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        unsigned* o = partial + (((size_t)b * 3 + frame) * SQ_CHUNKS + chunk) * SQ_REC;
+        const unsigned w = __float_as_uint((red[0] + red[1]) + (red[2] + red[3]));
+        if (FOLD) {
+            __hip_atomic_store(o, w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            agent_stores_done();
+        } else {
+            o[0] = w;
+        }
+    }
+    if (!FOLD) return;
+    if (!last_workgroup(counters + b, 3u * SQ_CHUNKS, &ticket)) return;
+    if (wid < 3) se_class_excite_wave<true>(partial, HW, v, b, wid, lane, w1, b1, w2, b2, tab);
+    if (threadIdx.x == 0) __hip_atomic_store(counters + b, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
 __device__ __forceinline__ float att_lookup(const float* tab19, float seg) {
     // tf.cast(float -> int32) truncates toward zero; one_hot of an out-of-range id is a zero row.  NaN / inf /
     // beyond-int32 labels are platform-defined in the cast (x86: INT_MIN, GPUs: 0 or saturation) and pinned to
@@ -576,6 +634,11 @@ __device__ __forceinline__ void snapshot_inputs_if_range_fails(const SnapArgs& a
     const size_t n_img = (size_t)a.img_vec * a.B, n_seg = (size_t)a.seg_vec * a.B, n_flow = (size_t)a.flow_vec_half * a.B;
     for (size_t i = worker; i < n_img; i += nworkers) di[i] = si[i];
     for (size_t i = worker; i < n_seg; i += nworkers) ds[i] = ss[i];
+    if (a.s_depth) {                                           // depth sources: the planes are as large as the label maps
+        const uint4* sd = reinterpret_cast<const uint4*>(a.depth);
+        uint4* dd = reinterpret_cast<uint4*>(a.s_depth);
+        for (size_t i = worker; i < n_seg; i += nworkers) dd[i] = sd[i];
+    }
     for (size_t i = worker; i < n_flow; i += nworkers) {
         const size_t b = i / a.flow_vec_half, o = i - b * a.flow_vec_half;
         df[b * a.flow_vec + o] = sf[b * a.flow_vec + o];

@@ -66,7 +66,7 @@ void pack_conv_weights(const float* w_tf, int KS, int cin_tf, int cout, const in
 
 // ---- weights ----------------------------------------------------------------------------
 const char* se_weight_name(int att_source, int k) {
-    static const char* const names[4][4] = {
+    static const char* const names[5][4] = {
         {"pose_exp_net/se_flow/bottleneck_fc/kernel", "pose_exp_net/se_flow/bottleneck_fc/bias",
          "pose_exp_net/se_flow/recover_fc/kernel", "pose_exp_net/se_flow/recover_fc/bias"},
         {"pose_exp_net/se_seg/bottleneck_fc/kernel", "pose_exp_net/se_seg/bottleneck_fc/bias",              // davo.py:1304-1310
@@ -74,13 +74,15 @@ const char* se_weight_name(int att_source, int k) {
         {"pose_exp_net/se_rgb/bottleneck_fc/kernel", "pose_exp_net/se_rgb/bottleneck_fc/bias",              // :1274-1292
          "pose_exp_net/se_rgb/recover_fc/kernel", "pose_exp_net/se_rgb/recover_fc/bias"},
         {"pose_exp_net/se_segflow/bottleneck_fc/kernel", "pose_exp_net/se_segflow/bottleneck_fc/bias",      // :1341-1374
-         "pose_exp_net/se_segflow/recover_fc/kernel", "pose_exp_net/se_segflow/recover_fc/bias"}};
-    const int scope = att_source == 4 ? 1 : att_desc_rgb(att_source) ? 2 : att_source >= 7 ? 3 : 0;
+         "pose_exp_net/se_segflow/recover_fc/kernel", "pose_exp_net/se_segflow/recover_fc/bias"},
+        {"pose_exp_net/se_depth/bottleneck_fc/kernel", "pose_exp_net/se_depth/bottleneck_fc/bias",          // :1211-1227
+         "pose_exp_net/se_depth/recover_fc/kernel", "pose_exp_net/se_depth/recover_fc/bias"}};
+    const int scope = att_source == 4 ? 1 : att_desc_rgb(att_source) ? 2 : att_desc_depth(att_source) ? 4 : att_source >= 7 ? 3 : 0;
     return names[scope][k & 3];
 }
 
 bool is_dense_weight(const std::string& nm) {
-    for (const char* s : {"/se_flow/", "/se_seg/", "/se_rgb/", "/se_segflow/", "seg_channel_weight"})
+    for (const char* s : {"/se_flow/", "/se_seg/", "/se_rgb/", "/se_segflow/", "/se_depth/", "seg_channel_weight"})
         if (nm.find(s) != std::string::npos) return true;
     return false;
 }
@@ -136,7 +138,7 @@ bool expected_shape(const davo_ctx* c, const std::string& name, std::vector<int6
     else if (is("pose_exp_net/se_flow/recover_fc/bias")) *sh = {NCLS};
     else if (is("pose_exp_net/pose_exp_net/seg_channel_weight/weight")) *sh = {NCLS};
     else if (att_class_table(c->v.att_source) && name.compare(0, 16, "pose_exp_net/se_") == 0) {
-        // the class-table sources' scope (se_seg / se_rgb / se_segflow): [in, hidden] -> [hidden, 19]
+        // the class-table sources' scope (se_seg / se_rgb / se_segflow / se_depth): [in, hidden] -> [hidden, 19]
         const int a = c->v.att_source, nin = att_se_in(a), nh = att_se_hidden(a);
         if (name == se_weight_name(a, 0)) *sh = {nin, nh};
         else if (name == se_weight_name(a, 1)) *sh = {nh};

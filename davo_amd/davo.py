@@ -3,7 +3,7 @@
 Mirrors ``DAVO.__init__`` (reference davo.py:31-33), ``setup_inference`` (davo.py:1533-1551)
 and ``inference`` (davo.py:1553-1569).  The TF reference takes tensors of a tf.data iterator
 and pulls the next batch inside ``sess.run``; here the inputs are numpy arrays, or an iterator
-yielding ``(img_u8, flow, seg)`` batches, pulled once per ``inference`` call.  Weights enter
+yielding ``(img_u8, flow, seg)`` batches (``(img_u8, flow, seg, depth)`` for a depth-source variant), pulled once per ``inference`` call.  Weights enter
 through ``load_weights`` — the stand-in for ``tf.train.Saver(...).restore``
 (test_kitti_pose.py:129-131) — keyed by the TF variable names.
 """
@@ -131,21 +131,33 @@ class Engine:
             shape = (ctypes.c_int64 * a.ndim)(*a.shape)
             self._check(self._L.davo_load_weight(self._ctx, name.encode(), a.ctypes.data_as(ctypes.POINTER(ctypes.c_float)), shape, a.ndim))
 
-    def forward(self, img, flow, seg):
+    def _depth_arg(self, depth, B):
+        """The depth planes of a batch as the `_depth' entry points take them ([B,3,H,W,1] float32, file order src0, tgt,
+        src1: davo.py:991-996), or None for a variant that reads none (a depth array handed to such a variant is ignored,
+        as the reference ignores its depth input there)."""
+        if not self.cfg.needs_depth:
+            return None
+        if depth is None:
+            raise ValueError("image, flow, seglabel and depth inputs are all required for version `%s'" % self.cfg.version)
+        depth = np.ascontiguousarray(depth, np.float32)
+        if depth.shape != (B, 3, self.H, self.W, 1):
+            raise ValueError("depth shape %s != %s" % (depth.shape, (B, 3, self.H, self.W, 1)))
+        return depth
+
+    def forward(self, img, flow, seg, depth=None):
         img = np.ascontiguousarray(img, np.uint8)
         flow = np.ascontiguousarray(flow, np.float32)
         seg = np.ascontiguousarray(seg, np.float32)
-        B = img.shape[0]
-        if img.shape != (B, self.H, 3 * self.W, 3):
-            raise ValueError("img shape %s != %s" % (img.shape, (B, self.H, 3 * self.W, 3)))
-        if flow.shape != (B, 4, self.H, self.W, 2):
-            raise ValueError("flow shape %s != %s" % (flow.shape, (B, 4, self.H, self.W, 2)))
-        if seg.shape != (B, 3, self.H, self.W, 1):
-            raise ValueError("seg shape %s != %s" % (seg.shape, (B, 3, self.H, self.W, 1)))
+        B = self._check_batch(img, flow, seg)
+        depth = self._depth_arg(depth, B)
         out = np.empty((B, 2, 6), np.float32)
         vp = ctypes.c_void_p
-        self._check(self._L.davo_forward(self._ctx, B, img.ctypes.data_as(vp), flow.ctypes.data_as(vp),
-                                         seg.ctypes.data_as(vp), out.ctypes.data_as(vp)))
+        if depth is not None:
+            self._check(self._L.davo_forward_depth(self._ctx, B, img.ctypes.data_as(vp), flow.ctypes.data_as(vp),
+                                                   seg.ctypes.data_as(vp), depth.ctypes.data_as(vp), out.ctypes.data_as(vp)))
+        else:
+            self._check(self._L.davo_forward(self._ctx, B, img.ctypes.data_as(vp), flow.ctypes.data_as(vp),
+                                             seg.ctypes.data_as(vp), out.ctypes.data_as(vp)))
         return out
 
     def _check_batch(self, img, flow, seg):
@@ -158,10 +170,11 @@ class Engine:
             raise ValueError("seg shape %s != %s" % (seg.shape, (B, 3, self.H, self.W, 1)))
         return B
 
-    def submit(self, img, flow, seg, out, hold=0):
+    def submit(self, img, flow, seg, out, hold=0, depth=None):
         """Streaming form of forward (include/davo_hip.h: davo_submit): issue the batch and return; ``out`` - a C-contiguous
         float32 [B,2,6] array the caller keeps alive - receives the poses when the batch is delivered (a later submit, wait()
-        or synchronize()).  On return the input arrays of the batch submitted ``hold`` calls ago may be overwritten."""
+        or synchronize()).  On return the input arrays of the batch submitted ``hold`` calls ago may be overwritten.
+        ``depth``: the depth planes of a depth-source variant (davo_submit_depth), held like the other inputs."""
         if not (isinstance(img, np.ndarray) and img.dtype == np.uint8 and img.flags.c_contiguous and
                 isinstance(flow, np.ndarray) and flow.dtype == np.float32 and flow.flags.c_contiguous and
                 isinstance(seg, np.ndarray) and seg.dtype == np.float32 and seg.flags.c_contiguous):
@@ -171,11 +184,18 @@ class Engine:
             flow = np.ascontiguousarray(flow, np.float32)
             seg = np.ascontiguousarray(seg, np.float32)
         B = self._check_batch(img, flow, seg)
+        if self.cfg.needs_depth and hold and not (isinstance(depth, np.ndarray) and depth.dtype == np.float32 and depth.flags.c_contiguous):
+            raise ValueError("submit(hold > 0) needs a C-contiguous float32 depth array (a converted copy would not outlive the call)")
+        depth = self._depth_arg(depth, B)
         if not (isinstance(out, np.ndarray) and out.dtype == np.float32 and out.flags.c_contiguous and out.shape == (B, 2, 6)):
             raise ValueError("out must be a C-contiguous float32 array of shape (%d, 2, 6)" % B)
         vp = ctypes.c_void_p
-        self._check(self._L.davo_submit(self._ctx, B, img.ctypes.data_as(vp), flow.ctypes.data_as(vp), seg.ctypes.data_as(vp),
-                                        out.ctypes.data_as(vp), int(hold)))
+        if depth is not None:
+            self._check(self._L.davo_submit_depth(self._ctx, B, img.ctypes.data_as(vp), flow.ctypes.data_as(vp), seg.ctypes.data_as(vp),
+                                                  depth.ctypes.data_as(vp), out.ctypes.data_as(vp), int(hold)))
+        else:
+            self._check(self._L.davo_submit(self._ctx, B, img.ctypes.data_as(vp), flow.ctypes.data_as(vp), seg.ctypes.data_as(vp),
+                                            out.ctypes.data_as(vp), int(hold)))
 
     def wait(self, leave_pending=0):
         """Deliver submitted batches until at most ``leave_pending`` are outstanding (include/davo_hip.h: davo_wait)."""
@@ -186,19 +206,23 @@ class Engine:
 
     LAYERS = ("cnv1", "cnv2", "cnv3", "cnv4", "cnv5", "cnv6")
 
-    def calibrate(self, img, flow, seg):
+    def calibrate(self, img, flow, seg, depth=None):
         """Choose the power-of-two storage scales of the f16x3 activations from a sample batch
-        (include/davo_hip.h: davo_calibrate).  -> {layer: log2 scale}."""
+        (include/davo_hip.h: davo_calibrate; davo_calibrate_depth for a depth-source variant).  -> {layer: log2 scale}."""
         img = np.ascontiguousarray(img, np.uint8)
         flow = np.ascontiguousarray(flow, np.float32)
         seg = np.ascontiguousarray(seg, np.float32)
         B = img.shape[0]
         if img.shape != (B, self.H, 3 * self.W, 3) or flow.shape != (B, 4, self.H, self.W, 2) or seg.shape != (B, 3, self.H, self.W, 1):
             raise ValueError("calibration batch shapes %s %s %s do not match the engine" % (img.shape, flow.shape, seg.shape))
-        bufs = [self.alloc(a.nbytes).upload(a) for a in (img, flow, seg)]
+        depth = self._depth_arg(depth, B)
+        bufs = [self.alloc(a.nbytes).upload(a) for a in (img, flow, seg) + (() if depth is None else (depth,))]
         shifts = (ctypes.c_int * 6)()
         try:
-            self._check(self._L.davo_calibrate(self._ctx, B, bufs[0].ptr, bufs[1].ptr, bufs[2].ptr, shifts))
+            if depth is not None:
+                self._check(self._L.davo_calibrate_depth(self._ctx, B, bufs[0].ptr, bufs[1].ptr, bufs[2].ptr, bufs[3].ptr, shifts))
+            else:
+                self._check(self._L.davo_calibrate(self._ctx, B, bufs[0].ptr, bufs[1].ptr, bufs[2].ptr, shifts))
         finally:
             for b in bufs:
                 b.free()
@@ -230,10 +254,17 @@ class Engine:
         vals = [shifts[k] for k in self.LAYERS] if isinstance(shifts, dict) else list(shifts)
         self._check(self._L.davo_set_activation_shifts(self._ctx, (ctypes.c_int * 6)(*vals)))
 
-    def forward_device(self, B, d_img, d_flow, d_seg, d_pose, timed=False):
+    def forward_device(self, B, d_img, d_flow, d_seg, d_pose, timed=False, depth=None):
+        """``depth``: the DeviceBuffer of the depth planes, required by a depth-source variant (davo_forward_device_depth)."""
         ms = ctypes.c_float(0.0)
-        self._check(self._L.davo_forward_device(self._ctx, B, d_img.ptr, d_flow.ptr, d_seg.ptr, d_pose.ptr,
-                                                ctypes.byref(ms) if timed else None))
+        if self.cfg.needs_depth:
+            if depth is None:
+                raise ValueError("image, flow, seglabel and depth inputs are all required for version `%s'" % self.cfg.version)
+            self._check(self._L.davo_forward_device_depth(self._ctx, B, d_img.ptr, d_flow.ptr, d_seg.ptr, depth.ptr, d_pose.ptr,
+                                                          ctypes.byref(ms) if timed else None))
+        else:
+            self._check(self._L.davo_forward_device(self._ctx, B, d_img.ptr, d_flow.ptr, d_seg.ptr, d_pose.ptr,
+                                                    ctypes.byref(ms) if timed else None))
         return ms.value if timed else None
 
     def alloc(self, nbytes):
@@ -335,9 +366,9 @@ class DAVO(object):
                         input_img_uint8=None, input_pose=None, input_flow=None, input_depth=None,
                         input_seglabel=None):
         """davo.py:1533-1551.  ``input_*`` are numpy arrays ([B,H,3W,3] u8, [B,4,H,W,2] f32,
-        [B,3,H,W,1] f32) or ``input_img_uint8`` is an iterator yielding (img, flow, seg);
-        ``input_pose`` / ``input_depth`` are accepted and ignored like the reference does for
-        this variant."""
+        [B,3,H,W,1] f32) or ``input_img_uint8`` is an iterator yielding (img, flow, seg) - (img, flow, seg, depth)
+        for a depth-source variant; ``input_depth`` ([B,3,H,W,1] f32, file order src0, tgt, src1: davo.py:991-996) is
+        kept for such a variant and ignored otherwise, ``input_pose`` is accepted and ignored, like the reference does."""
         self.img_height, self.img_width, self.mode, self.batch_size = img_height, img_width, mode, batch_size
         if self.mode != 'davo':
             return                                        # davo.py:1548: other modes do nothing
@@ -357,7 +388,7 @@ class DAVO(object):
             # already copied and running (two in flight on the GPU)
             self.engine.set_inflight(2)
         else:
-            self._inputs = (input_img_uint8, input_flow, input_seglabel)
+            self._inputs = (input_img_uint8, input_flow, input_seglabel) + ((input_depth,) if self.cfg.needs_depth else ())
 
     def load_weights(self, weights):
         """Stand-in for tf.train.Saver(tf.trainable_variables()).restore (test_kitti_pose.py:129-131)."""
@@ -366,7 +397,7 @@ class DAVO(object):
             self.engine.load_weights(weights)
 
     def calibrate(self, inputs):
-        """Range-calibrate the f16x3 arithmetic on a sample batch (img, flow, seg); see Engine.calibrate.  Optional:
+        """Range-calibrate the f16x3 arithmetic on a sample batch (img, flow, seg[, depth]); see Engine.calibrate.  Optional:
         ``inference`` re-calibrates by itself on the first batch that leaves the range (the reference's float32
         graph has no counterpart and never fails, davo.py:1553-1569); calling it up front only saves that re-issue."""
         if self.engine is None:
@@ -381,13 +412,20 @@ class DAVO(object):
             raise DavoError("setup_inference(..., mode='davo') has not been called")
         if inputs is None and not isinstance(self._inputs, tuple):
             return {'pose': self._next_from_iterator()}
-        if inputs is not None:
-            img, flow, seg = inputs
-        else:
-            img, flow, seg = self._inputs
+        img, flow, seg, depth = self._split(inputs if inputs is not None else self._inputs)
         if img is None or flow is None or seg is None:
             raise ValueError("image, flow and seglabel inputs are all required for version `%s'" % self.version)
-        return {'pose': self.engine.forward(img, flow, seg)}
+        return {'pose': self.engine.forward(img, flow, seg, depth)}
+
+    def _split(self, inputs):
+        """(img, flow, seg) or, for a depth-source variant, (img, flow, seg, depth) -> the four, depth None without it."""
+        inputs = tuple(inputs)
+        if self.cfg.needs_depth:
+            if len(inputs) != 4 or inputs[3] is None:
+                raise ValueError("image, flow, seglabel and depth inputs are all required for version `%s'" % self.version)
+            return inputs
+        img, flow, seg = inputs[:3] if len(inputs) == 4 else inputs      # a fourth array is ignored like the reference's depth input
+        return img, flow, seg, None
 
     def _next_from_iterator(self):
         """Poses of the iterator's next batch; the batch after it is submitted before this one is waited for.  A batch the
@@ -396,9 +434,9 @@ class DAVO(object):
             item = next(self._inputs, None)
             if item is None:
                 break
-            img, flow, seg = item
+            img, flow, seg, depth = self._split(item)
             out = np.empty((np.shape(img)[0], 2, 6), np.float32)
-            self.engine.submit(img, flow, seg, out)             # hold = 0: the batch is copied when this returns
+            self.engine.submit(img, flow, seg, out, depth=depth)       # hold = 0: the batch is copied when this returns
             self._ahead.append(out)
         if not self._ahead:
             raise StopIteration("the input iterator is exhausted")      # tf.errors.OutOfRangeError's counterpart

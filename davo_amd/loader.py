@@ -9,6 +9,8 @@ sequence ``SS`` is
     <dump>/SS/FFFFFF.jpg              128 x 1248 RGB strip  src0 | tgt | src1
     <dump>/SS/FFFFFF-flownet2.npy     float32 (4, H, W, 2)
     <dump>/SS/FFFFFF-seglabel.npy     float32 (3, H, W, 1)   (file order src0, tgt, src1)
+    <dump>/SS/FFFFFF-monodepth2_depth.npy  float32 (3, H, W, 1)   (same order; read only for a depth-source variant:
+                                           test_kitti_pose.py:48,91, data_loader.py:271-274,500-501)
 
 ``ThreadedWindowLoader`` is the same pipeline with a thread pool and a bounded prefetch queue: batches
 come out in window order while the next ones are being decoded, so file IO overlaps the GPU.
@@ -29,8 +31,13 @@ def window_paths(dump_dir, seq, tgt_idx):
     return stem + ".jpg", stem + "-flownet2.npy", stem + "-seglabel.npy"
 
 
-def load_window(dump_dir, seq, tgt_idx, H, W):
-    """One window -> (img u8 [H,3W,3], flow f32 [4,H,W,2], seg f32 [3,H,W,1])."""
+def depth_path(dump_dir, seq, tgt_idx):
+    return os.path.join(dump_dir, "%.2d" % seq, "%.6d" % tgt_idx) + "-monodepth2_depth.npy"        # test_kitti_pose.py:48
+
+
+def load_window(dump_dir, seq, tgt_idx, H, W, depth=False):
+    """One window -> (img u8 [H,3W,3], flow f32 [4,H,W,2], seg f32 [3,H,W,1]); with ``depth`` also the depth planes
+    f32 [3,H,W,1] in file order, as a fourth element."""
     from PIL import Image
     jpg, flo, sg = window_paths(dump_dir, seq, tgt_idx)
     with Image.open(jpg) as im:
@@ -40,6 +47,9 @@ def load_window(dump_dir, seq, tgt_idx, H, W):
     # memory-mapped: the one copy of these arrays is the worker's write into its slot of the batch buffer
     flow = np.load(flo, mmap_mode="r").astype(np.float32, copy=False).reshape(4, H, W, 2)
     seg = np.load(sg, mmap_mode="r").astype(np.float32, copy=False).reshape(3, H, W, 1)
+    if depth:
+        dep = np.load(depth_path(dump_dir, seq, tgt_idx), mmap_mode="r").astype(np.float32, copy=False).reshape(3, H, W, 1)
+        return img, flow, seg, dep
     return img, flow, seg
 
 
@@ -100,9 +110,10 @@ FLOW_PLANES_USED = (0, 1)           # davo.py:978-982: pred_flows = [0, flow[:,0
 SEG_PLANES_SOURCES = (0, 2)         # davo.py:998-1004 + 1408-1412: the target frame's attention is overwritten by ones
 
 
-def load_window_into(dump_dir, seq, tgt_idx, H, W, img, flow, seg, decoder=None, flow_planes=None, seg_planes=None):
+def load_window_into(dump_dir, seq, tgt_idx, H, W, img, flow, seg, decoder=None, flow_planes=None, seg_planes=None, depth=None):
     """load_window writing into the caller's [H,3W,3] / [4,H,W,2] / [3,H,W,1] slots; ``flow_planes`` / ``seg_planes``
-    restrict the .npy reads to the planes the variant consumes (None = all)."""
+    restrict the .npy reads to the planes the variant consumes (None = all).  ``depth``: a [3,H,W,1] slot for the depth planes
+    of a depth-source variant (all three are consumed: the target's depth enters every frame's descriptor, davo.py:1109)."""
     jpg, flo, sg = window_paths(dump_dir, seq, tgt_idx)
     if decoder is None:
         from PIL import Image
@@ -115,6 +126,8 @@ def load_window_into(dump_dir, seq, tgt_idx, H, W, img, flow, seg, decoder=None,
     img[...] = a
     _read_npy_into(flo, flow, flow_planes)
     _read_npy_into(sg, seg, seg_planes)
+    if depth is not None:
+        _read_npy_into(depth_path(dump_dir, seq, tgt_idx), depth)
 
 
 def count_frames(dump_dir, seq, seq_length=3):
@@ -154,10 +167,10 @@ class ThreadedWindowLoader:
 
         def fill(w, bufs, i, parts=None):              # runs in a pool thread: decode + the single copy into the batch
             if parts is None and self.load_into is not None:
-                self.load_into(w, bufs[0][i], bufs[1][i], bufs[2][i])
+                self.load_into(w, *(b[i] for b in bufs))
                 return
             parts = self.load_one(w) if parts is None else parts
-            for k in range(3):
+            for k in range(len(bufs)):                # three planes sets, four with depth
                 bufs[k][i] = parts[k]
 
         def producer():
@@ -292,7 +305,8 @@ def _slot_worker(k, P, names, ctrl_name, B, H, W, dump_dir, seq, flow_planes, se
             t = [shared_memory.SharedMemory(name=n) for n in trio]
             segs += t
             ring.append((np.ndarray((B, H, 3 * W, 3), np.uint8, buffer=t[0].buf), np.ndarray((B, 4, H, W, 2), np.float32, buffer=t[1].buf),
-                         np.ndarray((B, 3, H, W, 1), np.float32, buffer=t[2].buf)))
+                         np.ndarray((B, 3, H, W, 1), np.float32, buffer=t[2].buf)) +
+                        ((np.ndarray((B, 3, H, W, 1), np.float32, buffer=t[3].buf),) if len(t) == 4 else ()))     # a depth variant's fourth buffer
         cpb = -(-B // chunk)                               # chunks per batch (the last one of a batch may be short)
         nbatches = -(-(hi - lo) // B)
         for c in range(nbatches * cpb):
@@ -309,10 +323,12 @@ def _slot_worker(k, P, names, ctrl_name, B, H, W, dump_dir, seq, flow_planes, se
                 if ctrl[1]:
                     return
                 t0 = time.perf_counter_ns()
-                img, flow, seg = ring[bi % nring]
+                img, flow, seg = ring[bi % nring][:3]
+                dep = ring[bi % nring][3] if len(ring[bi % nring]) == 4 else None
                 for w in range(w0, w1):
                     i = w - lo - bi * B
-                    load_window_into(dump_dir, seq, w + 1, H, W, img[i], flow[i], seg[i], None, flow_planes, seg_planes)
+                    load_window_into(dump_dir, seq, w + 1, H, W, img[i], flow[i], seg[i], None, flow_planes, seg_planes,
+                                     depth=None if dep is None else dep[i])
                 ctrl[2 + P + k] += time.perf_counter_ns() - t0
             ctrl[2 + k] += 1
             sem.release()
@@ -356,14 +372,17 @@ class ProcessWindowLoader:
     ``pin(array)`` / ``unpin(array)`` page-lock the buffers for the H2D DMA (davo_amd.pin_array: hipHostRegister over the shared
     mapping).  Only the flow planes and label maps the variant consumes are read; the rest of a slot keeps its zeros.  Workers
     are forks of a warm fork server (worker_context): the parent may hold a HIP context, the server never does.
+    ``depth``: one more shared, page-locked buffer per ring place for the depth planes of a depth-source variant (all three are
+    read); batches are then (img, flow, seg, depth).
 
     A batch is valid until the consumer has asked for ``hold`` + 1 further ones (``hold`` = 0: until the next one); the last
     ones until ``close()`` (or the loader's deletion), which unpins and unmaps the buffers.  The end of iteration stops the
     workers and removes the segments' names."""
 
     def __init__(self, dump_dir, seq, H, W, lo, hi, batch_size, procs=8, prefetch=2, chunk=None, pin=None, unpin=None,
-                 flow_planes=FLOW_PLANES_USED, seg_planes=SEG_PLANES_SOURCES, shm_budget=None, hold=0):
+                 flow_planes=FLOW_PLANES_USED, seg_planes=SEG_PLANES_SOURCES, shm_budget=None, hold=0, depth=False):
         self.args = (dump_dir, seq, H, W)
+        self.depth = bool(depth)
         self.lo, self.hi, self.B = lo, hi, batch_size
         self.procs, self.prefetch, self.hold = max(1, procs), max(1, prefetch), max(0, hold)
         self.chunk = max(1, min(chunk or 4, batch_size))
@@ -371,7 +390,7 @@ class ProcessWindowLoader:
         self.fill = max(2, -(-3 * self.procs * self.chunk // batch_size))
         # the ring is sized in BYTES: prefetch + fill + 2 (+ hold) batch buffer trios if they fit the budget (shm_budget_bytes),
         # fewer batches in flight if not, and a clear error - the caller falls back to the threaded loader - if not even four fit
-        per_batch = batch_size * (H * 3 * W * 3 + 4 * H * W * 2 * 4 + 3 * H * W * 4)
+        per_batch = batch_size * (H * 3 * W * 3 + 4 * H * W * 2 * 4 + 3 * H * W * 4 + (3 * H * W * 4 if self.depth else 0))
         budget = shm_budget_bytes() if shm_budget is None else shm_budget
         want = self.prefetch + self.fill + 2 + self.hold
         self.nring = min(want, budget // per_batch)
@@ -396,13 +415,15 @@ class ProcessWindowLoader:
         from multiprocessing import shared_memory
         dump_dir, seq, H, W = self.args
         B, P = self.B, self.procs
-        sizes = (B * H * 3 * W * 3, B * 4 * H * W * 2 * 4, B * 3 * H * W * 4)
+        sizes = (B * H * 3 * W * 3, B * 4 * H * W * 2 * 4, B * 3 * H * W * 4) + ((B * 3 * H * W * 4,) if self.depth else ())
         for _ in range(self.nring):
             trio = [shared_memory.SharedMemory(create=True, size=max(n, 1)) for n in sizes]
             self._segs.append(trio)
             views = (np.ndarray((B, H, 3 * W, 3), np.uint8, buffer=trio[0].buf),
                      np.ndarray((B, 4, H, W, 2), np.float32, buffer=trio[1].buf),
                      np.ndarray((B, 3, H, W, 1), np.float32, buffer=trio[2].buf))
+            if self.depth:
+                views += (np.ndarray((B, 3, H, W, 1), np.float32, buffer=trio[3].buf),)
             self._views.append(views)
         self._ctrl_shm = shared_memory.SharedMemory(create=True, size=8 * (2 + 2 * P))
         self._ctrl = np.ndarray((2 + 2 * P,), np.int64, buffer=self._ctrl_shm.buf)
@@ -542,14 +563,15 @@ class ProcessWindowLoader:
             self._stop()
 
 
-def kitti_loader(dump_dir, seq, H, W, lo, hi, batch_size, workers=4, prefetch=2, alloc=None, decode_procs=0):
+def kitti_loader(dump_dir, seq, H, W, lo, hi, batch_size, workers=4, prefetch=2, alloc=None, decode_procs=0, depth=False):
     """Windows [lo, hi) of a sequence dump; window w has target frame w + 1.  ``decode_procs`` > 0 decodes the
-    strips in that many processes (the ``workers`` threads then only wait for them and read the .npy files)."""
+    strips in that many processes (the ``workers`` threads then only wait for them and read the .npy files).
+    ``depth``: batches are (img, flow, seg, depth) - the depth files are opened only then."""
     dec = JpegDecodePool(decode_procs) if decode_procs > 0 else None
     return ThreadedWindowLoader(
-        lambda w: load_window(dump_dir, seq, w + 1, H, W), lo, hi, batch_size,
+        lambda w: load_window(dump_dir, seq, w + 1, H, W, depth), lo, hi, batch_size,
         max(workers, 2 * decode_procs), prefetch, alloc,
-        load_into=lambda w, i, f, s: load_window_into(dump_dir, seq, w + 1, H, W, i, f, s, dec),
+        load_into=lambda w, i, f, s, d=None: load_window_into(dump_dir, seq, w + 1, H, W, i, f, s, dec, depth=d),
         on_close=dec.close if dec else None)
 
 
@@ -572,8 +594,9 @@ def scene_like_strip(H, W, window, seed=0):
     return np.clip(out, 0, 255).astype(np.uint8)
 
 
-def write_synthetic_dump(dump_dir, seq, n_frames, H, W, seed=None, quality=None, images="noise"):
+def write_synthetic_dump(dump_dir, seq, n_frames, H, W, seed=None, quality=None, images="noise", depth=False):
     """Write a dump in the reference's on-disk format from the seeded synthetic tensors (no KITTI offline).
+    ``depth``: also write the ``-monodepth2_depth.npy`` files (``synth.make_depth``) a depth-source variant reads.
     ``images``: "noise" = the parity inputs' uniform-noise strips at quality 95 (worst case for the decoder), "scene" =
     ``scene_like_strip`` at quality 75 (a real dump's file size and decode cost).  Returns the number of windows written."""
     from PIL import Image
@@ -591,4 +614,7 @@ def write_synthetic_dump(dump_dir, seq, n_frames, H, W, seed=None, quality=None,
         Image.fromarray(strip).save(jpg, quality=quality)
         np.save(flo, flow[0])
         np.save(sg, seg[0])
+        if depth:
+            np.save(depth_path(dump_dir, seq, w + 1),
+                    synth.make_depth(1, H, W, seed=synth.SEED if seed is None else seed, first_window=w)[0])
     return n_frames - 2

@@ -115,6 +115,8 @@ def main(argv=None):
     gpu_ready = threading.Event()
     H, W = a.img_height, a.img_width
     load = weights = None
+    from .version import parse_version
+    needs_depth = parse_version(a.version).needs_depth           # a depth source: <dump>/SS/FFFFFF-monodepth2_depth.npy beside the other files
     if a.synthetic:
         n_frames = a.synthetic
     else:
@@ -136,13 +138,12 @@ def main(argv=None):
             except (OSError, ValueError):
                 pass
             procs = max(1, min(16, cores - 2))
-        from .version import parse_version
         tgt_planes = loader_seg_planes(parse_version(a.version))
         load = S.kitti_window_loader(a.concat_img_dir, a.test_seq, n_frames, H, W,
                                      alloc=lambda shape, dtype: pinned_empty(shape, dtype, device_index),
                                      workers=a.loader_threads, decode_procs=a.decode_procs, procs=procs,
                                      pin=lambda arr: (gpu_ready.wait(), pin_array(arr, device_index)), unpin=unpin_array,
-                                     seg_planes=tgt_planes, hold=0 if a.sync_driver else 1)
+                                     seg_planes=tgt_planes, hold=0 if a.sync_driver else 1, depth=needs_depth)
         # the loader's buffers are created and its workers start filling them on a thread of its own, before anything else: the
         # workers need no GPU.  Page-locking the buffers (1.4 GB at batch 64: 0.3 s) follows on the loader's own thread, entry by
         # entry, once the context below exists: HIP serialises hipHostRegister with the context's own allocations, and pinning
@@ -178,7 +179,7 @@ def main(argv=None):
 
     if a.synthetic:
         from . import synth
-        load = S.synthetic_window_loader(H, W)
+        load = S.synthetic_window_loader(H, W, depth=needs_depth)
         weights = synth.make_weights(a.version)
     else:
         weights_thread.join()
@@ -188,7 +189,7 @@ def main(argv=None):
     mark("inputs_and_weights_ready")
     system.load_weights(weights)
     mark("weights_on_gpu")
-    infer = lambda img, flow, seg: system.inference(None, "pose", inputs=(img, flow, seg))["pose"]   # noqa: E731
+    infer = lambda *parts: system.inference(None, "pose", inputs=parts)["pose"]   # noqa: E731  (img, flow, seg[, depth])
     if loader_thread is not None:
         loader_thread.join()
     mark("loader_started")

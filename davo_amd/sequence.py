@@ -126,6 +126,14 @@ def _pad_batch(img, flow, seg, batch_size):
     return img, flow, seg, n
 
 
+def _pad_parts(parts, batch_size):
+    """_pad_batch for a batch of three or four arrays (a depth-source variant's batches carry the depth planes)"""
+    n = parts[0].shape[0]
+    if n < batch_size:
+        parts = tuple(np.concatenate([p, np.repeat(p[-1:], batch_size - n, 0)]) for p in parts)
+    return tuple(parts), n
+
+
 class PoseStream:
     """The library's streaming entry point (include/davo_hip.h: davo_submit / davo_wait) as run_shard's ``stream``: batches
     are issued without waiting for their poses, so the H2D copy and the kernels of batch n+1 run while batch n computes and
@@ -144,8 +152,8 @@ class PoseStream:
             inflight = 4 if engine.max_batch <= 2 else 3
         engine.set_inflight(inflight)
 
-    def submit(self, img, flow, seg, out):
-        self.engine.submit(img, flow, seg, out, self.hold)
+    def submit(self, img, flow, seg, out, depth=None):
+        self.engine.submit(img, flow, seg, out, self.hold, depth=depth)
 
     def drain(self):
         self.engine.synchronize()
@@ -159,6 +167,9 @@ def run_shard(infer_fn, load_windows, lo, hi, batch_size, timing=None, stream=No
 
     ``stream`` (a PoseStream) replaces ``infer_fn``: batches are submitted and their poses collected at the end, so input
     wait, copies and kernels overlap instead of adding up; the poses are the same bits (same kernels on the same batches).
+
+    A depth-source variant's batches are ``(img, flow, seg, depth)``: ``infer_fn`` then takes four arrays and ``stream.submit``
+    gets ``depth=``; every other variant sees the three-array calls it always did.
 
     ``load_windows`` is either a callable ``(s, e) -> (img, flow, seg)`` or an iterable of
     ``(s, e, (img, flow, seg))`` in window order (davo_amd.loader.ThreadedWindowLoader: the next
@@ -178,16 +189,17 @@ def run_shard(infer_fn, load_windows, lo, hi, batch_size, timing=None, stream=No
         t_load += t1 - t0
         if item is None:
             break
-        s, e, (img, flow, seg) = item
-        img, flow, seg, n = _pad_batch(img, flow, seg, batch_size)
+        s, e, parts = item
+        parts, n = _pad_parts(parts, batch_size)
+        extra = {"depth": parts[3]} if len(parts) == 4 else {}
         if stream is None:
-            out[s - lo:e - lo] = np.asarray(infer_fn(img, flow, seg))[:n]
+            out[s - lo:e - lo] = np.asarray(infer_fn(*parts))[:n]
         elif n == batch_size:
-            stream.submit(img, flow, seg, out[s - lo:e - lo])          # delivered straight into its rows of `out`
+            stream.submit(*parts[:3], out[s - lo:e - lo], **extra)     # delivered straight into its rows of `out`
         else:
             full = np.empty((batch_size, 2, 6), np.float32)
-            stream.submit(img, flow, seg, full)
-            tails.append((full, s - lo, n, (img, flow, seg)))           # the padded copies stay alive until the drain
+            stream.submit(*parts[:3], full, **extra)
+            tails.append((full, s - lo, n, parts))                      # the padded copies stay alive until the drain
         t_fwd += time.perf_counter() - t1
     if stream is not None:
         t1 = time.perf_counter()
@@ -258,7 +270,8 @@ class kitti_window_loader:
     threaded, prefetching batch iterator of a rank's shard; calling it ``(s, e)`` loads one batch inline."""
 
     def __init__(self, concat_img_dir, seq, n_frames, H, W, workers=4, prefetch=2, alloc=None, decode_procs=0, procs=0,
-                 pin=None, unpin=None, seg_planes=None, hold=0):
+                 pin=None, unpin=None, seg_planes=None, hold=0, depth=False):
+        self.depth = depth        # a depth-source variant: batches are (img, flow, seg, depth)
         self.dir, self.seq, self.n_frames, self.H, self.W = concat_img_dir, seq, n_frames, H, W
         self.workers, self.prefetch, self.alloc, self.decode_procs = workers, prefetch, alloc, decode_procs
         self.procs, self.pin, self.unpin, self.seg_planes = procs, pin, unpin, seg_planes
@@ -281,22 +294,26 @@ class kitti_window_loader:
         if self.procs > 0:      # worker processes fill shared (page-locked) batch buffers: davo_amd/loader.py, ProcessWindowLoader
             try:
                 return L.ProcessWindowLoader(self.dir, self.seq, self.H, self.W, lo, hi, batch_size, self.procs, self.prefetch,
-                                             pin=self.pin, unpin=self.unpin, hold=self.hold,
+                                             pin=self.pin, unpin=self.unpin, hold=self.hold, depth=self.depth,
                                              seg_planes=L.SEG_PLANES_SOURCES if self.seg_planes is None else self.seg_planes)
             except L.ShmBudgetError as e:      # e.g. a container with the usual 64 MB /dev/shm: decode threads into pinned buffers instead
                 import sys
                 print("davo_amd: %s - falling back to the threaded loader" % e, file=sys.stderr)
-        return L.kitti_loader(self.dir, self.seq, self.H, self.W, lo, hi, batch_size, self.workers, self.prefetch, self.alloc, self.decode_procs)
+        return L.kitti_loader(self.dir, self.seq, self.H, self.W, lo, hi, batch_size, self.workers, self.prefetch, self.alloc, self.decode_procs,
+                              depth=self.depth)
 
     def __call__(self, s, e):
         from .loader import load_window
-        parts = [load_window(self.dir, self.seq, w + 1, self.H, self.W) for w in range(s, e)]
-        return tuple(np.stack([p[k] for p in parts]) for k in range(3))
+        parts = [load_window(self.dir, self.seq, w + 1, self.H, self.W, self.depth) for w in range(s, e)]
+        return tuple(np.stack([p[k] for p in parts]) for k in range(4 if self.depth else 3))
 
 
-def synthetic_window_loader(H, W, seed=None):
+def synthetic_window_loader(H, W, seed=None, depth=False):
     from . import synth
 
     def load(s, e):
-        return synth.make_inputs(e - s, H, W, seed=synth.SEED if seed is None else seed, first_window=s)
+        parts = synth.make_inputs(e - s, H, W, seed=synth.SEED if seed is None else seed, first_window=s)
+        if depth:
+            parts += (synth.make_depth(e - s, H, W, seed=synth.SEED if seed is None else seed, first_window=s),)
+        return parts
     return load

@@ -9,6 +9,7 @@ No KITTI dump, FlowNet2/DeepLab output or checkpoint exists offline, so tests an
   reference hard-codes (``davo.py:1090``)
 * ``seg``  f32 ``[B,3,H,W,1]``  Cityscapes train ids 0..18 in 8x8 blocks, 3 % of blocks 255
   (ignore id, ``utils/seg_utils/labels.py:64-70``)
+* ``depth`` f32 ``[B,3,H,W,1]`` (``make_depth``, depth-source variants only) smooth positive fields in (1, 80)
 
 The PRNG is splitmix64 and every float is produced by integer arithmetic plus IEEE
 add/mul/sqrt only (the "normal" is an Irwin-Hall sum of four uniforms), so the same
@@ -85,13 +86,40 @@ def make_inputs(B, H=128, W=416, seed=SEED, first_window=0):
     return img, flow, seg
 
 
+def make_depth(B, H=128, W=416, seed=SEED, first_window=0):
+    """Synthetic depth planes f32 ``[B,3,H,W,1]`` (file order src0, tgt, src1; reference ``davo.py:991-996``,
+    ``test_kitti_pose.py:48``) in a monodepth2-like range: per plane a smooth field - a coarse 5x9 grid of depths, log-uniform
+    in [1.5, 60], interpolated bilinearly, times a per-pixel ripple of +-5 % - so every value lies strictly inside (1, 80).
+    Reproducible per window like ``make_inputs`` (streams of their own: the other planes do not move); integer arithmetic plus
+    IEEE add/mul only after the grid's exponentiation, which is float64 ``np.exp2`` of 45 values per plane."""
+    depth = np.empty((B, 3, H, W, 1), np.float32)
+    gh, gw = 5, 9
+    ys = np.linspace(0.0, gh - 1.0, H)
+    xs = np.linspace(0.0, gw - 1.0, W)
+    y0 = np.minimum(ys.astype(np.int64), gh - 2)
+    x0 = np.minimum(xs.astype(np.int64), gw - 2)
+    fy = (ys - y0)[:, None]
+    fx = (xs - x0)[None, :]
+    for b in range(B):
+        w = first_window + b
+        u = uniform01(seed, _stream("depth") + 7919 * w, 3 * gh * gw).reshape(3, gh, gw)
+        grid = 1.5 * np.exp2(u * math.log2(60.0 / 1.5))
+        rip = uniform01(seed, _stream("depth_ripple") + 7919 * w, 3 * H * W).reshape(3, H, W)
+        for p in range(3):
+            g = grid[p]
+            top = g[y0][:, x0] * (1.0 - fx) + g[y0][:, x0 + 1] * fx
+            bot = g[y0 + 1][:, x0] * (1.0 - fx) + g[y0 + 1][:, x0 + 1] * fx
+            depth[b, p, :, :, 0] = ((top * (1.0 - fy) + bot * fy) * (0.95 + 0.1 * rip[p])).astype(np.float32)
+    return depth
+
+
 def make_weights(version_or_cfg, seed=SEED):
     """dict TF-name -> float32 array (HWIO conv kernels, [in,out] dense kernels).
 
     conv ~ U(+-sqrt(6/fan_in)) (He-uniform keeps activations O(1) through eight ReLU
     layers, so the 6-DoF outputs are large enough for the 1e-4 absolute bar to bite),
     conv biases U(+-0.05), SE kernels variance-scaling as nets/attention_module.py:60,
-    SE biases U(+-0.5) (every SE scope: se_flow, se_seg, se_rgb, se_segflow), static seg weights stddev 0.05 as
+    SE biases U(+-0.5) (every SE scope: se_flow, se_seg, se_rgb, se_segflow, se_depth), static seg weights stddev 0.05 as
     nets/posenn.py:387-388."""
     cfg = parse_version(version_or_cfg) if isinstance(version_or_cfg, str) else version_or_cfg
     out = {}

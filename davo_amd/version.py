@@ -26,7 +26,9 @@ ATT_SOURCE = {"ones": 0, "se_flow": 1, "static_src": 2, "static_all": 3,
               # class-table SE sources (davo.py:1274-1292, 1304-1310, 1341-1374): sigmoid table of 19 classes per frame
               "se_seg_wo_tgt": 4, "se_rgb_wo_tgt_to_seg": 5, "se_rgb_to_seg": 6,
               "se_SegFlow_to_seg_wo_tgt": 7, "se_SegFlow_to_seg": 8,
-              "se_SegFlow_to_seg_8_wo_tgt": 9, "se_SegFlow_to_seg_8": 10}
+              "se_SegFlow_to_seg_8_wo_tgt": 9, "se_SegFlow_to_seg_8": 10,
+              # depth-source class tables (davo.py:1211-1227): the descriptor is the mean of depth_frame + depth_tgt
+              "se_depth_wo_tgt_to_seg": 11, "se_depth_to_seg": 12}
 MASK_INFO = {"none": 0, "att": 1}
 
 
@@ -57,6 +59,11 @@ class VariantConfig:
         return self.att_source in _TGT_ATTENDED
 
     @property
+    def needs_depth(self):
+        """The attention source consumes the depth planes (a fourth input beside img, flow, seg)."""
+        return self.att_source in _DEPTH_SOURCES
+
+    @property
     def se_scope(self):
         """TF variable scope of the SE dense layers under pose_exp_net/, None without them."""
         return _SE_SCOPE.get(self.att_source)
@@ -73,7 +80,7 @@ class VariantConfig:
 _BEFORE_SE_FLOW = ("-se_flow_on_depthseg_sharedlayers", "-se_flow_on_depthseg_seplayers",
                    "-se_flow_on_depthseg", "-se_mixDepthFlow", "-se_mixDispFlow")
 # branches AFTER "-se_flow" and before "-no_segmask", in the reference's order; the ones in _CLASS_TABLE_SOURCES run here,
-# the rest need depth / SPP / gp2x2 pooling or an se_block whose map is not a class table
+# the rest need disparity / SPP / gp2x2 pooling or an se_block whose map is not a class table
 _AFTER_SE_FLOW = ("-se_gp2x2_flow_nobottle", "-se_gp2x2_flow", "-se_spp21_flow", "-se_spp2_flow",
                   "-se_spp_flow", "-se_spp864_flow", "-se_depth_wo_tgt_to_seg", "-se_depth_to_seg",
                   "-se_depth_wo_tgt", "-se_depth", "-se_disp_wo_tgt_to_seg", "-se_disp_to_seg",
@@ -91,16 +98,21 @@ _CLASS_TABLE_SOURCES = {"-se_seg_wo_tgt": "se_seg_wo_tgt",                      
                         "-se_SegFlow_to_seg_8_wo_tgt": "se_SegFlow_to_seg_8_wo_tgt",  # :1341-1349
                         "-se_SegFlow_to_seg_8": "se_SegFlow_to_seg_8",              # :1350-1356
                         "-se_SegFlow_to_seg_wo_tgt": "se_SegFlow_to_seg_wo_tgt",    # :1358-1366
-                        "-se_SegFlow_to_seg": "se_SegFlow_to_seg"}                  # :1367-1374
-_TGT_ATTENDED = ("static_all", "se_rgb_to_seg", "se_SegFlow_to_seg", "se_SegFlow_to_seg_8")
+                        "-se_SegFlow_to_seg": "se_SegFlow_to_seg",                  # :1367-1374
+                        "-se_depth_wo_tgt_to_seg": "se_depth_wo_tgt_to_seg",        # :1211-1219
+                        "-se_depth_to_seg": "se_depth_to_seg"}                      # :1220-1227
+_TGT_ATTENDED = ("static_all", "se_rgb_to_seg", "se_SegFlow_to_seg", "se_SegFlow_to_seg_8", "se_depth_to_seg")
+_DEPTH_SOURCES = ("se_depth_wo_tgt_to_seg", "se_depth_to_seg")
 _SE_SCOPE = {"se_flow": "se_flow", "se_seg_wo_tgt": "se_seg", "se_rgb_wo_tgt_to_seg": "se_rgb", "se_rgb_to_seg": "se_rgb",
              "se_SegFlow_to_seg_wo_tgt": "se_segflow", "se_SegFlow_to_seg": "se_segflow",
-             "se_SegFlow_to_seg_8_wo_tgt": "se_segflow", "se_SegFlow_to_seg_8": "se_segflow"}
+             "se_SegFlow_to_seg_8_wo_tgt": "se_segflow", "se_SegFlow_to_seg_8": "se_segflow",
+             "se_depth_wo_tgt_to_seg": "se_depth", "se_depth_to_seg": "se_depth"}
 # SE dense layer widths (in, hidden); the recovery layer always has the 19 classes
 _SE_WIDTHS = {"se_flow": (2, 8), "se_seg_wo_tgt": (NUM_SEG_CLASSES, NUM_SEG_CLASSES), "se_rgb_wo_tgt_to_seg": (3, 8),
               "se_rgb_to_seg": (3, 8), "se_SegFlow_to_seg_wo_tgt": (NUM_SEG_CLASSES + 2, NUM_SEG_CLASSES),
               "se_SegFlow_to_seg": (NUM_SEG_CLASSES + 2, NUM_SEG_CLASSES),
-              "se_SegFlow_to_seg_8_wo_tgt": (NUM_SEG_CLASSES + 2, 8), "se_SegFlow_to_seg_8": (NUM_SEG_CLASSES + 2, 8)}
+              "se_SegFlow_to_seg_8_wo_tgt": (NUM_SEG_CLASSES + 2, 8), "se_SegFlow_to_seg_8": (NUM_SEG_CLASSES + 2, 8),
+              "se_depth_wo_tgt_to_seg": (1, 8), "se_depth_to_seg": (1, 8)}
 
 
 def parse_version(version):
@@ -111,9 +123,18 @@ def parse_version(version):
     assert version is not None                          # davo.py:959
     v = version
 
-    # -- davo.py:960: depth inputs are files this build does not consume
-    if "depth" in v or "disp" in v:
-        raise UnsupportedVariantError("version `%s': depth/disp inputs are not supported." % v)
+    # -- davo.py:960: depth files are read when the version contains `depth' or `disp'; only the two depth class-table
+    #    sources (davo.py:1211-1227) consume them here
+    if "disp" in v:
+        # test_kitti_pose.py:91 reads depth files only for `depth'; for `disp' it hands the label maps in as depth (:61-64)
+        raise UnsupportedVariantError("version `%s': disparity sources are not supported (the reference's driver feeds "
+                                      "them the label maps, test_kitti_pose.py:61-64,91)." % v)
+    if "-norm_depth" in v:
+        raise UnsupportedVariantError("version `%s': `-norm_depth' is not supported (davo.py:1110-1111 iterates over "
+                                      "what davo.py:1109 made a tensor)." % v)
+    if "depth" in re.sub("-se_depth_wo_tgt_to_seg|-se_depth_to_seg", "", v):
+        raise UnsupportedVariantError("version `%s': the only depth sources supported are `-se_depth_wo_tgt_to_seg' and "
+                                      "`-se_depth_to_seg'." % v)
 
     # -- davo.py:1010-1017: se_block inside the PoseNN
     for s in ("-se_insert", "-se_skipadd", "-se_replace"):

@@ -50,7 +50,12 @@ typedef struct {
                              *   7 -se_SegFlow_to_seg_wo_tgt    histogram + flow mean 21 -> 19 -> 19, tgt=1 (scope se_segflow)
                              *   8 -se_SegFlow_to_seg           21 -> 19 -> 19                          (scope se_segflow)
                              *   9 -se_SegFlow_to_seg_8_wo_tgt  21 -> 8 -> 19, tgt=1                    (scope se_segflow)
-                             *  10 -se_SegFlow_to_seg_8         21 -> 8 -> 19                           (scope se_segflow) */
+                             *  10 -se_SegFlow_to_seg_8         21 -> 8 -> 19                           (scope se_segflow)
+                             * depth class tables (davo.py:1109, 1211-1227): the descriptor of frame i is the mean of
+                             * depth_i + depth_tgt (the reference's `list + tensor' broadcasts the target's depth onto every
+                             * frame).  They read a fourth input, the depth planes: the `_depth' entry points below.
+                             *  11 -se_depth_wo_tgt_to_seg      depth mean 1 -> 8 -> 19, tgt=1          (scope se_depth)
+                             *  12 -se_depth_to_seg             depth mean 1 -> 8 -> 19                 (scope se_depth) */
     int32_t mask_rgb;       /* rgb_k *= att_k                          (davo.py:1419-1423)        */
     int32_t mask_info;      /* flow_k *= att_k  (-segmask_all)         (davo.py:1430-1434)        */
 } davo_variant;
@@ -82,6 +87,26 @@ int davo_weights_missing(davo_ctx* ctx);
  * Synchronous: returns after pose_out is written.  1 <= B <= max_batch. */
 int davo_forward(davo_ctx* ctx, int B, const uint8_t* img, const float* flow, const float* seg,
                  float* pose_out);
+
+/* The depth sources (att_source 11, 12) read a fourth input (davo.py:960, 991-996; test_kitti_pose.py:48, 91):
+ *   depth f32  [B,3,H,W,1] (file order src0,tgt,src1 like the label maps; <dump>/SS/FFFFFF-monodepth2_depth.npy),
+ * 16-byte aligned where it is a device pointer.  Each entry point that takes inputs has a `_depth' form with that argument
+ * behind `seg'; everything said about the three-input form holds for it, the depth planes included: davo_forward_depth copies
+ * them with each sub-batch, davo_submit_depth stages all three planes per slot, the f16x3 range recovery keeps and re-issues them
+ * with the batch.  On a context whose variant reads depth the three-input forms return DAVO_ERR_INVALID (the message names the
+ * `_depth' form); on any other variant the `_depth' forms accept a depth pointer or NULL and ignore it.
+ *   davo_forward_depth          davo_forward           + depth (host pointer)     DAVO.inference, davo.py:1553-1569
+ *   davo_forward_device_depth   davo_forward_device    + d_depth (device pointer)
+ *   davo_submit_depth           davo_submit            + depth (host pointer)     test_kitti_pose.py:133-145
+ *   davo_calibrate_depth        davo_calibrate         + d_depth (device pointer) */
+int davo_forward_depth(davo_ctx* ctx, int B, const uint8_t* img, const float* flow, const float* seg,
+                       const float* depth, float* pose_out);
+int davo_forward_device_depth(davo_ctx* ctx, int B, const void* d_img, const void* d_flow, const void* d_seg,
+                              const void* d_depth, void* d_pose, float* elapsed_ms);
+int davo_submit_depth(davo_ctx* ctx, int B, const uint8_t* img, const float* flow, const float* seg,
+                      const float* depth, float* pose_out, int hold);
+int davo_calibrate_depth(davo_ctx* ctx, int batch, const void* d_img, const void* d_flow, const void* d_seg,
+                         const void* d_depth, int* shifts_out);
 
 /* Same computation on device-resident buffers (the path bench.py times; multi-GPU shards keep
  * their windows in HBM).  Asynchronous on the context's stream unless elapsed_ms != NULL, in

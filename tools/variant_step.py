@@ -31,6 +31,7 @@ def main():
     a = ap.parse_args()
     B, H, W = a.batch, a.height, a.width
     img, flow, seg = synth.make_inputs(B, H, W)
+    depth = synth.make_depth(B, H, W)              # uploaded for the depth sources only
     runs = []
     for v in a.versions:
         cfg = parse_version(v)
@@ -38,19 +39,21 @@ def main():
         e.load_weights(synth.make_weights(cfg))
         e.set_precision(a.precision)
         bufs = [e.alloc(x.nbytes).upload(x) for x in (img, flow, seg)] + [e.alloc(B * 12 * 4)]
+        kw = {"depth": e.alloc(depth.nbytes).upload(depth)} if cfg.needs_depth else {}
         for _ in range(a.warmup):
-            e.forward_device(B, *bufs)
+            e.forward_device(B, *bufs, **kw)
         e.synchronize()
-        runs.append((v, e, bufs, []))
+        runs.append((v, e, bufs, [], kw))
     for _ in range(a.rounds):
-        for v, e, bufs, ms in runs:
+        for v, e, bufs, ms, kw in runs:
             e.synchronize()
             t = time.perf_counter()
             for _ in range(a.steps):
-                e.forward_device(B, *bufs)
+                e.forward_device(B, *bufs, **kw)
             e.synchronize()
             ms.append((time.perf_counter() - t) * 1e3 / a.steps)
-    for v, e, bufs, ms in runs:
+    for v, e, bufs, ms, kw in runs:
+        bufs = bufs + list(kw.values())
         pose = bufs[3].download((B, 2, 6))
         best = min(ms)
         print(json.dumps({"version": v, "precision": a.precision, "batch": B, "height": H, "width": W, "steps": a.steps,
