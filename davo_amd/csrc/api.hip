@@ -25,6 +25,27 @@ int zero_now(davo_ctx* c, void* p, size_t bytes) {
     return DAVO_OK;
 }
 
+// Room for max_batch windows of every plane the variant reads.  zero_unread: the flow and label planes start out zero - what the path
+// never reads (flow planes 2,3; the target frame's label map) is never copied into a davo_submit staging set: defined contents all the same
+int alloc_input_set(davo_ctx* c, InputSet* s, bool zero_unread) {
+    const PlaneBytes nb = plane_bytes(c);
+    const size_t n = (size_t)c->max_batch;
+    HIP_TRY(c, hipMalloc(&s->img, nb.img * n));
+    HIP_TRY(c, hipMalloc(&s->flow, nb.flow * n));
+    HIP_TRY(c, hipMalloc(&s->seg, nb.seg * n));
+    if (needs_depth(c)) HIP_TRY(c, hipMalloc(&s->depth, nb.depth * n));      // always copied whole
+    if (zero_unread) {
+        { int rc = zero_now(c, s->flow, nb.flow * n); if (rc) return rc; }
+        { int rc = zero_now(c, s->seg, nb.seg * n); if (rc) return rc; }
+    }
+    return DAVO_OK;
+}
+
+void free_input_set(InputSet& s) {
+    for (void* q : {s.img, s.flow, s.seg, s.depth}) if (q) (void)hipFree(q);
+    s = InputSet();
+}
+
 void free_slot(Slot& s) {
     for (auto p : s.d_act) if (p) (void)hipFree(p);
     void* misc[] = {s.d_partial, s.d_tab, s.d_packed, s.d_pose_partial, s.d_counters};
@@ -175,12 +196,6 @@ namespace {
 constexpr int RING = RANGE_RING;
 constexpr int FRESH_EVERY = 256;
 
-size_t img_bytes(const davo_ctx* c) { return (size_t)c->H * c->W * 9; }
-size_t flow_bytes(const davo_ctx* c) { return (size_t)c->H * c->W * 8 * sizeof(float); }
-size_t seg_bytes(const davo_ctx* c) { return (size_t)c->H * c->W * 3 * sizeof(float); }
-size_t depth_bytes(const davo_ctx* c) { return (size_t)c->H * c->W * 3 * sizeof(float); }      // [3,H,W,1] float32 like the label maps (davo.py:991-996)
-bool needs_depth(const davo_ctx* c) { return att_desc_depth(c->v.att_source); }
-
 // The depth argument of an entry point.  A depth-source variant (att_source 11, 12) must be called through the `_depth' form with
 // the planes; every other variant reads no depth: the `_depth' forms accept a pointer (or null) and ignore it.
 int resolve_depth(davo_ctx* c, const char* fn, bool depth_form, const void** depth) {
@@ -197,14 +212,8 @@ int ensure_ring(davo_ctx* c, bool snapshots) {
         HIP_TRY(c, hipHostGetDevicePointer(reinterpret_cast<void**>(&c->h_range_dev), c->h_range, 0));
         memset(c->h_range, 0, (1 + RANGE_RING) * RANGE_WORDS * sizeof(unsigned));
     }
-    if (snapshots && !c->snap_img[0]) {
-        for (int r = 0; r < RING; ++r) {
-            HIP_TRY(c, hipMalloc(&c->snap_img[r], img_bytes(c) * c->max_batch));
-            HIP_TRY(c, hipMalloc(&c->snap_flow[r], flow_bytes(c) * c->max_batch));
-            HIP_TRY(c, hipMalloc(&c->snap_seg[r], seg_bytes(c) * c->max_batch));
-            if (needs_depth(c)) HIP_TRY(c, hipMalloc(&c->snap_depth[r], depth_bytes(c) * c->max_batch));
-        }
-    }
+    if (snapshots && !c->snap_sets[0].img)
+        for (InputSet& set : c->snap_sets) { int rc = alloc_input_set(c, &set, false); if (rc) return rc; }
     return DAVO_OK;
 }
 
@@ -256,14 +265,14 @@ int freeze_pending_and_reset_ring(davo_ctx* c) {
 // value into [512, 1024).  A layer computed from badly ranged inputs still has about the right magnitude, so each
 // pass fixes at least the first badly ranged layer exactly and the later ones to within a few powers of two.
 // Runs on the base record; every stream must be idle.
-int calibrate_on(davo_ctx* c, int B, const void* d_img, const void* d_flow, const void* d_seg, const void* d_depth, void* d_pose) {
+int calibrate_on(davo_ctx* c, int B, const Inputs& in, void* d_pose) {
     int rc = DAVO_OK;
     const int save_precision = c->precision, save_impl = c->impl;
     c->precision = 1; c->impl = 0;
     c->d_range = c->d_range_base;
     for (int pass = 0; pass < 8 && rc == DAVO_OK; ++pass) {
         if ((rc = zero_base_record(c, c->stream))) break;
-        rc = forward_device(c, B, d_img, d_flow, d_seg, d_depth, d_pose);
+        rc = forward_device(c, B, in, d_pose);
         if (rc) break;
         if (hipStreamSynchronize(c->stream) != hipSuccess) { rc = fail(c, DAVO_ERR_HIP, "hipStreamSynchronize failed"); break; }
         unsigned raw[RANGE_WORDS];
@@ -290,7 +299,7 @@ int calibrate_on(davo_ctx* c, int B, const void* d_img, const void* d_flow, cons
 int run_judged(davo_ctx* c, const Ticket& b) {
     c->d_range = c->d_range_base;
     { int rc = zero_base_record(c, c->stream); if (rc) return rc; }
-    int rc = forward_device(c, b.B, b.img, b.flow, b.seg, b.depth, b.pose);
+    int rc = forward_device(c, b.B, b.in, b.pose);
     if (rc) return rc;
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     if (c->last_precision != 1) return DAVO_OK;
@@ -324,7 +333,7 @@ int recover_batch(davo_ctx* c, const Ticket& orig) {
     activate_slot(c, 0);
     int rc = run_judged(c, b);
     if (rc == DAVO_ERR_RANGE) {
-        if ((rc = calibrate_on(c, b.B, b.img, b.flow, b.seg, b.depth, b.pose))) return rc;
+        if ((rc = calibrate_on(c, b.B, b.in, b.pose))) return rc;
         ++c->n_recalibrations;
         rc = run_judged(c, b);
         c->range_report = "re-calibrated: " + verdict;
@@ -332,7 +341,7 @@ int recover_batch(davo_ctx* c, const Ticket& orig) {
     if (rc == DAVO_ERR_RANGE) {
         const int save = c->precision;
         c->precision = 0;
-        rc = forward_device(c, b.B, b.img, b.flow, b.seg, b.depth, b.pose);
+        rc = forward_device(c, b.B, b.in, b.pose);
         c->precision = save;
         if (rc == DAVO_OK && hipStreamSynchronize(c->stream) != hipSuccess) rc = fail(c, DAVO_ERR_HIP, "hipStreamSynchronize failed");
         ++c->n_f32_batches;
@@ -432,13 +441,16 @@ int ticket_reserve(davo_ctx* c) {
     return DAVO_OK;
 }
 
-// ... the batch's kernels record into the slot's record; its last kernel keeps the inputs there if the record fails
-int ticket_begin(davo_ctx* c, int B, const void* d_img, const void* d_flow, const void* d_seg, const void* d_depth, bool* snap, bool own_inputs = false) {
+// ... the batch's kernels record into the slot's record; its last kernel keeps the inputs there if the record fails.  *t receives what
+// is known of the batch's ticket now: above all what a re-issue would read
+int ticket_begin(davo_ctx* c, int B, const Inputs& in, Ticket* t, bool own_inputs = false) {
     const int r = c->ring_next;
+    *t = Ticket{};
+    t->B = B; t->ring = r;
     // own_inputs: the batch reads a staging set of the context (davo_submit), which the next batches overwrite whatever the caller declared
-    *snap = c->opt_auto_range && (!c->opt_stable_inputs || own_inputs);
-    if (*snap && (((uintptr_t)d_img | (uintptr_t)d_flow | (uintptr_t)d_seg | (uintptr_t)d_depth) & 15)) return fail(c, DAVO_ERR_INVALID, "device input buffers must be 16-byte aligned");
-    { int rc = ensure_ring(c, *snap); if (rc) return rc; }
+    t->snap = c->opt_auto_range && (!c->opt_stable_inputs || own_inputs);
+    if (t->snap && (((uintptr_t)in.img | (uintptr_t)in.flow | (uintptr_t)in.seg | (uintptr_t)in.depth) & 15)) return fail(c, DAVO_ERR_INVALID, "device input buffers must be 16-byte aligned");
+    { int rc = ensure_ring(c, t->snap); if (rc) return rc; }
     c->d_range = ring_record(c, r);
     c->range_zero = true;
     // The records hold RUNNING maxima (params.h): "clamped" is exact per batch, "too small" is judged on everything a slot has stored
@@ -450,32 +462,31 @@ int ticket_begin(davo_ctx* c, int B, const void* d_img, const void* d_flow, cons
         HIP_TRY(c, hipMemsetAsync(c->d_range, 0, 6 * sizeof(unsigned), c->stream));
     }
     if (++c->batch_seq == 0) c->batch_seq = 1;
-    c->snap_seq_issued = c->batch_seq;
+    c->snap_seq_issued = t->seq = c->batch_seq;
+    const InputSet keep = t->snap ? c->snap_sets[r] : InputSet();      // no snapshot: no destination, and the ticket remembers the caller's buffers
+    t->in = t->snap ? keep.view() : in;
+    const PlaneBytes nb = plane_bytes(c);
+    auto src = [](const void* q) { return static_cast<const uint8_t*>(q); };
+    auto dst = [](void* q) { return static_cast<uint8_t*>(q); };
     c->snap = SnapArgs{c->d_range, c->h_range_dev + RANGE_WORDS * (1 + r), c->batch_seq,
-                       static_cast<const uint8_t*>(d_img), static_cast<const uint8_t*>(d_flow), static_cast<const uint8_t*>(d_seg),
-                       *snap ? static_cast<uint8_t*>(c->snap_img[r]) : nullptr, *snap ? static_cast<uint8_t*>(c->snap_flow[r]) : nullptr,
-                       *snap ? static_cast<uint8_t*>(c->snap_seg[r]) : nullptr,
-                       (unsigned)(img_bytes(c) / 16), (unsigned)(flow_bytes(c) / 32), (unsigned)(flow_bytes(c) / 16), (unsigned)(seg_bytes(c) / 16), B,
-                       static_cast<const uint8_t*>(d_depth), (*snap && d_depth) ? static_cast<uint8_t*>(c->snap_depth[r]) : nullptr};
+                       src(in.img), src(in.flow), src(in.seg), dst(keep.img), dst(keep.flow), dst(keep.seg),
+                       (unsigned)(nb.img / 16), (unsigned)(nb.flow / 32), (unsigned)(nb.flow / 16), (unsigned)(nb.seg / 16), B,
+                       src(in.depth), dst(keep.depth)};
     return DAVO_OK;
 }
 
-int ticket_end(davo_ctx* c, int rc, int B, const void* d_img, const void* d_flow, const void* d_seg, const void* d_depth, void* d_pose, bool snap, float* h_pose = nullptr) {
-    const int r = c->ring_next;
+int ticket_end(davo_ctx* c, int rc, Ticket t, void* d_pose, float* h_pose = nullptr) {
     c->d_range = c->d_range_base;
     c->range_zero = false;
     c->snap = SnapArgs{};
     if (rc) return rc;
     if (c->f32_fallback) ++c->n_f32_batches;
     if (c->last_precision != 1) return DAVO_OK;                                  // float32 kernels (weight guard): no record, no verdict
-    Ticket t{};
-    t.B = B; t.img = snap ? c->snap_img[r] : d_img; t.flow = snap ? c->snap_flow[r] : d_flow; t.seg = snap ? c->snap_seg[r] : d_seg;
-    t.depth = (snap && d_depth) ? c->snap_depth[r] : d_depth;
-    t.pose = d_pose; t.ring = r; t.snap = snap; t.seq = c->snap_seq_issued; t.stream = c->stream; t.h_pose = h_pose; t.issue = c->n_issued;
+    t.pose = d_pose; t.stream = c->stream; t.h_pose = h_pose; t.issue = c->n_issued;
     for (int i = 0; i < 6; ++i) t.shifts[i] = c->act_shift[i];
     c->tickets.push_back(t);
-    c->ring_busy[r] = true;
-    c->ring_next = (r + 1) % RING;
+    c->ring_busy[t.ring] = true;
+    c->ring_next = (t.ring + 1) % RING;
     return DAVO_OK;
 }
 
@@ -488,14 +499,15 @@ static int forward_device_entry(davo_ctx* c, int B, const void* d_img, const voi
     if (B < 1 || B > c->max_batch) return fail(c, DAVO_ERR_INVALID, "batch %d outside [1,%d]", B, c->max_batch);
     if (!d_img || !d_flow || !d_seg || !d_pose) return fail(c, DAVO_ERR_INVALID, "null device pointer");
     { int rc = resolve_depth(c, "davo_forward_device", depth_form, &d_depth); if (rc) return rc; }
+    const Inputs in{d_img, d_flow, d_seg, d_depth};
     HIP_TRY(c, hipSetDevice(c->device));
     const bool ticketed = c->impl == 0 && c->precision == 1;      // f16x3: the batch gets a record (and a copy of its inputs) of its own
     if (ticketed) { int rc = ticket_reserve(c); if (rc) return rc; }
     // rotate through the in-flight slots: this batch runs on its own stream and workspace
     activate_slot(c, c->next_slot);
     c->next_slot = (c->next_slot + 1) % c->inflight;
-    bool snap = false;
-    if (ticketed) { int rc = ticket_begin(c, B, d_img, d_flow, d_seg, d_depth, &snap); if (rc) return rc; }
+    Ticket t{};
+    if (ticketed) { int rc = ticket_begin(c, B, in, &t); if (rc) return rc; }
     if (!ticketed && c->pose_spans.size() > 64) {          // float32 batches behind pending f16x3 tickets: bounded
         const int rc = judge_all(c);
         if (rc == DAVO_ERR_RANGE) { c->sticky_range_rc = rc; c->sticky_range_err = c->err; }       // "auto_range" 0: reported by the next davo_synchronize
@@ -503,8 +515,8 @@ static int forward_device_entry(davo_ctx* c, int B, const void* d_img, const voi
     }
     note_pose_span(c, d_pose, B);
     if (!elapsed_ms) {
-        int rc = forward_device(c, B, d_img, d_flow, d_seg, d_depth, d_pose);
-        if (ticketed) rc = ticket_end(c, rc, B, d_img, d_flow, d_seg, d_depth, d_pose, snap);
+        int rc = forward_device(c, B, in, d_pose);
+        if (ticketed) rc = ticket_end(c, rc, t, d_pose);
         else if (rc == DAVO_OK && c->f32_fallback) ++c->n_f32_batches;
         return rc;
     }
@@ -516,14 +528,14 @@ static int forward_device_entry(davo_ctx* c, int B, const void* d_img, const voi
     };
     if (hip_ok(hipEventCreate(&e0), "hipEventCreate") && hip_ok(hipEventCreate(&e1), "hipEventCreate") &&
         hip_ok(hipEventRecord(e0, c->stream), "hipEventRecord")) {
-        rc = forward_device(c, B, d_img, d_flow, d_seg, d_depth, d_pose);
+        rc = forward_device(c, B, in, d_pose);
         if (rc == DAVO_OK && hip_ok(hipEventRecord(e1, c->stream), "hipEventRecord") &&
             hip_ok(hipEventSynchronize(e1), "hipEventSynchronize"))
             hip_ok(hipEventElapsedTime(elapsed_ms, e0, e1), "hipEventElapsedTime");
     }
     if (e0) (void)hipEventDestroy(e0);
     if (e1) (void)hipEventDestroy(e1);
-    if (ticketed) rc = ticket_end(c, rc, B, d_img, d_flow, d_seg, d_depth, d_pose, snap);
+    if (ticketed) rc = ticket_end(c, rc, t, d_pose);
     // the timed form is synchronous, so it can judge (and, if need be, re-issue) its own batch; elapsed_ms is the first issue's
     if (rc == DAVO_OK && c->inflight == 1) rc = judge_all(c);
     return rc;
@@ -561,15 +573,35 @@ int ensure_stream_state(davo_ctx* c, int slot) {
             HIP_TRY(c, hipEventCreateWithFlags(&c->pose_done[k], hipEventDisableTiming));
             HIP_TRY(c, hipEventCreateWithFlags(&c->st_copied[k], hipEventDisableTiming));
         }
-    if (!c->st_img[slot]) {
-        HIP_TRY(c, hipMalloc(&c->st_img[slot], img_bytes(c) * c->max_batch));
-        HIP_TRY(c, hipMalloc(&c->st_flow[slot], flow_bytes(c) * c->max_batch));
-        HIP_TRY(c, hipMalloc(&c->st_seg[slot], seg_bytes(c) * c->max_batch));
-        // planes the path never reads (flow 2,3; the target frame's label map) are never copied either: defined contents all the same
-        { int rc = zero_now(c, c->st_flow[slot], flow_bytes(c) * c->max_batch); if (rc) return rc; }
-        { int rc = zero_now(c, c->st_seg[slot], seg_bytes(c) * c->max_batch); if (rc) return rc; }
-        if (needs_depth(c)) HIP_TRY(c, hipMalloc(&c->st_depth[slot], depth_bytes(c) * c->max_batch));      // copied whole by every submit
-    }
+    if (!c->stream_sets[slot].img) { int rc = alloc_input_set(c, &c->stream_sets[slot], true); if (rc) return rc; }
+    return DAVO_OK;
+}
+
+// windows b0.. of a batch's planes
+Inputs from_window(const davo_ctx* c, const Inputs& in, int b0) {
+    const PlaneBytes nb = plane_bytes(c);
+    auto at = [b0](const void* q, size_t bytes) -> const void* { return q ? static_cast<const uint8_t*>(q) + bytes * b0 : nullptr; };
+    return Inputs{at(in.img, nb.img), at(in.flow, nb.flow), at(in.seg, nb.seg), at(in.depth, nb.depth)};
+}
+
+// Host -> device, on stream s: windows [b0, b0 + nb) of the caller's arrays into the same windows of a staging set.  Only what the path
+// reads crosses PCIe: flow planes 0,1 (davo.py:978-982); the label maps; for the depth sources all three depth planes (the target's
+// depth enters every frame's descriptor, davo.py:1109).  sources_only_seg: unless the variant reads the target frame's label map too
+// (-segmask_all-static, the with-target class-table sources), only the two source frames' maps go (davo.py:998-1004, 1408-1412), in
+// batches of four windows and more.
+int stage_inputs(davo_ctx* c, const InputSet& set, const Inputs& host, int b0, int nb, bool sources_only_seg, hipStream_t s) {
+    const PlaneBytes n = plane_bytes(c);
+    const Inputs src = from_window(c, host, b0);
+    auto dst = [b0](void* q, size_t bytes) { return static_cast<uint8_t*>(q) + bytes * b0; };
+    HIP_TRY(c, hipMemcpyAsync(dst(set.img, n.img), src.img, n.img * nb, hipMemcpyHostToDevice, s));
+    if (nb == 1) HIP_TRY(c, hipMemcpyAsync(dst(set.flow, n.flow), src.flow, n.flow / 2, hipMemcpyHostToDevice, s));
+    else HIP_TRY(c, hipMemcpy2DAsync(dst(set.flow, n.flow), n.flow, src.flow, n.flow, n.flow / 2, nb, hipMemcpyHostToDevice, s));
+    if (!sources_only_seg || att_tgt_attended(c->v.att_source) || nb < 4) HIP_TRY(c, hipMemcpyAsync(dst(set.seg, n.seg), src.seg, n.seg * nb, hipMemcpyHostToDevice, s));
+    else
+        for (int plane = 0; plane < 3; plane += 2)
+            HIP_TRY(c, hipMemcpy2DAsync(dst(set.seg, n.seg) + plane * (n.seg / 3), n.seg, (const uint8_t*)src.seg + plane * (n.seg / 3), n.seg,
+                                        n.seg / 3, nb, hipMemcpyHostToDevice, s));
+    if (src.depth) HIP_TRY(c, hipMemcpyAsync(dst(set.depth, n.depth), src.depth, n.depth * nb, hipMemcpyHostToDevice, s));
     return DAVO_OK;
 }
 
@@ -622,35 +654,23 @@ static int submit_entry(davo_ctx* c, int B, const uint8_t* img, const float* flo
     activate_slot(c, slot);
     c->next_slot = (c->next_slot + 1) % c->inflight;
     hipStream_t s = c->stream;
-    const size_t nb_img = img_bytes(c), nb_flow = flow_bytes(c), nb_seg = seg_bytes(c);
-    // H2D on the slot's stream, in order behind the forward that last read this staging set.  Only what the path reads crosses PCIe:
-    // flow planes 0,1 (davo.py:978-982) and, unless the variant reads the target frame's label map too (-segmask_all-static, the
-    // with-target class-table sources), the two source frames' maps (davo.py:998-1004, 1408-1412).
-    HIP_TRY(c, hipMemcpyAsync(c->st_img[slot], img, nb_img * B, hipMemcpyHostToDevice, s));
-    if (B == 1) HIP_TRY(c, hipMemcpyAsync(c->st_flow[slot], flow, nb_flow / 2, hipMemcpyHostToDevice, s));
-    else HIP_TRY(c, hipMemcpy2DAsync(c->st_flow[slot], nb_flow, flow, nb_flow, nb_flow / 2, B, hipMemcpyHostToDevice, s));
-    if (att_tgt_attended(c->v.att_source) || B < 4) HIP_TRY(c, hipMemcpyAsync(c->st_seg[slot], seg, nb_seg * B, hipMemcpyHostToDevice, s));
-    else
-        for (int plane = 0; plane < 3; plane += 2)
-            HIP_TRY(c, hipMemcpy2DAsync((uint8_t*)c->st_seg[slot] + plane * (nb_seg / 3), nb_seg, (const uint8_t*)seg + plane * (nb_seg / 3), nb_seg,
-                                        nb_seg / 3, B, hipMemcpyHostToDevice, s));
-    // depth sources: all three planes are read (the target's depth enters every frame's descriptor, davo.py:1109)
-    void* const st_depth = depth ? c->st_depth[slot] : nullptr;
-    if (depth) HIP_TRY(c, hipMemcpyAsync(st_depth, depth, depth_bytes(c) * B, hipMemcpyHostToDevice, s));
+    // H2D on the slot's stream, in order behind the forward that last read this staging set
+    const InputSet& set = c->stream_sets[slot];
+    { int rc = stage_inputs(c, set, Inputs{img, flow, seg, depth}, 0, B, true, s); if (rc) return rc; }
     // the caller keeps a batch's inputs unchanged for `hold` more submits.  With hold >= STREAM_POSES the pose ring already implies it
     // (a batch is delivered - so its copies are long done - before the eighth submit after it returns): no event then
     const bool track_copy = hold < STREAM_POSES;
     if (track_copy) HIP_TRY(c, hipEventRecord(c->st_copied[pr], s));
 
-    bool snap = false;
-    if (ticketed) { int rc = ticket_begin(c, B, c->st_img[slot], c->st_flow[slot], c->st_seg[slot], st_depth, &snap, true); if (rc) return rc; }
+    Ticket t{};
+    if (ticketed) { int rc = ticket_begin(c, B, set.view(), &t, true); if (rc) return rc; }
     ++c->n_issued;                    // (no pose span: a pose ring entry is not reused before its batch has been delivered)
-    int rc = forward_device(c, B, c->st_img[slot], c->st_flow[slot], c->st_seg[slot], st_depth, c->d_pose_ring[pr]);
+    int rc = forward_device(c, B, set.view(), c->d_pose_ring[pr]);
     const unsigned seq = c->snap_seq_issued;
     bool has_ticket = false;
     if (ticketed) {
         const size_t before = c->tickets.size();
-        rc = ticket_end(c, rc, B, c->st_img[slot], c->st_flow[slot], c->st_seg[slot], st_depth, c->d_pose_ring[pr], snap, c->h_pose_ring[pr]);
+        rc = ticket_end(c, rc, t, c->d_pose_ring[pr], c->h_pose_ring[pr]);
         has_ticket = c->tickets.size() > before;            // (the weight guard's float32 batches get no ticket)
     } else if (rc == DAVO_OK && c->f32_fallback) ++c->n_f32_batches;
     if (rc) return rc;
@@ -698,14 +718,9 @@ static int forward_entry(davo_ctx* c, int B, const uint8_t* img, const float* fl
     { int rc = deliver_all(c); if (rc) return rc; }          // davo_submit batches still under way: delivered first
     { int rc = sync_all_slots(c); if (rc) return rc; }       // the host path owns the single staging buffer set
     activate_slot(c, 0);
-    const size_t HW = (size_t)c->H * c->W;
-    const size_t nb_img = HW * 9, nb_flow = HW * 8 * sizeof(float), nb_seg = HW * 3 * sizeof(float);
-    if (!c->s_img) {
-        HIP_TRY(c, hipMalloc(&c->s_img, nb_img * c->max_batch));
-        HIP_TRY(c, hipMalloc(&c->s_flow, nb_flow * c->max_batch));
-        HIP_TRY(c, hipMalloc(&c->s_seg, nb_seg * c->max_batch));
+    if (!c->host_set.img) {
+        { int rc = alloc_input_set(c, &c->host_set, false); if (rc) return rc; }
         HIP_TRY(c, hipMalloc(&c->s_pose, (size_t)c->max_batch * 12 * sizeof(float)));
-        if (needs_depth(c)) HIP_TRY(c, hipMalloc(&c->s_depth, depth_bytes(c) * c->max_batch));
     }
     if (!c->copy_stream) HIP_TRY(c, hipStreamCreateWithFlags(&c->copy_stream, hipStreamNonBlocking));
     { int rc = judge_all(c); if (rc) return rc; }               // device-path batches issued before this call
@@ -742,16 +757,8 @@ static int forward_entry(davo_ctx* c, int B, const uint8_t* img, const float* fl
     unsigned seq = 0;
     for (int i = 0; i < nchunks; ++i) {
         const int b0 = i * chunk, nb = std::min(chunk, B - b0);
-        uint8_t* di = (uint8_t*)c->s_img + nb_img * b0;
-        uint8_t* df = (uint8_t*)c->s_flow + nb_flow * b0;
-        uint8_t* ds = (uint8_t*)c->s_seg + nb_seg * b0;
         hipStream_t cs = nchunks == 1 ? c->stream : c->copy_stream;
-        HIP_TRY(c, hipMemcpyAsync(di, img + nb_img * b0, nb_img * nb, hipMemcpyHostToDevice, cs));
-        if (nb == 1) HIP_TRY(c, hipMemcpyAsync(df, (const uint8_t*)flow + nb_flow * b0, nb_flow / 2, hipMemcpyHostToDevice, cs));
-        else HIP_TRY(c, hipMemcpy2DAsync(df, nb_flow, (const uint8_t*)flow + nb_flow * b0, nb_flow, nb_flow / 2, nb, hipMemcpyHostToDevice, cs));
-        HIP_TRY(c, hipMemcpyAsync(ds, (const uint8_t*)seg + nb_seg * b0, nb_seg * nb, hipMemcpyHostToDevice, cs));
-        uint8_t* dd = depth ? (uint8_t*)c->s_depth + nb_seg * b0 : nullptr;          // depth planes: the label maps' size
-        if (depth) HIP_TRY(c, hipMemcpyAsync(dd, (const uint8_t*)depth + nb_seg * b0, nb_seg * nb, hipMemcpyHostToDevice, cs));
+        { int rc = stage_inputs(c, c->host_set, Inputs{img, flow, seg, depth}, b0, nb, false, cs); if (rc) return rc; }      // the label maps whole
         if (nchunks > 1) {
             HIP_TRY(c, hipEventRecord(c->copy_done[i], c->copy_stream));
             HIP_TRY(c, hipStreamWaitEvent(c->stream, c->copy_done[i], 0));
@@ -762,7 +769,7 @@ static int forward_entry(davo_ctx* c, int B, const uint8_t* img, const float* fl
             c->snap = SnapArgs{};
             c->snap.record = c->d_range_base; c->snap.host_mirror = c->h_range_dev; c->snap.seq = seq; c->snap.B = nb;
         }
-        int rc = forward_device(c, nb, di, (const float*)df, (const float*)ds, dd, (float*)c->s_pose + (size_t)b0 * 12);
+        int rc = forward_device(c, nb, from_window(c, c->host_set.view(), b0), (float*)c->s_pose + (size_t)b0 * 12);
         c->snap = SnapArgs{};
         if (rc) return rc;
         f32_fallback |= c->f32_fallback;
@@ -781,7 +788,7 @@ static int forward_entry(davo_ctx* c, int B, const uint8_t* img, const float* fl
     if (rc == DAVO_OK) note_seen(c, raw, c->act_shift);
     if (rc == DAVO_ERR_RANGE && c->opt_auto_range) {
         // the staged copy of the batch is still in HBM: re-issue it whole (recalibrated, or on the float32 kernels)
-        rc = recover_batch(c, [&] { Ticket t{}; t.B = B; t.img = c->s_img; t.flow = c->s_flow; t.seg = c->s_seg; t.depth = depth ? c->s_depth : nullptr; t.pose = c->s_pose; t.ring = -1; t.stream = c->stream; t.issue = ~0ull; return t; }());
+        rc = recover_batch(c, [&] { Ticket t{}; t.B = B; t.in = c->host_set.view(); t.pose = c->s_pose; t.ring = -1; t.stream = c->stream; t.issue = ~0ull; return t; }());
         if (rc == DAVO_OK) HIP_TRY(c, hipMemcpy(pose_out, c->s_pose, (size_t)B * 12 * sizeof(float), hipMemcpyDeviceToHost));
     }
     return rc;
@@ -843,7 +850,7 @@ static int calibrate_entry(davo_ctx* c, int B, const void* d_img, const void* d_
     activate_slot(c, 0);
     float* d_pose = nullptr;
     HIP_TRY(c, hipMalloc(reinterpret_cast<void**>(&d_pose), (size_t)B * 12 * sizeof(float)));
-    const int rc = calibrate_on(c, B, d_img, d_flow, d_seg, d_depth, d_pose);
+    const int rc = calibrate_on(c, B, Inputs{d_img, d_flow, d_seg, d_depth}, d_pose);
     (void)hipFree(d_pose);
     if (rc == DAVO_OK && shifts_out) for (int i = 0; i < 6; ++i) shifts_out[i] = c->act_shift[i];
     return rc;
@@ -873,11 +880,10 @@ void davo_destroy(davo_ctx* c) {
     }
     for (auto e : c->copy_done) (void)hipEventDestroy(e);
     if (c->copy_stream) { (void)hipStreamSynchronize(c->copy_stream); (void)hipStreamDestroy(c->copy_stream); }
-    for (int k = 0; k < STREAM_SETS; ++k)
-        for (void* q : {c->st_img[k], c->st_flow[k], c->st_seg[k], c->st_depth[k]}) if (q) (void)hipFree(q);
-    // the range-recovery ring: the input snapshots (depth planes included), the records' host mirror and the stream that reads them
-    for (int r = 0; r < RANGE_RING; ++r)
-        for (void* q : {c->snap_img[r], c->snap_flow[r], c->snap_seg[r], c->snap_depth[r]}) if (q) (void)hipFree(q);
+    free_input_set(c->host_set);
+    for (InputSet& set : c->stream_sets) free_input_set(set);
+    // the range-recovery ring: the input snapshots, the records' host mirror and the stream that reads them
+    for (InputSet& set : c->snap_sets) free_input_set(set);
     if (c->read_stream) { (void)hipStreamSynchronize(c->read_stream); (void)hipStreamDestroy(c->read_stream); }
     if (c->h_range) (void)hipHostFree(c->h_range);
     for (int k = 0; k < STREAM_POSES; ++k) {
@@ -887,7 +893,7 @@ void davo_destroy(davo_ctx* c) {
         if (c->st_copied[k]) (void)hipEventDestroy(c->st_copied[k]);
     }
     if (c->h_sync_pose) (void)hipHostFree(c->h_sync_pose);
-    void* misc[] = {c->d_reissue_pose, c->d_range_base, c->d_splitk, c->d_pose_tiles, c->d_w1patch, c->d_w2patch, c->d_w3patch, c->d_w1patch_f32, c->d_w2patch_f32, c->d_w3patch_f32, c->d_zeros, c->d_wpred, c->d_bpred, c->s_img, c->s_flow, c->s_seg, c->s_depth, c->s_pose};
+    void* misc[] = {c->d_reissue_pose, c->d_range_base, c->d_splitk, c->d_pose_tiles, c->d_w1patch, c->d_w2patch, c->d_w3patch, c->d_w1patch_f32, c->d_w2patch_f32, c->d_w3patch_f32, c->d_zeros, c->d_wpred, c->d_bpred, c->s_pose};
     for (auto p : misc) if (p) (void)hipFree(p);
     for (auto& kv : c->tile_orders) if (kv.second) (void)hipFree(kv.second);
     for (auto& pe : c->prof_entries)
@@ -1111,8 +1117,8 @@ int davo_debug_read(davo_ctx* c, const char* tensor, float* host_out, size_t n_f
     if (t == "att_table") { src = c->d_tab; n = (size_t)c->last_B * 3 * NCLS; }
     else if (t == "packed") {
         if (!c->packed_valid) {          // fused path: materialise the packed tensor on demand from the last inputs
-            HIP_TRY(c, launch_mask_pack(16, static_cast<const uint8_t*>(c->last_img), static_cast<const float*>(c->last_flow),
-                                        static_cast<const float*>(c->last_seg), c->d_tab, c->v, c->last_B, c->H, c->W, c->d_packed, c->stream));
+            HIP_TRY(c, launch_mask_pack(16, static_cast<const uint8_t*>(c->last_in.img), static_cast<const float*>(c->last_in.flow),
+                                        static_cast<const float*>(c->last_in.seg), c->d_tab, c->v, c->last_B, c->H, c->W, c->d_packed, c->stream));
             c->packed_valid = true;
         }
         src = c->d_packed; n = NB * c->H * c->W * c->packed_ld;

@@ -3,7 +3,7 @@
 // conv_igemm_h3.h, conv_igemm_h3s.h, conv_patch_h3.h and prologue.h and are launched through launch.h.
 //
 // Translation units (built in parallel by davo_amd/_lib.py, linked into one shared library):
-//   api.hip         extern "C" entry points (context, weights, forward, calibration, test hooks)
+//   api.hip         extern "C" entry points (context, weights, forward, calibration, test hooks); owns the InputSets
 //   forward.hip     the forward plan of the pose path (which kernel, which buffers, in what order)
 //   plan.hip        launch planning: tile shapes and whole-round launch splits (pure host logic)
 //   weights.hip     weight re-layout: HWIO float32 -> packed f32 / split-fp16 operands
@@ -67,6 +67,18 @@ struct Slot {
     unsigned* d_counters = nullptr;              // "last workgroup" tickets (pose_tail.h): [0] cnv7's pose tail, [1 + b] triplet b's squeeze, [1 + max_batch + t] tile t of a split-K launch
 };
 
+// The planes of one batch, as every host function hands them on: img [B][H][W][9] bytes, flow [B][8][H][W], seg [B][3][H][W] and
+// depth [B][3][H][W] float32 in file order (src0, tgt, src1).  depth is read by the depth sources only (att_source 11, 12) and is
+// null for every other variant.
+struct Inputs { const void *img, *flow, *seg, *depth; };
+
+// Device room of the context for max_batch windows of every plane the variant reads (api.hip: alloc_input_set / free_input_set);
+// depth stays null unless the variant reads it, so a set's view says by itself whether there are depth planes to carry along.
+struct InputSet {
+    void *img = nullptr, *flow = nullptr, *seg = nullptr, *depth = nullptr;
+    Inputs view() const { return Inputs{img, flow, seg, depth}; }
+};
+
 // A batch davo_forward_device has issued whose f16x3 range record has not been judged yet.  Every such batch owns one slot of a
 // small ring: a range record of its own and - unless the caller declared its inputs stable - room for a context-owned copy of
 // its inputs, which the batch's last kernel fills if (and only if) the record will fail the verdict, so that the re-issue reads
@@ -75,11 +87,10 @@ constexpr int RANGE_RING = 8;
 constexpr int SK_TILE_COUNTERS = 256;            // tiles of a split-K launch whose fix-up is folded in (forward.hip): at most one per CU
 struct Ticket {
     int B;
-    const void *img, *flow, *seg;              // what a re-issue reads: the ring slot's snapshot, or the caller's buffers ("stable_inputs")
-    const void* depth;                         // ... and the depth planes of a depth-source variant (else null)
+    Inputs in;                                 // what a re-issue reads: the ring slot's snapshot, or the caller's buffers ("stable_inputs")
     void* pose;
     int ring;
-    bool snap;                                 // img / flow / seg are the ring slot's copy
+    bool snap;                                 // `in` is the ring slot's copy
     bool frozen;                               // raw holds the batch's record (read before the ring's records were reset)
     unsigned raw[RANGE_WORDS];
     unsigned seq;                              // the batch's sequence number: its last kernel writes it into the slot's host mirror
@@ -171,11 +182,11 @@ struct davo_ctx {
     int packed_ld = 8;
     int last_B = 0;
     bool packed_valid = true;                  // false when cnv1 consumed the raw inputs directly (fused)
-    const void *last_img = nullptr, *last_flow = nullptr, *last_seg = nullptr;
+    davo::Inputs last_in{};                    // the last forward's inputs: davo_debug_read("packed") re-packs from them after a fused cnv1
     int last_plan[7][2] = {};                  // per layer, per launch: 128-row M tiles * 1000 + tile id / BN (reported by the bench)
     // host-API staging
-    void *s_img = nullptr, *s_flow = nullptr, *s_seg = nullptr, *s_pose = nullptr;
-    void* s_depth = nullptr;                   // depth-source variants only
+    davo::InputSet host_set;                   // davo_forward's staging set (allocated by its first call)
+    void* s_pose = nullptr;
     float* h_sync_pose = nullptr;              // davo_forward: page-locked bounce buffer of the poses
     hipStream_t copy_stream = nullptr;         // H2D of the next sub-batch runs here while the previous one computes
     std::vector<hipEvent_t> copy_done;
@@ -193,8 +204,7 @@ struct davo_ctx {
     std::deque<davo::Ticket> tickets;
     bool ring_busy[davo::RANGE_RING] = {};
     int ring_next = 0;
-    void *snap_img[davo::RANGE_RING] = {}, *snap_flow[davo::RANGE_RING] = {}, *snap_seg[davo::RANGE_RING] = {};
-    void* snap_depth[davo::RANGE_RING] = {};   // depth-source variants only: the depth planes travel with the other three
+    davo::InputSet snap_sets[davo::RANGE_RING];        // the ring slots' input snapshots (allocated by the first ticket that wants one)
     davo::SnapArgs snap{};                     // set around a ticketed batch: its last kernel copies the inputs if the record fails (prologue.h)
     hipStream_t read_stream = nullptr;
     unsigned batch_seq = 0, snap_seq_issued = 0;   // sequence number of the last ticketed batch (never 0 for a batch)
@@ -208,8 +218,7 @@ struct davo_ctx {
     long long n_recalibrations = 0, n_f32_batches = 0, n_reissued = 0;
     int host_chunk = 8;                        // davo_forward: windows per sub-batch (davo_set_option "host_chunk"; 0 = whole batch)
     // streaming host entry (davo_submit / davo_wait): staging input sets, pose ring, undelivered batches in issue order
-    void *st_img[davo::STREAM_SETS] = {}, *st_flow[davo::STREAM_SETS] = {}, *st_seg[davo::STREAM_SETS] = {};     // one staging set per in-flight slot
-    void* st_depth[davo::STREAM_SETS] = {};    // ... with the depth planes for a depth-source variant
+    davo::InputSet stream_sets[davo::STREAM_SETS];     // one staging set per in-flight slot (allocated by the slot's first davo_submit)
     hipEvent_t st_copied[davo::STREAM_POSES] = {};             // "the H2D copies of the batch in pose ring entry k are done" (recorded only for hold < STREAM_POSES)
     bool copy_tracked[davo::STREAM_POSES] = {};
     float *d_pose_ring[davo::STREAM_POSES] = {}, *h_pose_ring[davo::STREAM_POSES] = {};
@@ -262,6 +271,14 @@ inline void same_pad(int in, int k, int stride, int rate, int* out, int* before)
     *before = total / 2;
 }
 
+// bytes of one window of each input plane
+struct PlaneBytes { size_t img, flow, seg, depth; };
+inline PlaneBytes plane_bytes(const davo_ctx* c) {
+    const size_t HW = (size_t)c->H * c->W;
+    return PlaneBytes{HW * 9, HW * 8 * sizeof(float), HW * 3 * sizeof(float), HW * 3 * sizeof(float)};      // depth: [3,H,W,1] float32 like the label maps (davo.py:991-996)
+}
+inline bool needs_depth(const davo_ctx* c) { return att_desc_depth(c->v.att_source); }
+
 inline int ilog2_exact(int v) {
     int l = 0;
     while ((1 << l) < v) ++l;
@@ -306,9 +323,7 @@ inline void split_f16(float v, _Float16* hi, _Float16* lo) {
 
 // ---- forward.hip ----------------------------------------------------------------------------
 void activate_slot(davo_ctx* c, int i);
-// d_depth: [B][3][H][W] float32 depth planes in file order (src0, tgt, src1), read by the depth sources only (att_source 11, 12;
-// null otherwise)
-int forward_device(davo_ctx* c, int B, const void* d_img, const void* d_flow, const void* d_seg, const void* d_depth, void* d_pose);
+int forward_device(davo_ctx* c, int B, const Inputs& in, void* d_pose);
 // f16x3: verdict on the range record (d_range) read back from the device; DAVO_ERR_RANGE names the layer
 int check_range(davo_ctx* c, const unsigned* raw /*[RANGE_WORDS]*/, const int* shifts = nullptr);
 

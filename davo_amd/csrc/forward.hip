@@ -157,6 +157,21 @@ const int* tile_order_for(davo_ctx* c, int li, int kind, int bm, int mtile0, int
     return dev;
 }
 
+// ---- per-slot scratch -------------------------------------------------------------------------------
+int slot_idx(const davo_ctx* c) { return (c->next_slot + c->inflight - 1) % c->inflight; }      // the slot this batch runs in
+
+// A scratch buffer of the context with one region of *floats floats per in-flight slot: grown (behind every stream) if this launch
+// needs more per slot than it has, then -> the region of this batch's slot.  extra_bytes: room behind the four regions.
+int slot_scratch(davo_ctx* c, float** buf, size_t* floats, size_t need, float** region, size_t extra_bytes = 0) {
+    if (need > *floats) {
+        if (*buf) { int rs = sync_all_slots(c); if (rs) return rs; HIP_TRY(c, hipFree(*buf)); *buf = nullptr; }
+        HIP_TRY(c, hipMalloc(reinterpret_cast<void**>(buf), need * sizeof(float) * 4 + extra_bytes));   // x4: one region per in-flight slot
+        *floats = need;
+    }
+    *region = *buf + (size_t)slot_idx(c) * *floats;
+    return DAVO_OK;
+}
+
 // ---- one conv layer, FP32-MFMA path ---------------------------------------------------------------
 // fuse_pose (cnv7): the pose head runs in the epilogue (conv_igemm.h); *pose_mt receives the layer's M tiles
 int run_conv_layer(davo_ctx* c, int li, const float* x, int x_ld, int Hin, int Win, float* y, int y_ld, int NB, bool fuse_pose = false, int* pose_mt = nullptr) {
@@ -179,14 +194,8 @@ int run_conv_layer(davo_ctx* c, int li, const float* x, int x_ld, int Hin, int W
     std::vector<Launch> plan = plan_layer(mtiles, L.npad, L.groups, c->ncu);
     if (li == 0 && L.cout <= 16 && c->opt_f32_n16) plan = {{0, mtiles, 16}};      // cnv1 on the 128x16 tile at every batch size (conv_igemm.h, N16)
     if (fuse_pose) {
-        const size_t need = (size_t)L.groups * mtiles * 8 * 6;
-        if (need > c->pose_tiles_floats) {
-            if (c->d_pose_tiles) { int rs = sync_all_slots(c); if (rs) return rs; HIP_TRY(c, hipFree(c->d_pose_tiles)); c->d_pose_tiles = nullptr; }
-            HIP_TRY(c, hipMalloc(reinterpret_cast<void**>(&c->d_pose_tiles), need * sizeof(float) * 4));   // x4: one region per in-flight slot
-            c->pose_tiles_floats = need;
-        }
-        const int slot_idx = (c->next_slot + c->inflight - 1) % c->inflight;
-        p.pose_w = c->d_wpred; p.pose_partial = c->d_pose_tiles + (size_t)slot_idx * c->pose_tiles_floats;
+        { int rs = slot_scratch(c, &c->d_pose_tiles, &c->pose_tiles_floats, (size_t)L.groups * mtiles * 8 * 6, &p.pose_partial); if (rs) return rs; }
+        p.pose_w = c->d_wpred;
         p.pose_P = Ho * Wo; p.pose_mt = mtiles;
         if (pose_mt) *pose_mt = mtiles;
     }
@@ -290,18 +299,12 @@ int run_conv_layer_h3(davo_ctx* c, int li, const void* x, int x_ch, int Hin, int
         plan = {{0, p.M, best}};
         const TileShape ts = tile_shape(best);
         const int mt = (p.M + ts.bm - 1) / ts.bm, ntn = L.npad_h / ts.bn;
-        const size_t need = (size_t)L.groups * mt * ntn * 6;
-        if (need > c->pose_tiles_floats) {
-            if (c->d_pose_tiles) { int rs = sync_all_slots(c); if (rs) return rs; HIP_TRY(c, hipFree(c->d_pose_tiles)); c->d_pose_tiles = nullptr; }
+        size_t debug_bytes = 0;
 #ifdef DAVO_POSE_DEBUG
-            HIP_TRY(c, hipMalloc(reinterpret_cast<void**>(&c->d_pose_tiles), need * sizeof(float) * 4 + (size_t)L.groups * mt * ntn * 512 * 20 * sizeof(float)));
-#else
-            HIP_TRY(c, hipMalloc(reinterpret_cast<void**>(&c->d_pose_tiles), need * sizeof(float) * 4));   // x4: one region per in-flight slot
+        debug_bytes = (size_t)L.groups * mt * ntn * 512 * 20 * sizeof(float);
 #endif
-            c->pose_tiles_floats = need;
-        }
-        const int slot_idx = (c->next_slot + c->inflight - 1) % c->inflight;      // the slot this batch runs in
-        p.y_mode = 2; p.pose_w = c->d_wpred; p.pose_partial = c->d_pose_tiles + (size_t)slot_idx * c->pose_tiles_floats;
+        { int rs = slot_scratch(c, &c->d_pose_tiles, &c->pose_tiles_floats, (size_t)L.groups * mt * ntn * 6, &p.pose_partial, debug_bytes); if (rs) return rs; }
+        p.y_mode = 2; p.pose_w = c->d_wpred;
         p.pose_P = P; p.pose_mt = mt;
         if (pose_out) {      // the launch's last workgroup adds the tiles and writes the poses (pose_tail.h)
             p.pose_counter = c->d_counters; p.pose_bias = c->d_bpred; p.pose_out = pose_out;
@@ -384,14 +387,8 @@ int run_conv_layer_h3(davo_ctx* c, int li, const void* x, int x_ch, int Hin, int
         const int per_cu = ts.lds * 2 <= 160 * 1024 ? 2 : 1;
         const int S = (fits(4) && tiles * 4 <= (long)per_cu * c->ncu && tiles * 2 <= c->ncu) ? 4 : (fits(2) && tiles * 2 <= c->ncu ? 2 : 1);       // two parts at two per CU (B = 2) measured slower: 54 -> 57 us
         if (S > 1) {
-            const size_t need = (size_t)p.M * S * L.cout;
-            if (need > c->splitk_floats) {
-                if (c->d_splitk) { int rs = sync_all_slots(c); if (rs) return rs; HIP_TRY(c, hipFree(c->d_splitk)); c->d_splitk = nullptr; }
-                HIP_TRY(c, hipMalloc(reinterpret_cast<void**>(&c->d_splitk), need * sizeof(float) * 4));   // x4: one region per in-flight slot
-                c->splitk_floats = need;
-            }
-            const int slot_idx = (c->next_slot + c->inflight - 1) % c->inflight;
-            float* part = c->d_splitk + (size_t)slot_idx * c->splitk_floats;
+            float* part = nullptr;
+            { int rs = slot_scratch(c, &c->d_splitk, &c->splitk_floats, (size_t)p.M * S * L.cout, &part); if (rs) return rs; }
             ConvParamsH ps = p;
             ps.nchunks = L.nchunks_h / S;
             ps.g_x_boff = (L.cin / S) * 4; ps.g_w = (long)ps.nchunks * 128; ps.g_bias = L.npad_h; ps.g_y_coff = L.cout;
@@ -458,126 +455,45 @@ int run_conv_layer_h3(davo_ctx* c, int li, const void* x, int x_ch, int Hin, int
     return DAVO_OK;
 }
 
-// cnv1 of the f16x3 path from an LDS-staged input patch (conv_patch_h3.h).  fused: the patch is built
-// from the raw inputs (mask + pack fused in); otherwise it is copied from the packed tensor.
-int run_cnv1_patch(davo_ctx* c, bool fused, const void* d_img, const void* d_flow, const void* d_seg, void* y, int NB) {
-    const ConvLayer& L = c->L[0];
-    ConvPatchParams p{};
-    int Ho, Wo, pt, pl;
-    same_pad(c->H, 7, 2, 1, &Ho, &pt);
-    same_pad(c->W, 7, 2, 1, &Wo, &pl);
-    p.x = reinterpret_cast<const uint8_t*>(c->d_packed); p.w = c->d_w1patch; p.bias = L.d_bh; p.y = static_cast<uint8_t*>(y);
-    p.zeros = reinterpret_cast<const uint8_t*>(c->d_zeros);
-    p.H = c->H; p.W = c->W; p.Ho = Ho; p.Wo = Wo; p.pad_t = pt; p.pad_l = pl;
-    p.tiles_x = (Wo + cp1::TW - 1) / cp1::TW; p.tiles_y = (Ho + cp1::TH - 1) / cp1::TH;
-    p.out_scale = ldexpf(1.0f / L.wscale, c->act_shift[0]);
-    p.bias_scale = L.wscale;
-    p.range = c->d_range;
-    p.ntiles = NB * p.tiles_x * p.tiles_y;
-    p.img = static_cast<const uint8_t*>(d_img); p.flow = static_cast<const float*>(d_flow);
-    p.seg = static_cast<const float*>(d_seg); p.tab = c->d_tab; p.v = c->v;
-    c->last_plan[0][0] = ((NB * Ho * Wo + 127) / 128) * 1000 + 99; c->last_plan[0][1] = 0;
-    const int nblk = p.ntiles < 3 * c->ncu ? p.ntiles : 3 * c->ncu;   // 3 workgroups per CU, each walks its tiles
-    if (const char* e = tuning_env("DAVO_PDBG")) p.dbg = atoi(e);      // tuning build only
-    ProfScope ps(c, "cnv1");
-    HIP_TRY(c, launch_cnv1_patch(fused, p, nblk, c->stream));
-    return DAVO_OK;
-}
+// cnv1 / cnv2 / cnv3 (li 0..2) from an LDS-staged input patch: conv_patch_h3.h (x and y split-fp16 blocked) or, f32, conv_patch_f32.h
+// (x and y float32 NHWC).  fused (f16x3 cnv1): the patch is built from the raw inputs (mask + pack fused in); otherwise it is
+// copied from x, for cnv1 the packed tensor.
+struct PatchLayer { int tw, th, per_cu, plan_id; };       // output tile; workgroups per CU, each walks its tiles; id in last_plan
+constexpr PatchLayer PATCH_LAYERS[3] = {
+    {cp1::TW, cp1::TH, 3, 99},
+    {cp2::TW, cp2::TH, 2, 98},       // f16x3: 120 weight registers per lane; float32: three per CU measured 4 % slower
+    {cp3::TW, cp3::TH, 3, 97}};      // its padding, cp3::RATE on every side, is what SAME padding gives a 3x3 at dilation 2
 
-// cnv2 of the f16x3 path from an LDS-staged input patch (conv_patch_h3.h, conv_patch_cnv2_h3)
-int run_cnv2_patch(davo_ctx* c, const void* x, void* y, int NB) {
-    const ConvLayer& L = c->L[1];
+int run_patch_layer(davo_ctx* c, int li, bool f32, const void* x, void* y, int NB, bool fused = false, const Inputs& in = Inputs{}) {
+    const ConvLayer& L = c->L[li];
+    const PatchLayer& t = PATCH_LAYERS[li];
+    const uint8_t* const w_h3[3] = {c->d_w1patch, c->d_w2patch, c->d_w3patch};
+    const float* const w_f32[3] = {c->d_w1patch_f32, c->d_w2patch_f32, c->d_w3patch_f32};
+    const int Hin[3] = {c->H, c->H1, c->H2}, Win[3] = {c->W, c->W1, c->W2};
     ConvPatchParams p{};
-    int Ho, Wo, pt, pl;
-    same_pad(c->H1, 5, 2, 1, &Ho, &pt);
-    same_pad(c->W1, 5, 2, 1, &Wo, &pl);
-    p.x = static_cast<const uint8_t*>(x); p.w = c->d_w2patch; p.bias = L.d_bh; p.y = static_cast<uint8_t*>(y);
+    same_pad(Hin[li], L.KS, L.stride, L.rate, &p.Ho, &p.pad_t);
+    same_pad(Win[li], L.KS, L.stride, L.rate, &p.Wo, &p.pad_l);
+    p.x = static_cast<const uint8_t*>(x); p.w = f32 ? reinterpret_cast<const uint8_t*>(w_f32[li]) : w_h3[li];
+    p.bias = f32 ? L.d_b : L.d_bh; p.y = static_cast<uint8_t*>(y);
     p.zeros = reinterpret_cast<const uint8_t*>(c->d_zeros);
-    p.H = c->H1; p.W = c->W1; p.Ho = Ho; p.Wo = Wo; p.pad_t = pt; p.pad_l = pl;
-    p.tiles_x = (Wo + cp2::TW - 1) / cp2::TW; p.tiles_y = (Ho + cp2::TH - 1) / cp2::TH;
-    p.out_scale = ldexpf(1.0f / L.wscale, c->act_shift[1] - c->act_shift[0]);
-    p.bias_scale = ldexpf(L.wscale, c->act_shift[0]);
-    p.range = c->d_range ? c->d_range + 1 : nullptr;
+    p.H = Hin[li]; p.W = Win[li];
+    p.tiles_x = (p.Wo + t.tw - 1) / t.tw; p.tiles_y = (p.Ho + t.th - 1) / t.th;
     p.ntiles = NB * p.tiles_x * p.tiles_y;
-    c->last_plan[1][0] = ((NB * Ho * Wo + 127) / 128) * 1000 + 98; c->last_plan[1][1] = 0;
-    const int nblk = p.ntiles < 2 * c->ncu ? p.ntiles : 2 * c->ncu;   // 2 workgroups per CU (120 weight registers per lane), each walks its tiles
-    if (const char* e = tuning_env("DAVO_PDBG")) p.dbg = atoi(e);      // tuning build only
-    ProfScope ps(c, "cnv2");
-    HIP_TRY(c, launch_cnv2_patch(p, nblk, c->stream));
-    return DAVO_OK;
-}
-
-// cnv1 of the float32 mode from an LDS-staged input patch (conv_patch_f32.h); x: the packed float32 input [NB][H][W][8], y: [NB][H1][W1][16]
-int run_cnv1_patch_f32(davo_ctx* c, const void* x, void* y, int NB) {
-    const ConvLayer& L = c->L[0];
-    ConvPatchParams p{};
-    int Ho, Wo, pt, pl;
-    same_pad(c->H, 7, 2, 1, &Ho, &pt);
-    same_pad(c->W, 7, 2, 1, &Wo, &pl);
-    p.x = static_cast<const uint8_t*>(x); p.w = reinterpret_cast<const uint8_t*>(c->d_w1patch_f32); p.bias = L.d_b; p.y = static_cast<uint8_t*>(y);
-    p.zeros = reinterpret_cast<const uint8_t*>(c->d_zeros);
-    p.H = c->H; p.W = c->W; p.Ho = Ho; p.Wo = Wo; p.pad_t = pt; p.pad_l = pl;
-    p.tiles_x = (Wo + cp1::TW - 1) / cp1::TW; p.tiles_y = (Ho + cp1::TH - 1) / cp1::TH;
-    p.ntiles = NB * p.tiles_x * p.tiles_y;
-    c->last_plan[0][0] = ((NB * Ho * Wo + 127) / 128) * 1000 + 99; c->last_plan[0][1] = 0;
-    const int nblk = p.ntiles < 3 * c->ncu ? p.ntiles : 3 * c->ncu;   // three workgroups per CU, each walks its tiles
-    ProfScope ps(c, "cnv1");
-    HIP_TRY(c, launch_cnv1_patch_f32(p, nblk, c->stream));
-    return DAVO_OK;
-}
-
-// cnv2 of the float32 mode from an LDS-staged input patch (conv_patch_f32.h); x: float32 NHWC [NB][H1][W1][16], y: [NB][H2][W2][32]
-int run_cnv2_patch_f32(davo_ctx* c, const void* x, void* y, int NB) {
-    const ConvLayer& L = c->L[1];
-    ConvPatchParams p{};
-    int Ho, Wo, pt, pl;
-    same_pad(c->H1, 5, 2, 1, &Ho, &pt);
-    same_pad(c->W1, 5, 2, 1, &Wo, &pl);
-    p.x = static_cast<const uint8_t*>(x); p.w = reinterpret_cast<const uint8_t*>(c->d_w2patch_f32); p.bias = L.d_b; p.y = static_cast<uint8_t*>(y);
-    p.zeros = reinterpret_cast<const uint8_t*>(c->d_zeros);
-    p.H = c->H1; p.W = c->W1; p.Ho = Ho; p.Wo = Wo; p.pad_t = pt; p.pad_l = pl;
-    p.tiles_x = (Wo + cp2::TW - 1) / cp2::TW; p.tiles_y = (Ho + cp2::TH - 1) / cp2::TH;
-    p.ntiles = NB * p.tiles_x * p.tiles_y;
-    c->last_plan[1][0] = ((NB * Ho * Wo + 127) / 128) * 1000 + 98; c->last_plan[1][1] = 0;
-    const int nblk = p.ntiles < 2 * c->ncu ? p.ntiles : 2 * c->ncu;   // two workgroups per CU (three measured 4 % slower), each walks its tiles
-    ProfScope ps(c, "cnv2");
-    HIP_TRY(c, launch_cnv2_patch_f32(p, nblk, c->stream));
-    return DAVO_OK;
-}
-
-// cnv3 of the float32 mode from an LDS-staged input patch (conv_patch_f32.h); x: float32 NHWC [NB][H2][W2][32], y: [NB][H2][W2][64]
-int run_cnv3_patch_f32(davo_ctx* c, const void* x, void* y, int NB) {
-    const ConvLayer& L = c->L[2];
-    ConvPatchParams p{};
-    p.x = static_cast<const uint8_t*>(x); p.w = reinterpret_cast<const uint8_t*>(c->d_w3patch_f32); p.bias = L.d_b; p.y = static_cast<uint8_t*>(y);
-    p.zeros = reinterpret_cast<const uint8_t*>(c->d_zeros);
-    p.H = c->H2; p.W = c->W2; p.Ho = c->H2; p.Wo = c->W2; p.pad_t = cp3::RATE; p.pad_l = cp3::RATE;
-    p.tiles_x = (p.Wo + cp3::TW - 1) / cp3::TW; p.tiles_y = (p.Ho + cp3::TH - 1) / cp3::TH;
-    p.ntiles = NB * p.tiles_x * p.tiles_y;
-    c->last_plan[2][0] = ((NB * p.Ho * p.Wo + 127) / 128) * 1000 + 97; c->last_plan[2][1] = 0;
-    const int nblk = p.ntiles < 3 * c->ncu ? p.ntiles : 3 * c->ncu;
-    ProfScope ps(c, "cnv3");
-    HIP_TRY(c, launch_cnv3_patch_f32(p, nblk, c->stream));
-    return DAVO_OK;
-}
-
-// cnv3 of the f16x3 path from an LDS-staged input patch (conv_patch_h3.h, conv_patch_cnv3_h3)
-int run_cnv3_patch(davo_ctx* c, const void* x, void* y, int NB) {
-    const ConvLayer& L = c->L[2];
-    ConvPatchParams p{};
-    p.x = static_cast<const uint8_t*>(x); p.w = c->d_w3patch; p.bias = L.d_bh; p.y = static_cast<uint8_t*>(y);
-    p.zeros = reinterpret_cast<const uint8_t*>(c->d_zeros);
-    p.H = c->H2; p.W = c->W2; p.Ho = c->H2; p.Wo = c->W2; p.pad_t = cp3::RATE; p.pad_l = cp3::RATE;
-    p.tiles_x = (p.Wo + cp3::TW - 1) / cp3::TW; p.tiles_y = (p.Ho + cp3::TH - 1) / cp3::TH;
-    p.out_scale = ldexpf(1.0f / L.wscale, c->act_shift[2] - c->act_shift[1]);
-    p.bias_scale = ldexpf(L.wscale, c->act_shift[1]);
-    p.range = c->d_range ? c->d_range + 2 : nullptr;
-    p.ntiles = NB * p.tiles_x * p.tiles_y;
-    c->last_plan[2][0] = ((NB * p.Ho * p.Wo + 127) / 128) * 1000 + 97; c->last_plan[2][1] = 0;
-    const int nblk = p.ntiles < 3 * c->ncu ? p.ntiles : 3 * c->ncu;   // 3 workgroups per CU, each walks its tiles
-    if (const char* e = tuning_env("DAVO_PDBG")) p.dbg = atoi(e);      // tuning build only
-    ProfScope ps(c, "cnv3");
-    HIP_TRY(c, launch_cnv3_patch(p, nblk, c->stream));
+    if (!f32) {      // stored activations carry 2^act_shift (exact); cnv1's input carries none
+        const int sin = li == 0 ? 0 : c->act_shift[li - 1];
+        p.out_scale = ldexpf(1.0f / L.wscale, c->act_shift[li] - sin);
+        p.bias_scale = ldexpf(L.wscale, sin);
+        p.range = c->d_range ? c->d_range + li : nullptr;
+        if (const char* e = tuning_env("DAVO_PDBG")) p.dbg = atoi(e);      // tuning build only
+        if (li == 0) {
+            p.img = static_cast<const uint8_t*>(in.img); p.flow = static_cast<const float*>(in.flow);
+            p.seg = static_cast<const float*>(in.seg); p.tab = c->d_tab; p.v = c->v;
+        }
+    }
+    c->last_plan[li][0] = ((NB * p.Ho * p.Wo + 127) / 128) * 1000 + t.plan_id; c->last_plan[li][1] = 0;
+    const int nblk = p.ntiles < t.per_cu * c->ncu ? p.ntiles : t.per_cu * c->ncu;
+    ProfScope ps(c, L.label);
+    HIP_TRY(c, launch_patch_layer(li, f32, fused, p, nblk, c->stream));
     return DAVO_OK;
 }
 
@@ -599,10 +515,10 @@ int run_direct(davo_ctx* c, const char* label, const float* x, int N, int Hin, i
 
 }  // namespace
 
-int forward_device(davo_ctx* c, int B, const void* d_img, const void* d_flow, const void* d_seg, const void* d_depth, void* d_pose) {
+int forward_device(davo_ctx* c, int B, const Inputs& in, void* d_pose) {
     if (B < 1 || B > c->max_batch) return fail(c, DAVO_ERR_INVALID, "batch %d outside [1,%d]", B, c->max_batch);
-    if (!d_img || !d_flow || !d_seg || !d_pose) return fail(c, DAVO_ERR_INVALID, "null device pointer");
-    if (att_desc_depth(c->v.att_source) && (!d_depth || ((uintptr_t)d_depth & 15)))
+    if (!in.img || !in.flow || !in.seg || !d_pose) return fail(c, DAVO_ERR_INVALID, "null device pointer");
+    if (needs_depth(c) && (!in.depth || ((uintptr_t)in.depth & 15)))
         return fail(c, DAVO_ERR_INVALID, "this variant reads depth planes: a 16-byte aligned device pointer is required");
     {
         std::string names;
@@ -633,6 +549,9 @@ int forward_device(davo_ctx* c, int B, const void* d_img, const void* d_flow, co
     const int H = c->H, W = c->W, HW = H * W, NB = 2 * B;
     const Variant& v = c->v;
     hipStream_t s = c->stream;
+    const uint8_t* const d_img = static_cast<const uint8_t*>(in.img);
+    const float* const d_flow = static_cast<const float*>(in.flow);
+    const float* const d_seg = static_cast<const float*>(in.seg);
     auto wdev = [&](const char* n) -> const float* {
         auto it = c->weights.find(n);
         return it == c->weights.end() ? nullptr : it->second.dev;
@@ -649,27 +568,26 @@ int forward_device(davo_ctx* c, int B, const void* d_img, const void* d_flow, co
     const float* se_b1 = wdev(se_weight_name(v.att_source, 1));
     const float* se_w2 = wdev(se_weight_name(v.att_source, 2));
     const float* se_b2 = wdev(se_weight_name(v.att_source, 3));
-    if (att_desc_depth(v.att_source)) {
+    if (needs_depth(c)) {
         // depth sources: one float32 sum per depth plane and chunk, then (or, folded, in the same launch) the excitation
         ProfScope ps(c, "se_depth_squeeze");
-        HIP_TRY(c, launch_se_depth_squeeze(fold_excite, static_cast<const float*>(d_depth), B, HW, v, reinterpret_cast<unsigned*>(c->d_partial),
+        HIP_TRY(c, launch_se_depth_squeeze(fold_excite, static_cast<const float*>(in.depth), B, HW, v, reinterpret_cast<unsigned*>(c->d_partial),
                                            c->d_counters + 1, se_w1, se_b1, se_w2, se_b2, c->d_tab, range_reset, s));
     } else if (class_table) {
         // segmentation / rgb / seg+flow sources: per-frame histogram, byte or flow sums, then (or, folded, in the same launch) the
         // excitation
         ProfScope ps(c, "se_class_squeeze");
-        HIP_TRY(c, launch_se_class_squeeze(fold_excite, static_cast<const uint8_t*>(d_img), static_cast<const float*>(d_flow),
-                                           static_cast<const float*>(d_seg), B, H, W, v, reinterpret_cast<unsigned*>(c->d_partial),
+        HIP_TRY(c, launch_se_class_squeeze(fold_excite, d_img, d_flow, d_seg, B, H, W, v, reinterpret_cast<unsigned*>(c->d_partial),
                                            c->d_counters + 1, se_w1, se_b1, se_w2, se_b2, c->d_tab, range_reset, s));
     } else if (fold_excite) {
         // squeeze + excitation in one launch: the workgroup that delivers a triplet's last partial sum evaluates its tables
         ProfScope ps(c, "se_squeeze_partial");
-        HIP_TRY(c, launch_se_squeeze_excite(static_cast<const float*>(d_flow), B, HW, v, c->d_partial, c->d_counters + 1,
+        HIP_TRY(c, launch_se_squeeze_excite(d_flow, B, HW, v, c->d_partial, c->d_counters + 1,
                                             se_w1, se_b1, se_w2, se_b2,
                                             wdev("pose_exp_net/pose_exp_net/seg_channel_weight/weight"), c->d_tab, range_reset, s));
     } else if (v.att_source == 1) {
         ProfScope ps(c, "se_squeeze_partial");
-        HIP_TRY(c, launch_se_squeeze(static_cast<const float*>(d_flow), B, HW, v, c->d_partial, s));
+        HIP_TRY(c, launch_se_squeeze(d_flow, B, HW, v, c->d_partial, s));
     }
     if (!fold_excite) {
         ProfScope ps(c, "se_excite");
@@ -685,13 +603,11 @@ int forward_device(davo_ctx* c, int B, const void* d_img, const void* d_flow, co
     const bool patch1 = !(pe && atoi(pe) == 0);
     const bool fused = h3 && patch1 && fuse_env;
     c->packed_valid = !fused;
-    c->last_img = d_img; c->last_flow = d_flow; c->last_seg = d_seg;
+    c->last_in = in;
     c->packed_ld = c->impl == 0 ? 8 : 10;
     if (!fused) {
         ProfScope ps(c, "mask_pack");
-        HIP_TRY(c, launch_mask_pack(h3 ? 16 : (c->impl == 0 ? 8 : 10), static_cast<const uint8_t*>(d_img),
-                                    static_cast<const float*>(d_flow), static_cast<const float*>(d_seg), c->d_tab, v, B, H, W,
-                                    c->d_packed, s));
+        HIP_TRY(c, launch_mask_pack(h3 ? 16 : (c->impl == 0 ? 8 : 10), d_img, d_flow, d_seg, c->d_tab, v, B, H, W, c->d_packed, s));
     }
     const int c6 = v.cnv6_out;
     float** a = c->d_act;
@@ -700,13 +616,13 @@ int forward_device(davo_ctx* c, int B, const void* d_img, const void* d_flow, co
     int pose_bm = 0, pose_mt = 0, pose_ntn = 0;
     c->cnv7_valid = true;
     if (h3) {
-        if (patch1) { if ((rc = run_cnv1_patch(c, fused, d_img, d_flow, d_seg, a[0], NB))) return rc; }
+        if (patch1) { if ((rc = run_patch_layer(c, 0, false, c->d_packed, a[0], NB, fused, in))) return rc; }
         else if ((rc = run_conv_layer_h3(c, 0, c->d_packed, 8, H, W, a[0], 16, false, NB))) return rc;
         const char* p2e = tuning_env("DAVO_CNV2_PATCH");
-        if (c->opt_patch_cnv2 && c->L[1].tile_h < 0 && !(p2e && atoi(p2e) == 0)) { if ((rc = run_cnv2_patch(c, a[0], a[1], NB))) return rc; }
+        if (c->opt_patch_cnv2 && c->L[1].tile_h < 0 && !(p2e && atoi(p2e) == 0)) { if ((rc = run_patch_layer(c, 1, false, a[0], a[1], NB))) return rc; }
         else if ((rc = run_conv_layer_h3(c, 1, a[0], 16, c->H1, c->W1, a[1], 32, false, NB))) return rc;
         const char* p3e = tuning_env("DAVO_CNV3_PATCH");
-        if (c->opt_patch_cnv3 && c->L[2].tile_h < 0 && !(p3e && atoi(p3e) == 0)) { if ((rc = run_cnv3_patch(c, a[1], a[2], NB))) return rc; }
+        if (c->opt_patch_cnv3 && c->L[2].tile_h < 0 && !(p3e && atoi(p3e) == 0)) { if ((rc = run_patch_layer(c, 2, false, a[1], a[2], NB))) return rc; }
         else if ((rc = run_conv_layer_h3(c, 2, a[1], 32, c->H2, c->W2, a[2], 64, false, NB))) return rc;
         if ((rc = run_conv_layer_h3(c, 3, a[2], 64, c->H2, c->W2, a[3], 128, false, NB))) return rc;
         if ((rc = run_conv_layer_h3(c, 4, a[3], 128, c->H2, c->W2, a[4], 256, false, NB))) return rc;
@@ -716,11 +632,11 @@ int forward_device(davo_ctx* c, int B, const void* d_img, const void* d_flow, co
                                     fold_pose ? static_cast<float*>(d_pose) : nullptr))) return rc;
         c->cnv7_valid = !pose_fused;
     } else if (c->impl == 0) {
-        if (c->opt_patch_f32 && c->d_w1patch_f32 && c->packed_ld == 8) { if ((rc = run_cnv1_patch_f32(c, c->d_packed, a[0], NB))) return rc; }
+        if (c->opt_patch_f32 && c->d_w1patch_f32 && c->packed_ld == 8) { if ((rc = run_patch_layer(c, 0, true, c->d_packed, a[0], NB))) return rc; }
         else if ((rc = run_conv_layer(c, 0, c->d_packed, 8, H, W, a[0], 16, NB))) return rc;
-        if (c->opt_patch_f32 && c->d_w2patch_f32) { if ((rc = run_cnv2_patch_f32(c, a[0], a[1], NB))) return rc; }
+        if (c->opt_patch_f32 && c->d_w2patch_f32) { if ((rc = run_patch_layer(c, 1, true, a[0], a[1], NB))) return rc; }
         else if ((rc = run_conv_layer(c, 1, a[0], 16, c->H1, c->W1, a[1], 32, NB))) return rc;
-        if (c->opt_patch_f32 && c->d_w3patch_f32) { if ((rc = run_cnv3_patch_f32(c, a[1], a[2], NB))) return rc; }
+        if (c->opt_patch_f32 && c->d_w3patch_f32) { if ((rc = run_patch_layer(c, 2, true, a[1], a[2], NB))) return rc; }
         else if ((rc = run_conv_layer(c, 2, a[1], 32, c->H2, c->W2, a[2], 64, NB))) return rc;
         if ((rc = run_conv_layer(c, 3, a[2], 64, c->H2, c->W2, a[3], 128, NB))) return rc;
         if ((rc = run_conv_layer(c, 4, a[3], 128, c->H2, c->W2, a[4], 256, NB))) return rc;
@@ -751,8 +667,7 @@ int forward_device(davo_ctx* c, int B, const void* d_img, const void* d_flow, co
     if (!(pose_fused && fold_pose)) {
         ProfScope ps(c, "pose_head");
         if (pose_fused) {
-            const int slot_idx = (c->next_slot + c->inflight - 1) % c->inflight;
-            HIP_TRY(c, launch_pose_from_tiles(c->d_pose_tiles + (size_t)slot_idx * c->pose_tiles_floats, NB, c->H3 * c->W3, pose_bm,
+            HIP_TRY(c, launch_pose_from_tiles(c->d_pose_tiles + (size_t)slot_idx(c) * c->pose_tiles_floats, NB, c->H3 * c->W3, pose_bm,
                                               pose_mt, pose_ntn, c->d_bpred, static_cast<float*>(d_pose), h3 ? c->snap : SnapArgs{}, s));
             snap_done = true;
         } else {

@@ -64,13 +64,9 @@ hipError_t launch_se_depth_squeeze(bool fold, const float* d_depth, int B, int H
 // ld: 16 = split-fp16 8-channel layout (f16x3), 8 = float32 8-channel, 10 = the reference's 10-channel layout
 hipError_t launch_mask_pack(int ld, const uint8_t* d_img, const float* d_flow, const float* d_seg, const float* d_tab,
                             const Variant& v, int B, int H, int W, float* d_packed, hipStream_t s);
-hipError_t launch_cnv1_patch(bool fused, const ConvPatchParams& p, int nblk, hipStream_t s);
-hipError_t launch_cnv2_patch(const ConvPatchParams& p, int nblk, hipStream_t s);
-hipError_t launch_cnv3_patch(const ConvPatchParams& p, int nblk, hipStream_t s);
-// float32 mode (conv_patch_f32.h)
-hipError_t launch_cnv1_patch_f32(const ConvPatchParams& p, int nblk, hipStream_t s);
-hipError_t launch_cnv2_patch_f32(const ConvPatchParams& p, int nblk, hipStream_t s);
-hipError_t launch_cnv3_patch_f32(const ConvPatchParams& p, int nblk, hipStream_t s);
+// cnv1 / cnv2 / cnv3 (layer 0..2) from an LDS-staged input patch: conv_patch_cnvN_h3, or conv_patch_cnvN_f32 in float32 mode (f32);
+// fused: conv_patch_cnv1_h3<true> (f16x3 cnv1 only)
+hipError_t launch_patch_layer(int layer, bool f32, bool fused, const ConvPatchParams& p, int nblk, hipStream_t s);
 // split-K fix-up: d_part [M][S][N] float32 partial sums -> the layer's stored activation (ReLU, fp16 hi/lo pairs, range monitor)
 hipError_t launch_splitk_fixup(const float* d_part, long M, int N, int S, int relu, uint8_t* d_y, unsigned* d_range, hipStream_t s);
 hipError_t launch_pose_from_tiles(const float* d_tiles, int NB, int P, int bm, int mtiles, int ntiles_n,

@@ -82,47 +82,19 @@ hipError_t launch_mask_pack(int ld, const uint8_t* d_img, const float* d_flow, c
     return hipGetLastError();
 }
 
-hipError_t launch_cnv1_patch(bool fused, const ConvPatchParams& p, int nblk, hipStream_t s) {
-    hipError_t e = fused ? ensure_dynamic_lds(reinterpret_cast<const void*>(conv_patch_cnv1_h3<true>), cp1::LDS_BYTES)
-                         : ensure_dynamic_lds(reinterpret_cast<const void*>(conv_patch_cnv1_h3<false>), cp1::LDS_BYTES);
+hipError_t launch_patch_layer(int layer, bool f32, bool fused, const ConvPatchParams& p, int nblk, hipStream_t s) {
+    using Kernel = void (*)(ConvPatchParams);
+    struct Row { Kernel h3, f32; int threads, lds; };
+    static const Kernel cnv1_fused = conv_patch_cnv1_h3<true>;
+    static const Row rows[3] = {{conv_patch_cnv1_h3<false>, conv_patch_cnv1_f32, cp1::THREADS, cp1::LDS_BYTES},
+                                {conv_patch_cnv2_h3, conv_patch_cnv2_f32, cp2::THREADS, cp2::LDS_BYTES},
+                                {conv_patch_cnv3_h3, conv_patch_cnv3_f32, cp3::THREADS, cp3::LDS_BYTES}};
+    if (layer < 0 || layer > 2 || (fused && (f32 || layer != 0))) return hipErrorInvalidValue;
+    const Row& r = rows[layer];
+    const Kernel k = fused ? cnv1_fused : (f32 ? r.f32 : r.h3);
+    hipError_t e = ensure_dynamic_lds(reinterpret_cast<const void*>(k), r.lds);
     if (e != hipSuccess) return e;
-    if (fused) hipLaunchKernelGGL(conv_patch_cnv1_h3<true>, dim3(nblk), dim3(cp1::THREADS), cp1::LDS_BYTES, s, p);
-    else hipLaunchKernelGGL(conv_patch_cnv1_h3<false>, dim3(nblk), dim3(cp1::THREADS), cp1::LDS_BYTES, s, p);
-    return hipGetLastError();
-}
-
-hipError_t launch_cnv2_patch(const ConvPatchParams& p, int nblk, hipStream_t s) {
-    hipError_t e = ensure_dynamic_lds(reinterpret_cast<const void*>(conv_patch_cnv2_h3), cp2::LDS_BYTES);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(conv_patch_cnv2_h3, dim3(nblk), dim3(cp2::THREADS), cp2::LDS_BYTES, s, p);
-    return hipGetLastError();
-}
-
-hipError_t launch_cnv1_patch_f32(const ConvPatchParams& p, int nblk, hipStream_t s) {
-    hipError_t e = ensure_dynamic_lds(reinterpret_cast<const void*>(conv_patch_cnv1_f32), cp1::LDS_BYTES);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(conv_patch_cnv1_f32, dim3(nblk), dim3(cp1::THREADS), cp1::LDS_BYTES, s, p);
-    return hipGetLastError();
-}
-
-hipError_t launch_cnv2_patch_f32(const ConvPatchParams& p, int nblk, hipStream_t s) {
-    hipError_t e = ensure_dynamic_lds(reinterpret_cast<const void*>(conv_patch_cnv2_f32), cp2::LDS_BYTES);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(conv_patch_cnv2_f32, dim3(nblk), dim3(cp2::THREADS), cp2::LDS_BYTES, s, p);
-    return hipGetLastError();
-}
-
-hipError_t launch_cnv3_patch_f32(const ConvPatchParams& p, int nblk, hipStream_t s) {
-    hipError_t e = ensure_dynamic_lds(reinterpret_cast<const void*>(conv_patch_cnv3_f32), cp3::LDS_BYTES);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(conv_patch_cnv3_f32, dim3(nblk), dim3(cp3::THREADS), cp3::LDS_BYTES, s, p);
-    return hipGetLastError();
-}
-
-hipError_t launch_cnv3_patch(const ConvPatchParams& p, int nblk, hipStream_t s) {
-    hipError_t e = ensure_dynamic_lds(reinterpret_cast<const void*>(conv_patch_cnv3_h3), cp3::LDS_BYTES);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(conv_patch_cnv3_h3, dim3(nblk), dim3(cp3::THREADS), cp3::LDS_BYTES, s, p);
+    hipLaunchKernelGGL(k, dim3(nblk), dim3(r.threads), r.lds, s, p);
     return hipGetLastError();
 }
 
