@@ -42,7 +42,7 @@ EXPORTS = (
     "davo_forward_depth", "davo_forward_device_depth", "davo_submit_depth", "davo_calibrate_depth",
     "davo_last_error", "davo_destroy", "davo_device_malloc", "davo_device_free", "davo_memcpy_h2d",
     "davo_memcpy_d2h", "davo_synchronize", "davo_set_stream", "davo_set_inflight", "davo_profile_enable",
-    "davo_profile_reset", "davo_profile_entry", "davo_profile_samples", "davo_last_plan", "davo_set_option", "davo_set_precision", "davo_set_impl", "davo_debug_read", "davo_conv2d_same",
+    "davo_profile_reset", "davo_profile_entry", "davo_profile_samples", "davo_last_plan", "davo_last_split", "davo_set_option", "davo_set_precision", "davo_set_impl", "davo_debug_read", "davo_conv2d_same",
     "davo_host_alloc", "davo_host_free", "davo_host_register", "davo_host_unregister", "davo_calibrate", "davo_activation_range", "davo_set_activation_shifts", "davo_range_stats", "davo_range_report",
     "davo_comm_preload", "davo_comm_unique_id", "davo_comm_init", "davo_comm_size", "davo_allgather_poses", "davo_allgather_poses_device",
     "davo_comm_allreduce", "davo_comm_barrier", "davo_comm_destroy", "davo_plan_layer", "davo_tile_filter_rows",
@@ -202,6 +202,7 @@ def _load():
     L.davo_profile_entry.argtypes = [vp, i, ctypes.c_char_p, i, ctypes.POINTER(i), ctypes.POINTER(ctypes.c_double)]
     L.davo_profile_samples.argtypes = [vp, ctypes.c_char_p, i, f32p, i]
     L.davo_last_plan.argtypes = [vp, i, i, ctypes.POINTER(i), ctypes.POINTER(i)]
+    L.davo_last_split.argtypes = [vp, i, ctypes.POINTER(i)]
     L.davo_set_option.argtypes = [vp, ctypes.c_char_p, i]
     L.davo_set_precision.argtypes = [vp, i]
     L.davo_set_impl.argtypes = [vp, i]

@@ -1011,6 +1011,12 @@ int davo_last_plan(davo_ctx* c, int layer, int launch, int* mtiles, int* bn) {
     return DAVO_OK;
 }
 
+int davo_last_split(davo_ctx* c, int layer, int* parts) {
+    if (!c || layer < 0 || layer > 6) return DAVO_ERR_INVALID;
+    if (parts) *parts = c->last_split[layer];
+    return DAVO_OK;
+}
+
 // (Re)create the slots' streams.  With cu_partition on, slot i of n gets the CUs [i*32/n, (i+1)*32/n) of EVERY XCD
 // (hipExtStreamCreateWithCUMask; mask bit b = CU b/8 of XCD b%8, and a mask must leave no XCD empty — probed with
 // tools/exp/cumask_probe.hip), so batches in different slots run side by side on disjoint CUs and the write bursts of

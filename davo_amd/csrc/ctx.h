@@ -184,6 +184,7 @@ struct davo_ctx {
     bool packed_valid = true;                  // false when cnv1 consumed the raw inputs directly (fused)
     davo::Inputs last_in{};                    // the last forward's inputs: davo_debug_read("packed") re-packs from them after a fused cnv1
     int last_plan[7][2] = {};                  // per layer, per launch: 128-row M tiles * 1000 + tile id / BN (reported by the bench)
+    int last_split[7] = {};                    // per layer: split-K parts of the last forward's launch (1: one K chain; davo_last_split)
     // host-API staging
     davo::InputSet host_set;                   // davo_forward's staging set (allocated by its first call)
     void* s_pose = nullptr;

@@ -199,7 +199,7 @@ int run_conv_layer(davo_ctx* c, int li, const float* x, int x_ld, int Hin, int W
         p.pose_P = Ho * Wo; p.pose_mt = mtiles;
         if (pose_mt) *pose_mt = mtiles;
     }
-    c->last_plan[li][0] = c->last_plan[li][1] = 0;
+    c->last_plan[li][0] = c->last_plan[li][1] = 0; c->last_split[li] = 1;
     auto order_for = [&](const Launch& l, int ntn) {
         return (L.KS == 3 && L.cin_log2 >= 5) ? tile_order_for(c, li, 0, BM, l.mtile0, l.mtiles, ntn, p.M, Ho, Wo, Hin, L.stride, pt, L.rate) : nullptr;
     };
@@ -314,7 +314,7 @@ int run_conv_layer_h3(davo_ctx* c, int li, const void* x, int x_ch, int Hin, int
         if (pose_mt) *pose_mt = mt;
         if (pose_ntn) *pose_ntn = ntn;
     }
-    c->last_plan[li][0] = c->last_plan[li][1] = 0;
+    c->last_plan[li][0] = c->last_plan[li][1] = 0; c->last_split[li] = 1;
     // cnv4 on conv_igemm_h3w128's 256 x 128 tiles, every row in one launch - where the 256-row tiles fill whole rounds of the CUs or
     // nearly so: a round of them takes 24.4 us against 29.2 for the same rows on conv_igemm_h3's tiles (B = 128: 0.385 -> 0.318 ms),
     // which a last round that is three quarters empty gives back (B = 32, 3.25 rounds: 0.0925 -> 0.0938 ms)
@@ -343,7 +343,9 @@ int run_conv_layer_h3(davo_ctx* c, int li, const void* x, int x_ch, int Hin, int
             plan = {{0, rows1, TILE_256x128}, {rows1, rem, TILE_128x128}};
     }
     const bool merge_256 = plan.size() == 2 && plan[0].tile == TILE_256x256 && plan[1].tile == TILE_128x128 && L.npad_h == 256;
-    const bool merge_128 = plan.size() == 2 && plan[0].tile == TILE_256x128 && plan[1].tile == TILE_128x128 && L.npad_h == 128;
+    // the merged grid's 256x128 main tile is instantiated for cnv4 alone (launch_h3.hip): a cnv6 of 128 columns (-cnv6_64) with the same
+    // plan keeps its two launches
+    const bool merge_128 = li == 3 && plan.size() == 2 && plan[0].tile == TILE_256x128 && plan[1].tile == TILE_128x128 && L.npad_h == 128;
     if (c->opt_merge_rem && !fuse_pose && (merge_256 || merge_128) && L.groups == 1 && c->ncu == 256 && !tuning_env("DAVO_NO_MERGE")) {
         // main + remainder as one grid (conv_igemm_h3_mainrem): same tiles, same arithmetic, de-phased store bursts
         ConvParamsH pm = p, pr = p;
@@ -396,7 +398,7 @@ int run_conv_layer_h3(davo_ctx* c, int li, const void* x, int x_ch, int Hin, int
             ps.ntiles_n = ntn; ps.mtile0 = 0;
             dim3 grid(mtiles * ntn, S);
             ps.deep = c->opt_deep_ring && tiles * S <= c->ncu;
-            c->last_plan[li][0] = ((p.M + 127) / 128) * 1000 + plan[0].tile;
+            c->last_plan[li][0] = ((p.M + 127) / 128) * 1000 + plan[0].tile; c->last_split[li] = S;
             // The fix-up folded into the launch (pose_tail.h, splitk_tail): with an x extent that is a multiple of 8 the S parts of a
             // tile run on one XCD, so the part that finishes last finds the others' partial sums in its own L2 and writes the stored
             // form itself - no splitk_fixup launch (7 us each at batch 1, two per forward).  Checked once per context on the device.
@@ -490,7 +492,7 @@ int run_patch_layer(davo_ctx* c, int li, bool f32, const void* x, void* y, int N
             p.seg = static_cast<const float*>(in.seg); p.tab = c->d_tab; p.v = c->v;
         }
     }
-    c->last_plan[li][0] = ((NB * p.Ho * p.Wo + 127) / 128) * 1000 + t.plan_id; c->last_plan[li][1] = 0;
+    c->last_plan[li][0] = ((NB * p.Ho * p.Wo + 127) / 128) * 1000 + t.plan_id; c->last_plan[li][1] = 0; c->last_split[li] = 1;
     const int nblk = p.ntiles < t.per_cu * c->ncu ? p.ntiles : t.per_cu * c->ncu;
     ProfScope ps(c, L.label);
     HIP_TRY(c, launch_patch_layer(li, f32, fused, p, nblk, c->stream));

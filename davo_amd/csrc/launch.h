@@ -25,7 +25,8 @@ hipError_t launch_layer_mainrem(int layer, int rbn, const ConvParams& pm, const 
 // ---- launch_h3.hip: conv_igemm_h3 (f16x3) -----------------------------------------------------------
 hipError_t launch_layer_h3(int layer, int tile, const ConvParamsH& p, dim3 grid, hipStream_t s);
 // main launch (256x256 tiles, shared-tap staging) + remainder launch (128x128 tiles) of cnv5 / cnv6 (layer 4 / 5) as one grid
-// (conv_igemm_h3_mainrem); hipErrorNotSupported when the two launches do not have that shape: the caller issues them separately
+// (conv_igemm_h3_mainrem), or 256x128 + 128x128 of cnv4 (layer 3); hipErrorNotSupported when the two launches do not have that shape
+// or the layer's padded Cout is narrower than the instantiation's main tile (a -cnv6_64 cnv6 has 128 columns): the caller issues them separately
 // whether launch_layer_h3_mainrem would issue this shape (asked BEFORE the profiling scope of the launch is opened)
 bool layer_h3_mainrem_supported(int layer, const ConvParamsH& pm, int n_main, int n_rem);
 // order: 0 = the short tiles' offset inside every XCD (round 2), 1 = per XCD (even XCDs short tiles first, odd XCDs last)

@@ -22,10 +22,13 @@ hipError_t launch_layer_h3(int layer, int tile, const ConvParamsH& p, dim3 grid,
 namespace {
 
 // the shared-tap instantiation's own conditions (launch_h3_impl.h, launch_m) and the grid shape the id order assumes
-template <int LAYER>
+// TNM: the main tile spans TNM * 64 columns, and its weight DMA walks that many rows of the packed weights from the tile's first
+// row with no bound of its own (conv_igemm_h3.h, boff): a layer whose padded Cout is narrower has no such rows, so it is refused here
+template <int LAYER, int TNM>
 bool mainrem_ok(const ConvParamsH& pm, int n_main, int n_rem) {
     using namespace h3impl;
     constexpr int RATE = layer_rate(LAYER);
+    if (TNM * 64 > h3_npad(pm.Cout)) return false;
     if (!(pm.xs && pm.rate == RATE && pm.pad_l == RATE && pm.pad_t == RATE && pm.Hin == pm.Hout && pm.Win == pm.Wout &&
           pm.nchunks % 3 == 0 && pm.Wout > 2 * RATE && pm.x_pix_log2 >= 7 && use_m16()))
         return false;
@@ -40,7 +43,7 @@ hipError_t launch_mainrem(const ConvParamsH& pm, int n_main, const ConvParamsH& 
     using TX = TileX<4, 2, 2, TNM, 2, RATE>;
     using TR = TileH<4, 2, 1, 2, DAVO_REM_STAGES>;
     static_assert(DAVO_REM_STAGES == 3, "conv_igemm_h3_mainrem instantiates the three-slot remainder tile");
-    if (!mainrem_ok<LAYER>(pm, n_main, n_rem)) return hipErrorNotSupported;
+    if (!mainrem_ok<LAYER, TNM>(pm, n_main, n_rem)) return hipErrorNotSupported;
     constexpr int lds = TX::LDS_BYTES > TR::LDS_BYTES_DMA ? TX::LDS_BYTES : TR::LDS_BYTES_DMA;
     auto kern = conv_igemm_h3_mainrem<LAYER, RATE, TNM>;
     hipError_t e = ensure_dynamic_lds(reinterpret_cast<const void*>(kern), lds);
@@ -52,9 +55,9 @@ hipError_t launch_mainrem(const ConvParamsH& pm, int n_main, const ConvParamsH& 
 }  // namespace
 
 bool layer_h3_mainrem_supported(int layer, const ConvParamsH& pm, int n_main, int n_rem) {
-    if (layer == 3) return mainrem_ok<4>(pm, n_main, n_rem);
-    if (layer == 4) return mainrem_ok<5>(pm, n_main, n_rem);
-    if (layer == 5) return mainrem_ok<6>(pm, n_main, n_rem);
+    if (layer == 3) return mainrem_ok<4, 2>(pm, n_main, n_rem);
+    if (layer == 4) return mainrem_ok<5, 4>(pm, n_main, n_rem);
+    if (layer == 5) return mainrem_ok<6, 4>(pm, n_main, n_rem);
     return false;
 }
 

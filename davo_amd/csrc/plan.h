@@ -29,6 +29,13 @@ enum { TILE_128x32 = 0, TILE_256x64 = 1, TILE_256x128 = 2, TILE_128x256 = 3, TIL
 inline bool is_208(int t) { return t == TILE_208x256 || t == TILE_208x128; }
 struct TileShape { int bm, bn, threads, lds; };
 TileShape tile_shape(int t);
+// rows of a layer's packed f16x3 weights and bias per group: Cout padded to the widest N tile a launch may use.
+// The packers' allocation (weights.hip, L.npad_h) and the merged grid's bound on its main tile (launch_h3.hip, mainrem_ok) both
+// call this: the bound holds only while the allocation comes from the same function.
+inline int h3_npad(int cout) {
+    const int gran = cout > 128 ? 256 : cout > 64 ? 128 : cout > 32 ? 64 : 32;
+    return (cout + gran - 1) / gran * gran;
+}
 
 struct TileInfo { int id, per_cu; double eff; };
 struct LaunchH { int row0, rows, tile; };

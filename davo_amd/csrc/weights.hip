@@ -175,8 +175,7 @@ void init_layer(ConvLayer& L, const char* label, int KS, int stride, int rate, i
         const char* only = tuning_env("DAVO_H3_TILE_LABEL"); // restrict the force to one layer ("cnv4")
         if (t >= 0 && t < NUM_TILES && cout >= tile_shape(t).bn && (!only || strcmp(only, L.label) == 0)) L.tile_h = t;
     }
-    const int gran = cout > 128 ? 256 : cout > 64 ? 128 : cout > 32 ? 64 : 32;    // widest N tile a launch may use
-    L.npad_h = (cout + gran - 1) / gran * gran;
+    L.npad_h = h3_npad(cout);
 }
 
 // the pose head's 1x1 kernels [2][256][3] + [2][3]: every arithmetic mode reads them, so they are built at the first forward whatever

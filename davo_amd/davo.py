@@ -327,6 +327,12 @@ class Engine:
                 out.append((m.value, bn.value))
         return out
 
+    def last_split(self, layer):
+        """Split-K parts of conv layer 0..6's launch in the last forward (1: a single chain over K)."""
+        s = ctypes.c_int(0)
+        self._check(self._L.davo_last_split(self._ctx, layer, ctypes.byref(s)))
+        return s.value
+
     def debug_read(self, tensor, shape):
         out = np.empty(shape, np.float32)
         self._check(self._L.davo_debug_read(self._ctx, tensor.encode(), out.ctypes.data_as(ctypes.POINTER(ctypes.c_float)), out.size))

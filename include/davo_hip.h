@@ -213,6 +213,10 @@ int davo_profile_samples(davo_ctx* ctx, const char* name, int which, float* out,
  * covers `mtiles` 128-row M tiles x all output channels, in N tiles of `bn`.  bench.py uses it to
  * price the FLOPs of the launch it puts on the roofline. */
 int davo_last_plan(davo_ctx* ctx, int layer, int launch, int* mtiles, int* bn);
+/* Split-K parts of that layer's launch in the LAST forward: 1 where every output is one chain over K (and 0 before the
+ * first forward), else the number of partial sums a fix-up added (f16x3 cnv5 / cnv6 on a launch of few tiles, "split_k").
+ * davo_last_plan reports the same tiles either way; the tests use this to show which branch ran. */
+int davo_last_split(davo_ctx* ctx, int layer, int* parts);
 
 /* Arithmetic of the convolution stack:
  *   1 (default) "f16x3": every float32 operand is split into two fp16 halves (22 significant

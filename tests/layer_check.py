@@ -17,6 +17,9 @@ Two bars per layer:
       alone, beside REL_MAX = 5e-6 (2^-17.6) for everything else: so (a) becomes max|got - ref| <= REL_MAX * max|ref| + floor.
 The network's inputs: `packed' against the oracle's packing and `att_table' against its class tables, at 2e-6.  The pose:
 0.01 * mean(pred(cnv7)) in float64 from the GPU's cnv7 when it is stored, else from cnv7(GPU cnv6) (fused pose head)."""
+import json
+import os
+
 import numpy as np
 
 from davo_amd.version import ATT_SOURCE, NUM_SEG_CLASSES
@@ -64,6 +67,24 @@ PACK8 = [0, 1, 2, 5, 6, 7, 8, 9]
 
 # worst bar-(b) ratio seen in this process per (precision, layer): tests report it
 WORST = {}
+_REPORTS = {}                   # module -> its worst ratios, of the modules that finished in this process
+
+
+def report_worst_ratios(module):
+    """The body of a module-scoped autouse fixture (tests/test_plan_layers_gpu.py, tests/test_cnv6_widths_gpu.py): the worst
+    bar-(b) ratio per precision and layer over that module alone, printed, and written as JSON {module: {"precision/layer":
+    ratio}} where DAVO_LAYER_RATIOS names a file (how TAU above was measured).  A module that finishes later in the same
+    run adds its own entry and leaves the others' as they were."""
+    WORST.clear()
+    yield
+    worst = {"%s/%s" % k: v for k, v in sorted(WORST.items())}
+    print("worst |err| / L1 mass (%s):" % module, json.dumps(worst))
+    _REPORTS[module] = worst
+    path = os.environ.get("DAVO_LAYER_RATIOS")
+    if path:
+        os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+        with open(path, "w") as f:
+            json.dump(_REPORTS, f, indent=1, sort_keys=True)
 
 
 def conv64(x, w, b, stride, rate, relu=True):

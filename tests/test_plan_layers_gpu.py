@@ -4,9 +4,6 @@ mass); the packed inputs and attention tables against the oracle; the pose head 
 the GPU's last stored activation.  Default plans at the shapes and batch sizes that select them, every launch option at a
 shape where it is taken, the float32 merged / unmerged grids to the bit, and the attention sources on labels placed on
 the class-table squeeze's chunk boundaries."""
-import json
-import os
-
 import numpy as np
 import pytest
 
@@ -24,14 +21,7 @@ _WEIGHTS = {}
 def _report_worst_ratios():
     """The worst bar-(b) ratio per precision and layer over the module; written as JSON where DAVO_LAYER_RATIOS names a
     file (how TAU in layer_check.py was measured)."""
-    yield
-    worst = {"%s/%s" % k: v for k, v in sorted(LC.WORST.items())}
-    print("worst |err| / L1 mass:", json.dumps(worst))
-    path = os.environ.get("DAVO_LAYER_RATIOS")
-    if path:
-        os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
-        with open(path, "w") as f:
-            json.dump(worst, f, indent=1)
+    yield from LC.report_worst_ratios("test_plan_layers_gpu")
 
 
 def _weights(cfg):
@@ -53,11 +43,13 @@ def _fuses(H, W, fuse_pose):
     return bool(fuse_pose) and h7 * w7 >= 128
 
 
-def _run(e, cfg, inputs, precision, what, images=None, stop_after=None, plan_check=None):
+def _run(e, cfg, inputs, precision, what, images=None, stop_after=None, plan_check=None, checked=None):
+    """checked: LC.check_forward's dict of the layers an earlier forward on the same inputs and images stored as the same bits."""
     poses = LC.forward(e, *inputs)
     if plan_check is not None:
         assert plan_check(e), (what, [e.last_plan(li) for li in range(7)])
-    return LC.check_forward(e, cfg, _weights(cfg), *inputs, poses, precision, images=images, what=what, stop_after=stop_after)
+    return LC.check_forward(e, cfg, _weights(cfg), *inputs, poses, precision, images=images, what=what, stop_after=stop_after,
+                            checked=checked)
 
 
 # ---- default plans -------------------------------------------------------------------------------------------------
