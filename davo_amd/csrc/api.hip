@@ -48,10 +48,25 @@ void free_input_set(InputSet& s) {
 
 void free_slot(Slot& s) {
     for (auto p : s.d_act) if (p) (void)hipFree(p);
-    void* misc[] = {s.d_partial, s.d_tab, s.d_packed, s.d_pose_partial, s.d_counters};
+    void* misc[] = {s.d_partial, s.d_tab, s.d_packed, s.d_pose_partial, s.d_counters, s.d_se, s.d_se_scale, s.d_se_partial};
     for (auto p : misc) if (p) (void)hipFree(p);
     if (s.stream) (void)hipStreamDestroy(s.stream);
     s = Slot();
+}
+
+// the feature-attention variant's room in one slot (posenn_se.h): the 512-channel scaled tensor of cnv5's geometry (2,048 bytes per
+// pixel in either arithmetic mode), the scale table and the squeeze's partial sums.  Nothing of it exists with the mode off.
+void free_se_workspace(Slot& s) {
+    for (float** p : {&s.d_se, &s.d_se_scale, &s.d_se_partial}) { if (*p) (void)hipFree(*p); *p = nullptr; }
+}
+
+int alloc_se_workspace(davo_ctx* c, Slot* s) {
+    const size_t NB = 2 * (size_t)c->max_batch;
+    free_se_workspace(*s);
+    HIP_TRY(c, hipMalloc(reinterpret_cast<void**>(&s->d_se), NB * c->H2 * c->W2 * 512 * sizeof(float)));
+    HIP_TRY(c, hipMalloc(reinterpret_cast<void**>(&s->d_se_scale), NB * 2 * 256 * sizeof(float)));
+    HIP_TRY(c, hipMalloc(reinterpret_cast<void**>(&s->d_se_partial), NB * SE5_CHUNKS * 256 * sizeof(float)));
+    return DAVO_OK;
 }
 
 // allocate one in-flight slot (stream + activation workspace for max_batch triplets)
@@ -69,6 +84,7 @@ int alloc_slot(davo_ctx* c, Slot* s) {
     { int rc = zero_now(c, s->d_partial, partial_bytes); if (rc) return rc; }
     HIP_TRY(c, hipMalloc(reinterpret_cast<void**>(&s->d_counters), ((size_t)c->max_batch + 1 + SK_TILE_COUNTERS) * sizeof(unsigned)));
     { int rc = zero_now(c, s->d_counters, ((size_t)c->max_batch + 1 + SK_TILE_COUNTERS) * sizeof(unsigned)); if (rc) return rc; }
+    if (c->posenn_se) { int rc = alloc_se_workspace(c, s); if (rc) return rc; }
     return DAVO_OK;
 }
 
@@ -131,6 +147,29 @@ int davo_create(davo_ctx** out, int device, int H, int W, int max_batch, const d
     HIP_TRY(c, hipMalloc(reinterpret_cast<void**>(&c->d_range_base), (1 + RANGE_RING) * RANGE_WORDS * sizeof(unsigned)));
     { int rc = zero_now(c, c->d_range_base, (1 + RANGE_RING) * RANGE_WORDS * sizeof(unsigned)); if (rc) return rc; }
     c->d_range = c->d_range_base;
+    return DAVO_OK;
+}
+
+int davo_set_posenn_se(davo_ctx* c, int mode) {
+    if (!c) return DAVO_ERR_INVALID;
+    if (mode != 0 && mode != 1) return fail(c, DAVO_ERR_INVALID, "posenn_se mode must be 0 (none) or 1 (insert)");
+    if (!c->weights.empty() || c->forward_seen)
+        return fail(c, DAVO_ERR_INVALID, "davo_set_posenn_se must be called before the first davo_load_weight and the first forward "
+                    "(it changes the variant's variables and cnv6's layout)");
+    if (mode && c->v.att_source != 0)
+        return fail(c, DAVO_ERR_INVALID, "the feature-attention PoseNN (`-se_insert') runs with att_source 0 (`-no_segmask') only, got %d", c->v.att_source);
+    HIP_TRY(c, hipSetDevice(c->device));
+    c->posenn_se = mode;
+    // the heads read different inputs now: cnv6 becomes one group per head, the grouped path cnv7 runs on (forward.hip)
+    const int c6 = c->v.cnv6_out;
+    if (mode) init_layer(c->L[5], "cnv6", 3, 1, 2, 256, c6, 2);
+    else init_layer(c->L[5], "cnv6", 3, 1, 2, 256, 2 * c6, 1);
+    c->needed = needed_names(c->v, mode);
+    for (Slot& s : c->slots) {
+        if (mode) { int rc = alloc_se_workspace(c, &s); if (rc) return rc; }
+        else free_se_workspace(s);
+    }
+    activate_slot(c, 0);
     return DAVO_OK;
 }
 
@@ -460,6 +499,7 @@ int ticket_begin(davo_ctx* c, int B, const Inputs& in, Ticket* t, bool own_input
     if (++c->since_fresh_record >= FRESH_EVERY) {
         c->since_fresh_record = 0;
         HIP_TRY(c, hipMemsetAsync(c->d_range, 0, 6 * sizeof(unsigned), c->stream));
+        if (c->posenn_se) HIP_TRY(c, hipMemsetAsync(c->d_range + RANGE_SE, 0, sizeof(unsigned), c->stream));
     }
     if (++c->batch_seq == 0) c->batch_seq = 1;
     c->snap_seq_issued = t->seq = c->batch_seq;
@@ -471,7 +511,7 @@ int ticket_begin(davo_ctx* c, int B, const Inputs& in, Ticket* t, bool own_input
     c->snap = SnapArgs{c->d_range, c->h_range_dev + RANGE_WORDS * (1 + r), c->batch_seq,
                        src(in.img), src(in.flow), src(in.seg), dst(keep.img), dst(keep.flow), dst(keep.seg),
                        (unsigned)(nb.img / 16), (unsigned)(nb.flow / 32), (unsigned)(nb.flow / 16), (unsigned)(nb.seg / 16), B,
-                       src(in.depth), dst(keep.depth)};
+                       src(in.depth), dst(keep.depth), c->posenn_se};
     return DAVO_OK;
 }
 
@@ -767,7 +807,7 @@ static int forward_entry(davo_ctx* c, int B, const uint8_t* img, const float* fl
             if (++c->batch_seq == 0) c->batch_seq = 1;
             seq = c->batch_seq;
             c->snap = SnapArgs{};
-            c->snap.record = c->d_range_base; c->snap.host_mirror = c->h_range_dev; c->snap.seq = seq; c->snap.B = nb;
+            c->snap.record = c->d_range_base; c->snap.host_mirror = c->h_range_dev; c->snap.seq = seq; c->snap.B = nb; c->snap.se = c->posenn_se;
         }
         int rc = forward_device(c, nb, from_window(c, c->host_set.view(), b0), (float*)c->s_pose + (size_t)b0 * 12);
         c->snap = SnapArgs{};
@@ -1121,6 +1161,11 @@ int davo_debug_read(davo_ctx* c, const char* tensor, float* host_out, size_t n_f
     size_t n = 0;
     const std::string t = tensor;
     if (t == "att_table") { src = c->d_tab; n = (size_t)c->last_B * 3 * NCLS; }
+    else if (t == "cnv5_se_scale" || t == "cnv5_se") {      // feature attention (posenn_se.h): [2B][2][256] s_r | s_r s_t; [2B][H2][W2][512] rotation | translation input of cnv6
+        if (!c->posenn_se) return fail(c, DAVO_ERR_NOT_READY, "`%s' exists in the feature-attention variant only (davo_set_posenn_se)", tensor);
+        if (t == "cnv5_se") { src = c->d_se; n = NB * c->H2 * c->W2 * 512; }
+        else { src = c->d_se_scale; n = NB * 2 * 256; }
+    }
     else if (t == "packed") {
         if (!c->packed_valid) {          // fused path: materialise the packed tensor on demand from the last inputs
             HIP_TRY(c, launch_mask_pack(16, static_cast<const uint8_t*>(c->last_in.img), static_cast<const float*>(c->last_in.flow),
@@ -1147,13 +1192,14 @@ int davo_debug_read(davo_ctx* c, const char* tensor, float* host_out, size_t n_f
     if (n != n_floats) return fail(c, DAVO_ERR_INVALID, "`%s' holds %zu floats, caller asked for %zu", tensor, n, n_floats);
     int rc = davo_memcpy_d2h(c, host_out, src, n * sizeof(float));
     if (rc) return rc;
-    const bool split = c->last_precision == 1 && t != "att_table" && t != "cnv7";
+    const bool split = c->last_precision == 1 && t != "att_table" && t != "cnv7" && t != "cnv5_se_scale";
     if (split) {       // split-fp16 blocked -> plain float32 NHWC
         int ch = 8;
         const char* names[6] = {"cnv1", "cnv2", "cnv3", "cnv4", "cnv5", "cnv6"};
         for (int i = 0; i < 6; ++i) if (t == names[i]) ch = c->act_ch[i];
+        if (t == "cnv5_se") ch = 512;                // cnv5's storage ...
         const int cb = ch < 32 ? ch : 32;
-        int shift = 0;
+        int shift = t == "cnv5_se" ? c->act_shift[4] : 0;       // ... and its scale
         for (int i = 0; i < 6; ++i) if (t == names[i]) shift = c->act_shift[i];
         std::vector<float> tmp(ch);
         const size_t npix = n / ch;

@@ -10,7 +10,7 @@
 //   launch_f32.hip  conv_igemm_f32 instantiations + dispatch
 //   launch_h3.hip   conv_igemm_h3 instantiations + dispatch (the f16x3 path, the long compile)
 //   launch_h3s.hip  conv_igemm_h3s instantiations (208x256 tile); launch_h3_generic.hip: davo_conv2d_same's shapes
-//   launch_misc.hip prologue / pose head / cnv1..cnv3 patch / direct-convolution kernels + dispatch
+//   launch_misc.hip prologue / pose head / cnv1..cnv3 patch / feature-attention (posenn_se.h) / direct-convolution kernels + dispatch
 //   comm.hip        RCCL communicator behind the C ABI (pose gather of the window-sharded driver)
 #pragma once
 #include <hip/hip_runtime.h>
@@ -64,6 +64,7 @@ struct Slot {
     hipStream_t stream = nullptr;
     float *d_partial = nullptr, *d_tab = nullptr, *d_packed = nullptr, *d_pose_partial = nullptr;
     float* d_act[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    float *d_se = nullptr, *d_se_scale = nullptr, *d_se_partial = nullptr;      // feature attention (posenn_se.h; null with the mode off): [NB][P2][512] scaled cnv5, [NB][2][256] scales, [NB][SE5_CHUNKS][256] sums
     unsigned* d_counters = nullptr;              // "last workgroup" tickets (pose_tail.h): [0] cnv7's pose tail, [1 + b] triplet b's squeeze, [1 + max_batch + t] tile t of a split-K launch
 };
 
@@ -152,6 +153,8 @@ struct davo_ctx {
     size_t pose_tiles_floats = 0;
     bool cnv7_valid = true;
     davo::Variant v{};
+    int posenn_se = 0;                         // davo_set_posenn_se: 0 none | 1 insert - an SE block on cnv5 ahead of each head's cnv6 (posenn_se.h); cnv6 is then a two-group layer
+    bool forward_seen = false;                 // a forward has been issued (davo_set_posenn_se is refused from then on)
     int impl = 0;
     int precision = 1;                         // 0 = FP32 MFMA (bit-exact fmaf chains), 1 = f16x3 split (default)
     bool packed_h_ready = false;
@@ -176,6 +179,7 @@ struct davo_ctx {
     // workspace
     float *d_partial = nullptr, *d_tab = nullptr, *d_packed = nullptr, *d_zeros = nullptr, *d_pose_partial = nullptr;
     unsigned* d_counters = nullptr;            // the active slot's ticket counters
+    float *d_se = nullptr, *d_se_scale = nullptr, *d_se_partial = nullptr;      // ... and its feature-attention workspace
     float* d_act[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     size_t act_floats_per_img[7];
     int act_ch[7];
@@ -299,7 +303,7 @@ int sync_all_slots(davo_ctx* c);
 
 // ---- weights.hip ----------------------------------------------------------------------------
 void init_layer(ConvLayer& L, const char* label, int KS, int stride, int rate, int cin, int cout, int groups);
-std::vector<std::string> needed_names(const Variant& v);
+std::vector<std::string> needed_names(const Variant& v, int posenn_se = 0);
 // TF name of an SE dense tensor of the variant's scope (k: 0 bottleneck_fc/kernel, 1 its bias, 2 recover_fc/kernel, 3 its bias);
 // the se_flow scope's for the variants without SE layers (the kernels do not read them there)
 const char* se_weight_name(int att_source, int k);

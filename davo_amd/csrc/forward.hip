@@ -3,6 +3,8 @@
 //   se_squeeze_partial (se_class_squeeze for the class-table sources) -> se_excite -> mask_pack -> cnv1..cnv5 -> cnv6 (rotation|translation
 //   fused into one N = 2*cnv6_out GEMM, both read cnv5: nets/posenn.py:222-238)
 //   -> cnv7 (grouped x2) -> pose head.
+//   Feature attention (`-se_insert', davo_set_posenn_se): cnv5 -> se5_squeeze -> se5_excite -> se5_scale -> [cnv5 s_r | cnv5 s_r s_t]
+//   -> cnv6 as a two-group layer (group g reads channels [256 g, 256 g + 256)) -> cnv7 as before (posenn_se.h).
 //
 // The two PoseNN calls of a triplet (davo.py:1456-1457, shared weights) run as one batch of
 // 2B pair images.  Host code only: kernels are reached through launch.h.
@@ -84,6 +86,7 @@ void activate_slot(davo_ctx* c, int i) {
     if (!(c->user_stream && i == 0)) c->stream = s.stream;
     c->d_partial = s.d_partial; c->d_tab = s.d_tab; c->d_packed = s.d_packed; c->d_pose_partial = s.d_pose_partial;
     c->d_counters = s.d_counters;
+    c->d_se = s.d_se; c->d_se_scale = s.d_se_scale; c->d_se_partial = s.d_se_partial;
     for (int k = 0; k < 7; ++k) c->d_act[k] = s.d_act[k];
 }
 
@@ -96,6 +99,16 @@ int check_range(davo_ctx* c, const unsigned* raw, const int* shifts) {
     if (!shifts) shifts = c->act_shift;              // the scales the judged batch was issued under
     for (int i = 0; i < 6; ++i) {
         float v;
+        if (i == 5 && c->posenn_se) {                // in the order of the forward: between cnv5 and cnv6
+            // the scaled cnv5 of the feature-attention variant is a stored activation of its own.  It shares cnv5's scale and every
+            // factor is a sigmoid, so it cannot clamp where cnv5 did not, but it can sink below the floor - and no calibration moves
+            // it there without moving cnv5: such a batch ends on the float32 kernels (api.hip: recover_batch)
+            memcpy(&v, &raw[RANGE_SE], sizeof v);
+            if (range_value_fails(v))
+                return fail(c, DAVO_ERR_RANGE, "cnv5_se activations (cnv5 times its feature-attention scales) are at most %.4g: %s for the fp16-pair "
+                            "storage at cnv5's scale 2^%d - davo_set_precision(ctx, 0)", (double)ldexpf(v, -shifts[4]),
+                            v < 65504.f ? "too small" : "outside the range", shifts[4]);
+        }
         memcpy(&v, &raw[i], sizeof v);
         if (!range_value_fails(v)) continue;         // params.h: the test the batch's last kernel applies too
         const float actual = ldexpf(v, -shifts[i]);
@@ -515,6 +528,32 @@ int run_direct(davo_ctx* c, const char* label, const float* x, int N, int Hin, i
     return DAVO_OK;
 }
 
+// feature attention (posenn_se.h): cnv5 (x, in the mode's storage) -> c->d_se = [x s_r | x s_r s_t], 512 channels of cnv5's geometry
+int run_posenn_se(davo_ctx* c, bool h3, const void* x, int NB) {
+    static const char* const heads[2] = {"rotation", "translation"};
+    static const char* const parts[4] = {"bottleneck_fc/kernel", "bottleneck_fc/bias", "recover_fc/kernel", "recover_fc/bias"};
+    const float* w[8];
+    for (int h = 0; h < 2; ++h)
+        for (int k = 0; k < 4; ++k) {
+            const auto it = c->weights.find(std::string("pose_exp_net/pose/") + heads[h] + "/cnv5_se_attention/" + parts[k]);
+            if (it == c->weights.end() || !it->second.dev) return fail(c, DAVO_ERR_NOT_READY, "feature-attention weights not loaded");
+            w[h * 4 + k] = it->second.dev;
+        }
+    if (!c->d_se || !c->d_se_scale || !c->d_se_partial) return fail(c, DAVO_ERR_INVALID, "internal: no feature-attention workspace");
+    const int P = c->H2 * c->W2;
+    {
+        ProfScope ps(c, "se5_squeeze");
+        HIP_TRY(c, launch_se5_squeeze(h3, x, NB, P, c->d_se_partial, c->stream));
+    }
+    {
+        ProfScope ps(c, "se5_excite");
+        HIP_TRY(c, launch_se5_excite(c->d_se_partial, NB, P, h3 ? ldexpf(1.0f, -c->act_shift[4]) : 1.0f, w, c->d_se_scale, c->stream));
+    }
+    ProfScope ps(c, "se5_scale");
+    HIP_TRY(c, launch_se5_scale(h3, x, c->d_se_scale, NB, P, c->d_se, (h3 && c->d_range) ? c->d_range + RANGE_SE : nullptr, c->stream));
+    return DAVO_OK;
+}
+
 }  // namespace
 
 int forward_device(davo_ctx* c, int B, const Inputs& in, void* d_pose) {
@@ -527,6 +566,7 @@ int forward_device(davo_ctx* c, int B, const Inputs& in, void* d_pose) {
         if (missing_weights(c, &names)) return fail(c, DAVO_ERR_NOT_READY, "weights not loaded: %s", names.c_str());
     }
     HIP_TRY(c, hipSetDevice(c->device));
+    c->forward_seen = true;
     if (!c->pred_ready) { int rc = build_pred_weights(c); if (rc) return rc; }
     bool h3 = c->impl == 0 && c->precision == 1;
     c->f32_fallback = false;
@@ -628,7 +668,10 @@ int forward_device(davo_ctx* c, int B, const Inputs& in, void* d_pose) {
         else if ((rc = run_conv_layer_h3(c, 2, a[1], 32, c->H2, c->W2, a[2], 64, false, NB))) return rc;
         if ((rc = run_conv_layer_h3(c, 3, a[2], 64, c->H2, c->W2, a[3], 128, false, NB))) return rc;
         if ((rc = run_conv_layer_h3(c, 4, a[3], 128, c->H2, c->W2, a[4], 256, false, NB))) return rc;
-        if ((rc = run_conv_layer_h3(c, 5, a[4], 256, c->H2, c->W2, a[5], 2 * c6, false, NB))) return rc;
+        if (c->posenn_se) {
+            if ((rc = run_posenn_se(c, true, a[4], NB))) return rc;
+            if ((rc = run_conv_layer_h3(c, 5, c->d_se, 512, c->H2, c->W2, a[5], 2 * c6, false, NB))) return rc;
+        } else if ((rc = run_conv_layer_h3(c, 5, a[4], 256, c->H2, c->W2, a[5], 2 * c6, false, NB))) return rc;
         pose_fused = c->opt_fuse_pose && c->H3 * c->W3 >= 128;
         if ((rc = run_conv_layer_h3(c, 6, a[5], 2 * c6, c->H2, c->W2, a[6], 512, true, NB, pose_fused, &pose_bm, &pose_mt, &pose_ntn,
                                     fold_pose ? static_cast<float*>(d_pose) : nullptr))) return rc;
@@ -642,7 +685,10 @@ int forward_device(davo_ctx* c, int B, const Inputs& in, void* d_pose) {
         else if ((rc = run_conv_layer(c, 2, a[1], 32, c->H2, c->W2, a[2], 64, NB))) return rc;
         if ((rc = run_conv_layer(c, 3, a[2], 64, c->H2, c->W2, a[3], 128, NB))) return rc;
         if ((rc = run_conv_layer(c, 4, a[3], 128, c->H2, c->W2, a[4], 256, NB))) return rc;
-        if ((rc = run_conv_layer(c, 5, a[4], 256, c->H2, c->W2, a[5], 2 * c6, NB))) return rc;
+        if (c->posenn_se) {
+            if ((rc = run_posenn_se(c, false, a[4], NB))) return rc;
+            if ((rc = run_conv_layer(c, 5, c->d_se, 512, c->H2, c->W2, a[5], 2 * c6, NB))) return rc;
+        } else if ((rc = run_conv_layer(c, 5, a[4], 256, c->H2, c->W2, a[5], 2 * c6, NB))) return rc;
         // float32 mode, round 4: the pose head in cnv7's epilogue like the f16x3 path's (the 109 MB activation is neither written nor
         // read back, pose_head_partial + pose_finish become pose_from_tiles); tiles of 128 rows must not span more than two images
         pose_fused = c->opt_fuse_pose && c->H3 * c->W3 >= 128 && c->L[6].npad == 256;
@@ -658,10 +704,13 @@ int forward_device(davo_ctx* c, int B, const Inputs& in, void* d_pose) {
         if ((rc = run_direct(c, "cnv3", a[1], NB, c->H2, c->W2, 32, 32, 0, P + "cnv3/weights", P + "cnv3/biases", 3, 64, 1, 2, a[2], 64, 0))) return rc;
         if ((rc = run_direct(c, "cnv4", a[2], NB, c->H2, c->W2, 64, 64, 0, P + "cnv4/weights", P + "cnv4/biases", 3, 128, 1, 4, a[3], 128, 0))) return rc;
         if ((rc = run_direct(c, "cnv5", a[3], NB, c->H2, c->W2, 128, 128, 0, P + "cnv5/weights", P + "cnv5/biases", 3, 256, 1, 8, a[4], 256, 0))) return rc;
+        if (c->posenn_se && (rc = run_posenn_se(c, false, a[4], NB))) return rc;      // float32 NHWC like the float32 mode's cnv5
         const char* heads[2] = {"rotation", "translation"};
         for (int h = 0; h < 2; ++h) {
             const std::string hp = P + "pose/" + heads[h] + "/";
-            if ((rc = run_direct(c, "cnv6", a[4], NB, c->H2, c->W2, 256, 256, 0, hp + "cnv6/weights", hp + "cnv6/biases", 3, c6, 1, 2, a[5], 2 * c6, h * c6))) return rc;
+            // feature attention: head h reads its half of the scaled tensor
+            const float* x6 = c->posenn_se ? c->d_se : a[4];
+            if ((rc = run_direct(c, "cnv6", x6, NB, c->H2, c->W2, 256, c->posenn_se ? 512 : 256, c->posenn_se ? h * 256 : 0, hp + "cnv6/weights", hp + "cnv6/biases", 3, c6, 1, 2, a[5], 2 * c6, h * c6))) return rc;
             if ((rc = run_direct(c, "cnv7", a[5], NB, c->H2, c->W2, c6, 2 * c6, h * c6, hp + "cnv7/weights", hp + "cnv7/biases", 3, 256, 2, 1, a[6], 512, h * 256))) return rc;
         }
     }

@@ -79,5 +79,11 @@ hipError_t launch_pose_head(const float* d_c7, int NB, int P, const float* d_wpr
 hipError_t launch_conv_direct(const float* x, int N, int Hin, int Win, int cin, int x_ld, int x_coff, const float* w, int KS,
                               int cout, const float* bias, int stride, int rate, int pt, int pl, int Ho, int Wo, int relu,
                               float* y, int y_ld, int y_coff, hipStream_t s);
+// the feature-attention variant's SE block on cnv5 (posenn_se.h): squeeze, excite, scale.  h3: x and y are split-fp16 blocked
+// (else float32 NHWC); P = pixels per pair image; d_partial [NB][SE5_CHUNKS][256], d_scale [NB][2][256] (s_r | s_r * s_t),
+// d_y [NB][P][512]; se_w: the eight dense tensors, rotation's {W1, b1, W2, b2} then translation's; unscale = 2^-(cnv5's storage shift)
+hipError_t launch_se5_squeeze(bool h3, const void* d_x, int NB, int P, float* d_partial, hipStream_t s);
+hipError_t launch_se5_excite(const float* d_partial, int NB, int P, float unscale, const float* const se_w[8], float* d_scale, hipStream_t s);
+hipError_t launch_se5_scale(bool h3, const void* d_x, const float* d_scale, int NB, int P, void* d_y, unsigned* d_range, hipStream_t s);
 
 }  // namespace davo

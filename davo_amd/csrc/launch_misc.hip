@@ -7,6 +7,7 @@
 #include "conv_patch_h3.h"
 #include "conv_patch_f32.h"
 #include "launch.h"
+#include "posenn_se.h"
 #include "prologue.h"
 
 namespace davo {
@@ -156,6 +157,32 @@ hipError_t launch_conv_direct(const float* x, int N, int Hin, int Win, int cin, 
     const long total = (long)N * Ho * Wo * cout;
     hipLaunchKernelGGL(conv_direct, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, x, N, Hin, Win, cin, x_ld, x_coff,
                        w, KS, cout, bias, stride, rate, pt, pl, Ho, Wo, relu, y, y_ld, y_coff);
+    return hipGetLastError();
+}
+
+hipError_t launch_se5_squeeze(bool h3, const void* d_x, int NB, int P, float* d_partial, hipStream_t s) {
+    if (NB < 1 || P < 1 || !d_x || !d_partial) return hipErrorInvalidValue;
+    const uint8_t* x = static_cast<const uint8_t*>(d_x);
+    if (h3) hipLaunchKernelGGL(se5_squeeze<true>, dim3(SE5_CHUNKS, NB), dim3(256), 0, s, x, P, d_partial);
+    else hipLaunchKernelGGL(se5_squeeze<false>, dim3(SE5_CHUNKS, NB), dim3(256), 0, s, x, P, d_partial);
+    return hipGetLastError();
+}
+
+hipError_t launch_se5_excite(const float* d_partial, int NB, int P, float unscale, const float* const se_w[8], float* d_scale, hipStream_t s) {
+    if (NB < 1 || P < 1 || !d_partial || !d_scale) return hipErrorInvalidValue;
+    for (int k = 0; k < 8; ++k) if (!se_w[k]) return hipErrorInvalidValue;
+    const Se5Weights w{se_w[0], se_w[1], se_w[2], se_w[3], se_w[4], se_w[5], se_w[6], se_w[7]};
+    hipLaunchKernelGGL(se5_excite, dim3(NB), dim3(256), 0, s, d_partial, P, unscale, w, d_scale);
+    return hipGetLastError();
+}
+
+hipError_t launch_se5_scale(bool h3, const void* d_x, const float* d_scale, int NB, int P, void* d_y, unsigned* d_range, hipStream_t s) {
+    if (NB < 1 || P < 1 || !d_x || !d_scale || !d_y) return hipErrorInvalidValue;
+    const uint8_t* x = static_cast<const uint8_t*>(d_x);
+    uint8_t* y = static_cast<uint8_t*>(d_y);
+    const dim3 grid((unsigned)(((long)P * (h3 ? 32 : 64) + 255) / 256), NB);
+    if (h3) hipLaunchKernelGGL(se5_scale<true>, grid, dim3(256), 0, s, x, d_scale, P, y, d_range);
+    else hipLaunchKernelGGL(se5_scale<false>, grid, dim3(256), 0, s, x, d_scale, P, y, d_range);
     return hipGetLastError();
 }
 

@@ -22,6 +22,8 @@ namespace davo {
 constexpr int NCLS = 19;            // Cityscapes train ids (utils/seg_utils/labels.py:64-101)
 constexpr int SQ_CHUNKS = 32;       // SE squeeze: partial sums per (triplet, source) plane
 constexpr int PH_SPLIT = 8;         // pose head: partial sums per (image, head)
+// feature attention (posenn_se.h): cnv5 channels, bottleneck units (ratio 8), partial sums per pair image [NB][SE5_CHUNKS][256]
+constexpr int SE5_C = 256, SE5_HID = 32, SE5_CHUNKS = 32;
 
 struct Variant {
     int cin_per_frame, cnv6_out, se_act, norm_flow, abs_mode, att_source, mask_rgb, mask_info;
@@ -294,7 +296,11 @@ struct ConvPatchParams {
 // ---- f16x3 range guard ---------------------------------------------------------------------------------------------------
 // A range record is RANGE_WORDS unsigned words: [layer] = bit pattern of the largest magnitude a storing epilogue of cnv1..cnv6 has
 // written (atomicMax; non-negative floats order like their bit patterns), [RANGE_SNAP] = 1 once a batch's inputs were copied for
-// a re-issue, [RANGE_SEQ] = sequence number of the last batch whose final kernel has seen the record (host mirror only).
+// a re-issue, [RANGE_SEQ] = sequence number of the last batch whose final kernel has seen the record (host mirror only),
+// [RANGE_SE] = the maximum of the feature-attention variant's scaled cnv5 (posenn_se.h; written, mirrored and judged only in that
+// mode: with it off no kernel loads or stores the word, and it stays zero).  The six layer words fill the mirror's two 16-byte
+// stores together with SNAP and SEQ, so the ninth word opens a third quad; records stay a whole number of quads (12 words) so that
+// every record and mirror of the ring keeps the 16-byte alignment of those stores.
 // The maxima are RUNNING maxima over the batches that share a record: zeroed when a verdict failed or the scales changed, not
 // per batch.  Why: a wave only pays for the atomic if it would raise the record, and a record that starts every batch at zero is
 // raised by every wave of the first round - measured at batch 1 with per-batch zeroing: cnv1 8 -> 29 us, cnv5 28 -> 133 us,
@@ -305,7 +311,7 @@ struct ConvPatchParams {
 // whose scale does not fit shows in the first batch; activations that collapse by 2^-20 between two batches of one network on
 // bounded inputs do not occur (ReLU layers are homogeneous in the input, the strip is u8), and the host path - one record per
 // call - still sees them.  This is round 3's guard between two davo_synchronize calls, without its reset at each of them.
-constexpr int RANGE_WORDS = 8, RANGE_SNAP = 6, RANGE_SEQ = 7;
+constexpr int RANGE_WORDS = 12, RANGE_SNAP = 6, RANGE_SEQ = 7, RANGE_SE = 8;
 // the verdict on one layer's maximum, shared by the host (forward.hip: check_range) and the kernel that keeps the inputs when it will fail
 __host__ __device__ inline bool range_value_fails(float vmax) {
     return !(vmax < 65504.f) || (vmax > 0.f && vmax < 0x1p-6f);       // clamped / inf, or too small for the fp16 pairs' low halves
@@ -331,6 +337,7 @@ struct SnapArgs {
     int B;
     const uint8_t* depth;                   // depth sources only (else null): the caller's depth planes, seg_vec units per window ...
     uint8_t* s_depth;                       // ... and the ring slot's copy of them
+    int se;                                 // feature-attention variant: record[RANGE_SE] is part of the verdict and of the mirror
 };
 
 }  // namespace davo

@@ -595,7 +595,7 @@ __global__ __launch_bounds__(64) void pose_finish(const float* __restrict__ part
 // every batch of a well-ranged checkpoint - costs six loads per thread and no copy.  Only flow planes 0 and 1 are read by the
 // path (davo.py:978-982): the first half of every window's block.
 // phase 1 (top of the kernel, so that the memory-side round trips pass behind the kernel's own work): the maxima, and the first half of the mirror
-struct RangePeek { unsigned w[6]; bool fails; };
+struct RangePeek { unsigned w[6]; bool fails; };       // (the feature-attention word is judged and mirrored at once: no copy kept)
 __device__ __forceinline__ RangePeek range_peek(const SnapArgs& a, unsigned worker) {
     RangePeek r{};
     if (!a.record) return r;
@@ -604,9 +604,15 @@ __device__ __forceinline__ RangePeek range_peek(const SnapArgs& a, unsigned work
         r.w[i] = __atomic_load_n(a.record + i, __ATOMIC_RELAXED);
         r.fails |= range_value_fails(__uint_as_float(r.w[i]));
     }
+    unsigned se = 0u;
+    if (a.se) {                                    // the scaled cnv5 of the feature-attention variant (posenn_se.h)
+        se = __atomic_load_n(a.record + RANGE_SE, __ATOMIC_RELAXED);
+        r.fails |= range_value_fails(__uint_as_float(se));
+    }
     if (worker == 0) {
         typedef unsigned v4u __attribute__((ext_vector_type(4)));
         __builtin_nontemporal_store((v4u){r.w[0], r.w[1], r.w[2], r.w[3]}, reinterpret_cast<v4u*>(a.host_mirror));
+        if (a.se) __builtin_nontemporal_store(se, a.host_mirror + RANGE_SE);      // acknowledged, like the quad above, before phase 2 stores the sequence number
     }
     return r;
 }

@@ -4,7 +4,8 @@
 //   f16x3 path  HWIO -> [Cout_pad][chunk][32 hi | 32 lo] halves, channel-block major / tap minor,
 //               pre-multiplied by a power of two so the fp16 residuals of small weights stay normal
 // rotation/cnv6 and translation/cnv6 are stacked along N (one GEMM, both read cnv5:
-// nets/posenn.py:222-238); cnv7 is one group per head.
+// nets/posenn.py:222-238); cnv7 is one group per head - and so is cnv6 in the feature-attention variant, whose heads read
+// different inputs (davo_set_posenn_se; nets/posenn.py:225-228).
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
@@ -82,12 +83,12 @@ const char* se_weight_name(int att_source, int k) {
 }
 
 bool is_dense_weight(const std::string& nm) {
-    for (const char* s : {"/se_flow/", "/se_seg/", "/se_rgb/", "/se_segflow/", "/se_depth/", "seg_channel_weight"})
+    for (const char* s : {"/se_flow/", "/se_seg/", "/se_rgb/", "/se_segflow/", "/se_depth/", "/cnv5_se_attention/", "seg_channel_weight"})
         if (nm.find(s) != std::string::npos) return true;
     return false;
 }
 
-std::vector<std::string> needed_names(const Variant& v) {
+std::vector<std::string> needed_names(const Variant& v, int posenn_se) {
     std::vector<std::string> n;
     const char* trunk[] = {"cnv1", "cnv2", "cnv3", "cnv4", "cnv5"};
     for (auto l : trunk) {
@@ -106,6 +107,10 @@ std::vector<std::string> needed_names(const Variant& v) {
     } else if (v.att_source == 2 || v.att_source == 3) {
         n.push_back("pose_exp_net/pose_exp_net/seg_channel_weight/weight");
     }
+    if (posenn_se)       // each head's se_block on cnv5 (nets/posenn.py:227, nets/attention_module.py:37-49)
+        for (auto h : heads)
+            for (auto t : {"bottleneck_fc/kernel", "bottleneck_fc/bias", "recover_fc/kernel", "recover_fc/bias"})
+                n.push_back(std::string("pose_exp_net/pose/") + h + "/cnv5_se_attention/" + t);
     return n;
 }
 
@@ -132,6 +137,10 @@ bool expected_shape(const davo_ctx* c, const std::string& name, std::vector<int6
     else if (ends("/cnv7/biases")) *sh = {256};
     else if (ends("/pred/weights")) *sh = {1, 1, 256, 3};
     else if (ends("/pred/biases")) *sh = {3};
+    else if (c->posenn_se && ends("/cnv5_se_attention/bottleneck_fc/kernel")) *sh = {256, 32};     // se_block(cnv5, ratio=8)
+    else if (c->posenn_se && ends("/cnv5_se_attention/bottleneck_fc/bias")) *sh = {32};
+    else if (c->posenn_se && ends("/cnv5_se_attention/recover_fc/kernel")) *sh = {32, 256};
+    else if (c->posenn_se && ends("/cnv5_se_attention/recover_fc/bias")) *sh = {256};
     else if (is("pose_exp_net/se_flow/bottleneck_fc/kernel")) *sh = {2, 8};
     else if (is("pose_exp_net/se_flow/bottleneck_fc/bias")) *sh = {8};
     else if (is("pose_exp_net/se_flow/recover_fc/kernel")) *sh = {8, NCLS};
@@ -221,14 +230,14 @@ int build_packed_weights(davo_ctx* c) {
         rc = upload(c, bp, &L.d_b); if (rc) return rc;
     }
     const char* heads[2] = {"rotation", "translation"};
-    {   // cnv6: one GEMM, N = [rotation c6 | translation c6]
+    {   // cnv6: one GEMM, N = [rotation c6 | translation c6]; feature attention: one group per head like cnv7
         ConvLayer& L = c->L[5];
-        std::vector<float> wp((size_t)L.npad * L.kpad, 0.f), bp(L.npad, 0.f);
+        const size_t wstep = L.groups == 2 ? (size_t)L.npad * L.kpad : (size_t)c6 * L.kpad, bstep = L.groups == 2 ? L.npad : c6;
+        std::vector<float> wp((size_t)L.groups * L.npad * L.kpad, 0.f), bp((size_t)L.groups * L.npad, 0.f);
         for (int h = 0; h < 2; ++h) {
             const std::string p = std::string("pose_exp_net/pose/") + heads[h] + "/cnv6/";
-            pack_conv_weights(W(p + "weights").data.data(), 3, 256, c6, nullptr, 256, c6, L.kpad,
-                              wp.data() + (size_t)h * c6 * L.kpad);
-            memcpy(bp.data() + h * c6, W(p + "biases").data.data(), c6 * sizeof(float));
+            pack_conv_weights(W(p + "weights").data.data(), 3, 256, c6, nullptr, 256, c6, L.kpad, wp.data() + h * wstep);
+            memcpy(bp.data() + h * bstep, W(p + "biases").data.data(), c6 * sizeof(float));
         }
         int rc = upload(c, wp, &L.d_w); if (rc) return rc;
         rc = upload(c, bp, &L.d_b); if (rc) return rc;
@@ -338,10 +347,11 @@ int build_packed_weights_h3(davo_ctx* c) {
             const char* names[5] = {"cnv1", "cnv2", "cnv3", "cnv4", "cnv5"};
             const std::string p = std::string("pose_exp_net/") + names[li] + "/";
             pack(p + "weights", p + "biases", li == 0 ? 2 * cpf : L.cin, L.cout, li == 0 ? chmap1 : nullptr, wp.data(), bp.data());
-        } else if (li == 5) {       // rotation | translation stacked along N
+        } else if (li == 5) {       // rotation | translation stacked along N; feature attention: one group per head
+            const size_t wstep = L.groups == 2 ? per_group : (size_t)c6 * L.nchunks_h * 64, bstep = L.groups == 2 ? L.npad_h : c6;
             for (int h = 0; h < 2; ++h) {
                 const std::string p = std::string("pose_exp_net/pose/") + heads[h] + "/cnv6/";
-                pack(p + "weights", p + "biases", 256, c6, nullptr, wp.data() + (size_t)h * c6 * L.nchunks_h * 64, bp.data() + h * c6);
+                pack(p + "weights", p + "biases", 256, c6, nullptr, wp.data() + h * wstep, bp.data() + h * bstep);
             }
         } else {                    // cnv7: one group per head
             for (int h = 0; h < 2; ++h) {

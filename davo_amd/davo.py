@@ -109,6 +109,12 @@ class Engine:
                 self._L.davo_destroy(self._ctx)
                 self._ctx = ctypes.c_void_p()
             raise _PY_ERR.get(rc, DavoError)(msg)
+        if cfg.posenn_se != "none":               # `-se_insert': before any weight is loaded (include/davo_hip.h)
+            try:
+                self._check(self._L.davo_set_posenn_se(self._ctx, {"insert": 1}[cfg.posenn_se]))
+            except Exception:
+                self.close()
+                raise
 
     def _check(self, rc):
         if rc != 0:

@@ -48,6 +48,8 @@ class VariantConfig:
     att_source: str          # a key of ATT_SOURCE
     mask_rgb: bool           # rgb_k *= att_k          (davo.py:1419-1423 / 1447-1450)
     mask_info: bool          # flow_k *= att_k         (davo.py:1430-1434)
+    posenn_se: str = "none"  # none | insert: se_block on cnv5 ahead of each head's cnv6 (davo.py:1010-1011, nets/posenn.py:225-228);
+                             # not a davo_variant field: Engine hands it to davo_set_posenn_se
 
     @property
     def cin_per_frame(self):
@@ -136,8 +138,10 @@ def parse_version(version):
         raise UnsupportedVariantError("version `%s': the only depth sources supported are `-se_depth_wo_tgt_to_seg' and "
                                       "`-se_depth_to_seg'." % v)
 
-    # -- davo.py:1010-1017: se_block inside the PoseNN
-    for s in ("-se_insert", "-se_skipadd", "-se_replace"):
+    # -- davo.py:1010-1017: se_block inside the PoseNN (if / elif: `-se_insert' wins).  `-se_insert' runs where the attention
+    #    source resolves to `ones' (checked below, once the source is known); the other two modes do not run
+    posenn_se = "insert" if "-se_insert" in v else "none"
+    for s in ("-se_skipadd", "-se_replace"):
         if s in v:
             raise UnsupportedVariantError("version `%s': `%s' PoseNN mode is not supported." % (v, s))
 
@@ -214,6 +218,12 @@ def parse_version(version):
         else:
             att_source = "static_all"          # davo.py:1396-1400: tgt masked as well
 
+    if posenn_se == "insert" and att_source != "ones":
+        # "Ours w/ feature attention" is published with `-no_segmask' alone (doc/arch-variants.md); beside an input-attention
+        # source the block is not built
+        raise UnsupportedVariantError("version `%s': `-se_insert' PoseNN mode is supported with `-no_segmask' only "
+                                      "(attention source `%s')." % (v, att_source))
+
     # -- davo.py:1415-1450 masking
     if use_flow_info:
         mask_rgb = "-segmask_" in v
@@ -224,7 +234,7 @@ def parse_version(version):
 
     return VariantConfig(version=v, major=major, use_flow_info=use_flow_info, cnv6_out=cnv6_out,
                          se_act=se_act, norm_flow=norm_flow, abs_mode=abs_mode,
-                         att_source=att_source, mask_rgb=mask_rgb, mask_info=mask_info)
+                         att_source=att_source, mask_rgb=mask_rgb, mask_info=mask_info, posenn_se=posenn_se)
 
 
 def weight_shapes(cfg):
@@ -248,6 +258,12 @@ def weight_shapes(cfg):
         sh[p + "cnv7/biases"] = (256,)
         sh[p + "pred/weights"] = (1, 1, 256, 3)
         sh[p + "pred/biases"] = (3,)
+        if cfg.posenn_se == "insert":               # se_block(cnv5, 'cnv5_se_attention', ratio=8): nets/attention_module.py:37-49
+            q = p + "cnv5_se_attention/"
+            sh[q + "bottleneck_fc/kernel"] = (256, 256 // 8)
+            sh[q + "bottleneck_fc/bias"] = (256 // 8,)
+            sh[q + "recover_fc/kernel"] = (256 // 8, 256)
+            sh[q + "recover_fc/bias"] = (256,)
     if cfg.se_scope is not None:
         nin, nh = _SE_WIDTHS[cfg.att_source]
         p = "pose_exp_net/%s/" % cfg.se_scope

@@ -66,6 +66,18 @@ typedef struct {
  * H and W must be multiples of 4. */
 int davo_create(davo_ctx** out, int device, int H, int W, int max_batch, const davo_variant* v);
 
+/* The se_block inside the PoseNN (davo.py:1010-1017 -> nets/posenn.py:225-236), which is not part of davo_variant (its eight
+ * fields are ABI).  mode 0 = none (the default), 1 = insert (`-se_insert', "Ours w/ feature attention"): inside the loop over
+ * the heads `rotation', `translation' the reference re-binds cnv5 = se_block(cnv5, 'cnv5_se_attention', ratio=8) and convolves
+ * that (nets/posenn.py:227-228; nets/attention_module.py:9-52: mean over (h, w), dense 256 -> 32 ReLU, dense 32 -> 256 sigmoid,
+ * x * s), so rotation/cnv6 reads cnv5 * s_r and translation/cnv6 reads (cnv5 * s_r) * s_t with s_t computed from the ALREADY
+ * scaled tensor.  The variant gains the variables pose_exp_net/pose/{rotation,translation}/cnv5_se_attention/
+ * {bottleneck_fc,recover_fc}/{kernel,bias}: (256,32), (32,), (32,256), (256,).  Valid with att_source 0 (`-no_segmask', the
+ * published combination) only, and only before the first davo_load_weight and the first forward (it changes the set of
+ * variables, cnv6's weight layout and the workspace): afterwards DAVO_ERR_INVALID.  Inputs and every other entry point are
+ * unchanged; `-se_skipadd' and `-se_replace' are not built. */
+int davo_set_posenn_se(davo_ctx* ctx, int mode);
+
 /* Replaces tf.train.Saver(tf.trainable_variables()).restore(sess, ckpt)
  * (test_kitti_pose.py:129-131), one tensor at a time, keyed by the TF variable name
  * (e.g. "pose_exp_net/cnv1/weights", "pose_exp_net/pose/rotation/cnv6/biases",
@@ -380,12 +392,15 @@ int davo_comm_destroy(davo_ctx* ctx);
 /* ---- test hooks -------------------------------------------------------------------------
  * impl 0 = MFMA implicit-GEMM kernels (default, the product path);
  * impl 1 = one-thread-per-output direct convolution in HIP on the reference's own tensor
- *          layouts (10-channel input, HWIO weights) — an on-device cross-check, never timed. */
+ *          layouts (10-channel input, HWIO weights) — an on-device cross-check, never timed
+ *          (the feature-attention block runs on it too: the float32 forms of its three kernels). */
 int davo_set_impl(davo_ctx* ctx, int impl);
 
 /* Copy an intermediate of the LAST forward to host (float32, NHWC, pair-image major = 2B images):
  * "att_table" [B,3,19], "packed" [2B,H,W,8|10], "cnv1".."cnv5", "cnv6" [.., 2*cnv6_out]
- * (rotation | translation), "cnv7" [.., 512].  n_floats must equal the tensor size. */
+ * (rotation | translation), "cnv7" [.., 512].  With davo_set_posenn_se(ctx, 1) also "cnv5_se_scale" [2B,2,256] (row 0 = s_r,
+ * row 1 = s_r * s_t) and "cnv5_se" [2B,H/4,W/4,512] (cnv6's rotation input | its translation input).
+ * n_floats must equal the tensor size. */
 int davo_debug_read(davo_ctx* ctx, const char* tensor, float* host_out, size_t n_floats);
 
 /* Stand-alone slim.conv2d(padding='SAME') (nets/posenn.py:205-215) through the same MFMA
