@@ -877,6 +877,29 @@ int davo_set_activation_shifts(davo_ctx* c, const int* shifts) {
     return DAVO_OK;
 }
 
+int davo_reset_range_state(davo_ctx* c) {
+    if (!c) return DAVO_ERR_INVALID;
+    HIP_TRY(c, hipSetDevice(c->device));
+    // batches issued so far get their verdict - and their recovery - under the scales they ran with; with "auto_range" 0 a failed
+    // verdict is this call's result, after the state has been reset all the same
+    const int verdict = judge_all(c);
+    if (verdict && verdict != DAVO_ERR_RANGE) return verdict;
+    const std::string verdict_err = c->err;
+    { int rc = freeze_pending_and_reset_ring(c); if (rc) return rc; }       // no ticket is pending: this zeroes the ring's records
+    { int rc = zero_now(c, c->d_range_base, RANGE_WORDS * sizeof(unsigned)); if (rc) return rc; }
+    for (int i = 0; i < 7; ++i) c->act_shift[i] = 0;
+    for (int i = 0; i < 6; ++i) c->range_seen[i] = 0.f;
+    c->host_since_fresh = 1 << 30;                                           // the counters' and the cursor's initial values (ctx.h)
+    c->since_fresh_record = 0;
+    c->ring_next = 0;
+    c->d_range = c->d_range_base;
+    c->range_zero = false;
+    c->sticky_range_rc = 0; c->sticky_range_err.clear();
+    c->range_report.clear();
+    if (verdict) { c->err = verdict_err; return verdict; }
+    return DAVO_OK;
+}
+
 // the body of davo_calibrate / davo_calibrate_depth (depth_form)
 static int calibrate_entry(davo_ctx* c, int B, const void* d_img, const void* d_flow, const void* d_seg, const void* d_depth, int* shifts_out,
                            bool depth_form) {

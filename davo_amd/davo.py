@@ -260,6 +260,12 @@ class Engine:
         vals = [shifts[k] for k in self.LAYERS] if isinstance(shifts, dict) else list(shifts)
         self._check(self._L.davo_set_activation_shifts(self._ctx, (ctypes.c_int * 6)(*vals)))
 
+    def reset_range_state(self):
+        """Back to a new engine's range state: no storage scales, zeroed range records and counters, an empty range_report
+        (include/davo_hip.h: davo_reset_range_state).  Between independent jobs on one engine - the sequences of one
+        run_kitti_pose launch - so that a job computes what it would on an engine of its own.  range_stats() keeps counting."""
+        self._check(self._L.davo_reset_range_state(self._ctx))
+
     def forward_device(self, B, d_img, d_flow, d_seg, d_pose, timed=False, depth=None):
         """``depth``: the DeviceBuffer of the depth planes, required by a depth-source variant (davo_forward_device_depth)."""
         ms = ctypes.c_float(0.0)

@@ -287,17 +287,28 @@ def _chunk_owner(c, chunks_per_ring, P):
     return (c % chunks_per_ring) % P
 
 
-def _slot_worker(k, P, names, ctrl_name, B, H, W, dump_dir, seq, flow_planes, seg_planes, lo, hi, chunk, nring, sem, errq):
-    """Worker k of P (a fork of the warm fork server): fills its chunks of windows [lo, hi) in order, straight into the shared batch
-    buffers.  No task queue: which chunks are its own follows from k (_chunk_owner); ctrl[0] = number of batches that may be filled
+def _segment_batches(segments, B):
+    """The batches of ``segments`` = [(seq, lo, hi), ...] in the order they are served: [(seq, s, e), ...].  A segment is batched on
+    its own (its last batch may be short, an empty segment has none), and a batch's index in this list - not its window numbers - is
+    what places it in the ring and gives its chunks their owners, so a segment's length never shifts the ownership of the next one's."""
+    return [(seq, s, min(s + B, hi)) for seq, lo, hi in segments for s in range(lo, hi, B)]
+
+
+def _slot_worker(k, P, names, ctrl_name, B, H, W, dump_dir, segments, flow_planes, seg_planes, chunk, nring, sem, errq):
+    """Worker k of P (a fork of the warm fork server): fills its chunks of the batches of ``segments`` (_segment_batches) in order,
+    straight into the shared batch buffers, walking on from one segment into the next as ring places free up.  No task queue: which
+    chunks are its own follows from k (_chunk_owner); ctrl[0] = number of batches that may be filled
     (the consumer's progress + the ring), ctrl[1] = stop, ctrl[2 + k] = chunks this worker has finished, ctrl[2 + P + k] = ns it
-    worked.  One semaphore post per finished chunk wakes the consumer."""
+    worked, ctrl[2 + 2 P + k] = 1 + the batch at which this worker failed (0 = it has not): the consumer raises the failure when it
+    comes to that batch, and the batches before it - an earlier segment's, say - are still served.  One semaphore post per finished
+    chunk wakes the consumer."""
     import time
     from multiprocessing import shared_memory
     _keep_freed_memory_mapped()
     ctrl_shm = shared_memory.SharedMemory(name=ctrl_name)
-    ctrl = np.ndarray((2 + 2 * P,), np.int64, buffer=ctrl_shm.buf)
+    ctrl = np.ndarray((2 + 3 * P,), np.int64, buffer=ctrl_shm.buf)
     segs = []
+    bi = 0
     try:
         ring = []
         for trio in names:
@@ -308,13 +319,14 @@ def _slot_worker(k, P, names, ctrl_name, B, H, W, dump_dir, seq, flow_planes, se
                          np.ndarray((B, 3, H, W, 1), np.float32, buffer=t[2].buf)) +
                         ((np.ndarray((B, 3, H, W, 1), np.float32, buffer=t[3].buf),) if len(t) == 4 else ()))     # a depth variant's fourth buffer
         cpb = -(-B // chunk)                               # chunks per batch (the last one of a batch may be short)
-        nbatches = -(-(hi - lo) // B)
-        for c in range(nbatches * cpb):
+        batches = _segment_batches(segments, B)
+        for c in range(len(batches) * cpb):
             if _chunk_owner(c, cpb * nring, P) != k:
                 continue
             bi, j = divmod(c, cpb)
-            w0 = lo + bi * B + j * chunk
-            w1 = min(w0 + chunk, lo + bi * B + B, hi)
+            seq, s, e = batches[bi]
+            w0 = s + j * chunk
+            w1 = min(w0 + chunk, e)
             if w0 < w1:
                 while ctrl[0] <= bi:                       # the ring entry still holds a batch the consumer has not released
                     if ctrl[1]:
@@ -326,7 +338,7 @@ def _slot_worker(k, P, names, ctrl_name, B, H, W, dump_dir, seq, flow_planes, se
                 img, flow, seg = ring[bi % nring][:3]
                 dep = ring[bi % nring][3] if len(ring[bi % nring]) == 4 else None
                 for w in range(w0, w1):
-                    i = w - lo - bi * B
+                    i = w - s
                     load_window_into(dump_dir, seq, w + 1, H, W, img[i], flow[i], seg[i], None, flow_planes, seg_planes,
                                      depth=None if dep is None else dep[i])
                 ctrl[2 + P + k] += time.perf_counter_ns() - t0
@@ -344,7 +356,7 @@ def _slot_worker(k, P, names, ctrl_name, B, H, W, dump_dir, seq, flow_planes, se
             errq.put(exc)
         except Exception:                                  # noqa: BLE001 - an exception that does not pickle
             errq.put(RuntimeError("loader worker %d: %r" % (k, exc)))
-        ctrl[1] = 1
+        ctrl[2 + 2 * P + k] = bi + 1                       # after the put: the consumer that sees this finds the exception queued
         sem.release()
     finally:
         del ctrl
@@ -377,13 +389,32 @@ class ProcessWindowLoader:
 
     A batch is valid until the consumer has asked for ``hold`` + 1 further ones (``hold`` = 0: until the next one); the last
     ones until ``close()`` (or the loader's deletion), which unpins and unmaps the buffers.  The end of iteration stops the
-    workers and removes the segments' names."""
+    workers and removes the segments' names.
+
+    ``segments`` = [(seq, lo, hi), ...] (then ``seq``, ``lo`` and ``hi`` are None): several window ranges, usually of several
+    sequences, from ONE worker pool and ONE ring - the workers fork and attach once, the parent page-locks once.  ``segment(k)``
+    iterates the batches of segment k, in the order of the list; each segment is batched on its own (its batches are those of a
+    loader built for it alone), and behind a segment's last batch the workers walk on into the next one as ring places free up,
+    so it is being decoded while the consumer is still busy with what follows the segment (a gather, a file to write).  ``hold``
+    counts batches across the boundary: the last batch of segment k stays valid until ``hold`` + 1 batches of later segments have
+    been asked for.  The workers stop when the last segment has been served, or when an iterator is abandoned or fails."""
 
     def __init__(self, dump_dir, seq, H, W, lo, hi, batch_size, procs=8, prefetch=2, chunk=None, pin=None, unpin=None,
-                 flow_planes=FLOW_PLANES_USED, seg_planes=SEG_PLANES_SOURCES, shm_budget=None, hold=0, depth=False):
+                 flow_planes=FLOW_PLANES_USED, seg_planes=SEG_PLANES_SOURCES, shm_budget=None, hold=0, depth=False, segments=None):
+        if segments is None:
+            segments = [(seq, lo, hi)]
+        elif seq is not None or lo is not None or hi is not None:
+            raise ValueError("segments= replaces seq, lo and hi: pass None for those")
+        self.segments = [(int(q), int(a), max(int(a), int(b))) for q, a, b in segments]
+        if not self.segments:
+            raise ValueError("no segment to load")
+        seq, lo, hi = self.segments[0]
         self.args = (dump_dir, seq, H, W)
         self.depth = bool(depth)
         self.lo, self.hi, self.B = lo, hi, batch_size
+        self._batches = _segment_batches(self.segments, batch_size)
+        self._first = np.cumsum([0] + [-(-(b - a) // batch_size) for _, a, b in self.segments])      # a segment's first batch
+        self._served = 0                                   # segments handed out so far (they are served in order)
         self.procs, self.prefetch, self.hold = max(1, procs), max(1, prefetch), max(0, hold)
         self.chunk = max(1, min(chunk or 4, batch_size))
         # batches being filled at once: enough windows in flight (three chunks per worker) that no worker idles at a batch's end
@@ -408,7 +439,11 @@ class ProcessWindowLoader:
         self.busy_s = 0.0
 
     def __len__(self):
-        return -(-(self.hi - self.lo) // self.B)
+        return len(self._batches)                          # of all segments
+
+    def worker_pids(self):
+        """process ids of the running workers (none before start() and after the end of iteration)"""
+        return [p.pid for p in self._pool or []]
 
     def _open(self):
         self.close()                                      # a second iteration starts from fresh buffers
@@ -425,15 +460,15 @@ class ProcessWindowLoader:
             if self.depth:
                 views += (np.ndarray((B, 3, H, W, 1), np.float32, buffer=trio[3].buf),)
             self._views.append(views)
-        self._ctrl_shm = shared_memory.SharedMemory(create=True, size=8 * (2 + 2 * P))
-        self._ctrl = np.ndarray((2 + 2 * P,), np.int64, buffer=self._ctrl_shm.buf)
+        self._ctrl_shm = shared_memory.SharedMemory(create=True, size=8 * (2 + 3 * P))
+        self._ctrl = np.ndarray((2 + 3 * P,), np.int64, buffer=self._ctrl_shm.buf)
         self._ctrl[:] = 0
         self._ctrl[0] = self.nring                        # nothing is with the consumer yet: every ring entry may be filled
         names = [[sm.name for sm in trio] for trio in self._segs]
         ctx = worker_context()
         self._sem, self._errq = ctx.Semaphore(0), ctx.SimpleQueue()
         self._pool = [ctx.Process(target=_slot_worker, daemon=True,
-                                  args=(k, P, names, self._ctrl_shm.name, B, H, W, dump_dir, seq, self.fp, self.sp, self.lo, self.hi,
+                                  args=(k, P, names, self._ctrl_shm.name, B, H, W, dump_dir, self.segments, self.fp, self.sp,
                                         self.chunk, self.nring, self._sem, self._errq)) for k in range(P)]
         for p in self._pool:                              # forks of the warm server: they attach the buffers and start filling at once
             p.start()
@@ -464,6 +499,7 @@ class ProcessWindowLoader:
         self._cpb = -(-B // self.chunk)
         self._need = np.zeros(P, np.int64)
         self._need_upto = 0                               # chunks counted into _need so far
+        self._served = 0
 
     def _stop(self):
         """end of iteration: the workers stop; the names leave /dev/shm (nothing leaks if the process dies from here on) while
@@ -533,34 +569,52 @@ class ProcessWindowLoader:
         for c in range(self._need_upto, upto):
             self._need[_chunk_owner(c, self._cpb * self.nring, P)] += 1
         self._need_upto = max(self._need_upto, upto)
-        prog = self._ctrl[2:2 + P]
-        while not (prog >= self._need).all():
+        prog, failed = self._ctrl[2:2 + P], self._ctrl[2 + 2 * P:2 + 3 * P]
+        while True:
+            # a worker's failure belongs to the batch it met it at: the batches before that one are served first
+            if failed.any() and failed[failed > 0].min() - 1 <= bi:
+                raise self._errq.get()
+            if (prog >= self._need).all():
+                return
             if not self._sem.acquire(timeout=0.05):
                 for p in self._pool:
                     if not p.is_alive() and p.exitcode not in (0, None):
                         raise RuntimeError("a loader worker died (exit code %s)" % p.exitcode)
             if self._ctrl[1]:
-                if not self._errq.empty():
-                    raise self._errq.get()
                 raise RuntimeError("the loader's workers stopped")
 
     def __iter__(self):
+        if len(self.segments) > 1:
+            raise TypeError("a loader of several segments is iterated segment by segment: segment(k)")
+        return self.segment(0)
+
+    def segment(self, k):
+        """Iterator over the batches of segment k: ``(s, e, parts)`` with s, e the segment's own window numbers.  Segments are
+        served in order, each once per start()."""
         self.start()
-        nb = len(self)
+        if k != self._served:
+            raise ValueError("segment %d asked for, segment %d is next: segments are served in order" % (k, self._served))
+        self._served += 1
+        return self._serve(k)
+
+    def _serve(self, k):
+        done = False
         try:
-            for bi in range(nb):
+            for bi in range(self._first[k], self._first[k + 1]):
                 # asking for batch bi releases the batches up to bi - 1 - hold: their ring entries may be refilled
                 self._ctrl[0] = max(0, bi - self.hold) + self.nring
                 self._wait_for(bi)
                 self._pin_ready[bi % self.nring].wait()
                 if getattr(self, "_pin_exc", None) is not None:
                     raise self._pin_exc
-                s = self.lo + bi * self.B
-                e = min(s + self.B, self.hi)
+                _, s, e = self._batches[bi]
+                done = bi + 1 == self._first[k + 1]        # a consumer that never asks beyond the last batch has not abandoned the segment
                 yield s, e, tuple(v[:e - s] for v in self._views[bi % self.nring])
+            done = True
         finally:
-            self._started = False
-            self._stop()
+            if not done or k + 1 == len(self.segments):    # the last segment's end, a failure or an abandoned iterator: the workers stop
+                self._started = False
+                self._stop()
 
 
 def kitti_loader(dump_dir, seq, H, W, lo, hi, batch_size, workers=4, prefetch=2, alloc=None, decode_procs=0, depth=False):

@@ -5,6 +5,8 @@ writes ``<seq>-pred_kitti_pose.txt``.
     python -m davo_amd.run_kitti_pose --test_seq 3 --concat_img_dir DUMP --ckpt_file W.npz \
         --output_dir out --version v1-...                    # one GPU
     python -m davo_amd.run_kitti_pose ... --batch_size 64 --gpus 8     # windows sharded over 8 GPUs
+    python -m davo_amd.run_kitti_pose --test_seq 0-10 ...              # eleven sequences, one launch: one context, one
+                                                                       # communicator, one loader pool; a file per sequence
 
 With ``--gpus N`` the command starts N ranks of itself, one per GPU (davo_amd/launch.py; a launcher that
 sets RANK / LOCAL_RANK / WORLD_SIZE itself, e.g. ``python -m torch.distributed.run``, works too); the ranks'
@@ -50,18 +52,60 @@ def loader_seg_planes(cfg):
     return (0, 1, 2) if cfg.tgt_attended else None
 
 
+def check_checkpoint(path):
+    """--ckpt_file names something that can be opened: an .npz, or a TF V2 checkpoint's prefix / .index file / directory (the
+    file itself is read later, behind the GPU set-up).  Raises FileNotFoundError / ValueError with the path."""
+    if not path:
+        raise ValueError("--ckpt_file is required without --synthetic")
+    if path.endswith(".npz"):
+        if not os.path.isfile(path):
+            raise FileNotFoundError("no checkpoint %s" % path)
+        return
+    from .tf_checkpoint import resolve_checkpoint
+    index = resolve_checkpoint(path) + ".index"
+    if not os.path.isfile(index):
+        raise FileNotFoundError("no checkpoint %s (%s is missing)" % (path, index))
+
+
+def sequences_to_run(a):
+    """The run's sequences from the parsed flags, validated without touching a GPU: -> ([(seq, n_frames), ...], synthetic).
+    Every <dump>/NN exists, every sequence has a window (three frames), the checkpoint is there; ValueError / FileNotFoundError
+    name what is not."""
+    seqs = S.parse_seq_list(a.test_seq)
+    counts = S.parse_frame_counts(a.synthetic, len(seqs)) if a.synthetic is not None else [0]
+    synthetic = any(counts)                                  # "--synthetic 0" is "not synthetic", as it has always been
+    if not synthetic:
+        if not a.concat_img_dir:
+            raise ValueError("--concat_img_dir (or --synthetic N) is required")
+        counts = []
+        for q in seqs:
+            d = os.path.join(a.concat_img_dir, "%.2d" % q)
+            if not os.path.isdir(d):
+                raise FileNotFoundError("sequence %.2d: no directory %s" % (q, d))
+            counts.append(sum(1 for f in os.listdir(d) if f.endswith(".jpg")) + 2 * int((a.seq_length - 1) / 2))   # test_kitti_pose.py:81-82
+        check_checkpoint(a.ckpt_file)
+    for q, n in zip(seqs, counts):
+        if n < 3:
+            raise ValueError("sequence %.2d has %d frames: a window needs three" % (q, n))
+    return list(zip(seqs, counts)), synthetic
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch_size", type=int, default=1)          # test_kitti_pose.py:21
     ap.add_argument("--img_height", type=int, default=128)
     ap.add_argument("--img_width", type=int, default=416)
     ap.add_argument("--seq_length", type=int, default=3)
-    ap.add_argument("--test_seq", type=int, default=9)
+    ap.add_argument("--test_seq", default="9",
+                    help="a sequence number, or several for one launch: comma-separated numbers and inclusive ranges, e.g. 0,2,5-7 or "
+                         "0-10.  They run one after another, in this order, on one GPU context, one communicator and one loader worker "
+                         "pool; each gets its own NN-pred_kitti_pose.txt, byte for byte the file of a launch of its own")
     ap.add_argument("--concat_img_dir", default=None)
     ap.add_argument("--output_dir", required=True)
     ap.add_argument("--ckpt_file", default=None)
     ap.add_argument("--version", default=FLAGSHIP_VERSION)
-    ap.add_argument("--synthetic", type=int, default=0, help="frame count of a synthetic sequence")
+    ap.add_argument("--synthetic", default=None,
+                    help="frame count of a synthetic sequence: one count for every sequence of --test_seq, or a comma list with one per sequence")
     ap.add_argument("--gpus", type=int, default=1, help="GPUs of this node to shard the windows over (one rank per GPU)")
     ap.add_argument("--no_calibrate", action="store_true",
                     help="skip the activation-range calibration of the f16x3 arithmetic (include/davo_hip.h: davo_calibrate)")
@@ -92,6 +136,14 @@ def main(argv=None):
     def mark(name):
         marks.append((name, time.time()))
 
+    # what is to run, checked before anything is started - ranks, loader workers, the GPU context: a missing <dump>/NN of the
+    # eighth sequence is found now, not after the seven before it have run
+    try:
+        sequences, synthetic = sequences_to_run(a)
+    except ValueError as exc:
+        ap.error(str(exc))
+    except FileNotFoundError as exc:
+        raise SystemExit("davo_amd.run_kitti_pose: %s" % exc)
     from .comm import RcclComm, world_from_env, preload_in_background
     rank, local_rank, world = world_from_env()
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -102,12 +154,14 @@ def main(argv=None):
         raise SystemExit("--gpus %d but WORLD_SIZE=%d" % (a.gpus, world))
     device_index = local_rank
     emulate = tuple(int(x) for x in a.emulate_shard.split("/")) if a.emulate_shard else None
+    shard_of = lambda n_frames: S.shard_windows(n_frames - 2, *((world, rank) if emulate is None else (emulate[1], emulate[0])))   # noqa: E731
     need_comm = world > 1 or a.force_comm
     # Start-up is a rank's whole run on a sharded sequence (a 568-window shard is 0.1 s of work), so everything that does not depend
     # on each other starts at once: librccl loads on a thread of its own (573 MB to map: most of a second, needed only at the
     # gather), the input pipeline's workers fork and its buffers are created and page-locked on another, while this thread reads
     # the checkpoint and builds the GPU context.  (Round 4 did these one after the other: 2.9 s from process start to the first
-    # batch in a fresh process, 1.7 s of it the communicator: profiles/r05b_config4_scene_streamed.json.)
+    # batch in a fresh process, 1.7 s of it the communicator: profiles/r05b_config4_scene_streamed.json.)  All of it is paid once
+    # per launch, however many sequences the launch runs.
     if need_comm:
         preload_in_background()
     import threading
@@ -117,16 +171,14 @@ def main(argv=None):
     load = weights = None
     from .version import parse_version
     needs_depth = parse_version(a.version).needs_depth           # a depth source: <dump>/SS/FFFFFF-monodepth2_depth.npy beside the other files
-    if a.synthetic:
-        n_frames = a.synthetic
-    else:
+    # this rank's shard of every sequence, in running order: the segments of the one loader
+    segments = [(seq, ) + shard_of(n_frames) for seq, n_frames in sequences]
+    if not synthetic:
         if a.loader_procs != 0:
             # the fork server the loader's workers come from starts importing numpy / Pillow now (davo_amd/loader.py: worker_context);
             # it is a spawned interpreter that never touches a GPU, and its 0.2 s of imports pass behind HIP's initialisation
             from .loader import warm_workers
             warm_workers()
-        d = os.path.join(a.concat_img_dir, "%.2d" % a.test_seq)
-        n_frames = sum(1 for f in os.listdir(d) if f.endswith(".jpg")) + 2 * int((a.seq_length - 1) / 2)      # test_kitti_pose.py:81-82
         from .davo import pinned_empty, pin_array, unpin_array    # batches are decoded straight into page-locked memory
         procs = a.loader_procs
         if procs < 0:
@@ -139,7 +191,7 @@ def main(argv=None):
                 pass
             procs = max(1, min(16, cores - 2))
         tgt_planes = loader_seg_planes(parse_version(a.version))
-        load = S.kitti_window_loader(a.concat_img_dir, a.test_seq, n_frames, H, W,
+        load = S.kitti_window_loader(a.concat_img_dir, sequences[0][0], sequences[0][1], H, W,
                                      alloc=lambda shape, dtype: pinned_empty(shape, dtype, device_index),
                                      workers=a.loader_threads, decode_procs=a.decode_procs, procs=procs,
                                      pin=lambda arr: (gpu_ready.wait(), pin_array(arr, device_index)), unpin=unpin_array,
@@ -148,8 +200,7 @@ def main(argv=None):
         # workers need no GPU.  Page-locking the buffers (1.4 GB at batch 64: 0.3 s) follows on the loader's own thread, entry by
         # entry, once the context below exists: HIP serialises hipHostRegister with the context's own allocations, and pinning
         # beside them made the context 0.25 s slower (profiles/r05an_config4_scene_shard_nocomm.json against r05ao).
-        shard = S.shard_windows(n_frames - 2, *((world, rank) if emulate is None else (emulate[1], emulate[0])))
-        loader_thread = threading.Thread(target=load.prestart, args=(shard[0], shard[1], a.batch_size), name="davo-loader-start")
+        loader_thread = threading.Thread(target=load.prestart_segments, args=(segments, a.batch_size), name="davo-loader-start")
         loader_thread.start()
         # ... and the checkpoint is read and parsed (0.06-0.1 s of file and numpy work, no GPU) on a third
         from .tf_checkpoint import load_weights
@@ -162,102 +213,152 @@ def main(argv=None):
                 ckpt["error"] = exc
         weights_thread = threading.Thread(target=read_checkpoint, name="davo-checkpoint-read")
         weights_thread.start()
-    # the GPU context: the communicator's thread needs it, and HIP's own initialisation (0.2-0.4 s) is on every path
-    from . import _lib
+    comm = None
     try:
-        _lib.lib()
-        mark("library_loaded")
-        system = DAVO(version=a.version, device=device_index)
-        system.setup_inference(H, W, "davo", a.seq_length, a.batch_size)
-        mark("gpu_context_created")
-    finally:
-        gpu_ready.set()                        # also on failure: the loader's pinning thread must not wait for ever
-    # the communicator is not needed before the gather: the id exchange and ncclCommInitRank (1.5-1.7 s, most of it inside HIP's
-    # code-object loading, which other HIP calls queue behind) run on a second thread from here on (collective; fails loudly at the
-    # gather, no other transport)
-    comm = RcclComm.from_env_async(system.engine) if need_comm else None
+        # the GPU context: the communicator's thread needs it, and HIP's own initialisation (0.2-0.4 s) is on every path
+        from . import _lib
+        try:
+            _lib.lib()
+            mark("library_loaded")
+            system = DAVO(version=a.version, device=device_index)
+            system.setup_inference(H, W, "davo", a.seq_length, a.batch_size)
+            mark("gpu_context_created")
+        finally:
+            gpu_ready.set()                        # also on failure: the loader's pinning thread must not wait for ever
+        # the communicator is not needed before the gather: the id exchange and ncclCommInitRank (1.5-1.7 s, most of it inside HIP's
+        # code-object loading, which other HIP calls queue behind) run on a second thread from here on (collective; fails loudly at the
+        # gather, no other transport)
+        comm = RcclComm.from_env_async(system.engine) if need_comm else None
 
-    if a.synthetic:
-        from . import synth
-        load = S.synthetic_window_loader(H, W, depth=needs_depth)
-        weights = synth.make_weights(a.version)
-    else:
-        weights_thread.join()
-        if "error" in ckpt:
-            raise ckpt["error"]
-        weights = ckpt["weights"]
-    mark("inputs_and_weights_ready")
-    system.load_weights(weights)
-    mark("weights_on_gpu")
-    infer = lambda *parts: system.inference(None, "pose", inputs=parts)["pose"]   # noqa: E731  (img, flow, seg[, depth])
-    if loader_thread is not None:
-        loader_thread.join()
-    mark("loader_started")
-    lo_hi = S.shard_windows(n_frames - 2, *((world, rank) if emulate is None else (emulate[1], emulate[0])))
-    ld = load.for_range(*lo_hi, a.batch_size) if hasattr(load, "for_range") else load
-    batches = ld
-    if not a.no_calibrate:
-        if a.calibrate_on_first_windows or a.synthetic or not hasattr(ld, "__iter__") or lo_hi[0] >= lo_hi[1]:
-            # windows 0..7 of the sequence on every rank: the storage scales - and with them the trajectory's last bits - do not
-            # depend on the world size.  Loaded inline: Pillow's import and eight decodes in front of this rank's first batch
-            system.calibrate(load(0, min(a.batch_size, 8, n_frames - 2)))
+        if synthetic:
+            from . import synth
+            load = S.synthetic_window_loader(H, W, depth=needs_depth)     # the same seeded windows whatever the sequence's number
+            weights = synth.make_weights(a.version)
         else:
-            # the first eight windows of THIS rank's first batch, which its loader's workers are decoding anyway (round 5: the inline
-            # load was 0.35 s of a rank's 0.8 s start-up, most of it importing Pillow into this process).  The scales are exact
-            # powers of two with 64x headroom: ranks that calibrate on different windows agree to float32 rounding
-            # (test_calibration_is_neutral_for_a_well_ranged_checkpoint), not to the bit: --calibrate_on_first_windows restores that
-            import itertools
-            it = iter(ld)
-            first = next(it)
-            n8 = min(8, first[1] - first[0])
-            system.calibrate(tuple(x[:n8] for x in first[2]))
-            batches = itertools.chain([first], it)
-    mark("calibrated_first_forward_done")
-    # streamed: a batch of the process loader stays valid while the next one is asked for (hold = 1), so davo_submit does not wait for
-    # its own copy; the threaded loader and the synthetic windows give no such promise (hold = 0)
-    from .loader import ProcessWindowLoader
-    stream_hold = lambda ld: 1 if isinstance(ld, ProcessWindowLoader) else 0      # noqa: E731
-    t0 = time.perf_counter()
-    timing = {}
-    # this rank's prefetching loader (started above): handed in ready-made and closed only after the trajectory is written -
-    # unpinning and unmapping ~1 GB of batch buffers takes 0.15 s and used to run inside run_sequence when the last reference died
-    stream = None if a.sync_driver else S.PoseStream(system.engine, hold=stream_hold(ld))
-    traj, poses = S.run_sequence(infer, batches, n_frames, a.batch_size, rank, world, comm, timing, emulate, stream)
-    dt = time.perf_counter() - t0
-    if rank == 0:
-        os.makedirs(a.output_dir, exist_ok=True)
-        out = os.path.join(a.output_dir, "%.2d-pred_kitti_pose.txt" % a.test_seq)   # :116
-        tw = time.perf_counter()
-        S.write_kitti_poses(out, traj)
-        timing["write_s"] = time.perf_counter() - tw
-        t_proc = _process_start_time()
-        names = [m[0] for m in marks]
-        times = [m[1] for m in marks]
-        startup = {"%s_s" % names[i]: times[i] - times[i - 1] for i in range(1, len(marks))}
-        if t_proc is not None and fresh:
-            startup["process_start_to_interpreter_up_s"] = times[0] - t_proc
-            startup["process_start_to_first_batch_s"] = times[-1] - t_proc
-        startup["first_batch_to_trajectory_written_s"] = time.time() - times[-1]
-        if getattr(comm, "t_ready", None) is not None and t_proc is not None and fresh:
-            startup["process_start_to_communicator_ready_s"] = comm.t_ready - t_proc      # built on a second thread; the gather waited for it
-            startup["process_start_to_trajectory_written_s"] = time.time() - t_proc
-        timing["startup"] = {k: round(v, 4) for k, v in startup.items()}
-        timing.update(total_s=dt + timing["write_s"], windows=n_frames - 2, world=world, batch_size=a.batch_size,
-                      windows_per_s=(n_frames - 2) / dt, range_recovery=system.engine.range_stats(),
-                      note="rank 0's seconds; load_wait_s = time the GPU side waited for the input pipeline, forward_s = H2D + kernels + "
-                           "pose D2H inside DAVO.inference (streamed: the time inside davo_submit), gather_s = the RCCL all-gather incl. staging and the "
-                           "wait for the communicator, which is built on a second thread from the moment the GPU context exists")
-        print("Done. Please check %s  (%d windows on %d GPU(s) in %.2f s incl. input generation/IO: input wait %.2f, forward %.2f, "
-              "gather %.3f, stitch %.2f, write %.2f%s)" % (out, n_frames - 2, world, dt, timing["load_wait_s"], timing["forward_s"],
-                                                           timing["gather_s"], timing["stitch_s"], timing["write_s"],
-                                                           "; streamed: forward = time inside davo_submit, drain %.3f" % timing["drain_s"]
-                                                           if "drain_s" in timing else ""))
-        if a.report:
-            import json
-            with open(a.report, "w") as f:
-                json.dump({k: (round(v, 4) if isinstance(v, float) else v) for k, v in timing.items()}, f)
-    if hasattr(ld, "close"):
-        ld.close()
+            weights_thread.join()
+            if "error" in ckpt:
+                raise ckpt["error"]
+            weights = ckpt["weights"]
+        mark("inputs_and_weights_ready")
+        system.load_weights(weights)
+        mark("weights_on_gpu")
+        infer = lambda *parts: system.inference(None, "pose", inputs=parts)["pose"]   # noqa: E731  (img, flow, seg[, depth])
+        if loader_thread is not None:
+            loader_thread.join()
+            loader_thread = None
+        mark("loader_started")
+        # streamed: a batch of the process loader stays valid while the next one is asked for (hold = 1) - across a sequence boundary
+        # too - so davo_submit does not wait for its own copy; the threaded loader and the synthetic windows give no such promise
+        # (hold = 0).  One stream serves the whole run
+        process_loader = not synthetic and load.segment_loader is not None
+        stream = None if a.sync_driver else S.PoseStream(system.engine, hold=1 if process_loader else 0)
+        clock = {}
+
+        def source(k, seq, n_frames, lo, hi):
+            # this rank's prefetching loader (started above) hands out the sequence's segment; it is closed only after the last
+            # trajectory is written - unpinning and unmapping ~1 GB of batch buffers takes 0.15 s
+            return load if synthetic else load.for_segment(k, segments, a.batch_size)
+
+        def before_sequence(k, seq, n_frames, ld):
+            """every sequence starts from a new context's range state and is calibrated as a launch of its own would calibrate it:
+            its trajectory does not depend on the sequences before it"""
+            if k:
+                system.engine.reset_range_state()
+            batches = None
+            if not a.no_calibrate:
+                lo, hi = shard_of(n_frames)
+                if a.calibrate_on_first_windows or synthetic or not hasattr(ld, "__iter__") or lo >= hi:
+                    # windows 0..7 of the sequence on every rank: the storage scales - and with them the trajectory's last bits - do not
+                    # depend on the world size.  Loaded inline: Pillow's import and eight decodes in front of this rank's first batch
+                    n8 = min(a.batch_size, 8, n_frames - 2)
+                    system.calibrate(load(0, n8) if synthetic else load.load_inline(seq, 0, n8))
+                else:
+                    # the first eight windows of THIS rank's first batch, which its loader's workers are decoding anyway (round 5: the inline
+                    # load was 0.35 s of a rank's 0.8 s start-up, most of it importing Pillow into this process).  The scales are exact
+                    # powers of two with 64x headroom: ranks that calibrate on different windows agree to float32 rounding
+                    # (test_calibration_is_neutral_for_a_well_ranged_checkpoint), not to the bit: --calibrate_on_first_windows restores that
+                    import itertools
+                    it = iter(ld)
+                    first = next(it)
+                    n8 = min(8, first[1] - first[0])
+                    system.calibrate(tuple(x[:n8] for x in first[2]))
+                    batches = itertools.chain([first], it)
+            if k == 0:
+                mark("calibrated_first_forward_done")
+                clock["wall"] = time.perf_counter()            # "first batch ready": where the first sequence's wall_s starts
+            clock["t0"] = time.perf_counter()
+            clock["range"] = system.engine.range_stats()
+            return batches
+
+        entries = []
+        for seq, traj, poses, timing in S.run_sequences(infer, sequences, source, a.batch_size, rank, world, comm, emulate, stream,
+                                                        before_sequence):
+            dt = time.perf_counter() - clock["t0"]
+            if rank != 0:
+                continue
+            n_windows = len(traj) - 2
+            os.makedirs(a.output_dir, exist_ok=True)
+            out = os.path.join(a.output_dir, "%.2d-pred_kitti_pose.txt" % seq)   # :116
+            tw = time.perf_counter()
+            S.write_kitti_poses(out, traj)
+            now = time.perf_counter()
+            timing["write_s"] = now - tw
+            stats = system.engine.range_stats()
+            timing.update(total_s=dt + timing["write_s"], windows=n_windows, windows_per_s=n_windows / dt,
+                          range_recovery={key: stats[key] - clock["range"][key] for key in stats})     # this sequence's own
+            entries.append(dict(timing, seq=seq, wall_s=now - clock["wall"]))   # from the previous trajectory written (or the first batch ready)
+            clock["wall"] = now
+            print("Done. Please check %s  (%d windows on %d GPU(s) in %.2f s incl. input generation/IO: input wait %.2f, forward %.2f, "
+                  "gather %.3f, stitch %.2f, write %.2f%s)" % (out, n_windows, world, dt, timing["load_wait_s"], timing["forward_s"],
+                                                               timing["gather_s"], timing["stitch_s"], timing["write_s"],
+                                                               "; streamed: forward = time inside davo_submit, drain %.3f" % timing["drain_s"]
+                                                               if "drain_s" in timing else ""))
+        if rank == 0:
+            t_proc = _process_start_time()
+            names = [m[0] for m in marks]
+            times = [m[1] for m in marks]
+            startup = {"%s_s" % names[i]: times[i] - times[i - 1] for i in range(1, len(marks))}
+            if t_proc is not None and fresh:
+                startup["process_start_to_interpreter_up_s"] = times[0] - t_proc
+                startup["process_start_to_first_batch_s"] = times[-1] - t_proc
+            startup["first_batch_to_trajectory_written_s"] = time.time() - times[-1]       # several sequences: to the last one's
+            if getattr(comm, "t_ready", None) is not None and t_proc is not None and fresh:
+                startup["process_start_to_communicator_ready_s"] = comm.t_ready - t_proc      # built on a second thread; the gather waited for it
+                startup["process_start_to_trajectory_written_s"] = time.time() - t_proc
+            run_wide = dict(startup={k: round(v, 4) for k, v in startup.items()}, world=world, batch_size=a.batch_size,
+                            note="rank 0's seconds; load_wait_s = time the GPU side waited for the input pipeline, forward_s = H2D + kernels + "
+                                 "pose D2H inside DAVO.inference (streamed: the time inside davo_submit), gather_s = the RCCL all-gather incl. staging and the "
+                                 "wait for the communicator, which is built on a second thread from the moment the GPU context exists")
+            if len(entries) == 1:          # one sequence: the report it has always had
+                report = {k: v for k, v in entries[0].items() if k not in ("seq", "wall_s")}
+                report.update(run_wide)
+            else:                          # several: the run's totals, and every sequence's own split under "sequences"
+                report = dict(run_wide, windows=sum(e["windows"] for e in entries), total_s=sum(e["wall_s"] for e in entries),
+                              sequences=entries)
+                report["note"] += "; sequences[i].wall_s = from the previous trajectory written (the first batch ready, for the first) to " \
+                                  "this one written, total_s = their sum; range_recovery = that sequence's own re-issues"
+            if a.report:
+                import json
+                rounded = lambda d: {k: (round(v, 4) if isinstance(v, float) else v) for k, v in d.items()}      # noqa: E731
+                if "sequences" in report:
+                    report["sequences"] = [rounded(e) for e in report["sequences"]]
+                with open(a.report, "w") as f:
+                    json.dump(rounded(report), f)
+    except BaseException:
+        # a sequence failed (S.SequenceError names it; run_sequences has drained the stream) or the set-up did: the workers stop and
+        # /dev/shm is cleaned, the communicator goes - without the barrier the other ranks may never reach.  Files written stay.
+        if loader_thread is not None:
+            loader_thread.join()
+        if hasattr(load, "close"):
+            load.close()
+        if comm is not None:
+            try:
+                comm.close()
+            except Exception:                  # noqa: BLE001 - the failure being raised is the one to report
+                pass
+        raise
+    if hasattr(load, "close"):
+        load.close()
     if comm is not None:
         comm.barrier()
         comm.close()

@@ -264,6 +264,84 @@ def run_sequence(infer_fn, load_windows, n_frames, batch_size, rank=0, world=1, 
     return traj, poses
 
 
+# ---- several sequences in one launch (run_inference.sh and kitti_benchmark/pose_kitti_eval.sh:28-37 loop over 00-10) ------
+def parse_seq_list(text):
+    """``--test_seq``: comma-separated sequence numbers and inclusive ranges, "0,2,5-7" -> [0, 2, 5, 6, 7].  The order is kept
+    as given; an empty item, a reversed range, a negative number or a sequence named twice is a ValueError."""
+    out = []
+    for item in str(text).split(","):
+        item = item.strip()
+        lo, dash, hi = item.partition("-")
+        if not lo.strip().isdigit() or (dash and not hi.strip().isdigit()):
+            raise ValueError("sequence list `%s': `%s' is neither a sequence number nor a range a-b" % (text, item))
+        lo, hi = int(lo), int(hi) if dash else int(lo)
+        if hi < lo:
+            raise ValueError("sequence list `%s': the range `%s' runs backwards" % (text, item))
+        for q in range(lo, hi + 1):
+            if q in out:
+                raise ValueError("sequence list `%s': sequence %d is named twice" % (text, q))
+            out.append(q)
+    return out
+
+
+def parse_frame_counts(text, n_sequences):
+    """``--synthetic``: one frame count for every sequence, or a comma list with one count per sequence -> [n_frames, ...]"""
+    items = [x.strip() for x in str(text).split(",")]
+    if not all(x.isdigit() for x in items):
+        raise ValueError("frame counts `%s': not a list of whole numbers" % text)
+    counts = [int(x) for x in items]
+    if len(counts) == 1:
+        counts *= n_sequences
+    if len(counts) != n_sequences:
+        raise ValueError("frame counts `%s': %d counts for %d sequences" % (text, len(counts), n_sequences))
+    return counts
+
+
+class SequenceError(RuntimeError):
+    """A sequence of a several-sequence run failed; ``seq`` is its number, ``__cause__`` what went wrong."""
+
+    def __init__(self, seq, cause):
+        super().__init__("sequence %.2d failed: %s: %s" % (seq, type(cause).__name__, cause))
+        self.seq = seq
+
+
+def run_sequences(infer_fn, sequences, source, batch_size, rank=0, world=1, comm=None, emulate=None, stream=None,
+                  before_sequence=None):
+    """run_sequence over several sequences, one after another, on one engine, one communicator and one stream: a generator of
+    ``(seq, traj, poses, timing)`` per sequence, in the order of ``sequences`` = [(seq, n_frames), ...].  Every sequence is
+    sharded over the ranks on its own (shard_windows(n_frames - 2, world, rank); a rank whose shard of a short sequence is empty
+    still takes part in its gather) and batched on its own: no batch straddles two sequences, and a sequence's batches - hence
+    its launch plans and its bits - are those of a run of that sequence alone.  A streamed run drains at every sequence's end:
+    the gather needs the poses.  ``timing`` is that sequence's own dict, as run_sequence fills it.
+
+    ``source(k, seq, n_frames, lo, hi)`` gives the k-th sequence's ``load_windows`` for this rank's shard [lo, hi) - anything
+    run_sequence takes; it is asked when the sequence's turn comes.  ``before_sequence(k, seq, n_frames, load_windows)`` runs in
+    front of each sequence (the product resets the range state and calibrates there) and may return a ``load_windows`` to use
+    instead - one it has taken the first batch from and put it back, say.
+
+    The caller consumes a sequence's result (writes its file) before asking for the next one, so what it does in between runs
+    while the loader's workers are already decoding the next sequence.  If a sequence fails, the stream is drained first - nothing
+    is delivered later into arrays that are gone - and a SequenceError naming it is raised from the failure; sequences already
+    yielded stay as they are.  Closing the loader and the communicator is the caller's."""
+    for k, (seq, n_frames) in enumerate(sequences):
+        timing = {}
+        try:
+            lo, hi = shard_windows(n_frames - 2, *((world, rank) if emulate is None else (emulate[1], emulate[0])))
+            load = source(k, seq, n_frames, lo, hi)
+            if before_sequence is not None:
+                replaced = before_sequence(k, seq, n_frames, load)
+                load = load if replaced is None else replaced
+            traj, poses = run_sequence(infer_fn, load, n_frames, batch_size, rank, world, comm, timing, emulate, stream)
+        except Exception as exc:
+            if stream is not None:
+                try:
+                    stream.drain()                        # the failed shard's output array is still alive here (the traceback holds it)
+                except Exception:                         # noqa: BLE001 - the first failure is the one to report
+                    pass
+            raise SequenceError(seq, exc) from exc
+        yield seq, traj, poses, timing
+
+
 # ---- on-disk inputs (data_loader.py:241-325; doc/preprocessing.md:50-114) -------------------
 class kitti_window_loader:
     """Loader factory over the reference's dump (davo_amd/loader.py): ``for_range(lo, hi, B)`` gives the
@@ -303,9 +381,56 @@ class kitti_window_loader:
                               depth=self.depth)
 
     def __call__(self, s, e):
+        return self.load_inline(self.seq, s, e)
+
+    def load_inline(self, seq, s, e):
+        """windows [s, e) of sequence ``seq``, loaded in this process"""
         from .loader import load_window
-        parts = [load_window(self.dir, self.seq, w + 1, self.H, self.W, self.depth) for w in range(s, e)]
+        parts = [load_window(self.dir, seq, w + 1, self.H, self.W, self.depth) for w in range(s, e)]
         return tuple(np.stack([p[k] for p in parts]) for k in range(4 if self.depth else 3))
+
+    # several sequences from one worker pool (``seq`` and ``n_frames`` of the constructor are not used by these)
+    def prestart_segments(self, segments, batch_size):
+        """prestart for a run over several sequences: ``segments`` = [(seq, lo, hi), ...], this rank's shard of every sequence
+        in the order they will run.  ONE process loader serves them all (davo_amd/loader.py: ProcessWindowLoader(segments=...)):
+        its workers fork, its buffers are created and page-locked once, and it decodes sequence k+1 behind sequence k's tail.
+        for_segment hands the segments out."""
+        if self.procs > 0 and getattr(self, "_multi", None) is None:
+            from . import loader as L
+            try:
+                ld = L.ProcessWindowLoader(self.dir, None, self.H, self.W, None, None, batch_size, self.procs, self.prefetch,
+                                           pin=self.pin, unpin=self.unpin, hold=self.hold, depth=self.depth, segments=segments,
+                                           seg_planes=L.SEG_PLANES_SOURCES if self.seg_planes is None else self.seg_planes)
+                self._multi = ((list(segments), batch_size), ld.start())
+            except L.ShmBudgetError as e:      # as for_range: the threaded loader, built per sequence
+                import sys
+                print("davo_amd: %s - falling back to the threaded loader" % e, file=sys.stderr)
+                self._multi = ((list(segments), batch_size), None)
+
+    @property
+    def segment_loader(self):
+        """the process loader that serves the segments (None: the threaded loader is built per sequence)"""
+        return (getattr(self, "_multi", None) or (None, None))[1]
+
+    def for_segment(self, k, segments, batch_size):
+        """The batch iterator of segment k of ``segments`` (see prestart_segments, which this calls if nobody has): the process
+        loader's ``segment(k)``, or - ``procs`` = 0, or /dev/shm too small - a threaded loader for that segment alone."""
+        self.prestart_segments(segments, batch_size)
+        multi = getattr(self, "_multi", None)
+        if multi is not None and multi[0] != (list(segments), batch_size):
+            raise ValueError("for_segment: not the segments the loader was started with")
+        if multi is not None and multi[1] is not None:
+            return multi[1].segment(k)
+        from . import loader as L
+        seq, lo, hi = segments[k]
+        return L.kitti_loader(self.dir, seq, self.H, self.W, lo, hi, batch_size, self.workers, self.prefetch, self.alloc, self.decode_procs,
+                              depth=self.depth)
+
+    def close(self):
+        """stop and unmap the several-segment loader, if one was built"""
+        multi, self._multi = getattr(self, "_multi", None), None
+        if multi is not None and multi[1] is not None:
+            multi[1].close()
 
 
 def synthetic_window_loader(H, W, seed=None, depth=False):

@@ -259,6 +259,14 @@ int davo_set_precision(davo_ctx* ctx, int precision);
 int davo_calibrate(davo_ctx* ctx, int batch, const void* d_img, const void* d_flow, const void* d_seg, int* shifts_out);
 int davo_activation_range(davo_ctx* ctx, float* max_abs, int* shifts, int reset);
 int davo_set_activation_shifts(davo_ctx* ctx, const int* shifts);
+/* Back to the range state davo_create left: batches issued so far are judged (and recovered) first, then the storage scales
+ * are all zero again, every range record is zeroed, the maxima of davo_activation_range start over, the every-256th-batch
+ * counters and the record ring's cursor are where a new context has them, and davo_range_report is "".  What the context does
+ * next - a davo_calibrate, its batches, their verdicts - is then what a new context with the same weights would do: a driver
+ * that runs several independent jobs (sequences) on one context calls this between them, and a job's results do not depend on
+ * the jobs before it.  The counts of davo_range_stats are not reset (they are "since davo_create"; take differences).
+ * Synchronises; launches nothing and changes nothing for a caller that never calls it. */
+int davo_reset_range_state(davo_ctx* ctx);
 /* Range recoveries since davo_create: re-calibrations triggered by a failed verdict, batches that ran on the float32
  * kernels because no scale covered them, batches re-issued in total.  Any pointer may be NULL. */
 int davo_range_stats(davo_ctx* ctx, long long* recalibrations, long long* f32_batches, long long* reissued);
