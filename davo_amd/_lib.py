@@ -46,6 +46,7 @@ EXPORTS = (
     "davo_host_alloc", "davo_host_free", "davo_host_register", "davo_host_unregister", "davo_calibrate", "davo_activation_range", "davo_set_activation_shifts", "davo_reset_range_state", "davo_range_stats", "davo_range_report",
     "davo_comm_preload", "davo_comm_unique_id", "davo_comm_init", "davo_comm_size", "davo_allgather_poses", "davo_allgather_poses_device",
     "davo_comm_allreduce", "davo_comm_barrier", "davo_comm_destroy", "davo_plan_layer", "davo_tile_filter_rows",
+    "davo_set_pairs", "davo_get_pairs",
 )
 COMM_ID_BYTES = 128
 
@@ -208,6 +209,8 @@ def _load():
     L.davo_set_option.argtypes = [vp, ctypes.c_char_p, i]
     L.davo_set_precision.argtypes = [vp, i]
     L.davo_set_impl.argtypes = [vp, i]
+    L.davo_set_pairs.argtypes = [vp, i]
+    L.davo_get_pairs.argtypes = [vp]
     L.davo_debug_read.argtypes = [vp, ctypes.c_char_p, f32p, ctypes.c_size_t]
     L.davo_conv2d_same.argtypes = [i, f32p, i, i, i, i, f32p, i, i, f32p, i, i, i, i, f32p, ctypes.c_char_p, i]
     ip = ctypes.POINTER(i)

@@ -303,15 +303,16 @@ int freeze_pending_and_reset_ring(davo_ctx* c) {
 // power-of-two storage scales from a sample batch: each pass runs the path and moves every layer's largest stored
 // value into [512, 1024).  A layer computed from badly ranged inputs still has about the right magnitude, so each
 // pass fixes at least the first badly ranged layer exactly and the later ones to within a few powers of two.
-// Runs on the base record; every stream must be idle.
-int calibrate_on(davo_ctx* c, int B, const Inputs& in, void* d_pose) {
+// Runs on the base record; every stream must be idle.  sel: davo_calibrate runs both pairs of the batch it is handed; a re-issue
+// calibrates on the pairs the batch ran (an unselected frame's planes may never have been copied: stale bytes).
+int calibrate_on(davo_ctx* c, int B, const Inputs& in, void* d_pose, int sel) {
     int rc = DAVO_OK;
     const int save_precision = c->precision, save_impl = c->impl;
     c->precision = 1; c->impl = 0;
     c->d_range = c->d_range_base;
     for (int pass = 0; pass < 8 && rc == DAVO_OK; ++pass) {
         if ((rc = zero_base_record(c, c->stream))) break;
-        rc = forward_device(c, B, in, d_pose);
+        rc = forward_device(c, B, in, d_pose, sel);
         if (rc) break;
         if (hipStreamSynchronize(c->stream) != hipSuccess) { rc = fail(c, DAVO_ERR_HIP, "hipStreamSynchronize failed"); break; }
         unsigned raw[RANGE_WORDS];
@@ -338,7 +339,7 @@ int calibrate_on(davo_ctx* c, int B, const Inputs& in, void* d_pose) {
 int run_judged(davo_ctx* c, const Ticket& b) {
     c->d_range = c->d_range_base;
     { int rc = zero_base_record(c, c->stream); if (rc) return rc; }
-    int rc = forward_device(c, b.B, b.in, b.pose);
+    int rc = forward_device(c, b.B, b.in, b.pose, b.pairs);
     if (rc) return rc;
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     if (c->last_precision != 1) return DAVO_OK;
@@ -349,7 +350,7 @@ int run_judged(davo_ctx* c, const Ticket& b) {
     return rc;
 }
 
-// A failed verdict: re-issue the batch - as issued if the scales have moved since and now hold it, re-calibrated on itself if
+// A failed verdict: re-issue the batch, with the pair selection it was issued with (Ticket::pairs) - as issued if the scales have moved since and now hold it, re-calibrated on itself if
 // not, on the float32 kernels if even that leaves the range (per-layer scales cannot cover e.g. an inf / NaN producing net).
 // Drains every stream first: the re-issue uses slot 0's workspace and the base record.
 // A caller may have handed the batch's pose buffer to a LATER batch since (two alternating buffers, one buffer overwritten every
@@ -372,7 +373,7 @@ int recover_batch(davo_ctx* c, const Ticket& orig) {
     activate_slot(c, 0);
     int rc = run_judged(c, b);
     if (rc == DAVO_ERR_RANGE) {
-        if ((rc = calibrate_on(c, b.B, b.in, b.pose))) return rc;
+        if ((rc = calibrate_on(c, b.B, b.in, b.pose, b.pairs))) return rc;
         ++c->n_recalibrations;
         rc = run_judged(c, b);
         c->range_report = "re-calibrated: " + verdict;
@@ -380,7 +381,7 @@ int recover_batch(davo_ctx* c, const Ticket& orig) {
     if (rc == DAVO_ERR_RANGE) {
         const int save = c->precision;
         c->precision = 0;
-        rc = forward_device(c, b.B, b.in, b.pose);
+        rc = forward_device(c, b.B, b.in, b.pose, b.pairs);
         c->precision = save;
         if (rc == DAVO_OK && hipStreamSynchronize(c->stream) != hipSuccess) rc = fail(c, DAVO_ERR_HIP, "hipStreamSynchronize failed");
         ++c->n_f32_batches;
@@ -485,7 +486,7 @@ int ticket_reserve(davo_ctx* c) {
 int ticket_begin(davo_ctx* c, int B, const Inputs& in, Ticket* t, bool own_inputs = false) {
     const int r = c->ring_next;
     *t = Ticket{};
-    t->B = B; t->ring = r;
+    t->B = B; t->ring = r; t->pairs = c->pairs;
     // own_inputs: the batch reads a staging set of the context (davo_submit), which the next batches overwrite whatever the caller declared
     t->snap = c->opt_auto_range && (!c->opt_stable_inputs || own_inputs);
     if (t->snap && (((uintptr_t)in.img | (uintptr_t)in.flow | (uintptr_t)in.seg | (uintptr_t)in.depth) & 15)) return fail(c, DAVO_ERR_INVALID, "device input buffers must be 16-byte aligned");
@@ -555,7 +556,7 @@ static int forward_device_entry(davo_ctx* c, int B, const void* d_img, const voi
     }
     note_pose_span(c, d_pose, B);
     if (!elapsed_ms) {
-        int rc = forward_device(c, B, in, d_pose);
+        int rc = forward_device(c, B, in, d_pose, c->pairs);
         if (ticketed) rc = ticket_end(c, rc, t, d_pose);
         else if (rc == DAVO_OK && c->f32_fallback) ++c->n_f32_batches;
         return rc;
@@ -568,7 +569,7 @@ static int forward_device_entry(davo_ctx* c, int B, const void* d_img, const voi
     };
     if (hip_ok(hipEventCreate(&e0), "hipEventCreate") && hip_ok(hipEventCreate(&e1), "hipEventCreate") &&
         hip_ok(hipEventRecord(e0, c->stream), "hipEventRecord")) {
-        rc = forward_device(c, B, in, d_pose);
+        rc = forward_device(c, B, in, d_pose, c->pairs);
         if (rc == DAVO_OK && hip_ok(hipEventRecord(e1, c->stream), "hipEventRecord") &&
             hip_ok(hipEventSynchronize(e1), "hipEventSynchronize"))
             hip_ok(hipEventElapsedTime(elapsed_ms, e0, e1), "hipEventElapsedTime");
@@ -629,10 +630,29 @@ Inputs from_window(const davo_ctx* c, const Inputs& in, int b0) {
 // depth enters every frame's descriptor, davo.py:1109).  sources_only_seg: unless the variant reads the target frame's label map too
 // (-segmask_all-static, the with-target class-table sources), only the two source frames' maps go (davo.py:998-1004, 1408-1412), in
 // batches of four windows and more.
-int stage_inputs(davo_ctx* c, const InputSet& set, const Inputs& host, int b0, int nb, bool sources_only_seg, hipStream_t s) {
+// One pair selected (sel, params.h): only what that pair reads is copied, each plane to its usual place - of every strip row the
+// byte range of (tgt, selected source), the source's flow plane, its label map (and the target's where the variant attends it),
+// for the depth sources the target's and the source's depth plane.  The regions skipped keep whatever they held; no kernel of a
+// one-pair batch reads them.  At 128x416: 319,488 + 425,984 + 212,992 = 958,464 B per window instead of 1,757,184.
+int stage_inputs(davo_ctx* c, const InputSet& set, const Inputs& host, int b0, int nb, bool sources_only_seg, int sel, hipStream_t s) {
     const PlaneBytes n = plane_bytes(c);
     const Inputs src = from_window(c, host, b0);
     auto dst = [b0](void* q, size_t bytes) { return static_cast<uint8_t*>(q) + bytes * b0; };
+    if (sel != PAIRS_BOTH) {
+        const int src1 = sel == PAIRS_SRC1;
+        auto copy2d = [&](uint8_t* d, const void* h, size_t pitch, size_t off, size_t width, size_t rows) {
+            return hipMemcpy2DAsync(d + off, pitch, static_cast<const uint8_t*>(h) + off, pitch, width, rows, hipMemcpyHostToDevice, s);
+        };
+        const size_t row = (size_t)c->W * 9, third = row / 3;       // strip row: src0 | tgt | src1 (data_loader.py:537-557)
+        HIP_TRY(c, copy2d(dst(set.img, n.img), src.img, row, src1 ? third : 0, 2 * third, (size_t)nb * c->H));
+        HIP_TRY(c, copy2d(dst(set.flow, n.flow), src.flow, n.flow, src1 ? n.flow / 4 : 0, n.flow / 4, nb));
+        // planes in file order src0, tgt, src1 (davo.py:991-1004): with the target, two neighbouring planes
+        const size_t plane = n.seg / 3;
+        if (att_tgt_attended(c->v.att_source)) HIP_TRY(c, copy2d(dst(set.seg, n.seg), src.seg, n.seg, src1 ? plane : 0, 2 * plane, nb));
+        else HIP_TRY(c, copy2d(dst(set.seg, n.seg), src.seg, n.seg, src1 ? 2 * plane : 0, plane, nb));
+        if (src.depth) HIP_TRY(c, copy2d(dst(set.depth, n.depth), src.depth, n.depth, src1 ? plane : 0, 2 * plane, nb));
+        return DAVO_OK;
+    }
     HIP_TRY(c, hipMemcpyAsync(dst(set.img, n.img), src.img, n.img * nb, hipMemcpyHostToDevice, s));
     if (nb == 1) HIP_TRY(c, hipMemcpyAsync(dst(set.flow, n.flow), src.flow, n.flow / 2, hipMemcpyHostToDevice, s));
     else HIP_TRY(c, hipMemcpy2DAsync(dst(set.flow, n.flow), n.flow, src.flow, n.flow, n.flow / 2, nb, hipMemcpyHostToDevice, s));
@@ -696,7 +716,7 @@ static int submit_entry(davo_ctx* c, int B, const uint8_t* img, const float* flo
     hipStream_t s = c->stream;
     // H2D on the slot's stream, in order behind the forward that last read this staging set
     const InputSet& set = c->stream_sets[slot];
-    { int rc = stage_inputs(c, set, Inputs{img, flow, seg, depth}, 0, B, true, s); if (rc) return rc; }
+    { int rc = stage_inputs(c, set, Inputs{img, flow, seg, depth}, 0, B, true, c->pairs, s); if (rc) return rc; }
     // the caller keeps a batch's inputs unchanged for `hold` more submits.  With hold >= STREAM_POSES the pose ring already implies it
     // (a batch is delivered - so its copies are long done - before the eighth submit after it returns): no event then
     const bool track_copy = hold < STREAM_POSES;
@@ -705,7 +725,7 @@ static int submit_entry(davo_ctx* c, int B, const uint8_t* img, const float* flo
     Ticket t{};
     if (ticketed) { int rc = ticket_begin(c, B, set.view(), &t, true); if (rc) return rc; }
     ++c->n_issued;                    // (no pose span: a pose ring entry is not reused before its batch has been delivered)
-    int rc = forward_device(c, B, set.view(), c->d_pose_ring[pr]);
+    int rc = forward_device(c, B, set.view(), c->d_pose_ring[pr], c->pairs);
     const unsigned seq = c->snap_seq_issued;
     bool has_ticket = false;
     if (ticketed) {
@@ -798,7 +818,7 @@ static int forward_entry(davo_ctx* c, int B, const uint8_t* img, const float* fl
     for (int i = 0; i < nchunks; ++i) {
         const int b0 = i * chunk, nb = std::min(chunk, B - b0);
         hipStream_t cs = nchunks == 1 ? c->stream : c->copy_stream;
-        { int rc = stage_inputs(c, c->host_set, Inputs{img, flow, seg, depth}, b0, nb, false, cs); if (rc) return rc; }      // the label maps whole
+        { int rc = stage_inputs(c, c->host_set, Inputs{img, flow, seg, depth}, b0, nb, false, c->pairs, cs); if (rc) return rc; }      // both pairs: the label maps whole
         if (nchunks > 1) {
             HIP_TRY(c, hipEventRecord(c->copy_done[i], c->copy_stream));
             HIP_TRY(c, hipStreamWaitEvent(c->stream, c->copy_done[i], 0));
@@ -809,7 +829,7 @@ static int forward_entry(davo_ctx* c, int B, const uint8_t* img, const float* fl
             c->snap = SnapArgs{};
             c->snap.record = c->d_range_base; c->snap.host_mirror = c->h_range_dev; c->snap.seq = seq; c->snap.B = nb; c->snap.se = c->posenn_se;
         }
-        int rc = forward_device(c, nb, from_window(c, c->host_set.view(), b0), (float*)c->s_pose + (size_t)b0 * 12);
+        int rc = forward_device(c, nb, from_window(c, c->host_set.view(), b0), (float*)c->s_pose + (size_t)b0 * 12, c->pairs);
         c->snap = SnapArgs{};
         if (rc) return rc;
         f32_fallback |= c->f32_fallback;
@@ -828,7 +848,7 @@ static int forward_entry(davo_ctx* c, int B, const uint8_t* img, const float* fl
     if (rc == DAVO_OK) note_seen(c, raw, c->act_shift);
     if (rc == DAVO_ERR_RANGE && c->opt_auto_range) {
         // the staged copy of the batch is still in HBM: re-issue it whole (recalibrated, or on the float32 kernels)
-        rc = recover_batch(c, [&] { Ticket t{}; t.B = B; t.in = c->host_set.view(); t.pose = c->s_pose; t.ring = -1; t.stream = c->stream; t.issue = ~0ull; return t; }());
+        rc = recover_batch(c, [&] { Ticket t{}; t.B = B; t.pairs = c->pairs; t.in = c->host_set.view(); t.pose = c->s_pose; t.ring = -1; t.stream = c->stream; t.issue = ~0ull; return t; }());
         if (rc == DAVO_OK) HIP_TRY(c, hipMemcpy(pose_out, c->s_pose, (size_t)B * 12 * sizeof(float), hipMemcpyDeviceToHost));
     }
     return rc;
@@ -913,7 +933,7 @@ static int calibrate_entry(davo_ctx* c, int B, const void* d_img, const void* d_
     activate_slot(c, 0);
     float* d_pose = nullptr;
     HIP_TRY(c, hipMalloc(reinterpret_cast<void**>(&d_pose), (size_t)B * 12 * sizeof(float)));
-    const int rc = calibrate_on(c, B, Inputs{d_img, d_flow, d_seg, d_depth}, d_pose);
+    const int rc = calibrate_on(c, B, Inputs{d_img, d_flow, d_seg, d_depth}, d_pose, PAIRS_BOTH);
     (void)hipFree(d_pose);
     if (rc == DAVO_OK && shifts_out) for (int i = 0; i < 6; ++i) shifts_out[i] = c->act_shift[i];
     return rc;
@@ -1170,6 +1190,16 @@ int davo_set_precision(davo_ctx* c, int precision) {
     return DAVO_OK;
 }
 
+int davo_set_pairs(davo_ctx* c, int pairs) {
+    if (!c) return DAVO_ERR_INVALID;
+    if (pairs != DAVO_PAIRS_SRC0 && pairs != DAVO_PAIRS_SRC1 && pairs != DAVO_PAIRS_BOTH)
+        return fail(c, DAVO_ERR_INVALID, "pairs must be DAVO_PAIRS_SRC0 (1), DAVO_PAIRS_SRC1 (2) or DAVO_PAIRS_BOTH (3), got %d", pairs);
+    c->pairs = pairs;              // batches in flight and their re-issues keep theirs (Ticket::pairs)
+    return DAVO_OK;
+}
+
+int davo_get_pairs(const davo_ctx* c) { return c ? c->pairs : DAVO_ERR_INVALID; }
+
 int davo_set_impl(davo_ctx* c, int impl) {
     if (!c || (impl != 0 && impl != 1)) return fail(c, DAVO_ERR_INVALID, "impl must be 0 (mfma) or 1 (direct)");
     c->impl = impl;
@@ -1179,7 +1209,7 @@ int davo_set_impl(davo_ctx* c, int impl) {
 int davo_debug_read(davo_ctx* c, const char* tensor, float* host_out, size_t n_floats) {
     if (!c || !tensor || !host_out) return DAVO_ERR_INVALID;
     if (c->last_B < 1) return fail(c, DAVO_ERR_NOT_READY, "no forward has run yet");
-    const size_t NB = 2 * (size_t)c->last_B;
+    const size_t NB = (size_t)pairs_per_window(c->last_pairs) * c->last_B;      // pair images of the last forward
     const float* src = nullptr;
     size_t n = 0;
     const std::string t = tensor;
@@ -1192,7 +1222,7 @@ int davo_debug_read(davo_ctx* c, const char* tensor, float* host_out, size_t n_f
     else if (t == "packed") {
         if (!c->packed_valid) {          // fused path: materialise the packed tensor on demand from the last inputs
             HIP_TRY(c, launch_mask_pack(16, static_cast<const uint8_t*>(c->last_in.img), static_cast<const float*>(c->last_in.flow),
-                                        static_cast<const float*>(c->last_in.seg), c->d_tab, c->v, c->last_B, c->H, c->W, c->d_packed, c->stream));
+                                        static_cast<const float*>(c->last_in.seg), c->d_tab, c->v, c->last_B, c->H, c->W, c->d_packed, c->last_pairs, c->stream));
             c->packed_valid = true;
         }
         src = c->d_packed; n = NB * c->H * c->W * c->packed_ld;

@@ -142,7 +142,7 @@ __global__ __launch_bounds__(cp1::THREADS, 3) void conv_patch_cnv1_h3(ConvPatchP
                 __builtin_amdgcn_global_load_lds((gptr_t*)src, (lptr_t*)(patch + k * 1024), 16, 0, 0);
             }
         } else {
-            const int b = n >> 1, s = n & 1;
+            const int b = pair_window(n, p.sel), s = pair_source(n, p.sel);
             const Variant& v = p.v;
             const size_t HW = (size_t)p.H * p.W;
             const float* tab_s = p.tab + ((size_t)b * 3 + 1 + s) * NCLS;

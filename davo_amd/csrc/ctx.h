@@ -88,6 +88,7 @@ constexpr int RANGE_RING = 8;
 constexpr int SK_TILE_COUNTERS = 256;            // tiles of a split-K launch whose fix-up is folded in (forward.hip): at most one per CU
 struct Ticket {
     int B;
+    int pairs;                                 // the pair selection the batch was issued with: every re-issue runs the same pairs, whatever davo_set_pairs said since
     Inputs in;                                 // what a re-issue reads: the ring slot's snapshot, or the caller's buffers ("stable_inputs")
     void* pose;
     int ring;
@@ -185,6 +186,9 @@ struct davo_ctx {
     int act_ch[7];
     int packed_ld = 8;
     int last_B = 0;
+    int pairs = davo::PAIRS_BOTH;              // davo_set_pairs: the pairs of every window the batches issued from now on run
+    int run_pairs = davo::PAIRS_BOTH;          // ... of the batch forward_device is issuing (the layer runners read it)
+    int last_pairs = davo::PAIRS_BOTH;         // ... of the last forward: davo_debug_read sizes its tensors by last_B windows of that many pair images
     bool packed_valid = true;                  // false when cnv1 consumed the raw inputs directly (fused)
     davo::Inputs last_in{};                    // the last forward's inputs: davo_debug_read("packed") re-packs from them after a fused cnv1
     int last_plan[7][2] = {};                  // per layer, per launch: 128-row M tiles * 1000 + tile id / BN (reported by the bench)
@@ -328,7 +332,8 @@ inline void split_f16(float v, _Float16* hi, _Float16* lo) {
 
 // ---- forward.hip ----------------------------------------------------------------------------
 void activate_slot(davo_ctx* c, int i);
-int forward_device(davo_ctx* c, int B, const Inputs& in, void* d_pose);
+// sel: the batch's pair selection (params.h: PAIRS_*) - the context's for a new batch, the ticket's for a re-issue
+int forward_device(davo_ctx* c, int B, const Inputs& in, void* d_pose, int sel);
 // f16x3: verdict on the range record (d_range) read back from the device; DAVO_ERR_RANGE names the layer
 int check_range(davo_ctx* c, const unsigned* raw /*[RANGE_WORDS]*/, const int* shifts = nullptr);
 

@@ -7,7 +7,9 @@
 //   -> cnv6 as a two-group layer (group g reads channels [256 g, 256 g + 256)) -> cnv7 as before (posenn_se.h).
 //
 // The two PoseNN calls of a triplet (davo.py:1456-1457, shared weights) run as one batch of
-// 2B pair images.  Host code only: kernels are reached through launch.h.
+// 2B pair images - or, with one pair selected (davo_set_pairs; params.h), as B pair images: the prologue and the pose kernels map
+// a pair image to its (window, source frame), every layer in between takes the count.  Host code only: kernels are reached
+// through launch.h.
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
@@ -321,7 +323,7 @@ int run_conv_layer_h3(davo_ctx* c, int li, const void* x, int x_ch, int Hin, int
         p.pose_P = P; p.pose_mt = mt;
         if (pose_out) {      // the launch's last workgroup adds the tiles and writes the poses (pose_tail.h)
             p.pose_counter = c->d_counters; p.pose_bias = c->d_bpred; p.pose_out = pose_out;
-            p.pose_NB = NB; p.pose_bm = ts.bm; p.pose_total = L.groups * mt * ntn;
+            p.pose_NB = NB; p.pose_bm = ts.bm; p.pose_total = L.groups * mt * ntn; p.pose_sel = c->run_pairs;
         }
         if (pose_bm) *pose_bm = ts.bm;
         if (pose_mt) *pose_mt = mt;
@@ -502,7 +504,7 @@ int run_patch_layer(davo_ctx* c, int li, bool f32, const void* x, void* y, int N
         if (const char* e = tuning_env("DAVO_PDBG")) p.dbg = atoi(e);      // tuning build only
         if (li == 0) {
             p.img = static_cast<const uint8_t*>(in.img); p.flow = static_cast<const float*>(in.flow);
-            p.seg = static_cast<const float*>(in.seg); p.tab = c->d_tab; p.v = c->v;
+            p.seg = static_cast<const float*>(in.seg); p.tab = c->d_tab; p.v = c->v; p.sel = c->run_pairs;
         }
     }
     c->last_plan[li][0] = ((NB * p.Ho * p.Wo + 127) / 128) * 1000 + t.plan_id; c->last_plan[li][1] = 0; c->last_split[li] = 1;
@@ -556,7 +558,8 @@ int run_posenn_se(davo_ctx* c, bool h3, const void* x, int NB) {
 
 }  // namespace
 
-int forward_device(davo_ctx* c, int B, const Inputs& in, void* d_pose) {
+int forward_device(davo_ctx* c, int B, const Inputs& in, void* d_pose, int sel) {
+    if (sel != PAIRS_SRC0 && sel != PAIRS_SRC1 && sel != PAIRS_BOTH) return fail(c, DAVO_ERR_INVALID, "internal: pair selection %d", sel);
     if (B < 1 || B > c->max_batch) return fail(c, DAVO_ERR_INVALID, "batch %d outside [1,%d]", B, c->max_batch);
     if (!in.img || !in.flow || !in.seg || !d_pose) return fail(c, DAVO_ERR_INVALID, "null device pointer");
     if (needs_depth(c) && (!in.depth || ((uintptr_t)in.depth & 15)))
@@ -588,7 +591,8 @@ int forward_device(davo_ctx* c, int B, const Inputs& in, void* d_pose) {
     if (!h3 && c->impl == 0 && !c->packed_ready) { int rc = build_packed_weights(c); if (rc) return rc; }      // float32 kernels: packed at their first use
     unsigned* const range_reset = (h3 && c->range_zero) ? c->d_range : nullptr;
 
-    const int H = c->H, W = c->W, HW = H * W, NB = 2 * B;
+    const int H = c->H, W = c->W, HW = H * W, NB = pairs_per_window(sel) * B;
+    c->run_pairs = sel;
     const Variant& v = c->v;
     hipStream_t s = c->stream;
     const uint8_t* const d_img = static_cast<const uint8_t*>(in.img);
@@ -614,27 +618,27 @@ int forward_device(davo_ctx* c, int B, const Inputs& in, void* d_pose) {
         // depth sources: one float32 sum per depth plane and chunk, then (or, folded, in the same launch) the excitation
         ProfScope ps(c, "se_depth_squeeze");
         HIP_TRY(c, launch_se_depth_squeeze(fold_excite, static_cast<const float*>(in.depth), B, HW, v, reinterpret_cast<unsigned*>(c->d_partial),
-                                           c->d_counters + 1, se_w1, se_b1, se_w2, se_b2, c->d_tab, range_reset, s));
+                                           c->d_counters + 1, se_w1, se_b1, se_w2, se_b2, c->d_tab, range_reset, sel, s));
     } else if (class_table) {
         // segmentation / rgb / seg+flow sources: per-frame histogram, byte or flow sums, then (or, folded, in the same launch) the
         // excitation
         ProfScope ps(c, "se_class_squeeze");
         HIP_TRY(c, launch_se_class_squeeze(fold_excite, d_img, d_flow, d_seg, B, H, W, v, reinterpret_cast<unsigned*>(c->d_partial),
-                                           c->d_counters + 1, se_w1, se_b1, se_w2, se_b2, c->d_tab, range_reset, s));
+                                           c->d_counters + 1, se_w1, se_b1, se_w2, se_b2, c->d_tab, range_reset, sel, s));
     } else if (fold_excite) {
         // squeeze + excitation in one launch: the workgroup that delivers a triplet's last partial sum evaluates its tables
         ProfScope ps(c, "se_squeeze_partial");
         HIP_TRY(c, launch_se_squeeze_excite(d_flow, B, HW, v, c->d_partial, c->d_counters + 1,
                                             se_w1, se_b1, se_w2, se_b2,
-                                            wdev("pose_exp_net/pose_exp_net/seg_channel_weight/weight"), c->d_tab, range_reset, s));
+                                            wdev("pose_exp_net/pose_exp_net/seg_channel_weight/weight"), c->d_tab, range_reset, sel, s));
     } else if (v.att_source == 1) {
         ProfScope ps(c, "se_squeeze_partial");
-        HIP_TRY(c, launch_se_squeeze(d_flow, B, HW, v, c->d_partial, s));
+        HIP_TRY(c, launch_se_squeeze(d_flow, B, HW, v, c->d_partial, sel, s));
     }
     if (!fold_excite) {
         ProfScope ps(c, "se_excite");
         HIP_TRY(c, launch_se_excite(c->d_partial, B, HW, v, se_w1, se_b1, se_w2, se_b2,
-                                    wdev("pose_exp_net/pose_exp_net/seg_channel_weight/weight"), c->d_tab, range_reset, s));
+                                    wdev("pose_exp_net/pose_exp_net/seg_channel_weight/weight"), c->d_tab, range_reset, sel, s));
     }
     // f16x3, fuse_pack: cnv1 builds its input patch straight from the raw inputs (mask + pack fused in,
     // the packed tensor never touches HBM).  Measured equal in time to mask_pack + cnv1 (the fused fill is bound
@@ -649,7 +653,7 @@ int forward_device(davo_ctx* c, int B, const Inputs& in, void* d_pose) {
     c->packed_ld = c->impl == 0 ? 8 : 10;
     if (!fused) {
         ProfScope ps(c, "mask_pack");
-        HIP_TRY(c, launch_mask_pack(h3 ? 16 : (c->impl == 0 ? 8 : 10), d_img, d_flow, d_seg, c->d_tab, v, B, H, W, c->d_packed, s));
+        HIP_TRY(c, launch_mask_pack(h3 ? 16 : (c->impl == 0 ? 8 : 10), d_img, d_flow, d_seg, c->d_tab, v, B, H, W, c->d_packed, sel, s));
     }
     const int c6 = v.cnv6_out;
     float** a = c->d_act;
@@ -719,15 +723,16 @@ int forward_device(davo_ctx* c, int B, const Inputs& in, void* d_pose) {
         ProfScope ps(c, "pose_head");
         if (pose_fused) {
             HIP_TRY(c, launch_pose_from_tiles(c->d_pose_tiles + (size_t)slot_idx(c) * c->pose_tiles_floats, NB, c->H3 * c->W3, pose_bm,
-                                              pose_mt, pose_ntn, c->d_bpred, static_cast<float*>(d_pose), h3 ? c->snap : SnapArgs{}, s));
+                                              pose_mt, pose_ntn, c->d_bpred, static_cast<float*>(d_pose), h3 ? c->snap : SnapArgs{}, sel, s));
             snap_done = true;
         } else {
-            HIP_TRY(c, launch_pose_head(a[6], NB, c->H3 * c->W3, c->d_wpred, c->d_bpred, c->d_pose_partial, static_cast<float*>(d_pose), s));
+            HIP_TRY(c, launch_pose_head(a[6], NB, c->H3 * c->W3, c->d_wpred, c->d_bpred, c->d_pose_partial, static_cast<float*>(d_pose), sel, s));
         }
     }
     // the range guard's conditional copy of this batch's inputs (api.hip: tickets) rides in pose_from_tiles; other pose heads get a launch
     if (h3 && c->snap.record && !snap_done) HIP_TRY(c, launch_range_guard_snapshot(c->snap, s));
     c->last_B = B;
+    c->last_pairs = sel;
     c->last_precision = h3 ? 1 : 0;
     return DAVO_OK;
 }

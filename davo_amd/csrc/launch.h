@@ -42,40 +42,40 @@ hipError_t launch_layer_h3w64(int layer, const ConvParamsH& p, hipStream_t s);  
 hipError_t launch_h3_generic(int KS, int stride, int tile, const ConvParamsH& p, dim3 grid, hipStream_t s);
 
 // ---- launch_misc.hip: prologue, pose head, cnv1 patch kernel, direct convolution ---------------------
-hipError_t launch_se_squeeze(const float* d_flow, int B, int HW, const Variant& v, float* d_partial, hipStream_t s);
+hipError_t launch_se_squeeze(const float* d_flow, int B, int HW, const Variant& v, float* d_partial, int sel, hipStream_t s);
 hipError_t launch_se_excite(const float* d_partial, int B, int HW, const Variant& v, const float* w1, const float* b1,
-                            const float* w2, const float* b2, const float* wstatic, float* d_tab, unsigned* d_range_reset, hipStream_t s);
+                            const float* w2, const float* b2, const float* wstatic, float* d_tab, unsigned* d_range_reset, int sel, hipStream_t s);
 // squeeze + excitation in one launch: the last workgroup of each triplet evaluates its tables (prologue.h, pose_tail.h);
 // -> 1 if the parts (x, 0..3) of a 64 x 4 grid ran on one XCD each for every x (what the folded split-K fix-up relies on), 0 if not
 hipError_t xcd_round_robin_probe(hipStream_t s, int* ok);
 // d_counters: one zeroed unsigned per triplet, left at zero
 hipError_t launch_se_squeeze_excite(const float* d_flow, int B, int HW, const Variant& v, float* d_partial, unsigned* d_counters,
                                     const float* w1, const float* b1, const float* w2, const float* b2, const float* wstatic,
-                                    float* d_tab, unsigned* d_range_reset, hipStream_t s);
+                                    float* d_tab, unsigned* d_range_reset, int sel, hipStream_t s);
 // segmentation / rgb / seg+flow class-table sources (att_source 4..10): per-frame descriptor records into d_partial (max_batch x 3 x SQ_CHUNKS x SQ_REC words);
 // fold: the triplet's last workgroup evaluates its tables too (d_counters as above), otherwise launch_se_excite follows
 hipError_t launch_se_class_squeeze(bool fold, const uint8_t* d_img, const float* d_flow, const float* d_seg, int B, int H, int W,
                                   const Variant& v, unsigned* d_partial, unsigned* d_counters, const float* w1, const float* b1,
-                                  const float* w2, const float* b2, float* d_tab, unsigned* d_range_reset, hipStream_t s);
+                                  const float* w2, const float* b2, float* d_tab, unsigned* d_range_reset, int sel, hipStream_t s);
 // depth sources (att_source 11, 12): one float32 sum per (triplet, frame, chunk) into word 0 of the same records; d_depth is
 // [B][3][H][W] float32 in file order (src0, tgt, src1), 16-byte aligned; fold as above
 hipError_t launch_se_depth_squeeze(bool fold, const float* d_depth, int B, int HW, const Variant& v, unsigned* d_partial,
                                    unsigned* d_counters, const float* w1, const float* b1, const float* w2, const float* b2,
-                                   float* d_tab, unsigned* d_range_reset, hipStream_t s);
+                                   float* d_tab, unsigned* d_range_reset, int sel, hipStream_t s);
 // ld: 16 = split-fp16 8-channel layout (f16x3), 8 = float32 8-channel, 10 = the reference's 10-channel layout
 hipError_t launch_mask_pack(int ld, const uint8_t* d_img, const float* d_flow, const float* d_seg, const float* d_tab,
-                            const Variant& v, int B, int H, int W, float* d_packed, hipStream_t s);
+                            const Variant& v, int B, int H, int W, float* d_packed, int sel, hipStream_t s);
 // cnv1 / cnv2 / cnv3 (layer 0..2) from an LDS-staged input patch: conv_patch_cnvN_h3, or conv_patch_cnvN_f32 in float32 mode (f32);
 // fused: conv_patch_cnv1_h3<true> (f16x3 cnv1 only)
 hipError_t launch_patch_layer(int layer, bool f32, bool fused, const ConvPatchParams& p, int nblk, hipStream_t s);
 // split-K fix-up: d_part [M][S][N] float32 partial sums -> the layer's stored activation (ReLU, fp16 hi/lo pairs, range monitor)
 hipError_t launch_splitk_fixup(const float* d_part, long M, int N, int S, int relu, uint8_t* d_y, unsigned* d_range, hipStream_t s);
 hipError_t launch_pose_from_tiles(const float* d_tiles, int NB, int P, int bm, int mtiles, int ntiles_n,
-                                  const float* d_bpred, float* d_pose, const SnapArgs& snap, hipStream_t s);
+                                  const float* d_bpred, float* d_pose, const SnapArgs& snap, int sel, hipStream_t s);
 // the range guard's conditional copy of the batch's inputs as a launch of its own (prologue.h)
 hipError_t launch_range_guard_snapshot(const SnapArgs& snap, hipStream_t s);
 hipError_t launch_pose_head(const float* d_c7, int NB, int P, const float* d_wpred, const float* d_bpred,
-                            float* d_partial, float* d_pose, hipStream_t s);
+                            float* d_partial, float* d_pose, int sel, hipStream_t s);
 hipError_t launch_conv_direct(const float* x, int N, int Hin, int Win, int cin, int x_ld, int x_coff, const float* w, int KS,
                               int cout, const float* bias, int stride, int rate, int pt, int pl, int Ho, int Wo, int relu,
                               float* y, int y_ld, int y_coff, hipStream_t s);

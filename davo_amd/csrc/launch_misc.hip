@@ -26,59 +26,59 @@ hipError_t ensure_dynamic_lds(const void* kernel, int bytes) {
     return e;
 }
 
-hipError_t launch_se_squeeze(const float* d_flow, int B, int HW, const Variant& v, float* d_partial, hipStream_t s) {
-    hipLaunchKernelGGL(se_squeeze_partial, dim3(SQ_CHUNKS, 2, B), dim3(256), 0, s, d_flow, HW, v.norm_flow, v.abs_mode, d_partial);
+hipError_t launch_se_squeeze(const float* d_flow, int B, int HW, const Variant& v, float* d_partial, int sel, hipStream_t s) {
+    hipLaunchKernelGGL(se_squeeze_partial, dim3(SQ_CHUNKS, pairs_per_window(sel), B), dim3(256), 0, s, d_flow, HW, v.norm_flow, v.abs_mode, sel, d_partial);
     return hipGetLastError();
 }
 
 hipError_t launch_se_excite(const float* d_partial, int B, int HW, const Variant& v, const float* w1, const float* b1,
-                            const float* w2, const float* b2, const float* wstatic, float* d_tab, unsigned* d_range_reset, hipStream_t s) {
-    hipLaunchKernelGGL(se_excite, dim3(B, 3), dim3(64), 0, s, d_partial, HW, v, w1, b1, w2, b2, wstatic, d_tab, d_range_reset);
+                            const float* w2, const float* b2, const float* wstatic, float* d_tab, unsigned* d_range_reset, int sel, hipStream_t s) {
+    hipLaunchKernelGGL(se_excite, dim3(B, 3), dim3(64), 0, s, d_partial, HW, v, w1, b1, w2, b2, wstatic, d_tab, d_range_reset, sel);
     return hipGetLastError();
 }
 
 hipError_t launch_se_squeeze_excite(const float* d_flow, int B, int HW, const Variant& v, float* d_partial, unsigned* d_counters,
                                     const float* w1, const float* b1, const float* w2, const float* b2, const float* wstatic,
-                                    float* d_tab, unsigned* d_range_reset, hipStream_t s) {
-    hipLaunchKernelGGL(se_squeeze_excite, dim3(SQ_CHUNKS, 2, B), dim3(256), 0, s, d_flow, HW, v, d_partial, d_counters, w1, b1, w2, b2,
-                       wstatic, d_tab, d_range_reset);
+                                    float* d_tab, unsigned* d_range_reset, int sel, hipStream_t s) {
+    hipLaunchKernelGGL(se_squeeze_excite, dim3(SQ_CHUNKS, pairs_per_window(sel), B), dim3(256), 0, s, d_flow, HW, v, d_partial, d_counters, w1, b1, w2, b2,
+                       wstatic, d_tab, d_range_reset, sel);
     return hipGetLastError();
 }
 
 hipError_t launch_se_class_squeeze(bool fold, const uint8_t* d_img, const float* d_flow, const float* d_seg, int B, int H, int W,
                                   const Variant& v, unsigned* d_partial, unsigned* d_counters, const float* w1, const float* b1,
-                                  const float* w2, const float* b2, float* d_tab, unsigned* d_range_reset, hipStream_t s) {
-    const dim3 grid(SQ_CHUNKS, att_se_frames(v.att_source), B);
+                                  const float* w2, const float* b2, float* d_tab, unsigned* d_range_reset, int sel, hipStream_t s) {
+    const dim3 grid(SQ_CHUNKS, att_se_frames(v.att_source) - (sel == PAIRS_BOTH ? 0 : 1), B);
     if (fold)
         hipLaunchKernelGGL(se_class_squeeze<true>, grid, dim3(256), 0, s, d_img, d_flow, d_seg, H, W, v, d_partial, d_counters,
-                           w1, b1, w2, b2, d_tab, d_range_reset);
+                           w1, b1, w2, b2, d_tab, d_range_reset, sel);
     else
         hipLaunchKernelGGL(se_class_squeeze<false>, grid, dim3(256), 0, s, d_img, d_flow, d_seg, H, W, v, d_partial, d_counters,
-                           w1, b1, w2, b2, d_tab, d_range_reset);
+                           w1, b1, w2, b2, d_tab, d_range_reset, sel);
     return hipGetLastError();
 }
 
 hipError_t launch_se_depth_squeeze(bool fold, const float* d_depth, int B, int HW, const Variant& v, unsigned* d_partial,
                                    unsigned* d_counters, const float* w1, const float* b1, const float* w2, const float* b2,
-                                   float* d_tab, unsigned* d_range_reset, hipStream_t s) {
+                                   float* d_tab, unsigned* d_range_reset, int sel, hipStream_t s) {
     if (!att_desc_depth(v.att_source) || !d_depth || HW % 16) return hipErrorInvalidValue;
-    const dim3 grid(SQ_CHUNKS, 3, B);
+    const dim3 grid(SQ_CHUNKS, 1 + pairs_per_window(sel), B);
     if (fold)
         hipLaunchKernelGGL(se_depth_squeeze<true>, grid, dim3(256), 0, s, d_depth, HW, v, d_partial, d_counters, w1, b1, w2, b2, d_tab,
-                           d_range_reset);
+                           d_range_reset, sel);
     else
         hipLaunchKernelGGL(se_depth_squeeze<false>, grid, dim3(256), 0, s, d_depth, HW, v, d_partial, d_counters, w1, b1, w2, b2, d_tab,
-                           d_range_reset);
+                           d_range_reset, sel);
     return hipGetLastError();
 }
 
 hipError_t launch_mask_pack(int ld, const uint8_t* d_img, const float* d_flow, const float* d_seg, const float* d_tab,
-                            const Variant& v, int B, int H, int W, float* d_packed, hipStream_t s) {
-    const long nthreads = (long)2 * B * H * (W / 4);
+                            const Variant& v, int B, int H, int W, float* d_packed, int sel, hipStream_t s) {
+    const long nthreads = (long)pairs_per_window(sel) * B * H * (W / 4);
     const dim3 grid((unsigned)((nthreads + 255) / 256));
-    if (ld == 16) hipLaunchKernelGGL(mask_pack<16>, grid, dim3(256), 0, s, d_img, d_flow, d_seg, d_tab, v, B, H, W, d_packed);
-    else if (ld == 8) hipLaunchKernelGGL(mask_pack<8>, grid, dim3(256), 0, s, d_img, d_flow, d_seg, d_tab, v, B, H, W, d_packed);
-    else if (ld == 10) hipLaunchKernelGGL(mask_pack<10>, grid, dim3(256), 0, s, d_img, d_flow, d_seg, d_tab, v, B, H, W, d_packed);
+    if (ld == 16) hipLaunchKernelGGL(mask_pack<16>, grid, dim3(256), 0, s, d_img, d_flow, d_seg, d_tab, v, B, sel, H, W, d_packed);
+    else if (ld == 8) hipLaunchKernelGGL(mask_pack<8>, grid, dim3(256), 0, s, d_img, d_flow, d_seg, d_tab, v, B, sel, H, W, d_packed);
+    else if (ld == 10) hipLaunchKernelGGL(mask_pack<10>, grid, dim3(256), 0, s, d_img, d_flow, d_seg, d_tab, v, B, sel, H, W, d_packed);
     else return hipErrorInvalidValue;
     return hipGetLastError();
 }
@@ -132,8 +132,8 @@ hipError_t launch_splitk_fixup(const float* d_part, long M, int N, int S, int re
 }
 
 hipError_t launch_pose_from_tiles(const float* d_tiles, int NB, int P, int bm, int mtiles, int ntiles_n,
-                                  const float* d_bpred, float* d_pose, const SnapArgs& snap, hipStream_t s) {
-    hipLaunchKernelGGL(pose_from_tiles, dim3(NB * 6), dim3(64), 0, s, d_tiles, NB, P, bm, mtiles, ntiles_n, d_bpred, d_pose, snap);
+                                  const float* d_bpred, float* d_pose, const SnapArgs& snap, int sel, hipStream_t s) {
+    hipLaunchKernelGGL(pose_from_tiles, dim3(NB * 6), dim3(64), 0, s, d_tiles, NB, P, bm, mtiles, ntiles_n, d_bpred, d_pose, sel, snap);
     return hipGetLastError();
 }
 
@@ -143,11 +143,11 @@ hipError_t launch_range_guard_snapshot(const SnapArgs& snap, hipStream_t s) {
 }
 
 hipError_t launch_pose_head(const float* d_c7, int NB, int P, const float* d_wpred, const float* d_bpred,
-                            float* d_partial, float* d_pose, hipStream_t s) {
+                            float* d_partial, float* d_pose, int sel, hipStream_t s) {
     hipLaunchKernelGGL(pose_head_partial, dim3(PH_SPLIT, NB, 2), dim3(256), 0, s, d_c7, P, d_wpred, d_partial);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(pose_finish, dim3((NB * 6 + 63) / 64), dim3(64), 0, s, d_partial, NB, P, d_bpred, d_pose);
+    hipLaunchKernelGGL(pose_finish, dim3((NB * 6 + 63) / 64), dim3(64), 0, s, d_partial, NB, P, d_bpred, d_pose, sel);
     return hipGetLastError();
 }
 

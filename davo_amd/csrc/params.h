@@ -48,6 +48,19 @@ __host__ __device__ inline int att_se_hidden(int a) { return (a == 4 || a == 7 |
 // every plane once, the target's included: its sum enters both source frames' descriptors (davo.py:1109)
 __host__ __device__ inline int att_se_frames(int a) { return (att_tgt_attended(a) || att_desc_depth(a)) ? 3 : 2; }
 
+// ---- pair selection (davo_set_pairs, include/davo_hip.h) -------------------------------------------------------------------
+// A window's two poses come from two independent evaluations of the PoseNN (davo.py:1456-1457): pair 0 = (tgt, src0), pair 1 =
+// (tgt, src1).  sel 3 runs both: pair image n is pair n & 1 of window n >> 1.  sel 1 / 2 runs pair 0 / 1 alone: pair image n is
+// window n's selected pair, and nothing of the other source frame is read.  The poses keep their [B][2][6] layout in every case.
+constexpr int PAIRS_SRC0 = 1, PAIRS_SRC1 = 2, PAIRS_BOTH = 3;
+__host__ __device__ inline int pairs_per_window(int sel) { return sel == PAIRS_BOTH ? 2 : 1; }
+__host__ __device__ inline int pair_window(int n, int sel) { return sel == PAIRS_BOTH ? n >> 1 : n; }
+__host__ __device__ inline int pair_source(int n, int sel) { return sel == PAIRS_BOTH ? n & 1 : sel >> 1; }
+// pose row of pair image n in [B][2][6]; with one pair selected the window's other row is written as +0.0 by the same thread
+__host__ __device__ inline int pair_pose_row(int n, int sel) { return 2 * pair_window(n, sel) + pair_source(n, sel); }
+// does a launch over the frames (0 tgt, 1 src0, 2 src1) have work for `frame'?
+__host__ __device__ inline bool pair_reads_frame(int frame, int sel) { return frame == 0 || ((sel >> (frame - 1)) & 1); }
+
 // ---- filter rows that only see padding ------------------------------------------------------
 // 3x3 layers: the filter rows ky that land inside the image for at least one output pixel of the flattened pixel range
 // [m0, m1] are [ky0, ky0 + nky); a range that crosses an image boundary keeps all three.  A tile whose pixels all sit in
@@ -173,8 +186,9 @@ struct ConvParamsH {
     // partial sums in a fixed order and writes the poses; null pose_counter = a separate pose_from_tiles launch does it
     unsigned* pose_counter; // one counter per in-flight slot, zero between launches
     const float* pose_bias; // [groups][3] pred biases
-    float* pose_out;        // [NB][6]
+    float* pose_out;        // [B][2][6]: pair image n -> row pair_pose_row(n, pose_sel)
     int pose_NB, pose_bm, pose_total;   // pair images, tile height, workgroups of the launch
+    int pose_sel;           // pair selection of the batch (PAIRS_*)
     int dbg;                // measurement only (DAVO_DBG; results are wrong with any bit set): 1 DMA reads the zero line,
                             // 2 no matrix phase, 4 no wave-half stagger (32x32x16 form), 32 no epilogue, 64 stores fold onto 256 tiles
 };
@@ -290,6 +304,7 @@ struct ConvPatchParams {
     const float* seg;       // [B][3][H][W][1]
     const float* tab;       // [B][3][19] attention tables (se_excite)
     Variant v;
+    int sel;                // pair selection of the batch (PAIRS_*): pair image n -> (window, source frame)
     int dbg;                // measurement only (-DDAVO_TUNING, DAVO_PDBG): 1 = every patch load reads the zero line, 2 = no stores
 };
 

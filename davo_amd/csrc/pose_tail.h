@@ -40,6 +40,14 @@ __device__ __forceinline__ bool last_workgroup(unsigned* counter, unsigned total
     return *ticket_lds == total - 1;
 }
 
+// Component hk of pair image n's pose into the [B][2][6] array: the pair's own row, and - with one pair selected - exactly +0.0
+// ("zero motion") into the window's other row, so that the array is fully written whatever the selection.
+__device__ __forceinline__ void pose_store(float* __restrict__ pose, int n, int hk, int sel, float v) {
+    const int row = pair_pose_row(n, sel);
+    pose[row * 6 + hk] = v;
+    if (sel != PAIRS_BOTH) pose[(row ^ 1) * 6 + hk] = 0.f;
+}
+
 // One wave's sum over the per-tile partial sums that cover image n, head / component hk (partial[head][mtile][ntile][slot][k],
 // slot 0 = the tile's first image, 1 = the next one): entry j = (tile t0 + j / ntn, N tile j % ntn) goes to lane j % 64 (a
 // lane adds its entries in order), then a fixed butterfly over the lanes — the same bits whoever computes it (the
@@ -71,7 +79,7 @@ __device__ __forceinline__ void pose_from_tiles_tail(const ConvParamsH& p) {
     for (int i = wave; i < p.pose_NB * 6; i += THREADS / 64) {
         const int n = i / 6, hk = i - n * 6;
         const float tot = pose_tile_sum<true>(p.pose_partial, n, hk, p.pose_P, p.pose_bm, p.pose_mt, p.ntiles_n, lane);
-        if (lane == 0) p.pose_out[i] = 0.01f * (tot / (float)p.pose_P + p.pose_bias[hk]);
+        if (lane == 0) pose_store(p.pose_out, n, hk, p.pose_sel, 0.01f * (tot / (float)p.pose_P + p.pose_bias[hk]));
     }
     if (threadIdx.x == 0) __hip_atomic_store(p.pose_counter, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }

@@ -25,12 +25,12 @@ __device__ __forceinline__ float wave_sum(float v) {
 }
 
 // SE squeeze, pass 1: partial[b][s][chunk][2] = sum over the chunk's pixels of t(flow[b][s]).
-// grid (SQ_CHUNKS, 2, B), 256 threads; float4 = two pixels x (fx, fy).  Fixed chunking and a
-// fixed reduction tree -> bitwise reproducible run to run.
+// grid (SQ_CHUNKS, selected sources, B), 256 threads; float4 = two pixels x (fx, fy).  Fixed chunking and a
+// fixed reduction tree -> bitwise reproducible run to run.  With one pair selected (sel, params.h) only that source's plane is read.
 __global__ __launch_bounds__(256) void se_squeeze_partial(const float* __restrict__ flow, int HW,
-                                                          int norm_flow, int abs_mode,
+                                                          int norm_flow, int abs_mode, int sel,
                                                           float* __restrict__ partial) {
-    const int chunk = blockIdx.x, s = blockIdx.y, b = blockIdx.z;
+    const int chunk = blockIdx.x, s = pair_source(blockIdx.y, sel), b = blockIdx.z;
     const float4* f = reinterpret_cast<const float4*>(flow + ((size_t)b * 4 + s) * HW * 2);
     const int nvec = HW / 2;                                   // HW is a multiple of 16
     const int per = (nvec + SQ_CHUNKS - 1) / SQ_CHUNKS;
@@ -198,10 +198,11 @@ __global__ __launch_bounds__(64) void se_excite(const float* __restrict__ partia
                                                 const float* __restrict__ w1, const float* __restrict__ b1,
                                                 const float* __restrict__ w2, const float* __restrict__ b2,
                                                 const float* __restrict__ wstatic,
-                                                float* __restrict__ tab, unsigned* __restrict__ range_reset) {
+                                                float* __restrict__ tab, unsigned* __restrict__ range_reset, int sel) {
     // a ticketed device-path batch starts its own f16x3 range record (api.hip): first kernel of the forward, so in stream
     // order before any storing epilogue; a null pointer = the record is the caller's business
     if (range_reset && blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) range_reset[RANGE_SNAP] = 0u;   // the per-batch word (params.h)
+    if (!pair_reads_frame(blockIdx.y, sel)) return;           // an unselected source frame has no squeeze record and no reader of its table
     se_excite_wave<false>(partial, HW, v, blockIdx.x, blockIdx.y, threadIdx.x, w1, b1, w2, b2, wstatic, tab);
 }
 
@@ -213,9 +214,9 @@ __global__ __launch_bounds__(256) void se_squeeze_excite(const float* __restrict
                                                          const float* __restrict__ w1, const float* __restrict__ b1,
                                                          const float* __restrict__ w2, const float* __restrict__ b2,
                                                          const float* __restrict__ wstatic, float* __restrict__ tab,
-                                                         unsigned* __restrict__ range_reset) {
-    const int chunk = blockIdx.x, s = blockIdx.y, b = blockIdx.z;
-    if (range_reset && chunk == 0 && s == 0 && b == 0 && threadIdx.x == 0) range_reset[RANGE_SNAP] = 0u;      // as se_excite
+                                                         unsigned* __restrict__ range_reset, int sel) {
+    const int chunk = blockIdx.x, s = pair_source(blockIdx.y, sel), b = blockIdx.z;
+    if (range_reset && chunk == 0 && blockIdx.y == 0 && b == 0 && threadIdx.x == 0) range_reset[RANGE_SNAP] = 0u;      // as se_excite
     const float4* f = reinterpret_cast<const float4*>(flow + ((size_t)b * 4 + s) * HW * 2);
     const int nvec = HW / 2;                                   // HW is a multiple of 16
     const int per = (nvec + SQ_CHUNKS - 1) / SQ_CHUNKS;
@@ -245,8 +246,8 @@ __global__ __launch_bounds__(256) void se_squeeze_excite(const float* __restrict
         agent_store(o + 1, (red[1][0] + red[1][1]) + (red[1][2] + red[1][3]));
         agent_stores_done();
     }
-    if (!last_workgroup(counters + b, 2u * SQ_CHUNKS, &ticket)) return;
-    if (wid < 3) se_excite_wave<true>(partial, HW, v, b, wid, lane, w1, b1, w2, b2, wstatic, tab);
+    if (!last_workgroup(counters + b, (unsigned)(pairs_per_window(sel) * SQ_CHUNKS), &ticket)) return;
+    if (wid < 3 && pair_reads_frame(wid, sel)) se_excite_wave<true>(partial, HW, v, b, wid, lane, w1, b1, w2, b2, wstatic, tab);
     if (threadIdx.x == 0) __hip_atomic_store(counters + b, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
@@ -267,9 +268,11 @@ __global__ __launch_bounds__(256) void se_class_squeeze(const uint8_t* __restric
                                                         unsigned* __restrict__ partial, unsigned* __restrict__ counters,
                                                         const float* __restrict__ w1, const float* __restrict__ b1,
                                                         const float* __restrict__ w2, const float* __restrict__ b2,
-                                                        float* __restrict__ tab, unsigned* __restrict__ range_reset) {
+                                                        float* __restrict__ tab, unsigned* __restrict__ range_reset, int sel) {
     const int a = v.att_source, nf = att_se_frames(a);
-    const int chunk = blockIdx.x, frame = blockIdx.y + 3 - nf, b = blockIdx.z;
+    // one pair selected (params.h): grid y is nf - 1 - the target where the source covers it, then the selected source frame
+    const int chunk = blockIdx.x, b = blockIdx.z;
+    const int frame = sel == PAIRS_BOTH ? (int)blockIdx.y + 3 - nf : ((nf == 3 && blockIdx.y == 0) ? 0 : 1 + (sel >> 1));
     if (FOLD && range_reset && chunk == 0 && blockIdx.y == 0 && b == 0 && threadIdx.x == 0) range_reset[RANGE_SNAP] = 0u;   // as se_excite
     const int HW = H * W;
     const int nunits = HW >> 2;                                // 4-pixel units; W is a multiple of 4, so a unit never wraps a row
@@ -357,8 +360,8 @@ __global__ __launch_bounds__(256) void se_class_squeeze(const uint8_t* __restric
         if (FOLD) agent_stores_done();
     }
     if (!FOLD) return;
-    if (!last_workgroup(counters + b, (unsigned)(nf * SQ_CHUNKS), &ticket)) return;
-    if (wid < 3) se_class_excite_wave<true>(partial, HW, v, b, wid, lane, w1, b1, w2, b2, tab);
+    if (!last_workgroup(counters + b, (unsigned)((nf - (sel == PAIRS_BOTH ? 0 : 1)) * SQ_CHUNKS), &ticket)) return;
+    if (wid < 3 && pair_reads_frame(wid, sel)) se_class_excite_wave<true>(partial, HW, v, b, wid, lane, w1, b1, w2, b2, tab);
     if (threadIdx.x == 0) __hip_atomic_store(counters + b, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
@@ -375,8 +378,10 @@ __global__ __launch_bounds__(256) void se_depth_squeeze(const float* __restrict_
                                                         unsigned* __restrict__ partial, unsigned* __restrict__ counters,
                                                         const float* __restrict__ w1, const float* __restrict__ b1,
                                                         const float* __restrict__ w2, const float* __restrict__ b2,
-                                                        float* __restrict__ tab, unsigned* __restrict__ range_reset) {
-    const int chunk = blockIdx.x, frame = blockIdx.y, b = blockIdx.z;
+                                                        float* __restrict__ tab, unsigned* __restrict__ range_reset, int sel) {
+    // one pair selected (params.h): grid y is 2 - the target, whose sum enters every descriptor, and the selected source frame
+    const int chunk = blockIdx.x, b = blockIdx.z;
+    const int frame = (sel == PAIRS_BOTH || blockIdx.y == 0) ? (int)blockIdx.y : 1 + (sel >> 1);
     if (FOLD && range_reset && chunk == 0 && frame == 0 && b == 0 && threadIdx.x == 0) range_reset[RANGE_SNAP] = 0u;   // as se_excite
     const int plane = frame == 0 ? 1 : frame == 1 ? 0 : 2;     // (tgt, src0, src1) -> file order src0, tgt, src1 (davo.py:991-996)
     const float4* dp = reinterpret_cast<const float4*>(depth + ((size_t)b * 3 + plane) * HW);
@@ -405,8 +410,8 @@ __global__ __launch_bounds__(256) void se_depth_squeeze(const float* __restrict_
         }
     }
     if (!FOLD) return;
-    if (!last_workgroup(counters + b, 3u * SQ_CHUNKS, &ticket)) return;
-    if (wid < 3) se_class_excite_wave<true>(partial, HW, v, b, wid, lane, w1, b1, w2, b2, tab);
+    if (!last_workgroup(counters + b, (unsigned)((1 + pairs_per_window(sel)) * SQ_CHUNKS), &ticket)) return;
+    if (wid < 3 && pair_reads_frame(wid, sel)) se_class_excite_wave<true>(partial, HW, v, b, wid, lane, w1, b1, w2, b2, tab);
     if (threadIdx.x == 0) __hip_atomic_store(counters + b, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
@@ -422,16 +427,17 @@ __device__ __forceinline__ float u8_to_unit(uint32_t byte) {
 }
 
 // Mask + pack: one thread per 4 horizontally adjacent pixels of one pair image.
-// out[(b*2+s)][y][x][0..LD): LD = 8 : tgt rgb | src rgb*att | flow*att      (product layout; the
+// out[n][y][x][0..LD), n = the pair image of (window b, source s) under the batch's pair selection (params.h):
+//                            LD = 8 : tgt rgb | src rgb*att | flow*att      (product layout; the
 //                                      two identically-zero tgt-flow channels are dropped)
 //                            LD = 10: tgt rgb | 0 0 | src rgb*att | flow*att (reference layout)
 // v0 variants (rgb only) leave the flow slots zero.
 template <int LD>
 __global__ __launch_bounds__(256) void mask_pack(const uint8_t* __restrict__ img, const float* __restrict__ flow,
                                                  const float* __restrict__ seg, const float* __restrict__ tab,
-                                                 Variant v, int B, int H, int W, float* __restrict__ out) {
+                                                 Variant v, int B, int sel, int H, int W, float* __restrict__ out) {
     const int W4 = W >> 2;
-    const long total = (long)B * 2 * H * W4;
+    const long total = (long)B * pairs_per_window(sel) * H * W4;
     const long gid_raw = (long)blockIdx.x * 256 + threadIdx.x;
     const bool valid = gid_raw < total;
     constexpr bool STAGED = LD == 16 || LD == 8;               // 32 B per pixel: the stores leave through LDS (below)
@@ -440,7 +446,7 @@ __global__ __launch_bounds__(256) void mask_pack(const uint8_t* __restrict__ img
     const int x4 = (int)(gid % W4);
     long t = gid / W4;
     const int y = (int)(t % H); t /= H;
-    const int s = (int)(t & 1), b = (int)(t >> 1);
+    const int n = (int)t, s = pair_source(n, sel), b = pair_window(n, sel);
     const int x = x4 * 4;
 
     const uint8_t* row = img + ((size_t)b * H + y) * (size_t)(9 * W);
@@ -480,7 +486,7 @@ __global__ __launch_bounds__(256) void mask_pack(const uint8_t* __restrict__ img
         fl[4] = f1.x; fl[5] = f1.y; fl[6] = f1.z; fl[7] = f1.w;
     }
     constexpr int OUT_FLOATS = LD == 16 ? 8 : LD;          // LD 16 = split-fp16 layout, 8 floats' worth per pixel
-    float* o = out + (((size_t)(b * 2 + s) * H + y) * W + x) * OUT_FLOATS;
+    float* o = out + (((size_t)n * H + y) * W + x) * OUT_FLOATS;
     // LD 16 / 8: a thread's 4 pixels are 8 x 16 B, 128 B apart from its neighbour's - stored directly, every store
     // instruction would touch 64 separate lines.  The workgroup's 32 KB (contiguous: output offset = gid * 128 B)
     // go through LDS instead and leave as 1 KiB per wave instruction.  Unit t*8 + (k ^ (t&7)): 2-way bank conflicts
@@ -573,7 +579,7 @@ __global__ __launch_bounds__(256) void pose_head_partial(const float* __restrict
 
 __global__ __launch_bounds__(64) void pose_finish(const float* __restrict__ partial, int NB, int P,
                                                   const float* __restrict__ bpred /*[2][3]*/,
-                                                  float* __restrict__ pose /*[2B][6]*/) {
+                                                  float* __restrict__ pose /*[B][2][6]*/, int sel) {
     const int i = blockIdx.x * 64 + threadIdx.x;           // (n, head, j)
     if (i >= NB * 6) return;
     const int n = i / 6, hj = i - n * 6, head = hj / 3, j = hj - head * 3;
@@ -581,7 +587,7 @@ __global__ __launch_bounds__(64) void pose_finish(const float* __restrict__ part
     float tot = 0.f;
 #pragma unroll
     for (int s = 0; s < PH_SPLIT; ++s) tot += pp[s * 3];
-    pose[i] = 0.01f * (tot / (float)P + bpred[hj]);
+    pose_store(pose, n, hj, sel, 0.01f * (tot / (float)P + bpred[hj]));
 }
 
 // Pose from the per-tile partial sums cnv7's fused epilogue wrote (conv_igemm_h3.h, y_mode 2):
@@ -653,12 +659,12 @@ __device__ __forceinline__ void snapshot_inputs_if_range_fails(const SnapArgs& a
 
 __global__ __launch_bounds__(64) void pose_from_tiles(const float* __restrict__ partial, int NB, int P, int bm,
                                                       int mtiles, int ntiles_n, const float* __restrict__ bpred,
-                                                      float* __restrict__ pose /*[2B][6]*/, SnapArgs snap) {
+                                                      float* __restrict__ pose /*[B][2][6]*/, int sel, SnapArgs snap) {
     const int i = blockIdx.x;                              // (n, head, k)
     const int n = i / 6, hk = i - n * 6;
     const RangePeek peek = range_peek(snap, blockIdx.x * 64 + threadIdx.x);
     const float tot = pose_tile_sum<false>(partial, n, hk, P, bm, mtiles, ntiles_n, threadIdx.x);
-    if (threadIdx.x == 0) pose[i] = 0.01f * (tot / (float)P + bpred[hk]);
+    if (threadIdx.x == 0) pose_store(pose, n, hk, sel, 0.01f * (tot / (float)P + bpred[hk]));
     snapshot_inputs_if_range_fails(snap, peek, blockIdx.x * 64 + threadIdx.x, gridDim.x * 64);
 }
 

@@ -294,6 +294,25 @@ class Engine:
         """Batches kept in flight by forward_device (1..4): n streams + n workspaces, rotated per call."""
         self._check(self._L.davo_set_inflight(self._ctx, int(n)))
 
+    PAIRS = {"src0": 1, "src1": 2, "both": 3}
+
+    def set_pairs(self, pairs):
+        """Which of a window's two pairs the batches issued from now on run (include/davo_hip.h: davo_set_pairs): 'both'
+        (default), 'src0' (tgt->src0 only) or 'src1' (tgt->src1 only - all that a trajectory needs of every window but a
+        sequence's first, test_kitti_pose.py:143-145).  Outputs stay [B,2,6]; the row that was not selected is exactly zero.
+        Batches in flight, and their range-recovery re-issues, keep the selection they were issued with."""
+        if pairs not in self.PAIRS:
+            raise ValueError("pairs must be 'both', 'src0' or 'src1', got %r" % (pairs,))
+        self._check(self._L.davo_set_pairs(self._ctx, self.PAIRS[pairs]))
+
+    @property
+    def pairs(self):
+        v = self._L.davo_get_pairs(self._ctx)
+        for name, code in self.PAIRS.items():
+            if code == v:
+                return name
+        raise DavoError("davo_get_pairs returned %d" % v)
+
     def set_impl(self, impl):
         self._check(self._L.davo_set_impl(self._ctx, {"mfma": 0, "direct": 1}.get(impl, impl)))
 

@@ -90,7 +90,7 @@ def sequences_to_run(a):
     return list(zip(seqs, counts)), synthetic
 
 
-def main(argv=None):
+def build_parser():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch_size", type=int, default=1)          # test_kitti_pose.py:21
     ap.add_argument("--img_height", type=int, default=128)
@@ -127,6 +127,15 @@ def main(argv=None):
     ap.add_argument("--sync_driver", action="store_true",
                     help="one synchronous davo_forward per batch (input wait + copy + kernels + pose copy add up) instead of the streaming "
                          "entry point (davo_submit: three batches in flight (four up to batch 2), copies and input wait overlapped with the kernels)")
+    ap.add_argument("--pairs", choices=S.PAIRS_MODES, default="both",
+                    help="both: every window runs tgt->src0 and tgt->src1, as the reference does.  trajectory: only what the trajectory "
+                         "reads (test_kitti_pose.py:143-145) - both pairs for the batch that holds a sequence's window 0, tgt->src1 alone "
+                         "for every other batch: half the arithmetic and 55 %% of the input bytes; the written file is the same")
+    return ap
+
+
+def main(argv=None):
+    ap = build_parser()
     a = ap.parse_args(argv)
     # start-up split (wall clock).  Only the first main() of a process can say what the process start cost
     global _FIRST_MAIN
@@ -242,7 +251,10 @@ def main(argv=None):
         mark("inputs_and_weights_ready")
         system.load_weights(weights)
         mark("weights_on_gpu")
-        infer = lambda *parts: system.inference(None, "pose", inputs=parts)["pose"]   # noqa: E731  (img, flow, seg[, depth])
+        def infer(*parts, pairs=None):                 # (img, flow, seg[, depth]); pairs: the batch's selection under --pairs trajectory
+            if pairs is not None and pairs != system.engine.pairs:
+                system.engine.set_pairs(pairs)
+            return system.inference(None, "pose", inputs=parts)["pose"]
         if loader_thread is not None:
             loader_thread.join()
             loader_thread = None
@@ -292,7 +304,7 @@ def main(argv=None):
 
         entries = []
         for seq, traj, poses, timing in S.run_sequences(infer, sequences, source, a.batch_size, rank, world, comm, emulate, stream,
-                                                        before_sequence):
+                                                        before_sequence, a.pairs):
             dt = time.perf_counter() - clock["t0"]
             if rank != 0:
                 continue
@@ -329,6 +341,8 @@ def main(argv=None):
                             note="rank 0's seconds; load_wait_s = time the GPU side waited for the input pipeline, forward_s = H2D + kernels + "
                                  "pose D2H inside DAVO.inference (streamed: the time inside davo_submit), gather_s = the RCCL all-gather incl. staging and the "
                                  "wait for the communicator, which is built on a second thread from the moment the GPU context exists")
+            if a.pairs != "both":          # the default run's report is the one it has always been
+                run_wide["pairs"] = a.pairs
             if len(entries) == 1:          # one sequence: the report it has always had
                 report = {k: v for k, v in entries[0].items() if k not in ("seq", "wall_s")}
                 report.update(run_wide)

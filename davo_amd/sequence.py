@@ -152,14 +152,34 @@ class PoseStream:
             inflight = 4 if engine.max_batch <= 2 else 3
         engine.set_inflight(inflight)
 
-    def submit(self, img, flow, seg, out, depth=None):
+    def submit(self, img, flow, seg, out, depth=None, pairs=None):
+        """``pairs`` ('both' | 'src0' | 'src1'; None = leave the engine's selection alone): the pairs this batch runs.  The switch
+        goes through davo_set_pairs ahead of the submit, so by the ABI's ordering it applies to this batch and the later ones;
+        the batches already in flight keep theirs."""
+        if pairs is not None and pairs != self.engine.pairs:
+            self.engine.set_pairs(pairs)
         self.engine.submit(img, flow, seg, out, self.hold, depth=depth)
 
     def drain(self):
         self.engine.synchronize()
 
 
-def run_shard(infer_fn, load_windows, lo, hi, batch_size, timing=None, stream=None):
+PAIRS_MODES = ("both", "trajectory")
+
+
+def batch_pairs(mode, s):
+    """The pair selection of the batch that starts at window ``s`` of its sequence.  'trajectory': stitch_trajectory reads
+    row 0 of window 0 and row 1 of every window (test_kitti_pose.py:143-145), so the batch that contains window 0 - the first
+    batch of the rank that owns it - runs both pairs and every other batch of every rank runs tgt->src1 alone; no batch
+    boundary moves.  'both' -> None: the calls are made as they always were."""
+    if mode not in PAIRS_MODES:
+        raise ValueError("pairs must be one of %s, got %r" % (", ".join(PAIRS_MODES), mode))
+    if mode == "both":
+        return None
+    return "both" if s == 0 else "src1"
+
+
+def run_shard(infer_fn, load_windows, lo, hi, batch_size, timing=None, stream=None, pairs="both"):
     """Run windows [lo,hi) in batches; the last batch is padded by repeating its last window
     and the padded outputs are dropped (the reference's complete_batch_size,
     utils/common_utils.py:8-13, would append duplicate poses for B>1; parity is defined on
@@ -171,10 +191,15 @@ def run_shard(infer_fn, load_windows, lo, hi, batch_size, timing=None, stream=No
     A depth-source variant's batches are ``(img, flow, seg, depth)``: ``infer_fn`` then takes four arrays and ``stream.submit``
     gets ``depth=``; every other variant sees the three-array calls it always did.
 
+    ``pairs``: 'both' (default) or 'trajectory' (batch_pairs).  With 'trajectory' every call carries the batch's selection as
+    ``pairs='both' | 'src1'`` - to ``infer_fn`` and to ``stream.submit`` alike; the rows a batch did not select come back as
+    exact zeros, which stitch_trajectory never reads.  With 'both' no call gets the argument.
+
     ``load_windows`` is either a callable ``(s, e) -> (img, flow, seg)`` or an iterable of
     ``(s, e, (img, flow, seg))`` in window order (davo_amd.loader.ThreadedWindowLoader: the next
     batches are decoded while this one is on the GPU).  ``timing`` (a dict) receives the seconds spent waiting for
     input and inside ``infer_fn``."""
+    batch_pairs(pairs, lo)                                # an unknown mode fails before anything is loaded
     out = np.zeros((hi - lo, 2, 6), np.float32)
     tails = []                                            # streamed partial batches: (padded poses, where they go)
     if callable(load_windows):
@@ -192,8 +217,11 @@ def run_shard(infer_fn, load_windows, lo, hi, batch_size, timing=None, stream=No
         s, e, parts = item
         parts, n = _pad_parts(parts, batch_size)
         extra = {"depth": parts[3]} if len(parts) == 4 else {}
+        sel = batch_pairs(pairs, s)
+        if sel is not None:
+            extra["pairs"] = sel
         if stream is None:
-            out[s - lo:e - lo] = np.asarray(infer_fn(*parts))[:n]
+            out[s - lo:e - lo] = np.asarray(infer_fn(*parts, **({"pairs": sel} if sel is not None else {})))[:n]
         elif n == batch_size:
             stream.submit(*parts[:3], out[s - lo:e - lo], **extra)     # delivered straight into its rows of `out`
         else:
@@ -238,19 +266,22 @@ def gather_poses(local, n_windows, world, rank, comm=None):
     return np.concatenate(parts, 0)
 
 
-def run_sequence(infer_fn, load_windows, n_frames, batch_size, rank=0, world=1, comm=None, timing=None, emulate=None, stream=None):
+def run_sequence(infer_fn, load_windows, n_frames, batch_size, rank=0, world=1, comm=None, timing=None, emulate=None, stream=None,
+                 pairs="both"):
     """The driver loop of test_kitti_pose.py:133-149, sharded: returns the Nf 4x4 poses on
     every rank (the stitch is cheap and sequential; rank 0 writes the file).  ``timing`` (a dict) receives this
     rank's seconds per stage: load_wait_s, forward_s, gather_s, stitch_s.
 
     ``emulate=(r, R)`` (measurement aid, one process): do exactly what rank r of R would do - its window shard, the gather
     (through ``comm`` at its real world size, normally 1), the stitch of the whole sequence - with the other ranks' windows left
-    at zero motion.  ``stream`` (a PoseStream): the shard runs through the library's streaming entry point (run_shard)."""
+    at zero motion.  ``stream`` (a PoseStream): the shard runs through the library's streaming entry point (run_shard).
+    ``pairs='trajectory'``: only the pairs the stitch reads are run (batch_pairs); the trajectory is the both-pairs one bit for
+    bit, and the returned ``poses`` hold zeros in the rows that were not run."""
     n_windows = n_frames - 2
     lo, hi = shard_windows(n_windows, *((world, rank) if emulate is None else (emulate[1], emulate[0])))
     if hasattr(load_windows, "for_range"):               # a loader factory: build this rank's prefetching loader
         load_windows = load_windows.for_range(lo, hi, batch_size)
-    local = run_shard(infer_fn, load_windows, lo, hi, batch_size, timing, stream)
+    local = run_shard(infer_fn, load_windows, lo, hi, batch_size, timing, stream, pairs)
     t0 = time.perf_counter()
     if emulate is None:
         poses = gather_poses(local, n_windows, world, rank, comm)
@@ -306,13 +337,14 @@ class SequenceError(RuntimeError):
 
 
 def run_sequences(infer_fn, sequences, source, batch_size, rank=0, world=1, comm=None, emulate=None, stream=None,
-                  before_sequence=None):
+                  before_sequence=None, pairs="both"):
     """run_sequence over several sequences, one after another, on one engine, one communicator and one stream: a generator of
     ``(seq, traj, poses, timing)`` per sequence, in the order of ``sequences`` = [(seq, n_frames), ...].  Every sequence is
     sharded over the ranks on its own (shard_windows(n_frames - 2, world, rank); a rank whose shard of a short sequence is empty
     still takes part in its gather) and batched on its own: no batch straddles two sequences, and a sequence's batches - hence
     its launch plans and its bits - are those of a run of that sequence alone.  A streamed run drains at every sequence's end:
-    the gather needs the poses.  ``timing`` is that sequence's own dict, as run_sequence fills it.
+    the gather needs the poses.  ``timing`` is that sequence's own dict, as run_sequence fills it.  ``pairs`` is run_sequence's: with 'trajectory' the both-pairs
+    batch repeats at every sequence's first batch.
 
     ``source(k, seq, n_frames, lo, hi)`` gives the k-th sequence's ``load_windows`` for this rank's shard [lo, hi) - anything
     run_sequence takes; it is asked when the sequence's turn comes.  ``before_sequence(k, seq, n_frames, load_windows)`` runs in
@@ -331,7 +363,7 @@ def run_sequences(infer_fn, sequences, source, batch_size, rank=0, world=1, comm
             if before_sequence is not None:
                 replaced = before_sequence(k, seq, n_frames, load)
                 load = load if replaced is None else replaced
-            traj, poses = run_sequence(infer_fn, load, n_frames, batch_size, rank, world, comm, timing, emulate, stream)
+            traj, poses = run_sequence(infer_fn, load, n_frames, batch_size, rank, world, comm, timing, emulate, stream, pairs)
         except Exception as exc:
             if stream is not None:
                 try:

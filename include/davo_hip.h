@@ -170,6 +170,27 @@ int davo_submit(davo_ctx* ctx, int B, const uint8_t* img, const float* flow, con
 int davo_wait(davo_ctx* ctx, int leave_pending);
 int davo_pending(davo_ctx* ctx);
 
+/* Pair selection.  A window's two poses come from two independent evaluations of the shared PoseNN (davo.py:1456-1457): pair 0
+ * reads (tgt, src0), pair 1 reads (tgt, src1), and nothing of one enters the other.  The reference's trajectory driver
+ * (test_kitti_pose.py:143-145) uses T(tgt->src0) of a sequence's first window only and inv(T(tgt->src1)) of every window, so for
+ * every window but the first, half of the arithmetic and 45 % of the input bytes serve a pose its caller drops.
+ * davo_set_pairs chooses which pairs the batches issued AFTER the call run: DAVO_PAIRS_BOTH (the default: every launch, copied
+ * byte and pose bit as without this entry point), DAVO_PAIRS_SRC0 or DAVO_PAIRS_SRC1; any other value returns DAVO_ERR_INVALID
+ * with a message.  It may be called between batches at any time (no re-creation, no weight reload) and covers davo_forward,
+ * davo_forward_device, davo_submit and their `_depth' forms.  Batches already in flight keep the selection they were issued with,
+ * and so does every range-recovery re-issue of an earlier batch (as issued, re-calibrated, or on the float32 kernels).
+ * The pose layout does not change: pose_out stays [B,2,6].  The selected pair's row is its pose - the same float32 chains per
+ * pixel as in a both-pairs batch; the row of the pair that was not selected is written as exactly +0.0 ("zero motion").
+ * With one pair selected a batch of B windows runs B pair images instead of 2 B, and no kernel reads a byte of the unselected source
+ * frame - its third of the image strip, its flow plane, its label map, its depth plane - so device-path callers need not fill them;
+ * the host entry points copy only what the selection reads (958,464 instead of 1,757,184 bytes per 128x416 window of the flagship).
+ * davo_calibrate[_depth] keeps running both pairs of the batch it is handed.  davo_debug_read sizes the per-pair-image tensors
+ * (cnv1..cnv7, packed, cnv5_se, cnv5_se_scale) by the pair images of the last forward: B of them with one pair, image n being
+ * window n's selected pair.  davo_last_plan / davo_last_split report what ran.  davo_get_pairs returns the current selection. */
+enum { DAVO_PAIRS_SRC0 = 1, DAVO_PAIRS_SRC1 = 2, DAVO_PAIRS_BOTH = 3 };
+int davo_set_pairs(davo_ctx* ctx, int pairs);
+int davo_get_pairs(const davo_ctx* ctx);
+
 const char* davo_last_error(const davo_ctx* ctx);
 void davo_destroy(davo_ctx* ctx);
 

@@ -11,6 +11,63 @@ sys.path.insert(0, ROOT)
 import numpy as np                                                   # noqa: E402
 from davo_amd import Engine, synth, parse_version, FLAGSHIP_VERSION   # noqa: E402
 
+
+
+def h2d_bytes_per_window(H, W, pairs):
+    """what davo_submit copies per window of the flagship (api.hip: stage_inputs): the strip, the flow planes the path reads, the
+    source frames' label maps (batches of four and more; smaller both-pairs batches copy all three) - or, with one pair, the
+    (tgt, source) two thirds of every strip row, one flow plane and one label map"""
+    hw = H * W
+    return hw * 6 + hw * 8 + hw * 4 if pairs != "both" else hw * 9 + hw * 16 + hw * 8
+
+
+def pairs_measurement(arms, rounds, n=30, H=128, W=416):
+    """`--pairs both src1 [--rounds R]`: windows/s of the streamed path (davo_submit from page-locked host memory, the slots
+    PoseStream picks: three at B = 32, four at B = 1) for each pair selection, the arms alternating inside every round of one
+    process, with the H2D bytes per window beside them.  f16x3 and float32."""
+    from davo_amd import pinned_empty
+    cfg = parse_version(FLAGSHIP_VERSION)
+    weights = synth.make_weights(cfg)
+    img, flow, seg = synth.make_inputs(8, H, W)
+    for B, slots in ((32, 3), (1, 4)):
+        reps = -(-B // 8)
+        host = tuple(np.tile(a, (reps,) + (1,) * (a.ndim - 1))[:B] for a in (img, flow, seg))
+        e = Engine(cfg, H, W, B)
+        e.load_weights(weights)
+        e.set_inflight(slots)
+        pinned = tuple(pinned_empty(a.shape, a.dtype) for a in host)
+        for d, a in zip(pinned, host):
+            d[...] = a
+        nb = n if B > 1 else 20 * n
+        outs = [np.empty((B, 2, 6), np.float32) for _ in range(nb)]
+        for prec in ("f16x3", "f32"):
+            e.set_precision(prec)
+            rates = {arm: [] for arm in arms}
+            for r in range(rounds + 1):                      # round 0 warms up
+                for arm in arms:
+                    e.set_pairs(arm)
+                    t0 = time.perf_counter()
+                    for o in outs:
+                        e.submit(*pinned, o, hold=8)
+                    e.synchronize()
+                    if r:
+                        rates[arm].append(B * nb / (time.perf_counter() - t0))
+            for arm in arms:
+                mb = h2d_bytes_per_window(H, W, arm) + (0 if (arm != "both" or B >= 4) else H * W * 4)
+                print("davo_submit pinned %-5s B=%-2d %d slots pairs=%-4s: %9.1f windows/s best, rounds %s; %d B H2D per window -> %.1f GB/s"
+                      % (prec, B, slots, arm, max(rates[arm]), " ".join("%.0f" % x for x in rates[arm]), mb, mb * max(rates[arm]) / 1e9), flush=True)
+        e.close()
+
+
+if "--pairs" in sys.argv:
+    import argparse
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--pairs", nargs="+", choices=sorted(Engine.PAIRS), required=True)
+    ap.add_argument("--rounds", type=int, default=3)
+    args = ap.parse_args()
+    pairs_measurement(args.pairs, args.rounds)
+    sys.exit(0)
+
 B = 32
 cfg = parse_version(FLAGSHIP_VERSION)
 img, flow, seg = synth.make_inputs(8, 128, 416)

@@ -4,6 +4,12 @@ alternating rounds (`--rounds`) so that a drift of the card's clocks does not fa
 
     python tools/variant_step.py --precision f16x3 --batch 32 <version> [<version> ...]
 
+`--pairs ARM [ARM ...]` runs every version once per arm, the arms alternating inside each round: ARM is a pair selection
+(both | src0 | src1; include/davo_hip.h: davo_set_pairs), optionally `@B` for that arm's batch size.  The measurement of
+DESIGN.md section 2 - does one pair of B windows run the launches of both pairs of B / 2? - is
+
+    python tools/variant_step.py --batch 32 --rounds 5 --pairs both src1 both@16 <version>
+
 Under `rocprofv3 --kernel-trace --stats -- python3 tools/variant_step.py ...` it gives the per-kernel table of a variant."""
 import argparse
 import json
@@ -28,37 +34,51 @@ def main():
     ap.add_argument("--steps", type=int, default=100)
     ap.add_argument("--warmup", type=int, default=30)
     ap.add_argument("--rounds", type=int, default=1)
+    ap.add_argument("--pairs", nargs="+", default=None, metavar="ARM",
+                    help="arms of (pair selection[@batch]): both | src0 | src1, e.g. --pairs both src1 both@16")
     a = ap.parse_args()
-    B, H, W = a.batch, a.height, a.width
-    img, flow, seg = synth.make_inputs(B, H, W)
-    depth = synth.make_depth(B, H, W)              # uploaded for the depth sources only
+    H, W = a.height, a.width
+    arms = []
+    for arm in a.pairs or ["both"]:
+        sel, _, b = arm.partition("@")
+        if sel not in Engine.PAIRS or (b and not b.isdigit()):
+            ap.error("--pairs: `%s' is not both | src0 | src1, optionally @batch" % arm)
+        arms.append((sel, int(b) if b else a.batch))
+    Bmax = max(b for _, b in arms)
+    img, flow, seg = synth.make_inputs(Bmax, H, W)
+    depth = synth.make_depth(Bmax, H, W)           # uploaded for the depth sources only
     runs = []
     for v in a.versions:
         cfg = parse_version(v)
-        e = Engine(cfg, H, W, B)
-        e.load_weights(synth.make_weights(cfg))
-        e.set_precision(a.precision)
-        bufs = [e.alloc(x.nbytes).upload(x) for x in (img, flow, seg)] + [e.alloc(B * 12 * 4)]
-        kw = {"depth": e.alloc(depth.nbytes).upload(depth)} if cfg.needs_depth else {}
-        for _ in range(a.warmup):
-            e.forward_device(B, *bufs, **kw)
-        e.synchronize()
-        runs.append((v, e, bufs, [], kw))
+        for sel, B in arms:
+            e = Engine(cfg, H, W, B)
+            e.load_weights(synth.make_weights(cfg))
+            e.set_precision(a.precision)
+            e.set_pairs(sel)
+            bufs = [e.alloc(x[:B].nbytes).upload(x[:B]) for x in (img, flow, seg)] + [e.alloc(B * 12 * 4)]
+            kw = {"depth": e.alloc(depth[:B].nbytes).upload(depth[:B])} if cfg.needs_depth else {}
+            for _ in range(a.warmup):
+                e.forward_device(B, *bufs, **kw)
+            e.synchronize()
+            runs.append((v, e, bufs, [], kw, sel, B))
     for _ in range(a.rounds):
-        for v, e, bufs, ms, kw in runs:
+        for v, e, bufs, ms, kw, sel, B in runs:
             e.synchronize()
             t = time.perf_counter()
             for _ in range(a.steps):
                 e.forward_device(B, *bufs, **kw)
             e.synchronize()
             ms.append((time.perf_counter() - t) * 1e3 / a.steps)
-    for v, e, bufs, ms, kw in runs:
+    for v, e, bufs, ms, kw, sel, B in runs:
         bufs = bufs + list(kw.values())
         pose = bufs[3].download((B, 2, 6))
         best = min(ms)
-        print(json.dumps({"version": v, "precision": a.precision, "batch": B, "height": H, "width": W, "steps": a.steps,
-                          "ms_per_step": round(best, 4), "ms_per_round": [round(x, 4) for x in ms],
-                          "triplets_per_s": round(B / best * 1e3, 1), "finite": bool(np.isfinite(pose).all())}), flush=True)
+        line = {"version": v, "precision": a.precision, "batch": B, "height": H, "width": W, "steps": a.steps,
+                "ms_per_step": round(best, 4), "ms_per_round": [round(x, 4) for x in ms],
+                "triplets_per_s": round(B / best * 1e3, 1), "finite": bool(np.isfinite(pose).all())}
+        if a.pairs:
+            line.update(pairs=sel, plan=[e.last_plan(l) for l in range(7)])
+        print(json.dumps(line), flush=True)
         for buf in bufs:
             buf.free()
         e.close()
