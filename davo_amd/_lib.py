@@ -10,7 +10,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(_HERE, "csrc")
 INCLUDE = os.path.join(os.path.dirname(_HERE), "include")
 # translation units of the library (csrc/ctx.h lists what each one holds); built in parallel, linked into one .so
-UNITS = ("api", "forward", "plan", "weights", "launch_f32", "launch_h3", "launch_h3s", "launch_h3w", "launch_h3_generic", "launch_misc", "comm")
+UNITS = ("api", "forward", "plan", "weights", "launch_f32", "launch_h3", "launch_h3s", "launch_h3w", "launch_h3_generic", "launch_misc", "launch_feature", "comm")
 
 
 # -fno-slp-vectorize: with SLP vectorisation hipcc (ROCm 7.2) fuses neighbouring scalar float updates into packed
@@ -47,6 +47,7 @@ EXPORTS = (
     "davo_comm_preload", "davo_comm_unique_id", "davo_comm_init", "davo_comm_size", "davo_allgather_poses", "davo_allgather_poses_device",
     "davo_comm_allreduce", "davo_comm_barrier", "davo_comm_destroy", "davo_plan_layer", "davo_tile_filter_rows",
     "davo_set_pairs", "davo_get_pairs",
+    "davo_set_feature_export", "davo_forward_features",
 )
 COMM_ID_BYTES = 128
 
@@ -54,6 +55,11 @@ COMM_ID_BYTES = 128
 class DavoVariant(ctypes.Structure):
     _fields_ = [(n, ctypes.c_int32) for n in ("cin_per_frame", "cnv6_out", "se_act", "norm_flow",
                                               "abs_mode", "att_source", "mask_rgb", "mask_info")]
+
+
+class DavoFeatureOut(ctypes.Structure):
+    """davo_feature_out (include/davo_hip.h): host pointers, None = that output is neither computed nor copied."""
+    _fields_ = [(n, ctypes.c_void_p) for n in ("att_19", "attention", "masked_image", "image", "feat_rot", "feat_trans")]
 
 
 def sources():
@@ -211,6 +217,8 @@ def _load():
     L.davo_set_impl.argtypes = [vp, i]
     L.davo_set_pairs.argtypes = [vp, i]
     L.davo_get_pairs.argtypes = [vp]
+    L.davo_set_feature_export.argtypes = [vp, i]
+    L.davo_forward_features.argtypes = [vp, i, vp, vp, vp, vp, vp, ctypes.POINTER(DavoFeatureOut)]
     L.davo_debug_read.argtypes = [vp, ctypes.c_char_p, f32p, ctypes.c_size_t]
     L.davo_conv2d_same.argtypes = [i, f32p, i, i, i, i, f32p, i, i, f32p, i, i, i, i, f32p, ctypes.c_char_p, i]
     ip = ctypes.POINTER(i)

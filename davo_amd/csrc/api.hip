@@ -766,9 +766,93 @@ int davo_wait(davo_ctx* c, int leave_pending) {
 
 int davo_pending(davo_ctx* c) { return c ? (int)c->jobs.size() : DAVO_ERR_INVALID; }
 
-// the body of davo_forward / davo_forward_depth (depth_form)
+// ---- feature export: davo_set_feature_export / davo_forward_features ----------------------------------------------
+// What DAVO.inference(sess, mode='feature') fetches beside the poses (davo.py:1553-1569; generate_feature_map.py:183-260 is its
+// reader): everything is computed from what a forward leaves on the device - the class tables (d_tab), the staged inputs and cnv6
+// in the storage form the forward ran in - by the two kernels of feature_export.h, into one workspace block of the context, and
+// copied to the caller's arrays piece by piece.  The block holds fx_cap windows of every export tensor: the largest sub-batch
+// davo_forward issues under the host_chunk of the moment the export was switched on; a larger run of windows (a re-issued batch,
+// a host_chunk raised since) goes out in pieces of fx_cap.  With the export off nothing here is allocated or launched.
+namespace {
+
+struct FxLayout { size_t rot, trans, masked, image, attention, att_19, total; };      // float offsets into d_fx for `cap' windows
+FxLayout fx_layout(const davo_ctx* c, int cap) {
+    const size_t HW = (size_t)c->H * c->W, n = (size_t)cap, c6 = (size_t)c->v.cnv6_out;
+    FxLayout l{};
+    l.rot = 0;
+    l.trans = l.rot + n * HW * c6;
+    l.masked = l.trans + n * HW * c6;
+    l.image = l.masked + n * HW * 9;
+    l.attention = l.image + n * HW * 9;
+    l.att_19 = l.attention + n * HW * 3;              // last: the only section that is no multiple of 16 bytes
+    l.total = l.att_19 + n * 3 * NCLS;
+    return l;
+}
+
+void free_fx_workspace(davo_ctx* c) {
+    if (c->d_fx) (void)hipFree(c->d_fx);
+    c->d_fx = nullptr;
+    c->fx_cap = 0;
+}
+
+bool fx_wanted(const davo_feature_out* o) {
+    return o && (o->att_19 || o->attention || o->masked_image || o->image || o->feat_rot || o->feat_trans);
+}
+
+// Windows [w0, w0 + nw) of the forward that last ran on slot 0 - `in' are that forward's device inputs, window 0 - go to windows
+// [b0, b0 + nw) of the caller's arrays of B windows.  Reads d_tab, the inputs and d_act[5] as that forward left them, in the
+// precision it ran (last_precision) and under the storage scale it stored cnv6 with.  Returns with the copies done.
+int export_features(davo_ctx* c, const Inputs& in, int w0, int nw, int b0, int B, const davo_feature_out& out) {
+    if (!c->d_fx || c->fx_cap < 1) return fail(c, DAVO_ERR_INVALID, "internal: no feature export workspace");
+    if (c->last_pairs != PAIRS_BOTH || w0 < 0 || w0 + nw > c->last_B) return fail(c, DAVO_ERR_INVALID, "internal: feature export of windows the last forward did not run");
+    const size_t HW = (size_t)c->H * c->W, c6 = (size_t)c->v.cnv6_out;
+    const bool h3 = c->last_precision == 1;
+    const FxLayout l = fx_layout(c, c->fx_cap);
+    hipStream_t s = c->stream;
+    for (int p0 = 0; p0 < nw; p0 += c->fx_cap) {
+        const int np = std::min(c->fx_cap, nw - p0);
+        const Inputs win = from_window(c, in, w0 + p0);
+        float* const w_att19 = out.att_19 ? c->d_fx + l.att_19 : nullptr;
+        float* const w_att = out.attention ? c->d_fx + l.attention : nullptr;
+        float* const w_masked = out.masked_image ? c->d_fx + l.masked : nullptr;
+        float* const w_image = out.image ? c->d_fx + l.image : nullptr;
+        float* const w_rot = out.feat_rot ? c->d_fx + l.rot : nullptr;
+        float* const w_trans = out.feat_trans ? c->d_fx + l.trans : nullptr;
+        if (w_att19 || w_att || w_masked || w_image) {
+            ProfScope ps(c, "feature_maps");
+            HIP_TRY(c, launch_feature_maps(static_cast<const uint8_t*>(win.img), static_cast<const float*>(win.seg),
+                                           c->d_tab + (size_t)(w0 + p0) * 3 * NCLS, c->v, np, c->H, c->W, w_att19, w_att, w_masked, w_image, s));
+        }
+        if (w_rot || w_trans) {
+            ProfScope ps(c, "feature_resize_cnv6");
+            HIP_TRY(c, launch_feature_resize_cnv6(h3, c->d_act[5], w0 + p0, np, c->H2, c->W2, (int)c6, h3 ? ldexpf(1.0f, -c->act_shift[5]) : 1.0f,
+                                                  w_rot, w_trans, s));
+        }
+        // the caller's per-frame arrays are [3][B][...], the workspace's [3][np][...]: one copy per frame
+        const size_t first = (size_t)(b0 + p0);
+        auto frames = [&](float* host, const float* dev, size_t per_window) -> int {
+            if (!host) return DAVO_OK;
+            for (int f = 0; f < 3; ++f)
+                HIP_TRY(c, hipMemcpyAsync(host + ((size_t)f * B + first) * per_window, dev + (size_t)f * np * per_window,
+                                          (size_t)np * per_window * sizeof(float), hipMemcpyDeviceToHost, s));
+            return DAVO_OK;
+        };
+        { int rc = frames(out.att_19, w_att19, NCLS); if (rc) return rc; }
+        { int rc = frames(out.attention, w_att, HW); if (rc) return rc; }
+        { int rc = frames(out.masked_image, w_masked, HW * 3); if (rc) return rc; }
+        { int rc = frames(out.image, w_image, HW * 3); if (rc) return rc; }
+        if (w_rot) HIP_TRY(c, hipMemcpyAsync(out.feat_rot + first * HW * c6, w_rot, (size_t)np * HW * c6 * sizeof(float), hipMemcpyDeviceToHost, s));
+        if (w_trans) HIP_TRY(c, hipMemcpyAsync(out.feat_trans + first * HW * c6, w_trans, (size_t)np * HW * c6 * sizeof(float), hipMemcpyDeviceToHost, s));
+        HIP_TRY(c, hipStreamSynchronize(s));              // the next piece reuses the workspace
+    }
+    return DAVO_OK;
+}
+
+}  // namespace
+
+// the body of davo_forward / davo_forward_depth (depth_form) and of davo_forward_features (fx: the exports wanted, else null)
 static int forward_entry(davo_ctx* c, int B, const uint8_t* img, const float* flow, const float* seg, const float* depth_in, float* pose_out,
-                         bool depth_form) {
+                         bool depth_form, const davo_feature_out* fx = nullptr) {
     if (!c) return DAVO_ERR_INVALID;
     if (!img || !flow || !seg || !pose_out) return fail(c, DAVO_ERR_INVALID, "null host pointer");
     const void* depth = depth_in;
@@ -833,12 +917,17 @@ static int forward_entry(davo_ctx* c, int B, const uint8_t* img, const float* fl
         c->snap = SnapArgs{};
         if (rc) return rc;
         f32_fallback |= c->f32_fallback;
+        // feature export: the context holds one sub-batch's activations, so every sub-batch but the last is exported before the next
+        // one runs; the last one waits for the verdict below
+        if (fx && i < nchunks - 1 && (rc = export_features(c, from_window(c, c->host_set.view(), b0), 0, nb, b0, B, *fx))) return rc;
     }
+    const int last_b0 = (nchunks - 1) * chunk;
+    auto export_last = [&]() { return fx ? export_features(c, from_window(c, c->host_set.view(), last_b0), 0, B - last_b0, last_b0, B, *fx) : DAVO_OK; };
     if (f32_fallback) ++c->n_f32_batches;                      // once per call, not per sub-batch
     HIP_TRY(c, hipMemcpyAsync(c->h_sync_pose, c->s_pose, (size_t)B * 12 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     memcpy(pose_out, c->h_sync_pose, (size_t)B * 12 * sizeof(float));
-    if (c->last_precision != 1) return DAVO_OK;
+    if (c->last_precision != 1) return export_last();
     unsigned raw[RANGE_WORDS];
     int rc = DAVO_OK;
     if (seq && __atomic_load_n(&c->h_range[RANGE_SEQ], __ATOMIC_ACQUIRE) == seq) memcpy(raw, c->h_range, sizeof raw);      // the stream is idle: the mirror is final
@@ -850,8 +939,12 @@ static int forward_entry(davo_ctx* c, int B, const uint8_t* img, const float* fl
         // the staged copy of the batch is still in HBM: re-issue it whole (recalibrated, or on the float32 kernels)
         rc = recover_batch(c, [&] { Ticket t{}; t.B = B; t.pairs = c->pairs; t.in = c->host_set.view(); t.pose = c->s_pose; t.ring = -1; t.stream = c->stream; t.issue = ~0ull; return t; }());
         if (rc == DAVO_OK) HIP_TRY(c, hipMemcpy(pose_out, c->s_pose, (size_t)B * 12 * sizeof(float), hipMemcpyDeviceToHost));
+        // the re-issue ran the whole batch as one forward and produced the poses returned: every window's exports come from it, in
+        // the precision and under the scales it ran with (what the sub-batches exported above is overwritten)
+        if (rc == DAVO_OK && fx) rc = export_features(c, c->host_set.view(), 0, B, 0, B, *fx);
+        return rc;
     }
-    return rc;
+    return rc == DAVO_OK ? export_last() : rc;
 }
 
 int davo_forward(davo_ctx* c, int B, const uint8_t* img, const float* flow, const float* seg, float* pose_out) {
@@ -860,6 +953,30 @@ int davo_forward(davo_ctx* c, int B, const uint8_t* img, const float* flow, cons
 
 int davo_forward_depth(davo_ctx* c, int B, const uint8_t* img, const float* flow, const float* seg, const float* depth, float* pose_out) {
     return forward_entry(c, B, img, flow, seg, depth, pose_out, true);
+}
+
+int davo_set_feature_export(davo_ctx* c, int on) {
+    if (!c) return DAVO_ERR_INVALID;
+    HIP_TRY(c, hipSetDevice(c->device));
+    { int rc = sync_all_slots(c); if (rc) return rc; }
+    if (!on) { free_fx_workspace(c); c->fx_on = false; return DAVO_OK; }
+    if (!c->d_fx) {
+        const int cap = c->host_chunk > 0 ? std::min(c->max_batch, 2 * c->host_chunk - 1) : c->max_batch;      // davo_forward's largest sub-batch
+        HIP_TRY(c, hipMalloc(reinterpret_cast<void**>(&c->d_fx), fx_layout(c, cap).total * sizeof(float)));
+        c->fx_cap = cap;
+    }
+    c->fx_on = true;
+    return DAVO_OK;
+}
+
+int davo_forward_features(davo_ctx* c, int B, const uint8_t* img, const float* flow, const float* seg, const float* depth, float* pose_out,
+                          const davo_feature_out* out) {
+    if (!c) return DAVO_ERR_INVALID;
+    if (!c->fx_on) return fail(c, DAVO_ERR_NOT_READY, "davo_forward_features: the feature export is off - call davo_set_feature_export(ctx, 1) first");
+    if (c->pairs != PAIRS_BOTH)
+        return fail(c, DAVO_ERR_INVALID, "davo_forward_features runs both pairs of every window, the reference's semantics (davo.py:1456-1457): "
+                    "davo_set_pairs(ctx, DAVO_PAIRS_BOTH) first (the selection is %d)", c->pairs);
+    return forward_entry(c, B, img, flow, seg, depth, pose_out, true, fx_wanted(out) ? out : nullptr);
 }
 
 int davo_range_stats(davo_ctx* c, long long* recalibrations, long long* f32_batches, long long* reissued) {
@@ -976,6 +1093,7 @@ void davo_destroy(davo_ctx* c) {
         if (c->st_copied[k]) (void)hipEventDestroy(c->st_copied[k]);
     }
     if (c->h_sync_pose) (void)hipHostFree(c->h_sync_pose);
+    free_fx_workspace(c);
     void* misc[] = {c->d_reissue_pose, c->d_range_base, c->d_splitk, c->d_pose_tiles, c->d_w1patch, c->d_w2patch, c->d_w3patch, c->d_w1patch_f32, c->d_w2patch_f32, c->d_w3patch_f32, c->d_zeros, c->d_wpred, c->d_bpred, c->s_pose};
     for (auto p : misc) if (p) (void)hipFree(p);
     for (auto& kv : c->tile_orders) if (kv.second) (void)hipFree(kv.second);

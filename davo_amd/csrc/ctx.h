@@ -11,6 +11,7 @@
 //   launch_h3.hip   conv_igemm_h3 instantiations + dispatch (the f16x3 path, the long compile)
 //   launch_h3s.hip  conv_igemm_h3s instantiations (208x256 tile); launch_h3_generic.hip: davo_conv2d_same's shapes
 //   launch_misc.hip prologue / pose head / cnv1..cnv3 patch / feature-attention (posenn_se.h) / direct-convolution kernels + dispatch
+//   launch_feature.hip  the feature export kernels (feature_export.h) + dispatch
 //   comm.hip        RCCL communicator behind the C ABI (pose gather of the window-sharded driver)
 #pragma once
 #include <hip/hip_runtime.h>
@@ -226,6 +227,11 @@ struct davo_ctx {
     std::string range_report;                  // what the range management last did, in words (davo_range_report)
     long long n_recalibrations = 0, n_f32_batches = 0, n_reissued = 0;
     int host_chunk = 8;                        // davo_forward: windows per sub-batch (davo_set_option "host_chunk"; 0 = whole batch)
+    // feature export (davo_set_feature_export / davo_forward_features, api.hip): one device block for fx_cap windows of every
+    // export tensor, null with the export off
+    bool fx_on = false;
+    float* d_fx = nullptr;
+    int fx_cap = 0;
     // streaming host entry (davo_submit / davo_wait): staging input sets, pose ring, undelivered batches in issue order
     davo::InputSet stream_sets[davo::STREAM_SETS];     // one staging set per in-flight slot (allocated by the slot's first davo_submit)
     hipEvent_t st_copied[davo::STREAM_POSES] = {};             // "the H2D copies of the batch in pose ring entry k are done" (recorded only for hold < STREAM_POSES)

@@ -1,0 +1,161 @@
+// feature_export.h — the export kernels behind davo_forward_features (include/davo_hip.h): what
+// DAVO.inference(sess, mode='feature') fetches beside the poses (reference davo.py:1553-1569), computed from what a forward
+// leaves on the device - the attention tables, the inputs, and cnv6 in either storage form.  Nothing of the pose path runs here.
+//
+//   feature_maps         per frame (tgt, src0, src1): the attention map that was multiplied in (davo.py:1387,1394,1218,1405-1414,
+//                        1468), the masked rgb (davo.py:1419-1421,1447-1449,1471-1475), the plain preprocessed rgb
+//                        (davo.py:967-971, 1519-1522), and the 19-entry rows the maps are gathers of
+//   feature_resize_cnv6  tf.image.resize_bilinear(cnv6 of the tgt->src1 call, (H, W)) of each head (davo.py:1457,1463-1465)
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "input_decode.h"
+#include "params.h"
+
+namespace davo {
+
+// Which frames' maps are class-table gathers; the others are the reference's tf.ones_like overrides: 1.0 on every pixel, ignore
+// labels included.  The same two tests mask_pack applies (prologue.h).
+__host__ __device__ inline bool feature_frame_looked_up(int att_source, int frame) {
+    return frame == 0 ? att_tgt_attended(att_source) : att_source != 0;
+}
+
+struct FeatureMapsOut {          // device pointers of one piece of nw windows; null = not wanted
+    float* att_19;               // [3][nw][19]
+    float* attention;            // [3][nw][H][W]
+    float* masked;               // [3][nw][H][W][3]
+    float* image;                // [3][nw][H][W][3]
+};
+
+// One thread per 4 horizontally adjacent pixels of one window, all three frames (mask_pack's unit).  img / seg / tab point at the
+// first window of the piece.  The masked rgb is mask_pack's float32 expression - u8_to_unit, then one multiply by the frame's map
+// where the variant masks rgb - so it equals the packed tensor's rgb channels to the bit.  The first 3 * nw * 19 threads also write
+// the att_19 rows: the table row the forward used for a looked-up frame, 19 ones for an overridden one, whatever d_tab holds there.
+__global__ __launch_bounds__(256) void feature_maps(const uint8_t* __restrict__ img, const float* __restrict__ seg,
+                                                    const float* __restrict__ tab, Variant v, int nw, int H, int W, FeatureMapsOut o) {
+    const int W4 = W >> 2;
+    const long total = (long)nw * H * W4;
+    const long gid = (long)blockIdx.x * 256 + threadIdx.x;
+    if (o.att_19 && gid < (long)nw * 3 * NCLS) {                 // (b, frame, class) -> [frame][b][class]
+        const int cls = (int)(gid % NCLS), bf = (int)(gid / NCLS), frame = bf % 3, b = bf / 3;
+        o.att_19[((size_t)frame * nw + b) * NCLS + cls] = feature_frame_looked_up(v.att_source, frame) ? tab[((size_t)b * 3 + frame) * NCLS + cls] : 1.0f;
+    }
+    if (gid >= total) return;
+    const int x4 = (int)(gid % W4);
+    long t = gid / W4;
+    const int y = (int)(t % H), b = (int)(t / H);
+    const int x = x4 * 4;
+    const size_t HW = (size_t)H * W, pix = (size_t)y * W + x;
+    const uint8_t* row = img + ((size_t)b * H + y) * (size_t)(9 * W);
+#pragma unroll
+    for (int frame = 0; frame < 3; ++frame) {
+        // (tgt, src0, src1) -> strip slot src0 | tgt | src1 (data_loader.py:537-557) and seg file plane src0, tgt, src1 (davo.py:998-1004)
+        const int slot = frame == 0 ? 1 : frame == 1 ? 0 : 2;
+        float a[4] = {1.f, 1.f, 1.f, 1.f};
+        if (feature_frame_looked_up(v.att_source, frame)) {
+            const float4 sg = *reinterpret_cast<const float4*>(seg + ((size_t)b * 3 + slot) * HW + pix);
+            const float* tab_f = tab + ((size_t)b * 3 + frame) * NCLS;
+            a[0] = att_lookup(tab_f, sg.x); a[1] = att_lookup(tab_f, sg.y);
+            a[2] = att_lookup(tab_f, sg.z); a[3] = att_lookup(tab_f, sg.w);
+        }
+        const size_t at = ((size_t)frame * nw + b) * HW + pix;
+        if (o.attention) *reinterpret_cast<float4*>(o.attention + at) = make_float4(a[0], a[1], a[2], a[3]);
+        if (!o.masked && !o.image) continue;
+        const uint32_t* ps = reinterpret_cast<const uint32_t*>(row + (size_t)(slot * W + x) * 3);
+        const uint32_t q0 = ps[0], q1 = ps[1], q2 = ps[2];
+        const uint8_t bytes[12] = {(uint8_t)q0, (uint8_t)(q0 >> 8), (uint8_t)(q0 >> 16), (uint8_t)(q0 >> 24),
+                                   (uint8_t)q1, (uint8_t)(q1 >> 8), (uint8_t)(q1 >> 16), (uint8_t)(q1 >> 24),
+                                   (uint8_t)q2, (uint8_t)(q2 >> 8), (uint8_t)(q2 >> 16), (uint8_t)(q2 >> 24)};
+        float plain[12], masked[12];
+#pragma unroll
+        for (int k = 0; k < 12; ++k) {
+            float r = u8_to_unit(bytes[k]);
+            plain[k] = r;
+            if (v.mask_rgb) r *= a[k / 3];
+            masked[k] = r;
+        }
+        float4* om = o.masked ? reinterpret_cast<float4*>(o.masked + at * 3) : nullptr;
+        float4* oi = o.image ? reinterpret_cast<float4*>(o.image + at * 3) : nullptr;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            if (om) om[k] = make_float4(masked[4 * k], masked[4 * k + 1], masked[4 * k + 2], masked[4 * k + 3]);
+            if (oi) oi[k] = make_float4(plain[4 * k], plain[4 * k + 1], plain[4 * k + 2], plain[4 * k + 3]);
+        }
+    }
+}
+
+// TF 1.13's resize_bilinear (align_corners=False, no half-pixel centres) at the one scale the library has: cnv6 is [H/4, W/4], so
+// in = out / 4 exactly, lo = out >> 2, lerp = (out & 3) / 4, hi = min(lo + 1, last).  TF's order per value, float32, no contraction:
+// top = tl + (tr - tl) * xl; bot = bl + (br - bl) * xl; out = top + (bot - top) * yl.
+struct ResizeParams {
+    const uint8_t* x;            // cnv6 of the forward, pair image 0: float32 NHWC [2B][H2][W2][2 c6], or the f16x3 blocked form (per
+                                 // pixel and block of 32 channels [32 hi | 32 lo] halves, scaled by 2^act_shift)
+    float* out[2];               // rotation, translation: [nw][4 H2][4 W2][c6] float32 of the piece; null = head not wanted
+    int w0, nw;                  // windows [w0, w0 + nw) of that forward; window b's features are pair image 2 b + 1 (tgt->src1)
+    int H2, W2, c6, cq_log2;     // cq = c6 / 4 channel quads per pixel
+    int head0;                   // head of blockIdx.y == 0
+    float unscale;               // 2^-act_shift[cnv6] (f16x3), exact
+};
+
+// four channels of one input pixel, decoded with davo_debug_read's expression (api.hip): (float)hi + (float)lo, times 2^-shift
+template <bool H3>
+__device__ __forceinline__ void resize_load4(const ResizeParams& p, size_t pixel, int ch, float v[4]) {
+#pragma clang fp contract(off)
+    if (H3) {
+        const uint8_t* q = p.x + pixel * ((size_t)p.c6 * 8) + (size_t)(ch >> 5) * 128 + (size_t)(ch & 31) * 2;
+        const uint2 hi = *reinterpret_cast<const uint2*>(q), lo = *reinterpret_cast<const uint2*>(q + 64);
+        _Float16 h[4], l[4];
+        __builtin_memcpy(h, &hi, 8);
+        __builtin_memcpy(l, &lo, 8);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) v[k] = ((float)h[k] + (float)l[k]) * p.unscale;
+    } else {
+        const float4 f = *reinterpret_cast<const float4*>(p.x + (pixel * ((size_t)p.c6 * 2) + ch) * sizeof(float));
+        v[0] = f.x; v[1] = f.y; v[2] = f.z; v[3] = f.w;
+    }
+}
+
+// A thread takes four channels of one output column and one (top, bottom) input row pair: one read of the two rows' corner pixels,
+// the two horizontal lerps once, then the four output rows 4 iy .. 4 iy + 3 that share the pair.  Lanes run along the channel quads
+// of consecutive columns, so each of a wave's four store instructions writes 1 KiB of contiguous output, 16 bytes per lane.  grid
+// (ceil(nw H2 W cq / 256), heads wanted); all offsets 64-bit (B H W c6 passes 2^31 at B = 32 of the flagship shape).
+template <bool H3>
+__global__ __launch_bounds__(256) void feature_resize_cnv6(ResizeParams p) {
+#pragma clang fp contract(off)
+    const int W = p.W2 * 4, H = p.H2 * 4;
+    const long g = (long)blockIdx.x * 256 + threadIdx.x;
+    const int cq = (int)(g & ((1 << p.cq_log2) - 1));
+    long t = g >> p.cq_log2;
+    const int x = (int)(t % W); t /= W;
+    const int iy = (int)(t % p.H2);
+    const long b = t / p.H2;
+    if (b >= p.nw) return;
+    const int head = p.head0 + blockIdx.y;
+    const int ix = x >> 2, ix1 = min(ix + 1, p.W2 - 1), iy1 = min(iy + 1, p.H2 - 1);
+    const float xl = (float)(x & 3) * 0.25f;
+    const size_t n = 2 * (size_t)(p.w0 + b) + 1;
+    const size_t r0 = (n * p.H2 + iy) * p.W2, r1 = (n * p.H2 + iy1) * p.W2;
+    const int ch = head * p.c6 + 4 * cq;
+    float tl[4], tr[4], bl[4], br[4];
+    resize_load4<H3>(p, r0 + ix, ch, tl);
+    resize_load4<H3>(p, r0 + ix1, ch, tr);
+    resize_load4<H3>(p, r1 + ix, ch, bl);
+    resize_load4<H3>(p, r1 + ix1, ch, br);
+    float top[4], dv[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        top[k] = tl[k] + (tr[k] - tl[k]) * xl;
+        const float bot = bl[k] + (br[k] - bl[k]) * xl;
+        dv[k] = bot - top[k];
+    }
+    float* o = p.out[head] + ((((size_t)b * H + 4 * (size_t)iy) * W + x) * p.c6 + 4 * cq);
+    const size_t row = (size_t)W * p.c6;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        const float yl = (float)r * 0.25f;
+        *reinterpret_cast<float4*>(o + r * row) = make_float4(top[0] + dv[0] * yl, top[1] + dv[1] * yl, top[2] + dv[2] * yl, top[3] + dv[3] * yl);
+    }
+}
+
+}  // namespace davo

@@ -86,4 +86,14 @@ hipError_t launch_se5_squeeze(bool h3, const void* d_x, int NB, int P, float* d_
 hipError_t launch_se5_excite(const float* d_partial, int NB, int P, float unscale, const float* const se_w[8], float* d_scale, hipStream_t s);
 hipError_t launch_se5_scale(bool h3, const void* d_x, const float* d_scale, int NB, int P, void* d_y, unsigned* d_range, hipStream_t s);
 
+// ---- launch_feature.hip: the feature export (feature_export.h; davo_forward_features) -----------------------------
+// one piece of nw windows: d_img / d_seg / d_tab point at the piece's first window; outputs [3][nw][19], [3][nw][H][W], [3][nw][H][W][3] x 2,
+// frames in the order tgt, src0, src1; a null output is not written
+hipError_t launch_feature_maps(const uint8_t* d_img, const float* d_seg, const float* d_tab, const Variant& v, int nw, int H, int W,
+                               float* d_att_19, float* d_attention, float* d_masked, float* d_image, hipStream_t s);
+// d_cnv6: the whole stored cnv6 of a both-pairs forward (h3: f16x3 blocked, scaled by 1 / unscale; else float32 NHWC); windows
+// [w0, w0 + nw) of it -> d_rot / d_trans [nw][4 H2][4 W2][c6]; a null head is not computed
+hipError_t launch_feature_resize_cnv6(bool h3, const void* d_cnv6, int w0, int nw, int H2, int W2, int c6, float unscale,
+                                      float* d_rot, float* d_trans, hipStream_t s);
+
 }  // namespace davo

@@ -13,6 +13,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "input_decode.h"
 #include "params.h"
 #include "pose_tail.h"
 
@@ -413,17 +414,6 @@ __global__ __launch_bounds__(256) void se_depth_squeeze(const float* __restrict_
     if (!last_workgroup(counters + b, (unsigned)((1 + pairs_per_window(sel)) * SQ_CHUNKS), &ticket)) return;
     if (wid < 3 && pair_reads_frame(wid, sel)) se_class_excite_wave<true>(partial, HW, v, b, wid, lane, w1, b1, w2, b2, tab);
     if (threadIdx.x == 0) __hip_atomic_store(counters + b, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-__device__ __forceinline__ float att_lookup(const float* tab19, float seg) {
-    // tf.cast(float -> int32) truncates toward zero; one_hot of an out-of-range id is a zero row.  NaN / inf /
-    // beyond-int32 labels are platform-defined in the cast (x86: INT_MIN, GPUs: 0 or saturation) and pinned to
-    // "no class" here: only finite values in (-1, 19) select a row (the comparison is false for NaN).
-    return (seg > -1.0f && seg < (float)NCLS) ? tab19[(int)seg] : 0.f;
-}
-
-__device__ __forceinline__ float u8_to_unit(uint32_t byte) {
-    return (float)byte * (1.0f / 255.0f) * 2.0f - 1.0f;        // davo.py:1521-1522
 }
 
 // Mask + pack: one thread per 4 horizontally adjacent pixels of one pair image.

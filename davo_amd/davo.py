@@ -166,6 +166,40 @@ class Engine:
                                              seg.ctypes.data_as(vp), out.ctypes.data_as(vp)))
         return out
 
+    FEATURE_OUTPUTS = ("att_19", "attention", "masked_image", "image", "feat_rot", "feat_trans")
+
+    def set_feature_export(self, on=True):
+        """Allocate (or free) the workspace of forward_features (include/davo_hip.h: davo_set_feature_export); off by default."""
+        self._check(self._L.davo_set_feature_export(self._ctx, int(bool(on))))
+
+    def forward_features(self, img, flow, seg, depth=None, want=FEATURE_OUTPUTS):
+        """forward() plus the tensors of the reference's mode='feature' fetches from the same forward (include/davo_hip.h:
+        davo_forward_features; needs set_feature_export() and the 'both' pair selection).  -> {'pose': [B,2,6]} and, for each
+        name in ``want``: 'att_19' [3,B,19], 'attention' [3,B,H,W], 'masked_image' and 'image' [3,B,H,W,3] - frames in the
+        order tgt, src0, src1 - 'feat_rot' and 'feat_trans' [B,H,W,cnv6_out]; all float32.  An output that is not wanted is
+        neither computed nor copied."""
+        unknown = [w for w in want if w not in self.FEATURE_OUTPUTS]
+        if unknown:
+            raise ValueError("unknown feature output(s) %s: choose from %s" % (unknown, list(self.FEATURE_OUTPUTS)))
+        img = np.ascontiguousarray(img, np.uint8)
+        flow = np.ascontiguousarray(flow, np.float32)
+        seg = np.ascontiguousarray(seg, np.float32)
+        B = self._check_batch(img, flow, seg)
+        depth = self._depth_arg(depth, B)
+        H, W, c6 = self.H, self.W, self.cfg.cnv6_out
+        shapes = {"att_19": (3, B, 19), "attention": (3, B, H, W), "masked_image": (3, B, H, W, 3), "image": (3, B, H, W, 3),
+                  "feat_rot": (B, H, W, c6), "feat_trans": (B, H, W, c6)}
+        res = {"pose": np.empty((B, 2, 6), np.float32)}
+        for name in self.FEATURE_OUTPUTS:
+            if name in want:
+                res[name] = np.empty(shapes[name], np.float32)
+        vp = ctypes.c_void_p
+        out = _lib.DavoFeatureOut(*[res[n].ctypes.data if n in res else None for n in self.FEATURE_OUTPUTS])
+        self._check(self._L.davo_forward_features(self._ctx, B, img.ctypes.data_as(vp), flow.ctypes.data_as(vp), seg.ctypes.data_as(vp),
+                                                  depth.ctypes.data_as(vp) if depth is not None else None,
+                                                  res["pose"].ctypes.data_as(vp), ctypes.byref(out)))
+        return res
+
     def _check_batch(self, img, flow, seg):
         B = img.shape[0]
         if img.shape != (B, self.H, 3 * self.W, 3):
@@ -389,6 +423,17 @@ def conv2d_same(x, w, b, stride=1, rate=1, relu=True, device=0, precision="f32")
     return y
 
 
+def seg_one_hot(seg):
+    """The reference's seg_19 (davo.py:1115: tf.one_hot(tf.cast(seg, int32), 19)) of label maps [..., 1] -> [..., 19] float32, by
+    the rules the kernels' class gather follows: the cast truncates toward zero, and a label outside [0, 19) after it - or NaN or
+    infinite, where the cast is platform-defined - selects no class: a zero row."""
+    seg = np.asarray(seg, np.float32)[..., 0]
+    with np.errstate(invalid="ignore"):
+        ok = np.isfinite(seg) & (seg > -1.0) & (seg < 19.0)
+    idx = np.where(ok, seg, 0.0).astype(np.int32)
+    return ((idx[..., None] == np.arange(19, dtype=np.int32)) & ok[..., None]).astype(np.float32)
+
+
 class DAVO(object):
     """Drop-in for the reference class on the inference path (reference davo.py:30)."""
 
@@ -398,6 +443,15 @@ class DAVO(object):
         self.device = device
         self.engine = None
         self._weights = None
+        self._feature_mode = False
+
+    def enable_feature_mode(self):
+        """Opt in to ``inference(mode='feature')``: allocates the library's export workspace (include/davo_hip.h:
+        davo_set_feature_export) - now if ``setup_inference`` has run, else when it does.  Returns self."""
+        self._feature_mode = True
+        if self.engine is not None:
+            self.engine.set_feature_export(True)
+        return self
 
     def setup_inference(self, img_height, img_width, mode, seq_length=3, batch_size=1,
                         input_img_uint8=None, input_pose=None, input_flow=None, input_depth=None,
@@ -417,6 +471,8 @@ class DAVO(object):
         self.engine = Engine(self.cfg, img_height, img_width, batch_size, self.device)
         if self._weights is not None:
             self.engine.load_weights(self._weights)
+        if self._feature_mode:
+            self.engine.set_feature_export(True)
         self._ahead = []                                   # iterator inputs: batches submitted and not returned yet
         if input_img_uint8 is not None and not isinstance(input_img_uint8, np.ndarray) and input_flow is None:
             self._inputs = iter(input_img_uint8)
@@ -442,17 +498,55 @@ class DAVO(object):
         return self.engine.calibrate(*inputs)
 
     def inference(self, sess=None, mode='pose', inputs=None):
-        """davo.py:1553-1569: -> {'pose': float32 [B,2,6]}; ``sess`` is accepted and ignored."""
-        if mode != 'pose':
-            raise NotImplementedError("mode `%s': only 'pose' is built (davo.py:1555-1556)" % mode)
+        """davo.py:1553-1569.  ``sess`` is accepted and ignored.
+        mode='pose' -> {'pose': float32 [B,2,6]}.
+        mode='feature' (after ``enable_feature_mode()``) -> the reference's dict, float32 throughout, lists in the frame order
+        tgt, src0, src1:
+          'pose'      [B,2,6], bit for bit mode='pose';
+          'masks'     {'attention': 3 x [B,H,W,1], the maps multiplied in (after the tf.ones_like overrides);
+                       'image': 3 x [B,H,W,3], the frames' rgb after masking (the plain rgb where the version masks none);
+                       'att_19': 3 x [B,1,1,19], att_19[f][b,0,0,c] = the value frame f's map takes on class c};
+          'features'  {'rot', 'trans'}: [B,H,W,cnv6_out], resize_bilinear of the tgt->src1 call's cnv6 heads;
+          'images'    3 x [B,H,W,3] preprocessed, unmasked;
+          'seg_19'    3 x [B,H,W,19] one-hot label maps (built on the host, seg_one_hot).
+        Deviations from the reference: 'att_19' is defined for every variant, and a frame whose map the reference overrides
+        with ones reports 19 ones (the reference keeps an se() output there that nothing multiplies in and
+        generate_feature_map.py never reads); 'flows' and 'segs' - colourings of the caller's own inputs - are not built, the
+        keys are absent.  With iterator inputs a 'feature' call first waits for what 'pose' calls have in flight, then takes
+        the iterator's next batch synchronously."""
+        if mode == 'feature' and not self._feature_mode:
+            raise NotImplementedError("mode `feature' is an opt-in: call enable_feature_mode() on this DAVO first (davo.py:1557-1569)")
+        if mode not in ('pose', 'feature'):
+            raise NotImplementedError("mode `%s': only 'pose' and 'feature' are built (davo.py:1555-1569)" % mode)
         if self.engine is None:
             raise DavoError("setup_inference(..., mode='davo') has not been called")
+        if mode == 'feature':
+            return self._inference_feature(inputs)
         if inputs is None and not isinstance(self._inputs, tuple):
             return {'pose': self._next_from_iterator()}
         img, flow, seg, depth = self._split(inputs if inputs is not None else self._inputs)
         if img is None or flow is None or seg is None:
             raise ValueError("image, flow and seglabel inputs are all required for version `%s'" % self.version)
         return {'pose': self.engine.forward(img, flow, seg, depth)}
+
+    def _inference_feature(self, inputs):
+        if inputs is None and not isinstance(self._inputs, tuple):
+            self.engine.wait(0)                                # batches 'pose' calls submitted ahead: delivered into _ahead, in order
+            inputs = next(self._inputs, None)
+            if inputs is None:
+                raise StopIteration("the input iterator is exhausted")
+        img, flow, seg, depth = self._split(inputs if inputs is not None else self._inputs)
+        if img is None or flow is None or seg is None:
+            raise ValueError("image, flow and seglabel inputs are all required for version `%s'" % self.version)
+        r = self.engine.forward_features(img, flow, seg, depth)
+        one_hot = seg_one_hot(seg)                             # [B,3,H,W,19], file order src0, tgt, src1 (davo.py:998-1004)
+        return {'pose': r['pose'],
+                'masks': {'attention': [r['attention'][f][..., None] for f in range(3)],
+                          'image': [r['masked_image'][f] for f in range(3)],
+                          'att_19': [r['att_19'][f][:, None, None, :] for f in range(3)]},
+                'features': {'rot': r['feat_rot'], 'trans': r['feat_trans']},
+                'images': [r['image'][f] for f in range(3)],
+                'seg_19': [one_hot[:, plane] for plane in (1, 0, 2)]}
 
     def _split(self, inputs):
         """(img, flow, seg) or, for a depth-source variant, (img, flow, seg, depth) -> the four, depth None without it."""

@@ -191,6 +191,56 @@ enum { DAVO_PAIRS_SRC0 = 1, DAVO_PAIRS_SRC1 = 2, DAVO_PAIRS_BOTH = 3 };
 int davo_set_pairs(davo_ctx* ctx, int pairs);
 int davo_get_pairs(const davo_ctx* ctx);
 
+/* Feature export.  Replaces DAVO.inference(sess, mode='feature') (davo.py:1553-1569), the call generate_feature_map.py:183-260
+ * makes to draw the class-attention table and the cnv6 feature maps: the poses of davo_forward and, from the same forward, the
+ * tensors of the reference's `masks', `features' and `images' fetches.  Frames are in the order tgt, src0, src1 throughout.
+ *   att_19        [3][B][19]       att_19[f][b][c] is the value frame f's attention map takes on a pixel of class c
+ *                                  (generate_feature_map.py:187-192 reads rows 1 and 2; davo.py:1493 has the fetch commented out).
+ *                                  Where the forward looked a class table up for the frame - the source frames of every table source,
+ *                                  the target where the variant attends it - the row is that table; where the reference overrides the
+ *                                  map with tf.ones_like (the target under -se_flow, `_wo_tgt' and -static, every frame under
+ *                                  -no_segmask: davo.py:1387,1394,1218) it is 19 ones.  (The reference's att_19s holds an se() output
+ *                                  nobody multiplies in there; this entry point reports what was applied.)
+ *   attention     [3][B][H][W]     the maps multiplied in, after those overrides (davo.py:1405-1414,1468): the gather of att_19 through
+ *                                  int(seg), 0 on labels outside [0,19) (one_hot of an out-of-range id, davo.py:1115), 1 everywhere on
+ *                                  an overridden frame
+ *   masked_image  [3][B][H][W][3]  input_images[k][..., :3] after masking (davo.py:1419-1421,1447-1449,1471-1475): the float32
+ *                                  expression the PoseNN input is packed with; the plain rgb where the version does not mask rgb
+ *   image         [3][B][H][W][3]  the preprocessed frames u8 * (1/255) * 2 - 1, unmasked (davo.py:967-971,1519-1522)
+ *   feat_rot,     [B][H][W][cnv6_out] each: tf.image.resize_bilinear(cnv6, (H, W)) of the rotation / translation head of the
+ *   feat_trans                     tgt->src1 PoseNN call (davo.py:1457,1463-1465).  TF 1.13's resize: align_corners=False, no half-pixel
+ *                                  centres, so in = out / 4 exactly (cnv6 is [H/4, W/4] for every shape davo_create accepts),
+ *                                  lo = out >> 2, lerp = (out & 3) / 4, hi = min(lo + 1, last); per value in float32, in TF's order
+ *                                  top = tl + (tr - tl) xl, bot = bl + (br - bl) xl, out = top + (bot - top) yl.  The corners are the
+ *                                  stored cnv6 as davo_debug_read("cnv6") decodes it, so out[4i][4j] equals it to the bit.
+ * `flows' and `segs' of the reference's dict are colourings of the caller's own inputs (flow_to_image, label_to_color_image) and
+ * are not built; `seg_19' is the one-hot of the caller's label maps and needs nothing from the device (davo_amd.DAVO builds it).
+ *
+ * davo_set_feature_export(ctx, 1) allocates the export workspace (room for one davo_forward sub-batch of every tensor above),
+ * davo_set_feature_export(ctx, 0) and davo_destroy free it; it is off by default, and a context that never switches it on
+ * allocates and launches nothing for it.
+ * davo_forward_features takes host pointers like davo_forward (depth: the planes of a depth source as davo_forward_depth takes
+ * them, NULL or ignored for any other variant) and is synchronous.  pose_out receives bit for bit what davo_forward returns on
+ * the same inputs and context state.  Every member of *out that is not NULL receives its tensor for all B windows, whatever
+ * "host_chunk" is; a NULL member is neither computed nor copied, and out == NULL or all members NULL is a plain davo_forward.
+ * The exports come from the forward that produced the returned poses: a batch whose f16x3 range record fails its verdict is
+ * re-issued first (re-calibrated, or on the float32 kernels) and exported from the re-issue, in the precision it ran.
+ * Errors: DAVO_ERR_NOT_READY while the export is off; DAVO_ERR_INVALID unless the pair selection is DAVO_PAIRS_BOTH (the
+ * reference's semantics: features are those of the second pair, maps of all three frames); otherwise davo_forward_depth's.
+ * Works in both precisions, with davo_set_posenn_se (the features are still the stored cnv6, rotation | translation) and with
+ * davo_set_impl(ctx, 1).  There is no streaming (davo_submit) form: this is the visualisation path. */
+int davo_set_feature_export(davo_ctx* ctx, int on);
+typedef struct {
+    float* att_19;
+    float* attention;
+    float* masked_image;
+    float* image;
+    float* feat_rot;
+    float* feat_trans;
+} davo_feature_out;
+int davo_forward_features(davo_ctx* ctx, int B, const uint8_t* img, const float* flow, const float* seg,
+                          const float* depth, float* pose_out, const davo_feature_out* out);
+
 const char* davo_last_error(const davo_ctx* ctx);
 void davo_destroy(davo_ctx* ctx);
 
