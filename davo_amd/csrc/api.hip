@@ -140,13 +140,10 @@ int davo_create(davo_ctx** out, int device, int H, int W, int max_batch, const d
     }
     c->slots.resize(1);
     { int rc = alloc_slot(c, &c->slots[0]); if (rc) return rc; }
-    c->own_stream = c->slots[0].stream;
-    activate_slot(c, 0);
     HIP_TRY(c, hipMalloc(reinterpret_cast<void**>(&c->d_zeros), 256));
     { int rc = zero_now(c, c->d_zeros, 256); if (rc) return rc; }
     HIP_TRY(c, hipMalloc(reinterpret_cast<void**>(&c->d_range_base), (1 + RANGE_RING) * RANGE_WORDS * sizeof(unsigned)));
     { int rc = zero_now(c, c->d_range_base, (1 + RANGE_RING) * RANGE_WORDS * sizeof(unsigned)); if (rc) return rc; }
-    c->d_range = c->d_range_base;
     return DAVO_OK;
 }
 
@@ -169,7 +166,7 @@ int davo_set_posenn_se(davo_ctx* c, int mode) {
         if (mode) { int rc = alloc_se_workspace(c, &s); if (rc) return rc; }
         else free_se_workspace(s);
     }
-    activate_slot(c, 0);
+    c->last_slot = 0;
     return DAVO_OK;
 }
 
@@ -307,14 +304,13 @@ int freeze_pending_and_reset_ring(davo_ctx* c) {
 // calibrates on the pairs the batch ran (an unselected frame's planes may never have been copied: stale bytes).
 int calibrate_on(davo_ctx* c, int B, const Inputs& in, void* d_pose, int sel) {
     int rc = DAVO_OK;
-    const int save_precision = c->precision, save_impl = c->impl;
-    c->precision = 1; c->impl = 0;
-    c->d_range = c->d_range_base;
+    Run run = make_run(c, 0);
+    run.pairs = sel; run.precision = 1; run.impl = 0;
     for (int pass = 0; pass < 8 && rc == DAVO_OK; ++pass) {
-        if ((rc = zero_base_record(c, c->stream))) break;
-        rc = forward_device(c, B, in, d_pose, sel);
+        if ((rc = zero_base_record(c, run.stream))) break;
+        rc = forward_device(c, run, B, in, d_pose);
         if (rc) break;
-        if (hipStreamSynchronize(c->stream) != hipSuccess) { rc = fail(c, DAVO_ERR_HIP, "hipStreamSynchronize failed"); break; }
+        if (hipStreamSynchronize(run.stream) != hipSuccess) { rc = fail(c, DAVO_ERR_HIP, "hipStreamSynchronize failed"); break; }
         unsigned raw[RANGE_WORDS];
         if ((rc = read_record(c, c->d_range_base, raw))) break;
         bool changed = false;
@@ -330,19 +326,18 @@ int calibrate_on(davo_ctx* c, int B, const Inputs& in, void* d_pose, int sel) {
         }
         if (!changed) break;
     }
-    c->precision = save_precision; c->impl = save_impl;
-    (void)zero_base_record(c, c->stream);
+    (void)zero_base_record(c, run.stream);
     return rc;
 }
 
 // one batch, synchronously, on the base record; -> DAVO_OK, DAVO_ERR_RANGE (the verdict) or a hard error
-int run_judged(davo_ctx* c, const Ticket& b) {
-    c->d_range = c->d_range_base;
-    { int rc = zero_base_record(c, c->stream); if (rc) return rc; }
-    int rc = forward_device(c, b.B, b.in, b.pose, b.pairs);
+int run_judged(davo_ctx* c, const Run& run, const Ticket& b) {
+    { int rc = zero_base_record(c, run.stream); if (rc) return rc; }
+    RunResult res;
+    int rc = forward_device(c, run, b.B, b.in, b.pose, &res);
     if (rc) return rc;
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    if (c->last_precision != 1) return DAVO_OK;
+    HIP_TRY(c, hipStreamSynchronize(run.stream));
+    if (!res.h3) return DAVO_OK;
     unsigned raw[RANGE_WORDS];
     if ((rc = read_record(c, c->d_range_base, raw))) return rc;
     rc = check_range(c, raw);
@@ -370,25 +365,24 @@ int recover_batch(davo_ctx* c, const Ticket& orig) {
     if (!c->d_reissue_pose) HIP_TRY(c, hipMalloc(reinterpret_cast<void**>(&c->d_reissue_pose), (size_t)c->max_batch * 12 * sizeof(float)));
     Ticket b = orig;
     b.pose = c->d_reissue_pose;
-    activate_slot(c, 0);
-    int rc = run_judged(c, b);
+    Run run = make_run(c, 0);
+    run.pairs = b.pairs;
+    int rc = run_judged(c, run, b);
     if (rc == DAVO_ERR_RANGE) {
         if ((rc = calibrate_on(c, b.B, b.in, b.pose, b.pairs))) return rc;
         ++c->n_recalibrations;
-        rc = run_judged(c, b);
+        rc = run_judged(c, run, b);
         c->range_report = "re-calibrated: " + verdict;
     }
     if (rc == DAVO_ERR_RANGE) {
-        const int save = c->precision;
-        c->precision = 0;
-        rc = forward_device(c, b.B, b.in, b.pose, b.pairs);
-        c->precision = save;
-        if (rc == DAVO_OK && hipStreamSynchronize(c->stream) != hipSuccess) rc = fail(c, DAVO_ERR_HIP, "hipStreamSynchronize failed");
+        run.precision = 0;
+        rc = forward_device(c, run, b.B, b.in, b.pose);
+        if (rc == DAVO_OK && hipStreamSynchronize(run.stream) != hipSuccess) rc = fail(c, DAVO_ERR_HIP, "hipStreamSynchronize failed");
         ++c->n_f32_batches;
         c->range_report = "float32 kernels for one batch: " + verdict;
     }
     if (rc) return rc;
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    HIP_TRY(c, hipStreamSynchronize(run.stream));
     if (!pose_superseded(c, orig))
         HIP_TRY(c, hipMemcpy(orig.pose, c->d_reissue_pose, (size_t)orig.B * 12 * sizeof(float), hipMemcpyDeviceToDevice));
     ++c->n_reissued;
@@ -481,49 +475,47 @@ int ticket_reserve(davo_ctx* c) {
     return DAVO_OK;
 }
 
-// ... the batch's kernels record into the slot's record; its last kernel keeps the inputs there if the record fails.  *t receives what
-// is known of the batch's ticket now: above all what a re-issue would read
-int ticket_begin(davo_ctx* c, int B, const Inputs& in, Ticket* t, bool own_inputs = false) {
+// ... the batch's kernels record into the slot's record; its last kernel keeps the inputs there if the record fails: *run is told so.
+// *t receives what is known of the batch's ticket now: above all what a re-issue would read
+int ticket_begin(davo_ctx* c, Run* run, int B, const Inputs& in, Ticket* t, bool own_inputs = false) {
     const int r = c->ring_next;
     *t = Ticket{};
-    t->B = B; t->ring = r; t->pairs = c->pairs;
+    t->B = B; t->ring = r; t->pairs = run->pairs; t->stream = run->stream;
     // own_inputs: the batch reads a staging set of the context (davo_submit), which the next batches overwrite whatever the caller declared
     t->snap = c->opt_auto_range && (!c->opt_stable_inputs || own_inputs);
     if (t->snap && (((uintptr_t)in.img | (uintptr_t)in.flow | (uintptr_t)in.seg | (uintptr_t)in.depth) & 15)) return fail(c, DAVO_ERR_INVALID, "device input buffers must be 16-byte aligned");
     { int rc = ensure_ring(c, t->snap); if (rc) return rc; }
-    c->d_range = ring_record(c, r);
-    c->range_zero = true;
+    run->range = ring_record(c, r);
+    run->zero_record = true;
     // The records hold RUNNING maxima (params.h): "clamped" is exact per batch, "too small" is judged on everything a slot has stored
     // since its record was last zeroed.  So that a long stream that never synchronises still notices activations that collapse,
     // every FRESH_EVERY-th batch starts from a zeroed record (a memset in stream order ahead of the batch's kernels; that batch pays
     // its first round's atomics, ~0.2 ms, once in FRESH_EVERY batches).
     if (++c->since_fresh_record >= FRESH_EVERY) {
         c->since_fresh_record = 0;
-        HIP_TRY(c, hipMemsetAsync(c->d_range, 0, 6 * sizeof(unsigned), c->stream));
-        if (c->posenn_se) HIP_TRY(c, hipMemsetAsync(c->d_range + RANGE_SE, 0, sizeof(unsigned), c->stream));
+        HIP_TRY(c, hipMemsetAsync(run->range, 0, 6 * sizeof(unsigned), run->stream));
+        if (c->posenn_se) HIP_TRY(c, hipMemsetAsync(run->range + RANGE_SE, 0, sizeof(unsigned), run->stream));
     }
     if (++c->batch_seq == 0) c->batch_seq = 1;
-    c->snap_seq_issued = t->seq = c->batch_seq;
+    t->seq = c->batch_seq;
     const InputSet keep = t->snap ? c->snap_sets[r] : InputSet();      // no snapshot: no destination, and the ticket remembers the caller's buffers
     t->in = t->snap ? keep.view() : in;
     const PlaneBytes nb = plane_bytes(c);
     auto src = [](const void* q) { return static_cast<const uint8_t*>(q); };
     auto dst = [](void* q) { return static_cast<uint8_t*>(q); };
-    c->snap = SnapArgs{c->d_range, c->h_range_dev + RANGE_WORDS * (1 + r), c->batch_seq,
+    run->snap = SnapArgs{run->range, c->h_range_dev + RANGE_WORDS * (1 + r), c->batch_seq,
                        src(in.img), src(in.flow), src(in.seg), dst(keep.img), dst(keep.flow), dst(keep.seg),
                        (unsigned)(nb.img / 16), (unsigned)(nb.flow / 32), (unsigned)(nb.flow / 16), (unsigned)(nb.seg / 16), B,
                        src(in.depth), dst(keep.depth), c->posenn_se};
     return DAVO_OK;
 }
 
-int ticket_end(davo_ctx* c, int rc, Ticket t, void* d_pose, float* h_pose = nullptr) {
-    c->d_range = c->d_range_base;
-    c->range_zero = false;
-    c->snap = SnapArgs{};
+// the batch is out (rc, res: forward_device's): its ticket is filed
+int ticket_end(davo_ctx* c, int rc, const RunResult& res, Ticket t, void* d_pose, float* h_pose = nullptr) {
     if (rc) return rc;
-    if (c->f32_fallback) ++c->n_f32_batches;
-    if (c->last_precision != 1) return DAVO_OK;                                  // float32 kernels (weight guard): no record, no verdict
-    t.pose = d_pose; t.stream = c->stream; t.h_pose = h_pose; t.issue = c->n_issued;
+    if (res.f32_fallback) ++c->n_f32_batches;
+    if (!res.h3) return DAVO_OK;                                                 // float32 kernels (weight guard): no record, no verdict
+    t.pose = d_pose; t.h_pose = h_pose; t.issue = c->n_issued;
     for (int i = 0; i < 6; ++i) t.shifts[i] = c->act_shift[i];
     c->tickets.push_back(t);
     c->ring_busy[t.ring] = true;
@@ -545,21 +537,20 @@ static int forward_device_entry(davo_ctx* c, int B, const void* d_img, const voi
     const bool ticketed = c->impl == 0 && c->precision == 1;      // f16x3: the batch gets a record (and a copy of its inputs) of its own
     if (ticketed) { int rc = ticket_reserve(c); if (rc) return rc; }
     // rotate through the in-flight slots: this batch runs on its own stream and workspace
-    activate_slot(c, c->next_slot);
+    Run run = make_run(c, c->next_slot);
     c->next_slot = (c->next_slot + 1) % c->inflight;
     Ticket t{};
-    if (ticketed) { int rc = ticket_begin(c, B, in, &t); if (rc) return rc; }
+    if (ticketed) { int rc = ticket_begin(c, &run, B, in, &t); if (rc) return rc; }
     if (!ticketed && c->pose_spans.size() > 64) {          // float32 batches behind pending f16x3 tickets: bounded
         const int rc = judge_all(c);
         if (rc == DAVO_ERR_RANGE) { c->sticky_range_rc = rc; c->sticky_range_err = c->err; }       // "auto_range" 0: reported by the next davo_synchronize
         else if (rc) return rc;
     }
     note_pose_span(c, d_pose, B);
+    RunResult res;
     if (!elapsed_ms) {
-        int rc = forward_device(c, B, in, d_pose, c->pairs);
-        if (ticketed) rc = ticket_end(c, rc, t, d_pose);
-        else if (rc == DAVO_OK && c->f32_fallback) ++c->n_f32_batches;
-        return rc;
+        int rc = forward_device(c, run, B, in, d_pose, &res);
+        return ticketed ? ticket_end(c, rc, res, t, d_pose) : rc;      // (only a ticketed batch starts as f16x3, so only it can fall back)
     }
     hipEvent_t e0 = nullptr, e1 = nullptr;
     int rc = DAVO_OK;
@@ -568,15 +559,15 @@ static int forward_device_entry(davo_ctx* c, int B, const void* d_img, const voi
         return e == hipSuccess;
     };
     if (hip_ok(hipEventCreate(&e0), "hipEventCreate") && hip_ok(hipEventCreate(&e1), "hipEventCreate") &&
-        hip_ok(hipEventRecord(e0, c->stream), "hipEventRecord")) {
-        rc = forward_device(c, B, in, d_pose, c->pairs);
-        if (rc == DAVO_OK && hip_ok(hipEventRecord(e1, c->stream), "hipEventRecord") &&
+        hip_ok(hipEventRecord(e0, run.stream), "hipEventRecord")) {
+        rc = forward_device(c, run, B, in, d_pose, &res);
+        if (rc == DAVO_OK && hip_ok(hipEventRecord(e1, run.stream), "hipEventRecord") &&
             hip_ok(hipEventSynchronize(e1), "hipEventSynchronize"))
             hip_ok(hipEventElapsedTime(elapsed_ms, e0, e1), "hipEventElapsedTime");
     }
     if (e0) (void)hipEventDestroy(e0);
     if (e1) (void)hipEventDestroy(e1);
-    if (ticketed) rc = ticket_end(c, rc, t, d_pose);
+    if (ticketed) rc = ticket_end(c, rc, res, t, d_pose);
     // the timed form is synchronous, so it can judge (and, if need be, re-issue) its own batch; elapsed_ms is the first issue's
     if (rc == DAVO_OK && c->inflight == 1) rc = judge_all(c);
     return rc;
@@ -711,9 +702,9 @@ static int submit_entry(davo_ctx* c, int B, const uint8_t* img, const float* flo
     if (ticketed) { int rc = ticket_reserve(c); if (rc) return rc; }          // may judge - and re-issue - an older batch: before the slot rotation
     const int slot = c->next_slot, pr = (int)(c->n_submitted % STREAM_POSES);
     { int rc = ensure_stream_state(c, slot); if (rc) return rc; }
-    activate_slot(c, slot);
+    Run run = make_run(c, slot);
     c->next_slot = (c->next_slot + 1) % c->inflight;
-    hipStream_t s = c->stream;
+    hipStream_t s = run.stream;
     // H2D on the slot's stream, in order behind the forward that last read this staging set
     const InputSet& set = c->stream_sets[slot];
     { int rc = stage_inputs(c, set, Inputs{img, flow, seg, depth}, 0, B, true, c->pairs, s); if (rc) return rc; }
@@ -723,20 +714,15 @@ static int submit_entry(davo_ctx* c, int B, const uint8_t* img, const float* flo
     if (track_copy) HIP_TRY(c, hipEventRecord(c->st_copied[pr], s));
 
     Ticket t{};
-    if (ticketed) { int rc = ticket_begin(c, B, set.view(), &t, true); if (rc) return rc; }
+    if (ticketed) { int rc = ticket_begin(c, &run, B, set.view(), &t, true); if (rc) return rc; }
     ++c->n_issued;                    // (no pose span: a pose ring entry is not reused before its batch has been delivered)
-    int rc = forward_device(c, B, set.view(), c->d_pose_ring[pr], c->pairs);
-    const unsigned seq = c->snap_seq_issued;
-    bool has_ticket = false;
-    if (ticketed) {
-        const size_t before = c->tickets.size();
-        rc = ticket_end(c, rc, t, c->d_pose_ring[pr], c->h_pose_ring[pr]);
-        has_ticket = c->tickets.size() > before;            // (the weight guard's float32 batches get no ticket)
-    } else if (rc == DAVO_OK && c->f32_fallback) ++c->n_f32_batches;
+    RunResult res;
+    int rc = forward_device(c, run, B, set.view(), c->d_pose_ring[pr], &res);
+    if (ticketed) rc = ticket_end(c, rc, res, t, c->d_pose_ring[pr], c->h_pose_ring[pr]);
     if (rc) return rc;
     HIP_TRY(c, hipMemcpyAsync(c->h_pose_ring[pr], c->d_pose_ring[pr], (size_t)B * 12 * sizeof(float), hipMemcpyDeviceToHost, s));
     HIP_TRY(c, hipEventRecord(c->pose_done[pr], s));
-    c->jobs.push_back(StreamJob{B, pose_out, pr, has_ticket, seq});
+    c->jobs.push_back(StreamJob{B, pose_out, pr, ticketed && res.h3, t.seq});      // (the weight guard's float32 batches get no ticket)
     c->copy_tracked[pr] = track_copy;
     ++c->n_submitted;
     if (track_copy && (unsigned long long)hold < c->n_submitted) {
@@ -799,7 +785,7 @@ bool fx_wanted(const davo_feature_out* o) {
     return o && (o->att_19 || o->attention || o->masked_image || o->image || o->feat_rot || o->feat_trans);
 }
 
-// Windows [w0, w0 + nw) of the forward that last ran on slot 0 - `in' are that forward's device inputs, window 0 - go to windows
+// Windows [w0, w0 + nw) of the last forward - `in' are that forward's device inputs, window 0 - go to windows
 // [b0, b0 + nw) of the caller's arrays of B windows.  Reads d_tab, the inputs and d_act[5] as that forward left them, in the
 // precision it ran (last_precision) and under the storage scale it stored cnv6 with.  Returns with the copies done.
 int export_features(davo_ctx* c, const Inputs& in, int w0, int nw, int b0, int B, const davo_feature_out& out) {
@@ -808,7 +794,8 @@ int export_features(davo_ctx* c, const Inputs& in, int w0, int nw, int b0, int B
     const size_t HW = (size_t)c->H * c->W, c6 = (size_t)c->v.cnv6_out;
     const bool h3 = c->last_precision == 1;
     const FxLayout l = fx_layout(c, c->fx_cap);
-    hipStream_t s = c->stream;
+    const Slot& ws = last_workspace(c);
+    hipStream_t s = last_stream(c);
     for (int p0 = 0; p0 < nw; p0 += c->fx_cap) {
         const int np = std::min(c->fx_cap, nw - p0);
         const Inputs win = from_window(c, in, w0 + p0);
@@ -819,13 +806,13 @@ int export_features(davo_ctx* c, const Inputs& in, int w0, int nw, int b0, int B
         float* const w_rot = out.feat_rot ? c->d_fx + l.rot : nullptr;
         float* const w_trans = out.feat_trans ? c->d_fx + l.trans : nullptr;
         if (w_att19 || w_att || w_masked || w_image) {
-            ProfScope ps(c, "feature_maps");
+            ProfScope ps(c, s, "feature_maps");
             HIP_TRY(c, launch_feature_maps(static_cast<const uint8_t*>(win.img), static_cast<const float*>(win.seg),
-                                           c->d_tab + (size_t)(w0 + p0) * 3 * NCLS, c->v, np, c->H, c->W, w_att19, w_att, w_masked, w_image, s));
+                                           ws.d_tab + (size_t)(w0 + p0) * 3 * NCLS, c->v, np, c->H, c->W, w_att19, w_att, w_masked, w_image, s));
         }
         if (w_rot || w_trans) {
-            ProfScope ps(c, "feature_resize_cnv6");
-            HIP_TRY(c, launch_feature_resize_cnv6(h3, c->d_act[5], w0 + p0, np, c->H2, c->W2, (int)c6, h3 ? ldexpf(1.0f, -c->act_shift[5]) : 1.0f,
+            ProfScope ps(c, s, "feature_resize_cnv6");
+            HIP_TRY(c, launch_feature_resize_cnv6(h3, ws.d_act[5], w0 + p0, np, c->H2, c->W2, (int)c6, h3 ? ldexpf(1.0f, -c->act_shift[5]) : 1.0f,
                                                   w_rot, w_trans, s));
         }
         // the caller's per-frame arrays are [3][B][...], the workspace's [3][np][...]: one copy per frame
@@ -861,15 +848,13 @@ static int forward_entry(davo_ctx* c, int B, const uint8_t* img, const float* fl
     HIP_TRY(c, hipSetDevice(c->device));
     { int rc = deliver_all(c); if (rc) return rc; }          // davo_submit batches still under way: delivered first
     { int rc = sync_all_slots(c); if (rc) return rc; }       // the host path owns the single staging buffer set
-    activate_slot(c, 0);
     if (!c->host_set.img) {
         { int rc = alloc_input_set(c, &c->host_set, false); if (rc) return rc; }
         HIP_TRY(c, hipMalloc(&c->s_pose, (size_t)c->max_batch * 12 * sizeof(float)));
     }
     if (!c->copy_stream) HIP_TRY(c, hipStreamCreateWithFlags(&c->copy_stream, hipStreamNonBlocking));
     { int rc = judge_all(c); if (rc) return rc; }               // device-path batches issued before this call
-    activate_slot(c, 0);
-    c->d_range = c->d_range_base;
+    Run run = make_run(c, 0);                                   // slot 0, the base record
     // The base record holds RUNNING maxima like the ring's records (params.h): a record that starts at zero is raised by every wave of
     // every kernel's first round, and at batch 1 - the reference's operating point - those serialised atomics were 200 us of this
     // call's 417.  "Clamped" stays exact per call (the call that pushes a maximum past 65504 fails, and every recovery path zeroes
@@ -877,7 +862,7 @@ static int forward_entry(davo_ctx* c, int B, const uint8_t* img, const float* fl
     // and every FRESH_EVERY-th call.
     if (++c->host_since_fresh >= FRESH_EVERY) {
         c->host_since_fresh = 0;
-        HIP_TRY(c, hipMemsetAsync(c->d_range_base, 0, RANGE_WORDS * sizeof(unsigned), c->stream));
+        HIP_TRY(c, hipMemsetAsync(c->d_range_base, 0, RANGE_WORDS * sizeof(unsigned), run.stream));
     }
     // Sub-batches: the copy of chunk i+1 (copy_stream) overlaps the kernels of chunk i (compute stream).
     // Results do not depend on the split (windows are independent; tests/test_hip_parity.py batch invariance).
@@ -890,6 +875,7 @@ static int forward_entry(davo_ctx* c, int B, const uint8_t* img, const float* fl
         c->copy_done.push_back(e);
     }
     bool f32_fallback = false;
+    RunResult res;
     // Batch 1 is the reference's own operating point (run_inference.sh:44-51), and there this call was 474 us around 129 us of kernels
     // (round 5).  What went: the copy stream and its event for a call that is a single sub-batch (the copies go on the compute
     // stream itself); the read-back of the range record on a stream of its own behind the synchronise (the call's last kernel mirrors
@@ -901,22 +887,20 @@ static int forward_entry(davo_ctx* c, int B, const uint8_t* img, const float* fl
     unsigned seq = 0;
     for (int i = 0; i < nchunks; ++i) {
         const int b0 = i * chunk, nb = std::min(chunk, B - b0);
-        hipStream_t cs = nchunks == 1 ? c->stream : c->copy_stream;
+        hipStream_t cs = nchunks == 1 ? run.stream : c->copy_stream;
         { int rc = stage_inputs(c, c->host_set, Inputs{img, flow, seg, depth}, b0, nb, false, c->pairs, cs); if (rc) return rc; }      // both pairs: the label maps whole
         if (nchunks > 1) {
             HIP_TRY(c, hipEventRecord(c->copy_done[i], c->copy_stream));
-            HIP_TRY(c, hipStreamWaitEvent(c->stream, c->copy_done[i], 0));
+            HIP_TRY(c, hipStreamWaitEvent(run.stream, c->copy_done[i], 0));
         }
         if (h3_call && i == nchunks - 1) {       // the call's last kernel mirrors the finished record (all sub-batches) to the host
             if (++c->batch_seq == 0) c->batch_seq = 1;
             seq = c->batch_seq;
-            c->snap = SnapArgs{};
-            c->snap.record = c->d_range_base; c->snap.host_mirror = c->h_range_dev; c->snap.seq = seq; c->snap.B = nb; c->snap.se = c->posenn_se;
+            run.snap.record = c->d_range_base; run.snap.host_mirror = c->h_range_dev; run.snap.seq = seq; run.snap.B = nb; run.snap.se = c->posenn_se;
         }
-        int rc = forward_device(c, nb, from_window(c, c->host_set.view(), b0), (float*)c->s_pose + (size_t)b0 * 12, c->pairs);
-        c->snap = SnapArgs{};
+        int rc = forward_device(c, run, nb, from_window(c, c->host_set.view(), b0), (float*)c->s_pose + (size_t)b0 * 12, &res);
         if (rc) return rc;
-        f32_fallback |= c->f32_fallback;
+        f32_fallback |= res.f32_fallback;
         // feature export: the context holds one sub-batch's activations, so every sub-batch but the last is exported before the next
         // one runs; the last one waits for the verdict below
         if (fx && i < nchunks - 1 && (rc = export_features(c, from_window(c, c->host_set.view(), b0), 0, nb, b0, B, *fx))) return rc;
@@ -924,10 +908,10 @@ static int forward_entry(davo_ctx* c, int B, const uint8_t* img, const float* fl
     const int last_b0 = (nchunks - 1) * chunk;
     auto export_last = [&]() { return fx ? export_features(c, from_window(c, c->host_set.view(), last_b0), 0, B - last_b0, last_b0, B, *fx) : DAVO_OK; };
     if (f32_fallback) ++c->n_f32_batches;                      // once per call, not per sub-batch
-    HIP_TRY(c, hipMemcpyAsync(c->h_sync_pose, c->s_pose, (size_t)B * 12 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    HIP_TRY(c, hipMemcpyAsync(c->h_sync_pose, c->s_pose, (size_t)B * 12 * sizeof(float), hipMemcpyDeviceToHost, run.stream));
+    HIP_TRY(c, hipStreamSynchronize(run.stream));
     memcpy(pose_out, c->h_sync_pose, (size_t)B * 12 * sizeof(float));
-    if (c->last_precision != 1) return export_last();
+    if (!res.h3) return export_last();
     unsigned raw[RANGE_WORDS];
     int rc = DAVO_OK;
     if (seq && __atomic_load_n(&c->h_range[RANGE_SEQ], __ATOMIC_ACQUIRE) == seq) memcpy(raw, c->h_range, sizeof raw);      // the stream is idle: the mirror is final
@@ -937,7 +921,7 @@ static int forward_entry(davo_ctx* c, int B, const uint8_t* img, const float* fl
     if (rc == DAVO_OK) note_seen(c, raw, c->act_shift);
     if (rc == DAVO_ERR_RANGE && c->opt_auto_range) {
         // the staged copy of the batch is still in HBM: re-issue it whole (recalibrated, or on the float32 kernels)
-        rc = recover_batch(c, [&] { Ticket t{}; t.B = B; t.pairs = c->pairs; t.in = c->host_set.view(); t.pose = c->s_pose; t.ring = -1; t.stream = c->stream; t.issue = ~0ull; return t; }());
+        rc = recover_batch(c, [&] { Ticket t{}; t.B = B; t.pairs = c->pairs; t.in = c->host_set.view(); t.pose = c->s_pose; t.ring = -1; t.stream = run.stream; t.issue = ~0ull; return t; }());
         if (rc == DAVO_OK) HIP_TRY(c, hipMemcpy(pose_out, c->s_pose, (size_t)B * 12 * sizeof(float), hipMemcpyDeviceToHost));
         // the re-issue ran the whole batch as one forward and produced the poses returned: every window's exports come from it, in
         // the precision and under the scales it ran with (what the sub-batches exported above is overwritten)
@@ -1029,8 +1013,6 @@ int davo_reset_range_state(davo_ctx* c) {
     c->host_since_fresh = 1 << 30;                                           // the counters' and the cursor's initial values (ctx.h)
     c->since_fresh_record = 0;
     c->ring_next = 0;
-    c->d_range = c->d_range_base;
-    c->range_zero = false;
     c->sticky_range_rc = 0; c->sticky_range_err.clear();
     c->range_report.clear();
     if (verdict) { c->err = verdict_err; return verdict; }
@@ -1047,7 +1029,6 @@ static int calibrate_entry(davo_ctx* c, int B, const void* d_img, const void* d_
     HIP_TRY(c, hipSetDevice(c->device));
     { int rc = judge_all(c); if (rc) return rc; }             // batches issued under the old scales get their verdict first
     { int rc = freeze_pending_and_reset_ring(c); if (rc) return rc; }
-    activate_slot(c, 0);
     float* d_pose = nullptr;
     HIP_TRY(c, hipMalloc(reinterpret_cast<void**>(&d_pose), (size_t)B * 12 * sizeof(float)));
     const int rc = calibrate_on(c, B, Inputs{d_img, d_flow, d_seg, d_depth}, d_pose, PAIRS_BOTH);
@@ -1132,15 +1113,15 @@ int davo_device_free(davo_ctx* c, void* p) {
 int davo_memcpy_h2d(davo_ctx* c, void* dst, const void* src, size_t bytes) {
     if (!c) return DAVO_ERR_INVALID;
     HIP_TRY(c, hipSetDevice(c->device));
-    HIP_TRY(c, hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    HIP_TRY(c, hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, last_stream(c)));
+    HIP_TRY(c, hipStreamSynchronize(last_stream(c)));
     return DAVO_OK;
 }
 int davo_memcpy_d2h(davo_ctx* c, void* dst, const void* src, size_t bytes) {
     if (!c) return DAVO_ERR_INVALID;
     HIP_TRY(c, hipSetDevice(c->device));
-    HIP_TRY(c, hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    HIP_TRY(c, hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, last_stream(c)));
+    HIP_TRY(c, hipStreamSynchronize(last_stream(c)));
     return DAVO_OK;
 }
 int davo_synchronize(davo_ctx* c) {
@@ -1160,8 +1141,8 @@ int davo_set_stream(davo_ctx* c, void* hip_stream) {
     HIP_TRY(c, hipSetDevice(c->device));
     { int rc = deliver_all(c); if (rc) return rc; }
     { int rc = judge_all(c); if (rc) return rc; }
-    c->user_stream = hip_stream != nullptr;
-    c->stream = hip_stream ? static_cast<hipStream_t>(hip_stream) : c->own_stream;
+    c->user_stream = static_cast<hipStream_t>(hip_stream);
+    c->last_slot = 0;
     return DAVO_OK;
 }
 
@@ -1236,14 +1217,13 @@ static int rebuild_slot_streams(davo_ctx* c, int n) {
             HIP_TRY(c, hipStreamCreateWithFlags(&s.stream, hipStreamNonBlocking));
         }
     }
-    c->own_stream = c->slots[0].stream;
     c->ncu = (c->cu_partition && n > 1 && c->dev_cus == 256) ? 256 / n : c->dev_cus;
-    activate_slot(c, 0);
+    c->last_slot = 0;
     return DAVO_OK;
 }
 
 int davo_set_inflight(davo_ctx* c, int n) {
-    if (!c || n < 1 || n > 4) return fail(c, DAVO_ERR_INVALID, "inflight must be 1..4");
+    if (!c || n < 1 || n > MAX_INFLIGHT) return fail(c, DAVO_ERR_INVALID, "inflight must be 1..4");
     if (n > 1 && c->user_stream) return fail(c, DAVO_ERR_INVALID, "in-flight slots use the context's own streams: clear davo_set_stream first");
     HIP_TRY(c, hipSetDevice(c->device));
     { int rc = deliver_all(c); if (rc) return rc; }
@@ -1331,24 +1311,25 @@ int davo_debug_read(davo_ctx* c, const char* tensor, float* host_out, size_t n_f
     const float* src = nullptr;
     size_t n = 0;
     const std::string t = tensor;
-    if (t == "att_table") { src = c->d_tab; n = (size_t)c->last_B * 3 * NCLS; }
+    const Slot& ws = last_workspace(c);
+    if (t == "att_table") { src = ws.d_tab; n = (size_t)c->last_B * 3 * NCLS; }
     else if (t == "cnv5_se_scale" || t == "cnv5_se") {      // feature attention (posenn_se.h): [2B][2][256] s_r | s_r s_t; [2B][H2][W2][512] rotation | translation input of cnv6
         if (!c->posenn_se) return fail(c, DAVO_ERR_NOT_READY, "`%s' exists in the feature-attention variant only (davo_set_posenn_se)", tensor);
-        if (t == "cnv5_se") { src = c->d_se; n = NB * c->H2 * c->W2 * 512; }
-        else { src = c->d_se_scale; n = NB * 2 * 256; }
+        if (t == "cnv5_se") { src = ws.d_se; n = NB * c->H2 * c->W2 * 512; }
+        else { src = ws.d_se_scale; n = NB * 2 * 256; }
     }
     else if (t == "packed") {
         if (!c->packed_valid) {          // fused path: materialise the packed tensor on demand from the last inputs
             HIP_TRY(c, launch_mask_pack(16, static_cast<const uint8_t*>(c->last_in.img), static_cast<const float*>(c->last_in.flow),
-                                        static_cast<const float*>(c->last_in.seg), c->d_tab, c->v, c->last_B, c->H, c->W, c->d_packed, c->last_pairs, c->stream));
+                                        static_cast<const float*>(c->last_in.seg), ws.d_tab, c->v, c->last_B, c->H, c->W, ws.d_packed, c->last_pairs, last_stream(c)));
             c->packed_valid = true;
         }
-        src = c->d_packed; n = NB * c->H * c->W * c->packed_ld;
+        src = ws.d_packed; n = NB * c->H * c->W * c->packed_ld;
     }
     else {
         const char* names[7] = {"cnv1", "cnv2", "cnv3", "cnv4", "cnv5", "cnv6", "cnv7"};
         for (int i = 0; i < 7; ++i)
-            if (t == names[i]) { src = c->d_act[i]; n = NB * c->act_floats_per_img[i]; }
+            if (t == names[i]) { src = ws.d_act[i]; n = NB * c->act_floats_per_img[i]; }
     }
     if (t == "pose_tiles") {          // the fused pose head's per-tile partial sums of the last batch (slot 0's region)
         if (c->cnv7_valid || !c->d_pose_tiles) return fail(c, DAVO_ERR_NOT_READY, "the pose head did not run fused");

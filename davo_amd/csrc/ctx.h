@@ -13,6 +13,12 @@
 //   launch_misc.hip prologue / pose head / cnv1..cnv3 patch / feature-attention (posenn_se.h) / direct-convolution kernels + dispatch
 //   launch_feature.hip  the feature export kernels (feature_export.h) + dispatch
 //   comm.hip        RCCL communicator behind the C ABI (pose gather of the window-sharded driver)
+//
+// A forward's inputs.  forward_device(c, run, B, in, d_pose, &res) reads the context for what lasts (geometry, weights, options,
+// storage scales, the slots' workspaces); what belongs to the batch travels in one argument, `run' (struct Run below): its slot and
+// stream, its range record, its snapshot arguments, its pair selection and its arithmetic mode.  The entry point builds it on its
+// stack, so nothing is set on the context before a forward or put back after it; `res' says what really ran, and what the context
+// keeps of a forward is reported state (last_*), which no forward reads.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -61,6 +67,7 @@ struct ProfEntry {
 constexpr size_t PROF_SAMPLES_CAP = 8192;
 
 // One in-flight batch: its own HIP stream and activation workspace.  Weights are shared.
+constexpr int MAX_INFLIGHT = 4;                  // slots a context rotates through at most (davo_set_inflight; the per-slot scratch and staging sets are sized by it)
 struct Slot {
     hipStream_t stream = nullptr;
     float *d_partial = nullptr, *d_tab = nullptr, *d_packed = nullptr, *d_pose_partial = nullptr;
@@ -104,15 +111,32 @@ struct Ticket {
 };
 
 // A batch davo_submit has issued whose poses have not been delivered to the caller's array yet (api.hip: streaming entry point).
-// Its inputs live in the staging set of its in-flight slot (at most STREAM_SETS slots), its poses in entry `pr` of a ring of STREAM_POSES device
+// Its inputs live in the staging set of its in-flight slot (at most MAX_INFLIGHT slots), its poses in entry `pr` of a ring of STREAM_POSES device
 // buffers with page-locked host twins, so neither a re-issue nor the caller's buffer recycling can touch another batch's data.
-constexpr int STREAM_SETS = 4, STREAM_POSES = 8;
+constexpr int STREAM_POSES = 8;
 struct StreamJob {
     int B;
     float* pose_out;                           // the caller's [B,2,6] (pageable is fine: written by the host at delivery)
     int pr;                                    // pose ring entry
     bool ticketed;                             // has a range ticket (f16x3) that must be judged before delivery
     unsigned seq;                              // ... its sequence number
+};
+
+// How one batch runs.  The entry point (api.hip) fills one on its stack and forward_device hands it down to every layer runner:
+// the forward is a function of (context, Run, batch), and no entry point leaves anything behind on the context for it.
+struct Run {
+    int slot = 0;                              // the in-flight slot: its workspace is c->slots[slot], its per-slot scratch region `slot`
+    hipStream_t stream = nullptr;              // slot_stream(c, slot): every launch, memset and copy of the batch goes here
+    unsigned* range = nullptr;                 // f16x3: the range record the storing epilogues raise (d_range_base or one of the ring's)
+    bool zero_record = false;                  // ... and whether the forward's first kernel zeroes it (ticketed device-path batches)
+    SnapArgs snap{};                           // ticketed batches: the last kernel copies the inputs if the record fails (prologue.h)
+    int pairs = PAIRS_BOTH;                    // pair selection (params.h): the context's for a new batch, the ticket's for a re-issue
+    int precision = 1, impl = 0;               // the arithmetic of THIS run (calibration and the float32 re-issue differ from the context's)
+};
+// What forward_device reports back: the arithmetic it really ran
+struct RunResult {
+    bool h3 = false;                           // f16x3 kernels: the record holds this batch's maxima
+    bool f32_fallback = false;                 // float32 kernels because of the weight guard (counted once per API call by the caller)
 };
 
 struct PoseSpan { uintptr_t lo, hi; unsigned long long issue; };      // the pose buffer range of an issued batch (api.hip: pose_superseded)
@@ -128,7 +152,7 @@ struct davo_ctx {
     int dev_cus = 256;                         // compute units of the device (hipDeviceProp_t::multiProcessorCount, read by davo_create)
     int ncu = 256;                             // compute units a launch of this context may use (CU-masked slot streams: dev_cus / slots)
     bool cu_partition = false;                 // davo_set_option "cu_partition": slot i's stream is masked to its own share of every XCD's CUs
-    bool user_stream = false;
+    hipStream_t user_stream = nullptr;         // davo_set_stream: the caller's stream, which slot 0 then runs on (null: the slot's own)
     bool opt_fuse_pose = true;                 // f16x3: pose head fused into cnv7's epilogue (davo_set_option)
     int opt_fuse_pack = -1;                    // f16x3: mask+pack fused into cnv1's patch fill: 0 off | 1 on | -1 where it pays (small batches: one launch fewer)
     bool opt_patch_cnv2 = true;                // f16x3: cnv2 from an LDS-staged input patch (conv_patch_cnv2_h3) instead of the implicit GEMM
@@ -149,7 +173,7 @@ struct davo_ctx {
     bool opt_fold_fixup = false;               // f16x3 split-K: the part that finishes a tile last adds its partial sums (no splitk_fixup launch); needs xcd_rr > 0.  Measured slower (batch 1: 0.141 against 0.132 ms): off
     int xcd_rr = -1;                           // workgroups (x, y) of a grid whose x extent is a multiple of 8 share an XCD for every y: -1 not probed yet | 0 no | 1 yes
     bool opt_split_k = true;                   // f16x3: cnv5 / cnv6 launches of at most half a workgroup per CU split their K loop in two (forward.hip)
-    float* d_splitk = nullptr;                 // split-K partial sums [4 slots][M][2][N] float32
+    float* d_splitk = nullptr;                 // split-K partial sums [MAX_INFLIGHT slots][M][2][N] float32
     size_t splitk_floats = 0;                  // ... per slot
     float* d_pose_tiles = nullptr;             // per-tile partial sums of the fused pose head
     size_t pose_tiles_floats = 0;
@@ -162,8 +186,6 @@ struct davo_ctx {
     bool packed_h_ready = false;
     int weight_channel_spread_log2 = 0;        // largest log2 spread of the per-input-channel weight norms over cnv2..cnv7 (weights.hip)
     std::string weight_channel_spread_layer;   // ... and the tensor that has it
-    int last_precision = 0;
-    hipStream_t own_stream = nullptr, stream = nullptr;
     std::string err;
     std::map<std::string, davo::HostTensor> weights;
     std::vector<std::string> needed;
@@ -178,18 +200,17 @@ struct davo_ctx {
     uint8_t* d_w3patch = nullptr;              // cnv3 B fragments for conv_patch_cnv3_h3
     // geometry
     int H1, W1, H2, W2, H3, W3;
-    // workspace
-    float *d_partial = nullptr, *d_tab = nullptr, *d_packed = nullptr, *d_zeros = nullptr, *d_pose_partial = nullptr;
-    unsigned* d_counters = nullptr;            // the active slot's ticket counters
-    float *d_se = nullptr, *d_se_scale = nullptr, *d_se_partial = nullptr;      // ... and its feature-attention workspace
-    float* d_act[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    float* d_zeros = nullptr;
     size_t act_floats_per_img[7];
     int act_ch[7];
-    int packed_ld = 8;
-    int last_B = 0;
     int pairs = davo::PAIRS_BOTH;              // davo_set_pairs: the pairs of every window the batches issued from now on run
-    int run_pairs = davo::PAIRS_BOTH;          // ... of the batch forward_device is issuing (the layer runners read it)
-    int last_pairs = davo::PAIRS_BOTH;         // ... of the last forward: davo_debug_read sizes its tensors by last_B windows of that many pair images
+    // The last forward, as reported: written by forward_device, read by davo_debug_read / davo_last_plan / the feature export
+    // alone (last_slot also by last_stream() below) - never an input of a forward
+    int last_slot = 0;                         // its slot; 0 again after davo_create, davo_set_posenn_se, davo_set_stream and a rebuild of the slot streams
+    int last_B = 0;
+    int last_pairs = davo::PAIRS_BOTH;         // davo_debug_read sizes its tensors by last_B windows of that many pair images
+    int last_precision = 0;
+    int packed_ld = 8;
     bool packed_valid = true;                  // false when cnv1 consumed the raw inputs directly (fused)
     davo::Inputs last_in{};                    // the last forward's inputs: davo_debug_read("packed") re-packs from them after a fused cnv1
     int last_plan[7][2] = {};                  // per layer, per launch: 128-row M tiles * 1000 + tile id / BN (reported by the bench)
@@ -201,11 +222,9 @@ struct davo_ctx {
     hipStream_t copy_stream = nullptr;         // H2D of the next sub-batch runs here while the previous one computes
     std::vector<hipEvent_t> copy_done;
     // f16x3 range management: activations are stored as fp16 pairs scaled by 2^act_shift[layer] (davo_calibrate);
-    // every storing epilogue atomicMax-es the largest stored magnitude into d_range[layer]
+    // every storing epilogue atomicMax-es the largest stored magnitude into word `layer' of the run's record (Run::range)
     int act_shift[7] = {0, 0, 0, 0, 0, 0, 0};
     unsigned* d_range_base = nullptr;          // [1 + RANGE_RING][RANGE_WORDS] (params.h): record 0 serves the host path, calibration and re-issues; 1.. the ring
-    unsigned* d_range = nullptr;               // the record the next launches write to (one of the above)
-    bool range_zero = false;                   // the next forward's first kernel zeroes that record itself (ticketed device-path batches)
     // Range recovery (davo_set_option "auto_range", default on): every device-path batch is judged on a record of its own, at the
     // latest when its ring slot is needed again (RANGE_RING batches later) or at davo_synchronize; a failed verdict re-issues that
     // batch from the context's own copy of its inputs - recalibrated, or on the float32 kernels (api.hip)
@@ -215,15 +234,13 @@ struct davo_ctx {
     bool ring_busy[davo::RANGE_RING] = {};
     int ring_next = 0;
     davo::InputSet snap_sets[davo::RANGE_RING];        // the ring slots' input snapshots (allocated by the first ticket that wants one)
-    davo::SnapArgs snap{};                     // set around a ticketed batch: its last kernel copies the inputs if the record fails (prologue.h)
     hipStream_t read_stream = nullptr;
-    unsigned batch_seq = 0, snap_seq_issued = 0;   // sequence number of the last ticketed batch (never 0 for a batch)
+    unsigned batch_seq = 0;                    // sequence number of the last ticketed batch (never 0 for a batch)
     unsigned* h_range = nullptr;               // page-locked: [0] landing pad of a record read, [1 + r] the mirror ring slot r's last kernel writes
     unsigned* h_range_dev = nullptr;           // ... as the device sees it
     float range_seen[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};      // largest true |activation| judged since the last reset
     int sticky_range_rc = 0;                   // "auto_range" 0: a failed verdict met while issuing is reported by the next davo_synchronize
     std::string sticky_range_err;
-    bool f32_fallback = false;                 // the last forward_device ran the float32 kernels because of the weight guard
     std::string range_report;                  // what the range management last did, in words (davo_range_report)
     long long n_recalibrations = 0, n_f32_batches = 0, n_reissued = 0;
     int host_chunk = 8;                        // davo_forward: windows per sub-batch (davo_set_option "host_chunk"; 0 = whole batch)
@@ -233,7 +250,7 @@ struct davo_ctx {
     float* d_fx = nullptr;
     int fx_cap = 0;
     // streaming host entry (davo_submit / davo_wait): staging input sets, pose ring, undelivered batches in issue order
-    davo::InputSet stream_sets[davo::STREAM_SETS];     // one staging set per in-flight slot (allocated by the slot's first davo_submit)
+    davo::InputSet stream_sets[davo::MAX_INFLIGHT];     // one staging set per in-flight slot (allocated by the slot's first davo_submit)
     hipEvent_t st_copied[davo::STREAM_POSES] = {};             // "the H2D copies of the batch in pose ring entry k are done" (recorded only for hold < STREAM_POSES)
     bool copy_tracked[davo::STREAM_POSES] = {};
     float *d_pose_ring[davo::STREAM_POSES] = {}, *h_pose_ring[davo::STREAM_POSES] = {};
@@ -300,12 +317,23 @@ inline int ilog2_exact(int v) {
     return (1 << l) == v ? l : -1;
 }
 
-// ---- profiling: HIP events around a launch on the launch stream -----------------------------
+// the stream slot i runs on: its own, or the caller's for slot 0 (davo_set_stream)
+inline hipStream_t slot_stream(const davo_ctx* c, int i) { return (c->user_stream && i == 0) ? c->user_stream : c->slots[i].stream; }
+// a batch in slot i as the context's settings of the moment say, on the base record (api.hip: ticket_begin moves it to a record of its own)
+inline Run make_run(const davo_ctx* c, int i) {
+    return Run{i, slot_stream(c, i), c->d_range_base, false, SnapArgs{}, c->pairs, c->precision, c->impl};
+}
+// outside a forward (davo_memcpy_*, davo_debug_read, the feature export): the stream and workspace of the most recently issued batch
+inline hipStream_t last_stream(const davo_ctx* c) { return slot_stream(c, c->last_slot); }
+inline const Slot& last_workspace(const davo_ctx* c) { return c->slots[c->last_slot]; }
+
+// ---- profiling: HIP events around a launch on stream s ---------------------------------------
 struct ProfScope {
     davo_ctx* c;
+    hipStream_t s;
     ProfEntry* e = nullptr;
     hipEvent_t a = nullptr, b = nullptr;
-    ProfScope(davo_ctx* ctx, const char* name);
+    ProfScope(davo_ctx* ctx, hipStream_t stream, const char* name);
     ~ProfScope();
 };
 int prof_collect(davo_ctx* c);
@@ -337,10 +365,9 @@ inline void split_f16(float v, _Float16* hi, _Float16* lo) {
 }
 
 // ---- forward.hip ----------------------------------------------------------------------------
-void activate_slot(davo_ctx* c, int i);
-// sel: the batch's pair selection (params.h: PAIRS_*) - the context's for a new batch, the ticket's for a re-issue
-int forward_device(davo_ctx* c, int B, const Inputs& in, void* d_pose, int sel);
-// f16x3: verdict on the range record (d_range) read back from the device; DAVO_ERR_RANGE names the layer
+// B windows of `in' -> d_pose, run as `run' says; *res (if not null) receives what really ran
+int forward_device(davo_ctx* c, const Run& run, int B, const Inputs& in, void* d_pose, RunResult* res = nullptr);
+// f16x3: verdict on a range record read back from the device; DAVO_ERR_RANGE names the layer
 int check_range(davo_ctx* c, const unsigned* raw /*[RANGE_WORDS]*/, const int* shifts = nullptr);
 
 // ---- comm.hip -------------------------------------------------------------------------------

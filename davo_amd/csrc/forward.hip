@@ -21,7 +21,7 @@
 namespace davo {
 
 // ---- profiling ------------------------------------------------------------------------------------
-ProfScope::ProfScope(davo_ctx* ctx, const char* name) : c(ctx) {
+ProfScope::ProfScope(davo_ctx* ctx, hipStream_t stream, const char* name) : c(ctx), s(stream) {
     if (!c->prof) return;
     if (c->prof_dominant_only) {
         if (strcmp(name, "cnv6") != 0) return;
@@ -41,12 +41,12 @@ ProfScope::ProfScope(davo_ctx* ctx, const char* name) : c(ctx) {
         return ev;
     };
     a = get(); b = get();
-    if (a) (void)hipEventRecord(a, c->stream);
+    if (a) (void)hipEventRecord(a, s);
 }
 
 ProfScope::~ProfScope() {
     if (!e) return;
-    if (b) (void)hipEventRecord(b, c->stream);
+    if (b) (void)hipEventRecord(b, s);
     if (a && b) e->pending.emplace_back(a, b);
     else {                                    // half a pair is of no use: back to the pool
         if (a) c->event_pool.push_back(a);
@@ -56,7 +56,7 @@ ProfScope::~ProfScope() {
 
 int sync_all_slots(davo_ctx* c) {
     for (auto& s : c->slots) HIP_TRY(c, hipStreamSynchronize(s.stream));
-    if (c->user_stream) HIP_TRY(c, hipStreamSynchronize(c->stream));
+    if (c->user_stream) HIP_TRY(c, hipStreamSynchronize(c->user_stream));
     return DAVO_OK;
 }
 
@@ -80,16 +80,6 @@ int prof_collect(davo_ctx* c) {
         pe.pending.clear();
     }
     return DAVO_OK;
-}
-
-// bind a slot's stream and workspace to the members every launch helper uses
-void activate_slot(davo_ctx* c, int i) {
-    const Slot& s = c->slots[i];
-    if (!(c->user_stream && i == 0)) c->stream = s.stream;
-    c->d_partial = s.d_partial; c->d_tab = s.d_tab; c->d_packed = s.d_packed; c->d_pose_partial = s.d_pose_partial;
-    c->d_counters = s.d_counters;
-    c->d_se = s.d_se; c->d_se_scale = s.d_se_scale; c->d_se_partial = s.d_se_partial;
-    for (int k = 0; k < 7; ++k) c->d_act[k] = s.d_act[k];
 }
 
 // f16x3 only.  Stored activations (fp16 hi/lo pairs) are float32-grade while the layer's largest stored value is
@@ -173,23 +163,21 @@ const int* tile_order_for(davo_ctx* c, int li, int kind, int bm, int mtile0, int
 }
 
 // ---- per-slot scratch -------------------------------------------------------------------------------
-int slot_idx(const davo_ctx* c) { return (c->next_slot + c->inflight - 1) % c->inflight; }      // the slot this batch runs in
-
 // A scratch buffer of the context with one region of *floats floats per in-flight slot: grown (behind every stream) if this launch
-// needs more per slot than it has, then -> the region of this batch's slot.  extra_bytes: room behind the four regions.
-int slot_scratch(davo_ctx* c, float** buf, size_t* floats, size_t need, float** region, size_t extra_bytes = 0) {
+// needs more per slot than it has, then -> the region of this batch's slot.  extra_bytes: room behind the regions.
+int slot_scratch(davo_ctx* c, const Run& run, float** buf, size_t* floats, size_t need, float** region, size_t extra_bytes = 0) {
     if (need > *floats) {
         if (*buf) { int rs = sync_all_slots(c); if (rs) return rs; HIP_TRY(c, hipFree(*buf)); *buf = nullptr; }
-        HIP_TRY(c, hipMalloc(reinterpret_cast<void**>(buf), need * sizeof(float) * 4 + extra_bytes));   // x4: one region per in-flight slot
+        HIP_TRY(c, hipMalloc(reinterpret_cast<void**>(buf), need * sizeof(float) * MAX_INFLIGHT + extra_bytes));   // one region per in-flight slot
         *floats = need;
     }
-    *region = *buf + (size_t)slot_idx(c) * *floats;
+    *region = *buf + (size_t)run.slot * *floats;
     return DAVO_OK;
 }
 
 // ---- one conv layer, FP32-MFMA path ---------------------------------------------------------------
 // fuse_pose (cnv7): the pose head runs in the epilogue (conv_igemm.h); *pose_mt receives the layer's M tiles
-int run_conv_layer(davo_ctx* c, int li, const float* x, int x_ld, int Hin, int Win, float* y, int y_ld, int NB, bool fuse_pose = false, int* pose_mt = nullptr) {
+int run_conv_layer(davo_ctx* c, const Run& run, int li, const float* x, int x_ld, int Hin, int Win, float* y, int y_ld, int NB, bool fuse_pose = false, int* pose_mt = nullptr) {
     const ConvLayer& L = c->L[li];
     ConvParams p{};
     int Ho, Wo, pt, pl;
@@ -209,7 +197,7 @@ int run_conv_layer(davo_ctx* c, int li, const float* x, int x_ld, int Hin, int W
     std::vector<Launch> plan = plan_layer(mtiles, L.npad, L.groups, c->ncu);
     if (li == 0 && L.cout <= 16 && c->opt_f32_n16) plan = {{0, mtiles, 16}};      // cnv1 on the 128x16 tile at every batch size (conv_igemm.h, N16)
     if (fuse_pose) {
-        { int rs = slot_scratch(c, &c->d_pose_tiles, &c->pose_tiles_floats, (size_t)L.groups * mtiles * 8 * 6, &p.pose_partial); if (rs) return rs; }
+        { int rs = slot_scratch(c, run, &c->d_pose_tiles, &c->pose_tiles_floats, (size_t)L.groups * mtiles * 8 * 6, &p.pose_partial); if (rs) return rs; }
         p.pose_w = c->d_wpred;
         p.pose_P = Ho * Wo; p.pose_mt = mtiles;
         if (pose_mt) *pose_mt = mtiles;
@@ -226,8 +214,8 @@ int run_conv_layer(davo_ctx* c, int li, const float* x, int x_ld, int Hin, int W
         pm.mtile0 = 0; pm.ntiles_n = 1;
         pm.tile_order = tile_order_for(c, li, 2, BM, 0, main_m, 1, p.M, Ho, Wo, Hin, L.stride, pt, L.rate);
         {
-            ProfScope ps(c, L.label);
-            HIP_TRY(c, launch_layer_n256(li, pm, dim3(main_m, 1), c->stream));
+            ProfScope ps(c, run.stream, L.label);
+            HIP_TRY(c, launch_layer_n256(li, pm, dim3(main_m, 1), run.stream));
         }
         c->last_plan[li][0] = main_m * 1000 + 256;
         if (main_m < mtiles) {
@@ -235,8 +223,8 @@ int run_conv_layer(davo_ctx* c, int li, const float* x, int x_ld, int Hin, int W
             pr.mtile0 = main_m; pr.ntiles_n = L.npad / 64;
             pr.tile_order = tile_order_for(c, li, 0, BM, main_m, mtiles - main_m, pr.ntiles_n, p.M, Ho, Wo, Hin, L.stride, pt, L.rate);
             const std::string label = std::string(L.label) + ".rem";
-            ProfScope ps(c, label.c_str());
-            HIP_TRY(c, launch_layer(li, 64, pr, dim3((mtiles - main_m) * pr.ntiles_n, 1), c->stream));
+            ProfScope ps(c, run.stream, label.c_str());
+            HIP_TRY(c, launch_layer(li, 64, pr, dim3((mtiles - main_m) * pr.ntiles_n, 1), run.stream));
             c->last_plan[li][1] = (mtiles - main_m) * 1000 + 64;
         }
         return DAVO_OK;
@@ -252,8 +240,8 @@ int run_conv_layer(davo_ctx* c, int li, const float* x, int x_ld, int Hin, int W
         pr.mtile0 = plan[1].mtile0; pr.ntiles_n = L.npad / plan[1].BN; pr.tile_order = order_for(plan[1], pr.ntiles_n);
         const int n_main = plan[0].mtiles * pm.ntiles_n, n_rem = plan[1].mtiles * pr.ntiles_n;
         if (n_main % 8 == 0 && (L.groups == 1 || n_rem % 8 == 0)) {
-            ProfScope ps(c, L.label);
-            HIP_TRY(c, launch_layer_mainrem(li, plan[1].BN, pm, pr, n_main, n_rem, L.groups, c->stream));
+            ProfScope ps(c, run.stream, L.label);
+            HIP_TRY(c, launch_layer_mainrem(li, plan[1].BN, pm, pr, n_main, n_rem, L.groups, run.stream));
             c->last_plan[li][0] = (plan[0].mtiles + plan[1].mtiles) * 1000 + 128;      // one launch covers the layer
             return DAVO_OK;
         }
@@ -264,15 +252,15 @@ int run_conv_layer(davo_ctx* c, int li, const float* x, int x_ld, int Hin, int W
         dim3 grid(plan[i].mtiles * p.ntiles_n, L.groups);
         p.tile_order = (L.KS == 3 && L.cin_log2 >= 5) ? tile_order_for(c, li, 0, BM, plan[i].mtile0, plan[i].mtiles, p.ntiles_n, p.M, Ho, Wo, Hin, L.stride, pt, L.rate) : nullptr;
         const std::string label = i == 0 ? std::string(L.label) : std::string(L.label) + ".rem";
-        ProfScope ps(c, label.c_str());
-        HIP_TRY(c, launch_layer(li, plan[i].BN, p, grid, c->stream));
+        ProfScope ps(c, run.stream, label.c_str());
+        HIP_TRY(c, launch_layer(li, plan[i].BN, p, grid, run.stream));
         c->last_plan[li][i] = plan[i].mtiles * 1000 + plan[i].BN;
     }
     return DAVO_OK;
 }
 
 // ---- one conv layer, f16x3 path: x and y are split-fp16 blocked tensors (y float32 when y_f32) -----
-int run_conv_layer_h3(davo_ctx* c, int li, const void* x, int x_ch, int Hin, int Win, void* y, int y_ld,
+int run_conv_layer_h3(davo_ctx* c, const Run& run, int li, const void* x, int x_ch, int Hin, int Win, void* y, int y_ld,
                       bool y_f32, int NB, bool fuse_pose = false, int* pose_bm = nullptr, int* pose_mt = nullptr,
                       int* pose_ntn = nullptr, float* pose_out = nullptr) {
     const ConvLayer& L = c->L[li];
@@ -294,7 +282,7 @@ int run_conv_layer_h3(davo_ctx* c, int li, const void* x, int x_ch, int Hin, int
         const int sin = li == 0 ? 0 : c->act_shift[li - 1], sout = li == 6 ? 0 : c->act_shift[li];
         p.out_scale = ldexpf(1.0f / L.wscale, sout - sin);
         p.bias_scale = ldexpf(L.wscale, sin);
-        p.range = c->d_range ? c->d_range + li : nullptr;
+        p.range = run.range ? run.range + li : nullptr;
     }
     if (L.groups == 2) {
         p.g_x_boff = L.cin * 4; p.g_y_coff = L.cout;
@@ -318,12 +306,12 @@ int run_conv_layer_h3(davo_ctx* c, int li, const void* x, int x_ch, int Hin, int
 #ifdef DAVO_POSE_DEBUG
         debug_bytes = (size_t)L.groups * mt * ntn * 512 * 20 * sizeof(float);
 #endif
-        { int rs = slot_scratch(c, &c->d_pose_tiles, &c->pose_tiles_floats, (size_t)L.groups * mt * ntn * 6, &p.pose_partial, debug_bytes); if (rs) return rs; }
+        { int rs = slot_scratch(c, run, &c->d_pose_tiles, &c->pose_tiles_floats, (size_t)L.groups * mt * ntn * 6, &p.pose_partial, debug_bytes); if (rs) return rs; }
         p.y_mode = 2; p.pose_w = c->d_wpred;
         p.pose_P = P; p.pose_mt = mt;
         if (pose_out) {      // the launch's last workgroup adds the tiles and writes the poses (pose_tail.h)
-            p.pose_counter = c->d_counters; p.pose_bias = c->d_bpred; p.pose_out = pose_out;
-            p.pose_NB = NB; p.pose_bm = ts.bm; p.pose_total = L.groups * mt * ntn; p.pose_sel = c->run_pairs;
+            p.pose_counter = c->slots[run.slot].d_counters; p.pose_bias = c->d_bpred; p.pose_out = pose_out;
+            p.pose_NB = NB; p.pose_bm = ts.bm; p.pose_total = L.groups * mt * ntn; p.pose_sel = run.pairs;
         }
         if (pose_bm) *pose_bm = ts.bm;
         if (pose_mt) *pose_mt = mt;
@@ -341,8 +329,8 @@ int run_conv_layer_h3(davo_ctx* c, int li, const void* x, int x_ch, int Hin, int
         pw.ntiles_n = 1; pw.mtile0 = 0;
         if (layer_h3w128_supported(pw)) {
             {
-                ProfScope ps(c, L.label);
-                HIP_TRY(c, launch_layer_h3w128(pw, c->stream));
+                ProfScope ps(c, run.stream, L.label);
+                HIP_TRY(c, launch_layer_h3w128(pw, run.stream));
             }
             c->last_plan[li][0] = ((p.M + 127) / 128) * 1000 + TILE_256x128;
             return DAVO_OK;
@@ -379,8 +367,8 @@ int run_conv_layer_h3(davo_ctx* c, int li, const void* x, int x_ch, int Hin, int
             pm.tile_order = c->opt_skip_order >= 2 ? tile_order_for(c, li, 1, 256, 0, n_main, 1, pm.M, Ho, Wo, Hin, L.stride, pt, L.rate) : nullptr;
             const int order = c->opt_merge_order >= 0 ? c->opt_merge_order : (pm.tile_order ? 2 : 0);
             {
-                ProfScope ps(c, L.label);
-                HIP_TRY(c, launch_layer_h3_mainrem(li, pm, n_main, pr, n_rem, order, c->stream));
+                ProfScope ps(c, run.stream, L.label);
+                HIP_TRY(c, launch_layer_h3_mainrem(li, pm, n_main, pr, n_rem, order, run.stream));
             }
             c->last_plan[li][0] = ((plan[0].rows + plan[1].rows + 127) / 128) * 1000 + 7;     // 7: 256x256 + 128x128 in one grid
             return DAVO_OK;
@@ -405,7 +393,7 @@ int run_conv_layer_h3(davo_ctx* c, int li, const void* x, int x_ch, int Hin, int
         const int S = (fits(4) && tiles * 4 <= (long)per_cu * c->ncu && tiles * 2 <= c->ncu) ? 4 : (fits(2) && tiles * 2 <= c->ncu ? 2 : 1);       // two parts at two per CU (B = 2) measured slower: 54 -> 57 us
         if (S > 1) {
             float* part = nullptr;
-            { int rs = slot_scratch(c, &c->d_splitk, &c->splitk_floats, (size_t)p.M * S * L.cout, &part); if (rs) return rs; }
+            { int rs = slot_scratch(c, run, &c->d_splitk, &c->splitk_floats, (size_t)p.M * S * L.cout, &part); if (rs) return rs; }
             ConvParamsH ps = p;
             ps.nchunks = L.nchunks_h / S;
             ps.g_x_boff = (L.cin / S) * 4; ps.g_w = (long)ps.nchunks * 128; ps.g_bias = L.npad_h; ps.g_y_coff = L.cout;
@@ -421,17 +409,17 @@ int run_conv_layer_h3(davo_ctx* c, int li, const void* x, int x_ch, int Hin, int
                         !c->user_stream;
             if (fold && c->xcd_rr < 0) {
                 int ok = 0;
-                HIP_TRY(c, xcd_round_robin_probe(c->stream, &ok));
+                HIP_TRY(c, xcd_round_robin_probe(run.stream, &ok));
                 c->xcd_rr = ok;
             }
             fold = fold && c->xcd_rr > 0;
             if (fold) {
-                ps.sk_counter = c->d_counters + 1 + c->max_batch;
+                ps.sk_counter = c->slots[run.slot].d_counters + 1 + c->max_batch;
                 ps.sk_y = p.y; ps.sk_range = p.range; ps.sk_parts = S; ps.sk_relu = 1;
             }
-            ProfScope pscope(c, L.label);
-            HIP_TRY(c, launch_layer_h3(li, plan[0].tile, ps, grid, c->stream));
-            if (!fold) HIP_TRY(c, launch_splitk_fixup(part, p.M, L.cout, S, 1, p.y, p.range, c->stream));
+            ProfScope pscope(c, run.stream, L.label);
+            HIP_TRY(c, launch_layer_h3(li, plan[0].tile, ps, grid, run.stream));
+            if (!fold) HIP_TRY(c, launch_splitk_fixup(part, p.M, L.cout, S, 1, p.y, p.range, run.stream));
             return DAVO_OK;
         }
     }
@@ -449,23 +437,23 @@ int run_conv_layer_h3(davo_ctx* c, int li, const void* x, int x_ch, int Hin, int
         // 97.4 long-first (profiles/r04e_skip_padding_rows.md); the merged grids above and the float32 launches take one
         const std::string label = i == 0 ? std::string(L.label) : std::string(L.label) + ".rem";
         {
-            ProfScope ps(c, label.c_str());
+            ProfScope ps(c, run.stream, label.c_str());
             bool done = false;
             if (c->opt_wave128 && L.groups == 1 && !fuse_pose) {
                 if (plan[i].tile == TILE_256x256 && layer_h3w_supported(li, p)) {
-                    HIP_TRY(c, launch_layer_h3w(li, p, grid, c->stream));
+                    HIP_TRY(c, launch_layer_h3w(li, p, grid, run.stream));
                     done = true;
                 } else if (c->opt_wave128 >= 2 && i == 1 && plan.size() == 2 && plan[0].tile == TILE_256x256 && plan[1].tile == TILE_128x128 &&
                            L.npad_h == 256 && plan[1].row0 % 256 == 0 && plan[1].rows % 256 == 0) {
                     // the remainder rows of a layer whose main launch ran on conv_igemm_h3w: 256 x 64 tiles (conv_igemm_h3w64)
                     ConvParamsH pr = p;
                     pr.ntiles_n = 4; pr.mtile0 = plan[1].row0 / 256;
-                    const hipError_t e = launch_layer_h3w64(li, pr, c->stream);
+                    const hipError_t e = launch_layer_h3w64(li, pr, run.stream);
                     if (e == hipSuccess) done = true;
                     else if (e != hipErrorNotSupported) HIP_TRY(c, e);
                 }
             }
-            if (!done) HIP_TRY(c, launch_layer_h3(li, plan[i].tile, p, grid, c->stream));
+            if (!done) HIP_TRY(c, launch_layer_h3(li, plan[i].tile, p, grid, run.stream));
         }
         p.M = full_m;
     }
@@ -481,7 +469,7 @@ constexpr PatchLayer PATCH_LAYERS[3] = {
     {cp2::TW, cp2::TH, 2, 98},       // f16x3: 120 weight registers per lane; float32: three per CU measured 4 % slower
     {cp3::TW, cp3::TH, 3, 97}};      // its padding, cp3::RATE on every side, is what SAME padding gives a 3x3 at dilation 2
 
-int run_patch_layer(davo_ctx* c, int li, bool f32, const void* x, void* y, int NB, bool fused = false, const Inputs& in = Inputs{}) {
+int run_patch_layer(davo_ctx* c, const Run& run, int li, bool f32, const void* x, void* y, int NB, bool fused = false, const Inputs& in = Inputs{}) {
     const ConvLayer& L = c->L[li];
     const PatchLayer& t = PATCH_LAYERS[li];
     const uint8_t* const w_h3[3] = {c->d_w1patch, c->d_w2patch, c->d_w3patch};
@@ -500,21 +488,21 @@ int run_patch_layer(davo_ctx* c, int li, bool f32, const void* x, void* y, int N
         const int sin = li == 0 ? 0 : c->act_shift[li - 1];
         p.out_scale = ldexpf(1.0f / L.wscale, c->act_shift[li] - sin);
         p.bias_scale = ldexpf(L.wscale, sin);
-        p.range = c->d_range ? c->d_range + li : nullptr;
+        p.range = run.range ? run.range + li : nullptr;
         if (const char* e = tuning_env("DAVO_PDBG")) p.dbg = atoi(e);      // tuning build only
         if (li == 0) {
             p.img = static_cast<const uint8_t*>(in.img); p.flow = static_cast<const float*>(in.flow);
-            p.seg = static_cast<const float*>(in.seg); p.tab = c->d_tab; p.v = c->v; p.sel = c->run_pairs;
+            p.seg = static_cast<const float*>(in.seg); p.tab = c->slots[run.slot].d_tab; p.v = c->v; p.sel = run.pairs;
         }
     }
     c->last_plan[li][0] = ((NB * p.Ho * p.Wo + 127) / 128) * 1000 + t.plan_id; c->last_plan[li][1] = 0; c->last_split[li] = 1;
     const int nblk = p.ntiles < t.per_cu * c->ncu ? p.ntiles : t.per_cu * c->ncu;
-    ProfScope ps(c, L.label);
-    HIP_TRY(c, launch_patch_layer(li, f32, fused, p, nblk, c->stream));
+    ProfScope ps(c, run.stream, L.label);
+    HIP_TRY(c, launch_patch_layer(li, f32, fused, p, nblk, run.stream));
     return DAVO_OK;
 }
 
-int run_direct(davo_ctx* c, const char* label, const float* x, int N, int Hin, int Win, int cin, int x_ld,
+int run_direct(davo_ctx* c, const Run& run, const char* label, const float* x, int N, int Hin, int Win, int cin, int x_ld,
                int x_coff, const std::string& wname, const std::string& bname, int KS, int cout, int stride,
                int rate, float* y, int y_ld, int y_coff) {
     int Ho, Wo, pt, pl;
@@ -524,14 +512,14 @@ int run_direct(davo_ctx* c, const char* label, const float* x, int N, int Hin, i
         HostTensor& t = c->weights.at(*n);
         if (!t.dev) { int rc = upload(c, t.data, &t.dev); if (rc) return rc; }
     }
-    ProfScope ps(c, label);
+    ProfScope ps(c, run.stream, label);
     HIP_TRY(c, launch_conv_direct(x, N, Hin, Win, cin, x_ld, x_coff, c->weights.at(wname).dev, KS, cout,
-                                  c->weights.at(bname).dev, stride, rate, pt, pl, Ho, Wo, 1, y, y_ld, y_coff, c->stream));
+                                  c->weights.at(bname).dev, stride, rate, pt, pl, Ho, Wo, 1, y, y_ld, y_coff, run.stream));
     return DAVO_OK;
 }
 
-// feature attention (posenn_se.h): cnv5 (x, in the mode's storage) -> c->d_se = [x s_r | x s_r s_t], 512 channels of cnv5's geometry
-int run_posenn_se(davo_ctx* c, bool h3, const void* x, int NB) {
+// feature attention (posenn_se.h): cnv5 (x, in the mode's storage) -> the slot's d_se = [x s_r | x s_r s_t], 512 channels of cnv5's geometry
+int run_posenn_se(davo_ctx* c, const Run& run, bool h3, const void* x, int NB) {
     static const char* const heads[2] = {"rotation", "translation"};
     static const char* const parts[4] = {"bottleneck_fc/kernel", "bottleneck_fc/bias", "recover_fc/kernel", "recover_fc/bias"};
     const float* w[8];
@@ -541,24 +529,26 @@ int run_posenn_se(davo_ctx* c, bool h3, const void* x, int NB) {
             if (it == c->weights.end() || !it->second.dev) return fail(c, DAVO_ERR_NOT_READY, "feature-attention weights not loaded");
             w[h * 4 + k] = it->second.dev;
         }
-    if (!c->d_se || !c->d_se_scale || !c->d_se_partial) return fail(c, DAVO_ERR_INVALID, "internal: no feature-attention workspace");
+    const Slot& ws = c->slots[run.slot];
+    if (!ws.d_se || !ws.d_se_scale || !ws.d_se_partial) return fail(c, DAVO_ERR_INVALID, "internal: no feature-attention workspace");
     const int P = c->H2 * c->W2;
     {
-        ProfScope ps(c, "se5_squeeze");
-        HIP_TRY(c, launch_se5_squeeze(h3, x, NB, P, c->d_se_partial, c->stream));
+        ProfScope ps(c, run.stream, "se5_squeeze");
+        HIP_TRY(c, launch_se5_squeeze(h3, x, NB, P, ws.d_se_partial, run.stream));
     }
     {
-        ProfScope ps(c, "se5_excite");
-        HIP_TRY(c, launch_se5_excite(c->d_se_partial, NB, P, h3 ? ldexpf(1.0f, -c->act_shift[4]) : 1.0f, w, c->d_se_scale, c->stream));
+        ProfScope ps(c, run.stream, "se5_excite");
+        HIP_TRY(c, launch_se5_excite(ws.d_se_partial, NB, P, h3 ? ldexpf(1.0f, -c->act_shift[4]) : 1.0f, w, ws.d_se_scale, run.stream));
     }
-    ProfScope ps(c, "se5_scale");
-    HIP_TRY(c, launch_se5_scale(h3, x, c->d_se_scale, NB, P, c->d_se, (h3 && c->d_range) ? c->d_range + RANGE_SE : nullptr, c->stream));
+    ProfScope ps(c, run.stream, "se5_scale");
+    HIP_TRY(c, launch_se5_scale(h3, x, ws.d_se_scale, NB, P, ws.d_se, (h3 && run.range) ? run.range + RANGE_SE : nullptr, run.stream));
     return DAVO_OK;
 }
 
 }  // namespace
 
-int forward_device(davo_ctx* c, int B, const Inputs& in, void* d_pose, int sel) {
+int forward_device(davo_ctx* c, const Run& run, int B, const Inputs& in, void* d_pose, RunResult* res) {
+    const int sel = run.pairs;
     if (sel != PAIRS_SRC0 && sel != PAIRS_SRC1 && sel != PAIRS_BOTH) return fail(c, DAVO_ERR_INVALID, "internal: pair selection %d", sel);
     if (B < 1 || B > c->max_batch) return fail(c, DAVO_ERR_INVALID, "batch %d outside [1,%d]", B, c->max_batch);
     if (!in.img || !in.flow || !in.seg || !d_pose) return fail(c, DAVO_ERR_INVALID, "null device pointer");
@@ -570,9 +560,9 @@ int forward_device(davo_ctx* c, int B, const Inputs& in, void* d_pose, int sel) 
     }
     HIP_TRY(c, hipSetDevice(c->device));
     c->forward_seen = true;
+    c->last_slot = run.slot;
     if (!c->pred_ready) { int rc = build_pred_weights(c); if (rc) return rc; }
-    bool h3 = c->impl == 0 && c->precision == 1;
-    c->f32_fallback = false;
+    bool h3 = run.impl == 0 && run.precision == 1, f32_fallback = false;
     if (h3 && !c->packed_h_ready) { int rc = build_packed_weights_h3(c); if (rc) return rc; }
     if (h3 && c->weight_channel_spread_log2 > MAX_WEIGHT_CHANNEL_SPREAD_LOG2) {
         // a consumer's per-input-channel weight norms span more than 2^14: per-layer storage scales cannot keep every channel's fp16
@@ -582,19 +572,19 @@ int forward_device(davo_ctx* c, int B, const Inputs& in, void* d_pose, int sel) 
                         "float32-grade - davo_set_precision(ctx, 0), or leave \"auto_range\" on", c->weight_channel_spread_layer.c_str(),
                         c->weight_channel_spread_log2, MAX_WEIGHT_CHANNEL_SPREAD_LOG2);
         h3 = false;
-        c->f32_fallback = true;              // counted once per API call by the caller (api.hip)
+        f32_fallback = true;                 // counted once per API call by the caller (api.hip)
         char note[256];
         snprintf(note, sizeof note, "float32 kernels: per-input-channel weight norms of `%s' span 2^%d (> 2^%d)",
                  c->weight_channel_spread_layer.c_str(), c->weight_channel_spread_log2, MAX_WEIGHT_CHANNEL_SPREAD_LOG2);
         c->range_report = note;
     }
-    if (!h3 && c->impl == 0 && !c->packed_ready) { int rc = build_packed_weights(c); if (rc) return rc; }      // float32 kernels: packed at their first use
-    unsigned* const range_reset = (h3 && c->range_zero) ? c->d_range : nullptr;
+    if (!h3 && run.impl == 0 && !c->packed_ready) { int rc = build_packed_weights(c); if (rc) return rc; }      // float32 kernels: packed at their first use
+    unsigned* const range_reset = (h3 && run.zero_record) ? run.range : nullptr;
 
     const int H = c->H, W = c->W, HW = H * W, NB = pairs_per_window(sel) * B;
-    c->run_pairs = sel;
     const Variant& v = c->v;
-    hipStream_t s = c->stream;
+    const Slot& ws = c->slots[run.slot];
+    hipStream_t s = run.stream;
     const uint8_t* const d_img = static_cast<const uint8_t*>(in.img);
     const float* const d_flow = static_cast<const float*>(in.flow);
     const float* const d_seg = static_cast<const float*>(in.seg);
@@ -616,29 +606,29 @@ int forward_device(davo_ctx* c, int B, const Inputs& in, void* d_pose, int sel) 
     const float* se_b2 = wdev(se_weight_name(v.att_source, 3));
     if (needs_depth(c)) {
         // depth sources: one float32 sum per depth plane and chunk, then (or, folded, in the same launch) the excitation
-        ProfScope ps(c, "se_depth_squeeze");
-        HIP_TRY(c, launch_se_depth_squeeze(fold_excite, static_cast<const float*>(in.depth), B, HW, v, reinterpret_cast<unsigned*>(c->d_partial),
-                                           c->d_counters + 1, se_w1, se_b1, se_w2, se_b2, c->d_tab, range_reset, sel, s));
+        ProfScope ps(c, run.stream, "se_depth_squeeze");
+        HIP_TRY(c, launch_se_depth_squeeze(fold_excite, static_cast<const float*>(in.depth), B, HW, v, reinterpret_cast<unsigned*>(ws.d_partial),
+                                           ws.d_counters + 1, se_w1, se_b1, se_w2, se_b2, ws.d_tab, range_reset, sel, s));
     } else if (class_table) {
         // segmentation / rgb / seg+flow sources: per-frame histogram, byte or flow sums, then (or, folded, in the same launch) the
         // excitation
-        ProfScope ps(c, "se_class_squeeze");
-        HIP_TRY(c, launch_se_class_squeeze(fold_excite, d_img, d_flow, d_seg, B, H, W, v, reinterpret_cast<unsigned*>(c->d_partial),
-                                           c->d_counters + 1, se_w1, se_b1, se_w2, se_b2, c->d_tab, range_reset, sel, s));
+        ProfScope ps(c, run.stream, "se_class_squeeze");
+        HIP_TRY(c, launch_se_class_squeeze(fold_excite, d_img, d_flow, d_seg, B, H, W, v, reinterpret_cast<unsigned*>(ws.d_partial),
+                                           ws.d_counters + 1, se_w1, se_b1, se_w2, se_b2, ws.d_tab, range_reset, sel, s));
     } else if (fold_excite) {
         // squeeze + excitation in one launch: the workgroup that delivers a triplet's last partial sum evaluates its tables
-        ProfScope ps(c, "se_squeeze_partial");
-        HIP_TRY(c, launch_se_squeeze_excite(d_flow, B, HW, v, c->d_partial, c->d_counters + 1,
+        ProfScope ps(c, run.stream, "se_squeeze_partial");
+        HIP_TRY(c, launch_se_squeeze_excite(d_flow, B, HW, v, ws.d_partial, ws.d_counters + 1,
                                             se_w1, se_b1, se_w2, se_b2,
-                                            wdev("pose_exp_net/pose_exp_net/seg_channel_weight/weight"), c->d_tab, range_reset, sel, s));
+                                            wdev("pose_exp_net/pose_exp_net/seg_channel_weight/weight"), ws.d_tab, range_reset, sel, s));
     } else if (v.att_source == 1) {
-        ProfScope ps(c, "se_squeeze_partial");
-        HIP_TRY(c, launch_se_squeeze(d_flow, B, HW, v, c->d_partial, sel, s));
+        ProfScope ps(c, run.stream, "se_squeeze_partial");
+        HIP_TRY(c, launch_se_squeeze(d_flow, B, HW, v, ws.d_partial, sel, s));
     }
     if (!fold_excite) {
-        ProfScope ps(c, "se_excite");
-        HIP_TRY(c, launch_se_excite(c->d_partial, B, HW, v, se_w1, se_b1, se_w2, se_b2,
-                                    wdev("pose_exp_net/pose_exp_net/seg_channel_weight/weight"), c->d_tab, range_reset, sel, s));
+        ProfScope ps(c, run.stream, "se_excite");
+        HIP_TRY(c, launch_se_excite(ws.d_partial, B, HW, v, se_w1, se_b1, se_w2, se_b2,
+                                    wdev("pose_exp_net/pose_exp_net/seg_channel_weight/weight"), ws.d_tab, range_reset, sel, s));
     }
     // f16x3, fuse_pack: cnv1 builds its input patch straight from the raw inputs (mask + pack fused in,
     // the packed tensor never touches HBM).  Measured equal in time to mask_pack + cnv1 (the fused fill is bound
@@ -650,90 +640,91 @@ int forward_device(davo_ctx* c, int B, const Inputs& in, void* d_pose, int sel) 
     const bool fused = h3 && patch1 && fuse_env;
     c->packed_valid = !fused;
     c->last_in = in;
-    c->packed_ld = c->impl == 0 ? 8 : 10;
+    c->packed_ld = run.impl == 0 ? 8 : 10;
     if (!fused) {
-        ProfScope ps(c, "mask_pack");
-        HIP_TRY(c, launch_mask_pack(h3 ? 16 : (c->impl == 0 ? 8 : 10), d_img, d_flow, d_seg, c->d_tab, v, B, H, W, c->d_packed, sel, s));
+        ProfScope ps(c, run.stream, "mask_pack");
+        HIP_TRY(c, launch_mask_pack(h3 ? 16 : (run.impl == 0 ? 8 : 10), d_img, d_flow, d_seg, ws.d_tab, v, B, H, W, ws.d_packed, sel, s));
     }
     const int c6 = v.cnv6_out;
-    float** a = c->d_act;
+    float* const* a = ws.d_act;
     int rc;
     bool pose_fused = false;
     int pose_bm = 0, pose_mt = 0, pose_ntn = 0;
     c->cnv7_valid = true;
     if (h3) {
-        if (patch1) { if ((rc = run_patch_layer(c, 0, false, c->d_packed, a[0], NB, fused, in))) return rc; }
-        else if ((rc = run_conv_layer_h3(c, 0, c->d_packed, 8, H, W, a[0], 16, false, NB))) return rc;
+        if (patch1) { if ((rc = run_patch_layer(c, run, 0, false, ws.d_packed, a[0], NB, fused, in))) return rc; }
+        else if ((rc = run_conv_layer_h3(c, run, 0, ws.d_packed, 8, H, W, a[0], 16, false, NB))) return rc;
         const char* p2e = tuning_env("DAVO_CNV2_PATCH");
-        if (c->opt_patch_cnv2 && c->L[1].tile_h < 0 && !(p2e && atoi(p2e) == 0)) { if ((rc = run_patch_layer(c, 1, false, a[0], a[1], NB))) return rc; }
-        else if ((rc = run_conv_layer_h3(c, 1, a[0], 16, c->H1, c->W1, a[1], 32, false, NB))) return rc;
+        if (c->opt_patch_cnv2 && c->L[1].tile_h < 0 && !(p2e && atoi(p2e) == 0)) { if ((rc = run_patch_layer(c, run, 1, false, a[0], a[1], NB))) return rc; }
+        else if ((rc = run_conv_layer_h3(c, run, 1, a[0], 16, c->H1, c->W1, a[1], 32, false, NB))) return rc;
         const char* p3e = tuning_env("DAVO_CNV3_PATCH");
-        if (c->opt_patch_cnv3 && c->L[2].tile_h < 0 && !(p3e && atoi(p3e) == 0)) { if ((rc = run_patch_layer(c, 2, false, a[1], a[2], NB))) return rc; }
-        else if ((rc = run_conv_layer_h3(c, 2, a[1], 32, c->H2, c->W2, a[2], 64, false, NB))) return rc;
-        if ((rc = run_conv_layer_h3(c, 3, a[2], 64, c->H2, c->W2, a[3], 128, false, NB))) return rc;
-        if ((rc = run_conv_layer_h3(c, 4, a[3], 128, c->H2, c->W2, a[4], 256, false, NB))) return rc;
+        if (c->opt_patch_cnv3 && c->L[2].tile_h < 0 && !(p3e && atoi(p3e) == 0)) { if ((rc = run_patch_layer(c, run, 2, false, a[1], a[2], NB))) return rc; }
+        else if ((rc = run_conv_layer_h3(c, run, 2, a[1], 32, c->H2, c->W2, a[2], 64, false, NB))) return rc;
+        if ((rc = run_conv_layer_h3(c, run, 3, a[2], 64, c->H2, c->W2, a[3], 128, false, NB))) return rc;
+        if ((rc = run_conv_layer_h3(c, run, 4, a[3], 128, c->H2, c->W2, a[4], 256, false, NB))) return rc;
         if (c->posenn_se) {
-            if ((rc = run_posenn_se(c, true, a[4], NB))) return rc;
-            if ((rc = run_conv_layer_h3(c, 5, c->d_se, 512, c->H2, c->W2, a[5], 2 * c6, false, NB))) return rc;
-        } else if ((rc = run_conv_layer_h3(c, 5, a[4], 256, c->H2, c->W2, a[5], 2 * c6, false, NB))) return rc;
+            if ((rc = run_posenn_se(c, run, true, a[4], NB))) return rc;
+            if ((rc = run_conv_layer_h3(c, run, 5, ws.d_se, 512, c->H2, c->W2, a[5], 2 * c6, false, NB))) return rc;
+        } else if ((rc = run_conv_layer_h3(c, run, 5, a[4], 256, c->H2, c->W2, a[5], 2 * c6, false, NB))) return rc;
         pose_fused = c->opt_fuse_pose && c->H3 * c->W3 >= 128;
-        if ((rc = run_conv_layer_h3(c, 6, a[5], 2 * c6, c->H2, c->W2, a[6], 512, true, NB, pose_fused, &pose_bm, &pose_mt, &pose_ntn,
+        if ((rc = run_conv_layer_h3(c, run, 6, a[5], 2 * c6, c->H2, c->W2, a[6], 512, true, NB, pose_fused, &pose_bm, &pose_mt, &pose_ntn,
                                     fold_pose ? static_cast<float*>(d_pose) : nullptr))) return rc;
         c->cnv7_valid = !pose_fused;
-    } else if (c->impl == 0) {
-        if (c->opt_patch_f32 && c->d_w1patch_f32 && c->packed_ld == 8) { if ((rc = run_patch_layer(c, 0, true, c->d_packed, a[0], NB))) return rc; }
-        else if ((rc = run_conv_layer(c, 0, c->d_packed, 8, H, W, a[0], 16, NB))) return rc;
-        if (c->opt_patch_f32 && c->d_w2patch_f32) { if ((rc = run_patch_layer(c, 1, true, a[0], a[1], NB))) return rc; }
-        else if ((rc = run_conv_layer(c, 1, a[0], 16, c->H1, c->W1, a[1], 32, NB))) return rc;
-        if (c->opt_patch_f32 && c->d_w3patch_f32) { if ((rc = run_patch_layer(c, 2, true, a[1], a[2], NB))) return rc; }
-        else if ((rc = run_conv_layer(c, 2, a[1], 32, c->H2, c->W2, a[2], 64, NB))) return rc;
-        if ((rc = run_conv_layer(c, 3, a[2], 64, c->H2, c->W2, a[3], 128, NB))) return rc;
-        if ((rc = run_conv_layer(c, 4, a[3], 128, c->H2, c->W2, a[4], 256, NB))) return rc;
+    } else if (run.impl == 0) {
+        if (c->opt_patch_f32 && c->d_w1patch_f32 && c->packed_ld == 8) { if ((rc = run_patch_layer(c, run, 0, true, ws.d_packed, a[0], NB))) return rc; }
+        else if ((rc = run_conv_layer(c, run, 0, ws.d_packed, 8, H, W, a[0], 16, NB))) return rc;
+        if (c->opt_patch_f32 && c->d_w2patch_f32) { if ((rc = run_patch_layer(c, run, 1, true, a[0], a[1], NB))) return rc; }
+        else if ((rc = run_conv_layer(c, run, 1, a[0], 16, c->H1, c->W1, a[1], 32, NB))) return rc;
+        if (c->opt_patch_f32 && c->d_w3patch_f32) { if ((rc = run_patch_layer(c, run, 2, true, a[1], a[2], NB))) return rc; }
+        else if ((rc = run_conv_layer(c, run, 2, a[1], 32, c->H2, c->W2, a[2], 64, NB))) return rc;
+        if ((rc = run_conv_layer(c, run, 3, a[2], 64, c->H2, c->W2, a[3], 128, NB))) return rc;
+        if ((rc = run_conv_layer(c, run, 4, a[3], 128, c->H2, c->W2, a[4], 256, NB))) return rc;
         if (c->posenn_se) {
-            if ((rc = run_posenn_se(c, false, a[4], NB))) return rc;
-            if ((rc = run_conv_layer(c, 5, c->d_se, 512, c->H2, c->W2, a[5], 2 * c6, NB))) return rc;
-        } else if ((rc = run_conv_layer(c, 5, a[4], 256, c->H2, c->W2, a[5], 2 * c6, NB))) return rc;
+            if ((rc = run_posenn_se(c, run, false, a[4], NB))) return rc;
+            if ((rc = run_conv_layer(c, run, 5, ws.d_se, 512, c->H2, c->W2, a[5], 2 * c6, NB))) return rc;
+        } else if ((rc = run_conv_layer(c, run, 5, a[4], 256, c->H2, c->W2, a[5], 2 * c6, NB))) return rc;
         // float32 mode, round 4: the pose head in cnv7's epilogue like the f16x3 path's (the 109 MB activation is neither written nor
         // read back, pose_head_partial + pose_finish become pose_from_tiles); tiles of 128 rows must not span more than two images
         pose_fused = c->opt_fuse_pose && c->H3 * c->W3 >= 128 && c->L[6].npad == 256;
         pose_bm = 128; pose_ntn = 8;
-        if ((rc = run_conv_layer(c, 6, a[5], 2 * c6, c->H2, c->W2, a[6], 512, NB, pose_fused, &pose_mt))) return rc;
+        if ((rc = run_conv_layer(c, run, 6, a[5], 2 * c6, c->H2, c->W2, a[6], 512, NB, pose_fused, &pose_mt))) return rc;
         c->cnv7_valid = !pose_fused;
     } else {
         const std::string P = "pose_exp_net/";
         const int c10 = 2 * v.cin_per_frame;
         if (v.cin_per_frame != 5) return fail(c, DAVO_ERR_INVALID, "impl 1 supports the 10-channel (v1) input only");
-        if ((rc = run_direct(c, "cnv1", c->d_packed, NB, H, W, c10, 10, 0, P + "cnv1/weights", P + "cnv1/biases", 7, 16, 2, 1, a[0], 16, 0))) return rc;
-        if ((rc = run_direct(c, "cnv2", a[0], NB, c->H1, c->W1, 16, 16, 0, P + "cnv2/weights", P + "cnv2/biases", 5, 32, 2, 1, a[1], 32, 0))) return rc;
-        if ((rc = run_direct(c, "cnv3", a[1], NB, c->H2, c->W2, 32, 32, 0, P + "cnv3/weights", P + "cnv3/biases", 3, 64, 1, 2, a[2], 64, 0))) return rc;
-        if ((rc = run_direct(c, "cnv4", a[2], NB, c->H2, c->W2, 64, 64, 0, P + "cnv4/weights", P + "cnv4/biases", 3, 128, 1, 4, a[3], 128, 0))) return rc;
-        if ((rc = run_direct(c, "cnv5", a[3], NB, c->H2, c->W2, 128, 128, 0, P + "cnv5/weights", P + "cnv5/biases", 3, 256, 1, 8, a[4], 256, 0))) return rc;
-        if (c->posenn_se && (rc = run_posenn_se(c, false, a[4], NB))) return rc;      // float32 NHWC like the float32 mode's cnv5
+        if ((rc = run_direct(c, run, "cnv1", ws.d_packed, NB, H, W, c10, 10, 0, P + "cnv1/weights", P + "cnv1/biases", 7, 16, 2, 1, a[0], 16, 0))) return rc;
+        if ((rc = run_direct(c, run, "cnv2", a[0], NB, c->H1, c->W1, 16, 16, 0, P + "cnv2/weights", P + "cnv2/biases", 5, 32, 2, 1, a[1], 32, 0))) return rc;
+        if ((rc = run_direct(c, run, "cnv3", a[1], NB, c->H2, c->W2, 32, 32, 0, P + "cnv3/weights", P + "cnv3/biases", 3, 64, 1, 2, a[2], 64, 0))) return rc;
+        if ((rc = run_direct(c, run, "cnv4", a[2], NB, c->H2, c->W2, 64, 64, 0, P + "cnv4/weights", P + "cnv4/biases", 3, 128, 1, 4, a[3], 128, 0))) return rc;
+        if ((rc = run_direct(c, run, "cnv5", a[3], NB, c->H2, c->W2, 128, 128, 0, P + "cnv5/weights", P + "cnv5/biases", 3, 256, 1, 8, a[4], 256, 0))) return rc;
+        if (c->posenn_se && (rc = run_posenn_se(c, run, false, a[4], NB))) return rc;      // float32 NHWC like the float32 mode's cnv5
         const char* heads[2] = {"rotation", "translation"};
         for (int h = 0; h < 2; ++h) {
             const std::string hp = P + "pose/" + heads[h] + "/";
             // feature attention: head h reads its half of the scaled tensor
-            const float* x6 = c->posenn_se ? c->d_se : a[4];
-            if ((rc = run_direct(c, "cnv6", x6, NB, c->H2, c->W2, 256, c->posenn_se ? 512 : 256, c->posenn_se ? h * 256 : 0, hp + "cnv6/weights", hp + "cnv6/biases", 3, c6, 1, 2, a[5], 2 * c6, h * c6))) return rc;
-            if ((rc = run_direct(c, "cnv7", a[5], NB, c->H2, c->W2, c6, 2 * c6, h * c6, hp + "cnv7/weights", hp + "cnv7/biases", 3, 256, 2, 1, a[6], 512, h * 256))) return rc;
+            const float* x6 = c->posenn_se ? ws.d_se : a[4];
+            if ((rc = run_direct(c, run, "cnv6", x6, NB, c->H2, c->W2, 256, c->posenn_se ? 512 : 256, c->posenn_se ? h * 256 : 0, hp + "cnv6/weights", hp + "cnv6/biases", 3, c6, 1, 2, a[5], 2 * c6, h * c6))) return rc;
+            if ((rc = run_direct(c, run, "cnv7", a[5], NB, c->H2, c->W2, c6, 2 * c6, h * c6, hp + "cnv7/weights", hp + "cnv7/biases", 3, 256, 2, 1, a[6], 512, h * 256))) return rc;
         }
     }
     bool snap_done = false;
     if (!(pose_fused && fold_pose)) {
-        ProfScope ps(c, "pose_head");
+        ProfScope ps(c, run.stream, "pose_head");
         if (pose_fused) {
-            HIP_TRY(c, launch_pose_from_tiles(c->d_pose_tiles + (size_t)slot_idx(c) * c->pose_tiles_floats, NB, c->H3 * c->W3, pose_bm,
-                                              pose_mt, pose_ntn, c->d_bpred, static_cast<float*>(d_pose), h3 ? c->snap : SnapArgs{}, sel, s));
+            HIP_TRY(c, launch_pose_from_tiles(c->d_pose_tiles + (size_t)run.slot * c->pose_tiles_floats, NB, c->H3 * c->W3, pose_bm,
+                                              pose_mt, pose_ntn, c->d_bpred, static_cast<float*>(d_pose), h3 ? run.snap : SnapArgs{}, sel, s));
             snap_done = true;
         } else {
-            HIP_TRY(c, launch_pose_head(a[6], NB, c->H3 * c->W3, c->d_wpred, c->d_bpred, c->d_pose_partial, static_cast<float*>(d_pose), sel, s));
+            HIP_TRY(c, launch_pose_head(a[6], NB, c->H3 * c->W3, c->d_wpred, c->d_bpred, ws.d_pose_partial, static_cast<float*>(d_pose), sel, s));
         }
     }
     // the range guard's conditional copy of this batch's inputs (api.hip: tickets) rides in pose_from_tiles; other pose heads get a launch
-    if (h3 && c->snap.record && !snap_done) HIP_TRY(c, launch_range_guard_snapshot(c->snap, s));
+    if (h3 && run.snap.record && !snap_done) HIP_TRY(c, launch_range_guard_snapshot(run.snap, s));
     c->last_B = B;
     c->last_pairs = sel;
     c->last_precision = h3 ? 1 : 0;
+    if (res) *res = RunResult{h3, f32_fallback};
     return DAVO_OK;
 }
 

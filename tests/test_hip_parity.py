@@ -567,6 +567,52 @@ def test_two_batches_in_flight(c_oracle):
     e.close()
 
 
+@pytest.mark.parametrize("B", [2, 1])
+@pytest.mark.parametrize("tripped", [False, True], ids=["in_range", "range_guard_trips"])
+def test_slot_zero_paths_while_the_rotation_points_elsewhere(c_oracle, tripped, B):
+    """davo_set_inflight(3) with the entry points mixed.  The host call, a calibration and every re-issue run in slot 0 whatever
+    slot the device path's rotation will hand out next; davo_debug_read reads the slot of the batch issued last, on that batch's
+    stream.  128x416 runs the fused pose head, and at B = 1 split-K on cnv5 / cnv6 (at most half a workgroup per CU): the pose tiles
+    and the split-K partial sums are scratch with one region per slot.  The same calls with one batch at a time (davo_set_inflight(1): slot 0 throughout) must give the same bits - poses and cnv6.
+    tripped: a checkpoint that fails the range verdict, so that recover_batch re-issues batches while next_slot is 1 and 2."""
+    cfg = parse_version(FLAGSHIP_VERSION)
+    H, W = 128, 416
+    weights = synth.make_weights(cfg)
+    data = [synth.make_inputs(B, H, W, first_window=5 * k) for k in range(6)]
+
+    def run(inflight):
+        e = _engine(cfg, H, W, B, _rescaled(weights, 16) if tripped else weights, "f16x3")
+        sets = [tuple(e.alloc(a.nbytes).upload(a) for a in d) + (e.alloc(B * 48),) for d in data]
+        e.set_inflight(inflight)
+        e.forward_device(B, *sets[0])                                      # slot 0; the rotation moves on to slot 1
+        cnv6 = e.debug_read("cnv6", (2 * B, H // 4, W // 4, 2 * cfg.cnv6_out))      # not synchronised: behind batch 0 on its stream
+        if B == 1:
+            assert max(e.last_split(4), e.last_split(5)) > 1, (e.last_split(4), e.last_split(5))      # cnv5 / cnv6: split-K
+        host = e.forward(*data[1])                                         # slot 0 again; tripped: judges and re-issues batch 0 first
+        for k in (2, 3):
+            e.forward_device(B, *sets[k])                                  # slots 1 and 2
+        e.synchronize()
+        e.reset_range_state()                                              # tripped: the next two batches fail their verdicts again
+        for k in (4, 5):
+            e.forward_device(B, *sets[k])                                  # slots 0 and 1; their re-issues run with next_slot at 2
+        e.synchronize()
+        poses = {k: sets[k][3].download((B, 2, 6)) for k in (0, 2, 3, 4, 5)}
+        poses[1] = host
+        st = e.range_stats()
+        e.close()
+        return cnv6, poses, st
+
+    cnv6_1, poses_1, st_1 = run(1)
+    cnv6_3, poses_3, st_3 = run(3)
+    assert np.array_equal(cnv6_3, cnv6_1)
+    for k in range(6):
+        assert np.array_equal(poses_3[k], poses_1[k]), "batch %d" % k
+    for k in (0, 5):                                                       # ... and the right bits: a re-issued batch of either phase
+        assert_pose_close(poses_3[k], c_oracle.forward(cfg, *data[k], weights), "three in flight, batch %d" % k)
+    assert st_3 == st_1, (st_3, st_1)
+    assert (st_3["reissued"] >= 3 and st_3["f32_batches"] == 0) if tripped else st_3["reissued"] == 0, st_3
+
+
 @pytest.mark.parametrize("precision", PRECISIONS)
 def test_seg_label_edge_values(precision):
     """tf.cast(float->int32) truncates toward zero and tf.one_hot of an out-of-range id is a zero row
