@@ -1,7 +1,8 @@
 // api.hip — the extern "C" entry points of libdavo_hip.so (include/davo_hip.h): context life
-// cycle, weight loading, the host- and device-buffer forward calls, f16x3 range management,
-// measurement and test hooks.  The forward plan itself is forward.hip; kernels are reached
-// through launch.h; the RCCL communicator is comm.hip.
+// cycle, weight loading, the host- and device-buffer forward calls, the streaming state,
+// measurement and test hooks.  The forward plan itself is forward.hip; the f16x3 range guard
+// around it is range_guard.hip (bookkeeping: range_book.h); kernels are reached through
+// launch.h; the RCCL communicator is comm.hip.
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
@@ -14,7 +15,7 @@
 
 using namespace davo;
 
-namespace {
+namespace davo {
 
 // hipMemset runs on the null stream and may return before the fill has run; the context's streams are non-blocking, so nothing
 // orders them behind it.  (Found as one wrong batch in twenty streamed runs: the zero fill of a slot's new staging set landed on
@@ -40,6 +41,10 @@ int alloc_input_set(davo_ctx* c, InputSet* s, bool zero_unread) {
     }
     return DAVO_OK;
 }
+
+}  // namespace davo
+
+namespace {
 
 void free_input_set(InputSet& s) {
     for (void* q : {s.img, s.flow, s.seg, s.depth}) if (q) (void)hipFree(q);
@@ -211,26 +216,9 @@ int davo_weights_missing(davo_ctx* c) {
     return n;
 }
 
-// ---- f16x3 range verdicts and recovery -----------------------------------------------------------------
-// The reference's float32 graph (nets/posenn.py:205-215, davo.py:1553-1569) never fails on a finite network, so the
-// default f16x3 arithmetic must not either: a batch whose range record fails the verdict is re-issued here - first
-// with the storage scales re-calibrated on that very batch, and if it still leaves the fp16-pair range, on the
-// library's own float32 kernels (davo_set_precision(ctx, 0) for that batch only).  "auto_range" 0 restores the plain
-// DAVO_ERR_RANGE verdict.
-//
-// Device path (round 4).  Every batch davo_forward_device issues owns one slot of a ring of RANGE_RING: a record of its own
-// (zeroed by the forward's first kernel) and, unless the caller declared "stable_inputs", room for a copy of its inputs.  The
-// batch's LAST kernel reads the finished record and, if a layer left the range, copies the inputs it was issued on into the
-// slot (prologue.h: snapshot_inputs_if_range_fails) - in stream order behind the kernels that read them and ahead of anything
-// the caller orders behind the batch, e.g. the next H2D into the same buffers.  A batch in range costs six loads per thread and
-// no copy.  A batch is judged when its slot is needed again, at davo_synchronize, or before anything that changes the scales;
-// a failed verdict re-issues THAT batch from the slot's copy, so a streaming caller that recycles its input buffers still gets
-// float32-grade poses for every batch.  (First built with an unconditional side-stream copy: +1.6 % of the step at B = 32,
-// profiles/r04_snapshot_ab.log.)
+// ---- the forward entry points ----------------------------------------------------------------------------
+// The f16x3 batches they issue are judged by the range guard (range_guard.hip, reached through ctx.h; bookkeeping: c->book).
 namespace {
-
-constexpr int RING = RANGE_RING;
-constexpr int FRESH_EVERY = 256;
 
 // The depth argument of an entry point.  A depth-source variant (att_source 11, 12) must be called through the `_depth' form with
 // the planes; every other variant reads no depth: the `_depth' forms accept a pointer (or null) and ignore it.
@@ -238,288 +226,6 @@ int resolve_depth(davo_ctx* c, const char* fn, bool depth_form, const void** dep
     if (!needs_depth(c)) { *depth = nullptr; return DAVO_OK; }
     if (!depth_form) return fail(c, DAVO_ERR_INVALID, "%s: this variant reads depth planes (att_source %d): call %s_depth", fn, c->v.att_source, fn);
     if (!*depth) return fail(c, DAVO_ERR_INVALID, "%s_depth: null depth pointer", fn);
-    return DAVO_OK;
-}
-
-int ensure_ring(davo_ctx* c, bool snapshots) {
-    if (!c->read_stream) {
-        HIP_TRY(c, hipStreamCreateWithFlags(&c->read_stream, hipStreamNonBlocking));
-        HIP_TRY(c, hipHostMalloc(reinterpret_cast<void**>(&c->h_range), (1 + RANGE_RING) * RANGE_WORDS * sizeof(unsigned), hipHostMallocMapped | hipHostMallocCoherent));
-        HIP_TRY(c, hipHostGetDevicePointer(reinterpret_cast<void**>(&c->h_range_dev), c->h_range, 0));
-        memset(c->h_range, 0, (1 + RANGE_RING) * RANGE_WORDS * sizeof(unsigned));
-    }
-    if (snapshots && !c->snap_sets[0].img)
-        for (InputSet& set : c->snap_sets) { int rc = alloc_input_set(c, &set, false); if (rc) return rc; }
-    return DAVO_OK;
-}
-
-// a record -> host, on a stream of its own (never behind queued batches, never through the null stream)
-int read_record(davo_ctx* c, const unsigned* d_rec, unsigned raw[RANGE_WORDS]) {
-    if (!c->read_stream) { int rc = ensure_ring(c, false); if (rc) return rc; }
-    HIP_TRY(c, hipMemcpyAsync(c->h_range, d_rec, RANGE_WORDS * sizeof(unsigned), hipMemcpyDeviceToHost, c->read_stream));
-    HIP_TRY(c, hipStreamSynchronize(c->read_stream));
-    memcpy(raw, c->h_range, RANGE_WORDS * sizeof(unsigned));
-    return DAVO_OK;
-}
-
-unsigned* ring_record(davo_ctx* c, int r) { return c->d_range_base + RANGE_WORDS * (1 + r); }
-
-void note_seen(davo_ctx* c, const unsigned raw[6], const int* shifts) {
-    for (int i = 0; i < 6; ++i) {
-        float v;
-        memcpy(&v, &raw[i], sizeof v);
-        const float t = ldexpf(v, -shifts[i]);
-        if (!(t <= c->range_seen[i])) c->range_seen[i] = t;          // NaN / inf records stay visible
-    }
-}
-
-int zero_base_record(davo_ctx* c, hipStream_t s) {
-    HIP_TRY(c, hipMemsetAsync(c->d_range_base, 0, RANGE_WORDS * sizeof(unsigned), s));
-    return DAVO_OK;
-}
-
-// Every stream idle.  The ring's running maxima (params.h) are about to lose their meaning - a failed verdict, or the scales are
-// going to change: read the record of every batch that is still waiting for its verdict into its ticket first, then reset the ring.
-int freeze_pending_and_reset_ring(davo_ctx* c) {
-    for (Ticket& t : c->tickets)
-        if (!t.frozen) {
-            // every stream the context knows is idle, so the mirrors are final - unless the batch went out on a caller's stream the
-            // context no longer runs on (davo_set_stream judges its tickets before a switch; this is the belt to those braces)
-            const unsigned* m = c->h_range + RANGE_WORDS * (1 + t.ring);
-            if (__atomic_load_n(&m[RANGE_SEQ], __ATOMIC_ACQUIRE) != t.seq) {
-                HIP_TRY(c, hipStreamSynchronize(t.stream));
-                if (__atomic_load_n(&m[RANGE_SEQ], __ATOMIC_ACQUIRE) != t.seq) return fail(c, DAVO_ERR_HIP, "a batch finished without reporting its range record");
-            }
-            memcpy(t.raw, m, sizeof t.raw);
-            t.frozen = true;
-        }
-    { int rc = zero_now(c, c->d_range_base + RANGE_WORDS, RANGE_RING * RANGE_WORDS * sizeof(unsigned)); if (rc) return rc; }
-    return DAVO_OK;
-}
-
-// power-of-two storage scales from a sample batch: each pass runs the path and moves every layer's largest stored
-// value into [512, 1024).  A layer computed from badly ranged inputs still has about the right magnitude, so each
-// pass fixes at least the first badly ranged layer exactly and the later ones to within a few powers of two.
-// Runs on the base record; every stream must be idle.  sel: davo_calibrate runs both pairs of the batch it is handed; a re-issue
-// calibrates on the pairs the batch ran (an unselected frame's planes may never have been copied: stale bytes).
-int calibrate_on(davo_ctx* c, int B, const Inputs& in, void* d_pose, int sel) {
-    int rc = DAVO_OK;
-    Run run = make_run(c, 0);
-    run.pairs = sel; run.precision = 1; run.impl = 0;
-    for (int pass = 0; pass < 8 && rc == DAVO_OK; ++pass) {
-        if ((rc = zero_base_record(c, run.stream))) break;
-        rc = forward_device(c, run, B, in, d_pose);
-        if (rc) break;
-        if (hipStreamSynchronize(run.stream) != hipSuccess) { rc = fail(c, DAVO_ERR_HIP, "hipStreamSynchronize failed"); break; }
-        unsigned raw[RANGE_WORDS];
-        if ((rc = read_record(c, c->d_range_base, raw))) break;
-        bool changed = false;
-        for (int i = 0; i < 6; ++i) {
-            float v;
-            memcpy(&v, &raw[i], sizeof v);
-            int delta = 0;
-            if (!std::isfinite(v)) delta = -32;
-            else if (v > 0.f) { int e; (void)frexpf(v, &e); delta = 10 - e; }        // stored max -> [2^9, 2^10): 64x headroom
-            int ns = c->act_shift[i] + delta;
-            ns = ns < -60 ? -60 : (ns > 60 ? 60 : ns);
-            if (ns != c->act_shift[i]) { c->act_shift[i] = ns; changed = true; }
-        }
-        if (!changed) break;
-    }
-    (void)zero_base_record(c, run.stream);
-    return rc;
-}
-
-// one batch, synchronously, on the base record; -> DAVO_OK, DAVO_ERR_RANGE (the verdict) or a hard error
-int run_judged(davo_ctx* c, const Run& run, const Ticket& b) {
-    { int rc = zero_base_record(c, run.stream); if (rc) return rc; }
-    RunResult res;
-    int rc = forward_device(c, run, b.B, b.in, b.pose, &res);
-    if (rc) return rc;
-    HIP_TRY(c, hipStreamSynchronize(run.stream));
-    if (!res.h3) return DAVO_OK;
-    unsigned raw[RANGE_WORDS];
-    if ((rc = read_record(c, c->d_range_base, raw))) return rc;
-    rc = check_range(c, raw);
-    if (rc == DAVO_OK) note_seen(c, raw, c->act_shift);
-    return rc;
-}
-
-// A failed verdict: re-issue the batch, with the pair selection it was issued with (Ticket::pairs) - as issued if the scales have moved since and now hold it, re-calibrated on itself if
-// not, on the float32 kernels if even that leaves the range (per-layer scales cannot cover e.g. an inf / NaN producing net).
-// Drains every stream first: the re-issue uses slot 0's workspace and the base record.
-// A caller may have handed the batch's pose buffer to a LATER batch since (two alternating buffers, one buffer overwritten every
-// step): the re-issue therefore writes into a pose buffer of the context and is copied to the caller's only if no batch
-// issued after this one targets an overlapping range - the newest writer of a buffer always wins (pose_spans: davo_forward_device).
-bool pose_superseded(const davo_ctx* c, const Ticket& t) {
-    const uintptr_t lo = (uintptr_t)t.pose, hi = lo + (size_t)t.B * 12 * sizeof(float);
-    for (const PoseSpan& sp : c->pose_spans)
-        if (sp.issue > t.issue && sp.lo < hi && lo < sp.hi) return true;
-    return false;
-}
-
-int recover_batch(davo_ctx* c, const Ticket& orig) {
-    { int rc = sync_all_slots(c); if (rc) return rc; }
-    const std::string verdict = c->err;
-    { int rc = freeze_pending_and_reset_ring(c); if (rc) return rc; }       // the failed slot's maximum must go; the scales may move
-    if (!c->d_reissue_pose) HIP_TRY(c, hipMalloc(reinterpret_cast<void**>(&c->d_reissue_pose), (size_t)c->max_batch * 12 * sizeof(float)));
-    Ticket b = orig;
-    b.pose = c->d_reissue_pose;
-    Run run = make_run(c, 0);
-    run.pairs = b.pairs;
-    int rc = run_judged(c, run, b);
-    if (rc == DAVO_ERR_RANGE) {
-        if ((rc = calibrate_on(c, b.B, b.in, b.pose, b.pairs))) return rc;
-        ++c->n_recalibrations;
-        rc = run_judged(c, run, b);
-        c->range_report = "re-calibrated: " + verdict;
-    }
-    if (rc == DAVO_ERR_RANGE) {
-        run.precision = 0;
-        rc = forward_device(c, run, b.B, b.in, b.pose);
-        if (rc == DAVO_OK && hipStreamSynchronize(run.stream) != hipSuccess) rc = fail(c, DAVO_ERR_HIP, "hipStreamSynchronize failed");
-        ++c->n_f32_batches;
-        c->range_report = "float32 kernels for one batch: " + verdict;
-    }
-    if (rc) return rc;
-    HIP_TRY(c, hipStreamSynchronize(run.stream));
-    if (!pose_superseded(c, orig))
-        HIP_TRY(c, hipMemcpy(orig.pose, c->d_reissue_pose, (size_t)orig.B * 12 * sizeof(float), hipMemcpyDeviceToDevice));
-    ++c->n_reissued;
-    c->err.clear();
-    return DAVO_OK;
-}
-
-// verdict on the oldest unjudged device-path batch (waits for that batch only)
-int judge_front(davo_ctx* c) {
-    const Ticket t = c->tickets.front();
-    c->tickets.pop_front();
-    unsigned raw[RANGE_WORDS];
-    int rc = DAVO_OK;
-    if (t.frozen) memcpy(raw, t.raw, sizeof raw);        // read when the ring was reset (every stream was idle then)
-    else {
-        // the batch's last kernel writes its sequence number into the slot's host mirror behind the maxima (prologue.h): poll that,
-        // with the stream's own state as the way out if the device has failed
-        volatile const unsigned* m = c->h_range + RANGE_WORDS * (1 + t.ring);
-        for (unsigned spin = 0; m[RANGE_SEQ] != t.seq; ++spin) {
-            if ((spin & 1023u) == 1023u) {
-                const hipError_t q = hipStreamQuery(t.stream);
-                if (q == hipSuccess) {                                    // the stream is idle: the store is on its way or the kernel never ran
-                    if (m[RANGE_SEQ] == t.seq) break;
-                    HIP_TRY(c, hipStreamSynchronize(t.stream));
-                    if (m[RANGE_SEQ] != t.seq) return fail(c, DAVO_ERR_HIP, "a batch finished without reporting its range record");
-                    break;
-                }
-                if (q != hipErrorNotReady) return fail(c, DAVO_ERR_HIP, "hipStreamQuery failed: %s", hipGetErrorString(q));
-            }
-        }
-        __atomic_thread_fence(__ATOMIC_ACQUIRE);
-        for (int i = 0; i < RANGE_WORDS; ++i) raw[i] = m[i];
-    }
-    if (rc == DAVO_OK) {
-        rc = check_range(c, raw, t.shifts);
-        if (rc == DAVO_OK) note_seen(c, raw, t.shifts);
-        else if (rc == DAVO_ERR_RANGE && c->opt_auto_range) {
-            // the batch's last kernel reached the same verdict on the same record and kept the inputs (prologue.h)
-            if (t.snap && raw[RANGE_SNAP] != 1u) rc = fail(c, DAVO_ERR_INVALID, "internal: a batch failed its range verdict but its inputs were not kept");
-            else {
-                rc = recover_batch(c, t);
-                // a davo_submit batch: the re-issue rewrote the pose ring entry, its page-locked twin follows (every stream is idle)
-                if (rc == DAVO_OK && t.h_pose && hipMemcpy(t.h_pose, t.pose, (size_t)t.B * 12 * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess)
-                    rc = fail(c, DAVO_ERR_HIP, "copying re-issued poses to the host failed");
-            }
-        } else if (rc == DAVO_ERR_RANGE && !t.frozen) {
-            // no recovery ("auto_range" 0): the slot's running maximum has served its verdict - the next batch starts afresh
-            const std::string keep = c->err;
-            if (hipMemsetAsync(ring_record(c, t.ring), 0, RANGE_WORDS * sizeof(unsigned), c->read_stream) != hipSuccess ||
-                hipStreamSynchronize(c->read_stream) != hipSuccess) rc = fail(c, DAVO_ERR_HIP, "resetting a range record failed");
-            else c->err = keep;
-        }
-    }
-    c->ring_busy[t.ring] = false;              // after the re-issue: it read the slot's copy of the inputs
-    return rc;
-}
-
-// every unjudged batch; a failed verdict with "auto_range" 0 does not stop the others from being judged
-int judge_all(davo_ctx* c) {
-    int first = c->sticky_range_rc;
-    std::string first_err = c->sticky_range_err;
-    c->sticky_range_rc = 0; c->sticky_range_err.clear();
-    while (!c->tickets.empty()) {
-        const int rc = judge_front(c);
-        if (rc == DAVO_ERR_RANGE) { if (!first) { first = rc; first_err = c->err; } }
-        else if (rc) { for (auto& t : c->tickets) c->ring_busy[t.ring] = false; c->tickets.clear(); return rc; }
-    }
-    { int rc = sync_all_slots(c); if (rc) return rc; }
-    if (first) { c->err = first_err; return first; }
-    return DAVO_OK;
-}
-
-// the batch about to be issued takes ring slot ring_next: judge what still holds it (may re-issue: before the slot rotation)
-// every batch davo_forward_device issues leaves the range of its pose buffer here (pose_superseded); entries no pending ticket can
-// be older than are dropped
-void note_pose_span(davo_ctx* c, const void* d_pose, int B) {
-    ++c->n_issued;
-    const unsigned long long oldest = c->tickets.empty() ? c->n_issued : c->tickets.front().issue;
-    while (!c->pose_spans.empty() && c->pose_spans.front().issue <= oldest) c->pose_spans.pop_front();
-    if (!c->tickets.empty()) c->pose_spans.push_back(PoseSpan{(uintptr_t)d_pose, (uintptr_t)d_pose + (size_t)B * 12 * sizeof(float), c->n_issued});
-}
-
-int ticket_reserve(davo_ctx* c) {
-    while (c->ring_busy[c->ring_next]) {
-        const int rc = judge_front(c);
-        if (rc == DAVO_ERR_RANGE && !c->opt_auto_range) {          // reported by the next davo_synchronize; this batch is issued all the same
-            if (!c->sticky_range_rc) { c->sticky_range_rc = rc; c->sticky_range_err = c->err; }
-        } else if (rc) return rc;
-    }
-    return DAVO_OK;
-}
-
-// ... the batch's kernels record into the slot's record; its last kernel keeps the inputs there if the record fails: *run is told so.
-// *t receives what is known of the batch's ticket now: above all what a re-issue would read
-int ticket_begin(davo_ctx* c, Run* run, int B, const Inputs& in, Ticket* t, bool own_inputs = false) {
-    const int r = c->ring_next;
-    *t = Ticket{};
-    t->B = B; t->ring = r; t->pairs = run->pairs; t->stream = run->stream;
-    // own_inputs: the batch reads a staging set of the context (davo_submit), which the next batches overwrite whatever the caller declared
-    t->snap = c->opt_auto_range && (!c->opt_stable_inputs || own_inputs);
-    if (t->snap && (((uintptr_t)in.img | (uintptr_t)in.flow | (uintptr_t)in.seg | (uintptr_t)in.depth) & 15)) return fail(c, DAVO_ERR_INVALID, "device input buffers must be 16-byte aligned");
-    { int rc = ensure_ring(c, t->snap); if (rc) return rc; }
-    run->range = ring_record(c, r);
-    run->zero_record = true;
-    // The records hold RUNNING maxima (params.h): "clamped" is exact per batch, "too small" is judged on everything a slot has stored
-    // since its record was last zeroed.  So that a long stream that never synchronises still notices activations that collapse,
-    // every FRESH_EVERY-th batch starts from a zeroed record (a memset in stream order ahead of the batch's kernels; that batch pays
-    // its first round's atomics, ~0.2 ms, once in FRESH_EVERY batches).
-    if (++c->since_fresh_record >= FRESH_EVERY) {
-        c->since_fresh_record = 0;
-        HIP_TRY(c, hipMemsetAsync(run->range, 0, 6 * sizeof(unsigned), run->stream));
-        if (c->posenn_se) HIP_TRY(c, hipMemsetAsync(run->range + RANGE_SE, 0, sizeof(unsigned), run->stream));
-    }
-    if (++c->batch_seq == 0) c->batch_seq = 1;
-    t->seq = c->batch_seq;
-    const InputSet keep = t->snap ? c->snap_sets[r] : InputSet();      // no snapshot: no destination, and the ticket remembers the caller's buffers
-    t->in = t->snap ? keep.view() : in;
-    const PlaneBytes nb = plane_bytes(c);
-    auto src = [](const void* q) { return static_cast<const uint8_t*>(q); };
-    auto dst = [](void* q) { return static_cast<uint8_t*>(q); };
-    run->snap = SnapArgs{run->range, c->h_range_dev + RANGE_WORDS * (1 + r), c->batch_seq,
-                       src(in.img), src(in.flow), src(in.seg), dst(keep.img), dst(keep.flow), dst(keep.seg),
-                       (unsigned)(nb.img / 16), (unsigned)(nb.flow / 32), (unsigned)(nb.flow / 16), (unsigned)(nb.seg / 16), B,
-                       src(in.depth), dst(keep.depth), c->posenn_se};
-    return DAVO_OK;
-}
-
-// the batch is out (rc, res: forward_device's): its ticket is filed
-int ticket_end(davo_ctx* c, int rc, const RunResult& res, Ticket t, void* d_pose, float* h_pose = nullptr) {
-    if (rc) return rc;
-    if (res.f32_fallback) ++c->n_f32_batches;
-    if (!res.h3) return DAVO_OK;                                                 // float32 kernels (weight guard): no record, no verdict
-    t.pose = d_pose; t.h_pose = h_pose; t.issue = c->n_issued;
-    for (int i = 0; i < 6; ++i) t.shifts[i] = c->act_shift[i];
-    c->tickets.push_back(t);
-    c->ring_busy[t.ring] = true;
-    c->ring_next = (t.ring + 1) % RING;
     return DAVO_OK;
 }
 
@@ -541,12 +247,12 @@ static int forward_device_entry(davo_ctx* c, int B, const void* d_img, const voi
     c->next_slot = (c->next_slot + 1) % c->inflight;
     Ticket t{};
     if (ticketed) { int rc = ticket_begin(c, &run, B, in, &t); if (rc) return rc; }
-    if (!ticketed && c->pose_spans.size() > 64) {          // float32 batches behind pending f16x3 tickets: bounded
+    if (!ticketed && c->book.spans_full()) {               // float32 batches behind pending f16x3 tickets: bounded
         const int rc = judge_all(c);
-        if (rc == DAVO_ERR_RANGE) { c->sticky_range_rc = rc; c->sticky_range_err = c->err; }       // "auto_range" 0: reported by the next davo_synchronize
+        if (rc == DAVO_ERR_RANGE) c->book.defer(rc, c->err);       // "auto_range" 0: reported by the next davo_synchronize (judge_all has just emptied the store)
         else if (rc) return rc;
     }
-    note_pose_span(c, d_pose, B);
+    c->book.note_issue(d_pose, B);
     RunResult res;
     if (!elapsed_ms) {
         int rc = forward_device(c, run, B, in, d_pose, &res);
@@ -656,20 +362,14 @@ int stage_inputs(davo_ctx* c, const InputSet& set, const Inputs& host, int b0, i
     return DAVO_OK;
 }
 
-bool ticket_pending(const davo_ctx* c, unsigned seq) {
-    for (const Ticket& t : c->tickets) if (t.seq == seq) return true;
-    return false;
-}
-
 // the oldest undelivered batch: verdict (and re-issue) first, then its poses go to the caller's array
 int deliver_front(davo_ctx* c) {
     const StreamJob j = c->jobs.front();
     c->jobs.pop_front();
-    while (j.ticketed && ticket_pending(c, j.seq)) {
+    while (j.ticketed && c->book.pending(j.seq)) {
         const int rc = judge_front(c);
-        if (rc == DAVO_ERR_RANGE && !c->opt_auto_range) {          // "auto_range" 0: reported by the next davo_synchronize; the poses are delivered as they are
-            if (!c->sticky_range_rc) { c->sticky_range_rc = rc; c->sticky_range_err = c->err; }
-        } else if (rc) return rc;
+        if (rc == DAVO_ERR_RANGE && !c->opt_auto_range) c->book.defer(rc, c->err);      // reported by the next davo_synchronize; the poses are delivered as they are
+        else if (rc) return rc;
     }
     HIP_TRY(c, hipEventSynchronize(c->pose_done[j.pr]));
     memcpy(j.pose_out, c->h_pose_ring[j.pr], (size_t)j.B * 12 * sizeof(float));
@@ -715,7 +415,7 @@ static int submit_entry(davo_ctx* c, int B, const uint8_t* img, const float* flo
 
     Ticket t{};
     if (ticketed) { int rc = ticket_begin(c, &run, B, set.view(), &t, true); if (rc) return rc; }
-    ++c->n_issued;                    // (no pose span: a pose ring entry is not reused before its batch has been delivered)
+    c->book.note_issue();             // (no pose span: a pose ring entry is not reused before its batch has been delivered)
     RunResult res;
     int rc = forward_device(c, run, B, set.view(), c->d_pose_ring[pr], &res);
     if (ticketed) rc = ticket_end(c, rc, res, t, c->d_pose_ring[pr], c->h_pose_ring[pr]);
@@ -860,8 +560,7 @@ static int forward_entry(davo_ctx* c, int B, const uint8_t* img, const float* fl
     // call's 417.  "Clamped" stays exact per call (the call that pushes a maximum past 65504 fails, and every recovery path zeroes
     // the record); "too small" is judged on what has been stored since the record was last zeroed: by a recovery, a change of scales,
     // and every FRESH_EVERY-th call.
-    if (++c->host_since_fresh >= FRESH_EVERY) {
-        c->host_since_fresh = 0;
+    if (c->book.host_record_due()) {
         HIP_TRY(c, hipMemsetAsync(c->d_range_base, 0, RANGE_WORDS * sizeof(unsigned), run.stream));
     }
     // Sub-batches: the copy of chunk i+1 (copy_stream) overlaps the kernels of chunk i (compute stream).
@@ -894,8 +593,7 @@ static int forward_entry(davo_ctx* c, int B, const uint8_t* img, const float* fl
             HIP_TRY(c, hipStreamWaitEvent(run.stream, c->copy_done[i], 0));
         }
         if (h3_call && i == nchunks - 1) {       // the call's last kernel mirrors the finished record (all sub-batches) to the host
-            if (++c->batch_seq == 0) c->batch_seq = 1;
-            seq = c->batch_seq;
+            seq = c->book.next_seq();
             run.snap.record = c->d_range_base; run.snap.host_mirror = c->h_range_dev; run.snap.seq = seq; run.snap.B = nb; run.snap.se = c->posenn_se;
         }
         int rc = forward_device(c, run, nb, from_window(c, c->host_set.view(), b0), (float*)c->s_pose + (size_t)b0 * 12, &res);
@@ -912,16 +610,17 @@ static int forward_entry(davo_ctx* c, int B, const uint8_t* img, const float* fl
     HIP_TRY(c, hipStreamSynchronize(run.stream));
     memcpy(pose_out, c->h_sync_pose, (size_t)B * 12 * sizeof(float));
     if (!res.h3) return export_last();
+    // The call ran f16x3 (res is the last sub-batch's), so that sub-batch carried run.snap - h3_call reads the same impl and precision
+    // run does - and its last kernel, pose_from_tiles or range_guard_snapshot (forward.hip), has stored the record and seq in the
+    // mirror; the stream is idle, so the wait returns at once
     unsigned raw[RANGE_WORDS];
-    int rc = DAVO_OK;
-    if (seq && __atomic_load_n(&c->h_range[RANGE_SEQ], __ATOMIC_ACQUIRE) == seq) memcpy(raw, c->h_range, sizeof raw);      // the stream is idle: the mirror is final
-    else rc = read_record(c, c->d_range_base, raw);
+    int rc = wait_record(c, c->h_range, seq, run.stream, raw);
     if (rc) return rc;
-    rc = check_range(c, raw);
-    if (rc == DAVO_OK) note_seen(c, raw, c->act_shift);
+    rc = judge_record(c, raw, c->act_shift);
     if (rc == DAVO_ERR_RANGE && c->opt_auto_range) {
-        // the staged copy of the batch is still in HBM: re-issue it whole (recalibrated, or on the float32 kernels)
-        rc = recover_batch(c, [&] { Ticket t{}; t.B = B; t.pairs = c->pairs; t.in = c->host_set.view(); t.pose = c->s_pose; t.ring = -1; t.stream = run.stream; t.issue = ~0ull; return t; }());
+        // the staged copy of the batch is still in HBM: re-issue it whole (recalibrated, or on the float32 kernels); nothing has
+        // been issued since, so its pose buffer is its own
+        rc = recover_batch(c, Reissue{B, c->pairs, c->host_set.view(), c->s_pose, false, 0});
         if (rc == DAVO_OK) HIP_TRY(c, hipMemcpy(pose_out, c->s_pose, (size_t)B * 12 * sizeof(float), hipMemcpyDeviceToHost));
         // the re-issue ran the whole batch as one forward and produced the poses returned: every window's exports come from it, in
         // the precision and under the scales it ran with (what the sub-batches exported above is overwritten)
@@ -989,7 +688,7 @@ int davo_set_activation_shifts(davo_ctx* c, const int* shifts) {
     if (!c) return DAVO_ERR_INVALID;
     { int rc = judge_all(c); if (rc) return rc; }             // batches issued under the old scales get their verdict first
     { int rc = freeze_pending_and_reset_ring(c); if (rc) return rc; }      // maxima stored under the old scales say nothing about the new
-    c->host_since_fresh = FRESH_EVERY;                                       // ... the host path's record included: its next call starts afresh
+    c->book.host_record_stale();                                             // ... the host path's record included: its next call starts afresh
     for (int i = 0; i < 6; ++i) {
         const int s = shifts ? shifts[i] : 0;
         if (s < -60 || s > 60) return fail(c, DAVO_ERR_INVALID, "activation shift %d outside [-60,60]", s);
@@ -1010,10 +709,7 @@ int davo_reset_range_state(davo_ctx* c) {
     { int rc = zero_now(c, c->d_range_base, RANGE_WORDS * sizeof(unsigned)); if (rc) return rc; }
     for (int i = 0; i < 7; ++i) c->act_shift[i] = 0;
     for (int i = 0; i < 6; ++i) c->range_seen[i] = 0.f;
-    c->host_since_fresh = 1 << 30;                                           // the counters' and the cursor's initial values (ctx.h)
-    c->since_fresh_record = 0;
-    c->ring_next = 0;
-    c->sticky_range_rc = 0; c->sticky_range_err.clear();
+    c->book.reset();                                                         // the counters' and the cursor's initial values, no deferred verdict
     c->range_report.clear();
     if (verdict) { c->err = verdict_err; return verdict; }
     return DAVO_OK;

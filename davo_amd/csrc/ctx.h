@@ -5,6 +5,7 @@
 // Translation units (built in parallel by davo_amd/_lib.py, linked into one shared library):
 //   api.hip         extern "C" entry points (context, weights, forward, calibration, test hooks); owns the InputSets
 //   forward.hip     the forward plan of the pose path (which kernel, which buffers, in what order)
+//   range_guard.hip the f16x3 range guard: records, verdicts, calibration, re-issues, tickets (its bookkeeping: range_book.h)
 //   plan.hip        launch planning: tile shapes and whole-round launch splits (pure host logic)
 //   weights.hip     weight re-layout: HWIO float32 -> packed f32 / split-fp16 operands
 //   launch_f32.hip  conv_igemm_f32 instantiations + dispatch
@@ -32,8 +33,11 @@
 
 #include "../../include/davo_hip.h"
 #include "params.h"
+#include "range_book.h"
 
 namespace davo {
+
+static_assert(RECORD_WORDS == RANGE_WORDS, "range_book.h sizes a ticket's copy of its record");
 
 struct HostTensor {
     std::vector<float> data;
@@ -76,11 +80,6 @@ struct Slot {
     unsigned* d_counters = nullptr;              // "last workgroup" tickets (pose_tail.h): [0] cnv7's pose tail, [1 + b] triplet b's squeeze, [1 + max_batch + t] tile t of a split-K launch
 };
 
-// The planes of one batch, as every host function hands them on: img [B][H][W][9] bytes, flow [B][8][H][W], seg [B][3][H][W] and
-// depth [B][3][H][W] float32 in file order (src0, tgt, src1).  depth is read by the depth sources only (att_source 11, 12) and is
-// null for every other variant.
-struct Inputs { const void *img, *flow, *seg, *depth; };
-
 // Device room of the context for max_batch windows of every plane the variant reads (api.hip: alloc_input_set / free_input_set);
 // depth stays null unless the variant reads it, so a set's view says by itself whether there are depth planes to carry along.
 struct InputSet {
@@ -88,27 +87,7 @@ struct InputSet {
     Inputs view() const { return Inputs{img, flow, seg, depth}; }
 };
 
-// A batch davo_forward_device has issued whose f16x3 range record has not been judged yet.  Every such batch owns one slot of a
-// small ring: a range record of its own and - unless the caller declared its inputs stable - room for a context-owned copy of
-// its inputs, which the batch's last kernel fills if (and only if) the record will fail the verdict, so that the re-issue reads
-// exactly what was issued whatever the caller has done to its buffers since (api.hip, prologue.h).
-constexpr int RANGE_RING = 8;
 constexpr int SK_TILE_COUNTERS = 256;            // tiles of a split-K launch whose fix-up is folded in (forward.hip): at most one per CU
-struct Ticket {
-    int B;
-    int pairs;                                 // the pair selection the batch was issued with: every re-issue runs the same pairs, whatever davo_set_pairs said since
-    Inputs in;                                 // what a re-issue reads: the ring slot's snapshot, or the caller's buffers ("stable_inputs")
-    void* pose;
-    int ring;
-    bool snap;                                 // `in` is the ring slot's copy
-    bool frozen;                               // raw holds the batch's record (read before the ring's records were reset)
-    unsigned raw[RANGE_WORDS];
-    unsigned seq;                              // the batch's sequence number: its last kernel writes it into the slot's host mirror
-    hipStream_t stream;                        // the stream it was issued on
-    int shifts[6];                             // storage scales the batch was issued under (davo_activation_range reports true magnitudes)
-    unsigned long long issue;                  // issue number of the batch (pose_superseded, api.hip)
-    float* h_pose;                             // davo_submit batches: page-locked host copy of `pose`, refreshed after a re-issue (else null)
-};
 
 // A batch davo_submit has issued whose poses have not been delivered to the caller's array yet (api.hip: streaming entry point).
 // Its inputs live in the staging set of its in-flight slot (at most MAX_INFLIGHT slots), its poses in entry `pr` of a ring of STREAM_POSES device
@@ -138,8 +117,6 @@ struct RunResult {
     bool h3 = false;                           // f16x3 kernels: the record holds this batch's maxima
     bool f32_fallback = false;                 // float32 kernels because of the weight guard (counted once per API call by the caller)
 };
-
-struct PoseSpan { uintptr_t lo, hi; unsigned long long issue; };      // the pose buffer range of an issued batch (api.hip: pose_superseded)
 
 struct Comm;                                     // comm.hip: RCCL communicator state
 
@@ -230,17 +207,12 @@ struct davo_ctx {
     // batch from the context's own copy of its inputs - recalibrated, or on the float32 kernels (api.hip)
     bool opt_auto_range = true;
     bool opt_stable_inputs = false;            // "stable_inputs": the caller keeps inputs unchanged until the verdict, no copies are taken
-    std::deque<davo::Ticket> tickets;
-    bool ring_busy[davo::RANGE_RING] = {};
-    int ring_next = 0;
+    davo::RangeBook book;                      // the guard's bookkeeping: ring cursor, tickets, pose spans, deferred verdict (range_book.h)
     davo::InputSet snap_sets[davo::RANGE_RING];        // the ring slots' input snapshots (allocated by the first ticket that wants one)
     hipStream_t read_stream = nullptr;
-    unsigned batch_seq = 0;                    // sequence number of the last ticketed batch (never 0 for a batch)
     unsigned* h_range = nullptr;               // page-locked: [0] landing pad of a record read, [1 + r] the mirror ring slot r's last kernel writes
     unsigned* h_range_dev = nullptr;           // ... as the device sees it
     float range_seen[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};      // largest true |activation| judged since the last reset
-    int sticky_range_rc = 0;                   // "auto_range" 0: a failed verdict met while issuing is reported by the next davo_synchronize
-    std::string sticky_range_err;
     std::string range_report;                  // what the range management last did, in words (davo_range_report)
     long long n_recalibrations = 0, n_f32_batches = 0, n_reissued = 0;
     int host_chunk = 8;                        // davo_forward: windows per sub-batch (davo_set_option "host_chunk"; 0 = whole batch)
@@ -258,10 +230,6 @@ struct davo_ctx {
     std::deque<davo::StreamJob> jobs;
     unsigned long long n_submitted = 0;
     float* d_reissue_pose = nullptr;           // a re-issued batch writes here first; copied to its own pose buffer unless a later batch has taken that
-    std::deque<davo::PoseSpan> pose_spans;     // pose buffer ranges of the batches issued since the oldest pending ticket
-    unsigned long long n_issued = 0;
-    int host_since_fresh = 1 << 30;            // davo_forward calls since the base record was last zeroed (api.hip); the first call starts afresh
-    int since_fresh_record = 0;                // ticketed batches since one last started from a zeroed range record (api.hip: ticket_begin)
     // profiling
     bool prof = false;
     bool prof_dominant_only = false;           // profile mode 2: bracket only the main cnv6 launch
@@ -319,7 +287,7 @@ inline int ilog2_exact(int v) {
 
 // the stream slot i runs on: its own, or the caller's for slot 0 (davo_set_stream)
 inline hipStream_t slot_stream(const davo_ctx* c, int i) { return (c->user_stream && i == 0) ? c->user_stream : c->slots[i].stream; }
-// a batch in slot i as the context's settings of the moment say, on the base record (api.hip: ticket_begin moves it to a record of its own)
+// a batch in slot i as the context's settings of the moment say, on the base record (range_guard.hip: ticket_begin moves it to a record of its own)
 inline Run make_run(const davo_ctx* c, int i) {
     return Run{i, slot_stream(c, i), c->d_range_base, false, SnapArgs{}, c->pairs, c->precision, c->impl};
 }
@@ -367,8 +335,25 @@ inline void split_f16(float v, _Float16* hi, _Float16* lo) {
 // ---- forward.hip ----------------------------------------------------------------------------
 // B windows of `in' -> d_pose, run as `run' says; *res (if not null) receives what really ran
 int forward_device(davo_ctx* c, const Run& run, int B, const Inputs& in, void* d_pose, RunResult* res = nullptr);
-// f16x3: verdict on a range record read back from the device; DAVO_ERR_RANGE names the layer
-int check_range(davo_ctx* c, const unsigned* raw /*[RANGE_WORDS]*/, const int* shifts = nullptr);
+
+// ---- api.hip --------------------------------------------------------------------------------
+int zero_now(davo_ctx* c, void* p, size_t bytes);                              // hipMemset that returns when the bytes ARE zero
+int alloc_input_set(davo_ctx* c, InputSet* s, bool zero_unread);
+
+// ---- range_guard.hip: what the entry points need of the f16x3 range guard --------------------
+int ensure_ring(davo_ctx* c, bool snapshots);                                  // the records' host mirrors (and the ring's input snapshots)
+// the record of sequence number seq is final in mirror m (its last kernel ran on stream s) -> raw; at once where s is idle
+int wait_record(davo_ctx* c, const unsigned* m, unsigned seq, hipStream_t s, unsigned raw[RANGE_WORDS]);
+int judge_record(davo_ctx* c, const unsigned* raw /*[RANGE_WORDS]*/, const int* shifts);      // the verdict: DAVO_ERR_RANGE names the layer
+int recover_batch(davo_ctx* c, const Reissue& b);                              // a failed verdict: re-issue (as is, recalibrated, float32)
+int judge_front(davo_ctx* c);                                                  // verdict (and re-issue) of the oldest pending ticket
+int judge_all(davo_ctx* c);                                                    // ... of every one; returns the deferred verdict, if any
+int freeze_pending_and_reset_ring(davo_ctx* c);                                // every stream idle, the scales are about to change
+int calibrate_on(davo_ctx* c, int B, const Inputs& in, void* d_pose, int sel);
+// a ticketed batch: the ring slot is free / *run records into it, *t says what a re-issue would read / the batch is out
+int ticket_reserve(davo_ctx* c);
+int ticket_begin(davo_ctx* c, Run* run, int B, const Inputs& in, Ticket* t, bool own_inputs = false);
+int ticket_end(davo_ctx* c, int rc, const RunResult& res, Ticket t, void* d_pose, float* h_pose = nullptr);
 
 // ---- comm.hip -------------------------------------------------------------------------------
 void comm_release(davo_ctx* c);

@@ -82,37 +82,6 @@ int prof_collect(davo_ctx* c) {
     return DAVO_OK;
 }
 
-// f16x3 only.  Stored activations (fp16 hi/lo pairs) are float32-grade while the layer's largest stored value is
-// below the fp16 maximum (above it values were clamped) and not so small that the pairs lose their low bits
-// (tools/exp_activation_scale.py: with ONE layer off its scale the 1e-4 bar holds down to ~2^-16 of O(1) activations; with
-// all six stored layers at the floor the errors add up, so the guard is 2^-6: docs/F16X3_NUMERICS.md, "The guard's floor").
-int check_range(davo_ctx* c, const unsigned* raw, const int* shifts) {
-    static const char* names[6] = {"cnv1", "cnv2", "cnv3", "cnv4", "cnv5", "cnv6"};
-    if (!shifts) shifts = c->act_shift;              // the scales the judged batch was issued under
-    for (int i = 0; i < 6; ++i) {
-        float v;
-        if (i == 5 && c->posenn_se) {                // in the order of the forward: between cnv5 and cnv6
-            // the scaled cnv5 of the feature-attention variant is a stored activation of its own.  It shares cnv5's scale and every
-            // factor is a sigmoid, so it cannot clamp where cnv5 did not, but it can sink below the floor - and no calibration moves
-            // it there without moving cnv5: such a batch ends on the float32 kernels (api.hip: recover_batch)
-            memcpy(&v, &raw[RANGE_SE], sizeof v);
-            if (range_value_fails(v))
-                return fail(c, DAVO_ERR_RANGE, "cnv5_se activations (cnv5 times its feature-attention scales) are at most %.4g: %s for the fp16-pair "
-                            "storage at cnv5's scale 2^%d - davo_set_precision(ctx, 0)", (double)ldexpf(v, -shifts[4]),
-                            v < 65504.f ? "too small" : "outside the range", shifts[4]);
-        }
-        memcpy(&v, &raw[i], sizeof v);
-        if (!range_value_fails(v)) continue;         // params.h: the test the batch's last kernel applies too
-        const float actual = ldexpf(v, -shifts[i]);
-        if (!(v < 65504.f))
-            return fail(c, DAVO_ERR_RANGE, "%s activations reach %.4g: outside the fp16-pair storage range at scale 2^%d "
-                        "(values were clamped) - run davo_calibrate() or davo_set_precision(ctx, 0)", names[i], (double)actual, shifts[i]);
-        return fail(c, DAVO_ERR_RANGE, "%s activations are at most %.4g: too small for the fp16-pair storage at scale 2^%d "
-                        "- run davo_calibrate() or davo_set_precision(ctx, 0)", names[i], (double)actual, shifts[i]);
-    }
-    return DAVO_OK;
-}
-
 namespace {
 
 constexpr int MAX_WEIGHT_CHANNEL_SPREAD_LOG2 = 14;     // f16x3 per-channel guard (weights.hip)

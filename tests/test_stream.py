@@ -10,7 +10,7 @@ import sys
 import numpy as np
 import pytest
 
-from davo_amd import DAVO, Engine, synth, parse_version, FLAGSHIP_VERSION
+from davo_amd import DAVO, DavoRangeError, Engine, synth, parse_version, FLAGSHIP_VERSION
 from davo_amd import _lib
 from davo_amd import sequence as S
 
@@ -297,6 +297,103 @@ def test_recycled_pose_buffer_never_receives_a_late_reissue(c_oracle):
     for k in range(8):
         assert_pose_close(own[k].download((B, 2, 6)), wants[k], "own buffer, batch %d" % k)
     e.close(); e2.close()
+
+
+# ---- deferred verdicts: "auto_range" 0, a failed verdict met while issuing or delivering ------------------------------------
+# Flagship variant, f16x3, 64x96, B = 2, cnv3 clamping (_rescaled(weights, 16)), no recovery: an entry point that has to judge an
+# older batch on the way (its ring slot comes round, its poses are delivered, too many float32 spans pile up behind it) issues
+# or delivers all the same, and the verdict is davo_synchronize's - once.  Nothing is re-issued, so every pose buffer holds what
+# the batch computes when it is issued alone.
+_DV_B, _DV_H, _DV_W, _DV_N = 2, 64, 96, 10
+
+
+def _deferred_engine():
+    cfg = parse_version(FLAGSHIP_VERSION)
+    e = _engine(cfg, _DV_H, _DV_W, _DV_B, _rescaled(synth.make_weights(cfg), 16), "f16x3")
+    e.set_option("auto_range", 0)
+    return e
+
+
+def _sync_raises_the_cnv3_verdict_once(e):
+    with pytest.raises(DavoRangeError, match="cnv3 activations"):
+        e.synchronize()
+    e.synchronize()
+
+
+@pytest.fixture(scope="module")
+def deferred_alone():
+    """-> (ten batches, the poses of each issued alone: one davo_forward_device, one davo_synchronize - which raises)"""
+    e = _deferred_engine()
+    data = [synth.make_inputs(_DV_B, _DV_H, _DV_W, first_window=3 * k) for k in range(_DV_N)]
+    pose = e.alloc(_DV_B * 48)
+    alone = []
+    for d in data:
+        bufs = [e.alloc(a.nbytes).upload(a) for a in d]
+        e.forward_device(_DV_B, *bufs, pose)
+        with pytest.raises(DavoRangeError, match="cnv3 activations"):
+            e.synchronize()
+        alone.append(pose.download((_DV_B, 2, 6)))
+        alone[-1].setflags(write=False)
+        for b in bufs:
+            b.free()
+    e.close()
+    assert np.abs(alone[0] - alone[1]).max() > 1e-3                      # the batches are told apart by their poses
+    return data, alone
+
+
+def test_deferred_verdict_device_path_when_the_ring_wraps(deferred_alone):
+    """Ten davo_forward_device calls without a synchronize: the ring of eight wraps, calls nine and ten judge batches one and two
+    to get their slots, and neither raises; davo_synchronize raises the verdict once."""
+    data, alone = deferred_alone
+    e = _deferred_engine()
+    st = e.range_stats()
+    sets = [tuple(e.alloc(a.nbytes).upload(a) for a in d) for d in data]
+    poses = [e.alloc(_DV_B * 48) for _ in data]
+    for k in range(_DV_N):
+        e.forward_device(_DV_B, *sets[k], poses[k])
+    _sync_raises_the_cnv3_verdict_once(e)
+    for k in range(_DV_N):
+        assert np.array_equal(poses[k].download((_DV_B, 2, 6)), alone[k]), k
+    assert e.range_stats() == st
+    e.close()
+
+
+def test_deferred_verdict_submit_with_two_in_flight(deferred_alone):
+    """Three davo_submit batches on two slots and a davo_wait: the poses are delivered as they are, without raising;
+    davo_synchronize raises the verdict once."""
+    data, alone = deferred_alone
+    e = _deferred_engine()
+    st = e.range_stats()
+    e.set_inflight(2)
+    outs = [np.full((_DV_B, 2, 6), np.nan, np.float32) for _ in range(3)]
+    for k in range(3):
+        e.submit(*data[k], outs[k])
+    e.wait()
+    assert e.pending() == 0
+    for k in range(3):
+        assert np.array_equal(outs[k], alone[k]), k
+    _sync_raises_the_cnv3_verdict_once(e)
+    assert e.range_stats() == st
+    e.close()
+
+
+def test_deferred_verdict_float32_batches_behind_a_pending_ticket(deferred_alone):
+    """One f16x3 davo_forward_device, then 66 float32 ones: past the bound of 64 pose spans kept behind a pending ticket the
+    ticket is judged by a float32 call, which does not raise; davo_synchronize raises the verdict once."""
+    data, alone = deferred_alone
+    e = _deferred_engine()
+    st = e.range_stats()
+    bufs = tuple(e.alloc(a.nbytes).upload(a) for a in data[0])
+    pose, pose32 = e.alloc(_DV_B * 48), e.alloc(_DV_B * 48)
+    e.forward_device(_DV_B, *bufs, pose)
+    e.set_precision("f32")
+    for _ in range(66):
+        e.forward_device(_DV_B, *bufs, pose32)
+    _sync_raises_the_cnv3_verdict_once(e)
+    assert np.array_equal(pose.download((_DV_B, 2, 6)), alone[0])
+    assert np.isfinite(pose32.download((_DV_B, 2, 6))).all()
+    assert e.range_stats() == st
+    e.close()
 
 
 # ---- the rank launcher with two ranks on the box's GPU ----------------------------------------------------------------
