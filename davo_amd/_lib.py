@@ -48,6 +48,7 @@ EXPORTS = (
     "davo_comm_allreduce", "davo_comm_barrier", "davo_comm_destroy", "davo_plan_layer", "davo_tile_filter_rows",
     "davo_set_pairs", "davo_get_pairs",
     "davo_set_feature_export", "davo_forward_features",
+    "davo_pad_class_tables", "davo_pad_class_tile_order", "davo_plan_layer_f32",
 )
 COMM_ID_BYTES = 128
 
@@ -224,6 +225,10 @@ def _load():
     ip = ctypes.POINTER(i)
     L.davo_plan_layer.argtypes = [i, i, i, ip, ip, ip]
     L.davo_tile_filter_rows.argtypes = [i] * 8 + [ip, ip, i, ip]
+    usp = ctypes.POINTER(ctypes.c_uint16)
+    L.davo_pad_class_tables.argtypes = [i] * 8 + [ip, usp]
+    L.davo_pad_class_tile_order.argtypes = [usp, i, i, i, ip]
+    L.davo_plan_layer_f32.argtypes = [i] * 4 + [ip, ip, ip]
     L.davo_comm_preload.argtypes = [ctypes.c_char_p, i]
     L.davo_comm_unique_id.argtypes = [vp, ctypes.c_char_p, i]
     L.davo_comm_init.argtypes = [vp, i, i, vp]

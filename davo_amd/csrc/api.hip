@@ -11,6 +11,7 @@
 
 #include "ctx.h"
 #include "launch.h"
+#include "pad_classes.h"
 #include "plan.h"
 
 using namespace davo;
@@ -774,6 +775,7 @@ void davo_destroy(davo_ctx* c) {
     void* misc[] = {c->d_reissue_pose, c->d_range_base, c->d_splitk, c->d_pose_tiles, c->d_w1patch, c->d_w2patch, c->d_w3patch, c->d_w1patch_f32, c->d_w2patch_f32, c->d_w3patch_f32, c->d_zeros, c->d_wpred, c->d_bpred, c->s_pose};
     for (auto p : misc) if (p) (void)hipFree(p);
     for (auto& kv : c->tile_orders) if (kv.second) (void)hipFree(kv.second);
+    for (auto& kv : c->pad_tables) { (void)hipFree(kv.second.row_pixel); (void)hipFree(kv.second.tile_taps); }
     for (auto& pe : c->prof_entries)
         for (auto& ab : pe.pending) { (void)hipEventDestroy(ab.first); (void)hipEventDestroy(ab.second); }
     for (auto e : c->event_pool) (void)hipEventDestroy(e);
@@ -946,6 +948,12 @@ int davo_set_option(davo_ctx* c, const char* key, int value) {
     else if (k == "tile_208x128") c->opt_tile_208x128 = value != 0;
     else if (k == "merge_order") c->opt_merge_order = value < 0 ? -1 : (value > 2 ? 0 : value);
     else if (k == "skip_order") c->opt_skip_order = value < 0 ? 0 : (value > 2 ? 2 : value);
+    else if (k == "pad_classes") {
+        // 0 off | 1 the default layers | 8 + mask: the layers of the mask (1 cnv4, 2 cnv5, 4 cnv6)
+        if (value == 0 || value == 1) c->opt_pad_classes = value ? PAD_CLASS_LAYERS : 0;
+        else if (value >= 8 && value <= 15) c->opt_pad_classes = value & 7;
+        else return fail(c, DAVO_ERR_INVALID, "pad_classes must be 0, 1 or 8 + a layer mask (8..15), got %d", value);
+    }
     else if (k == "patch_cnv2") c->opt_patch_cnv2 = value != 0;
     else if (k == "patch_cnv3") c->opt_patch_cnv3 = value != 0;
     else if (k == "fold_tails") c->opt_fold_tails = value < 0 ? -1 : (value > 2 ? 1 : value);
@@ -1072,6 +1080,32 @@ int davo_tile_filter_rows(int m0, int m1, int Hout, int Wout, int Hin, int strid
     if (chunk_map)
         for (int v = 0; v < 3 * fr.nky * nblocks; ++v) chunk_map[v] = h3_real_chunk(v, fr.ky0, fr.nky);
     return DAVO_OK;
+}
+
+int davo_pad_class_tables(int NB, int Hout, int Wout, int Hin, int Win, int pad_t, int pad_l, int rate, int* row_pixel, unsigned short* tile_taps) {
+    if (!row_pixel || !tile_taps || NB < 1 || Hout < 1 || Wout < 1 || Hin < 1 || Win < 1 || rate < 1 || (long)NB * Hout * Wout > 0x7fffff00L) return DAVO_ERR_INVALID;
+    std::vector<int32_t> rows;
+    std::vector<uint16_t> taps;
+    const bool sorted = pad_class_tables(NB, Hout, Wout, Hin, Win, pad_t, pad_l, rate, BM, &rows, &taps);
+    memcpy(row_pixel, rows.data(), rows.size() * sizeof(int32_t));
+    memcpy(tile_taps, taps.data(), taps.size() * sizeof(uint16_t));
+    return sorted ? 1 : 0;
+}
+
+int davo_pad_class_tile_order(const unsigned short* tile_taps, int mtile0, int mtiles, int ntiles_n, int* order) {
+    if (!tile_taps || !order || mtile0 < 0 || mtiles < 1 || ntiles_n < 1) return DAVO_ERR_INVALID;
+    std::vector<int> o;
+    pad_class_tile_order(tile_taps, mtile0, mtiles, ntiles_n, &o);
+    memcpy(order, o.data(), o.size() * sizeof(int));
+    return DAVO_OK;
+}
+
+int davo_plan_layer_f32(int mtiles, int npad, int groups, int ncu, int* mtile0, int* launch_mtiles, int* tile_bn) {
+    if (mtiles < 1 || npad < 32 || npad % 32 || groups < 1 || ncu < 1 || !mtile0 || !launch_mtiles || !tile_bn) return DAVO_ERR_INVALID;
+    const std::vector<Launch> plan = plan_layer(mtiles, npad, groups, ncu);
+    if (plan.empty() || plan.size() > 2) return DAVO_ERR_INVALID;
+    for (size_t i = 0; i < plan.size(); ++i) { mtile0[i] = plan[i].mtile0; launch_mtiles[i] = plan[i].mtiles; tile_bn[i] = plan[i].BN; }
+    return (int)plan.size();
 }
 
 int davo_plan_layer(int M, int npad, int groups, int* rows, int* tile_bm, int* tile_bn) {

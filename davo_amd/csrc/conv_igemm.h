@@ -91,9 +91,12 @@ __device__ __forceinline__ int xcd_remap(int bid, int nwg) {
 
 // LAYER only names the instantiation (0 = generic, 1..7 = cnv1..cnv7) so that rocprofv3's
 // per-kernel statistics separate the layers that share a tile shape (cnv4/cnv5/cnv6).
-template <int KS, int STRIDE, int BN, int LAYER>
+// PC (pad classes, pad_classes.h): the tile's GEMM rows are the pixels p.row_pixel names, and the tile walks the taps of p.tile_taps
+// instead of a range of filter rows.  PC = false compiles to the code it was before the switch existed.
+template <int KS, int STRIDE, int BN, int LAYER, bool PC = false>
 __device__ __forceinline__ void conv_igemm_f32_body(const ConvParams& p, const int wg_x, const int nwg_x, const int wg_y) {
     using T = Tile<BN>;
+    static_assert(!PC || (KS == 3 && STRIDE == 1 && BN >= 32 && BN <= 128), "pad classes: the dilated 3x3 stride-1 layers on four-wave tiles");
     constexpr bool N16 = BN == 16;             // 16 output columns: four waves of 32 x 16 on v_mfma_f32_16x16x4_f32
     extern __shared__ __attribute__((aligned(16))) float smem[];
     float* As = smem;                          // [2][BM][LDK]
@@ -120,8 +123,10 @@ __device__ __forceinline__ void conv_igemm_f32_body(const ConvParams& p, const i
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
         if (j >= T::A_LOADS) { iy0[j] = -(1 << 28); ix0[j] = 0; pix0[j] = 0; continue; }
-        const int m = mtile * BM + r0 + RPP * j;
-        if (m < p.M) {
+        int m = mtile * BM + r0 + RPP * j;
+        bool m_ok = m < p.M;
+        if constexpr (PC) { m = p.row_pixel[m]; m_ok = m >= 0; }       // the table is padded to whole tiles with -1
+        if (m_ok) {
             const int hw = p.Hout * p.Wout;
             const int n = m / hw, rem = m - n * hw;
             const int oy = rem / p.Wout, ox = rem - oy * p.Wout;
@@ -151,6 +156,15 @@ __device__ __forceinline__ void conv_igemm_f32_body(const ConvParams& p, const i
     int st0 = 0, st1 = 0, st2 = 0, st3 = 0;                       // floats to the same pixel's next 32 channels, or 0
     const int cpt = p.cin_log2 >= 5 ? 1 << (p.cin_log2 - 5) : 1;  // chunks per tap
     int l_cb = 0;                                                 // chunk inside the current tap (every launch starts on a tap boundary)
+    // PC: the taps still to load, lowest bit = the tap the next loaded chunk belongs to.  Wave-uniform, like l_cb: chunks are
+    // loaded strictly in walking order, so "the next chunk" is (lowest tap, l_cb) whatever q_ the caller names
+    int pc_taps = 0;
+    int* pc_rows = reinterpret_cast<int*>(smem + 2 * (BM + BN) * LDK);   // PC: the tile's 128 row_pixel entries, behind the staging buffers
+    if constexpr (PC) {
+        pc_taps = __builtin_amdgcn_readfirstlane(p.tile_taps[mtile]) & 0x1ff;
+        if (pc_taps == 0) pc_taps = 1 << 4;                       // (never: the centre tap is real for every pixel)
+        if (tid < BM) pc_rows[tid] = p.row_pixel[mtile * BM + tid];   // read by the epilogue, behind the loop's barriers
+    }
 #define DAVO_ADDR_A(j_, ptr_, st_)                                                                 \
     {                                                                                              \
         const int iy = iy0[j_] + dy, ix = ix0[j_] + dx;                                            \
@@ -163,7 +177,7 @@ __device__ __forceinline__ void conv_igemm_f32_body(const ConvParams& p, const i
 #define DAVO_LOAD_CHUNK(q_) DAVO_LOAD_CHUNK_R(q_, ra0, ra1, ra2, ra3, rb0, rb1, rb2, rb3)
 #define DAVO_LOAD_CHUNK_R(q_, ra0, ra1, ra2, ra3, rb0, rb1, rb2, rb3)                              \
     {                                                                                              \
-        const int kg = (q_) * BK + kk;                                                             \
+        const int kg = (PC ? __builtin_ctz(pc_taps) * cpt + l_cb : (q_)) * BK + kk;                \
         if (l_cb == 0) {                                                                           \
             const int tap = kg >> p.cin_log2, c = kg & cmask;                                      \
             const int ky = tap / KS, kx = tap - ky * KS;                                           \
@@ -176,6 +190,7 @@ __device__ __forceinline__ void conv_igemm_f32_body(const ConvParams& p, const i
             if constexpr (T::A_LOADS > 2) { pa2 += st2; pa3 += st3; }                              \
         }                                                                                          \
         l_cb = l_cb + 1 == cpt ? 0 : l_cb + 1;                                                     \
+        if (PC && l_cb == 0) pc_taps &= pc_taps - 1;                                               \
         ra0 = *reinterpret_cast<const float4*>(pa0);                                               \
         ra1 = *reinterpret_cast<const float4*>(pa1);                                               \
         if constexpr (T::A_LOADS > 2) {                                                            \
@@ -238,7 +253,9 @@ __device__ __forceinline__ void conv_igemm_f32_body(const ConvParams& p, const i
     // valid_filter_rows): here chunks run tap by tap, so a filter row is one contiguous run of 3 * Cin / 32 chunks.
     // The skipped terms are exact zeros: the float32 fma chain of every output is the oracle's without them.
     int q0 = 0, q1 = p.nchunks;
-    if constexpr (KS == 3) {
+    if constexpr (PC) {
+        q1 = __builtin_popcount(pc_taps) * cpt;                   // q only counts the walked chunks; which chunk is which: pc_taps
+    } else if constexpr (KS == 3) {
         if (p.cin_log2 >= 5) {
             const FilterRows fr = valid_filter_rows(mtile * BM, min(mtile * BM + BM, p.M) - 1, p.Hout, p.Wout, p.Hin, STRIDE, p.pad_t, p.rate);
             const int per_row = 3 << (p.cin_log2 - 5);
@@ -445,15 +462,18 @@ __device__ __forceinline__ void conv_igemm_f32_body(const ConvParams& p, const i
     // Interior tile (every row < M, every column < Cout: all but a launch's last tile row): a uniform 64-bit tile base and 32-bit
     // offsets, no bounds tests - the general loop below pays a 64-bit address product and two compares per value, 64 values per lane:
     // a tenth of cnv4's 18-chunk tiles.
-    if (DAVO_F32_FAST_EPILOGUE && (mtile + 1) * BM <= p.M && (ntile + 1) * BN <= p.Cout) {
-        float* __restrict__ tbase = yg + (long)mtile * BM * p.y_ld + ntile * BN;
+    // PC: row r of the tile is pixel pc_rows[r] (no -1 among them in a tile of whole rows); the uniform base is the layer's, and
+    // the 32-bit element offsets must then span the whole activation
+    if (DAVO_F32_FAST_EPILOGUE && (mtile + 1) * BM <= p.M && (ntile + 1) * BN <= p.Cout && (!PC || (long)p.M * p.y_ld <= 0x7fffffffL)) {
+        float* __restrict__ tbase = yg + (PC ? 0L : (long)mtile * BM * p.y_ld) + ntile * BN;
         const unsigned ld = (unsigned)p.y_ld;
         const bool relu = p.relu != 0;
 #pragma unroll
         for (int i = 0; i < T::TM; ++i)
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const unsigned roff = (unsigned)(wm * T::TM * 32 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh) * ld + (unsigned)(wn * T::TN * 32 + li);
+                const int trow = wm * T::TM * 32 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
+                const unsigned roff = (unsigned)(PC ? pc_rows[trow] : trow) * ld + (unsigned)(wn * T::TN * 32 + li);
 #pragma unroll
                 for (int j = 0; j < T::TN; ++j) {
                     float v = acc[i][j][r];
@@ -473,10 +493,10 @@ __device__ __forceinline__ void conv_igemm_f32_body(const ConvParams& p, const i
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
                 const int row = wm * T::TM * 32 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
-                const int m = mtile * BM + row;
+                const int m = PC ? pc_rows[row] : mtile * BM + row;
                 float v = acc[i][j][r];
                 if (p.relu) v = fmaxf(v, 0.f);
-                if (n_ok && m < p.M) yg[(long)m * p.y_ld + n] = v;
+                if (n_ok && (PC ? m >= 0 : m < p.M)) yg[(long)m * p.y_ld + n] = v;
             }
     }
 }
@@ -484,6 +504,13 @@ __device__ __forceinline__ void conv_igemm_f32_body(const ConvParams& p, const i
 template <int KS, int STRIDE, int BN, int LAYER>
 __global__ __launch_bounds__(256, 2) void conv_igemm_f32(ConvParams p) {
     conv_igemm_f32_body<KS, STRIDE, BN, LAYER>(p, blockIdx.x, gridDim.x, blockIdx.y);
+}
+
+// the same kernel on class-sorted rows (PC above): cnv4, cnv5, cnv6 of the float32 path; 512 bytes of LDS more (the tile's row table)
+constexpr int PC_LDS_EXTRA = BM * 4;
+template <int KS, int STRIDE, int BN, int LAYER>
+__global__ __launch_bounds__(256, 2) void conv_igemm_f32_pc(ConvParams p) {
+    conv_igemm_f32_body<KS, STRIDE, BN, LAYER, true>(p, blockIdx.x, gridDim.x, blockIdx.y);
 }
 
 // 128 x 256 tile, eight waves (64 x 64 each), one workgroup per CU (round 5 experiment, "f32_n256"): a pixel tile is staged once for
@@ -506,6 +533,13 @@ __global__ __launch_bounds__(256, 2) void conv_igemm_f32_mainrem(ConvParams pm, 
     const int b = blockIdx.x, nm = groups * n_main;
     if (b < nm) conv_igemm_f32_body<KS, STRIDE, 128, LAYER>(pm, b % n_main, n_main, b / n_main);
     else conv_igemm_f32_body<KS, STRIDE, RBN, LAYER>(pr, (b - nm) % n_rem, n_rem, (b - nm) / n_rem);
+}
+
+template <int KS, int STRIDE, int RBN, int LAYER>
+__global__ __launch_bounds__(256, 2) void conv_igemm_f32_mainrem_pc(ConvParams pm, ConvParams pr, int n_main, int n_rem, int groups) {
+    const int b = blockIdx.x, nm = groups * n_main;
+    if (b < nm) conv_igemm_f32_body<KS, STRIDE, 128, LAYER, true>(pm, b % n_main, n_main, b / n_main);
+    else conv_igemm_f32_body<KS, STRIDE, RBN, LAYER, true>(pr, (b - nm) % n_rem, n_rem, (b - nm) / n_rem);
 }
 
 #undef DAVO_ADDR_A

@@ -118,6 +118,15 @@ struct RunResult {
     bool f32_fallback = false;                 // float32 kernels because of the weight guard (counted once per API call by the caller)
 };
 
+// device tables of a layer whose GEMM rows are sorted by padding class (pad_classes.h), and the host copy of the per-tile tap masks
+// (what a tile costs: tile_order_pc, forward.hip)
+struct PadTables {
+    int* row_pixel = nullptr;
+    unsigned short* tile_taps = nullptr;
+    std::vector<uint16_t> host_taps;
+};
+constexpr int PAD_CLASS_LAYERS = 6;              // "pad_classes" 1: cnv5 | cnv6 (bits: 1 cnv4, 2 cnv5, 4 cnv6).  cnv4 measured level (245.2 -> 243.4 us, inside its run-to-run spread) and stays on the natural order
+
 struct Comm;                                     // comm.hip: RCCL communicator state
 
 }  // namespace davo
@@ -141,6 +150,8 @@ struct davo_ctx {
     int opt_merge_order = -1;                  // merged grids: 0 = short tiles offset inside every XCD, 1 = per XCD, 2 = main tiles (long first) then the remainder; -1 = 2 where a tile order exists, else 0
     int opt_skip_order = 1;                    // launches whose tiles skip different numbers of padding rows of the filter hand out the long tiles first (tile_order_for, forward.hip): 0 = never, 1 = float32 launches, 2 = the f16x3 merged grids too
     std::map<std::vector<int>, int*> tile_orders;   // device tables of those launches, by (layer, tile rows, tiles, ...); nullptr = uniform
+    int opt_pad_classes = davo::PAD_CLASS_LAYERS;                  // float32: the layers of the mask (1 cnv4, 2 cnv5, 4 cnv6) run on rows sorted by padding class, every tile walks only the taps that are real for its own pixels (pad_classes.h)
+    std::map<std::vector<int>, davo::PadTables> pad_tables;   // their device tables, by (layer, pair images, map, padding, rate)
     bool opt_tile_208x128 = false;             // f16x3: cnv4 may run on the four-wave 208x128 tile (conv_igemm_h3s.h; measured 8 % behind the 128x128 tile at B = 32: off)
     bool opt_merge_cnv4 = false;               // f16x3: cnv4 as whole rounds of 256x128 tiles + 128x128 remainder tiles in one grid where the batch allows
     bool opt_share_taps = true;                // f16x3: cnv3..cnv6 stage one pixel patch per filter row for its three taps

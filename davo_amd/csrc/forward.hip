@@ -16,6 +16,7 @@
 
 #include "ctx.h"
 #include "launch.h"
+#include "pad_classes.h"
 #include "plan.h"
 
 namespace davo {
@@ -131,6 +132,59 @@ const int* tile_order_for(davo_ctx* c, int li, int kind, int bm, int mtile0, int
     return dev;
 }
 
+// ---- class-sorted rows (pad_classes.h; "pad_classes") -------------------------------------------------
+// The device tables of one layer at one shape: built at the first batch of that shape, kept until the context goes.
+// nullptr with *rc set: the tables could not be put on the device - an error, never the natural order in silence.  nullptr with
+// *rc DAVO_OK: at this shape the sorted rows walk no fewer taps than the natural order (pad_classes.h), the layer runs without tables.
+const PadTables* pad_tables_for(davo_ctx* c, int li, int NB, int Hout, int Wout, int Hin, int Win, int pad_t, int pad_l, int rate, int* rc) {
+    *rc = DAVO_OK;
+    const std::vector<int> key = {li, NB, Hout, Wout, Hin, Win, pad_t, pad_l, rate};
+    auto it = c->pad_tables.find(key);
+    if (it != c->pad_tables.end()) return it->second.row_pixel ? &it->second : nullptr;
+    PadTables t;
+    std::vector<int32_t> rows;
+    if (!pad_class_tables(NB, Hout, Wout, Hin, Win, pad_t, pad_l, rate, BM, &rows, &t.host_taps)) {
+        c->pad_tables[key] = PadTables();                       // remembered: nothing to build at this shape
+        return nullptr;
+    }
+    auto upload = [&](void** dev, const void* src, size_t bytes) {
+        if (hipMalloc(dev, bytes) != hipSuccess) { *dev = nullptr; return false; }
+        return hipMemcpy(*dev, src, bytes, hipMemcpyHostToDevice) == hipSuccess;
+    };
+    if (!upload(reinterpret_cast<void**>(&t.row_pixel), rows.data(), rows.size() * sizeof(int32_t)) ||
+        !upload(reinterpret_cast<void**>(&t.tile_taps), t.host_taps.data(), t.host_taps.size() * sizeof(uint16_t))) {
+        if (t.row_pixel) (void)hipFree(t.row_pixel);
+        if (t.tile_taps) (void)hipFree(t.tile_taps);
+        *rc = fail(c, DAVO_ERR_HIP, "pad-class tables of layer %d: %s", li, hipGetErrorString(hipGetLastError()));
+        return nullptr;
+    }
+    return &(c->pad_tables[key] = std::move(t));
+}
+
+// tile_order_for where the tiles walk their own taps: a tile costs the tap count of its mask, the XCDs' runs are dealt out level
+// (pad_classes.h, pad_class_tile_order)
+const int* tile_order_pc(davo_ctx* c, int li, int mtile0, int mtiles, int ntiles_n, int M, int Hout, int Wout, const PadTables& t) {
+    if (!c->opt_skip_order) return nullptr;
+    const std::vector<int> key = {li, 100, BM, mtile0, mtiles, ntiles_n, M, Hout, Wout};
+    auto it = c->tile_orders.find(key);
+    if (it != c->tile_orders.end()) return it->second;
+    bool uniform = true;
+    for (int m = 1; m < mtiles; ++m) uniform = uniform && tap_count(t.host_taps[mtile0 + m]) == tap_count(t.host_taps[mtile0]);
+    int* dev = nullptr;
+    if (!uniform) {
+        std::vector<int> order;
+        pad_class_tile_order(t.host_taps.data(), mtile0, mtiles, ntiles_n, &order);
+        if (hipMalloc(reinterpret_cast<void**>(&dev), order.size() * sizeof(int)) != hipSuccess ||
+            hipMemcpy(dev, order.data(), order.size() * sizeof(int), hipMemcpyHostToDevice) != hipSuccess) {
+            if (dev) (void)hipFree(dev);
+            dev = nullptr;                                   // not fatal: natural order
+            (void)hipGetLastError();
+        }
+    }
+    c->tile_orders[key] = dev;
+    return dev;
+}
+
 // ---- per-slot scratch -------------------------------------------------------------------------------
 // A scratch buffer of the context with one region of *floats floats per in-flight slot: grown (behind every stream) if this launch
 // needs more per slot than it has, then -> the region of this batch's slot.  extra_bytes: room behind the regions.
@@ -172,7 +226,16 @@ int run_conv_layer(davo_ctx* c, const Run& run, int li, const float* x, int x_ld
         if (pose_mt) *pose_mt = mtiles;
     }
     c->last_plan[li][0] = c->last_plan[li][1] = 0; c->last_split[li] = 1;
+    // cnv4, cnv5, cnv6: GEMM rows sorted by padding class, every tile walks the taps of its own pixels ("pad_classes")
+    const PadTables* pc = nullptr;
+    if (li >= 3 && li <= 5 && ((c->opt_pad_classes >> (li - 3)) & 1) && L.KS == 3 && L.stride == 1 && L.cin_log2 >= 5 && L.groups == 1 && !fuse_pose && !c->opt_f32_n256) {
+        int rc = DAVO_OK;
+        pc = pad_tables_for(c, li, NB, Ho, Wo, Hin, Win, pt, pl, L.rate, &rc);
+        if (rc) return rc;
+        if (pc) { p.row_pixel = pc->row_pixel; p.tile_taps = pc->tile_taps; }
+    }
     auto order_for = [&](const Launch& l, int ntn) {
+        if (pc) return tile_order_pc(c, li, l.mtile0, l.mtiles, ntn, p.M, Ho, Wo, *pc);
         return (L.KS == 3 && L.cin_log2 >= 5) ? tile_order_for(c, li, 0, BM, l.mtile0, l.mtiles, ntn, p.M, Ho, Wo, Hin, L.stride, pt, L.rate) : nullptr;
     };
     // experiment ("f32_n256"): cnv5 / cnv6 as whole rounds of 128 x 256 tiles (eight waves, one workgroup per CU) + a remainder launch of
@@ -219,7 +282,7 @@ int run_conv_layer(davo_ctx* c, const Run& run, int li, const float* x, int x_ld
         p.mtile0 = plan[i].mtile0;
         p.ntiles_n = plan[i].BN == 16 ? 1 : L.npad / plan[i].BN;
         dim3 grid(plan[i].mtiles * p.ntiles_n, L.groups);
-        p.tile_order = (L.KS == 3 && L.cin_log2 >= 5) ? tile_order_for(c, li, 0, BM, plan[i].mtile0, plan[i].mtiles, p.ntiles_n, p.M, Ho, Wo, Hin, L.stride, pt, L.rate) : nullptr;
+        p.tile_order = order_for(plan[i], p.ntiles_n);
         const std::string label = i == 0 ? std::string(L.label) : std::string(L.label) + ".rem";
         ProfScope ps(c, run.stream, label.c_str());
         HIP_TRY(c, launch_layer(li, plan[i].BN, p, grid, run.stream));

@@ -14,6 +14,35 @@ hipError_t launch_conv_t(const ConvParams& p, dim3 grid, hipStream_t s) {
     return hipGetLastError();
 }
 
+// class-sorted rows (pad_classes.h): p.row_pixel / p.tile_taps are set
+template <int BN, int LAYER>
+hipError_t launch_conv_pc_t(const ConvParams& p, dim3 grid, hipStream_t s) {
+    auto kern = conv_igemm_f32_pc<3, 1, BN, LAYER>;
+    hipError_t e = ensure_dynamic_lds(reinterpret_cast<const void*>(kern), Tile<BN>::LDS_BYTES + PC_LDS_EXTRA);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(kern, grid, dim3(256), Tile<BN>::LDS_BYTES + PC_LDS_EXTRA, s, p);
+    return hipGetLastError();
+}
+
+template <int LAYER>
+hipError_t launch_bn_pc(int BN, const ConvParams& p, dim3 grid, hipStream_t s) {
+    switch (BN) {
+        case 32: return launch_conv_pc_t<32, LAYER>(p, grid, s);
+        case 64: return launch_conv_pc_t<64, LAYER>(p, grid, s);
+        case 128: return launch_conv_pc_t<128, LAYER>(p, grid, s);
+    }
+    return hipErrorInvalidValue;
+}
+
+template <int RBN, int LAYER>
+hipError_t launch_mainrem_pc_t(const ConvParams& pm, const ConvParams& pr, int n_main, int n_rem, int groups, hipStream_t s) {
+    auto kern = conv_igemm_f32_mainrem_pc<3, 1, RBN, LAYER>;
+    hipError_t e = ensure_dynamic_lds(reinterpret_cast<const void*>(kern), Tile<128>::LDS_BYTES + PC_LDS_EXTRA);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(kern, dim3((n_main + n_rem) * groups), dim3(256), Tile<128>::LDS_BYTES + PC_LDS_EXTRA, s, pm, pr, n_main, n_rem, groups);
+    return hipGetLastError();
+}
+
 template <int KS, int STRIDE, int LAYER>
 hipError_t launch_bn(int BN, const ConvParams& p, dim3 grid, hipStream_t s) {
     switch (BN) {
@@ -54,6 +83,19 @@ hipError_t launch_layer_n256(int layer, const ConvParams& p, dim3 grid, hipStrea
 // main (128-column tiles) + remainder (rbn-column tiles) of cnv4..cnv7 as one grid (conv_igemm.h: conv_igemm_f32_mainrem)
 hipError_t launch_layer_mainrem(int layer, int rbn, const ConvParams& pm, const ConvParams& pr, int n_main, int n_rem, int groups, hipStream_t s) {
     if (n_main < 8 || n_main % 8 || n_rem < 1 || (groups > 1 && n_rem % 8)) return hipErrorInvalidValue;
+    if ((pm.row_pixel != nullptr) != (pr.row_pixel != nullptr)) return hipErrorInvalidValue;
+    if (pm.row_pixel) {
+        if (!pm.tile_taps || !pr.tile_taps) return hipErrorInvalidValue;
+        switch (layer * 1000 + rbn) {
+            case 3032: return launch_mainrem_pc_t<32, 4>(pm, pr, n_main, n_rem, groups, s);
+            case 3064: return launch_mainrem_pc_t<64, 4>(pm, pr, n_main, n_rem, groups, s);
+            case 4032: return launch_mainrem_pc_t<32, 5>(pm, pr, n_main, n_rem, groups, s);
+            case 4064: return launch_mainrem_pc_t<64, 5>(pm, pr, n_main, n_rem, groups, s);
+            case 5032: return launch_mainrem_pc_t<32, 6>(pm, pr, n_main, n_rem, groups, s);
+            case 5064: return launch_mainrem_pc_t<64, 6>(pm, pr, n_main, n_rem, groups, s);
+        }
+        return hipErrorInvalidValue;          // a missing kernel is an error, never the natural order in silence
+    }
     switch (layer * 1000 + rbn) {
         case 3032: return launch_mainrem_t<3, 1, 32, 4>(pm, pr, n_main, n_rem, groups, s);
         case 3064: return launch_mainrem_t<3, 1, 64, 4>(pm, pr, n_main, n_rem, groups, s);
@@ -88,6 +130,15 @@ hipError_t launch_conv(int KS, int stride, int BN, const ConvParams& p, dim3 gri
 
 hipError_t launch_layer(int layer, int BN, const ConvParams& p, dim3 grid, hipStream_t s) {
     if (layer == 0 && BN == 16) return launch_conv_t<7, 2, 16, 1>(p, grid, s);      // cnv1: 16 output channels, no padded columns
+    if (p.row_pixel) {
+        if (!p.tile_taps) return hipErrorInvalidValue;
+        switch (layer) {
+            case 3: return launch_bn_pc<4>(BN, p, grid, s);
+            case 4: return launch_bn_pc<5>(BN, p, grid, s);
+            case 5: return launch_bn_pc<6>(BN, p, grid, s);
+        }
+        return hipErrorInvalidValue;
+    }
     switch (layer) {
         case 0: return launch_bn<7, 2, 1>(BN, p, grid, s);
         case 1: return launch_bn<5, 2, 2>(BN, p, grid, s);

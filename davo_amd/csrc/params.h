@@ -117,6 +117,10 @@ struct ConvParams {
     const float* pose_w;    // [groups][256][3] pred kernels; null = store the activation as before
     float* pose_partial;
     int pose_P, pose_mt;    // output pixels per image (>= 128), M tiles of the whole layer
+    // class-sorted rows (pad_classes.h; the conv_igemm_f32_pc kernels only): GEMM row -> flattened output pixel, -1 behind the last one
+    // up to a whole tile; per M tile of the layer, the filter taps (bit ky * 3 + kx) that are real for at least one of its rows
+    const int* row_pixel;
+    const unsigned short* tile_taps;
 };
 
 constexpr int BM = 128;

@@ -398,6 +398,12 @@ const char* davo_range_report(const davo_ctx* ctx);
  *       long tiles first (a device table per launch shape): 0 = never, 1 = in the float32 launches (cnv5 850 -> 793 us),
  *       2 = in the f16x3 merged grids too (cnv5 259.9 -> 256.8 us, a third more HBM reads, same step time under the power cap).
  *       Bit-identical results.
+ *   "pad_classes" (default 1; float32 mode): cnv5 and cnv6 run on GEMM rows sorted by padding class - the pixels of a tile
+ *       share the set of filter taps that land inside the image, and the tile walks only those (davo_pad_class_tables): the
+ *       column taps of the left and right `rate` map columns are dropped too, which no flat run of pixels can do.  The dropped
+ *       terms are exact zeros: bit-identical to 0 = the natural order.  8 + mask (8..15): exactly the layers of the mask (1 cnv4,
+ *       2 cnv5, 4 cnv6); cnv4 has the kernels too but measured level at B = 32 and is not in the default.  Other values are
+ *       refused.  Float32 step at B = 32: 3.553 -> 3.493 ms (cnv5 798 -> 761 us, cnv6 1770 -> 1745 us).
  *   "merge_cnv4" (default 0): cnv4 as whole rounds of 256x128 tiles + 128x128 remainder tiles in one grid like cnv5 / cnv6
  *       ("merge_rem"); measured level with the single launch of 128x128 tiles.  Bit-identical results.
  *   "fuse_pack" (default -1 = auto, which is off: measured level at every batch): 1 = cnv1 builds its input patch from
@@ -502,6 +508,28 @@ int davo_plan_layer(int M, int npad, int groups, int* rows, int* tile_bm, int* t
  * weight rows, of the v-th chunk the f16x3 kernels walk for such a tile.  Returns DAVO_OK or a negative davo_status. */
 int davo_tile_filter_rows(int m0, int m1, int Hout, int Wout, int Hin, int stride, int pad_t, int rate,
                           int* ky0, int* nky, int nblocks, int* chunk_map);
+
+/* Class-sorted GEMM rows of the float32 dilated 3x3 layers on their own (no GPU needed; "pad_classes", csrc/pad_classes.h).
+ * For NB images of a [Hout, Wout] output map read from a [Hin, Win] input with pad_t / pad_l zero rows / columns in front and
+ * dilation `rate` (stride 1):
+ *   row_pixel[ceil(M / 128) * 128], M = NB * Hout * Wout: GEMM row -> flattened output pixel n * Hout * Wout + oy * Wout + ox,
+ *     -1 behind the last pixel.  Images are taken in blocks of ceil(NB / 8); inside a block the pixels are sorted by the set
+ *     of filter taps that land inside the input (descending tap count, ties by ascending mask), in (image, oy, ox) order inside
+ *     a class.  Where tiles that straddle classes would make that order walk no fewer taps than the natural one (few images
+ *     per block), row_pixel is the natural order, row m = pixel m, the masks are that order's, and the layer runs the kernel
+ *     without tables at this shape.  Returns 1 (class-sorted) or 0 (natural order), or a negative davo_status.
+ *   tile_taps[ceil(M / 128)]: bit ky * 3 + kx is set when tap (ky, kx) is real for at least one row of that 128-row tile; the
+ *     kernel walks exactly these taps for the tile.
+ * davo_pad_class_tile_order: order[i], i < mtiles * ntiles_n = the tile (M tile t / ntiles_n of the launch, first M tile mtile0)
+ *   that the i-th workgroup of a launch takes; the eight XCDs run the contiguous eighths of the table (the first (mtiles * ntiles_n)
+ *   % 8 of them one entry longer), each with its long tiles first and all with the same work to within a tile.
+ * davo_plan_layer_f32: the float32 path's launches for a layer of mtiles 128-row tiles x npad output channels on ncu compute
+ *   units: launch i covers M tiles [mtile0[i], mtile0[i] + launch_mtiles[i]) at tile_bn[i] columns; returns 1 or 2.
+ * The latter two return DAVO_OK (the plan: its launch count) or a negative davo_status. */
+int davo_pad_class_tables(int NB, int Hout, int Wout, int Hin, int Win, int pad_t, int pad_l, int rate,
+                          int* row_pixel, unsigned short* tile_taps);
+int davo_pad_class_tile_order(const unsigned short* tile_taps, int mtile0, int mtiles, int ntiles_n, int* order);
+int davo_plan_layer_f32(int mtiles, int npad, int groups, int ncu, int* mtile0, int* launch_mtiles, int* tile_bn);
 
 #ifdef __cplusplus
 }
