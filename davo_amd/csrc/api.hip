@@ -29,17 +29,19 @@ int zero_now(davo_ctx* c, void* p, size_t bytes) {
 
 // Room for max_batch windows of every plane the variant reads.  zero_unread: the flow and label planes start out zero - what the path
 // never reads (flow planes 2,3; the target frame's label map) is never copied into a davo_submit staging set: defined contents all the same
-int alloc_input_set(davo_ctx* c, InputSet* s, bool zero_unread) {
+int alloc_input_set(davo_ctx* c, InputSet* out, bool zero_unread) {
     const PlaneBytes nb = plane_bytes(c);
     const size_t n = (size_t)c->max_batch;
-    HIP_TRY(c, hipMalloc(&s->img, nb.img * n));
-    HIP_TRY(c, hipMalloc(&s->flow, nb.flow * n));
-    HIP_TRY(c, hipMalloc(&s->seg, nb.seg * n));
-    if (needs_depth(c)) HIP_TRY(c, hipMalloc(&s->depth, nb.depth * n));      // always copied whole
+    InputSet s;
+    HIP_TRY(c, dev_alloc(&s.img, nb.img * n));
+    HIP_TRY(c, dev_alloc(&s.flow, nb.flow * n));
+    HIP_TRY(c, dev_alloc(&s.seg, nb.seg * n));
+    if (needs_depth(c)) HIP_TRY(c, dev_alloc(&s.depth, nb.depth * n));      // always copied whole
     if (zero_unread) {
-        { int rc = zero_now(c, s->flow, nb.flow * n); if (rc) return rc; }
-        { int rc = zero_now(c, s->seg, nb.seg * n); if (rc) return rc; }
+        { int rc = zero_now(c, s.flow.get(), nb.flow * n); if (rc) return rc; }
+        { int rc = zero_now(c, s.seg.get(), nb.seg * n); if (rc) return rc; }
     }
+    *out = std::move(s);
     return DAVO_OK;
 }
 
@@ -47,50 +49,37 @@ int alloc_input_set(davo_ctx* c, InputSet* s, bool zero_unread) {
 
 namespace {
 
-void free_input_set(InputSet& s) {
-    for (void* q : {s.img, s.flow, s.seg, s.depth}) if (q) (void)hipFree(q);
-    s = InputSet();
-}
-
-void free_slot(Slot& s) {
-    for (auto p : s.d_act) if (p) (void)hipFree(p);
-    void* misc[] = {s.d_partial, s.d_tab, s.d_packed, s.d_pose_partial, s.d_counters, s.d_se, s.d_se_scale, s.d_se_partial};
-    for (auto p : misc) if (p) (void)hipFree(p);
-    if (s.stream) (void)hipStreamDestroy(s.stream);
-    s = Slot();
-}
-
 // the feature-attention variant's room in one slot (posenn_se.h): the 512-channel scaled tensor of cnv5's geometry (2,048 bytes per
 // pixel in either arithmetic mode), the scale table and the squeeze's partial sums.  Nothing of it exists with the mode off.
-void free_se_workspace(Slot& s) {
-    for (float** p : {&s.d_se, &s.d_se_scale, &s.d_se_partial}) { if (*p) (void)hipFree(*p); *p = nullptr; }
-}
-
 int alloc_se_workspace(davo_ctx* c, Slot* s) {
     const size_t NB = 2 * (size_t)c->max_batch;
-    free_se_workspace(*s);
-    HIP_TRY(c, hipMalloc(reinterpret_cast<void**>(&s->d_se), NB * c->H2 * c->W2 * 512 * sizeof(float)));
-    HIP_TRY(c, hipMalloc(reinterpret_cast<void**>(&s->d_se_scale), NB * 2 * 256 * sizeof(float)));
-    HIP_TRY(c, hipMalloc(reinterpret_cast<void**>(&s->d_se_partial), NB * SE5_CHUNKS * 256 * sizeof(float)));
+    s->se.reset();
+    SeWorkspace w;
+    HIP_TRY(c, dev_alloc(&w.d_se, NB * c->H2 * c->W2 * 512));
+    HIP_TRY(c, dev_alloc(&w.d_se_scale, NB * 2 * 256));
+    HIP_TRY(c, dev_alloc(&w.d_se_partial, NB * SE5_CHUNKS * 256));
+    s->se = std::move(w);
     return DAVO_OK;
 }
 
-// allocate one in-flight slot (stream + activation workspace for max_batch triplets)
-int alloc_slot(davo_ctx* c, Slot* s) {
+// one more in-flight slot (stream + activation workspace for max_batch triplets): appended once it is complete
+int add_slot(davo_ctx* c) {
     const size_t NB = 2 * (size_t)c->max_batch;
-    HIP_TRY(c, hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking));
-    for (int i = 0; i < 7; ++i)
-        HIP_TRY(c, hipMalloc(reinterpret_cast<void**>(&s->d_act[i]), NB * c->act_floats_per_img[i] * sizeof(float)));
-    HIP_TRY(c, hipMalloc(reinterpret_cast<void**>(&s->d_packed), NB * (size_t)c->H * c->W * 10 * sizeof(float)));
+    Slot s;
+    HIP_TRY(c, stream_create(&s.stream));
+    for (int i = 0; i < 7; ++i) HIP_TRY(c, dev_alloc(&s.d_act[i], NB * c->act_floats_per_img[i]));
+    HIP_TRY(c, dev_alloc(&s.d_packed, NB * (size_t)c->H * c->W * 10));
     // squeeze partials: se_flow [B][2 sources][SQ_CHUNKS][2] floats, the class-table sources [B][3 frames][SQ_CHUNKS][SQ_REC] words
-    const size_t partial_bytes = (size_t)c->max_batch * SQ_CHUNKS * (att_class_table(c->v.att_source) ? 3 * SQ_REC : 2 * 2) * sizeof(float);
-    HIP_TRY(c, hipMalloc(reinterpret_cast<void**>(&s->d_partial), partial_bytes));
-    HIP_TRY(c, hipMalloc(reinterpret_cast<void**>(&s->d_tab), (size_t)c->max_batch * 3 * NCLS * sizeof(float)));
-    HIP_TRY(c, hipMalloc(reinterpret_cast<void**>(&s->d_pose_partial), NB * 2 * PH_SPLIT * 3 * sizeof(float)));
-    { int rc = zero_now(c, s->d_partial, partial_bytes); if (rc) return rc; }
-    HIP_TRY(c, hipMalloc(reinterpret_cast<void**>(&s->d_counters), ((size_t)c->max_batch + 1 + SK_TILE_COUNTERS) * sizeof(unsigned)));
-    { int rc = zero_now(c, s->d_counters, ((size_t)c->max_batch + 1 + SK_TILE_COUNTERS) * sizeof(unsigned)); if (rc) return rc; }
-    if (c->posenn_se) { int rc = alloc_se_workspace(c, s); if (rc) return rc; }
+    const size_t partial_floats = (size_t)c->max_batch * SQ_CHUNKS * (att_class_table(c->v.att_source) ? 3 * SQ_REC : 2 * 2);
+    HIP_TRY(c, dev_alloc(&s.d_partial, partial_floats));
+    HIP_TRY(c, dev_alloc(&s.d_tab, (size_t)c->max_batch * 3 * NCLS));
+    HIP_TRY(c, dev_alloc(&s.d_pose_partial, NB * 2 * PH_SPLIT * 3));
+    { int rc = zero_now(c, s.d_partial.get(), partial_floats * sizeof(float)); if (rc) return rc; }
+    const size_t counters = (size_t)c->max_batch + 1 + SK_TILE_COUNTERS;
+    HIP_TRY(c, dev_alloc(&s.d_counters, counters));
+    { int rc = zero_now(c, s.d_counters.get(), counters * sizeof(unsigned)); if (rc) return rc; }
+    if (c->posenn_se) { int rc = alloc_se_workspace(c, &s); if (rc) return rc; }
+    c->slots.push_back(std::move(s));
     return DAVO_OK;
 }
 
@@ -144,12 +133,11 @@ int davo_create(davo_ctx** out, int device, int H, int W, int max_batch, const d
         c->act_ch[i] = ch[i];
         c->act_floats_per_img[i] = px[i] * ch[i];
     }
-    c->slots.resize(1);
-    { int rc = alloc_slot(c, &c->slots[0]); if (rc) return rc; }
-    HIP_TRY(c, hipMalloc(reinterpret_cast<void**>(&c->d_zeros), 256));
-    { int rc = zero_now(c, c->d_zeros, 256); if (rc) return rc; }
-    HIP_TRY(c, hipMalloc(reinterpret_cast<void**>(&c->d_range_base), (1 + RANGE_RING) * RANGE_WORDS * sizeof(unsigned)));
-    { int rc = zero_now(c, c->d_range_base, (1 + RANGE_RING) * RANGE_WORDS * sizeof(unsigned)); if (rc) return rc; }
+    { int rc = add_slot(c); if (rc) return rc; }
+    HIP_TRY(c, dev_alloc(&c->d_zeros, 256 / sizeof(float)));
+    { int rc = zero_now(c, c->d_zeros.get(), 256); if (rc) return rc; }
+    HIP_TRY(c, dev_alloc(&c->d_range_base, (1 + RANGE_RING) * RANGE_WORDS));
+    { int rc = zero_now(c, c->d_range_base.get(), (1 + RANGE_RING) * RANGE_WORDS * sizeof(unsigned)); if (rc) return rc; }
     return DAVO_OK;
 }
 
@@ -170,7 +158,7 @@ int davo_set_posenn_se(davo_ctx* c, int mode) {
     c->needed = needed_names(c->v, mode);
     for (Slot& s : c->slots) {
         if (mode) { int rc = alloc_se_workspace(c, &s); if (rc) return rc; }
-        else free_se_workspace(s);
+        else s.se.reset();
     }
     c->last_slot = 0;
     return DAVO_OK;
@@ -201,7 +189,7 @@ int davo_load_weight(davo_ctx* c, const char* tf_name, const float* data, const 
     // (impl 1: uploaded on demand, forward.hip) - 20 hipMalloc + copies less in front of a rank's first batch
     const std::string nm = tf_name;
     const bool dense = is_dense_weight(nm);
-    if (t.dev) { (void)hipFree(t.dev); t.dev = nullptr; }
+    t.dev.reset();
     if (dense) { int rc = upload(c, t.data, &t.dev); if (rc) return rc; }
     c->packed_ready = false;
     c->packed_h_ready = false;
@@ -259,21 +247,19 @@ static int forward_device_entry(davo_ctx* c, int B, const void* d_img, const voi
         int rc = forward_device(c, run, B, in, d_pose, &res);
         return ticketed ? ticket_end(c, rc, res, t, d_pose) : rc;      // (only a ticketed batch starts as f16x3, so only it can fall back)
     }
-    hipEvent_t e0 = nullptr, e1 = nullptr;
+    EventOwner e0, e1;
     int rc = DAVO_OK;
     auto hip_ok = [&](hipError_t e, const char* what) {
         if (e != hipSuccess && rc == DAVO_OK) rc = fail(c, DAVO_ERR_HIP, "%s failed: %s", what, hipGetErrorString(e));
         return e == hipSuccess;
     };
-    if (hip_ok(hipEventCreate(&e0), "hipEventCreate") && hip_ok(hipEventCreate(&e1), "hipEventCreate") &&
-        hip_ok(hipEventRecord(e0, run.stream), "hipEventRecord")) {
+    if (hip_ok(event_create(&e0), "hipEventCreate") && hip_ok(event_create(&e1), "hipEventCreate") &&
+        hip_ok(hipEventRecord(e0.get(), run.stream), "hipEventRecord")) {
         rc = forward_device(c, run, B, in, d_pose, &res);
-        if (rc == DAVO_OK && hip_ok(hipEventRecord(e1, run.stream), "hipEventRecord") &&
-            hip_ok(hipEventSynchronize(e1), "hipEventSynchronize"))
-            hip_ok(hipEventElapsedTime(elapsed_ms, e0, e1), "hipEventElapsedTime");
+        if (rc == DAVO_OK && hip_ok(hipEventRecord(e1.get(), run.stream), "hipEventRecord") &&
+            hip_ok(hipEventSynchronize(e1.get()), "hipEventSynchronize"))
+            hip_ok(hipEventElapsedTime(elapsed_ms, e0.get(), e1.get()), "hipEventElapsedTime");
     }
-    if (e0) (void)hipEventDestroy(e0);
-    if (e1) (void)hipEventDestroy(e1);
     if (ticketed) rc = ticket_end(c, rc, res, t, d_pose);
     // the timed form is synchronous, so it can judge (and, if need be, re-issue) its own batch; elapsed_ms is the first issue's
     if (rc == DAVO_OK && c->inflight == 1) rc = judge_all(c);
@@ -305,14 +291,17 @@ int davo_forward_device_depth(davo_ctx* c, int B, const void* d_img, const void*
 namespace {
 
 int ensure_stream_state(davo_ctx* c, int slot) {
-    if (!c->d_pose_ring[0])
-        for (int k = 0; k < STREAM_POSES; ++k) {
-            HIP_TRY(c, hipMalloc(reinterpret_cast<void**>(&c->d_pose_ring[k]), (size_t)c->max_batch * 12 * sizeof(float)));
-            HIP_TRY(c, hipHostMalloc(reinterpret_cast<void**>(&c->h_pose_ring[k]), (size_t)c->max_batch * 12 * sizeof(float), hipHostMallocDefault));
-            HIP_TRY(c, hipEventCreateWithFlags(&c->pose_done[k], hipEventDisableTiming));
-            HIP_TRY(c, hipEventCreateWithFlags(&c->st_copied[k], hipEventDisableTiming));
+    if (!c->pose_ring) {
+        PoseRing ring;
+        for (PoseRing::Entry& e : ring.e) {
+            HIP_TRY(c, dev_alloc(&e.dev, (size_t)c->max_batch * 12));
+            HIP_TRY(c, pinned_alloc(&e.host, (size_t)c->max_batch * 12, hipHostMallocDefault));
+            HIP_TRY(c, event_create(&e.pose_done, hipEventDisableTiming));
+            HIP_TRY(c, event_create(&e.copied, hipEventDisableTiming));
         }
-    if (!c->stream_sets[slot].img) { int rc = alloc_input_set(c, &c->stream_sets[slot], true); if (rc) return rc; }
+        c->pose_ring = std::move(ring);
+    }
+    if (!c->stream_sets[slot].built()) { int rc = alloc_input_set(c, &c->stream_sets[slot], true); if (rc) return rc; }
     return DAVO_OK;
 }
 
@@ -335,7 +324,7 @@ Inputs from_window(const davo_ctx* c, const Inputs& in, int b0) {
 int stage_inputs(davo_ctx* c, const InputSet& set, const Inputs& host, int b0, int nb, bool sources_only_seg, int sel, hipStream_t s) {
     const PlaneBytes n = plane_bytes(c);
     const Inputs src = from_window(c, host, b0);
-    auto dst = [b0](void* q, size_t bytes) { return static_cast<uint8_t*>(q) + bytes * b0; };
+    auto dst = [b0](const DevMem<void>& q, size_t bytes) { return static_cast<uint8_t*>(q.get()) + bytes * b0; };
     if (sel != PAIRS_BOTH) {
         const int src1 = sel == PAIRS_SRC1;
         auto copy2d = [&](uint8_t* d, const void* h, size_t pitch, size_t off, size_t width, size_t rows) {
@@ -372,9 +361,17 @@ int deliver_front(davo_ctx* c) {
         if (rc == DAVO_ERR_RANGE && !c->opt_auto_range) c->book.defer(rc, c->err);      // reported by the next davo_synchronize; the poses are delivered as they are
         else if (rc) return rc;
     }
-    HIP_TRY(c, hipEventSynchronize(c->pose_done[j.pr]));
-    memcpy(j.pose_out, c->h_pose_ring[j.pr], (size_t)j.B * 12 * sizeof(float));
+    const PoseRing::Entry& e = c->pose_ring->e[j.pr];           // (a job exists, so the ring does)
+    HIP_TRY(c, hipEventSynchronize(e.pose_done.get()));
+    memcpy(j.pose_out, e.host.get(), (size_t)j.B * 12 * sizeof(float));
     return DAVO_OK;
+}
+
+// every stream the context runs work on is idle: the slots' (and the caller's), the host path's copy stream, the guard's read stream
+void drain_own_streams(davo_ctx* c) {
+    (void)sync_all_slots(c);
+    if (c->host) (void)hipStreamSynchronize(c->host->copy_stream.get());
+    if (c->ring) (void)hipStreamSynchronize(c->ring->read_stream.get());
 }
 
 int deliver_all(davo_ctx* c) {
@@ -395,7 +392,7 @@ static int submit_entry(davo_ctx* c, int B, const uint8_t* img, const float* flo
     if (hold < 0) return fail(c, DAVO_ERR_INVALID, "hold must be >= 0");
     HIP_TRY(c, hipSetDevice(c->device));
     // deliver what has finished (never blocks), and make room in the pose ring (blocks on the oldest batch only when the ring is full)
-    while (!c->jobs.empty() && ((int)c->jobs.size() >= STREAM_POSES || hipEventQuery(c->pose_done[c->jobs.front().pr]) == hipSuccess)) {
+    while (!c->jobs.empty() && ((int)c->jobs.size() >= STREAM_POSES || hipEventQuery(c->pose_ring->e[c->jobs.front().pr].pose_done.get()) == hipSuccess)) {
         const int rc = deliver_front(c);
         if (rc) return rc;
     }
@@ -408,27 +405,28 @@ static int submit_entry(davo_ctx* c, int B, const uint8_t* img, const float* flo
     hipStream_t s = run.stream;
     // H2D on the slot's stream, in order behind the forward that last read this staging set
     const InputSet& set = c->stream_sets[slot];
+    PoseRing::Entry& e = c->pose_ring->e[pr];
     { int rc = stage_inputs(c, set, Inputs{img, flow, seg, depth}, 0, B, true, c->pairs, s); if (rc) return rc; }
     // the caller keeps a batch's inputs unchanged for `hold` more submits.  With hold >= STREAM_POSES the pose ring already implies it
     // (a batch is delivered - so its copies are long done - before the eighth submit after it returns): no event then
     const bool track_copy = hold < STREAM_POSES;
-    if (track_copy) HIP_TRY(c, hipEventRecord(c->st_copied[pr], s));
+    if (track_copy) HIP_TRY(c, hipEventRecord(e.copied.get(), s));
 
     Ticket t{};
     if (ticketed) { int rc = ticket_begin(c, &run, B, set.view(), &t, true); if (rc) return rc; }
     c->book.note_issue();             // (no pose span: a pose ring entry is not reused before its batch has been delivered)
     RunResult res;
-    int rc = forward_device(c, run, B, set.view(), c->d_pose_ring[pr], &res);
-    if (ticketed) rc = ticket_end(c, rc, res, t, c->d_pose_ring[pr], c->h_pose_ring[pr]);
+    int rc = forward_device(c, run, B, set.view(), e.dev.get(), &res);
+    if (ticketed) rc = ticket_end(c, rc, res, t, e.dev.get(), e.host.get());
     if (rc) return rc;
-    HIP_TRY(c, hipMemcpyAsync(c->h_pose_ring[pr], c->d_pose_ring[pr], (size_t)B * 12 * sizeof(float), hipMemcpyDeviceToHost, s));
-    HIP_TRY(c, hipEventRecord(c->pose_done[pr], s));
+    HIP_TRY(c, hipMemcpyAsync(e.host.get(), e.dev.get(), (size_t)B * 12 * sizeof(float), hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipEventRecord(e.pose_done.get(), s));
     c->jobs.push_back(StreamJob{B, pose_out, pr, ticketed && res.h3, t.seq});      // (the weight guard's float32 batches get no ticket)
-    c->copy_tracked[pr] = track_copy;
+    e.copy_tracked = track_copy;
     ++c->n_submitted;
     if (track_copy && (unsigned long long)hold < c->n_submitted) {
         const int q = (int)((c->n_submitted - 1 - hold) % STREAM_POSES);
-        if (c->copy_tracked[q]) HIP_TRY(c, hipEventSynchronize(c->st_copied[q]));
+        if (c->pose_ring->e[q].copy_tracked) HIP_TRY(c, hipEventSynchronize(c->pose_ring->e[q].copied.get()));
         // (a batch submitted with hold >= 8 recorded no event: it has been delivered by now if it is 8 or more submits back, and a
         // caller that lowers `hold` from one call to the next keeps the larger promise for the batches it made it for)
     }
@@ -476,12 +474,6 @@ FxLayout fx_layout(const davo_ctx* c, int cap) {
     return l;
 }
 
-void free_fx_workspace(davo_ctx* c) {
-    if (c->d_fx) (void)hipFree(c->d_fx);
-    c->d_fx = nullptr;
-    c->fx_cap = 0;
-}
-
 bool fx_wanted(const davo_feature_out* o) {
     return o && (o->att_19 || o->attention || o->masked_image || o->image || o->feat_rot || o->feat_trans);
 }
@@ -490,30 +482,32 @@ bool fx_wanted(const davo_feature_out* o) {
 // [b0, b0 + nw) of the caller's arrays of B windows.  Reads d_tab, the inputs and d_act[5] as that forward left them, in the
 // precision it ran (last_precision) and under the storage scale it stored cnv6 with.  Returns with the copies done.
 int export_features(davo_ctx* c, const Inputs& in, int w0, int nw, int b0, int B, const davo_feature_out& out) {
-    if (!c->d_fx || c->fx_cap < 1) return fail(c, DAVO_ERR_INVALID, "internal: no feature export workspace");
+    if (!c->fx || c->fx->cap < 1) return fail(c, DAVO_ERR_INVALID, "internal: no feature export workspace");
+    float* const d_fx = c->fx->d.get();
+    const int fx_cap = c->fx->cap;
     if (c->last_pairs != PAIRS_BOTH || w0 < 0 || w0 + nw > c->last_B) return fail(c, DAVO_ERR_INVALID, "internal: feature export of windows the last forward did not run");
     const size_t HW = (size_t)c->H * c->W, c6 = (size_t)c->v.cnv6_out;
     const bool h3 = c->last_precision == 1;
-    const FxLayout l = fx_layout(c, c->fx_cap);
+    const FxLayout l = fx_layout(c, fx_cap);
     const Slot& ws = last_workspace(c);
     hipStream_t s = last_stream(c);
-    for (int p0 = 0; p0 < nw; p0 += c->fx_cap) {
-        const int np = std::min(c->fx_cap, nw - p0);
+    for (int p0 = 0; p0 < nw; p0 += fx_cap) {
+        const int np = std::min(fx_cap, nw - p0);
         const Inputs win = from_window(c, in, w0 + p0);
-        float* const w_att19 = out.att_19 ? c->d_fx + l.att_19 : nullptr;
-        float* const w_att = out.attention ? c->d_fx + l.attention : nullptr;
-        float* const w_masked = out.masked_image ? c->d_fx + l.masked : nullptr;
-        float* const w_image = out.image ? c->d_fx + l.image : nullptr;
-        float* const w_rot = out.feat_rot ? c->d_fx + l.rot : nullptr;
-        float* const w_trans = out.feat_trans ? c->d_fx + l.trans : nullptr;
+        float* const w_att19 = out.att_19 ? d_fx + l.att_19 : nullptr;
+        float* const w_att = out.attention ? d_fx + l.attention : nullptr;
+        float* const w_masked = out.masked_image ? d_fx + l.masked : nullptr;
+        float* const w_image = out.image ? d_fx + l.image : nullptr;
+        float* const w_rot = out.feat_rot ? d_fx + l.rot : nullptr;
+        float* const w_trans = out.feat_trans ? d_fx + l.trans : nullptr;
         if (w_att19 || w_att || w_masked || w_image) {
             ProfScope ps(c, s, "feature_maps");
             HIP_TRY(c, launch_feature_maps(static_cast<const uint8_t*>(win.img), static_cast<const float*>(win.seg),
-                                           ws.d_tab + (size_t)(w0 + p0) * 3 * NCLS, c->v, np, c->H, c->W, w_att19, w_att, w_masked, w_image, s));
+                                           ws.d_tab.get() + (size_t)(w0 + p0) * 3 * NCLS, c->v, np, c->H, c->W, w_att19, w_att, w_masked, w_image, s));
         }
         if (w_rot || w_trans) {
             ProfScope ps(c, s, "feature_resize_cnv6");
-            HIP_TRY(c, launch_feature_resize_cnv6(h3, ws.d_act[5], w0 + p0, np, c->H2, c->W2, (int)c6, h3 ? ldexpf(1.0f, -c->act_shift[5]) : 1.0f,
+            HIP_TRY(c, launch_feature_resize_cnv6(h3, ws.d_act[5].get(), w0 + p0, np, c->H2, c->W2, (int)c6, h3 ? ldexpf(1.0f, -c->act_shift[5]) : 1.0f,
                                                   w_rot, w_trans, s));
         }
         // the caller's per-frame arrays are [3][B][...], the workspace's [3][np][...]: one copy per frame
@@ -549,11 +543,15 @@ static int forward_entry(davo_ctx* c, int B, const uint8_t* img, const float* fl
     HIP_TRY(c, hipSetDevice(c->device));
     { int rc = deliver_all(c); if (rc) return rc; }          // davo_submit batches still under way: delivered first
     { int rc = sync_all_slots(c); if (rc) return rc; }       // the host path owns the single staging buffer set
-    if (!c->host_set.img) {
-        { int rc = alloc_input_set(c, &c->host_set, false); if (rc) return rc; }
-        HIP_TRY(c, hipMalloc(&c->s_pose, (size_t)c->max_batch * 12 * sizeof(float)));
+    if (!c->host) {
+        HostStaging h;
+        { int rc = alloc_input_set(c, &h.set, false); if (rc) return rc; }
+        HIP_TRY(c, dev_alloc(&h.d_pose, (size_t)c->max_batch * 12));
+        HIP_TRY(c, stream_create(&h.copy_stream));
+        HIP_TRY(c, pinned_alloc(&h.h_pose, (size_t)c->max_batch * 12, hipHostMallocDefault));
+        c->host = std::move(h);
     }
-    if (!c->copy_stream) HIP_TRY(c, hipStreamCreateWithFlags(&c->copy_stream, hipStreamNonBlocking));
+    HostStaging& hs = *c->host;
     { int rc = judge_all(c); if (rc) return rc; }               // device-path batches issued before this call
     Run run = make_run(c, 0);                                   // slot 0, the base record
     // The base record holds RUNNING maxima like the ring's records (params.h): a record that starts at zero is raised by every wave of
@@ -562,17 +560,17 @@ static int forward_entry(davo_ctx* c, int B, const uint8_t* img, const float* fl
     // the record); "too small" is judged on what has been stored since the record was last zeroed: by a recovery, a change of scales,
     // and every FRESH_EVERY-th call.
     if (c->book.host_record_due()) {
-        HIP_TRY(c, hipMemsetAsync(c->d_range_base, 0, RANGE_WORDS * sizeof(unsigned), run.stream));
+        HIP_TRY(c, hipMemsetAsync(c->d_range_base.get(), 0, RANGE_WORDS * sizeof(unsigned), run.stream));
     }
     // Sub-batches: the copy of chunk i+1 (copy_stream) overlaps the kernels of chunk i (compute stream).
     // Results do not depend on the split (windows are independent; tests/test_hip_parity.py batch invariance).
     // Only flow planes 0 and 1 are read by the path (davo.py:978-982), so only those cross PCIe.
     const int chunk = (c->host_chunk > 0 && B >= 2 * c->host_chunk) ? c->host_chunk : B;
     const int nchunks = (B + chunk - 1) / chunk;
-    while ((int)c->copy_done.size() < nchunks) {
-        hipEvent_t e;
-        HIP_TRY(c, hipEventCreateWithFlags(&e, hipEventDisableTiming));
-        c->copy_done.push_back(e);
+    while ((int)hs.copy_done.size() < nchunks) {
+        EventOwner e;
+        HIP_TRY(c, event_create(&e, hipEventDisableTiming));
+        hs.copy_done.push_back(std::move(e));
     }
     bool f32_fallback = false;
     RunResult res;
@@ -583,49 +581,48 @@ static int forward_entry(davo_ctx* c, int B, const uint8_t* img, const float* fl
     // bounce buffer, then memcpy).
     const bool h3_call = c->impl == 0 && c->precision == 1;
     if (h3_call) { int rc = ensure_ring(c, false); if (rc) return rc; }
-    if (!c->h_sync_pose) HIP_TRY(c, hipHostMalloc(reinterpret_cast<void**>(&c->h_sync_pose), (size_t)c->max_batch * 12 * sizeof(float), hipHostMallocDefault));
     unsigned seq = 0;
     for (int i = 0; i < nchunks; ++i) {
         const int b0 = i * chunk, nb = std::min(chunk, B - b0);
-        hipStream_t cs = nchunks == 1 ? run.stream : c->copy_stream;
-        { int rc = stage_inputs(c, c->host_set, Inputs{img, flow, seg, depth}, b0, nb, false, c->pairs, cs); if (rc) return rc; }      // both pairs: the label maps whole
+        hipStream_t cs = nchunks == 1 ? run.stream : hs.copy_stream.get();
+        { int rc = stage_inputs(c, hs.set, Inputs{img, flow, seg, depth}, b0, nb, false, c->pairs, cs); if (rc) return rc; }      // both pairs: the label maps whole
         if (nchunks > 1) {
-            HIP_TRY(c, hipEventRecord(c->copy_done[i], c->copy_stream));
-            HIP_TRY(c, hipStreamWaitEvent(run.stream, c->copy_done[i], 0));
+            HIP_TRY(c, hipEventRecord(hs.copy_done[i].get(), cs));
+            HIP_TRY(c, hipStreamWaitEvent(run.stream, hs.copy_done[i].get(), 0));
         }
         if (h3_call && i == nchunks - 1) {       // the call's last kernel mirrors the finished record (all sub-batches) to the host
             seq = c->book.next_seq();
-            run.snap.record = c->d_range_base; run.snap.host_mirror = c->h_range_dev; run.snap.seq = seq; run.snap.B = nb; run.snap.se = c->posenn_se;
+            run.snap.record = c->d_range_base.get(); run.snap.host_mirror = c->ring->h_range_dev; run.snap.seq = seq; run.snap.B = nb; run.snap.se = c->posenn_se;
         }
-        int rc = forward_device(c, run, nb, from_window(c, c->host_set.view(), b0), (float*)c->s_pose + (size_t)b0 * 12, &res);
+        int rc = forward_device(c, run, nb, from_window(c, hs.set.view(), b0), hs.d_pose.get() + (size_t)b0 * 12, &res);
         if (rc) return rc;
         f32_fallback |= res.f32_fallback;
         // feature export: the context holds one sub-batch's activations, so every sub-batch but the last is exported before the next
         // one runs; the last one waits for the verdict below
-        if (fx && i < nchunks - 1 && (rc = export_features(c, from_window(c, c->host_set.view(), b0), 0, nb, b0, B, *fx))) return rc;
+        if (fx && i < nchunks - 1 && (rc = export_features(c, from_window(c, hs.set.view(), b0), 0, nb, b0, B, *fx))) return rc;
     }
     const int last_b0 = (nchunks - 1) * chunk;
-    auto export_last = [&]() { return fx ? export_features(c, from_window(c, c->host_set.view(), last_b0), 0, B - last_b0, last_b0, B, *fx) : DAVO_OK; };
+    auto export_last = [&]() { return fx ? export_features(c, from_window(c, hs.set.view(), last_b0), 0, B - last_b0, last_b0, B, *fx) : DAVO_OK; };
     if (f32_fallback) ++c->n_f32_batches;                      // once per call, not per sub-batch
-    HIP_TRY(c, hipMemcpyAsync(c->h_sync_pose, c->s_pose, (size_t)B * 12 * sizeof(float), hipMemcpyDeviceToHost, run.stream));
+    HIP_TRY(c, hipMemcpyAsync(hs.h_pose.get(), hs.d_pose.get(), (size_t)B * 12 * sizeof(float), hipMemcpyDeviceToHost, run.stream));
     HIP_TRY(c, hipStreamSynchronize(run.stream));
-    memcpy(pose_out, c->h_sync_pose, (size_t)B * 12 * sizeof(float));
+    memcpy(pose_out, hs.h_pose.get(), (size_t)B * 12 * sizeof(float));
     if (!res.h3) return export_last();
     // The call ran f16x3 (res is the last sub-batch's), so that sub-batch carried run.snap - h3_call reads the same impl and precision
     // run does - and its last kernel, pose_from_tiles or range_guard_snapshot (forward.hip), has stored the record and seq in the
     // mirror; the stream is idle, so the wait returns at once
     unsigned raw[RANGE_WORDS];
-    int rc = wait_record(c, c->h_range, seq, run.stream, raw);
+    int rc = wait_record(c, c->ring->h_range.get(), seq, run.stream, raw);
     if (rc) return rc;
     rc = judge_record(c, raw, c->act_shift);
     if (rc == DAVO_ERR_RANGE && c->opt_auto_range) {
         // the staged copy of the batch is still in HBM: re-issue it whole (recalibrated, or on the float32 kernels); nothing has
         // been issued since, so its pose buffer is its own
-        rc = recover_batch(c, Reissue{B, c->pairs, c->host_set.view(), c->s_pose, false, 0});
-        if (rc == DAVO_OK) HIP_TRY(c, hipMemcpy(pose_out, c->s_pose, (size_t)B * 12 * sizeof(float), hipMemcpyDeviceToHost));
+        rc = recover_batch(c, Reissue{B, c->pairs, hs.set.view(), hs.d_pose.get(), false, 0});
+        if (rc == DAVO_OK) HIP_TRY(c, hipMemcpy(pose_out, hs.d_pose.get(), (size_t)B * 12 * sizeof(float), hipMemcpyDeviceToHost));
         // the re-issue ran the whole batch as one forward and produced the poses returned: every window's exports come from it, in
         // the precision and under the scales it ran with (what the sub-batches exported above is overwritten)
-        if (rc == DAVO_OK && fx) rc = export_features(c, c->host_set.view(), 0, B, 0, B, *fx);
+        if (rc == DAVO_OK && fx) rc = export_features(c, hs.set.view(), 0, B, 0, B, *fx);
         return rc;
     }
     return rc == DAVO_OK ? export_last() : rc;
@@ -643,11 +640,12 @@ int davo_set_feature_export(davo_ctx* c, int on) {
     if (!c) return DAVO_ERR_INVALID;
     HIP_TRY(c, hipSetDevice(c->device));
     { int rc = sync_all_slots(c); if (rc) return rc; }
-    if (!on) { free_fx_workspace(c); c->fx_on = false; return DAVO_OK; }
-    if (!c->d_fx) {
-        const int cap = c->host_chunk > 0 ? std::min(c->max_batch, 2 * c->host_chunk - 1) : c->max_batch;      // davo_forward's largest sub-batch
-        HIP_TRY(c, hipMalloc(reinterpret_cast<void**>(&c->d_fx), fx_layout(c, cap).total * sizeof(float)));
-        c->fx_cap = cap;
+    if (!on) { c->fx.reset(); c->fx_on = false; return DAVO_OK; }
+    if (!c->fx) {
+        FxBlock fx;
+        fx.cap = c->host_chunk > 0 ? std::min(c->max_batch, 2 * c->host_chunk - 1) : c->max_batch;      // davo_forward's largest sub-batch
+        HIP_TRY(c, dev_alloc(&fx.d, fx_layout(c, fx.cap).total));
+        c->fx = std::move(fx);
     }
     c->fx_on = true;
     return DAVO_OK;
@@ -707,7 +705,7 @@ int davo_reset_range_state(davo_ctx* c) {
     if (verdict && verdict != DAVO_ERR_RANGE) return verdict;
     const std::string verdict_err = c->err;
     { int rc = freeze_pending_and_reset_ring(c); if (rc) return rc; }       // no ticket is pending: this zeroes the ring's records
-    { int rc = zero_now(c, c->d_range_base, RANGE_WORDS * sizeof(unsigned)); if (rc) return rc; }
+    { int rc = zero_now(c, c->d_range_base.get(), RANGE_WORDS * sizeof(unsigned)); if (rc) return rc; }
     for (int i = 0; i < 7; ++i) c->act_shift[i] = 0;
     for (int i = 0; i < 6; ++i) c->range_seen[i] = 0.f;
     c->book.reset();                                                         // the counters' and the cursor's initial values, no deferred verdict
@@ -726,10 +724,9 @@ static int calibrate_entry(davo_ctx* c, int B, const void* d_img, const void* d_
     HIP_TRY(c, hipSetDevice(c->device));
     { int rc = judge_all(c); if (rc) return rc; }             // batches issued under the old scales get their verdict first
     { int rc = freeze_pending_and_reset_ring(c); if (rc) return rc; }
-    float* d_pose = nullptr;
-    HIP_TRY(c, hipMalloc(reinterpret_cast<void**>(&d_pose), (size_t)B * 12 * sizeof(float)));
-    const int rc = calibrate_on(c, B, Inputs{d_img, d_flow, d_seg, d_depth}, d_pose, PAIRS_BOTH);
-    (void)hipFree(d_pose);
+    DevMem<float> d_pose;
+    HIP_TRY(c, dev_alloc(&d_pose, (size_t)B * 12));
+    const int rc = calibrate_on(c, B, Inputs{d_img, d_flow, d_seg, d_depth}, d_pose.get(), PAIRS_BOTH);
     if (rc == DAVO_OK && shifts_out) for (int i = 0; i < 6; ++i) shifts_out[i] = c->act_shift[i];
     return rc;
 }
@@ -744,42 +741,13 @@ int davo_calibrate_depth(davo_ctx* c, int B, const void* d_img, const void* d_fl
 
 const char* davo_last_error(const davo_ctx* c) { return c ? c->err.c_str() : "null context"; }
 
+// Every member of the context frees what it owns (owned.h), in any order: the streams are drained first so that nothing on the
+// device still reads what goes.
 void davo_destroy(davo_ctx* c) {
     if (!c) return;
     (void)hipSetDevice(c->device);
-    (void)sync_all_slots(c);
+    drain_own_streams(c);
     comm_release(c);
-    for (auto& kv : c->weights) if (kv.second.dev) (void)hipFree(kv.second.dev);
-    for (auto& L : c->L) {
-        if (L.d_w) (void)hipFree(L.d_w);
-        if (L.d_b) (void)hipFree(L.d_b);
-        if (L.d_wh) (void)hipFree(L.d_wh);
-        if (L.d_bh) (void)hipFree(L.d_bh);
-    }
-    for (auto e : c->copy_done) (void)hipEventDestroy(e);
-    if (c->copy_stream) { (void)hipStreamSynchronize(c->copy_stream); (void)hipStreamDestroy(c->copy_stream); }
-    free_input_set(c->host_set);
-    for (InputSet& set : c->stream_sets) free_input_set(set);
-    // the range-recovery ring: the input snapshots, the records' host mirror and the stream that reads them
-    for (InputSet& set : c->snap_sets) free_input_set(set);
-    if (c->read_stream) { (void)hipStreamSynchronize(c->read_stream); (void)hipStreamDestroy(c->read_stream); }
-    if (c->h_range) (void)hipHostFree(c->h_range);
-    for (int k = 0; k < STREAM_POSES; ++k) {
-        if (c->d_pose_ring[k]) (void)hipFree(c->d_pose_ring[k]);
-        if (c->h_pose_ring[k]) (void)hipHostFree(c->h_pose_ring[k]);
-        if (c->pose_done[k]) (void)hipEventDestroy(c->pose_done[k]);
-        if (c->st_copied[k]) (void)hipEventDestroy(c->st_copied[k]);
-    }
-    if (c->h_sync_pose) (void)hipHostFree(c->h_sync_pose);
-    free_fx_workspace(c);
-    void* misc[] = {c->d_reissue_pose, c->d_range_base, c->d_splitk, c->d_pose_tiles, c->d_w1patch, c->d_w2patch, c->d_w3patch, c->d_w1patch_f32, c->d_w2patch_f32, c->d_w3patch_f32, c->d_zeros, c->d_wpred, c->d_bpred, c->s_pose};
-    for (auto p : misc) if (p) (void)hipFree(p);
-    for (auto& kv : c->tile_orders) if (kv.second) (void)hipFree(kv.second);
-    for (auto& kv : c->pad_tables) { (void)hipFree(kv.second.row_pixel); (void)hipFree(kv.second.tile_taps); }
-    for (auto& pe : c->prof_entries)
-        for (auto& ab : pe.pending) { (void)hipEventDestroy(ab.first); (void)hipEventDestroy(ab.second); }
-    for (auto e : c->event_pool) (void)hipEventDestroy(e);
-    for (auto& sl : c->slots) free_slot(sl);
     delete c;
 }
 
@@ -904,16 +872,18 @@ int davo_last_split(davo_ctx* c, int layer, int* parts) {
 static int rebuild_slot_streams(davo_ctx* c, int n) {
     for (int i = 0; i < (int)c->slots.size(); ++i) {
         Slot& s = c->slots[i];
-        if (s.stream) { HIP_TRY(c, hipStreamDestroy(s.stream)); s.stream = nullptr; }
+        StreamOwner fresh;                                                     // the slot keeps a live stream whatever fails here
         if (c->cu_partition && n > 1 && i < n && c->dev_cus == 256) {          // the mask layout below is the 8 XCD x 32 CU part's
             uint32_t mask[8] = {0, 0, 0, 0, 0, 0, 0, 0};
             const int lo = i * 32 / n, hi = (i + 1) * 32 / n;                 // CU indices inside an XCD
             for (int b = 0; b < 256; ++b)
                 if (b / 8 >= lo && b / 8 < hi) mask[b / 32] |= 1u << (b % 32);
-            HIP_TRY(c, hipExtStreamCreateWithCUMask(&s.stream, 8, mask));
+            HIP_TRY(c, stream_create(&fresh, 8, mask));
         } else {
-            HIP_TRY(c, hipStreamCreateWithFlags(&s.stream, hipStreamNonBlocking));
+            HIP_TRY(c, stream_create(&fresh));
         }
+        std::swap(s.stream, fresh);
+        if (fresh) HIP_TRY(c, hipStreamDestroy(fresh.release()));              // the old one: a failure is reported
     }
     c->ncu = (c->cu_partition && n > 1 && c->dev_cus == 256) ? 256 / n : c->dev_cus;
     c->last_slot = 0;
@@ -926,11 +896,7 @@ int davo_set_inflight(davo_ctx* c, int n) {
     HIP_TRY(c, hipSetDevice(c->device));
     { int rc = deliver_all(c); if (rc) return rc; }
     { int rc = sync_all_slots(c); if (rc) return rc; }
-    while ((int)c->slots.size() < n) {
-        c->slots.emplace_back();
-        int rc = alloc_slot(c, &c->slots.back());
-        if (rc) return rc;
-    }
+    while ((int)c->slots.size() < n) { int rc = add_slot(c); if (rc) return rc; }      // a slot that could not be built whole is not appended
     c->inflight = n;
     c->next_slot = 0;
     if (c->cu_partition || c->ncu != c->dev_cus) { int rc = rebuild_slot_streams(c, n); if (rc) return rc; }
@@ -1016,31 +982,31 @@ int davo_debug_read(davo_ctx* c, const char* tensor, float* host_out, size_t n_f
     size_t n = 0;
     const std::string t = tensor;
     const Slot& ws = last_workspace(c);
-    if (t == "att_table") { src = ws.d_tab; n = (size_t)c->last_B * 3 * NCLS; }
+    if (t == "att_table") { src = ws.d_tab.get(); n = (size_t)c->last_B * 3 * NCLS; }
     else if (t == "cnv5_se_scale" || t == "cnv5_se") {      // feature attention (posenn_se.h): [2B][2][256] s_r | s_r s_t; [2B][H2][W2][512] rotation | translation input of cnv6
-        if (!c->posenn_se) return fail(c, DAVO_ERR_NOT_READY, "`%s' exists in the feature-attention variant only (davo_set_posenn_se)", tensor);
-        if (t == "cnv5_se") { src = ws.d_se; n = NB * c->H2 * c->W2 * 512; }
-        else { src = ws.d_se_scale; n = NB * 2 * 256; }
+        if (!c->posenn_se || !ws.se) return fail(c, DAVO_ERR_NOT_READY, "`%s' exists in the feature-attention variant only (davo_set_posenn_se)", tensor);
+        if (t == "cnv5_se") { src = ws.se->d_se.get(); n = NB * c->H2 * c->W2 * 512; }
+        else { src = ws.se->d_se_scale.get(); n = NB * 2 * 256; }
     }
     else if (t == "packed") {
         if (!c->packed_valid) {          // fused path: materialise the packed tensor on demand from the last inputs
             HIP_TRY(c, launch_mask_pack(16, static_cast<const uint8_t*>(c->last_in.img), static_cast<const float*>(c->last_in.flow),
-                                        static_cast<const float*>(c->last_in.seg), ws.d_tab, c->v, c->last_B, c->H, c->W, ws.d_packed, c->last_pairs, last_stream(c)));
+                                        static_cast<const float*>(c->last_in.seg), ws.d_tab.get(), c->v, c->last_B, c->H, c->W, ws.d_packed.get(), c->last_pairs, last_stream(c)));
             c->packed_valid = true;
         }
-        src = ws.d_packed; n = NB * c->H * c->W * c->packed_ld;
+        src = ws.d_packed.get(); n = NB * c->H * c->W * c->packed_ld;
     }
     else {
         const char* names[7] = {"cnv1", "cnv2", "cnv3", "cnv4", "cnv5", "cnv6", "cnv7"};
         for (int i = 0; i < 7; ++i)
-            if (t == names[i]) { src = ws.d_act[i]; n = NB * c->act_floats_per_img[i]; }
+            if (t == names[i]) { src = ws.d_act[i].get(); n = NB * c->act_floats_per_img[i]; }
     }
     if (t == "pose_tiles") {          // the fused pose head's per-tile partial sums of the last batch (slot 0's region)
-        if (c->cnv7_valid || !c->d_pose_tiles) return fail(c, DAVO_ERR_NOT_READY, "the pose head did not run fused");
+        if (c->cnv7_valid || !c->d_pose_tiles.get()) return fail(c, DAVO_ERR_NOT_READY, "the pose head did not run fused");
 #ifndef DAVO_POSE_DEBUG
         if (n_floats > c->pose_tiles_floats) return fail(c, DAVO_ERR_INVALID, "pose_tiles holds %zu floats", c->pose_tiles_floats);
 #endif
-        return davo_memcpy_d2h(c, host_out, c->d_pose_tiles, n_floats * sizeof(float));
+        return davo_memcpy_d2h(c, host_out, c->d_pose_tiles.get(), n_floats * sizeof(float));
     }
     if (t == "cnv7" && !c->cnv7_valid)
         return fail(c, DAVO_ERR_NOT_READY, "cnv7 was not materialised: the pose head ran fused (davo_set_option(ctx, \"fuse_pose\", 0))");
@@ -1162,24 +1128,24 @@ int davo_conv2d_same(int device, const float* x, int N, int H, int W, int Cin, c
         pack_conv_weights(w, k, Cin, Cout, nullptr, Cin, L.npad, L.kpad, wp.data());
         hw = wp.data(); wbytes = wp.size() * sizeof(float);
     }
-    void *dx = nullptr, *dw = nullptr, *db = nullptr, *dy = nullptr, *dz = nullptr;
+    DevMem<void> dx, dw, db, dy, dz;
     hipError_t e = hipSuccess;
     auto chk = [&](hipError_t r) { if (e == hipSuccess) e = r; };
-    chk(hipMalloc(&dx, nx * 4)); chk(hipMalloc(&dw, wbytes));
-    chk(hipMalloc(&db, bp.size() * 4)); chk(hipMalloc(&dy, ny * 4));
-    chk(hipMalloc(&dz, 256));
+    chk(dev_alloc(&dx, nx * 4)); chk(dev_alloc(&dw, wbytes));
+    chk(dev_alloc(&db, bp.size() * 4)); chk(dev_alloc(&dy, ny * 4));
+    chk(dev_alloc(&dz, 256));
     if (e == hipSuccess) {
-        chk(hipMemset(dz, 0, 256));
-        chk(hipMemcpy(dx, hx, nx * 4, hipMemcpyHostToDevice));
-        chk(hipMemcpy(dw, hw, wbytes, hipMemcpyHostToDevice));
-        chk(hipMemcpy(db, bp.data(), bp.size() * 4, hipMemcpyHostToDevice));
+        chk(hipMemset(dz.get(), 0, 256));
+        chk(hipMemcpy(dx.get(), hx, nx * 4, hipMemcpyHostToDevice));
+        chk(hipMemcpy(dw.get(), hw, wbytes, hipMemcpyHostToDevice));
+        chk(hipMemcpy(db.get(), bp.data(), bp.size() * 4, hipMemcpyHostToDevice));
         if (precision == 1) {
             const int tile = Cout <= 32 ? TILE_128x32 : Cout <= 64 ? TILE_256x64 : Cout <= 128 ? TILE_256x128 : TILE_128x256;
             const TileShape ts = tile_shape(tile);
             ConvParamsH p{};
-            p.x = static_cast<const uint8_t*>(dx); p.w = static_cast<const uint8_t*>(dw);
-            p.bias = static_cast<const float*>(db); p.y = static_cast<uint8_t*>(dy);
-            p.zeros = static_cast<const uint8_t*>(dz);
+            p.x = static_cast<const uint8_t*>(dx.get()); p.w = static_cast<const uint8_t*>(dw.get());
+            p.bias = static_cast<const float*>(db.get()); p.y = static_cast<uint8_t*>(dy.get());
+            p.zeros = static_cast<const uint8_t*>(dz.get());
             p.Hin = H; p.Win = W; p.Hout = Ho; p.Wout = Wo; p.x_pix_bytes = (long)Cin * 4; p.x_pix_log2 = -1;
             p.cb_log2 = L.cb_log2; p.tpc_log2 = L.tpc_log2; p.cpb = L.cpb; p.nchunks = L.nchunks_h;
             p.w_row_bytes = (long)L.nchunks_h * 128; p.y_mode = 0; p.y_ld = Cout; p.Cout = Cout;
@@ -1190,9 +1156,9 @@ int davo_conv2d_same(int device, const float* x, int N, int H, int W, int Cin, c
             chk(le);
         } else {
             ConvParams p{};
-            p.x = static_cast<const float*>(dx); p.w = static_cast<const float*>(dw);
-            p.bias = static_cast<const float*>(db); p.y = static_cast<float*>(dy);
-            p.zeros = static_cast<const float*>(dz);
+            p.x = static_cast<const float*>(dx.get()); p.w = static_cast<const float*>(dw.get());
+            p.bias = static_cast<const float*>(db.get()); p.y = static_cast<float*>(dy.get());
+            p.zeros = static_cast<const float*>(dz.get());
             p.Hin = H; p.Win = W; p.Hout = Ho; p.Wout = Wo; p.cin_log2 = cl; p.x_ld = Cin; p.y_ld = Cout;
             p.Cout = Cout; p.pad_t = pt; p.pad_l = pl; p.rate = rate; p.M = N * Ho * Wo;
             p.nchunks = L.nchunks; p.Kpad = L.kpad; p.ntaps = k * k; p.ntiles_n = L.npad / L.BN; p.relu = relu;
@@ -1200,9 +1166,8 @@ int davo_conv2d_same(int device, const float* x, int N, int H, int W, int Cin, c
             chk(launch_conv(k, stride, L.BN, p, grid, nullptr));
         }
         chk(hipDeviceSynchronize());
-        chk(hipMemcpy(y, dy, ny * 4, hipMemcpyDeviceToHost));
+        chk(hipMemcpy(y, dy.get(), ny * 4, hipMemcpyDeviceToHost));
     }
-    (void)hipFree(dz); (void)hipFree(dx); (void)hipFree(dw); (void)hipFree(db); (void)hipFree(dy);
     if (e != hipSuccess) return bad(hipGetErrorString(e), DAVO_ERR_HIP);
     return DAVO_OK;
 }

@@ -66,10 +66,9 @@ static Rccl* rccl(std::string* why) {
 struct Comm {
     ncclComm_t comm = nullptr;
     int nranks = 0, rank = 0;
-    hipStream_t stream = nullptr;
-    void *d_send = nullptr, *d_recv = nullptr;     // staging for the host-buffer entry points
-    size_t send_bytes = 0, recv_bytes = 0;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
+    StreamOwner stream;
+    GrowBuf d_send, d_recv;                        // staging for the host-buffer entry points
+    EventOwner e0, e1;
 };
 
 #define NCCL_TRY(c, R, expr)                                                                          \
@@ -89,27 +88,14 @@ static int need_comm(davo_ctx* c, Rccl** R) {
     return DAVO_OK;
 }
 
-static int grow(davo_ctx* c, void** p, size_t* have, size_t want) {
-    if (*have >= want) return DAVO_OK;
-    if (*p) { HIP_TRY(c, hipFree(*p)); *p = nullptr; *have = 0; }
-    HIP_TRY(c, hipMalloc(p, want));
-    *have = want;
-    return DAVO_OK;
-}
-
 void comm_release(davo_ctx* c) {
     if (!c || !c->comm) return;
     Comm* m = c->comm;
     std::string why;
     Rccl* R = rccl(&why);
-    if (m->stream) (void)hipStreamSynchronize(m->stream);
+    if (m->stream) (void)hipStreamSynchronize(m->stream.get());
     if (m->comm && R) (void)R->CommDestroy(m->comm);
-    if (m->d_send) (void)hipFree(m->d_send);
-    if (m->d_recv) (void)hipFree(m->d_recv);
-    if (m->e0) (void)hipEventDestroy(m->e0);
-    if (m->e1) (void)hipEventDestroy(m->e1);
-    if (m->stream) (void)hipStreamDestroy(m->stream);
-    delete m;
+    delete m;                                      // its stream, events and buffers go with it
     c->comm = nullptr;
 }
 
@@ -154,24 +140,18 @@ int davo_comm_init(davo_ctx* c, int nranks, int rank, const void* id) {
     // second thread while the context's owner thread issues forwards (davo_hip.h) - until the last line it touches the context
     // only to report a failure.
     if (hipSetDevice(c->device) != hipSuccess) return fail(c, DAVO_ERR_HIP, "hipSetDevice(%d) failed", c->device);
-    Comm* m = new Comm();
+    std::unique_ptr<Comm> m(new Comm());
     m->nranks = nranks; m->rank = rank;
     ncclUniqueId uid;
     memcpy(&uid, id, sizeof uid);
     const ncclResult_t r = R->CommInitRank(&m->comm, nranks, uid, rank);
-    if (r != ncclSuccess) {
-        delete m;
+    if (r != ncclSuccess)
         return fail(c, DAVO_ERR_COMM, "ncclCommInitRank(rank %d of %d, device %d) failed: %s", rank, nranks, c->device, R->GetErrorString(r));
-    }
-    if (hipStreamCreateWithFlags(&m->stream, hipStreamNonBlocking) != hipSuccess || hipEventCreate(&m->e0) != hipSuccess ||
-        hipEventCreate(&m->e1) != hipSuccess) {
+    if (stream_create(&m->stream) != hipSuccess || event_create(&m->e0) != hipSuccess || event_create(&m->e1) != hipSuccess) {
         (void)R->CommDestroy(m->comm);
-        if (m->stream) (void)hipStreamDestroy(m->stream);
-        if (m->e0) (void)hipEventDestroy(m->e0);
-        delete m;
         return fail(c, DAVO_ERR_HIP, "creating the communicator's stream and events failed");
     }
-    c->comm = m;
+    c->comm = m.release();
     return DAVO_OK;
 }
 
@@ -195,11 +175,11 @@ int davo_allgather_poses_device(davo_ctx* c, const void* d_local, int n_per_rank
     if (!d_local || !d_all || n_per_rank < 1) return fail(c, DAVO_ERR_INVALID, "davo_allgather_poses_device: bad argument");
     Comm* m = c->comm;
     { int rc = sync_all_slots(c); if (rc) return rc; }                // the poses of the shard are complete
-    if (elapsed_ms) HIP_TRY(c, hipEventRecord(m->e0, m->stream));
-    NCCL_TRY(c, R, R->AllGather(d_local, d_all, (size_t)n_per_rank * 12, ncclFloat32, m->comm, m->stream));
-    if (elapsed_ms) HIP_TRY(c, hipEventRecord(m->e1, m->stream));
-    HIP_TRY(c, hipStreamSynchronize(m->stream));
-    if (elapsed_ms) HIP_TRY(c, hipEventElapsedTime(elapsed_ms, m->e0, m->e1));
+    if (elapsed_ms) HIP_TRY(c, hipEventRecord(m->e0.get(), m->stream.get()));
+    NCCL_TRY(c, R, R->AllGather(d_local, d_all, (size_t)n_per_rank * 12, ncclFloat32, m->comm, m->stream.get()));
+    if (elapsed_ms) HIP_TRY(c, hipEventRecord(m->e1.get(), m->stream.get()));
+    HIP_TRY(c, hipStreamSynchronize(m->stream.get()));
+    if (elapsed_ms) HIP_TRY(c, hipEventElapsedTime(elapsed_ms, m->e0.get(), m->e1.get()));
     return DAVO_OK;
 }
 
@@ -210,16 +190,16 @@ int davo_allgather_poses(davo_ctx* c, const float* local, int n_local, int n_per
         return fail(c, DAVO_ERR_INVALID, "davo_allgather_poses: %d local windows, %d per rank", n_local, n_per_rank);
     Comm* m = c->comm;
     const size_t per = (size_t)n_per_rank * 12 * sizeof(float);
-    { int rc = grow(c, &m->d_send, &m->send_bytes, per); if (rc) return rc; }
-    { int rc = grow(c, &m->d_recv, &m->recv_bytes, per * m->nranks); if (rc) return rc; }
-    HIP_TRY(c, hipMemsetAsync(m->d_send, 0, per, m->stream));         // ranks with a short last shard pad with zeros
-    if (n_local) HIP_TRY(c, hipMemcpyAsync(m->d_send, local, (size_t)n_local * 12 * sizeof(float), hipMemcpyHostToDevice, m->stream));
-    if (elapsed_ms) HIP_TRY(c, hipEventRecord(m->e0, m->stream));
-    NCCL_TRY(c, R, R->AllGather(m->d_send, m->d_recv, (size_t)n_per_rank * 12, ncclFloat32, m->comm, m->stream));
-    if (elapsed_ms) HIP_TRY(c, hipEventRecord(m->e1, m->stream));
-    HIP_TRY(c, hipMemcpyAsync(all, m->d_recv, per * m->nranks, hipMemcpyDeviceToHost, m->stream));
-    HIP_TRY(c, hipStreamSynchronize(m->stream));
-    if (elapsed_ms) HIP_TRY(c, hipEventElapsedTime(elapsed_ms, m->e0, m->e1));
+    HIP_TRY(c, m->d_send.reserve(per));
+    HIP_TRY(c, m->d_recv.reserve(per * m->nranks));
+    HIP_TRY(c, hipMemsetAsync(m->d_send.get(), 0, per, m->stream.get()));         // ranks with a short last shard pad with zeros
+    if (n_local) HIP_TRY(c, hipMemcpyAsync(m->d_send.get(), local, (size_t)n_local * 12 * sizeof(float), hipMemcpyHostToDevice, m->stream.get()));
+    if (elapsed_ms) HIP_TRY(c, hipEventRecord(m->e0.get(), m->stream.get()));
+    NCCL_TRY(c, R, R->AllGather(m->d_send.get(), m->d_recv.get(), (size_t)n_per_rank * 12, ncclFloat32, m->comm, m->stream.get()));
+    if (elapsed_ms) HIP_TRY(c, hipEventRecord(m->e1.get(), m->stream.get()));
+    HIP_TRY(c, hipMemcpyAsync(all, m->d_recv.get(), per * m->nranks, hipMemcpyDeviceToHost, m->stream.get()));
+    HIP_TRY(c, hipStreamSynchronize(m->stream.get()));
+    if (elapsed_ms) HIP_TRY(c, hipEventElapsedTime(elapsed_ms, m->e0.get(), m->e1.get()));
     return DAVO_OK;
 }
 
@@ -229,13 +209,13 @@ int davo_comm_allreduce(davo_ctx* c, double* value, int op) {
     { int rc = need_comm(c, &R); if (rc) return rc; }
     if (!value || op < 0 || op > 2) return fail(c, DAVO_ERR_INVALID, "davo_comm_allreduce: bad argument");
     Comm* m = c->comm;
-    { int rc = grow(c, &m->d_send, &m->send_bytes, 64); if (rc) return rc; }
-    { int rc = grow(c, &m->d_recv, &m->recv_bytes, 64); if (rc) return rc; }
-    HIP_TRY(c, hipMemcpyAsync(m->d_send, value, sizeof(double), hipMemcpyHostToDevice, m->stream));
+    HIP_TRY(c, m->d_send.reserve(64));
+    HIP_TRY(c, m->d_recv.reserve(64));
+    HIP_TRY(c, hipMemcpyAsync(m->d_send.get(), value, sizeof(double), hipMemcpyHostToDevice, m->stream.get()));
     const ncclRedOp_t ops[3] = {ncclSum, ncclMax, ncclMin};
-    NCCL_TRY(c, R, R->AllReduce(m->d_send, m->d_recv, 1, ncclFloat64, ops[op], m->comm, m->stream));
-    HIP_TRY(c, hipMemcpyAsync(value, m->d_recv, sizeof(double), hipMemcpyDeviceToHost, m->stream));
-    HIP_TRY(c, hipStreamSynchronize(m->stream));
+    NCCL_TRY(c, R, R->AllReduce(m->d_send.get(), m->d_recv.get(), 1, ncclFloat64, ops[op], m->comm, m->stream.get()));
+    HIP_TRY(c, hipMemcpyAsync(value, m->d_recv.get(), sizeof(double), hipMemcpyDeviceToHost, m->stream.get()));
+    HIP_TRY(c, hipStreamSynchronize(m->stream.get()));
     return DAVO_OK;
 }
 

@@ -3,7 +3,7 @@
 // conv_igemm_h3.h, conv_igemm_h3s.h, conv_patch_h3.h and prologue.h and are launched through launch.h.
 //
 // Translation units (built in parallel by davo_amd/_lib.py, linked into one shared library):
-//   api.hip         extern "C" entry points (context, weights, forward, calibration, test hooks); owns the InputSets
+//   api.hip         extern "C" entry points (context, weights, forward, calibration, test hooks); builds the context's resource groups
 //   forward.hip     the forward plan of the pose path (which kernel, which buffers, in what order)
 //   range_guard.hip the f16x3 range guard: records, verdicts, calibration, re-issues, tickets (its bookkeeping: range_book.h)
 //   plan.hip        launch planning: tile shapes and whole-round launch splits (pure host logic)
@@ -14,6 +14,9 @@
 //   launch_misc.hip prologue / pose head / cnv1..cnv3 patch / feature-attention (posenn_se.h) / direct-convolution kernels + dispatch
 //   launch_feature.hip  the feature export kernels (feature_export.h) + dispatch
 //   comm.hip        RCCL communicator behind the C ABI (pose gather of the window-sharded driver)
+// owned.h holds the owner types (device / page-locked memory, streams, events): everything a context allocates is a member of
+// one of them, so `delete ctx' is the whole teardown.  What is built lazily is a named group (HostStaging, PoseRing, RangeRing,
+// Snapshots, FxBlock, SeWorkspace, a Slot), built into a local and moved in complete: a group exists whole or not at all.
 //
 // A forward's inputs.  forward_device(c, run, B, in, d_pose, &res) reads the context for what lasts (geometry, weights, options,
 // storage scales, the slots' workspaces); what belongs to the batch travels in one argument, `run' (struct Run below): its slot and
@@ -28,10 +31,13 @@
 #include <cstdio>
 #include <deque>
 #include <map>
+#include <optional>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/davo_hip.h"
+#include "owned.h"
 #include "params.h"
 #include "range_book.h"
 
@@ -42,7 +48,7 @@ static_assert(RECORD_WORDS == RANGE_WORDS, "range_book.h sizes a ticket's copy o
 struct HostTensor {
     std::vector<float> data;
     std::vector<int64_t> shape;
-    float* dev = nullptr;          // raw copy in the reference layout (impl 1, pose_head, SE)
+    DevMem<float> dev;             // raw copy in the reference layout (impl 1, pose_head, SE)
 };
 
 struct ConvLayer {
@@ -50,20 +56,20 @@ struct ConvLayer {
     int KS, stride, rate;
     int cin, cin_log2, cout;       // packed input channels per tap (power of two), valid outputs
     int BN, npad, kpad, nchunks, groups;
-    float* d_w = nullptr;          // [groups][npad][kpad]
-    float* d_b = nullptr;          // [groups][npad]
+    DevMem<float> d_w;             // [groups][npad][kpad]
+    DevMem<float> d_b;             // [groups][npad]
     // f16x3 path (conv_igemm_h3.h): channel-blocked k order, split-fp16 packed weights
     int cb_log2 = 0, tpc_log2 = 0, cpb = 0, nchunks_h = 0, npad_h = 0, tile_h = 0;
     float wscale = 1.f;            // power of two the packed fp16 weights are multiplied by
-    uint8_t* d_wh = nullptr;       // [groups][npad_h][nchunks_h][32 hi | 32 lo] halves
-    float* d_bh = nullptr;         // [groups][npad_h]
+    DevMem<uint8_t> d_wh;          // [groups][npad_h][nchunks_h][32 hi | 32 lo] halves
+    DevMem<float> d_bh;            // [groups][npad_h]
 };
 
 struct ProfEntry {
     std::string name;
     int launches = 0;
     double total_ms = 0.0;
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> pending;
+    std::vector<std::pair<EventOwner, EventOwner>> pending;
     // per-launch record since the last reset (davo_profile_samples; at most PROF_SAMPLES_CAP kept): the launch's own duration
     // and the time from the previous bracketed launch's start to this one's (-1 when the previous start is not known)
     std::vector<float> dur_ms, period_ms;
@@ -72,19 +78,25 @@ constexpr size_t PROF_SAMPLES_CAP = 8192;
 
 // One in-flight batch: its own HIP stream and activation workspace.  Weights are shared.
 constexpr int MAX_INFLIGHT = 4;                  // slots a context rotates through at most (davo_set_inflight; the per-slot scratch and staging sets are sized by it)
-struct Slot {
-    hipStream_t stream = nullptr;
-    float *d_partial = nullptr, *d_tab = nullptr, *d_packed = nullptr, *d_pose_partial = nullptr;
-    float* d_act[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    float *d_se = nullptr, *d_se_scale = nullptr, *d_se_partial = nullptr;      // feature attention (posenn_se.h; null with the mode off): [NB][P2][512] scaled cnv5, [NB][2][256] scales, [NB][SE5_CHUNKS][256] sums
-    unsigned* d_counters = nullptr;              // "last workgroup" tickets (pose_tail.h): [0] cnv7's pose tail, [1 + b] triplet b's squeeze, [1 + max_batch + t] tile t of a split-K launch
+struct SeWorkspace {                             // feature attention (posenn_se.h): [NB][P2][512] scaled cnv5, [NB][2][256] scales, [NB][SE5_CHUNKS][256] sums
+    DevMem<float> d_se, d_se_scale, d_se_partial;
 };
+struct Slot {
+    StreamOwner stream;
+    DevMem<float> d_partial, d_tab, d_packed, d_pose_partial;
+    DevMem<float> d_act[7];
+    std::optional<SeWorkspace> se;               // absent with the feature-attention mode off
+    DevMem<unsigned> d_counters;                 // "last workgroup" tickets (pose_tail.h): [0] cnv7's pose tail, [1 + b] triplet b's squeeze, [1 + max_batch + t] tile t of a split-K launch
+};
+static_assert(std::is_nothrow_move_constructible<Slot>::value, "davo_ctx::slots is a std::vector");
 
-// Device room of the context for max_batch windows of every plane the variant reads (api.hip: alloc_input_set / free_input_set);
+// Device room of the context for max_batch windows of every plane the variant reads (api.hip: alloc_input_set builds one whole);
 // depth stays null unless the variant reads it, so a set's view says by itself whether there are depth planes to carry along.
+// A set is only ever assigned whole, so it is either empty or built.
 struct InputSet {
-    void *img = nullptr, *flow = nullptr, *seg = nullptr, *depth = nullptr;
-    Inputs view() const { return Inputs{img, flow, seg, depth}; }
+    DevMem<void> img, flow, seg, depth;
+    bool built() const { return static_cast<bool>(img); }
+    Inputs view() const { return Inputs{img.get(), flow.get(), seg.get(), depth.get()}; }
 };
 
 constexpr int SK_TILE_COUNTERS = 256;            // tiles of a split-K launch whose fix-up is folded in (forward.hip): at most one per CU
@@ -121,11 +133,46 @@ struct RunResult {
 // device tables of a layer whose GEMM rows are sorted by padding class (pad_classes.h), and the host copy of the per-tile tap masks
 // (what a tile costs: tile_order_pc, forward.hip)
 struct PadTables {
-    int* row_pixel = nullptr;
-    unsigned short* tile_taps = nullptr;
+    DevMem<int> row_pixel;
+    DevMem<unsigned short> tile_taps;
     std::vector<uint16_t> host_taps;
 };
 constexpr int PAD_CLASS_LAYERS = 6;              // "pad_classes" 1: cnv5 | cnv6 (bits: 1 cnv4, 2 cnv5, 4 cnv6).  cnv4 measured level (245.2 -> 243.4 us, inside its run-to-run spread) and stays on the natural order
+
+// ---- what the context builds at a first use, each whole or not at all ------------------------------------------------------------
+// davo_forward's staging (its first call): the input set, the poses on the device and their page-locked bounce buffer, the stream
+// the H2D of the next sub-batch runs on while the previous one computes, and one event per sub-batch (the only part that grows)
+struct HostStaging {
+    InputSet set;
+    DevMem<float> d_pose;
+    PinnedMem<float> h_pose;
+    StreamOwner copy_stream;
+    std::vector<EventOwner> copy_done;
+};
+// davo_submit's pose ring (its first call): entry k holds a batch's poses on the device, their page-locked twin, "the poses are in
+// the twin" and "the H2D copies of the batch are done" (recorded only for hold < STREAM_POSES: copy_tracked)
+struct PoseRing {
+    struct Entry {
+        DevMem<float> dev;
+        PinnedMem<float> host;
+        EventOwner pose_done, copied;
+        bool copy_tracked = false;
+    } e[STREAM_POSES];
+};
+// the range guard's ring, stage one (the first f16x3 batch): the stream that reads records and their page-locked mirrors -
+// [0] landing pad of a record read, [1 + r] the mirror ring slot r's last kernel writes; h_range_dev is h_range as the device sees it
+struct RangeRing {
+    StreamOwner read_stream;
+    PinnedMem<unsigned> h_range;
+    unsigned* h_range_dev = nullptr;
+};
+// ... stage two (the first ticket that wants a copy of its inputs): the ring slots' input snapshots
+struct Snapshots { InputSet sets[RANGE_RING]; };
+// the feature export's device block for `cap' windows of every export tensor (davo_set_feature_export)
+struct FxBlock {
+    DevMem<float> d;
+    int cap = 0;
+};
 
 struct Comm;                                     // comm.hip: RCCL communicator state
 
@@ -149,7 +196,7 @@ struct davo_ctx {
     bool opt_deep_ring = true;                 // f16x3: launches of at most one workgroup per CU (batch 1..4) run on LDS rings of 3..6 slots
     int opt_merge_order = -1;                  // merged grids: 0 = short tiles offset inside every XCD, 1 = per XCD, 2 = main tiles (long first) then the remainder; -1 = 2 where a tile order exists, else 0
     int opt_skip_order = 1;                    // launches whose tiles skip different numbers of padding rows of the filter hand out the long tiles first (tile_order_for, forward.hip): 0 = never, 1 = float32 launches, 2 = the f16x3 merged grids too
-    std::map<std::vector<int>, int*> tile_orders;   // device tables of those launches, by (layer, tile rows, tiles, ...); nullptr = uniform
+    std::map<std::vector<int>, davo::DevMem<int>> tile_orders;   // device tables of those launches, by (layer, tile rows, tiles, ...); nullptr = uniform
     int opt_pad_classes = davo::PAD_CLASS_LAYERS;                  // float32: the layers of the mask (1 cnv4, 2 cnv5, 4 cnv6) run on rows sorted by padding class, every tile walks only the taps that are real for its own pixels (pad_classes.h)
     std::map<std::vector<int>, davo::PadTables> pad_tables;   // their device tables, by (layer, pair images, map, padding, rate)
     bool opt_tile_208x128 = false;             // f16x3: cnv4 may run on the four-wave 208x128 tile (conv_igemm_h3s.h; measured 8 % behind the 128x128 tile at B = 32: off)
@@ -161,9 +208,9 @@ struct davo_ctx {
     bool opt_fold_fixup = false;               // f16x3 split-K: the part that finishes a tile last adds its partial sums (no splitk_fixup launch); needs xcd_rr > 0.  Measured slower (batch 1: 0.141 against 0.132 ms): off
     int xcd_rr = -1;                           // workgroups (x, y) of a grid whose x extent is a multiple of 8 share an XCD for every y: -1 not probed yet | 0 no | 1 yes
     bool opt_split_k = true;                   // f16x3: cnv5 / cnv6 launches of at most half a workgroup per CU split their K loop in two (forward.hip)
-    float* d_splitk = nullptr;                 // split-K partial sums [MAX_INFLIGHT slots][M][2][N] float32
+    davo::GrowBuf d_splitk;                    // split-K partial sums [MAX_INFLIGHT slots][M][2][N] float32
     size_t splitk_floats = 0;                  // ... per slot
-    float* d_pose_tiles = nullptr;             // per-tile partial sums of the fused pose head
+    davo::GrowBuf d_pose_tiles;                // per-tile partial sums of the fused pose head, one region per slot likewise
     size_t pose_tiles_floats = 0;
     bool cnv7_valid = true;
     davo::Variant v{};
@@ -180,15 +227,15 @@ struct davo_ctx {
     bool packed_ready = false;                 // float32 convolution weights packed (built at the first float32 forward)
     bool pred_ready = false;                   // pose head kernels on the device (every mode)
     davo::ConvLayer L[7];                      // cnv1..cnv5, cnv6 (fused), cnv7 (grouped)
-    float *d_wpred = nullptr, *d_bpred = nullptr;
-    uint8_t* d_w1patch = nullptr;              // cnv1 B fragments for conv_patch_cnv1_h3
-    uint8_t* d_w2patch = nullptr;              // cnv2 B fragments for conv_patch_cnv2_h3
-    float *d_w1patch_f32 = nullptr, *d_w2patch_f32 = nullptr, *d_w3patch_f32 = nullptr;      // float32 mode: cnv1 / cnv2 / cnv3 weights in the patch kernels' register order (conv_patch_f32.h)
+    davo::DevMem<float> d_wpred, d_bpred;
+    davo::DevMem<uint8_t> d_w1patch;           // cnv1 B fragments for conv_patch_cnv1_h3
+    davo::DevMem<uint8_t> d_w2patch;           // cnv2 B fragments for conv_patch_cnv2_h3
+    davo::DevMem<float> d_w1patch_f32, d_w2patch_f32, d_w3patch_f32;      // float32 mode: cnv1 / cnv2 / cnv3 weights in the patch kernels' register order (conv_patch_f32.h)
     bool opt_patch_f32 = true;                 // float32 mode: cnv1 / cnv2 / cnv3 from an LDS-staged input patch (conv_patch_f32.h) instead of the implicit GEMM
-    uint8_t* d_w3patch = nullptr;              // cnv3 B fragments for conv_patch_cnv3_h3
+    davo::DevMem<uint8_t> d_w3patch;           // cnv3 B fragments for conv_patch_cnv3_h3
     // geometry
     int H1, W1, H2, W2, H3, W3;
-    float* d_zeros = nullptr;
+    davo::DevMem<float> d_zeros;
     size_t act_floats_per_img[7];
     int act_ch[7];
     int pairs = davo::PAIRS_BOTH;              // davo_set_pairs: the pairs of every window the batches issued from now on run
@@ -203,53 +250,42 @@ struct davo_ctx {
     davo::Inputs last_in{};                    // the last forward's inputs: davo_debug_read("packed") re-packs from them after a fused cnv1
     int last_plan[7][2] = {};                  // per layer, per launch: 128-row M tiles * 1000 + tile id / BN (reported by the bench)
     int last_split[7] = {};                    // per layer: split-K parts of the last forward's launch (1: one K chain; davo_last_split)
-    // host-API staging
-    davo::InputSet host_set;                   // davo_forward's staging set (allocated by its first call)
-    void* s_pose = nullptr;
-    float* h_sync_pose = nullptr;              // davo_forward: page-locked bounce buffer of the poses
-    hipStream_t copy_stream = nullptr;         // H2D of the next sub-batch runs here while the previous one computes
-    std::vector<hipEvent_t> copy_done;
+    std::optional<davo::HostStaging> host;     // davo_forward's staging (built by its first call)
     // f16x3 range management: activations are stored as fp16 pairs scaled by 2^act_shift[layer] (davo_calibrate);
     // every storing epilogue atomicMax-es the largest stored magnitude into word `layer' of the run's record (Run::range)
     int act_shift[7] = {0, 0, 0, 0, 0, 0, 0};
-    unsigned* d_range_base = nullptr;          // [1 + RANGE_RING][RANGE_WORDS] (params.h): record 0 serves the host path, calibration and re-issues; 1.. the ring
+    davo::DevMem<unsigned> d_range_base;       // [1 + RANGE_RING][RANGE_WORDS] (params.h): record 0 serves the host path, calibration and re-issues; 1.. the ring
     // Range recovery (davo_set_option "auto_range", default on): every device-path batch is judged on a record of its own, at the
     // latest when its ring slot is needed again (RANGE_RING batches later) or at davo_synchronize; a failed verdict re-issues that
     // batch from the context's own copy of its inputs - recalibrated, or on the float32 kernels (api.hip)
     bool opt_auto_range = true;
     bool opt_stable_inputs = false;            // "stable_inputs": the caller keeps inputs unchanged until the verdict, no copies are taken
     davo::RangeBook book;                      // the guard's bookkeeping: ring cursor, tickets, pose spans, deferred verdict (range_book.h)
-    davo::InputSet snap_sets[davo::RANGE_RING];        // the ring slots' input snapshots (allocated by the first ticket that wants one)
-    hipStream_t read_stream = nullptr;
-    unsigned* h_range = nullptr;               // page-locked: [0] landing pad of a record read, [1 + r] the mirror ring slot r's last kernel writes
-    unsigned* h_range_dev = nullptr;           // ... as the device sees it
+    std::optional<davo::RangeRing> ring;       // the records' host mirrors and the stream that reads them (range_guard.hip: ensure_ring)
+    std::optional<davo::Snapshots> snaps;      // the ring slots' input snapshots (built for the first ticket that wants one)
     float range_seen[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};      // largest true |activation| judged since the last reset
     std::string range_report;                  // what the range management last did, in words (davo_range_report)
     long long n_recalibrations = 0, n_f32_batches = 0, n_reissued = 0;
     int host_chunk = 8;                        // davo_forward: windows per sub-batch (davo_set_option "host_chunk"; 0 = whole batch)
-    // feature export (davo_set_feature_export / davo_forward_features, api.hip): one device block for fx_cap windows of every
-    // export tensor, null with the export off
+    // feature export (davo_set_feature_export / davo_forward_features, api.hip): one device block for fx->cap windows of every
+    // export tensor, absent with the export off
     bool fx_on = false;
-    float* d_fx = nullptr;
-    int fx_cap = 0;
+    std::optional<davo::FxBlock> fx;
     // streaming host entry (davo_submit / davo_wait): staging input sets, pose ring, undelivered batches in issue order
-    davo::InputSet stream_sets[davo::MAX_INFLIGHT];     // one staging set per in-flight slot (allocated by the slot's first davo_submit)
-    hipEvent_t st_copied[davo::STREAM_POSES] = {};             // "the H2D copies of the batch in pose ring entry k are done" (recorded only for hold < STREAM_POSES)
-    bool copy_tracked[davo::STREAM_POSES] = {};
-    float *d_pose_ring[davo::STREAM_POSES] = {}, *h_pose_ring[davo::STREAM_POSES] = {};
-    hipEvent_t pose_done[davo::STREAM_POSES] = {};
+    davo::InputSet stream_sets[davo::MAX_INFLIGHT];     // one staging set per in-flight slot (built by the slot's first davo_submit)
+    std::optional<davo::PoseRing> pose_ring;   // built by the first davo_submit
     std::deque<davo::StreamJob> jobs;
     unsigned long long n_submitted = 0;
-    float* d_reissue_pose = nullptr;           // a re-issued batch writes here first; copied to its own pose buffer unless a later batch has taken that
+    davo::DevMem<float> d_reissue_pose;        // a re-issued batch writes here first; copied to its own pose buffer unless a later batch has taken that
     // profiling
     bool prof = false;
     bool prof_dominant_only = false;           // profile mode 2: bracket only the main cnv6 launch
     int prof_stride = 1, prof_tick = 0;        // ... of every prof_stride-th batch (davo_set_option "profile_stride"): an event pair
                                                // costs two ~6 us bubbles around the launch it brackets
     std::vector<davo::ProfEntry> prof_entries;
-    std::vector<hipEvent_t> event_pool;
+    std::vector<davo::EventOwner> event_pool;
     // multi-GPU (comm.hip)
-    davo::Comm* comm = nullptr;
+    davo::Comm* comm = nullptr;                // owned through comm_release (the type is comm.hip's)
 };
 
 namespace davo {
@@ -297,10 +333,10 @@ inline int ilog2_exact(int v) {
 }
 
 // the stream slot i runs on: its own, or the caller's for slot 0 (davo_set_stream)
-inline hipStream_t slot_stream(const davo_ctx* c, int i) { return (c->user_stream && i == 0) ? c->user_stream : c->slots[i].stream; }
+inline hipStream_t slot_stream(const davo_ctx* c, int i) { return (c->user_stream && i == 0) ? c->user_stream : c->slots[i].stream.get(); }
 // a batch in slot i as the context's settings of the moment say, on the base record (range_guard.hip: ticket_begin moves it to a record of its own)
 inline Run make_run(const davo_ctx* c, int i) {
-    return Run{i, slot_stream(c, i), c->d_range_base, false, SnapArgs{}, c->pairs, c->precision, c->impl};
+    return Run{i, slot_stream(c, i), c->d_range_base.get(), false, SnapArgs{}, c->pairs, c->precision, c->impl};
 }
 // outside a forward (davo_memcpy_*, davo_debug_read, the feature export): the stream and workspace of the most recently issued batch
 inline hipStream_t last_stream(const davo_ctx* c) { return slot_stream(c, c->last_slot); }
@@ -311,7 +347,7 @@ struct ProfScope {
     davo_ctx* c;
     hipStream_t s;
     ProfEntry* e = nullptr;
-    hipEvent_t a = nullptr, b = nullptr;
+    EventOwner a, b;                           // out of the context's pool, back into it (or into e->pending) at the end
     ProfScope(davo_ctx* ctx, hipStream_t stream, const char* name);
     ~ProfScope();
 };
@@ -327,7 +363,7 @@ const char* se_weight_name(int att_source, int k);
 // the SE layers' scope is a dense tensor the kernels read in the reference's [in,out] layout (not re-laid-out like a convolution)
 bool is_dense_weight(const std::string& name);
 bool expected_shape(const davo_ctx* c, const std::string& name, std::vector<int64_t>* sh);
-int upload(davo_ctx* c, const std::vector<float>& host, float** dev);
+int upload(davo_ctx* c, const std::vector<float>& host, DevMem<float>* dev);      // frees what *dev held first
 int build_packed_weights(davo_ctx* c);
 int build_pred_weights(davo_ctx* c);
 int build_packed_weights_h3(davo_ctx* c);
@@ -349,7 +385,7 @@ int forward_device(davo_ctx* c, const Run& run, int B, const Inputs& in, void* d
 
 // ---- api.hip --------------------------------------------------------------------------------
 int zero_now(davo_ctx* c, void* p, size_t bytes);                              // hipMemset that returns when the bytes ARE zero
-int alloc_input_set(davo_ctx* c, InputSet* s, bool zero_unread);
+int alloc_input_set(davo_ctx* c, InputSet* s, bool zero_unread);               // *s is assigned whole, or left as it was
 
 // ---- range_guard.hip: what the entry points need of the f16x3 range guard --------------------
 int ensure_ring(davo_ctx* c, bool snapshots);                                  // the records' host mirrors (and the ring's input snapshots)

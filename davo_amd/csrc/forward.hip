@@ -36,27 +36,27 @@ ProfScope::ProfScope(davo_ctx* ctx, hipStream_t stream, const char* name) : c(ct
         e->name = name;
     }
     auto get = [&]() {
-        hipEvent_t ev = nullptr;
-        if (!c->event_pool.empty()) { ev = c->event_pool.back(); c->event_pool.pop_back(); }
-        else if (hipEventCreate(&ev) != hipSuccess) ev = nullptr;
+        EventOwner ev;
+        if (!c->event_pool.empty()) { ev = std::move(c->event_pool.back()); c->event_pool.pop_back(); }
+        else (void)event_create(&ev);
         return ev;
     };
     a = get(); b = get();
-    if (a) (void)hipEventRecord(a, s);
+    if (a) (void)hipEventRecord(a.get(), s);
 }
 
 ProfScope::~ProfScope() {
     if (!e) return;
-    if (b) (void)hipEventRecord(b, s);
-    if (a && b) e->pending.emplace_back(a, b);
+    if (b) (void)hipEventRecord(b.get(), s);
+    if (a && b) e->pending.emplace_back(std::move(a), std::move(b));
     else {                                    // half a pair is of no use: back to the pool
-        if (a) c->event_pool.push_back(a);
-        if (b) c->event_pool.push_back(b);
+        if (a) c->event_pool.push_back(std::move(a));
+        if (b) c->event_pool.push_back(std::move(b));
     }
 }
 
 int sync_all_slots(davo_ctx* c) {
-    for (auto& s : c->slots) HIP_TRY(c, hipStreamSynchronize(s.stream));
+    for (auto& s : c->slots) HIP_TRY(c, hipStreamSynchronize(s.stream.get()));
     if (c->user_stream) HIP_TRY(c, hipStreamSynchronize(c->user_stream));
     return DAVO_OK;
 }
@@ -64,20 +64,20 @@ int sync_all_slots(davo_ctx* c) {
 int prof_collect(davo_ctx* c) {
     { int rc = sync_all_slots(c); if (rc) return rc; }
     for (auto& pe : c->prof_entries) {
-        hipEvent_t prev_start = nullptr;
+        EventOwner prev_start;
         for (auto& ab : pe.pending) {
             float ms = 0.f, gap = -1.f;
-            if (hipEventElapsedTime(&ms, ab.first, ab.second) == hipSuccess) {
+            if (hipEventElapsedTime(&ms, ab.first.get(), ab.second.get()) == hipSuccess) {
                 pe.total_ms += ms;
                 pe.launches += 1;
-                if (prev_start && hipEventElapsedTime(&gap, prev_start, ab.first) != hipSuccess) gap = -1.f;
+                if (prev_start && hipEventElapsedTime(&gap, prev_start.get(), ab.first.get()) != hipSuccess) gap = -1.f;
                 if (pe.dur_ms.size() < PROF_SAMPLES_CAP) { pe.dur_ms.push_back(ms); pe.period_ms.push_back(gap); }
             }
-            if (prev_start) c->event_pool.push_back(prev_start);
-            prev_start = ab.first;
-            c->event_pool.push_back(ab.second);
+            if (prev_start) c->event_pool.push_back(std::move(prev_start));
+            prev_start = std::move(ab.first);
+            c->event_pool.push_back(std::move(ab.second));
         }
-        if (prev_start) c->event_pool.push_back(prev_start);
+        if (prev_start) c->event_pool.push_back(std::move(prev_start));
         pe.pending.clear();
     }
     return DAVO_OK;
@@ -89,6 +89,20 @@ constexpr int MAX_WEIGHT_CHANNEL_SPREAD_LOG2 = 14;     // f16x3 per-channel guar
 constexpr int FOLD_EXCITE_MAX_BATCH = 2;       // auto modes: largest batch that folds the excitation / fuses mask + pack into cnv1
 constexpr int FUSE_PACK_MAX_BATCH = 0;        // measured level at every batch (cnv1 +5 us for mask_pack's 6.7): nowhere by default
 
+// ---- tile orders ------------------------------------------------------------------------------------
+// One cache for every launch's table (davo_ctx::tile_orders): `build' is asked once per key for the order, an empty one meaning
+// that no table is needed, and the table is uploaded.  A table that cannot be put on the device is not fatal: natural order.
+template <class Build>
+const int* cached_tile_order(davo_ctx* c, const std::vector<int>& key, Build build) {
+    if (!c->opt_skip_order) return nullptr;
+    auto it = c->tile_orders.find(key);
+    if (it != c->tile_orders.end()) return it->second.get();
+    const std::vector<int> order = build();
+    DevMem<int> dev;
+    if (!order.empty() && !(dev = upload_table(order))) (void)hipGetLastError();
+    return (c->tile_orders[key] = std::move(dev)).get();
+}
+
 // ---- long tiles first ------------------------------------------------------------------------------
 // The 3x3 kernels skip the chunks of filter rows that are all padding for a tile (params.h, valid_filter_rows), so the tiles
 // of one launch differ in length (dilation 8 on a 32-row map: 6 of an image's 13 tiles of 256 pixels walk two thirds of the
@@ -99,20 +113,16 @@ constexpr int FUSE_PACK_MAX_BATCH = 0;        // measured level at every batch (
 // the short tiles pack the end.  Returns nullptr when all tiles of the launch cost the same.
 const int* tile_order_for(davo_ctx* c, int li, int kind, int bm, int mtile0, int mtiles, int ntiles_n, int M,
                           int Hout, int Wout, int Hin, int stride, int pad_t, int rate) {
-    if (!c->opt_skip_order) return nullptr;
-    const std::vector<int> key = {li, kind, bm, mtile0, mtiles, ntiles_n, M, Hout, Wout};
-    auto it = c->tile_orders.find(key);
-    if (it != c->tile_orders.end()) return it->second;
-    const int nt = mtiles * ntiles_n;
-    std::vector<int> cost(nt), order(nt);
-    bool uniform = true;
-    for (int t = 0; t < nt; ++t) {
-        const int m0 = (mtile0 + t / ntiles_n) * bm, m1 = std::min(m0 + bm, M) - 1;
-        cost[t] = valid_filter_rows(m0, m1, Hout, Wout, Hin, stride, pad_t, rate).nky;
-        uniform = uniform && cost[t] == cost[0];
-    }
-    int* dev = nullptr;
-    if (!uniform) {
+    return cached_tile_order(c, {li, kind, bm, mtile0, mtiles, ntiles_n, M, Hout, Wout}, [&]() {
+        const int nt = mtiles * ntiles_n;
+        std::vector<int> cost(nt), order(nt);
+        bool uniform = true;
+        for (int t = 0; t < nt; ++t) {
+            const int m0 = (mtile0 + t / ntiles_n) * bm, m1 = std::min(m0 + bm, M) - 1;
+            cost[t] = valid_filter_rows(m0, m1, Hout, Wout, Hin, stride, pad_t, rate).nky;
+            uniform = uniform && cost[t] == cost[0];
+        }
+        if (uniform) return std::vector<int>();
         const int q = nt >> 3, r = nt & 7;
         for (int x = 0; x < 8; ++x) {                       // xcd_remap: XCD x runs tiles [start, start + len)
             const int start = x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q, len = q + (x < r ? 1 : 0);
@@ -121,15 +131,8 @@ const int* tile_order_for(davo_ctx* c, int li, int kind, int bm, int mtile0, int
                 for (int t = start; t < start + len; ++t)
                     if (cost[t] == want) order[w++] = t;
         }
-        if (hipMalloc(reinterpret_cast<void**>(&dev), nt * sizeof(int)) != hipSuccess ||
-            hipMemcpy(dev, order.data(), nt * sizeof(int), hipMemcpyHostToDevice) != hipSuccess) {
-            if (dev) (void)hipFree(dev);
-            dev = nullptr;                                   // not fatal: natural order
-            (void)hipGetLastError();
-        }
-    }
-    c->tile_orders[key] = dev;
-    return dev;
+        return order;
+    });
 }
 
 // ---- class-sorted rows (pad_classes.h; "pad_classes") -------------------------------------------------
@@ -147,14 +150,7 @@ const PadTables* pad_tables_for(davo_ctx* c, int li, int NB, int Hout, int Wout,
         c->pad_tables[key] = PadTables();                       // remembered: nothing to build at this shape
         return nullptr;
     }
-    auto upload = [&](void** dev, const void* src, size_t bytes) {
-        if (hipMalloc(dev, bytes) != hipSuccess) { *dev = nullptr; return false; }
-        return hipMemcpy(*dev, src, bytes, hipMemcpyHostToDevice) == hipSuccess;
-    };
-    if (!upload(reinterpret_cast<void**>(&t.row_pixel), rows.data(), rows.size() * sizeof(int32_t)) ||
-        !upload(reinterpret_cast<void**>(&t.tile_taps), t.host_taps.data(), t.host_taps.size() * sizeof(uint16_t))) {
-        if (t.row_pixel) (void)hipFree(t.row_pixel);
-        if (t.tile_taps) (void)hipFree(t.tile_taps);
+    if (!(t.row_pixel = upload_table(rows)) || !(t.tile_taps = upload_table(t.host_taps))) {
         *rc = fail(c, DAVO_ERR_HIP, "pad-class tables of layer %d: %s", li, hipGetErrorString(hipGetLastError()));
         return nullptr;
     }
@@ -164,37 +160,27 @@ const PadTables* pad_tables_for(davo_ctx* c, int li, int NB, int Hout, int Wout,
 // tile_order_for where the tiles walk their own taps: a tile costs the tap count of its mask, the XCDs' runs are dealt out level
 // (pad_classes.h, pad_class_tile_order)
 const int* tile_order_pc(davo_ctx* c, int li, int mtile0, int mtiles, int ntiles_n, int M, int Hout, int Wout, const PadTables& t) {
-    if (!c->opt_skip_order) return nullptr;
-    const std::vector<int> key = {li, 100, BM, mtile0, mtiles, ntiles_n, M, Hout, Wout};
-    auto it = c->tile_orders.find(key);
-    if (it != c->tile_orders.end()) return it->second;
-    bool uniform = true;
-    for (int m = 1; m < mtiles; ++m) uniform = uniform && tap_count(t.host_taps[mtile0 + m]) == tap_count(t.host_taps[mtile0]);
-    int* dev = nullptr;
-    if (!uniform) {
+    return cached_tile_order(c, {li, 100, BM, mtile0, mtiles, ntiles_n, M, Hout, Wout}, [&]() {
         std::vector<int> order;
-        pad_class_tile_order(t.host_taps.data(), mtile0, mtiles, ntiles_n, &order);
-        if (hipMalloc(reinterpret_cast<void**>(&dev), order.size() * sizeof(int)) != hipSuccess ||
-            hipMemcpy(dev, order.data(), order.size() * sizeof(int), hipMemcpyHostToDevice) != hipSuccess) {
-            if (dev) (void)hipFree(dev);
-            dev = nullptr;                                   // not fatal: natural order
-            (void)hipGetLastError();
-        }
-    }
-    c->tile_orders[key] = dev;
-    return dev;
+        bool uniform = true;
+        for (int m = 1; m < mtiles; ++m) uniform = uniform && tap_count(t.host_taps[mtile0 + m]) == tap_count(t.host_taps[mtile0]);
+        if (!uniform) pad_class_tile_order(t.host_taps.data(), mtile0, mtiles, ntiles_n, &order);
+        return order;
+    });
 }
 
 // ---- per-slot scratch -------------------------------------------------------------------------------
 // A scratch buffer of the context with one region of *floats floats per in-flight slot: grown (behind every stream) if this launch
 // needs more per slot than it has, then -> the region of this batch's slot.  extra_bytes: room behind the regions.
-int slot_scratch(davo_ctx* c, const Run& run, float** buf, size_t* floats, size_t need, float** region, size_t extra_bytes = 0) {
+int slot_scratch(davo_ctx* c, const Run& run, GrowBuf* buf, size_t* floats, size_t need, float** region, size_t extra_bytes = 0) {
     if (need > *floats) {
-        if (*buf) { int rs = sync_all_slots(c); if (rs) return rs; HIP_TRY(c, hipFree(*buf)); *buf = nullptr; }
-        HIP_TRY(c, hipMalloc(reinterpret_cast<void**>(buf), need * sizeof(float) * MAX_INFLIGHT + extra_bytes));   // one region per in-flight slot
+        const size_t bytes = need * sizeof(float) * MAX_INFLIGHT + extra_bytes;         // one region per in-flight slot
+        if (buf->get() && bytes > buf->bytes()) { int rs = sync_all_slots(c); if (rs) return rs; }      // only ahead of a free
+        *floats = 0;
+        HIP_TRY(c, buf->reserve(bytes));
         *floats = need;
     }
-    *region = *buf + (size_t)run.slot * *floats;
+    *region = static_cast<float*>(buf->get()) + (size_t)run.slot * *floats;
     return DAVO_OK;
 }
 
@@ -206,7 +192,7 @@ int run_conv_layer(davo_ctx* c, const Run& run, int li, const float* x, int x_ld
     int Ho, Wo, pt, pl;
     same_pad(Hin, L.KS, L.stride, L.rate, &Ho, &pt);
     same_pad(Win, L.KS, L.stride, L.rate, &Wo, &pl);
-    p.x = x; p.w = L.d_w; p.bias = L.d_b; p.y = y; p.zeros = c->d_zeros;
+    p.x = x; p.w = L.d_w.get(); p.bias = L.d_b.get(); p.y = y; p.zeros = c->d_zeros.get();
     p.Hin = Hin; p.Win = Win; p.Hout = Ho; p.Wout = Wo;
     p.cin_log2 = L.cin_log2; p.x_ld = x_ld; p.x_coff = 0; p.y_ld = y_ld; p.y_coff = 0;
     p.Cout = L.cout; p.pad_t = pt; p.pad_l = pl; p.rate = L.rate;
@@ -221,7 +207,7 @@ int run_conv_layer(davo_ctx* c, const Run& run, int li, const float* x, int x_ld
     if (li == 0 && L.cout <= 16 && c->opt_f32_n16) plan = {{0, mtiles, 16}};      // cnv1 on the 128x16 tile at every batch size (conv_igemm.h, N16)
     if (fuse_pose) {
         { int rs = slot_scratch(c, run, &c->d_pose_tiles, &c->pose_tiles_floats, (size_t)L.groups * mtiles * 8 * 6, &p.pose_partial); if (rs) return rs; }
-        p.pose_w = c->d_wpred;
+        p.pose_w = c->d_wpred.get();
         p.pose_P = Ho * Wo; p.pose_mt = mtiles;
         if (pose_mt) *pose_mt = mtiles;
     }
@@ -232,7 +218,7 @@ int run_conv_layer(davo_ctx* c, const Run& run, int li, const float* x, int x_ld
         int rc = DAVO_OK;
         pc = pad_tables_for(c, li, NB, Ho, Wo, Hin, Win, pt, pl, L.rate, &rc);
         if (rc) return rc;
-        if (pc) { p.row_pixel = pc->row_pixel; p.tile_taps = pc->tile_taps; }
+        if (pc) { p.row_pixel = pc->row_pixel.get(); p.tile_taps = pc->tile_taps.get(); }
     }
     auto order_for = [&](const Launch& l, int ntn) {
         if (pc) return tile_order_pc(c, li, l.mtile0, l.mtiles, ntn, p.M, Ho, Wo, *pc);
@@ -300,8 +286,8 @@ int run_conv_layer_h3(davo_ctx* c, const Run& run, int li, const void* x, int x_
     int Ho, Wo, pt, pl;
     same_pad(Hin, L.KS, L.stride, L.rate, &Ho, &pt);
     same_pad(Win, L.KS, L.stride, L.rate, &Wo, &pl);
-    p.x = static_cast<const uint8_t*>(x); p.w = L.d_wh; p.bias = L.d_bh; p.y = static_cast<uint8_t*>(y);
-    p.zeros = reinterpret_cast<const uint8_t*>(c->d_zeros);
+    p.x = static_cast<const uint8_t*>(x); p.w = L.d_wh.get(); p.bias = L.d_bh.get(); p.y = static_cast<uint8_t*>(y);
+    p.zeros = reinterpret_cast<const uint8_t*>(c->d_zeros.get());
     p.Hin = Hin; p.Win = Win; p.Hout = Ho; p.Wout = Wo;
     p.x_pix_bytes = (long)x_ch * 4; p.x_boff = 0; p.x_pix_log2 = ilog2_exact(x_ch * 4);
     p.cb_log2 = L.cb_log2; p.tpc_log2 = L.tpc_log2; p.cpb = L.cpb; p.nchunks = L.nchunks_h;
@@ -339,10 +325,10 @@ int run_conv_layer_h3(davo_ctx* c, const Run& run, int li, const void* x, int x_
         debug_bytes = (size_t)L.groups * mt * ntn * 512 * 20 * sizeof(float);
 #endif
         { int rs = slot_scratch(c, run, &c->d_pose_tiles, &c->pose_tiles_floats, (size_t)L.groups * mt * ntn * 6, &p.pose_partial, debug_bytes); if (rs) return rs; }
-        p.y_mode = 2; p.pose_w = c->d_wpred;
+        p.y_mode = 2; p.pose_w = c->d_wpred.get();
         p.pose_P = P; p.pose_mt = mt;
         if (pose_out) {      // the launch's last workgroup adds the tiles and writes the poses (pose_tail.h)
-            p.pose_counter = c->slots[run.slot].d_counters; p.pose_bias = c->d_bpred; p.pose_out = pose_out;
+            p.pose_counter = c->slots[run.slot].d_counters.get(); p.pose_bias = c->d_bpred.get(); p.pose_out = pose_out;
             p.pose_NB = NB; p.pose_bm = ts.bm; p.pose_total = L.groups * mt * ntn; p.pose_sel = run.pairs;
         }
         if (pose_bm) *pose_bm = ts.bm;
@@ -446,7 +432,7 @@ int run_conv_layer_h3(davo_ctx* c, const Run& run, int li, const void* x, int x_
             }
             fold = fold && c->xcd_rr > 0;
             if (fold) {
-                ps.sk_counter = c->slots[run.slot].d_counters + 1 + c->max_batch;
+                ps.sk_counter = c->slots[run.slot].d_counters.get() + 1 + c->max_batch;
                 ps.sk_y = p.y; ps.sk_range = p.range; ps.sk_parts = S; ps.sk_relu = 1;
             }
             ProfScope pscope(c, run.stream, L.label);
@@ -504,15 +490,15 @@ constexpr PatchLayer PATCH_LAYERS[3] = {
 int run_patch_layer(davo_ctx* c, const Run& run, int li, bool f32, const void* x, void* y, int NB, bool fused = false, const Inputs& in = Inputs{}) {
     const ConvLayer& L = c->L[li];
     const PatchLayer& t = PATCH_LAYERS[li];
-    const uint8_t* const w_h3[3] = {c->d_w1patch, c->d_w2patch, c->d_w3patch};
-    const float* const w_f32[3] = {c->d_w1patch_f32, c->d_w2patch_f32, c->d_w3patch_f32};
+    const uint8_t* const w_h3[3] = {c->d_w1patch.get(), c->d_w2patch.get(), c->d_w3patch.get()};
+    const float* const w_f32[3] = {c->d_w1patch_f32.get(), c->d_w2patch_f32.get(), c->d_w3patch_f32.get()};
     const int Hin[3] = {c->H, c->H1, c->H2}, Win[3] = {c->W, c->W1, c->W2};
     ConvPatchParams p{};
     same_pad(Hin[li], L.KS, L.stride, L.rate, &p.Ho, &p.pad_t);
     same_pad(Win[li], L.KS, L.stride, L.rate, &p.Wo, &p.pad_l);
     p.x = static_cast<const uint8_t*>(x); p.w = f32 ? reinterpret_cast<const uint8_t*>(w_f32[li]) : w_h3[li];
-    p.bias = f32 ? L.d_b : L.d_bh; p.y = static_cast<uint8_t*>(y);
-    p.zeros = reinterpret_cast<const uint8_t*>(c->d_zeros);
+    p.bias = f32 ? L.d_b.get() : L.d_bh.get(); p.y = static_cast<uint8_t*>(y);
+    p.zeros = reinterpret_cast<const uint8_t*>(c->d_zeros.get());
     p.H = Hin[li]; p.W = Win[li];
     p.tiles_x = (p.Wo + t.tw - 1) / t.tw; p.tiles_y = (p.Ho + t.th - 1) / t.th;
     p.ntiles = NB * p.tiles_x * p.tiles_y;
@@ -524,7 +510,7 @@ int run_patch_layer(davo_ctx* c, const Run& run, int li, bool f32, const void* x
         if (const char* e = tuning_env("DAVO_PDBG")) p.dbg = atoi(e);      // tuning build only
         if (li == 0) {
             p.img = static_cast<const uint8_t*>(in.img); p.flow = static_cast<const float*>(in.flow);
-            p.seg = static_cast<const float*>(in.seg); p.tab = c->slots[run.slot].d_tab; p.v = c->v; p.sel = run.pairs;
+            p.seg = static_cast<const float*>(in.seg); p.tab = c->slots[run.slot].d_tab.get(); p.v = c->v; p.sel = run.pairs;
         }
     }
     c->last_plan[li][0] = ((NB * p.Ho * p.Wo + 127) / 128) * 1000 + t.plan_id; c->last_plan[li][1] = 0; c->last_split[li] = 1;
@@ -545,8 +531,8 @@ int run_direct(davo_ctx* c, const Run& run, const char* label, const float* x, i
         if (!t.dev) { int rc = upload(c, t.data, &t.dev); if (rc) return rc; }
     }
     ProfScope ps(c, run.stream, label);
-    HIP_TRY(c, launch_conv_direct(x, N, Hin, Win, cin, x_ld, x_coff, c->weights.at(wname).dev, KS, cout,
-                                  c->weights.at(bname).dev, stride, rate, pt, pl, Ho, Wo, 1, y, y_ld, y_coff, run.stream));
+    HIP_TRY(c, launch_conv_direct(x, N, Hin, Win, cin, x_ld, x_coff, c->weights.at(wname).dev.get(), KS, cout,
+                                  c->weights.at(bname).dev.get(), stride, rate, pt, pl, Ho, Wo, 1, y, y_ld, y_coff, run.stream));
     return DAVO_OK;
 }
 
@@ -559,21 +545,21 @@ int run_posenn_se(davo_ctx* c, const Run& run, bool h3, const void* x, int NB) {
         for (int k = 0; k < 4; ++k) {
             const auto it = c->weights.find(std::string("pose_exp_net/pose/") + heads[h] + "/cnv5_se_attention/" + parts[k]);
             if (it == c->weights.end() || !it->second.dev) return fail(c, DAVO_ERR_NOT_READY, "feature-attention weights not loaded");
-            w[h * 4 + k] = it->second.dev;
+            w[h * 4 + k] = it->second.dev.get();
         }
-    const Slot& ws = c->slots[run.slot];
-    if (!ws.d_se || !ws.d_se_scale || !ws.d_se_partial) return fail(c, DAVO_ERR_INVALID, "internal: no feature-attention workspace");
+    if (!c->slots[run.slot].se) return fail(c, DAVO_ERR_INVALID, "internal: no feature-attention workspace");
+    const SeWorkspace& ws = *c->slots[run.slot].se;
     const int P = c->H2 * c->W2;
     {
         ProfScope ps(c, run.stream, "se5_squeeze");
-        HIP_TRY(c, launch_se5_squeeze(h3, x, NB, P, ws.d_se_partial, run.stream));
+        HIP_TRY(c, launch_se5_squeeze(h3, x, NB, P, ws.d_se_partial.get(), run.stream));
     }
     {
         ProfScope ps(c, run.stream, "se5_excite");
-        HIP_TRY(c, launch_se5_excite(ws.d_se_partial, NB, P, h3 ? ldexpf(1.0f, -c->act_shift[4]) : 1.0f, w, ws.d_se_scale, run.stream));
+        HIP_TRY(c, launch_se5_excite(ws.d_se_partial.get(), NB, P, h3 ? ldexpf(1.0f, -c->act_shift[4]) : 1.0f, w, ws.d_se_scale.get(), run.stream));
     }
     ProfScope ps(c, run.stream, "se5_scale");
-    HIP_TRY(c, launch_se5_scale(h3, x, ws.d_se_scale, NB, P, ws.d_se, (h3 && run.range) ? run.range + RANGE_SE : nullptr, run.stream));
+    HIP_TRY(c, launch_se5_scale(h3, x, ws.d_se_scale.get(), NB, P, ws.d_se.get(), (h3 && run.range) ? run.range + RANGE_SE : nullptr, run.stream));
     return DAVO_OK;
 }
 
@@ -616,13 +602,18 @@ int forward_device(davo_ctx* c, const Run& run, int B, const Inputs& in, void* d
     const int H = c->H, W = c->W, HW = H * W, NB = pairs_per_window(sel) * B;
     const Variant& v = c->v;
     const Slot& ws = c->slots[run.slot];
+    float *const d_partial = ws.d_partial.get(), *const d_tab = ws.d_tab.get(), *const d_packed = ws.d_packed.get();
+    float* const d_se = ws.se ? ws.se->d_se.get() : nullptr;                  // feature attention: cnv6's input (run_posenn_se fills it)
+    unsigned* const d_counters = ws.d_counters.get();
+    float* a[7];
+    for (int i = 0; i < 7; ++i) a[i] = ws.d_act[i].get();
     hipStream_t s = run.stream;
     const uint8_t* const d_img = static_cast<const uint8_t*>(in.img);
     const float* const d_flow = static_cast<const float*>(in.flow);
     const float* const d_seg = static_cast<const float*>(in.seg);
     auto wdev = [&](const char* n) -> const float* {
         auto it = c->weights.find(n);
-        return it == c->weights.end() ? nullptr : it->second.dev;
+        return it == c->weights.end() ? nullptr : it->second.dev.get();
     };
     // Launches are ~6 us each whatever they do; at batch 1 the path is 11 of them around 0.1 ms of work.  Where a launch can be
     // folded into its neighbour at less than that, small batches do it (measured per batch: profiles/):
@@ -639,28 +630,28 @@ int forward_device(davo_ctx* c, const Run& run, int B, const Inputs& in, void* d
     if (needs_depth(c)) {
         // depth sources: one float32 sum per depth plane and chunk, then (or, folded, in the same launch) the excitation
         ProfScope ps(c, run.stream, "se_depth_squeeze");
-        HIP_TRY(c, launch_se_depth_squeeze(fold_excite, static_cast<const float*>(in.depth), B, HW, v, reinterpret_cast<unsigned*>(ws.d_partial),
-                                           ws.d_counters + 1, se_w1, se_b1, se_w2, se_b2, ws.d_tab, range_reset, sel, s));
+        HIP_TRY(c, launch_se_depth_squeeze(fold_excite, static_cast<const float*>(in.depth), B, HW, v, reinterpret_cast<unsigned*>(d_partial),
+                                           d_counters + 1, se_w1, se_b1, se_w2, se_b2, d_tab, range_reset, sel, s));
     } else if (class_table) {
         // segmentation / rgb / seg+flow sources: per-frame histogram, byte or flow sums, then (or, folded, in the same launch) the
         // excitation
         ProfScope ps(c, run.stream, "se_class_squeeze");
-        HIP_TRY(c, launch_se_class_squeeze(fold_excite, d_img, d_flow, d_seg, B, H, W, v, reinterpret_cast<unsigned*>(ws.d_partial),
-                                           ws.d_counters + 1, se_w1, se_b1, se_w2, se_b2, ws.d_tab, range_reset, sel, s));
+        HIP_TRY(c, launch_se_class_squeeze(fold_excite, d_img, d_flow, d_seg, B, H, W, v, reinterpret_cast<unsigned*>(d_partial),
+                                           d_counters + 1, se_w1, se_b1, se_w2, se_b2, d_tab, range_reset, sel, s));
     } else if (fold_excite) {
         // squeeze + excitation in one launch: the workgroup that delivers a triplet's last partial sum evaluates its tables
         ProfScope ps(c, run.stream, "se_squeeze_partial");
-        HIP_TRY(c, launch_se_squeeze_excite(d_flow, B, HW, v, ws.d_partial, ws.d_counters + 1,
+        HIP_TRY(c, launch_se_squeeze_excite(d_flow, B, HW, v, d_partial, d_counters + 1,
                                             se_w1, se_b1, se_w2, se_b2,
-                                            wdev("pose_exp_net/pose_exp_net/seg_channel_weight/weight"), ws.d_tab, range_reset, sel, s));
+                                            wdev("pose_exp_net/pose_exp_net/seg_channel_weight/weight"), d_tab, range_reset, sel, s));
     } else if (v.att_source == 1) {
         ProfScope ps(c, run.stream, "se_squeeze_partial");
-        HIP_TRY(c, launch_se_squeeze(d_flow, B, HW, v, ws.d_partial, sel, s));
+        HIP_TRY(c, launch_se_squeeze(d_flow, B, HW, v, d_partial, sel, s));
     }
     if (!fold_excite) {
         ProfScope ps(c, run.stream, "se_excite");
-        HIP_TRY(c, launch_se_excite(ws.d_partial, B, HW, v, se_w1, se_b1, se_w2, se_b2,
-                                    wdev("pose_exp_net/pose_exp_net/seg_channel_weight/weight"), ws.d_tab, range_reset, sel, s));
+        HIP_TRY(c, launch_se_excite(d_partial, B, HW, v, se_w1, se_b1, se_w2, se_b2,
+                                    wdev("pose_exp_net/pose_exp_net/seg_channel_weight/weight"), d_tab, range_reset, sel, s));
     }
     // f16x3, fuse_pack: cnv1 builds its input patch straight from the raw inputs (mask + pack fused in,
     // the packed tensor never touches HBM).  Measured equal in time to mask_pack + cnv1 (the fused fill is bound
@@ -675,17 +666,16 @@ int forward_device(davo_ctx* c, const Run& run, int B, const Inputs& in, void* d
     c->packed_ld = run.impl == 0 ? 8 : 10;
     if (!fused) {
         ProfScope ps(c, run.stream, "mask_pack");
-        HIP_TRY(c, launch_mask_pack(h3 ? 16 : (run.impl == 0 ? 8 : 10), d_img, d_flow, d_seg, ws.d_tab, v, B, H, W, ws.d_packed, sel, s));
+        HIP_TRY(c, launch_mask_pack(h3 ? 16 : (run.impl == 0 ? 8 : 10), d_img, d_flow, d_seg, d_tab, v, B, H, W, d_packed, sel, s));
     }
     const int c6 = v.cnv6_out;
-    float* const* a = ws.d_act;
     int rc;
     bool pose_fused = false;
     int pose_bm = 0, pose_mt = 0, pose_ntn = 0;
     c->cnv7_valid = true;
     if (h3) {
-        if (patch1) { if ((rc = run_patch_layer(c, run, 0, false, ws.d_packed, a[0], NB, fused, in))) return rc; }
-        else if ((rc = run_conv_layer_h3(c, run, 0, ws.d_packed, 8, H, W, a[0], 16, false, NB))) return rc;
+        if (patch1) { if ((rc = run_patch_layer(c, run, 0, false, d_packed, a[0], NB, fused, in))) return rc; }
+        else if ((rc = run_conv_layer_h3(c, run, 0, d_packed, 8, H, W, a[0], 16, false, NB))) return rc;
         const char* p2e = tuning_env("DAVO_CNV2_PATCH");
         if (c->opt_patch_cnv2 && c->L[1].tile_h < 0 && !(p2e && atoi(p2e) == 0)) { if ((rc = run_patch_layer(c, run, 1, false, a[0], a[1], NB))) return rc; }
         else if ((rc = run_conv_layer_h3(c, run, 1, a[0], 16, c->H1, c->W1, a[1], 32, false, NB))) return rc;
@@ -696,15 +686,15 @@ int forward_device(davo_ctx* c, const Run& run, int B, const Inputs& in, void* d
         if ((rc = run_conv_layer_h3(c, run, 4, a[3], 128, c->H2, c->W2, a[4], 256, false, NB))) return rc;
         if (c->posenn_se) {
             if ((rc = run_posenn_se(c, run, true, a[4], NB))) return rc;
-            if ((rc = run_conv_layer_h3(c, run, 5, ws.d_se, 512, c->H2, c->W2, a[5], 2 * c6, false, NB))) return rc;
+            if ((rc = run_conv_layer_h3(c, run, 5, d_se, 512, c->H2, c->W2, a[5], 2 * c6, false, NB))) return rc;
         } else if ((rc = run_conv_layer_h3(c, run, 5, a[4], 256, c->H2, c->W2, a[5], 2 * c6, false, NB))) return rc;
         pose_fused = c->opt_fuse_pose && c->H3 * c->W3 >= 128;
         if ((rc = run_conv_layer_h3(c, run, 6, a[5], 2 * c6, c->H2, c->W2, a[6], 512, true, NB, pose_fused, &pose_bm, &pose_mt, &pose_ntn,
                                     fold_pose ? static_cast<float*>(d_pose) : nullptr))) return rc;
         c->cnv7_valid = !pose_fused;
     } else if (run.impl == 0) {
-        if (c->opt_patch_f32 && c->d_w1patch_f32 && c->packed_ld == 8) { if ((rc = run_patch_layer(c, run, 0, true, ws.d_packed, a[0], NB))) return rc; }
-        else if ((rc = run_conv_layer(c, run, 0, ws.d_packed, 8, H, W, a[0], 16, NB))) return rc;
+        if (c->opt_patch_f32 && c->d_w1patch_f32 && c->packed_ld == 8) { if ((rc = run_patch_layer(c, run, 0, true, d_packed, a[0], NB))) return rc; }
+        else if ((rc = run_conv_layer(c, run, 0, d_packed, 8, H, W, a[0], 16, NB))) return rc;
         if (c->opt_patch_f32 && c->d_w2patch_f32) { if ((rc = run_patch_layer(c, run, 1, true, a[0], a[1], NB))) return rc; }
         else if ((rc = run_conv_layer(c, run, 1, a[0], 16, c->H1, c->W1, a[1], 32, NB))) return rc;
         if (c->opt_patch_f32 && c->d_w3patch_f32) { if ((rc = run_patch_layer(c, run, 2, true, a[1], a[2], NB))) return rc; }
@@ -713,7 +703,7 @@ int forward_device(davo_ctx* c, const Run& run, int B, const Inputs& in, void* d
         if ((rc = run_conv_layer(c, run, 4, a[3], 128, c->H2, c->W2, a[4], 256, NB))) return rc;
         if (c->posenn_se) {
             if ((rc = run_posenn_se(c, run, false, a[4], NB))) return rc;
-            if ((rc = run_conv_layer(c, run, 5, ws.d_se, 512, c->H2, c->W2, a[5], 2 * c6, NB))) return rc;
+            if ((rc = run_conv_layer(c, run, 5, d_se, 512, c->H2, c->W2, a[5], 2 * c6, NB))) return rc;
         } else if ((rc = run_conv_layer(c, run, 5, a[4], 256, c->H2, c->W2, a[5], 2 * c6, NB))) return rc;
         // float32 mode, round 4: the pose head in cnv7's epilogue like the f16x3 path's (the 109 MB activation is neither written nor
         // read back, pose_head_partial + pose_finish become pose_from_tiles); tiles of 128 rows must not span more than two images
@@ -725,7 +715,7 @@ int forward_device(davo_ctx* c, const Run& run, int B, const Inputs& in, void* d
         const std::string P = "pose_exp_net/";
         const int c10 = 2 * v.cin_per_frame;
         if (v.cin_per_frame != 5) return fail(c, DAVO_ERR_INVALID, "impl 1 supports the 10-channel (v1) input only");
-        if ((rc = run_direct(c, run, "cnv1", ws.d_packed, NB, H, W, c10, 10, 0, P + "cnv1/weights", P + "cnv1/biases", 7, 16, 2, 1, a[0], 16, 0))) return rc;
+        if ((rc = run_direct(c, run, "cnv1", d_packed, NB, H, W, c10, 10, 0, P + "cnv1/weights", P + "cnv1/biases", 7, 16, 2, 1, a[0], 16, 0))) return rc;
         if ((rc = run_direct(c, run, "cnv2", a[0], NB, c->H1, c->W1, 16, 16, 0, P + "cnv2/weights", P + "cnv2/biases", 5, 32, 2, 1, a[1], 32, 0))) return rc;
         if ((rc = run_direct(c, run, "cnv3", a[1], NB, c->H2, c->W2, 32, 32, 0, P + "cnv3/weights", P + "cnv3/biases", 3, 64, 1, 2, a[2], 64, 0))) return rc;
         if ((rc = run_direct(c, run, "cnv4", a[2], NB, c->H2, c->W2, 64, 64, 0, P + "cnv4/weights", P + "cnv4/biases", 3, 128, 1, 4, a[3], 128, 0))) return rc;
@@ -735,7 +725,7 @@ int forward_device(davo_ctx* c, const Run& run, int B, const Inputs& in, void* d
         for (int h = 0; h < 2; ++h) {
             const std::string hp = P + "pose/" + heads[h] + "/";
             // feature attention: head h reads its half of the scaled tensor
-            const float* x6 = c->posenn_se ? ws.d_se : a[4];
+            const float* x6 = c->posenn_se ? d_se : a[4];
             if ((rc = run_direct(c, run, "cnv6", x6, NB, c->H2, c->W2, 256, c->posenn_se ? 512 : 256, c->posenn_se ? h * 256 : 0, hp + "cnv6/weights", hp + "cnv6/biases", 3, c6, 1, 2, a[5], 2 * c6, h * c6))) return rc;
             if ((rc = run_direct(c, run, "cnv7", a[5], NB, c->H2, c->W2, c6, 2 * c6, h * c6, hp + "cnv7/weights", hp + "cnv7/biases", 3, 256, 2, 1, a[6], 512, h * 256))) return rc;
         }
@@ -744,11 +734,11 @@ int forward_device(davo_ctx* c, const Run& run, int B, const Inputs& in, void* d
     if (!(pose_fused && fold_pose)) {
         ProfScope ps(c, run.stream, "pose_head");
         if (pose_fused) {
-            HIP_TRY(c, launch_pose_from_tiles(c->d_pose_tiles + (size_t)run.slot * c->pose_tiles_floats, NB, c->H3 * c->W3, pose_bm,
-                                              pose_mt, pose_ntn, c->d_bpred, static_cast<float*>(d_pose), h3 ? run.snap : SnapArgs{}, sel, s));
+            HIP_TRY(c, launch_pose_from_tiles(static_cast<const float*>(c->d_pose_tiles.get()) + (size_t)run.slot * c->pose_tiles_floats, NB, c->H3 * c->W3, pose_bm,
+                                              pose_mt, pose_ntn, c->d_bpred.get(), static_cast<float*>(d_pose), h3 ? run.snap : SnapArgs{}, sel, s));
             snap_done = true;
         } else {
-            HIP_TRY(c, launch_pose_head(a[6], NB, c->H3 * c->W3, c->d_wpred, c->d_bpred, ws.d_pose_partial, static_cast<float*>(d_pose), sel, s));
+            HIP_TRY(c, launch_pose_head(a[6], NB, c->H3 * c->W3, c->d_wpred.get(), c->d_bpred.get(), ws.d_pose_partial.get(), static_cast<float*>(d_pose), sel, s));
         }
     }
     // the range guard's conditional copy of this batch's inputs (api.hip: tickets) rides in pose_from_tiles; other pose heads get a launch

@@ -7,6 +7,7 @@
 #include "conv_patch_h3.h"
 #include "conv_patch_f32.h"
 #include "launch.h"
+#include "owned.h"
 #include "posenn_se.h"
 #include "prologue.h"
 
@@ -106,16 +107,15 @@ __global__ __launch_bounds__(64) void xcd_probe_kernel(unsigned* out) {
 
 hipError_t xcd_round_robin_probe(hipStream_t s, int* ok) {
     constexpr int NX = 64, NY = 4;
-    unsigned* d = nullptr;
+    DevMem<unsigned> d;
     unsigned h[NX * NY];
     *ok = 0;
-    hipError_t e = hipMalloc(reinterpret_cast<void**>(&d), sizeof h);
+    hipError_t e = dev_alloc(&d, NX * NY);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(xcd_probe_kernel, dim3(NX, NY), dim3(64), 0, s, d);
+    hipLaunchKernelGGL(xcd_probe_kernel, dim3(NX, NY), dim3(64), 0, s, d.get());
     e = hipGetLastError();
-    if (e == hipSuccess) e = hipMemcpyAsync(h, d, sizeof h, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(h, d.get(), sizeof h, hipMemcpyDeviceToHost, s);
     if (e == hipSuccess) e = hipStreamSynchronize(s);
-    (void)hipFree(d);
     if (e != hipSuccess) return e;
     bool same = true;
     for (int y = 1; y < NY; ++y)

@@ -28,14 +28,20 @@
 namespace davo {
 
 int ensure_ring(davo_ctx* c, bool snapshots) {
-    if (!c->read_stream) {
-        HIP_TRY(c, hipStreamCreateWithFlags(&c->read_stream, hipStreamNonBlocking));
-        HIP_TRY(c, hipHostMalloc(reinterpret_cast<void**>(&c->h_range), (1 + RANGE_RING) * RANGE_WORDS * sizeof(unsigned), hipHostMallocMapped | hipHostMallocCoherent));
-        HIP_TRY(c, hipHostGetDevicePointer(reinterpret_cast<void**>(&c->h_range_dev), c->h_range, 0));
-        memset(c->h_range, 0, (1 + RANGE_RING) * RANGE_WORDS * sizeof(unsigned));
+    if (!c->ring) {
+        constexpr size_t words = (1 + RANGE_RING) * RANGE_WORDS;
+        RangeRing r;
+        HIP_TRY(c, stream_create(&r.read_stream));
+        HIP_TRY(c, pinned_alloc(&r.h_range, words, hipHostMallocMapped | hipHostMallocCoherent));
+        HIP_TRY(c, hipHostGetDevicePointer(reinterpret_cast<void**>(&r.h_range_dev), r.h_range.get(), 0));
+        memset(r.h_range.get(), 0, words * sizeof(unsigned));
+        c->ring = std::move(r);
     }
-    if (snapshots && !c->snap_sets[0].img)
-        for (InputSet& set : c->snap_sets) { int rc = alloc_input_set(c, &set, false); if (rc) return rc; }
+    if (snapshots && !c->snaps) {
+        Snapshots sn;
+        for (InputSet& set : sn.sets) { int rc = alloc_input_set(c, &set, false); if (rc) return rc; }
+        c->snaps = std::move(sn);
+    }
     return DAVO_OK;
 }
 
@@ -43,18 +49,19 @@ namespace {
 
 // a record -> host, on a stream of its own (never behind queued batches, never through the null stream)
 int read_record(davo_ctx* c, const unsigned* d_rec, unsigned raw[RANGE_WORDS]) {
-    if (!c->read_stream) { int rc = ensure_ring(c, false); if (rc) return rc; }
-    HIP_TRY(c, hipMemcpyAsync(c->h_range, d_rec, RANGE_WORDS * sizeof(unsigned), hipMemcpyDeviceToHost, c->read_stream));
-    HIP_TRY(c, hipStreamSynchronize(c->read_stream));
-    memcpy(raw, c->h_range, RANGE_WORDS * sizeof(unsigned));
+    { int rc = ensure_ring(c, false); if (rc) return rc; }
+    const RangeRing& r = *c->ring;
+    HIP_TRY(c, hipMemcpyAsync(r.h_range.get(), d_rec, RANGE_WORDS * sizeof(unsigned), hipMemcpyDeviceToHost, r.read_stream.get()));
+    HIP_TRY(c, hipStreamSynchronize(r.read_stream.get()));
+    memcpy(raw, r.h_range.get(), RANGE_WORDS * sizeof(unsigned));
     return DAVO_OK;
 }
 
-unsigned* ring_record(davo_ctx* c, int r) { return c->d_range_base + RANGE_WORDS * (1 + r); }
-const unsigned* ring_mirror(const davo_ctx* c, int r) { return c->h_range + RANGE_WORDS * (1 + r); }
+unsigned* ring_record(davo_ctx* c, int r) { return c->d_range_base.get() + RANGE_WORDS * (1 + r); }
+const unsigned* ring_mirror(const davo_ctx* c, int r) { return c->ring->h_range.get() + RANGE_WORDS * (1 + r); }      // (a ticket exists, so the ring does)
 
 int zero_base_record(davo_ctx* c, hipStream_t s) {
-    HIP_TRY(c, hipMemsetAsync(c->d_range_base, 0, RANGE_WORDS * sizeof(unsigned), s));
+    HIP_TRY(c, hipMemsetAsync(c->d_range_base.get(), 0, RANGE_WORDS * sizeof(unsigned), s));
     return DAVO_OK;
 }
 
@@ -130,7 +137,7 @@ int freeze_pending_and_reset_ring(davo_ctx* c) {
             { int rc = wait_record(c, ring_mirror(c, t.ring), t.seq, t.stream, t.raw); if (rc) return rc; }
             t.frozen = true;
         }
-    { int rc = zero_now(c, c->d_range_base + RANGE_WORDS, RANGE_RING * RANGE_WORDS * sizeof(unsigned)); if (rc) return rc; }
+    { int rc = zero_now(c, c->d_range_base.get() + RANGE_WORDS, RANGE_RING * RANGE_WORDS * sizeof(unsigned)); if (rc) return rc; }
     return DAVO_OK;
 }
 
@@ -149,7 +156,7 @@ int calibrate_on(davo_ctx* c, int B, const Inputs& in, void* d_pose, int sel) {
         if (rc) break;
         if (hipStreamSynchronize(run.stream) != hipSuccess) { rc = fail(c, DAVO_ERR_HIP, "hipStreamSynchronize failed"); break; }
         unsigned raw[RANGE_WORDS];
-        if ((rc = read_record(c, c->d_range_base, raw))) break;
+        if ((rc = read_record(c, c->d_range_base.get(), raw))) break;
         bool changed = false;
         for (int i = 0; i < 6; ++i) {
             float v;
@@ -178,7 +185,7 @@ int run_judged(davo_ctx* c, const Run& run, const Reissue& b) {
     HIP_TRY(c, hipStreamSynchronize(run.stream));
     if (!res.h3) return DAVO_OK;
     unsigned raw[RANGE_WORDS];
-    if ((rc = read_record(c, c->d_range_base, raw))) return rc;
+    if ((rc = read_record(c, c->d_range_base.get(), raw))) return rc;
     return judge_record(c, raw, c->act_shift);
 }
 
@@ -194,9 +201,9 @@ int recover_batch(davo_ctx* c, const Reissue& orig) {
     { int rc = sync_all_slots(c); if (rc) return rc; }
     const std::string verdict = c->err;
     { int rc = freeze_pending_and_reset_ring(c); if (rc) return rc; }       // the failed slot's maximum must go; the scales may move
-    if (!c->d_reissue_pose) HIP_TRY(c, hipMalloc(reinterpret_cast<void**>(&c->d_reissue_pose), (size_t)c->max_batch * 12 * sizeof(float)));
+    if (!c->d_reissue_pose) HIP_TRY(c, dev_alloc(&c->d_reissue_pose, (size_t)c->max_batch * 12));
     Reissue b = orig;
-    b.pose = c->d_reissue_pose;
+    b.pose = c->d_reissue_pose.get();
     Run run = make_run(c, 0);
     run.pairs = b.pairs;
     int rc = run_judged(c, run, b);
@@ -216,7 +223,7 @@ int recover_batch(davo_ctx* c, const Reissue& orig) {
     if (rc) return rc;
     HIP_TRY(c, hipStreamSynchronize(run.stream));
     if (!c->book.superseded(orig))
-        HIP_TRY(c, hipMemcpy(orig.pose, c->d_reissue_pose, (size_t)orig.B * 12 * sizeof(float), hipMemcpyDeviceToDevice));
+        HIP_TRY(c, hipMemcpy(orig.pose, c->d_reissue_pose.get(), (size_t)orig.B * 12 * sizeof(float), hipMemcpyDeviceToDevice));
     ++c->n_reissued;
     c->err.clear();
     return DAVO_OK;
@@ -241,8 +248,8 @@ int judge_front(davo_ctx* c) {
     } else if (rc == DAVO_ERR_RANGE && !t.frozen) {
         // no recovery ("auto_range" 0): the slot's running maximum has served its verdict - the next batch starts afresh
         const std::string keep = c->err;
-        if (hipMemsetAsync(ring_record(c, t.ring), 0, RANGE_WORDS * sizeof(unsigned), c->read_stream) != hipSuccess ||
-            hipStreamSynchronize(c->read_stream) != hipSuccess) rc = fail(c, DAVO_ERR_HIP, "resetting a range record failed");
+        if (hipMemsetAsync(ring_record(c, t.ring), 0, RANGE_WORDS * sizeof(unsigned), c->ring->read_stream.get()) != hipSuccess ||
+            hipStreamSynchronize(c->ring->read_stream.get()) != hipSuccess) rc = fail(c, DAVO_ERR_HIP, "resetting a range record failed");
         else c->err = keep;
     }
     c->book.release(t.ring);              // after the re-issue: it read the slot's copy of the inputs
@@ -294,12 +301,13 @@ int ticket_begin(davo_ctx* c, Run* run, int B, const Inputs& in, Ticket* t, bool
         if (c->posenn_se) HIP_TRY(c, hipMemsetAsync(run->range + RANGE_SE, 0, sizeof(unsigned), run->stream));
     }
     t->seq = c->book.next_seq();
-    const InputSet keep = t->snap ? c->snap_sets[r] : InputSet();      // no snapshot: no destination, and the ticket remembers the caller's buffers
+    const InputSet none;
+    const InputSet& keep = t->snap ? c->snaps->sets[r] : none;        // no snapshot: no destination, and the ticket remembers the caller's buffers
     t->in = t->snap ? keep.view() : in;
     const PlaneBytes nb = plane_bytes(c);
     auto src = [](const void* q) { return static_cast<const uint8_t*>(q); };
-    auto dst = [](void* q) { return static_cast<uint8_t*>(q); };
-    run->snap = SnapArgs{run->range, c->h_range_dev + RANGE_WORDS * (1 + r), t->seq,
+    auto dst = [](const DevMem<void>& q) { return static_cast<uint8_t*>(q.get()); };
+    run->snap = SnapArgs{run->range, c->ring->h_range_dev + RANGE_WORDS * (1 + r), t->seq,
                        src(in.img), src(in.flow), src(in.seg), dst(keep.img), dst(keep.flow), dst(keep.seg),
                        (unsigned)(nb.img / 16), (unsigned)(nb.flow / 32), (unsigned)(nb.flow / 16), (unsigned)(nb.seg / 16), B,
                        src(in.depth), dst(keep.depth), c->posenn_se};

@@ -159,12 +159,15 @@ bool expected_shape(const davo_ctx* c, const std::string& name, std::vector<int6
     return true;
 }
 
-int upload(davo_ctx* c, const std::vector<float>& host, float** dev) {
-    if (*dev) { HIP_TRY(c, hipFree(*dev)); *dev = nullptr; }
-    HIP_TRY(c, hipMalloc(reinterpret_cast<void**>(dev), host.size() * sizeof(float)));
-    HIP_TRY(c, hipMemcpy(*dev, host.data(), host.size() * sizeof(float), hipMemcpyHostToDevice));
+// n elements of host memory -> *dev, which gives up what it held first (a failed free is reported)
+template <class T>
+static int upload_n(davo_ctx* c, const void* host, size_t n, DevMem<T>* dev) {
+    HIP_TRY(c, dev_realloc(dev, n));
+    HIP_TRY(c, hipMemcpy(dev->get(), host, n * sizeof(T), hipMemcpyHostToDevice));
     return DAVO_OK;
 }
+
+int upload(davo_ctx* c, const std::vector<float>& host, DevMem<float>* dev) { return upload_n(c, host.data(), host.size(), dev); }
 
 void init_layer(ConvLayer& L, const char* label, int KS, int stride, int rate, int cin, int cout, int groups) {
     L.label = label; L.KS = KS; L.stride = stride; L.rate = rate;
@@ -302,13 +305,6 @@ int build_packed_weights(davo_ctx* c) {
     return DAVO_OK;
 }
 
-static int upload_bytes(davo_ctx* c, const void* host, size_t bytes, void** dev) {
-    if (*dev) { HIP_TRY(c, hipFree(*dev)); *dev = nullptr; }
-    HIP_TRY(c, hipMalloc(dev, bytes));
-    HIP_TRY(c, hipMemcpy(*dev, host, bytes, hipMemcpyHostToDevice));
-    return DAVO_OK;
-}
-
 // split-fp16 weights for the f16x3 path, same layer structure as build_packed_weights
 int build_packed_weights_h3(davo_ctx* c) {
     const int c6 = c->v.cnv6_out, cpf = c->v.cin_per_frame;
@@ -359,7 +355,7 @@ int build_packed_weights_h3(davo_ctx* c) {
                 pack(p + "weights", p + "biases", c6, 256, nullptr, wp.data() + (size_t)h * per_group, bp.data() + (size_t)h * L.npad_h);
             }
         }
-        int rc = upload_bytes(c, wp.data(), wp.size() * sizeof(_Float16), reinterpret_cast<void**>(&L.d_wh));
+        int rc = upload_n(c, wp.data(), wp.size() * sizeof(_Float16), &L.d_wh);
         if (rc) return rc;
         rc = upload(c, bp, &L.d_bh);
         if (rc) return rc;
@@ -380,7 +376,7 @@ int build_packed_weights_h3(davo_ctx* c) {
                     split_f16(v, &wp[((size_t)(step * 2 + 0) * 64 + l) * 8 + j], &wp[((size_t)(step * 2 + 1) * 64 + l) * 8 + j]);
                 }
             }
-        int rc = upload_bytes(c, wp.data(), wp.size() * sizeof(_Float16), reinterpret_cast<void**>(&c->d_w1patch));
+        int rc = upload_n(c, wp.data(), wp.size() * sizeof(_Float16), &c->d_w1patch);
         if (rc) return rc;
     }
     {   // cnv2 patch kernel: [15 steps = ky x tap pair h][N group][hi|lo][64 lanes][8 halves]; lane = (channel c = l&15,
@@ -400,7 +396,7 @@ int build_packed_weights_h3(davo_ctx* c) {
                         split_f16(v, &wp[(base + l) * 8 + j], &wp[(base + 64 + l) * 8 + j]);
                     }
                 }
-        int rc = upload_bytes(c, wp.data(), wp.size() * sizeof(_Float16), reinterpret_cast<void**>(&c->d_w2patch));
+        int rc = upload_n(c, wp.data(), wp.size() * sizeof(_Float16), &c->d_w2patch);
         if (rc) return rc;
     }
     {   // cnv3 patch kernel: [9 taps][4 N groups][hi|lo][64 lanes][8 halves]; lane = (channel c = l&15, channel quarter kq = l>>4)
@@ -417,7 +413,7 @@ int build_packed_weights_h3(davo_ctx* c) {
                         split_f16(v, &wp[(base + l) * 8 + j], &wp[(base + 64 + l) * 8 + j]);
                     }
                 }
-        int rc = upload_bytes(c, wp.data(), wp.size() * sizeof(_Float16), reinterpret_cast<void**>(&c->d_w3patch));
+        int rc = upload_n(c, wp.data(), wp.size() * sizeof(_Float16), &c->d_w3patch);
         if (rc) return rc;
     }
     {   // Per-channel guard of the f16x3 arithmetic.  One power-of-two scale per layer keeps the LAYER's largest

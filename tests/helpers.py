@@ -1,3 +1,4 @@
+import ctypes
 import json
 import os
 
@@ -55,3 +56,12 @@ def checksum_matches(arr, ck, rtol=1e-5):
     assert abs(a.mean() - ck["mean"]) <= rtol * scale
     for i, v in ck["samples"]:
         assert abs(a[i] - v) <= 10 * rtol * max(abs(v), scale), (i, a[i], v)
+
+
+def hip_free_bytes():
+    """free device memory through hipMemGetInfo of the HIP runtime the library itself is linked against"""
+    path = next(line.split()[-1] for line in open("/proc/self/maps") if "libamdhip64" in line)
+    hip = ctypes.CDLL(path)
+    free, total = ctypes.c_size_t(0), ctypes.c_size_t(0)
+    assert hip.hipMemGetInfo(ctypes.byref(free), ctypes.byref(total)) == 0
+    return free.value

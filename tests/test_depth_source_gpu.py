@@ -13,7 +13,7 @@ from davo_amd.version import NUM_SEG_CLASSES, weight_shapes
 
 import depth_source_ref as D
 import layer_check as LC
-from helpers import assert_pose_close, ABS_TOL, REL_TOL
+from helpers import assert_pose_close, ABS_TOL, REL_TOL, hip_free_bytes
 
 pytestmark = pytest.mark.gpu
 
@@ -332,15 +332,6 @@ def test_three_input_entry_points_refuse_a_depth_context_and_depth_forms_serve_t
     f.close()
 
 
-def _hip_free_bytes():
-    """free device memory through hipMemGetInfo of the HIP runtime the library itself is linked against"""
-    path = next(line.split()[-1] for line in open("/proc/self/maps") if "libamdhip64" in line)
-    hip = ctypes.CDLL(path)
-    free, total = ctypes.c_size_t(0), ctypes.c_size_t(0)
-    assert hip.hipMemGetInfo(ctypes.byref(free), ctypes.byref(total)) == 0
-    return free.value
-
-
 def test_create_and_close_leaves_no_device_memory_behind():
     """Ten depth engines that each stream two batches and recover the first: staging sets, the snapshot ring (depth planes
     included), the records' host mirror - everything goes with the context."""
@@ -359,7 +350,7 @@ def test_create_and_close_leaves_no_device_memory_behind():
         e.synchronize()
         assert e.range_stats()["reissued"] >= 1
         e.close()
-        free.append(_hip_free_bytes())
+        free.append(hip_free_bytes())
     assert free[9] == free[0], free
 
 

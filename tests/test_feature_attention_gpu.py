@@ -18,7 +18,7 @@ from davo_amd.davo import DavoRangeError
 import feature_attention_cases as K
 import feature_attention_ref as F
 import layer_check as LC
-from helpers import assert_pose_close
+from helpers import assert_pose_close, hip_free_bytes
 
 pytestmark = pytest.mark.gpu
 
@@ -213,15 +213,6 @@ def test_the_mode_is_fixed_before_the_first_weight():
     p.close()
 
 
-def _hip_free_bytes():
-    """free device memory through hipMemGetInfo of the HIP runtime the library itself is linked against"""
-    path = next(line.split()[-1] for line in open("/proc/self/maps") if "libamdhip64" in line)
-    hip = ctypes.CDLL(path)
-    free, total = ctypes.c_size_t(0), ctypes.c_size_t(0)
-    assert hip.hipMemGetInfo(ctypes.byref(free), ctypes.byref(total)) == 0
-    return free.value
-
-
 def test_create_and_close_leaves_no_device_memory_behind():
     H, W, B = SMALL
     cfg, inp, w, _ = K.case(H, W, B)
@@ -234,7 +225,7 @@ def test_create_and_close_leaves_no_device_memory_behind():
         e.submit(*inp, out)
         e.wait()
         e.close()
-        free.append(_hip_free_bytes())
+        free.append(hip_free_bytes())
     assert free[9] == free[0], free
 
 

@@ -15,6 +15,8 @@ import pytest
 
 from davo_amd import DAVO, DavoError, Engine, FLAGSHIP_VERSION, parse_version, synth
 
+from helpers import hip_free_bytes
+
 import depth_source_ref as D
 import feature_export_ref as FR
 import layer_check as LC
@@ -307,15 +309,6 @@ def test_errors():
 
 
 # ---- memory -----------------------------------------------------------------------------------------------------------
-def _hip_free_bytes():
-    """free device memory through hipMemGetInfo of the HIP runtime the library itself is linked against"""
-    path = next(line.split()[-1] for line in open("/proc/self/maps") if "libamdhip64" in line)
-    hip = ctypes.CDLL(path)
-    free, total = ctypes.c_size_t(0), ctypes.c_size_t(0)
-    assert hip.hipMemGetInfo(ctypes.byref(free), ctypes.byref(total)) == 0
-    return free.value
-
-
 def test_the_workspace_goes_with_the_context_and_costs_nothing_while_off():
     cfg = parse_version(FLAGSHIP_VERSION)
     B, H, W = 3, 64, 96
@@ -326,18 +319,18 @@ def test_the_workspace_goes_with_the_context_and_costs_nothing_while_off():
         e = _engine(cfg, H, W, B, weights, "f16x3")
         _features(e, inputs)
         e.close()
-        free.append(_hip_free_bytes())
+        free.append(hip_free_bytes())
     assert free[9] == free[0], free
     # never enabled: what a context allocates is what it allocates after enable + disable
     e = _engine(cfg, H, W, B, weights, "f16x3", export=False)
     _forward(e, inputs)
-    never = _hip_free_bytes()
+    never = hip_free_bytes()
     e.set_feature_export(True)
-    assert _hip_free_bytes() < never                       # 2 x 3 x 64 x 96 x 128 x 4 B of features alone
+    assert hip_free_bytes() < never                       # 2 x 3 x 64 x 96 x 128 x 4 B of features alone
     e.set_feature_export(False)
-    assert _hip_free_bytes() == never
+    assert hip_free_bytes() == never
     _forward(e, inputs)
-    assert _hip_free_bytes() == never
+    assert hip_free_bytes() == never
     e.close()
 
 

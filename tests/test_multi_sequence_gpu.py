@@ -4,7 +4,6 @@ synthetic, and after a neighbour whose windows tripped the f16x3 range guard - w
 weights once and builds one communicator, and leaves no device memory behind.  The oracle is the checker only.
 
 The sequences are those of tests/test_multi_sequence.py: 13, 6, 3 and 22 frames of 64x96, each written from its own seed."""
-import ctypes
 import gc
 import json
 import os
@@ -16,7 +15,7 @@ from davo_amd import synth, parse_version, FLAGSHIP_VERSION
 from davo_amd import loader as L
 from davo_amd import sequence as S
 
-from helpers import assert_pose_close
+from helpers import assert_pose_close, hip_free_bytes
 
 pytestmark = pytest.mark.gpu
 H, W = 64, 96
@@ -159,20 +158,11 @@ def test_a_neighbour_that_trips_the_range_guard_does_not_leak_into_the_next_sequ
     assert file_of(tmp_path / "multi", 5) == file_of(tmp_path / "single", 5)
 
 
-def _hip_free_bytes():
-    """free device memory through hipMemGetInfo of the HIP runtime the library itself is linked against"""
-    path = next(line.split()[-1] for line in open("/proc/self/maps") if "libamdhip64" in line)
-    hip = ctypes.CDLL(path)
-    free, total = ctypes.c_size_t(0), ctypes.c_size_t(0)
-    assert hip.hipMemGetInfo(ctypes.byref(free), ctypes.byref(total)) == 0
-    return free.value
-
-
 def test_four_sequences_leave_no_more_device_memory_behind_than_one(world, tmp_path):
     common = ["--concat_img_dir", world["dump"], "--ckpt_file", world["ckpt"], "--batch_size", "4"]
     free = []
     for seqs in ("3", "3", LIST, "3"):                       # the first run also pays what the runtime keeps for the process
         run(common + ["--test_seq", seqs], tmp_path)
         gc.collect()
-        free.append(_hip_free_bytes())
+        free.append(hip_free_bytes())
     assert free[1] == free[2] == free[3], free

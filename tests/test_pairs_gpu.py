@@ -4,7 +4,6 @@ layer is a single K chain (fuse_pose 0, split_k 0: the property of test_batching
 pair-image counts), to 1e-6 of max|both| at the default options (the tolerance of the batch-position tests) - and against the
 float64 oracle and the project's restatements at the parity bar of tests/helpers.py.  The row of the pair that was not selected
 is exactly +0.0.  Frames are 64x96 (cnv2..cnv6 maps 16x24, cnv7 8x12) unless a test says otherwise; max_batch is 8."""
-import ctypes
 
 import numpy as np
 import pytest
@@ -17,7 +16,7 @@ import depth_source_ref as D
 import feature_attention_cases as FA
 import feature_attention_ref as F
 import layer_check as LC
-from helpers import assert_pose_close
+from helpers import assert_pose_close, hip_free_bytes
 
 pytestmark = pytest.mark.gpu
 
@@ -351,15 +350,6 @@ def test_one_pair_of_four_windows_runs_the_plan_of_both_pairs_of_two(precision):
     e.close()
 
 
-def _hip_free_bytes():
-    """free device memory through hipMemGetInfo of the HIP runtime the library itself is linked against"""
-    path = next(line.split()[-1] for line in open("/proc/self/maps") if "libamdhip64" in line)
-    hip = ctypes.CDLL(path)
-    free, total = ctypes.c_size_t(0), ctypes.c_size_t(0)
-    assert hip.hipMemGetInfo(ctypes.byref(free), ctypes.byref(total)) == 0
-    return free.value
-
-
 def test_create_set_pairs_stream_and_close_leaves_no_device_memory_behind():
     f = _flagship()
     inputs = _first(f["inputs"], 2)
@@ -376,7 +366,7 @@ def test_create_set_pairs_stream_and_close_leaves_no_device_memory_behind():
         e.synchronize()
         assert e.range_stats()["reissued"] >= 1
         e.close()
-        free.append(_hip_free_bytes())
+        free.append(hip_free_bytes())
     assert free[9] == free[0], free
 
 

@@ -59,6 +59,48 @@ def pairs_measurement(arms, rounds, n=30, H=128, W=416):
         e.close()
 
 
+def batch1_measurement(calls=3000, H=128, W=416):
+    """`--batch1`: host cost of the two host entry points at the reference's operating point, one window per call from
+    page-locked memory - us per davo_forward call (one slot) and us per davo_submit on four slots (delivery included), the best
+    of three passes of `calls` calls each, f16x3 and float32."""
+    from davo_amd import pinned_empty
+    cfg = parse_version(FLAGSHIP_VERSION)
+    host = synth.make_inputs(1, H, W)
+    pinned = tuple(pinned_empty(a.shape, a.dtype) for a in host)
+    for d, a in zip(pinned, host):
+        d[...] = a
+    e = Engine(cfg, H, W, 1)
+    e.load_weights(synth.make_weights(cfg))
+    outs = [np.empty((1, 2, 6), np.float32) for _ in range(calls)]
+    for prec in ("f16x3", "f32"):
+        e.set_precision(prec)
+        e.set_inflight(1)
+        for _ in range(200):
+            e.forward(*pinned)
+        best = float("inf")
+        for _ in range(3):
+            t0 = time.perf_counter()
+            for _ in range(calls):
+                e.forward(*pinned)
+            best = min(best, (time.perf_counter() - t0) / calls * 1e6)
+        print("host_b1 forward_%s_us %.2f" % (prec, best), flush=True)
+        e.set_inflight(4)
+        best = float("inf")
+        for rep in range(4):                                 # pass 0 warms up
+            t0 = time.perf_counter()
+            for o in outs:
+                e.submit(*pinned, o, hold=8)
+            e.synchronize()
+            if rep:
+                best = min(best, (time.perf_counter() - t0) / calls * 1e6)
+        print("host_b1 submit_%s_us %.2f" % (prec, best), flush=True)
+    e.close()
+
+
+if "--batch1" in sys.argv:
+    batch1_measurement()
+    sys.exit(0)
+
 if "--pairs" in sys.argv:
     import argparse
     ap = argparse.ArgumentParser()
