@@ -47,7 +47,7 @@ EXPORTS = (
     "davo_comm_preload", "davo_comm_unique_id", "davo_comm_init", "davo_comm_size", "davo_allgather_poses", "davo_allgather_poses_device",
     "davo_comm_allreduce", "davo_comm_barrier", "davo_comm_destroy", "davo_plan_layer", "davo_tile_filter_rows",
     "davo_set_pairs", "davo_get_pairs",
-    "davo_set_feature_export", "davo_forward_features",
+    "davo_set_feature_export", "davo_forward_features", "davo_set_heat_export", "davo_forward_heat",
     "davo_pad_class_tables", "davo_pad_class_tile_order", "davo_plan_layer_f32",
 )
 COMM_ID_BYTES = 128
@@ -61,6 +61,11 @@ class DavoVariant(ctypes.Structure):
 class DavoFeatureOut(ctypes.Structure):
     """davo_feature_out (include/davo_hip.h): host pointers, None = that output is neither computed nor copied."""
     _fields_ = [(n, ctypes.c_void_p) for n in ("att_19", "attention", "masked_image", "image", "feat_rot", "feat_trans")]
+
+
+class DavoHeatOut(ctypes.Structure):
+    """davo_heat_out (include/davo_hip.h): host pointers, None = that output is neither computed nor copied."""
+    _fields_ = [(n, ctypes.c_void_p) for n in ("rot_sum", "trans_sum", "rot_max", "trans_max")]
 
 
 def sources():
@@ -220,6 +225,8 @@ def _load():
     L.davo_get_pairs.argtypes = [vp]
     L.davo_set_feature_export.argtypes = [vp, i]
     L.davo_forward_features.argtypes = [vp, i, vp, vp, vp, vp, vp, ctypes.POINTER(DavoFeatureOut)]
+    L.davo_set_heat_export.argtypes = [vp, i]
+    L.davo_forward_heat.argtypes = [vp, i, vp, vp, vp, vp, vp, ctypes.POINTER(DavoFeatureOut), ctypes.POINTER(DavoHeatOut)]
     L.davo_debug_read.argtypes = [vp, ctypes.c_char_p, f32p, ctypes.c_size_t]
     L.davo_conv2d_same.argtypes = [i, f32p, i, i, i, i, f32p, i, i, f32p, i, i, i, i, f32p, ctypes.c_char_p, i]
     ip = ctypes.POINTER(i)

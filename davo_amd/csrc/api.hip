@@ -530,11 +530,73 @@ int export_features(davo_ctx* c, const Inputs& in, int w0, int nw, int b0, int B
     return DAVO_OK;
 }
 
+// ---- heat export: davo_set_heat_export / davo_forward_heat ------------------------------------------------------
+// What generate_feature_map.py:204-265 keeps of the two feature maps: per head and window the channel sum of the resized cnv6 and
+// the block's maximum, reduced where cnv6 lies (feature_export.h: feature_heat_cnv6, feature_resize_plane) into a block of the
+// context's own - 2 (H/4 W/4 + H W + 1) floats per window - and copied out piece by piece like the full export.
+struct HeatLayout { size_t plane, sum, max, total; };      // float offsets into the block for `cap' windows; head h at + h * cap * per-window
+HeatLayout heat_layout(const davo_ctx* c, int cap) {
+    const size_t HW = (size_t)c->H * c->W, HW2 = (size_t)c->H2 * c->W2, n = (size_t)cap;
+    HeatLayout l{};
+    l.plane = 0;                                       // first: written as float4, H W is a multiple of 16
+    l.sum = l.plane + 2 * n * HW;
+    l.max = l.sum + 2 * n * HW2;
+    l.total = l.max + 2 * n;
+    return l;
+}
+
+bool heat_wanted(const davo_heat_out* o) { return o && (o->rot_sum || o->trans_sum || o->rot_max || o->trans_max); }
+
+// export_features' contract for the heat members: windows [w0, w0 + nw) of the last forward -> windows [b0, b0 + nw) of the caller's
+int export_heat(davo_ctx* c, int w0, int nw, int b0, const davo_heat_out& out) {
+    if (!c->heat || c->heat->cap < 1) return fail(c, DAVO_ERR_INVALID, "internal: no heat export workspace");
+    float* const d = c->heat->d.get();
+    const int cap = c->heat->cap;
+    if (c->last_pairs != PAIRS_BOTH || w0 < 0 || w0 + nw > c->last_B) return fail(c, DAVO_ERR_INVALID, "internal: heat export of windows the last forward did not run");
+    const size_t HW = (size_t)c->H * c->W, HW2 = (size_t)c->H2 * c->W2;
+    const bool h3 = c->last_precision == 1;
+    const HeatLayout l = heat_layout(c, cap);
+    const Slot& ws = last_workspace(c);
+    hipStream_t s = last_stream(c);
+    const bool rot = out.rot_sum || out.rot_max, trans = out.trans_sum || out.trans_max;
+    for (int p0 = 0; p0 < nw; p0 += cap) {
+        const int np = std::min(cap, nw - p0);
+        float* const w_plane[2] = {out.rot_sum ? d + l.plane : nullptr, out.trans_sum ? d + l.plane + (size_t)cap * HW : nullptr};
+        float* const w_sum[2] = {rot ? d + l.sum : nullptr, trans ? d + l.sum + (size_t)cap * HW2 : nullptr};
+        float* const w_max[2] = {rot ? d + l.max : nullptr, trans ? d + l.max + cap : nullptr};
+        {
+            ProfScope ps(c, s, "feature_heat_cnv6");
+            HIP_TRY(c, launch_feature_heat(h3, ws.d_act[5].get(), w0 + p0, np, c->H2, c->W2, c->v.cnv6_out, h3 ? ldexpf(1.0f, -c->act_shift[5]) : 1.0f,
+                                           w_sum[0], w_sum[1], w_max[0], w_max[1], w_plane[0], w_plane[1], s));
+        }
+        c->heat->last_np = np;
+        const size_t first = (size_t)(b0 + p0);
+        if (out.rot_sum) HIP_TRY(c, hipMemcpyAsync(out.rot_sum + first * HW, w_plane[0], (size_t)np * HW * sizeof(float), hipMemcpyDeviceToHost, s));
+        if (out.trans_sum) HIP_TRY(c, hipMemcpyAsync(out.trans_sum + first * HW, w_plane[1], (size_t)np * HW * sizeof(float), hipMemcpyDeviceToHost, s));
+        if (out.rot_max) HIP_TRY(c, hipMemcpyAsync(out.rot_max + first, w_max[0], (size_t)np * sizeof(float), hipMemcpyDeviceToHost, s));
+        if (out.trans_max) HIP_TRY(c, hipMemcpyAsync(out.trans_max + first, w_max[1], (size_t)np * sizeof(float), hipMemcpyDeviceToHost, s));
+        HIP_TRY(c, hipStreamSynchronize(s));              // the next piece reuses the workspace
+    }
+    return DAVO_OK;
+}
+
+// what a davo_forward_features / davo_forward_heat call wants beside the poses; null = nothing of that kind
+struct Exports {
+    const davo_feature_out* fx = nullptr;
+    const davo_heat_out* heat = nullptr;
+    explicit operator bool() const { return fx || heat; }
+};
+int export_all(davo_ctx* c, const Exports& ex, const Inputs& in, int w0, int nw, int b0, int B) {
+    if (ex.fx) { int rc = export_features(c, in, w0, nw, b0, B, *ex.fx); if (rc) return rc; }
+    if (ex.heat) { int rc = export_heat(c, w0, nw, b0, *ex.heat); if (rc) return rc; }
+    return DAVO_OK;
+}
+
 }  // namespace
 
-// the body of davo_forward / davo_forward_depth (depth_form) and of davo_forward_features (fx: the exports wanted, else null)
+// the body of davo_forward / davo_forward_depth (depth_form) and of davo_forward_features / davo_forward_heat (ex: the exports wanted)
 static int forward_entry(davo_ctx* c, int B, const uint8_t* img, const float* flow, const float* seg, const float* depth_in, float* pose_out,
-                         bool depth_form, const davo_feature_out* fx = nullptr) {
+                         bool depth_form, const Exports ex = Exports{}) {
     if (!c) return DAVO_ERR_INVALID;
     if (!img || !flow || !seg || !pose_out) return fail(c, DAVO_ERR_INVALID, "null host pointer");
     const void* depth = depth_in;
@@ -599,10 +661,10 @@ static int forward_entry(davo_ctx* c, int B, const uint8_t* img, const float* fl
         f32_fallback |= res.f32_fallback;
         // feature export: the context holds one sub-batch's activations, so every sub-batch but the last is exported before the next
         // one runs; the last one waits for the verdict below
-        if (fx && i < nchunks - 1 && (rc = export_features(c, from_window(c, hs.set.view(), b0), 0, nb, b0, B, *fx))) return rc;
+        if (ex && i < nchunks - 1 && (rc = export_all(c, ex, from_window(c, hs.set.view(), b0), 0, nb, b0, B))) return rc;
     }
     const int last_b0 = (nchunks - 1) * chunk;
-    auto export_last = [&]() { return fx ? export_features(c, from_window(c, hs.set.view(), last_b0), 0, B - last_b0, last_b0, B, *fx) : DAVO_OK; };
+    auto export_last = [&]() { return !ex ? DAVO_OK : export_all(c, ex, from_window(c, hs.set.view(), last_b0), 0, B - last_b0, last_b0, B); };
     if (f32_fallback) ++c->n_f32_batches;                      // once per call, not per sub-batch
     HIP_TRY(c, hipMemcpyAsync(hs.h_pose.get(), hs.d_pose.get(), (size_t)B * 12 * sizeof(float), hipMemcpyDeviceToHost, run.stream));
     HIP_TRY(c, hipStreamSynchronize(run.stream));
@@ -622,7 +684,7 @@ static int forward_entry(davo_ctx* c, int B, const uint8_t* img, const float* fl
         if (rc == DAVO_OK) HIP_TRY(c, hipMemcpy(pose_out, hs.d_pose.get(), (size_t)B * 12 * sizeof(float), hipMemcpyDeviceToHost));
         // the re-issue ran the whole batch as one forward and produced the poses returned: every window's exports come from it, in
         // the precision and under the scales it ran with (what the sub-batches exported above is overwritten)
-        if (rc == DAVO_OK && fx) rc = export_features(c, hs.set.view(), 0, B, 0, B, *fx);
+        if (rc == DAVO_OK && ex) rc = export_all(c, ex, hs.set.view(), 0, B, 0, B);
         return rc;
     }
     return rc == DAVO_OK ? export_last() : rc;
@@ -658,7 +720,33 @@ int davo_forward_features(davo_ctx* c, int B, const uint8_t* img, const float* f
     if (c->pairs != PAIRS_BOTH)
         return fail(c, DAVO_ERR_INVALID, "davo_forward_features runs both pairs of every window, the reference's semantics (davo.py:1456-1457): "
                     "davo_set_pairs(ctx, DAVO_PAIRS_BOTH) first (the selection is %d)", c->pairs);
-    return forward_entry(c, B, img, flow, seg, depth, pose_out, true, fx_wanted(out) ? out : nullptr);
+    return forward_entry(c, B, img, flow, seg, depth, pose_out, true, Exports{fx_wanted(out) ? out : nullptr, nullptr});
+}
+
+int davo_set_heat_export(davo_ctx* c, int on) {
+    if (!c) return DAVO_ERR_INVALID;
+    HIP_TRY(c, hipSetDevice(c->device));
+    { int rc = sync_all_slots(c); if (rc) return rc; }
+    if (!on) { c->heat.reset(); return DAVO_OK; }
+    if (!c->heat) {
+        HeatBlock h;
+        h.cap = c->host_chunk > 0 ? std::min(c->max_batch, 2 * c->host_chunk - 1) : c->max_batch;      // davo_forward's largest sub-batch
+        HIP_TRY(c, dev_alloc(&h.d, heat_layout(c, h.cap).total));
+        c->heat = std::move(h);
+    }
+    return DAVO_OK;
+}
+
+int davo_forward_heat(davo_ctx* c, int B, const uint8_t* img, const float* flow, const float* seg, const float* depth, float* pose_out,
+                      const davo_feature_out* out, const davo_heat_out* heat) {
+    if (!c) return DAVO_ERR_INVALID;
+    const bool want_fx = fx_wanted(out), want_heat = heat_wanted(heat);
+    if (want_fx && !c->fx_on) return fail(c, DAVO_ERR_NOT_READY, "davo_forward_heat: a member of `out' is wanted and the feature export is off - call davo_set_feature_export(ctx, 1) first");
+    if (want_heat && !c->heat) return fail(c, DAVO_ERR_NOT_READY, "davo_forward_heat: a member of `heat' is wanted and the heat export is off - call davo_set_heat_export(ctx, 1) first");
+    if (c->pairs != PAIRS_BOTH)
+        return fail(c, DAVO_ERR_INVALID, "davo_forward_heat runs both pairs of every window, the reference's semantics (davo.py:1456-1457): "
+                    "davo_set_pairs(ctx, DAVO_PAIRS_BOTH) first (the selection is %d)", c->pairs);
+    return forward_entry(c, B, img, flow, seg, depth, pose_out, true, Exports{want_fx ? out : nullptr, want_heat ? heat : nullptr});
 }
 
 int davo_range_stats(davo_ctx* c, long long* recalibrations, long long* f32_batches, long long* reissued) {
@@ -1000,6 +1088,17 @@ int davo_debug_read(davo_ctx* c, const char* tensor, float* host_out, size_t n_f
         const char* names[7] = {"cnv1", "cnv2", "cnv3", "cnv4", "cnv5", "cnv6", "cnv7"};
         for (int i = 0; i < 7; ++i)
             if (t == names[i]) { src = ws.d_act[i].get(); n = NB * c->act_floats_per_img[i]; }
+    }
+    if (t == "heat_sum") {            // the heat export's channel sums of the piece it exported last: [2][np][H2][W2], rotation | translation
+        if (!c->heat || c->heat->last_np < 1) return fail(c, DAVO_ERR_NOT_READY, "`heat_sum' exists after a davo_forward_heat with the heat export on");
+        const size_t per = (size_t)c->H2 * c->W2, np = (size_t)c->heat->last_np;
+        if (n_floats != 2 * np * per) return fail(c, DAVO_ERR_INVALID, "`heat_sum' holds %zu floats, caller asked for %zu", 2 * np * per, n_floats);
+        const size_t at = (size_t)2 * c->heat->cap * c->H * c->W;
+        for (int h = 0; h < 2; ++h) {
+            int rc = davo_memcpy_d2h(c, host_out + h * np * per, c->heat->d.get() + at + (size_t)h * c->heat->cap * per, np * per * sizeof(float));
+            if (rc) return rc;
+        }
+        return DAVO_OK;
     }
     if (t == "pose_tiles") {          // the fused pose head's per-tile partial sums of the last batch (slot 0's region)
         if (c->cnv7_valid || !c->d_pose_tiles.get()) return fail(c, DAVO_ERR_NOT_READY, "the pose head did not run fused");

@@ -173,6 +173,13 @@ struct FxBlock {
     DevMem<float> d;
     int cap = 0;
 };
+// the heat export's device block (davo_set_heat_export): for `cap' windows and both heads the resized sum planes [2][cap][H][W], the
+// channel sums they are resized from [2][cap][H/4][W/4] and the maxima [2][cap]; last_np = windows of the piece it holds
+struct HeatBlock {
+    DevMem<float> d;
+    int cap = 0;
+    int last_np = 0;
+};
 
 struct Comm;                                     // comm.hip: RCCL communicator state
 
@@ -271,6 +278,8 @@ struct davo_ctx {
     // export tensor, absent with the export off
     bool fx_on = false;
     std::optional<davo::FxBlock> fx;
+    // heat export (davo_set_heat_export / davo_forward_heat, api.hip): a block of its own, absent with the export off
+    std::optional<davo::HeatBlock> heat;
     // streaming host entry (davo_submit / davo_wait): staging input sets, pose ring, undelivered batches in issue order
     davo::InputSet stream_sets[davo::MAX_INFLIGHT];     // one staging set per in-flight slot (built by the slot's first davo_submit)
     std::optional<davo::PoseRing> pose_ring;   // built by the first davo_submit

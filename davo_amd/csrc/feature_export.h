@@ -6,6 +6,9 @@
 //                        1468), the masked rgb (davo.py:1419-1421,1447-1449,1471-1475), the plain preprocessed rgb
 //                        (davo.py:967-971, 1519-1522), and the 19-entry rows the maps are gathers of
 //   feature_resize_cnv6  tf.image.resize_bilinear(cnv6 of the tgt->src1 call, (H, W)) of each head (davo.py:1457,1463-1465)
+// and behind davo_forward_heat, what generate_feature_map.py:204-265 reduces those maps to, computed where cnv6 lies:
+//   feature_heat_cnv6    per head and window the channel sum of the stored cnv6 [H/4][W/4] and the maximum of the whole block
+//   feature_resize_plane the same resize of that one-channel sum plane to [H][W]
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -99,8 +102,8 @@ struct ResizeParams {
 };
 
 // four channels of one input pixel, decoded with davo_debug_read's expression (api.hip): (float)hi + (float)lo, times 2^-shift
-template <bool H3>
-__device__ __forceinline__ void resize_load4(const ResizeParams& p, size_t pixel, int ch, float v[4]) {
+template <bool H3, class Params>
+__device__ __forceinline__ void resize_load4(const Params& p, size_t pixel, int ch, float v[4]) {
 #pragma clang fp contract(off)
     if (H3) {
         const uint8_t* q = p.x + pixel * ((size_t)p.c6 * 8) + (size_t)(ch >> 5) * 128 + (size_t)(ch & 31) * 2;
@@ -155,6 +158,104 @@ __global__ __launch_bounds__(256) void feature_resize_cnv6(ResizeParams p) {
     for (int r = 0; r < 4; ++r) {
         const float yl = (float)r * 0.25f;
         *reinterpret_cast<float4*>(o + r * row) = make_float4(top[0] + dv[0] * yl, top[1] + dv[1] * yl, top[2] + dv[2] * yl, top[3] + dv[3] * yl);
+    }
+}
+
+// ---- the heat export: channel sum and maximum of cnv6, reduced on the device (davo_forward_heat) ------------------------------
+// generate_feature_map.py:204-265 keeps of resize_bilinear(cnv6) only np.sum / np.mean over the channels and the block's maximum.
+// The resize is linear, so the channel sum of the resized map is the resize of the channel sum; every stored value reappears at
+// out[4i][4j] and every other output lies between its corners, so the maximum of the resized map is the maximum of the stored one.
+struct HeatParams {
+    const uint8_t* x;            // cnv6 as ResizeParams::x
+    float* sum[2];               // rotation, translation: [nw][H2][W2] float32 of the piece; null = head not wanted
+    unsigned* max[2];            // [nw] words, zeroed before the launch: the bit pattern of the head's largest value (cnv6 is post-ReLU)
+    int w0, nw;                  // as ResizeParams
+    int H2, W2, c6, cq_log2;
+    int head0;
+    float unscale;
+};
+
+// Lanes run along the channel quads of consecutive pixels: a lane adds its four channels as (c0 + c1) + (c2 + c3), then the cq
+// lanes of a pixel add along a butterfly (lane ^ 1, ^ 2, ...): float32 addition commutes, so both partners hold the same bits and
+// the sum is one fixed tree, 2 + log2(cq) <= 8 roundings deep, whatever the launch.  The maximum rides the same butterfly; where a
+// wave lies inside one window it goes on to the wave's 64 lanes and one lane raises the window's word, else one lane per pixel does.
+// Values that are not above zero (cnv6 is post-ReLU: zeros of either sign) count as +0, so the unsigned order is the float order.
+// grid (ceil(nw H2 W2 cq / 256), heads wanted).
+template <bool H3>
+__global__ __launch_bounds__(256) void feature_heat_cnv6(HeatParams p) {
+#pragma clang fp contract(off)
+    const long g = (long)blockIdx.x * 256 + threadIdx.x;
+    const int ncq = 1 << p.cq_log2;
+    const int cq = (int)(g & (ncq - 1));
+    const long HW2 = (long)p.H2 * p.W2, npix = (long)p.nw * HW2;
+    const long pix = g >> p.cq_log2;
+    const bool live = pix < npix;
+    const long pc = live ? pix : npix - 1;             // a lane past the end repeats the last pixel: it takes part in the butterfly
+    const int b = (int)(pc / HW2);
+    const int head = p.head0 + blockIdx.y;
+    const size_t n = 2 * (size_t)(p.w0 + b) + 1;
+    float v[4];
+    resize_load4<H3>(p, n * (size_t)HW2 + (size_t)(pc - (long)b * HW2), head * p.c6 + 4 * cq, v);
+    float s = (v[0] + v[1]) + (v[2] + v[3]);
+    float m = 0.0f;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) m = v[k] > m ? v[k] : m;
+    for (int d = 1; d < ncq; d <<= 1) {
+        s += __shfl_xor(s, d);
+        const float o = __shfl_xor(m, d);
+        m = o > m ? o : m;
+    }
+    if (live && cq == 0) p.sum[head][pix] = s;
+    const bool one_window = __shfl(b, 0) == __shfl(b, 63);
+    if (one_window) {
+        for (int d = ncq; d < 64; d <<= 1) {
+            const float o = __shfl_xor(m, d);
+            m = o > m ? o : m;
+        }
+        if ((threadIdx.x & 63) == 0 && m > 0.0f) atomicMax(p.max[head] + b, __float_as_uint(m));
+    } else if (live && cq == 0 && m > 0.0f) {
+        atomicMax(p.max[head] + b, __float_as_uint(m));
+    }
+}
+
+struct PlaneParams {
+    const float* sum[2];         // [nw][H2][W2], feature_heat_cnv6's
+    float* out[2];               // [nw][4 H2][4 W2]; null = head not wanted
+    int nw, H2, W2;
+    int head0;
+};
+
+// feature_resize_cnv6's index rule and float32 order on the one-channel plane: a thread takes one input pixel's 4 x 4 outputs - the
+// four corners once, the four horizontal lerps once, then four rows of one float4 each; lanes run along the input row, so a wave's
+// store is contiguous.  out[4i][4j] is sum[i][j] to the bit (both lerp weights are 0).  grid (ceil(nw H2 W2 / 256), heads wanted).
+__global__ __launch_bounds__(256) void feature_resize_plane(PlaneParams p) {
+#pragma clang fp contract(off)
+    const long g = (long)blockIdx.x * 256 + threadIdx.x;
+    const long HW2 = (long)p.H2 * p.W2;
+    if (g >= (long)p.nw * HW2) return;
+    const int ix = (int)(g % p.W2);
+    long t = g / p.W2;
+    const int iy = (int)(t % p.H2);
+    const long b = t / p.H2;
+    const int head = p.head0 + blockIdx.y;
+    const int ix1 = min(ix + 1, p.W2 - 1), iy1 = min(iy + 1, p.H2 - 1);
+    const float* src = p.sum[head] + b * HW2;
+    const float tl = src[(long)iy * p.W2 + ix], tr = src[(long)iy * p.W2 + ix1];
+    const float bl = src[(long)iy1 * p.W2 + ix], br = src[(long)iy1 * p.W2 + ix1];
+    float top[4], dv[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const float xl = (float)k * 0.25f;
+        top[k] = tl + (tr - tl) * xl;
+        const float bot = bl + (br - bl) * xl;
+        dv[k] = bot - top[k];
+    }
+    const size_t W = 4 * (size_t)p.W2, H = 4 * (size_t)p.H2;
+    float* o = p.out[head] + (((size_t)b * H + 4 * (size_t)iy) * W + 4 * (size_t)ix);
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        const float yl = (float)r * 0.25f;
+        *reinterpret_cast<float4*>(o + r * W) = make_float4(top[0] + dv[0] * yl, top[1] + dv[1] * yl, top[2] + dv[2] * yl, top[3] + dv[3] * yl);
     }
 }
 

@@ -95,5 +95,11 @@ hipError_t launch_feature_maps(const uint8_t* d_img, const float* d_seg, const f
 // [w0, w0 + nw) of it -> d_rot / d_trans [nw][4 H2][4 W2][c6]; a null head is not computed
 hipError_t launch_feature_resize_cnv6(bool h3, const void* d_cnv6, int w0, int nw, int H2, int W2, int c6, float unscale,
                                       float* d_rot, float* d_trans, hipStream_t s);
+// the heat export (davo_forward_heat) of the same windows: per head the channel sum of the stored cnv6 -> d_sum_* [nw][H2][W2], the
+// block's maximum -> d_max_* [nw] (zeroed here, then raised as bit patterns), and the resize of the sum -> d_plane_* [nw][4 H2][4 W2].
+// A head is computed when its sum and max are given; its plane may be null (the maximum alone is wanted)
+hipError_t launch_feature_heat(bool h3, const void* d_cnv6, int w0, int nw, int H2, int W2, int c6, float unscale,
+                               float* d_sum_rot, float* d_sum_trans, float* d_max_rot, float* d_max_trans,
+                               float* d_plane_rot, float* d_plane_trans, hipStream_t s);
 
 }  // namespace davo

@@ -33,4 +33,37 @@ hipError_t launch_feature_resize_cnv6(bool h3, const void* d_cnv6, int w0, int n
     return hipGetLastError();
 }
 
+hipError_t launch_feature_heat(bool h3, const void* d_cnv6, int w0, int nw, int H2, int W2, int c6, float unscale,
+                               float* d_sum_rot, float* d_sum_trans, float* d_max_rot, float* d_max_trans,
+                               float* d_plane_rot, float* d_plane_trans, hipStream_t s) {
+    int cq_log2 = 0;
+    while ((4 << cq_log2) < c6) ++cq_log2;
+    if (nw < 1 || w0 < 0 || H2 < 1 || W2 < 1 || c6 < 32 || c6 > 256 || (4 << cq_log2) != c6 || !d_cnv6) return hipErrorInvalidValue;
+    const bool rot = d_sum_rot && d_max_rot, trans = d_sum_trans && d_max_trans;
+    if ((d_plane_rot && !rot) || (d_plane_trans && !trans)) return hipErrorInvalidValue;
+    if (!rot && !trans) return hipSuccess;
+    HeatParams p{};
+    p.x = static_cast<const uint8_t*>(d_cnv6);
+    p.sum[0] = rot ? d_sum_rot : nullptr; p.sum[1] = trans ? d_sum_trans : nullptr;
+    p.max[0] = rot ? reinterpret_cast<unsigned*>(d_max_rot) : nullptr; p.max[1] = trans ? reinterpret_cast<unsigned*>(d_max_trans) : nullptr;
+    p.w0 = w0; p.nw = nw; p.H2 = H2; p.W2 = W2; p.c6 = c6; p.cq_log2 = cq_log2;
+    p.head0 = rot ? 0 : 1;
+    p.unscale = unscale;
+    for (int h = 0; h < 2; ++h)
+        if (p.max[h]) { hipError_t e = hipMemsetAsync(p.max[h], 0, (size_t)nw * sizeof(unsigned), s); if (e != hipSuccess) return e; }
+    const long npix = (long)nw * H2 * W2;
+    const dim3 grid((unsigned)(((npix << cq_log2) + 255) / 256), (rot && trans) ? 2 : 1);
+    if (h3) hipLaunchKernelGGL(feature_heat_cnv6<true>, grid, dim3(256), 0, s, p);
+    else hipLaunchKernelGGL(feature_heat_cnv6<false>, grid, dim3(256), 0, s, p);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess || (!d_plane_rot && !d_plane_trans)) return e;
+    PlaneParams q{};
+    q.sum[0] = d_sum_rot; q.sum[1] = d_sum_trans;
+    q.out[0] = d_plane_rot; q.out[1] = d_plane_trans;
+    q.nw = nw; q.H2 = H2; q.W2 = W2;
+    q.head0 = d_plane_rot ? 0 : 1;
+    hipLaunchKernelGGL(feature_resize_plane, dim3((unsigned)((npix + 255) / 256), (d_plane_rot && d_plane_trans) ? 2 : 1), dim3(256), 0, s, q);
+    return hipGetLastError();
+}
+
 }  // namespace davo

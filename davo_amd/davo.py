@@ -12,7 +12,7 @@ import ctypes
 import numpy as np
 
 from . import _lib
-from .version import parse_version, weight_shapes
+from .version import ATT_SOURCE, NUM_SEG_CLASSES, parse_version, weight_shapes
 
 
 class DavoError(RuntimeError):
@@ -101,6 +101,7 @@ class Engine:
         self.cfg, self.H, self.W, self.max_batch, self.device = cfg, img_height, img_width, max_batch, device
         self._L = _lib.lib()
         self._ctx = ctypes.c_void_p()
+        self.host_chunk = 8                       # davo_set_option "host_chunk" as last set through set_option (its default)
         v = _lib.DavoVariant(*cfg.as_c_ints())
         rc = self._L.davo_create(ctypes.byref(self._ctx), device, img_height, img_width, max_batch, ctypes.byref(v))
         if rc != 0:
@@ -172,13 +173,22 @@ class Engine:
         """Allocate (or free) the workspace of forward_features (include/davo_hip.h: davo_set_feature_export); off by default."""
         self._check(self._L.davo_set_feature_export(self._ctx, int(bool(on))))
 
+    HEAT_OUTPUTS = ("heat_rot", "heat_trans", "max_rot", "max_trans")
+
+    def set_heat_export(self, on=True):
+        """Allocate (or free) the workspace of forward_features' heat outputs (include/davo_hip.h: davo_set_heat_export); off by
+        default, independent of set_feature_export."""
+        self._check(self._L.davo_set_heat_export(self._ctx, int(bool(on))))
+
     def forward_features(self, img, flow, seg, depth=None, want=FEATURE_OUTPUTS):
         """forward() plus the tensors of the reference's mode='feature' fetches from the same forward (include/davo_hip.h:
         davo_forward_features; needs set_feature_export() and the 'both' pair selection).  -> {'pose': [B,2,6]} and, for each
         name in ``want``: 'att_19' [3,B,19], 'attention' [3,B,H,W], 'masked_image' and 'image' [3,B,H,W,3] - frames in the
         order tgt, src0, src1 - 'feat_rot' and 'feat_trans' [B,H,W,cnv6_out]; all float32.  An output that is not wanted is
-        neither computed nor copied."""
-        unknown = [w for w in want if w not in self.FEATURE_OUTPUTS]
+        neither computed nor copied.
+        ``want`` may also name HEAT_OUTPUTS (davo_forward_heat; needs set_heat_export()): 'heat_rot' / 'heat_trans' [B,H,W], the
+        channel sum of feat_rot / feat_trans reduced on the device, and 'max_rot' / 'max_trans' [B], their maxima."""
+        unknown = [w for w in want if w not in self.FEATURE_OUTPUTS and w not in self.HEAT_OUTPUTS]
         if unknown:
             raise ValueError("unknown feature output(s) %s: choose from %s" % (unknown, list(self.FEATURE_OUTPUTS)))
         img = np.ascontiguousarray(img, np.uint8)
@@ -188,16 +198,21 @@ class Engine:
         depth = self._depth_arg(depth, B)
         H, W, c6 = self.H, self.W, self.cfg.cnv6_out
         shapes = {"att_19": (3, B, 19), "attention": (3, B, H, W), "masked_image": (3, B, H, W, 3), "image": (3, B, H, W, 3),
-                  "feat_rot": (B, H, W, c6), "feat_trans": (B, H, W, c6)}
+                  "feat_rot": (B, H, W, c6), "feat_trans": (B, H, W, c6),
+                  "heat_rot": (B, H, W), "heat_trans": (B, H, W), "max_rot": (B,), "max_trans": (B,)}
         res = {"pose": np.empty((B, 2, 6), np.float32)}
-        for name in self.FEATURE_OUTPUTS:
+        for name in self.FEATURE_OUTPUTS + self.HEAT_OUTPUTS:
             if name in want:
                 res[name] = np.empty(shapes[name], np.float32)
         vp = ctypes.c_void_p
         out = _lib.DavoFeatureOut(*[res[n].ctypes.data if n in res else None for n in self.FEATURE_OUTPUTS])
-        self._check(self._L.davo_forward_features(self._ctx, B, img.ctypes.data_as(vp), flow.ctypes.data_as(vp), seg.ctypes.data_as(vp),
-                                                  depth.ctypes.data_as(vp) if depth is not None else None,
-                                                  res["pose"].ctypes.data_as(vp), ctypes.byref(out)))
+        args = (self._ctx, B, img.ctypes.data_as(vp), flow.ctypes.data_as(vp), seg.ctypes.data_as(vp),
+                depth.ctypes.data_as(vp) if depth is not None else None, res["pose"].ctypes.data_as(vp), ctypes.byref(out))
+        if any(n in res for n in self.HEAT_OUTPUTS):
+            heat = _lib.DavoHeatOut(*[res[n].ctypes.data if n in res else None for n in self.HEAT_OUTPUTS])
+            self._check(self._L.davo_forward_heat(*(args + (ctypes.byref(heat),))))
+        else:
+            self._check(self._L.davo_forward_features(*args))
         return res
 
     def _check_batch(self, img, flow, seg):
@@ -323,6 +338,8 @@ class Engine:
         """'auto_range' (default 1), 'fuse_pose' (default 1), 'fuse_pack' (default 0), 'host_chunk' (default 8), ...:
         see include/davo_hip.h."""
         self._check(self._L.davo_set_option(self._ctx, key.encode(), int(value)))
+        if key == "host_chunk":
+            self.host_chunk = int(value)
 
     def set_inflight(self, n):
         """Batches kept in flight by forward_device (1..4): n streams + n workspaces, rotated per call."""
@@ -434,6 +451,34 @@ def seg_one_hot(seg):
     return ((idx[..., None] == np.arange(19, dtype=np.int32)) & ok[..., None]).astype(np.float32)
 
 
+def host_maps(cfg, img, seg, tables):
+    """The four map outputs of Engine.forward_features - 'att_19' [3,B,19], 'attention' [3,B,H,W], 'masked_image' and 'image'
+    [3,B,H,W,3], frames tgt, src0, src1 - rebuilt on the host from a batch's inputs and the class tables its forward computed
+    (Engine.debug_read("att_table"), [B,3,19]), in the kernels' float32 expressions (csrc/feature_export.h: feature_maps), so to
+    the bit what the device exports.  DAVO's features='heat' mode uses it: the device-side maps live in the full export's
+    workspace, which that mode never allocates."""
+    img = np.asarray(img, np.uint8)
+    seg = np.asarray(seg, np.float32)
+    tables = np.asarray(tables, np.float32)
+    B, H, W3, _ = img.shape
+    W = W3 // 3
+    unit = (img.astype(np.float32) * np.float32(1.0 / 255.0)) * np.float32(2.0) - np.float32(1.0)      # davo.py:1521-1522
+    a19 = np.ones((3, B, NUM_SEG_CLASSES), np.float32)
+    att = np.ones((3, B, H, W), np.float32)
+    image = np.empty((3, B, H, W, 3), np.float32)
+    for f, plane in enumerate((1, 0, 2)):                      # (tgt, src0, src1) -> strip slot / label plane src0, tgt, src1
+        image[f] = unit[:, :, plane * W:(plane + 1) * W]
+        if cfg.tgt_attended if f == 0 else ATT_SOURCE[cfg.att_source] != 0:       # else the reference's tf.ones_like override
+            a19[f] = tables[:, f]
+            lab = seg[:, plane, :, :, 0]
+            with np.errstate(invalid="ignore"):
+                ok = np.isfinite(lab) & (lab > -1.0) & (lab < float(NUM_SEG_CLASSES))
+            idx = np.where(ok, lab, 0.0).astype(np.int64).reshape(B, -1)
+            att[f] = np.where(ok, np.take_along_axis(a19[f], idx, axis=1).reshape(B, H, W), np.float32(0.0))
+    masked = image * att[..., None] if cfg.mask_rgb else image.copy()
+    return {"att_19": a19, "attention": att, "masked_image": masked, "image": image}
+
+
 class DAVO(object):
     """Drop-in for the reference class on the inference path (reference davo.py:30)."""
 
@@ -444,14 +489,27 @@ class DAVO(object):
         self.engine = None
         self._weights = None
         self._feature_mode = False
+        self._features = 'full'
 
-    def enable_feature_mode(self):
-        """Opt in to ``inference(mode='feature')``: allocates the library's export workspace (include/davo_hip.h:
-        davo_set_feature_export) - now if ``setup_inference`` has run, else when it does.  Returns self."""
+    def enable_feature_mode(self, features='full'):
+        """Opt in to ``inference(mode='feature')``: allocates the library's export workspace - now if ``setup_inference`` has
+        run, else when it does.  Returns self.
+        features='full' (include/davo_hip.h: davo_set_feature_export): 'features' holds the two resized cnv6 maps.
+        features='heat' (davo_set_heat_export alone; the maps' workspace is never allocated): 'features' holds what
+        generate_feature_map.py:204-265 reduces the maps to, computed on the device - see ``inference``."""
+        if features not in ('full', 'heat'):
+            raise ValueError("features must be 'full' or 'heat', got %r" % (features,))
         self._feature_mode = True
+        self._features = features
         if self.engine is not None:
-            self.engine.set_feature_export(True)
+            self._switch_exports()
         return self
+
+    def _switch_exports(self):
+        if self._features == 'heat':
+            self.engine.set_heat_export(True)
+        else:
+            self.engine.set_feature_export(True)
 
     def setup_inference(self, img_height, img_width, mode, seq_length=3, batch_size=1,
                         input_img_uint8=None, input_pose=None, input_flow=None, input_depth=None,
@@ -472,7 +530,7 @@ class DAVO(object):
         if self._weights is not None:
             self.engine.load_weights(self._weights)
         if self._feature_mode:
-            self.engine.set_feature_export(True)
+            self._switch_exports()
         self._ahead = []                                   # iterator inputs: batches submitted and not returned yet
         if input_img_uint8 is not None and not isinstance(input_img_uint8, np.ndarray) and input_flow is None:
             self._inputs = iter(input_img_uint8)
@@ -506,7 +564,10 @@ class DAVO(object):
           'masks'     {'attention': 3 x [B,H,W,1], the maps multiplied in (after the tf.ones_like overrides);
                        'image': 3 x [B,H,W,3], the frames' rgb after masking (the plain rgb where the version masks none);
                        'att_19': 3 x [B,1,1,19], att_19[f][b,0,0,c] = the value frame f's map takes on class c};
-          'features'  {'rot', 'trans'}: [B,H,W,cnv6_out], resize_bilinear of the tgt->src1 call's cnv6 heads;
+          'features'  {'rot', 'trans'}: [B,H,W,cnv6_out], resize_bilinear of the tgt->src1 call's cnv6 heads; after
+                      ``enable_feature_mode(features='heat')`` instead {'rot_sum', 'trans_sum'}: [B,H,W], the maps' sum over
+                      the channels; {'rot_avg', 'trans_avg'}: [B,H,W] = sum * (1 / cnv6_out), exact; {'rot_max', 'trans_max'}:
+                      [B], the maps' maxima (generate_feature_map.py:249-263 draws these);
           'images'    3 x [B,H,W,3] preprocessed, unmasked;
           'seg_19'    3 x [B,H,W,19] one-hot label maps (built on the host, seg_one_hot).
         Deviations from the reference: 'att_19' is defined for every variant, and a frame whose map the reference overrides
@@ -538,15 +599,44 @@ class DAVO(object):
         img, flow, seg, depth = self._split(inputs if inputs is not None else self._inputs)
         if img is None or flow is None or seg is None:
             raise ValueError("image, flow and seglabel inputs are all required for version `%s'" % self.version)
-        r = self.engine.forward_features(img, flow, seg, depth)
+        heat = self._features == 'heat'
+        r = self._forward_heat(img, flow, seg, depth) if heat else self.engine.forward_features(img, flow, seg, depth)
+        if heat:
+            inv = np.float32(1.0 / self.cfg.cnv6_out)          # a power of two: the mean is exact
+            features = {'rot_sum': r['heat_rot'], 'trans_sum': r['heat_trans'], 'rot_avg': r['heat_rot'] * inv,
+                        'trans_avg': r['heat_trans'] * inv, 'rot_max': r['max_rot'], 'trans_max': r['max_trans']}
+        else:
+            features = {'rot': r['feat_rot'], 'trans': r['feat_trans']}
         one_hot = seg_one_hot(seg)                             # [B,3,H,W,19], file order src0, tgt, src1 (davo.py:998-1004)
         return {'pose': r['pose'],
                 'masks': {'attention': [r['attention'][f][..., None] for f in range(3)],
                           'image': [r['masked_image'][f] for f in range(3)],
                           'att_19': [r['att_19'][f][:, None, None, :] for f in range(3)]},
-                'features': {'rot': r['feat_rot'], 'trans': r['feat_trans']},
+                'features': features,
                 'images': [r['image'][f] for f in range(3)],
                 'seg_19': [one_hot[:, plane] for plane in (1, 0, 2)]}
+
+    def _forward_heat(self, img, flow, seg, depth):
+        """Engine.forward_features' dict with the heat outputs in place of the two feature maps.  The device delivers the poses,
+        planes and maxima (davo_forward_heat); the four maps are rebuilt by ``host_maps`` from the class tables of the forward,
+        which the context holds for one sub-batch: a batch that davo_forward would split (2 x host_chunk windows or more) is
+        issued here as those sub-batches, one call each - the same forwards, so the same poses (a range recovery then re-issues
+        a sub-batch, not the batch)."""
+        e = self.engine
+        img, flow, seg = np.asarray(img), np.asarray(flow), np.asarray(seg)
+        depth = None if depth is None else np.asarray(depth)
+        B = img.shape[0]
+        step = e.host_chunk if e.host_chunk > 0 and B >= 2 * e.host_chunk else B
+        parts = []
+        for b0 in range(0, B, step):
+            part = [None if a is None else a[b0:b0 + step] for a in (img, flow, seg, depth)]
+            r = e.forward_features(*part, want=Engine.HEAT_OUTPUTS)
+            r.update(host_maps(self.cfg, part[0], part[2], e.debug_read("att_table", (len(part[0]), 3, NUM_SEG_CLASSES))))
+            parts.append(r)
+        if len(parts) == 1:
+            return parts[0]
+        frame_major = ("att_19", "attention", "masked_image", "image")
+        return {k: np.concatenate([p[k] for p in parts], axis=1 if k in frame_major else 0) for k in parts[0]}
 
     def _split(self, inputs):
         """(img, flow, seg) or, for a depth-source variant, (img, flow, seg, depth) -> the four, depth None without it."""

@@ -241,6 +241,43 @@ typedef struct {
 int davo_forward_features(davo_ctx* ctx, int B, const uint8_t* img, const float* flow, const float* seg,
                           const float* depth, float* pose_out, const davo_feature_out* out);
 
+/* Heat export.  The reference's only reader of feat_rot / feat_trans is generate_feature_map.py:204-265, which reduces each map at
+ * once to np.sum(axis=-1), np.mean(axis=-1) and the scalar max() that normalises the mean image, and draws those: two [H,W] planes
+ * and two scalars per window (426 KB at 128x416) where the full maps are 54.5 MB.  davo_forward_heat delivers exactly that, reduced on
+ * the device where cnv6 lies, at [H/4, W/4], reading it once; the full maps exist on neither side of the bus.  Two identities:
+ *   - sum o resize = resize o sum: the resize is linear with weights that do not depend on the channel, so the channel sum of
+ *     resize_bilinear(cnv6) is resize_bilinear of the channel sum;
+ *   - max of the resized map = max of the stored map: at the library's one scale (lo = out >> 2, lerp (out & 3) / 4) every stored
+ *     value reappears unchanged at out[4i][4j], and every other output is an interpolation between corners that does not leave
+ *     their range - in float32 and TF's order too.
+ *   rot_sum, trans_sum  [B][H][W]  resize_bilinear (feat_rot's rule and float32 order: top = tl + (tr - tl) xl, bot likewise,
+ *                                  out = top + (bot - top) yl) of the float32 sum over the head's cnv6_out channels of the stored cnv6
+ *                                  of the tgt->src1 call, each value decoded as davo_debug_read("cnv6") decodes it.  The sum is one
+ *                                  fixed tree, (c0 + c1) + (c2 + c3) per four channels and then pairwise, at most 8 roundings deep:
+ *                                  bitwise reproducible.  out[4i][4j] is that sum to the bit.  The mean is sum * (1 / cnv6_out), exact
+ *                                  (the width is a power of two); the caller multiplies.
+ *   rot_max, trans_max  [B]        the largest value of the head's [H/4][W/4][cnv6_out] block, equal to feat_*.max() of the same
+ *                                  forward to the bit (cnv6 is post-ReLU: at least +0).
+ * davo_set_heat_export(ctx, 1) allocates a workspace of its own - per window of one davo_forward sub-batch 2 (H/4 W/4 + H W + 1)
+ * floats - independent of davo_set_feature_export; (ctx, 0) and davo_destroy free it; off by default, and a context that never
+ * switches it on allocates and launches nothing for it.
+ * davo_forward_heat is davo_forward_features plus the heat members: the same inputs, synchronous, the same sub-batching under
+ * "host_chunk", the same pair-selection rule (DAVO_PAIRS_BOTH, else DAVO_ERR_INVALID), both precisions, davo_set_posenn_se and
+ * davo_set_impl(ctx, 1); pose_out is bit for bit davo_forward's; a batch that fails its f16x3 range verdict is re-issued first and
+ * exported from the re-issue, in the precision it ran.  A NULL member is neither computed nor copied; `out' or `heat' may be NULL.
+ * Non-NULL members of `out' need davo_set_feature_export on, non-NULL members of `heat' need davo_set_heat_export on: otherwise
+ * DAVO_ERR_NOT_READY with a message naming the switch. */
+typedef struct {
+    float* rot_sum;
+    float* trans_sum;
+    float* rot_max;
+    float* trans_max;
+} davo_heat_out;
+int davo_set_heat_export(davo_ctx* ctx, int on);
+int davo_forward_heat(davo_ctx* ctx, int B, const uint8_t* img, const float* flow, const float* seg,
+                      const float* depth, float* pose_out,
+                      const davo_feature_out* out, const davo_heat_out* heat);
+
 const char* davo_last_error(const davo_ctx* ctx);
 void davo_destroy(davo_ctx* ctx);
 
@@ -484,7 +521,9 @@ int davo_set_impl(davo_ctx* ctx, int impl);
 /* Copy an intermediate of the LAST forward to host (float32, NHWC, pair-image major = 2B images):
  * "att_table" [B,3,19], "packed" [2B,H,W,8|10], "cnv1".."cnv5", "cnv6" [.., 2*cnv6_out]
  * (rotation | translation), "cnv7" [.., 512].  With davo_set_posenn_se(ctx, 1) also "cnv5_se_scale" [2B,2,256] (row 0 = s_r,
- * row 1 = s_r * s_t) and "cnv5_se" [2B,H/4,W/4,512] (cnv6's rotation input | its translation input).
+ * row 1 = s_r * s_t) and "cnv5_se" [2B,H/4,W/4,512] (cnv6's rotation input | its translation input).  After a davo_forward_heat
+ * with the heat export on also "heat_sum" [2,n,H/4,W/4]: the channel sums (rotation | translation) the planes of the piece exported
+ * last were resized from, n = that piece's windows (all B where the workspace holds the batch).
  * n_floats must equal the tensor size. */
 int davo_debug_read(davo_ctx* ctx, const char* tensor, float* host_out, size_t n_floats);
 
