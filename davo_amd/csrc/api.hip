@@ -73,6 +73,7 @@ int add_slot(davo_ctx* c) {
     const size_t partial_floats = (size_t)c->max_batch * SQ_CHUNKS * (att_class_table(c->v.att_source) ? 3 * SQ_REC : 2 * 2);
     HIP_TRY(c, dev_alloc(&s.d_partial, partial_floats));
     HIP_TRY(c, dev_alloc(&s.d_tab, (size_t)c->max_batch * 3 * NCLS));
+    if (c->v.att_source == ATT_DEPTH_SPLIT) HIP_TRY(c, dev_alloc(&s.d_tab_far, (size_t)c->max_batch * 3 * NCLS));      // the far MLP's tables: this source only
     HIP_TRY(c, dev_alloc(&s.d_pose_partial, NB * 2 * PH_SPLIT * 3));
     { int rc = zero_now(c, s.d_partial.get(), partial_floats * sizeof(float)); if (rc) return rc; }
     const size_t counters = (size_t)c->max_batch + 1 + SK_TILE_COUNTERS;
@@ -100,7 +101,7 @@ int davo_create(davo_ctx** out, int device, int H, int W, int max_batch, const d
     if (max_batch < 1) return fail(c, DAVO_ERR_INVALID, "max_batch must be >= 1");
     if (v->cin_per_frame != 5 && v->cin_per_frame != 3) return fail(c, DAVO_ERR_INVALID, "cin_per_frame must be 3 or 5");
     if (ilog2_exact(v->cnv6_out) < 5 || v->cnv6_out > 256) return fail(c, DAVO_ERR_INVALID, "cnv6_out must be 32, 64, 128 or 256");
-    if (v->se_act < 0 || v->se_act > 2 || v->abs_mode < 0 || v->abs_mode > 3 || v->att_source < 0 || v->att_source > 12)
+    if (v->se_act < 0 || v->se_act > 2 || v->abs_mode < 0 || v->abs_mode > 3 || v->att_source < 0 || v->att_source > ATT_DEPTH_SPLIT)
         return fail(c, DAVO_ERR_INVALID, "variant field out of range");
     int ndev = 0;
     HIP_TRY(c, hipGetDeviceCount(&ndev));
@@ -165,13 +166,15 @@ int davo_set_posenn_se(davo_ctx* c, int mode) {
 }
 
 int davo_load_weight(davo_ctx* c, const char* tf_name, const float* data, const int64_t* shape, int ndim) {
-    if (!c || !tf_name || !data || !shape || ndim < 1 || ndim > 4) return fail(c, DAVO_ERR_INVALID, "bad argument to davo_load_weight");
+    // ndim 0: a scalar variable (the depth threshold); shape may then be null
+    if (!c || !tf_name || !data || ndim < 0 || ndim > 4 || (!shape && ndim > 0)) return fail(c, DAVO_ERR_INVALID, "bad argument to davo_load_weight");
     std::vector<int64_t> want;
     if (!expected_shape(c, tf_name, &want)) return fail(c, DAVO_ERR_INVALID, "unknown variable `%s'", tf_name);
     bool listed = false;
     for (auto& n : c->needed) listed |= (n == tf_name);
     if (!listed) return fail(c, DAVO_ERR_INVALID, "variable `%s' is not part of this variant", tf_name);
-    std::vector<int64_t> got(shape, shape + ndim);
+    std::vector<int64_t> got;
+    if (ndim > 0) got.assign(shape, shape + ndim);
     if (got != want) {
         std::string g, w;
         for (auto d : got) g += std::to_string(d) + ",";
@@ -183,6 +186,7 @@ int davo_load_weight(davo_ctx* c, const char* tf_name, const float* data, const 
     HostTensor& t = c->weights[tf_name];
     t.shape = got;
     t.data.assign(data, data + n);
+    if (strcmp(tf_name, DEPTH_THRESHOLD_NAME) == 0) c->depth_thr = data[0];      // the kernels take it as an argument from this host copy
     HIP_TRY(c, hipSetDevice(c->device));
     // the kernels read the small dense tensors (SE fully-connected layers, static channel weights) in the reference's own layout;
     // the convolution tensors are re-laid-out at the first forward (weights.hip) and their raw device copy is only the test hook's
@@ -209,7 +213,7 @@ int davo_weights_missing(davo_ctx* c) {
 // The f16x3 batches they issue are judged by the range guard (range_guard.hip, reached through ctx.h; bookkeeping: c->book).
 namespace {
 
-// The depth argument of an entry point.  A depth-source variant (att_source 11, 12) must be called through the `_depth' form with
+// The depth argument of an entry point.  A variant that reads depth planes (att_source 11, 12, 13) must be called through the `_depth' form with
 // the planes; every other variant reads no depth: the `_depth' forms accept a pointer (or null) and ignore it.
 int resolve_depth(davo_ctx* c, const char* fn, bool depth_form, const void** depth) {
     if (!needs_depth(c)) { *depth = nullptr; return DAVO_OK; }
@@ -337,7 +341,9 @@ int stage_inputs(davo_ctx* c, const InputSet& set, const Inputs& host, int b0, i
         const size_t plane = n.seg / 3;
         if (att_tgt_attended(c->v.att_source)) HIP_TRY(c, copy2d(dst(set.seg, n.seg), src.seg, n.seg, src1 ? plane : 0, 2 * plane, nb));
         else HIP_TRY(c, copy2d(dst(set.seg, n.seg), src.seg, n.seg, src1 ? 2 * plane : 0, plane, nb));
-        if (src.depth) HIP_TRY(c, copy2d(dst(set.depth, n.depth), src.depth, n.depth, src1 ? plane : 0, 2 * plane, nb));
+        // depth sources: the target's plane and the source's; the depth-split attention reads the source frame's plane alone
+        if (src.depth && c->v.att_source == ATT_DEPTH_SPLIT) HIP_TRY(c, copy2d(dst(set.depth, n.depth), src.depth, n.depth, src1 ? 2 * plane : 0, plane, nb));
+        else if (src.depth) HIP_TRY(c, copy2d(dst(set.depth, n.depth), src.depth, n.depth, src1 ? plane : 0, 2 * plane, nb));
         return DAVO_OK;
     }
     HIP_TRY(c, hipMemcpyAsync(dst(set.img, n.img), src.img, n.img * nb, hipMemcpyHostToDevice, s));
@@ -503,7 +509,8 @@ int export_features(davo_ctx* c, const Inputs& in, int w0, int nw, int b0, int B
         if (w_att19 || w_att || w_masked || w_image) {
             ProfScope ps(c, s, "feature_maps");
             HIP_TRY(c, launch_feature_maps(static_cast<const uint8_t*>(win.img), static_cast<const float*>(win.seg),
-                                           ws.d_tab.get() + (size_t)(w0 + p0) * 3 * NCLS, c->v, np, c->H, c->W, w_att19, w_att, w_masked, w_image, s));
+                                           ws.d_tab.get() + (size_t)(w0 + p0) * 3 * NCLS, c->v, np, c->H, c->W, w_att19, w_att, w_masked, w_image, s,
+                                           static_cast<const float*>(win.depth), ws.d_tab_far ? ws.d_tab_far.get() + (size_t)(w0 + p0) * 3 * NCLS : nullptr, c->depth_thr));
         }
         if (w_rot || w_trans) {
             ProfScope ps(c, s, "feature_resize_cnv6");
@@ -578,6 +585,14 @@ int export_heat(davo_ctx* c, int w0, int nw, int b0, const davo_heat_out& out) {
         HIP_TRY(c, hipStreamSynchronize(s));              // the next piece reuses the workspace
     }
     return DAVO_OK;
+}
+
+// The depth-split flow attention applies two tables per frame, chosen per pixel: there is no 19-row table an `att_19' member could
+// hold (the reference sets no att_19s for the branch either, davo.py:1470).  Refused before anything runs; the context stays usable.
+int refuse_att_19(davo_ctx* c, const char* fn, const davo_feature_out* out) {
+    if (c->v.att_source != ATT_DEPTH_SPLIT || !out || !out->att_19) return DAVO_OK;
+    return fail(c, DAVO_ERR_INVALID, "%s: `att_19' does not exist for the depth-split flow attention (att_source %d): every source pixel takes its "
+                "weight from the near or the far table by its depth, no single 19-row table was applied - pass att_19 = NULL", fn, ATT_DEPTH_SPLIT);
 }
 
 // what a davo_forward_features / davo_forward_heat call wants beside the poses; null = nothing of that kind
@@ -720,6 +735,7 @@ int davo_forward_features(davo_ctx* c, int B, const uint8_t* img, const float* f
     if (c->pairs != PAIRS_BOTH)
         return fail(c, DAVO_ERR_INVALID, "davo_forward_features runs both pairs of every window, the reference's semantics (davo.py:1456-1457): "
                     "davo_set_pairs(ctx, DAVO_PAIRS_BOTH) first (the selection is %d)", c->pairs);
+    { int rc = refuse_att_19(c, "davo_forward_features", out); if (rc) return rc; }
     return forward_entry(c, B, img, flow, seg, depth, pose_out, true, Exports{fx_wanted(out) ? out : nullptr, nullptr});
 }
 
@@ -746,6 +762,7 @@ int davo_forward_heat(davo_ctx* c, int B, const uint8_t* img, const float* flow,
     if (c->pairs != PAIRS_BOTH)
         return fail(c, DAVO_ERR_INVALID, "davo_forward_heat runs both pairs of every window, the reference's semantics (davo.py:1456-1457): "
                     "davo_set_pairs(ctx, DAVO_PAIRS_BOTH) first (the selection is %d)", c->pairs);
+    { int rc = refuse_att_19(c, "davo_forward_heat", out); if (rc) return rc; }
     return forward_entry(c, B, img, flow, seg, depth, pose_out, true, Exports{want_fx ? out : nullptr, want_heat ? heat : nullptr});
 }
 
@@ -1070,7 +1087,11 @@ int davo_debug_read(davo_ctx* c, const char* tensor, float* host_out, size_t n_f
     size_t n = 0;
     const std::string t = tensor;
     const Slot& ws = last_workspace(c);
-    if (t == "att_table") { src = ws.d_tab.get(); n = (size_t)c->last_B * 3 * NCLS; }
+    if (t == "att_table") { src = ws.d_tab.get(); n = (size_t)c->last_B * 3 * NCLS; }       // att_source 13: the near MLP's tables
+    else if (t == "att_table_far") {                         // ... and the far MLP's; the target's rows are ones in both
+        if (!ws.d_tab_far) return fail(c, DAVO_ERR_INVALID, "`att_table_far' exists for the depth-split flow attention only (att_source %d, got %d)", ATT_DEPTH_SPLIT, c->v.att_source);
+        src = ws.d_tab_far.get(); n = (size_t)c->last_B * 3 * NCLS;
+    }
     else if (t == "cnv5_se_scale" || t == "cnv5_se") {      // feature attention (posenn_se.h): [2B][2][256] s_r | s_r s_t; [2B][H2][W2][512] rotation | translation input of cnv6
         if (!c->posenn_se || !ws.se) return fail(c, DAVO_ERR_NOT_READY, "`%s' exists in the feature-attention variant only (davo_set_posenn_se)", tensor);
         if (t == "cnv5_se") { src = ws.se->d_se.get(); n = NB * c->H2 * c->W2 * 512; }
@@ -1113,7 +1134,7 @@ int davo_debug_read(davo_ctx* c, const char* tensor, float* host_out, size_t n_f
     if (n != n_floats) return fail(c, DAVO_ERR_INVALID, "`%s' holds %zu floats, caller asked for %zu", tensor, n, n_floats);
     int rc = davo_memcpy_d2h(c, host_out, src, n * sizeof(float));
     if (rc) return rc;
-    const bool split = c->last_precision == 1 && t != "att_table" && t != "cnv7" && t != "cnv5_se_scale";
+    const bool split = c->last_precision == 1 && t != "att_table" && t != "att_table_far" && t != "cnv7" && t != "cnv5_se_scale";
     if (split) {       // split-fp16 blocked -> plain float32 NHWC
         int ch = 8;
         const char* names[6] = {"cnv1", "cnv2", "cnv3", "cnv4", "cnv5", "cnv6"};

@@ -84,6 +84,7 @@ struct SeWorkspace {                             // feature attention (posenn_se
 struct Slot {
     StreamOwner stream;
     DevMem<float> d_partial, d_tab, d_packed, d_pose_partial;
+    DevMem<float> d_tab_far;                     // depth-split flow attention (att_source 13): the far MLP's tables [B][3][19] (d_tab holds the near ones); null in every other variant
     DevMem<float> d_act[7];
     std::optional<SeWorkspace> se;               // absent with the feature-attention mode off
     DevMem<unsigned> d_counters;                 // "last workgroup" tickets (pose_tail.h): [0] cnv7's pose tail, [1 + b] triplet b's squeeze, [1 + max_batch + t] tile t of a split-K launch
@@ -221,6 +222,7 @@ struct davo_ctx {
     size_t pose_tiles_floats = 0;
     bool cnv7_valid = true;
     davo::Variant v{};
+    float depth_thr = 0.f;                     // att_source 13: pose_exp_net/se_flow/depth_threshold as davo_load_weight received it (the kernels take it as an argument)
     int posenn_se = 0;                         // davo_set_posenn_se: 0 none | 1 insert - an SE block on cnv5 ahead of each head's cnv6 (posenn_se.h); cnv6 is then a two-group layer
     bool forward_seen = false;                 // a forward has been issued (davo_set_posenn_se is refused from then on)
     int impl = 0;
@@ -333,7 +335,7 @@ inline PlaneBytes plane_bytes(const davo_ctx* c) {
     const size_t HW = (size_t)c->H * c->W;
     return PlaneBytes{HW * 9, HW * 8 * sizeof(float), HW * 3 * sizeof(float), HW * 3 * sizeof(float)};      // depth: [3,H,W,1] float32 like the label maps (davo.py:991-996)
 }
-inline bool needs_depth(const davo_ctx* c) { return att_desc_depth(c->v.att_source); }
+inline bool needs_depth(const davo_ctx* c) { return att_reads_depth(c->v.att_source); }
 
 inline int ilog2_exact(int v) {
     int l = 0;
@@ -369,6 +371,9 @@ std::vector<std::string> needed_names(const Variant& v, int posenn_se = 0);
 // TF name of an SE dense tensor of the variant's scope (k: 0 bottleneck_fc/kernel, 1 its bias, 2 recover_fc/kernel, 3 its bias);
 // the se_flow scope's for the variants without SE layers (the kernels do not read them there)
 const char* se_weight_name(int att_source, int k);
+// att_source 13: the se_flow_near tensors are se_weight_name(13, k), the se_flow_far ones se_far_weight_name(k); the scalar threshold:
+const char* se_far_weight_name(int k);
+constexpr const char* DEPTH_THRESHOLD_NAME = "pose_exp_net/se_flow/depth_threshold";
 // the SE layers' scope is a dense tensor the kernels read in the reference's [in,out] layout (not re-laid-out like a convolution)
 bool is_dense_weight(const std::string& name);
 bool expected_shape(const davo_ctx* c, const std::string& name, std::vector<int64_t>* sh);

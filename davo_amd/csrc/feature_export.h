@@ -35,8 +35,13 @@ struct FeatureMapsOut {          // device pointers of one piece of nw windows; 
 // first window of the piece.  The masked rgb is mask_pack's float32 expression - u8_to_unit, then one multiply by the frame's map
 // where the variant masks rgb - so it equals the packed tensor's rgb channels to the bit.  The first 3 * nw * 19 threads also write
 // the att_19 rows: the table row the forward used for a looked-up frame, 19 ones for an overridden one, whatever d_tab holds there.
-__global__ __launch_bounds__(256) void feature_maps(const uint8_t* __restrict__ img, const float* __restrict__ seg,
-                                                    const float* __restrict__ tab, Variant v, int nw, int H, int W, FeatureMapsOut o) {
+// DSPLIT (att_source 13): a source frame's map is mask_pack_depthsplit's select - the frame's own depth plane against the threshold
+// chooses the near table `tab' or the far table `ds.tab_far' per pixel (input_decode.h); depth points at the piece's first window
+// like img and seg.  No single 19-row table was applied there (the reference sets no att_19s, davo.py:1470): o.att_19 is null.
+template <bool DSPLIT>
+__device__ __forceinline__ void feature_maps_body(const uint8_t* __restrict__ img, const float* __restrict__ seg,
+                                                  const float* __restrict__ tab, const Variant& v, int nw, int H, int W, const FeatureMapsOut& o,
+                                                  const DepthSplit& ds) {
     const int W4 = W >> 2;
     const long total = (long)nw * H * W4;
     const long gid = (long)blockIdx.x * 256 + threadIdx.x;
@@ -59,8 +64,15 @@ __global__ __launch_bounds__(256) void feature_maps(const uint8_t* __restrict__ 
         if (feature_frame_looked_up(v.att_source, frame)) {
             const float4 sg = *reinterpret_cast<const float4*>(seg + ((size_t)b * 3 + slot) * HW + pix);
             const float* tab_f = tab + ((size_t)b * 3 + frame) * NCLS;
-            a[0] = att_lookup(tab_f, sg.x); a[1] = att_lookup(tab_f, sg.y);
-            a[2] = att_lookup(tab_f, sg.z); a[3] = att_lookup(tab_f, sg.w);
+            if (DSPLIT) {
+                const float4 dp = *reinterpret_cast<const float4*>(ds.depth + ((size_t)b * 3 + slot) * HW + pix);
+                const float* far_f = ds.tab_far + ((size_t)b * 3 + frame) * NCLS;
+                a[0] = att_lookup_split(tab_f, far_f, ds.thr, dp.x, sg.x); a[1] = att_lookup_split(tab_f, far_f, ds.thr, dp.y, sg.y);
+                a[2] = att_lookup_split(tab_f, far_f, ds.thr, dp.z, sg.z); a[3] = att_lookup_split(tab_f, far_f, ds.thr, dp.w, sg.w);
+            } else {
+                a[0] = att_lookup(tab_f, sg.x); a[1] = att_lookup(tab_f, sg.y);
+                a[2] = att_lookup(tab_f, sg.z); a[3] = att_lookup(tab_f, sg.w);
+            }
         }
         const size_t at = ((size_t)frame * nw + b) * HW + pix;
         if (o.attention) *reinterpret_cast<float4*>(o.attention + at) = make_float4(a[0], a[1], a[2], a[3]);
@@ -86,6 +98,17 @@ __global__ __launch_bounds__(256) void feature_maps(const uint8_t* __restrict__ 
             if (oi) oi[k] = make_float4(plain[4 * k], plain[4 * k + 1], plain[4 * k + 2], plain[4 * k + 3]);
         }
     }
+}
+
+__global__ __launch_bounds__(256) void feature_maps(const uint8_t* __restrict__ img, const float* __restrict__ seg,
+                                                    const float* __restrict__ tab, Variant v, int nw, int H, int W, FeatureMapsOut o) {
+    feature_maps_body<false>(img, seg, tab, v, nw, H, W, o, DepthSplit{});
+}
+
+__global__ __launch_bounds__(256) void feature_maps_depthsplit(const uint8_t* __restrict__ img, const float* __restrict__ seg,
+                                                               const float* __restrict__ tab, Variant v, int nw, int H, int W, FeatureMapsOut o,
+                                                               DepthSplit ds) {
+    feature_maps_body<true>(img, seg, tab, v, nw, H, W, o, ds);
 }
 
 // TF 1.13's resize_bilinear (align_corners=False, no half-pixel centres) at the one scale the library has: cnv6 is [H/4, W/4], so

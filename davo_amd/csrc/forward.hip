@@ -620,14 +620,22 @@ int forward_device(davo_ctx* c, const Run& run, int B, const Inputs& in, void* d
     //   the excitation MLP in the squeeze launch's last workgroup (costs two memory-side round trips per workgroup: +2 us at
     //   B = 1, +18 us at B = 32), mask + pack inside cnv1's patch fill (level at B = 32).
     const bool class_table = att_class_table(v.att_source);
-    const bool fold_excite = (v.att_source == 1 || class_table) &&
+    const bool fold_excite = (att_flow_squeeze(v.att_source) || class_table) &&
                              (c->opt_fold_tails >= 1 || (c->opt_fold_tails < 0 && B <= FOLD_EXCITE_MAX_BATCH));
     const bool fold_pose = c->opt_fold_tails == 1;
     const float* se_w1 = wdev(se_weight_name(v.att_source, 0));
     const float* se_b1 = wdev(se_weight_name(v.att_source, 1));
     const float* se_w2 = wdev(se_weight_name(v.att_source, 2));
     const float* se_b2 = wdev(se_weight_name(v.att_source, 3));
-    if (needs_depth(c)) {
+    const bool depth_split = v.att_source == ATT_DEPTH_SPLIT;
+    const float* far_w[4] = {nullptr, nullptr, nullptr, nullptr};
+    float* const d_tab_far = ws.d_tab_far.get();
+    if (depth_split) {
+        for (int k = 0; k < 4; ++k) far_w[k] = wdev(se_far_weight_name(k));
+        if (!d_tab_far || !se_w1 || !se_b1 || !se_w2 || !se_b2 || !far_w[0] || !far_w[1] || !far_w[2] || !far_w[3])
+            return fail(c, DAVO_ERR_INVALID, "internal: the depth-split attention's tables or dense tensors are missing");
+    }
+    if (att_desc_depth(v.att_source)) {
         // depth sources: one float32 sum per depth plane and chunk, then (or, folded, in the same launch) the excitation
         ProfScope ps(c, run.stream, "se_depth_squeeze");
         HIP_TRY(c, launch_se_depth_squeeze(fold_excite, static_cast<const float*>(in.depth), B, HW, v, reinterpret_cast<unsigned*>(d_partial),
@@ -638,13 +646,18 @@ int forward_device(davo_ctx* c, const Run& run, int B, const Inputs& in, void* d
         ProfScope ps(c, run.stream, "se_class_squeeze");
         HIP_TRY(c, launch_se_class_squeeze(fold_excite, d_img, d_flow, d_seg, B, H, W, v, reinterpret_cast<unsigned*>(d_partial),
                                            d_counters + 1, se_w1, se_b1, se_w2, se_b2, d_tab, range_reset, sel, s));
+    } else if (fold_excite && depth_split) {
+        // the flagship's squeeze; the triplet's last workgroup evaluates the near tables and the far tables from the same sums
+        ProfScope ps(c, run.stream, "se_squeeze_partial");
+        const float* near_w[4] = {se_w1, se_b1, se_w2, se_b2};
+        HIP_TRY(c, launch_se_squeeze_excite_split(d_flow, B, HW, v, d_partial, d_counters + 1, near_w, far_w, d_tab, d_tab_far, range_reset, sel, s));
     } else if (fold_excite) {
         // squeeze + excitation in one launch: the workgroup that delivers a triplet's last partial sum evaluates its tables
         ProfScope ps(c, run.stream, "se_squeeze_partial");
         HIP_TRY(c, launch_se_squeeze_excite(d_flow, B, HW, v, d_partial, d_counters + 1,
                                             se_w1, se_b1, se_w2, se_b2,
                                             wdev("pose_exp_net/pose_exp_net/seg_channel_weight/weight"), d_tab, range_reset, sel, s));
-    } else if (v.att_source == 1) {
+    } else if (att_flow_squeeze(v.att_source)) {
         ProfScope ps(c, run.stream, "se_squeeze_partial");
         HIP_TRY(c, launch_se_squeeze(d_flow, B, HW, v, d_partial, sel, s));
     }
@@ -653,6 +666,12 @@ int forward_device(davo_ctx* c, const Run& run, int B, const Inputs& in, void* d
         HIP_TRY(c, launch_se_excite(d_partial, B, HW, v, se_w1, se_b1, se_w2, se_b2,
                                     wdev("pose_exp_net/pose_exp_net/seg_channel_weight/weight"), d_tab, range_reset, sel, s));
     }
+    if (!fold_excite && depth_split) {
+        // depth-split: the same launch again on the far MLP, reading the same partial sums (a profile entry of its own, so that
+        // "se_excite" is one launch per forward in every variant)
+        ProfScope ps(c, run.stream, "se_excite_far");
+        HIP_TRY(c, launch_se_excite(d_partial, B, HW, v, far_w[0], far_w[1], far_w[2], far_w[3], nullptr, d_tab_far, nullptr, sel, s));
+    }
     // f16x3, fuse_pack: cnv1 builds its input patch straight from the raw inputs (mask + pack fused in,
     // the packed tensor never touches HBM).  Measured equal in time to mask_pack + cnv1 (the fused fill is bound
     // by its byte loads), so the two-kernel form stays the default.  Tuning build: DAVO_FUSE_PACK=1 / DAVO_CNV1_PATCH=0.
@@ -660,13 +679,15 @@ int forward_device(davo_ctx* c, const Run& run, int B, const Inputs& in, void* d
     const char* pe = tuning_env("DAVO_CNV1_PATCH");
     const bool fuse_env = (fe && atoi(fe) == 1) || c->opt_fuse_pack == 1 || (c->opt_fuse_pack < 0 && B <= FUSE_PACK_MAX_BATCH);
     const bool patch1 = !(pe && atoi(pe) == 0);
-    const bool fused = h3 && patch1 && fuse_env;
+    // (the depth-split attention has no fused fill: its packer is always mask_pack's depth-split form, whatever "fuse_pack" says)
+    const bool fused = h3 && patch1 && fuse_env && !depth_split;
     c->packed_valid = !fused;
     c->last_in = in;
     c->packed_ld = run.impl == 0 ? 8 : 10;
     if (!fused) {
         ProfScope ps(c, run.stream, "mask_pack");
-        HIP_TRY(c, launch_mask_pack(h3 ? 16 : (run.impl == 0 ? 8 : 10), d_img, d_flow, d_seg, d_tab, v, B, H, W, d_packed, sel, s));
+        HIP_TRY(c, launch_mask_pack(h3 ? 16 : (run.impl == 0 ? 8 : 10), d_img, d_flow, d_seg, d_tab, v, B, H, W, d_packed, sel, s,
+                                    static_cast<const float*>(in.depth), d_tab_far, c->depth_thr));
     }
     const int c6 = v.cnv6_out;
     int rc;

@@ -52,6 +52,11 @@ hipError_t xcd_round_robin_probe(hipStream_t s, int* ok);
 hipError_t launch_se_squeeze_excite(const float* d_flow, int B, int HW, const Variant& v, float* d_partial, unsigned* d_counters,
                                     const float* w1, const float* b1, const float* w2, const float* b2, const float* wstatic,
                                     float* d_tab, unsigned* d_range_reset, int sel, hipStream_t s);
+// att_source 13: the same launch with both excitations in the last workgroup - near_w / far_w = {bottleneck kernel, bias, recover kernel,
+// bias} of se_flow_near / se_flow_far, d_tab the near tables, d_tab_far the far ones
+hipError_t launch_se_squeeze_excite_split(const float* d_flow, int B, int HW, const Variant& v, float* d_partial, unsigned* d_counters,
+                                          const float* const near_w[4], const float* const far_w[4], float* d_tab, float* d_tab_far,
+                                          unsigned* d_range_reset, int sel, hipStream_t s);
 // segmentation / rgb / seg+flow class-table sources (att_source 4..10): per-frame descriptor records into d_partial (max_batch x 3 x SQ_CHUNKS x SQ_REC words);
 // fold: the triplet's last workgroup evaluates its tables too (d_counters as above), otherwise launch_se_excite follows
 hipError_t launch_se_class_squeeze(bool fold, const uint8_t* d_img, const float* d_flow, const float* d_seg, int B, int H, int W,
@@ -63,8 +68,11 @@ hipError_t launch_se_depth_squeeze(bool fold, const float* d_depth, int B, int H
                                    unsigned* d_counters, const float* w1, const float* b1, const float* w2, const float* b2,
                                    float* d_tab, unsigned* d_range_reset, int sel, hipStream_t s);
 // ld: 16 = split-fp16 8-channel layout (f16x3), 8 = float32 8-channel, 10 = the reference's 10-channel layout
+// att_source 13 (the depth-split flow attention) runs the depth-split form: d_depth (16-byte aligned), the far tables and the threshold are
+// required there and ignored everywhere else
 hipError_t launch_mask_pack(int ld, const uint8_t* d_img, const float* d_flow, const float* d_seg, const float* d_tab,
-                            const Variant& v, int B, int H, int W, float* d_packed, int sel, hipStream_t s);
+                            const Variant& v, int B, int H, int W, float* d_packed, int sel, hipStream_t s,
+                            const float* d_depth = nullptr, const float* d_tab_far = nullptr, float depth_thr = 0.f);
 // cnv1 / cnv2 / cnv3 (layer 0..2) from an LDS-staged input patch: conv_patch_cnvN_h3, or conv_patch_cnvN_f32 in float32 mode (f32);
 // fused: conv_patch_cnv1_h3<true> (f16x3 cnv1 only)
 hipError_t launch_patch_layer(int layer, bool f32, bool fused, const ConvPatchParams& p, int nblk, hipStream_t s);
@@ -90,7 +98,8 @@ hipError_t launch_se5_scale(bool h3, const void* d_x, const float* d_scale, int 
 // one piece of nw windows: d_img / d_seg / d_tab point at the piece's first window; outputs [3][nw][19], [3][nw][H][W], [3][nw][H][W][3] x 2,
 // frames in the order tgt, src0, src1; a null output is not written
 hipError_t launch_feature_maps(const uint8_t* d_img, const float* d_seg, const float* d_tab, const Variant& v, int nw, int H, int W,
-                               float* d_att_19, float* d_attention, float* d_masked, float* d_image, hipStream_t s);
+                               float* d_att_19, float* d_attention, float* d_masked, float* d_image, hipStream_t s,
+                               const float* d_depth = nullptr, const float* d_tab_far = nullptr, float depth_thr = 0.f);      // att_source 13: as launch_mask_pack
 // d_cnv6: the whole stored cnv6 of a both-pairs forward (h3: f16x3 blocked, scaled by 1 / unscale; else float32 NHWC); windows
 // [w0, w0 + nw) of it -> d_rot / d_trans [nw][4 H2][4 W2][c6]; a null head is not computed
 hipError_t launch_feature_resize_cnv6(bool h3, const void* d_cnv6, int w0, int nw, int H2, int W2, int c6, float unscale,

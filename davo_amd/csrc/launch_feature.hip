@@ -5,12 +5,19 @@
 namespace davo {
 
 hipError_t launch_feature_maps(const uint8_t* d_img, const float* d_seg, const float* d_tab, const Variant& v, int nw, int H, int W,
-                               float* d_att_19, float* d_attention, float* d_masked, float* d_image, hipStream_t s) {
+                               float* d_att_19, float* d_attention, float* d_masked, float* d_image, hipStream_t s,
+                               const float* d_depth, const float* d_tab_far, float depth_thr) {
     if (nw < 1 || H < 16 || W < 16 || H % 4 || W % 4 || !d_img || !d_seg || !d_tab) return hipErrorInvalidValue;
     if (!d_att_19 && !d_attention && !d_masked && !d_image) return hipSuccess;
     const long nthreads = (long)nw * H * (W / 4);             // >= 3 * nw * 19: the att_19 rows fit the first threads
     const FeatureMapsOut o{d_att_19, d_attention, d_masked, d_image};
-    hipLaunchKernelGGL(feature_maps, dim3((unsigned)((nthreads + 255) / 256)), dim3(256), 0, s, d_img, d_seg, d_tab, v, nw, H, W, o);
+    const dim3 grid((unsigned)((nthreads + 255) / 256));
+    if (v.att_source == ATT_DEPTH_SPLIT) {                    // two tables per frame: no att_19 rows (api.hip refuses the member)
+        if (d_att_19 || !d_depth || ((uintptr_t)d_depth & 15) || !d_tab_far) return hipErrorInvalidValue;
+        hipLaunchKernelGGL(feature_maps_depthsplit, grid, dim3(256), 0, s, d_img, d_seg, d_tab, v, nw, H, W, o, DepthSplit{d_depth, d_tab_far, depth_thr});
+    } else {
+        hipLaunchKernelGGL(feature_maps, grid, dim3(256), 0, s, d_img, d_seg, d_tab, v, nw, H, W, o);
+    }
     return hipGetLastError();
 }
 

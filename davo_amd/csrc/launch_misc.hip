@@ -46,6 +46,17 @@ hipError_t launch_se_squeeze_excite(const float* d_flow, int B, int HW, const Va
     return hipGetLastError();
 }
 
+hipError_t launch_se_squeeze_excite_split(const float* d_flow, int B, int HW, const Variant& v, float* d_partial, unsigned* d_counters,
+                                          const float* const near_w[4], const float* const far_w[4], float* d_tab, float* d_tab_far,
+                                          unsigned* d_range_reset, int sel, hipStream_t s) {
+    if (v.att_source != ATT_DEPTH_SPLIT || !d_tab_far) return hipErrorInvalidValue;
+    for (int k = 0; k < 4; ++k) if (!near_w[k] || !far_w[k]) return hipErrorInvalidValue;
+    const SeFar far{far_w[0], far_w[1], far_w[2], far_w[3], d_tab_far};
+    hipLaunchKernelGGL(se_squeeze_excite_split, dim3(SQ_CHUNKS, pairs_per_window(sel), B), dim3(256), 0, s, d_flow, HW, v, d_partial, d_counters,
+                       near_w[0], near_w[1], near_w[2], near_w[3], d_tab, d_range_reset, sel, far);
+    return hipGetLastError();
+}
+
 hipError_t launch_se_class_squeeze(bool fold, const uint8_t* d_img, const float* d_flow, const float* d_seg, int B, int H, int W,
                                   const Variant& v, unsigned* d_partial, unsigned* d_counters, const float* w1, const float* b1,
                                   const float* w2, const float* b2, float* d_tab, unsigned* d_range_reset, int sel, hipStream_t s) {
@@ -74,9 +85,19 @@ hipError_t launch_se_depth_squeeze(bool fold, const float* d_depth, int B, int H
 }
 
 hipError_t launch_mask_pack(int ld, const uint8_t* d_img, const float* d_flow, const float* d_seg, const float* d_tab,
-                            const Variant& v, int B, int H, int W, float* d_packed, int sel, hipStream_t s) {
+                            const Variant& v, int B, int H, int W, float* d_packed, int sel, hipStream_t s,
+                            const float* d_depth, const float* d_tab_far, float depth_thr) {
     const long nthreads = (long)pairs_per_window(sel) * B * H * (W / 4);
     const dim3 grid((unsigned)((nthreads + 255) / 256));
+    if (v.att_source == ATT_DEPTH_SPLIT) {             // the depth-split form: a missing plane or table is an error, never the plain packer
+        if (!d_depth || ((uintptr_t)d_depth & 15) || !d_tab_far) return hipErrorInvalidValue;
+        const DepthSplit ds{d_depth, d_tab_far, depth_thr};
+        if (ld == 16) hipLaunchKernelGGL(mask_pack_depthsplit<16>, grid, dim3(256), 0, s, d_img, d_flow, d_seg, d_tab, v, B, sel, H, W, d_packed, ds);
+        else if (ld == 8) hipLaunchKernelGGL(mask_pack_depthsplit<8>, grid, dim3(256), 0, s, d_img, d_flow, d_seg, d_tab, v, B, sel, H, W, d_packed, ds);
+        else if (ld == 10) hipLaunchKernelGGL(mask_pack_depthsplit<10>, grid, dim3(256), 0, s, d_img, d_flow, d_seg, d_tab, v, B, sel, H, W, d_packed, ds);
+        else return hipErrorInvalidValue;
+        return hipGetLastError();
+    }
     if (ld == 16) hipLaunchKernelGGL(mask_pack<16>, grid, dim3(256), 0, s, d_img, d_flow, d_seg, d_tab, v, B, sel, H, W, d_packed);
     else if (ld == 8) hipLaunchKernelGGL(mask_pack<8>, grid, dim3(256), 0, s, d_img, d_flow, d_seg, d_tab, v, B, sel, H, W, d_packed);
     else if (ld == 10) hipLaunchKernelGGL(mask_pack<10>, grid, dim3(256), 0, s, d_img, d_flow, d_seg, d_tab, v, B, sel, H, W, d_packed);

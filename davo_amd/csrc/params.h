@@ -34,11 +34,17 @@ struct Variant {
 // rgb mean, or histogram + SE-transformed flow mean), two dense layers, a 19-class sigmoid table looked up per pixel.
 // 11, 12 are the depth-source class tables (davo.py:1109, 1211-1227): the descriptor is the mean of depth_frame + depth_tgt over
 // the frame (one value), dense 1 -> 8 -> 19; they read a fourth input, the depth planes.
+// 13 is the depth-split flow attention (davo.py:1136-1155): se_flow's squeeze, then TWO 2 -> 8 -> 19 excitations (scopes se_flow_near,
+// se_flow_far) on the same sums; a pixel of a source frame looks its class up in the near table where depth < depth_threshold (a trained
+// scalar), else in the far one.  It reads the depth planes like 11 and 12 but squeezes nothing from them; the target's map is ones.
+constexpr int ATT_DEPTH_SPLIT = 13;
 constexpr int SQ_REC = 24;          // class-table squeeze: words per (triplet, frame, chunk): 19 counts | 2 flow sums (or 3 rgb sums, or 1 depth sum)
 __host__ __device__ inline bool att_class_table(int a) { return a >= 4 && a <= 12; }
 // the target frame's rgb is masked by its own table (static_all and the with-target class-table sources)
 __host__ __device__ inline bool att_tgt_attended(int a) { return a == 3 || a == 6 || a == 8 || a == 10 || a == 12; }
 __host__ __device__ inline bool att_desc_depth(int a) { return a == 11 || a == 12; }       // descriptor is the depth mean (needs the depth input)
+__host__ __device__ inline bool att_reads_depth(int a) { return att_desc_depth(a) || a == ATT_DEPTH_SPLIT; }   // the `_depth' entry points' fourth input
+__host__ __device__ inline bool att_flow_squeeze(int a) { return a == 1 || a == ATT_DEPTH_SPLIT; }   // se_squeeze_partial's sums feed the excitation
 __host__ __device__ inline bool att_desc_hist(int a) { return a == 4 || (a >= 7 && a <= 10); }   // descriptor holds the label histogram
 __host__ __device__ inline bool att_desc_rgb(int a) { return a == 5 || a == 6; }           // ... the rgb mean
 __host__ __device__ inline bool att_desc_flow(int a) { return a >= 7 && a <= 10; }         // ... the transformed flow mean

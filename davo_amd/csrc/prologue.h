@@ -1,5 +1,5 @@
 // prologue.h — the HBM-bound front of the pose path: SE squeeze, the 2->8->19 excitation
-// MLP (se_flow), the class-table squeeze / excitation of the segmentation, rgb, seg+flow and
+// MLP (se_flow; twice, near and far, for the depth-split flow attention), the class-table squeeze / excitation of the segmentation, rgb, seg+flow and
 // depth sources, and the mask + pack pass that builds the PoseNN input.
 //
 // Reference (all under /root/reference): davo.py:1519-1522 (u8 -> f32 * (1/255) * 2 - 1),
@@ -163,7 +163,7 @@ __device__ __forceinline__ void se_excite_wave(const float* __restrict__ partial
         return;
     }
     float* t = tab + ((size_t)b * 3 + frame) * NCLS;
-    if (v.att_source == 1 && frame >= 1) {
+    if (att_flow_squeeze(v.att_source) && frame >= 1) {        // se_flow, and each of the depth-split source's two MLPs
         const float* pp = partial + ((size_t)b * 2 + (frame - 1)) * SQ_CHUNKS * 2;
         static_assert(SQ_CHUNKS == 32, "one partial pair per lane of the lower half-wave");
         float sx = 0.f, sy = 0.f;
@@ -210,12 +210,20 @@ __global__ __launch_bounds__(64) void se_excite(const float* __restrict__ partia
 // Squeeze and excitation in ONE launch (attention_module.py:64-67 then :89-101): se_squeeze_partial's body, and the
 // workgroup that delivers the LAST of a triplet's 2 x SQ_CHUNKS partial sums evaluates that triplet's three tables
 // (pose_tail.h: ticket counter per triplet, agent-scope fences).  Same sums in the same order as the two launches.
-__global__ __launch_bounds__(256) void se_squeeze_excite(const float* __restrict__ flow, int HW, Variant v,
-                                                         float* __restrict__ partial, unsigned* __restrict__ counters,
-                                                         const float* __restrict__ w1, const float* __restrict__ b1,
-                                                         const float* __restrict__ w2, const float* __restrict__ b2,
-                                                         const float* __restrict__ wstatic, float* __restrict__ tab,
-                                                         unsigned* __restrict__ range_reset, int sel) {
+// The second excitation of the depth-split source (att_source 13): the far MLP's tensors and the far table [B][3][19].  The far
+// tables are evaluated from the same partial sums, in the same order, by the same code as the near ones: equal MLPs give equal bits.
+struct SeFar {
+    const float *w1, *b1, *w2, *b2;
+    float* tab;
+};
+
+template <bool SPLIT>
+__device__ __forceinline__ void se_squeeze_excite_body(const float* __restrict__ flow, int HW, const Variant& v,
+                                                       float* __restrict__ partial, unsigned* __restrict__ counters,
+                                                       const float* __restrict__ w1, const float* __restrict__ b1,
+                                                       const float* __restrict__ w2, const float* __restrict__ b2,
+                                                       const float* __restrict__ wstatic, float* __restrict__ tab,
+                                                       unsigned* __restrict__ range_reset, int sel, const SeFar& far) {
     const int chunk = blockIdx.x, s = pair_source(blockIdx.y, sel), b = blockIdx.z;
     if (range_reset && chunk == 0 && blockIdx.y == 0 && b == 0 && threadIdx.x == 0) range_reset[RANGE_SNAP] = 0u;      // as se_excite
     const float4* f = reinterpret_cast<const float4*>(flow + ((size_t)b * 4 + s) * HW * 2);
@@ -248,8 +256,29 @@ __global__ __launch_bounds__(256) void se_squeeze_excite(const float* __restrict
         agent_stores_done();
     }
     if (!last_workgroup(counters + b, (unsigned)(pairs_per_window(sel) * SQ_CHUNKS), &ticket)) return;
-    if (wid < 3 && pair_reads_frame(wid, sel)) se_excite_wave<true>(partial, HW, v, b, wid, lane, w1, b1, w2, b2, wstatic, tab);
+    if (wid < 3 && pair_reads_frame(wid, sel)) {
+        se_excite_wave<true>(partial, HW, v, b, wid, lane, w1, b1, w2, b2, wstatic, tab);
+        if (SPLIT) se_excite_wave<true>(partial, HW, v, b, wid, lane, far.w1, far.b1, far.w2, far.b2, wstatic, far.tab);
+    }
     if (threadIdx.x == 0) __hip_atomic_store(counters + b, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+__global__ __launch_bounds__(256) void se_squeeze_excite(const float* __restrict__ flow, int HW, Variant v,
+                                                         float* __restrict__ partial, unsigned* __restrict__ counters,
+                                                         const float* __restrict__ w1, const float* __restrict__ b1,
+                                                         const float* __restrict__ w2, const float* __restrict__ b2,
+                                                         const float* __restrict__ wstatic, float* __restrict__ tab,
+                                                         unsigned* __restrict__ range_reset, int sel) {
+    se_squeeze_excite_body<false>(flow, HW, v, partial, counters, w1, b1, w2, b2, wstatic, tab, range_reset, sel, SeFar{});
+}
+
+// ... of the depth-split source: the triplet's last workgroup evaluates the near tables, then the far ones
+__global__ __launch_bounds__(256) void se_squeeze_excite_split(const float* __restrict__ flow, int HW, Variant v,
+                                                               float* __restrict__ partial, unsigned* __restrict__ counters,
+                                                               const float* __restrict__ w1, const float* __restrict__ b1,
+                                                               const float* __restrict__ w2, const float* __restrict__ b2,
+                                                               float* __restrict__ tab, unsigned* __restrict__ range_reset, int sel, SeFar far) {
+    se_squeeze_excite_body<true>(flow, HW, v, partial, counters, w1, b1, w2, b2, nullptr, tab, range_reset, sel, far);
 }
 
 // Class-table SE squeeze (att_source 4..10): one workgroup per (chunk, frame, triplet), grid (SQ_CHUNKS, att_se_frames, B); frame =
@@ -422,10 +451,13 @@ __global__ __launch_bounds__(256) void se_depth_squeeze(const float* __restrict_
 //                                      two identically-zero tgt-flow channels are dropped)
 //                            LD = 10: tgt rgb | 0 0 | src rgb*att | flow*att (reference layout)
 // v0 variants (rgb only) leave the flow slots zero.
-template <int LD>
-__global__ __launch_bounds__(256) void mask_pack(const uint8_t* __restrict__ img, const float* __restrict__ flow,
-                                                 const float* __restrict__ seg, const float* __restrict__ tab,
-                                                 Variant v, int B, int sel, int H, int W, float* __restrict__ out) {
+// DSPLIT (att_source 13, the depth-split flow attention): per 4-pixel group one more float4, of the depth plane of the source frame
+// the label map belongs to (file plane 0 or 2), and each pixel's class is looked up in the near table `tab' or the far table
+// `ds.tab_far' by att_lookup_split (input_decode.h, with DepthSplit); everything else is the same code.  The target's map is ones.
+template <int LD, bool DSPLIT>
+__device__ __forceinline__ void mask_pack_body(const uint8_t* __restrict__ img, const float* __restrict__ flow,
+                                               const float* __restrict__ seg, const float* __restrict__ tab,
+                                               const Variant& v, int B, int sel, int H, int W, float* __restrict__ out, const DepthSplit& ds) {
     const int W4 = W >> 2;
     const long total = (long)B * pairs_per_window(sel) * H * W4;
     const long gid_raw = (long)blockIdx.x * 256 + threadIdx.x;
@@ -457,12 +489,17 @@ __global__ __launch_bounds__(256) void mask_pack(const uint8_t* __restrict__ img
     // tf.ones_like overrides are ones everywhere, ignore-label pixels included: every frame for
     // -no_segmask (davo.py:1387), the tgt frame unless static_all (davo.py:1394,1411).
     float as[4] = {1.f, 1.f, 1.f, 1.f};
-    if (v.att_source != 0) {
+    if (DSPLIT) {
+        const float4 dp = *reinterpret_cast<const float4*>(ds.depth + ((size_t)b * 3 + (s ? 2 : 0)) * H * W + pix);
+        const float* far_s = ds.tab_far + ((size_t)b * 3 + 1 + s) * NCLS;
+        as[0] = att_lookup_split(tab_s, far_s, ds.thr, dp.x, sg.x); as[1] = att_lookup_split(tab_s, far_s, ds.thr, dp.y, sg.y);
+        as[2] = att_lookup_split(tab_s, far_s, ds.thr, dp.z, sg.z); as[3] = att_lookup_split(tab_s, far_s, ds.thr, dp.w, sg.w);
+    } else if (v.att_source != 0) {
         as[0] = att_lookup(tab_s, sg.x); as[1] = att_lookup(tab_s, sg.y);
         as[2] = att_lookup(tab_s, sg.z); as[3] = att_lookup(tab_s, sg.w);
     }
     float at[4] = {1.f, 1.f, 1.f, 1.f};
-    if (att_tgt_attended(v.att_source)) {                     // static_all / a with-target class table: tgt frame is masked too
+    if (!DSPLIT && att_tgt_attended(v.att_source)) {                     // static_all / a with-target class table: tgt frame is masked too
         const float4 tg = *reinterpret_cast<const float4*>(seg + ((size_t)b * 3 + 1) * H * W + pix);
         const float* tab_t = tab + (size_t)b * 3 * NCLS;
         at[0] = att_lookup(tab_t, tg.x); at[1] = att_lookup(tab_t, tg.y);
@@ -529,6 +566,20 @@ __global__ __launch_bounds__(256) void mask_pack(const uint8_t* __restrict__ img
             if ((long)blockIdx.x * 256 + (j >> 3) < total) og[(j & ~7) + k] = stage[j];
         }
     }
+}
+
+template <int LD>
+__global__ __launch_bounds__(256) void mask_pack(const uint8_t* __restrict__ img, const float* __restrict__ flow,
+                                                 const float* __restrict__ seg, const float* __restrict__ tab,
+                                                 Variant v, int B, int sel, int H, int W, float* __restrict__ out) {
+    mask_pack_body<LD, false>(img, flow, seg, tab, v, B, sel, H, W, out, DepthSplit{});
+}
+
+template <int LD>
+__global__ __launch_bounds__(256) void mask_pack_depthsplit(const uint8_t* __restrict__ img, const float* __restrict__ flow,
+                                                            const float* __restrict__ seg, const float* __restrict__ tab,
+                                                            Variant v, int B, int sel, int H, int W, float* __restrict__ out, DepthSplit ds) {
+    mask_pack_body<LD, true>(img, flow, seg, tab, v, B, sel, H, W, out, ds);
 }
 
 // Pose head tail: pred (1x1, 256 -> 3, linear) + mean over H3 x W3 + 0.01 scale

@@ -1,5 +1,5 @@
 // weights.hip — weight tensors of the pose path: the TF variable names and shapes a variant needs
-// (the SE scopes se_flow / se_seg / se_rgb / se_segflow), and their one-time re-layout into the kernels' operand formats:
+// (the SE scopes se_flow / se_flow_near / se_flow_far / se_seg / se_rgb / se_segflow / se_depth), and their one-time re-layout into the kernels' operand formats:
 //   f32 path    HWIO [KS,KS,Cin,Cout] -> Wp[Cout_pad][K_pad] floats, k = tap * Cin_packed + c
 //   f16x3 path  HWIO -> [Cout_pad][chunk][32 hi | 32 lo] halves, channel-block major / tap minor,
 //               pre-multiplied by a power of two so the fp16 residuals of small weights stay normal
@@ -67,7 +67,7 @@ void pack_conv_weights(const float* w_tf, int KS, int cin_tf, int cout, const in
 
 // ---- weights ----------------------------------------------------------------------------
 const char* se_weight_name(int att_source, int k) {
-    static const char* const names[5][4] = {
+    static const char* const names[6][4] = {
         {"pose_exp_net/se_flow/bottleneck_fc/kernel", "pose_exp_net/se_flow/bottleneck_fc/bias",
          "pose_exp_net/se_flow/recover_fc/kernel", "pose_exp_net/se_flow/recover_fc/bias"},
         {"pose_exp_net/se_seg/bottleneck_fc/kernel", "pose_exp_net/se_seg/bottleneck_fc/bias",              // davo.py:1304-1310
@@ -77,13 +77,23 @@ const char* se_weight_name(int att_source, int k) {
         {"pose_exp_net/se_segflow/bottleneck_fc/kernel", "pose_exp_net/se_segflow/bottleneck_fc/bias",      // :1341-1374
          "pose_exp_net/se_segflow/recover_fc/kernel", "pose_exp_net/se_segflow/recover_fc/bias"},
         {"pose_exp_net/se_depth/bottleneck_fc/kernel", "pose_exp_net/se_depth/bottleneck_fc/bias",          // :1211-1227
-         "pose_exp_net/se_depth/recover_fc/kernel", "pose_exp_net/se_depth/recover_fc/bias"}};
+         "pose_exp_net/se_depth/recover_fc/kernel", "pose_exp_net/se_depth/recover_fc/bias"},
+        {"pose_exp_net/se_flow_near/bottleneck_fc/kernel", "pose_exp_net/se_flow_near/bottleneck_fc/bias",  // :1136-1155
+         "pose_exp_net/se_flow_near/recover_fc/kernel", "pose_exp_net/se_flow_near/recover_fc/bias"}};
+    if (att_source == ATT_DEPTH_SPLIT) return names[5][k & 3];
     const int scope = att_source == 4 ? 1 : att_desc_rgb(att_source) ? 2 : att_desc_depth(att_source) ? 4 : att_source >= 7 ? 3 : 0;
     return names[scope][k & 3];
 }
 
+const char* se_far_weight_name(int k) {
+    static const char* const names[4] = {"pose_exp_net/se_flow_far/bottleneck_fc/kernel", "pose_exp_net/se_flow_far/bottleneck_fc/bias",
+                                         "pose_exp_net/se_flow_far/recover_fc/kernel", "pose_exp_net/se_flow_far/recover_fc/bias"};
+    return names[k & 3];
+}
+
 bool is_dense_weight(const std::string& nm) {
-    for (const char* s : {"/se_flow/", "/se_seg/", "/se_rgb/", "/se_segflow/", "/se_depth/", "/cnv5_se_attention/", "seg_channel_weight"})
+    if (nm == DEPTH_THRESHOLD_NAME) return false;        // a host scalar: it travels as a kernel argument
+    for (const char* s : {"/se_flow/", "/se_flow_near/", "/se_flow_far/", "/se_seg/", "/se_rgb/", "/se_segflow/", "/se_depth/", "/cnv5_se_attention/", "seg_channel_weight"})
         if (nm.find(s) != std::string::npos) return true;
     return false;
 }
@@ -104,6 +114,10 @@ std::vector<std::string> needed_names(const Variant& v, int posenn_se) {
         }
     if (v.att_source == 1 || att_class_table(v.att_source)) {
         for (int k = 0; k < 4; ++k) n.push_back(se_weight_name(v.att_source, k));
+    } else if (v.att_source == ATT_DEPTH_SPLIT) {         // two se_flow MLPs and the threshold; none of se_flow/*_fc
+        for (int k = 0; k < 4; ++k) n.push_back(se_weight_name(v.att_source, k));
+        for (int k = 0; k < 4; ++k) n.push_back(se_far_weight_name(k));
+        n.push_back(DEPTH_THRESHOLD_NAME);
     } else if (v.att_source == 2 || v.att_source == 3) {
         n.push_back("pose_exp_net/pose_exp_net/seg_channel_weight/weight");
     }
@@ -146,6 +160,14 @@ bool expected_shape(const davo_ctx* c, const std::string& name, std::vector<int6
     else if (is("pose_exp_net/se_flow/recover_fc/kernel")) *sh = {8, NCLS};
     else if (is("pose_exp_net/se_flow/recover_fc/bias")) *sh = {NCLS};
     else if (is("pose_exp_net/pose_exp_net/seg_channel_weight/weight")) *sh = {NCLS};
+    else if (c->v.att_source == ATT_DEPTH_SPLIT && is(DEPTH_THRESHOLD_NAME)) sh->clear();          // shape (): a rank-0 variable
+    else if (c->v.att_source == ATT_DEPTH_SPLIT && (name.compare(0, 26, "pose_exp_net/se_flow_near/") == 0 || name.compare(0, 25, "pose_exp_net/se_flow_far/") == 0)) {
+        if (ends("/bottleneck_fc/kernel")) *sh = {2, 8};
+        else if (ends("/bottleneck_fc/bias")) *sh = {8};
+        else if (ends("/recover_fc/kernel")) *sh = {8, NCLS};
+        else if (ends("/recover_fc/bias")) *sh = {NCLS};
+        else return false;
+    }
     else if (att_class_table(c->v.att_source) && name.compare(0, 16, "pose_exp_net/se_") == 0) {
         // the class-table sources' scope (se_seg / se_rgb / se_segflow / se_depth): [in, hidden] -> [hidden, 19]
         const int a = c->v.att_source, nin = att_se_in(a), nh = att_se_hidden(a);

@@ -15,6 +15,9 @@ from . import _lib
 from .version import ATT_SOURCE, NUM_SEG_CLASSES, parse_version, weight_shapes
 
 
+DEPTH_THRESHOLD = "pose_exp_net/se_flow/depth_threshold"      # the rank-0 variable of `-se_flow_on_depthseg_seplayers'
+
+
 class DavoError(RuntimeError):
     pass
 
@@ -134,7 +137,8 @@ class Engine:
             if name not in weights:
                 raise KeyError("checkpoint has no variable `%s'" % name)
         for name in want:
-            a = np.ascontiguousarray(weights[name], np.float32)
+            a = np.asarray(weights[name], np.float32)
+            a = a.copy() if a.shape == () else np.ascontiguousarray(a)      # (np.ascontiguousarray would make a rank-0 variable [1])
             shape = (ctypes.c_int64 * a.ndim)(*a.shape)
             self._check(self._L.davo_load_weight(self._ctx, name.encode(), a.ctypes.data_as(ctypes.POINTER(ctypes.c_float)), shape, a.ndim))
 
@@ -451,12 +455,18 @@ def seg_one_hot(seg):
     return ((idx[..., None] == np.arange(19, dtype=np.int32)) & ok[..., None]).astype(np.float32)
 
 
-def host_maps(cfg, img, seg, tables):
+def host_maps(cfg, img, seg, tables, depth=None, tables_far=None, thr=None):
     """The four map outputs of Engine.forward_features - 'att_19' [3,B,19], 'attention' [3,B,H,W], 'masked_image' and 'image'
     [3,B,H,W,3], frames tgt, src0, src1 - rebuilt on the host from a batch's inputs and the class tables its forward computed
     (Engine.debug_read("att_table"), [B,3,19]), in the kernels' float32 expressions (csrc/feature_export.h: feature_maps), so to
     the bit what the device exports.  DAVO's features='heat' mode uses it: the device-side maps live in the full export's
-    workspace, which that mode never allocates."""
+    workspace, which that mode never allocates.
+    The depth-split flow attention (`-se_flow_on_depthseg_seplayers') also takes the batch's depth planes, the far tables
+    (debug_read("att_table_far")) and the loaded threshold: a source pixel's weight comes from ``tables`` where
+    float32(depth) < thr, else from ``tables_far`` (a NaN depth is far); 'att_19' is absent there - no single table was applied."""
+    split = cfg.att_source == "se_flow_depthseg_sep"
+    if split and (depth is None or tables_far is None or thr is None):
+        raise ValueError("version `%s' needs depth, tables_far and thr" % cfg.version)
     img = np.asarray(img, np.uint8)
     seg = np.asarray(seg, np.float32)
     tables = np.asarray(tables, np.float32)
@@ -474,9 +484,18 @@ def host_maps(cfg, img, seg, tables):
             with np.errstate(invalid="ignore"):
                 ok = np.isfinite(lab) & (lab > -1.0) & (lab < float(NUM_SEG_CLASSES))
             idx = np.where(ok, lab, 0.0).astype(np.int64).reshape(B, -1)
-            att[f] = np.where(ok, np.take_along_axis(a19[f], idx, axis=1).reshape(B, H, W), np.float32(0.0))
+            looked = np.take_along_axis(a19[f], idx, axis=1).reshape(B, H, W)
+            if split:
+                far = np.take_along_axis(np.asarray(tables_far, np.float32)[:, f], idx, axis=1).reshape(B, H, W)
+                with np.errstate(invalid="ignore"):
+                    near = np.asarray(depth, np.float32)[:, plane, :, :, 0] < np.float32(thr)
+                looked = np.where(near, looked, far)
+            att[f] = np.where(ok, looked, np.float32(0.0))
     masked = image * att[..., None] if cfg.mask_rgb else image.copy()
-    return {"att_19": a19, "attention": att, "masked_image": masked, "image": image}
+    out = {"att_19": a19, "attention": att, "masked_image": masked, "image": image}
+    if split:
+        del out["att_19"]
+    return out
 
 
 class DAVO(object):
@@ -563,7 +582,9 @@ class DAVO(object):
           'pose'      [B,2,6], bit for bit mode='pose';
           'masks'     {'attention': 3 x [B,H,W,1], the maps multiplied in (after the tf.ones_like overrides);
                        'image': 3 x [B,H,W,3], the frames' rgb after masking (the plain rgb where the version masks none);
-                       'att_19': 3 x [B,1,1,19], att_19[f][b,0,0,c] = the value frame f's map takes on class c};
+                       'att_19': 3 x [B,1,1,19], att_19[f][b,0,0,c] = the value frame f's map takes on class c - an empty list
+                       for `-se_flow_on_depthseg_seplayers', where a pixel's weight comes from one of two tables by its depth
+                       and the reference sets no att_19s (davo.py:1470)};
           'features'  {'rot', 'trans'}: [B,H,W,cnv6_out], resize_bilinear of the tgt->src1 call's cnv6 heads; after
                       ``enable_feature_mode(features='heat')`` instead {'rot_sum', 'trans_sum'}: [B,H,W], the maps' sum over
                       the channels; {'rot_avg', 'trans_avg'}: [B,H,W] = sum * (1 / cnv6_out), exact; {'rot_max', 'trans_max'}:
@@ -600,7 +621,10 @@ class DAVO(object):
         if img is None or flow is None or seg is None:
             raise ValueError("image, flow and seglabel inputs are all required for version `%s'" % self.version)
         heat = self._features == 'heat'
-        r = self._forward_heat(img, flow, seg, depth) if heat else self.engine.forward_features(img, flow, seg, depth)
+        # the depth-split flow attention has no att_19 (include/davo_hip.h): the library is asked for the other members only
+        split = self.cfg.att_source == "se_flow_depthseg_sep"
+        want = tuple(n for n in Engine.FEATURE_OUTPUTS if not (split and n == "att_19"))
+        r = self._forward_heat(img, flow, seg, depth) if heat else self.engine.forward_features(img, flow, seg, depth, want=want)
         if heat:
             inv = np.float32(1.0 / self.cfg.cnv6_out)          # a power of two: the mean is exact
             features = {'rot_sum': r['heat_rot'], 'trans_sum': r['heat_trans'], 'rot_avg': r['heat_rot'] * inv,
@@ -611,7 +635,7 @@ class DAVO(object):
         return {'pose': r['pose'],
                 'masks': {'attention': [r['attention'][f][..., None] for f in range(3)],
                           'image': [r['masked_image'][f] for f in range(3)],
-                          'att_19': [r['att_19'][f][:, None, None, :] for f in range(3)]},
+                          'att_19': [] if split else [r['att_19'][f][:, None, None, :] for f in range(3)]},
                 'features': features,
                 'images': [r['image'][f] for f in range(3)],
                 'seg_19': [one_hot[:, plane] for plane in (1, 0, 2)]}
@@ -631,11 +655,16 @@ class DAVO(object):
         for b0 in range(0, B, step):
             part = [None if a is None else a[b0:b0 + step] for a in (img, flow, seg, depth)]
             r = e.forward_features(*part, want=Engine.HEAT_OUTPUTS)
-            r.update(host_maps(self.cfg, part[0], part[2], e.debug_read("att_table", (len(part[0]), 3, NUM_SEG_CLASSES))))
+            tab_shape = (len(part[0]), 3, NUM_SEG_CLASSES)
+            if self.cfg.att_source == "se_flow_depthseg_sep":
+                r.update(host_maps(self.cfg, part[0], part[2], e.debug_read("att_table", tab_shape), depth=part[3],
+                                   tables_far=e.debug_read("att_table_far", tab_shape), thr=self._weights[DEPTH_THRESHOLD]))
+            else:
+                r.update(host_maps(self.cfg, part[0], part[2], e.debug_read("att_table", tab_shape)))
             parts.append(r)
         if len(parts) == 1:
             return parts[0]
-        frame_major = ("att_19", "attention", "masked_image", "image")
+        frame_major = ("att_19", "attention", "masked_image", "image")      # (no att_19 for the depth-split flow attention)
         return {k: np.concatenate([p[k] for p in parts], axis=1 if k in frame_major else 0) for k in parts[0]}
 
     def _split(self, inputs):

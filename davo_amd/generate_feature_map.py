@@ -108,6 +108,12 @@ def main(argv=None):
     from .version import parse_version
     H, W, seq = a.img_height, a.img_width, a.test_seq
     cfg = parse_version(a.version)
+    if cfg.att_source == "se_flow_depthseg_sep":
+        # the table files hold att_19[1] / att_19[2], one 19-value row per window; this branch applies two tables per frame, chosen
+        # per pixel by depth, and sets no att_19s (reference davo.py:1470; its own script fails on line 187 there)
+        raise SystemExit("davo_amd.generate_feature_map: version `%s': `-se_flow_on_depthseg_seplayers' has no per-frame 19-class "
+                         "table to write (a near and a far table are selected per pixel by depth); use "
+                         "DAVO.inference(mode='feature') for its attention maps and features" % a.version)
     synthetic = bool(a.synthetic)
     if synthetic:
         from . import synth

@@ -119,8 +119,9 @@ def make_weights(version_or_cfg, seed=SEED):
     conv ~ U(+-sqrt(6/fan_in)) (He-uniform keeps activations O(1) through eight ReLU
     layers, so the 6-DoF outputs are large enough for the 1e-4 absolute bar to bite),
     conv biases U(+-0.05), SE kernels variance-scaling as nets/attention_module.py:60,
-    SE biases U(+-0.5) (every SE scope: se_flow, se_seg, se_rgb, se_segflow, se_depth), static seg weights stddev 0.05 as
-    nets/posenn.py:387-388."""
+    SE biases U(+-0.5) (every SE scope: se_flow, se_flow_near, se_flow_far, se_seg, se_rgb, se_segflow, se_depth - each
+    tensor on a stream of its own, named after it), static seg weights stddev 0.05 as nets/posenn.py:387-388, the depth
+    threshold of `-se_flow_on_depthseg_seplayers' N(cfg.depth_thres_init, 0.1), its initialiser (davo.py:1136-1141)."""
     cfg = parse_version(version_or_cfg) if isinstance(version_or_cfg, str) else version_or_cfg
     out = {}
     for name, shape in weight_shapes(cfg).items():
@@ -139,6 +140,8 @@ def make_weights(version_or_cfg, seed=SEED):
             a = (uniform01(seed, st, n) * 2.0 - 1.0) * 0.5
         elif name.endswith("seg_channel_weight/weight"):
             a = normalish(seed, st, n) * 0.05
+        elif name.endswith("/depth_threshold"):             # davo.py:1136-1141: random_normal(mean = the version's number, stddev 0.1)
+            a = cfg.depth_thres_init + normalish(seed, st, n) * 0.1
         else:
             raise KeyError(name)
         out[name] = a.astype(np.float32).reshape(shape)

@@ -28,7 +28,9 @@ ATT_SOURCE = {"ones": 0, "se_flow": 1, "static_src": 2, "static_all": 3,
               "se_SegFlow_to_seg_wo_tgt": 7, "se_SegFlow_to_seg": 8,
               "se_SegFlow_to_seg_8_wo_tgt": 9, "se_SegFlow_to_seg_8": 10,
               # depth-source class tables (davo.py:1211-1227): the descriptor is the mean of depth_frame + depth_tgt
-              "se_depth_wo_tgt_to_seg": 11, "se_depth_to_seg": 12}
+              "se_depth_wo_tgt_to_seg": 11, "se_depth_to_seg": 12,
+              # the flow-driven attention evaluated by two SE MLPs, selected per pixel by depth < depth_threshold (davo.py:1136-1155)
+              "se_flow_depthseg_sep": 13}
 MASK_INFO = {"none": 0, "att": 1}
 
 
@@ -50,6 +52,8 @@ class VariantConfig:
     mask_info: bool          # flow_k *= att_k         (davo.py:1430-1434)
     posenn_se: str = "none"  # none | insert: se_block on cnv5 ahead of each head's cnv6 (davo.py:1010-1011, nets/posenn.py:225-228);
                              # not a davo_variant field: Engine hands it to davo_set_posenn_se
+    depth_thres_init: float = 15.0   # -se_flow_on_depthseg_.*layers_([0-9.]+): initialiser of se_flow/depth_threshold (davo.py:1136-1141);
+                                     # inference uses the loaded value, so this only reaches synth.make_weights
 
     @property
     def cin_per_frame(self):
@@ -81,6 +85,8 @@ class VariantConfig:
 # chain: if one of these matches, the reference never reaches the se_flow branch.
 _BEFORE_SE_FLOW = ("-se_flow_on_depthseg_sharedlayers", "-se_flow_on_depthseg_seplayers",
                    "-se_flow_on_depthseg", "-se_mixDepthFlow", "-se_mixDispFlow")
+# the one of them that runs: se_flow_near / se_flow_far tables selected per pixel by depth < depth_threshold (davo.py:1136-1155)
+_DEPTHSEG_SEP = "-se_flow_on_depthseg_seplayers"
 # branches AFTER "-se_flow" and before "-no_segmask", in the reference's order; the ones in _CLASS_TABLE_SOURCES run here,
 # the rest need disparity / SPP / gp2x2 pooling or an se_block whose map is not a class table
 _AFTER_SE_FLOW = ("-se_gp2x2_flow_nobottle", "-se_gp2x2_flow", "-se_spp21_flow", "-se_spp2_flow",
@@ -104,7 +110,7 @@ _CLASS_TABLE_SOURCES = {"-se_seg_wo_tgt": "se_seg_wo_tgt",                      
                         "-se_depth_wo_tgt_to_seg": "se_depth_wo_tgt_to_seg",        # :1211-1219
                         "-se_depth_to_seg": "se_depth_to_seg"}                      # :1220-1227
 _TGT_ATTENDED = ("static_all", "se_rgb_to_seg", "se_SegFlow_to_seg", "se_SegFlow_to_seg_8", "se_depth_to_seg")
-_DEPTH_SOURCES = ("se_depth_wo_tgt_to_seg", "se_depth_to_seg")
+_DEPTH_SOURCES = ("se_depth_wo_tgt_to_seg", "se_depth_to_seg", "se_flow_depthseg_sep")
 _SE_SCOPE = {"se_flow": "se_flow", "se_seg_wo_tgt": "se_seg", "se_rgb_wo_tgt_to_seg": "se_rgb", "se_rgb_to_seg": "se_rgb",
              "se_SegFlow_to_seg_wo_tgt": "se_segflow", "se_SegFlow_to_seg": "se_segflow",
              "se_SegFlow_to_seg_8_wo_tgt": "se_segflow", "se_SegFlow_to_seg_8": "se_segflow",
@@ -134,9 +140,9 @@ def parse_version(version):
     if "-norm_depth" in v:
         raise UnsupportedVariantError("version `%s': `-norm_depth' is not supported (davo.py:1110-1111 iterates over "
                                       "what davo.py:1109 made a tensor)." % v)
-    if "depth" in re.sub("-se_depth_wo_tgt_to_seg|-se_depth_to_seg", "", v):
-        raise UnsupportedVariantError("version `%s': the only depth sources supported are `-se_depth_wo_tgt_to_seg' and "
-                                      "`-se_depth_to_seg'." % v)
+    if "depth" in re.sub("-se_depth_wo_tgt_to_seg|-se_depth_to_seg|" + _DEPTHSEG_SEP, "", v):
+        raise UnsupportedVariantError("version `%s': the only depth sources supported are `-se_depth_wo_tgt_to_seg', "
+                                      "`-se_depth_to_seg' and `%s'." % (v, _DEPTHSEG_SEP))
 
     # -- davo.py:1010-1017: se_block inside the PoseNN (if / elif: `-se_insert' wins).  `-se_insert' runs where the attention
     #    source resolves to `ones' (checked below, once the source is known); the other two modes do not run
@@ -200,11 +206,20 @@ def parse_version(version):
         abs_mode = "none"
 
     # -- davo.py:1117-1400 attention source, same elif order
-    for s in _BEFORE_SE_FLOW:
-        if s in v:
-            raise UnsupportedVariantError("version `%s': `%s' attention is not supported." % (v, s))
-    after = next((s for s in _AFTER_SE_FLOW if s in v), None)     # the first branch of the chain that matches
-    if "-se_flow" in v:
+    before = next((s for s in _BEFORE_SE_FLOW if s in v), None)   # the first branch of the chain that matches
+    if before is not None and before != _DEPTHSEG_SEP:
+        raise UnsupportedVariantError("version `%s': `%s' attention is not supported." % (v, before))
+    after = next((s for s in _AFTER_SE_FLOW if s in v), None)     # likewise, behind `-se_flow'
+    depth_thres_init = 15.0
+    if before == _DEPTHSEG_SEP:
+        att_source = "se_flow_depthseg_sep"
+        m = re.search("-se_flow_on_depthseg_.*layers_([0-9.]+)", v)   # davo.py:1136-1141
+        if m is not None:
+            try:
+                depth_thres_init = float(m.group(1))                   # (the reference's float() raises on `1.2.3' or `.')
+            except ValueError:
+                raise UnsupportedVariantError("version `%s': `%s' behind `%s' is not a number." % (v, m.group(1), _DEPTHSEG_SEP)) from None
+    elif "-se_flow" in v:
         att_source = "se_flow"
     elif after in _CLASS_TABLE_SOURCES:
         att_source = _CLASS_TABLE_SOURCES[after]
@@ -234,7 +249,8 @@ def parse_version(version):
 
     return VariantConfig(version=v, major=major, use_flow_info=use_flow_info, cnv6_out=cnv6_out,
                          se_act=se_act, norm_flow=norm_flow, abs_mode=abs_mode,
-                         att_source=att_source, mask_rgb=mask_rgb, mask_info=mask_info, posenn_se=posenn_se)
+                         att_source=att_source, mask_rgb=mask_rgb, mask_info=mask_info, posenn_se=posenn_se,
+                         depth_thres_init=depth_thres_init)
 
 
 def weight_shapes(cfg):
@@ -271,6 +287,14 @@ def weight_shapes(cfg):
         sh[p + "bottleneck_fc/bias"] = (nh,)
         sh[p + "recover_fc/kernel"] = (nh, NUM_SEG_CLASSES)
         sh[p + "recover_fc/bias"] = (NUM_SEG_CLASSES,)
+    elif cfg.att_source == "se_flow_depthseg_sep":      # two se_flow MLPs and the trained threshold (davo.py:1136-1155)
+        for scope in ("se_flow_near", "se_flow_far"):
+            p = "pose_exp_net/%s/" % scope
+            sh[p + "bottleneck_fc/kernel"] = (2, 8)
+            sh[p + "bottleneck_fc/bias"] = (8,)
+            sh[p + "recover_fc/kernel"] = (8, NUM_SEG_CLASSES)
+            sh[p + "recover_fc/bias"] = (NUM_SEG_CLASSES,)
+        sh["pose_exp_net/se_flow/depth_threshold"] = ()
     elif cfg.att_source in ("static_src", "static_all"):
         sh["pose_exp_net/pose_exp_net/seg_channel_weight/weight"] = (NUM_SEG_CLASSES,)
     return sh

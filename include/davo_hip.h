@@ -55,7 +55,12 @@ typedef struct {
                              * depth_i + depth_tgt (the reference's `list + tensor' broadcasts the target's depth onto every
                              * frame).  They read a fourth input, the depth planes: the `_depth' entry points below.
                              *  11 -se_depth_wo_tgt_to_seg      depth mean 1 -> 8 -> 19, tgt=1          (scope se_depth)
-                             *  12 -se_depth_to_seg             depth mean 1 -> 8 -> 19                 (scope se_depth) */
+                             *  12 -se_depth_to_seg             depth mean 1 -> 8 -> 19                 (scope se_depth)
+                             * depth-split flow attention (davo.py:1136-1155): se_flow's squeeze, two excitations on it, and per
+                             * pixel of a source frame the near or the far table by depth < depth_threshold (float32, strict; a NaN
+                             * depth is far); the target's map is ones.  It reads the depth planes too (`_depth' entry points):
+                             *  13 -se_flow_on_depthseg_seplayers  flow mean 2 -> 8 -> 19 twice, tgt=1   (scopes se_flow_near,
+                             *                                   se_flow_far; scalar pose_exp_net/se_flow/depth_threshold) */
     int32_t mask_rgb;       /* rgb_k *= att_k                          (davo.py:1419-1423)        */
     int32_t mask_info;      /* flow_k *= att_k  (-segmask_all)         (davo.py:1430-1434)        */
 } davo_variant;
@@ -82,7 +87,8 @@ int davo_set_posenn_se(davo_ctx* ctx, int mode);
  * (test_kitti_pose.py:129-131), one tensor at a time, keyed by the TF variable name
  * (e.g. "pose_exp_net/cnv1/weights", "pose_exp_net/pose/rotation/cnv6/biases",
  * "pose_exp_net/se_flow/bottleneck_fc/kernel", "pose_exp_net/se_segflow/recover_fc/bias").  `data` is a host pointer; the context keeps
- * its own (re-laid-out) device copy. */
+ * its own (re-laid-out) device copy.  ndim = 0 (shape may be NULL) is a scalar variable: att_source 13's
+ * "pose_exp_net/se_flow/depth_threshold", whose value the context keeps on the host and hands to its kernels as an argument. */
 int davo_load_weight(davo_ctx* ctx, const char* tf_name, const float* data,
                      const int64_t* shape, int ndim);
 
@@ -100,11 +106,11 @@ int davo_weights_missing(davo_ctx* ctx);
 int davo_forward(davo_ctx* ctx, int B, const uint8_t* img, const float* flow, const float* seg,
                  float* pose_out);
 
-/* The depth sources (att_source 11, 12) read a fourth input (davo.py:960, 991-996; test_kitti_pose.py:48, 91):
+/* The depth sources (att_source 11, 12) and the depth-split flow attention (13) read a fourth input (davo.py:960, 991-996; test_kitti_pose.py:48, 91):
  *   depth f32  [B,3,H,W,1] (file order src0,tgt,src1 like the label maps; <dump>/SS/FFFFFF-monodepth2_depth.npy),
  * 16-byte aligned where it is a device pointer.  Each entry point that takes inputs has a `_depth' form with that argument
  * behind `seg'; everything said about the three-input form holds for it, the depth planes included: davo_forward_depth copies
- * them with each sub-batch, davo_submit_depth stages all three planes per slot, the f16x3 range recovery keeps and re-issues them
+ * them with each sub-batch, davo_submit_depth stages all three planes per slot (13 never reads the target's plane), the f16x3 range recovery keeps and re-issues them
  * with the batch.  On a context whose variant reads depth the three-input forms return DAVO_ERR_INVALID (the message names the
  * `_depth' form); on any other variant the `_depth' forms accept a depth pointer or NULL and ignore it.
  *   davo_forward_depth          davo_forward           + depth (host pointer)     DAVO.inference, davo.py:1553-1569
@@ -213,6 +219,9 @@ int davo_get_pairs(const davo_ctx* ctx);
  *                                  lo = out >> 2, lerp = (out & 3) / 4, hi = min(lo + 1, last); per value in float32, in TF's order
  *                                  top = tl + (tr - tl) xl, bot = bl + (br - bl) xl, out = top + (bot - top) yl.  The corners are the
  *                                  stored cnv6 as davo_debug_read("cnv6") decodes it, so out[4i][4j] equals it to the bit.
+ * att_source 13 (the depth-split flow attention): `attention' is the per-pixel select of the near and the far table by the frame's own
+ * depth plane, `masked_image' the packer's expression with it; no single 19-row table was applied and the reference sets no att_19s
+ * for the branch (davo.py:1470), so a non-NULL att_19 member returns DAVO_ERR_INVALID before anything runs.
  * `flows' and `segs' of the reference's dict are colourings of the caller's own inputs (flow_to_image, label_to_color_image) and
  * are not built; `seg_19' is the one-hot of the caller's label maps and needs nothing from the device (davo_amd.DAVO builds it).
  *
@@ -519,7 +528,8 @@ int davo_comm_destroy(davo_ctx* ctx);
 int davo_set_impl(davo_ctx* ctx, int impl);
 
 /* Copy an intermediate of the LAST forward to host (float32, NHWC, pair-image major = 2B images):
- * "att_table" [B,3,19], "packed" [2B,H,W,8|10], "cnv1".."cnv5", "cnv6" [.., 2*cnv6_out]
+ * "att_table" [B,3,19] (att_source 13: the near MLP's tables; "att_table_far" [B,3,19] holds the far MLP's and returns
+ * DAVO_ERR_INVALID on every other variant), "packed" [2B,H,W,8|10], "cnv1".."cnv5", "cnv6" [.., 2*cnv6_out]
  * (rotation | translation), "cnv7" [.., 512].  With davo_set_posenn_se(ctx, 1) also "cnv5_se_scale" [2B,2,256] (row 0 = s_r,
  * row 1 = s_r * s_t) and "cnv5_se" [2B,H/4,W/4,512] (cnv6's rotation input | its translation input).  After a davo_forward_heat
  * with the heat export on also "heat_sum" [2,n,H/4,W/4]: the channel sums (rotation | translation) the planes of the piece exported

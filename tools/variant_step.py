@@ -10,6 +10,13 @@ DESIGN.md section 2 - does one pair of B windows run the launches of both pairs 
 
     python tools/variant_step.py --batch 32 --rounds 5 --pairs both src1 both@16 <version>
 
+`--stages N` adds the library's own event profile (Engine.profile(1)) behind the timed rounds: N forwards per version and round,
+the versions taken in forward order in even rounds and in reverse order in odd ones, so that whatever the card's clocks do while
+events bracket every launch falls on each version alike; the line then carries `stage_us` (mean us per launch and profile entry
+over the rounds) and `stage_us_per_round`.  The measurement of DESIGN.md section 2, "Depth-split flow attention", is
+
+    python tools/variant_step.py --precision f16x3 --batch 32 --rounds 6 --stages 20 <flagship> <-se_flow_on_depthseg_seplayers string>
+
 Under `rocprofv3 --kernel-trace --stats -- python3 tools/variant_step.py ...` it gives the per-kernel table of a variant."""
 import argparse
 import json
@@ -36,6 +43,8 @@ def main():
     ap.add_argument("--rounds", type=int, default=1)
     ap.add_argument("--pairs", nargs="+", default=None, metavar="ARM",
                     help="arms of (pair selection[@batch]): both | src0 | src1, e.g. --pairs both src1 both@16")
+    ap.add_argument("--stages", type=int, default=0, metavar="N",
+                    help="after the timed rounds, profile N forwards per version and round (alternating order): us per launch and profile entry")
     a = ap.parse_args()
     H, W = a.height, a.width
     arms = []
@@ -69,13 +78,28 @@ def main():
                 e.forward_device(B, *bufs, **kw)
             e.synchronize()
             ms.append((time.perf_counter() - t) * 1e3 / a.steps)
-    for v, e, bufs, ms, kw, sel, B in runs:
+    stages = [[] for _ in runs]                     # per run: one {entry: us per launch} per round
+    for rnd in range(a.rounds if a.stages > 0 else 0):
+        order = list(range(len(runs)))
+        for i in (order if rnd % 2 == 0 else order[::-1]):
+            v, e, bufs, ms, kw, sel, B = runs[i]
+            e.profile(1)
+            e.profile_reset()
+            for _ in range(a.stages):
+                e.forward_device(B, *bufs, **kw)
+            e.synchronize()
+            stages[i].append({k: 1e3 * total / n for k, (n, total) in e.profile_entries().items() if n > 0})
+            e.profile(0)
+    for (v, e, bufs, ms, kw, sel, B), st in zip(runs, stages):
         bufs = bufs + list(kw.values())
         pose = bufs[3].download((B, 2, 6))
         best = min(ms)
         line = {"version": v, "precision": a.precision, "batch": B, "height": H, "width": W, "steps": a.steps,
                 "ms_per_step": round(best, 4), "ms_per_round": [round(x, 4) for x in ms],
                 "triplets_per_s": round(B / best * 1e3, 1), "finite": bool(np.isfinite(pose).all())}
+        if st:
+            line.update(stage_us={k: round(sum(r[k] for r in st) / len(st), 2) for k in st[0]},
+                        stage_us_per_round=[{k: round(x, 2) for k, x in r.items()} for r in st])
         if a.pairs:
             line.update(pairs=sel, plan=[e.last_plan(l) for l in range(7)])
         print(json.dumps(line), flush=True)
