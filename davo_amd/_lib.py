@@ -46,11 +46,12 @@ EXPORTS = (
     "davo_host_alloc", "davo_host_free", "davo_host_register", "davo_host_unregister", "davo_calibrate", "davo_activation_range", "davo_set_activation_shifts", "davo_reset_range_state", "davo_range_stats", "davo_range_report",
     "davo_comm_preload", "davo_comm_unique_id", "davo_comm_init", "davo_comm_size", "davo_allgather_poses", "davo_allgather_poses_device",
     "davo_comm_allreduce", "davo_comm_barrier", "davo_comm_destroy", "davo_plan_layer", "davo_tile_filter_rows",
-    "davo_set_pairs", "davo_get_pairs",
+    "davo_set_pairs", "davo_get_pairs", "davo_set_label_format", "davo_get_label_format",
     "davo_set_feature_export", "davo_forward_features", "davo_set_heat_export", "davo_forward_heat",
     "davo_pad_class_tables", "davo_pad_class_tile_order", "davo_plan_layer_f32",
 )
 COMM_ID_BYTES = 128
+LABELS_F32, LABELS_U8 = 0, 1          # DAVO_LABELS_F32, DAVO_LABELS_U8 (davo_set_label_format)
 
 
 class DavoVariant(ctypes.Structure):
@@ -223,6 +224,8 @@ def _load():
     L.davo_set_impl.argtypes = [vp, i]
     L.davo_set_pairs.argtypes = [vp, i]
     L.davo_get_pairs.argtypes = [vp]
+    L.davo_set_label_format.argtypes = [vp, i]
+    L.davo_get_label_format.argtypes = [vp]
     L.davo_set_feature_export.argtypes = [vp, i]
     L.davo_forward_features.argtypes = [vp, i, vp, vp, vp, vp, vp, ctypes.POINTER(DavoFeatureOut)]
     L.davo_set_heat_export.argtypes = [vp, i]

@@ -165,6 +165,22 @@ int davo_set_posenn_se(davo_ctx* c, int mode) {
     return DAVO_OK;
 }
 
+int davo_set_label_format(davo_ctx* c, int fmt) {
+    if (!c) return DAVO_ERR_INVALID;
+    if (fmt != DAVO_LABELS_F32 && fmt != DAVO_LABELS_U8)
+        return fail(c, DAVO_ERR_INVALID, "label format must be DAVO_LABELS_F32 (0) or DAVO_LABELS_U8 (1), got %d", fmt);
+    // everything sized by plane_bytes() follows the format: it is fixed once inputs were taken or a set of them was allocated
+    bool sets = static_cast<bool>(c->host) || static_cast<bool>(c->snaps);
+    for (const InputSet& s : c->stream_sets) sets = sets || s.built();
+    if (c->inputs_seen || c->forward_seen || sets)
+        return fail(c, DAVO_ERR_INVALID, "davo_set_label_format must be called before the first call that takes inputs "
+                    "(the staging sets, the range guard's snapshots and every copy are sized by it)");
+    c->label_fmt = fmt;
+    return DAVO_OK;
+}
+
+int davo_get_label_format(const davo_ctx* c) { return c ? c->label_fmt : DAVO_ERR_INVALID; }
+
 int davo_load_weight(davo_ctx* c, const char* tf_name, const float* data, const int64_t* shape, int ndim) {
     // ndim 0: a scalar variable (the depth threshold); shape may then be null
     if (!c || !tf_name || !data || ndim < 0 || ndim > 4 || (!shape && ndim > 0)) return fail(c, DAVO_ERR_INVALID, "bad argument to davo_load_weight");
@@ -231,6 +247,7 @@ static int forward_device_entry(davo_ctx* c, int B, const void* d_img, const voi
     if (B < 1 || B > c->max_batch) return fail(c, DAVO_ERR_INVALID, "batch %d outside [1,%d]", B, c->max_batch);
     if (!d_img || !d_flow || !d_seg || !d_pose) return fail(c, DAVO_ERR_INVALID, "null device pointer");
     { int rc = resolve_depth(c, "davo_forward_device", depth_form, &d_depth); if (rc) return rc; }
+    c->inputs_seen = true;
     const Inputs in{d_img, d_flow, d_seg, d_depth};
     HIP_TRY(c, hipSetDevice(c->device));
     const bool ticketed = c->impl == 0 && c->precision == 1;      // f16x3: the batch gets a record (and a copy of its inputs) of its own
@@ -342,8 +359,9 @@ int stage_inputs(davo_ctx* c, const InputSet& set, const Inputs& host, int b0, i
         if (att_tgt_attended(c->v.att_source)) HIP_TRY(c, copy2d(dst(set.seg, n.seg), src.seg, n.seg, src1 ? plane : 0, 2 * plane, nb));
         else HIP_TRY(c, copy2d(dst(set.seg, n.seg), src.seg, n.seg, src1 ? 2 * plane : 0, plane, nb));
         // depth sources: the target's plane and the source's; the depth-split attention reads the source frame's plane alone
-        if (src.depth && c->v.att_source == ATT_DEPTH_SPLIT) HIP_TRY(c, copy2d(dst(set.depth, n.depth), src.depth, n.depth, src1 ? 2 * plane : 0, plane, nb));
-        else if (src.depth) HIP_TRY(c, copy2d(dst(set.depth, n.depth), src.depth, n.depth, src1 ? plane : 0, 2 * plane, nb));
+        const size_t dplane = n.depth / 3;                     // (float32 whatever the label format)
+        if (src.depth && c->v.att_source == ATT_DEPTH_SPLIT) HIP_TRY(c, copy2d(dst(set.depth, n.depth), src.depth, n.depth, src1 ? 2 * dplane : 0, dplane, nb));
+        else if (src.depth) HIP_TRY(c, copy2d(dst(set.depth, n.depth), src.depth, n.depth, src1 ? dplane : 0, 2 * dplane, nb));
         return DAVO_OK;
     }
     HIP_TRY(c, hipMemcpyAsync(dst(set.img, n.img), src.img, n.img * nb, hipMemcpyHostToDevice, s));
@@ -396,6 +414,7 @@ static int submit_entry(davo_ctx* c, int B, const uint8_t* img, const float* flo
     { int rc = resolve_depth(c, "davo_submit", depth_form, &depth); if (rc) return rc; }
     if (B < 1 || B > c->max_batch) return fail(c, DAVO_ERR_INVALID, "batch %d outside [1,%d]", B, c->max_batch);
     if (hold < 0) return fail(c, DAVO_ERR_INVALID, "hold must be >= 0");
+    c->inputs_seen = true;
     HIP_TRY(c, hipSetDevice(c->device));
     // deliver what has finished (never blocks), and make room in the pose ring (blocks on the oldest batch only when the ring is full)
     while (!c->jobs.empty() && ((int)c->jobs.size() >= STREAM_POSES || hipEventQuery(c->pose_ring->e[c->jobs.front().pr].pose_done.get()) == hipSuccess)) {
@@ -508,7 +527,7 @@ int export_features(davo_ctx* c, const Inputs& in, int w0, int nw, int b0, int B
         float* const w_trans = out.feat_trans ? d_fx + l.trans : nullptr;
         if (w_att19 || w_att || w_masked || w_image) {
             ProfScope ps(c, s, "feature_maps");
-            HIP_TRY(c, launch_feature_maps(static_cast<const uint8_t*>(win.img), static_cast<const float*>(win.seg),
+            HIP_TRY(c, launch_feature_maps(static_cast<const uint8_t*>(win.img), win.seg, c->label_fmt,
                                            ws.d_tab.get() + (size_t)(w0 + p0) * 3 * NCLS, c->v, np, c->H, c->W, w_att19, w_att, w_masked, w_image, s,
                                            static_cast<const float*>(win.depth), ws.d_tab_far ? ws.d_tab_far.get() + (size_t)(w0 + p0) * 3 * NCLS : nullptr, c->depth_thr));
         }
@@ -617,6 +636,7 @@ static int forward_entry(davo_ctx* c, int B, const uint8_t* img, const float* fl
     const void* depth = depth_in;
     { int rc = resolve_depth(c, "davo_forward", depth_form, &depth); if (rc) return rc; }
     if (B < 1 || B > c->max_batch) return fail(c, DAVO_ERR_INVALID, "batch %d outside [1,%d]", B, c->max_batch);
+    c->inputs_seen = true;
     HIP_TRY(c, hipSetDevice(c->device));
     { int rc = deliver_all(c); if (rc) return rc; }          // davo_submit batches still under way: delivered first
     { int rc = sync_all_slots(c); if (rc) return rc; }       // the host path owns the single staging buffer set
@@ -826,6 +846,7 @@ static int calibrate_entry(davo_ctx* c, int B, const void* d_img, const void* d_
     if (B < 1 || B > c->max_batch) return fail(c, DAVO_ERR_INVALID, "batch %d outside [1,%d]", B, c->max_batch);
     if (!d_img || !d_flow || !d_seg) return fail(c, DAVO_ERR_INVALID, "null device pointer");
     { int rc = resolve_depth(c, "davo_calibrate", depth_form, &d_depth); if (rc) return rc; }
+    c->inputs_seen = true;
     HIP_TRY(c, hipSetDevice(c->device));
     { int rc = judge_all(c); if (rc) return rc; }             // batches issued under the old scales get their verdict first
     { int rc = freeze_pending_and_reset_ring(c); if (rc) return rc; }
@@ -1100,7 +1121,7 @@ int davo_debug_read(davo_ctx* c, const char* tensor, float* host_out, size_t n_f
     else if (t == "packed") {
         if (!c->packed_valid) {          // fused path: materialise the packed tensor on demand from the last inputs
             HIP_TRY(c, launch_mask_pack(16, static_cast<const uint8_t*>(c->last_in.img), static_cast<const float*>(c->last_in.flow),
-                                        static_cast<const float*>(c->last_in.seg), ws.d_tab.get(), c->v, c->last_B, c->H, c->W, ws.d_packed.get(), c->last_pairs, last_stream(c)));
+                                        c->last_in.seg, c->label_fmt, ws.d_tab.get(), c->v, c->last_B, c->H, c->W, ws.d_packed.get(), c->last_pairs, last_stream(c)));
             c->packed_valid = true;
         }
         src = ws.d_packed.get(); n = NB * c->H * c->W * c->packed_ld;

@@ -94,7 +94,8 @@ __device__ __forceinline__ void split_pair_relu(float x0, float x1, float scale,
 // Persistent form: the grid is 3 workgroups per CU; each loads the 28 KB of B fragments into registers
 // once and then walks its share of the output tiles (tile t, t + gridDim.x, ...), re-filling only the
 // 42 KB input patch per tile.  The co-resident workgroups overlap each other's fill / matrix / store phases.
-template <bool FUSED>
+// LT (FUSED only): the label format the fused fill reads, float32 or bytes (input_decode.h).
+template <bool FUSED, typename LT = float>
 __global__ __launch_bounds__(cp1::THREADS, 3) void conv_patch_cnv1_h3(ConvPatchParams p) {
     using namespace cp1;
     extern __shared__ __attribute__((aligned(16))) uint8_t smem_p[];
@@ -147,6 +148,7 @@ __global__ __launch_bounds__(cp1::THREADS, 3) void conv_patch_cnv1_h3(ConvPatchP
             const size_t HW = (size_t)p.H * p.W;
             const float* tab_s = p.tab + ((size_t)b * 3 + 1 + s) * NCLS;
             const float* tab_t = p.tab + (size_t)b * 3 * NCLS;
+            const LT* seg = static_cast<const LT*>(p.seg);
             // PW + 1 columns: unit (parity 1, px2 = 18) is read by the zero-weight dummy tap kx = 7 of
             // the last output column and must hold finite data (0 x NaN would poison the sum)
             constexpr int PWF = PW + 1;
@@ -160,8 +162,8 @@ __global__ __launch_bounds__(cp1::THREADS, 3) void conv_patch_cnv1_h3(ConvPatchP
                     const uint8_t* ps = row + (size_t)((s ? 2 * p.W : 0) + ix) * 3;
                     const size_t pix = (size_t)iy * p.W + ix;
                     float as = 1.f, at = 1.f;
-                    if (v.att_source != 0) as = att_lookup(tab_s, p.seg[((size_t)b * 3 + (s ? 2 : 0)) * HW + pix]);
-                    if (att_tgt_attended(v.att_source)) at = att_lookup(tab_t, p.seg[((size_t)b * 3 + 1) * HW + pix]);
+                    if (v.att_source != 0) as = att_lookup(tab_s, seg[((size_t)b * 3 + (s ? 2 : 0)) * HW + pix]);
+                    if (att_tgt_attended(v.att_source)) at = att_lookup(tab_t, seg[((size_t)b * 3 + 1) * HW + pix]);
                     r[0] = u8_to_unit(pt[0]); r[1] = u8_to_unit(pt[1]); r[2] = u8_to_unit(pt[2]);
                     r[3] = u8_to_unit(ps[0]); r[4] = u8_to_unit(ps[1]); r[5] = u8_to_unit(ps[2]);
                     if (v.mask_rgb) {

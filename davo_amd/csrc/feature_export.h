@@ -38,8 +38,9 @@ struct FeatureMapsOut {          // device pointers of one piece of nw windows; 
 // DSPLIT (att_source 13): a source frame's map is mask_pack_depthsplit's select - the frame's own depth plane against the threshold
 // chooses the near table `tab' or the far table `ds.tab_far' per pixel (input_decode.h); depth points at the piece's first window
 // like img and seg.  No single 19-row table was applied there (the reference sets no att_19s, davo.py:1470): o.att_19 is null.
-template <bool DSPLIT>
-__device__ __forceinline__ void feature_maps_body(const uint8_t* __restrict__ img, const float* __restrict__ seg,
+// LT: the label format, float32 or bytes (input_decode.h).
+template <bool DSPLIT, typename LT>
+__device__ __forceinline__ void feature_maps_body(const uint8_t* __restrict__ img, const LT* __restrict__ seg,
                                                   const float* __restrict__ tab, const Variant& v, int nw, int H, int W, const FeatureMapsOut& o,
                                                   const DepthSplit& ds) {
     const int W4 = W >> 2;
@@ -62,16 +63,16 @@ __device__ __forceinline__ void feature_maps_body(const uint8_t* __restrict__ im
         const int slot = frame == 0 ? 1 : frame == 1 ? 0 : 2;
         float a[4] = {1.f, 1.f, 1.f, 1.f};
         if (feature_frame_looked_up(v.att_source, frame)) {
-            const float4 sg = *reinterpret_cast<const float4*>(seg + ((size_t)b * 3 + slot) * HW + pix);
+            const LabelIds4 sg = label_fetch4(seg + ((size_t)b * 3 + slot) * HW, pix);
             const float* tab_f = tab + ((size_t)b * 3 + frame) * NCLS;
             if (DSPLIT) {
                 const float4 dp = *reinterpret_cast<const float4*>(ds.depth + ((size_t)b * 3 + slot) * HW + pix);
                 const float* far_f = ds.tab_far + ((size_t)b * 3 + frame) * NCLS;
-                a[0] = att_lookup_split(tab_f, far_f, ds.thr, dp.x, sg.x); a[1] = att_lookup_split(tab_f, far_f, ds.thr, dp.y, sg.y);
-                a[2] = att_lookup_split(tab_f, far_f, ds.thr, dp.z, sg.z); a[3] = att_lookup_split(tab_f, far_f, ds.thr, dp.w, sg.w);
+                a[0] = att_lookup_split(tab_f, far_f, ds.thr, dp.x, sg.id[0]); a[1] = att_lookup_split(tab_f, far_f, ds.thr, dp.y, sg.id[1]);
+                a[2] = att_lookup_split(tab_f, far_f, ds.thr, dp.z, sg.id[2]); a[3] = att_lookup_split(tab_f, far_f, ds.thr, dp.w, sg.id[3]);
             } else {
-                a[0] = att_lookup(tab_f, sg.x); a[1] = att_lookup(tab_f, sg.y);
-                a[2] = att_lookup(tab_f, sg.z); a[3] = att_lookup(tab_f, sg.w);
+                a[0] = att_lookup_id(tab_f, sg.id[0]); a[1] = att_lookup_id(tab_f, sg.id[1]);
+                a[2] = att_lookup_id(tab_f, sg.id[2]); a[3] = att_lookup_id(tab_f, sg.id[3]);
             }
         }
         const size_t at = ((size_t)frame * nw + b) * HW + pix;
@@ -100,12 +101,14 @@ __device__ __forceinline__ void feature_maps_body(const uint8_t* __restrict__ im
     }
 }
 
-__global__ __launch_bounds__(256) void feature_maps(const uint8_t* __restrict__ img, const float* __restrict__ seg,
+template <typename LT>
+__global__ __launch_bounds__(256) void feature_maps(const uint8_t* __restrict__ img, const LT* __restrict__ seg,
                                                     const float* __restrict__ tab, Variant v, int nw, int H, int W, FeatureMapsOut o) {
     feature_maps_body<false>(img, seg, tab, v, nw, H, W, o, DepthSplit{});
 }
 
-__global__ __launch_bounds__(256) void feature_maps_depthsplit(const uint8_t* __restrict__ img, const float* __restrict__ seg,
+template <typename LT>
+__global__ __launch_bounds__(256) void feature_maps_depthsplit(const uint8_t* __restrict__ img, const LT* __restrict__ seg,
                                                                const float* __restrict__ tab, Variant v, int nw, int H, int W, FeatureMapsOut o,
                                                                DepthSplit ds) {
     feature_maps_body<true>(img, seg, tab, v, nw, H, W, o, ds);

@@ -9,17 +9,38 @@
 
 namespace davo {
 
-__device__ __forceinline__ float att_lookup(const float* tab19, float seg) {
-    // tf.cast(float -> int32) truncates toward zero; one_hot of an out-of-range id is a zero row.  NaN / inf /
-    // beyond-int32 labels are platform-defined in the cast (x86: INT_MIN, GPUs: 0 or saturation) and pinned to
-    // "no class" here: only finite values in (-1, 19) select a row (the comparison is false for NaN).
-    return (seg > -1.0f && seg < (float)NCLS) ? tab19[(int)seg] : 0.f;
+// A label is a class id per pixel, in one of the two formats of davo_set_label_format (include/davo_hip.h): the reference's float32
+// or a byte.  label_id: the class a label selects, -1 for "no class".
+//   float32: tf.cast(float -> int32) truncates toward zero; one_hot of an out-of-range id is a zero row.  NaN / inf /
+//            beyond-int32 labels are platform-defined in the cast (x86: INT_MIN, GPUs: 0 or saturation) and pinned to
+//            "no class" here: only finite values in (-1, 19) select a row (the comparison is false for NaN).
+//   byte:    that rule folded into a byte by the host (davo_amd.labels_to_u8): L < 19 selects row L, 19..255 none (Cityscapes' 255
+//            among them).
+__device__ __forceinline__ int label_id(float seg) { return (seg > -1.0f && seg < (float)NCLS) ? (int)seg : -1; }
+__device__ __forceinline__ int label_id(uint8_t L) { return L < NCLS ? (int)L : -1; }
+
+__device__ __forceinline__ float att_lookup_id(const float* tab19, int id) { return id >= 0 ? tab19[id] : 0.f; }
+template <typename LT>
+__device__ __forceinline__ float att_lookup(const float* tab19, LT label) { return att_lookup_id(tab19, label_id(label)); }
+
+// The label fetch of a 4-pixel unit (mask_pack, se_class_squeeze, feature_maps: a thread's four horizontally adjacent pixels): the
+// class ids of pixels pix .. pix + 3 of one label plane.  float32: one 16-byte load; bytes: one 32-bit load.  `plane' is the
+// frame's [H][W] plane and pix a multiple of 4, so the load is naturally aligned wherever the labels' base is 16-byte aligned: a
+// byte plane holds H W bytes, W a multiple of 4 and H W a multiple of 16 (davo_create), float32 planes four times that.
+struct LabelIds4 { int id[4]; };
+__device__ __forceinline__ LabelIds4 label_fetch4(const float* __restrict__ plane, size_t pix) {
+    const float4 q = *reinterpret_cast<const float4*>(plane + pix);
+    return LabelIds4{{label_id(q.x), label_id(q.y), label_id(q.z), label_id(q.w)}};
+}
+__device__ __forceinline__ LabelIds4 label_fetch4(const uint8_t* __restrict__ plane, size_t pix) {
+    const uint32_t q = *reinterpret_cast<const uint32_t*>(plane + pix);
+    return LabelIds4{{label_id((uint8_t)q), label_id((uint8_t)(q >> 8)), label_id((uint8_t)(q >> 16)), label_id((uint8_t)(q >> 24))}};
 }
 
 // Depth-split attention (att_source 13, davo.py:1143-1155): near = depth < thr in float32, strict; tf.where sends a NaN depth (the
 // comparison is false) to the far side.  The pixel's class is looked up in the chosen table by att_lookup's rule.
-__device__ __forceinline__ float att_lookup_split(const float* near19, const float* far19, float thr, float depth, float seg) {
-    return att_lookup(depth < thr ? near19 : far19, seg);
+__device__ __forceinline__ float att_lookup_split(const float* near19, const float* far19, float thr, float depth, int id) {
+    return att_lookup_id(depth < thr ? near19 : far19, id);
 }
 
 // what the depth-split forms of mask_pack (prologue.h) and feature_maps (feature_export.h) take beside the near tables
@@ -28,6 +49,8 @@ struct DepthSplit {
     const float* tab_far;        // [B][3][19]
     float thr;                   // depth_threshold, the host's copy of the loaded scalar
 };
+// The label maps have the same planes in the context's label format, [B][3 file planes: src0, tgt, src1][H][W] float32 or uint8,
+// and the same requirement: a 16-byte aligned base (then every unit's load above is aligned, in either format).
 
 __device__ __forceinline__ float u8_to_unit(uint32_t byte) {
     return (float)byte * (1.0f / 255.0f) * 2.0f - 1.0f;        // davo.py:1521-1522

@@ -58,8 +58,9 @@ hipError_t launch_se_squeeze_excite_split(const float* d_flow, int B, int HW, co
                                           const float* const near_w[4], const float* const far_w[4], float* d_tab, float* d_tab_far,
                                           unsigned* d_range_reset, int sel, hipStream_t s);
 // segmentation / rgb / seg+flow class-table sources (att_source 4..10): per-frame descriptor records into d_partial (max_batch x 3 x SQ_CHUNKS x SQ_REC words);
-// fold: the triplet's last workgroup evaluates its tables too (d_counters as above), otherwise launch_se_excite follows
-hipError_t launch_se_class_squeeze(bool fold, const uint8_t* d_img, const float* d_flow, const float* d_seg, int B, int H, int W,
+// fold: the triplet's last workgroup evaluates its tables too (d_counters as above), otherwise launch_se_excite follows.
+// d_seg / label_fmt (here and below): the label maps in the format LABELS_F32 or LABELS_U8 (params.h); any other value is an error
+hipError_t launch_se_class_squeeze(bool fold, const uint8_t* d_img, const float* d_flow, const void* d_seg, int label_fmt, int B, int H, int W,
                                   const Variant& v, unsigned* d_partial, unsigned* d_counters, const float* w1, const float* b1,
                                   const float* w2, const float* b2, float* d_tab, unsigned* d_range_reset, int sel, hipStream_t s);
 // depth sources (att_source 11, 12): one float32 sum per (triplet, frame, chunk) into word 0 of the same records; d_depth is
@@ -70,12 +71,12 @@ hipError_t launch_se_depth_squeeze(bool fold, const float* d_depth, int B, int H
 // ld: 16 = split-fp16 8-channel layout (f16x3), 8 = float32 8-channel, 10 = the reference's 10-channel layout
 // att_source 13 (the depth-split flow attention) runs the depth-split form: d_depth (16-byte aligned), the far tables and the threshold are
 // required there and ignored everywhere else
-hipError_t launch_mask_pack(int ld, const uint8_t* d_img, const float* d_flow, const float* d_seg, const float* d_tab,
+hipError_t launch_mask_pack(int ld, const uint8_t* d_img, const float* d_flow, const void* d_seg, int label_fmt, const float* d_tab,
                             const Variant& v, int B, int H, int W, float* d_packed, int sel, hipStream_t s,
                             const float* d_depth = nullptr, const float* d_tab_far = nullptr, float depth_thr = 0.f);
 // cnv1 / cnv2 / cnv3 (layer 0..2) from an LDS-staged input patch: conv_patch_cnvN_h3, or conv_patch_cnvN_f32 in float32 mode (f32);
-// fused: conv_patch_cnv1_h3<true> (f16x3 cnv1 only)
-hipError_t launch_patch_layer(int layer, bool f32, bool fused, const ConvPatchParams& p, int nblk, hipStream_t s);
+// fused: conv_patch_cnv1_h3<true, float | uint8_t> by label_fmt (f16x3 cnv1 only; p.seg is in that format)
+hipError_t launch_patch_layer(int layer, bool f32, bool fused, const ConvPatchParams& p, int nblk, hipStream_t s, int label_fmt = LABELS_F32);
 // split-K fix-up: d_part [M][S][N] float32 partial sums -> the layer's stored activation (ReLU, fp16 hi/lo pairs, range monitor)
 hipError_t launch_splitk_fixup(const float* d_part, long M, int N, int S, int relu, uint8_t* d_y, unsigned* d_range, hipStream_t s);
 hipError_t launch_pose_from_tiles(const float* d_tiles, int NB, int P, int bm, int mtiles, int ntiles_n,
@@ -97,7 +98,7 @@ hipError_t launch_se5_scale(bool h3, const void* d_x, const float* d_scale, int 
 // ---- launch_feature.hip: the feature export (feature_export.h; davo_forward_features) -----------------------------
 // one piece of nw windows: d_img / d_seg / d_tab point at the piece's first window; outputs [3][nw][19], [3][nw][H][W], [3][nw][H][W][3] x 2,
 // frames in the order tgt, src0, src1; a null output is not written
-hipError_t launch_feature_maps(const uint8_t* d_img, const float* d_seg, const float* d_tab, const Variant& v, int nw, int H, int W,
+hipError_t launch_feature_maps(const uint8_t* d_img, const void* d_seg, int label_fmt, const float* d_tab, const Variant& v, int nw, int H, int W,
                                float* d_att_19, float* d_attention, float* d_masked, float* d_image, hipStream_t s,
                                const float* d_depth = nullptr, const float* d_tab_far = nullptr, float depth_thr = 0.f);      // att_source 13: as launch_mask_pack
 // d_cnv6: the whole stored cnv6 of a both-pairs forward (h3: f16x3 blocked, scaled by 1 / unscale; else float32 NHWC); windows

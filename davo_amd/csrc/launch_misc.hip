@@ -57,16 +57,28 @@ hipError_t launch_se_squeeze_excite_split(const float* d_flow, int B, int HW, co
     return hipGetLastError();
 }
 
-hipError_t launch_se_class_squeeze(bool fold, const uint8_t* d_img, const float* d_flow, const float* d_seg, int B, int H, int W,
+namespace {
+template <typename LT>
+void se_class_squeeze_as(bool fold, const dim3& grid, hipStream_t s, const uint8_t* d_img, const float* d_flow, const void* d_seg, int H, int W,
+                         const Variant& v, unsigned* d_partial, unsigned* d_counters, const float* w1, const float* b1,
+                         const float* w2, const float* b2, float* d_tab, unsigned* d_range_reset, int sel) {
+    const LT* seg = static_cast<const LT*>(d_seg);
+    if (fold)
+        hipLaunchKernelGGL((se_class_squeeze<true, LT>), grid, dim3(256), 0, s, d_img, d_flow, seg, H, W, v, d_partial, d_counters,
+                           w1, b1, w2, b2, d_tab, d_range_reset, sel);
+    else
+        hipLaunchKernelGGL((se_class_squeeze<false, LT>), grid, dim3(256), 0, s, d_img, d_flow, seg, H, W, v, d_partial, d_counters,
+                           w1, b1, w2, b2, d_tab, d_range_reset, sel);
+}
+}  // namespace
+
+hipError_t launch_se_class_squeeze(bool fold, const uint8_t* d_img, const float* d_flow, const void* d_seg, int label_fmt, int B, int H, int W,
                                   const Variant& v, unsigned* d_partial, unsigned* d_counters, const float* w1, const float* b1,
                                   const float* w2, const float* b2, float* d_tab, unsigned* d_range_reset, int sel, hipStream_t s) {
     const dim3 grid(SQ_CHUNKS, att_se_frames(v.att_source) - (sel == PAIRS_BOTH ? 0 : 1), B);
-    if (fold)
-        hipLaunchKernelGGL(se_class_squeeze<true>, grid, dim3(256), 0, s, d_img, d_flow, d_seg, H, W, v, d_partial, d_counters,
-                           w1, b1, w2, b2, d_tab, d_range_reset, sel);
-    else
-        hipLaunchKernelGGL(se_class_squeeze<false>, grid, dim3(256), 0, s, d_img, d_flow, d_seg, H, W, v, d_partial, d_counters,
-                           w1, b1, w2, b2, d_tab, d_range_reset, sel);
+    if (label_fmt == LABELS_F32) se_class_squeeze_as<float>(fold, grid, s, d_img, d_flow, d_seg, H, W, v, d_partial, d_counters, w1, b1, w2, b2, d_tab, d_range_reset, sel);
+    else if (label_fmt == LABELS_U8) se_class_squeeze_as<uint8_t>(fold, grid, s, d_img, d_flow, d_seg, H, W, v, d_partial, d_counters, w1, b1, w2, b2, d_tab, d_range_reset, sel);
+    else return hipErrorInvalidValue;
     return hipGetLastError();
 }
 
@@ -84,31 +96,46 @@ hipError_t launch_se_depth_squeeze(bool fold, const float* d_depth, int B, int H
     return hipGetLastError();
 }
 
-hipError_t launch_mask_pack(int ld, const uint8_t* d_img, const float* d_flow, const float* d_seg, const float* d_tab,
+namespace {
+template <typename LT>
+hipError_t mask_pack_as(int ld, const dim3& grid, hipStream_t s, const uint8_t* d_img, const float* d_flow, const void* d_seg, const float* d_tab,
+                        const Variant& v, int B, int sel, int H, int W, float* d_packed, const DepthSplit* ds) {
+    const LT* seg = static_cast<const LT*>(d_seg);
+    if (ds) {
+        if (ld == 16) hipLaunchKernelGGL((mask_pack_depthsplit<16, LT>), grid, dim3(256), 0, s, d_img, d_flow, seg, d_tab, v, B, sel, H, W, d_packed, *ds);
+        else if (ld == 8) hipLaunchKernelGGL((mask_pack_depthsplit<8, LT>), grid, dim3(256), 0, s, d_img, d_flow, seg, d_tab, v, B, sel, H, W, d_packed, *ds);
+        else if (ld == 10) hipLaunchKernelGGL((mask_pack_depthsplit<10, LT>), grid, dim3(256), 0, s, d_img, d_flow, seg, d_tab, v, B, sel, H, W, d_packed, *ds);
+        else return hipErrorInvalidValue;
+        return hipGetLastError();
+    }
+    if (ld == 16) hipLaunchKernelGGL((mask_pack<16, LT>), grid, dim3(256), 0, s, d_img, d_flow, seg, d_tab, v, B, sel, H, W, d_packed);
+    else if (ld == 8) hipLaunchKernelGGL((mask_pack<8, LT>), grid, dim3(256), 0, s, d_img, d_flow, seg, d_tab, v, B, sel, H, W, d_packed);
+    else if (ld == 10) hipLaunchKernelGGL((mask_pack<10, LT>), grid, dim3(256), 0, s, d_img, d_flow, seg, d_tab, v, B, sel, H, W, d_packed);
+    else return hipErrorInvalidValue;
+    return hipGetLastError();
+}
+}  // namespace
+
+hipError_t launch_mask_pack(int ld, const uint8_t* d_img, const float* d_flow, const void* d_seg, int label_fmt, const float* d_tab,
                             const Variant& v, int B, int H, int W, float* d_packed, int sel, hipStream_t s,
                             const float* d_depth, const float* d_tab_far, float depth_thr) {
     const long nthreads = (long)pairs_per_window(sel) * B * H * (W / 4);
     const dim3 grid((unsigned)((nthreads + 255) / 256));
-    if (v.att_source == ATT_DEPTH_SPLIT) {             // the depth-split form: a missing plane or table is an error, never the plain packer
-        if (!d_depth || ((uintptr_t)d_depth & 15) || !d_tab_far) return hipErrorInvalidValue;
-        const DepthSplit ds{d_depth, d_tab_far, depth_thr};
-        if (ld == 16) hipLaunchKernelGGL(mask_pack_depthsplit<16>, grid, dim3(256), 0, s, d_img, d_flow, d_seg, d_tab, v, B, sel, H, W, d_packed, ds);
-        else if (ld == 8) hipLaunchKernelGGL(mask_pack_depthsplit<8>, grid, dim3(256), 0, s, d_img, d_flow, d_seg, d_tab, v, B, sel, H, W, d_packed, ds);
-        else if (ld == 10) hipLaunchKernelGGL(mask_pack_depthsplit<10>, grid, dim3(256), 0, s, d_img, d_flow, d_seg, d_tab, v, B, sel, H, W, d_packed, ds);
-        else return hipErrorInvalidValue;
-        return hipGetLastError();
-    }
-    if (ld == 16) hipLaunchKernelGGL(mask_pack<16>, grid, dim3(256), 0, s, d_img, d_flow, d_seg, d_tab, v, B, sel, H, W, d_packed);
-    else if (ld == 8) hipLaunchKernelGGL(mask_pack<8>, grid, dim3(256), 0, s, d_img, d_flow, d_seg, d_tab, v, B, sel, H, W, d_packed);
-    else if (ld == 10) hipLaunchKernelGGL(mask_pack<10>, grid, dim3(256), 0, s, d_img, d_flow, d_seg, d_tab, v, B, sel, H, W, d_packed);
-    else return hipErrorInvalidValue;
-    return hipGetLastError();
+    const bool split = v.att_source == ATT_DEPTH_SPLIT;
+    // the depth-split form: a missing plane or table is an error, never the plain packer
+    if (split && (!d_depth || ((uintptr_t)d_depth & 15) || !d_tab_far)) return hipErrorInvalidValue;
+    const DepthSplit ds{d_depth, d_tab_far, depth_thr};
+    if (label_fmt == LABELS_F32) return mask_pack_as<float>(ld, grid, s, d_img, d_flow, d_seg, d_tab, v, B, sel, H, W, d_packed, split ? &ds : nullptr);
+    if (label_fmt == LABELS_U8) return mask_pack_as<uint8_t>(ld, grid, s, d_img, d_flow, d_seg, d_tab, v, B, sel, H, W, d_packed, split ? &ds : nullptr);
+    return hipErrorInvalidValue;
 }
 
-hipError_t launch_patch_layer(int layer, bool f32, bool fused, const ConvPatchParams& p, int nblk, hipStream_t s) {
+hipError_t launch_patch_layer(int layer, bool f32, bool fused, const ConvPatchParams& p, int nblk, hipStream_t s, int label_fmt) {
     using Kernel = void (*)(ConvPatchParams);
     struct Row { Kernel h3, f32; int threads, lds; };
-    static const Kernel cnv1_fused = conv_patch_cnv1_h3<true>;
+    if (label_fmt != LABELS_F32 && label_fmt != LABELS_U8) return hipErrorInvalidValue;
+    static const Kernel cnv1_fused_f32 = conv_patch_cnv1_h3<true, float>, cnv1_fused_u8 = conv_patch_cnv1_h3<true, uint8_t>;
+    const Kernel cnv1_fused = label_fmt == LABELS_U8 ? cnv1_fused_u8 : cnv1_fused_f32;
     static const Row rows[3] = {{conv_patch_cnv1_h3<false>, conv_patch_cnv1_f32, cp1::THREADS, cp1::LDS_BYTES},
                                 {conv_patch_cnv2_h3, conv_patch_cnv2_f32, cp2::THREADS, cp2::LDS_BYTES},
                                 {conv_patch_cnv3_h3, conv_patch_cnv3_f32, cp3::THREADS, cp3::LDS_BYTES}};

@@ -54,6 +54,11 @@ __host__ __device__ inline int att_se_hidden(int a) { return (a == 4 || a == 7 |
 // every plane once, the target's included: its sum enters both source frames' descriptors (davo.py:1109)
 __host__ __device__ inline int att_se_frames(int a) { return (att_tgt_attended(a) || att_desc_depth(a)) ? 3 : 2; }
 
+// ---- label format (davo_set_label_format, include/davo_hip.h) ----------------------------------------------------------------
+// What the label maps of a context are made of: the reference's float32 (the default) or one byte per pixel.  The kernels that read
+// labels are templated on the element type (input_decode.h); the launchers take the format and pick the instantiation.
+constexpr int LABELS_F32 = 0, LABELS_U8 = 1;
+
 // ---- pair selection (davo_set_pairs, include/davo_hip.h) -------------------------------------------------------------------
 // A window's two poses come from two independent evaluations of the PoseNN (davo.py:1456-1457): pair 0 = (tgt, src0), pair 1 =
 // (tgt, src1).  sel 3 runs both: pair image n is pair n & 1 of window n >> 1.  sel 1 / 2 runs pair 0 / 1 alone: pair image n is
@@ -311,7 +316,7 @@ struct ConvPatchParams {
     // is never materialised): davo.py:1519-1522 (u8 -> f32), :1115,1178 (LUT attention), :1404-1442
     const uint8_t* img;     // u8 [B][H][3W][3]
     const float* flow;      // [B][4][H][W][2]
-    const float* seg;       // [B][3][H][W][1]
+    const void* seg;        // [B][3][H][W][1] float32, or bytes in the kernel's byte-label instantiation (input_decode.h)
     const float* tab;       // [B][3][19] attention tables (se_excite)
     Variant v;
     int sel;                // pair selection of the batch (PAIRS_*): pair image n -> (window, source frame)
@@ -360,9 +365,10 @@ struct SnapArgs {
     uint8_t *s_img, *s_flow, *s_seg;        // the ring slot's
     unsigned img_vec, flow_vec_half, flow_vec, seg_vec;      // per window, in 16-byte units: strip, flow planes 0-1, whole flow block, seg
     int B;
-    const uint8_t* depth;                   // depth sources only (else null): the caller's depth planes, seg_vec units per window ...
+    const uint8_t* depth;                   // depth sources only (else null): the caller's depth planes, depth_vec units per window ...
     uint8_t* s_depth;                       // ... and the ring slot's copy of them
     int se;                                 // feature-attention variant: record[RANGE_SE] is part of the verdict and of the mirror
+    unsigned depth_vec;                     // 16-byte units of a window's depth planes (float32 always; seg_vec follows the label format)
 };
 
 }  // namespace davo

@@ -287,14 +287,15 @@ __global__ __launch_bounds__(256) void se_squeeze_excite_split(const float* __re
 //                      counts in no bin but in the HW denominator, davo.py:1115), SegFlow: [19, 21) float sums of the SE-transformed
 //                      flow (src frames; the target's flow is zeros and has no sums);
 //   rgb sources:       [0, 3) sums of the frame's u8 channel bytes.
-// A thread takes 4 horizontally adjacent pixels per step (one float4 of labels, 12 strip bytes, two float4 of flow).  Label counts:
+// A thread takes 4 horizontally adjacent pixels per step (one label_fetch4 - a float4 of labels, or four bytes in the byte
+// format LT = uint8_t, input_decode.h - 12 strip bytes, two float4 of flow).  Label counts:
 // per class one 64-bit ballot per pixel slot and a scalar popcount - wave-uniform sums with no LDS atomics on a hot bin (the labels
 // come in 8x8 blocks of one class).  The loop's trip count is uniform, so every lane sees every ballot.  The counts and byte sums
 // are exact integers and the flow sums use a fixed tree: bitwise reproducible.  FOLD: the workgroup that delivers the triplet's
 // last record evaluates its three tables (se_squeeze_excite's protocol, pose_tail.h).
-template <bool FOLD>
+template <bool FOLD, typename LT>
 __global__ __launch_bounds__(256) void se_class_squeeze(const uint8_t* __restrict__ img, const float* __restrict__ flow,
-                                                        const float* __restrict__ seg, int H, int W, Variant v,
+                                                        const LT* __restrict__ seg, int H, int W, Variant v,
                                                         unsigned* __restrict__ partial, unsigned* __restrict__ counters,
                                                         const float* __restrict__ w1, const float* __restrict__ b1,
                                                         const float* __restrict__ w2, const float* __restrict__ b2,
@@ -313,7 +314,7 @@ __global__ __launch_bounds__(256) void se_class_squeeze(const uint8_t* __restric
     // strip slot / seg file plane of the frame: (tgt, src0, src1) -> strip src0|tgt|src1 (data_loader.py:537-557), seg file
     // order src0, tgt, src1 (davo.py:998-1004)
     const int slot = frame == 0 ? 1 : frame == 1 ? 0 : 2;
-    const float4* lab = reinterpret_cast<const float4*>(seg + ((size_t)b * 3 + slot) * HW);
+    const LT* lab = seg + ((size_t)b * 3 + slot) * HW;         // LT: the label format, float32 or bytes (input_decode.h)
     const float4* fv = reinterpret_cast<const float4*>(flow + ((size_t)b * 4 + (frame >= 1 ? frame - 1 : 0)) * HW * 2);
     unsigned cnt[NCLS];
 #pragma unroll
@@ -324,13 +325,8 @@ __global__ __launch_bounds__(256) void se_class_squeeze(const uint8_t* __restric
         const int i = base + threadIdx.x;
         const bool ok = i < end;
         if (hist) {
-            int id[4] = {-1, -1, -1, -1};
-            if (ok) {
-                const float4 q = lab[i];
-                const float l[4] = {q.x, q.y, q.z, q.w};
-#pragma unroll
-                for (int k = 0; k < 4; ++k) id[k] = (l[k] > -1.0f && l[k] < (float)NCLS) ? (int)l[k] : -1;
-            }
+            const LabelIds4 q = ok ? label_fetch4(lab, (size_t)i << 2) : LabelIds4{{-1, -1, -1, -1}};
+            const int* id = q.id;
 #pragma unroll
             for (int c = 0; c < NCLS; ++c)
                 cnt[c] += (unsigned)(__popcll(__ballot(id[0] == c)) + __popcll(__ballot(id[1] == c)) +
@@ -451,12 +447,13 @@ __global__ __launch_bounds__(256) void se_depth_squeeze(const float* __restrict_
 //                                      two identically-zero tgt-flow channels are dropped)
 //                            LD = 10: tgt rgb | 0 0 | src rgb*att | flow*att (reference layout)
 // v0 variants (rgb only) leave the flow slots zero.
+// LT: the label format, float32 or bytes; a thread's four labels of a plane come from one label_fetch4 (input_decode.h).
 // DSPLIT (att_source 13, the depth-split flow attention): per 4-pixel group one more float4, of the depth plane of the source frame
 // the label map belongs to (file plane 0 or 2), and each pixel's class is looked up in the near table `tab' or the far table
 // `ds.tab_far' by att_lookup_split (input_decode.h, with DepthSplit); everything else is the same code.  The target's map is ones.
-template <int LD, bool DSPLIT>
+template <int LD, bool DSPLIT, typename LT>
 __device__ __forceinline__ void mask_pack_body(const uint8_t* __restrict__ img, const float* __restrict__ flow,
-                                               const float* __restrict__ seg, const float* __restrict__ tab,
+                                               const LT* __restrict__ seg, const float* __restrict__ tab,
                                                const Variant& v, int B, int sel, int H, int W, float* __restrict__ out, const DepthSplit& ds) {
     const int W4 = W >> 2;
     const long total = (long)B * pairs_per_window(sel) * H * W4;
@@ -484,7 +481,7 @@ __device__ __forceinline__ void mask_pack_body(const uint8_t* __restrict__ img, 
                             (uint8_t)s2, (uint8_t)(s2 >> 8), (uint8_t)(s2 >> 16), (uint8_t)(s2 >> 24)};
 
     const size_t pix = (size_t)y * W + x;
-    const float4 sg = *reinterpret_cast<const float4*>(seg + ((size_t)b * 3 + (s ? 2 : 0)) * H * W + pix);
+    const LabelIds4 sg = label_fetch4(seg + ((size_t)b * 3 + (s ? 2 : 0)) * H * W, pix);
     const float* tab_s = tab + ((size_t)b * 3 + 1 + s) * NCLS;
     // tf.ones_like overrides are ones everywhere, ignore-label pixels included: every frame for
     // -no_segmask (davo.py:1387), the tgt frame unless static_all (davo.py:1394,1411).
@@ -492,18 +489,18 @@ __device__ __forceinline__ void mask_pack_body(const uint8_t* __restrict__ img, 
     if (DSPLIT) {
         const float4 dp = *reinterpret_cast<const float4*>(ds.depth + ((size_t)b * 3 + (s ? 2 : 0)) * H * W + pix);
         const float* far_s = ds.tab_far + ((size_t)b * 3 + 1 + s) * NCLS;
-        as[0] = att_lookup_split(tab_s, far_s, ds.thr, dp.x, sg.x); as[1] = att_lookup_split(tab_s, far_s, ds.thr, dp.y, sg.y);
-        as[2] = att_lookup_split(tab_s, far_s, ds.thr, dp.z, sg.z); as[3] = att_lookup_split(tab_s, far_s, ds.thr, dp.w, sg.w);
+        as[0] = att_lookup_split(tab_s, far_s, ds.thr, dp.x, sg.id[0]); as[1] = att_lookup_split(tab_s, far_s, ds.thr, dp.y, sg.id[1]);
+        as[2] = att_lookup_split(tab_s, far_s, ds.thr, dp.z, sg.id[2]); as[3] = att_lookup_split(tab_s, far_s, ds.thr, dp.w, sg.id[3]);
     } else if (v.att_source != 0) {
-        as[0] = att_lookup(tab_s, sg.x); as[1] = att_lookup(tab_s, sg.y);
-        as[2] = att_lookup(tab_s, sg.z); as[3] = att_lookup(tab_s, sg.w);
+        as[0] = att_lookup_id(tab_s, sg.id[0]); as[1] = att_lookup_id(tab_s, sg.id[1]);
+        as[2] = att_lookup_id(tab_s, sg.id[2]); as[3] = att_lookup_id(tab_s, sg.id[3]);
     }
     float at[4] = {1.f, 1.f, 1.f, 1.f};
     if (!DSPLIT && att_tgt_attended(v.att_source)) {                     // static_all / a with-target class table: tgt frame is masked too
-        const float4 tg = *reinterpret_cast<const float4*>(seg + ((size_t)b * 3 + 1) * H * W + pix);
+        const LabelIds4 tg = label_fetch4(seg + ((size_t)b * 3 + 1) * H * W, pix);
         const float* tab_t = tab + (size_t)b * 3 * NCLS;
-        at[0] = att_lookup(tab_t, tg.x); at[1] = att_lookup(tab_t, tg.y);
-        at[2] = att_lookup(tab_t, tg.z); at[3] = att_lookup(tab_t, tg.w);
+        at[0] = att_lookup_id(tab_t, tg.id[0]); at[1] = att_lookup_id(tab_t, tg.id[1]);
+        at[2] = att_lookup_id(tab_t, tg.id[2]); at[3] = att_lookup_id(tab_t, tg.id[3]);
     }
     float fl[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
     if (v.cin_per_frame == 5) {
@@ -568,16 +565,16 @@ __device__ __forceinline__ void mask_pack_body(const uint8_t* __restrict__ img, 
     }
 }
 
-template <int LD>
+template <int LD, typename LT>
 __global__ __launch_bounds__(256) void mask_pack(const uint8_t* __restrict__ img, const float* __restrict__ flow,
-                                                 const float* __restrict__ seg, const float* __restrict__ tab,
+                                                 const LT* __restrict__ seg, const float* __restrict__ tab,
                                                  Variant v, int B, int sel, int H, int W, float* __restrict__ out) {
     mask_pack_body<LD, false>(img, flow, seg, tab, v, B, sel, H, W, out, DepthSplit{});
 }
 
-template <int LD>
+template <int LD, typename LT>
 __global__ __launch_bounds__(256) void mask_pack_depthsplit(const uint8_t* __restrict__ img, const float* __restrict__ flow,
-                                                            const float* __restrict__ seg, const float* __restrict__ tab,
+                                                            const LT* __restrict__ seg, const float* __restrict__ tab,
                                                             Variant v, int B, int sel, int H, int W, float* __restrict__ out, DepthSplit ds) {
     mask_pack_body<LD, true>(img, flow, seg, tab, v, B, sel, H, W, out, ds);
 }
@@ -687,10 +684,11 @@ __device__ __forceinline__ void snapshot_inputs_if_range_fails(const SnapArgs& a
     const size_t n_img = (size_t)a.img_vec * a.B, n_seg = (size_t)a.seg_vec * a.B, n_flow = (size_t)a.flow_vec_half * a.B;
     for (size_t i = worker; i < n_img; i += nworkers) di[i] = si[i];
     for (size_t i = worker; i < n_seg; i += nworkers) ds[i] = ss[i];
-    if (a.s_depth) {                                           // depth sources: the planes are as large as the label maps
+    if (a.s_depth) {                                           // depth sources: float32 planes, whatever the label format
         const uint4* sd = reinterpret_cast<const uint4*>(a.depth);
         uint4* dd = reinterpret_cast<uint4*>(a.s_depth);
-        for (size_t i = worker; i < n_seg; i += nworkers) dd[i] = sd[i];
+        const size_t n_depth = (size_t)a.depth_vec * a.B;
+        for (size_t i = worker; i < n_depth; i += nworkers) dd[i] = sd[i];
     }
     for (size_t i = worker; i < n_flow; i += nworkers) {
         const size_t b = i / a.flow_vec_half, o = i - b * a.flow_vec_half;

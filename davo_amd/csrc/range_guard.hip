@@ -310,7 +310,7 @@ int ticket_begin(davo_ctx* c, Run* run, int B, const Inputs& in, Ticket* t, bool
     run->snap = SnapArgs{run->range, c->ring->h_range_dev + RANGE_WORDS * (1 + r), t->seq,
                        src(in.img), src(in.flow), src(in.seg), dst(keep.img), dst(keep.flow), dst(keep.seg),
                        (unsigned)(nb.img / 16), (unsigned)(nb.flow / 32), (unsigned)(nb.flow / 16), (unsigned)(nb.seg / 16), B,
-                       src(in.depth), dst(keep.depth), c->posenn_se};
+                       src(in.depth), dst(keep.depth), c->posenn_se, (unsigned)(nb.depth / 16)};
     return DAVO_OK;
 }
 

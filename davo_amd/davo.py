@@ -12,6 +12,7 @@ import ctypes
 import numpy as np
 
 from . import _lib
+from .labels import LABEL_DTYPES, LABEL_FORMATS, check_label_format, labels_to_u8  # noqa: F401
 from .version import ATT_SOURCE, NUM_SEG_CLASSES, parse_version, weight_shapes
 
 
@@ -75,6 +76,7 @@ class DeviceBuffer:
 
     def __init__(self, engine, nbytes):
         self.engine, self.nbytes = engine, int(nbytes)
+        self.dtype = None                                  # of the array uploaded last (Engine.forward_device checks the label maps' against its format)
         p = ctypes.c_void_p()
         engine._check(_lib.lib().davo_device_malloc(engine._ctx, self.nbytes, ctypes.byref(p)))
         self.ptr = p
@@ -82,6 +84,7 @@ class DeviceBuffer:
     def upload(self, arr):
         arr = np.ascontiguousarray(arr)
         assert arr.nbytes <= self.nbytes
+        self.dtype = arr.dtype
         self.engine._check(_lib.lib().davo_memcpy_h2d(self.engine._ctx, self.ptr, arr.ctypes.data_as(ctypes.c_void_p), arr.nbytes))
         return self
 
@@ -100,8 +103,12 @@ class DeviceBuffer:
 class Engine:
     """Thin object wrapper of one ``davo_ctx`` (one GPU, one host thread)."""
 
-    def __init__(self, cfg, img_height, img_width, max_batch, device=0):
+    def __init__(self, cfg, img_height, img_width, max_batch, device=0, labels="f32"):
+        """``labels``: the format of every label map this engine takes - "f32" (the reference's float32 [B,3,H,W,1], the default)
+        or "u8" (uint8 class ids, a quarter of the bytes; include/davo_hip.h: davo_set_label_format, davo_amd.labels_to_u8)."""
+        check_label_format(labels)
         self.cfg, self.H, self.W, self.max_batch, self.device = cfg, img_height, img_width, max_batch, device
+        self.labels = "f32"
         self._L = _lib.lib()
         self._ctx = ctypes.c_void_p()
         self.host_chunk = 8                       # davo_set_option "host_chunk" as last set through set_option (its default)
@@ -119,6 +126,31 @@ class Engine:
             except Exception:
                 self.close()
                 raise
+        if labels != "f32":
+            try:
+                self.set_label_format(labels)
+            except Exception:
+                self.close()
+                raise
+
+    def set_label_format(self, labels):
+        """Select the label format, "f32" or "u8" (include/davo_hip.h: davo_set_label_format): before the first call that takes
+        inputs, ValueError afterwards.  From then on every label array must have that dtype; nothing is converted silently."""
+        self._check(self._L.davo_set_label_format(self._ctx, LABEL_FORMATS[check_label_format(labels)]))
+        self.labels = labels
+
+    def _label_arg(self, seg):
+        """The label maps of a batch as the entry points take them: C-contiguous [B,3,H,W,1] of the engine's format.  A byte
+        array handed to a float32 engine, or anything but bytes to a byte engine, is a ValueError."""
+        is_u8 = np.asarray(seg).dtype == np.uint8
+        if self.labels == "u8":
+            if not is_u8:
+                raise ValueError("this engine takes uint8 label maps (labels='u8'), got dtype %s: convert with davo_amd.labels_to_u8" % np.asarray(seg).dtype)
+            seg = np.ascontiguousarray(seg)
+            return seg[..., None] if seg.ndim == 4 else seg
+        if is_u8:
+            raise ValueError("this engine takes float32 label maps (labels='f32'), got uint8: create it with labels='u8'")
+        return np.ascontiguousarray(seg, np.float32)
 
     def _check(self, rc):
         if rc != 0:
@@ -158,7 +190,7 @@ class Engine:
     def forward(self, img, flow, seg, depth=None):
         img = np.ascontiguousarray(img, np.uint8)
         flow = np.ascontiguousarray(flow, np.float32)
-        seg = np.ascontiguousarray(seg, np.float32)
+        seg = self._label_arg(seg)
         B = self._check_batch(img, flow, seg)
         depth = self._depth_arg(depth, B)
         out = np.empty((B, 2, 6), np.float32)
@@ -197,7 +229,7 @@ class Engine:
             raise ValueError("unknown feature output(s) %s: choose from %s" % (unknown, list(self.FEATURE_OUTPUTS)))
         img = np.ascontiguousarray(img, np.uint8)
         flow = np.ascontiguousarray(flow, np.float32)
-        seg = np.ascontiguousarray(seg, np.float32)
+        seg = self._label_arg(seg)
         B = self._check_batch(img, flow, seg)
         depth = self._depth_arg(depth, B)
         H, W, c6 = self.H, self.W, self.cfg.cnv6_out
@@ -236,12 +268,13 @@ class Engine:
         ``depth``: the depth planes of a depth-source variant (davo_submit_depth), held like the other inputs."""
         if not (isinstance(img, np.ndarray) and img.dtype == np.uint8 and img.flags.c_contiguous and
                 isinstance(flow, np.ndarray) and flow.dtype == np.float32 and flow.flags.c_contiguous and
-                isinstance(seg, np.ndarray) and seg.dtype == np.float32 and seg.flags.c_contiguous):
+                isinstance(seg, np.ndarray) and seg.dtype == LABEL_DTYPES[self.labels] and seg.flags.c_contiguous and seg.ndim == 5):
             if hold:
-                raise ValueError("submit(hold > 0) needs C-contiguous uint8 / float32 / float32 arrays (a converted copy would not outlive the call)")
+                raise ValueError("submit(hold > 0) needs C-contiguous uint8 / float32 / %s arrays (a converted copy would not outlive the call)"
+                                 % LABEL_DTYPES[self.labels])
             img = np.ascontiguousarray(img, np.uint8)
             flow = np.ascontiguousarray(flow, np.float32)
-            seg = np.ascontiguousarray(seg, np.float32)
+            seg = self._label_arg(seg)
         B = self._check_batch(img, flow, seg)
         if self.cfg.needs_depth and hold and not (isinstance(depth, np.ndarray) and depth.dtype == np.float32 and depth.flags.c_contiguous):
             raise ValueError("submit(hold > 0) needs a C-contiguous float32 depth array (a converted copy would not outlive the call)")
@@ -270,7 +303,7 @@ class Engine:
         (include/davo_hip.h: davo_calibrate; davo_calibrate_depth for a depth-source variant).  -> {layer: log2 scale}."""
         img = np.ascontiguousarray(img, np.uint8)
         flow = np.ascontiguousarray(flow, np.float32)
-        seg = np.ascontiguousarray(seg, np.float32)
+        seg = self._label_arg(seg)
         B = img.shape[0]
         if img.shape != (B, self.H, 3 * self.W, 3) or flow.shape != (B, 4, self.H, self.W, 2) or seg.shape != (B, 3, self.H, self.W, 1):
             raise ValueError("calibration batch shapes %s %s %s do not match the engine" % (img.shape, flow.shape, seg.shape))
@@ -322,6 +355,8 @@ class Engine:
     def forward_device(self, B, d_img, d_flow, d_seg, d_pose, timed=False, depth=None):
         """``depth``: the DeviceBuffer of the depth planes, required by a depth-source variant (davo_forward_device_depth)."""
         ms = ctypes.c_float(0.0)
+        if getattr(d_seg, "dtype", None) is not None and (d_seg.dtype == np.uint8) != (self.labels == "u8"):
+            raise ValueError("d_seg holds %s label maps, this engine takes labels='%s'" % (d_seg.dtype, self.labels))
         if self.cfg.needs_depth:
             if depth is None:
                 raise ValueError("image, flow, seglabel and depth inputs are all required for version `%s'" % self.cfg.version)
@@ -447,8 +482,10 @@ def conv2d_same(x, w, b, stride=1, rate=1, relu=True, device=0, precision="f32")
 def seg_one_hot(seg):
     """The reference's seg_19 (davo.py:1115: tf.one_hot(tf.cast(seg, int32), 19)) of label maps [..., 1] -> [..., 19] float32, by
     the rules the kernels' class gather follows: the cast truncates toward zero, and a label outside [0, 19) after it - or NaN or
-    infinite, where the cast is platform-defined - selects no class: a zero row."""
-    seg = np.asarray(seg, np.float32)[..., 0]
+    infinite, where the cast is platform-defined - selects no class: a zero row.  Byte label maps (uint8 [..., 1] or without the
+    trailing axis) follow the same rule: a byte's value as a float selects the class the byte selects on the device."""
+    seg = np.asarray(seg)
+    seg = (seg if seg.dtype == np.uint8 and seg.ndim == 4 else seg[..., 0]).astype(np.float32)
     with np.errstate(invalid="ignore"):
         ok = np.isfinite(seg) & (seg > -1.0) & (seg < 19.0)
     idx = np.where(ok, seg, 0.0).astype(np.int32)
@@ -468,7 +505,8 @@ def host_maps(cfg, img, seg, tables, depth=None, tables_far=None, thr=None):
     if split and (depth is None or tables_far is None or thr is None):
         raise ValueError("version `%s' needs depth, tables_far and thr" % cfg.version)
     img = np.asarray(img, np.uint8)
-    seg = np.asarray(seg, np.float32)
+    seg = np.asarray(seg)
+    seg = (seg[..., None] if seg.dtype == np.uint8 and seg.ndim == 4 else seg).astype(np.float32)      # bytes: the same class as floats
     tables = np.asarray(tables, np.float32)
     B, H, W3, _ = img.shape
     W = W3 // 3
@@ -509,6 +547,16 @@ class DAVO(object):
         self._weights = None
         self._feature_mode = False
         self._features = 'full'
+        self._labels = "f32"
+
+    def use_u8_labels(self):
+        """Opt in to byte label maps (include/davo_hip.h: davo_set_label_format): ``input_seglabel``, ``inference(inputs=...)`` and
+        iterator inputs then carry uint8 [B,3,H,W,1] or [B,3,H,W] class ids (davo_amd.labels_to_u8 of the float maps) and float
+        maps are refused.  Before ``setup_inference``.  Returns self."""
+        if self.engine is not None:
+            raise DavoError("use_u8_labels() must be called before setup_inference")
+        self._labels = "u8"
+        return self
 
     def enable_feature_mode(self, features='full'):
         """Opt in to ``inference(mode='feature')``: allocates the library's export workspace - now if ``setup_inference`` has
@@ -545,7 +593,7 @@ class DAVO(object):
         self.seq_length, self.num_source = seq_length, seq_length - 1
         assert self.version is not None                   # davo.py:959
         self.cfg = parse_version(self.version)
-        self.engine = Engine(self.cfg, img_height, img_width, batch_size, self.device)
+        self.engine = Engine(self.cfg, img_height, img_width, batch_size, self.device, labels=self._labels)
         if self._weights is not None:
             self.engine.load_weights(self._weights)
         if self._feature_mode:

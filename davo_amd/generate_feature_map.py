@@ -94,6 +94,9 @@ def build_parser():
     ap.add_argument("--synthetic", type=int, default=None, help="frame count of a synthetic sequence (seeded inputs and weights)")
     ap.add_argument("--npy", action="store_true", help="also write the float32 planes beside the index images")
     ap.add_argument("--device", type=int, default=0)
+    ap.add_argument("--labels", choices=("f32", "u8"), default="f32",
+                    help="u8: the label maps are loaded and handed to the library as uint8 class ids (davo_set_label_format); "
+                         "the written files are the same")
     return ap
 
 
@@ -118,7 +121,7 @@ def main(argv=None):
     if synthetic:
         from . import synth
         n_frames = a.synthetic
-        load = S.synthetic_window_loader(H, W, depth=cfg.needs_depth)
+        load = S.synthetic_window_loader(H, W, depth=cfg.needs_depth, labels=a.labels)
         weights = synth.make_weights(a.version)
     else:
         if not a.concat_img_dir or not a.ckpt_file:
@@ -128,7 +131,7 @@ def main(argv=None):
             raise SystemExit("davo_amd.generate_feature_map: sequence %.2d: no directory %s" % (seq, d))
         n_frames = sum(1 for f in os.listdir(d) if f.endswith(".jpg")) + 2 * int((a.seq_length - 1) / 2)       # :83-84
         from .tf_checkpoint import load_weights
-        load = S.kitti_window_loader(a.concat_img_dir, seq, n_frames, H, W, depth=cfg.needs_depth, seg_planes=(0, 1, 2))
+        load = S.kitti_window_loader(a.concat_img_dir, seq, n_frames, H, W, depth=cfg.needs_depth, seg_planes=(0, 1, 2), labels=a.labels)
         weights = load_weights(a.ckpt_file)
     if n_frames < 3:
         raise SystemExit("davo_amd.generate_feature_map: sequence %.2d has %d frames: a window needs three" % (seq, n_frames))
@@ -136,6 +139,8 @@ def main(argv=None):
     map_dir = os.path.join(a.output_dir, "%.2d-featuremaps" % seq)
     os.makedirs(map_dir, exist_ok=True)
     system = DAVO(version=a.version, device=a.device).enable_feature_mode(features='heat')
+    if a.labels == "u8":
+        system.use_u8_labels()
     system.setup_inference(H, W, "davo", a.seq_length, a.batch_size)
     system.load_weights(weights)
     poses = np.empty((n_windows, 2, 6), np.float32)

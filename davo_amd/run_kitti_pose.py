@@ -131,6 +131,11 @@ def build_parser():
                     help="both: every window runs tgt->src0 and tgt->src1, as the reference does.  trajectory: only what the trajectory "
                          "reads (test_kitti_pose.py:143-145) - both pairs for the batch that holds a sequence's window 0, tgt->src1 alone "
                          "for every other batch: half the arithmetic and 55 %% of the input bytes; the written file is the same")
+    ap.add_argument("--labels", choices=("f32", "u8"), default="f32",
+                    help="f32: the label maps cross the link as the reference's float32.  u8: as uint8 class ids (include/davo_hip.h: "
+                         "davo_set_label_format) - a quarter of the label bytes in the loader's buffers, over the link and in the staging "
+                         "sets; uint8 -seglabel.npy files are read as they are, float32 ones converted by the loader's workers "
+                         "(davo_amd.labels_to_u8).  The written file is the same")
     return ap
 
 
@@ -204,7 +209,7 @@ def main(argv=None):
                                      alloc=lambda shape, dtype: pinned_empty(shape, dtype, device_index),
                                      workers=a.loader_threads, decode_procs=a.decode_procs, procs=procs,
                                      pin=lambda arr: (gpu_ready.wait(), pin_array(arr, device_index)), unpin=unpin_array,
-                                     seg_planes=tgt_planes, hold=0 if a.sync_driver else 1, depth=needs_depth)
+                                     seg_planes=tgt_planes, hold=0 if a.sync_driver else 1, depth=needs_depth, labels=a.labels)
         # the loader's buffers are created and its workers start filling them on a thread of its own, before anything else: the
         # workers need no GPU.  Page-locking the buffers (1.4 GB at batch 64: 0.3 s) follows on the loader's own thread, entry by
         # entry, once the context below exists: HIP serialises hipHostRegister with the context's own allocations, and pinning
@@ -230,6 +235,8 @@ def main(argv=None):
             _lib.lib()
             mark("library_loaded")
             system = DAVO(version=a.version, device=device_index)
+            if a.labels == "u8":
+                system.use_u8_labels()
             system.setup_inference(H, W, "davo", a.seq_length, a.batch_size)
             mark("gpu_context_created")
         finally:
@@ -241,7 +248,7 @@ def main(argv=None):
 
         if synthetic:
             from . import synth
-            load = S.synthetic_window_loader(H, W, depth=needs_depth)     # the same seeded windows whatever the sequence's number
+            load = S.synthetic_window_loader(H, W, depth=needs_depth, labels=a.labels)     # the same seeded windows whatever the sequence's number
             weights = synth.make_weights(a.version)
         else:
             weights_thread.join()
@@ -343,6 +350,8 @@ def main(argv=None):
                                  "wait for the communicator, which is built on a second thread from the moment the GPU context exists")
             if a.pairs != "both":          # the default run's report is the one it has always been
                 run_wide["pairs"] = a.pairs
+            if a.labels != "f32":
+                run_wide["labels"] = a.labels
             if len(entries) == 1:          # one sequence: the report it has always had
                 report = {k: v for k, v in entries[0].items() if k not in ("seq", "wall_s")}
                 report.update(run_wide)

@@ -63,10 +63,13 @@ def _stream(name):
     return h
 
 
-def make_inputs(B, H=128, W=416, seed=SEED, first_window=0):
+def make_inputs(B, H=128, W=416, seed=SEED, first_window=0, labels="f32"):
     """Synthetic batch of B triplets; window w of a sequence is reproducible on its own
     (``first_window`` offsets the per-window streams), which is what lets ranks generate
-    just their shard."""
+    just their shard.  ``labels`` = "u8": the label maps are the byte twin of the float ones
+    (``davo_amd.labels_to_u8``), uint8 [B,3,H,W,1]."""
+    from .labels import check_label_format, labels_to_u8
+    check_label_format(labels)
     img = np.empty((B, H, 3 * W, 3), np.uint8)
     flow = np.empty((B, 4, H, W, 2), np.float32)
     seg = np.empty((B, 3, H, W, 1), np.float32)
@@ -83,7 +86,7 @@ def make_inputs(B, H=128, W=416, seed=SEED, first_window=0):
         ids[ign] = 255.0
         blk = ids.reshape(3, hb, wb)
         seg[b, :, :, :, 0] = np.repeat(np.repeat(blk, 8, axis=1), 8, axis=2)[:, :H, :W]
-    return img, flow, seg
+    return img, flow, (labels_to_u8(seg) if labels == "u8" else seg)
 
 
 def make_depth(B, H=128, W=416, seed=SEED, first_window=0):

@@ -83,6 +83,26 @@ int davo_create(davo_ctx** out, int device, int H, int W, int max_batch, const d
  * unchanged; `-se_skipadd' and `-se_replace' are not built. */
 int davo_set_posenn_se(davo_ctx* ctx, int mode);
 
+/* Label format.  A label map is a class id per pixel, and nothing on the path reads more of it than "class 0..18, or none"; the
+ * reference's preprocessing stores it as float32 [B,3,H,W,1] (data_loader.py:313-317), which is what every entry point takes by
+ * default (DAVO_LABELS_F32).  davo_set_label_format(ctx, DAVO_LABELS_U8) makes the context take bytes instead: uint8 [B,3,H,W,1],
+ * same plane order (src0, tgt, src1).  A byte L < 19 selects class L; 19..255 select no class (Cityscapes' ignore label 255 among
+ * them).  The float32 rule folded into a byte - a finite value in (-1, 19) becomes its truncation toward zero, anything else 255
+ * (davo_amd.labels_to_u8) - selects the same class for every pixel, so poses, layer tensors and exports are bit-identical to the
+ * float32 context's on the converted maps.  The kernels read the bytes natively (no widening pass, no float copy on the device).
+ * On a DAVO_LABELS_U8 context the `seg' / `d_seg' argument of EVERY entry point below points at bytes (a C caller casts the
+ * pointer): davo_forward, davo_forward_device, davo_submit, davo_calibrate, their `_depth' forms, davo_forward_features and
+ * davo_forward_heat; and everything the context sizes by a window's label maps follows - the host entry points' copies (3 H W
+ * bytes per window instead of 12 H W: a 128x416 window is 1,437,696 B across the link instead of 1,757,184), the staging sets of
+ * the streaming slots, the range guard's input snapshots and its re-issues.  Device label maps must be 16-byte aligned in either
+ * format (every kernel then loads a 4-pixel unit of labels with one aligned load: H W is a multiple of 16).  A `-no_segmask'
+ * context accepts the call and reads no label byte.  The depth planes stay float32.
+ * Like davo_set_posenn_se this is called right after davo_create: once any call has taken inputs (or a staging set or the
+ * snapshot ring exists) it returns DAVO_ERR_INVALID, and so does any other value of fmt.  davo_get_label_format reads it back. */
+enum { DAVO_LABELS_F32 = 0, DAVO_LABELS_U8 = 1 };
+int davo_set_label_format(davo_ctx* ctx, int fmt);
+int davo_get_label_format(const davo_ctx* ctx);
+
 /* Replaces tf.train.Saver(tf.trainable_variables()).restore(sess, ckpt)
  * (test_kitti_pose.py:129-131), one tensor at a time, keyed by the TF variable name
  * (e.g. "pose_exp_net/cnv1/weights", "pose_exp_net/pose/rotation/cnv6/biases",
@@ -100,7 +120,8 @@ int davo_weights_missing(davo_ctx* ctx);
  * Host pointers, shapes as the reference's test driver sets them (test_kitti_pose.py:110-114):
  *   img  uint8 [B,H,3W,3]  (strip src0|tgt|src1, data_loader.py:537-557)
  *   flow f32   [B,4,H,W,2] (planes 0,1 used, davo.py:978-982)
- *   seg  f32   [B,3,H,W,1] (file order src0,tgt,src1, davo.py:998-1004)
+ *   seg  f32   [B,3,H,W,1] (file order src0,tgt,src1, davo.py:998-1004); uint8 [B,3,H,W,1] behind the same pointer type on a
+ *              DAVO_LABELS_U8 context (davo_set_label_format) - here and for every `seg' / `d_seg' argument below
  *   pose_out f32 [B,2,6]   rows = (tgt->src0, tgt->src1), each [rz,ry,rx,tx,ty,tz]
  * Synchronous: returns after pose_out is written.  1 <= B <= max_batch. */
 int davo_forward(davo_ctx* ctx, int B, const uint8_t* img, const float* flow, const float* seg,
@@ -156,7 +177,8 @@ int davo_forward_device(davo_ctx* ctx, int B, const void* d_img, const void* d_f
 
 /* The sequence loop as a stream.  The reference's driver pulls batches through tf.data's prefetch(8*B) while the session runs
  * (test_kitti_pose.py:133-145, data_loader.py:321-324), so input transfer, compute and result delivery of neighbouring batches
- * overlap; davo_forward returns poses and cannot.  davo_submit takes host pointers shaped as davo_forward's and rotates through the
+ * overlap; davo_forward returns poses and cannot.  davo_submit takes host pointers shaped as davo_forward's (seg: bytes on a
+ * DAVO_LABELS_U8 context) and rotates through the
  * in-flight slots (davo_set_inflight) like davo_forward_device: on the slot's own stream it queues the H2D copies of the planes the
  * path reads into the slot's staging set, the forward, and the D2H of the poses into a page-locked ring entry of the context.  With
  * two or more slots the copies of batch n+1 run under the kernels of batch n (one slot: copy and kernels alternate, still without
@@ -228,7 +250,7 @@ int davo_get_pairs(const davo_ctx* ctx);
  * davo_set_feature_export(ctx, 1) allocates the export workspace (room for one davo_forward sub-batch of every tensor above),
  * davo_set_feature_export(ctx, 0) and davo_destroy free it; it is off by default, and a context that never switches it on
  * allocates and launches nothing for it.
- * davo_forward_features takes host pointers like davo_forward (depth: the planes of a depth source as davo_forward_depth takes
+ * davo_forward_features takes host pointers like davo_forward (seg: bytes on a DAVO_LABELS_U8 context; depth: the planes of a depth source as davo_forward_depth takes
  * them, NULL or ignored for any other variant) and is synchronous.  pose_out receives bit for bit what davo_forward returns on
  * the same inputs and context state.  Every member of *out that is not NULL receives its tensor for all B windows, whatever
  * "host_chunk" is; a NULL member is neither computed nor copied, and out == NULL or all members NULL is a plain davo_forward.
@@ -270,7 +292,7 @@ int davo_forward_features(davo_ctx* ctx, int B, const uint8_t* img, const float*
  * davo_set_heat_export(ctx, 1) allocates a workspace of its own - per window of one davo_forward sub-batch 2 (H/4 W/4 + H W + 1)
  * floats - independent of davo_set_feature_export; (ctx, 0) and davo_destroy free it; off by default, and a context that never
  * switches it on allocates and launches nothing for it.
- * davo_forward_heat is davo_forward_features plus the heat members: the same inputs, synchronous, the same sub-batching under
+ * davo_forward_heat is davo_forward_features plus the heat members: the same inputs (seg: bytes on a DAVO_LABELS_U8 context), synchronous, the same sub-batching under
  * "host_chunk", the same pair-selection rule (DAVO_PAIRS_BOTH, else DAVO_ERR_INVALID), both precisions, davo_set_posenn_se and
  * davo_set_impl(ctx, 1); pose_out is bit for bit davo_forward's; a batch that fails its f16x3 range verdict is re-issued first and
  * exported from the re-issue, in the precision it ran.  A NULL member is neither computed nor copied; `out' or `heat' may be NULL.
@@ -366,7 +388,7 @@ int davo_set_precision(davo_ctx* ctx, int precision);
  * later batches run f16x3 with the new scales.  davo_range_stats counts what happened.  davo_set_option(ctx,
  * "auto_range", 0) turns the recovery off: the entry points then return DAVO_ERR_RANGE (poses are still written, not
  * float32-grade) and the caller calibrates or changes mode itself.  davo_calibrate runs the path on
- * a sample batch (device buffers, as davo_forward_device) and gives every layer an exact power-of-two storage
+ * a sample batch (device buffers, as davo_forward_device: d_seg points at bytes on a DAVO_LABELS_U8 context) and gives every layer an exact power-of-two storage
  * scale that puts its largest value in [512, 1024); results inside the safe range do not depend on the scales
  * beyond rounding noise (~1e-8).  The reference's float32 graph needs none of this (TF conv2d, nets/posenn.py:205-215);
  * mode 0 (f32) ignores the scales.

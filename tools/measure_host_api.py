@@ -97,8 +97,108 @@ def batch1_measurement(calls=3000, H=128, W=416):
     e.close()
 
 
+def labels_measurement(arms, rounds, n=30, H=128, W=416):
+    """`--labels f32 u8 [--rounds R]`: the label formats (davo_set_label_format) against each other, one engine per format in ONE
+    process, the arms alternating inside every round (round 0 warms up), f16x3 and float32:
+      resident  ms per davo_forward_device step at B = 32 with the inputs in HBM (the bench's path): per arm the median, and the
+                spread (max - min) of its rounds - the margin of the "byte labels are not slower" bound;
+      streamed  windows/s of davo_submit from page-locked memory at B = 32 and at batch 1, with 1..4 slots, best of the rounds,
+                beside the H2D bytes per window;
+    and once per format the device memory a context holds after streaming on four slots (staging sets + the guard's snapshots)."""
+    import ctypes
+    from davo_amd import pinned_empty
+    from davo_amd import _lib
+    from davo_amd.labels import LABEL_DTYPES
+    _lib.lib()                                               # loads the HIP runtime free_bytes asks
+
+    def free_bytes():
+        hip = ctypes.CDLL(next(line.split()[-1] for line in open("/proc/self/maps") if "libamdhip64" in line))
+        free, total = ctypes.c_size_t(0), ctypes.c_size_t(0)
+        hip.hipMemGetInfo(ctypes.byref(free), ctypes.byref(total))
+        return free.value
+
+    cfg = parse_version(FLAGSHIP_VERSION)
+    weights = synth.make_weights(cfg)
+    hw = H * W
+    for B in (32, 1):
+        engines, host, pinned, dev = {}, {}, {}, {}
+        for arm in arms:
+            img, flow, seg = synth.make_inputs(min(8, B), H, W, labels=arm)
+            reps = -(-B // 8)
+            host[arm] = tuple(np.tile(a, (reps,) + (1,) * (a.ndim - 1))[:B] for a in (img, flow, seg))
+            before = free_bytes()
+            e = engines[arm] = Engine(cfg, H, W, B, labels=arm)
+            e.load_weights(weights)
+            pinned[arm] = tuple(pinned_empty(a.shape, a.dtype) for a in host[arm])
+            for d, a in zip(pinned[arm], host[arm]):
+                d[...] = a
+            e.set_inflight(4)
+            outs = [np.empty((B, 2, 6), np.float32) for _ in range(5)]
+            for o in outs:
+                e.submit(*pinned[arm], o, hold=8)
+            e.synchronize()
+            lab = LABEL_DTYPES[arm].itemsize
+            print("labels=%-3s B=%-2d: %d B of device memory held by the context after streaming on 4 slots; a window's label maps "
+                  "%d B, a staging set's %d B, the eight snapshots' %d B" % (arm, B, before - free_bytes(), 3 * hw * lab, 3 * hw * lab * B, 8 * 3 * hw * lab * B), flush=True)
+            dev[arm] = tuple(e.alloc(a.nbytes).upload(a) for a in host[arm]) + (e.alloc(B * 48),)
+        nb = n if B > 1 else 20 * n
+        outs = [np.empty((B, 2, 6), np.float32) for _ in range(nb)]
+        for prec in ("f16x3", "f32"):
+            for e in engines.values():
+                e.set_precision(prec)
+            if B == 32:
+                step = {arm: [] for arm in arms}
+                for e in engines.values():
+                    e.set_inflight(1)
+                for r in range(rounds + 1):
+                    for arm in arms:
+                        e = engines[arm]
+                        for _ in range(5):
+                            e.forward_device(B, *dev[arm])
+                        e.synchronize()
+                        t0 = time.perf_counter()
+                        for _ in range(n):
+                            e.forward_device(B, *dev[arm])
+                        e.synchronize()
+                        if r:
+                            step[arm].append((time.perf_counter() - t0) / n * 1e3)
+                for arm in arms:
+                    v = sorted(step[arm])
+                    print("resident davo_forward_device %-5s B=%d labels=%-3s: median %.4f ms per step, spread %.4f (rounds %s)"
+                          % (prec, B, arm, v[len(v) // 2], v[-1] - v[0], " ".join("%.4f" % x for x in step[arm])), flush=True)
+            for slots in (1, 2, 3, 4):
+                rates = {arm: [] for arm in arms}
+                for e in engines.values():
+                    e.set_inflight(slots)
+                for r in range(rounds + 1):
+                    for arm in arms:
+                        e = engines[arm]
+                        t0 = time.perf_counter()
+                        for o in outs:
+                            e.submit(*pinned[arm], o, hold=8)
+                        e.synchronize()
+                        if r:
+                            rates[arm].append(B * nb / (time.perf_counter() - t0))
+                for arm in arms:
+                    lab = LABEL_DTYPES[arm].itemsize
+                    mb = hw * 9 + hw * 16 + hw * lab * (2 if B >= 4 else 3)
+                    print("davo_submit pinned %-5s B=%-2d %d slot(s) labels=%-3s: %9.1f windows/s best, rounds %s; %d B H2D per window -> %.1f GB/s"
+                          % (prec, B, slots, arm, max(rates[arm]), " ".join("%.0f" % x for x in rates[arm]), mb, mb * max(rates[arm]) / 1e9), flush=True)
+        for e in engines.values():
+            e.close()
+
+
 if "--batch1" in sys.argv:
     batch1_measurement()
+    sys.exit(0)
+
+if "--labels" in sys.argv:
+    import argparse
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--labels", nargs="+", choices=("f32", "u8"), required=True)
+    ap.add_argument("--rounds", type=int, default=3)
+    args = ap.parse_args()
+    labels_measurement(args.labels, args.rounds)
     sys.exit(0)
 
 if "--pairs" in sys.argv:
