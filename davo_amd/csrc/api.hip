@@ -13,6 +13,7 @@
 #include "launch.h"
 #include "pad_classes.h"
 #include "plan.h"
+#include "window_gather.h"
 
 using namespace davo;
 
@@ -172,6 +173,7 @@ int davo_set_label_format(davo_ctx* c, int fmt) {
     // everything sized by plane_bytes() follows the format: it is fixed once inputs were taken or a set of them was allocated
     bool sets = static_cast<bool>(c->host) || static_cast<bool>(c->snaps);
     for (const InputSet& s : c->stream_sets) sets = sets || s.built();
+    for (const FrameSet& s : c->frame_sets) sets = sets || s.built();
     if (c->inputs_seen || c->forward_seen || sets)
         return fail(c, DAVO_ERR_INVALID, "davo_set_label_format must be called before the first call that takes inputs "
                     "(the staging sets, the range guard's snapshots and every copy are sized by it)");
@@ -238,25 +240,48 @@ int resolve_depth(davo_ctx* c, const char* fn, bool depth_form, const void** dep
     return DAVO_OK;
 }
 
+// frame layout (defined with the streaming entry point below)
+// A frame-layout batch as the caller handed it: frames [N+2,H,W,3], flow2 [N,2,H,W,2], seg and depth [N+2,H,W,1]
+struct FrameInputs { const void *frames, *flow2, *seg, *depth; };
+int resolve_frames_depth(davo_ctx* c, const char* fn, const void** depth);
+int gather_windows(davo_ctx* c, const InputSet& set, const FrameInputs& fr, int b0, int nb, int sel, hipStream_t s);
+
 }  // namespace
 
-// the body of davo_forward_device / davo_forward_device_depth (depth_form)
+// the body of davo_forward_device / davo_forward_device_depth (depth_form) and of davo_forward_device_frames (frames: d_img, d_flow,
+// d_seg, d_depth are the frame layout's d_frames, d_flow2, d_seg, d_depth; the batch runs on the slot's staging set, gathered from them)
 static int forward_device_entry(davo_ctx* c, int B, const void* d_img, const void* d_flow, const void* d_seg, const void* d_depth,
-                                void* d_pose, float* elapsed_ms, bool depth_form) {
+                                void* d_pose, float* elapsed_ms, bool depth_form, bool frames = false) {
     if (!c) return DAVO_ERR_INVALID;
     if (B < 1 || B > c->max_batch) return fail(c, DAVO_ERR_INVALID, "batch %d outside [1,%d]", B, c->max_batch);
     if (!d_img || !d_flow || !d_seg || !d_pose) return fail(c, DAVO_ERR_INVALID, "null device pointer");
-    { int rc = resolve_depth(c, "davo_forward_device", depth_form, &d_depth); if (rc) return rc; }
+    { int rc = frames ? resolve_frames_depth(c, "davo_forward_device_frames", &d_depth) : resolve_depth(c, "davo_forward_device", depth_form, &d_depth); if (rc) return rc; }
+    if (frames && (((uintptr_t)d_img | (uintptr_t)d_flow | (uintptr_t)d_seg | (uintptr_t)d_depth) & 15))
+        return fail(c, DAVO_ERR_INVALID, "davo_forward_device_frames: device input buffers must be 16-byte aligned");
     c->inputs_seen = true;
-    const Inputs in{d_img, d_flow, d_seg, d_depth};
     HIP_TRY(c, hipSetDevice(c->device));
+    if (frames && !c->stream_sets[c->next_slot].built()) { int rc = alloc_input_set(c, &c->stream_sets[c->next_slot], true); if (rc) return rc; }
+    const Inputs in = frames ? c->stream_sets[c->next_slot].view() : Inputs{d_img, d_flow, d_seg, d_depth};
     const bool ticketed = c->impl == 0 && c->precision == 1;      // f16x3: the batch gets a record (and a copy of its inputs) of its own
     if (ticketed) { int rc = ticket_reserve(c); if (rc) return rc; }
     // rotate through the in-flight slots: this batch runs on its own stream and workspace
     Run run = make_run(c, c->next_slot);
+    const int slot = c->next_slot;
     c->next_slot = (c->next_slot + 1) % c->inflight;
+    EventOwner e0, e1;
+    if (frames) {
+        // the windows into the slot's staging set, in stream order behind the forward that last read it and ahead of the ticket: the
+        // caller's buffers are free once this launch has run, and the batch is the library's own from here on (own_inputs below).
+        // The timed form brackets the gather too: elapsed_ms is what the layout costs on resident inputs
+        if (elapsed_ms) {
+            HIP_TRY(c, event_create(&e0));
+            HIP_TRY(c, hipEventRecord(e0.get(), run.stream));
+        }
+        int rc = gather_windows(c, c->stream_sets[slot], FrameInputs{d_img, d_flow, d_seg, d_depth}, 0, B, run.pairs, run.stream);
+        if (rc) return rc;
+    }
     Ticket t{};
-    if (ticketed) { int rc = ticket_begin(c, &run, B, in, &t); if (rc) return rc; }
+    if (ticketed) { int rc = ticket_begin(c, &run, B, in, &t, frames); if (rc) return rc; }
     if (!ticketed && c->book.spans_full()) {               // float32 batches behind pending f16x3 tickets: bounded
         const int rc = judge_all(c);
         if (rc == DAVO_ERR_RANGE) c->book.defer(rc, c->err);       // "auto_range" 0: reported by the next davo_synchronize (judge_all has just emptied the store)
@@ -268,14 +293,13 @@ static int forward_device_entry(davo_ctx* c, int B, const void* d_img, const voi
         int rc = forward_device(c, run, B, in, d_pose, &res);
         return ticketed ? ticket_end(c, rc, res, t, d_pose) : rc;      // (only a ticketed batch starts as f16x3, so only it can fall back)
     }
-    EventOwner e0, e1;
     int rc = DAVO_OK;
     auto hip_ok = [&](hipError_t e, const char* what) {
         if (e != hipSuccess && rc == DAVO_OK) rc = fail(c, DAVO_ERR_HIP, "%s failed: %s", what, hipGetErrorString(e));
         return e == hipSuccess;
     };
-    if (hip_ok(event_create(&e0), "hipEventCreate") && hip_ok(event_create(&e1), "hipEventCreate") &&
-        hip_ok(hipEventRecord(e0.get(), run.stream), "hipEventRecord")) {
+    if (hip_ok(event_create(&e1), "hipEventCreate") &&
+        (e0 || (hip_ok(event_create(&e0), "hipEventCreate") && hip_ok(hipEventRecord(e0.get(), run.stream), "hipEventRecord")))) {
         rc = forward_device(c, run, B, in, d_pose, &res);
         if (rc == DAVO_OK && hip_ok(hipEventRecord(e1.get(), run.stream), "hipEventRecord") &&
             hip_ok(hipEventSynchronize(e1.get()), "hipEventSynchronize"))
@@ -295,6 +319,24 @@ int davo_forward_device(davo_ctx* c, int B, const void* d_img, const void* d_flo
 int davo_forward_device_depth(davo_ctx* c, int B, const void* d_img, const void* d_flow, const void* d_seg, const void* d_depth,
                               void* d_pose, float* elapsed_ms) {
     return forward_device_entry(c, B, d_img, d_flow, d_seg, d_depth, d_pose, elapsed_ms, true);
+}
+
+int davo_forward_device_frames(davo_ctx* c, int N, const void* d_frames, const void* d_flow2, const void* d_seg, const void* d_depth,
+                               void* d_pose, float* elapsed_ms) {
+    return forward_device_entry(c, N, d_frames, d_flow2, d_seg, d_depth, d_pose, elapsed_ms, true, true);
+}
+
+int davo_frames_plan(int H, int W, int N, int pairs, int att_source, int label_fmt, int* ranges, long long* link_bytes) {
+    if (H < 1 || W < 1 || N < 1 || (pairs != PAIRS_SRC0 && pairs != PAIRS_SRC1 && pairs != PAIRS_BOTH) || att_source < 0 || att_source > ATT_DEPTH_SPLIT ||
+        (label_fmt != LABELS_F32 && label_fmt != LABELS_U8))
+        return DAVO_ERR_INVALID;
+    const FramePlan p = frame_plan(N, pairs, att_source);
+    if (ranges) {
+        const int r[8] = {p.img[0], p.img[1], p.seg[0], p.seg[1], p.depth[0], p.depth[1], p.flow[0], p.flow[1]};
+        memcpy(ranges, r, sizeof r);
+    }
+    if (link_bytes) *link_bytes = frame_plan_bytes(p, N, H, W, label_fmt == LABELS_U8 ? 1 : 4);
+    return DAVO_OK;
 }
 
 
@@ -376,6 +418,72 @@ int stage_inputs(davo_ctx* c, const InputSet& set, const Inputs& host, int b0, i
     return DAVO_OK;
 }
 
+// ---- frame layout (window_gather.h; include/davo_hip.h "Frame sequences") ---------------------------------------
+// bytes of one frame of each plane kind (flow2: of one window)
+PlaneBytes frame_bytes(const davo_ctx* c) {
+    const PlaneBytes n = plane_bytes(c);
+    return PlaneBytes{n.img / 3, n.flow / 2, n.seg / 3, n.depth / 3};
+}
+// the depth argument of a `_frames' entry point: in the signature, NULL where the variant reads none
+int resolve_frames_depth(davo_ctx* c, const char* fn, const void** depth) {
+    if (!needs_depth(c)) { *depth = nullptr; return DAVO_OK; }
+    if (!*depth) return fail(c, DAVO_ERR_INVALID, "%s: this variant reads depth planes (att_source %d): depth must not be NULL", fn, c->v.att_source);
+    return DAVO_OK;
+}
+
+int ensure_frame_set(davo_ctx* c, int slot) {
+    if (c->frame_sets[slot].built()) return DAVO_OK;
+    const PlaneBytes f = frame_bytes(c);
+    const size_t n = (size_t)c->max_batch + 2;
+    FrameSet s;
+    HIP_TRY(c, dev_alloc(&s.img, f.img * n));
+    HIP_TRY(c, dev_alloc(&s.seg, f.seg * n));
+    if (needs_depth(c)) HIP_TRY(c, dev_alloc(&s.depth, f.depth * n));
+    c->frame_sets[slot] = std::move(s);
+    return DAVO_OK;
+}
+
+// frames copied so far of each plane kind by the sub-batches of one call (a frame crosses the link once per call)
+struct FrameCursor { int img = 0, seg = 0, depth = 0; };
+
+// Host -> device, on stream s, for windows [b0, b0 + nb) of a frame-layout call: the frames frame_plan says they read and no
+// earlier sub-batch of the call has brought (*cur) into the slot's frame buffer, frame f to place f; the flow planes of the
+// selection straight into planes 0, 1 of the same windows of the staging set, as stage_inputs puts them.
+int stage_frames(davo_ctx* c, const FrameSet& fs, const InputSet& set, const FrameInputs& host, int b0, int nb, int sel, FrameCursor* cur, hipStream_t s) {
+    const PlaneBytes f = frame_bytes(c), n = plane_bytes(c);
+    const FramePlan p = frame_plan(nb, sel, c->v.att_source);
+    auto copy = [&](const DevMem<void>& d, const void* h, size_t per, const int r[2], int* done) -> int {
+        const int lo = std::max(b0 + r[0], *done), hi = b0 + r[1];
+        if (hi > lo) HIP_TRY(c, hipMemcpyAsync(static_cast<uint8_t*>(d.get()) + per * lo, static_cast<const uint8_t*>(h) + per * lo, per * (hi - lo), hipMemcpyHostToDevice, s));
+        *done = std::max(*done, hi);
+        return DAVO_OK;
+    };
+    { int rc = copy(fs.img, host.frames, f.img, p.img, &cur->img); if (rc) return rc; }
+    { int rc = copy(fs.seg, host.seg, f.seg, p.seg, &cur->seg); if (rc) return rc; }
+    if (host.depth) { int rc = copy(fs.depth, host.depth, f.depth, p.depth, &cur->depth); if (rc) return rc; }
+    const size_t plane = n.flow / 4, off = plane * p.flow[0], width = plane * (p.flow[1] - p.flow[0]);
+    uint8_t* const d = static_cast<uint8_t*>(set.flow.get()) + n.flow * b0 + off;
+    const uint8_t* const h = static_cast<const uint8_t*>(host.flow2) + f.flow * b0 + off;
+    if (nb == 1) HIP_TRY(c, hipMemcpyAsync(d, h, width, hipMemcpyHostToDevice, s));
+    else HIP_TRY(c, hipMemcpy2DAsync(d, n.flow, h, f.flow, width, nb, hipMemcpyHostToDevice, s));
+    return DAVO_OK;
+}
+
+// window_gather on stream s: windows [b0, b0 + nb) of `set' from frames [b0, b0 + nb + 2) of `fr' (device pointers, frame 0 of the
+// call); fr.flow2 null: the flow is in the set already
+int gather_windows(davo_ctx* c, const InputSet& set, const FrameInputs& fr, int b0, int nb, int sel, hipStream_t s) {
+    const PlaneBytes f = frame_bytes(c), n = plane_bytes(c);
+    const FramePlan p = frame_plan(nb, sel, c->v.att_source);
+    auto src = [b0](const void* q, size_t per) { return q ? static_cast<const uint8_t*>(q) + per * b0 : nullptr; };
+    auto dst = [b0](const DevMem<void>& q, size_t per) { return q ? static_cast<uint8_t*>(q.get()) + per * b0 : nullptr; };
+    const GatherArgs a{src(fr.frames, f.img), src(fr.seg, f.seg), src(fr.depth, f.depth), src(fr.flow2, f.flow),
+                       dst(set.img, n.img), dst(set.seg, n.seg), dst(set.depth, n.depth), dst(set.flow, n.flow),
+                       c->H, c->W, sel, p.seg_tgt, p.depth_tgt};
+    ProfScope ps(c, s, "window_gather");
+    HIP_TRY(c, launch_window_gather(a, nb, c->label_fmt, s));
+    return DAVO_OK;
+}
+
 // the oldest undelivered batch: verdict (and re-issue) first, then its poses go to the caller's array
 int deliver_front(davo_ctx* c) {
     const StreamJob j = c->jobs.front();
@@ -405,13 +513,14 @@ int deliver_all(davo_ctx* c) {
 
 }  // namespace
 
-// the body of davo_submit / davo_submit_depth (depth_form)
+// the body of davo_submit / davo_submit_depth (depth_form) and of davo_submit_frames (frames: img, flow, seg, depth_in are the frame
+// layout's frames, flow2, seg, depth)
 static int submit_entry(davo_ctx* c, int B, const uint8_t* img, const float* flow, const float* seg, const float* depth_in, float* pose_out,
-                        int hold, bool depth_form) {
+                        int hold, bool depth_form, bool frames = false) {
     if (!c) return DAVO_ERR_INVALID;
     if (!img || !flow || !seg || !pose_out) return fail(c, DAVO_ERR_INVALID, "null host pointer");
     const void* depth = depth_in;
-    { int rc = resolve_depth(c, "davo_submit", depth_form, &depth); if (rc) return rc; }
+    { int rc = frames ? resolve_frames_depth(c, "davo_submit_frames", &depth) : resolve_depth(c, "davo_submit", depth_form, &depth); if (rc) return rc; }
     if (B < 1 || B > c->max_batch) return fail(c, DAVO_ERR_INVALID, "batch %d outside [1,%d]", B, c->max_batch);
     if (hold < 0) return fail(c, DAVO_ERR_INVALID, "hold must be >= 0");
     c->inputs_seen = true;
@@ -425,17 +534,26 @@ static int submit_entry(davo_ctx* c, int B, const uint8_t* img, const float* flo
     if (ticketed) { int rc = ticket_reserve(c); if (rc) return rc; }          // may judge - and re-issue - an older batch: before the slot rotation
     const int slot = c->next_slot, pr = (int)(c->n_submitted % STREAM_POSES);
     { int rc = ensure_stream_state(c, slot); if (rc) return rc; }
+    if (frames) { int rc = ensure_frame_set(c, slot); if (rc) return rc; }
     Run run = make_run(c, slot);
     c->next_slot = (c->next_slot + 1) % c->inflight;
     hipStream_t s = run.stream;
     // H2D on the slot's stream, in order behind the forward that last read this staging set
     const InputSet& set = c->stream_sets[slot];
     PoseRing::Entry& e = c->pose_ring->e[pr];
-    { int rc = stage_inputs(c, set, Inputs{img, flow, seg, depth}, 0, B, true, c->pairs, s); if (rc) return rc; }
+    if (frames) {      // the frames into the slot's frame buffer (behind the gather that last read it), the flow into the set
+        FrameCursor cur;
+        { int rc = stage_frames(c, c->frame_sets[slot], set, FrameInputs{img, flow, seg, depth}, 0, B, c->pairs, &cur, s); if (rc) return rc; }
+    } else { int rc = stage_inputs(c, set, Inputs{img, flow, seg, depth}, 0, B, true, c->pairs, s); if (rc) return rc; }
     // the caller keeps a batch's inputs unchanged for `hold` more submits.  With hold >= STREAM_POSES the pose ring already implies it
     // (a batch is delivered - so its copies are long done - before the eighth submit after it returns): no event then
     const bool track_copy = hold < STREAM_POSES;
     if (track_copy) HIP_TRY(c, hipEventRecord(e.copied.get(), s));
+    if (frames) {      // the windows, from the device's copy of the frames: the staging set is an ordinary window batch from here on
+        const FrameSet& fs = c->frame_sets[slot];
+        int rc = gather_windows(c, set, FrameInputs{fs.img.get(), nullptr, fs.seg.get(), fs.depth.get()}, 0, B, c->pairs, s);
+        if (rc) return rc;
+    }
 
     Ticket t{};
     if (ticketed) { int rc = ticket_begin(c, &run, B, set.view(), &t, true); if (rc) return rc; }
@@ -464,6 +582,10 @@ int davo_submit(davo_ctx* c, int B, const uint8_t* img, const float* flow, const
 
 int davo_submit_depth(davo_ctx* c, int B, const uint8_t* img, const float* flow, const float* seg, const float* depth, float* pose_out, int hold) {
     return submit_entry(c, B, img, flow, seg, depth, pose_out, hold, true);
+}
+
+int davo_submit_frames(davo_ctx* c, int N, const uint8_t* frames, const float* flow2, const float* seg, const float* depth, float* pose_out, int hold) {
+    return submit_entry(c, N, frames, flow2, seg, depth, pose_out, hold, true, true);
 }
 
 int davo_wait(davo_ctx* c, int leave_pending) {
@@ -629,12 +751,13 @@ int export_all(davo_ctx* c, const Exports& ex, const Inputs& in, int w0, int nw,
 }  // namespace
 
 // the body of davo_forward / davo_forward_depth (depth_form) and of davo_forward_features / davo_forward_heat (ex: the exports wanted)
+// ... and of davo_forward_frames (frames: img, flow, seg, depth_in are the frame layout's frames, flow2, seg, depth)
 static int forward_entry(davo_ctx* c, int B, const uint8_t* img, const float* flow, const float* seg, const float* depth_in, float* pose_out,
-                         bool depth_form, const Exports ex = Exports{}) {
+                         bool depth_form, const Exports ex = Exports{}, bool frames = false) {
     if (!c) return DAVO_ERR_INVALID;
     if (!img || !flow || !seg || !pose_out) return fail(c, DAVO_ERR_INVALID, "null host pointer");
     const void* depth = depth_in;
-    { int rc = resolve_depth(c, "davo_forward", depth_form, &depth); if (rc) return rc; }
+    { int rc = frames ? resolve_frames_depth(c, "davo_forward_frames", &depth) : resolve_depth(c, "davo_forward", depth_form, &depth); if (rc) return rc; }
     if (B < 1 || B > c->max_batch) return fail(c, DAVO_ERR_INVALID, "batch %d outside [1,%d]", B, c->max_batch);
     c->inputs_seen = true;
     HIP_TRY(c, hipSetDevice(c->device));
@@ -649,6 +772,8 @@ static int forward_entry(davo_ctx* c, int B, const uint8_t* img, const float* fl
         c->host = std::move(h);
     }
     HostStaging& hs = *c->host;
+    if (frames) { int rc = ensure_frame_set(c, 0); if (rc) return rc; }      // slot 0's: every slot is idle
+    FrameCursor cur;
     { int rc = judge_all(c); if (rc) return rc; }               // device-path batches issued before this call
     Run run = make_run(c, 0);                                   // slot 0, the base record
     // The base record holds RUNNING maxima like the ring's records (params.h): a record that starts at zero is raised by every wave of
@@ -682,7 +807,11 @@ static int forward_entry(davo_ctx* c, int B, const uint8_t* img, const float* fl
     for (int i = 0; i < nchunks; ++i) {
         const int b0 = i * chunk, nb = std::min(chunk, B - b0);
         hipStream_t cs = nchunks == 1 ? run.stream : hs.copy_stream.get();
-        { int rc = stage_inputs(c, hs.set, Inputs{img, flow, seg, depth}, b0, nb, false, c->pairs, cs); if (rc) return rc; }      // both pairs: the label maps whole
+        if (frames) {      // windows [b0, b0 + nb) take frames [b0, b0 + nb + 2): the two it shares with the sub-batch before are on the device already
+            const FrameSet& fs = c->frame_sets[0];
+            { int rc = stage_frames(c, fs, hs.set, FrameInputs{img, flow, seg, depth}, b0, nb, c->pairs, &cur, cs); if (rc) return rc; }
+            { int rc = gather_windows(c, hs.set, FrameInputs{fs.img.get(), nullptr, fs.seg.get(), fs.depth.get()}, b0, nb, c->pairs, cs); if (rc) return rc; }
+        } else { int rc = stage_inputs(c, hs.set, Inputs{img, flow, seg, depth}, b0, nb, false, c->pairs, cs); if (rc) return rc; }      // both pairs: the label maps whole
         if (nchunks > 1) {
             HIP_TRY(c, hipEventRecord(hs.copy_done[i].get(), cs));
             HIP_TRY(c, hipStreamWaitEvent(run.stream, hs.copy_done[i].get(), 0));
@@ -731,6 +860,10 @@ int davo_forward(davo_ctx* c, int B, const uint8_t* img, const float* flow, cons
 
 int davo_forward_depth(davo_ctx* c, int B, const uint8_t* img, const float* flow, const float* seg, const float* depth, float* pose_out) {
     return forward_entry(c, B, img, flow, seg, depth, pose_out, true);
+}
+
+int davo_forward_frames(davo_ctx* c, int N, const uint8_t* frames, const float* flow2, const float* seg, const float* depth, float* pose_out) {
+    return forward_entry(c, N, frames, flow2, seg, depth, pose_out, true, Exports{}, true);
 }
 
 int davo_set_feature_export(davo_ctx* c, int on) {

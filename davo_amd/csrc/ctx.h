@@ -100,6 +100,14 @@ struct InputSet {
     Inputs view() const { return Inputs{img.get(), flow.get(), seg.get(), depth.get()}; }
 };
 
+// A slot's frame buffer (window_gather.h): the frames of a frame-layout batch as the host entry points copy them, max_batch + 2
+// frames per plane, before window_gather expands them into the slot's staging set.  No flow (it is copied straight into the
+// staging set); depth only where the variant reads it.  Built whole by the slot's first `_frames' call (api.hip).
+struct FrameSet {
+    DevMem<void> img, seg, depth;
+    bool built() const { return static_cast<bool>(img); }
+};
+
 constexpr int SK_TILE_COUNTERS = 256;            // tiles of a split-K launch whose fix-up is folded in (forward.hip): at most one per CU
 
 // A batch davo_submit has issued whose poses have not been delivered to the caller's array yet (api.hip: streaming entry point).
@@ -285,8 +293,9 @@ struct davo_ctx {
     // heat export (davo_set_heat_export / davo_forward_heat, api.hip): a block of its own, absent with the export off
     std::optional<davo::HeatBlock> heat;
     // streaming host entry (davo_submit / davo_wait): staging input sets, pose ring, undelivered batches in issue order
-    davo::InputSet stream_sets[davo::MAX_INFLIGHT];     // one staging set per in-flight slot (built by the slot's first davo_submit)
+    davo::InputSet stream_sets[davo::MAX_INFLIGHT];     // one staging set per in-flight slot (built by the slot's first davo_submit, davo_submit_frames or davo_forward_device_frames)
     std::optional<davo::PoseRing> pose_ring;   // built by the first davo_submit
+    davo::FrameSet frame_sets[davo::MAX_INFLIGHT];      // frame layout: one frame buffer per in-flight slot (built by the slot's first davo_submit_frames; [0] also by davo_forward_frames)
     std::deque<davo::StreamJob> jobs;
     unsigned long long n_submitted = 0;
     davo::DevMem<float> d_reissue_pose;        // a re-issued batch writes here first; copied to its own pose buffer unless a later batch has taken that

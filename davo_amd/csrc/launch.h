@@ -74,6 +74,10 @@ hipError_t launch_se_depth_squeeze(bool fold, const float* d_depth, int B, int H
 hipError_t launch_mask_pack(int ld, const uint8_t* d_img, const float* d_flow, const void* d_seg, int label_fmt, const float* d_tab,
                             const Variant& v, int B, int H, int W, float* d_packed, int sel, hipStream_t s,
                             const float* d_depth = nullptr, const float* d_tab_far = nullptr, float depth_thr = 0.f);
+// window_gather.h: N windows of a frame-layout batch into the window-major planes every kernel above reads; every pointer 16-byte
+// aligned; a.f_flow null = the flow planes are in place already (the host entry points copy them there)
+struct GatherArgs;
+hipError_t launch_window_gather(const GatherArgs& a, int N, int label_fmt, hipStream_t s);
 // cnv1 / cnv2 / cnv3 (layer 0..2) from an LDS-staged input patch: conv_patch_cnvN_h3, or conv_patch_cnvN_f32 in float32 mode (f32);
 // fused: conv_patch_cnv1_h3<true, float | uint8_t> by label_fmt (f16x3 cnv1 only; p.seg is in that format)
 hipError_t launch_patch_layer(int layer, bool f32, bool fused, const ConvPatchParams& p, int nblk, hipStream_t s, int label_fmt = LABELS_F32);

@@ -1,5 +1,6 @@
 // launch_misc.hip — the small kernels of the path (SE squeeze/excite, mask + pack, pose head, the
 // cnv1 LDS-patch kernel, the direct-convolution cross-check) and the per-device attribute cache.
+#include <algorithm>
 #include <mutex>
 #include <set>
 #include <utility>
@@ -10,6 +11,7 @@
 #include "owned.h"
 #include "posenn_se.h"
 #include "prologue.h"
+#include "window_gather.h"
 
 namespace davo {
 
@@ -128,6 +130,24 @@ hipError_t launch_mask_pack(int ld, const uint8_t* d_img, const float* d_flow, c
     if (label_fmt == LABELS_F32) return mask_pack_as<float>(ld, grid, s, d_img, d_flow, d_seg, d_tab, v, B, sel, H, W, d_packed, split ? &ds : nullptr);
     if (label_fmt == LABELS_U8) return mask_pack_as<uint8_t>(ld, grid, s, d_img, d_flow, d_seg, d_tab, v, B, sel, H, W, d_packed, split ? &ds : nullptr);
     return hipErrorInvalidValue;
+}
+
+hipError_t launch_window_gather(const GatherArgs& a, int N, int label_fmt, hipStream_t s) {
+    if (N < 1 || a.H < 1 || a.W < 4 || a.W % 4 || ((size_t)a.H * a.W) % 16 || !a.f_img || !a.f_seg || !a.w_img || !a.w_seg || !a.w_flow ||
+        (a.f_depth && !a.w_depth))
+        return hipErrorInvalidValue;
+    if (((uintptr_t)a.f_img | (uintptr_t)a.f_seg | (uintptr_t)a.f_depth | (uintptr_t)a.f_flow | (uintptr_t)a.w_img | (uintptr_t)a.w_seg |
+         (uintptr_t)a.w_depth | (uintptr_t)a.w_flow) & 15)
+        return hipErrorInvalidValue;
+    // the largest job decides the pieces per job (a flow plane, else a frame or a float32 plane); at most 8, the rest in rounds
+    const size_t HW = (size_t)a.H * a.W;
+    const size_t vecs = a.f_flow ? HW / 2 : (a.W % 16 == 0 ? HW * 3 / 16 : HW * 3 / 4);
+    const unsigned gx = (unsigned)std::min<size_t>(8, (std::max(vecs, HW / 4) + GATHER_PIECE - 1) / GATHER_PIECE);
+    const dim3 grid(gx, (unsigned)N, GATHER_JOBS);
+    if (label_fmt == LABELS_F32) hipLaunchKernelGGL(window_gather<float>, grid, dim3(256), 0, s, a);
+    else if (label_fmt == LABELS_U8) hipLaunchKernelGGL(window_gather<uint8_t>, grid, dim3(256), 0, s, a);
+    else return hipErrorInvalidValue;
+    return hipGetLastError();
 }
 
 hipError_t launch_patch_layer(int layer, bool f32, bool fused, const ConvPatchParams& p, int nblk, hipStream_t s, int label_fmt) {

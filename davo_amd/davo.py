@@ -289,6 +289,91 @@ class Engine:
             self._check(self._L.davo_submit(self._ctx, B, img.ctypes.data_as(vp), flow.ctypes.data_as(vp), seg.ctypes.data_as(vp),
                                             out.ctypes.data_as(vp), int(hold)))
 
+    # ---- frame layout (include/davo_hip.h "Frame sequences"; davo_amd/frames.py) -------------------------------------
+    def _frame_label_arg(self, seg, convert=True):
+        """The label maps of a frame-layout batch: C-contiguous [N+2,H,W,1] of the engine's format.  As _label_arg: a byte array
+        handed to a float32 engine, or anything but bytes to a byte engine, is a ValueError; nothing is converted silently."""
+        dt = np.asarray(seg).dtype
+        if self.labels == "u8" and dt != np.uint8:
+            raise ValueError("this engine takes uint8 label maps (labels='u8'), got dtype %s: convert with davo_amd.labels_to_u8" % dt)
+        if self.labels != "u8" and dt == np.uint8:
+            raise ValueError("this engine takes float32 label maps (labels='f32'), got uint8: create it with labels='u8'")
+        if convert:
+            seg = np.ascontiguousarray(seg, LABEL_DTYPES[self.labels])
+        return seg[..., None] if seg.ndim == 3 else seg
+
+    def _check_frames(self, frames, flow2, seg):
+        N = flow2.shape[0]
+        if frames.shape != (N + 2, self.H, self.W, 3):
+            raise ValueError("frames shape %s != %s" % (frames.shape, (N + 2, self.H, self.W, 3)))
+        if flow2.shape != (N, 2, self.H, self.W, 2):
+            raise ValueError("flow2 shape %s != %s" % (flow2.shape, (N, 2, self.H, self.W, 2)))
+        if seg.shape != (N + 2, self.H, self.W, 1):
+            raise ValueError("seg shape %s != %s" % (seg.shape, (N + 2, self.H, self.W, 1)))
+        return N
+
+    def _frames_depth_arg(self, depth, N, convert=True):
+        """The depth planes of a frame-layout batch ([N+2,H,W,1] float32), or None for a variant that reads none."""
+        if not self.cfg.needs_depth:
+            return None
+        if depth is None:
+            raise ValueError("frames, flow2, seg and depth inputs are all required for version `%s'" % self.cfg.version)
+        if convert:
+            depth = np.ascontiguousarray(depth, np.float32)
+        if depth.shape != (N + 2, self.H, self.W, 1):
+            raise ValueError("depth shape %s != %s" % (depth.shape, (N + 2, self.H, self.W, 1)))
+        return depth
+
+    def forward_frames(self, frames, flow2, seg, depth=None):
+        """forward() on the frame layout (include/davo_hip.h: davo_forward_frames): ``frames`` u8 [N+2,H,W,3], ``flow2`` f32
+        [N,2,H,W,2], ``seg`` [N+2,H,W,1] in the engine's label format, ``depth`` f32 [N+2,H,W,1] for a depth-source variant;
+        window n is frames (n, n+1, n+2).  -> [N,2,6], the bits of forward() on davo_amd.windows_from_frames of the same arrays."""
+        frames = np.ascontiguousarray(frames, np.uint8)
+        flow2 = np.ascontiguousarray(flow2, np.float32)
+        seg = self._frame_label_arg(seg)
+        N = self._check_frames(frames, flow2, seg)
+        depth = self._frames_depth_arg(depth, N)
+        out = np.empty((N, 2, 6), np.float32)
+        vp = ctypes.c_void_p
+        self._check(self._L.davo_forward_frames(self._ctx, N, frames.ctypes.data_as(vp), flow2.ctypes.data_as(vp), seg.ctypes.data_as(vp),
+                                                depth.ctypes.data_as(vp) if depth is not None else None, out.ctypes.data_as(vp)))
+        return out
+
+    def submit_frames(self, frames, flow2, seg, out, hold=0, depth=None):
+        """submit() on the frame layout (include/davo_hip.h: davo_submit_frames; shapes as forward_frames).  ``out`` [N,2,6] and
+        ``hold`` as submit's; window and frame submits count alike."""
+        ok = lambda a, dt: isinstance(a, np.ndarray) and a.dtype == dt and a.flags.c_contiguous      # noqa: E731
+        if not (ok(frames, np.uint8) and ok(flow2, np.float32) and ok(seg, LABEL_DTYPES[self.labels]) and seg.ndim == 4):
+            if hold:
+                raise ValueError("submit_frames(hold > 0) needs C-contiguous uint8 / float32 / %s arrays (a converted copy would not outlive the call)"
+                                 % LABEL_DTYPES[self.labels])
+            frames = np.ascontiguousarray(frames, np.uint8)
+            flow2 = np.ascontiguousarray(flow2, np.float32)
+            seg = self._frame_label_arg(seg)
+        N = self._check_frames(frames, flow2, seg)
+        if self.cfg.needs_depth and hold and not ok(depth, np.float32):
+            raise ValueError("submit_frames(hold > 0) needs a C-contiguous float32 depth array (a converted copy would not outlive the call)")
+        depth = self._frames_depth_arg(depth, N)
+        if not (ok(out, np.float32) and out.shape == (N, 2, 6)):
+            raise ValueError("out must be a C-contiguous float32 array of shape (%d, 2, 6)" % N)
+        vp = ctypes.c_void_p
+        self._check(self._L.davo_submit_frames(self._ctx, N, frames.ctypes.data_as(vp), flow2.ctypes.data_as(vp), seg.ctypes.data_as(vp),
+                                               depth.ctypes.data_as(vp) if depth is not None else None, out.ctypes.data_as(vp), int(hold)))
+
+    def forward_device_frames(self, N, d_frames, d_flow2, d_seg, d_pose, timed=False, depth=None):
+        """forward_device() on the frame layout (include/davo_hip.h: davo_forward_device_frames): DeviceBuffers of frames
+        [N+2,H,W,3], flow2 [N,2,H,W,2], label maps [N+2,H,W,1] and - a depth-source variant - ``depth`` [N+2,H,W,1].  The timed
+        form's milliseconds include the gather."""
+        ms = ctypes.c_float(0.0)
+        if getattr(d_seg, "dtype", None) is not None and (d_seg.dtype == np.uint8) != (self.labels == "u8"):
+            raise ValueError("d_seg holds %s label maps, this engine takes labels='%s'" % (d_seg.dtype, self.labels))
+        if self.cfg.needs_depth and depth is None:
+            raise ValueError("frames, flow2, seg and depth inputs are all required for version `%s'" % self.cfg.version)
+        self._check(self._L.davo_forward_device_frames(self._ctx, int(N), d_frames.ptr, d_flow2.ptr, d_seg.ptr,
+                                                       depth.ptr if depth is not None else None, d_pose.ptr,
+                                                       ctypes.byref(ms) if timed else None))
+        return ms.value if timed else None
+
     def wait(self, leave_pending=0):
         """Deliver submitted batches until at most ``leave_pending`` are outstanding (include/davo_hip.h: davo_wait)."""
         self._check(self._L.davo_wait(self._ctx, int(leave_pending)))

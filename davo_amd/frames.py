@@ -1,0 +1,93 @@
+"""The frame layout of a batch (include/davo_hip.h: "Frame sequences") on the host: conversion to and from the reference's
+window layout, and the table of what a batch reads.
+
+A sequence of N windows is N + 2 frames; window n is (src0, tgt, src1) = frames (n, n + 1, n + 2):
+
+* ``frames`` u8  ``[N+2,H,W,3]``
+* ``flow2``  f32 ``[N,2,H,W,2]``   planes (tgt->src0, tgt->src1) of window n - planes 0, 1 of the window layout's ``[B,4,H,W,2]``
+* ``seg``        ``[N+2,H,W,1]``   float32 or uint8 (davo_amd.labels_to_u8)
+* ``depth``  f32 ``[N+2,H,W,1]``   depth-source variants only
+
+The window layout is the reference's (``data_loader.py:537-557``, ``davo.py:978-1004``): strip ``[B,H,3W,3]`` src0|tgt|src1,
+planes ``[B,3,H,W,1]`` in file order src0, tgt, src1.  ``Engine.forward_frames`` / ``submit_frames`` / ``forward_device_frames`` take
+the frame layout as it is; the functions here are for callers and tests that need the other one."""
+import ctypes
+
+import numpy as np
+
+from . import _lib
+from .labels import LABEL_FORMATS, check_label_format
+from .version import ATT_SOURCE
+
+PAIRS = {"src0": 1, "src1": 2, "both": 3}
+
+
+def windows_from_frames(frames, flow2, seg, depth=None):
+    """Frame layout -> the window-layout arrays ``(img, flow, seg)`` - ``(img, flow, seg, depth)`` when depth is given - that the
+    window entry points take for the same N windows: byte for byte what the device gathers.  Flow planes 2, 3 are zero."""
+    frames, flow2, seg = np.asarray(frames), np.asarray(flow2), np.asarray(seg)
+    N = flow2.shape[0]
+    if frames.ndim != 4 or frames.shape[0] != N + 2 or frames.shape[3] != 3:
+        raise ValueError("frames shape %s: expected [N+2,H,W,3] for the %d windows of flow2" % (frames.shape, N))
+    H, W = frames.shape[1:3]
+    if flow2.shape != (N, 2, H, W, 2):
+        raise ValueError("flow2 shape %s != %s" % (flow2.shape, (N, 2, H, W, 2)))
+    seg = seg[..., None] if seg.ndim == 3 else seg
+    if seg.shape != (N + 2, H, W, 1):
+        raise ValueError("seg shape %s != %s" % (seg.shape, (N + 2, H, W, 1)))
+    img = np.empty((N, H, 3 * W, 3), frames.dtype)
+    for k in range(3):
+        img[:, :, k * W:(k + 1) * W] = frames[k:k + N]
+    flow = np.zeros((N, 4, H, W, 2), flow2.dtype)
+    flow[:, :2] = flow2
+    out = (img, flow, np.stack([seg[k:k + N] for k in range(3)], axis=1))
+    if depth is not None:
+        depth = np.asarray(depth)
+        if depth.shape != (N + 2, H, W, 1):
+            raise ValueError("depth shape %s != %s" % (depth.shape, (N + 2, H, W, 1)))
+        out += (np.stack([depth[k:k + N] for k in range(3)], axis=1),)
+    return out
+
+
+def frames_from_windows(img, flow, seg, depth=None):
+    """The inverse for CONSECUTIVE windows (window n + 1 starts one frame after window n): ``(frames, flow2, seg)`` -
+    ``(frames, flow2, seg, depth)`` with depth.  Every frame but the first and the last is held by two or three windows;
+    where they disagree a ValueError names the window and the plane (img / seg / depth, 0 src0, 1 tgt, 2 src1)."""
+    img, flow, seg = np.asarray(img), np.asarray(flow), np.asarray(seg)
+    B, H, W3 = img.shape[:3]
+    W = W3 // 3
+    if img.shape != (B, H, 3 * W, 3) or flow.shape != (B, 4, H, W, 2):
+        raise ValueError("img %s / flow %s are not [B,H,3W,3] / [B,4,H,W,2]" % (img.shape, flow.shape))
+    seg = seg[..., None] if seg.ndim == 4 else seg
+    planes = {"img": np.stack([img[:, :, k * W:(k + 1) * W] for k in range(3)], axis=1), "seg": seg}
+    if depth is not None:
+        planes["depth"] = np.asarray(depth)
+    out = {}
+    for name, p in planes.items():
+        if p.shape[:4] != (B, 3, H, W):
+            raise ValueError("%s shape %s is not [B,3,H,W,...] of the %d windows of img" % (name, p.shape, B))
+        f = np.concatenate([p[:, 0], p[-1, 1:]])                   # src0 of every window, then the last window's tgt and src1
+        for n in range(B):
+            for k in range(3):
+                if not np.array_equal(p[n, k], f[n + k], equal_nan=p.dtype.kind == "f"):
+                    raise ValueError("window %d, %s plane %d does not hold frame %d as its neighbours do: the windows are not "
+                                     "consecutive windows of one sequence" % (n, name, k, n + k))
+        out[name] = f
+    res = (out["img"], np.ascontiguousarray(flow[:, :2]), out["seg"])
+    return res + ((out["depth"],) if depth is not None else ())
+
+
+def frames_plan(H, W, N, pairs="both", att_source="se_flow", labels="f32"):
+    """What a frame-layout batch of N windows reads (include/davo_hip.h: davo_frames_plan - the function the library's copies and
+    its gather kernel are driven by; no GPU needed): ``{'frames', 'seg', 'depth', 'flow': (lo, hi), 'link_bytes': int}`` - frame
+    ranges of the pixels, the label maps and the depth planes ((0, 0) where the source reads no depth), the flow planes, and the
+    bytes the host entry points send.  ``att_source``: a name of davo_amd.version.ATT_SOURCE or its number."""
+    if pairs not in PAIRS:
+        raise ValueError("pairs must be 'both', 'src0' or 'src1', got %r" % (pairs,))
+    att = ATT_SOURCE[att_source] if isinstance(att_source, str) else int(att_source)
+    r = (ctypes.c_int * 8)()
+    nbytes = ctypes.c_longlong(0)
+    rc = _lib.lib().davo_frames_plan(int(H), int(W), int(N), PAIRS[pairs], att, LABEL_FORMATS[check_label_format(labels)], r, ctypes.byref(nbytes))
+    if rc != 0:
+        raise ValueError("davo_frames_plan(%r) refused its arguments" % ((H, W, N, pairs, att_source, labels),))
+    return {"frames": (r[0], r[1]), "seg": (r[2], r[3]), "depth": (r[4], r[5]), "flow": (r[6], r[7]), "link_bytes": nbytes.value}

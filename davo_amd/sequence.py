@@ -160,6 +160,12 @@ class PoseStream:
             self.engine.set_pairs(pairs)
         self.engine.submit(img, flow, seg, out, self.hold, depth=depth)
 
+    def submit_frames(self, frames, flow2, seg, out, depth=None, pairs=None):
+        """submit on the frame layout (Engine.submit_frames; davo_amd/frames.py): each frame crosses the link once per batch."""
+        if pairs is not None and pairs != self.engine.pairs:
+            self.engine.set_pairs(pairs)
+        self.engine.submit_frames(frames, flow2, seg, out, self.hold, depth=depth)
+
     def drain(self):
         self.engine.synchronize()
 
@@ -293,6 +299,36 @@ def run_sequence(infer_fn, load_windows, n_frames, batch_size, rank=0, world=1, 
     if timing is not None:
         timing.update(gather_s=t1 - t0, stitch_s=time.perf_counter() - t1, windows_this_rank=hi - lo)
     return traj, poses
+
+
+def run_frames(engine_or_stream, load_frames, n_frames, batch_size, pairs="both"):
+    """run_sequence for a caller that holds frames, not windows (include/davo_hip.h "Frame sequences"): the n_frames - 2 windows
+    of a sequence in batches of ``batch_size`` through the frame-layout entry points - ``Engine.forward_frames``, or a PoseStream's
+    ``submit_frames`` (batches then overlap, and are drained at the end).  ``load_frames(lo, hi)`` returns the frames [lo, hi + 2)
+    and the flow of the windows [lo, hi): ``(frames, flow2, seg)``, or ``(frames, flow2, seg, depth)`` for a depth-source variant;
+    with a stream the arrays stay valid as its ``hold`` says.  A short last batch is issued short - nothing is padded.
+    ``pairs``: 'both' or 'trajectory' (batch_pairs: the batch with window 0 runs both pairs, every other one tgt->src1 alone; the
+    engine is left on the last batch's selection).  Returns ``(traj, poses)`` like run_sequence."""
+    n_windows = n_frames - 2
+    batch_pairs(pairs, 0)                                 # an unknown mode fails before anything is loaded
+    streamed = hasattr(engine_or_stream, "drain")
+    poses = np.zeros((max(n_windows, 0), 2, 6), np.float32)
+    for lo in range(0, n_windows, batch_size):
+        hi = min(lo + batch_size, n_windows)
+        parts = tuple(load_frames(lo, hi))
+        extra = {"depth": parts[3]} if len(parts) == 4 else {}
+        sel = batch_pairs(pairs, lo)
+        if streamed:
+            if sel is not None:
+                extra["pairs"] = sel
+            engine_or_stream.submit_frames(*parts[:3], poses[lo:hi], **extra)      # delivered straight into its rows
+        else:
+            if sel is not None and engine_or_stream.pairs != sel:
+                engine_or_stream.set_pairs(sel)
+            poses[lo:hi] = engine_or_stream.forward_frames(*parts[:3], **extra)
+    if streamed:
+        engine_or_stream.drain()
+    return stitch_trajectory(poses), poses
 
 
 # ---- several sequences in one launch (run_inference.sh and kitti_benchmark/pose_kitti_eval.sh:28-37 loop over 00-10) ------

@@ -116,6 +116,38 @@ def make_depth(B, H=128, W=416, seed=SEED, first_window=0):
     return depth
 
 
+def make_frames(n_frames, H=128, W=416, seed=SEED, depth=False, labels="f32"):
+    """A synthetic sequence in the frame layout (davo_amd/frames.py): ``(frames, flow2, seg)`` - ``(frames, flow2, seg, depth)`` with
+    ``depth`` - for the n_frames - 2 windows of n_frames frames: frames u8 [n,H,W,3], flow2 f32 [n-2,2,H,W,2] (per window, the
+    statistics of ``make_inputs``), seg [n,H,W,1] (8x8 blocks of train ids, 3 % ignore; uint8 with labels="u8"), depth f32
+    [n,H,W,1] (the fields of ``make_depth``).  Every frame and every window draws from streams of its own, so no two frames agree
+    in any plane, and consecutive windows share their frames by construction - which ``make_inputs``' windows, drawn one by one,
+    do not."""
+    from .labels import check_label_format, labels_to_u8
+    check_label_format(labels)
+    if n_frames < 3:
+        raise ValueError("a sequence needs at least 3 frames, got %d" % n_frames)
+    frames = np.empty((n_frames, H, W, 3), np.uint8)
+    seg = np.empty((n_frames, H, W, 1), np.float32)
+    flow2 = np.empty((n_frames - 2, 2, H, W, 2), np.float32)
+    hb, wb = (H + 7) // 8, (W + 7) // 8
+    for f in range(n_frames):
+        r = splitmix64(seed, _stream("frame_img") + 7919 * f, (H * W * 3 + 7) // 8)
+        frames[f] = r.view(np.uint8)[: H * W * 3].reshape(H, W, 3)
+        r = splitmix64(seed, _stream("frame_seg") + 7919 * f, hb * wb)
+        ids = (r % np.uint64(NUM_SEG_CLASSES)).astype(np.float32)
+        ids[((r >> np.uint64(32)) % np.uint64(100)) < np.uint64(3)] = 255.0
+        seg[f, :, :, 0] = np.repeat(np.repeat(ids.reshape(hb, wb), 8, axis=0), 8, axis=1)[:H, :W]
+    for w in range(n_frames - 2):
+        v = normalish(seed, _stream("frame_flow") + 7919 * w, 2 * H * W * 2)
+        flow2[w] = (v * 15.384229 + 0.32140523).astype(np.float32).reshape(2, H, W, 2)
+    out = (frames, flow2, labels_to_u8(seg) if labels == "u8" else seg)
+    if depth:
+        planes = make_depth((n_frames + 2) // 3, H, W, seed=seed, first_window=1000003)      # three planes per draw, all different
+        out += (np.ascontiguousarray(planes.reshape(-1, H, W, 1)[:n_frames]),)
+    return out
+
+
 def make_weights(version_or_cfg, seed=SEED):
     """dict TF-name -> float32 array (HWIO conv kernels, [in,out] dense kernels).
 

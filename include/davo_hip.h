@@ -219,6 +219,56 @@ enum { DAVO_PAIRS_SRC0 = 1, DAVO_PAIRS_SRC1 = 2, DAVO_PAIRS_BOTH = 3 };
 int davo_set_pairs(davo_ctx* ctx, int pairs);
 int davo_get_pairs(const davo_ctx* ctx);
 
+/* Frame sequences.  The entry points above take the reference's per-window dump format, in which consecutive windows of a
+ * sequence repeat two of their three frames: a caller that holds a video (a camera, a decoder, a simulator) would build every
+ * frame into three strips and send it across the link three times.  The `_frames' forms take every frame once.  N windows
+ * (1 <= N <= max_batch) come as N + 2 frames; window n is (src0, tgt, src1) = frames (n, n + 1, n + 2):
+ *   frames   uint8 [N+2,H,W,3]
+ *   flow2    f32   [N,2,H,W,2]   planes (tgt->src0, tgt->src1) of window n: planes 0, 1 of davo_forward's [B,4,H,W,2], the two the
+ *                                path reads
+ *   seg            [N+2,H,W,1]   float32, or bytes on a DAVO_LABELS_U8 context (davo_set_label_format)
+ *   depth    f32   [N+2,H,W,1]   in the signature: NULL (or anything, ignored) where the variant reads no depth; where it does
+ *                                (att_source 11, 12, 13) a NULL pointer returns DAVO_ERR_INVALID with a message
+ *   pose_out f32   [N,2,6]       as davo_forward's
+ * Device pointers are 16-byte aligned (DAVO_ERR_INVALID otherwise).
+ * What is computed is the window form's, bit for bit: on the device one launch per batch (csrc/window_gather.h) expands the
+ * frames into the window layout of a staging set of the context - the windows the caller would have built, byte for byte -
+ * and the forward runs on that set like on any window batch.  So everything said above about davo_forward, davo_submit and
+ * davo_forward_device holds for davo_forward_frames, davo_submit_frames and davo_forward_device_frames: synchronous or
+ * streamed delivery and its order, `hold' (it counts the `_frames' and the window submits of a context alike), the f16x3 range
+ * ticket and the re-issue from the library's own copy of the batch, davo_wait, davo_pending, davo_set_inflight,
+ * davo_set_stream, davo_set_pairs, and davo_debug_read on the batch issued last (it sees the gathered window batch).  Window
+ * and frame calls may be mixed freely on one context.  Where the forms differ:
+ *   - davo_forward_frames sub-batches like davo_forward ("host_chunk"): windows [b0, b0 + nb) take frames [b0, b0 + nb + 2), and
+ *     the two frames a sub-batch shares with the one before it are not sent again.  Its poses are the bits of davo_forward on
+ *     the same windows.
+ *   - davo_forward_device_frames gathers into the staging set of its in-flight slot (built by the slot's first such call) and
+ *     runs that set: the caller's four buffers are free as soon as work ordered behind the call on the context's stream may
+ *     run, with or without "stable_inputs" (the range guard snapshots the staging set, which is the library's).  The timed form
+ *     brackets the gather too.
+ *   - each in-flight slot of the host entry points gets a frame buffer of max_batch + 2 frames per plane kind at its first
+ *     `_frames' call; a context that never makes one allocates nothing for the layout and issues no launch for it.
+ * Pair selection (davo_set_pairs) narrows what is copied and gathered to the frames some selected window reads; the skipped
+ * frames and flow planes may hold anything (device path: need not be filled).  Frames [lo, hi) of the caller's arrays:
+ *   selection   frames (pixels)   flow plane   label maps, target not attended / attended   depth, sources 11, 12 / 13
+ *   both        [0, N+2)          0, 1         [0, N+2)                                     [0, N+2)
+ *   src0        [0, N+1)          0            [0, N)   / [0, N+1)                          [0, N+1) / [0, N)
+ *   src1        [1, N+2)          1            [2, N+2) / [1, N+2)                          [1, N+2) / [2, N+2)
+ * Bytes across the link per window of a long batch at 128x416, both pairs, no depth: 159,744 (one frame) + 851,968 (two flow
+ * planes) + 212,992 (one float32 label map; 53,248 as bytes) = 1,224,704 (1,064,960 with byte labels) against the window
+ * form's 1,757,184 (1,437,696); each batch sends its two extra frames once more.
+ * davo_frames_plan is that table as a function (no context, no device): ranges[8] receives the [lo, hi) pairs of the frames,
+ * the label maps, the depth planes (0, 0 where att_source reads none) and the flow planes of a batch of N windows, *link_bytes
+ * the bytes the host entry points copy for it; either pointer may be NULL.  DAVO_ERR_INVALID for an argument out of range.
+ * There are no `_frames' forms of davo_calibrate, davo_forward_features and davo_forward_heat. */
+int davo_forward_frames(davo_ctx* ctx, int N, const uint8_t* frames, const float* flow2, const float* seg,
+                        const float* depth, float* pose_out);
+int davo_submit_frames(davo_ctx* ctx, int N, const uint8_t* frames, const float* flow2, const float* seg,
+                       const float* depth, float* pose_out, int hold);
+int davo_forward_device_frames(davo_ctx* ctx, int N, const void* d_frames, const void* d_flow2, const void* d_seg,
+                               const void* d_depth, void* d_pose, float* elapsed_ms);
+int davo_frames_plan(int H, int W, int N, int pairs, int att_source, int label_fmt, int* ranges, long long* link_bytes);
+
 /* Feature export.  Replaces DAVO.inference(sess, mode='feature') (davo.py:1553-1569), the call generate_feature_map.py:183-260
  * makes to draw the class-attention table and the cnv6 feature maps: the poses of davo_forward and, from the same forward, the
  * tensors of the reference's `masks', `features' and `images' fetches.  Frames are in the order tgt, src0, src1 throughout.

@@ -188,6 +188,84 @@ def labels_measurement(arms, rounds, n=30, H=128, W=416):
             e.close()
 
 
+def layout_measurement(arms, rounds, n=30, H=128, W=416):
+    """`--layout windows frames [--rounds R]` (default: windows only): the frame layout (include/davo_hip.h "Frame sequences")
+    against the window layout, ONE engine per label format (window and frame calls mix freely on a context), the arms alternating
+    inside every round (round 0 warms up), f16x3 and float32, float and byte labels:
+      resident  ms per davo_forward_device / davo_forward_device_frames step at B = 32 with the inputs in HBM: per arm the median
+                and the spread (max - min) of its rounds.  The difference of the medians is what the gather costs;
+      streamed  windows/s of davo_submit / davo_submit_frames from page-locked memory at B = 32 and at batch 1, with 1..4 slots,
+                best of the rounds, beside the H2D bytes per window (davo_frames_plan's for the frame arm)."""
+    from davo_amd import frames_plan, pinned_empty, windows_from_frames
+    cfg = parse_version(FLAGSHIP_VERSION)
+    weights = synth.make_weights(cfg)
+    hw = H * W
+    for labels in ("f32", "u8"):
+        lab = 4 if labels == "f32" else 1
+        for B in (32, 1):
+            fr = synth.make_frames(B + 2, H, W, labels=labels)
+            host = {"frames": fr, "windows": windows_from_frames(*fr)}
+            e = Engine(cfg, H, W, B, labels=labels)
+            e.load_weights(weights)
+            pinned = {arm: tuple(pinned_empty(a.shape, a.dtype) for a in host[arm]) for arm in arms}
+            dev = {}
+            for arm in arms:
+                for d, a in zip(pinned[arm], host[arm]):
+                    d[...] = a
+                dev[arm] = tuple(e.alloc(a.nbytes).upload(a) for a in host[arm]) + (e.alloc(B * 48),)
+            issue = {"windows": e.submit, "frames": e.submit_frames}
+            step_fn = {"windows": e.forward_device, "frames": e.forward_device_frames}
+            link = {"windows": hw * 9 + hw * 16 + hw * lab * (2 if B >= 4 else 3),
+                    "frames": frames_plan(H, W, B, "both", cfg.att_source, labels)["link_bytes"] // B}
+            nb = n if B > 1 else 20 * n
+            outs = [np.empty((B, 2, 6), np.float32) for _ in range(nb)]
+            for prec in ("f16x3", "f32"):
+                e.set_precision(prec)
+                if B == 32:
+                    e.set_inflight(1)
+                    step = {arm: [] for arm in arms}
+                    for r in range(rounds + 1):
+                        for arm in arms:
+                            for _ in range(5):
+                                step_fn[arm](B, *dev[arm])
+                            e.synchronize()
+                            t0 = time.perf_counter()
+                            for _ in range(n):
+                                step_fn[arm](B, *dev[arm])
+                            e.synchronize()
+                            if r:
+                                step[arm].append((time.perf_counter() - t0) / n * 1e3)
+                    for arm in arms:
+                        v = sorted(step[arm])
+                        print("resident %-7s %-5s B=%d labels=%-3s: median %.4f ms per step, spread %.4f (rounds %s)"
+                              % (arm, prec, B, labels, v[len(v) // 2], v[-1] - v[0], " ".join("%.4f" % x for x in step[arm])), flush=True)
+                for slots in (1, 2, 3, 4):
+                    e.set_inflight(slots)
+                    rates = {arm: [] for arm in arms}
+                    for r in range(rounds + 1):
+                        for arm in arms:
+                            t0 = time.perf_counter()
+                            for o in outs:
+                                issue[arm](*pinned[arm], o, hold=8)
+                            e.synchronize()
+                            if r:
+                                rates[arm].append(B * nb / (time.perf_counter() - t0))
+                    for arm in arms:
+                        print("streamed %-7s %-5s B=%-2d %d slot(s) labels=%-3s: %9.1f windows/s best, rounds %s; %d B H2D per window -> %.1f GB/s"
+                              % (arm, prec, B, slots, labels, max(rates[arm]), " ".join("%.0f" % x for x in rates[arm]), link[arm],
+                                 link[arm] * max(rates[arm]) / 1e9), flush=True)
+            e.close()
+
+
+if "--layout" in sys.argv:
+    import argparse
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--layout", nargs="+", choices=("windows", "frames"), default=["windows"])
+    ap.add_argument("--rounds", type=int, default=4)
+    args = ap.parse_args()
+    layout_measurement(args.layout, args.rounds)
+    sys.exit(0)
+
 if "--batch1" in sys.argv:
     batch1_measurement()
     sys.exit(0)
