@@ -3,7 +3,10 @@
 // conv_igemm_h3.h, conv_igemm_h3s.h, conv_patch_h3.h and prologue.h and are launched through launch.h.
 //
 // Translation units (built in parallel by davo_amd/_lib.py, linked into one shared library):
-//   api.hip         extern "C" entry points (context, weights, forward, calibration, test hooks); builds the context's resource groups
+//   api.hip         extern "C": context life cycle, weights, settings and the option table, range-state calls, davo_synchronize
+//   entry.hip       extern "C": the calls that take a batch (device, streaming and host forward families, both layouts), delivery
+//   export.hip      extern "C": the feature and heat exports (davo_set_*_export, davo_forward_features, davo_forward_heat)
+//   hooks.hip       extern "C": measurement and test hooks (davo_debug_read, davo_conv2d_same, plan and profile calls, memory helpers)
 //   forward.hip     the forward plan of the pose path (which kernel, which buffers, in what order)
 //   range_guard.hip the f16x3 range guard: records, verdicts, calibration, re-issues, tickets (its bookkeeping: range_book.h)
 //   plan.hip        launch planning: tile shapes and whole-round launch splits (pure host logic)
@@ -102,7 +105,7 @@ struct InputSet {
 
 // A slot's frame buffer (window_gather.h): the frames of a frame-layout batch as the host entry points copy them, max_batch + 2
 // frames per plane, before window_gather expands them into the slot's staging set.  No flow (it is copied straight into the
-// staging set); depth only where the variant reads it.  Built whole by the slot's first `_frames' call (api.hip).
+// staging set); depth only where the variant reads it.  Built whole by the slot's first `_frames' call (entry.hip: acquire_stager).
 struct FrameSet {
     DevMem<void> img, seg, depth;
     bool built() const { return static_cast<bool>(img); }
@@ -110,7 +113,7 @@ struct FrameSet {
 
 constexpr int SK_TILE_COUNTERS = 256;            // tiles of a split-K launch whose fix-up is folded in (forward.hip): at most one per CU
 
-// A batch davo_submit has issued whose poses have not been delivered to the caller's array yet (api.hip: streaming entry point).
+// A batch davo_submit has issued whose poses have not been delivered to the caller's array yet (entry.hip: streaming entry point).
 // Its inputs live in the staging set of its in-flight slot (at most MAX_INFLIGHT slots), its poses in entry `pr` of a ring of STREAM_POSES device
 // buffers with page-locked host twins, so neither a re-issue nor the caller's buffer recycling can touch another batch's data.
 constexpr int STREAM_POSES = 8;
@@ -122,7 +125,7 @@ struct StreamJob {
     unsigned seq;                              // ... its sequence number
 };
 
-// How one batch runs.  The entry point (api.hip) fills one on its stack and forward_device hands it down to every layer runner:
+// How one batch runs.  The entry point (entry.hip) fills one on its stack and forward_device hands it down to every layer runner:
 // the forward is a function of (context, Run, batch), and no entry point leaves anything behind on the context for it.
 struct Run {
     int slot = 0;                              // the in-flight slot: its workspace is c->slots[slot], its per-slot scratch region `slot`
@@ -276,7 +279,7 @@ struct davo_ctx {
     davo::DevMem<unsigned> d_range_base;       // [1 + RANGE_RING][RANGE_WORDS] (params.h): record 0 serves the host path, calibration and re-issues; 1.. the ring
     // Range recovery (davo_set_option "auto_range", default on): every device-path batch is judged on a record of its own, at the
     // latest when its ring slot is needed again (RANGE_RING batches later) or at davo_synchronize; a failed verdict re-issues that
-    // batch from the context's own copy of its inputs - recalibrated, or on the float32 kernels (api.hip)
+    // batch from the context's own copy of its inputs - recalibrated, or on the float32 kernels (range_guard.hip)
     bool opt_auto_range = true;
     bool opt_stable_inputs = false;            // "stable_inputs": the caller keeps inputs unchanged until the verdict, no copies are taken
     davo::RangeBook book;                      // the guard's bookkeeping: ring cursor, tickets, pose spans, deferred verdict (range_book.h)
@@ -286,11 +289,11 @@ struct davo_ctx {
     std::string range_report;                  // what the range management last did, in words (davo_range_report)
     long long n_recalibrations = 0, n_f32_batches = 0, n_reissued = 0;
     int host_chunk = 8;                        // davo_forward: windows per sub-batch (davo_set_option "host_chunk"; 0 = whole batch)
-    // feature export (davo_set_feature_export / davo_forward_features, api.hip): one device block for fx->cap windows of every
+    // feature export (davo_set_feature_export / davo_forward_features, export.hip): one device block for fx->cap windows of every
     // export tensor, absent with the export off
     bool fx_on = false;
     std::optional<davo::FxBlock> fx;
-    // heat export (davo_set_heat_export / davo_forward_heat, api.hip): a block of its own, absent with the export off
+    // heat export (davo_set_heat_export / davo_forward_heat, export.hip): a block of its own, absent with the export off
     std::optional<davo::HeatBlock> heat;
     // streaming host entry (davo_submit / davo_wait): staging input sets, pose ring, undelivered batches in issue order
     davo::InputSet stream_sets[davo::MAX_INFLIGHT];     // one staging set per in-flight slot (built by the slot's first davo_submit, davo_submit_frames or davo_forward_device_frames)
@@ -413,6 +416,43 @@ int forward_device(davo_ctx* c, const Run& run, int B, const Inputs& in, void* d
 // ---- api.hip --------------------------------------------------------------------------------
 int zero_now(davo_ctx* c, void* p, size_t bytes);                              // hipMemset that returns when the bytes ARE zero
 int alloc_input_set(davo_ctx* c, InputSet* s, bool zero_unread);               // *s is assigned whole, or left as it was
+
+// ---- export.hip -----------------------------------------------------------------------------
+// what a davo_forward_features / davo_forward_heat call wants beside the poses; null = nothing of that kind
+struct Exports {
+    const davo_feature_out* fx = nullptr;
+    const davo_heat_out* heat = nullptr;
+    explicit operator bool() const { return fx || heat; }
+};
+int export_all(davo_ctx* c, const Exports& ex, const Inputs& in, int w0, int nw, int b0, int B);
+
+// ---- entry.hip ------------------------------------------------------------------------------
+// A batch as the caller handed it to an entry point: the layout, the four pointers under the names the layout gives them (the two
+// structs share one shape: what treats all layouts alike reads `win'), where they point, the entry point's family name for
+// messages (the window forms append `_depth' themselves) and whether its signature has a depth parameter at all.
+// Windows: img [B,H,3W,3], flow [B,4,H,W,2], seg and depth [B,3,H,W,1]; frames: frames [N+2,H,W,3], flow2 [N,2,H,W,2], seg and depth [N+2,H,W,1]
+enum class Layout { Windows, Frames };
+struct FrameInputs { const void *frames, *flow2, *seg, *depth; };
+struct Batch {
+    Layout layout;
+    union { Inputs win; FrameInputs fr; };
+    bool on_device;
+    const char* fn;
+    bool depth_param;
+};
+inline Batch window_batch(const char* fn, bool on_device, bool depth_param, const void* img, const void* flow, const void* seg, const void* depth) {
+    return Batch{Layout::Windows, {Inputs{img, flow, seg, depth}}, on_device, fn, depth_param};
+}
+inline Batch frame_batch(const char* fn, bool on_device, const void* frames, const void* flow2, const void* seg, const void* depth) {
+    Batch b{Layout::Frames, {}, on_device, fn, true};
+    b.fr = FrameInputs{frames, flow2, seg, depth};
+    return b;
+}
+int check_batch(davo_ctx* c, Batch* b, int B, bool out_given, int hold = 0);   // the one argument check; clears a depth pointer the variant does not read
+Inputs from_window(const davo_ctx* c, const Inputs& in, int b0);               // windows b0.. of a batch's planes
+int forward_entry(davo_ctx* c, int B, Batch b, float* pose_out, Exports ex = Exports{});      // davo_forward's body, with the exports wanted
+int deliver_all(davo_ctx* c);                                                  // every davo_submit batch still under way, in issue order
+void drain_own_streams(davo_ctx* c);
 
 // ---- range_guard.hip: what the entry points need of the f16x3 range guard --------------------
 int ensure_ring(davo_ctx* c, bool snapshots);                                  // the records' host mirrors (and the ring's input snapshots)

@@ -1,0 +1,526 @@
+// entry.hip — the entry points of libdavo_hip.so that take a batch (include/davo_hip.h): the device-buffer, the streaming and the
+// host-buffer forward family, each in the window and the frame layout, with davo_wait / davo_pending and the delivery of streamed
+// batches.  A wrapper describes the batch as the caller handed it (ctx.h: Batch), one check serves them all, and a Stager brings
+// the batch's windows into the staging set the forward reads, whatever the layout.
+#include <algorithm>
+#include <cstdint>
+#include <cstring>
+
+#include "ctx.h"
+#include "launch.h"
+#include "window_gather.h"
+
+using namespace davo;
+
+// ---- the forward entry points ----------------------------------------------------------------------------
+// The f16x3 batches they issue are judged by the range guard (range_guard.hip, reached through ctx.h; bookkeeping: c->book).
+
+// The one argument check, in this order: null pointers, the depth argument, the batch range, hold, alignment.
+// Depth: a variant that reads depth planes (att_source 11, 12, 13) must be called with the planes - the window layout through the
+// `_depth' form, the frame layout with a non-null `depth'; every other variant reads no depth: a pointer (or null) is accepted and ignored.
+int davo::check_batch(davo_ctx* c, Batch* b, int B, bool out_given, int hold) {
+    if (!c) return DAVO_ERR_INVALID;
+    if (!b->win.img || !b->win.flow || !b->win.seg || !out_given) return fail(c, DAVO_ERR_INVALID, "null %s pointer", b->on_device ? "device" : "host");
+    if (!needs_depth(c)) b->win.depth = nullptr;
+    else if (b->layout == Layout::Frames) {
+        if (!b->fr.depth) return fail(c, DAVO_ERR_INVALID, "%s: this variant reads depth planes (att_source %d): depth must not be NULL", b->fn, c->v.att_source);
+    } else {
+        if (!b->depth_param) return fail(c, DAVO_ERR_INVALID, "%s: this variant reads depth planes (att_source %d): call %s_depth", b->fn, c->v.att_source, b->fn);
+        if (!b->win.depth) return fail(c, DAVO_ERR_INVALID, "%s_depth: null depth pointer", b->fn);
+    }
+    if (B < 1 || B > c->max_batch) return fail(c, DAVO_ERR_INVALID, "batch %d outside [1,%d]", B, c->max_batch);
+    if (hold < 0) return fail(c, DAVO_ERR_INVALID, "hold must be >= 0");
+    if (b->layout == Layout::Frames && b->on_device && (((uintptr_t)b->fr.frames | (uintptr_t)b->fr.flow2 | (uintptr_t)b->fr.seg | (uintptr_t)b->fr.depth) & 15))
+        return fail(c, DAVO_ERR_INVALID, "%s: device input buffers must be 16-byte aligned", b->fn);
+    return DAVO_OK;
+}
+
+// windows b0.. of a batch's planes
+Inputs davo::from_window(const davo_ctx* c, const Inputs& in, int b0) {
+    const PlaneBytes nb = plane_bytes(c);
+    auto at = [b0](const void* q, size_t bytes) -> const void* { return q ? static_cast<const uint8_t*>(q) + bytes * b0 : nullptr; };
+    return Inputs{at(in.img, nb.img), at(in.flow, nb.flow), at(in.seg, nb.seg), at(in.depth, nb.depth)};
+}
+
+namespace {
+
+int ensure_stream_state(davo_ctx* c, int slot) {
+    if (!c->pose_ring) {
+        PoseRing ring;
+        for (PoseRing::Entry& e : ring.e) {
+            HIP_TRY(c, dev_alloc(&e.dev, (size_t)c->max_batch * 12));
+            HIP_TRY(c, pinned_alloc(&e.host, (size_t)c->max_batch * 12, hipHostMallocDefault));
+            HIP_TRY(c, event_create(&e.pose_done, hipEventDisableTiming));
+            HIP_TRY(c, event_create(&e.copied, hipEventDisableTiming));
+        }
+        c->pose_ring = std::move(ring);
+    }
+    if (!c->stream_sets[slot].built()) { int rc = alloc_input_set(c, &c->stream_sets[slot], true); if (rc) return rc; }
+    return DAVO_OK;
+}
+
+// Host -> device, on stream s: windows [b0, b0 + nb) of the caller's arrays into the same windows of a staging set.  Only what the path
+// reads crosses PCIe: flow planes 0,1 (davo.py:978-982); the label maps; for the depth sources all three depth planes (the target's
+// depth enters every frame's descriptor, davo.py:1109).  sources_only_seg: unless the variant reads the target frame's label map too
+// (-segmask_all-static, the with-target class-table sources), only the two source frames' maps go (davo.py:998-1004, 1408-1412), in
+// batches of four windows and more.
+// One pair selected (sel, params.h): only what that pair reads is copied, each plane to its usual place - of every strip row the
+// byte range of (tgt, selected source), the source's flow plane, its label map (and the target's where the variant attends it),
+// for the depth sources the target's and the source's depth plane.  The regions skipped keep whatever they held; no kernel of a
+// one-pair batch reads them.  At 128x416: 319,488 + 425,984 + 212,992 = 958,464 B per window instead of 1,757,184.
+int stage_inputs(davo_ctx* c, const InputSet& set, const Inputs& host, int b0, int nb, bool sources_only_seg, int sel, hipStream_t s) {
+    const PlaneBytes n = plane_bytes(c);
+    const Inputs src = from_window(c, host, b0);
+    auto dst = [b0](const DevMem<void>& q, size_t bytes) { return static_cast<uint8_t*>(q.get()) + bytes * b0; };
+    if (sel != PAIRS_BOTH) {
+        const int src1 = sel == PAIRS_SRC1;
+        auto copy2d = [&](uint8_t* d, const void* h, size_t pitch, size_t off, size_t width, size_t rows) {
+            return hipMemcpy2DAsync(d + off, pitch, static_cast<const uint8_t*>(h) + off, pitch, width, rows, hipMemcpyHostToDevice, s);
+        };
+        const size_t row = (size_t)c->W * 9, third = row / 3;       // strip row: src0 | tgt | src1 (data_loader.py:537-557)
+        HIP_TRY(c, copy2d(dst(set.img, n.img), src.img, row, src1 ? third : 0, 2 * third, (size_t)nb * c->H));
+        HIP_TRY(c, copy2d(dst(set.flow, n.flow), src.flow, n.flow, src1 ? n.flow / 4 : 0, n.flow / 4, nb));
+        // planes in file order src0, tgt, src1 (davo.py:991-1004): with the target, two neighbouring planes
+        const size_t plane = n.seg / 3;
+        if (att_tgt_attended(c->v.att_source)) HIP_TRY(c, copy2d(dst(set.seg, n.seg), src.seg, n.seg, src1 ? plane : 0, 2 * plane, nb));
+        else HIP_TRY(c, copy2d(dst(set.seg, n.seg), src.seg, n.seg, src1 ? 2 * plane : 0, plane, nb));
+        // depth sources: the target's plane and the source's; the depth-split attention reads the source frame's plane alone
+        const size_t dplane = n.depth / 3;                     // (float32 whatever the label format)
+        if (src.depth && c->v.att_source == ATT_DEPTH_SPLIT) HIP_TRY(c, copy2d(dst(set.depth, n.depth), src.depth, n.depth, src1 ? 2 * dplane : 0, dplane, nb));
+        else if (src.depth) HIP_TRY(c, copy2d(dst(set.depth, n.depth), src.depth, n.depth, src1 ? dplane : 0, 2 * dplane, nb));
+        return DAVO_OK;
+    }
+    HIP_TRY(c, hipMemcpyAsync(dst(set.img, n.img), src.img, n.img * nb, hipMemcpyHostToDevice, s));
+    if (nb == 1) HIP_TRY(c, hipMemcpyAsync(dst(set.flow, n.flow), src.flow, n.flow / 2, hipMemcpyHostToDevice, s));
+    else HIP_TRY(c, hipMemcpy2DAsync(dst(set.flow, n.flow), n.flow, src.flow, n.flow, n.flow / 2, nb, hipMemcpyHostToDevice, s));
+    if (!sources_only_seg || att_tgt_attended(c->v.att_source) || nb < 4) HIP_TRY(c, hipMemcpyAsync(dst(set.seg, n.seg), src.seg, n.seg * nb, hipMemcpyHostToDevice, s));
+    else
+        for (int plane = 0; plane < 3; plane += 2)
+            HIP_TRY(c, hipMemcpy2DAsync(dst(set.seg, n.seg) + plane * (n.seg / 3), n.seg, (const uint8_t*)src.seg + plane * (n.seg / 3), n.seg,
+                                        n.seg / 3, nb, hipMemcpyHostToDevice, s));
+    if (src.depth) HIP_TRY(c, hipMemcpyAsync(dst(set.depth, n.depth), src.depth, n.depth * nb, hipMemcpyHostToDevice, s));
+    return DAVO_OK;
+}
+
+// ---- frame layout (window_gather.h; include/davo_hip.h "Frame sequences") ---------------------------------------
+// bytes of one frame of each plane kind (flow2: of one window)
+PlaneBytes frame_bytes(const davo_ctx* c) {
+    const PlaneBytes n = plane_bytes(c);
+    return PlaneBytes{n.img / 3, n.flow / 2, n.seg / 3, n.depth / 3};
+}
+
+int ensure_frame_set(davo_ctx* c, int slot) {
+    if (c->frame_sets[slot].built()) return DAVO_OK;
+    const PlaneBytes f = frame_bytes(c);
+    const size_t n = (size_t)c->max_batch + 2;
+    FrameSet s;
+    HIP_TRY(c, dev_alloc(&s.img, f.img * n));
+    HIP_TRY(c, dev_alloc(&s.seg, f.seg * n));
+    if (needs_depth(c)) HIP_TRY(c, dev_alloc(&s.depth, f.depth * n));
+    c->frame_sets[slot] = std::move(s);
+    return DAVO_OK;
+}
+
+// frames copied so far of each plane kind by the sub-batches of one call (a frame crosses the link once per call)
+struct FrameCursor { int img = 0, seg = 0, depth = 0; };
+
+// Host -> device, on stream s, for windows [b0, b0 + nb) of a frame-layout call: the frames frame_plan says they read and no
+// earlier sub-batch of the call has brought (*cur) into the slot's frame buffer, frame f to place f; the flow planes of the
+// selection straight into planes 0, 1 of the same windows of the staging set, as stage_inputs puts them.
+int stage_frames(davo_ctx* c, const FrameSet& fs, const InputSet& set, const FrameInputs& host, int b0, int nb, int sel, FrameCursor* cur, hipStream_t s) {
+    const PlaneBytes f = frame_bytes(c), n = plane_bytes(c);
+    const FramePlan p = frame_plan(nb, sel, c->v.att_source);
+    auto copy = [&](const DevMem<void>& d, const void* h, size_t per, const int r[2], int* done) -> int {
+        const int lo = std::max(b0 + r[0], *done), hi = b0 + r[1];
+        if (hi > lo) HIP_TRY(c, hipMemcpyAsync(static_cast<uint8_t*>(d.get()) + per * lo, static_cast<const uint8_t*>(h) + per * lo, per * (hi - lo), hipMemcpyHostToDevice, s));
+        *done = std::max(*done, hi);
+        return DAVO_OK;
+    };
+    { int rc = copy(fs.img, host.frames, f.img, p.img, &cur->img); if (rc) return rc; }
+    { int rc = copy(fs.seg, host.seg, f.seg, p.seg, &cur->seg); if (rc) return rc; }
+    if (host.depth) { int rc = copy(fs.depth, host.depth, f.depth, p.depth, &cur->depth); if (rc) return rc; }
+    const size_t plane = n.flow / 4, off = plane * p.flow[0], width = plane * (p.flow[1] - p.flow[0]);
+    uint8_t* const d = static_cast<uint8_t*>(set.flow.get()) + n.flow * b0 + off;
+    const uint8_t* const h = static_cast<const uint8_t*>(host.flow2) + f.flow * b0 + off;
+    if (nb == 1) HIP_TRY(c, hipMemcpyAsync(d, h, width, hipMemcpyHostToDevice, s));
+    else HIP_TRY(c, hipMemcpy2DAsync(d, n.flow, h, f.flow, width, nb, hipMemcpyHostToDevice, s));
+    return DAVO_OK;
+}
+
+// window_gather on stream s: windows [b0, b0 + nb) of `set' from frames [b0, b0 + nb + 2) of `fr' (device pointers, frame 0 of the
+// call); fr.flow2 null: the flow is in the set already
+int gather_windows(davo_ctx* c, const InputSet& set, const FrameInputs& fr, int b0, int nb, int sel, hipStream_t s) {
+    const PlaneBytes f = frame_bytes(c), n = plane_bytes(c);
+    const FramePlan p = frame_plan(nb, sel, c->v.att_source);
+    auto src = [b0](const void* q, size_t per) { return q ? static_cast<const uint8_t*>(q) + per * b0 : nullptr; };
+    auto dst = [b0](const DevMem<void>& q, size_t per) { return q ? static_cast<uint8_t*>(q.get()) + per * b0 : nullptr; };
+    const GatherArgs a{src(fr.frames, f.img), src(fr.seg, f.seg), src(fr.depth, f.depth), src(fr.flow2, f.flow),
+                       dst(set.img, n.img), dst(set.seg, n.seg), dst(set.depth, n.depth), dst(set.flow, n.flow),
+                       c->H, c->W, sel, p.seg_tgt, p.depth_tgt};
+    ProfScope ps(c, s, "window_gather");
+    HIP_TRY(c, launch_window_gather(a, nb, c->label_fmt, s));
+    return DAVO_OK;
+}
+
+// ---- the stager: a batch's windows into the staging set its forward reads, a run of windows [b0, b0 + nb) at a time ----------
+// Two steps per run, both on the stream given: stage_upload brings what the windows read onto the device, stage_windows makes the
+// set hold them as windows.  Window layout: stage_inputs, then nothing.  Frame layout: stage_frames into the slot's frame buffer
+// (a frame crosses the link once per call: cur), then gather_windows from it - or, for a batch on the device, nothing and then
+// gather_windows from the caller's buffers.  A window batch on the device has no set: its forward reads the caller's buffers.
+enum class Path { Device, Submit, Forward };
+struct Stager {
+    davo_ctx* c;
+    Batch b;
+    const InputSet* set = nullptr;             // the path's staging set of the slot (null: none, see above)
+    const FrameSet* fs = nullptr;              // frame layout from the host: the slot's frame buffer
+    bool sources_only_seg = false;             // stage_inputs': davo_submit's batches
+    FrameCursor cur;
+    Inputs inputs() const { return set ? set->view() : b.win; }      // what the forward reads
+};
+
+// The stager of batch b in `slot'; builds what the path keeps per slot at its first use, each group whole: davo_forward's staging
+// (slot 0), davo_submit's pose ring and the slot's staging set, the slot's frame buffer for frames that come from the host.
+int acquire_stager(davo_ctx* c, const Batch& b, Path path, int slot, Stager* st) {
+    *st = Stager{c, b};
+    if (path == Path::Forward) {
+        if (!c->host) {
+            HostStaging h;
+            { int rc = alloc_input_set(c, &h.set, false); if (rc) return rc; }
+            HIP_TRY(c, dev_alloc(&h.d_pose, (size_t)c->max_batch * 12));
+            HIP_TRY(c, stream_create(&h.copy_stream));
+            HIP_TRY(c, pinned_alloc(&h.h_pose, (size_t)c->max_batch * 12, hipHostMallocDefault));
+            c->host = std::move(h);
+        }
+        st->set = &c->host->set;
+    } else if (path == Path::Submit) {
+        { int rc = ensure_stream_state(c, slot); if (rc) return rc; }
+        st->set = &c->stream_sets[slot];
+        st->sources_only_seg = true;
+    } else if (b.layout == Layout::Frames) {
+        if (!c->stream_sets[slot].built()) { int rc = alloc_input_set(c, &c->stream_sets[slot], true); if (rc) return rc; }
+        st->set = &c->stream_sets[slot];
+    }
+    if (b.layout == Layout::Frames && !b.on_device) {
+        { int rc = ensure_frame_set(c, slot); if (rc) return rc; }
+        st->fs = &c->frame_sets[slot];
+    }
+    return DAVO_OK;
+}
+
+int stage_upload(Stager* st, int b0, int nb, hipStream_t s) {
+    if (st->b.on_device) return DAVO_OK;
+    if (st->fs) return stage_frames(st->c, *st->fs, *st->set, st->b.fr, b0, nb, st->c->pairs, &st->cur, s);
+    return stage_inputs(st->c, *st->set, st->b.win, b0, nb, st->sources_only_seg, st->c->pairs, s);
+}
+
+int stage_windows(Stager* st, int b0, int nb, hipStream_t s) {
+    if (st->b.layout != Layout::Frames) return DAVO_OK;
+    const FrameInputs dev = st->fs ? FrameInputs{st->fs->img.get(), nullptr, st->fs->seg.get(), st->fs->depth.get()} : st->b.fr;
+    return gather_windows(st->c, *st->set, dev, b0, nb, st->c->pairs, s);
+}
+
+// the oldest undelivered batch: verdict (and re-issue) first, then its poses go to the caller's array
+int deliver_front(davo_ctx* c) {
+    const StreamJob j = c->jobs.front();
+    c->jobs.pop_front();
+    while (j.ticketed && c->book.pending(j.seq)) {
+        const int rc = judge_front(c);
+        if (rc == DAVO_ERR_RANGE && !c->opt_auto_range) c->book.defer(rc, c->err);      // reported by the next davo_synchronize; the poses are delivered as they are
+        else if (rc) return rc;
+    }
+    const PoseRing::Entry& e = c->pose_ring->e[j.pr];           // (a job exists, so the ring does)
+    HIP_TRY(c, hipEventSynchronize(e.pose_done.get()));
+    memcpy(j.pose_out, e.host.get(), (size_t)j.B * 12 * sizeof(float));
+    return DAVO_OK;
+}
+
+}  // namespace
+
+// every stream the context runs work on is idle: the slots' (and the caller's), the host path's copy stream, the guard's read stream
+void davo::drain_own_streams(davo_ctx* c) {
+    (void)sync_all_slots(c);
+    if (c->host) (void)hipStreamSynchronize(c->host->copy_stream.get());
+    if (c->ring) (void)hipStreamSynchronize(c->ring->read_stream.get());
+}
+
+int davo::deliver_all(davo_ctx* c) {
+    while (!c->jobs.empty()) { const int rc = deliver_front(c); if (rc) { c->jobs.clear(); return rc; } }
+    return DAVO_OK;
+}
+
+// the body of davo_forward_device, davo_forward_device_depth and davo_forward_device_frames: b's pointers are device pointers.  A
+// frame batch runs on the slot's staging set, gathered from them
+static int forward_device_entry(davo_ctx* c, int B, Batch b, void* d_pose, float* elapsed_ms) {
+    { int rc = check_batch(c, &b, B, d_pose != nullptr); if (rc) return rc; }
+    c->inputs_seen = true;
+    HIP_TRY(c, hipSetDevice(c->device));
+    Stager st;
+    { int rc = acquire_stager(c, b, Path::Device, c->next_slot, &st); if (rc) return rc; }
+    const Inputs in = st.inputs();
+    const bool ticketed = c->impl == 0 && c->precision == 1;      // f16x3: the batch gets a record (and a copy of its inputs) of its own
+    if (ticketed) { int rc = ticket_reserve(c); if (rc) return rc; }
+    // rotate through the in-flight slots: this batch runs on its own stream and workspace
+    Run run = make_run(c, c->next_slot);
+    c->next_slot = (c->next_slot + 1) % c->inflight;
+    EventOwner e0, e1;
+    // the windows into the slot's staging set, in stream order behind the forward that last read it and ahead of the ticket: the
+    // caller's buffers are free once this launch has run, and the batch is the library's own from here on (own_inputs below).
+    // The timed form brackets the gather too: elapsed_ms is what the layout costs on resident inputs
+    if (elapsed_ms && st.set) {
+        HIP_TRY(c, event_create(&e0));
+        HIP_TRY(c, hipEventRecord(e0.get(), run.stream));
+    }
+    { int rc = stage_windows(&st, 0, B, run.stream); if (rc) return rc; }
+    Ticket t{};
+    if (ticketed) { int rc = ticket_begin(c, &run, B, in, &t, st.set != nullptr); if (rc) return rc; }
+    if (!ticketed && c->book.spans_full()) {               // float32 batches behind pending f16x3 tickets: bounded
+        const int rc = judge_all(c);
+        if (rc == DAVO_ERR_RANGE) c->book.defer(rc, c->err);       // "auto_range" 0: reported by the next davo_synchronize (judge_all has just emptied the store)
+        else if (rc) return rc;
+    }
+    c->book.note_issue(d_pose, B);
+    RunResult res;
+    if (!elapsed_ms) {
+        int rc = forward_device(c, run, B, in, d_pose, &res);
+        return ticketed ? ticket_end(c, rc, res, t, d_pose) : rc;      // (only a ticketed batch starts as f16x3, so only it can fall back)
+    }
+    int rc = DAVO_OK;
+    auto hip_ok = [&](hipError_t e, const char* what) {
+        if (e != hipSuccess && rc == DAVO_OK) rc = fail(c, DAVO_ERR_HIP, "%s failed: %s", what, hipGetErrorString(e));
+        return e == hipSuccess;
+    };
+    if (hip_ok(event_create(&e1), "hipEventCreate") &&
+        (e0 || (hip_ok(event_create(&e0), "hipEventCreate") && hip_ok(hipEventRecord(e0.get(), run.stream), "hipEventRecord")))) {
+        rc = forward_device(c, run, B, in, d_pose, &res);
+        if (rc == DAVO_OK && hip_ok(hipEventRecord(e1.get(), run.stream), "hipEventRecord") &&
+            hip_ok(hipEventSynchronize(e1.get()), "hipEventSynchronize"))
+            hip_ok(hipEventElapsedTime(elapsed_ms, e0.get(), e1.get()), "hipEventElapsedTime");
+    }
+    if (ticketed) rc = ticket_end(c, rc, res, t, d_pose);
+    // the timed form is synchronous, so it can judge (and, if need be, re-issue) its own batch; elapsed_ms is the first issue's
+    if (rc == DAVO_OK && c->inflight == 1) rc = judge_all(c);
+    return rc;
+}
+
+extern "C" {
+
+int davo_forward_device(davo_ctx* c, int B, const void* d_img, const void* d_flow, const void* d_seg,
+                        void* d_pose, float* elapsed_ms) {
+    return forward_device_entry(c, B, window_batch("davo_forward_device", true, false, d_img, d_flow, d_seg, nullptr), d_pose, elapsed_ms);
+}
+
+int davo_forward_device_depth(davo_ctx* c, int B, const void* d_img, const void* d_flow, const void* d_seg, const void* d_depth,
+                              void* d_pose, float* elapsed_ms) {
+    return forward_device_entry(c, B, window_batch("davo_forward_device", true, true, d_img, d_flow, d_seg, d_depth), d_pose, elapsed_ms);
+}
+
+int davo_forward_device_frames(davo_ctx* c, int N, const void* d_frames, const void* d_flow2, const void* d_seg, const void* d_depth,
+                               void* d_pose, float* elapsed_ms) {
+    return forward_device_entry(c, N, frame_batch("davo_forward_device_frames", true, d_frames, d_flow2, d_seg, d_depth), d_pose, elapsed_ms);
+}
+
+int davo_frames_plan(int H, int W, int N, int pairs, int att_source, int label_fmt, int* ranges, long long* link_bytes) {
+    if (H < 1 || W < 1 || N < 1 || (pairs != PAIRS_SRC0 && pairs != PAIRS_SRC1 && pairs != PAIRS_BOTH) || att_source < 0 || att_source > ATT_DEPTH_SPLIT ||
+        (label_fmt != LABELS_F32 && label_fmt != LABELS_U8))
+        return DAVO_ERR_INVALID;
+    const FramePlan p = frame_plan(N, pairs, att_source);
+    if (ranges) {
+        const int r[8] = {p.img[0], p.img[1], p.seg[0], p.seg[1], p.depth[0], p.depth[1], p.flow[0], p.flow[1]};
+        memcpy(ranges, r, sizeof r);
+    }
+    if (link_bytes) *link_bytes = frame_plan_bytes(p, N, H, W, label_fmt == LABELS_U8 ? 1 : 4);
+    return DAVO_OK;
+}
+
+
+// ---- streaming host entry: davo_submit / davo_wait ----------------------------------------------------------------
+// The reference's driver pulls batches through tf.data's prefetch(8B) while the session runs (test_kitti_pose.py:133-145,
+// data_loader.py:321-324): input transfer, compute and result delivery of neighbouring batches overlap.  davo_forward cannot (it
+// returns poses), so the sequence driver uses this pair.  davo_submit rotates through the in-flight slots like
+// davo_forward_device; on the slot's OWN stream it queues the H2D copies of the batch into the slot's staging set, the forward,
+// and the D2H of the poses into a page-locked ring entry.  A stream runs in order, so the staging set is safe to refill without an
+// event, and with two or more slots the copies of batch n+1 run under the kernels of batch n.  (First built with a copy stream
+// and events between it and the slots: each hipEventRecord costs 6 us of host time and a marker on the queue,
+// profiles/r05a_hip_call_cost.log, and the batch-1 loop ran at 134-168 us per window.)  davo_wait / davo_synchronize judge the
+// batch's range ticket (re-issuing it if need be) and only then write the poses into the caller's array.  Inputs, poses and range
+// snapshots of a batch all live in context-owned memory.
+
+// the body of davo_submit, davo_submit_depth and davo_submit_frames: b's pointers are host pointers
+static int submit_entry(davo_ctx* c, int B, Batch b, float* pose_out, int hold) {
+    { int rc = check_batch(c, &b, B, pose_out != nullptr, hold); if (rc) return rc; }
+    c->inputs_seen = true;
+    HIP_TRY(c, hipSetDevice(c->device));
+    // deliver what has finished (never blocks), and make room in the pose ring (blocks on the oldest batch only when the ring is full)
+    while (!c->jobs.empty() && ((int)c->jobs.size() >= STREAM_POSES || hipEventQuery(c->pose_ring->e[c->jobs.front().pr].pose_done.get()) == hipSuccess)) {
+        const int rc = deliver_front(c);
+        if (rc) return rc;
+    }
+    const bool ticketed = c->impl == 0 && c->precision == 1;
+    if (ticketed) { int rc = ticket_reserve(c); if (rc) return rc; }          // may judge - and re-issue - an older batch: before the slot rotation
+    const int slot = c->next_slot, pr = (int)(c->n_submitted % STREAM_POSES);
+    Stager st;
+    { int rc = acquire_stager(c, b, Path::Submit, slot, &st); if (rc) return rc; }
+    Run run = make_run(c, slot);
+    c->next_slot = (c->next_slot + 1) % c->inflight;
+    hipStream_t s = run.stream;
+    // H2D on the slot's stream, in order behind the forward that last read this staging set (and, the frame layout, behind the
+    // gather that last read the slot's frame buffer)
+    const InputSet& set = *st.set;
+    PoseRing::Entry& e = c->pose_ring->e[pr];
+    { int rc = stage_upload(&st, 0, B, s); if (rc) return rc; }
+    // the caller keeps a batch's inputs unchanged for `hold` more submits.  With hold >= STREAM_POSES the pose ring already implies it
+    // (a batch is delivered - so its copies are long done - before the eighth submit after it returns): no event then
+    const bool track_copy = hold < STREAM_POSES;
+    if (track_copy) HIP_TRY(c, hipEventRecord(e.copied.get(), s));
+    { int rc = stage_windows(&st, 0, B, s); if (rc) return rc; }      // the staging set is an ordinary window batch from here on
+
+    Ticket t{};
+    if (ticketed) { int rc = ticket_begin(c, &run, B, set.view(), &t, true); if (rc) return rc; }
+    c->book.note_issue();             // (no pose span: a pose ring entry is not reused before its batch has been delivered)
+    RunResult res;
+    int rc = forward_device(c, run, B, set.view(), e.dev.get(), &res);
+    if (ticketed) rc = ticket_end(c, rc, res, t, e.dev.get(), e.host.get());
+    if (rc) return rc;
+    HIP_TRY(c, hipMemcpyAsync(e.host.get(), e.dev.get(), (size_t)B * 12 * sizeof(float), hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipEventRecord(e.pose_done.get(), s));
+    c->jobs.push_back(StreamJob{B, pose_out, pr, ticketed && res.h3, t.seq});      // (the weight guard's float32 batches get no ticket)
+    e.copy_tracked = track_copy;
+    ++c->n_submitted;
+    if (track_copy && (unsigned long long)hold < c->n_submitted) {
+        const int q = (int)((c->n_submitted - 1 - hold) % STREAM_POSES);
+        if (c->pose_ring->e[q].copy_tracked) HIP_TRY(c, hipEventSynchronize(c->pose_ring->e[q].copied.get()));
+        // (a batch submitted with hold >= 8 recorded no event: it has been delivered by now if it is 8 or more submits back, and a
+        // caller that lowers `hold` from one call to the next keeps the larger promise for the batches it made it for)
+    }
+    return DAVO_OK;
+}
+
+int davo_submit(davo_ctx* c, int B, const uint8_t* img, const float* flow, const float* seg, float* pose_out, int hold) {
+    return submit_entry(c, B, window_batch("davo_submit", false, false, img, flow, seg, nullptr), pose_out, hold);
+}
+
+int davo_submit_depth(davo_ctx* c, int B, const uint8_t* img, const float* flow, const float* seg, const float* depth, float* pose_out, int hold) {
+    return submit_entry(c, B, window_batch("davo_submit", false, true, img, flow, seg, depth), pose_out, hold);
+}
+
+int davo_submit_frames(davo_ctx* c, int N, const uint8_t* frames, const float* flow2, const float* seg, const float* depth, float* pose_out, int hold) {
+    return submit_entry(c, N, frame_batch("davo_submit_frames", false, frames, flow2, seg, depth), pose_out, hold);
+}
+
+int davo_wait(davo_ctx* c, int leave_pending) {
+    if (!c) return DAVO_ERR_INVALID;
+    if (leave_pending < 0) return fail(c, DAVO_ERR_INVALID, "leave_pending must be >= 0");
+    HIP_TRY(c, hipSetDevice(c->device));
+    while ((int)c->jobs.size() > leave_pending) { const int rc = deliver_front(c); if (rc) return rc; }
+    return DAVO_OK;
+}
+
+int davo_pending(davo_ctx* c) { return c ? (int)c->jobs.size() : DAVO_ERR_INVALID; }
+
+}  // extern "C"
+
+// the body of davo_forward, davo_forward_depth and davo_forward_frames, and of davo_forward_features / davo_forward_heat (export.hip;
+// ex: the exports wanted): b's pointers are host pointers
+int davo::forward_entry(davo_ctx* c, int B, Batch b, float* pose_out, const Exports ex) {
+    { int rc = check_batch(c, &b, B, pose_out != nullptr); if (rc) return rc; }
+    c->inputs_seen = true;
+    HIP_TRY(c, hipSetDevice(c->device));
+    { int rc = deliver_all(c); if (rc) return rc; }          // davo_submit batches still under way: delivered first
+    { int rc = sync_all_slots(c); if (rc) return rc; }       // the host path owns the single staging buffer set
+    Stager st;
+    { int rc = acquire_stager(c, b, Path::Forward, 0, &st); if (rc) return rc; }      // slot 0's: every slot is idle
+    HostStaging& hs = *c->host;
+    { int rc = judge_all(c); if (rc) return rc; }               // device-path batches issued before this call
+    Run run = make_run(c, 0);                                   // slot 0, the base record
+    // The base record holds RUNNING maxima like the ring's records (params.h): a record that starts at zero is raised by every wave of
+    // every kernel's first round, and at batch 1 - the reference's operating point - those serialised atomics were 200 us of this
+    // call's 417.  "Clamped" stays exact per call (the call that pushes a maximum past 65504 fails, and every recovery path zeroes
+    // the record); "too small" is judged on what has been stored since the record was last zeroed: by a recovery, a change of scales,
+    // and every FRESH_EVERY-th call.
+    if (c->book.host_record_due()) {
+        HIP_TRY(c, hipMemsetAsync(c->d_range_base.get(), 0, RANGE_WORDS * sizeof(unsigned), run.stream));
+    }
+    // Sub-batches: the copy of chunk i+1 (copy_stream) overlaps the kernels of chunk i (compute stream).
+    // Results do not depend on the split (windows are independent; tests/test_hip_parity.py batch invariance).
+    // Only flow planes 0 and 1 are read by the path (davo.py:978-982), so only those cross PCIe.
+    const int chunk = (c->host_chunk > 0 && B >= 2 * c->host_chunk) ? c->host_chunk : B;
+    const int nchunks = (B + chunk - 1) / chunk;
+    while ((int)hs.copy_done.size() < nchunks) {
+        EventOwner e;
+        HIP_TRY(c, event_create(&e, hipEventDisableTiming));
+        hs.copy_done.push_back(std::move(e));
+    }
+    bool f32_fallback = false;
+    RunResult res;
+    // Batch 1 is the reference's own operating point (run_inference.sh:44-51), and there this call was 474 us around 129 us of kernels
+    // (round 5).  What went: the copy stream and its event for a call that is a single sub-batch (the copies go on the compute
+    // stream itself); the read-back of the range record on a stream of its own behind the synchronise (the call's last kernel mirrors
+    // the record into page-locked host memory like a ticketed batch's, prologue.h); the pose copy into pageable memory (a page-locked
+    // bounce buffer, then memcpy).
+    const bool h3_call = c->impl == 0 && c->precision == 1;
+    if (h3_call) { int rc = ensure_ring(c, false); if (rc) return rc; }
+    unsigned seq = 0;
+    for (int i = 0; i < nchunks; ++i) {
+        const int b0 = i * chunk, nb = std::min(chunk, B - b0);
+        hipStream_t cs = nchunks == 1 ? run.stream : hs.copy_stream.get();
+        // (frame layout: windows [b0, b0 + nb) take frames [b0, b0 + nb + 2), the two it shares with the sub-batch before are on the
+        // device already; window layout, both pairs: the label maps whole)
+        { int rc = stage_upload(&st, b0, nb, cs); if (rc) return rc; }
+        { int rc = stage_windows(&st, b0, nb, cs); if (rc) return rc; }
+        if (nchunks > 1) {
+            HIP_TRY(c, hipEventRecord(hs.copy_done[i].get(), cs));
+            HIP_TRY(c, hipStreamWaitEvent(run.stream, hs.copy_done[i].get(), 0));
+        }
+        if (h3_call && i == nchunks - 1) {       // the call's last kernel mirrors the finished record (all sub-batches) to the host
+            seq = c->book.next_seq();
+            run.snap.record = c->d_range_base.get(); run.snap.host_mirror = c->ring->h_range_dev; run.snap.seq = seq; run.snap.B = nb; run.snap.se = c->posenn_se;
+        }
+        int rc = forward_device(c, run, nb, from_window(c, hs.set.view(), b0), hs.d_pose.get() + (size_t)b0 * 12, &res);
+        if (rc) return rc;
+        f32_fallback |= res.f32_fallback;
+        // feature export: the context holds one sub-batch's activations, so every sub-batch but the last is exported before the next
+        // one runs; the last one waits for the verdict below
+        if (ex && i < nchunks - 1 && (rc = export_all(c, ex, from_window(c, hs.set.view(), b0), 0, nb, b0, B))) return rc;
+    }
+    const int last_b0 = (nchunks - 1) * chunk;
+    auto export_last = [&]() { return !ex ? DAVO_OK : export_all(c, ex, from_window(c, hs.set.view(), last_b0), 0, B - last_b0, last_b0, B); };
+    if (f32_fallback) ++c->n_f32_batches;                      // once per call, not per sub-batch
+    HIP_TRY(c, hipMemcpyAsync(hs.h_pose.get(), hs.d_pose.get(), (size_t)B * 12 * sizeof(float), hipMemcpyDeviceToHost, run.stream));
+    HIP_TRY(c, hipStreamSynchronize(run.stream));
+    memcpy(pose_out, hs.h_pose.get(), (size_t)B * 12 * sizeof(float));
+    if (!res.h3) return export_last();
+    // The call ran f16x3 (res is the last sub-batch's), so that sub-batch carried run.snap - h3_call reads the same impl and precision
+    // run does - and its last kernel, pose_from_tiles or range_guard_snapshot (forward.hip), has stored the record and seq in the
+    // mirror; the stream is idle, so the wait returns at once
+    unsigned raw[RANGE_WORDS];
+    int rc = wait_record(c, c->ring->h_range.get(), seq, run.stream, raw);
+    if (rc) return rc;
+    rc = judge_record(c, raw, c->act_shift);
+    if (rc == DAVO_ERR_RANGE && c->opt_auto_range) {
+        // the staged copy of the batch is still in HBM: re-issue it whole (recalibrated, or on the float32 kernels); nothing has
+        // been issued since, so its pose buffer is its own
+        rc = recover_batch(c, Reissue{B, c->pairs, hs.set.view(), hs.d_pose.get(), false, 0});
+        if (rc == DAVO_OK) HIP_TRY(c, hipMemcpy(pose_out, hs.d_pose.get(), (size_t)B * 12 * sizeof(float), hipMemcpyDeviceToHost));
+        // the re-issue ran the whole batch as one forward and produced the poses returned: every window's exports come from it, in
+        // the precision and under the scales it ran with (what the sub-batches exported above is overwritten)
+        if (rc == DAVO_OK && ex) rc = export_all(c, ex, hs.set.view(), 0, B, 0, B);
+        return rc;
+    }
+    return rc == DAVO_OK ? export_last() : rc;
+}
+
+extern "C" {
+
+int davo_forward(davo_ctx* c, int B, const uint8_t* img, const float* flow, const float* seg, float* pose_out) {
+    return forward_entry(c, B, window_batch("davo_forward", false, false, img, flow, seg, nullptr), pose_out);
+}
+
+int davo_forward_depth(davo_ctx* c, int B, const uint8_t* img, const float* flow, const float* seg, const float* depth, float* pose_out) {
+    return forward_entry(c, B, window_batch("davo_forward", false, true, img, flow, seg, depth), pose_out);
+}
+
+int davo_forward_frames(davo_ctx* c, int N, const uint8_t* frames, const float* flow2, const float* seg, const float* depth, float* pose_out) {
+    return forward_entry(c, N, frame_batch("davo_forward_frames", false, frames, flow2, seg, depth), pose_out);
+}
+
+}  // extern "C"

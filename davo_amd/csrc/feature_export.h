@@ -127,7 +127,7 @@ struct ResizeParams {
     float unscale;               // 2^-act_shift[cnv6] (f16x3), exact
 };
 
-// four channels of one input pixel, decoded with davo_debug_read's expression (api.hip): (float)hi + (float)lo, times 2^-shift
+// four channels of one input pixel, decoded with davo_debug_read's expression (hooks.hip): (float)hi + (float)lo, times 2^-shift
 template <bool H3, class Params>
 __device__ __forceinline__ void resize_load4(const Params& p, size_t pixel, int ch, float v[4]) {
 #pragma clang fp contract(off)

@@ -354,7 +354,7 @@ __device__ inline void range_note(unsigned* __restrict__ rec_layer, float vmax, 
     const unsigned u = __builtin_bit_cast(unsigned, vmax);
     if (u > __atomic_load_n(rec_layer, __ATOMIC_RELAXED)) (void)__hip_atomic_fetch_max(rec_layer, u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
-// What the last kernel of a ticketed device-path batch does for the range guard (api.hip, prologue.h): mirror the batch's finished
+// What the last kernel of a ticketed device-path batch does for the range guard (range_guard.hip, prologue.h): mirror the batch's finished
 // record into page-locked host memory (the host's verdict then costs no copy), and keep the batch's inputs in the context's
 // ring slot if the record fails.  record null = nothing to do; s_img null = no copy wanted ("stable_inputs", "auto_range" 0).
 struct SnapArgs {

@@ -200,7 +200,7 @@ __global__ __launch_bounds__(64) void se_excite(const float* __restrict__ partia
                                                 const float* __restrict__ w2, const float* __restrict__ b2,
                                                 const float* __restrict__ wstatic,
                                                 float* __restrict__ tab, unsigned* __restrict__ range_reset, int sel) {
-    // a ticketed device-path batch starts its own f16x3 range record (api.hip): first kernel of the forward, so in stream
+    // a ticketed device-path batch starts its own f16x3 range record (range_guard.hip: ticket_begin): first kernel of the forward, so in stream
     // order before any storing epilogue; a null pointer = the record is the caller's business
     if (range_reset && blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) range_reset[RANGE_SNAP] = 0u;   // the per-batch word (params.h)
     if (!pair_reads_frame(blockIdx.y, sel)) return;           // an unselected source frame has no squeeze record and no reader of its table
@@ -632,7 +632,7 @@ __global__ __launch_bounds__(64) void pose_finish(const float* __restrict__ part
 // partial[head][mtile][ntile][slot][k], slot 0 = the tile's first image, slot 1 = the next one.  One 64-lane wave per
 // output (n, head, k): the tiles' terms are spread over the lanes and added by a fixed butterfly (pose_tail.h) — a
 // single thread walking 56 dependent loads (128x32 tiles at batch 1) took 12 us.
-// Range guard, device side (api.hip: tickets).  The batch's range record is complete when its last kernel runs (stream order), so
+// Range guard, device side (range_guard.hip: tickets).  The batch's range record is complete when its last kernel runs (stream order), so
 // that kernel can see the verdict the host will reach later: if a layer left the fp16-pair range the batch will be re-issued,
 // and the inputs it was issued on are copied into the context's ring slot NOW - behind the kernels that read them, ahead of
 // anything the caller orders behind the batch (e.g. the H2D of the next batch into the same buffers).  A batch in range -

@@ -22,7 +22,7 @@ namespace davo {
 // Frame ranges [lo, hi) of each plane kind, and flow planes [lo, hi), that a batch of N windows reads (frame f of the batch is
 // frame f of the caller's arrays).  tgt->src0 reads frames (n + 1, n), tgt->src1 frames (n + 1, n + 2); the label map of the
 // target only where the variant attends it; the depth sources 11, 12 the target's and the source's depth plane, the depth-split
-// attention (13) the source's alone - stage_inputs' rules (api.hip), frame-major.
+// attention (13) the source's alone - stage_inputs' rules (entry.hip), frame-major.
 struct FramePlan {
     int img[2], seg[2], depth[2], flow[2];
     bool seg_tgt, depth_tgt;               // a one-pair batch reads the target's label map / depth plane too

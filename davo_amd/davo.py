@@ -71,6 +71,16 @@ def unpin_array(arr):
         raise DavoError("davo_host_unregister failed")
 
 
+def _is_ready(a, dtype):
+    """a C-contiguous numpy array of that dtype: it goes to the library as it is"""
+    return isinstance(a, np.ndarray) and a.dtype == dtype and a.flags.c_contiguous
+
+
+def _ptr(a):
+    """an argument as the library takes it: a numpy array's or a DeviceBuffer's address, anything else as it is"""
+    return a.ctypes.data if isinstance(a, np.ndarray) else getattr(a, "ptr", a)
+
+
 class DeviceBuffer:
     """A hipMalloc'd buffer owned through a context (bench / multi-GPU shards keep inputs in HBM)."""
 
@@ -174,33 +184,56 @@ class Engine:
             shape = (ctypes.c_int64 * a.ndim)(*a.shape)
             self._check(self._L.davo_load_weight(self._ctx, name.encode(), a.ctypes.data_as(ctypes.POINTER(ctypes.c_float)), shape, a.ndim))
 
-    def _depth_arg(self, depth, B):
-        """The depth planes of a batch as the `_depth' entry points take them ([B,3,H,W,1] float32, file order src0, tgt,
-        src1: davo.py:991-996), or None for a variant that reads none (a depth array handed to such a variant is ignored,
-        as the reference ignores its depth input there)."""
+    def _depth_arg(self, depth, shape, names, strict=None):
+        """The depth planes of a batch as the entry points take them (float32 of ``shape``: [B,3,H,W,1] in file order src0, tgt,
+        src1, davo.py:991-996, or the frame layout's [N+2,H,W,1]), or None for a variant that reads none (a depth array handed to
+        such a variant is ignored, as the reference ignores its depth input there).  ``strict``: see _contiguous."""
         if not self.cfg.needs_depth:
             return None
+        if strict and not _is_ready(depth, np.float32):
+            raise ValueError("%s(hold > 0) needs a C-contiguous float32 depth array (a converted copy would not outlive the call)" % strict)
         if depth is None:
-            raise ValueError("image, flow, seglabel and depth inputs are all required for version `%s'" % self.cfg.version)
+            raise ValueError("%s and depth inputs are all required for version `%s'" % (names, self.cfg.version))
         depth = np.ascontiguousarray(depth, np.float32)
-        if depth.shape != (B, 3, self.H, self.W, 1):
-            raise ValueError("depth shape %s != %s" % (depth.shape, (B, 3, self.H, self.W, 1)))
+        if depth.shape != shape:
+            raise ValueError("depth shape %s != %s" % (depth.shape, shape))
         return depth
 
+    def _contiguous(self, pixels, flow, seg, seg_ndim, label_arg, strict):
+        """A batch's uint8, float32 and label arrays as they are where they can go to the library so, else converted
+        (``label_arg`` for the label maps) - or, ``strict`` (the name of a ``hold > 0`` submit), refused: a converted copy
+        would not outlive the call."""
+        if not (_is_ready(pixels, np.uint8) and _is_ready(flow, np.float32) and _is_ready(seg, LABEL_DTYPES[self.labels]) and seg.ndim == seg_ndim):
+            if strict:
+                raise ValueError("%s(hold > 0) needs C-contiguous uint8 / float32 / %s arrays (a converted copy would not outlive the call)"
+                                 % (strict, LABEL_DTYPES[self.labels]))
+            pixels, flow, seg = np.ascontiguousarray(pixels, np.uint8), np.ascontiguousarray(flow, np.float32), label_arg(seg)
+        return pixels, flow, seg
+
+    def _window_batch(self, img, flow, seg, depth, strict=None, calibration=False):
+        """A window-layout batch as the caller handed it -> (img, flow, seg), depth or None, B: checked and C-contiguous."""
+        inputs = self._contiguous(img, flow, seg, 5, self._label_arg, strict)
+        B = self._check_batch(*inputs, calibration=calibration)
+        return inputs, self._depth_arg(depth, (B, 3, self.H, self.W, 1), "image, flow, seglabel", strict), B
+
+    def _frame_batch(self, frames, flow2, seg, depth, strict=None):
+        """A frame-layout batch as the caller handed it -> (frames, flow2, seg), depth or None, N: checked and C-contiguous."""
+        inputs = self._contiguous(frames, flow2, seg, 4, self._frame_label_arg, strict)
+        N = self._check_frames(*inputs)
+        return inputs, self._depth_arg(depth, (N + 2, self.H, self.W, 1), "frames, flow2, seg", strict), N
+
+    def _call(self, name, n, inputs, depth, *tail, depth_slot=False):
+        """``name``(ctx, n, *inputs[, depth], *tail), checked.  An entry point either has a depth slot whatever the variant
+        (``depth_slot``: the `_frames', feature and heat calls; None = NULL) or comes in a plain and a `_depth' form, chosen here
+        by ``depth``.  numpy arrays and DeviceBuffers go as their pointers, everything else as it is."""
+        if depth_slot or depth is not None:
+            inputs, name = tuple(inputs) + (depth,), name if depth_slot else name + "_depth"
+        self._check(getattr(self._L, name)(self._ctx, int(n), *map(_ptr, inputs), *map(_ptr, tail)))
+
     def forward(self, img, flow, seg, depth=None):
-        img = np.ascontiguousarray(img, np.uint8)
-        flow = np.ascontiguousarray(flow, np.float32)
-        seg = self._label_arg(seg)
-        B = self._check_batch(img, flow, seg)
-        depth = self._depth_arg(depth, B)
+        inputs, depth, B = self._window_batch(img, flow, seg, depth)
         out = np.empty((B, 2, 6), np.float32)
-        vp = ctypes.c_void_p
-        if depth is not None:
-            self._check(self._L.davo_forward_depth(self._ctx, B, img.ctypes.data_as(vp), flow.ctypes.data_as(vp),
-                                                   seg.ctypes.data_as(vp), depth.ctypes.data_as(vp), out.ctypes.data_as(vp)))
-        else:
-            self._check(self._L.davo_forward(self._ctx, B, img.ctypes.data_as(vp), flow.ctypes.data_as(vp),
-                                             seg.ctypes.data_as(vp), out.ctypes.data_as(vp)))
+        self._call("davo_forward", B, inputs, depth, out)
         return out
 
     FEATURE_OUTPUTS = ("att_19", "attention", "masked_image", "image", "feat_rot", "feat_trans")
@@ -227,11 +260,7 @@ class Engine:
         unknown = [w for w in want if w not in self.FEATURE_OUTPUTS and w not in self.HEAT_OUTPUTS]
         if unknown:
             raise ValueError("unknown feature output(s) %s: choose from %s" % (unknown, list(self.FEATURE_OUTPUTS)))
-        img = np.ascontiguousarray(img, np.uint8)
-        flow = np.ascontiguousarray(flow, np.float32)
-        seg = self._label_arg(seg)
-        B = self._check_batch(img, flow, seg)
-        depth = self._depth_arg(depth, B)
+        inputs, depth, B = self._window_batch(img, flow, seg, depth)
         H, W, c6 = self.H, self.W, self.cfg.cnv6_out
         shapes = {"att_19": (3, B, 19), "attention": (3, B, H, W), "masked_image": (3, B, H, W, 3), "image": (3, B, H, W, 3),
                   "feat_rot": (B, H, W, c6), "feat_trans": (B, H, W, c6),
@@ -240,25 +269,22 @@ class Engine:
         for name in self.FEATURE_OUTPUTS + self.HEAT_OUTPUTS:
             if name in want:
                 res[name] = np.empty(shapes[name], np.float32)
-        vp = ctypes.c_void_p
         out = _lib.DavoFeatureOut(*[res[n].ctypes.data if n in res else None for n in self.FEATURE_OUTPUTS])
-        args = (self._ctx, B, img.ctypes.data_as(vp), flow.ctypes.data_as(vp), seg.ctypes.data_as(vp),
-                depth.ctypes.data_as(vp) if depth is not None else None, res["pose"].ctypes.data_as(vp), ctypes.byref(out))
         if any(n in res for n in self.HEAT_OUTPUTS):
             heat = _lib.DavoHeatOut(*[res[n].ctypes.data if n in res else None for n in self.HEAT_OUTPUTS])
-            self._check(self._L.davo_forward_heat(*(args + (ctypes.byref(heat),))))
+            self._call("davo_forward_heat", B, inputs, depth, res["pose"], ctypes.byref(out), ctypes.byref(heat), depth_slot=True)
         else:
-            self._check(self._L.davo_forward_features(*args))
+            self._call("davo_forward_features", B, inputs, depth, res["pose"], ctypes.byref(out), depth_slot=True)
         return res
 
-    def _check_batch(self, img, flow, seg):
+    def _check_batch(self, img, flow, seg, calibration=False):
         B = img.shape[0]
-        if img.shape != (B, self.H, 3 * self.W, 3):
-            raise ValueError("img shape %s != %s" % (img.shape, (B, self.H, 3 * self.W, 3)))
-        if flow.shape != (B, 4, self.H, self.W, 2):
-            raise ValueError("flow shape %s != %s" % (flow.shape, (B, 4, self.H, self.W, 2)))
-        if seg.shape != (B, 3, self.H, self.W, 1):
-            raise ValueError("seg shape %s != %s" % (seg.shape, (B, 3, self.H, self.W, 1)))
+        want = ((B, self.H, 3 * self.W, 3), (B, 4, self.H, self.W, 2), (B, 3, self.H, self.W, 1))
+        got = (img.shape, flow.shape, seg.shape)
+        if got != want:
+            if calibration:
+                raise ValueError("calibration batch shapes %s %s %s do not match the engine" % got)
+            raise ValueError(next("%s shape %s != %s" % t for t in zip(("img", "flow", "seg"), got, want) if t[1] != t[2]))
         return B
 
     def submit(self, img, flow, seg, out, hold=0, depth=None):
@@ -266,31 +292,17 @@ class Engine:
         float32 [B,2,6] array the caller keeps alive - receives the poses when the batch is delivered (a later submit, wait()
         or synchronize()).  On return the input arrays of the batch submitted ``hold`` calls ago may be overwritten.
         ``depth``: the depth planes of a depth-source variant (davo_submit_depth), held like the other inputs."""
-        if not (isinstance(img, np.ndarray) and img.dtype == np.uint8 and img.flags.c_contiguous and
-                isinstance(flow, np.ndarray) and flow.dtype == np.float32 and flow.flags.c_contiguous and
-                isinstance(seg, np.ndarray) and seg.dtype == LABEL_DTYPES[self.labels] and seg.flags.c_contiguous and seg.ndim == 5):
-            if hold:
-                raise ValueError("submit(hold > 0) needs C-contiguous uint8 / float32 / %s arrays (a converted copy would not outlive the call)"
-                                 % LABEL_DTYPES[self.labels])
-            img = np.ascontiguousarray(img, np.uint8)
-            flow = np.ascontiguousarray(flow, np.float32)
-            seg = self._label_arg(seg)
-        B = self._check_batch(img, flow, seg)
-        if self.cfg.needs_depth and hold and not (isinstance(depth, np.ndarray) and depth.dtype == np.float32 and depth.flags.c_contiguous):
-            raise ValueError("submit(hold > 0) needs a C-contiguous float32 depth array (a converted copy would not outlive the call)")
-        depth = self._depth_arg(depth, B)
-        if not (isinstance(out, np.ndarray) and out.dtype == np.float32 and out.flags.c_contiguous and out.shape == (B, 2, 6)):
+        inputs, depth, B = self._window_batch(img, flow, seg, depth, strict="submit" if hold else None)
+        self._check_out(out, B)
+        self._call("davo_submit", B, inputs, depth, out, int(hold))
+
+    @staticmethod
+    def _check_out(out, B):
+        if not (_is_ready(out, np.float32) and out.shape == (B, 2, 6)):
             raise ValueError("out must be a C-contiguous float32 array of shape (%d, 2, 6)" % B)
-        vp = ctypes.c_void_p
-        if depth is not None:
-            self._check(self._L.davo_submit_depth(self._ctx, B, img.ctypes.data_as(vp), flow.ctypes.data_as(vp), seg.ctypes.data_as(vp),
-                                                  depth.ctypes.data_as(vp), out.ctypes.data_as(vp), int(hold)))
-        else:
-            self._check(self._L.davo_submit(self._ctx, B, img.ctypes.data_as(vp), flow.ctypes.data_as(vp), seg.ctypes.data_as(vp),
-                                            out.ctypes.data_as(vp), int(hold)))
 
     # ---- frame layout (include/davo_hip.h "Frame sequences"; davo_amd/frames.py) -------------------------------------
-    def _frame_label_arg(self, seg, convert=True):
+    def _frame_label_arg(self, seg):
         """The label maps of a frame-layout batch: C-contiguous [N+2,H,W,1] of the engine's format.  As _label_arg: a byte array
         handed to a float32 engine, or anything but bytes to a byte engine, is a ValueError; nothing is converted silently."""
         dt = np.asarray(seg).dtype
@@ -298,8 +310,7 @@ class Engine:
             raise ValueError("this engine takes uint8 label maps (labels='u8'), got dtype %s: convert with davo_amd.labels_to_u8" % dt)
         if self.labels != "u8" and dt == np.uint8:
             raise ValueError("this engine takes float32 label maps (labels='f32'), got uint8: create it with labels='u8'")
-        if convert:
-            seg = np.ascontiguousarray(seg, LABEL_DTYPES[self.labels])
+        seg = np.ascontiguousarray(seg, LABEL_DTYPES[self.labels])
         return seg[..., None] if seg.ndim == 3 else seg
 
     def _check_frames(self, frames, flow2, seg):
@@ -312,66 +323,38 @@ class Engine:
             raise ValueError("seg shape %s != %s" % (seg.shape, (N + 2, self.H, self.W, 1)))
         return N
 
-    def _frames_depth_arg(self, depth, N, convert=True):
-        """The depth planes of a frame-layout batch ([N+2,H,W,1] float32), or None for a variant that reads none."""
-        if not self.cfg.needs_depth:
-            return None
-        if depth is None:
-            raise ValueError("frames, flow2, seg and depth inputs are all required for version `%s'" % self.cfg.version)
-        if convert:
-            depth = np.ascontiguousarray(depth, np.float32)
-        if depth.shape != (N + 2, self.H, self.W, 1):
-            raise ValueError("depth shape %s != %s" % (depth.shape, (N + 2, self.H, self.W, 1)))
-        return depth
-
     def forward_frames(self, frames, flow2, seg, depth=None):
         """forward() on the frame layout (include/davo_hip.h: davo_forward_frames): ``frames`` u8 [N+2,H,W,3], ``flow2`` f32
         [N,2,H,W,2], ``seg`` [N+2,H,W,1] in the engine's label format, ``depth`` f32 [N+2,H,W,1] for a depth-source variant;
         window n is frames (n, n+1, n+2).  -> [N,2,6], the bits of forward() on davo_amd.windows_from_frames of the same arrays."""
-        frames = np.ascontiguousarray(frames, np.uint8)
-        flow2 = np.ascontiguousarray(flow2, np.float32)
-        seg = self._frame_label_arg(seg)
-        N = self._check_frames(frames, flow2, seg)
-        depth = self._frames_depth_arg(depth, N)
+        inputs, depth, N = self._frame_batch(frames, flow2, seg, depth)
         out = np.empty((N, 2, 6), np.float32)
-        vp = ctypes.c_void_p
-        self._check(self._L.davo_forward_frames(self._ctx, N, frames.ctypes.data_as(vp), flow2.ctypes.data_as(vp), seg.ctypes.data_as(vp),
-                                                depth.ctypes.data_as(vp) if depth is not None else None, out.ctypes.data_as(vp)))
+        self._call("davo_forward_frames", N, inputs, depth, out, depth_slot=True)
         return out
 
     def submit_frames(self, frames, flow2, seg, out, hold=0, depth=None):
         """submit() on the frame layout (include/davo_hip.h: davo_submit_frames; shapes as forward_frames).  ``out`` [N,2,6] and
         ``hold`` as submit's; window and frame submits count alike."""
-        ok = lambda a, dt: isinstance(a, np.ndarray) and a.dtype == dt and a.flags.c_contiguous      # noqa: E731
-        if not (ok(frames, np.uint8) and ok(flow2, np.float32) and ok(seg, LABEL_DTYPES[self.labels]) and seg.ndim == 4):
-            if hold:
-                raise ValueError("submit_frames(hold > 0) needs C-contiguous uint8 / float32 / %s arrays (a converted copy would not outlive the call)"
-                                 % LABEL_DTYPES[self.labels])
-            frames = np.ascontiguousarray(frames, np.uint8)
-            flow2 = np.ascontiguousarray(flow2, np.float32)
-            seg = self._frame_label_arg(seg)
-        N = self._check_frames(frames, flow2, seg)
-        if self.cfg.needs_depth and hold and not ok(depth, np.float32):
-            raise ValueError("submit_frames(hold > 0) needs a C-contiguous float32 depth array (a converted copy would not outlive the call)")
-        depth = self._frames_depth_arg(depth, N)
-        if not (ok(out, np.float32) and out.shape == (N, 2, 6)):
-            raise ValueError("out must be a C-contiguous float32 array of shape (%d, 2, 6)" % N)
-        vp = ctypes.c_void_p
-        self._check(self._L.davo_submit_frames(self._ctx, N, frames.ctypes.data_as(vp), flow2.ctypes.data_as(vp), seg.ctypes.data_as(vp),
-                                               depth.ctypes.data_as(vp) if depth is not None else None, out.ctypes.data_as(vp), int(hold)))
+        inputs, depth, N = self._frame_batch(frames, flow2, seg, depth, strict="submit_frames" if hold else None)
+        self._check_out(out, N)
+        self._call("davo_submit_frames", N, inputs, depth, out, int(hold), depth_slot=True)
 
     def forward_device_frames(self, N, d_frames, d_flow2, d_seg, d_pose, timed=False, depth=None):
         """forward_device() on the frame layout (include/davo_hip.h: davo_forward_device_frames): DeviceBuffers of frames
         [N+2,H,W,3], flow2 [N,2,H,W,2], label maps [N+2,H,W,1] and - a depth-source variant - ``depth`` [N+2,H,W,1].  The timed
         form's milliseconds include the gather."""
-        ms = ctypes.c_float(0.0)
+        return self._call_device("davo_forward_device_frames", N, (d_frames, d_flow2, d_seg), depth, d_pose, timed, "frames, flow2, seg", depth_slot=True)
+
+    def _call_device(self, name, n, bufs, depth, d_pose, timed, names, depth_slot=False):
+        """The device entry points' checks and call: the label maps' DeviceBuffer holds the engine's format (where it knows), a
+        depth-source variant gets its depth planes (any other ignores them).  -> milliseconds of the timed form, else None."""
+        d_seg = bufs[2]
         if getattr(d_seg, "dtype", None) is not None and (d_seg.dtype == np.uint8) != (self.labels == "u8"):
             raise ValueError("d_seg holds %s label maps, this engine takes labels='%s'" % (d_seg.dtype, self.labels))
         if self.cfg.needs_depth and depth is None:
-            raise ValueError("frames, flow2, seg and depth inputs are all required for version `%s'" % self.cfg.version)
-        self._check(self._L.davo_forward_device_frames(self._ctx, int(N), d_frames.ptr, d_flow2.ptr, d_seg.ptr,
-                                                       depth.ptr if depth is not None else None, d_pose.ptr,
-                                                       ctypes.byref(ms) if timed else None))
+            raise ValueError("%s and depth inputs are all required for version `%s'" % (names, self.cfg.version))
+        ms = ctypes.c_float(0.0)
+        self._call(name, n, bufs, depth if depth_slot or self.cfg.needs_depth else None, d_pose, ctypes.byref(ms) if timed else None, depth_slot=depth_slot)
         return ms.value if timed else None
 
     def wait(self, leave_pending=0):
@@ -386,20 +369,11 @@ class Engine:
     def calibrate(self, img, flow, seg, depth=None):
         """Choose the power-of-two storage scales of the f16x3 activations from a sample batch
         (include/davo_hip.h: davo_calibrate; davo_calibrate_depth for a depth-source variant).  -> {layer: log2 scale}."""
-        img = np.ascontiguousarray(img, np.uint8)
-        flow = np.ascontiguousarray(flow, np.float32)
-        seg = self._label_arg(seg)
-        B = img.shape[0]
-        if img.shape != (B, self.H, 3 * self.W, 3) or flow.shape != (B, 4, self.H, self.W, 2) or seg.shape != (B, 3, self.H, self.W, 1):
-            raise ValueError("calibration batch shapes %s %s %s do not match the engine" % (img.shape, flow.shape, seg.shape))
-        depth = self._depth_arg(depth, B)
-        bufs = [self.alloc(a.nbytes).upload(a) for a in (img, flow, seg) + (() if depth is None else (depth,))]
+        inputs, depth, B = self._window_batch(img, flow, seg, depth, calibration=True)
+        bufs = [self.alloc(a.nbytes).upload(a) for a in inputs + (() if depth is None else (depth,))]
         shifts = (ctypes.c_int * 6)()
         try:
-            if depth is not None:
-                self._check(self._L.davo_calibrate_depth(self._ctx, B, bufs[0].ptr, bufs[1].ptr, bufs[2].ptr, bufs[3].ptr, shifts))
-            else:
-                self._check(self._L.davo_calibrate(self._ctx, B, bufs[0].ptr, bufs[1].ptr, bufs[2].ptr, shifts))
+            self._call("davo_calibrate", B, bufs[:3], bufs[3] if depth is not None else None, shifts)
         finally:
             for b in bufs:
                 b.free()
@@ -439,18 +413,7 @@ class Engine:
 
     def forward_device(self, B, d_img, d_flow, d_seg, d_pose, timed=False, depth=None):
         """``depth``: the DeviceBuffer of the depth planes, required by a depth-source variant (davo_forward_device_depth)."""
-        ms = ctypes.c_float(0.0)
-        if getattr(d_seg, "dtype", None) is not None and (d_seg.dtype == np.uint8) != (self.labels == "u8"):
-            raise ValueError("d_seg holds %s label maps, this engine takes labels='%s'" % (d_seg.dtype, self.labels))
-        if self.cfg.needs_depth:
-            if depth is None:
-                raise ValueError("image, flow, seglabel and depth inputs are all required for version `%s'" % self.cfg.version)
-            self._check(self._L.davo_forward_device_depth(self._ctx, B, d_img.ptr, d_flow.ptr, d_seg.ptr, depth.ptr, d_pose.ptr,
-                                                          ctypes.byref(ms) if timed else None))
-        else:
-            self._check(self._L.davo_forward_device(self._ctx, B, d_img.ptr, d_flow.ptr, d_seg.ptr, d_pose.ptr,
-                                                    ctypes.byref(ms) if timed else None))
-        return ms.value if timed else None
+        return self._call_device("davo_forward_device", B, (d_img, d_flow, d_seg), depth, d_pose, timed, "image, flow, seglabel")
 
     def alloc(self, nbytes):
         return DeviceBuffer(self, nbytes)

@@ -159,6 +159,39 @@ def test_submit_frames_is_submit_to_the_bit(inflight, labels):
     e.close()
 
 
+@pytest.mark.parametrize("name,labels", [("flagship", "f32"), ("se_depth_to_seg", "u8")])
+def test_layouts_interleaved_among_busy_slots(name, labels):
+    """Twelve submits on four slots, hold = 0, window and frame layout alternating, batches of 5, 1, 2 of fresh arrays, and one
+    forward_frames after the sixth (it delivers what is pending first): a staging set, a frame buffer and a pose ring entry are
+    reused across the layouts while other slots are busy.  Every delivered batch is, to the bit, forward() on the windows of
+    the same arrays on a second, fresh engine."""
+    cfg = parse_version(VARIANTS[name])
+    H, W, n = 16, 20, 12
+    data = [_frames(cfg, (5, 1, 2)[k % 3], H, W, labels, seed=500 + k) for k in range(n + 1)]      # [n]: the forward_frames call's
+    depth = (lambda parts: {"depth": parts[3]}) if cfg.needs_depth else (lambda parts: {})
+    e = _engine(cfg, H, W, labels=labels)
+    e.set_inflight(4)
+    got = [np.full((d[0][1].shape[0], 2, 6), np.nan, np.float32) for d in data]
+    for k in range(n):
+        fr, win = data[k]
+        if k % 2:
+            e.submit_frames(*fr[:3], got[k], **depth(fr))
+        else:
+            e.submit(*win[:3], got[k], **depth(win))
+        if k == 5:
+            assert e.pending() > 0
+            got[n] = e.forward_frames(*data[n][0][:3], **depth(data[n][0]))
+            assert e.pending() == 0 and not any(np.isnan(g).any() for g in got[:6])
+    e.wait()
+    assert e.pending() == 0
+    e.close()
+    ref = _engine(cfg, H, W, labels=labels)
+    for k, (_, win) in enumerate(data):
+        want = ref.forward(*win[:3], **depth(win))
+        assert np.abs(want).max() > 0 and _same(got[k], want), (name, labels, k)
+    ref.close()
+
+
 # ---- 4. one pair -----------------------------------------------------------------------------------------------------------
 def _poisoned(fr, plan, labels):
     """the frame arrays with everything outside the selection's ranges overwritten: 0xFF bytes, NaN floats"""

@@ -14,7 +14,7 @@ from davo_amd import Engine, synth, parse_version, FLAGSHIP_VERSION   # noqa: E4
 
 
 def h2d_bytes_per_window(H, W, pairs):
-    """what davo_submit copies per window of the flagship (api.hip: stage_inputs): the strip, the flow planes the path reads, the
+    """what davo_submit copies per window of the flagship (entry.hip: stage_inputs): the strip, the flow planes the path reads, the
     source frames' label maps (batches of four and more; smaller both-pairs batches copy all three) - or, with one pair, the
     (tgt, source) two thirds of every strip row, one flow plane and one label map"""
     hw = H * W
