@@ -48,7 +48,7 @@ EXPORTS = (
     "davo_comm_allreduce", "davo_comm_barrier", "davo_comm_destroy", "davo_plan_layer", "davo_tile_filter_rows",
     "davo_set_pairs", "davo_get_pairs", "davo_set_label_format", "davo_get_label_format",
     "davo_set_feature_export", "davo_forward_features", "davo_set_heat_export", "davo_forward_heat",
-    "davo_pad_class_tables", "davo_pad_class_tile_order", "davo_plan_layer_f32",
+    "davo_pad_class_tables", "davo_pad_class_tile_order", "davo_plan_layer_f32", "davo_decide_layer",
     "davo_forward_frames", "davo_submit_frames", "davo_forward_device_frames", "davo_frames_plan",
 )
 COMM_ID_BYTES = 128
@@ -244,6 +244,7 @@ def _load():
     L.davo_pad_class_tables.argtypes = [i] * 8 + [ip, usp]
     L.davo_pad_class_tile_order.argtypes = [usp, i, i, i, ip]
     L.davo_plan_layer_f32.argtypes = [i] * 4 + [ip, ip, ip]
+    L.davo_decide_layer.argtypes = [i] * 7 + [ip, i, ip, i]
     L.davo_comm_preload.argtypes = [ctypes.c_char_p, i]
     L.davo_comm_unique_id.argtypes = [vp, ctypes.c_char_p, i]
     L.davo_comm_init.argtypes = [vp, i, i, vp]

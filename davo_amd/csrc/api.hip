@@ -113,13 +113,7 @@ int davo_create(davo_ctx** out, int device, int H, int W, int max_batch, const d
     c->H2 = (c->H1 + 1) / 2; c->W2 = (c->W1 + 1) / 2;
     c->H3 = (c->H2 + 1) / 2; c->W3 = (c->W2 + 1) / 2;
     const int c6 = c->v.cnv6_out;
-    init_layer(c->L[0], "cnv1", 7, 2, 1, 8, 16, 1);
-    init_layer(c->L[1], "cnv2", 5, 2, 1, 16, 32, 1);
-    init_layer(c->L[2], "cnv3", 3, 1, 2, 32, 64, 1);
-    init_layer(c->L[3], "cnv4", 3, 1, 4, 64, 128, 1);
-    init_layer(c->L[4], "cnv5", 3, 1, 8, 128, 256, 1);
-    init_layer(c->L[5], "cnv6", 3, 1, 2, 256, 2 * c6, 1);
-    init_layer(c->L[6], "cnv7", 3, 2, 1, c6, 256, 2);
+    init_posenn_layers(c->L, c6);
 
     const int ch[7] = {16, 32, 64, 128, 256, 2 * c6, 512};
     const size_t px[7] = {(size_t)c->H1 * c->W1, (size_t)c->H2 * c->W2, (size_t)c->H2 * c->W2, (size_t)c->H2 * c->W2,
@@ -400,7 +394,7 @@ int davo_set_option(davo_ctx* c, const char* key, int value) {
     else if (k == "force_tile") {
         // test hook: every f16x3 layer the tile fits runs as ONE launch of that tile shape (plan.h tile ids; -1 = planner)
         if (value < -1 || value >= NUM_TILES) return fail(c, DAVO_ERR_INVALID, "force_tile must be -1..%d", NUM_TILES - 1);
-        for (auto& L : c->L) L.tile_h = (value >= 0 && L.cout >= tile_shape(value).bn) ? value : -1;
+        for (auto& L : c->L) L.tile_h = forced_tile_h(value, L.cout);
     }
     else if (k == "cu_partition") {
         if (c->user_stream) return fail(c, DAVO_ERR_INVALID, "cu_partition uses the context's own streams: clear davo_set_stream first");

@@ -7,9 +7,9 @@
 //   entry.hip       extern "C": the calls that take a batch (device, streaming and host forward families, both layouts), delivery
 //   export.hip      extern "C": the feature and heat exports (davo_set_*_export, davo_forward_features, davo_forward_heat)
 //   hooks.hip       extern "C": measurement and test hooks (davo_debug_read, davo_conv2d_same, plan and profile calls, memory helpers)
-//   forward.hip     the forward plan of the pose path (which kernel, which buffers, in what order)
+//   forward.hip     the forward plan of the pose path (which buffers, in what order; the conv layers as plan.hip decides them)
 //   range_guard.hip the f16x3 range guard: records, verdicts, calibration, re-issues, tickets (its bookkeeping: range_book.h)
-//   plan.hip        launch planning: tile shapes and whole-round launch splits (pure host logic)
+//   plan.hip        launch planning: tile shapes, whole-round launch splits and every launch decision of a conv layer (pure host logic)
 //   weights.hip     weight re-layout: HWIO float32 -> packed f32 / split-fp16 operands
 //   launch_f32.hip  conv_igemm_f32 instantiations + dispatch
 //   launch_h3.hip   conv_igemm_h3 instantiations + dispatch (the f16x3 path, the long compile)
@@ -42,6 +42,7 @@
 #include "../../include/davo_hip.h"
 #include "owned.h"
 #include "params.h"
+#include "plan.h"
 #include "range_book.h"
 
 namespace davo {
@@ -54,17 +55,11 @@ struct HostTensor {
     DevMem<float> dev;             // raw copy in the reference layout (impl 1, pose_head, SE)
 };
 
-struct ConvLayer {
-    const char* label;
-    int KS, stride, rate;
-    int cin, cin_log2, cout;       // packed input channels per tap (power of two), valid outputs
-    int BN, npad, kpad, nchunks, groups;
+struct ConvLayer : LayerGeom {     // plan.h: the host fields, all that the launch decisions read
+    const char* label = nullptr;
     DevMem<float> d_w;             // [groups][npad][kpad]
     DevMem<float> d_b;             // [groups][npad]
-    // f16x3 path (conv_igemm_h3.h): channel-blocked k order, split-fp16 packed weights
-    int cb_log2 = 0, tpc_log2 = 0, cpb = 0, nchunks_h = 0, npad_h = 0, tile_h = 0;
-    float wscale = 1.f;            // power of two the packed fp16 weights are multiplied by
-    DevMem<uint8_t> d_wh;          // [groups][npad_h][nchunks_h][32 hi | 32 lo] halves
+    DevMem<uint8_t> d_wh;          // f16x3: [groups][npad_h][nchunks_h][32 hi | 32 lo] halves
     DevMem<float> d_bh;            // [groups][npad_h]
 };
 
@@ -110,8 +105,6 @@ struct FrameSet {
     DevMem<void> img, seg, depth;
     bool built() const { return static_cast<bool>(img); }
 };
-
-constexpr int SK_TILE_COUNTERS = 256;            // tiles of a split-K launch whose fix-up is folded in (forward.hip): at most one per CU
 
 // A batch davo_submit has issued whose poses have not been delivered to the caller's array yet (entry.hip: streaming entry point).
 // Its inputs live in the staging set of its in-flight slot (at most MAX_INFLIGHT slots), its poses in entry `pr` of a ring of STREAM_POSES device
@@ -333,16 +326,6 @@ inline int fail(davo_ctx* c, int code, const char* fmt, ...) {
                                 __FILE__, __LINE__);                                           \
     } while (0)
 
-// TF `SAME` padding (SURVEY.md note P): out = ceil(in/stride), pad_before = total // 2
-inline void same_pad(int in, int k, int stride, int rate, int* out, int* before) {
-    const int o = (in + stride - 1) / stride;
-    const int keff = (k - 1) * rate + 1;
-    int total = (o - 1) * stride + keff - in;
-    if (total < 0) total = 0;
-    *out = o;
-    *before = total / 2;
-}
-
 // bytes of one window of each input plane
 struct PlaneBytes { size_t img, flow, seg, depth; };
 inline PlaneBytes plane_bytes(const davo_ctx* c) {
@@ -352,12 +335,6 @@ inline PlaneBytes plane_bytes(const davo_ctx* c) {
     return PlaneBytes{HW * 9, HW * 8 * sizeof(float), HW * 3 * (c->label_fmt == LABELS_U8 ? 1 : sizeof(float)), HW * 3 * sizeof(float)};
 }
 inline bool needs_depth(const davo_ctx* c) { return att_reads_depth(c->v.att_source); }
-
-inline int ilog2_exact(int v) {
-    int l = 0;
-    while ((1 << l) < v) ++l;
-    return (1 << l) == v ? l : -1;
-}
 
 // the stream slot i runs on: its own, or the caller's for slot 0 (davo_set_stream)
 inline hipStream_t slot_stream(const davo_ctx* c, int i) { return (c->user_stream && i == 0) ? c->user_stream : c->slots[i].stream.get(); }
@@ -383,6 +360,7 @@ int sync_all_slots(davo_ctx* c);
 
 // ---- weights.hip ----------------------------------------------------------------------------
 void init_layer(ConvLayer& L, const char* label, int KS, int stride, int rate, int cin, int cout, int groups);
+void init_posenn_layers(ConvLayer (&L)[7], int c6);
 std::vector<std::string> needed_names(const Variant& v, int posenn_se = 0);
 // TF name of an SE dense tensor of the variant's scope (k: 0 bottleneck_fc/kernel, 1 its bias, 2 recover_fc/kernel, 3 its bias);
 // the se_flow scope's for the variants without SE layers (the kernels do not read them there)

@@ -184,296 +184,129 @@ int slot_scratch(davo_ctx* c, const Run& run, GrowBuf* buf, size_t* floats, size
     return DAVO_OK;
 }
 
-// ---- one conv layer, FP32-MFMA path ---------------------------------------------------------------
-// fuse_pose (cnv7): the pose head runs in the epilogue (conv_igemm.h); *pose_mt receives the layer's M tiles
+// ---- one conv layer: decided in plan.hip (decide_layer_f32 / decide_layer_h3), issued here ---------------------------------------
+PlanOptions plan_options(const davo_ctx* c, int li) {
+    PlanOptions o;
+    o.wave128 = c->opt_wave128; o.skip_order = c->opt_skip_order; o.merge_order = c->opt_merge_order; o.pad_classes = c->opt_pad_classes;
+    o.merge_rem_f32 = c->opt_merge_rem_f32; o.share_taps = c->opt_share_taps; o.merge_rem = c->opt_merge_rem; o.merge_cnv4 = c->opt_merge_cnv4;
+    o.tile_208x128 = c->opt_tile_208x128; o.deep_ring = c->opt_deep_ring; o.split_k = c->opt_split_k; o.fold_fixup = c->opt_fold_fixup;
+    o.f32_n16 = c->opt_f32_n16; o.f32_n256 = c->opt_f32_n256;
+    o.ncu = c->ncu; o.dev_cus = c->dev_cus; o.cu_partition = c->cu_partition; o.user_stream = c->user_stream != nullptr; o.max_batch = c->max_batch;
+    o.shift_in = li == 0 ? 0 : c->act_shift[li - 1]; o.shift_out = c->act_shift[li];
+    return o;
+}
+
+// the profile entry of a step; a launcher's own refusal of a decided step is an internal error, never another kernel in silence
+std::string step_label(const ConvLayer& L, bool rem) { return rem ? std::string(L.label) + ".rem" : std::string(L.label); }
+int launched(davo_ctx* c, int li, int family, hipError_t e) {
+    if (e == hipErrorNotSupported) return fail(c, DAVO_ERR_INVALID, "internal: layer %d was decided for the %s launcher, which refuses it", li, family_name(family));
+    HIP_TRY(c, e);
+    return DAVO_OK;
+}
+
+// FP32-MFMA path.  fuse_pose (cnv7): the pose head runs in the epilogue (conv_igemm.h); *pose_mt receives the layer's M tiles
 int run_conv_layer(davo_ctx* c, const Run& run, int li, const float* x, int x_ld, int Hin, int Win, float* y, int y_ld, int NB, bool fuse_pose = false, int* pose_mt = nullptr) {
     const ConvLayer& L = c->L[li];
-    ConvParams p{};
-    int Ho, Wo, pt, pl;
-    same_pad(Hin, L.KS, L.stride, L.rate, &Ho, &pt);
-    same_pad(Win, L.KS, L.stride, L.rate, &Wo, &pl);
-    p.x = x; p.w = L.d_w.get(); p.bias = L.d_b.get(); p.y = y; p.zeros = c->d_zeros.get();
-    p.Hin = Hin; p.Win = Win; p.Hout = Ho; p.Wout = Wo;
-    p.cin_log2 = L.cin_log2; p.x_ld = x_ld; p.x_coff = 0; p.y_ld = y_ld; p.y_coff = 0;
-    p.Cout = L.cout; p.pad_t = pt; p.pad_l = pl; p.rate = L.rate;
-    p.M = NB * Ho * Wo; p.nchunks = L.nchunks; p.Kpad = L.kpad; p.ntaps = L.KS * L.KS;
-    p.ntiles_n = L.npad / L.BN; p.relu = 1;
-    if (L.groups == 2) {
-        p.g_x_coff = L.cin; p.g_y_coff = L.cout;
-        p.g_w = (long)L.npad * L.kpad; p.g_bias = L.npad;
-    }
-    const int mtiles = (p.M + BM - 1) / BM;
-    std::vector<Launch> plan = plan_layer(mtiles, L.npad, L.groups, c->ncu);
-    if (li == 0 && L.cout <= 16 && c->opt_f32_n16) plan = {{0, mtiles, 16}};      // cnv1 on the 128x16 tile at every batch size (conv_igemm.h, N16)
-    if (fuse_pose) {
-        { int rs = slot_scratch(c, run, &c->d_pose_tiles, &c->pose_tiles_floats, (size_t)L.groups * mtiles * 8 * 6, &p.pose_partial); if (rs) return rs; }
-        p.pose_w = c->d_wpred.get();
-        p.pose_P = Ho * Wo; p.pose_mt = mtiles;
-        if (pose_mt) *pose_mt = mtiles;
-    }
-    c->last_plan[li][0] = c->last_plan[li][1] = 0; c->last_split[li] = 1;
-    // cnv4, cnv5, cnv6: GEMM rows sorted by padding class, every tile walks the taps of its own pixels ("pad_classes")
+    const LayerDecision<ConvParams> d = decide_layer_f32(L, LayerCall{li, x_ld, Hin, Win, y_ld, true, NB, fuse_pose, false}, plan_options(c, li));
+    if (d.err) return fail(c, d.err, "%s", d.msg);
+    float* pose_partial = nullptr;
+    if (d.pose_floats) { int rs = slot_scratch(c, run, &c->d_pose_tiles, &c->pose_tiles_floats, d.pose_floats, &pose_partial); if (rs) return rs; }
+    if (fuse_pose && pose_mt) *pose_mt = d.pose_mt;
+    c->last_plan[li][0] = d.plan_code[0]; c->last_plan[li][1] = d.plan_code[1]; c->last_split[li] = d.split;
+    const ConvParams& g = d.steps[0].p[0];
     const PadTables* pc = nullptr;
-    if (li >= 3 && li <= 5 && ((c->opt_pad_classes >> (li - 3)) & 1) && L.KS == 3 && L.stride == 1 && L.cin_log2 >= 5 && L.groups == 1 && !fuse_pose && !c->opt_f32_n256) {
+    if (d.pad_classes) {
         int rc = DAVO_OK;
-        pc = pad_tables_for(c, li, NB, Ho, Wo, Hin, Win, pt, pl, L.rate, &rc);
+        pc = pad_tables_for(c, li, NB, g.Hout, g.Wout, Hin, Win, g.pad_t, g.pad_l, L.rate, &rc);
         if (rc) return rc;
-        if (pc) { p.row_pixel = pc->row_pixel.get(); p.tile_taps = pc->tile_taps.get(); }
     }
-    auto order_for = [&](const Launch& l, int ntn) {
-        if (pc) return tile_order_pc(c, li, l.mtile0, l.mtiles, ntn, p.M, Ho, Wo, *pc);
-        return (L.KS == 3 && L.cin_log2 >= 5) ? tile_order_for(c, li, 0, BM, l.mtile0, l.mtiles, ntn, p.M, Ho, Wo, Hin, L.stride, pt, L.rate) : nullptr;
-    };
-    // experiment ("f32_n256"): cnv5 / cnv6 as whole rounds of 128 x 256 tiles (eight waves, one workgroup per CU) + a remainder launch of
-    // 128 x 64 tiles
-    if (c->opt_f32_n256 && (li == 4 || li == 5) && L.npad == 256 && L.groups == 1 && !fuse_pose && mtiles >= c->ncu) {
-        const int main_m = (mtiles / c->ncu) * c->ncu;
-        ConvParams pm = p;
-        pm.mtile0 = 0; pm.ntiles_n = 1;
-        pm.tile_order = tile_order_for(c, li, 2, BM, 0, main_m, 1, p.M, Ho, Wo, Hin, L.stride, pt, L.rate);
-        {
-            ProfScope ps(c, run.stream, L.label);
-            HIP_TRY(c, launch_layer_n256(li, pm, dim3(main_m, 1), run.stream));
+    for (int i = 0; i < d.nsteps; ++i) {
+        const LaunchStep<ConvParams>& s = d.steps[i];
+        ConvParams p[2] = {s.p[0], s.p[1]};
+        for (int b = 0; b < s.nblocks; ++b) {
+            const OrderRequest& r = s.ord[b];
+            p[b].x = x; p[b].w = L.d_w.get(); p[b].bias = L.d_b.get(); p[b].y = y; p[b].zeros = c->d_zeros.get();
+            if (fuse_pose) { p[b].pose_w = c->d_wpred.get(); p[b].pose_partial = pose_partial; }
+            if (pc) {
+                p[b].row_pixel = pc->row_pixel.get(); p[b].tile_taps = pc->tile_taps.get();
+                p[b].tile_order = tile_order_pc(c, li, r.mtile0, r.mtiles, r.ntiles_n, g.M, g.Hout, g.Wout, *pc);
+            } else if (r.kind == ORDER_LONG_FIRST)
+                p[b].tile_order = tile_order_for(c, li, r.key, r.bm, r.mtile0, r.mtiles, r.ntiles_n, g.M, g.Hout, g.Wout, Hin, L.stride, g.pad_t, L.rate);
         }
-        c->last_plan[li][0] = main_m * 1000 + 256;
-        if (main_m < mtiles) {
-            ConvParams pr = p;
-            pr.mtile0 = main_m; pr.ntiles_n = L.npad / 64;
-            pr.tile_order = tile_order_for(c, li, 0, BM, main_m, mtiles - main_m, pr.ntiles_n, p.M, Ho, Wo, Hin, L.stride, pt, L.rate);
-            const std::string label = std::string(L.label) + ".rem";
-            ProfScope ps(c, run.stream, label.c_str());
-            HIP_TRY(c, launch_layer(li, 64, pr, dim3((mtiles - main_m) * pr.ntiles_n, 1), run.stream));
-            c->last_plan[li][1] = (mtiles - main_m) * 1000 + 64;
-        }
-        return DAVO_OK;
-    }
-    // main + remainder as one grid (conv_igemm.h, conv_igemm_f32_mainrem; "merge_rem_f32"): the remainder's tiles start on the CUs
-    // that finish their last main tile first, instead of behind a launch boundary.  Same tiles, same arithmetic.
-    // (cnv7 keeps its two launches: merged it measured 0.532 against 0.439 + 0.052 ms - its 32-column remainder tiles then run two per CU
-    // on the main tile's LDS and register budget instead of three, and 0.545 with a 64-column remainder; cnv4 / cnv5 / cnv6: -5 / -4 / -1 %,
-    // profiles/r05q_f32_mainrem_ab.md)
-    if (c->opt_merge_rem_f32 && li >= 3 && (li <= 5 || c->opt_merge_rem_f32 > 1) && plan.size() == 2 && plan[0].BN == 128 && (plan[1].BN == 32 || plan[1].BN == 64)) {
-        ConvParams pm = p, pr = p;
-        pm.mtile0 = plan[0].mtile0; pm.ntiles_n = L.npad / 128; pm.tile_order = order_for(plan[0], pm.ntiles_n);
-        pr.mtile0 = plan[1].mtile0; pr.ntiles_n = L.npad / plan[1].BN; pr.tile_order = order_for(plan[1], pr.ntiles_n);
-        const int n_main = plan[0].mtiles * pm.ntiles_n, n_rem = plan[1].mtiles * pr.ntiles_n;
-        if (n_main % 8 == 0 && (L.groups == 1 || n_rem % 8 == 0)) {
-            ProfScope ps(c, run.stream, L.label);
-            HIP_TRY(c, launch_layer_mainrem(li, plan[1].BN, pm, pr, n_main, n_rem, L.groups, run.stream));
-            c->last_plan[li][0] = (plan[0].mtiles + plan[1].mtiles) * 1000 + 128;      // one launch covers the layer
-            return DAVO_OK;
-        }
-    }
-    for (size_t i = 0; i < plan.size(); ++i) {
-        p.mtile0 = plan[i].mtile0;
-        p.ntiles_n = plan[i].BN == 16 ? 1 : L.npad / plan[i].BN;
-        dim3 grid(plan[i].mtiles * p.ntiles_n, L.groups);
-        p.tile_order = order_for(plan[i], p.ntiles_n);
-        const std::string label = i == 0 ? std::string(L.label) : std::string(L.label) + ".rem";
-        ProfScope ps(c, run.stream, label.c_str());
-        HIP_TRY(c, launch_layer(li, plan[i].BN, p, grid, run.stream));
-        c->last_plan[li][i] = plan[i].mtiles * 1000 + plan[i].BN;
+        const dim3 grid(s.gx, s.gy);
+        ProfScope ps(c, run.stream, step_label(L, s.rem_label).c_str());
+        const hipError_t e = s.family == FAM_F32_N256      ? launch_layer_n256(li, p[0], grid, run.stream)
+                             : s.family == FAM_F32_MAINREM ? launch_layer_mainrem(li, s.tile, p[0], p[1], s.n_main, s.n_rem, L.groups, run.stream)
+                                                           : launch_layer(li, s.tile, p[0], grid, run.stream);
+        { int rc = launched(c, li, s.family, e); if (rc) return rc; }
     }
     return DAVO_OK;
 }
 
-// ---- one conv layer, f16x3 path: x and y are split-fp16 blocked tensors (y float32 when y_f32) -----
+// f16x3 path: x and y are split-fp16 blocked tensors (y float32 when y_f32).  pose_out: the launch's last workgroup writes the poses
 int run_conv_layer_h3(davo_ctx* c, const Run& run, int li, const void* x, int x_ch, int Hin, int Win, void* y, int y_ld,
                       bool y_f32, int NB, bool fuse_pose = false, int* pose_bm = nullptr, int* pose_mt = nullptr,
                       int* pose_ntn = nullptr, float* pose_out = nullptr) {
     const ConvLayer& L = c->L[li];
-    ConvParamsH p{};
-    int Ho, Wo, pt, pl;
-    same_pad(Hin, L.KS, L.stride, L.rate, &Ho, &pt);
-    same_pad(Win, L.KS, L.stride, L.rate, &Wo, &pl);
-    p.x = static_cast<const uint8_t*>(x); p.w = L.d_wh.get(); p.bias = L.d_bh.get(); p.y = static_cast<uint8_t*>(y);
-    p.zeros = reinterpret_cast<const uint8_t*>(c->d_zeros.get());
-    p.Hin = Hin; p.Win = Win; p.Hout = Ho; p.Wout = Wo;
-    p.x_pix_bytes = (long)x_ch * 4; p.x_boff = 0; p.x_pix_log2 = ilog2_exact(x_ch * 4);
-    p.cb_log2 = L.cb_log2; p.tpc_log2 = L.tpc_log2; p.cpb = L.cpb; p.nchunks = L.nchunks_h;
-    p.w_row_bytes = (long)L.nchunks_h * 128;
-    p.y_mode = y_f32 ? 0 : 1; p.y_ld = y_ld; p.y_coff = 0; p.Cout = L.cout;
-    p.pad_t = pt; p.pad_l = pl; p.rate = L.rate;
-    p.M = NB * Ho * Wo; p.ntaps = L.KS * L.KS; p.mtile0 = 0; p.relu = 1;
-    p.Mtot = p.M; p.xs = c->opt_share_taps ? 1 : 0;
-    {   // stored activations carry 2^act_shift (exact); cnv7 feeds the float32 pose head unscaled
-        const int sin = li == 0 ? 0 : c->act_shift[li - 1], sout = li == 6 ? 0 : c->act_shift[li];
-        p.out_scale = ldexpf(1.0f / L.wscale, sout - sin);
-        p.bias_scale = ldexpf(L.wscale, sin);
-        p.range = run.range ? run.range + li : nullptr;
+    const LayerDecision<ConvParamsH> d = decide_layer_h3(L, LayerCall{li, x_ch, Hin, Win, y_ld, y_f32, NB, fuse_pose, pose_out != nullptr}, plan_options(c, li));
+    if (d.err) return fail(c, d.err, "%s", d.msg);
+    // scratch before the launches that use it (growing it may synchronise every slot), the device probe before any profiling scope
+    float *pose_partial = nullptr, *part = nullptr;
+    if (d.pose_floats) { int rs = slot_scratch(c, run, &c->d_pose_tiles, &c->pose_tiles_floats, d.pose_floats, &pose_partial, d.pose_debug_bytes); if (rs) return rs; }
+    if (d.splitk_floats) { int rs = slot_scratch(c, run, &c->d_splitk, &c->splitk_floats, d.splitk_floats, &part); if (rs) return rs; }
+    if (d.fold_if_xcd && c->xcd_rr < 0) {
+        int ok = 0;
+        HIP_TRY(c, xcd_round_robin_probe(run.stream, &ok));
+        c->xcd_rr = ok;
     }
-    if (L.groups == 2) {
-        p.g_x_boff = L.cin * 4; p.g_y_coff = L.cout;
-        p.g_w = (long)L.npad_h * p.w_row_bytes; p.g_bias = L.npad_h;
+    const bool fold = d.fold_if_xcd && c->xcd_rr > 0;
+    if (fuse_pose) {
+        if (pose_bm) *pose_bm = d.pose_bm;
+        if (pose_mt) *pose_mt = d.pose_mt;
+        if (pose_ntn) *pose_ntn = d.pose_ntn;
     }
-    if (const char* e = tuning_env("DAVO_DBG")) p.dbg = atoi(e);       // tuning build only
-    // cnv5, cnv6, cnv7 (256 channels per group) and cnv4 (128): conv_igemm_h3s.h is instantiated for them
-    const bool allow_208 = (li >= 4 && L.npad_h == 256) || (li == 3 && L.npad_h == 128 && c->opt_tile_208x128);
-    // cnv5 / cnv6 with "wave128": the 256x256 tile is conv_igemm_h3w's, 4.7 % faster than the one the planner's table was fitted on
-    // (measured across 21 batch sizes with the table scaled: only B = 24 and 256x832 B = 6 change plan, -2.7 / -3.2 %: profiles/r05bn_planner_scale.log)
-    const double others_scale = (c->opt_wave128 && (li == 4 || li == 5) && L.npad_h == 256 && L.groups == 1 && !fuse_pose) ? 0.955 : 1.0;
-    std::vector<LaunchH> plan = plan_layer_h3(p.M, L.npad_h, L.groups, L.tile_h, allow_208, c->ncu, others_scale);
-    if (fuse_pose) {      // one launch, one tile shape no taller than an image, so a tile touches <= 2 images
-        const int P = Ho * Wo;
-        const int best = plan_single_tile_h3(p.M, L.npad_h, L.groups, P, L.tile_h, allow_208, c->ncu);
-        if (best < 0) return fail(c, DAVO_ERR_INVALID, "no tile fits the fused pose head");
-        plan = {{0, p.M, best}};
-        const TileShape ts = tile_shape(best);
-        const int mt = (p.M + ts.bm - 1) / ts.bm, ntn = L.npad_h / ts.bn;
-        size_t debug_bytes = 0;
-#ifdef DAVO_POSE_DEBUG
-        debug_bytes = (size_t)L.groups * mt * ntn * 512 * 20 * sizeof(float);
-#endif
-        { int rs = slot_scratch(c, run, &c->d_pose_tiles, &c->pose_tiles_floats, (size_t)L.groups * mt * ntn * 6, &p.pose_partial, debug_bytes); if (rs) return rs; }
-        p.y_mode = 2; p.pose_w = c->d_wpred.get();
-        p.pose_P = P; p.pose_mt = mt;
-        if (pose_out) {      // the launch's last workgroup adds the tiles and writes the poses (pose_tail.h)
-            p.pose_counter = c->slots[run.slot].d_counters.get(); p.pose_bias = c->d_bpred.get(); p.pose_out = pose_out;
-            p.pose_NB = NB; p.pose_bm = ts.bm; p.pose_total = L.groups * mt * ntn; p.pose_sel = run.pairs;
-        }
-        if (pose_bm) *pose_bm = ts.bm;
-        if (pose_mt) *pose_mt = mt;
-        if (pose_ntn) *pose_ntn = ntn;
-    }
-    c->last_plan[li][0] = c->last_plan[li][1] = 0; c->last_split[li] = 1;
-    // cnv4 on conv_igemm_h3w128's 256 x 128 tiles, every row in one launch - where the 256-row tiles fill whole rounds of the CUs or
-    // nearly so: a round of them takes 24.4 us against 29.2 for the same rows on conv_igemm_h3's tiles (B = 128: 0.385 -> 0.318 ms),
-    // which a last round that is three quarters empty gives back (B = 32, 3.25 rounds: 0.0925 -> 0.0938 ms)
-    const long t256 = (p.M + 255) / 256;
-    const bool rounds_ok = t256 >= c->ncu && (double)((t256 + c->ncu - 1) / c->ncu) * c->ncu <= 1.12 * (double)t256;
-    if ((c->opt_wave128 >= 3 || (c->opt_wave128 >= 2 && rounds_ok)) && li == 3 && !fuse_pose && L.groups == 1 && L.npad_h == 128 && L.tile_h < 0 &&
-        p.M >= 256 * c->ncu) {
-        ConvParamsH pw = p;
-        pw.ntiles_n = 1; pw.mtile0 = 0;
-        if (layer_h3w128_supported(pw)) {
-            {
-                ProfScope ps(c, run.stream, L.label);
-                HIP_TRY(c, launch_layer_h3w128(pw, run.stream));
+    c->last_plan[li][0] = d.plan_code[0]; c->last_plan[li][1] = d.plan_code[1]; c->last_split[li] = d.split;
+    uint8_t* const y8 = static_cast<uint8_t*>(y);
+    unsigned* const range = run.range ? run.range + li : nullptr;
+    for (int i = 0; i < d.nsteps; ++i) {
+        const LaunchStep<ConvParamsH>& s = d.steps[i];
+        ConvParamsH p[2] = {s.p[0], s.p[1]};
+        for (int b = 0; b < s.nblocks; ++b) {
+            const OrderRequest& r = s.ord[b];
+            p[b].x = static_cast<const uint8_t*>(x); p[b].w = L.d_wh.get(); p[b].bias = L.d_bh.get(); p[b].y = y8;
+            p[b].zeros = reinterpret_cast<const uint8_t*>(c->d_zeros.get());
+            p[b].range = range;
+            if (fuse_pose) { p[b].pose_w = c->d_wpred.get(); p[b].pose_partial = pose_partial; }
+            if (fuse_pose && pose_out) {      // pose_tail.h
+                p[b].pose_counter = c->slots[run.slot].d_counters.get(); p[b].pose_bias = c->d_bpred.get(); p[b].pose_out = pose_out;
+                p[b].pose_sel = run.pairs;
             }
-            c->last_plan[li][0] = ((p.M + 127) / 128) * 1000 + TILE_256x128;
-            return DAVO_OK;
+            if (r.kind == ORDER_LONG_FIRST)
+                p[b].tile_order = tile_order_for(c, li, r.key, r.bm, r.mtile0, r.mtiles, r.ntiles_n, p[b].M, p[b].Hout, p[b].Wout, Hin, L.stride, p[b].pad_t, L.rate);
         }
-    }
-    if (c->opt_merge_cnv4 && c->opt_merge_rem && li == 3 && !fuse_pose && L.npad_h == 128 && L.groups == 1 && c->ncu == 256 && L.tile_h < 0 &&
-        plan.size() == 1 && plan[0].tile == TILE_128x128) {
-        // cnv4 (N = 128): whole rounds of 256x128 tiles (shared-tap staging, twice the matrix work per staged byte of the
-        // 128x128 tile) + the remaining rows on 128x128 tiles, as one grid like cnv5 / cnv6 below
-        const int rows1 = (p.M / 256 / c->ncu) * c->ncu * 256;
-        const int rem = p.M - rows1, n_rem = (rem + 127) / 128;
-        if (rows1 > 0 && rem > 0 && rem % 128 == 0 && n_rem % 64 == 0 && n_rem <= 256)
-            plan = {{0, rows1, TILE_256x128}, {rows1, rem, TILE_128x128}};
-    }
-    const bool merge_256 = plan.size() == 2 && plan[0].tile == TILE_256x256 && plan[1].tile == TILE_128x128 && L.npad_h == 256;
-    // the merged grid's 256x128 main tile is instantiated for cnv4 alone (launch_h3.hip): a cnv6 of 128 columns (-cnv6_64) with the same
-    // plan keeps its two launches
-    const bool merge_128 = li == 3 && plan.size() == 2 && plan[0].tile == TILE_256x128 && plan[1].tile == TILE_128x128 && L.npad_h == 128;
-    if (c->opt_merge_rem && !fuse_pose && (merge_256 || merge_128) && L.groups == 1 && c->ncu == 256 && !tuning_env("DAVO_NO_MERGE")) {
-        // main + remainder as one grid (conv_igemm_h3_mainrem): same tiles, same arithmetic, de-phased store bursts
-        ConvParamsH pm = p, pr = p;
-        const int rem_ntn = L.npad_h / 128;                       // N tiles of a 128x128 remainder row block
-        pm.ntiles_n = 1; pm.mtile0 = 0; pm.M = plan[0].rows;
-        pr.ntiles_n = rem_ntn; pr.mtile0 = plan[1].row0 / 128; pr.M = plan[1].row0 + plan[1].rows;
-        const int n_main = plan[0].rows / 256, n_rem = ((plan[1].rows + 127) / 128) * rem_ntn;
-        // the shape test comes first: a profiling scope is opened only around a launch that is really issued
-        // (an empty event pair under the layer's label would halve its average and advance the stride counter twice)
-        // "wave128": the four-wave main tile (conv_igemm_h3w.h) runs as a launch of its own - merged with four-wave remainder tiles it
-        // measured 0.262 / 0.497 ms for cnv5 / cnv6 against 0.258 / 0.487 as two launches (profiles/r05bc_w128_ab.log)
-        const bool own_launch = c->opt_wave128 && merge_256 && layer_h3w_supported(li, pm);
-        if (!own_launch && layer_h3_mainrem_supported(li, pm, n_main, n_rem)) {
-            // f16x3: long-first measured 256.8 against 259.9 us on cnv5 with a third more HBM reads (205 -> 272 MB: neighbours no longer
-            // run side by side) and no change of the power-capped step: natural order unless "skip_order" is 2
-            pm.tile_order = c->opt_skip_order >= 2 ? tile_order_for(c, li, 1, 256, 0, n_main, 1, pm.M, Ho, Wo, Hin, L.stride, pt, L.rate) : nullptr;
-            const int order = c->opt_merge_order >= 0 ? c->opt_merge_order : (pm.tile_order ? 2 : 0);
-            {
-                ProfScope ps(c, run.stream, L.label);
-                HIP_TRY(c, launch_layer_h3_mainrem(li, pm, n_main, pr, n_rem, order, run.stream));
-            }
-            c->last_plan[li][0] = ((plan[0].rows + plan[1].rows + 127) / 128) * 1000 + 7;     // 7: 256x256 + 128x128 in one grid
-            return DAVO_OK;
-        }
-    }
-    // Split-K.  A launch of at most half a workgroup per CU (cnv6 at batch 1: 104 tiles of 128x128, each a serial chain of 72
-    // chunks at ~0.7 us) leaves half of the chip idle and is as long as its chain: the two halves of the input channels run
-    // as two "groups" of the same kernel (the grouped-convolution path cnv7 uses: own channel offset, weight offset and
-    // output slot; the second half starts from a zero bias) into float32 partial sums, and splitk_fixup adds the two,
-    // applies ReLU and writes the stored form.  Two partial sums instead of one chain change the float32 rounding of the
-    // layer's outputs (not their value: ~1e-7 relative), so batch sizes that split and batch sizes that do not agree to
-    // rounding, not to the bit ("split_k" 0 restores the single chain).  (With S parts: S groups, S partial sums.)
-    if (c->opt_split_k && !fuse_pose && (li == 4 || li == 5) && L.groups == 1 && plan.size() == 1 && p.y_mode == 1 && L.cout % 32 == 0 &&
-        !is_208(plan[0].tile)) {
-        const TileShape ts = tile_shape(plan[0].tile);
-        const int mtiles = (p.M + ts.bm - 1) / ts.bm, ntn = L.npad_h / ts.bn;
-        const long tiles = (long)mtiles * ntn;
-        // parts: whole channel blocks each, whole filter rows (shared-tap staging walks a row's three taps together).  Four parts
-        // where the workgroups then still fit side by side (two per CU on the two-slot ring), else two (one per CU, deep ring)
-        auto fits = [&](int S) { return L.nchunks_h % (S * L.cpb) == 0 && ((L.nchunks_h / S) % 3) == 0; };
-        const int per_cu = ts.lds * 2 <= 160 * 1024 ? 2 : 1;
-        const int S = (fits(4) && tiles * 4 <= (long)per_cu * c->ncu && tiles * 2 <= c->ncu) ? 4 : (fits(2) && tiles * 2 <= c->ncu ? 2 : 1);       // two parts at two per CU (B = 2) measured slower: 54 -> 57 us
-        if (S > 1) {
-            float* part = nullptr;
-            { int rs = slot_scratch(c, run, &c->d_splitk, &c->splitk_floats, (size_t)p.M * S * L.cout, &part); if (rs) return rs; }
-            ConvParamsH ps = p;
-            ps.nchunks = L.nchunks_h / S;
-            ps.g_x_boff = (L.cin / S) * 4; ps.g_w = (long)ps.nchunks * 128; ps.g_bias = L.npad_h; ps.g_y_coff = L.cout;
-            ps.y = reinterpret_cast<uint8_t*>(part); ps.y_mode = 0; ps.y_ld = S * L.cout; ps.relu = 0; ps.range = nullptr;
-            ps.ntiles_n = ntn; ps.mtile0 = 0;
-            dim3 grid(mtiles * ntn, S);
-            ps.deep = c->opt_deep_ring && tiles * S <= c->ncu;
-            c->last_plan[li][0] = ((p.M + 127) / 128) * 1000 + plan[0].tile; c->last_split[li] = S;
-            // The fix-up folded into the launch (pose_tail.h, splitk_tail): with an x extent that is a multiple of 8 the S parts of a
-            // tile run on one XCD, so the part that finishes last finds the others' partial sums in its own L2 and writes the stored
-            // form itself - no splitk_fixup launch (7 us each at batch 1, two per forward).  Checked once per context on the device.
-            bool fold = c->opt_fold_fixup && S <= 4 && grid.x % 8 == 0 && (int)grid.x <= SK_TILE_COUNTERS && c->ncu == c->dev_cus && !c->cu_partition &&
-                        !c->user_stream;
-            if (fold && c->xcd_rr < 0) {
-                int ok = 0;
-                HIP_TRY(c, xcd_round_robin_probe(run.stream, &ok));
-                c->xcd_rr = ok;
-            }
-            fold = fold && c->xcd_rr > 0;
-            if (fold) {
-                ps.sk_counter = c->slots[run.slot].d_counters.get() + 1 + c->max_batch;
-                ps.sk_y = p.y; ps.sk_range = p.range; ps.sk_parts = S; ps.sk_relu = 1;
-            }
-            ProfScope pscope(c, run.stream, L.label);
-            HIP_TRY(c, launch_layer_h3(li, plan[0].tile, ps, grid, run.stream));
-            if (!fold) HIP_TRY(c, launch_splitk_fixup(part, p.M, L.cout, S, 1, p.y, p.range, run.stream));
-            return DAVO_OK;
-        }
-    }
-    for (size_t i = 0; i < plan.size() && i < 2; ++i) {
-        const TileShape ts = tile_shape(plan[i].tile);
-        p.ntiles_n = L.npad_h / ts.bn;
-        p.mtile0 = plan[i].row0 / ts.bm;
-        const int full_m = p.M;
-        p.M = plan[i].row0 + plan[i].rows;                    // rows past this launch's range are not its job
-        const int mtiles = (plan[i].rows + ts.bm - 1) / ts.bm;
-        dim3 grid(mtiles * p.ntiles_n, L.groups);
-        p.deep = c->opt_deep_ring && plan.size() == 1 && (long)grid.x * grid.y <= c->ncu;       // at most one workgroup per CU
-        c->last_plan[li][i] = ((plan[i].rows + 127) / 128) * 1000 + plan[i].tile;
-        // no tile order here: cnv4's single launch of 128x128 tiles (two per CU, 6.5 rounds) measured 94.4 us in natural order and
-        // 97.4 long-first (profiles/r04e_skip_padding_rows.md); the merged grids above and the float32 launches take one
-        const std::string label = i == 0 ? std::string(L.label) : std::string(L.label) + ".rem";
-        {
-            ProfScope ps(c, run.stream, label.c_str());
-            bool done = false;
-            if (c->opt_wave128 && L.groups == 1 && !fuse_pose) {
-                if (plan[i].tile == TILE_256x256 && layer_h3w_supported(li, p)) {
-                    HIP_TRY(c, launch_layer_h3w(li, p, grid, run.stream));
-                    done = true;
-                } else if (c->opt_wave128 >= 2 && i == 1 && plan.size() == 2 && plan[0].tile == TILE_256x256 && plan[1].tile == TILE_128x128 &&
-                           L.npad_h == 256 && plan[1].row0 % 256 == 0 && plan[1].rows % 256 == 0) {
-                    // the remainder rows of a layer whose main launch ran on conv_igemm_h3w: 256 x 64 tiles (conv_igemm_h3w64)
-                    ConvParamsH pr = p;
-                    pr.ntiles_n = 4; pr.mtile0 = plan[1].row0 / 256;
-                    const hipError_t e = launch_layer_h3w64(li, pr, run.stream);
-                    if (e == hipSuccess) done = true;
-                    else if (e != hipErrorNotSupported) HIP_TRY(c, e);
+        const dim3 grid(s.gx, s.gy);
+        hipError_t e = hipSuccess;
+        ProfScope ps(c, run.stream, step_label(L, s.rem_label).c_str());       // split-K: the kernel and its fix-up together
+        switch (s.family) {
+            case FAM_H3: case FAM_H3S: e = launch_layer_h3(li, s.tile, p[0], grid, run.stream); break;
+            case FAM_H3W: e = launch_layer_h3w(li, p[0], grid, run.stream); break;
+            case FAM_H3W64: e = launch_layer_h3w64(li, p[0], run.stream); break;
+            case FAM_H3W128: e = launch_layer_h3w128(p[0], run.stream); break;
+            case FAM_H3_MAINREM:
+                e = launch_layer_h3_mainrem(li, p[0], s.n_main, p[1], s.n_rem, s.order >= 0 ? s.order : (p[0].tile_order ? 2 : 0), run.stream);
+                break;
+            case FAM_H3_SPLITK:
+                p[0].y = reinterpret_cast<uint8_t*>(part); p[0].range = nullptr;
+                if (fold) {
+                    p[0].sk_counter = c->slots[run.slot].d_counters.get() + d.sk_counter0;
+                    p[0].sk_y = y8; p[0].sk_range = range; p[0].sk_parts = d.split; p[0].sk_relu = 1;
                 }
-            }
-            if (!done) HIP_TRY(c, launch_layer_h3(li, plan[i].tile, p, grid, run.stream));
+                e = launch_layer_h3(li, s.tile, p[0], grid, run.stream);
+                if (e == hipSuccess && !fold) e = launch_splitk_fixup(part, d.sk_M, d.sk_cout, d.split, 1, y8, range, run.stream);
+                break;
+            default: e = hipErrorNotSupported;
         }
-        p.M = full_m;
+        { int rc = launched(c, li, s.family, e); if (rc) return rc; }
     }
     return DAVO_OK;
 }

@@ -233,6 +233,68 @@ int davo_plan_layer(int M, int npad, int groups, int* rows, int* tile_bm, int* t
     return (int)plan.size();
 }
 
+int davo_decide_layer(int precision, int layer, int H, int W, int NB, int cnv6_out, int fuse_pose, const int* options, int n_options,
+                      int* out, int out_cap) {
+    if (precision < 0 || precision > 1 || layer < 0 || layer > 6 || H < 1 || W < 1 || NB < 1 || cnv6_out < 1 || !out || (n_options > 0 && !options) ||
+        n_options < 0 || n_options > DAVO_DECIDE_OPTIONS)
+        return DAVO_ERR_INVALID;
+    PlanOptions o;
+    int force_tile = -1, pose_tail = 0, posenn_se = 0;
+    int* const slot[DAVO_DECIDE_OPTIONS] = {&o.wave128, &o.skip_order, &o.merge_order, &o.pad_classes, &o.merge_rem_f32, nullptr, nullptr, nullptr, nullptr, nullptr,
+                                            nullptr, nullptr, nullptr, nullptr, &o.ncu, &o.dev_cus, nullptr, nullptr, &o.max_batch, &o.shift_in, &o.shift_out,
+                                            &force_tile, &pose_tail, &posenn_se};
+    bool* const flag[DAVO_DECIDE_OPTIONS] = {nullptr, nullptr, nullptr, nullptr, nullptr, &o.share_taps, &o.merge_rem, &o.merge_cnv4, &o.tile_208x128, &o.deep_ring,
+                                             &o.split_k, &o.fold_fixup, &o.f32_n16, &o.f32_n256, nullptr, nullptr, &o.cu_partition, &o.user_stream};
+    for (int i = 0; i < n_options; ++i) {
+        if (slot[i]) *slot[i] = options[i];
+        else *flag[i] = options[i] != 0;
+    }
+    if (o.ncu < 1 || o.dev_cus < 1 || o.max_batch < 1 || force_tile < -1 || force_tile >= NUM_TILES) return DAVO_ERR_INVALID;
+    // the ladder of forward_device: cnv1 reads the 8-channel packed frame pair, cnv2 and cnv3 halve the map, cnv7 stores float32
+    ConvLayer L[7];
+    init_posenn_layers(L, cnv6_out);
+    if (posenn_se) init_layer(L[5], "cnv6", 3, 1, 2, 256, cnv6_out, 2);          // davo_set_posenn_se: one group per head
+    for (ConvLayer& l : L) l.tile_h = forced_tile_h(force_tile, l.cout);
+    const int H1 = (H + 1) / 2, W1 = (W + 1) / 2, H2 = (H1 + 1) / 2, W2 = (W1 + 1) / 2;
+    const int x_ch[7] = {8, 16, 32, 64, 128, posenn_se ? 512 : 256, 2 * cnv6_out}, y_ld[7] = {16, 32, 64, 128, 256, 2 * cnv6_out, 512};
+    const LayerCall call{layer, x_ch[layer], layer == 0 ? H : layer == 1 ? H1 : H2, layer == 0 ? W : layer == 1 ? W1 : W2, y_ld[layer],
+                         precision == 0 || layer == 6, NB, fuse_pose != 0, pose_tail != 0};
+    int n = 0;
+    auto put = [&](long v) { if (n < out_cap) out[n] = (int)v; ++n; };
+    // m_end: one past the step's last output row; deep, family_ok: f16x3 only (the family's own predicate on the step's own block)
+    auto record = [&](const auto& d, auto m_end, auto deep, auto family_ok) {
+        if (d.err) return d.err;
+        put(d.nsteps);
+        for (int i = 0; i < d.nsteps; ++i) {
+            const auto& s = d.steps[i];
+            const auto &p = s.p[0], &r = s.p[s.nblocks - 1];
+            for (long v : {(long)s.family, (long)s.tile, (long)s.row0, (long)m_end(s), (long)p.mtile0, (long)p.ntiles_n, (long)s.gx, (long)s.gy,
+                           (long)s.n_main, (long)s.n_rem, (long)s.order, (long)deep(s), (long)s.rem_label, (long)(s.nblocks > 1 ? r.mtile0 : 0),
+                           (long)(s.nblocks > 1 ? r.ntiles_n : 0), (long)s.ord[0].kind, (long)family_ok(s), (long)p.nchunks})
+                put(v);
+        }
+        for (long v : {(long)d.plan_code[0], (long)d.plan_code[1], (long)d.split, (long)d.fold_if_xcd, (long)d.pad_classes, (long)d.pose_bm, (long)d.pose_mt,
+                       (long)d.pose_ntn, (long)d.pose_floats, (long)d.splitk_floats, (long)L[layer].nchunks_h, (long)L[layer].cpb})
+            put(v);
+        return n;
+    };
+    if (precision == 0) {
+        typedef LaunchStep<ConvParams> S;
+        return record(decide_layer_f32(L[layer], call, o), [](const S& s) { return s.m_end; }, [](const S&) { return 0; }, [](const S&) { return 1; });
+    }
+    typedef LaunchStep<ConvParamsH> S;
+    return record(decide_layer_h3(L[layer], call, o), [](const S& s) { return s.p[s.nblocks - 1].M; }, [](const S& s) { return s.p[0].deep; },
+                  [&](const S& s) {
+                      const ConvParamsH& p = s.p[0];
+                      return s.family == FAM_H3W          ? layer_h3w_supported(layer, p)
+                             : s.family == FAM_H3W64      ? layer_h3w64_supported(layer, p)
+                             : s.family == FAM_H3W128     ? layer_h3w128_supported(p)
+                             : s.family == FAM_H3_MAINREM ? layer_h3_mainrem_supported(layer, p, s.n_main, s.n_rem)
+                             : s.family == FAM_H3S        ? is_208(s.tile)
+                                                          : !is_208(s.tile);
+                  });
+}
+
 int davo_conv2d_same(int device, const float* x, int N, int H, int W, int Cin, const float* w, int k, int Cout,
                      const float* bias, int stride, int rate, int relu, int precision, float* y, char* err, int err_len) {
     auto bad = [&](const char* m, int code) {
@@ -290,26 +352,21 @@ int davo_conv2d_same(int device, const float* x, int N, int H, int W, int Cin, c
         if (precision == 1) {
             const int tile = Cout <= 32 ? TILE_128x32 : Cout <= 64 ? TILE_256x64 : Cout <= 128 ? TILE_256x128 : TILE_128x256;
             const TileShape ts = tile_shape(tile);
-            ConvParamsH p{};
+            // float32 output, no shared-tap staging (the generic instantiations have none), unscaled storage
+            ConvParamsH p = fill_params_h3(L, LayerCall{0, Cin, H, W, Cout, true, N, false, false}, false, 0, 0);
             p.x = static_cast<const uint8_t*>(dx.get()); p.w = static_cast<const uint8_t*>(dw.get());
             p.bias = static_cast<const float*>(db.get()); p.y = static_cast<uint8_t*>(dy.get());
             p.zeros = static_cast<const uint8_t*>(dz.get());
-            p.Hin = H; p.Win = W; p.Hout = Ho; p.Wout = Wo; p.x_pix_bytes = (long)Cin * 4; p.x_pix_log2 = -1;
-            p.cb_log2 = L.cb_log2; p.tpc_log2 = L.tpc_log2; p.cpb = L.cpb; p.nchunks = L.nchunks_h;
-            p.w_row_bytes = (long)L.nchunks_h * 128; p.y_mode = 0; p.y_ld = Cout; p.Cout = Cout;
-            p.pad_t = pt; p.pad_l = pl; p.rate = rate; p.M = N * Ho * Wo; p.ntaps = k * k;
-            p.Mtot = p.M; p.xs = 0; p.ntiles_n = L.npad_h / ts.bn; p.relu = relu; p.out_scale = 1.0f / L.wscale; p.bias_scale = L.wscale; p.range = nullptr;
+            p.x_pix_log2 = -1; p.ntiles_n = L.npad_h / ts.bn; p.relu = relu;
             dim3 grid((p.M + ts.bm - 1) / ts.bm * p.ntiles_n, 1);
             const hipError_t le = launch_h3_generic(k, stride, tile, p, grid, nullptr);
             chk(le);
         } else {
-            ConvParams p{};
+            ConvParams p = fill_params_f32(L, LayerCall{0, Cin, H, W, Cout, true, N, false, false});
             p.x = static_cast<const float*>(dx.get()); p.w = static_cast<const float*>(dw.get());
             p.bias = static_cast<const float*>(db.get()); p.y = static_cast<float*>(dy.get());
             p.zeros = static_cast<const float*>(dz.get());
-            p.Hin = H; p.Win = W; p.Hout = Ho; p.Wout = Wo; p.cin_log2 = cl; p.x_ld = Cin; p.y_ld = Cout;
-            p.Cout = Cout; p.pad_t = pt; p.pad_l = pl; p.rate = rate; p.M = N * Ho * Wo;
-            p.nchunks = L.nchunks; p.Kpad = L.kpad; p.ntaps = k * k; p.ntiles_n = L.npad / L.BN; p.relu = relu;
+            p.relu = relu;
             dim3 grid((p.M + BM - 1) / BM * p.ntiles_n, 1);
             chk(launch_conv(k, stride, L.BN, p, grid, nullptr));
         }

@@ -25,19 +25,21 @@ hipError_t launch_layer_mainrem(int layer, int rbn, const ConvParams& pm, const 
 // ---- launch_h3.hip: conv_igemm_h3 (f16x3) -----------------------------------------------------------
 hipError_t launch_layer_h3(int layer, int tile, const ConvParamsH& p, dim3 grid, hipStream_t s);
 // main launch (256x256 tiles, shared-tap staging) + remainder launch (128x128 tiles) of cnv5 / cnv6 (layer 4 / 5) as one grid
-// (conv_igemm_h3_mainrem), or 256x128 + 128x128 of cnv4 (layer 3); hipErrorNotSupported when the two launches do not have that shape
-// or the layer's padded Cout is narrower than the instantiation's main tile (a -cnv6_64 cnv6 has 128 columns): the caller issues them separately
-// whether launch_layer_h3_mainrem would issue this shape (asked BEFORE the profiling scope of the launch is opened)
+// (conv_igemm_h3_mainrem), or 256x128 + 128x128 of cnv4 (layer 3).  Not supported where the two launches do not have that shape
+// or the layer's padded Cout is narrower than the instantiation's main tile (a -cnv6_64 cnv6 has 128 columns): such a layer keeps its two launches
 bool layer_h3_mainrem_supported(int layer, const ConvParamsH& pm, int n_main, int n_rem);
 // order: 0 = the short tiles' offset inside every XCD (round 2), 1 = per XCD (even XCDs short tiles first, odd XCDs last)
 hipError_t launch_layer_h3_mainrem(int layer, const ConvParamsH& pm, int n_main, const ConvParamsH& pr, int n_rem, int order, hipStream_t s);
 // launch_h3s.hip: conv_igemm_h3s (TILE_208x256) for layer 4..6 = cnv5, cnv6, cnv7
 hipError_t launch_layer_h3s(int layer, const ConvParamsH& p, dim3 grid, hipStream_t s);
 // conv_igemm_h3w.h: 256x256 tiles on four waves of 128x128 (cnv5, cnv6; option "wave128")
+// the *_supported predicates read geometry fields only: decide_layer_h3 (plan.hip) asks them, so no launch is ever tried; a launcher's
+// own hipErrorNotSupported is an assertion of last resort (forward.hip reports it as an internal error)
 bool layer_h3w_supported(int layer, const ConvParamsH& p);
 hipError_t launch_layer_h3w(int layer, const ConvParamsH& p, dim3 grid, hipStream_t s);
 bool layer_h3w128_supported(const ConvParamsH& p);
 hipError_t launch_layer_h3w128(const ConvParamsH& p, hipStream_t s);      // cnv4: 256x128 tiles, p.mtile0 in 256-row tiles
+bool layer_h3w64_supported(int layer, const ConvParamsH& p);
 hipError_t launch_layer_h3w64(int layer, const ConvParamsH& p, hipStream_t s);      // remainder rows: 256x64 tiles, p.ntiles_n = 4, p.mtile0 in 256-row tiles
 hipError_t launch_h3_generic(int KS, int stride, int tile, const ConvParamsH& p, dim3 grid, hipStream_t s);
 

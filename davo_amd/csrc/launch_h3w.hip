@@ -40,10 +40,14 @@ static hipError_t launch_w64(const ConvParamsH& p, dim3 grid, hipStream_t s) {
 }
 
 // p as for the 256x256 tile but with ntiles_n = 4
-hipError_t launch_layer_h3w64(int layer, const ConvParamsH& p, hipStream_t s) {
+bool layer_h3w64_supported(int layer, const ConvParamsH& p) {
     ConvParamsH q = p;
     q.ntiles_n = 1;
-    if (p.ntiles_n != 4 || !layer_h3w_supported(layer, q)) return hipErrorNotSupported;
+    return p.ntiles_n == 4 && layer_h3w_supported(layer, q);
+}
+
+hipError_t launch_layer_h3w64(int layer, const ConvParamsH& p, hipStream_t s) {
+    if (!layer_h3w64_supported(layer, p)) return hipErrorNotSupported;
     const dim3 grid((unsigned)((p.M - p.mtile0 * 256) / 256 * 4));
     if (layer == 4) return launch_w64<5, 8>(p, grid, s);
     return launch_w64<6, 2>(p, grid, s);

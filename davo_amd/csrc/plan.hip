@@ -1,9 +1,14 @@
 // plan.hip — launch planning (see plan.h).  Host logic only.
 #include "plan.h"
 
+#include <algorithm>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+
+#include "../../include/davo_hip.h"
+#include "launch.h"
 
 namespace davo {
 
@@ -174,6 +179,274 @@ int plan_single_tile_h3(int M, int npad, int groups, int max_bm, int forced_tile
         if (best >= 0 || forced_tile < 0) return best;
     }
     return -1;
+}
+
+// ---- a layer's launches (plan.h: LayerDecision) ----------------------------------------------------------------------------------
+const char* family_name(int family) {
+    static const char* const names[NUM_FAMILIES] = {"h3", "h3s", "h3w", "h3w64", "h3w128", "h3_mainrem", "h3 split-K", "f32", "f32 n256", "f32 mainrem"};
+    return family >= 0 && family < NUM_FAMILIES ? names[family] : "?";
+}
+
+ConvParamsH fill_params_h3(const LayerGeom& L, const LayerCall& call, bool share_taps, int shift_in, int shift_out) {
+    ConvParamsH p{};
+    same_pad(call.Hin, L.KS, L.stride, L.rate, &p.Hout, &p.pad_t);
+    same_pad(call.Win, L.KS, L.stride, L.rate, &p.Wout, &p.pad_l);
+    p.Hin = call.Hin; p.Win = call.Win;
+    p.x_pix_bytes = (long)call.x_ch * 4; p.x_boff = 0; p.x_pix_log2 = ilog2_exact(call.x_ch * 4);
+    p.cb_log2 = L.cb_log2; p.tpc_log2 = L.tpc_log2; p.cpb = L.cpb; p.nchunks = L.nchunks_h;
+    p.w_row_bytes = (long)L.nchunks_h * 128;
+    p.y_mode = call.y_f32 ? 0 : 1; p.y_ld = call.y_ld; p.y_coff = 0; p.Cout = L.cout;
+    p.rate = L.rate;
+    p.M = call.NB * p.Hout * p.Wout; p.ntaps = L.KS * L.KS; p.mtile0 = 0; p.relu = 1;
+    p.Mtot = p.M; p.xs = share_taps ? 1 : 0;
+    // stored activations carry 2^act_shift (exact)
+    p.out_scale = ldexpf(1.0f / L.wscale, shift_out - shift_in);
+    p.bias_scale = ldexpf(L.wscale, shift_in);
+    if (L.groups == 2) {
+        p.g_x_boff = L.cin * 4; p.g_y_coff = L.cout;
+        p.g_w = (long)L.npad_h * p.w_row_bytes; p.g_bias = L.npad_h;
+    }
+    return p;
+}
+
+ConvParams fill_params_f32(const LayerGeom& L, const LayerCall& call) {
+    ConvParams p{};
+    same_pad(call.Hin, L.KS, L.stride, L.rate, &p.Hout, &p.pad_t);
+    same_pad(call.Win, L.KS, L.stride, L.rate, &p.Wout, &p.pad_l);
+    p.Hin = call.Hin; p.Win = call.Win;
+    p.cin_log2 = L.cin_log2; p.x_ld = call.x_ch; p.x_coff = 0; p.y_ld = call.y_ld; p.y_coff = 0;
+    p.Cout = L.cout; p.rate = L.rate;
+    p.M = call.NB * p.Hout * p.Wout; p.nchunks = L.nchunks; p.Kpad = L.kpad; p.ntaps = L.KS * L.KS;
+    p.ntiles_n = L.npad / L.BN; p.relu = 1;
+    if (L.groups == 2) {
+        p.g_x_coff = L.cin; p.g_y_coff = L.cout;
+        p.g_w = (long)L.npad * L.kpad; p.g_bias = L.npad;
+    }
+    return p;
+}
+
+// The float32 rules, in order: the planner's launches (cnv1 on the 128x16 tile), then "f32_n256", then the merged
+// main + remainder grid, else one launch per planned launch.
+LayerDecision<ConvParams> decide_layer_f32(const LayerGeom& L, const LayerCall& call, const PlanOptions& o) {
+    LayerDecision<ConvParams> d;
+    const int li = call.li;
+    ConvParams p = fill_params_f32(L, call);
+    const int mtiles = (p.M + BM - 1) / BM;
+    std::vector<Launch> plan = plan_layer(mtiles, L.npad, L.groups, o.ncu);
+    if (li == 0 && L.cout <= 16 && o.f32_n16) plan = {{0, mtiles, 16}};      // cnv1 on the 128x16 tile at every batch size (conv_igemm.h, N16)
+    if (call.fuse_pose) {      // the pose head runs in the epilogue (conv_igemm.h)
+        d.pose_floats = (size_t)L.groups * mtiles * 8 * 6;
+        p.pose_P = p.Hout * p.Wout; p.pose_mt = mtiles;
+        d.pose_bm = BM; d.pose_mt = mtiles; d.pose_ntn = 8;
+    }
+    // cnv4, cnv5, cnv6: GEMM rows sorted by padding class, every tile walks the taps of its own pixels ("pad_classes")
+    d.pad_classes = li >= 3 && li <= 5 && ((o.pad_classes >> (li - 3)) & 1) && L.KS == 3 && L.stride == 1 && L.cin_log2 >= 5 && L.groups == 1 &&
+                    !call.fuse_pose && !o.f32_n256;
+    const bool long_first = L.KS == 3 && L.cin_log2 >= 5;       // the tiles of a 3x3 layer skip different numbers of padding rows
+    auto block = [&](LaunchStep<ConvParams>& s, int b, int key, int mtile0, int n_mtiles, int ntn) {
+        s.p[b] = p;
+        s.p[b].mtile0 = mtile0; s.p[b].ntiles_n = ntn;
+        s.ord[b] = {long_first ? ORDER_LONG_FIRST : ORDER_NONE, key, BM, mtile0, n_mtiles, ntn};
+        s.nblocks = b + 1;
+        s.m_end = std::min((mtile0 + n_mtiles) * BM, p.M);
+    };
+    // experiment ("f32_n256"): cnv5 / cnv6 as whole rounds of 128 x 256 tiles (eight waves, one workgroup per CU) + a remainder launch of
+    // 128 x 64 tiles
+    if (o.f32_n256 && (li == 4 || li == 5) && L.npad == 256 && L.groups == 1 && !call.fuse_pose && mtiles >= o.ncu) {
+        const int main_m = (mtiles / o.ncu) * o.ncu;
+        LaunchStep<ConvParams>& sm = d.steps[d.nsteps++];
+        sm.family = FAM_F32_N256; sm.tile = 256; sm.gx = main_m;
+        block(sm, 0, 2, 0, main_m, 1);
+        d.plan_code[0] = main_m * 1000 + 256;
+        if (main_m < mtiles) {
+            LaunchStep<ConvParams>& sr = d.steps[d.nsteps++];
+            sr.family = FAM_F32; sr.tile = 64; sr.row0 = main_m * BM; sr.rem_label = true;
+            block(sr, 0, 0, main_m, mtiles - main_m, L.npad / 64);
+            sr.gx = (mtiles - main_m) * sr.p[0].ntiles_n;
+            d.plan_code[1] = (mtiles - main_m) * 1000 + 64;
+        }
+        return d;
+    }
+    // main + remainder as one grid (conv_igemm.h, conv_igemm_f32_mainrem; "merge_rem_f32"): the remainder's tiles start on the CUs
+    // that finish their last main tile first, instead of behind a launch boundary.  Same tiles, same arithmetic.
+    // (cnv7 keeps its two launches: merged it measured 0.532 against 0.439 + 0.052 ms - its 32-column remainder tiles then run two per CU
+    // on the main tile's LDS and register budget instead of three, and 0.545 with a 64-column remainder; cnv4 / cnv5 / cnv6: -5 / -4 / -1 %,
+    // profiles/r05q_f32_mainrem_ab.md)
+    if (o.merge_rem_f32 && li >= 3 && (li <= 5 || o.merge_rem_f32 > 1) && plan.size() == 2 && plan[0].BN == 128 && (plan[1].BN == 32 || plan[1].BN == 64)) {
+        const int ntn_m = L.npad / 128, ntn_r = L.npad / plan[1].BN;
+        const int n_main = plan[0].mtiles * ntn_m, n_rem = plan[1].mtiles * ntn_r;
+        if (n_main % 8 == 0 && (L.groups == 1 || n_rem % 8 == 0)) {
+            LaunchStep<ConvParams>& s = d.steps[d.nsteps++];
+            s.family = FAM_F32_MAINREM; s.tile = plan[1].BN; s.n_main = n_main; s.n_rem = n_rem;
+            s.gx = (n_main + n_rem) * L.groups;
+            block(s, 0, 0, plan[0].mtile0, plan[0].mtiles, ntn_m);
+            block(s, 1, 0, plan[1].mtile0, plan[1].mtiles, ntn_r);
+            d.plan_code[0] = (plan[0].mtiles + plan[1].mtiles) * 1000 + 128;      // one launch covers the layer
+            return d;
+        }
+    }
+    for (size_t i = 0; i < plan.size() && i < 2; ++i) {
+        LaunchStep<ConvParams>& s = d.steps[d.nsteps++];
+        s.family = FAM_F32; s.tile = plan[i].BN; s.row0 = plan[i].mtile0 * BM; s.rem_label = i > 0;
+        block(s, 0, 0, plan[i].mtile0, plan[i].mtiles, plan[i].BN == 16 ? 1 : L.npad / plan[i].BN);
+        s.gx = plan[i].mtiles * s.p[0].ntiles_n; s.gy = L.groups;
+        d.plan_code[i] = plan[i].mtiles * 1000 + plan[i].BN;
+    }
+    return d;
+}
+
+// The f16x3 rules, in order: the planner's launches; the fused pose head's single tile; cnv4 on conv_igemm_h3w128;
+// "merge_cnv4"; the merged main + remainder grid; split-K; else one launch per planned launch, on conv_igemm_h3w / h3w64 where "wave128"
+// has a kernel for it.
+LayerDecision<ConvParamsH> decide_layer_h3(const LayerGeom& L, const LayerCall& call, const PlanOptions& o) {
+    LayerDecision<ConvParamsH> d;
+    const int li = call.li;
+    const bool fuse_pose = call.fuse_pose;
+    // cnv7 feeds the float32 pose head unscaled
+    ConvParamsH p = fill_params_h3(L, call, o.share_taps, o.shift_in, li == 6 ? 0 : o.shift_out);
+    if (const char* e = tuning_env("DAVO_DBG")) p.dbg = atoi(e);       // tuning build only
+    // cnv5, cnv6, cnv7 (256 channels per group) and cnv4 (128): conv_igemm_h3s.h is instantiated for them
+    const bool allow_208 = (li >= 4 && L.npad_h == 256) || (li == 3 && L.npad_h == 128 && o.tile_208x128);
+    // cnv5 / cnv6 with "wave128": the 256x256 tile is conv_igemm_h3w's, 4.7 % faster than the one the planner's table was fitted on
+    // (measured across 21 batch sizes with the table scaled: only B = 24 and 256x832 B = 6 change plan, -2.7 / -3.2 %: profiles/r05bn_planner_scale.log)
+    const double others_scale = (o.wave128 && (li == 4 || li == 5) && L.npad_h == 256 && L.groups == 1 && !fuse_pose) ? 0.955 : 1.0;
+    std::vector<LaunchH> plan = plan_layer_h3(p.M, L.npad_h, L.groups, L.tile_h, allow_208, o.ncu, others_scale);
+    if (fuse_pose) {      // one launch, one tile shape no taller than an image, so a tile touches <= 2 images
+        const int P = p.Hout * p.Wout;
+        const int best = plan_single_tile_h3(p.M, L.npad_h, L.groups, P, L.tile_h, allow_208, o.ncu);
+        if (best < 0) { d.err = DAVO_ERR_INVALID; d.msg = "no tile fits the fused pose head"; return d; }
+        plan = {{0, p.M, best}};
+        const TileShape ts = tile_shape(best);
+        const int mt = (p.M + ts.bm - 1) / ts.bm, ntn = L.npad_h / ts.bn;
+#ifdef DAVO_POSE_DEBUG
+        d.pose_debug_bytes = (size_t)L.groups * mt * ntn * 512 * 20 * sizeof(float);
+#endif
+        d.pose_floats = (size_t)L.groups * mt * ntn * 6;
+        p.y_mode = 2; p.pose_P = P; p.pose_mt = mt;
+        if (call.pose_tail) {      // the launch's last workgroup adds the tiles and writes the poses (pose_tail.h)
+            p.pose_NB = call.NB; p.pose_bm = ts.bm; p.pose_total = L.groups * mt * ntn;
+        }
+        d.pose_bm = ts.bm; d.pose_mt = mt; d.pose_ntn = ntn;
+    }
+    // cnv4 on conv_igemm_h3w128's 256 x 128 tiles, every row in one launch - where the 256-row tiles fill whole rounds of the CUs or
+    // nearly so: a round of them takes 24.4 us against 29.2 for the same rows on conv_igemm_h3's tiles (B = 128: 0.385 -> 0.318 ms),
+    // which a last round that is three quarters empty gives back (B = 32, 3.25 rounds: 0.0925 -> 0.0938 ms)
+    const long t256 = (p.M + 255) / 256;
+    const bool rounds_ok = t256 >= o.ncu && (double)((t256 + o.ncu - 1) / o.ncu) * o.ncu <= 1.12 * (double)t256;
+    if ((o.wave128 >= 3 || (o.wave128 >= 2 && rounds_ok)) && li == 3 && !fuse_pose && L.groups == 1 && L.npad_h == 128 && L.tile_h < 0 &&
+        p.M >= 256 * o.ncu) {
+        ConvParamsH pw = p;
+        pw.ntiles_n = 1; pw.mtile0 = 0;
+        if (layer_h3w128_supported(pw)) {
+            LaunchStep<ConvParamsH>& s = d.steps[d.nsteps++];
+            s.family = FAM_H3W128; s.tile = TILE_256x128; s.p[0] = pw; s.gx = (unsigned)(pw.M / 256);
+            d.plan_code[0] = ((p.M + 127) / 128) * 1000 + TILE_256x128;
+            return d;
+        }
+    }
+    if (o.merge_cnv4 && o.merge_rem && li == 3 && !fuse_pose && L.npad_h == 128 && L.groups == 1 && o.ncu == 256 && L.tile_h < 0 &&
+        plan.size() == 1 && plan[0].tile == TILE_128x128) {
+        // cnv4 (N = 128): whole rounds of 256x128 tiles (shared-tap staging, twice the matrix work per staged byte of the
+        // 128x128 tile) + the remaining rows on 128x128 tiles, as one grid like cnv5 / cnv6 below
+        const int rows1 = (p.M / 256 / o.ncu) * o.ncu * 256;
+        const int rem = p.M - rows1, n_rem = (rem + 127) / 128;
+        if (rows1 > 0 && rem > 0 && rem % 128 == 0 && n_rem % 64 == 0 && n_rem <= 256)
+            plan = {{0, rows1, TILE_256x128}, {rows1, rem, TILE_128x128}};
+    }
+    const bool merge_256 = plan.size() == 2 && plan[0].tile == TILE_256x256 && plan[1].tile == TILE_128x128 && L.npad_h == 256;
+    // the merged grid's 256x128 main tile is instantiated for cnv4 alone (launch_h3.hip): a cnv6 of 128 columns (-cnv6_64) with the same
+    // plan keeps its two launches
+    const bool merge_128 = li == 3 && plan.size() == 2 && plan[0].tile == TILE_256x128 && plan[1].tile == TILE_128x128 && L.npad_h == 128;
+    if (o.merge_rem && !fuse_pose && (merge_256 || merge_128) && L.groups == 1 && o.ncu == 256 && !tuning_env("DAVO_NO_MERGE")) {
+        // main + remainder as one grid (conv_igemm_h3_mainrem): same tiles, same arithmetic, de-phased store bursts
+        ConvParamsH pm = p, pr = p;
+        const int rem_ntn = L.npad_h / 128;                       // N tiles of a 128x128 remainder row block
+        pm.ntiles_n = 1; pm.mtile0 = 0; pm.M = plan[0].rows;
+        pr.ntiles_n = rem_ntn; pr.mtile0 = plan[1].row0 / 128; pr.M = plan[1].row0 + plan[1].rows;
+        const int n_main = plan[0].rows / 256, n_rem = ((plan[1].rows + 127) / 128) * rem_ntn;
+        // "wave128": the four-wave main tile (conv_igemm_h3w.h) runs as a launch of its own - merged with four-wave remainder tiles it
+        // measured 0.262 / 0.497 ms for cnv5 / cnv6 against 0.258 / 0.487 as two launches (profiles/r05bc_w128_ab.log)
+        const bool own_launch = o.wave128 && merge_256 && layer_h3w_supported(li, pm);
+        if (!own_launch && layer_h3_mainrem_supported(li, pm, n_main, n_rem)) {
+            LaunchStep<ConvParamsH>& s = d.steps[d.nsteps++];
+            s.family = FAM_H3_MAINREM; s.tile = plan[0].tile; s.nblocks = 2; s.p[0] = pm; s.p[1] = pr;
+            s.n_main = n_main; s.n_rem = n_rem; s.gx = n_main + n_rem;
+            // f16x3: long-first measured 256.8 against 259.9 us on cnv5 with a third more HBM reads (205 -> 272 MB: neighbours no longer
+            // run side by side) and no change of the power-capped step: natural order unless "skip_order" is 2
+            if (o.skip_order >= 2) s.ord[0] = {ORDER_LONG_FIRST, 1, 256, 0, n_main, 1};
+            s.order = o.merge_order;
+            d.plan_code[0] = ((plan[0].rows + plan[1].rows + 127) / 128) * 1000 + TILE_MERGED_MARK;     // 256x256 + 128x128 in one grid
+            return d;
+        }
+    }
+    // Split-K.  A launch of at most half a workgroup per CU (cnv6 at batch 1: 104 tiles of 128x128, each a serial chain of 72
+    // chunks at ~0.7 us) leaves half of the chip idle and is as long as its chain: the two halves of the input channels run
+    // as two "groups" of the same kernel (the grouped-convolution path cnv7 uses: own channel offset, weight offset and
+    // output slot; the second half starts from a zero bias) into float32 partial sums, and splitk_fixup adds the two,
+    // applies ReLU and writes the stored form.  Two partial sums instead of one chain change the float32 rounding of the
+    // layer's outputs (not their value: ~1e-7 relative), so batch sizes that split and batch sizes that do not agree to
+    // rounding, not to the bit ("split_k" 0 restores the single chain).  (With S parts: S groups, S partial sums.)
+    if (o.split_k && !fuse_pose && (li == 4 || li == 5) && L.groups == 1 && plan.size() == 1 && p.y_mode == 1 && L.cout % 32 == 0 &&
+        !is_208(plan[0].tile)) {
+        const TileShape ts = tile_shape(plan[0].tile);
+        const int mtiles = (p.M + ts.bm - 1) / ts.bm, ntn = L.npad_h / ts.bn;
+        const long tiles = (long)mtiles * ntn;
+        // parts: whole channel blocks each, whole filter rows (shared-tap staging walks a row's three taps together).  Four parts
+        // where the workgroups then still fit side by side (two per CU on the two-slot ring), else two (one per CU, deep ring)
+        auto fits = [&](int S) { return L.nchunks_h % (S * L.cpb) == 0 && ((L.nchunks_h / S) % 3) == 0; };
+        const int per_cu = ts.lds * 2 <= 160 * 1024 ? 2 : 1;
+        const int S = (fits(4) && tiles * 4 <= (long)per_cu * o.ncu && tiles * 2 <= o.ncu) ? 4 : (fits(2) && tiles * 2 <= o.ncu ? 2 : 1);       // two parts at two per CU (B = 2) measured slower: 54 -> 57 us
+        if (S > 1) {
+            LaunchStep<ConvParamsH>& s = d.steps[d.nsteps++];
+            ConvParamsH& ps = s.p[0];
+            ps = p;
+            ps.nchunks = L.nchunks_h / S;
+            ps.g_x_boff = (L.cin / S) * 4; ps.g_w = (long)ps.nchunks * 128; ps.g_bias = L.npad_h; ps.g_y_coff = L.cout;
+            ps.y_mode = 0; ps.y_ld = S * L.cout; ps.relu = 0;
+            ps.ntiles_n = ntn; ps.mtile0 = 0;
+            s.family = FAM_H3_SPLITK; s.tile = plan[0].tile; s.gx = mtiles * ntn; s.gy = S;
+            ps.deep = o.deep_ring && tiles * S <= o.ncu;
+            d.plan_code[0] = ((p.M + 127) / 128) * 1000 + plan[0].tile; d.split = S;
+            d.splitk_floats = (size_t)p.M * S * L.cout; d.sk_M = p.M; d.sk_cout = L.cout;
+            // The fix-up folded into the launch (pose_tail.h, splitk_tail): with an x extent that is a multiple of 8 the S parts of a
+            // tile run on one XCD, so the part that finishes last finds the others' partial sums in its own L2 and writes the stored
+            // form itself - no splitk_fixup launch (7 us each at batch 1, two per forward).  Checked once per context on the device.
+            d.fold_if_xcd = o.fold_fixup && S <= 4 && s.gx % 8 == 0 && (int)s.gx <= SK_TILE_COUNTERS && o.ncu == o.dev_cus && !o.cu_partition &&
+                            !o.user_stream;
+            d.sk_counter0 = 1 + o.max_batch;
+            return d;
+        }
+    }
+    for (size_t i = 0; i < plan.size() && i < 2; ++i) {
+        const TileShape ts = tile_shape(plan[i].tile);
+        LaunchStep<ConvParamsH>& s = d.steps[d.nsteps++];
+        ConvParamsH& q = s.p[0];
+        q = p;
+        q.ntiles_n = L.npad_h / ts.bn;
+        q.mtile0 = plan[i].row0 / ts.bm;
+        q.M = plan[i].row0 + plan[i].rows;                    // rows past this launch's range are not its job
+        const int mtiles = (plan[i].rows + ts.bm - 1) / ts.bm;
+        s.gx = mtiles * q.ntiles_n; s.gy = L.groups;
+        q.deep = o.deep_ring && plan.size() == 1 && (long)s.gx * s.gy <= o.ncu;       // at most one workgroup per CU
+        d.plan_code[i] = ((plan[i].rows + 127) / 128) * 1000 + plan[i].tile;
+        // no tile order here: cnv4's single launch of 128x128 tiles (two per CU, 6.5 rounds) measured 94.4 us in natural order and
+        // 97.4 long-first (profiles/r04e_skip_padding_rows.md); the merged grids above and the float32 launches take one
+        s.family = is_208(plan[i].tile) ? FAM_H3S : FAM_H3; s.tile = plan[i].tile; s.row0 = plan[i].row0; s.rem_label = i > 0;
+        if (o.wave128 && L.groups == 1 && !fuse_pose) {
+            if (plan[i].tile == TILE_256x256 && layer_h3w_supported(li, q)) s.family = FAM_H3W;
+            else if (o.wave128 >= 2 && i == 1 && plan.size() == 2 && plan[0].tile == TILE_256x256 && plan[1].tile == TILE_128x128 &&
+                     L.npad_h == 256 && plan[1].row0 % 256 == 0 && plan[1].rows % 256 == 0) {
+                // the remainder rows of a layer whose main launch ran on conv_igemm_h3w: 256 x 64 tiles (conv_igemm_h3w64)
+                ConvParamsH pr = q;
+                pr.ntiles_n = 4; pr.mtile0 = plan[1].row0 / 256;
+                if (layer_h3w64_supported(li, pr)) {
+                    q = pr;
+                    s.family = FAM_H3W64; s.gx = (unsigned)(plan[1].rows / 256 * 4); s.gy = 1;
+                }
+            }
+        }
+    }
+    return d;
 }
 
 }  // namespace davo

@@ -207,9 +207,20 @@ void init_layer(ConvLayer& L, const char* label, int KS, int stride, int rate, i
     if (const char* e = tuning_env("DAVO_H3_TILE")) {        // tuning build only: force a tile where it fits
         const int t = atoi(e);
         const char* only = tuning_env("DAVO_H3_TILE_LABEL"); // restrict the force to one layer ("cnv4")
-        if (t >= 0 && t < NUM_TILES && cout >= tile_shape(t).bn && (!only || strcmp(only, L.label) == 0)) L.tile_h = t;
+        if (!only || strcmp(only, L.label) == 0) L.tile_h = forced_tile_h(t, cout);
     }
     L.npad_h = h3_npad(cout);
+}
+
+// the seven layers of the PoseNN (nets/posenn.py:205-238): cnv6 is both heads side by side, cnv7 one group per head
+void init_posenn_layers(ConvLayer (&L)[7], int c6) {
+    init_layer(L[0], "cnv1", 7, 2, 1, 8, 16, 1);
+    init_layer(L[1], "cnv2", 5, 2, 1, 16, 32, 1);
+    init_layer(L[2], "cnv3", 3, 1, 2, 32, 64, 1);
+    init_layer(L[3], "cnv4", 3, 1, 4, 64, 128, 1);
+    init_layer(L[4], "cnv5", 3, 1, 8, 128, 256, 1);
+    init_layer(L[5], "cnv6", 3, 1, 2, 256, 2 * c6, 1);
+    init_layer(L[6], "cnv7", 3, 2, 1, c6, 256, 2);
 }
 
 // the pose head's 1x1 kernels [2][256][3] + [2][3]: every arithmetic mode reads them, so they are built at the first forward whatever

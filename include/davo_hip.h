@@ -652,6 +652,34 @@ int davo_pad_class_tables(int NB, int Hout, int Wout, int Hin, int Win, int pad_
 int davo_pad_class_tile_order(const unsigned short* tile_taps, int mtile0, int mtiles, int ntiles_n, int* order);
 int davo_plan_layer_f32(int mtiles, int npad, int groups, int ncu, int* mtile0, int* launch_mtiles, int* tile_bn);
 
+/* Every launch decision of one conv layer on its own (no GPU needed): what a forward of NB pair images of an H x W frame issues for
+ * layer 0..6 = cnv1..cnv7 through the implicit-GEMM kernels (csrc/plan.h: decide_layer_h3 for precision 1, decide_layer_f32 for 0),
+ * with cnv6_out channels per head.  fuse_pose: the pose head runs in this launch's epilogue (layer 6 where the forward fuses it).
+ * options[i], i < n_options <= DAVO_DECIDE_OPTIONS, in this order; the ones left out keep a new context's values:
+ *    0 wave128          1 skip_order    2 merge_order   3 pad_classes (mask 1 cnv4 | 2 cnv5 | 4 cnv6)   4 merge_rem_f32
+ *    5 share_taps       6 merge_rem     7 merge_cnv4    8 tile_208x128   9 deep_ring   10 split_k   11 fold_fixup
+ *   12 f32_n16         13 f32_n256     14 compute units a launch may use (256)   15 compute units of the device (256)
+ *   16 cu_partition    17 a caller's stream is set     18 max_batch (1)
+ *   19, 20 storage shifts of the layer's input and output (0)   21 force_tile (-1)
+ *   22 the launch's last workgroup writes the poses ("fold_tails" 1; 0)   23 feature attention: cnv6 as one group per head (0)
+ * out[0] = steps (1 or 2), then DAVO_DECIDE_STEP_INTS per step:
+ *   family (0 h3 | 1 h3s | 2 h3w | 3 h3w64 | 4 h3w128 | 5 h3 merged grid | 6 h3 split-K | 7 f32 | 8 f32 n256 | 9 f32 merged grid),
+ *   tile (f16x3: the planner's tile id; float32: the N tile's columns, of the remainder for a merged grid), first output row, one past the
+ *   last output row, mtile0, ntiles_n, grid x, grid y, n_main, n_rem, merge order (-1: 2 where a tile-order table exists, else 0), deep,
+ *   1 = profile entry "<layer>.rem", the merged grid's remainder mtile0 and ntiles_n, tile order wanted (0 none | 1 long tiles first),
+ *   1 = the family's own predicate holds for the step's block, chunks of K the step walks
+ * then DAVO_DECIDE_TAIL_INTS: the two davo_last_plan codes (M tiles * 1000 + tile | columns), davo_last_split, 1 = fold the split-K
+ *   fix-up where the device's dispatch order allows, 1 = float32 class-sorted rows where the shape has tables, the fused pose head's tile
+ *   height, M tiles and N tiles, pose-tile and split-K scratch floats per in-flight slot, the layer's f16x3 chunks of K and chunks per
+ *   channel block.
+ * Returns the number of ints the record holds (written up to out_cap), or a negative davo_status (DAVO_ERR_INVALID also where no tile
+ * fits the fused pose head). */
+#define DAVO_DECIDE_OPTIONS 24
+#define DAVO_DECIDE_STEP_INTS 18
+#define DAVO_DECIDE_TAIL_INTS 12
+int davo_decide_layer(int precision, int layer, int H, int W, int NB, int cnv6_out, int fuse_pose, const int* options, int n_options,
+                      int* out, int out_cap);
+
 #ifdef __cplusplus
 }
 #endif
