@@ -95,7 +95,8 @@ __device__ __forceinline__ void split_pair_relu(float x0, float x1, float scale,
 // once and then walks its share of the output tiles (tile t, t + gridDim.x, ...), re-filling only the
 // 42 KB input patch per tile.  The co-resident workgroups overlap each other's fill / matrix / store phases.
 // LT (FUSED only): the label format the fused fill reads, float32 or bytes (input_decode.h).
-template <bool FUSED, typename LT = float>
+// FT (FUSED only): the flow format it reads, float32 or binary16; a pixel's flow comes from one flow_fetch1 (input_decode.h).
+template <bool FUSED, typename LT = float, typename FT = float>
 __global__ __launch_bounds__(cp1::THREADS, 3) void conv_patch_cnv1_h3(ConvPatchParams p) {
     using namespace cp1;
     extern __shared__ __attribute__((aligned(16))) uint8_t smem_p[];
@@ -171,7 +172,7 @@ __global__ __launch_bounds__(cp1::THREADS, 3) void conv_patch_cnv1_h3(ConvPatchP
                         r[3] *= as; r[4] *= as; r[5] *= as;
                     }
                     if (v.cin_per_frame == 5) {
-                        const float2 f = *reinterpret_cast<const float2*>(p.flow + (((size_t)b * 4 + s) * HW + pix) * 2);
+                        const float2 f = flow_fetch1(static_cast<const FT*>(p.flow) + (((size_t)b * 4 + s) * HW + pix) * 2);
                         r[6] = v.mask_info ? f.x * as : f.x;
                         r[7] = v.mask_info ? f.y * as : f.y;
                     }

@@ -30,6 +30,9 @@ int davo::check_batch(davo_ctx* c, Batch* b, int B, bool out_given, int hold) {
     }
     if (B < 1 || B > c->max_batch) return fail(c, DAVO_ERR_INVALID, "batch %d outside [1,%d]", B, c->max_batch);
     if (hold < 0) return fail(c, DAVO_ERR_INVALID, "hold must be >= 0");
+    // a binary16 flow is read in 16-byte units of four pixels (input_decode.h: flow_fetch4): on the device its base is 16-byte aligned
+    if (c->flow_fmt == FLOW_F16 && b->on_device && b->layout == Layout::Windows && ((uintptr_t)b->win.flow & 15))
+        return fail(c, DAVO_ERR_INVALID, "%s: a binary16 device flow buffer (davo_set_flow_format) must be 16-byte aligned", b->fn);
     if (b->layout == Layout::Frames && b->on_device && (((uintptr_t)b->fr.frames | (uintptr_t)b->fr.flow2 | (uintptr_t)b->fr.seg | (uintptr_t)b->fr.depth) & 15))
         return fail(c, DAVO_ERR_INVALID, "%s: device input buffers must be 16-byte aligned", b->fn);
     return DAVO_OK;
@@ -158,7 +161,7 @@ int gather_windows(davo_ctx* c, const InputSet& set, const FrameInputs& fr, int 
                        dst(set.img, n.img), dst(set.seg, n.seg), dst(set.depth, n.depth), dst(set.flow, n.flow),
                        c->H, c->W, sel, p.seg_tgt, p.depth_tgt};
     ProfScope ps(c, s, "window_gather");
-    HIP_TRY(c, launch_window_gather(a, nb, c->label_fmt, s));
+    HIP_TRY(c, launch_window_gather(a, nb, c->label_fmt, c->flow_fmt, s));
     return DAVO_OK;
 }
 
@@ -319,17 +322,21 @@ int davo_forward_device_frames(davo_ctx* c, int N, const void* d_frames, const v
     return forward_device_entry(c, N, frame_batch("davo_forward_device_frames", true, d_frames, d_flow2, d_seg, d_depth), d_pose, elapsed_ms);
 }
 
-int davo_frames_plan(int H, int W, int N, int pairs, int att_source, int label_fmt, int* ranges, long long* link_bytes) {
+int davo_frames_plan_fmt(int H, int W, int N, int pairs, int att_source, int label_fmt, int flow_fmt, int* ranges, long long* link_bytes) {
     if (H < 1 || W < 1 || N < 1 || (pairs != PAIRS_SRC0 && pairs != PAIRS_SRC1 && pairs != PAIRS_BOTH) || att_source < 0 || att_source > ATT_DEPTH_SPLIT ||
-        (label_fmt != LABELS_F32 && label_fmt != LABELS_U8))
+        (label_fmt != LABELS_F32 && label_fmt != LABELS_U8) || (flow_fmt != FLOW_F32 && flow_fmt != FLOW_F16))
         return DAVO_ERR_INVALID;
     const FramePlan p = frame_plan(N, pairs, att_source);
     if (ranges) {
         const int r[8] = {p.img[0], p.img[1], p.seg[0], p.seg[1], p.depth[0], p.depth[1], p.flow[0], p.flow[1]};
         memcpy(ranges, r, sizeof r);
     }
-    if (link_bytes) *link_bytes = frame_plan_bytes(p, N, H, W, label_fmt == LABELS_U8 ? 1 : 4);
+    if (link_bytes) *link_bytes = frame_plan_bytes(p, N, H, W, label_fmt == LABELS_U8 ? 1 : 4, flow_fmt == FLOW_F16 ? 2 : 4);
     return DAVO_OK;
+}
+
+int davo_frames_plan(int H, int W, int N, int pairs, int att_source, int label_fmt, int* ranges, long long* link_bytes) {
+    return davo_frames_plan_fmt(H, W, N, pairs, att_source, label_fmt, FLOW_F32, ranges, link_bytes);
 }
 
 

@@ -342,14 +342,14 @@ int run_patch_layer(davo_ctx* c, const Run& run, int li, bool f32, const void* x
         p.range = run.range ? run.range + li : nullptr;
         if (const char* e = tuning_env("DAVO_PDBG")) p.dbg = atoi(e);      // tuning build only
         if (li == 0) {
-            p.img = static_cast<const uint8_t*>(in.img); p.flow = static_cast<const float*>(in.flow);
+            p.img = static_cast<const uint8_t*>(in.img); p.flow = in.flow;
             p.seg = in.seg; p.tab = c->slots[run.slot].d_tab.get(); p.v = c->v; p.sel = run.pairs;
         }
     }
     c->last_plan[li][0] = ((NB * p.Ho * p.Wo + 127) / 128) * 1000 + t.plan_id; c->last_plan[li][1] = 0; c->last_split[li] = 1;
     const int nblk = p.ntiles < t.per_cu * c->ncu ? p.ntiles : t.per_cu * c->ncu;
     ProfScope ps(c, run.stream, L.label);
-    HIP_TRY(c, launch_patch_layer(li, f32, fused, p, nblk, run.stream, c->label_fmt));
+    HIP_TRY(c, launch_patch_layer(li, f32, fused, p, nblk, run.stream, c->label_fmt, c->flow_fmt));
     return DAVO_OK;
 }
 
@@ -442,7 +442,8 @@ int forward_device(davo_ctx* c, const Run& run, int B, const Inputs& in, void* d
     for (int i = 0; i < 7; ++i) a[i] = ws.d_act[i].get();
     hipStream_t s = run.stream;
     const uint8_t* const d_img = static_cast<const uint8_t*>(in.img);
-    const float* const d_flow = static_cast<const float*>(in.flow);
+    const void* const d_flow = in.flow;                        // float32 or binary16: c->flow_fmt
+    const int ffmt = c->flow_fmt;
     const void* const d_seg = in.seg;                          // float32 or bytes: c->label_fmt
     auto wdev = [&](const char* n) -> const float* {
         auto it = c->weights.find(n);
@@ -477,22 +478,22 @@ int forward_device(davo_ctx* c, const Run& run, int B, const Inputs& in, void* d
         // segmentation / rgb / seg+flow sources: per-frame histogram, byte or flow sums, then (or, folded, in the same launch) the
         // excitation
         ProfScope ps(c, run.stream, "se_class_squeeze");
-        HIP_TRY(c, launch_se_class_squeeze(fold_excite, d_img, d_flow, d_seg, c->label_fmt, B, H, W, v, reinterpret_cast<unsigned*>(d_partial),
+        HIP_TRY(c, launch_se_class_squeeze(fold_excite, d_img, d_flow, ffmt, d_seg, c->label_fmt, B, H, W, v, reinterpret_cast<unsigned*>(d_partial),
                                            d_counters + 1, se_w1, se_b1, se_w2, se_b2, d_tab, range_reset, sel, s));
     } else if (fold_excite && depth_split) {
         // the flagship's squeeze; the triplet's last workgroup evaluates the near tables and the far tables from the same sums
         ProfScope ps(c, run.stream, "se_squeeze_partial");
         const float* near_w[4] = {se_w1, se_b1, se_w2, se_b2};
-        HIP_TRY(c, launch_se_squeeze_excite_split(d_flow, B, HW, v, d_partial, d_counters + 1, near_w, far_w, d_tab, d_tab_far, range_reset, sel, s));
+        HIP_TRY(c, launch_se_squeeze_excite_split(d_flow, ffmt, B, HW, v, d_partial, d_counters + 1, near_w, far_w, d_tab, d_tab_far, range_reset, sel, s));
     } else if (fold_excite) {
         // squeeze + excitation in one launch: the workgroup that delivers a triplet's last partial sum evaluates its tables
         ProfScope ps(c, run.stream, "se_squeeze_partial");
-        HIP_TRY(c, launch_se_squeeze_excite(d_flow, B, HW, v, d_partial, d_counters + 1,
+        HIP_TRY(c, launch_se_squeeze_excite(d_flow, ffmt, B, HW, v, d_partial, d_counters + 1,
                                             se_w1, se_b1, se_w2, se_b2,
                                             wdev("pose_exp_net/pose_exp_net/seg_channel_weight/weight"), d_tab, range_reset, sel, s));
     } else if (att_flow_squeeze(v.att_source)) {
         ProfScope ps(c, run.stream, "se_squeeze_partial");
-        HIP_TRY(c, launch_se_squeeze(d_flow, B, HW, v, d_partial, sel, s));
+        HIP_TRY(c, launch_se_squeeze(d_flow, ffmt, B, HW, v, d_partial, sel, s));
     }
     if (!fold_excite) {
         ProfScope ps(c, run.stream, "se_excite");
@@ -519,7 +520,7 @@ int forward_device(davo_ctx* c, const Run& run, int B, const Inputs& in, void* d
     c->packed_ld = run.impl == 0 ? 8 : 10;
     if (!fused) {
         ProfScope ps(c, run.stream, "mask_pack");
-        HIP_TRY(c, launch_mask_pack(h3 ? 16 : (run.impl == 0 ? 8 : 10), d_img, d_flow, d_seg, c->label_fmt, d_tab, v, B, H, W, d_packed, sel, s,
+        HIP_TRY(c, launch_mask_pack(h3 ? 16 : (run.impl == 0 ? 8 : 10), d_img, d_flow, ffmt, d_seg, c->label_fmt, d_tab, v, B, H, W, d_packed, sel, s,
                                     static_cast<const float*>(in.depth), d_tab_far, c->depth_thr));
     }
     const int c6 = v.cnv6_out;

@@ -37,6 +37,51 @@ __device__ __forceinline__ LabelIds4 label_fetch4(const uint8_t* __restrict__ pl
     return LabelIds4{{label_id((uint8_t)q), label_id((uint8_t)(q >> 8)), label_id((uint8_t)(q >> 16)), label_id((uint8_t)(q >> 24))}};
 }
 
+// The optical flow comes in one of the two formats of davo_set_flow_format (include/davo_hip.h): float32, or IEEE binary16 in the
+// same layout ([B][4][H][W][2], (fx, fy) per pixel).  FT is the element, float or flow_f16.  A reader takes its pixels through one
+// of the fetches below and computes in float32 from there on, so both formats run the same expressions in the same order: a
+// binary16 flow h gives the bits of the float32 flow (float)h.  The widening is v_cvt_f32_f16 per value (two per instruction
+// where the compiler pairs them): exact for every binary16 value - subnormals too (the code objects run with f16/f64 denormals
+// on, the amdgcn default; a half subnormal is a normal float32, so the float32 flush mode does not enter), signed zeros and
+// infinities; a NaN stays a NaN (a signalling one comes out quiet, as from any float conversion).
+// Each fetch takes the address of its unit's first element; the callers form it in element arithmetic, the same expression
+// for both formats (a pixel is two elements, a 4-pixel unit eight).
+//   flow_fetch4   a 4-pixel unit (mask_pack, se_class_squeeze): pixels pix .. pix + 3 of one flow plane, pix a multiple of 4.
+//                 float32: two 16-byte loads; binary16: ONE 16-byte load and eight widenings.  Aligned wherever the flow's base is
+//                 16-byte aligned: a plane holds 2 H W elements, H W a multiple of 16.
+//   flow_fetch2   a 2-pixel unit, the step of the SE squeeze's fixed chunking (se_squeeze_partial / se_squeeze_excite: unit i of
+//                 the plane, thread and chunk boundaries fall on units): one 16-byte load, or one 8-byte load and four widenings.
+//                 The squeeze keeps its units, so its summation order is the float32 format's.
+//   flow_fetch1   one pixel (the fused cnv1 patch fill): one 8-byte load, or one 4-byte load and two widenings.
+typedef _Float16 flow_f16;
+struct Flow4 { float v[8]; };                                  // x0 y0 x1 y1 x2 y2 x3 y3
+__device__ __forceinline__ Flow4 flow_fetch4(const float* __restrict__ unit) {
+    const float4* p = reinterpret_cast<const float4*>(unit);
+    const float4 a = p[0], b = p[1];
+    return Flow4{{a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w}};
+}
+__device__ __forceinline__ Flow4 flow_fetch4(const flow_f16* __restrict__ unit) {
+    typedef _Float16 flow_h8 __attribute__((ext_vector_type(8)));
+    const flow_h8 h = *reinterpret_cast<const flow_h8*>(unit);
+    return Flow4{{(float)h[0], (float)h[1], (float)h[2], (float)h[3], (float)h[4], (float)h[5], (float)h[6], (float)h[7]}};
+}
+__device__ __forceinline__ float4 flow_fetch2(const float* __restrict__ unit) {
+    return *reinterpret_cast<const float4*>(unit);
+}
+__device__ __forceinline__ float4 flow_fetch2(const flow_f16* __restrict__ unit) {
+    typedef _Float16 flow_h4 __attribute__((ext_vector_type(4)));
+    const flow_h4 h = *reinterpret_cast<const flow_h4*>(unit);
+    return make_float4((float)h[0], (float)h[1], (float)h[2], (float)h[3]);
+}
+__device__ __forceinline__ float2 flow_fetch1(const float* __restrict__ px) {
+    return *reinterpret_cast<const float2*>(px);
+}
+__device__ __forceinline__ float2 flow_fetch1(const flow_f16* __restrict__ px) {
+    typedef _Float16 flow_h2 __attribute__((ext_vector_type(2)));
+    const flow_h2 h = *reinterpret_cast<const flow_h2*>(px);
+    return make_float2((float)h[0], (float)h[1]);
+}
+
 // Depth-split attention (att_source 13, davo.py:1143-1155): near = depth < thr in float32, strict; tf.where sends a NaN depth (the
 // comparison is false) to the far side.  The pixel's class is looked up in the chosen table by att_lookup's rule.
 __device__ __forceinline__ float att_lookup_split(const float* near19, const float* far19, float thr, float depth, int id) {

@@ -44,25 +44,26 @@ hipError_t launch_layer_h3w64(int layer, const ConvParamsH& p, hipStream_t s);  
 hipError_t launch_h3_generic(int KS, int stride, int tile, const ConvParamsH& p, dim3 grid, hipStream_t s);
 
 // ---- launch_misc.hip: prologue, pose head, cnv1 patch kernel, direct convolution ---------------------
-hipError_t launch_se_squeeze(const float* d_flow, int B, int HW, const Variant& v, float* d_partial, int sel, hipStream_t s);
+// d_flow / flow_fmt (here and below): the flow in the format FLOW_F32 or FLOW_F16 (params.h); any other value is an error
+hipError_t launch_se_squeeze(const void* d_flow, int flow_fmt, int B, int HW, const Variant& v, float* d_partial, int sel, hipStream_t s);
 hipError_t launch_se_excite(const float* d_partial, int B, int HW, const Variant& v, const float* w1, const float* b1,
                             const float* w2, const float* b2, const float* wstatic, float* d_tab, unsigned* d_range_reset, int sel, hipStream_t s);
 // squeeze + excitation in one launch: the last workgroup of each triplet evaluates its tables (prologue.h, pose_tail.h);
 // -> 1 if the parts (x, 0..3) of a 64 x 4 grid ran on one XCD each for every x (what the folded split-K fix-up relies on), 0 if not
 hipError_t xcd_round_robin_probe(hipStream_t s, int* ok);
 // d_counters: one zeroed unsigned per triplet, left at zero
-hipError_t launch_se_squeeze_excite(const float* d_flow, int B, int HW, const Variant& v, float* d_partial, unsigned* d_counters,
+hipError_t launch_se_squeeze_excite(const void* d_flow, int flow_fmt, int B, int HW, const Variant& v, float* d_partial, unsigned* d_counters,
                                     const float* w1, const float* b1, const float* w2, const float* b2, const float* wstatic,
                                     float* d_tab, unsigned* d_range_reset, int sel, hipStream_t s);
 // att_source 13: the same launch with both excitations in the last workgroup - near_w / far_w = {bottleneck kernel, bias, recover kernel,
 // bias} of se_flow_near / se_flow_far, d_tab the near tables, d_tab_far the far ones
-hipError_t launch_se_squeeze_excite_split(const float* d_flow, int B, int HW, const Variant& v, float* d_partial, unsigned* d_counters,
+hipError_t launch_se_squeeze_excite_split(const void* d_flow, int flow_fmt, int B, int HW, const Variant& v, float* d_partial, unsigned* d_counters,
                                           const float* const near_w[4], const float* const far_w[4], float* d_tab, float* d_tab_far,
                                           unsigned* d_range_reset, int sel, hipStream_t s);
 // segmentation / rgb / seg+flow class-table sources (att_source 4..10): per-frame descriptor records into d_partial (max_batch x 3 x SQ_CHUNKS x SQ_REC words);
 // fold: the triplet's last workgroup evaluates its tables too (d_counters as above), otherwise launch_se_excite follows.
 // d_seg / label_fmt (here and below): the label maps in the format LABELS_F32 or LABELS_U8 (params.h); any other value is an error
-hipError_t launch_se_class_squeeze(bool fold, const uint8_t* d_img, const float* d_flow, const void* d_seg, int label_fmt, int B, int H, int W,
+hipError_t launch_se_class_squeeze(bool fold, const uint8_t* d_img, const void* d_flow, int flow_fmt, const void* d_seg, int label_fmt, int B, int H, int W,
                                   const Variant& v, unsigned* d_partial, unsigned* d_counters, const float* w1, const float* b1,
                                   const float* w2, const float* b2, float* d_tab, unsigned* d_range_reset, int sel, hipStream_t s);
 // depth sources (att_source 11, 12): one float32 sum per (triplet, frame, chunk) into word 0 of the same records; d_depth is
@@ -73,16 +74,17 @@ hipError_t launch_se_depth_squeeze(bool fold, const float* d_depth, int B, int H
 // ld: 16 = split-fp16 8-channel layout (f16x3), 8 = float32 8-channel, 10 = the reference's 10-channel layout
 // att_source 13 (the depth-split flow attention) runs the depth-split form: d_depth (16-byte aligned), the far tables and the threshold are
 // required there and ignored everywhere else
-hipError_t launch_mask_pack(int ld, const uint8_t* d_img, const float* d_flow, const void* d_seg, int label_fmt, const float* d_tab,
+hipError_t launch_mask_pack(int ld, const uint8_t* d_img, const void* d_flow, int flow_fmt, const void* d_seg, int label_fmt, const float* d_tab,
                             const Variant& v, int B, int H, int W, float* d_packed, int sel, hipStream_t s,
                             const float* d_depth = nullptr, const float* d_tab_far = nullptr, float depth_thr = 0.f);
 // window_gather.h: N windows of a frame-layout batch into the window-major planes every kernel above reads; every pointer 16-byte
 // aligned; a.f_flow null = the flow planes are in place already (the host entry points copy them there)
 struct GatherArgs;
-hipError_t launch_window_gather(const GatherArgs& a, int N, int label_fmt, hipStream_t s);
+hipError_t launch_window_gather(const GatherArgs& a, int N, int label_fmt, int flow_fmt, hipStream_t s);
 // cnv1 / cnv2 / cnv3 (layer 0..2) from an LDS-staged input patch: conv_patch_cnvN_h3, or conv_patch_cnvN_f32 in float32 mode (f32);
-// fused: conv_patch_cnv1_h3<true, float | uint8_t> by label_fmt (f16x3 cnv1 only; p.seg is in that format)
-hipError_t launch_patch_layer(int layer, bool f32, bool fused, const ConvPatchParams& p, int nblk, hipStream_t s, int label_fmt = LABELS_F32);
+// fused: conv_patch_cnv1_h3<true, float | uint8_t, float | flow_f16> by label_fmt and flow_fmt (f16x3 cnv1 only; p.seg and p.flow are in those formats)
+hipError_t launch_patch_layer(int layer, bool f32, bool fused, const ConvPatchParams& p, int nblk, hipStream_t s, int label_fmt = LABELS_F32,
+                              int flow_fmt = FLOW_F32);
 // split-K fix-up: d_part [M][S][N] float32 partial sums -> the layer's stored activation (ReLU, fp16 hi/lo pairs, range monitor)
 hipError_t launch_splitk_fixup(const float* d_part, long M, int N, int S, int relu, uint8_t* d_y, unsigned* d_range, hipStream_t s);
 hipError_t launch_pose_from_tiles(const float* d_tiles, int NB, int P, int bm, int mtiles, int ntiles_n,

@@ -29,8 +29,19 @@ hipError_t ensure_dynamic_lds(const void* kernel, int bytes) {
     return e;
 }
 
-hipError_t launch_se_squeeze(const float* d_flow, int B, int HW, const Variant& v, float* d_partial, int sel, hipStream_t s) {
-    hipLaunchKernelGGL(se_squeeze_partial, dim3(SQ_CHUNKS, pairs_per_window(sel), B), dim3(256), 0, s, d_flow, HW, v.norm_flow, v.abs_mode, sel, d_partial);
+namespace {
+using flow_f32 = float;
+inline bool flow_fmt_ok(int flow_fmt) { return flow_fmt == FLOW_F32 || flow_fmt == FLOW_F16; }
+}  // namespace
+
+// d_flow / flow_fmt (here and below): the flow in the format FLOW_F32 or FLOW_F16 (params.h); any other value is an error
+hipError_t launch_se_squeeze(const void* d_flow, int flow_fmt, int B, int HW, const Variant& v, float* d_partial, int sel, hipStream_t s) {
+    if (!flow_fmt_ok(flow_fmt)) return hipErrorInvalidValue;
+    const dim3 grid(SQ_CHUNKS, pairs_per_window(sel), B);
+    if (flow_fmt == FLOW_F16)
+        hipLaunchKernelGGL(se_squeeze_partial<flow_f16>, grid, dim3(256), 0, s, static_cast<const flow_f16*>(d_flow), HW, v.norm_flow, v.abs_mode, sel, d_partial);
+    else
+        hipLaunchKernelGGL(se_squeeze_partial<flow_f32>, grid, dim3(256), 0, s, static_cast<const float*>(d_flow), HW, v.norm_flow, v.abs_mode, sel, d_partial);
     return hipGetLastError();
 }
 
@@ -40,47 +51,65 @@ hipError_t launch_se_excite(const float* d_partial, int B, int HW, const Variant
     return hipGetLastError();
 }
 
-hipError_t launch_se_squeeze_excite(const float* d_flow, int B, int HW, const Variant& v, float* d_partial, unsigned* d_counters,
+hipError_t launch_se_squeeze_excite(const void* d_flow, int flow_fmt, int B, int HW, const Variant& v, float* d_partial, unsigned* d_counters,
                                     const float* w1, const float* b1, const float* w2, const float* b2, const float* wstatic,
                                     float* d_tab, unsigned* d_range_reset, int sel, hipStream_t s) {
-    hipLaunchKernelGGL(se_squeeze_excite, dim3(SQ_CHUNKS, pairs_per_window(sel), B), dim3(256), 0, s, d_flow, HW, v, d_partial, d_counters, w1, b1, w2, b2,
-                       wstatic, d_tab, d_range_reset, sel);
+    if (!flow_fmt_ok(flow_fmt)) return hipErrorInvalidValue;
+    const dim3 grid(SQ_CHUNKS, pairs_per_window(sel), B);
+    if (flow_fmt == FLOW_F16)
+        hipLaunchKernelGGL(se_squeeze_excite<flow_f16>, grid, dim3(256), 0, s, static_cast<const flow_f16*>(d_flow), HW, v, d_partial, d_counters, w1, b1, w2, b2,
+                           wstatic, d_tab, d_range_reset, sel);
+    else
+        hipLaunchKernelGGL(se_squeeze_excite<flow_f32>, grid, dim3(256), 0, s, static_cast<const float*>(d_flow), HW, v, d_partial, d_counters, w1, b1, w2, b2,
+                           wstatic, d_tab, d_range_reset, sel);
     return hipGetLastError();
 }
 
-hipError_t launch_se_squeeze_excite_split(const float* d_flow, int B, int HW, const Variant& v, float* d_partial, unsigned* d_counters,
+hipError_t launch_se_squeeze_excite_split(const void* d_flow, int flow_fmt, int B, int HW, const Variant& v, float* d_partial, unsigned* d_counters,
                                           const float* const near_w[4], const float* const far_w[4], float* d_tab, float* d_tab_far,
                                           unsigned* d_range_reset, int sel, hipStream_t s) {
-    if (v.att_source != ATT_DEPTH_SPLIT || !d_tab_far) return hipErrorInvalidValue;
+    if (v.att_source != ATT_DEPTH_SPLIT || !d_tab_far || !flow_fmt_ok(flow_fmt)) return hipErrorInvalidValue;
     for (int k = 0; k < 4; ++k) if (!near_w[k] || !far_w[k]) return hipErrorInvalidValue;
     const SeFar far{far_w[0], far_w[1], far_w[2], far_w[3], d_tab_far};
-    hipLaunchKernelGGL(se_squeeze_excite_split, dim3(SQ_CHUNKS, pairs_per_window(sel), B), dim3(256), 0, s, d_flow, HW, v, d_partial, d_counters,
-                       near_w[0], near_w[1], near_w[2], near_w[3], d_tab, d_range_reset, sel, far);
+    const dim3 grid(SQ_CHUNKS, pairs_per_window(sel), B);
+    if (flow_fmt == FLOW_F16)
+        hipLaunchKernelGGL(se_squeeze_excite_split<flow_f16>, grid, dim3(256), 0, s, static_cast<const flow_f16*>(d_flow), HW, v, d_partial, d_counters,
+                           near_w[0], near_w[1], near_w[2], near_w[3], d_tab, d_range_reset, sel, far);
+    else
+        hipLaunchKernelGGL(se_squeeze_excite_split<flow_f32>, grid, dim3(256), 0, s, static_cast<const float*>(d_flow), HW, v, d_partial, d_counters,
+                           near_w[0], near_w[1], near_w[2], near_w[3], d_tab, d_range_reset, sel, far);
     return hipGetLastError();
 }
 
 namespace {
-template <typename LT>
-void se_class_squeeze_as(bool fold, const dim3& grid, hipStream_t s, const uint8_t* d_img, const float* d_flow, const void* d_seg, int H, int W,
+template <typename LT, typename FT>
+void se_class_squeeze_as(bool fold, const dim3& grid, hipStream_t s, const uint8_t* d_img, const void* d_flow_raw, const void* d_seg, int H, int W,
                          const Variant& v, unsigned* d_partial, unsigned* d_counters, const float* w1, const float* b1,
                          const float* w2, const float* b2, float* d_tab, unsigned* d_range_reset, int sel) {
     const LT* seg = static_cast<const LT*>(d_seg);
+    const FT* d_flow = static_cast<const FT*>(d_flow_raw);
     if (fold)
-        hipLaunchKernelGGL((se_class_squeeze<true, LT>), grid, dim3(256), 0, s, d_img, d_flow, seg, H, W, v, d_partial, d_counters,
+        hipLaunchKernelGGL((se_class_squeeze<true, LT, FT>), grid, dim3(256), 0, s, d_img, d_flow, seg, H, W, v, d_partial, d_counters,
                            w1, b1, w2, b2, d_tab, d_range_reset, sel);
     else
-        hipLaunchKernelGGL((se_class_squeeze<false, LT>), grid, dim3(256), 0, s, d_img, d_flow, seg, H, W, v, d_partial, d_counters,
+        hipLaunchKernelGGL((se_class_squeeze<false, LT, FT>), grid, dim3(256), 0, s, d_img, d_flow, seg, H, W, v, d_partial, d_counters,
                            w1, b1, w2, b2, d_tab, d_range_reset, sel);
 }
 }  // namespace
 
-hipError_t launch_se_class_squeeze(bool fold, const uint8_t* d_img, const float* d_flow, const void* d_seg, int label_fmt, int B, int H, int W,
+hipError_t launch_se_class_squeeze(bool fold, const uint8_t* d_img, const void* d_flow, int flow_fmt, const void* d_seg, int label_fmt, int B, int H, int W,
                                   const Variant& v, unsigned* d_partial, unsigned* d_counters, const float* w1, const float* b1,
                                   const float* w2, const float* b2, float* d_tab, unsigned* d_range_reset, int sel, hipStream_t s) {
     const dim3 grid(SQ_CHUNKS, att_se_frames(v.att_source) - (sel == PAIRS_BOTH ? 0 : 1), B);
-    if (label_fmt == LABELS_F32) se_class_squeeze_as<float>(fold, grid, s, d_img, d_flow, d_seg, H, W, v, d_partial, d_counters, w1, b1, w2, b2, d_tab, d_range_reset, sel);
-    else if (label_fmt == LABELS_U8) se_class_squeeze_as<uint8_t>(fold, grid, s, d_img, d_flow, d_seg, H, W, v, d_partial, d_counters, w1, b1, w2, b2, d_tab, d_range_reset, sel);
-    else return hipErrorInvalidValue;
+    if (!flow_fmt_ok(flow_fmt) || (label_fmt != LABELS_F32 && label_fmt != LABELS_U8)) return hipErrorInvalidValue;
+    const bool u8 = label_fmt == LABELS_U8;
+    if (flow_fmt == FLOW_F16) {
+        if (u8) se_class_squeeze_as<uint8_t, flow_f16>(fold, grid, s, d_img, d_flow, d_seg, H, W, v, d_partial, d_counters, w1, b1, w2, b2, d_tab, d_range_reset, sel);
+        else se_class_squeeze_as<float, flow_f16>(fold, grid, s, d_img, d_flow, d_seg, H, W, v, d_partial, d_counters, w1, b1, w2, b2, d_tab, d_range_reset, sel);
+    } else {
+        if (u8) se_class_squeeze_as<uint8_t, flow_f32>(fold, grid, s, d_img, d_flow, d_seg, H, W, v, d_partial, d_counters, w1, b1, w2, b2, d_tab, d_range_reset, sel);
+        else se_class_squeeze_as<float, flow_f32>(fold, grid, s, d_img, d_flow, d_seg, H, W, v, d_partial, d_counters, w1, b1, w2, b2, d_tab, d_range_reset, sel);
+    }
     return hipGetLastError();
 }
 
@@ -99,26 +128,27 @@ hipError_t launch_se_depth_squeeze(bool fold, const float* d_depth, int B, int H
 }
 
 namespace {
-template <typename LT>
-hipError_t mask_pack_as(int ld, const dim3& grid, hipStream_t s, const uint8_t* d_img, const float* d_flow, const void* d_seg, const float* d_tab,
+template <typename LT, typename FT>
+hipError_t mask_pack_as(int ld, const dim3& grid, hipStream_t s, const uint8_t* d_img, const void* d_flow_raw, const void* d_seg, const float* d_tab,
                         const Variant& v, int B, int sel, int H, int W, float* d_packed, const DepthSplit* ds) {
     const LT* seg = static_cast<const LT*>(d_seg);
+    const FT* d_flow = static_cast<const FT*>(d_flow_raw);
     if (ds) {
-        if (ld == 16) hipLaunchKernelGGL((mask_pack_depthsplit<16, LT>), grid, dim3(256), 0, s, d_img, d_flow, seg, d_tab, v, B, sel, H, W, d_packed, *ds);
-        else if (ld == 8) hipLaunchKernelGGL((mask_pack_depthsplit<8, LT>), grid, dim3(256), 0, s, d_img, d_flow, seg, d_tab, v, B, sel, H, W, d_packed, *ds);
-        else if (ld == 10) hipLaunchKernelGGL((mask_pack_depthsplit<10, LT>), grid, dim3(256), 0, s, d_img, d_flow, seg, d_tab, v, B, sel, H, W, d_packed, *ds);
+        if (ld == 16) hipLaunchKernelGGL((mask_pack_depthsplit<16, LT, FT>), grid, dim3(256), 0, s, d_img, d_flow, seg, d_tab, v, B, sel, H, W, d_packed, *ds);
+        else if (ld == 8) hipLaunchKernelGGL((mask_pack_depthsplit<8, LT, FT>), grid, dim3(256), 0, s, d_img, d_flow, seg, d_tab, v, B, sel, H, W, d_packed, *ds);
+        else if (ld == 10) hipLaunchKernelGGL((mask_pack_depthsplit<10, LT, FT>), grid, dim3(256), 0, s, d_img, d_flow, seg, d_tab, v, B, sel, H, W, d_packed, *ds);
         else return hipErrorInvalidValue;
         return hipGetLastError();
     }
-    if (ld == 16) hipLaunchKernelGGL((mask_pack<16, LT>), grid, dim3(256), 0, s, d_img, d_flow, seg, d_tab, v, B, sel, H, W, d_packed);
-    else if (ld == 8) hipLaunchKernelGGL((mask_pack<8, LT>), grid, dim3(256), 0, s, d_img, d_flow, seg, d_tab, v, B, sel, H, W, d_packed);
-    else if (ld == 10) hipLaunchKernelGGL((mask_pack<10, LT>), grid, dim3(256), 0, s, d_img, d_flow, seg, d_tab, v, B, sel, H, W, d_packed);
+    if (ld == 16) hipLaunchKernelGGL((mask_pack<16, LT, FT>), grid, dim3(256), 0, s, d_img, d_flow, seg, d_tab, v, B, sel, H, W, d_packed);
+    else if (ld == 8) hipLaunchKernelGGL((mask_pack<8, LT, FT>), grid, dim3(256), 0, s, d_img, d_flow, seg, d_tab, v, B, sel, H, W, d_packed);
+    else if (ld == 10) hipLaunchKernelGGL((mask_pack<10, LT, FT>), grid, dim3(256), 0, s, d_img, d_flow, seg, d_tab, v, B, sel, H, W, d_packed);
     else return hipErrorInvalidValue;
     return hipGetLastError();
 }
 }  // namespace
 
-hipError_t launch_mask_pack(int ld, const uint8_t* d_img, const float* d_flow, const void* d_seg, int label_fmt, const float* d_tab,
+hipError_t launch_mask_pack(int ld, const uint8_t* d_img, const void* d_flow, int flow_fmt, const void* d_seg, int label_fmt, const float* d_tab,
                             const Variant& v, int B, int H, int W, float* d_packed, int sel, hipStream_t s,
                             const float* d_depth, const float* d_tab_far, float depth_thr) {
     const long nthreads = (long)pairs_per_window(sel) * B * H * (W / 4);
@@ -127,12 +157,17 @@ hipError_t launch_mask_pack(int ld, const uint8_t* d_img, const float* d_flow, c
     // the depth-split form: a missing plane or table is an error, never the plain packer
     if (split && (!d_depth || ((uintptr_t)d_depth & 15) || !d_tab_far)) return hipErrorInvalidValue;
     const DepthSplit ds{d_depth, d_tab_far, depth_thr};
-    if (label_fmt == LABELS_F32) return mask_pack_as<float>(ld, grid, s, d_img, d_flow, d_seg, d_tab, v, B, sel, H, W, d_packed, split ? &ds : nullptr);
-    if (label_fmt == LABELS_U8) return mask_pack_as<uint8_t>(ld, grid, s, d_img, d_flow, d_seg, d_tab, v, B, sel, H, W, d_packed, split ? &ds : nullptr);
-    return hipErrorInvalidValue;
+    const DepthSplit* const dsp = split ? &ds : nullptr;
+    if (!flow_fmt_ok(flow_fmt) || (label_fmt != LABELS_F32 && label_fmt != LABELS_U8)) return hipErrorInvalidValue;
+    if (flow_fmt == FLOW_F16) {
+        if (label_fmt == LABELS_U8) return mask_pack_as<uint8_t, flow_f16>(ld, grid, s, d_img, d_flow, d_seg, d_tab, v, B, sel, H, W, d_packed, dsp);
+        return mask_pack_as<float, flow_f16>(ld, grid, s, d_img, d_flow, d_seg, d_tab, v, B, sel, H, W, d_packed, dsp);
+    }
+    if (label_fmt == LABELS_U8) return mask_pack_as<uint8_t, flow_f32>(ld, grid, s, d_img, d_flow, d_seg, d_tab, v, B, sel, H, W, d_packed, dsp);
+    return mask_pack_as<float, flow_f32>(ld, grid, s, d_img, d_flow, d_seg, d_tab, v, B, sel, H, W, d_packed, dsp);
 }
 
-hipError_t launch_window_gather(const GatherArgs& a, int N, int label_fmt, hipStream_t s) {
+hipError_t launch_window_gather(const GatherArgs& a, int N, int label_fmt, int flow_fmt, hipStream_t s) {
     if (N < 1 || a.H < 1 || a.W < 4 || a.W % 4 || ((size_t)a.H * a.W) % 16 || !a.f_img || !a.f_seg || !a.w_img || !a.w_seg || !a.w_flow ||
         (a.f_depth && !a.w_depth))
         return hipErrorInvalidValue;
@@ -141,21 +176,29 @@ hipError_t launch_window_gather(const GatherArgs& a, int N, int label_fmt, hipSt
         return hipErrorInvalidValue;
     // the largest job decides the pieces per job (a flow plane, else a frame or a float32 plane); at most 8, the rest in rounds
     const size_t HW = (size_t)a.H * a.W;
-    const size_t vecs = a.f_flow ? HW / 2 : (a.W % 16 == 0 ? HW * 3 / 16 : HW * 3 / 4);
+    if (!flow_fmt_ok(flow_fmt) || (label_fmt != LABELS_F32 && label_fmt != LABELS_U8)) return hipErrorInvalidValue;
+    // (a binary16 flow plane is HW / 4 vectors, no more than a float32 label or depth plane: the max below covers it)
+    const size_t vecs = a.f_flow ? (flow_fmt == FLOW_F16 ? HW / 4 : HW / 2) : (a.W % 16 == 0 ? HW * 3 / 16 : HW * 3 / 4);
     const unsigned gx = (unsigned)std::min<size_t>(8, (std::max(vecs, HW / 4) + GATHER_PIECE - 1) / GATHER_PIECE);
     const dim3 grid(gx, (unsigned)N, GATHER_JOBS);
-    if (label_fmt == LABELS_F32) hipLaunchKernelGGL(window_gather<float>, grid, dim3(256), 0, s, a);
-    else if (label_fmt == LABELS_U8) hipLaunchKernelGGL(window_gather<uint8_t>, grid, dim3(256), 0, s, a);
-    else return hipErrorInvalidValue;
+    if (flow_fmt == FLOW_F16) {
+        if (label_fmt == LABELS_U8) hipLaunchKernelGGL((window_gather<uint8_t, flow_f16>), grid, dim3(256), 0, s, a);
+        else hipLaunchKernelGGL((window_gather<float, flow_f16>), grid, dim3(256), 0, s, a);
+    } else {
+        if (label_fmt == LABELS_U8) hipLaunchKernelGGL((window_gather<uint8_t, flow_f32>), grid, dim3(256), 0, s, a);
+        else hipLaunchKernelGGL((window_gather<float, flow_f32>), grid, dim3(256), 0, s, a);
+    }
     return hipGetLastError();
 }
 
-hipError_t launch_patch_layer(int layer, bool f32, bool fused, const ConvPatchParams& p, int nblk, hipStream_t s, int label_fmt) {
+hipError_t launch_patch_layer(int layer, bool f32, bool fused, const ConvPatchParams& p, int nblk, hipStream_t s, int label_fmt, int flow_fmt) {
     using Kernel = void (*)(ConvPatchParams);
     struct Row { Kernel h3, f32; int threads, lds; };
-    if (label_fmt != LABELS_F32 && label_fmt != LABELS_U8) return hipErrorInvalidValue;
+    if ((label_fmt != LABELS_F32 && label_fmt != LABELS_U8) || !flow_fmt_ok(flow_fmt)) return hipErrorInvalidValue;
     static const Kernel cnv1_fused_f32 = conv_patch_cnv1_h3<true, float>, cnv1_fused_u8 = conv_patch_cnv1_h3<true, uint8_t>;
-    const Kernel cnv1_fused = label_fmt == LABELS_U8 ? cnv1_fused_u8 : cnv1_fused_f32;
+    static const Kernel cnv1_fused_f32_hf = conv_patch_cnv1_h3<true, float, flow_f16>, cnv1_fused_u8_hf = conv_patch_cnv1_h3<true, uint8_t, flow_f16>;
+    const Kernel cnv1_fused = flow_fmt == FLOW_F16 ? (label_fmt == LABELS_U8 ? cnv1_fused_u8_hf : cnv1_fused_f32_hf)
+                                                   : (label_fmt == LABELS_U8 ? cnv1_fused_u8 : cnv1_fused_f32);
     static const Row rows[3] = {{conv_patch_cnv1_h3<false>, conv_patch_cnv1_f32, cp1::THREADS, cp1::LDS_BYTES},
                                 {conv_patch_cnv2_h3, conv_patch_cnv2_f32, cp2::THREADS, cp2::LDS_BYTES},
                                 {conv_patch_cnv3_h3, conv_patch_cnv3_f32, cp3::THREADS, cp3::LDS_BYTES}};

@@ -59,6 +59,12 @@ __host__ __device__ inline int att_se_frames(int a) { return (att_tgt_attended(a
 // labels are templated on the element type (input_decode.h); the launchers take the format and pick the instantiation.
 constexpr int LABELS_F32 = 0, LABELS_U8 = 1;
 
+// ---- flow format (davo_set_flow_format, include/davo_hip.h) ------------------------------------------------------------------
+// What the optical flow of a context is made of: float32 (the default) or IEEE binary16, same layout.  The kernels that read raw
+// flow are templated on the element type and widen through the fetches of input_decode.h; the launchers take the format and pick
+// the instantiation.
+constexpr int FLOW_F32 = 0, FLOW_F16 = 1;
+
 // ---- pair selection (davo_set_pairs, include/davo_hip.h) -------------------------------------------------------------------
 // A window's two poses come from two independent evaluations of the PoseNN (davo.py:1456-1457): pair 0 = (tgt, src0), pair 1 =
 // (tgt, src1).  sel 3 runs both: pair image n is pair n & 1 of window n >> 1.  sel 1 / 2 runs pair 0 / 1 alone: pair image n is
@@ -315,7 +321,7 @@ struct ConvPatchParams {
     // FUSED = true: the patch is built from the raw inputs (mask + pack fused in, the packed tensor
     // is never materialised): davo.py:1519-1522 (u8 -> f32), :1115,1178 (LUT attention), :1404-1442
     const uint8_t* img;     // u8 [B][H][3W][3]
-    const float* flow;      // [B][4][H][W][2]
+    const void* flow;       // [B][4][H][W][2] float32, or binary16 in the kernel's half-flow instantiation (input_decode.h)
     const void* seg;        // [B][3][H][W][1] float32, or bytes in the kernel's byte-label instantiation (input_decode.h)
     const float* tab;       // [B][3][19] attention tables (se_excite)
     Variant v;

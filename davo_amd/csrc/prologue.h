@@ -28,17 +28,19 @@ __device__ __forceinline__ float wave_sum(float v) {
 // SE squeeze, pass 1: partial[b][s][chunk][2] = sum over the chunk's pixels of t(flow[b][s]).
 // grid (SQ_CHUNKS, selected sources, B), 256 threads; float4 = two pixels x (fx, fy).  Fixed chunking and a
 // fixed reduction tree -> bitwise reproducible run to run.  With one pair selected (sel, params.h) only that source's plane is read.
-__global__ __launch_bounds__(256) void se_squeeze_partial(const float* __restrict__ flow, int HW,
+// FT: the flow element, float or flow_f16 (input_decode.h); a thread's unit comes from one flow_fetch2.
+template <typename FT>
+__global__ __launch_bounds__(256) void se_squeeze_partial(const FT* __restrict__ flow, int HW,
                                                           int norm_flow, int abs_mode, int sel,
                                                           float* __restrict__ partial) {
     const int chunk = blockIdx.x, s = pair_source(blockIdx.y, sel), b = blockIdx.z;
-    const float4* f = reinterpret_cast<const float4*>(flow + ((size_t)b * 4 + s) * HW * 2);
+    const FT* f = flow + ((size_t)b * 4 + s) * HW * 2;
     const int nvec = HW / 2;                                   // HW is a multiple of 16
     const int per = (nvec + SQ_CHUNKS - 1) / SQ_CHUNKS;
     const int beg = chunk * per, end = min(beg + per, nvec);
     float sx = 0.f, sy = 0.f;
     for (int i = beg + threadIdx.x; i < end; i += 256) {
-        float4 v = f[i];
+        float4 v = flow_fetch2(f + (size_t)i * 4);
         if (norm_flow) {
             v.x = (v.x - 0.32140523f) / 15.384229f; v.y = (v.y - 0.32140523f) / 15.384229f;
             v.z = (v.z - 0.32140523f) / 15.384229f; v.w = (v.w - 0.32140523f) / 15.384229f;
@@ -217,8 +219,8 @@ struct SeFar {
     float* tab;
 };
 
-template <bool SPLIT>
-__device__ __forceinline__ void se_squeeze_excite_body(const float* __restrict__ flow, int HW, const Variant& v,
+template <bool SPLIT, typename FT>
+__device__ __forceinline__ void se_squeeze_excite_body(const FT* __restrict__ flow, int HW, const Variant& v,
                                                        float* __restrict__ partial, unsigned* __restrict__ counters,
                                                        const float* __restrict__ w1, const float* __restrict__ b1,
                                                        const float* __restrict__ w2, const float* __restrict__ b2,
@@ -226,13 +228,13 @@ __device__ __forceinline__ void se_squeeze_excite_body(const float* __restrict__
                                                        unsigned* __restrict__ range_reset, int sel, const SeFar& far) {
     const int chunk = blockIdx.x, s = pair_source(blockIdx.y, sel), b = blockIdx.z;
     if (range_reset && chunk == 0 && blockIdx.y == 0 && b == 0 && threadIdx.x == 0) range_reset[RANGE_SNAP] = 0u;      // as se_excite
-    const float4* f = reinterpret_cast<const float4*>(flow + ((size_t)b * 4 + s) * HW * 2);
+    const FT* f = flow + ((size_t)b * 4 + s) * HW * 2;
     const int nvec = HW / 2;                                   // HW is a multiple of 16
     const int per = (nvec + SQ_CHUNKS - 1) / SQ_CHUNKS;
     const int beg = chunk * per, end = min(beg + per, nvec);
     float sx = 0.f, sy = 0.f;
     for (int i = beg + threadIdx.x; i < end; i += 256) {
-        float4 q = f[i];
+        float4 q = flow_fetch2(f + (size_t)i * 4);
         if (v.norm_flow) {
             q.x = (q.x - 0.32140523f) / 15.384229f; q.y = (q.y - 0.32140523f) / 15.384229f;
             q.z = (q.z - 0.32140523f) / 15.384229f; q.w = (q.w - 0.32140523f) / 15.384229f;
@@ -263,7 +265,8 @@ __device__ __forceinline__ void se_squeeze_excite_body(const float* __restrict__
     if (threadIdx.x == 0) __hip_atomic_store(counters + b, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
-__global__ __launch_bounds__(256) void se_squeeze_excite(const float* __restrict__ flow, int HW, Variant v,
+template <typename FT>
+__global__ __launch_bounds__(256) void se_squeeze_excite(const FT* __restrict__ flow, int HW, Variant v,
                                                          float* __restrict__ partial, unsigned* __restrict__ counters,
                                                          const float* __restrict__ w1, const float* __restrict__ b1,
                                                          const float* __restrict__ w2, const float* __restrict__ b2,
@@ -273,7 +276,8 @@ __global__ __launch_bounds__(256) void se_squeeze_excite(const float* __restrict
 }
 
 // ... of the depth-split source: the triplet's last workgroup evaluates the near tables, then the far ones
-__global__ __launch_bounds__(256) void se_squeeze_excite_split(const float* __restrict__ flow, int HW, Variant v,
+template <typename FT>
+__global__ __launch_bounds__(256) void se_squeeze_excite_split(const FT* __restrict__ flow, int HW, Variant v,
                                                                float* __restrict__ partial, unsigned* __restrict__ counters,
                                                                const float* __restrict__ w1, const float* __restrict__ b1,
                                                                const float* __restrict__ w2, const float* __restrict__ b2,
@@ -288,13 +292,13 @@ __global__ __launch_bounds__(256) void se_squeeze_excite_split(const float* __re
 //                      flow (src frames; the target's flow is zeros and has no sums);
 //   rgb sources:       [0, 3) sums of the frame's u8 channel bytes.
 // A thread takes 4 horizontally adjacent pixels per step (one label_fetch4 - a float4 of labels, or four bytes in the byte
-// format LT = uint8_t, input_decode.h - 12 strip bytes, two float4 of flow).  Label counts:
+// format LT = uint8_t, input_decode.h - 12 strip bytes, one flow_fetch4 of flow in the flow format FT).  Label counts:
 // per class one 64-bit ballot per pixel slot and a scalar popcount - wave-uniform sums with no LDS atomics on a hot bin (the labels
 // come in 8x8 blocks of one class).  The loop's trip count is uniform, so every lane sees every ballot.  The counts and byte sums
 // are exact integers and the flow sums use a fixed tree: bitwise reproducible.  FOLD: the workgroup that delivers the triplet's
 // last record evaluates its three tables (se_squeeze_excite's protocol, pose_tail.h).
-template <bool FOLD, typename LT>
-__global__ __launch_bounds__(256) void se_class_squeeze(const uint8_t* __restrict__ img, const float* __restrict__ flow,
+template <bool FOLD, typename LT, typename FT>
+__global__ __launch_bounds__(256) void se_class_squeeze(const uint8_t* __restrict__ img, const FT* __restrict__ flow,
                                                         const LT* __restrict__ seg, int H, int W, Variant v,
                                                         unsigned* __restrict__ partial, unsigned* __restrict__ counters,
                                                         const float* __restrict__ w1, const float* __restrict__ b1,
@@ -315,7 +319,7 @@ __global__ __launch_bounds__(256) void se_class_squeeze(const uint8_t* __restric
     // order src0, tgt, src1 (davo.py:998-1004)
     const int slot = frame == 0 ? 1 : frame == 1 ? 0 : 2;
     const LT* lab = seg + ((size_t)b * 3 + slot) * HW;         // LT: the label format, float32 or bytes (input_decode.h)
-    const float4* fv = reinterpret_cast<const float4*>(flow + ((size_t)b * 4 + (frame >= 1 ? frame - 1 : 0)) * HW * 2);
+    const FT* fv = flow + ((size_t)b * 4 + (frame >= 1 ? frame - 1 : 0)) * HW * 2;      // FT: the flow format (input_decode.h)
     unsigned cnt[NCLS];
 #pragma unroll
     for (int c = 0; c < NCLS; ++c) cnt[c] = 0u;
@@ -341,9 +345,9 @@ __global__ __launch_bounds__(256) void se_class_squeeze(const uint8_t* __restric
             sb += ((q0 >> 16) & 255u) + ((q1 >> 8) & 255u) + (q2 & 255u) + (q2 >> 24);
         }
         if (fl && ok) {
-            const float4 f0 = fv[2 * i], f1 = fv[2 * i + 1];
-            sx += (se_flow_transform(f0.x, 0, v) + se_flow_transform(f0.z, 0, v)) + (se_flow_transform(f1.x, 0, v) + se_flow_transform(f1.z, 0, v));
-            sy += (se_flow_transform(f0.y, 1, v) + se_flow_transform(f0.w, 1, v)) + (se_flow_transform(f1.y, 1, v) + se_flow_transform(f1.w, 1, v));
+            const Flow4 f = flow_fetch4(fv + (size_t)(2 * i) * 4);
+            sx += (se_flow_transform(f.v[0], 0, v) + se_flow_transform(f.v[2], 0, v)) + (se_flow_transform(f.v[4], 0, v) + se_flow_transform(f.v[6], 0, v));
+            sy += (se_flow_transform(f.v[1], 1, v) + se_flow_transform(f.v[3], 1, v)) + (se_flow_transform(f.v[5], 1, v) + se_flow_transform(f.v[7], 1, v));
         }
     }
     __shared__ unsigned red_u[4][NCLS];
@@ -448,11 +452,12 @@ __global__ __launch_bounds__(256) void se_depth_squeeze(const float* __restrict_
 //                            LD = 10: tgt rgb | 0 0 | src rgb*att | flow*att (reference layout)
 // v0 variants (rgb only) leave the flow slots zero.
 // LT: the label format, float32 or bytes; a thread's four labels of a plane come from one label_fetch4 (input_decode.h).
+// FT: the flow format, float32 or binary16; a thread's four pixels of flow come from one flow_fetch4 (input_decode.h).
 // DSPLIT (att_source 13, the depth-split flow attention): per 4-pixel group one more float4, of the depth plane of the source frame
 // the label map belongs to (file plane 0 or 2), and each pixel's class is looked up in the near table `tab' or the far table
 // `ds.tab_far' by att_lookup_split (input_decode.h, with DepthSplit); everything else is the same code.  The target's map is ones.
-template <int LD, bool DSPLIT, typename LT>
-__device__ __forceinline__ void mask_pack_body(const uint8_t* __restrict__ img, const float* __restrict__ flow,
+template <int LD, bool DSPLIT, typename LT, typename FT>
+__device__ __forceinline__ void mask_pack_body(const uint8_t* __restrict__ img, const FT* __restrict__ flow,
                                                const LT* __restrict__ seg, const float* __restrict__ tab,
                                                const Variant& v, int B, int sel, int H, int W, float* __restrict__ out, const DepthSplit& ds) {
     const int W4 = W >> 2;
@@ -504,10 +509,9 @@ __device__ __forceinline__ void mask_pack_body(const uint8_t* __restrict__ img, 
     }
     float fl[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
     if (v.cin_per_frame == 5) {
-        const float4* fp = reinterpret_cast<const float4*>(flow + (((size_t)b * 4 + s) * H * W + pix) * 2);
-        const float4 f0 = fp[0], f1 = fp[1];
-        fl[0] = f0.x; fl[1] = f0.y; fl[2] = f0.z; fl[3] = f0.w;
-        fl[4] = f1.x; fl[5] = f1.y; fl[6] = f1.z; fl[7] = f1.w;
+        const Flow4 f = flow_fetch4(flow + (((size_t)b * 4 + s) * H * W + pix) * 2);
+#pragma unroll
+        for (int k = 0; k < 8; ++k) fl[k] = f.v[k];
     }
     constexpr int OUT_FLOATS = LD == 16 ? 8 : LD;          // LD 16 = split-fp16 layout, 8 floats' worth per pixel
     float* o = out + (((size_t)n * H + y) * W + x) * OUT_FLOATS;
@@ -565,15 +569,15 @@ __device__ __forceinline__ void mask_pack_body(const uint8_t* __restrict__ img, 
     }
 }
 
-template <int LD, typename LT>
-__global__ __launch_bounds__(256) void mask_pack(const uint8_t* __restrict__ img, const float* __restrict__ flow,
+template <int LD, typename LT, typename FT>
+__global__ __launch_bounds__(256) void mask_pack(const uint8_t* __restrict__ img, const FT* __restrict__ flow,
                                                  const LT* __restrict__ seg, const float* __restrict__ tab,
                                                  Variant v, int B, int sel, int H, int W, float* __restrict__ out) {
     mask_pack_body<LD, false>(img, flow, seg, tab, v, B, sel, H, W, out, DepthSplit{});
 }
 
-template <int LD, typename LT>
-__global__ __launch_bounds__(256) void mask_pack_depthsplit(const uint8_t* __restrict__ img, const float* __restrict__ flow,
+template <int LD, typename LT, typename FT>
+__global__ __launch_bounds__(256) void mask_pack_depthsplit(const uint8_t* __restrict__ img, const FT* __restrict__ flow,
                                                             const LT* __restrict__ seg, const float* __restrict__ tab,
                                                             Variant v, int B, int sel, int H, int W, float* __restrict__ out, DepthSplit ds) {
     mask_pack_body<LD, true>(img, flow, seg, tab, v, B, sel, H, W, out, ds);

@@ -13,6 +13,7 @@ import numpy as np
 
 from . import _lib
 from .labels import LABEL_DTYPES, LABEL_FORMATS, check_label_format, labels_to_u8  # noqa: F401
+from .flow import FLOW_DTYPES, FLOW_FORMATS, check_flow_format, flow_from_f16, flow_to_f16  # noqa: F401
 from .version import ATT_SOURCE, NUM_SEG_CLASSES, parse_version, weight_shapes
 
 
@@ -113,12 +114,16 @@ class DeviceBuffer:
 class Engine:
     """Thin object wrapper of one ``davo_ctx`` (one GPU, one host thread)."""
 
-    def __init__(self, cfg, img_height, img_width, max_batch, device=0, labels="f32"):
+    def __init__(self, cfg, img_height, img_width, max_batch, device=0, labels="f32", flow="f32"):
         """``labels``: the format of every label map this engine takes - "f32" (the reference's float32 [B,3,H,W,1], the default)
-        or "u8" (uint8 class ids, a quarter of the bytes; include/davo_hip.h: davo_set_label_format, davo_amd.labels_to_u8)."""
+        or "u8" (uint8 class ids, a quarter of the bytes; include/davo_hip.h: davo_set_label_format, davo_amd.labels_to_u8).
+        ``flow``: the format of every flow array - "f32" (the default) or "f16" (IEEE binary16 in the same layout, half the
+        bytes; include/davo_hip.h: davo_set_flow_format, davo_amd.flow_to_f16)."""
         check_label_format(labels)
+        check_flow_format(flow)
         self.cfg, self.H, self.W, self.max_batch, self.device = cfg, img_height, img_width, max_batch, device
         self.labels = "f32"
+        self.flow = "f32"
         self._L = _lib.lib()
         self._ctx = ctypes.c_void_p()
         self.host_chunk = 8                       # davo_set_option "host_chunk" as last set through set_option (its default)
@@ -142,6 +147,30 @@ class Engine:
             except Exception:
                 self.close()
                 raise
+        if flow != "f32":
+            try:
+                self.set_flow_format(flow)
+            except Exception:
+                self.close()
+                raise
+
+    def set_flow_format(self, flow):
+        """Select the flow format, "f32" or "f16" (include/davo_hip.h: davo_set_flow_format): before the first call that takes
+        inputs, ValueError afterwards.  From then on every flow array must have that dtype; nothing is converted silently."""
+        self._check(self._L.davo_set_flow_format(self._ctx, FLOW_FORMATS[check_flow_format(flow)]))
+        self.flow = flow
+
+    def _flow_arg(self, flow):
+        """The flow of a batch as the entry points take it: C-contiguous, of the engine's format.  A float16 array handed to a
+        float32 engine, or anything but float16 to a binary16 engine, is a ValueError."""
+        is_f16 = np.asarray(flow).dtype == np.float16
+        if self.flow == "f16":
+            if not is_f16:
+                raise ValueError("this engine takes float16 flow (flow='f16'), got dtype %s: convert with davo_amd.flow_to_f16" % np.asarray(flow).dtype)
+            return np.ascontiguousarray(flow)
+        if is_f16:
+            raise ValueError("this engine takes float32 flow (flow='f32'), got float16: create it with flow='f16'")
+        return np.ascontiguousarray(flow, np.float32)
 
     def set_label_format(self, labels):
         """Select the label format, "f32" or "u8" (include/davo_hip.h: davo_set_label_format): before the first call that takes
@@ -203,11 +232,11 @@ class Engine:
         """A batch's uint8, float32 and label arrays as they are where they can go to the library so, else converted
         (``label_arg`` for the label maps) - or, ``strict`` (the name of a ``hold > 0`` submit), refused: a converted copy
         would not outlive the call."""
-        if not (_is_ready(pixels, np.uint8) and _is_ready(flow, np.float32) and _is_ready(seg, LABEL_DTYPES[self.labels]) and seg.ndim == seg_ndim):
+        if not (_is_ready(pixels, np.uint8) and _is_ready(flow, FLOW_DTYPES[self.flow]) and _is_ready(seg, LABEL_DTYPES[self.labels]) and seg.ndim == seg_ndim):
             if strict:
-                raise ValueError("%s(hold > 0) needs C-contiguous uint8 / float32 / %s arrays (a converted copy would not outlive the call)"
-                                 % (strict, LABEL_DTYPES[self.labels]))
-            pixels, flow, seg = np.ascontiguousarray(pixels, np.uint8), np.ascontiguousarray(flow, np.float32), label_arg(seg)
+                raise ValueError("%s(hold > 0) needs C-contiguous uint8 / %s / %s arrays (a converted copy would not outlive the call)"
+                                 % (strict, FLOW_DTYPES[self.flow], LABEL_DTYPES[self.labels]))
+            pixels, flow, seg = np.ascontiguousarray(pixels, np.uint8), self._flow_arg(flow), label_arg(seg)
         return pixels, flow, seg
 
     def _window_batch(self, img, flow, seg, depth, strict=None, calibration=False):
@@ -348,7 +377,9 @@ class Engine:
     def _call_device(self, name, n, bufs, depth, d_pose, timed, names, depth_slot=False):
         """The device entry points' checks and call: the label maps' DeviceBuffer holds the engine's format (where it knows), a
         depth-source variant gets its depth planes (any other ignores them).  -> milliseconds of the timed form, else None."""
-        d_seg = bufs[2]
+        d_flow, d_seg = bufs[1], bufs[2]
+        if getattr(d_flow, "dtype", None) is not None and (d_flow.dtype == np.float16) != (self.flow == "f16"):
+            raise ValueError("d_flow holds %s flow, this engine takes flow='%s'" % (d_flow.dtype, self.flow))
         if getattr(d_seg, "dtype", None) is not None and (d_seg.dtype == np.uint8) != (self.labels == "u8"):
             raise ValueError("d_seg holds %s label maps, this engine takes labels='%s'" % (d_seg.dtype, self.labels))
         if self.cfg.needs_depth and depth is None:
@@ -596,6 +627,16 @@ class DAVO(object):
         self._feature_mode = False
         self._features = 'full'
         self._labels = "f32"
+        self._flow = "f32"
+
+    def use_f16_flow(self):
+        """Opt in to binary16 flow (include/davo_hip.h: davo_set_flow_format): ``input_flow``, ``inference(inputs=...)`` and
+        iterator inputs then carry float16 [B,4,H,W,2] (davo_amd.flow_to_f16 of the float32 flow) and float32 flow is refused.
+        Before ``setup_inference`` - which also picks the format up by itself from a float16 ``input_flow``.  Returns self."""
+        if self.engine is not None:
+            raise DavoError("use_f16_flow() must be called before setup_inference")
+        self._flow = "f16"
+        return self
 
     def use_u8_labels(self):
         """Opt in to byte label maps (include/davo_hip.h: davo_set_label_format): ``input_seglabel``, ``inference(inputs=...)`` and
@@ -641,7 +682,9 @@ class DAVO(object):
         self.seq_length, self.num_source = seq_length, seq_length - 1
         assert self.version is not None                   # davo.py:959
         self.cfg = parse_version(self.version)
-        self.engine = Engine(self.cfg, img_height, img_width, batch_size, self.device, labels=self._labels)
+        if isinstance(input_flow, np.ndarray) and input_flow.dtype == np.float16:
+            self._flow = "f16"                             # a float16 ``input_flow`` selects the binary16 flow format
+        self.engine = Engine(self.cfg, img_height, img_width, batch_size, self.device, labels=self._labels, flow=self._flow)
         if self._weights is not None:
             self.engine.load_weights(self._weights)
         if self._feature_mode:

@@ -4,7 +4,7 @@ window layout, and the table of what a batch reads.
 A sequence of N windows is N + 2 frames; window n is (src0, tgt, src1) = frames (n, n + 1, n + 2):
 
 * ``frames`` u8  ``[N+2,H,W,3]``
-* ``flow2``  f32 ``[N,2,H,W,2]``   planes (tgt->src0, tgt->src1) of window n - planes 0, 1 of the window layout's ``[B,4,H,W,2]``
+* ``flow2``  f32 ``[N,2,H,W,2]``   (float16 for a binary16 engine, davo_amd.flow_to_f16: both conversions keep the dtype) planes (tgt->src0, tgt->src1) of window n - planes 0, 1 of the window layout's ``[B,4,H,W,2]``
 * ``seg``        ``[N+2,H,W,1]``   float32 or uint8 (davo_amd.labels_to_u8)
 * ``depth``  f32 ``[N+2,H,W,1]``   depth-source variants only
 
@@ -16,6 +16,7 @@ import ctypes
 import numpy as np
 
 from . import _lib
+from .flow import FLOW_FORMATS, check_flow_format
 from .labels import LABEL_FORMATS, check_label_format
 from .version import ATT_SOURCE
 
@@ -77,17 +78,22 @@ def frames_from_windows(img, flow, seg, depth=None):
     return res + ((out["depth"],) if depth is not None else ())
 
 
-def frames_plan(H, W, N, pairs="both", att_source="se_flow", labels="f32"):
+def frames_plan(H, W, N, pairs="both", att_source="se_flow", labels="f32", flow="f32"):
     """What a frame-layout batch of N windows reads (include/davo_hip.h: davo_frames_plan - the function the library's copies and
     its gather kernel are driven by; no GPU needed): ``{'frames', 'seg', 'depth', 'flow': (lo, hi), 'link_bytes': int}`` - frame
     ranges of the pixels, the label maps and the depth planes ((0, 0) where the source reads no depth), the flow planes, and the
-    bytes the host entry points send.  ``att_source``: a name of davo_amd.version.ATT_SOURCE or its number."""
+    bytes the host entry points send.  ``att_source``: a name of davo_amd.version.ATT_SOURCE or its number.  ``flow``: "f32", or
+    "f16" for a binary16 engine (davo_frames_plan_fmt): half the flow's bytes in 'link_bytes', the same ranges."""
     if pairs not in PAIRS:
         raise ValueError("pairs must be 'both', 'src0' or 'src1', got %r" % (pairs,))
     att = ATT_SOURCE[att_source] if isinstance(att_source, str) else int(att_source)
     r = (ctypes.c_int * 8)()
     nbytes = ctypes.c_longlong(0)
-    rc = _lib.lib().davo_frames_plan(int(H), int(W), int(N), PAIRS[pairs], att, LABEL_FORMATS[check_label_format(labels)], r, ctypes.byref(nbytes))
+    lab = LABEL_FORMATS[check_label_format(labels)]
+    if check_flow_format(flow) == "f32":
+        rc = _lib.lib().davo_frames_plan(int(H), int(W), int(N), PAIRS[pairs], att, lab, r, ctypes.byref(nbytes))
+    else:
+        rc = _lib.lib().davo_frames_plan_fmt(int(H), int(W), int(N), PAIRS[pairs], att, lab, FLOW_FORMATS[flow], r, ctypes.byref(nbytes))
     if rc != 0:
-        raise ValueError("davo_frames_plan(%r) refused its arguments" % ((H, W, N, pairs, att_source, labels),))
+        raise ValueError("davo_frames_plan(%r) refused its arguments" % ((H, W, N, pairs, att_source, labels, flow),))
     return {"frames": (r[0], r[1]), "seg": (r[2], r[3]), "depth": (r[4], r[5]), "flow": (r[6], r[7]), "link_bytes": nbytes.value}

@@ -7,7 +7,8 @@ The reference feeds the graph from a ``tf.data`` pipeline (``data_loader.py:241-
 sequence ``SS`` is
 
     <dump>/SS/FFFFFF.jpg              128 x 1248 RGB strip  src0 | tgt | src1
-    <dump>/SS/FFFFFF-flownet2.npy     float32 (4, H, W, 2)
+    <dump>/SS/FFFFFF-flownet2.npy     float32 (4, H, W, 2); a ``flow="f16"`` loader also reads float16 of the same shape as it is
+                                           (the binary16 form of davo_amd.flow_to_f16) and converts float32 files by that rule
     <dump>/SS/FFFFFF-seglabel.npy     float32 (3, H, W, 1)   (file order src0, tgt, src1); also accepted: uint8 class ids of
                                            the same shape (what DeepLab writes; the byte form of davo_amd.labels_to_u8)
     <dump>/SS/FFFFFF-monodepth2_depth.npy  float32 (3, H, W, 1)   (same order; read only for a depth-source variant:
@@ -26,6 +27,7 @@ from concurrent.futures import ProcessPoolExecutor, ThreadPoolExecutor
 
 import numpy as np
 
+from .flow import FLOW_DTYPES, check_flow_format, flow_to_f16
 from .labels import LABEL_DTYPES, check_label_format, labels_to_u8
 
 
@@ -47,11 +49,22 @@ def _labels_as_u8(a, path):
     raise ValueError("%s holds %s labels: a label file is float32 or uint8" % (path, a.dtype))
 
 
-def load_window(dump_dir, seq, tgt_idx, H, W, depth=False, labels="f32"):
+def _flow_as_f16(a, path):
+    """A flow file's array as binary16: float16 as it is, float32 by flow_to_f16; any other dtype is an error that names the file."""
+    if a.dtype == np.float16:
+        return a
+    if a.dtype == np.float32:
+        return flow_to_f16(a)
+    raise ValueError("%s holds %s flow: a flow file is float32 or float16" % (path, a.dtype))
+
+
+def load_window(dump_dir, seq, tgt_idx, H, W, depth=False, labels="f32", flow="f32"):
     """One window -> (img u8 [H,3W,3], flow f32 [4,H,W,2], seg f32 [3,H,W,1]); with ``depth`` also the depth planes
     f32 [3,H,W,1] in file order, as a fourth element.  ``labels`` = "u8": seg is uint8 [3,H,W,1] - a uint8 label file as it is,
-    a float32 one through labels_to_u8."""
+    a float32 one through labels_to_u8.  ``flow`` = "f16": flow is float16 [4,H,W,2] - a float16 flow file as it is, a float32
+    one through flow_to_f16."""
     check_label_format(labels)
+    flow_fmt = check_flow_format(flow)
     from PIL import Image
     jpg, flo, sg = window_paths(dump_dir, seq, tgt_idx)
     with Image.open(jpg) as im:
@@ -59,7 +72,10 @@ def load_window(dump_dir, seq, tgt_idx, H, W, depth=False, labels="f32"):
     if img.shape != (H, 3 * W, 3):
         raise ValueError("%s is %s, expected %s" % (jpg, img.shape, (H, 3 * W, 3)))
     # memory-mapped: the one copy of these arrays is the worker's write into its slot of the batch buffer
-    flow = np.load(flo, mmap_mode="r").astype(np.float32, copy=False).reshape(4, H, W, 2)
+    if flow_fmt == "f16":
+        flow = _flow_as_f16(np.load(flo, mmap_mode="r"), flo).reshape(4, H, W, 2)
+    else:
+        flow = np.load(flo, mmap_mode="r").astype(np.float32, copy=False).reshape(4, H, W, 2)
     if labels == "u8":
         seg = _labels_as_u8(np.load(sg, mmap_mode="r"), sg).reshape(3, H, W, 1)
     else:
@@ -70,13 +86,14 @@ def load_window(dump_dir, seq, tgt_idx, H, W, depth=False, labels="f32"):
     return img, flow, seg
 
 
-def _read_npy_into(path, dst, planes=None, labels=False):
+def _read_npy_into(path, dst, planes=None, labels=False, flow16=False):
     """Read a C-ordered .npy of dst's dtype and size straight into dst (no intermediate array); anything else
     goes through np.load + cast.  ``planes``: indices along the first axis that are wanted — the others are skipped
     in the file (seek) and left as they are in dst (the path reads flow planes 0,1 and the source frames' label maps only:
     davo.py:978-982,998-1004, so 1.3 of a window's 2.3 MB never have to leave the page cache).  ``labels``: dst is a byte label
     slot - a uint8 file is read straight into it like any file of dst's dtype, a float32 file is converted plane by plane with
-    labels_to_u8, any other dtype raises."""
+    labels_to_u8, any other dtype raises.  ``flow16``: dst is a binary16 flow slot - a float16 file is read straight into it, a
+    float32 file is converted plane by plane with flow_to_f16, any other dtype raises."""
     with open(path, "rb") as f:
         major, _ = np.lib.format.read_magic(f)
         shape, fortran, dtype = (np.lib.format.read_array_header_1_0 if major == 1 else np.lib.format.read_array_header_2_0)(f)
@@ -96,6 +113,11 @@ def _read_npy_into(path, dst, planes=None, labels=False):
         a = a.reshape(dst.shape)
         for k in (range(len(dst)) if planes is None else planes):
             dst[k] = _labels_as_u8(a[k], path)
+        return
+    if flow16:                                            # a binary16 flow slot: the file's own halves, or flow_to_f16 of its floats
+        a = a.reshape(dst.shape)
+        for k in (range(len(dst)) if planes is None else planes):
+            dst[k] = _flow_as_f16(a[k], path)
         return
     a = a.astype(dst.dtype, copy=False).reshape(dst.shape)
     if planes is None:
@@ -135,11 +157,17 @@ FLOW_PLANES_USED = (0, 1)           # davo.py:978-982: pred_flows = [0, flow[:,0
 SEG_PLANES_SOURCES = (0, 2)         # davo.py:998-1004 + 1408-1412: the target frame's attention is overwritten by ones
 
 
-def load_window_into(dump_dir, seq, tgt_idx, H, W, img, flow, seg, decoder=None, flow_planes=None, seg_planes=None, depth=None, labels=None):
+def load_window_into(dump_dir, seq, tgt_idx, H, W, img, flow, seg, decoder=None, flow_planes=None, seg_planes=None, depth=None, labels=None,
+                     flow_fmt=None):
     """load_window writing into the caller's [H,3W,3] / [4,H,W,2] / [3,H,W,1] slots; ``flow_planes`` / ``seg_planes``
     restrict the .npy reads to the planes the variant consumes (None = all).  ``labels``: "f32" or "u8", the format of the ``seg``
     slot, whose dtype must match (None = what the slot's dtype says).  ``depth``: a [3,H,W,1] slot for the depth planes
-    of a depth-source variant (all three are consumed: the target's depth enters every frame's descriptor, davo.py:1109)."""
+    of a depth-source variant (all three are consumed: the target's depth enters every frame's descriptor, davo.py:1109).
+    ``flow_fmt``: "f32" or "f16", the format of the ``flow`` slot, whose dtype must match (None = what the slot's dtype says)."""
+    if flow_fmt is None:
+        flow_fmt = "f16" if flow.dtype == np.float16 else "f32"
+    if flow.dtype != FLOW_DTYPES[check_flow_format(flow_fmt)]:
+        raise ValueError("flow=%r needs a %s flow slot, got %s" % (flow_fmt, FLOW_DTYPES[flow_fmt], flow.dtype))
     if labels is None:
         labels = "u8" if seg.dtype == np.uint8 else "f32"
     if seg.dtype != LABEL_DTYPES[check_label_format(labels)]:
@@ -154,7 +182,7 @@ def load_window_into(dump_dir, seq, tgt_idx, H, W, img, flow, seg, decoder=None,
     if a.shape != (H, 3 * W, 3):
         raise ValueError("%s is %s, expected %s" % (jpg, a.shape, (H, 3 * W, 3)))
     img[...] = a
-    _read_npy_into(flo, flow, flow_planes)
+    _read_npy_into(flo, flow, flow_planes, flow16=flow_fmt == "f16")
     _read_npy_into(sg, seg, seg_planes, labels=labels == "u8")
     if depth is not None:
         _read_npy_into(depth_path(dump_dir, seq, tgt_idx), depth)
@@ -324,7 +352,7 @@ def _segment_batches(segments, B):
     return [(seq, s, min(s + B, hi)) for seq, lo, hi in segments for s in range(lo, hi, B)]
 
 
-def _slot_worker(k, P, names, ctrl_name, B, H, W, dump_dir, segments, flow_planes, seg_planes, chunk, nring, sem, errq, labels="f32"):
+def _slot_worker(k, P, names, ctrl_name, B, H, W, dump_dir, segments, flow_planes, seg_planes, chunk, nring, sem, errq, labels="f32", flow_fmt="f32"):
     """Worker k of P (a fork of the warm fork server): fills its chunks of the batches of ``segments`` (_segment_batches) in order,
     straight into the shared batch buffers, walking on from one segment into the next as ring places free up.  No task queue: which
     chunks are its own follows from k (_chunk_owner); ctrl[0] = number of batches that may be filled
@@ -345,7 +373,7 @@ def _slot_worker(k, P, names, ctrl_name, B, H, W, dump_dir, segments, flow_plane
             # the names are registered with the parent's resource tracker already; the parent's close() is what unlinks them
             t = [shared_memory.SharedMemory(name=n) for n in trio]
             segs += t
-            ring.append((np.ndarray((B, H, 3 * W, 3), np.uint8, buffer=t[0].buf), np.ndarray((B, 4, H, W, 2), np.float32, buffer=t[1].buf),
+            ring.append((np.ndarray((B, H, 3 * W, 3), np.uint8, buffer=t[0].buf), np.ndarray((B, 4, H, W, 2), FLOW_DTYPES[flow_fmt], buffer=t[1].buf),
                          np.ndarray((B, 3, H, W, 1), LABEL_DTYPES[labels], buffer=t[2].buf)) +
                         ((np.ndarray((B, 3, H, W, 1), np.float32, buffer=t[3].buf),) if len(t) == 4 else ()))     # a depth variant's fourth buffer
         cpb = -(-B // chunk)                               # chunks per batch (the last one of a batch may be short)
@@ -370,7 +398,7 @@ def _slot_worker(k, P, names, ctrl_name, B, H, W, dump_dir, segments, flow_plane
                 for w in range(w0, w1):
                     i = w - s
                     load_window_into(dump_dir, seq, w + 1, H, W, img[i], flow[i], seg[i], None, flow_planes, seg_planes,
-                                     depth=None if dep is None else dep[i], labels=labels)
+                                     depth=None if dep is None else dep[i], labels=labels, flow_fmt=flow_fmt)
                 ctrl[2 + P + k] += time.perf_counter_ns() - t0
             ctrl[2 + k] += 1
             sem.release()
@@ -418,6 +446,8 @@ class ProcessWindowLoader:
     read); batches are then (img, flow, seg, depth).
     ``labels`` = "u8": the label buffers are uint8 - a quarter of their shared, page-locked bytes - filled from uint8 label files
     as they are and from float32 ones through labels_to_u8 in the worker.
+    ``flow`` = "f16": the flow buffers are float16 - half their shared, page-locked bytes - filled from float16 flow files as they
+    are and from float32 ones through flow_to_f16 in the worker.
 
     A batch is valid until the consumer has asked for ``hold`` + 1 further ones (``hold`` = 0: until the next one); the last
     ones until ``close()`` (or the loader's deletion), which unpins and unmaps the buffers.  The end of iteration stops the
@@ -433,8 +463,9 @@ class ProcessWindowLoader:
 
     def __init__(self, dump_dir, seq, H, W, lo, hi, batch_size, procs=8, prefetch=2, chunk=None, pin=None, unpin=None,
                  flow_planes=FLOW_PLANES_USED, seg_planes=SEG_PLANES_SOURCES, shm_budget=None, hold=0, depth=False, segments=None,
-                 labels="f32"):
+                 labels="f32", flow="f32"):
         self.labels = check_label_format(labels)
+        self.flow = check_flow_format(flow)
         if segments is None:
             segments = [(seq, lo, hi)]
         elif seq is not None or lo is not None or hi is not None:
@@ -456,7 +487,8 @@ class ProcessWindowLoader:
         # the ring is sized in BYTES: prefetch + fill + 2 (+ hold) batch buffer trios if they fit the budget (shm_budget_bytes),
         # fewer batches in flight if not, and a clear error - the caller falls back to the threaded loader - if not even four fit
         self._label_bytes = LABEL_DTYPES[self.labels].itemsize
-        per_batch = batch_size * (H * 3 * W * 3 + 4 * H * W * 2 * 4 + 3 * H * W * self._label_bytes + (3 * H * W * 4 if self.depth else 0))
+        self._flow_bytes = FLOW_DTYPES[self.flow].itemsize
+        per_batch = batch_size * (H * 3 * W * 3 + 4 * H * W * 2 * self._flow_bytes + 3 * H * W * self._label_bytes + (3 * H * W * 4 if self.depth else 0))
         budget = shm_budget_bytes() if shm_budget is None else shm_budget
         want = self.prefetch + self.fill + 2 + self.hold
         self.nring = min(want, budget // per_batch)
@@ -485,12 +517,12 @@ class ProcessWindowLoader:
         from multiprocessing import shared_memory
         dump_dir, seq, H, W = self.args
         B, P = self.B, self.procs
-        sizes = (B * H * 3 * W * 3, B * 4 * H * W * 2 * 4, B * 3 * H * W * self._label_bytes) + ((B * 3 * H * W * 4,) if self.depth else ())
+        sizes = (B * H * 3 * W * 3, B * 4 * H * W * 2 * self._flow_bytes, B * 3 * H * W * self._label_bytes) + ((B * 3 * H * W * 4,) if self.depth else ())
         for _ in range(self.nring):
             trio = [shared_memory.SharedMemory(create=True, size=max(n, 1)) for n in sizes]
             self._segs.append(trio)
             views = (np.ndarray((B, H, 3 * W, 3), np.uint8, buffer=trio[0].buf),
-                     np.ndarray((B, 4, H, W, 2), np.float32, buffer=trio[1].buf),
+                     np.ndarray((B, 4, H, W, 2), FLOW_DTYPES[self.flow], buffer=trio[1].buf),
                      np.ndarray((B, 3, H, W, 1), LABEL_DTYPES[self.labels], buffer=trio[2].buf))
             if self.depth:
                 views += (np.ndarray((B, 3, H, W, 1), np.float32, buffer=trio[3].buf),)
@@ -504,7 +536,7 @@ class ProcessWindowLoader:
         self._sem, self._errq = ctx.Semaphore(0), ctx.SimpleQueue()
         self._pool = [ctx.Process(target=_slot_worker, daemon=True,
                                   args=(k, P, names, self._ctrl_shm.name, B, H, W, dump_dir, self.segments, self.fp, self.sp,
-                                        self.chunk, self.nring, self._sem, self._errq, self.labels)) for k in range(P)]
+                                        self.chunk, self.nring, self._sem, self._errq, self.labels, self.flow)) for k in range(P)]
         for p in self._pool:                              # forks of the warm server: they attach the buffers and start filling at once
             p.start()
         # Page-locking (hipHostRegister) allocates and pins every page: 0.3 s for the 1.4 GB of a batch-64 ring, which used to sit in
@@ -652,17 +684,19 @@ class ProcessWindowLoader:
                 self._stop()
 
 
-def kitti_loader(dump_dir, seq, H, W, lo, hi, batch_size, workers=4, prefetch=2, alloc=None, decode_procs=0, depth=False, labels="f32"):
+def kitti_loader(dump_dir, seq, H, W, lo, hi, batch_size, workers=4, prefetch=2, alloc=None, decode_procs=0, depth=False, labels="f32",
+                 flow="f32"):
     """Windows [lo, hi) of a sequence dump; window w has target frame w + 1.  ``decode_procs`` > 0 decodes the
     strips in that many processes (the ``workers`` threads then only wait for them and read the .npy files).
     ``depth``: batches are (img, flow, seg, depth) - the depth files are opened only then.  ``labels`` = "u8": uint8 label batches
-    (load_window)."""
+    (load_window).  ``flow`` = "f16": float16 flow batches (load_window)."""
     check_label_format(labels)
+    flow_fmt = check_flow_format(flow)
     dec = JpegDecodePool(decode_procs) if decode_procs > 0 else None
     return ThreadedWindowLoader(
-        lambda w: load_window(dump_dir, seq, w + 1, H, W, depth, labels), lo, hi, batch_size,
+        lambda w: load_window(dump_dir, seq, w + 1, H, W, depth, labels, flow_fmt), lo, hi, batch_size,
         max(workers, 2 * decode_procs), prefetch, alloc,
-        load_into=lambda w, i, f, s, d=None: load_window_into(dump_dir, seq, w + 1, H, W, i, f, s, dec, depth=d, labels=labels),
+        load_into=lambda w, i, f, s, d=None: load_window_into(dump_dir, seq, w + 1, H, W, i, f, s, dec, depth=d, labels=labels, flow_fmt=flow_fmt),
         on_close=dec.close if dec else None)
 
 
@@ -685,13 +719,16 @@ def scene_like_strip(H, W, window, seed=0):
     return np.clip(out, 0, 255).astype(np.uint8)
 
 
-def write_synthetic_dump(dump_dir, seq, n_frames, H, W, seed=None, quality=None, images="noise", depth=False, labels="f32"):
+def write_synthetic_dump(dump_dir, seq, n_frames, H, W, seed=None, quality=None, images="noise", depth=False, labels="f32", flow="f32"):
     """Write a dump in the reference's on-disk format from the seeded synthetic tensors (no KITTI offline).
     ``depth``: also write the ``-monodepth2_depth.npy`` files (``synth.make_depth``) a depth-source variant reads.
     ``images``: "noise" = the parity inputs' uniform-noise strips at quality 95 (worst case for the decoder), "scene" =
     ``scene_like_strip`` at quality 75 (a real dump's file size and decode cost).  ``labels`` = "u8": the ``-seglabel.npy`` files
-    hold uint8 class ids, labels_to_u8 of the float maps.  Returns the number of windows written."""
+    hold uint8 class ids, labels_to_u8 of the float maps.  ``flow`` = "f16": the ``-flownet2.npy`` files hold float16,
+    flow_to_f16 of the float32 flow; "widened": float32 files of exactly those halves' values (flow_from_f16 of them) - the
+    float32 dump a binary16 run is bit-identical to.  Returns the number of windows written."""
     check_label_format(labels)
+    flow_fmt = flow if flow == "widened" else check_flow_format(flow)
     from PIL import Image
     from . import synth
     if images not in ("noise", "scene"):
@@ -705,7 +742,8 @@ def write_synthetic_dump(dump_dir, seq, n_frames, H, W, seed=None, quality=None,
         jpg, flo, sg = window_paths(dump_dir, seq, w + 1)
         strip = img[0] if images == "noise" else scene_like_strip(H, W, w, synth.SEED if seed is None else seed)
         Image.fromarray(strip).save(jpg, quality=quality)
-        np.save(flo, flow[0])
+        half = None if flow_fmt == "f32" else flow_to_f16(flow[0])
+        np.save(flo, flow[0] if flow_fmt == "f32" else half if flow_fmt == "f16" else half.astype(np.float32))
         np.save(sg, labels_to_u8(seg[0]) if labels == "u8" else seg[0])
         if depth:
             np.save(depth_path(dump_dir, seq, w + 1),

@@ -136,6 +136,11 @@ def build_parser():
                          "davo_set_label_format) - a quarter of the label bytes in the loader's buffers, over the link and in the staging "
                          "sets; uint8 -seglabel.npy files are read as they are, float32 ones converted by the loader's workers "
                          "(davo_amd.labels_to_u8).  The written file is the same")
+    ap.add_argument("--flow", choices=("f32", "f16"), default="f32",
+                    help="f32: the optical flow crosses the link as float32.  f16: as IEEE binary16 (include/davo_hip.h: "
+                         "davo_set_flow_format) - half the flow bytes in the loader's buffers, over the link and in the staging sets; "
+                         "float16 -flownet2.npy files are read as they are, float32 ones rounded by the loader's workers "
+                         "(davo_amd.flow_to_f16).  The written file is that of a float32 run on the rounded flow, to the byte")
     return ap
 
 
@@ -209,7 +214,7 @@ def main(argv=None):
                                      alloc=lambda shape, dtype: pinned_empty(shape, dtype, device_index),
                                      workers=a.loader_threads, decode_procs=a.decode_procs, procs=procs,
                                      pin=lambda arr: (gpu_ready.wait(), pin_array(arr, device_index)), unpin=unpin_array,
-                                     seg_planes=tgt_planes, hold=0 if a.sync_driver else 1, depth=needs_depth, labels=a.labels)
+                                     seg_planes=tgt_planes, hold=0 if a.sync_driver else 1, depth=needs_depth, labels=a.labels, flow=a.flow)
         # the loader's buffers are created and its workers start filling them on a thread of its own, before anything else: the
         # workers need no GPU.  Page-locking the buffers (1.4 GB at batch 64: 0.3 s) follows on the loader's own thread, entry by
         # entry, once the context below exists: HIP serialises hipHostRegister with the context's own allocations, and pinning
@@ -237,6 +242,8 @@ def main(argv=None):
             system = DAVO(version=a.version, device=device_index)
             if a.labels == "u8":
                 system.use_u8_labels()
+            if a.flow == "f16":
+                system.use_f16_flow()
             system.setup_inference(H, W, "davo", a.seq_length, a.batch_size)
             mark("gpu_context_created")
         finally:
@@ -248,7 +255,7 @@ def main(argv=None):
 
         if synthetic:
             from . import synth
-            load = S.synthetic_window_loader(H, W, depth=needs_depth, labels=a.labels)     # the same seeded windows whatever the sequence's number
+            load = S.synthetic_window_loader(H, W, depth=needs_depth, labels=a.labels, flow=a.flow)     # the same seeded windows whatever the sequence's number
             weights = synth.make_weights(a.version)
         else:
             weights_thread.join()
@@ -352,6 +359,8 @@ def main(argv=None):
                 run_wide["pairs"] = a.pairs
             if a.labels != "f32":
                 run_wide["labels"] = a.labels
+            if a.flow != "f32":
+                run_wide["flow"] = a.flow
             if len(entries) == 1:          # one sequence: the report it has always had
                 report = {k: v for k, v in entries[0].items() if k not in ("seq", "wall_s")}
                 report.update(run_wide)

@@ -416,9 +416,10 @@ class kitti_window_loader:
     threaded, prefetching batch iterator of a rank's shard; calling it ``(s, e)`` loads one batch inline."""
 
     def __init__(self, concat_img_dir, seq, n_frames, H, W, workers=4, prefetch=2, alloc=None, decode_procs=0, procs=0,
-                 pin=None, unpin=None, seg_planes=None, hold=0, depth=False, labels="f32"):
+                 pin=None, unpin=None, seg_planes=None, hold=0, depth=False, labels="f32", flow="f32"):
         self.depth = depth        # a depth-source variant: batches are (img, flow, seg, depth)
         self.labels = labels      # "u8": every loader below yields uint8 label batches (davo_amd/loader.py)
+        self.flow = flow          # "f16": every loader below yields float16 flow batches (davo_amd/loader.py)
         self.dir, self.seq, self.n_frames, self.H, self.W = concat_img_dir, seq, n_frames, H, W
         self.workers, self.prefetch, self.alloc, self.decode_procs = workers, prefetch, alloc, decode_procs
         self.procs, self.pin, self.unpin, self.seg_planes = procs, pin, unpin, seg_planes
@@ -441,13 +442,13 @@ class kitti_window_loader:
         if self.procs > 0:      # worker processes fill shared (page-locked) batch buffers: davo_amd/loader.py, ProcessWindowLoader
             try:
                 return L.ProcessWindowLoader(self.dir, self.seq, self.H, self.W, lo, hi, batch_size, self.procs, self.prefetch,
-                                             pin=self.pin, unpin=self.unpin, hold=self.hold, depth=self.depth, labels=self.labels,
+                                             pin=self.pin, unpin=self.unpin, hold=self.hold, depth=self.depth, labels=self.labels, flow=self.flow,
                                              seg_planes=L.SEG_PLANES_SOURCES if self.seg_planes is None else self.seg_planes)
             except L.ShmBudgetError as e:      # e.g. a container with the usual 64 MB /dev/shm: decode threads into pinned buffers instead
                 import sys
                 print("davo_amd: %s - falling back to the threaded loader" % e, file=sys.stderr)
         return L.kitti_loader(self.dir, self.seq, self.H, self.W, lo, hi, batch_size, self.workers, self.prefetch, self.alloc, self.decode_procs,
-                              depth=self.depth, labels=self.labels)
+                              depth=self.depth, labels=self.labels, flow=self.flow)
 
     def __call__(self, s, e):
         return self.load_inline(self.seq, s, e)
@@ -455,7 +456,7 @@ class kitti_window_loader:
     def load_inline(self, seq, s, e):
         """windows [s, e) of sequence ``seq``, loaded in this process"""
         from .loader import load_window
-        parts = [load_window(self.dir, seq, w + 1, self.H, self.W, self.depth, self.labels) for w in range(s, e)]
+        parts = [load_window(self.dir, seq, w + 1, self.H, self.W, self.depth, self.labels, self.flow) for w in range(s, e)]
         return tuple(np.stack([p[k] for p in parts]) for k in range(4 if self.depth else 3))
 
     # several sequences from one worker pool (``seq`` and ``n_frames`` of the constructor are not used by these)
@@ -468,7 +469,7 @@ class kitti_window_loader:
             from . import loader as L
             try:
                 ld = L.ProcessWindowLoader(self.dir, None, self.H, self.W, None, None, batch_size, self.procs, self.prefetch,
-                                           pin=self.pin, unpin=self.unpin, hold=self.hold, depth=self.depth, segments=segments, labels=self.labels,
+                                           pin=self.pin, unpin=self.unpin, hold=self.hold, depth=self.depth, segments=segments, labels=self.labels, flow=self.flow,
                                            seg_planes=L.SEG_PLANES_SOURCES if self.seg_planes is None else self.seg_planes)
                 self._multi = ((list(segments), batch_size), ld.start())
             except L.ShmBudgetError as e:      # as for_range: the threaded loader, built per sequence
@@ -493,7 +494,7 @@ class kitti_window_loader:
         from . import loader as L
         seq, lo, hi = segments[k]
         return L.kitti_loader(self.dir, seq, self.H, self.W, lo, hi, batch_size, self.workers, self.prefetch, self.alloc, self.decode_procs,
-                              depth=self.depth, labels=self.labels)
+                              depth=self.depth, labels=self.labels, flow=self.flow)
 
     def close(self):
         """stop and unmap the several-segment loader, if one was built"""
@@ -502,11 +503,11 @@ class kitti_window_loader:
             multi[1].close()
 
 
-def synthetic_window_loader(H, W, seed=None, depth=False, labels="f32"):
+def synthetic_window_loader(H, W, seed=None, depth=False, labels="f32", flow="f32"):
     from . import synth
 
     def load(s, e):
-        parts = synth.make_inputs(e - s, H, W, seed=synth.SEED if seed is None else seed, first_window=s, labels=labels)
+        parts = synth.make_inputs(e - s, H, W, seed=synth.SEED if seed is None else seed, first_window=s, labels=labels, flow=flow)
         if depth:
             parts += (synth.make_depth(e - s, H, W, seed=synth.SEED if seed is None else seed, first_window=s),)
         return parts

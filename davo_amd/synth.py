@@ -63,13 +63,16 @@ def _stream(name):
     return h
 
 
-def make_inputs(B, H=128, W=416, seed=SEED, first_window=0, labels="f32"):
+def make_inputs(B, H=128, W=416, seed=SEED, first_window=0, labels="f32", flow="f32"):
     """Synthetic batch of B triplets; window w of a sequence is reproducible on its own
     (``first_window`` offsets the per-window streams), which is what lets ranks generate
     just their shard.  ``labels`` = "u8": the label maps are the byte twin of the float ones
-    (``davo_amd.labels_to_u8``), uint8 [B,3,H,W,1]."""
+    (``davo_amd.labels_to_u8``), uint8 [B,3,H,W,1].  ``flow`` = "f16": the flow is the rounded twin of the float32 draw
+    (``davo_amd.flow_to_f16``), float16 [B,4,H,W,2]."""
+    from .flow import check_flow_format, flow_to_f16
     from .labels import check_label_format, labels_to_u8
     check_label_format(labels)
+    flow_fmt = check_flow_format(flow)
     img = np.empty((B, H, 3 * W, 3), np.uint8)
     flow = np.empty((B, 4, H, W, 2), np.float32)
     seg = np.empty((B, 3, H, W, 1), np.float32)
@@ -86,7 +89,7 @@ def make_inputs(B, H=128, W=416, seed=SEED, first_window=0, labels="f32"):
         ids[ign] = 255.0
         blk = ids.reshape(3, hb, wb)
         seg[b, :, :, :, 0] = np.repeat(np.repeat(blk, 8, axis=1), 8, axis=2)[:, :H, :W]
-    return img, flow, (labels_to_u8(seg) if labels == "u8" else seg)
+    return img, (flow_to_f16(flow) if flow_fmt == "f16" else flow), (labels_to_u8(seg) if labels == "u8" else seg)
 
 
 def make_depth(B, H=128, W=416, seed=SEED, first_window=0):
@@ -116,15 +119,17 @@ def make_depth(B, H=128, W=416, seed=SEED, first_window=0):
     return depth
 
 
-def make_frames(n_frames, H=128, W=416, seed=SEED, depth=False, labels="f32"):
+def make_frames(n_frames, H=128, W=416, seed=SEED, depth=False, labels="f32", flow="f32"):
     """A synthetic sequence in the frame layout (davo_amd/frames.py): ``(frames, flow2, seg)`` - ``(frames, flow2, seg, depth)`` with
     ``depth`` - for the n_frames - 2 windows of n_frames frames: frames u8 [n,H,W,3], flow2 f32 [n-2,2,H,W,2] (per window, the
     statistics of ``make_inputs``), seg [n,H,W,1] (8x8 blocks of train ids, 3 % ignore; uint8 with labels="u8"), depth f32
     [n,H,W,1] (the fields of ``make_depth``).  Every frame and every window draws from streams of its own, so no two frames agree
     in any plane, and consecutive windows share their frames by construction - which ``make_inputs``' windows, drawn one by one,
-    do not."""
+    do not.  ``flow`` = "f16": flow2 is float16, ``davo_amd.flow_to_f16`` of the float32 draw."""
+    from .flow import check_flow_format, flow_to_f16
     from .labels import check_label_format, labels_to_u8
     check_label_format(labels)
+    check_flow_format(flow)
     if n_frames < 3:
         raise ValueError("a sequence needs at least 3 frames, got %d" % n_frames)
     frames = np.empty((n_frames, H, W, 3), np.uint8)
@@ -141,7 +146,7 @@ def make_frames(n_frames, H=128, W=416, seed=SEED, depth=False, labels="f32"):
     for w in range(n_frames - 2):
         v = normalish(seed, _stream("frame_flow") + 7919 * w, 2 * H * W * 2)
         flow2[w] = (v * 15.384229 + 0.32140523).astype(np.float32).reshape(2, H, W, 2)
-    out = (frames, flow2, labels_to_u8(seg) if labels == "u8" else seg)
+    out = (frames, flow_to_f16(flow2) if flow == "f16" else flow2, labels_to_u8(seg) if labels == "u8" else seg)
     if depth:
         planes = make_depth((n_frames + 2) // 3, H, W, seed=seed, first_window=1000003)      # three planes per draw, all different
         out += (np.ascontiguousarray(planes.reshape(-1, H, W, 1)[:n_frames]),)

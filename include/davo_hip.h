@@ -103,6 +103,33 @@ enum { DAVO_LABELS_F32 = 0, DAVO_LABELS_U8 = 1 };
 int davo_set_label_format(davo_ctx* ctx, int fmt);
 int davo_get_label_format(const davo_ctx* ctx);
 
+/* Flow format.  The optical flow is what FlowNet2 estimates, to about a pixel; the reference's dump stores it as float32
+ * [B,4,H,W,2] (24 significant bits), which is what every entry point takes by default (DAVO_FLOW_F32).
+ * davo_set_flow_format(ctx, DAVO_FLOW_F16) makes the context take IEEE binary16 instead, in the same layout: 11 significant
+ * bits, a rounding error of at most 2^-12 relative - under 0.004 px at 15 px; above 2048 px the spacing is 2 px and more.
+ * davo_amd.flow_to_f16 is the one rule by which float32 flow becomes halves: round to nearest even, finite values beyond
+ * +-65504 go to +-65504 (a finite flow stays finite), NaN stays NaN.  The kernels read the halves natively: a 4-pixel unit is
+ * one aligned 16-byte load, widened value by value (exact for every binary16 value, subnormals, signed zeros and infinities
+ * included; NaN stays NaN), and every float32 expression and summation order behind the widening is the float32 format's.  So
+ * for any binary16 array h, a DAVO_FLOW_F16 context on h and a DAVO_FLOW_F32 context on (float)h give the same bits in every
+ * tensor: attention tables, the packed input, cnv1..cnv7, poses, range records, feature and heat exports, in both precisions.
+ * On a DAVO_FLOW_F16 context the `flow' / `d_flow' / `flow2' argument of EVERY entry point below points at halves (a C caller
+ * casts the pointer): davo_forward, davo_forward_device, davo_submit, davo_calibrate, their `_depth' forms, the three `_frames'
+ * forms ([N,2,H,W,2]), davo_forward_features and davo_forward_heat; and everything the context sizes by a window's flow follows -
+ * the host entry points' copies and their sub-batching, the staging sets of the streaming slots, the frame layout's gather, the
+ * range guard's input snapshots and its re-issues (as issued, re-calibrated or on the float32 kernels).  Device flow buffers
+ * must be 16-byte aligned (DAVO_ERR_INVALID otherwise).  A variant that reads no flow (`v0' with a flow-free attention
+ * source) accepts the call; every variant still takes the pointer.
+ * Bytes across the link per window at 128x416, both pairs, byte labels: the window form sends 479,232 (strip) + 425,984 (two
+ * binary16 flow planes; 851,968 as float32) + 106,496 (two label maps) = 1,011,712 instead of 1,437,696; the frame layout
+ * 159,744 + 425,984 + 53,248 = 638,976 instead of 1,064,960 (40 % fewer).
+ * The ordering rule is the label format's: called right after davo_create; once any call has taken inputs (or a staging set, a
+ * frame buffer or the snapshot ring exists) it returns DAVO_ERR_INVALID, and so does any other value of fmt.  It is independent
+ * of davo_set_label_format, davo_set_posenn_se and davo_set_pairs, in any order.  davo_get_flow_format reads it back. */
+enum { DAVO_FLOW_F32 = 0, DAVO_FLOW_F16 = 1 };
+int davo_set_flow_format(davo_ctx* ctx, int fmt);
+int davo_get_flow_format(const davo_ctx* ctx);
+
 /* Replaces tf.train.Saver(tf.trainable_variables()).restore(sess, ckpt)
  * (test_kitti_pose.py:129-131), one tensor at a time, keyed by the TF variable name
  * (e.g. "pose_exp_net/cnv1/weights", "pose_exp_net/pose/rotation/cnv6/biases",
@@ -119,7 +146,8 @@ int davo_weights_missing(davo_ctx* ctx);
 /* Replaces DAVO.inference(sess, mode='pose') (davo.py:1553-1569 -> sess.run({'pose': pred_poses})).
  * Host pointers, shapes as the reference's test driver sets them (test_kitti_pose.py:110-114):
  *   img  uint8 [B,H,3W,3]  (strip src0|tgt|src1, data_loader.py:537-557)
- *   flow f32   [B,4,H,W,2] (planes 0,1 used, davo.py:978-982)
+ *   flow f32   [B,4,H,W,2] (planes 0,1 used, davo.py:978-982); binary16 [B,4,H,W,2] behind the same pointer type on a
+ *              DAVO_FLOW_F16 context (davo_set_flow_format) - here and for every `flow' / `d_flow' / `flow2' argument below
  *   seg  f32   [B,3,H,W,1] (file order src0,tgt,src1, davo.py:998-1004); uint8 [B,3,H,W,1] behind the same pointer type on a
  *              DAVO_LABELS_U8 context (davo_set_label_format) - here and for every `seg' / `d_seg' argument below
  *   pose_out f32 [B,2,6]   rows = (tgt->src0, tgt->src1), each [rz,ry,rx,tx,ty,tz]
@@ -224,7 +252,7 @@ int davo_get_pairs(const davo_ctx* ctx);
  * frame into three strips and send it across the link three times.  The `_frames' forms take every frame once.  N windows
  * (1 <= N <= max_batch) come as N + 2 frames; window n is (src0, tgt, src1) = frames (n, n + 1, n + 2):
  *   frames   uint8 [N+2,H,W,3]
- *   flow2    f32   [N,2,H,W,2]   planes (tgt->src0, tgt->src1) of window n: planes 0, 1 of davo_forward's [B,4,H,W,2], the two the
+ *   flow2    f32   [N,2,H,W,2]   (binary16 on a DAVO_FLOW_F16 context) planes (tgt->src0, tgt->src1) of window n: planes 0, 1 of davo_forward's [B,4,H,W,2], the two the
  *                                path reads
  *   seg            [N+2,H,W,1]   float32, or bytes on a DAVO_LABELS_U8 context (davo_set_label_format)
  *   depth    f32   [N+2,H,W,1]   in the signature: NULL (or anything, ignored) where the variant reads no depth; where it does
@@ -260,6 +288,9 @@ int davo_get_pairs(const davo_ctx* ctx);
  * davo_frames_plan is that table as a function (no context, no device): ranges[8] receives the [lo, hi) pairs of the frames,
  * the label maps, the depth planes (0, 0 where att_source reads none) and the flow planes of a batch of N windows, *link_bytes
  * the bytes the host entry points copy for it; either pointer may be NULL.  DAVO_ERR_INVALID for an argument out of range.
+ * davo_frames_plan_fmt is the same with the flow format as an argument (DAVO_FLOW_F32 or DAVO_FLOW_F16: 8 or 4 bytes per
+ * pixel and flow plane in *link_bytes; 638,976 per window for the line above with byte labels and binary16 flow);
+ * davo_frames_plan means flow_fmt = DAVO_FLOW_F32.
  * There are no `_frames' forms of davo_calibrate, davo_forward_features and davo_forward_heat. */
 int davo_forward_frames(davo_ctx* ctx, int N, const uint8_t* frames, const float* flow2, const float* seg,
                         const float* depth, float* pose_out);
@@ -268,6 +299,7 @@ int davo_submit_frames(davo_ctx* ctx, int N, const uint8_t* frames, const float*
 int davo_forward_device_frames(davo_ctx* ctx, int N, const void* d_frames, const void* d_flow2, const void* d_seg,
                                const void* d_depth, void* d_pose, float* elapsed_ms);
 int davo_frames_plan(int H, int W, int N, int pairs, int att_source, int label_fmt, int* ranges, long long* link_bytes);
+int davo_frames_plan_fmt(int H, int W, int N, int pairs, int att_source, int label_fmt, int flow_fmt, int* ranges, long long* link_bytes);
 
 /* Feature export.  Replaces DAVO.inference(sess, mode='feature') (davo.py:1553-1569), the call generate_feature_map.py:183-260
  * makes to draw the class-attention table and the cnv6 feature maps: the poses of davo_forward and, from the same forward, the

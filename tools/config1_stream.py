@@ -3,7 +3,9 @@
 128x416 (run_inference.sh:44-51, test_kitti_pose.py:133-145) - from memory: windows/s of the sequence loop with the time split,
 synchronous driver (one davo_forward per window) against the streaming entry point (davo_submit, two windows in flight).
 
-    python tools/config1_stream.py [out.json]
+    python tools/config1_stream.py [out.json] [--labels f32|u8] [--flow f32|f16] [--quick]
+        --labels u8 / --flow f16: the windows cross the link as byte label maps / binary16 flow (davo_set_label_format,
+        davo_set_flow_format); --quick: f16x3 only, the synchronous driver and two streamed ones
 
 The 799 windows are 64 distinct synthetic ones in page-locked memory (generating 799 takes minutes of host time); every window
 is its own submit, trajectory stitched at the end as the CLI does."""
@@ -22,7 +24,12 @@ def main():
     from davo_amd import sequence as S
     H, W, NF, n = 128, 416, 801, 64
     cfg = parse_version(FLAGSHIP_VERSION)
-    src = synth.make_inputs(n, H, W)
+    argv = sys.argv[1:]
+    labels = argv.pop(argv.index("--labels") + 1) if "--labels" in argv else "f32"
+    flow = argv.pop(argv.index("--flow") + 1) if "--flow" in argv else "f32"
+    quick = "--quick" in argv
+    sys.argv = sys.argv[:1] + [a for a in argv if a not in ("--labels", "--flow", "--quick")]
+    src = synth.make_inputs(n, H, W, labels=labels, flow=flow)
     pinned = [pinned_empty(a.shape, a.dtype) for a in src]
     for p, a in zip(pinned, src):
         p[...] = a
@@ -30,7 +37,7 @@ def main():
     def load(s, e):
         k = (s * 37) % n
         return tuple(p[k:k + 1] for p in pinned)         # views of page-locked memory: no host copy per window
-    eng = Engine(cfg, H, W, 1)
+    eng = Engine(cfg, H, W, 1, labels=labels, flow=flow)
     eng.load_weights(synth.make_weights(cfg))
     opts = [a for a in sys.argv[1:] if "=" in a]                      # e.g. fold_tails=1 fuse_pack=1 (davo_set_option)
     sys.argv = [a for a in sys.argv if "=" not in a]
@@ -38,14 +45,17 @@ def main():
         k, v = kv.split("=")
         eng.set_option(k, int(v))
     eng.calibrate(*load(0, 1))
-    rec = {"what": "BASELINE configs[0] shape from memory: 799 windows, batch 1, 128x416, f16x3 (default arithmetic) and f32", "options": opts, "runs": []}
+    rec = {"what": "BASELINE configs[0] shape from memory: 799 windows, batch 1, 128x416, f16x3 (default arithmetic) and f32", "options": opts, "labels": labels, "flow": flow,
+           "h2d_bytes_per_window": int(src[0][0].nbytes + src[1][0].nbytes // 2 + src[2][0].nbytes), "runs": []}
     ref = None
-    for precision in ("f16x3", "f32"):
+    for precision in (("f16x3",) if quick else ("f16x3", "f32")):
         eng.set_precision(precision)
         for name, mk in (("synchronous", lambda: None), ("streamed_hold0", lambda: S.PoseStream(eng, 2, hold=0)),
                          ("streamed_hold8", lambda: S.PoseStream(eng, 2, hold=8)),
                          ("streamed_hold0_inflight3", lambda: S.PoseStream(eng, 3, hold=0)), ("streamed_hold8_inflight3", lambda: S.PoseStream(eng, 3, hold=8)),
                          ("streamed_hold8_inflight4", lambda: S.PoseStream(eng, 4, hold=8))):
+            if quick and name not in ("synchronous", "streamed_hold8", "streamed_hold8_inflight4"):
+                continue
             best = None
             for rep in range(3):
                 eng.set_inflight(1)

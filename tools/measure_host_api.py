@@ -257,6 +257,102 @@ def layout_measurement(arms, rounds, n=30, H=128, W=416):
             e.close()
 
 
+def flow_measurement(arms, rounds, n=30, H=128, W=416):
+    """`--flow f32 f16 [--rounds R]`: the flow formats (davo_set_flow_format) against each other, byte labels, one engine per
+    format in ONE process, the arms alternating inside every round (round 0 warms up), f16x3 and float32:
+      resident  ms per davo_forward_device step at B = 32 with the inputs in HBM (the bench's path): per arm the median, and the
+                spread (max - min) of its rounds - the margin of the "binary16 flow is not slower" bound; then, profiled, the
+                mean launch time of the squeeze and of mask_pack (davo_profile_entry);
+      streamed  windows/s of davo_submit (window layout) and davo_submit_frames (frame layout) from page-locked memory at B = 32
+                and at batch 1, with 1, 2 and 4 slots, best of the rounds, beside the H2D bytes per window.
+    The float32 arm on flow_from_f16 of the binary16 arm's halves computes the same bits (tests/test_f16_flow_gpu.py)."""
+    from davo_amd import flow_from_f16, frames_plan, pinned_empty, windows_from_frames
+    cfg = parse_version(FLAGSHIP_VERSION)
+    weights = synth.make_weights(cfg)
+    hw = H * W
+    for B in (32, 1):
+        engines, pinned, dev, link = {}, {}, {}, {}
+        fr16 = synth.make_frames(B + 2, H, W, labels="u8", flow="f16")
+        for arm in arms:
+            fr = fr16 if arm == "f16" else (fr16[0], flow_from_f16(fr16[1]), fr16[2])
+            host = {"windows": windows_from_frames(*fr), "frames": fr}
+            e = engines[arm] = Engine(cfg, H, W, B, labels="u8", flow=arm)
+            e.load_weights(weights)
+            pinned[arm] = {k: tuple(pinned_empty(a.shape, a.dtype) for a in v) for k, v in host.items()}
+            for k in host:
+                for d, a in zip(pinned[arm][k], host[k]):
+                    d[...] = a
+            dev[arm] = tuple(e.alloc(a.nbytes).upload(a) for a in host["windows"]) + (e.alloc(B * 48),)
+            fb = 2 if arm == "f16" else 4
+            link[arm] = {"windows": hw * 9 + hw * 4 * fb + hw * (2 if B >= 4 else 3),
+                         "frames": frames_plan(H, W, B, "both", cfg.att_source, "u8", arm)["link_bytes"] // B}
+        nb = n if B > 1 else 20 * n
+        outs = [np.empty((B, 2, 6), np.float32) for _ in range(nb)]
+        for prec in ("f16x3", "f32"):
+            for e in engines.values():
+                e.set_precision(prec)
+            if B == 32:
+                step = {arm: [] for arm in arms}
+                for e in engines.values():
+                    e.set_inflight(1)
+                for r in range(rounds + 1):
+                    for arm in arms:
+                        e = engines[arm]
+                        for _ in range(5):
+                            e.forward_device(B, *dev[arm])
+                        e.synchronize()
+                        t0 = time.perf_counter()
+                        for _ in range(n):
+                            e.forward_device(B, *dev[arm])
+                        e.synchronize()
+                        if r:
+                            step[arm].append((time.perf_counter() - t0) / n * 1e3)
+                for arm in arms:
+                    v = sorted(step[arm])
+                    print("resident davo_forward_device %-5s B=%d flow=%-3s: median %.4f ms per step, spread %.4f (rounds %s)"
+                          % (prec, B, arm, v[len(v) // 2], v[-1] - v[0], " ".join("%.4f" % x for x in step[arm])), flush=True)
+                for arm in arms:                             # the launches that read raw flow, bracketed by events
+                    e = engines[arm]
+                    e.profile(1)
+                    e.profile_reset()
+                    for _ in range(n):
+                        e.forward_device(B, *dev[arm])
+                    e.synchronize()
+                    ent = e.profile_entries()
+                    e.profile(0)
+                    print("profiled %-5s B=%d flow=%-3s: %s" % (prec, B, arm, "  ".join(
+                        "%s %.1f us x %d" % (k, 1e3 * ent[k][1] / max(ent[k][0], 1), ent[k][0]) for k in ("se_squeeze_partial", "mask_pack", "cnv1") if k in ent)), flush=True)
+            for layout, issue in (("windows", "submit"), ("frames", "submit_frames")):
+                for slots in (1, 2, 4):
+                    rates = {arm: [] for arm in arms}
+                    for e in engines.values():
+                        e.set_inflight(slots)
+                    for r in range(rounds + 1):
+                        for arm in arms:
+                            e = engines[arm]
+                            t0 = time.perf_counter()
+                            for o in outs:
+                                getattr(e, issue)(*pinned[arm][layout], o, hold=8)
+                            e.synchronize()
+                            if r:
+                                rates[arm].append(B * nb / (time.perf_counter() - t0))
+                    for arm in arms:
+                        mb = link[arm][layout]
+                        print("streamed %-7s %-5s B=%-2d %d slot(s) flow=%-3s: %9.1f windows/s best, rounds %s; %d B H2D per window -> %.1f GB/s"
+                              % (layout, prec, B, slots, arm, max(rates[arm]), " ".join("%.0f" % x for x in rates[arm]), mb, mb * max(rates[arm]) / 1e9), flush=True)
+        for e in engines.values():
+            e.close()
+
+
+if "--flow" in sys.argv:
+    import argparse
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--flow", nargs="+", choices=("f32", "f16"), required=True)
+    ap.add_argument("--rounds", type=int, default=3)
+    args = ap.parse_args()
+    flow_measurement(args.flow, args.rounds)
+    sys.exit(0)
+
 if "--layout" in sys.argv:
     import argparse
     ap = argparse.ArgumentParser()
