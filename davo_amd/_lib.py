@@ -50,7 +50,7 @@ EXPORTS = (
     "davo_set_feature_export", "davo_forward_features", "davo_set_heat_export", "davo_forward_heat",
     "davo_pad_class_tables", "davo_pad_class_tile_order", "davo_plan_layer_f32", "davo_decide_layer",
     "davo_forward_frames", "davo_submit_frames", "davo_forward_device_frames", "davo_frames_plan",
-    "davo_set_flow_format", "davo_get_flow_format", "davo_frames_plan_fmt",
+    "davo_set_flow_format", "davo_get_flow_format", "davo_frames_plan_fmt", "davo_pool_plan",
 )
 COMM_ID_BYTES = 128
 LABELS_F32, LABELS_U8 = 0, 1          # DAVO_LABELS_F32, DAVO_LABELS_U8 (davo_set_label_format)
@@ -240,6 +240,7 @@ def _load():
     L.davo_forward_device_frames.argtypes = [vp, i, vp, vp, vp, vp, vp, ctypes.POINTER(ctypes.c_float)]
     L.davo_frames_plan.argtypes = [i] * 6 + [ctypes.POINTER(i), ctypes.POINTER(ctypes.c_longlong)]
     L.davo_frames_plan_fmt.argtypes = [i] * 7 + [ctypes.POINTER(i), ctypes.POINTER(ctypes.c_longlong)]
+    L.davo_pool_plan.argtypes = [i] * 3 + [ctypes.POINTER(i), ctypes.POINTER(i), f32p]
     L.davo_debug_read.argtypes = [vp, ctypes.c_char_p, f32p, ctypes.c_size_t]
     L.davo_conv2d_same.argtypes = [i, f32p, i, i, i, i, f32p, i, i, f32p, i, i, i, i, f32p, ctypes.c_char_p, i]
     ip = ctypes.POINTER(i)

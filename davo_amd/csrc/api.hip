@@ -7,6 +7,7 @@
 
 #include "ctx.h"
 #include "plan.h"
+#include "pool_plan.h"
 
 using namespace davo;
 
@@ -56,6 +57,24 @@ int alloc_se_workspace(davo_ctx* c, Slot* s) {
     return DAVO_OK;
 }
 
+// att_source 14..17: the pool plan of the context's image size, once, on the device (pool_plan.h)
+int build_pool_plan(davo_ctx* c) {
+    const PoolPlan p = pool_plan(c->H, c->W, c->v.att_source);
+    if (p.cells.empty() || p.items.empty() || 2 * (int)p.cells.size() != att_se_in(c->v.att_source))
+        return fail(c, DAVO_ERR_INVALID, "internal: pool plan of %dx%d, att_source %d has %zu cells, %zu work items", c->H, c->W, c->v.att_source,
+                    p.cells.size(), p.items.size());
+    std::vector<int> items;
+    std::vector<float> inv;
+    for (const PoolItem& it : p.items) { items.push_back(it.y0); items.push_back(it.y1); items.push_back(it.x0); items.push_back(it.x1); }
+    for (const PoolCell& cell : p.cells) inv.push_back(cell.inv_div);
+    c->d_pool_items = upload_table(items);
+    c->d_pool_cell_first = upload_table(p.cell_first);
+    c->d_pool_inv_div = upload_table(inv);
+    if (!c->d_pool_items || !c->d_pool_cell_first || !c->d_pool_inv_div) HIP_TRY(c, hipErrorOutOfMemory);
+    c->pool = PoolDev{c->d_pool_items.get(), c->d_pool_cell_first.get(), c->d_pool_inv_div.get(), (int)p.items.size(), (int)p.cells.size()};
+    return DAVO_OK;
+}
+
 // one more in-flight slot (stream + activation workspace for max_batch triplets): appended once it is complete
 int add_slot(davo_ctx* c) {
     const size_t NB = 2 * (size_t)c->max_batch;
@@ -64,12 +83,19 @@ int add_slot(davo_ctx* c) {
     for (int i = 0; i < 7; ++i) HIP_TRY(c, dev_alloc(&s.d_act[i], NB * c->act_floats_per_img[i]));
     HIP_TRY(c, dev_alloc(&s.d_packed, NB * (size_t)c->H * c->W * 10));
     // squeeze partials: se_flow [B][2 sources][SQ_CHUNKS][2] floats, the class-table sources [B][3 frames][SQ_CHUNKS][SQ_REC] words
-    const size_t partial_floats = (size_t)c->max_batch * SQ_CHUNKS * (att_class_table(c->v.att_source) ? 3 * SQ_REC : 2 * 2);
+    // (the pooled flow-attention variants: [B][2 sources][work items][2] floats)
+    const size_t partial_floats = att_pooled(c->v.att_source) ? (size_t)c->max_batch * 2 * c->pool.n_items * 2
+                                                              : (size_t)c->max_batch * SQ_CHUNKS * (att_class_table(c->v.att_source) ? 3 * SQ_REC : 2 * 2);
     HIP_TRY(c, dev_alloc(&s.d_partial, partial_floats));
     HIP_TRY(c, dev_alloc(&s.d_tab, (size_t)c->max_batch * 3 * NCLS));
     if (c->v.att_source == ATT_DEPTH_SPLIT) HIP_TRY(c, dev_alloc(&s.d_tab_far, (size_t)c->max_batch * 3 * NCLS));      // the far MLP's tables: this source only
     HIP_TRY(c, dev_alloc(&s.d_pose_partial, NB * 2 * PH_SPLIT * 3));
     { int rc = zero_now(c, s.d_partial.get(), partial_floats * sizeof(float)); if (rc) return rc; }
+    if (att_pooled(c->v.att_source)) {      // the descriptors [B][2][D]: this family only; zero, so that a one-pair batch leaves the other source's row defined
+        const size_t desc_floats = (size_t)c->max_batch * 2 * 2 * c->pool.n_cells;
+        HIP_TRY(c, dev_alloc(&s.d_desc, desc_floats));
+        { int rc = zero_now(c, s.d_desc.get(), desc_floats * sizeof(float)); if (rc) return rc; }
+    }
     const size_t counters = (size_t)c->max_batch + 1 + SK_TILE_COUNTERS;
     HIP_TRY(c, dev_alloc(&s.d_counters, counters));
     { int rc = zero_now(c, s.d_counters.get(), counters * sizeof(unsigned)); if (rc) return rc; }
@@ -95,7 +121,7 @@ int davo_create(davo_ctx** out, int device, int H, int W, int max_batch, const d
     if (max_batch < 1) return fail(c, DAVO_ERR_INVALID, "max_batch must be >= 1");
     if (v->cin_per_frame != 5 && v->cin_per_frame != 3) return fail(c, DAVO_ERR_INVALID, "cin_per_frame must be 3 or 5");
     if (ilog2_exact(v->cnv6_out) < 5 || v->cnv6_out > 256) return fail(c, DAVO_ERR_INVALID, "cnv6_out must be 32, 64, 128 or 256");
-    if (v->se_act < 0 || v->se_act > 2 || v->abs_mode < 0 || v->abs_mode > 3 || v->att_source < 0 || v->att_source > ATT_DEPTH_SPLIT)
+    if (v->se_act < 0 || v->se_act > 2 || v->abs_mode < 0 || v->abs_mode > 3 || v->att_source < 0 || v->att_source > ATT_MAX)
         return fail(c, DAVO_ERR_INVALID, "variant field out of range");
     int ndev = 0;
     HIP_TRY(c, hipGetDeviceCount(&ndev));
@@ -122,6 +148,7 @@ int davo_create(davo_ctx** out, int device, int H, int W, int max_batch, const d
         c->act_ch[i] = ch[i];
         c->act_floats_per_img[i] = px[i] * ch[i];
     }
+    if (att_pooled(c->v.att_source)) { int rc = build_pool_plan(c); if (rc) return rc; }      // the slots' squeeze partials are sized by it
     { int rc = add_slot(c); if (rc) return rc; }
     HIP_TRY(c, dev_alloc(&c->d_zeros, 256 / sizeof(float)));
     { int rc = zero_now(c, c->d_zeros.get(), 256); if (rc) return rc; }

@@ -1,6 +1,6 @@
 // ctx.h — host-side state of one davo_ctx (include/davo_hip.h) and the small helpers every
 // translation unit of libdavo_hip.so shares.  Host code only; the kernels live in conv_igemm.h,
-// conv_igemm_h3.h, conv_igemm_h3s.h, conv_patch_h3.h and prologue.h and are launched through launch.h.
+// conv_igemm_h3.h, conv_igemm_h3s.h, conv_patch_h3.h, prologue.h and se_pool.h and are launched through launch.h.
 //
 // Translation units (built in parallel by davo_amd/_lib.py, linked into one shared library):
 //   api.hip         extern "C": context life cycle, weights, settings and the option table, range-state calls, davo_synchronize
@@ -14,7 +14,7 @@
 //   launch_f32.hip  conv_igemm_f32 instantiations + dispatch
 //   launch_h3.hip   conv_igemm_h3 instantiations + dispatch (the f16x3 path, the long compile)
 //   launch_h3s.hip  conv_igemm_h3s instantiations (208x256 tile); launch_h3_generic.hip: davo_conv2d_same's shapes
-//   launch_misc.hip prologue / pose head / cnv1..cnv3 patch / feature-attention (posenn_se.h) / direct-convolution kernels + dispatch
+//   launch_misc.hip prologue / pooled squeeze and excite (se_pool.h) / pose head / cnv1..cnv3 patch / feature-attention (posenn_se.h) / direct-convolution kernels + dispatch
 //   launch_feature.hip  the feature export kernels (feature_export.h) + dispatch
 //   comm.hip        RCCL communicator behind the C ABI (pose gather of the window-sharded driver)
 // owned.h holds the owner types (device / page-locked memory, streams, events): everything a context allocates is a member of
@@ -83,8 +83,9 @@ struct Slot {
     StreamOwner stream;
     DevMem<float> d_partial, d_tab, d_packed, d_pose_partial;
     DevMem<float> d_tab_far;                     // depth-split flow attention (att_source 13): the far MLP's tables [B][3][19] (d_tab holds the near ones); null in every other variant
+    DevMem<float> d_desc;                        // pooled flow attention (att_source 14..17): the SE descriptors [B][2][D] ("se_desc"); null in every other variant
     DevMem<float> d_act[7];
-    std::optional<SeWorkspace> se;               // absent with the feature-attention mode off
+    std::optional<SeWorkspace> se;              // absent with the feature-attention mode off
     DevMem<unsigned> d_counters;                 // "last workgroup" tickets (pose_tail.h): [0] cnv7's pose tail, [1 + b] triplet b's squeeze, [1 + max_batch + t] tile t of a split-K launch
 };
 static_assert(std::is_nothrow_move_constructible<Slot>::value, "davo_ctx::slots is a std::vector");
@@ -227,6 +228,10 @@ struct davo_ctx {
     bool cnv7_valid = true;
     davo::Variant v{};
     float depth_thr = 0.f;                     // att_source 13: pose_exp_net/se_flow/depth_threshold as davo_load_weight received it (the kernels take it as an argument)
+    // att_source 14..17: the pool plan of (H, W, att_source) on the device (pool_plan.h; davo_create builds it once), empty in every other variant
+    davo::DevMem<int> d_pool_items, d_pool_cell_first;
+    davo::DevMem<float> d_pool_inv_div;
+    davo::PoolDev pool{};
     int posenn_se = 0;                         // davo_set_posenn_se: 0 none | 1 insert - an SE block on cnv5 ahead of each head's cnv6 (posenn_se.h); cnv6 is then a two-group layer
     bool forward_seen = false;                 // a forward has been issued (davo_set_posenn_se is refused from then on)
     int label_fmt = davo::LABELS_F32;          // davo_set_label_format: what every `seg' argument points at, and what plane_bytes().seg sizes

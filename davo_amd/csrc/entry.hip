@@ -8,6 +8,7 @@
 
 #include "ctx.h"
 #include "launch.h"
+#include "pool_plan.h"
 #include "window_gather.h"
 
 using namespace davo;
@@ -323,7 +324,7 @@ int davo_forward_device_frames(davo_ctx* c, int N, const void* d_frames, const v
 }
 
 int davo_frames_plan_fmt(int H, int W, int N, int pairs, int att_source, int label_fmt, int flow_fmt, int* ranges, long long* link_bytes) {
-    if (H < 1 || W < 1 || N < 1 || (pairs != PAIRS_SRC0 && pairs != PAIRS_SRC1 && pairs != PAIRS_BOTH) || att_source < 0 || att_source > ATT_DEPTH_SPLIT ||
+    if (H < 1 || W < 1 || N < 1 || (pairs != PAIRS_SRC0 && pairs != PAIRS_SRC1 && pairs != PAIRS_BOTH) || att_source < 0 || att_source > ATT_MAX ||
         (label_fmt != LABELS_F32 && label_fmt != LABELS_U8) || (flow_fmt != FLOW_F32 && flow_fmt != FLOW_F16))
         return DAVO_ERR_INVALID;
     const FramePlan p = frame_plan(N, pairs, att_source);
@@ -336,7 +337,21 @@ int davo_frames_plan_fmt(int H, int W, int N, int pairs, int att_source, int lab
 }
 
 int davo_frames_plan(int H, int W, int N, int pairs, int att_source, int label_fmt, int* ranges, long long* link_bytes) {
+    // the range this form was published with (tests/test_frames.py pins 14 as refused): the pooled sources go through davo_frames_plan_fmt
+    if (att_source > ATT_DEPTH_SPLIT) return DAVO_ERR_INVALID;
     return davo_frames_plan_fmt(H, W, N, pairs, att_source, label_fmt, FLOW_F32, ranges, link_bytes);
+}
+
+int davo_pool_plan(int H, int W, int att_source, int* n_cells, int* rects, float* inv_div) {
+    if (H < 1 || W < 1 || att_source < 0 || att_source > ATT_MAX || !n_cells) return DAVO_ERR_INVALID;
+    const PoolPlan p = pool_plan(H, W, att_source);
+    *n_cells = (int)p.cells.size();
+    for (size_t i = 0; i < p.cells.size(); ++i) {
+        const PoolCell& c = p.cells[i];
+        if (rects) { rects[4 * i] = c.y0; rects[4 * i + 1] = c.y1; rects[4 * i + 2] = c.x0; rects[4 * i + 3] = c.x1; }
+        if (inv_div) inv_div[i] = c.inv_div;
+    }
+    return DAVO_OK;
 }
 
 

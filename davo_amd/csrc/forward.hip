@@ -469,7 +469,18 @@ int forward_device(davo_ctx* c, const Run& run, int B, const Inputs& in, void* d
         if (!d_tab_far || !se_w1 || !se_b1 || !se_w2 || !se_b2 || !far_w[0] || !far_w[1] || !far_w[2] || !far_w[3])
             return fail(c, DAVO_ERR_INVALID, "internal: the depth-split attention's tables or dense tensors are missing");
     }
-    if (att_desc_depth(v.att_source)) {
+    const bool pooled = att_pooled(v.att_source);
+    if (pooled) {
+        // pooled flow attention (se_pool.h): the window sums of the context's pool plan, then the excitation as a launch of its own
+        // ("fold_tails" does not apply to these sources)
+        if (!ws.d_desc || !se_w1 || !se_b1 || !se_w2 || !se_b2) return fail(c, DAVO_ERR_INVALID, "internal: the pooled attention's descriptor buffer or dense tensors are missing");
+        {
+            ProfScope ps(c, run.stream, "se_pool_squeeze");
+            HIP_TRY(c, launch_se_pool_squeeze(d_flow, ffmt, B, H, W, v, c->pool, d_partial, sel, s));
+        }
+        ProfScope ps(c, run.stream, "se_pool_excite");
+        HIP_TRY(c, launch_se_pool_excite(d_partial, B, v, c->pool, se_w1, se_b1, se_w2, se_b2, d_tab, ws.d_desc.get(), range_reset, sel, s));
+    } else if (att_desc_depth(v.att_source)) {
         // depth sources: one float32 sum per depth plane and chunk, then (or, folded, in the same launch) the excitation
         ProfScope ps(c, run.stream, "se_depth_squeeze");
         HIP_TRY(c, launch_se_depth_squeeze(fold_excite, static_cast<const float*>(in.depth), B, HW, v, reinterpret_cast<unsigned*>(d_partial),
@@ -495,7 +506,7 @@ int forward_device(davo_ctx* c, const Run& run, int B, const Inputs& in, void* d
         ProfScope ps(c, run.stream, "se_squeeze_partial");
         HIP_TRY(c, launch_se_squeeze(d_flow, ffmt, B, HW, v, d_partial, sel, s));
     }
-    if (!fold_excite) {
+    if (!fold_excite && !pooled) {
         ProfScope ps(c, run.stream, "se_excite");
         HIP_TRY(c, launch_se_excite(d_partial, B, HW, v, se_w1, se_b1, se_w2, se_b2,
                                     wdev("pose_exp_net/pose_exp_net/seg_channel_weight/weight"), d_tab, range_reset, sel, s));

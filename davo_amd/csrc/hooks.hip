@@ -120,6 +120,10 @@ int davo_debug_read(davo_ctx* c, const char* tensor, float* host_out, size_t n_f
         if (!ws.d_tab_far) return fail(c, DAVO_ERR_INVALID, "`att_table_far' exists for the depth-split flow attention only (att_source %d, got %d)", ATT_DEPTH_SPLIT, c->v.att_source);
         src = ws.d_tab_far.get(); n = (size_t)c->last_B * 3 * NCLS;
     }
+    else if (t == "se_desc") {                               // pooled flow attention (se_pool.h): the SE descriptors [B][2][D] of the source frames
+        if (!ws.d_desc) return fail(c, DAVO_ERR_INVALID, "`se_desc' exists for the pooled flow-attention variants only (att_source %d..%d, got %d)", ATT_POOL_GP2X2, ATT_POOL_SPP864, c->v.att_source);
+        src = ws.d_desc.get(); n = (size_t)c->last_B * 2 * att_se_in(c->v.att_source);
+    }
     else if (t == "cnv5_se_scale" || t == "cnv5_se") {      // feature attention (posenn_se.h): [2B][2][256] s_r | s_r s_t; [2B][H2][W2][512] rotation | translation input of cnv6
         if (!c->posenn_se || !ws.se) return fail(c, DAVO_ERR_NOT_READY, "`%s' exists in the feature-attention variant only (davo_set_posenn_se)", tensor);
         if (t == "cnv5_se") { src = ws.se->d_se.get(); n = NB * c->H2 * c->W2 * 512; }
@@ -162,7 +166,7 @@ int davo_debug_read(davo_ctx* c, const char* tensor, float* host_out, size_t n_f
     if (n != n_floats) return fail(c, DAVO_ERR_INVALID, "`%s' holds %zu floats, caller asked for %zu", tensor, n, n_floats);
     int rc = davo_memcpy_d2h(c, host_out, src, n * sizeof(float));
     if (rc) return rc;
-    const bool split = c->last_precision == 1 && t != "att_table" && t != "att_table_far" && t != "cnv7" && t != "cnv5_se_scale";
+    const bool split = c->last_precision == 1 && t != "att_table" && t != "att_table_far" && t != "se_desc" && t != "cnv7" && t != "cnv5_se_scale";
     if (split) {       // split-fp16 blocked -> plain float32 NHWC
         int ch = 8;
         const char* names[6] = {"cnv1", "cnv2", "cnv3", "cnv4", "cnv5", "cnv6"};

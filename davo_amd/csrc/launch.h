@@ -71,6 +71,12 @@ hipError_t launch_se_class_squeeze(bool fold, const uint8_t* d_img, const void* 
 hipError_t launch_se_depth_squeeze(bool fold, const float* d_depth, int B, int HW, const Variant& v, unsigned* d_partial,
                                    unsigned* d_counters, const float* w1, const float* b1, const float* w2, const float* b2,
                                    float* d_tab, unsigned* d_range_reset, int sel, hipStream_t s);
+// pooled flow-attention variants (att_source 14..17; se_pool.h): window sums into d_partial [B][2][pd.n_items][2], then the excitation
+// (one launch each; "fold_tails" does not apply) -> d_tab [B][3][19] and the descriptor d_desc [B][2][2 pd.n_cells]
+hipError_t launch_se_pool_squeeze(const void* d_flow, int flow_fmt, int B, int H, int W, const Variant& v, const PoolDev& pd, float* d_partial,
+                                  int sel, hipStream_t s);
+hipError_t launch_se_pool_excite(const float* d_partial, int B, const Variant& v, const PoolDev& pd, const float* w1, const float* b1,
+                                 const float* w2, const float* b2, float* d_tab, float* d_desc, unsigned* d_range_reset, int sel, hipStream_t s);
 // ld: 16 = split-fp16 8-channel layout (f16x3), 8 = float32 8-channel, 10 = the reference's 10-channel layout
 // att_source 13 (the depth-split flow attention) runs the depth-split form: d_depth (16-byte aligned), the far tables and the threshold are
 // required there and ignored everywhere else

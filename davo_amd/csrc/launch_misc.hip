@@ -11,6 +11,7 @@
 #include "owned.h"
 #include "posenn_se.h"
 #include "prologue.h"
+#include "se_pool.h"
 #include "window_gather.h"
 
 namespace davo {
@@ -124,6 +125,30 @@ hipError_t launch_se_depth_squeeze(bool fold, const float* d_depth, int B, int H
     else
         hipLaunchKernelGGL(se_depth_squeeze<false>, grid, dim3(256), 0, s, d_depth, HW, v, d_partial, d_counters, w1, b1, w2, b2, d_tab,
                            d_range_reset, sel);
+    return hipGetLastError();
+}
+
+hipError_t launch_se_pool_squeeze(const void* d_flow, int flow_fmt, int B, int H, int W, const Variant& v, const PoolDev& pd, float* d_partial,
+                                  int sel, hipStream_t s) {
+    if (!att_pooled(v.att_source) || !flow_fmt_ok(flow_fmt) || W % 4 || pd.n_items < 1 || !pd.items || !d_flow || !d_partial) return hipErrorInvalidValue;
+    const dim3 grid(pd.n_items, pairs_per_window(sel), B);
+    if (flow_fmt == FLOW_F16)
+        hipLaunchKernelGGL(se_pool_squeeze<flow_f16>, grid, dim3(256), 0, s, static_cast<const flow_f16*>(d_flow), H, W, v, sel, pd, d_partial);
+    else
+        hipLaunchKernelGGL(se_pool_squeeze<flow_f32>, grid, dim3(256), 0, s, static_cast<const float*>(d_flow), H, W, v, sel, pd, d_partial);
+    return hipGetLastError();
+}
+
+hipError_t launch_se_pool_excite(const float* d_partial, int B, const Variant& v, const PoolDev& pd, const float* w1, const float* b1,
+                                 const float* w2, const float* b2, float* d_tab, float* d_desc, unsigned* d_range_reset, int sel, hipStream_t s) {
+    const int a = v.att_source;
+    if (!att_pooled(a) || 2 * pd.n_cells != att_se_in(a) || 2 * pd.n_cells > POOL_MAX_D || !pd.cell_first || !pd.inv_div ||
+        !d_partial || !w1 || !b1 || !w2 || !b2 || !d_tab || !d_desc)
+        return hipErrorInvalidValue;
+    if (att_se_hidden(a) == NCLS)
+        hipLaunchKernelGGL(se_pool_excite<NCLS>, dim3(B, 3), dim3(64), 0, s, d_partial, pd, v, w1, b1, w2, b2, d_tab, d_desc, d_range_reset, sel);
+    else
+        hipLaunchKernelGGL(se_pool_excite<8>, dim3(B, 3), dim3(64), 0, s, d_partial, pd, v, w1, b1, w2, b2, d_tab, d_desc, d_range_reset, sel);
     return hipGetLastError();
 }
 

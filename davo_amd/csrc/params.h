@@ -38,7 +38,25 @@ struct Variant {
 // se_flow_far) on the same sums; a pixel of a source frame looks its class up in the near table where depth < depth_threshold (a trained
 // scalar), else in the far one.  It reads the depth planes like 11 and 12 but squeezes nothing from them; the target's map is ones.
 constexpr int ATT_DEPTH_SPLIT = 13;
-constexpr int SQ_REC = 24;          // class-table squeeze: words per (triplet, frame, chunk): 19 counts | 2 flow sums (or 3 rgb sums, or 1 depth sum)
+// 14..17 are the pooled flow-attention variants (davo.py:1181-1210; nets/attention_module.py:68-86, 137-167): se_flow's scope, transform and
+// target map (ones), but the descriptor is a grid of window means of the transformed flow (pool_plan.h: cell list per variant and
+// image size), D = 2 values per cell, dense D -> nh -> 19.  se_pool.h squeezes and excites them.
+//   14 -se_gp2x2_flow_nobottle   four quadrant means, 8 -> 19 -> 19 (davo.py:1181-1186)
+//   15 -se_spp21_flow            SPP levels [2, 1], 10 -> 8 -> 19  (:1193-1198)
+//   16 -se_spp2_flow             SPP level  [2],     8 -> 8 -> 19  (:1199-1204)
+//   17 -se_spp864_flow           SPP levels [8, 6, 4], 232 -> 8 -> 19 (:1205-1210; the graph `-se_spp_flow' builds too)
+constexpr int ATT_POOL_GP2X2 = 14, ATT_POOL_SPP21 = 15, ATT_POOL_SPP2 = 16, ATT_POOL_SPP864 = 17;
+constexpr int ATT_MAX = ATT_POOL_SPP864;              // largest davo_variant.att_source
+constexpr int POOL_MAX_D = 256;                       // descriptor entries a wave of the pooled excitation holds (4 per lane); 232 used
+__host__ __device__ inline bool att_pooled(int a) { return a >= ATT_POOL_GP2X2 && a <= ATT_POOL_SPP864; }
+// the context's pool plan on the device (pool_plan.h; built once per context): what se_pool.h's kernels take
+struct PoolDev {
+    const int* items;         // [n_items][4]: rows [y0, y1), columns [x0, x1) of a work item, inside the image; 16-byte aligned
+    const int* cell_first;    // [n_cells + 1]: cell c owns items [cell_first[c], cell_first[c + 1])
+    const float* inv_div;     // [n_cells]: reciprocal divisor of the cell's mean
+    int n_items, n_cells;
+};
+constexpr int SQ_REC = 24;         // class-table squeeze: words per (triplet, frame, chunk): 19 counts | 2 flow sums (or 3 rgb sums, or 1 depth sum)
 __host__ __device__ inline bool att_class_table(int a) { return a >= 4 && a <= 12; }
 // the target frame's rgb is masked by its own table (static_all and the with-target class-table sources)
 __host__ __device__ inline bool att_tgt_attended(int a) { return a == 3 || a == 6 || a == 8 || a == 10 || a == 12; }
@@ -48,8 +66,11 @@ __host__ __device__ inline bool att_flow_squeeze(int a) { return a == 1 || a == 
 __host__ __device__ inline bool att_desc_hist(int a) { return a == 4 || (a >= 7 && a <= 10); }   // descriptor holds the label histogram
 __host__ __device__ inline bool att_desc_rgb(int a) { return a == 5 || a == 6; }           // ... the rgb mean
 __host__ __device__ inline bool att_desc_flow(int a) { return a >= 7 && a <= 10; }         // ... the transformed flow mean
-__host__ __device__ inline int att_se_in(int a) { return a == 1 ? 2 : att_desc_depth(a) ? 1 : att_desc_rgb(a) ? 3 : a == 4 ? NCLS : NCLS + 2; }
-__host__ __device__ inline int att_se_hidden(int a) { return (a == 4 || a == 7 || a == 8) ? NCLS : 8; }
+__host__ __device__ inline int att_se_in(int a) {
+    if (att_pooled(a)) return a == ATT_POOL_SPP864 ? 232 : a == ATT_POOL_SPP21 ? 10 : 8;      // 2 x cells: 64 + 36 + 16 | 4 + 1 | 4
+    return a == 1 ? 2 : att_desc_depth(a) ? 1 : att_desc_rgb(a) ? 3 : a == 4 ? NCLS : NCLS + 2;
+}
+__host__ __device__ inline int att_se_hidden(int a) { return (a == 4 || a == 7 || a == 8 || a == ATT_POOL_GP2X2) ? NCLS : 8; }
 // frames (0 tgt, 1 src0, 2 src1) the squeeze covers: the target's table is ones for the `_wo_tgt' sources.  The depth sources sum
 // every plane once, the target's included: its sum enters both source frames' descriptors (davo.py:1109)
 __host__ __device__ inline int att_se_frames(int a) { return (att_tgt_attended(a) || att_desc_depth(a)) ? 3 : 2; }

@@ -81,6 +81,7 @@ const char* se_weight_name(int att_source, int k) {
         {"pose_exp_net/se_flow_near/bottleneck_fc/kernel", "pose_exp_net/se_flow_near/bottleneck_fc/bias",  // :1136-1155
          "pose_exp_net/se_flow_near/recover_fc/kernel", "pose_exp_net/se_flow_near/recover_fc/bias"}};
     if (att_source == ATT_DEPTH_SPLIT) return names[5][k & 3];
+    if (att_pooled(att_source)) return names[0][k & 3];      // scope se_flow (davo.py:1181-1210)
     const int scope = att_source == 4 ? 1 : att_desc_rgb(att_source) ? 2 : att_desc_depth(att_source) ? 4 : att_source >= 7 ? 3 : 0;
     return names[scope][k & 3];
 }
@@ -112,7 +113,7 @@ std::vector<std::string> needed_names(const Variant& v, int posenn_se) {
             n.push_back(std::string("pose_exp_net/pose/") + h + "/" + l + "/weights");
             n.push_back(std::string("pose_exp_net/pose/") + h + "/" + l + "/biases");
         }
-    if (v.att_source == 1 || att_class_table(v.att_source)) {
+    if (v.att_source == 1 || att_class_table(v.att_source) || att_pooled(v.att_source)) {
         for (int k = 0; k < 4; ++k) n.push_back(se_weight_name(v.att_source, k));
     } else if (v.att_source == ATT_DEPTH_SPLIT) {         // two se_flow MLPs and the threshold; none of se_flow/*_fc
         for (int k = 0; k < 4; ++k) n.push_back(se_weight_name(v.att_source, k));
@@ -155,6 +156,15 @@ bool expected_shape(const davo_ctx* c, const std::string& name, std::vector<int6
     else if (c->posenn_se && ends("/cnv5_se_attention/bottleneck_fc/bias")) *sh = {32};
     else if (c->posenn_se && ends("/cnv5_se_attention/recover_fc/kernel")) *sh = {32, 256};
     else if (c->posenn_se && ends("/cnv5_se_attention/recover_fc/bias")) *sh = {256};
+    else if (att_pooled(c->v.att_source) && name.compare(0, 21, "pose_exp_net/se_flow/") == 0) {
+        // the pooled flow-attention variants: [D, hidden] -> [hidden, 19] under se_flow's names (D = 2 x cells, params.h)
+        const int a = c->v.att_source, nin = att_se_in(a), nh = att_se_hidden(a);
+        if (ends("/bottleneck_fc/kernel")) *sh = {nin, nh};
+        else if (ends("/bottleneck_fc/bias")) *sh = {nh};
+        else if (ends("/recover_fc/kernel")) *sh = {nh, NCLS};
+        else if (ends("/recover_fc/bias")) *sh = {NCLS};
+        else return false;
+    }
     else if (is("pose_exp_net/se_flow/bottleneck_fc/kernel")) *sh = {2, 8};
     else if (is("pose_exp_net/se_flow/bottleneck_fc/bias")) *sh = {8};
     else if (is("pose_exp_net/se_flow/recover_fc/kernel")) *sh = {8, NCLS};

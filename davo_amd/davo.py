@@ -14,7 +14,7 @@ import numpy as np
 from . import _lib
 from .labels import LABEL_DTYPES, LABEL_FORMATS, check_label_format, labels_to_u8  # noqa: F401
 from .flow import FLOW_DTYPES, FLOW_FORMATS, check_flow_format, flow_from_f16, flow_to_f16  # noqa: F401
-from .version import ATT_SOURCE, NUM_SEG_CLASSES, parse_version, weight_shapes
+from .version import NUM_SEG_CLASSES, att_source_id, parse_version, weight_shapes
 
 
 DEPTH_THRESHOLD = "pose_exp_net/se_flow/depth_threshold"      # the rank-0 variable of `-se_flow_on_depthseg_seplayers'
@@ -595,7 +595,7 @@ def host_maps(cfg, img, seg, tables, depth=None, tables_far=None, thr=None):
     image = np.empty((3, B, H, W, 3), np.float32)
     for f, plane in enumerate((1, 0, 2)):                      # (tgt, src0, src1) -> strip slot / label plane src0, tgt, src1
         image[f] = unit[:, :, plane * W:(plane + 1) * W]
-        if cfg.tgt_attended if f == 0 else ATT_SOURCE[cfg.att_source] != 0:       # else the reference's tf.ones_like override
+        if cfg.tgt_attended if f == 0 else att_source_id(cfg.att_source) != 0:       # else the reference's tf.ones_like override
             a19[f] = tables[:, f]
             lab = seg[:, plane, :, :, 0]
             with np.errstate(invalid="ignore"):

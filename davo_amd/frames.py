@@ -18,7 +18,7 @@ import numpy as np
 from . import _lib
 from .flow import FLOW_FORMATS, check_flow_format
 from .labels import LABEL_FORMATS, check_label_format
-from .version import ATT_SOURCE
+from .version import att_source_id
 
 PAIRS = {"src0": 1, "src1": 2, "both": 3}
 
@@ -82,15 +82,15 @@ def frames_plan(H, W, N, pairs="both", att_source="se_flow", labels="f32", flow=
     """What a frame-layout batch of N windows reads (include/davo_hip.h: davo_frames_plan - the function the library's copies and
     its gather kernel are driven by; no GPU needed): ``{'frames', 'seg', 'depth', 'flow': (lo, hi), 'link_bytes': int}`` - frame
     ranges of the pixels, the label maps and the depth planes ((0, 0) where the source reads no depth), the flow planes, and the
-    bytes the host entry points send.  ``att_source``: a name of davo_amd.version.ATT_SOURCE or its number.  ``flow``: "f32", or
+    bytes the host entry points send.  ``att_source``: a name of davo_amd.version.ATT_SOURCE / POOLED_ATT_SOURCE or its number.  ``flow``: "f32", or
     "f16" for a binary16 engine (davo_frames_plan_fmt): half the flow's bytes in 'link_bytes', the same ranges."""
     if pairs not in PAIRS:
         raise ValueError("pairs must be 'both', 'src0' or 'src1', got %r" % (pairs,))
-    att = ATT_SOURCE[att_source] if isinstance(att_source, str) else int(att_source)
+    att = att_source_id(att_source) if isinstance(att_source, str) else int(att_source)
     r = (ctypes.c_int * 8)()
     nbytes = ctypes.c_longlong(0)
     lab = LABEL_FORMATS[check_label_format(labels)]
-    if check_flow_format(flow) == "f32":
+    if check_flow_format(flow) == "f32" and att <= 13:         # (davo_frames_plan keeps the range it was published with, 0..13)
         rc = _lib.lib().davo_frames_plan(int(H), int(W), int(N), PAIRS[pairs], att, lab, r, ctypes.byref(nbytes))
     else:
         rc = _lib.lib().davo_frames_plan_fmt(int(H), int(W), int(N), PAIRS[pairs], att, lab, FLOW_FORMATS[flow], r, ctypes.byref(nbytes))

@@ -31,7 +31,16 @@ ATT_SOURCE = {"ones": 0, "se_flow": 1, "static_src": 2, "static_all": 3,
               "se_depth_wo_tgt_to_seg": 11, "se_depth_to_seg": 12,
               # the flow-driven attention evaluated by two SE MLPs, selected per pixel by depth < depth_threshold (davo.py:1136-1155)
               "se_flow_depthseg_sep": 13}
+# pooled flow attention (davo.py:1181-1186, 1193-1210): se_flow whose descriptor is a grid of window means (gp2x2 | SPP levels).  They
+# continue davo_variant.att_source's numbering in a table of their own: ATT_SOURCE's extent, 0..13, is pinned by
+# tests/test_depthseg_attention.py.  att_source_id() resolves a name of either table.
+POOLED_ATT_SOURCE = {"se_gp2x2_flow_nobottle": 14, "se_spp21_flow": 15, "se_spp2_flow": 16, "se_spp864_flow": 17}
 MASK_INFO = {"none": 0, "att": 1}
+
+
+def att_source_id(name):
+    """davo_variant.att_source of an attention source's name (ATT_SOURCE or POOLED_ATT_SOURCE)."""
+    return ATT_SOURCE[name] if name in ATT_SOURCE else POOLED_ATT_SOURCE[name]
 
 
 class UnsupportedVariantError(NameError):
@@ -47,7 +56,7 @@ class VariantConfig:
     se_act: str              # relu | tanh | lrelu  (davo.py:1077-1085)
     norm_flow: bool          # (f-0.32140523)/15.384229 before abs (davo.py:1089-1091)
     abs_mode: str            # none | h | v | all  (davo.py:1094-1102)
-    att_source: str          # a key of ATT_SOURCE
+    att_source: str          # a key of ATT_SOURCE or POOLED_ATT_SOURCE
     mask_rgb: bool           # rgb_k *= att_k          (davo.py:1419-1423 / 1447-1450)
     mask_info: bool          # flow_k *= att_k         (davo.py:1430-1434)
     posenn_se: str = "none"  # none | insert: se_block on cnv5 ahead of each head's cnv6 (davo.py:1010-1011, nets/posenn.py:225-228);
@@ -78,7 +87,7 @@ class VariantConfig:
         """Field order of ``davo_variant`` in include/davo_hip.h."""
         return (self.cin_per_frame, self.cnv6_out, SE_ACT[self.se_act],
                 int(self.norm_flow), ABS_MODE[self.abs_mode],
-                ATT_SOURCE[self.att_source], int(self.mask_rgb), int(self.mask_info))
+                att_source_id(self.att_source), int(self.mask_rgb), int(self.mask_info))
 
 
 # attention branches of davo.py:1117-1384 that come BEFORE "-se_flow" in the elif
@@ -88,7 +97,8 @@ _BEFORE_SE_FLOW = ("-se_flow_on_depthseg_sharedlayers", "-se_flow_on_depthseg_se
 # the one of them that runs: se_flow_near / se_flow_far tables selected per pixel by depth < depth_threshold (davo.py:1136-1155)
 _DEPTHSEG_SEP = "-se_flow_on_depthseg_seplayers"
 # branches AFTER "-se_flow" and before "-no_segmask", in the reference's order; the ones in _CLASS_TABLE_SOURCES run here,
-# the rest need disparity / SPP / gp2x2 pooling or an se_block whose map is not a class table
+# so do the pooled flow sources of _POOLED_FLOW_SOURCES; the rest need disparity, the 8-unit gp2x2 / `-se_spp_flow' strings (pinned as
+# rejected) or an se_block / se_spp_block whose map is not a class table
 _AFTER_SE_FLOW = ("-se_gp2x2_flow_nobottle", "-se_gp2x2_flow", "-se_spp21_flow", "-se_spp2_flow",
                   "-se_spp_flow", "-se_spp864_flow", "-se_depth_wo_tgt_to_seg", "-se_depth_to_seg",
                   "-se_depth_wo_tgt", "-se_depth", "-se_disp_wo_tgt_to_seg", "-se_disp_to_seg",
@@ -109,18 +119,27 @@ _CLASS_TABLE_SOURCES = {"-se_seg_wo_tgt": "se_seg_wo_tgt",                      
                         "-se_SegFlow_to_seg": "se_SegFlow_to_seg",                  # :1367-1374
                         "-se_depth_wo_tgt_to_seg": "se_depth_wo_tgt_to_seg",        # :1211-1219
                         "-se_depth_to_seg": "se_depth_to_seg"}                      # :1220-1227
+# (substring, att_source) of the pooled flow-attention branches that run (davo.py:1181-1186, 1193-1210): se(se_input_flows[i], "se_flow",
+# ..., mode='gp2x2' | 'spp').  `-se_gp2x2_flow_nobottle' stands before the bare `-se_gp2x2_flow' in _AFTER_SE_FLOW, as in the reference;
+# `-se_spp864_flow' is the reference's own alias of `-se_spp_flow''s graph (davo.py:1205).  The bare `-se_gp2x2_flow' and `-se_spp_flow' stay
+# rejected.  The scope is se_flow, so use_se_flow holds and both target maps are ones (davo.py:1404-1412).
+_POOLED_FLOW_SOURCES = {"-se_gp2x2_flow_nobottle": "se_gp2x2_flow_nobottle", "-se_spp21_flow": "se_spp21_flow",
+                        "-se_spp2_flow": "se_spp2_flow", "-se_spp864_flow": "se_spp864_flow"}
 _TGT_ATTENDED = ("static_all", "se_rgb_to_seg", "se_SegFlow_to_seg", "se_SegFlow_to_seg_8", "se_depth_to_seg")
 _DEPTH_SOURCES = ("se_depth_wo_tgt_to_seg", "se_depth_to_seg", "se_flow_depthseg_sep")
 _SE_SCOPE = {"se_flow": "se_flow", "se_seg_wo_tgt": "se_seg", "se_rgb_wo_tgt_to_seg": "se_rgb", "se_rgb_to_seg": "se_rgb",
              "se_SegFlow_to_seg_wo_tgt": "se_segflow", "se_SegFlow_to_seg": "se_segflow",
              "se_SegFlow_to_seg_8_wo_tgt": "se_segflow", "se_SegFlow_to_seg_8": "se_segflow",
-             "se_depth_wo_tgt_to_seg": "se_depth", "se_depth_to_seg": "se_depth"}
+             "se_depth_wo_tgt_to_seg": "se_depth", "se_depth_to_seg": "se_depth",
+             "se_gp2x2_flow_nobottle": "se_flow", "se_spp21_flow": "se_flow", "se_spp2_flow": "se_flow", "se_spp864_flow": "se_flow"}
 # SE dense layer widths (in, hidden); the recovery layer always has the 19 classes
 _SE_WIDTHS = {"se_flow": (2, 8), "se_seg_wo_tgt": (NUM_SEG_CLASSES, NUM_SEG_CLASSES), "se_rgb_wo_tgt_to_seg": (3, 8),
               "se_rgb_to_seg": (3, 8), "se_SegFlow_to_seg_wo_tgt": (NUM_SEG_CLASSES + 2, NUM_SEG_CLASSES),
               "se_SegFlow_to_seg": (NUM_SEG_CLASSES + 2, NUM_SEG_CLASSES),
               "se_SegFlow_to_seg_8_wo_tgt": (NUM_SEG_CLASSES + 2, 8), "se_SegFlow_to_seg_8": (NUM_SEG_CLASSES + 2, 8),
-              "se_depth_wo_tgt_to_seg": (1, 8), "se_depth_to_seg": (1, 8)}
+              "se_depth_wo_tgt_to_seg": (1, 8), "se_depth_to_seg": (1, 8),
+              # pooled flow attention: D = 2 values per cell (4 | 4 + 1 | 4 | 64 + 36 + 16 cells); `_nobottle' is layer_channels [19, 19]
+              "se_gp2x2_flow_nobottle": (8, NUM_SEG_CLASSES), "se_spp21_flow": (10, 8), "se_spp2_flow": (8, 8), "se_spp864_flow": (232, 8)}
 
 
 def parse_version(version):
@@ -221,6 +240,8 @@ def parse_version(version):
                 raise UnsupportedVariantError("version `%s': `%s' behind `%s' is not a number." % (v, m.group(1), _DEPTHSEG_SEP)) from None
     elif "-se_flow" in v:
         att_source = "se_flow"
+    elif after in _POOLED_FLOW_SOURCES:
+        att_source = _POOLED_FLOW_SOURCES[after]
     elif after in _CLASS_TABLE_SOURCES:
         att_source = _CLASS_TABLE_SOURCES[after]
     elif after is not None:

@@ -60,7 +60,14 @@ typedef struct {
                              * pixel of a source frame the near or the far table by depth < depth_threshold (float32, strict; a NaN
                              * depth is far); the target's map is ones.  It reads the depth planes too (`_depth' entry points):
                              *  13 -se_flow_on_depthseg_seplayers  flow mean 2 -> 8 -> 19 twice, tgt=1   (scopes se_flow_near,
-                             *                                   se_flow_far; scalar pose_exp_net/se_flow/depth_threshold) */
+                             *                                   se_flow_far; scalar pose_exp_net/se_flow/depth_threshold)
+                             * pooled flow attention (davo.py:1181-1210; nets/attention_module.py:68-86, 137-167): se_flow's scope,
+                             * transform and target map (ones); the descriptor is a grid of window means of the transformed flow
+                             * (davo_pool_plan below), 2 values per cell, dense D -> nh -> 19:
+                             *  14 -se_gp2x2_flow_nobottle      four quadrants, 8 -> 19 -> 19            (davo.py:1181-1186)
+                             *  15 -se_spp21_flow               SPP levels [2, 1], 10 -> 8 -> 19          (:1193-1198)
+                             *  16 -se_spp2_flow                SPP level [2], 8 -> 8 -> 19               (:1199-1204)
+                             *  17 -se_spp864_flow              SPP levels [8, 6, 4], 232 -> 8 -> 19      (:1205-1210) */
     int32_t mask_rgb;       /* rgb_k *= att_k                          (davo.py:1419-1423)        */
     int32_t mask_info;      /* flow_k *= att_k  (-segmask_all)         (davo.py:1430-1434)        */
 } davo_variant;
@@ -290,7 +297,8 @@ int davo_get_pairs(const davo_ctx* ctx);
  * the bytes the host entry points copy for it; either pointer may be NULL.  DAVO_ERR_INVALID for an argument out of range.
  * davo_frames_plan_fmt is the same with the flow format as an argument (DAVO_FLOW_F32 or DAVO_FLOW_F16: 8 or 4 bytes per
  * pixel and flow plane in *link_bytes; 638,976 per window for the line above with byte labels and binary16 flow);
- * davo_frames_plan means flow_fmt = DAVO_FLOW_F32.
+ * davo_frames_plan means flow_fmt = DAVO_FLOW_F32 and takes att_source 0..13, the range it was published with; the pooled
+ * flow-attention sources (14..17), which read what att_source 1 reads, are planned by davo_frames_plan_fmt.
  * There are no `_frames' forms of davo_calibrate, davo_forward_features and davo_forward_heat. */
 int davo_forward_frames(davo_ctx* ctx, int N, const uint8_t* frames, const float* flow2, const float* seg,
                         const float* depth, float* pose_out);
@@ -300,6 +308,15 @@ int davo_forward_device_frames(davo_ctx* ctx, int N, const void* d_frames, const
                                const void* d_depth, void* d_pose, float* elapsed_ms);
 int davo_frames_plan(int H, int W, int N, int pairs, int att_source, int label_fmt, int* ranges, long long* link_bytes);
 int davo_frames_plan_fmt(int H, int W, int N, int pairs, int att_source, int label_fmt, int flow_fmt, int* ranges, long long* link_bytes);
+
+/* The pooled flow-attention variants' window geometry (att_source 14..17) as a function (no context, no device): the cells of the
+ * SE descriptor of an H x W frame, in descriptor order (entries 2 i, 2 i + 1 are the x and y means of cell i).  *n_cells receives
+ * their number (D / 2; 0 for a source that does not pool); rects, where not NULL, [n][4] = rows [y0, y1) and columns [x0, x1) of
+ * each cell cut to the real image (0, 0, 0, 0 for a cell that lies wholly in tf.pad's zeros); inv_div, where not NULL, [n] the
+ * reciprocal of the cell's divisor: its own pixel count for gp2x2, for SPP the window height times its columns inside the
+ * tf.pad-ded map - tf.pad's zeros count, SAME padding does not (nets/attention_module.py:68-77, 137-167).  Call it once with NULL
+ * arrays for the count (at most 116).  DAVO_ERR_INVALID for an argument out of range. */
+int davo_pool_plan(int H, int W, int att_source, int* n_cells, int* rects, float* inv_div);
 
 /* Feature export.  Replaces DAVO.inference(sess, mode='feature') (davo.py:1553-1569), the call generate_feature_map.py:183-260
  * makes to draw the class-attention table and the cnv6 feature maps: the poses of davo_forward and, from the same forward, the
@@ -633,7 +650,8 @@ int davo_set_impl(davo_ctx* ctx, int impl);
 
 /* Copy an intermediate of the LAST forward to host (float32, NHWC, pair-image major = 2B images):
  * "att_table" [B,3,19] (att_source 13: the near MLP's tables; "att_table_far" [B,3,19] holds the far MLP's and returns
- * DAVO_ERR_INVALID on every other variant), "packed" [2B,H,W,8|10], "cnv1".."cnv5", "cnv6" [.., 2*cnv6_out]
+ * DAVO_ERR_INVALID on every other variant), "se_desc" [B,2,D] (att_source 14..17 only: the pooled SE descriptors of src0, src1 as the
+ * dense layer reads them; a frame no selected pair reads keeps what it held), "packed" [2B,H,W,8|10], "cnv1".."cnv5", "cnv6" [.., 2*cnv6_out]
  * (rotation | translation), "cnv7" [.., 512].  With davo_set_posenn_se(ctx, 1) also "cnv5_se_scale" [2B,2,256] (row 0 = s_r,
  * row 1 = s_r * s_t) and "cnv5_se" [2B,H/4,W/4,512] (cnv6's rotation input | its translation input).  After a davo_forward_heat
  * with the heat export on also "heat_sum" [2,n,H/4,W/4]: the channel sums (rotation | translation) the planes of the piece exported
