@@ -38,7 +38,7 @@ def lib_path(suffix=None):
 LIB_PATH = lib_path()
 
 EXPORTS = (
-    "davo_create", "davo_set_posenn_se", "davo_load_weight", "davo_weights_missing", "davo_forward", "davo_forward_device", "davo_submit", "davo_wait", "davo_pending",
+    "davo_create", "davo_set_posenn_se", "davo_set_posenn_topology", "davo_load_weight", "davo_weights_missing", "davo_forward", "davo_forward_device", "davo_submit", "davo_wait", "davo_pending",
     "davo_forward_depth", "davo_forward_device_depth", "davo_submit_depth", "davo_calibrate_depth",
     "davo_last_error", "davo_destroy", "davo_device_malloc", "davo_device_free", "davo_memcpy_h2d",
     "davo_memcpy_d2h", "davo_synchronize", "davo_set_stream", "davo_set_inflight", "davo_profile_enable",
@@ -55,6 +55,7 @@ EXPORTS = (
 COMM_ID_BYTES = 128
 LABELS_F32, LABELS_U8 = 0, 1          # DAVO_LABELS_F32, DAVO_LABELS_U8 (davo_set_label_format)
 FLOW_F32, FLOW_F16 = 0, 1             # DAVO_FLOW_F32, DAVO_FLOW_F16 (davo_set_flow_format)
+POSENN_PAIRS, POSENN_TRIPLET = 0, 1   # DAVO_POSENN_PAIRS, DAVO_POSENN_TRIPLET (davo_set_posenn_topology)
 
 
 class DavoVariant(ctypes.Structure):
@@ -182,6 +183,7 @@ def _load():
     vp, i, f32p = ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(ctypes.c_float)
     L.davo_create.argtypes = [ctypes.POINTER(vp), i, i, i, i, ctypes.POINTER(DavoVariant)]
     L.davo_set_posenn_se.argtypes = [vp, i]
+    L.davo_set_posenn_topology.argtypes = [vp, i]
     L.davo_load_weight.argtypes = [vp, ctypes.c_char_p, f32p, ctypes.POINTER(ctypes.c_int64), i]
     L.davo_weights_missing.argtypes = [vp]
     L.davo_forward.argtypes = [vp, i, vp, vp, vp, vp]

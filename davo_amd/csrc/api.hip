@@ -165,6 +165,7 @@ int davo_set_posenn_se(davo_ctx* c, int mode) {
                     "(it changes the variant's variables and cnv6's layout)");
     if (mode && c->v.att_source != 0)
         return fail(c, DAVO_ERR_INVALID, "the feature-attention PoseNN (`-se_insert') runs with att_source 0 (`-no_segmask') only, got %d", c->v.att_source);
+    if (mode && triplet(c)) return fail(c, DAVO_ERR_INVALID, "the three-frame PoseNN (davo_set_posenn_topology) has no feature-attention form");
     HIP_TRY(c, hipSetDevice(c->device));
     c->posenn_se = mode;
     // the heads read different inputs now: cnv6 becomes one group per head, the grouped path cnv7 runs on (forward.hip)
@@ -176,6 +177,31 @@ int davo_set_posenn_se(davo_ctx* c, int mode) {
         if (mode) { int rc = alloc_se_workspace(c, &s); if (rc) return rc; }
         else s.se.reset();
     }
+    c->last_slot = 0;
+    return DAVO_OK;
+}
+
+int davo_set_posenn_topology(davo_ctx* c, int topology) {
+    if (!c) return DAVO_ERR_INVALID;
+    if (topology != DAVO_POSENN_PAIRS && topology != DAVO_POSENN_TRIPLET)
+        return fail(c, DAVO_ERR_INVALID, "topology must be DAVO_POSENN_PAIRS (0) or DAVO_POSENN_TRIPLET (1), got %d", topology);
+    if (!c->weights.empty() || c->forward_seen)
+        return fail(c, DAVO_ERR_INVALID, "davo_set_posenn_topology must be called before the first davo_load_weight and the first forward "
+                    "(it changes the shapes of cnv1 and pred and cnv1's layout)");
+    if (topology == DAVO_POSENN_TRIPLET) {
+        if (att_reads_depth(c->v.att_source))
+            return fail(c, DAVO_ERR_INVALID, "the three-frame PoseNN has no form of the depth sources (att_source 11..13, got %d)", c->v.att_source);
+        if (c->posenn_se)
+            return fail(c, DAVO_ERR_INVALID, "the three-frame PoseNN has no feature-attention form: davo_set_posenn_se(ctx, 1) is set");
+        if (c->pairs != PAIRS_BOTH)
+            return fail(c, DAVO_ERR_INVALID, "the three-frame PoseNN yields both poses from one pass: davo_set_pairs must be DAVO_PAIRS_BOTH, is %d", c->pairs);
+        if (c->impl != 0) return fail(c, DAVO_ERR_INVALID, "the three-frame PoseNN has no direct-convolution form: davo_set_impl(ctx, 1) is set");
+        if (c->fx_on || c->heat)
+            return fail(c, DAVO_ERR_INVALID, "the three-frame PoseNN has no feature or heat export: switch the exports off first");
+    }
+    c->topology = topology;
+    // cnv1 reads 16 packed channels (prologue.h, mask_pack3) instead of 8; every other layer is the same, on B images instead of 2 B
+    init_layer(c->L[0], "cnv1", 7, 2, 1, topology == DAVO_POSENN_TRIPLET ? 16 : 8, 16, 1);
     c->last_slot = 0;
     return DAVO_OK;
 }
@@ -424,6 +450,7 @@ int davo_set_option(davo_ctx* c, const char* key, int value) {
     }
     else if (k == "patch_cnv2") c->opt_patch_cnv2 = value != 0;
     else if (k == "patch_cnv3") c->opt_patch_cnv3 = value != 0;
+    else if (k == "patch_cnv1_t") c->opt_patch_cnv1_t = value != 0;
     else if (k == "fold_tails") c->opt_fold_tails = value < 0 ? -1 : (value > 2 ? 1 : value);
     else if (k == "deep_ring") c->opt_deep_ring = value != 0;
     else if (k == "wave128") c->opt_wave128 = value < 0 ? 0 : (value > 3 ? 3 : value);      // 3: cnv4 on conv_igemm_h3w128 whatever the round count (test hook)
@@ -464,6 +491,8 @@ int davo_set_pairs(davo_ctx* c, int pairs) {
     if (!c) return DAVO_ERR_INVALID;
     if (pairs != DAVO_PAIRS_SRC0 && pairs != DAVO_PAIRS_SRC1 && pairs != DAVO_PAIRS_BOTH)
         return fail(c, DAVO_ERR_INVALID, "pairs must be DAVO_PAIRS_SRC0 (1), DAVO_PAIRS_SRC1 (2) or DAVO_PAIRS_BOTH (3), got %d", pairs);
+    if (triplet(c) && pairs != DAVO_PAIRS_BOTH)
+        return fail(c, DAVO_ERR_INVALID, "the three-frame PoseNN yields both poses from one pass: pairs must be DAVO_PAIRS_BOTH (3), got %d", pairs);
     c->pairs = pairs;              // batches in flight and their re-issues keep theirs (Ticket::pairs)
     return DAVO_OK;
 }
@@ -472,6 +501,7 @@ int davo_get_pairs(const davo_ctx* c) { return c ? c->pairs : DAVO_ERR_INVALID; 
 
 int davo_set_impl(davo_ctx* c, int impl) {
     if (!c || (impl != 0 && impl != 1)) return fail(c, DAVO_ERR_INVALID, "impl must be 0 (mfma) or 1 (direct)");
+    if (impl && triplet(c)) return fail(c, DAVO_ERR_INVALID, "impl 1 (direct convolutions) has no three-frame PoseNN form");
     c->impl = impl;
     return DAVO_OK;
 }

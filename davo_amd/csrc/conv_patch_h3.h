@@ -296,6 +296,141 @@ __global__ __launch_bounds__(cp1::THREADS, 3) void conv_patch_cnv1_h3(ConvPatchP
     }
 }
 
+// ---- cnv1 of the three-frame PoseNN (7x7, stride 2, 16 packed input channels -> 16) ------------------
+// The input is [NB][H][W][16 hi | 16 lo] halves, 64 B per pixel (prologue.h, mask_pack3).  K doubles against the 8-channel
+// kernel above: 28 steps of v_mfma_f32_16x16x32_f16, whose hi and lo weight fragments would be 224 registers per lane, and a
+// patch of both channel halves would be 86 KB.  So a tile runs as TWO PASSES over the kernel above's patch, its layout and
+// its fragment addressing unchanged: pass 0 stages channels 0..7 (tgt | src0 | flow0: the 16-byte units at byte 0 and 32 of
+// a pixel) and walks the 14 steps with that half's fragments from registers, pass 1 re-fills the same 43 KB with channels
+// 8..15 (src1 | flow1 | 0: the units at byte 16 and 48) and walks them again into the same accumulators, its fragments read
+// from LDS (28 KB, copied once per workgroup; lane-contiguous 16-byte reads, no bank conflicts).  72 KB of LDS and 112
+// resident weight registers: two workgroups per CU.  Pass 1's fill is exposed to its own workgroup (the buffer is the one
+// pass 0 just read); the tile after it is prefetched under the stores as before.
+// Every unit of the patch is written by every fill - a pixel's, or the zero line's outside the image and beyond column 36 -
+// so the dummy tap kx = 7 reads zeros, never stale LDS.  Same hi/lo split, three MFMAs per step into one float32
+// accumulator; the sum runs half by half, so it agrees with the implicit GEMM's (tap-pair by tap-pair) to rounding.
+__global__ __launch_bounds__(cp1::THREADS, cp1t::PER_CU) void conv_patch_cnv1t_h3(ConvPatchParams p) {
+    using namespace cp1;
+    extern __shared__ __attribute__((aligned(16))) uint8_t smem_p1t[];
+    uint8_t* patch = smem_p1t;                 // [2][PH][2][UNITS] x 16 B, one channel half at a time
+    uint8_t* wlds = smem_p1t + cp1t::WLDS;     // [STEPS][2][64] x 16 B: the second half's B fragments
+
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    half8 wreg[STEPS][2];                      // the first half's, resident
+#pragma unroll
+    for (int st = 0; st < STEPS; ++st) {
+        wreg[st][0] = *reinterpret_cast<const half8*>(p.w + ((size_t)(st * 2 + 0) * 64 + lane) * 16);
+        wreg[st][1] = *reinterpret_cast<const half8*>(p.w + ((size_t)(st * 2 + 1) * 64 + lane) * 16);
+    }
+    for (int i = tid; i < cp1t::WHALF / 16; i += THREADS)
+        *reinterpret_cast<float4*>(wlds + i * 16) = *reinterpret_cast<const float4*>(p.w + cp1t::WHALF + (size_t)i * 16);
+    __builtin_amdgcn_s_waitcnt((7 << 4) | (15 << 8));          // as in conv_patch_cnv1_h3: the weight loads are waited for here
+
+    const int r = lane & 15, kq = lane >> 4;
+    const float bv = p.bias[r] * p.bias_scale;
+    const int a_lane = (kq & 1) * ROWB + (r + (kq >> 1)) * 16;
+    const uint8_t* a0 = patch + (2 * (2 * wave) * 2) * ROWB + a_lane;
+    const uint8_t* wl = wlds + lane * 16;
+
+    // stage channel half hf of one tile's patch by LDS-DMA: one wave-instruction = 64 units = one py of one plane, both parities
+    auto issue_patch = [&](const TileCoord& tc, int hf) {
+        const int iy_base = tc.ty * TH * 2 - p.pad_t, ix_base = tc.tx * TW * 2 - p.pad_l;
+        const uint8_t* xin = p.x + (size_t)tc.n * p.H * p.W * 64;
+        const int par = lane >> 5, px2 = lane & 31;
+        const int ix = ix_base + 2 * px2 + par;
+        const bool okx = px2 * 2 + par < PW && (unsigned)ix < (unsigned)p.W && !CP_DBG(1);
+        const unsigned offx = (unsigned)ix * 64u + (unsigned)hf * 16u;
+        for (int k = wave; k < 2 * PH; k += 4) {
+            const int plane = k >= PH ? 1 : 0;
+            const int iy = iy_base + k - plane * PH;                    // uniform
+            const bool ok = okx && (unsigned)iy < (unsigned)p.H;
+            const uint8_t* src = patch_src(ok, xin, (unsigned)(iy * p.W) * 64u + offx + plane * 32, p.zeros);
+            __builtin_amdgcn_global_load_lds((gptr_t*)src, (lptr_t*)(patch + k * 1024), 16, 0, 0);
+        }
+    };
+
+    const TileWalk tw = tile_walk(p.ntiles);
+    int t = tw.first;
+    float vmax = 0.f;
+    TileCoord tc = tile_coord(t, p.tiles_x, p.tiles_y);
+    const TileCoord ts = tile_coord(tw.step, p.tiles_x, p.tiles_y);
+    if (t < tw.end) issue_patch(tc, 0);
+    while (t < tw.end) {
+        const int n = tc.n;
+        const int oy0 = tc.ty * TH, ox0 = tc.tx * TW;
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __syncthreads();                                       // pass 0's patch (and, the first time, the LDS fragments) are in place
+
+        f32x4 acc0 = {bv, bv, bv, bv}, acc1 = acc0;
+#pragma unroll
+        for (int step = 0; step < STEPS; ++step) {
+            const int aoff = (step >> 1) * 2 * ROWB + (step & 1) * 32;
+            const half8 bh = wreg[step][0], bl = wreg[step][1];
+            const half8 ah0 = lds_frag(a0 + aoff), al0 = lds_frag(a0 + aoff + PLANE);
+            const half8 ah1 = lds_frag(a0 + 4 * ROWB + aoff), al1 = lds_frag(a0 + 4 * ROWB + aoff + PLANE);
+            acc0 = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah0, bh, acc0, 0, 0, 0);
+            acc1 = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah1, bh, acc1, 0, 0, 0);
+            acc0 = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah0, bl, acc0, 0, 0, 0);
+            acc1 = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah1, bl, acc1, 0, 0, 0);
+            acc0 = __builtin_amdgcn_mfma_f32_16x16x32_f16(al0, bh, acc0, 0, 0, 0);
+            acc1 = __builtin_amdgcn_mfma_f32_16x16x32_f16(al1, bh, acc1, 0, 0, 0);
+        }
+        __syncthreads();                                       // every wave is done reading pass 0's patch
+        issue_patch(tc, 1);
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __syncthreads();
+#pragma unroll
+        for (int step = 0; step < STEPS; ++step) {
+            const int aoff = (step >> 1) * 2 * ROWB + (step & 1) * 32;
+            const half8 bh = lds_frag(wl + (step * 2 + 0) * 1024), bl = lds_frag(wl + (step * 2 + 1) * 1024);
+            const half8 ah0 = lds_frag(a0 + aoff), al0 = lds_frag(a0 + aoff + PLANE);
+            const half8 ah1 = lds_frag(a0 + 4 * ROWB + aoff), al1 = lds_frag(a0 + 4 * ROWB + aoff + PLANE);
+            acc0 = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah0, bh, acc0, 0, 0, 0);
+            acc1 = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah1, bh, acc1, 0, 0, 0);
+            acc0 = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah0, bl, acc0, 0, 0, 0);
+            acc1 = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah1, bl, acc1, 0, 0, 0);
+            acc0 = __builtin_amdgcn_mfma_f32_16x16x32_f16(al0, bh, acc0, 0, 0, 0);
+            acc1 = __builtin_amdgcn_mfma_f32_16x16x32_f16(al1, bh, acc1, 0, 0, 0);
+        }
+        __syncthreads();                                       // ... pass 1's
+        const int tnext = t + tw.step;
+        tc = tile_next(tc, ts, p.tiles_x, p.tiles_y);
+        if (tnext < tw.end) issue_patch(tc, 0);                // the next tile's first half flies under this tile's stores
+
+        // ---- epilogue: conv_patch_cnv1_h3's (the output is the same 16-channel blocked tensor)
+        const bool odd = r & 1;
+        const unsigned sel = odd ? 0x03020706u : 0x05040100u;
+        const int choff = odd ? 32 + (r - 1) * 2 : r * 2;
+        const bool interior = oy0 + TH <= p.Ho && ox0 + TW <= p.Wo;
+#pragma unroll
+        for (int sub = 0; sub < 2; ++sub) {
+            const int oy = oy0 + 2 * wave + sub;
+            if (!interior && oy >= p.Ho) continue;
+            uint8_t* __restrict__ orow = p.y + (((size_t)n * p.Ho + oy) * p.Wo + ox0 + 4 * kq) * 64 + choff;
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                float v = fmaxf((sub == 0 ? acc0[i] : acc1[i]) * p.out_scale, 0.f);
+                const bool ok = interior || ox0 + 4 * kq + i < p.Wo;
+                if (ok) vmax = fmaxf(vmax, v);
+                v = fminf(v, 65504.f);
+                const _Float16 hi = (_Float16)v;
+                const _Float16 lo = (_Float16)(v - (float)hi);
+                const unsigned x = (unsigned)__builtin_bit_cast(unsigned short, hi) |
+                                   ((unsigned)__builtin_bit_cast(unsigned short, lo) << 16);
+                const unsigned xn = (unsigned)__builtin_amdgcn_mov_dpp((int)x, 0xB1, 0xF, 0xF, true);   // quad_perm [1,0,3,2]
+                if (ok && !CP_DBG(2)) *reinterpret_cast<unsigned*>(orow + i * 64) = __builtin_amdgcn_perm(xn, x, sel);
+            }
+        }
+        t = tnext;
+    }
+    if (p.range) {
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) vmax = fmaxf(vmax, __shfl_xor(vmax, o, 64));
+        range_note(p.range, vmax, lane == 0);
+    }
+}
+
 // ---- cnv2 (5x5, stride 2, 16 -> 32 channels) from an LDS patch ------------------------------------
 // As an implicit GEMM cnv2 was bound by its gather (13 chunks x 128-byte rows assembled from 16-byte pieces of two taps:
 // 0.043 ms at B=32, 0.028 with the loads pointed at one line, 0.003 of it matrix time).  Here a workgroup stages the

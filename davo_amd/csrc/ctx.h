@@ -233,7 +233,10 @@ struct davo_ctx {
     davo::DevMem<float> d_pool_inv_div;
     davo::PoolDev pool{};
     int posenn_se = 0;                         // davo_set_posenn_se: 0 none | 1 insert - an SE block on cnv5 ahead of each head's cnv6 (posenn_se.h); cnv6 is then a two-group layer
-    bool forward_seen = false;                 // a forward has been issued (davo_set_posenn_se is refused from then on)
+    int topology = DAVO_POSENN_PAIRS;          // davo_set_posenn_topology: DAVO_POSENN_TRIPLET = one (tgt, src0, src1) image per window through cnv1..cnv7 (cnv1 at 16 packed
+                                               // channels, B images a batch), pred six columns wide, the unfused two-pass pose head (forward.hip)
+    bool opt_patch_cnv1_t = true;              // three-frame PoseNN, f16x3: "patch_cnv1_t" - cnv1 from an LDS-staged 16-channel patch (conv_patch_cnv1t_h3) instead of the implicit GEMM at cin = 16
+    bool forward_seen = false;                 // a forward has been issued (davo_set_posenn_se and davo_set_posenn_topology are refused from then on)
     int label_fmt = davo::LABELS_F32;          // davo_set_label_format: what every `seg' argument points at, and what plane_bytes().seg sizes
     int flow_fmt = davo::FLOW_F32;             // davo_set_flow_format: what every `flow' argument points at, and what plane_bytes().flow sizes
     bool inputs_seen = false;                  // an entry point has taken inputs (davo_set_label_format and davo_set_flow_format are refused from then on)
@@ -249,7 +252,7 @@ struct davo_ctx {
     bool pred_ready = false;                   // pose head kernels on the device (every mode)
     davo::ConvLayer L[7];                      // cnv1..cnv5, cnv6 (fused), cnv7 (grouped)
     davo::DevMem<float> d_wpred, d_bpred;
-    davo::DevMem<uint8_t> d_w1patch;           // cnv1 B fragments for conv_patch_cnv1_h3
+    davo::DevMem<uint8_t> d_w1patch;           // cnv1 B fragments for conv_patch_cnv1_h3 (three-frame PoseNN: for conv_patch_cnv1t_h3)
     davo::DevMem<uint8_t> d_w2patch;           // cnv2 B fragments for conv_patch_cnv2_h3
     davo::DevMem<float> d_w1patch_f32, d_w2patch_f32, d_w3patch_f32;      // float32 mode: cnv1 / cnv2 / cnv3 weights in the patch kernels' register order (conv_patch_f32.h)
     bool opt_patch_f32 = true;                 // float32 mode: cnv1 / cnv2 / cnv3 from an LDS-staged input patch (conv_patch_f32.h) instead of the implicit GEMM
@@ -342,6 +345,12 @@ inline PlaneBytes plane_bytes(const davo_ctx* c) {
     return PlaneBytes{HW * 9, HW * 8 * (c->flow_fmt == FLOW_F16 ? 2 : sizeof(float)), HW * 3 * (c->label_fmt == LABELS_U8 ? 1 : sizeof(float)), HW * 3 * sizeof(float)};
 }
 inline bool needs_depth(const davo_ctx* c) { return att_reads_depth(c->v.att_source); }
+inline bool triplet(const davo_ctx* c) { return c->topology == DAVO_POSENN_TRIPLET; }
+// images a batch of B windows sends through cnv1..cnv7: one per selected pair, or one per window in the three-frame PoseNN
+inline int batch_images(const davo_ctx* c, int B, int sel) { return triplet(c) ? B : pairs_per_window(sel) * B; }
+// columns of a head's pred, and TF input channels of cnv1 (nets/posenn.py:78,120)
+inline int pred_cols(const davo_ctx* c) { return triplet(c) ? 6 : 3; }
+inline int cnv1_cin_tf(const davo_ctx* c) { return (triplet(c) ? 3 : 2) * c->v.cin_per_frame; }
 
 // the stream slot i runs on: its own, or the caller's for slot 0 (davo_set_stream)
 inline hipStream_t slot_stream(const davo_ctx* c, int i) { return (c->user_stream && i == 0) ? c->user_stream : c->slots[i].stream.get(); }

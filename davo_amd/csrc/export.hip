@@ -165,6 +165,7 @@ int davo_set_feature_export(davo_ctx* c, int on) {
     HIP_TRY(c, hipSetDevice(c->device));
     { int rc = sync_all_slots(c); if (rc) return rc; }
     if (!on) { c->fx.reset(); c->fx_on = false; return DAVO_OK; }
+    if (triplet(c)) return fail(c, DAVO_ERR_INVALID, "the feature export has no three-frame PoseNN form yet (davo_set_posenn_topology): its maps and cnv6 windows are per pair image");
     if (!c->fx) {
         FxBlock fx;
         fx.cap = export_cap(c);
@@ -191,6 +192,7 @@ int davo_set_heat_export(davo_ctx* c, int on) {
     HIP_TRY(c, hipSetDevice(c->device));
     { int rc = sync_all_slots(c); if (rc) return rc; }
     if (!on) { c->heat.reset(); return DAVO_OK; }
+    if (triplet(c)) return fail(c, DAVO_ERR_INVALID, "the heat export has no three-frame PoseNN form yet (davo_set_posenn_topology): its cnv6 windows are per pair image");
     if (!c->heat) {
         HeatBlock h;
         h.cap = export_cap(c);

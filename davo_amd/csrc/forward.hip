@@ -8,7 +8,10 @@
 //
 // The two PoseNN calls of a triplet (davo.py:1456-1457, shared weights) run as one batch of
 // 2B pair images - or, with one pair selected (davo_set_pairs; params.h), as B pair images: the prologue and the pose kernels map
-// a pair image to its (window, source frame), every layer in between takes the count.  Host code only: kernels are reached
+// a pair image to its (window, source frame), every layer in between takes the count.
+// The three-frame PoseNN (davo_set_posenn_topology; nets/posenn.py:69-131) runs ONE image per window: mask_pack3 (16 channels) ->
+// cnv1 (conv_patch_cnv1t_h3, or the implicit GEMM at cin = 16) -> cnv2..cnv7 as above on B images -> the two-pass pose head with six
+// pred columns per head (cnv7 stored; the fused epilogue has three columns).  Host code only: kernels are reached
 // through launch.h.
 #include <cmath>
 #include <cstdlib>
@@ -353,6 +356,29 @@ int run_patch_layer(davo_ctx* c, const Run& run, int li, bool f32, const void* x
     return DAVO_OK;
 }
 
+// cnv1 of the three-frame PoseNN from an LDS-staged patch (conv_patch_cnv1t_h3): x the 16-channel split-fp16 packed tensor
+constexpr int PATCH_CNV1T_PLAN_ID = 96;
+int run_patch_cnv1t(davo_ctx* c, const Run& run, const void* x, void* y, int NB) {
+    const ConvLayer& L = c->L[0];
+    ConvPatchParams p{};
+    same_pad(c->H, L.KS, L.stride, L.rate, &p.Ho, &p.pad_t);
+    same_pad(c->W, L.KS, L.stride, L.rate, &p.Wo, &p.pad_l);
+    p.x = static_cast<const uint8_t*>(x); p.w = c->d_w1patch.get(); p.bias = L.d_bh.get(); p.y = static_cast<uint8_t*>(y);
+    p.zeros = reinterpret_cast<const uint8_t*>(c->d_zeros.get());
+    p.H = c->H; p.W = c->W;
+    p.tiles_x = (p.Wo + cp1::TW - 1) / cp1::TW; p.tiles_y = (p.Ho + cp1::TH - 1) / cp1::TH;
+    p.ntiles = NB * p.tiles_x * p.tiles_y;
+    p.out_scale = ldexpf(1.0f / L.wscale, c->act_shift[0]);       // cnv1's input carries no storage scale
+    p.bias_scale = L.wscale;
+    p.range = run.range;                                          // word 0 of the record is cnv1's
+    if (const char* e = tuning_env("DAVO_PDBG")) p.dbg = atoi(e);      // tuning build only
+    c->last_plan[0][0] = ((NB * p.Ho * p.Wo + 127) / 128) * 1000 + PATCH_CNV1T_PLAN_ID; c->last_plan[0][1] = 0; c->last_split[0] = 1;
+    const int nblk = p.ntiles < cp1t::PER_CU * c->ncu ? p.ntiles : cp1t::PER_CU * c->ncu;
+    ProfScope ps(c, run.stream, L.label);
+    HIP_TRY(c, launch_patch_cnv1t(p, nblk, run.stream));
+    return DAVO_OK;
+}
+
 int run_direct(davo_ctx* c, const Run& run, const char* label, const float* x, int N, int Hin, int Win, int cin, int x_ld,
                int x_coff, const std::string& wname, const std::string& bname, int KS, int cout, int stride,
                int rate, float* y, int y_ld, int y_coff) {
@@ -401,6 +427,8 @@ int run_posenn_se(davo_ctx* c, const Run& run, bool h3, const void* x, int NB) {
 int forward_device(davo_ctx* c, const Run& run, int B, const Inputs& in, void* d_pose, RunResult* res) {
     const int sel = run.pairs;
     if (sel != PAIRS_SRC0 && sel != PAIRS_SRC1 && sel != PAIRS_BOTH) return fail(c, DAVO_ERR_INVALID, "internal: pair selection %d", sel);
+    const bool tri = triplet(c);       // the three-frame PoseNN: one image per window, both poses from one pass
+    if (tri && (sel != PAIRS_BOTH || run.impl != 0)) return fail(c, DAVO_ERR_INVALID, "internal: the three-frame PoseNN runs both pairs on the MFMA kernels (pairs %d, impl %d)", sel, run.impl);
     if (B < 1 || B > c->max_batch) return fail(c, DAVO_ERR_INVALID, "batch %d outside [1,%d]", B, c->max_batch);
     if (!in.img || !in.flow || !in.seg || !d_pose) return fail(c, DAVO_ERR_INVALID, "null device pointer");
     if (needs_depth(c) && (!in.depth || ((uintptr_t)in.depth & 15)))
@@ -432,7 +460,7 @@ int forward_device(davo_ctx* c, const Run& run, int B, const Inputs& in, void* d
     if (!h3 && run.impl == 0 && !c->packed_ready) { int rc = build_packed_weights(c); if (rc) return rc; }      // float32 kernels: packed at their first use
     unsigned* const range_reset = (h3 && run.zero_record) ? run.range : nullptr;
 
-    const int H = c->H, W = c->W, HW = H * W, NB = pairs_per_window(sel) * B;
+    const int H = c->H, W = c->W, HW = H * W, NB = batch_images(c, B, sel);
     const Variant& v = c->v;
     const Slot& ws = c->slots[run.slot];
     float *const d_partial = ws.d_partial.get(), *const d_tab = ws.d_tab.get(), *const d_packed = ws.d_packed.get();
@@ -525,11 +553,14 @@ int forward_device(davo_ctx* c, const Run& run, int B, const Inputs& in, void* d
     const bool fuse_env = (fe && atoi(fe) == 1) || c->opt_fuse_pack == 1 || (c->opt_fuse_pack < 0 && B <= FUSE_PACK_MAX_BATCH);
     const bool patch1 = !(pe && atoi(pe) == 0);
     // (the depth-split attention has no fused fill: its packer is always mask_pack's depth-split form, whatever "fuse_pack" says)
-    const bool fused = h3 && patch1 && fuse_env && !depth_split;
+    const bool fused = h3 && patch1 && fuse_env && !depth_split && !tri;
     c->packed_valid = !fused;
     c->last_in = in;
-    c->packed_ld = run.impl == 0 ? 8 : 10;
-    if (!fused) {
+    c->packed_ld = tri ? 16 : (run.impl == 0 ? 8 : 10);
+    if (tri) {
+        ProfScope ps(c, run.stream, "mask_pack");
+        HIP_TRY(c, launch_mask_pack3(h3, d_img, d_flow, ffmt, d_seg, c->label_fmt, d_tab, v, B, H, W, d_packed, s));
+    } else if (!fused) {
         ProfScope ps(c, run.stream, "mask_pack");
         HIP_TRY(c, launch_mask_pack(h3 ? 16 : (run.impl == 0 ? 8 : 10), d_img, d_flow, ffmt, d_seg, c->label_fmt, d_tab, v, B, H, W, d_packed, sel, s,
                                     static_cast<const float*>(in.depth), d_tab_far, c->depth_thr));
@@ -540,7 +571,12 @@ int forward_device(davo_ctx* c, const Run& run, int B, const Inputs& in, void* d
     int pose_bm = 0, pose_mt = 0, pose_ntn = 0;
     c->cnv7_valid = true;
     if (h3) {
-        if (patch1) { if ((rc = run_patch_layer(c, run, 0, false, d_packed, a[0], NB, fused, in))) return rc; }
+        if (tri) {
+            // cnv1 at 16 packed channels: the LDS-patch kernel ("patch_cnv1_t"), else the implicit GEMM at cin = 16
+            if (c->opt_patch_cnv1_t && c->L[0].tile_h < 0) { if ((rc = run_patch_cnv1t(c, run, d_packed, a[0], NB))) return rc; }
+            else if ((rc = run_conv_layer_h3(c, run, 0, d_packed, 16, H, W, a[0], 16, false, NB))) return rc;
+        }
+        else if (patch1) { if ((rc = run_patch_layer(c, run, 0, false, d_packed, a[0], NB, fused, in))) return rc; }
         else if ((rc = run_conv_layer_h3(c, run, 0, d_packed, 8, H, W, a[0], 16, false, NB))) return rc;
         const char* p2e = tuning_env("DAVO_CNV2_PATCH");
         if (c->opt_patch_cnv2 && c->L[1].tile_h < 0 && !(p2e && atoi(p2e) == 0)) { if ((rc = run_patch_layer(c, run, 1, false, a[0], a[1], NB))) return rc; }
@@ -554,13 +590,13 @@ int forward_device(davo_ctx* c, const Run& run, int B, const Inputs& in, void* d
             if ((rc = run_posenn_se(c, run, true, a[4], NB))) return rc;
             if ((rc = run_conv_layer_h3(c, run, 5, d_se, 512, c->H2, c->W2, a[5], 2 * c6, false, NB))) return rc;
         } else if ((rc = run_conv_layer_h3(c, run, 5, a[4], 256, c->H2, c->W2, a[5], 2 * c6, false, NB))) return rc;
-        pose_fused = c->opt_fuse_pose && c->H3 * c->W3 >= 128;
+        pose_fused = c->opt_fuse_pose && c->H3 * c->W3 >= 128 && !tri;      // the three-frame PoseNN stores cnv7: the fused epilogue has three columns per head
         if ((rc = run_conv_layer_h3(c, run, 6, a[5], 2 * c6, c->H2, c->W2, a[6], 512, true, NB, pose_fused, &pose_bm, &pose_mt, &pose_ntn,
                                     fold_pose ? static_cast<float*>(d_pose) : nullptr))) return rc;
         c->cnv7_valid = !pose_fused;
     } else if (run.impl == 0) {
         if (c->opt_patch_f32 && c->d_w1patch_f32 && c->packed_ld == 8) { if ((rc = run_patch_layer(c, run, 0, true, d_packed, a[0], NB))) return rc; }
-        else if ((rc = run_conv_layer(c, run, 0, d_packed, 8, H, W, a[0], 16, NB))) return rc;
+        else if ((rc = run_conv_layer(c, run, 0, d_packed, tri ? 16 : 8, H, W, a[0], 16, NB))) return rc;      // the three-frame PoseNN: conv_igemm_f32 at cin = 16
         if (c->opt_patch_f32 && c->d_w2patch_f32) { if ((rc = run_patch_layer(c, run, 1, true, a[0], a[1], NB))) return rc; }
         else if ((rc = run_conv_layer(c, run, 1, a[0], 16, c->H1, c->W1, a[1], 32, NB))) return rc;
         if (c->opt_patch_f32 && c->d_w3patch_f32) { if ((rc = run_patch_layer(c, run, 2, true, a[1], a[2], NB))) return rc; }
@@ -573,7 +609,7 @@ int forward_device(davo_ctx* c, const Run& run, int B, const Inputs& in, void* d
         } else if ((rc = run_conv_layer(c, run, 5, a[4], 256, c->H2, c->W2, a[5], 2 * c6, NB))) return rc;
         // float32 mode, round 4: the pose head in cnv7's epilogue like the f16x3 path's (the 109 MB activation is neither written nor
         // read back, pose_head_partial + pose_finish become pose_from_tiles); tiles of 128 rows must not span more than two images
-        pose_fused = c->opt_fuse_pose && c->H3 * c->W3 >= 128 && c->L[6].npad == 256;
+        pose_fused = c->opt_fuse_pose && c->H3 * c->W3 >= 128 && c->L[6].npad == 256 && !tri;
         pose_bm = 128; pose_ntn = 8;
         if ((rc = run_conv_layer(c, run, 6, a[5], 2 * c6, c->H2, c->W2, a[6], 512, NB, pose_fused, &pose_mt))) return rc;
         c->cnv7_valid = !pose_fused;
@@ -603,6 +639,8 @@ int forward_device(davo_ctx* c, const Run& run, int B, const Inputs& in, void* d
             HIP_TRY(c, launch_pose_from_tiles(static_cast<const float*>(c->d_pose_tiles.get()) + (size_t)run.slot * c->pose_tiles_floats, NB, c->H3 * c->W3, pose_bm,
                                               pose_mt, pose_ntn, c->d_bpred.get(), static_cast<float*>(d_pose), h3 ? run.snap : SnapArgs{}, sel, s));
             snap_done = true;
+        } else if (tri) {
+            HIP_TRY(c, launch_pose_head6(a[6], B, c->H3 * c->W3, c->d_wpred.get(), c->d_bpred.get(), ws.d_pose_partial.get(), static_cast<float*>(d_pose), s));
         } else {
             HIP_TRY(c, launch_pose_head(a[6], NB, c->H3 * c->W3, c->d_wpred.get(), c->d_bpred.get(), ws.d_pose_partial.get(), static_cast<float*>(d_pose), sel, s));
         }

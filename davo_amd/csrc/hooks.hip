@@ -110,7 +110,7 @@ int davo_last_split(davo_ctx* c, int layer, int* parts) {
 int davo_debug_read(davo_ctx* c, const char* tensor, float* host_out, size_t n_floats) {
     if (!c || !tensor || !host_out) return DAVO_ERR_INVALID;
     if (c->last_B < 1) return fail(c, DAVO_ERR_NOT_READY, "no forward has run yet");
-    const size_t NB = (size_t)pairs_per_window(c->last_pairs) * c->last_B;      // pair images of the last forward
+    const size_t NB = (size_t)batch_images(c, c->last_B, c->last_pairs);      // pair images of the last forward (three-frame PoseNN: one image per window)
     const float* src = nullptr;
     size_t n = 0;
     const std::string t = tensor;
@@ -168,7 +168,7 @@ int davo_debug_read(davo_ctx* c, const char* tensor, float* host_out, size_t n_f
     if (rc) return rc;
     const bool split = c->last_precision == 1 && t != "att_table" && t != "att_table_far" && t != "se_desc" && t != "cnv7" && t != "cnv5_se_scale";
     if (split) {       // split-fp16 blocked -> plain float32 NHWC
-        int ch = 8;
+        int ch = triplet(c) ? 16 : 8;                // "packed"
         const char* names[6] = {"cnv1", "cnv2", "cnv3", "cnv4", "cnv5", "cnv6"};
         for (int i = 0; i < 6; ++i) if (t == names[i]) ch = c->act_ch[i];
         if (t == "cnv5_se") ch = 512;                // cnv5's storage ...

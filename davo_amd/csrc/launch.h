@@ -83,6 +83,9 @@ hipError_t launch_se_pool_excite(const float* d_partial, int B, const Variant& v
 hipError_t launch_mask_pack(int ld, const uint8_t* d_img, const void* d_flow, int flow_fmt, const void* d_seg, int label_fmt, const float* d_tab,
                             const Variant& v, int B, int H, int W, float* d_packed, int sel, hipStream_t s,
                             const float* d_depth = nullptr, const float* d_tab_far = nullptr, float depth_thr = 0.f);
+// the three-frame PoseNN's packer (prologue.h, mask_pack3): B windows -> [B][H][W][16], float32 or (h3) split-fp16 [16 hi | 16 lo]
+hipError_t launch_mask_pack3(bool h3, const uint8_t* d_img, const void* d_flow, int flow_fmt, const void* d_seg, int label_fmt, const float* d_tab,
+                             const Variant& v, int B, int H, int W, float* d_packed, hipStream_t s);
 // window_gather.h: N windows of a frame-layout batch into the window-major planes every kernel above reads; every pointer 16-byte
 // aligned; a.f_flow null = the flow planes are in place already (the host entry points copy them there)
 struct GatherArgs;
@@ -91,6 +94,9 @@ hipError_t launch_window_gather(const GatherArgs& a, int N, int label_fmt, int f
 // fused: conv_patch_cnv1_h3<true, float | uint8_t, float | flow_f16> by label_fmt and flow_fmt (f16x3 cnv1 only; p.seg and p.flow are in those formats)
 hipError_t launch_patch_layer(int layer, bool f32, bool fused, const ConvPatchParams& p, int nblk, hipStream_t s, int label_fmt = LABELS_F32,
                               int flow_fmt = FLOW_F32);
+// cnv1 of the three-frame PoseNN from an LDS-staged patch (conv_patch_cnv1t_h3): p.x the 16-channel split-fp16 packed tensor, p.w
+// cp1t::WBYTES of fragments
+hipError_t launch_patch_cnv1t(const ConvPatchParams& p, int nblk, hipStream_t s);
 // split-K fix-up: d_part [M][S][N] float32 partial sums -> the layer's stored activation (ReLU, fp16 hi/lo pairs, range monitor)
 hipError_t launch_splitk_fixup(const float* d_part, long M, int N, int S, int relu, uint8_t* d_y, unsigned* d_range, hipStream_t s);
 hipError_t launch_pose_from_tiles(const float* d_tiles, int NB, int P, int bm, int mtiles, int ntiles_n,
@@ -99,6 +105,9 @@ hipError_t launch_pose_from_tiles(const float* d_tiles, int NB, int P, int bm, i
 hipError_t launch_range_guard_snapshot(const SnapArgs& snap, hipStream_t s);
 hipError_t launch_pose_head(const float* d_c7, int NB, int P, const float* d_wpred, const float* d_bpred,
                             float* d_partial, float* d_pose, int sel, hipStream_t s);
+// ... of the three-frame PoseNN: d_c7 [B][P][512], d_wpred6 [2][256][6], d_bpred6 [2][6], d_partial [B][2][PH_SPLIT][6] -> d_pose [B][2][6]
+hipError_t launch_pose_head6(const float* d_c7, int B, int P, const float* d_wpred6, const float* d_bpred6,
+                             float* d_partial, float* d_pose, hipStream_t s);
 hipError_t launch_conv_direct(const float* x, int N, int Hin, int Win, int cin, int x_ld, int x_coff, const float* w, int KS,
                               int cout, const float* bias, int stride, int rate, int pt, int pl, int Ho, int Wo, int relu,
                               float* y, int y_ld, int y_coff, hipStream_t s);

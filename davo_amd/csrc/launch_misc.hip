@@ -192,6 +192,33 @@ hipError_t launch_mask_pack(int ld, const uint8_t* d_img, const void* d_flow, in
     return mask_pack_as<float, flow_f32>(ld, grid, s, d_img, d_flow, d_seg, d_tab, v, B, sel, H, W, d_packed, dsp);
 }
 
+namespace {
+template <typename LT, typename FT>
+hipError_t mask_pack3_as(bool h3, const dim3& grid, hipStream_t s, const uint8_t* d_img, const void* d_flow, const void* d_seg, const float* d_tab,
+                         const Variant& v, int B, int H, int W, float* d_packed) {
+    const LT* seg = static_cast<const LT*>(d_seg);
+    const FT* flow = static_cast<const FT*>(d_flow);
+    if (h3) hipLaunchKernelGGL((mask_pack3<true, LT, FT>), grid, dim3(PACK3_THREADS), 0, s, d_img, flow, seg, d_tab, v, B, H, W, d_packed);
+    else hipLaunchKernelGGL((mask_pack3<false, LT, FT>), grid, dim3(PACK3_THREADS), 0, s, d_img, flow, seg, d_tab, v, B, H, W, d_packed);
+    return hipGetLastError();
+}
+}  // namespace
+
+hipError_t launch_mask_pack3(bool h3, const uint8_t* d_img, const void* d_flow, int flow_fmt, const void* d_seg, int label_fmt, const float* d_tab,
+                             const Variant& v, int B, int H, int W, float* d_packed, hipStream_t s) {
+    if (B < 1 || H < 1 || W < 4 || W % 4 || !d_img || !d_flow || !d_seg || !d_tab || !d_packed) return hipErrorInvalidValue;
+    if (!flow_fmt_ok(flow_fmt) || (label_fmt != LABELS_F32 && label_fmt != LABELS_U8)) return hipErrorInvalidValue;
+    if (att_reads_depth(v.att_source)) return hipErrorInvalidValue;      // no three-frame form of the depth sources
+    const long nthreads = (long)B * H * (W / 4);
+    const dim3 grid((unsigned)((nthreads + PACK3_THREADS - 1) / PACK3_THREADS));
+    if (flow_fmt == FLOW_F16) {
+        if (label_fmt == LABELS_U8) return mask_pack3_as<uint8_t, flow_f16>(h3, grid, s, d_img, d_flow, d_seg, d_tab, v, B, H, W, d_packed);
+        return mask_pack3_as<float, flow_f16>(h3, grid, s, d_img, d_flow, d_seg, d_tab, v, B, H, W, d_packed);
+    }
+    if (label_fmt == LABELS_U8) return mask_pack3_as<uint8_t, flow_f32>(h3, grid, s, d_img, d_flow, d_seg, d_tab, v, B, H, W, d_packed);
+    return mask_pack3_as<float, flow_f32>(h3, grid, s, d_img, d_flow, d_seg, d_tab, v, B, H, W, d_packed);
+}
+
 hipError_t launch_window_gather(const GatherArgs& a, int N, int label_fmt, int flow_fmt, hipStream_t s) {
     if (N < 1 || a.H < 1 || a.W < 4 || a.W % 4 || ((size_t)a.H * a.W) % 16 || !a.f_img || !a.f_seg || !a.w_img || !a.w_seg || !a.w_flow ||
         (a.f_depth && !a.w_depth))
@@ -233,6 +260,14 @@ hipError_t launch_patch_layer(int layer, bool f32, bool fused, const ConvPatchPa
     hipError_t e = ensure_dynamic_lds(reinterpret_cast<const void*>(k), r.lds);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(k, dim3(nblk), dim3(r.threads), r.lds, s, p);
+    return hipGetLastError();
+}
+
+hipError_t launch_patch_cnv1t(const ConvPatchParams& p, int nblk, hipStream_t s) {
+    if (nblk < 1 || !p.x || !p.w || !p.bias || !p.y || !p.zeros || p.ntiles < 1) return hipErrorInvalidValue;
+    hipError_t e = ensure_dynamic_lds(reinterpret_cast<const void*>(conv_patch_cnv1t_h3), cp1t::LDS_BYTES);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(conv_patch_cnv1t_h3, dim3(nblk), dim3(cp1::THREADS), cp1t::LDS_BYTES, s, p);
     return hipGetLastError();
 }
 
@@ -280,10 +315,20 @@ hipError_t launch_range_guard_snapshot(const SnapArgs& snap, hipStream_t s) {
 
 hipError_t launch_pose_head(const float* d_c7, int NB, int P, const float* d_wpred, const float* d_bpred,
                             float* d_partial, float* d_pose, int sel, hipStream_t s) {
-    hipLaunchKernelGGL(pose_head_partial, dim3(PH_SPLIT, NB, 2), dim3(256), 0, s, d_c7, P, d_wpred, d_partial);
+    hipLaunchKernelGGL(pose_head_partial<3>, dim3(PH_SPLIT, NB, 2), dim3(256), 0, s, d_c7, P, d_wpred, d_partial);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(pose_finish, dim3((NB * 6 + 63) / 64), dim3(64), 0, s, d_partial, NB, P, d_bpred, d_pose, sel);
+    return hipGetLastError();
+}
+
+hipError_t launch_pose_head6(const float* d_c7, int B, int P, const float* d_wpred6, const float* d_bpred6,
+                             float* d_partial, float* d_pose, hipStream_t s) {
+    if (B < 1 || P < 1 || !d_c7 || !d_wpred6 || !d_bpred6 || !d_partial || !d_pose) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(pose_head_partial<6>, dim3(PH_SPLIT, B, 2), dim3(256), 0, s, d_c7, P, d_wpred6, d_partial);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(pose_finish6, dim3((B * 12 + 63) / 64), dim3(64), 0, s, d_partial, B, P, d_bpred6, d_pose);
     return hipGetLastError();
 }
 

@@ -296,6 +296,15 @@ constexpr int LDS_BYTES = 2 * PLANE;                   // 43,008 B: the patch (t
 constexpr int THREADS = 256;
 }  // namespace cp1
 
+// ---- conv_patch_h3.h (cnv1 of the three-frame PoseNN: 16 packed channels as two 8-channel passes over cp1's patch) ----
+namespace cp1t {
+constexpr int WHALF = cp1::WBYTES;                     // 28,672 B of B fragments per channel half: [step][plane][lane] x 16 B
+constexpr int WBYTES = 2 * WHALF;                      // global: [half][step][plane][lane] x 16 B
+constexpr int WLDS = cp1::LDS_BYTES;                   // the second half's fragments sit behind the patch (a multiple of 16 B)
+constexpr int LDS_BYTES = cp1::LDS_BYTES + WHALF;      // 71,680 B: two workgroups per CU
+constexpr int PER_CU = 2;
+}  // namespace cp1t
+
 // ---- conv_patch_h3.h (cnv2 from an LDS patch) ---------------------------------------------
 namespace cp2 {
 constexpr int KS = 5, TH = 8, TW = 8;                  // filter, output tile: 4 pixel groups of 2 rows x 8 columns

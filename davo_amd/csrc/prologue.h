@@ -583,6 +583,121 @@ __global__ __launch_bounds__(256) void mask_pack_depthsplit(const uint8_t* __res
     mask_pack_body<LD, true>(img, flow, seg, tab, v, B, sel, H, W, out, ds);
 }
 
+// Mask + pack of the three-frame PoseNN (davo_set_posenn_topology; nets/posenn.py:78, davo.py:1460): one thread per 4 horizontally
+// adjacent pixels of one WINDOW, out[b][y][x][0..16):
+//   tgt rgb*att_t (3) | src0 rgb*att_0 (3) | flow0*att_0 (2) | src1 rgb*att_1 (3) | flow1*att_1 (2) | 0 0 0
+// (the target's two identically-zero info channels are dropped, as the 8-channel layout drops them; v0 leaves the flow slots zero).
+// H3 false: 16 floats per pixel; true: the split-fp16 form [16 hi | 16 lo] halves, the blocked layout of a 16-channel f16x3
+// tensor.  64 B per pixel either way.  Each of the three label maps and two flow planes of the group is fetched once
+// (label_fetch4 / flow_fetch4); the products are mask_pack's, in mask_pack's order.  The stores leave through LDS like
+// mask_pack's STAGED path: a thread's 256 B are 16 units of 16 B, unit t*16 + (k ^ (t & 15)), the workgroup's 32 KB are contiguous
+// in the output (offset = gid * 256 B) and leave as 1 KiB per wave instruction.
+constexpr int PACK3_THREADS = 128;
+template <bool H3, typename LT, typename FT>
+__global__ __launch_bounds__(PACK3_THREADS) void mask_pack3(const uint8_t* __restrict__ img, const FT* __restrict__ flow,
+                                                           const LT* __restrict__ seg, const float* __restrict__ tab,
+                                                           Variant v, int B, int H, int W, float* __restrict__ out) {
+    const int W4 = W >> 2;
+    const long total = (long)B * H * W4;
+    const long gid_raw = (long)blockIdx.x * PACK3_THREADS + threadIdx.x;
+    const long gid = gid_raw < total ? gid_raw : total - 1;     // every thread reaches the barrier below
+    const int x4 = (int)(gid % W4);
+    long t = gid / W4;
+    const int y = (int)(t % H);
+    const int b = (int)(t / H);
+    const int x = x4 * 4;
+    const size_t HW = (size_t)H * W, pix = (size_t)y * W + x;
+
+    // strip slots src0 | tgt | src1 (data_loader.py:537-557); frame f = 0 tgt, 1 src0, 2 src1
+    const uint8_t* row = img + ((size_t)b * H + y) * (size_t)(9 * W);
+    uint8_t px8[3][12];
+#pragma unroll
+    for (int f = 0; f < 3; ++f) {
+        const int slot = f == 0 ? 1 : f == 1 ? 0 : 2;
+        const uint32_t* q = reinterpret_cast<const uint32_t*>(row + (size_t)(slot * W + x) * 3);
+        const uint32_t q0 = q[0], q1 = q[1], q2 = q[2];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            px8[f][k] = (uint8_t)(q0 >> (8 * k)); px8[f][4 + k] = (uint8_t)(q1 >> (8 * k)); px8[f][8 + k] = (uint8_t)(q2 >> (8 * k));
+        }
+    }
+    // attention per frame and pixel: ones unless the variant looks the pixel's class up (mask_pack's rules); seg file planes
+    // src0, tgt, src1 (davo.py:998-1004)
+    float att[3][4];
+#pragma unroll
+    for (int f = 0; f < 3; ++f)
+#pragma unroll
+        for (int k = 0; k < 4; ++k) att[f][k] = 1.f;
+    if (v.att_source != 0) {
+#pragma unroll
+        for (int f = 1; f < 3; ++f) {
+            const LabelIds4 sg = label_fetch4(seg + ((size_t)b * 3 + (f == 1 ? 0 : 2)) * HW, pix);
+            const float* tab_f = tab + ((size_t)b * 3 + f) * NCLS;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) att[f][k] = att_lookup_id(tab_f, sg.id[k]);
+        }
+    }
+    if (att_tgt_attended(v.att_source)) {
+        const LabelIds4 tg = label_fetch4(seg + ((size_t)b * 3 + 1) * HW, pix);
+        const float* tab_t = tab + (size_t)b * 3 * NCLS;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) att[0][k] = att_lookup_id(tab_t, tg.id[k]);
+    }
+    float fl[2][8];
+#pragma unroll
+    for (int s = 0; s < 2; ++s)
+#pragma unroll
+        for (int k = 0; k < 8; ++k) fl[s][k] = 0.f;
+    if (v.cin_per_frame == 5) {
+#pragma unroll
+        for (int s = 0; s < 2; ++s) {
+            const Flow4 f = flow_fetch4(flow + (((size_t)b * 4 + s) * HW + pix) * 2);
+#pragma unroll
+            for (int k = 0; k < 8; ++k) fl[s][k] = f.v[k];
+        }
+    }
+    __shared__ float4 stage[PACK3_THREADS * 16];
+    const int t16 = threadIdx.x * 16, sw = threadIdx.x & 15;
+#pragma unroll
+    for (int px = 0; px < 4; ++px) {
+        float r[16];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            r[k] = u8_to_unit(px8[0][3 * px + k]);
+            r[3 + k] = u8_to_unit(px8[1][3 * px + k]);
+            r[8 + k] = u8_to_unit(px8[2][3 * px + k]);
+            if (v.mask_rgb) { r[k] *= att[0][px]; r[3 + k] *= att[1][px]; r[8 + k] *= att[2][px]; }
+        }
+        r[6] = v.mask_info ? fl[0][2 * px] * att[1][px] : fl[0][2 * px];
+        r[7] = v.mask_info ? fl[0][2 * px + 1] * att[1][px] : fl[0][2 * px + 1];
+        r[11] = v.mask_info ? fl[1][2 * px] * att[2][px] : fl[1][2 * px];
+        r[12] = v.mask_info ? fl[1][2 * px + 1] * att[2][px] : fl[1][2 * px + 1];
+        r[13] = 0.f; r[14] = 0.f; r[15] = 0.f;
+        if (H3) {
+            _Float16 hl[32];                       // [16 hi | 16 lo]: x = hi + lo
+#pragma unroll
+            for (int k = 0; k < 16; ++k) {
+                const _Float16 h = (_Float16)r[k];
+                hl[k] = h;
+                hl[16 + k] = (_Float16)(r[k] - (float)h);
+            }
+#pragma unroll
+            for (int u = 0; u < 4; ++u) stage[t16 + ((4 * px + u) ^ sw)] = *reinterpret_cast<const float4*>(&hl[8 * u]);
+        } else {
+#pragma unroll
+            for (int u = 0; u < 4; ++u) stage[t16 + ((4 * px + u) ^ sw)] = make_float4(r[4 * u], r[4 * u + 1], r[4 * u + 2], r[4 * u + 3]);
+        }
+    }
+    __syncthreads();
+    float4* og = reinterpret_cast<float4*>(out) + (size_t)blockIdx.x * (PACK3_THREADS * 16);
+#pragma unroll
+    for (int i = 0; i < 16; ++i) {
+        const int j = i * PACK3_THREADS + threadIdx.x;    // physical unit; owner thread j >> 4
+        const int k = (j & 15) ^ ((j >> 4) & 15);         // its logical 16-byte piece
+        if ((long)blockIdx.x * PACK3_THREADS + (j >> 4) < total) og[(j & ~15) + k] = stage[j];
+    }
+}
+
 // Pose head tail: pred (1x1, 256 -> 3, linear) + mean over H3 x W3 + 0.01 scale
 // (nets/posenn.py:240-241,248-250).  pred and the mean are both linear, so
 //   pose[n][head*3+j] = 0.01 * ( b[j] + (1/P) * sum_c ( sum_p cnv7[n][p][head][c] ) * Wp[c][j] ).
@@ -590,9 +705,12 @@ __global__ __launch_bounds__(256) void mask_pack_depthsplit(const uint8_t* __res
 // block s sums its slice of the P pixels and writes 3 partial dot products.  Pass 2 (pose_finish)
 // adds the PH_SPLIT partials in a fixed order -> bitwise reproducible.
 
+// NC: columns of a head's pred: 3 (one pose per pair image) or 6 (the three-frame PoseNN: both poses of a window from one image,
+// nets/posenn.py:120), wpred [2][256][NC], partial [images][2][PH_SPLIT][NC]; the sums of a column are the same in either form.
+template <int NC>
 __global__ __launch_bounds__(256) void pose_head_partial(const float* __restrict__ c7, int P,
-                                                         const float* __restrict__ wpred /*[2][256][3]*/,
-                                                         float* __restrict__ partial /*[2B][2][PH_SPLIT][3]*/) {
+                                                         const float* __restrict__ wpred /*[2][256][NC]*/,
+                                                         float* __restrict__ partial /*[images][2][PH_SPLIT][NC]*/) {
     const int sp = blockIdx.x, n = blockIdx.y, head = blockIdx.z, c = threadIdx.x;
     const int per = (P + PH_SPLIT - 1) / PH_SPLIT;
     const int p0 = sp * per, p1 = min(p0 + per, P);
@@ -605,18 +723,20 @@ __global__ __launch_bounds__(256) void pose_head_partial(const float* __restrict
     }
     for (; p < p1; ++p) s0 += src[(size_t)p * 512];
     const float sc = (s0 + s1) + (s2 + s3);
-    const float* wp = wpred + ((size_t)head * 256 + c) * 3;
-    float v[3] = {sc * wp[0], sc * wp[1], sc * wp[2]};
-    __shared__ float red[3][4];
+    const float* wp = wpred + ((size_t)head * 256 + c) * NC;
+    float v[NC];
+#pragma unroll
+    for (int j = 0; j < NC; ++j) v[j] = sc * wp[j];
+    __shared__ float red[NC][4];
     const int lane = c & 63, wid = c >> 6;
 #pragma unroll
-    for (int j = 0; j < 3; ++j) {
+    for (int j = 0; j < NC; ++j) {
         v[j] = wave_sum(v[j]);
         if (lane == 0) red[j][wid] = v[j];
     }
     __syncthreads();
-    if (c < 3)
-        partial[(((size_t)n * 2 + head) * PH_SPLIT + sp) * 3 + c] = (red[c][0] + red[c][1]) + (red[c][2] + red[c][3]);
+    if (c < NC)
+        partial[(((size_t)n * 2 + head) * PH_SPLIT + sp) * NC + c] = (red[c][0] + red[c][1]) + (red[c][2] + red[c][3]);
 }
 
 __global__ __launch_bounds__(64) void pose_finish(const float* __restrict__ partial, int NB, int P,
@@ -630,6 +750,22 @@ __global__ __launch_bounds__(64) void pose_finish(const float* __restrict__ part
 #pragma unroll
     for (int s = 0; s < PH_SPLIT; ++s) tot += pp[s * 3];
     pose_store(pose, n, hj, sel, 0.01f * (tot / (float)P + bpred[hj]));
+}
+
+// ... of the three-frame PoseNN: avg [B][6] per head, reshaped [-1, 2, 3] (nets/posenn.py:121-127):
+// pose[b][s][3 head + k] = 0.01 * avg_head[b][3 s + k]; the PH_SPLIT partials in the same fixed order
+__global__ __launch_bounds__(64) void pose_finish6(const float* __restrict__ partial /*[B][2][PH_SPLIT][6]*/, int B, int P,
+                                                   const float* __restrict__ bpred /*[2][6]*/,
+                                                   float* __restrict__ pose /*[B][2][6]*/) {
+    const int i = blockIdx.x * 64 + threadIdx.x;           // (b, s, head, k): the index of the pose array itself
+    if (i >= B * 12) return;
+    const int b = i / 12, r = i - b * 12, s = r / 6, hk = r - s * 6, head = hk / 3, k = hk - head * 3;
+    const int col = 3 * s + k;
+    const float* pp = partial + ((size_t)b * 2 + head) * PH_SPLIT * 6 + col;
+    float tot = 0.f;
+#pragma unroll
+    for (int q = 0; q < PH_SPLIT; ++q) tot += pp[q * 6];
+    pose[i] = 0.01f * (tot / (float)P + bpred[head * 6 + col]);
 }
 
 // Pose from the per-tile partial sums cnv7's fused epilogue wrote (conv_igemm_h3.h, y_mode 2):

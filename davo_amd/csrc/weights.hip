@@ -130,7 +130,7 @@ std::vector<std::string> needed_names(const Variant& v, int posenn_se) {
 }
 
 bool expected_shape(const davo_ctx* c, const std::string& name, std::vector<int64_t>* sh) {
-    const int c10 = 2 * c->v.cin_per_frame, c6 = c->v.cnv6_out;
+    const int c10 = cnv1_cin_tf(c), c6 = c->v.cnv6_out;
     auto is = [&](const char* s) { return name == s; };
     auto ends = [&](const char* s) {
         const size_t n = strlen(s);
@@ -150,8 +150,8 @@ bool expected_shape(const davo_ctx* c, const std::string& name, std::vector<int6
     else if (ends("/cnv6/biases")) *sh = {c6};
     else if (ends("/cnv7/weights")) *sh = {3, 3, c6, 256};
     else if (ends("/cnv7/biases")) *sh = {256};
-    else if (ends("/pred/weights")) *sh = {1, 1, 256, 3};
-    else if (ends("/pred/biases")) *sh = {3};
+    else if (ends("/pred/weights")) *sh = {1, 1, 256, pred_cols(c)};
+    else if (ends("/pred/biases")) *sh = {pred_cols(c)};
     else if (c->posenn_se && ends("/cnv5_se_attention/bottleneck_fc/kernel")) *sh = {256, 32};     // se_block(cnv5, ratio=8)
     else if (c->posenn_se && ends("/cnv5_se_attention/bottleneck_fc/bias")) *sh = {32};
     else if (c->posenn_se && ends("/cnv5_se_attention/recover_fc/kernel")) *sh = {32, 256};
@@ -233,17 +233,35 @@ void init_posenn_layers(ConvLayer (&L)[7], int c6) {
     init_layer(L[6], "cnv7", 3, 2, 1, c6, 256, 2);
 }
 
-// the pose head's 1x1 kernels [2][256][3] + [2][3]: every arithmetic mode reads them, so they are built at the first forward whatever
+// cnv1: packed input channel -> TF input channel.  Pairs, v1: [t r,g,b | 0,0 | s r,g,b | fx,fy]; the two zero channels
+// (davo.py:979,1065) are dropped.  v0: [t rgb | s rgb].  Three-frame PoseNN (prologue.h, mask_pack3), v1: TF [t rgb | 0 0 | s0 rgb |
+// f0 | s1 rgb | f1] -> packed [t rgb | s0 rgb | f0 | s1 rgb | f1 | - - -]; v0: TF [t rgb | s0 rgb | s1 rgb], the flow slots empty.
+// -> the number of packed channels (8 | 16)
+static int cnv1_chmap(const davo_ctx* c, int chmap[16]) {
+    const bool v1 = c->v.cin_per_frame == 5;
+    for (int i = 0; i < 16; ++i) chmap[i] = -1;
+    if (triplet(c)) {
+        const int m1[16] = {0, 1, 2, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, -1, -1, -1}, m0[16] = {0, 1, 2, 3, 4, 5, -1, -1, 6, 7, 8, -1, -1, -1, -1, -1};
+        memcpy(chmap, v1 ? m1 : m0, sizeof m1);
+        return 16;
+    }
+    const int m1[8] = {0, 1, 2, 5, 6, 7, 8, 9}, m0[8] = {0, 1, 2, 3, 4, 5, -1, -1};
+    memcpy(chmap, v1 ? m1 : m0, sizeof m1);
+    return 8;
+}
+
+// the pose head's 1x1 kernels [2][256][3] + [2][3] ([2][256][6] + [2][6] in the three-frame PoseNN): every arithmetic mode reads them, so they are built at the first forward whatever
 // the mode; the float32 convolution weights (below) only when a float32 forward is issued (round 5: a rank that runs f16x3 packs
 // and uploads 13 MB less in front of its first batch)
 int build_pred_weights(davo_ctx* c) {
     auto W = [&](const std::string& n) -> const HostTensor& { return c->weights.at(n); };
     const char* heads[2] = {"rotation", "translation"};
-    std::vector<float> wp(2 * 256 * 3), bp(2 * 3);
+    const int nc = pred_cols(c);
+    std::vector<float> wp(2 * 256 * nc), bp(2 * nc);
     for (int h = 0; h < 2; ++h) {
         const std::string p = std::string("pose_exp_net/pose/") + heads[h] + "/pred/";
-        memcpy(wp.data() + h * 768, W(p + "weights").data.data(), 768 * sizeof(float));
-        memcpy(bp.data() + h * 3, W(p + "biases").data.data(), 3 * sizeof(float));
+        memcpy(wp.data() + h * 256 * nc, W(p + "weights").data.data(), 256 * nc * sizeof(float));
+        memcpy(bp.data() + h * nc, W(p + "biases").data.data(), nc * sizeof(float));
     }
     int rc = upload(c, wp, &c->d_wpred); if (rc) return rc;
     rc = upload(c, bp, &c->d_bpred); if (rc) return rc;
@@ -254,14 +272,12 @@ int build_pred_weights(davo_ctx* c) {
 int build_packed_weights(davo_ctx* c) {
     const int c6 = c->v.cnv6_out, cpf = c->v.cin_per_frame;
     auto W = [&](const std::string& n) -> const HostTensor& { return c->weights.at(n); };
-    // cnv1: packed input channel -> TF input channel.  v1: [t r,g,b | 0,0 | s r,g,b | fx,fy];
-    // the two zero channels (davo.py:979,1065) are dropped.  v0: [t rgb | s rgb].
-    int chmap1[8];
-    if (cpf == 5) { const int m[8] = {0, 1, 2, 5, 6, 7, 8, 9}; memcpy(chmap1, m, sizeof m); }
-    else { const int m[8] = {0, 1, 2, 3, 4, 5, -1, -1}; memcpy(chmap1, m, sizeof m); }
+    int chmap1[16];
+    (void)cnv1_chmap(c, chmap1);
+    (void)cpf;
 
     struct Src { const char* w; const char* b; const int* chmap; int cin_tf; };
-    const Src trunk[5] = {{"pose_exp_net/cnv1/weights", "pose_exp_net/cnv1/biases", chmap1, 2 * cpf},
+    const Src trunk[5] = {{"pose_exp_net/cnv1/weights", "pose_exp_net/cnv1/biases", chmap1, cnv1_cin_tf(c)},
                           {"pose_exp_net/cnv2/weights", "pose_exp_net/cnv2/biases", nullptr, 16},
                           {"pose_exp_net/cnv3/weights", "pose_exp_net/cnv3/biases", nullptr, 32},
                           {"pose_exp_net/cnv4/weights", "pose_exp_net/cnv4/biases", nullptr, 64},
@@ -300,16 +316,7 @@ int build_packed_weights(davo_ctx* c) {
         int rc = upload(c, wp, &L.d_w); if (rc) return rc;
         rc = upload(c, bp, &L.d_b); if (rc) return rc;
     }
-    {   // pred: [2][256][3] + [2][3]
-        std::vector<float> wp(2 * 256 * 3), bp(2 * 3);
-        for (int h = 0; h < 2; ++h) {
-            const std::string p = std::string("pose_exp_net/pose/") + heads[h] + "/pred/";
-            memcpy(wp.data() + h * 768, W(p + "weights").data.data(), 768 * sizeof(float));
-            memcpy(bp.data() + h * 3, W(p + "biases").data.data(), 3 * sizeof(float));
-        }
-        int rc = upload(c, wp, &c->d_wpred); if (rc) return rc;
-        rc = upload(c, bp, &c->d_bpred); if (rc) return rc;
-    }
+    { int rc = build_pred_weights(c); if (rc) return rc; }      // pred: [2][256][3] + [2][3]
     {   // float32 patch kernels (conv_patch_f32.h): the weights as the MFMA's A operand, in the order the kernels consume them.
         // cnv2: [25 taps][2 N groups][4 instructions t][64 lanes]; lane (r = l & 15, kq = l >> 4) of instruction t holds
         // W[tap][input channel 4 kq + t][output channel 16 ng + r]
@@ -331,18 +338,20 @@ int build_packed_weights(davo_ctx* c) {
                         w3[((size_t)(tap * 4 + wv) * 8 + q) * 64 + l] = t3.data[((size_t)tap * 32 + 4 * (l >> 4) + (q & 3) + 16 * (q >> 2)) * 64 + 16 * wv + (l & 15)];
         rc = upload(c, w3, &c->d_w3patch_f32); if (rc) return rc;
         // cnv1: [14 steps = ky x h][8 packed channels c][64 lanes]: lane (r' = output channel, kq) holds W[ky][kx = 4 h + kq][chmap1[c]][r'],
-        // zero for the dummy tap kx = 7 and for packed channels the variant does not have
+        // zero for the dummy tap kx = 7 and for packed channels the variant does not have.  (The three-frame PoseNN has no float32
+        // patch kernel: its cnv1 stays on conv_igemm_f32 at cin = 16, and the fragments are not built.)
         const HostTensor& t1 = W("pose_exp_net/cnv1/weights");           // [7][7][2 cpf][16]
-        const int cin_tf = 2 * cpf;
+        const int cin_tf = cnv1_cin_tf(c);
         std::vector<float> w1((size_t)14 * 8 * 64, 0.f);
-        for (int st = 0; st < 14; ++st)
+        for (int st = 0; st < 14 && !triplet(c); ++st)
             for (int q = 0; q < 8; ++q)
                 for (int l = 0; l < 64; ++l) {
                     const int ky = st >> 1, kx = 4 * (st & 1) + (l >> 4), ci = chmap1[q];
                     if (kx >= 7 || ci < 0 || ci >= cin_tf) continue;
                     w1[((size_t)st * 8 + q) * 64 + l] = t1.data[(((size_t)ky * 7 + kx) * cin_tf + ci) * 16 + (l & 15)];
                 }
-        rc = upload(c, w1, &c->d_w1patch_f32); if (rc) return rc;
+        c->d_w1patch_f32.reset();
+        if (!triplet(c)) { rc = upload(c, w1, &c->d_w1patch_f32); if (rc) return rc; }
     }
     c->packed_ready = true;
     return DAVO_OK;
@@ -352,9 +361,9 @@ int build_packed_weights(davo_ctx* c) {
 int build_packed_weights_h3(davo_ctx* c) {
     const int c6 = c->v.cnv6_out, cpf = c->v.cin_per_frame;
     auto W = [&](const std::string& n) -> const HostTensor& { return c->weights.at(n); };
-    int chmap1[8];
-    if (cpf == 5) { const int m[8] = {0, 1, 2, 5, 6, 7, 8, 9}; memcpy(chmap1, m, sizeof m); }
-    else { const int m[8] = {0, 1, 2, 3, 4, 5, -1, -1}; memcpy(chmap1, m, sizeof m); }
+    int chmap1[16];
+    (void)cnv1_chmap(c, chmap1);
+    (void)cpf;
     const char* heads[2] = {"rotation", "translation"};
     for (int li = 0; li < 7; ++li) {
         ConvLayer& L = c->L[li];
@@ -385,7 +394,7 @@ int build_packed_weights_h3(davo_ctx* c) {
         if (li < 5) {
             const char* names[5] = {"cnv1", "cnv2", "cnv3", "cnv4", "cnv5"};
             const std::string p = std::string("pose_exp_net/") + names[li] + "/";
-            pack(p + "weights", p + "biases", li == 0 ? 2 * cpf : L.cin, L.cout, li == 0 ? chmap1 : nullptr, wp.data(), bp.data());
+            pack(p + "weights", p + "biases", li == 0 ? cnv1_cin_tf(c) : L.cin, L.cout, li == 0 ? chmap1 : nullptr, wp.data(), bp.data());
         } else if (li == 5) {       // rotation | translation stacked along N; feature attention: one group per head
             const size_t wstep = L.groups == 2 ? per_group : (size_t)c6 * L.nchunks_h * 64, bstep = L.groups == 2 ? L.npad_h : c6;
             for (int h = 0; h < 2; ++h) {
@@ -404,21 +413,27 @@ int build_packed_weights_h3(davo_ctx* c) {
         if (rc) return rc;
     }
     {   // cnv1 patch kernel: [14 steps][hi|lo][64 lanes][8 channels] halves, lane = (n = l&15, tap slot kq = l>>4)
+        // three-frame PoseNN (conv_patch_cnv1t_h3): the same block once per channel half, [half][14 steps][hi|lo][64 lanes][8 channels],
+        // half hf holding packed channels 8 hf .. 8 hf + 7
         const ConvLayer& L = c->L[0];
         const HostTensor& t = W("pose_exp_net/cnv1/weights");
-        const int cin_tf = 2 * cpf;
-        std::vector<_Float16> wp((size_t)cp1::STEPS * 2 * 64 * 8, (_Float16)0.0f);
-        for (int step = 0; step < cp1::STEPS; ++step)
-            for (int l = 0; l < 64; ++l) {
-                const int n = l & 15, kq = l >> 4, ky = step >> 1, kx = 4 * (step & 1) + kq;
-                if (kx >= 7) continue;
-                for (int j = 0; j < 8; ++j) {
-                    const int ci = chmap1[j];
-                    if (ci < 0 || ci >= cin_tf) continue;
-                    const float v = t.data[(((size_t)ky * 7 + kx) * cin_tf + ci) * 16 + n] * L.wscale;
-                    split_f16(v, &wp[((size_t)(step * 2 + 0) * 64 + l) * 8 + j], &wp[((size_t)(step * 2 + 1) * 64 + l) * 8 + j]);
+        const int cin_tf = cnv1_cin_tf(c), nhalf = triplet(c) ? 2 : 1;
+        const size_t per_half = (size_t)cp1::STEPS * 2 * 64 * 8;
+        static_assert(cp1::STEPS * 2 * 64 * 8 * 2 == cp1t::WHALF, "one half of conv_patch_cnv1t_h3's fragments is conv_patch_cnv1_h3's block");
+        std::vector<_Float16> wp(per_half * nhalf, (_Float16)0.0f);
+        for (int hf = 0; hf < nhalf; ++hf)
+            for (int step = 0; step < cp1::STEPS; ++step)
+                for (int l = 0; l < 64; ++l) {
+                    const int n = l & 15, kq = l >> 4, ky = step >> 1, kx = 4 * (step & 1) + kq;
+                    if (kx >= 7) continue;
+                    _Float16* const frag = wp.data() + hf * per_half + ((size_t)(step * 2) * 64 + l) * 8;      // hi; lo 64 lanes on
+                    for (int j = 0; j < 8; ++j) {
+                        const int ci = chmap1[8 * hf + j];
+                        if (ci < 0 || ci >= cin_tf) continue;
+                        const float v = t.data[(((size_t)ky * 7 + kx) * cin_tf + ci) * 16 + n] * L.wscale;
+                        split_f16(v, frag + j, frag + 64 * 8 + j);
+                    }
                 }
-            }
         int rc = upload_n(c, wp.data(), wp.size() * sizeof(_Float16), &c->d_w1patch);
         if (rc) return rc;
     }

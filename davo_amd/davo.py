@@ -141,6 +141,12 @@ class Engine:
             except Exception:
                 self.close()
                 raise
+        if cfg.posenn == "triplet":               # `-dilatedPoseNN' without `-sharedNN': likewise before any weight (davo_set_posenn_topology)
+            try:
+                self._check(self._L.davo_set_posenn_topology(self._ctx, _lib.POSENN_TRIPLET))
+            except Exception:
+                self.close()
+                raise
         if labels != "f32":
             try:
                 self.set_label_format(labels)

@@ -163,6 +163,11 @@ def main(argv=None):
         ap.error(str(exc))
     except FileNotFoundError as exc:
         raise SystemExit("davo_amd.run_kitti_pose: %s" % exc)
+    from .version import parse_version
+    if a.pairs != "both" and parse_version(a.version).posenn == "triplet":
+        # one pass of the three-frame PoseNN yields both poses of a window: there is no single pair to leave out
+        ap.error("--pairs %s: version `%s' is the three-frame PoseNN (`-dilatedPoseNN' without `-sharedNN'), whose one pass per window "
+                 "yields both poses; it runs with --pairs both only" % (a.pairs, a.version))
     from .comm import RcclComm, world_from_env, preload_in_background
     rank, local_rank, world = world_from_env()
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:

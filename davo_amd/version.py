@@ -63,6 +63,9 @@ class VariantConfig:
                              # not a davo_variant field: Engine hands it to davo_set_posenn_se
     depth_thres_init: float = 15.0   # -se_flow_on_depthseg_.*layers_([0-9.]+): initialiser of se_flow/depth_threshold (davo.py:1136-1141);
                                      # inference uses the loaded value, so this only reaches synth.make_weights
+    posenn: str = "pairs"    # pairs | triplet: decouple_sharednet_v0_dilation on two (tgt, src) images per window, or
+                             # decouple_net_v0_dilation on one (tgt, src0, src1) image (davo.py:1038-1040, nets/posenn.py:69-131);
+                             # not a davo_variant field: Engine hands it to davo_set_posenn_topology
 
     @property
     def cin_per_frame(self):
@@ -180,9 +183,18 @@ def parse_version(version):
             raise NameError("not support `-sharedNN-couplePoseNN' mode.")      # davo.py:1035
         else:
             raise NameError("unknown PoseNN type.")                            # davo.py:1037
+        posenn = "pairs"
+    elif "-dilatedPoseNN" in v:
+        posenn = "triplet"                              # decouple_net_v0_dilation: one (tgt, src0, src1) image per window
+    elif "-dilatedCouplePoseNN" in v:
+        raise UnsupportedVariantError("version `%s': couple_net_v0_dilation is not supported (without `-sharedNN' only "
+                                      "`-dilatedPoseNN', decouple_net_v0_dilation, runs)." % v)
+    elif "-couplePoseNN" in v:
+        raise UnsupportedVariantError("version `%s': couple_net_v0 is not supported (without `-sharedNN' only "
+                                      "`-dilatedPoseNN', decouple_net_v0_dilation, runs)." % v)
     else:
-        raise UnsupportedVariantError(
-            "version `%s': only the `-sharedNN-dilatedPoseNN' network is supported." % v)
+        raise UnsupportedVariantError("version `%s': decouple_net_v0 (no PoseNN substring) is not supported: only the "
+                                      "`-sharedNN-dilatedPoseNN' and `-dilatedPoseNN' networks are." % v)
 
     for s in ("-batch_norm", "-dropout", "-seglabelid"):
         if s in v:
@@ -268,17 +280,35 @@ def parse_version(version):
         mask_rgb = "-segmask" in v
         mask_info = False
 
+    if posenn == "triplet":
+        # the three-frame network (davo.py:1460): every source that ends in the [B,3,19] class table the packer reads runs; the depth
+        # planes and the feature-attention block have no three-frame form here
+        if att_source in _DEPTH_SOURCES:
+            raise UnsupportedVariantError("version `%s': the depth sources (`%s') are not supported with the three-frame "
+                                          "`-dilatedPoseNN' network (decouple_net_v0_dilation)." % (v, att_source))
+        if posenn_se != "none":
+            raise UnsupportedVariantError("version `%s': `-se_insert' is not supported with the three-frame `-dilatedPoseNN' "
+                                          "network (decouple_net_v0_dilation)." % v)
+        if att_source != "ones" and not mask_rgb:
+            # the precedent of `-se_insert' beside an attention source: a graph whose attention nothing applies is not built
+            raise UnsupportedVariantError("version `%s': attention source `%s' without `-segmask' would be built and never read; "
+                                          "the three-frame network runs an attention source only where it is applied." % (v, att_source))
+
     return VariantConfig(version=v, major=major, use_flow_info=use_flow_info, cnv6_out=cnv6_out,
                          se_act=se_act, norm_flow=norm_flow, abs_mode=abs_mode,
                          att_source=att_source, mask_rgb=mask_rgb, mask_info=mask_info, posenn_se=posenn_se,
-                         depth_thres_init=depth_thres_init)
+                         depth_thres_init=depth_thres_init, posenn=posenn)
 
 
 def weight_shapes(cfg):
     """TF checkpoint names -> shapes for a variant (SURVEY table W; scopes from
     nets/posenn.py:203,221-223,240, nets/attention_module.py:63,94,101,
     nets/posenn.py:386-388)."""
-    c10 = 2 * cfg.cin_per_frame
+    triplet = cfg.posenn == "triplet"
+    # cnv1 reads concat(tgt, src) - or concat(tgt, src0, src1) in the three-frame network, whose pred has 3 * num_source outputs
+    # (nets/posenn.py:78,120)
+    c10 = (3 if triplet else 2) * cfg.cin_per_frame
+    npred = 6 if triplet else 3
     c6 = cfg.cnv6_out
     sh = {
         "pose_exp_net/cnv1/weights": (7, 7, c10, 16), "pose_exp_net/cnv1/biases": (16,),
@@ -293,8 +323,8 @@ def weight_shapes(cfg):
         sh[p + "cnv6/biases"] = (c6,)
         sh[p + "cnv7/weights"] = (3, 3, c6, 256)
         sh[p + "cnv7/biases"] = (256,)
-        sh[p + "pred/weights"] = (1, 1, 256, 3)
-        sh[p + "pred/biases"] = (3,)
+        sh[p + "pred/weights"] = (1, 1, 256, npred)
+        sh[p + "pred/biases"] = (npred,)
         if cfg.posenn_se == "insert":               # se_block(cnv5, 'cnv5_se_attention', ratio=8): nets/attention_module.py:37-49
             q = p + "cnv5_se_attention/"
             sh[q + "bottleneck_fc/kernel"] = (256, 256 // 8)

@@ -90,6 +90,30 @@ int davo_create(davo_ctx** out, int device, int H, int W, int max_batch, const d
  * unchanged; `-se_skipadd' and `-se_replace' are not built. */
 int davo_set_posenn_se(davo_ctx* ctx, int mode);
 
+/* The PoseNN's topology (davo.py:1027-1049), which is not part of davo_variant either.  DAVO_POSENN_PAIRS (the default) is
+ * `-sharedNN-dilatedPoseNN', decouple_sharednet_v0_dilation: two (tgt, src) images per window through shared weights.
+ * DAVO_POSENN_TRIPLET is `-dilatedPoseNN' without `-sharedNN', decouple_net_v0_dilation (nets/posenn.py:69-131): ONE image
+ * concat(tgt, src0, src1) per window, one pass through cnv1..cnv7, and a pred of 3 * 2 outputs per head:
+ *   pose[b][s][3 * head + k] = 0.01 * mean(pred_head)[b][3 * s + k],  s = 0 for tgt->src0, 1 for tgt->src1, head 0 = rotation.
+ * The variables keep their names; pose_exp_net/cnv1/weights becomes (7,7,3 * cin_per_frame,16), each head's pred/weights
+ * (1,1,256,6) and pred/biases (6,).  Inputs, their layouts and the [B,2,6] output are unchanged, and every pose entry point
+ * works as before in both label and both flow formats (davo_forward, davo_forward_device, davo_submit / davo_wait,
+ * davo_calibrate, the three `_frames' calls), with the same range recovery.  The masking is davo.py:1415-1450's: with v1 the
+ * network reads tgt rgb*att_t | 0 0 | src0 rgb*att_0 | flow0*att_0 | src1 rgb*att_1 | flow1*att_1.  On the device the two zero
+ * channels are dropped and the packed tensor has 16 channels per pixel, in this order:
+ *   tgt rgb (3) | src0 rgb (3) | flow0 (2) | src1 rgb (3) | flow1 (2) | 0 0 0      (v0: the flow slots are zero)
+ * davo_debug_read sizes "packed" as [B,H,W,16] and "cnv1".."cnv7" by B images.
+ * Valid only before the first davo_load_weight and the first forward, like davo_set_posenn_se: afterwards DAVO_ERR_INVALID.
+ * DAVO_ERR_INVALID as well on a context whose att_source is 11..13 (the depth sources have no three-frame form), after
+ * davo_set_posenn_se(ctx, 1), after davo_set_pairs with anything but DAVO_PAIRS_BOTH, with impl 1 set or an export switched on.
+ * On a triplet context davo_set_pairs accepts DAVO_PAIRS_BOTH only (one pass yields both poses), davo_set_impl(ctx, 1),
+ * davo_set_posenn_se(ctx, 1), davo_set_feature_export(ctx, 1) and davo_set_heat_export(ctx, 1) return DAVO_ERR_INVALID (the
+ * exports of the three-frame network are a follow-up), cnv7 is stored and the pose head runs as two launches: the option
+ * "fuse_pose" 1 is accepted and has no effect (a six-column fused epilogue is a follow-up).  cnv1 runs on an LDS-patch kernel of
+ * its own or on the implicit GEMM at 16 input channels: option "patch_cnv1_t" below. */
+enum { DAVO_POSENN_PAIRS = 0, DAVO_POSENN_TRIPLET = 1 };
+int davo_set_posenn_topology(davo_ctx* ctx, int topology);
+
 /* Label format.  A label map is a class id per pixel, and nothing on the path reads more of it than "class 0..18, or none"; the
  * reference's preprocessing stores it as float32 [B,3,H,W,1] (data_loader.py:313-317), which is what every entry point takes by
  * default (DAVO_LABELS_F32).  davo_set_label_format(ctx, DAVO_LABELS_U8) makes the context take bytes instead: uint8 [B,3,H,W,1],
@@ -578,6 +602,11 @@ const char* davo_range_report(const davo_ctx* ctx);
  *   "patch_cnv2", "patch_cnv3" (default 1): cnv2 (5x5 stride 2) / cnv3 (3x3 dilation 2) read their taps from an LDS-staged
  *       input patch (csrc/conv_patch_h3.h); 0 = the implicit-GEMM kernel.  The two sum a pixel's taps in different orders:
  *       poses agree to float32 rounding.
+ *   "patch_cnv1_t" (default 1; three-frame PoseNN, davo_set_posenn_topology, f16x3 only): cnv1 at 16 packed channels reads its
+ *       taps from an LDS-staged patch, two 8-channel passes per tile (csrc/conv_patch_h3.h, conv_patch_cnv1t_h3); 0 = the
+ *       implicit-GEMM kernel at cin = 16.  Measured in one process, arms interleaved, 128x416: 54.8 against 112.6 us at B = 32,
+ *       12.1 against 23.3 us at B = 1 (profiles/three_frame_measure.log).  The two sum a pixel's products in different orders:
+ *       poses agree to float32 rounding.  No effect on a pairs context or in float32 mode (conv_igemm_f32 at cin = 16 there).
  *   "merge_rem" (default 1): where cnv5 / cnv6 are planned as a main launch of 256x256 tiles plus a remainder launch of
  *       128x128 tiles (B = 32), both run as ONE grid in which half of the CUs take their remainder tile first and the other
  *       half last (csrc/conv_igemm_h3.h, conv_igemm_h3_mainrem): the halves' store bursts no longer coincide.  0 = two

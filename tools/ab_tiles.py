@@ -1,9 +1,10 @@
 #!/usr/bin/env python
 """A/B of launch plans in ONE process on one GPU (cdna_hip_programming.md §5.4 rule 24): per-kernel HIP-event times
-of the flagship path with the f16x3 layers forced onto one tile shape (davo_set_option "force_tile") or planned.
+of the flagship path (or `--version`'s) with the f16x3 layers forced onto one tile shape (davo_set_option "force_tile") or planned.
 
     python tools/ab_tiles.py [--batch 32] [--tiles -1,5,6] [--rounds 3] [--steps 10] [--options k=v,...]
     python tools/ab_tiles.py --arms "patch_cnv2=1;patch_cnv2=0"      # arms = option sets instead of tile shapes
+    python tools/ab_tiles.py --version v1-...-dilatedPoseNN-... --arms "patch_cnv1_t=1;patch_cnv1_t=0"      # another variant's path
 """
 import argparse
 import os
@@ -25,9 +26,10 @@ def main():
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--options", default="", help="extra davo_set_option pairs applied to every arm, k=v,k=v")
     ap.add_argument("--arms", default="", help="arms as option sets 'k=v,k=v;k=v,...' (interleaved in one process) instead of --tiles")
+    ap.add_argument("--version", default=FLAGSHIP_VERSION, help="the variant whose path is measured (default: the flagship)")
     ap.add_argument("--inflight", type=int, default=1, help="batches in flight (consecutive calls rotate through that many streams)")
     a = ap.parse_args()
-    cfg = parse_version(FLAGSHIP_VERSION)
+    cfg = parse_version(a.version)
     B, H, W = a.batch, a.height, a.width
     e = Engine(cfg, H, W, B)
     e.load_weights(synth.make_weights(cfg))
