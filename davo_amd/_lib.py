@@ -51,6 +51,7 @@ EXPORTS = (
     "davo_pad_class_tables", "davo_pad_class_tile_order", "davo_plan_layer_f32", "davo_decide_layer",
     "davo_forward_frames", "davo_submit_frames", "davo_forward_device_frames", "davo_frames_plan",
     "davo_set_flow_format", "davo_get_flow_format", "davo_frames_plan_fmt", "davo_pool_plan",
+    "davo_set_flip", "davo_get_flip",
 )
 COMM_ID_BYTES = 128
 LABELS_F32, LABELS_U8 = 0, 1          # DAVO_LABELS_F32, DAVO_LABELS_U8 (davo_set_label_format)
@@ -233,6 +234,8 @@ def _load():
     L.davo_get_label_format.argtypes = [vp]
     L.davo_set_flow_format.argtypes = [vp, i]
     L.davo_get_flow_format.argtypes = [vp]
+    L.davo_set_flip.argtypes = [vp, i]
+    L.davo_get_flip.argtypes = [vp]
     L.davo_set_feature_export.argtypes = [vp, i]
     L.davo_forward_features.argtypes = [vp, i, vp, vp, vp, vp, vp, ctypes.POINTER(DavoFeatureOut)]
     L.davo_set_heat_export.argtypes = [vp, i]

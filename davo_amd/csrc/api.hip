@@ -346,7 +346,9 @@ static int calibrate_entry(davo_ctx* c, int B, Batch b, int* shifts_out) {
     { int rc = freeze_pending_and_reset_ring(c); if (rc) return rc; }
     DevMem<float> d_pose;
     HIP_TRY(c, dev_alloc(&d_pose, (size_t)B * 12));
-    const int rc = calibrate_on(c, B, b.win, d_pose.get(), PAIRS_BOTH);
+    Inputs in = b.win;
+    if (c->flip) { int rc = mirror_device_batch(c, b.win, B, &in); if (rc) return rc; }      // the caller's buffers are only read
+    const int rc = calibrate_on(c, B, in, d_pose.get(), PAIRS_BOTH);
     if (rc == DAVO_OK && shifts_out) for (int i = 0; i < 6; ++i) shifts_out[i] = c->act_shift[i];
     return rc;
 }
@@ -498,6 +500,15 @@ int davo_set_pairs(davo_ctx* c, int pairs) {
 }
 
 int davo_get_pairs(const davo_ctx* c) { return c ? c->pairs : DAVO_ERR_INVALID; }
+
+int davo_set_flip(davo_ctx* c, int on) {
+    if (!c) return DAVO_ERR_INVALID;
+    if (on != 0 && on != 1) return fail(c, DAVO_ERR_INVALID, "flip must be 0 (off) or 1 (on), got %d", on);
+    c->flip = on != 0;             // batches in flight are staged already; their re-issues read the mirrored copy (entry.hip: Stager)
+    return DAVO_OK;
+}
+
+int davo_get_flip(const davo_ctx* c) { return c ? (c->flip ? 1 : 0) : DAVO_ERR_INVALID; }
 
 int davo_set_impl(davo_ctx* c, int impl) {
     if (!c || (impl != 0 && impl != 1)) return fail(c, DAVO_ERR_INVALID, "impl must be 0 (mfma) or 1 (direct)");

@@ -14,7 +14,7 @@
 //   launch_f32.hip  conv_igemm_f32 instantiations + dispatch
 //   launch_h3.hip   conv_igemm_h3 instantiations + dispatch (the f16x3 path, the long compile)
 //   launch_h3s.hip  conv_igemm_h3s instantiations (208x256 tile); launch_h3_generic.hip: davo_conv2d_same's shapes
-//   launch_misc.hip prologue / pooled squeeze and excite (se_pool.h) / pose head / cnv1..cnv3 patch / feature-attention (posenn_se.h) / direct-convolution kernels + dispatch
+//   launch_misc.hip prologue / pooled squeeze and excite (se_pool.h) / pose head / cnv1..cnv3 patch / feature-attention (posenn_se.h) / window gather and mirror (window_gather.h, window_mirror.h) / direct-convolution kernels + dispatch
 //   launch_feature.hip  the feature export kernels (feature_export.h) + dispatch
 //   comm.hip        RCCL communicator behind the C ABI (pose gather of the window-sharded driver)
 // owned.h holds the owner types (device / page-locked memory, streams, events): everything a context allocates is a member of
@@ -263,6 +263,8 @@ struct davo_ctx {
     size_t act_floats_per_img[7];
     int act_ch[7];
     int pairs = davo::PAIRS_BOTH;              // davo_set_pairs: the pairs of every window the batches issued from now on run
+    bool flip = false;                         // davo_set_flip: the batches issued from now on are mirrored left-right where they are staged (window_mirror.h); a batch in
+                                               // flight is past that step and its re-issues read the mirrored staging set or snapshot, so neither mirrors again
     // The last forward, as reported: written by forward_device, read by davo_debug_read / davo_last_plan / the feature export
     // alone (last_slot also by last_stream() below) - never an input of a forward
     int last_slot = 0;                         // its slot; 0 again after davo_create, davo_set_posenn_se, davo_set_stream and a rebuild of the slot streams
@@ -447,6 +449,7 @@ Inputs from_window(const davo_ctx* c, const Inputs& in, int b0);               /
 int forward_entry(davo_ctx* c, int B, Batch b, float* pose_out, Exports ex = Exports{});      // davo_forward's body, with the exports wanted
 int deliver_all(davo_ctx* c);                                                  // every davo_submit batch still under way, in issue order
 void drain_own_streams(davo_ctx* c);
+int mirror_device_batch(davo_ctx* c, const Inputs& in, int B, Inputs* out);    // davo_calibrate with flip on: the batch mirrored into slot 0's staging set
 
 // ---- range_guard.hip: what the entry points need of the f16x3 range guard --------------------
 int ensure_ring(davo_ctx* c, bool snapshots);                                  // the records' host mirrors (and the ring's input snapshots)

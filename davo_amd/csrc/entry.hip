@@ -10,6 +10,7 @@
 #include "launch.h"
 #include "pool_plan.h"
 #include "window_gather.h"
+#include "window_mirror.h"
 
 using namespace davo;
 
@@ -34,6 +35,9 @@ int davo::check_batch(davo_ctx* c, Batch* b, int B, bool out_given, int hold) {
     // a binary16 flow is read in 16-byte units of four pixels (input_decode.h: flow_fetch4): on the device its base is 16-byte aligned
     if (c->flow_fmt == FLOW_F16 && b->on_device && b->layout == Layout::Windows && ((uintptr_t)b->win.flow & 15))
         return fail(c, DAVO_ERR_INVALID, "%s: a binary16 device flow buffer (davo_set_flow_format) must be 16-byte aligned", b->fn);
+    // flip on: window_mirror reads the caller's device buffers in 16-byte units
+    if (c->flip && b->on_device && b->layout == Layout::Windows && (((uintptr_t)b->win.img | (uintptr_t)b->win.flow | (uintptr_t)b->win.seg | (uintptr_t)b->win.depth) & 15))
+        return fail(c, DAVO_ERR_INVALID, "%s: with davo_set_flip on, device input buffers must be 16-byte aligned", b->fn);
     if (b->layout == Layout::Frames && b->on_device && (((uintptr_t)b->fr.frames | (uintptr_t)b->fr.flow2 | (uintptr_t)b->fr.seg | (uintptr_t)b->fr.depth) & 15))
         return fail(c, DAVO_ERR_INVALID, "%s: device input buffers must be 16-byte aligned", b->fn);
     return DAVO_OK;
@@ -152,8 +156,8 @@ int stage_frames(davo_ctx* c, const FrameSet& fs, const InputSet& set, const Fra
 }
 
 // window_gather on stream s: windows [b0, b0 + nb) of `set' from frames [b0, b0 + nb + 2) of `fr' (device pointers, frame 0 of the
-// call); fr.flow2 null: the flow is in the set already
-int gather_windows(davo_ctx* c, const InputSet& set, const FrameInputs& fr, int b0, int nb, int sel, hipStream_t s) {
+// call); fr.flow2 null: the flow is in the set already.  flip: the same launch stores every row mirrored (window_mirror.h)
+int gather_windows(davo_ctx* c, const InputSet& set, const FrameInputs& fr, int b0, int nb, int sel, bool flip, hipStream_t s) {
     const PlaneBytes f = frame_bytes(c), n = plane_bytes(c);
     const FramePlan p = frame_plan(nb, sel, c->v.att_source);
     auto src = [b0](const void* q, size_t per) { return q ? static_cast<const uint8_t*>(q) + per * b0 : nullptr; };
@@ -162,7 +166,23 @@ int gather_windows(davo_ctx* c, const InputSet& set, const FrameInputs& fr, int 
                        dst(set.img, n.img), dst(set.seg, n.seg), dst(set.depth, n.depth), dst(set.flow, n.flow),
                        c->H, c->W, sel, p.seg_tgt, p.depth_tgt};
     ProfScope ps(c, s, "window_gather");
-    HIP_TRY(c, launch_window_gather(a, nb, c->label_fmt, c->flow_fmt, s));
+    // (the mirrored form leaves out the target's label map where the variant does not attend it: no kernel reads it)
+    if (flip) HIP_TRY(c, launch_window_mirror(a, nb, true, c->label_fmt, c->flow_fmt, s));
+    else HIP_TRY(c, launch_window_gather(a, nb, c->label_fmt, c->flow_fmt, s));
+    return DAVO_OK;
+}
+
+// window_mirror on stream s: windows [b0, b0 + nb) of `set' mirrored left-right - in place (from null: the copies of stage_inputs
+// are there), or from the caller's device buffers `from' (window 0 of the batch), which are only read.  seg_tgt: the target's label
+// map is among what the set holds and the batch reads.  Only what the selection and the variant read is touched.
+int mirror_windows(davo_ctx* c, const InputSet& set, const Inputs* from, int b0, int nb, int sel, bool seg_tgt, hipStream_t s) {
+    const Inputs dst = from_window(c, set.view(), b0), src = from ? from_window(c, *from, b0) : dst;
+    auto rd = [](const void* q) { return static_cast<const uint8_t*>(q); };
+    auto wr = [](const void* q) { return const_cast<uint8_t*>(static_cast<const uint8_t*>(q)); };
+    const GatherArgs a{rd(src.img), rd(src.seg), dst.depth ? rd(src.depth) : nullptr, rd(src.flow), wr(dst.img), wr(dst.seg), wr(dst.depth), wr(dst.flow),
+                       c->H, c->W, sel, seg_tgt, att_desc_depth(c->v.att_source)};
+    ProfScope ps(c, s, "window_mirror");
+    HIP_TRY(c, launch_window_mirror(a, nb, false, c->label_fmt, c->flow_fmt, s));
     return DAVO_OK;
 }
 
@@ -171,10 +191,14 @@ int gather_windows(davo_ctx* c, const InputSet& set, const FrameInputs& fr, int 
 // set hold them as windows.  Window layout: stage_inputs, then nothing.  Frame layout: stage_frames into the slot's frame buffer
 // (a frame crosses the link once per call: cur), then gather_windows from it - or, for a batch on the device, nothing and then
 // gather_windows from the caller's buffers.  A window batch on the device has no set: its forward reads the caller's buffers.
+// With flip on (davo_set_flip, as it stood when the batch was issued) the second step also mirrors: the frame layout inside its one
+// gather launch; the window layout from the host with one window_mirror launch on the set, in place; a window batch on the device
+// gets the slot's staging set after all and is mirrored into it from the caller's buffers, which are never written.
 enum class Path { Device, Submit, Forward };
 struct Stager {
     davo_ctx* c;
     Batch b;
+    bool flip = false;                         // the context's setting when the batch was issued
     const InputSet* set = nullptr;             // the path's staging set of the slot (null: none, see above)
     const FrameSet* fs = nullptr;              // frame layout from the host: the slot's frame buffer
     bool sources_only_seg = false;             // stage_inputs': davo_submit's batches
@@ -185,7 +209,7 @@ struct Stager {
 // The stager of batch b in `slot'; builds what the path keeps per slot at its first use, each group whole: davo_forward's staging
 // (slot 0), davo_submit's pose ring and the slot's staging set, the slot's frame buffer for frames that come from the host.
 int acquire_stager(davo_ctx* c, const Batch& b, Path path, int slot, Stager* st) {
-    *st = Stager{c, b};
+    *st = Stager{c, b, c->flip};
     if (path == Path::Forward) {
         if (!c->host) {
             HostStaging h;
@@ -200,7 +224,7 @@ int acquire_stager(davo_ctx* c, const Batch& b, Path path, int slot, Stager* st)
         { int rc = ensure_stream_state(c, slot); if (rc) return rc; }
         st->set = &c->stream_sets[slot];
         st->sources_only_seg = true;
-    } else if (b.layout == Layout::Frames) {
+    } else if (b.layout == Layout::Frames || st->flip) {
         if (!c->stream_sets[slot].built()) { int rc = alloc_input_set(c, &c->stream_sets[slot], true); if (rc) return rc; }
         st->set = &c->stream_sets[slot];
     }
@@ -218,10 +242,27 @@ int stage_upload(Stager* st, int b0, int nb, hipStream_t s) {
 }
 
 int stage_windows(Stager* st, int b0, int nb, hipStream_t s) {
-    if (st->b.layout != Layout::Frames) return DAVO_OK;
+    davo_ctx* c = st->c;
+    if (st->b.layout != Layout::Frames) {
+        if (!st->flip) return DAVO_OK;
+        // the target's label map is read only where the variant attends it (davo_submit's staging does not even copy it otherwise)
+        return mirror_windows(c, *st->set, st->b.on_device ? &st->b.win : nullptr, b0, nb, c->pairs, att_tgt_attended(c->v.att_source), s);
+    }
     const FrameInputs dev = st->fs ? FrameInputs{st->fs->img.get(), nullptr, st->fs->seg.get(), st->fs->depth.get()} : st->b.fr;
-    return gather_windows(st->c, *st->set, dev, b0, nb, st->c->pairs, s);
+    return gather_windows(c, *st->set, dev, b0, nb, c->pairs, st->flip, s);
 }
+
+}  // namespace
+
+// davo_calibrate's batch with flip on: B windows of the caller's device buffers mirrored into slot 0's staging set on its stream
+// (every stream is idle); *out = what the calibration passes read
+int davo::mirror_device_batch(davo_ctx* c, const Inputs& in, int B, Inputs* out) {
+    if (!c->stream_sets[0].built()) { int rc = alloc_input_set(c, &c->stream_sets[0], true); if (rc) return rc; }
+    *out = c->stream_sets[0].view();
+    return mirror_windows(c, c->stream_sets[0], &in, 0, B, PAIRS_BOTH, att_tgt_attended(c->v.att_source), slot_stream(c, 0));
+}
+
+namespace {
 
 // the oldest undelivered batch: verdict (and re-issue) first, then its poses go to the caller's array
 int deliver_front(davo_ctx* c) {

@@ -90,6 +90,10 @@ hipError_t launch_mask_pack3(bool h3, const uint8_t* d_img, const void* d_flow, 
 // aligned; a.f_flow null = the flow planes are in place already (the host entry points copy them there)
 struct GatherArgs;
 hipError_t launch_window_gather(const GatherArgs& a, int N, int label_fmt, int flow_fmt, hipStream_t s);
+// window_mirror.h: N windows mirrored left-right (davo_set_flip).  frames: the gather above with mirrored stores, a's meaning
+// unchanged; else a.f_* are window-major like a.w_* - the same pointers (in place) or a caller's buffers - and a.f_flow is required.
+// a.seg_tgt: the target's label map is read at all.  Every pointer 16-byte aligned
+hipError_t launch_window_mirror(const GatherArgs& a, int N, bool frames, int label_fmt, int flow_fmt, hipStream_t s);
 // cnv1 / cnv2 / cnv3 (layer 0..2) from an LDS-staged input patch: conv_patch_cnvN_h3, or conv_patch_cnvN_f32 in float32 mode (f32);
 // fused: conv_patch_cnv1_h3<true, float | uint8_t, float | flow_f16> by label_fmt and flow_fmt (f16x3 cnv1 only; p.seg and p.flow are in those formats)
 hipError_t launch_patch_layer(int layer, bool f32, bool fused, const ConvPatchParams& p, int nblk, hipStream_t s, int label_fmt = LABELS_F32,

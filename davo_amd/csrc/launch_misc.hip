@@ -13,6 +13,7 @@
 #include "prologue.h"
 #include "se_pool.h"
 #include "window_gather.h"
+#include "window_mirror.h"
 
 namespace davo {
 
@@ -240,6 +241,37 @@ hipError_t launch_window_gather(const GatherArgs& a, int N, int label_fmt, int f
         if (label_fmt == LABELS_U8) hipLaunchKernelGGL((window_gather<uint8_t, flow_f32>), grid, dim3(256), 0, s, a);
         else hipLaunchKernelGGL((window_gather<float, flow_f32>), grid, dim3(256), 0, s, a);
     }
+    return hipGetLastError();
+}
+
+namespace {
+template <bool FRAMES>
+void window_mirror_as(const GatherArgs& a, const dim3& grid, int label_fmt, int flow_fmt, hipStream_t s) {
+    if (flow_fmt == FLOW_F16) {
+        if (label_fmt == LABELS_U8) hipLaunchKernelGGL((window_mirror<uint8_t, flow_f16, FRAMES>), grid, dim3(256), 0, s, a);
+        else hipLaunchKernelGGL((window_mirror<float, flow_f16, FRAMES>), grid, dim3(256), 0, s, a);
+    } else {
+        if (label_fmt == LABELS_U8) hipLaunchKernelGGL((window_mirror<uint8_t, flow_f32, FRAMES>), grid, dim3(256), 0, s, a);
+        else hipLaunchKernelGGL((window_mirror<float, flow_f32, FRAMES>), grid, dim3(256), 0, s, a);
+    }
+}
+}  // namespace
+
+hipError_t launch_window_mirror(const GatherArgs& a, int N, bool frames, int label_fmt, int flow_fmt, hipStream_t s) {
+    if (N < 1 || a.H < 1 || a.W < 4 || a.W % 4 || ((size_t)a.H * a.W) % 16 || !a.f_img || !a.f_seg || !a.w_img || !a.w_seg || !a.w_flow ||
+        (a.f_depth && !a.w_depth) || (!frames && !a.f_flow))
+        return hipErrorInvalidValue;
+    if (((uintptr_t)a.f_img | (uintptr_t)a.f_seg | (uintptr_t)a.f_depth | (uintptr_t)a.f_flow | (uintptr_t)a.w_img | (uintptr_t)a.w_seg |
+         (uintptr_t)a.w_depth | (uintptr_t)a.w_flow) & 15)
+        return hipErrorInvalidValue;
+    if (!flow_fmt_ok(flow_fmt) || (label_fmt != LABELS_F32 && label_fmt != LABELS_U8)) return hipErrorInvalidValue;
+    // the job with the most unit pairs decides the pieces per job: a flow plane (four pixels a unit, half as many pairs a row); at
+    // most 8, the rest in rounds
+    const size_t pairs = (size_t)a.H * ((a.W / 4 + 1) / 2);
+    const unsigned gx = (unsigned)std::min<size_t>(8, (pairs + MIRROR_PIECE - 1) / MIRROR_PIECE);
+    const dim3 grid(gx, (unsigned)N, GATHER_JOBS);
+    if (frames) window_mirror_as<true>(a, grid, label_fmt, flow_fmt, s);
+    else window_mirror_as<false>(a, grid, label_fmt, flow_fmt, s);
     return hipGetLastError();
 }
 

@@ -14,6 +14,7 @@ import numpy as np
 from . import _lib
 from .labels import LABEL_DTYPES, LABEL_FORMATS, check_label_format, labels_to_u8  # noqa: F401
 from .flow import FLOW_DTYPES, FLOW_FORMATS, check_flow_format, flow_from_f16, flow_to_f16  # noqa: F401
+from .frames import flip_windows
 from .version import NUM_SEG_CLASSES, att_source_id, parse_version, weight_shapes
 
 
@@ -488,6 +489,18 @@ class Engine:
                 return name
         raise DavoError("davo_get_pairs returned %d" % v)
 
+    def set_flip(self, on):
+        """Mirror the inputs of the batches issued from now on left-right, on the device (include/davo_hip.h: davo_set_flip): the
+        engine then computes on X what it computes with flip off on ``davo_amd.flip_windows(X)`` (``flip_frames`` for the frame
+        layout), bit for bit.  Off by default; may be switched between batches at any time, batches in flight keep theirs."""
+        if on not in (0, 1, False, True):
+            raise ValueError("flip must be True or False, got %r" % (on,))
+        self._check(self._L.davo_set_flip(self._ctx, int(on)))
+
+    @property
+    def flip(self):
+        return bool(self._L.davo_get_flip(self._ctx))
+
     def set_impl(self, impl):
         self._check(self._L.davo_set_impl(self._ctx, {"mfma": 0, "direct": 1}.get(impl, impl)))
 
@@ -624,7 +637,9 @@ def host_maps(cfg, img, seg, tables, depth=None, tables_far=None, thr=None):
 class DAVO(object):
     """Drop-in for the reference class on the inference path (reference davo.py:30)."""
 
-    def __init__(self, version=None, att_19=None, device=0):
+    def __init__(self, version=None, att_19=None, device=0, flip=False):
+        """``flip``: mirror every batch left-right on the device (Engine.set_flip; include/davo_hip.h: davo_set_flip) - for a
+        flip-trained checkpoint or the mirrored sequences (poses-flip); ``setup_inference(..., flip=...)`` overrides it."""
         self.version = version          # davo.py:32
         self.att_19 = att_19            # davo.py:33 (unused on the pose path)
         self.device = device
@@ -634,6 +649,7 @@ class DAVO(object):
         self._features = 'full'
         self._labels = "f32"
         self._flow = "f32"
+        self._flip = bool(flip)
 
     def use_f16_flow(self):
         """Opt in to binary16 flow (include/davo_hip.h: davo_set_flow_format): ``input_flow``, ``inference(inputs=...)`` and
@@ -675,11 +691,13 @@ class DAVO(object):
 
     def setup_inference(self, img_height, img_width, mode, seq_length=3, batch_size=1,
                         input_img_uint8=None, input_pose=None, input_flow=None, input_depth=None,
-                        input_seglabel=None):
+                        input_seglabel=None, flip=None):
         """davo.py:1533-1551.  ``input_*`` are numpy arrays ([B,H,3W,3] u8, [B,4,H,W,2] f32,
         [B,3,H,W,1] f32) or ``input_img_uint8`` is an iterator yielding (img, flow, seg) - (img, flow, seg, depth)
         for a depth-source variant; ``input_depth`` ([B,3,H,W,1] f32, file order src0, tgt, src1: davo.py:991-996) is
-        kept for such a variant and ignored otherwise, ``input_pose`` is accepted and ignored, like the reference does."""
+        kept for such a variant and ignored otherwise, ``input_pose`` is accepted and ignored, like the reference does.
+        ``flip``: True / False mirrors the inputs on the device or not (Engine.set_flip); None keeps the constructor's choice.
+        Every output of ``inference`` is then what a flip-off DAVO returns on ``davo_amd.flip_windows`` of the same inputs."""
         self.img_height, self.img_width, self.mode, self.batch_size = img_height, img_width, mode, batch_size
         if self.mode != 'davo':
             return                                        # davo.py:1548: other modes do nothing
@@ -693,6 +711,10 @@ class DAVO(object):
         self.engine = Engine(self.cfg, img_height, img_width, batch_size, self.device, labels=self._labels, flow=self._flow)
         if self._weights is not None:
             self.engine.load_weights(self._weights)
+        if flip is not None:
+            self._flip = bool(flip)
+        if self._flip:
+            self.engine.set_flip(True)
         if self._feature_mode:
             self._switch_exports()
         self._ahead = []                                   # iterator inputs: batches submitted and not returned yet
@@ -766,17 +788,22 @@ class DAVO(object):
         if img is None or flow is None or seg is None:
             raise ValueError("image, flow and seglabel inputs are all required for version `%s'" % self.version)
         heat = self._features == 'heat'
+        if self._flip:                                         # the parts rebuilt on the host (seg_19, the heat mode's maps) see what the device saw
+            host_in = flip_windows(img, flow, seg, depth)
+            seg_seen, depth_seen, img_seen = host_in[2], (host_in[3] if depth is not None else None), host_in[0]
+        else:
+            seg_seen, depth_seen, img_seen = seg, depth, img
         # the depth-split flow attention has no att_19 (include/davo_hip.h): the library is asked for the other members only
         split = self.cfg.att_source == "se_flow_depthseg_sep"
         want = tuple(n for n in Engine.FEATURE_OUTPUTS if not (split and n == "att_19"))
-        r = self._forward_heat(img, flow, seg, depth) if heat else self.engine.forward_features(img, flow, seg, depth, want=want)
+        r = self._forward_heat(img, flow, seg, depth, (img_seen, seg_seen, depth_seen)) if heat else self.engine.forward_features(img, flow, seg, depth, want=want)
         if heat:
             inv = np.float32(1.0 / self.cfg.cnv6_out)          # a power of two: the mean is exact
             features = {'rot_sum': r['heat_rot'], 'trans_sum': r['heat_trans'], 'rot_avg': r['heat_rot'] * inv,
                         'trans_avg': r['heat_trans'] * inv, 'rot_max': r['max_rot'], 'trans_max': r['max_trans']}
         else:
             features = {'rot': r['feat_rot'], 'trans': r['feat_trans']}
-        one_hot = seg_one_hot(seg)                             # [B,3,H,W,19], file order src0, tgt, src1 (davo.py:998-1004)
+        one_hot = seg_one_hot(seg_seen)                         # [B,3,H,W,19], file order src0, tgt, src1 (davo.py:998-1004)
         return {'pose': r['pose'],
                 'masks': {'attention': [r['attention'][f][..., None] for f in range(3)],
                           'image': [r['masked_image'][f] for f in range(3)],
@@ -785,13 +812,14 @@ class DAVO(object):
                 'images': [r['image'][f] for f in range(3)],
                 'seg_19': [one_hot[:, plane] for plane in (1, 0, 2)]}
 
-    def _forward_heat(self, img, flow, seg, depth):
+    def _forward_heat(self, img, flow, seg, depth, seen):
         """Engine.forward_features' dict with the heat outputs in place of the two feature maps.  The device delivers the poses,
         planes and maxima (davo_forward_heat); the four maps are rebuilt by ``host_maps`` from the class tables of the forward,
         which the context holds for one sub-batch: a batch that davo_forward would split (2 x host_chunk windows or more) is
         issued here as those sub-batches, one call each - the same forwards, so the same poses (a range recovery then re-issues
-        a sub-batch, not the batch)."""
+        a sub-batch, not the batch).  ``seen``: (img, seg, depth) as the device read them - mirrored with flip on."""
         e = self.engine
+        seen = [None if a is None else np.asarray(a) for a in seen]
         img, flow, seg = np.asarray(img), np.asarray(flow), np.asarray(seg)
         depth = None if depth is None else np.asarray(depth)
         B = img.shape[0]
@@ -800,12 +828,13 @@ class DAVO(object):
         for b0 in range(0, B, step):
             part = [None if a is None else a[b0:b0 + step] for a in (img, flow, seg, depth)]
             r = e.forward_features(*part, want=Engine.HEAT_OUTPUTS)
+            s_img, s_seg, s_depth = [None if a is None else a[b0:b0 + step] for a in seen]
             tab_shape = (len(part[0]), 3, NUM_SEG_CLASSES)
             if self.cfg.att_source == "se_flow_depthseg_sep":
-                r.update(host_maps(self.cfg, part[0], part[2], e.debug_read("att_table", tab_shape), depth=part[3],
+                r.update(host_maps(self.cfg, s_img, s_seg, e.debug_read("att_table", tab_shape), depth=s_depth,
                                    tables_far=e.debug_read("att_table_far", tab_shape), thr=self._weights[DEPTH_THRESHOLD]))
             else:
-                r.update(host_maps(self.cfg, part[0], part[2], e.debug_read("att_table", tab_shape)))
+                r.update(host_maps(self.cfg, s_img, s_seg, e.debug_read("att_table", tab_shape)))
             parts.append(r)
         if len(parts) == 1:
             return parts[0]

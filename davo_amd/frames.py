@@ -78,6 +78,49 @@ def frames_from_windows(img, flow, seg, depth=None):
     return res + ((out["depth"],) if depth is not None else ())
 
 
+def flip_windows(img, flow, seg, depth=None):
+    """The left-right mirror of a window-layout batch as ``Engine.set_flip`` applies it on the device (include/davo_hip.h:
+    davo_set_flip) - the training loader's rule (data_loader.py:142-169): every frame mirrored inside its own third of the strip,
+    every flow plane, label map and depth plane mirrored on its own; no value changes (the horizontal flow component is not
+    negated), plane and frame order stay.  -> new C-contiguous ``(img, flow, seg)`` - ``(img, flow, seg, depth)`` with depth - of
+    the dtypes and shapes given ([B,H,3W,3]; [B,4,H,W,2]; [B,3,H,W,1] or [B,3,H,W])."""
+    img, flow, seg = np.asarray(img), np.asarray(flow), np.asarray(seg)
+    if img.ndim != 4 or img.shape[3] != 3 or img.shape[2] % 3:
+        raise ValueError("img shape %s is not [B,H,3W,3]" % (img.shape,))
+    B, H, W3 = img.shape[:3]
+    W = W3 // 3
+    if flow.shape != (B, 4, H, W, 2):
+        raise ValueError("flow shape %s != %s" % (flow.shape, (B, 4, H, W, 2)))
+
+    def planes(a, name):
+        if a.shape[:4] != (B, 3, H, W) or a.shape[4:] not in ((), (1,)):
+            raise ValueError("%s shape %s is not [B,3,H,W,1]" % (name, a.shape))
+        return np.ascontiguousarray(a[:, :, :, ::-1])
+
+    out = (np.ascontiguousarray(img.reshape(B, H, 3, W, 3)[:, :, :, ::-1]).reshape(B, H, W3, 3),
+           np.ascontiguousarray(flow[:, :, :, ::-1]), planes(seg, "seg"))
+    return out if depth is None else out + (planes(np.asarray(depth), "depth"),)
+
+
+def flip_frames(frames, flow2, seg, depth=None):
+    """flip_windows' rule on the frame layout: every frame, flow plane, label map and depth plane mirrored left-right on its own
+    (frames [N+2,H,W,3], flow2 [N,2,H,W,2], seg and depth [N+2,H,W,1] or [N+2,H,W]); dtypes and shapes are kept.
+    ``windows_from_frames(*flip_frames(...))`` is ``flip_windows(*windows_from_frames(...))``."""
+    frames, flow2, seg = np.asarray(frames), np.asarray(flow2), np.asarray(seg)
+    if frames.ndim != 4 or frames.shape[3] != 3:
+        raise ValueError("frames shape %s is not [N+2,H,W,3]" % (frames.shape,))
+    if flow2.ndim != 5 or flow2.shape[1:] != (2,) + frames.shape[1:3] + (2,):
+        raise ValueError("flow2 shape %s is not [N,2,H,W,2] of the frames %s" % (flow2.shape, frames.shape))
+
+    def planes(a, name):
+        if a.shape[:3] != frames.shape[:3] or a.shape[3:] not in ((), (1,)):
+            raise ValueError("%s shape %s is not [N+2,H,W,1] of the frames %s" % (name, a.shape, frames.shape))
+        return np.ascontiguousarray(a[:, :, ::-1])
+
+    out = (np.ascontiguousarray(frames[:, :, ::-1]), np.ascontiguousarray(flow2[:, :, :, ::-1]), planes(seg, "seg"))
+    return out if depth is None else out + (planes(np.asarray(depth), "depth"),)
+
+
 def frames_plan(H, W, N, pairs="both", att_source="se_flow", labels="f32", flow="f32"):
     """What a frame-layout batch of N windows reads (include/davo_hip.h: davo_frames_plan - the function the library's copies and
     its gather kernel are driven by; no GPU needed): ``{'frames', 'seg', 'depth', 'flow': (lo, hi), 'link_bytes': int}`` - frame

@@ -97,6 +97,10 @@ def build_parser():
     ap.add_argument("--labels", choices=("f32", "u8"), default="f32",
                     help="u8: the label maps are loaded and handed to the library as uint8 class ids (davo_set_label_format); "
                          "the written files are the same")
+    ap.add_argument("--flip", action="store_true",
+                    help="run the left-right mirrored sequence (include/davo_hip.h: davo_set_flip, each frame mirrored on its own); the "
+                         "files go under <output_dir>-flip, as the reference's flip switch appends `-flip' to its output root "
+                         "(generate_feature_map.py:118-129)")
     return ap
 
 
@@ -136,9 +140,11 @@ def main(argv=None):
     if n_frames < 3:
         raise SystemExit("davo_amd.generate_feature_map: sequence %.2d has %d frames: a window needs three" % (seq, n_frames))
     n_windows = n_frames - 2
+    if a.flip:
+        a.output_dir = a.output_dir.rstrip("/" + os.sep) + "-flip"
     map_dir = os.path.join(a.output_dir, "%.2d-featuremaps" % seq)
     os.makedirs(map_dir, exist_ok=True)
-    system = DAVO(version=a.version, device=a.device).enable_feature_mode(features='heat')
+    system = DAVO(version=a.version, device=a.device, flip=a.flip).enable_feature_mode(features='heat')
     if a.labels == "u8":
         system.use_u8_labels()
     system.setup_inference(H, W, "davo", a.seq_length, a.batch_size)

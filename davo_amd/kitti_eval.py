@@ -75,11 +75,13 @@ def summary(errors_by_seq):
     return out
 
 
-def evaluate(gt_dir, result_dir, seqs):
-    """Evaluate `<result_dir>/NN.txt` (or NN-pred_kitti_pose.txt) against `<gt_dir>/NN.txt`."""
+def evaluate(gt_dir, result_dir, seqs, gt_pattern="%.2d.txt"):
+    """Evaluate `<result_dir>/NN.txt` (or NN-pred_kitti_pose.txt) against `<gt_dir>/NN.txt`.  ``gt_pattern``: the ground-truth
+    file's name as a format of the sequence number - "%.2d-flip.txt" reads kitti_benchmark's poses-flip/NN-flip.txt, the ground
+    truth of the mirrored sequences (run_kitti_pose --flip)."""
     errs = {}
     for s in seqs:
-        gt = load_poses(os.path.join(gt_dir, "%02d.txt" % s))
+        gt = load_poses(os.path.join(gt_dir, gt_pattern % s))
         cand = [os.path.join(result_dir, "%02d.txt" % s), os.path.join(result_dir, "%02d-pred_kitti_pose.txt" % s)]
         path = next((c for c in cand if os.path.exists(c)), None)
         if path is None:

@@ -141,6 +141,11 @@ def build_parser():
                          "davo_set_flow_format) - half the flow bytes in the loader's buffers, over the link and in the staging sets; "
                          "float16 -flownet2.npy files are read as they are, float32 ones rounded by the loader's workers "
                          "(davo_amd.flow_to_f16).  The written file is that of a float32 run on the rounded flow, to the byte")
+    ap.add_argument("--flip", action="store_true",
+                    help="run the left-right mirrored sequence: every window is mirrored on the device as it is staged (include/davo_hip.h: "
+                         "davo_set_flip; the training loader's --data_flip rule, davo_amd.flip_windows) - for a flip-trained checkpoint, or "
+                         "to evaluate against kitti_benchmark's poses-flip/NN-flip.txt.  The loaders deliver the dump as it is; the file "
+                         "names written are the same NN-pred_kitti_pose.txt")
     return ap
 
 
@@ -249,7 +254,7 @@ def main(argv=None):
                 system.use_u8_labels()
             if a.flow == "f16":
                 system.use_f16_flow()
-            system.setup_inference(H, W, "davo", a.seq_length, a.batch_size)
+            system.setup_inference(H, W, "davo", a.seq_length, a.batch_size, **({"flip": True} if a.flip else {}))
             mark("gpu_context_created")
         finally:
             gpu_ready.set()                        # also on failure: the loader's pinning thread must not wait for ever
@@ -366,6 +371,8 @@ def main(argv=None):
                 run_wide["labels"] = a.labels
             if a.flow != "f32":
                 run_wide["flow"] = a.flow
+            if a.flip:
+                run_wide["flip"] = True
             if len(entries) == 1:          # one sequence: the report it has always had
                 report = {k: v for k, v in entries[0].items() if k not in ("seq", "wall_s")}
                 report.update(run_wide)

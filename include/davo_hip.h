@@ -333,6 +333,38 @@ int davo_forward_device_frames(davo_ctx* ctx, int N, const void* d_frames, const
 int davo_frames_plan(int H, int W, int N, int pairs, int att_source, int label_fmt, int* ranges, long long* link_bytes);
 int davo_frames_plan_fmt(int H, int W, int N, int pairs, int att_source, int label_fmt, int flow_fmt, int* ranges, long long* link_bytes);
 
+/* Mirrored inputs.  The reference treats left-right mirrored sequences as data of their own: it trains with --data_flip
+ * (data_loader.py:77-84, 142-169), its feature-map driver writes `featuremaps-flip', and it ships mirrored ground truth
+ * (kitti_benchmark/data/odometry/poses-flip/NN-flip.txt).  davo_set_flip(ctx, 1) makes the context mirror every batch issued AFTER
+ * the call on the device, by the training loader's rule - flip(X):
+ *   - each frame is mirrored left-right inside its own third of the strip;
+ *   - each flow plane, label map and depth plane is mirrored left-right on its own;
+ *   - no value changes: in particular the horizontal flow component is NOT negated (npy_flip does not negate it, and that is
+ *     what a flip-trained network saw);
+ *   - plane order and frame order stay.
+ * The whole contract: a context with flip on, given X, computes bit for bit what the same context with flip off computes on
+ * flip(X) - for every entry point, format, pair selection, topology and precision, every tensor davo_debug_read returns and
+ * both exports.  (davo_amd.flip_windows / flip_frames are flip() in numpy.)
+ * NOT built: the reference's own test-time switch (generate_feature_map.py:118-129).  It hands the [B,H,3W,3] strip to img_flip,
+ * which sees three channels and treats the strip as ONE image: the strip is mirrored as a whole, src0 and src1 trade places while
+ * their flows and label maps do not.  That is an accident of img_flip's channel count, not a rule.
+ * Any value but 0 or 1 returns DAVO_ERR_INVALID with a message.  It may be called between batches at any time, like
+ * davo_set_pairs; batches in flight keep the setting they were issued with, and so does every range-recovery re-issue (the
+ * library's copy of a batch is taken after the mirror, so a re-issue never mirrors again).  The default is off: every launch,
+ * copied byte and pose bit is then what it is without this entry point, and a context that never switches it on allocates
+ * nothing and launches nothing for it.  davo_get_flip reads it back.  Where the mirror happens (csrc/window_mirror.h), always
+ * once, where a batch becomes the staging set its forward reads; only what the pair selection and the variant read is touched:
+ *   frame layout (every `_frames' call)                    inside the gather launch (mirrored stores): no launch more
+ *   window layout from the host (davo_forward, davo_submit, their `_depth' forms, davo_forward_features, davo_forward_heat)
+ *                                                          one `window_mirror' launch per sub-batch on the staging set, in place
+ *   window layout on the device (davo_forward_device[_depth], davo_calibrate[_depth])
+ *                                                          one `window_mirror' launch from the caller's buffers - never written -
+ *                                                          into the slot's staging set, which the batch then runs from like a
+ *                                                          device frame batch: it is the library's own copy, with or without
+ *                                                          "stable_inputs".  The four pointers must be 16-byte aligned. */
+int davo_set_flip(davo_ctx* ctx, int on);
+int davo_get_flip(const davo_ctx* ctx);
+
 /* The pooled flow-attention variants' window geometry (att_source 14..17) as a function (no context, no device): the cells of the
  * SE descriptor of an H x W frame, in descriptor order (entries 2 i, 2 i + 1 are the x and y means of cell i).  *n_cells receives
  * their number (D / 2; 0 for a source that does not pool); rects, where not NULL, [n][4] = rows [y0, y1) and columns [x0, x1) of

@@ -17,6 +17,12 @@ over the rounds) and `stage_us_per_round`.  The measurement of DESIGN.md section
 
     python tools/variant_step.py --precision f16x3 --batch 32 --rounds 6 --stages 20 <flagship> <-se_flow_on_depthseg_seplayers string>
 
+`--flip ARM [ARM ...]` (off | on; include/davo_hip.h: davo_set_flip) multiplies the arms by the mirror setting, and `--layout
+frames` issues davo_forward_device_frames on a synthetic frame sequence instead of davo_forward_device on windows.  What the
+mirror costs on resident inputs in either layout ("Mirrored inputs") is
+
+    python tools/variant_step.py --batch 32 --rounds 5 --stages 20 --flip off on [--layout frames] <flagship>
+
 Under `rocprofv3 --kernel-trace --stats -- python3 tools/variant_step.py ...` it gives the per-kernel table of a variant."""
 import argparse
 import json
@@ -45,6 +51,10 @@ def main():
                     help="arms of (pair selection[@batch]): both | src0 | src1, e.g. --pairs both src1 both@16")
     ap.add_argument("--stages", type=int, default=0, metavar="N",
                     help="after the timed rounds, profile N forwards per version and round (alternating order): us per launch and profile entry")
+    ap.add_argument("--flip", nargs="+", default=None, choices=["off", "on"], metavar="ARM",
+                    help="arms of the mirror setting (davo_set_flip): off | on, e.g. --flip off on; every pair arm runs once per flip arm")
+    ap.add_argument("--layout", choices=["windows", "frames"], default="windows",
+                    help="windows: davo_forward_device; frames: davo_forward_device_frames (the timed step includes the gather)")
     a = ap.parse_args()
     H, W = a.height, a.width
     arms = []
@@ -52,22 +62,30 @@ def main():
         sel, _, b = arm.partition("@")
         if sel not in Engine.PAIRS or (b and not b.isdigit()):
             ap.error("--pairs: `%s' is not both | src0 | src1, optionally @batch" % arm)
-        arms.append((sel, int(b) if b else a.batch))
-    Bmax = max(b for _, b in arms)
+        arms += [(sel, int(b) if b else a.batch, flip == "on") for flip in (a.flip or ["off"])]
+    Bmax = max(b for _, b, _ in arms)
+    frames = synth.make_frames(Bmax + 2, H, W, depth=True) if a.layout == "frames" else None
     img, flow, seg = synth.make_inputs(Bmax, H, W)
     depth = synth.make_depth(Bmax, H, W)           # uploaded for the depth sources only
     runs = []
     for v in a.versions:
         cfg = parse_version(v)
-        for sel, B in arms:
+        for sel, B, flip in arms:
             e = Engine(cfg, H, W, B)
             e.load_weights(synth.make_weights(cfg))
             e.set_precision(a.precision)
             e.set_pairs(sel)
-            bufs = [e.alloc(x[:B].nbytes).upload(x[:B]) for x in (img, flow, seg)] + [e.alloc(B * 12 * 4)]
-            kw = {"depth": e.alloc(depth[:B].nbytes).upload(depth[:B])} if cfg.needs_depth else {}
+            e.set_flip(flip)
+            if frames is not None:
+                parts, dep = (frames[0][:B + 2], frames[1][:B], frames[2][:B + 2]), frames[3][:B + 2]
+                e.step = e.forward_device_frames
+            else:
+                parts, dep = (img[:B], flow[:B], seg[:B]), depth[:B]
+                e.step = e.forward_device
+            bufs = [e.alloc(x.nbytes).upload(x) for x in parts] + [e.alloc(B * 12 * 4)]
+            kw = {"depth": e.alloc(dep.nbytes).upload(dep)} if cfg.needs_depth else {}
             for _ in range(a.warmup):
-                e.forward_device(B, *bufs, **kw)
+                e.step(B, *bufs, **kw)
             e.synchronize()
             runs.append((v, e, bufs, [], kw, sel, B))
     for _ in range(a.rounds):
@@ -75,7 +93,7 @@ def main():
             e.synchronize()
             t = time.perf_counter()
             for _ in range(a.steps):
-                e.forward_device(B, *bufs, **kw)
+                e.step(B, *bufs, **kw)
             e.synchronize()
             ms.append((time.perf_counter() - t) * 1e3 / a.steps)
     stages = [[] for _ in runs]                     # per run: one {entry: us per launch} per round
@@ -86,7 +104,7 @@ def main():
             e.profile(1)
             e.profile_reset()
             for _ in range(a.stages):
-                e.forward_device(B, *bufs, **kw)
+                e.step(B, *bufs, **kw)
             e.synchronize()
             stages[i].append({k: 1e3 * total / n for k, (n, total) in e.profile_entries().items() if n > 0})
             e.profile(0)
@@ -102,6 +120,8 @@ def main():
                         stage_us_per_round=[{k: round(x, 2) for k, x in r.items()} for r in st])
         if a.pairs:
             line.update(pairs=sel, plan=[e.last_plan(l) for l in range(7)])
+        if a.flip or a.layout != "windows":
+            line.update(flip=e.flip, layout=a.layout)
         print(json.dumps(line), flush=True)
         for buf in bufs:
             buf.free()
