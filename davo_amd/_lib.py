@@ -52,10 +52,12 @@ EXPORTS = (
     "davo_forward_frames", "davo_submit_frames", "davo_forward_device_frames", "davo_frames_plan",
     "davo_set_flow_format", "davo_get_flow_format", "davo_frames_plan_fmt", "davo_pool_plan",
     "davo_set_flip", "davo_get_flip",
+    "davo_set_depth_format", "davo_get_depth_format", "davo_frames_plan_fmt2",
 )
 COMM_ID_BYTES = 128
 LABELS_F32, LABELS_U8 = 0, 1          # DAVO_LABELS_F32, DAVO_LABELS_U8 (davo_set_label_format)
 FLOW_F32, FLOW_F16 = 0, 1             # DAVO_FLOW_F32, DAVO_FLOW_F16 (davo_set_flow_format)
+DEPTH_F32, DEPTH_F16 = 0, 1           # DAVO_DEPTH_F32, DAVO_DEPTH_F16 (davo_set_depth_format)
 POSENN_PAIRS, POSENN_TRIPLET = 0, 1   # DAVO_POSENN_PAIRS, DAVO_POSENN_TRIPLET (davo_set_posenn_topology)
 
 
@@ -234,6 +236,8 @@ def _load():
     L.davo_get_label_format.argtypes = [vp]
     L.davo_set_flow_format.argtypes = [vp, i]
     L.davo_get_flow_format.argtypes = [vp]
+    L.davo_set_depth_format.argtypes = [vp, i]
+    L.davo_get_depth_format.argtypes = [vp]
     L.davo_set_flip.argtypes = [vp, i]
     L.davo_get_flip.argtypes = [vp]
     L.davo_set_feature_export.argtypes = [vp, i]
@@ -245,6 +249,7 @@ def _load():
     L.davo_forward_device_frames.argtypes = [vp, i, vp, vp, vp, vp, vp, ctypes.POINTER(ctypes.c_float)]
     L.davo_frames_plan.argtypes = [i] * 6 + [ctypes.POINTER(i), ctypes.POINTER(ctypes.c_longlong)]
     L.davo_frames_plan_fmt.argtypes = [i] * 7 + [ctypes.POINTER(i), ctypes.POINTER(ctypes.c_longlong)]
+    L.davo_frames_plan_fmt2.argtypes = [i] * 8 + [ctypes.POINTER(i), ctypes.POINTER(ctypes.c_longlong)]
     L.davo_pool_plan.argtypes = [i] * 3 + [ctypes.POINTER(i), ctypes.POINTER(i), f32p]
     L.davo_debug_read.argtypes = [vp, ctypes.c_char_p, f32p, ctypes.c_size_t]
     L.davo_conv2d_same.argtypes = [i, f32p, i, i, i, i, f32p, i, i, f32p, i, i, i, i, f32p, ctypes.c_char_p, i]

@@ -240,6 +240,23 @@ int davo_set_flow_format(davo_ctx* c, int fmt) {
 
 int davo_get_flow_format(const davo_ctx* c) { return c ? c->flow_fmt : DAVO_ERR_INVALID; }
 
+int davo_set_depth_format(davo_ctx* c, int fmt) {
+    if (!c) return DAVO_ERR_INVALID;
+    if (fmt != DAVO_DEPTH_F32 && fmt != DAVO_DEPTH_F16)
+        return fail(c, DAVO_ERR_INVALID, "depth format must be DAVO_DEPTH_F32 (0) or DAVO_DEPTH_F16 (1), got %d", fmt);
+    // the label format's rule: everything sized by plane_bytes() follows the format
+    bool sets = static_cast<bool>(c->host) || static_cast<bool>(c->snaps);
+    for (const InputSet& s : c->stream_sets) sets = sets || s.built();
+    for (const FrameSet& s : c->frame_sets) sets = sets || s.built();
+    if (c->inputs_seen || c->forward_seen || sets)
+        return fail(c, DAVO_ERR_INVALID, "davo_set_depth_format must be called before the first call that takes inputs "
+                    "(the staging sets, the range guard's snapshots and every copy are sized by it)");
+    c->depth_fmt = fmt;
+    return DAVO_OK;
+}
+
+int davo_get_depth_format(const davo_ctx* c) { return c ? c->depth_fmt : DAVO_ERR_INVALID; }
+
 int davo_load_weight(davo_ctx* c, const char* tf_name, const float* data, const int64_t* shape, int ndim) {
     // ndim 0: a scalar variable (the depth threshold); shape may then be null
     if (!c || !tf_name || !data || ndim < 0 || ndim > 4 || (!shape && ndim > 0)) return fail(c, DAVO_ERR_INVALID, "bad argument to davo_load_weight");

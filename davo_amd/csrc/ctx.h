@@ -239,7 +239,8 @@ struct davo_ctx {
     bool forward_seen = false;                 // a forward has been issued (davo_set_posenn_se and davo_set_posenn_topology are refused from then on)
     int label_fmt = davo::LABELS_F32;          // davo_set_label_format: what every `seg' argument points at, and what plane_bytes().seg sizes
     int flow_fmt = davo::FLOW_F32;             // davo_set_flow_format: what every `flow' argument points at, and what plane_bytes().flow sizes
-    bool inputs_seen = false;                  // an entry point has taken inputs (davo_set_label_format and davo_set_flow_format are refused from then on)
+    int depth_fmt = davo::DEPTH_F32;           // davo_set_depth_format: what every `depth' argument points at, and what plane_bytes().depth sizes
+    bool inputs_seen = false;                  // an entry point has taken inputs (davo_set_label_format, davo_set_flow_format and davo_set_depth_format are refused from then on)
     int impl = 0;
     int precision = 1;                         // 0 = FP32 MFMA (bit-exact fmaf chains), 1 = f16x3 split (default)
     bool packed_h_ready = false;
@@ -341,10 +342,11 @@ inline int fail(davo_ctx* c, int code, const char* fmt, ...) {
 struct PlaneBytes { size_t img, flow, seg, depth; };
 inline PlaneBytes plane_bytes(const davo_ctx* c) {
     const size_t HW = (size_t)c->H * c->W;
-    // seg: [3,H,W,1] in the context's label format, float32 or bytes; depth: [3,H,W,1] float32 always (davo.py:991-996).  H W is a
+    // seg: [3,H,W,1] in the context's label format, float32 or bytes; depth: [3,H,W,1] in the context's depth format, float32 or binary16 (davo.py:991-996).  H W is a
     // multiple of 16, so every window of every plane starts 16-byte aligned where the block does, in either format.  flow: [4,H,W,2] in
     // the context's flow format, float32 or binary16: a plane of 2 H W halves is still a multiple of 64 bytes
-    return PlaneBytes{HW * 9, HW * 8 * (c->flow_fmt == FLOW_F16 ? 2 : sizeof(float)), HW * 3 * (c->label_fmt == LABELS_U8 ? 1 : sizeof(float)), HW * 3 * sizeof(float)};
+    return PlaneBytes{HW * 9, HW * 8 * (c->flow_fmt == FLOW_F16 ? 2 : sizeof(float)), HW * 3 * (c->label_fmt == LABELS_U8 ? 1 : sizeof(float)),
+                      HW * 3 * (c->depth_fmt == DEPTH_F16 ? 2 : sizeof(float))};
 }
 inline bool needs_depth(const davo_ctx* c) { return att_reads_depth(c->v.att_source); }
 inline bool triplet(const davo_ctx* c) { return c->topology == DAVO_POSENN_TRIPLET; }

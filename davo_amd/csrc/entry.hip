@@ -93,7 +93,7 @@ int stage_inputs(davo_ctx* c, const InputSet& set, const Inputs& host, int b0, i
         if (att_tgt_attended(c->v.att_source)) HIP_TRY(c, copy2d(dst(set.seg, n.seg), src.seg, n.seg, src1 ? plane : 0, 2 * plane, nb));
         else HIP_TRY(c, copy2d(dst(set.seg, n.seg), src.seg, n.seg, src1 ? 2 * plane : 0, plane, nb));
         // depth sources: the target's plane and the source's; the depth-split attention reads the source frame's plane alone
-        const size_t dplane = n.depth / 3;                     // (float32 whatever the label format)
+        const size_t dplane = n.depth / 3;                     // (the depth format's, whatever the label format)
         if (src.depth && c->v.att_source == ATT_DEPTH_SPLIT) HIP_TRY(c, copy2d(dst(set.depth, n.depth), src.depth, n.depth, src1 ? 2 * dplane : 0, dplane, nb));
         else if (src.depth) HIP_TRY(c, copy2d(dst(set.depth, n.depth), src.depth, n.depth, src1 ? dplane : 0, 2 * dplane, nb));
         return DAVO_OK;
@@ -167,8 +167,8 @@ int gather_windows(davo_ctx* c, const InputSet& set, const FrameInputs& fr, int 
                        c->H, c->W, sel, p.seg_tgt, p.depth_tgt};
     ProfScope ps(c, s, "window_gather");
     // (the mirrored form leaves out the target's label map where the variant does not attend it: no kernel reads it)
-    if (flip) HIP_TRY(c, launch_window_mirror(a, nb, true, c->label_fmt, c->flow_fmt, s));
-    else HIP_TRY(c, launch_window_gather(a, nb, c->label_fmt, c->flow_fmt, s));
+    if (flip) HIP_TRY(c, launch_window_mirror(a, nb, true, c->label_fmt, c->flow_fmt, c->depth_fmt, s));
+    else HIP_TRY(c, launch_window_gather(a, nb, c->label_fmt, c->flow_fmt, c->depth_fmt, s));
     return DAVO_OK;
 }
 
@@ -182,7 +182,7 @@ int mirror_windows(davo_ctx* c, const InputSet& set, const Inputs* from, int b0,
     const GatherArgs a{rd(src.img), rd(src.seg), dst.depth ? rd(src.depth) : nullptr, rd(src.flow), wr(dst.img), wr(dst.seg), wr(dst.depth), wr(dst.flow),
                        c->H, c->W, sel, seg_tgt, att_desc_depth(c->v.att_source)};
     ProfScope ps(c, s, "window_mirror");
-    HIP_TRY(c, launch_window_mirror(a, nb, false, c->label_fmt, c->flow_fmt, s));
+    HIP_TRY(c, launch_window_mirror(a, nb, false, c->label_fmt, c->flow_fmt, c->depth_fmt, s));
     return DAVO_OK;
 }
 
@@ -364,17 +364,22 @@ int davo_forward_device_frames(davo_ctx* c, int N, const void* d_frames, const v
     return forward_device_entry(c, N, frame_batch("davo_forward_device_frames", true, d_frames, d_flow2, d_seg, d_depth), d_pose, elapsed_ms);
 }
 
-int davo_frames_plan_fmt(int H, int W, int N, int pairs, int att_source, int label_fmt, int flow_fmt, int* ranges, long long* link_bytes) {
+int davo_frames_plan_fmt2(int H, int W, int N, int pairs, int att_source, int label_fmt, int flow_fmt, int depth_fmt, int* ranges, long long* link_bytes) {
     if (H < 1 || W < 1 || N < 1 || (pairs != PAIRS_SRC0 && pairs != PAIRS_SRC1 && pairs != PAIRS_BOTH) || att_source < 0 || att_source > ATT_MAX ||
-        (label_fmt != LABELS_F32 && label_fmt != LABELS_U8) || (flow_fmt != FLOW_F32 && flow_fmt != FLOW_F16))
+        (label_fmt != LABELS_F32 && label_fmt != LABELS_U8) || (flow_fmt != FLOW_F32 && flow_fmt != FLOW_F16) ||
+        (depth_fmt != DEPTH_F32 && depth_fmt != DEPTH_F16))
         return DAVO_ERR_INVALID;
     const FramePlan p = frame_plan(N, pairs, att_source);
     if (ranges) {
         const int r[8] = {p.img[0], p.img[1], p.seg[0], p.seg[1], p.depth[0], p.depth[1], p.flow[0], p.flow[1]};
         memcpy(ranges, r, sizeof r);
     }
-    if (link_bytes) *link_bytes = frame_plan_bytes(p, N, H, W, label_fmt == LABELS_U8 ? 1 : 4, flow_fmt == FLOW_F16 ? 2 : 4);
+    if (link_bytes) *link_bytes = frame_plan_bytes(p, N, H, W, label_fmt == LABELS_U8 ? 1 : 4, flow_fmt == FLOW_F16 ? 2 : 4, depth_fmt == DEPTH_F16 ? 2 : 4);
     return DAVO_OK;
+}
+
+int davo_frames_plan_fmt(int H, int W, int N, int pairs, int att_source, int label_fmt, int flow_fmt, int* ranges, long long* link_bytes) {
+    return davo_frames_plan_fmt2(H, W, N, pairs, att_source, label_fmt, flow_fmt, DEPTH_F32, ranges, link_bytes);
 }
 
 int davo_frames_plan(int H, int W, int N, int pairs, int att_source, int label_fmt, int* ranges, long long* link_bytes) {

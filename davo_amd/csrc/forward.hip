@@ -511,7 +511,7 @@ int forward_device(davo_ctx* c, const Run& run, int B, const Inputs& in, void* d
     } else if (att_desc_depth(v.att_source)) {
         // depth sources: one float32 sum per depth plane and chunk, then (or, folded, in the same launch) the excitation
         ProfScope ps(c, run.stream, "se_depth_squeeze");
-        HIP_TRY(c, launch_se_depth_squeeze(fold_excite, static_cast<const float*>(in.depth), B, HW, v, reinterpret_cast<unsigned*>(d_partial),
+        HIP_TRY(c, launch_se_depth_squeeze(fold_excite, in.depth, c->depth_fmt, B, HW, v, reinterpret_cast<unsigned*>(d_partial),
                                            d_counters + 1, se_w1, se_b1, se_w2, se_b2, d_tab, range_reset, sel, s));
     } else if (class_table) {
         // segmentation / rgb / seg+flow sources: per-frame histogram, byte or flow sums, then (or, folded, in the same launch) the
@@ -563,7 +563,7 @@ int forward_device(davo_ctx* c, const Run& run, int B, const Inputs& in, void* d
     } else if (!fused) {
         ProfScope ps(c, run.stream, "mask_pack");
         HIP_TRY(c, launch_mask_pack(h3 ? 16 : (run.impl == 0 ? 8 : 10), d_img, d_flow, ffmt, d_seg, c->label_fmt, d_tab, v, B, H, W, d_packed, sel, s,
-                                    static_cast<const float*>(in.depth), d_tab_far, c->depth_thr));
+                                    in.depth, d_tab_far, c->depth_thr, c->depth_fmt));
     }
     const int c6 = v.cnv6_out;
     int rc;

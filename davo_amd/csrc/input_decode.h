@@ -82,6 +82,25 @@ __device__ __forceinline__ float2 flow_fetch1(const flow_f16* __restrict__ px) {
     return make_float2((float)h[0], (float)h[1]);
 }
 
+// The depth planes come in one of the two formats of davo_set_depth_format (include/davo_hip.h): float32, or IEEE binary16 in the
+// same layout ([B][3 file planes: src0, tgt, src1][H][W], one value per pixel).  DT is the element, float or depth_f16.  Every
+// reader of raw depth takes four horizontally adjacent pixels through depth_fetch4 and computes in float32 from there on - the
+// same expressions in the same order for both formats, so binary16 planes h give the bits of the float32 planes (float)h.  The
+// widening is the flow fetches' (above): exact for every binary16 value, subnormals, signed zeros and infinities included; a NaN
+// stays a NaN.
+//   depth_fetch4  pixels pix .. pix + 3 of one plane, pix a multiple of 4; the argument is the unit's first element, formed in
+//                 element arithmetic.  float32: one 16-byte load; binary16: ONE 8-byte load and four widenings.  Aligned wherever
+//                 the planes' base is 16-byte aligned: a plane holds H W elements, H W a multiple of 16.
+typedef _Float16 depth_f16;
+__device__ __forceinline__ float4 depth_fetch4(const float* __restrict__ unit) {
+    return *reinterpret_cast<const float4*>(unit);
+}
+__device__ __forceinline__ float4 depth_fetch4(const depth_f16* __restrict__ unit) {
+    typedef _Float16 depth_h4 __attribute__((ext_vector_type(4)));
+    const depth_h4 h = *reinterpret_cast<const depth_h4*>(unit);
+    return make_float4((float)h[0], (float)h[1], (float)h[2], (float)h[3]);
+}
+
 // Depth-split attention (att_source 13, davo.py:1143-1155): near = depth < thr in float32, strict; tf.where sends a NaN depth (the
 // comparison is false) to the far side.  The pixel's class is looked up in the chosen table by att_lookup's rule.
 __device__ __forceinline__ float att_lookup_split(const float* near19, const float* far19, float thr, float depth, int id) {
@@ -89,11 +108,14 @@ __device__ __forceinline__ float att_lookup_split(const float* near19, const flo
 }
 
 // what the depth-split forms of mask_pack (prologue.h) and feature_maps (feature_export.h) take beside the near tables
-struct DepthSplit {
-    const float* depth;          // [B][3 file planes: src0, tgt, src1][H][W] float32, 16-byte aligned
+// (DT: the depth element, float or depth_f16 - the pointer keeps its element type all the way into the kernel)
+template <typename DT>
+struct DepthSplitOf {
+    const DT* depth;             // [B][3 file planes: src0, tgt, src1][H][W] in the depth format DT, 16-byte aligned
     const float* tab_far;        // [B][3][19]
     float thr;                   // depth_threshold, the host's copy of the loaded scalar
 };
+using DepthSplit = DepthSplitOf<float>;
 // The label maps have the same planes in the context's label format, [B][3 file planes: src0, tgt, src1][H][W] float32 or uint8,
 // and the same requirement: a 16-byte aligned base (then every unit's load above is aligned, in either format).
 

@@ -34,6 +34,8 @@ hipError_t ensure_dynamic_lds(const void* kernel, int bytes) {
 namespace {
 using flow_f32 = float;
 inline bool flow_fmt_ok(int flow_fmt) { return flow_fmt == FLOW_F32 || flow_fmt == FLOW_F16; }
+using depth_f32 = float;
+inline bool depth_fmt_ok(int depth_fmt) { return depth_fmt == DEPTH_F32 || depth_fmt == DEPTH_F16; }
 }  // namespace
 
 // d_flow / flow_fmt (here and below): the flow in the format FLOW_F32 or FLOW_F16 (params.h); any other value is an error
@@ -115,17 +117,28 @@ hipError_t launch_se_class_squeeze(bool fold, const uint8_t* d_img, const void* 
     return hipGetLastError();
 }
 
-hipError_t launch_se_depth_squeeze(bool fold, const float* d_depth, int B, int HW, const Variant& v, unsigned* d_partial,
-                                   unsigned* d_counters, const float* w1, const float* b1, const float* w2, const float* b2,
-                                   float* d_tab, unsigned* d_range_reset, int sel, hipStream_t s) {
-    if (!att_desc_depth(v.att_source) || !d_depth || HW % 16) return hipErrorInvalidValue;
-    const dim3 grid(SQ_CHUNKS, 1 + pairs_per_window(sel), B);
+namespace {
+template <typename DT>
+void se_depth_squeeze_as(bool fold, const dim3& grid, hipStream_t s, const void* d_depth_raw, int HW, const Variant& v, unsigned* d_partial,
+                         unsigned* d_counters, const float* w1, const float* b1, const float* w2, const float* b2, float* d_tab,
+                         unsigned* d_range_reset, int sel) {
+    const DT* d_depth = static_cast<const DT*>(d_depth_raw);
     if (fold)
-        hipLaunchKernelGGL(se_depth_squeeze<true>, grid, dim3(256), 0, s, d_depth, HW, v, d_partial, d_counters, w1, b1, w2, b2, d_tab,
+        hipLaunchKernelGGL((se_depth_squeeze<true, DT>), grid, dim3(256), 0, s, d_depth, HW, v, d_partial, d_counters, w1, b1, w2, b2, d_tab,
                            d_range_reset, sel);
     else
-        hipLaunchKernelGGL(se_depth_squeeze<false>, grid, dim3(256), 0, s, d_depth, HW, v, d_partial, d_counters, w1, b1, w2, b2, d_tab,
+        hipLaunchKernelGGL((se_depth_squeeze<false, DT>), grid, dim3(256), 0, s, d_depth, HW, v, d_partial, d_counters, w1, b1, w2, b2, d_tab,
                            d_range_reset, sel);
+}
+}  // namespace
+
+hipError_t launch_se_depth_squeeze(bool fold, const void* d_depth, int depth_fmt, int B, int HW, const Variant& v, unsigned* d_partial,
+                                   unsigned* d_counters, const float* w1, const float* b1, const float* w2, const float* b2,
+                                   float* d_tab, unsigned* d_range_reset, int sel, hipStream_t s) {
+    if (!att_desc_depth(v.att_source) || !d_depth || ((uintptr_t)d_depth & 15) || HW % 16 || !depth_fmt_ok(depth_fmt)) return hipErrorInvalidValue;
+    const dim3 grid(SQ_CHUNKS, 1 + pairs_per_window(sel), B);
+    if (depth_fmt == DEPTH_F16) se_depth_squeeze_as<depth_f16>(fold, grid, s, d_depth, HW, v, d_partial, d_counters, w1, b1, w2, b2, d_tab, d_range_reset, sel);
+    else se_depth_squeeze_as<depth_f32>(fold, grid, s, d_depth, HW, v, d_partial, d_counters, w1, b1, w2, b2, d_tab, d_range_reset, sel);
     return hipGetLastError();
 }
 
@@ -154,17 +167,31 @@ hipError_t launch_se_pool_excite(const float* d_partial, int B, const Variant& v
 }
 
 namespace {
+// the depth-split arguments as the host hands them on (the planes in the format depth_fmt); typed where the kernel is chosen
+struct DepthSplitArgs { const void* depth; const float* tab_far; float thr; };
+template <typename DT>
+DepthSplitOf<DT> depth_split_of(const DepthSplitArgs& a) { return DepthSplitOf<DT>{static_cast<const DT*>(a.depth), a.tab_far, a.thr}; }
+
+template <typename LT, typename FT, typename DT>
+hipError_t mask_pack_split_as(int ld, const dim3& grid, hipStream_t s, const uint8_t* d_img, const FT* d_flow, const LT* seg, const float* d_tab,
+                              const Variant& v, int B, int sel, int H, int W, float* d_packed, const DepthSplitArgs& args) {
+    const DepthSplitOf<DT> ds = depth_split_of<DT>(args);
+    if (ld == 16) hipLaunchKernelGGL((mask_pack_depthsplit<16, LT, FT, DT>), grid, dim3(256), 0, s, d_img, d_flow, seg, d_tab, v, B, sel, H, W, d_packed, ds);
+    else if (ld == 8) hipLaunchKernelGGL((mask_pack_depthsplit<8, LT, FT, DT>), grid, dim3(256), 0, s, d_img, d_flow, seg, d_tab, v, B, sel, H, W, d_packed, ds);
+    else if (ld == 10) hipLaunchKernelGGL((mask_pack_depthsplit<10, LT, FT, DT>), grid, dim3(256), 0, s, d_img, d_flow, seg, d_tab, v, B, sel, H, W, d_packed, ds);
+    else return hipErrorInvalidValue;
+    return hipGetLastError();
+}
+
+// ds: the depth-split form (null: the plain packer), its planes in the format depth_fmt
 template <typename LT, typename FT>
 hipError_t mask_pack_as(int ld, const dim3& grid, hipStream_t s, const uint8_t* d_img, const void* d_flow_raw, const void* d_seg, const float* d_tab,
-                        const Variant& v, int B, int sel, int H, int W, float* d_packed, const DepthSplit* ds) {
+                        const Variant& v, int B, int sel, int H, int W, float* d_packed, const DepthSplitArgs* ds, int depth_fmt) {
     const LT* seg = static_cast<const LT*>(d_seg);
     const FT* d_flow = static_cast<const FT*>(d_flow_raw);
     if (ds) {
-        if (ld == 16) hipLaunchKernelGGL((mask_pack_depthsplit<16, LT, FT>), grid, dim3(256), 0, s, d_img, d_flow, seg, d_tab, v, B, sel, H, W, d_packed, *ds);
-        else if (ld == 8) hipLaunchKernelGGL((mask_pack_depthsplit<8, LT, FT>), grid, dim3(256), 0, s, d_img, d_flow, seg, d_tab, v, B, sel, H, W, d_packed, *ds);
-        else if (ld == 10) hipLaunchKernelGGL((mask_pack_depthsplit<10, LT, FT>), grid, dim3(256), 0, s, d_img, d_flow, seg, d_tab, v, B, sel, H, W, d_packed, *ds);
-        else return hipErrorInvalidValue;
-        return hipGetLastError();
+        if (depth_fmt == DEPTH_F16) return mask_pack_split_as<LT, FT, depth_f16>(ld, grid, s, d_img, d_flow, seg, d_tab, v, B, sel, H, W, d_packed, *ds);
+        return mask_pack_split_as<LT, FT, depth_f32>(ld, grid, s, d_img, d_flow, seg, d_tab, v, B, sel, H, W, d_packed, *ds);
     }
     if (ld == 16) hipLaunchKernelGGL((mask_pack<16, LT, FT>), grid, dim3(256), 0, s, d_img, d_flow, seg, d_tab, v, B, sel, H, W, d_packed);
     else if (ld == 8) hipLaunchKernelGGL((mask_pack<8, LT, FT>), grid, dim3(256), 0, s, d_img, d_flow, seg, d_tab, v, B, sel, H, W, d_packed);
@@ -176,21 +203,21 @@ hipError_t mask_pack_as(int ld, const dim3& grid, hipStream_t s, const uint8_t* 
 
 hipError_t launch_mask_pack(int ld, const uint8_t* d_img, const void* d_flow, int flow_fmt, const void* d_seg, int label_fmt, const float* d_tab,
                             const Variant& v, int B, int H, int W, float* d_packed, int sel, hipStream_t s,
-                            const float* d_depth, const float* d_tab_far, float depth_thr) {
+                            const void* d_depth, const float* d_tab_far, float depth_thr, int depth_fmt) {
     const long nthreads = (long)pairs_per_window(sel) * B * H * (W / 4);
     const dim3 grid((unsigned)((nthreads + 255) / 256));
     const bool split = v.att_source == ATT_DEPTH_SPLIT;
     // the depth-split form: a missing plane or table is an error, never the plain packer
     if (split && (!d_depth || ((uintptr_t)d_depth & 15) || !d_tab_far)) return hipErrorInvalidValue;
-    const DepthSplit ds{d_depth, d_tab_far, depth_thr};
-    const DepthSplit* const dsp = split ? &ds : nullptr;
-    if (!flow_fmt_ok(flow_fmt) || (label_fmt != LABELS_F32 && label_fmt != LABELS_U8)) return hipErrorInvalidValue;
+    const DepthSplitArgs ds{d_depth, d_tab_far, depth_thr};
+    const DepthSplitArgs* const dsp = split ? &ds : nullptr;
+    if (!flow_fmt_ok(flow_fmt) || !depth_fmt_ok(depth_fmt) || (label_fmt != LABELS_F32 && label_fmt != LABELS_U8)) return hipErrorInvalidValue;
     if (flow_fmt == FLOW_F16) {
-        if (label_fmt == LABELS_U8) return mask_pack_as<uint8_t, flow_f16>(ld, grid, s, d_img, d_flow, d_seg, d_tab, v, B, sel, H, W, d_packed, dsp);
-        return mask_pack_as<float, flow_f16>(ld, grid, s, d_img, d_flow, d_seg, d_tab, v, B, sel, H, W, d_packed, dsp);
+        if (label_fmt == LABELS_U8) return mask_pack_as<uint8_t, flow_f16>(ld, grid, s, d_img, d_flow, d_seg, d_tab, v, B, sel, H, W, d_packed, dsp, depth_fmt);
+        return mask_pack_as<float, flow_f16>(ld, grid, s, d_img, d_flow, d_seg, d_tab, v, B, sel, H, W, d_packed, dsp, depth_fmt);
     }
-    if (label_fmt == LABELS_U8) return mask_pack_as<uint8_t, flow_f32>(ld, grid, s, d_img, d_flow, d_seg, d_tab, v, B, sel, H, W, d_packed, dsp);
-    return mask_pack_as<float, flow_f32>(ld, grid, s, d_img, d_flow, d_seg, d_tab, v, B, sel, H, W, d_packed, dsp);
+    if (label_fmt == LABELS_U8) return mask_pack_as<uint8_t, flow_f32>(ld, grid, s, d_img, d_flow, d_seg, d_tab, v, B, sel, H, W, d_packed, dsp, depth_fmt);
+    return mask_pack_as<float, flow_f32>(ld, grid, s, d_img, d_flow, d_seg, d_tab, v, B, sel, H, W, d_packed, dsp, depth_fmt);
 }
 
 namespace {
@@ -220,7 +247,15 @@ hipError_t launch_mask_pack3(bool h3, const uint8_t* d_img, const void* d_flow, 
     return mask_pack3_as<float, flow_f32>(h3, grid, s, d_img, d_flow, d_seg, d_tab, v, B, H, W, d_packed);
 }
 
-hipError_t launch_window_gather(const GatherArgs& a, int N, int label_fmt, int flow_fmt, hipStream_t s) {
+namespace {
+template <typename LT, typename FT>
+void window_gather_as(const GatherArgs& a, const dim3& grid, int depth_fmt, hipStream_t s) {
+    if (depth_fmt == DEPTH_F16) hipLaunchKernelGGL((window_gather<LT, FT, depth_f16>), grid, dim3(256), 0, s, a);
+    else hipLaunchKernelGGL((window_gather<LT, FT, depth_f32>), grid, dim3(256), 0, s, a);
+}
+}  // namespace
+
+hipError_t launch_window_gather(const GatherArgs& a, int N, int label_fmt, int flow_fmt, int depth_fmt, hipStream_t s) {
     if (N < 1 || a.H < 1 || a.W < 4 || a.W % 4 || ((size_t)a.H * a.W) % 16 || !a.f_img || !a.f_seg || !a.w_img || !a.w_seg || !a.w_flow ||
         (a.f_depth && !a.w_depth))
         return hipErrorInvalidValue;
@@ -229,49 +264,54 @@ hipError_t launch_window_gather(const GatherArgs& a, int N, int label_fmt, int f
         return hipErrorInvalidValue;
     // the largest job decides the pieces per job (a flow plane, else a frame or a float32 plane); at most 8, the rest in rounds
     const size_t HW = (size_t)a.H * a.W;
-    if (!flow_fmt_ok(flow_fmt) || (label_fmt != LABELS_F32 && label_fmt != LABELS_U8)) return hipErrorInvalidValue;
-    // (a binary16 flow plane is HW / 4 vectors, no more than a float32 label or depth plane: the max below covers it)
+    if (!flow_fmt_ok(flow_fmt) || !depth_fmt_ok(depth_fmt) || (label_fmt != LABELS_F32 && label_fmt != LABELS_U8)) return hipErrorInvalidValue;
+    // (a binary16 flow plane is HW / 4 vectors, no more than a float32 label or depth plane, a binary16 depth plane HW / 8: the max below covers them)
     const size_t vecs = a.f_flow ? (flow_fmt == FLOW_F16 ? HW / 4 : HW / 2) : (a.W % 16 == 0 ? HW * 3 / 16 : HW * 3 / 4);
     const unsigned gx = (unsigned)std::min<size_t>(8, (std::max(vecs, HW / 4) + GATHER_PIECE - 1) / GATHER_PIECE);
     const dim3 grid(gx, (unsigned)N, GATHER_JOBS);
     if (flow_fmt == FLOW_F16) {
-        if (label_fmt == LABELS_U8) hipLaunchKernelGGL((window_gather<uint8_t, flow_f16>), grid, dim3(256), 0, s, a);
-        else hipLaunchKernelGGL((window_gather<float, flow_f16>), grid, dim3(256), 0, s, a);
+        if (label_fmt == LABELS_U8) window_gather_as<uint8_t, flow_f16>(a, grid, depth_fmt, s);
+        else window_gather_as<float, flow_f16>(a, grid, depth_fmt, s);
     } else {
-        if (label_fmt == LABELS_U8) hipLaunchKernelGGL((window_gather<uint8_t, flow_f32>), grid, dim3(256), 0, s, a);
-        else hipLaunchKernelGGL((window_gather<float, flow_f32>), grid, dim3(256), 0, s, a);
+        if (label_fmt == LABELS_U8) window_gather_as<uint8_t, flow_f32>(a, grid, depth_fmt, s);
+        else window_gather_as<float, flow_f32>(a, grid, depth_fmt, s);
     }
     return hipGetLastError();
 }
 
 namespace {
-template <bool FRAMES>
+template <typename DT, bool FRAMES>
 void window_mirror_as(const GatherArgs& a, const dim3& grid, int label_fmt, int flow_fmt, hipStream_t s) {
     if (flow_fmt == FLOW_F16) {
-        if (label_fmt == LABELS_U8) hipLaunchKernelGGL((window_mirror<uint8_t, flow_f16, FRAMES>), grid, dim3(256), 0, s, a);
-        else hipLaunchKernelGGL((window_mirror<float, flow_f16, FRAMES>), grid, dim3(256), 0, s, a);
+        if (label_fmt == LABELS_U8) hipLaunchKernelGGL((window_mirror<uint8_t, flow_f16, DT, FRAMES>), grid, dim3(256), 0, s, a);
+        else hipLaunchKernelGGL((window_mirror<float, flow_f16, DT, FRAMES>), grid, dim3(256), 0, s, a);
     } else {
-        if (label_fmt == LABELS_U8) hipLaunchKernelGGL((window_mirror<uint8_t, flow_f32, FRAMES>), grid, dim3(256), 0, s, a);
-        else hipLaunchKernelGGL((window_mirror<float, flow_f32, FRAMES>), grid, dim3(256), 0, s, a);
+        if (label_fmt == LABELS_U8) hipLaunchKernelGGL((window_mirror<uint8_t, flow_f32, DT, FRAMES>), grid, dim3(256), 0, s, a);
+        else hipLaunchKernelGGL((window_mirror<float, flow_f32, DT, FRAMES>), grid, dim3(256), 0, s, a);
     }
 }
 }  // namespace
 
-hipError_t launch_window_mirror(const GatherArgs& a, int N, bool frames, int label_fmt, int flow_fmt, hipStream_t s) {
+hipError_t launch_window_mirror(const GatherArgs& a, int N, bool frames, int label_fmt, int flow_fmt, int depth_fmt, hipStream_t s) {
     if (N < 1 || a.H < 1 || a.W < 4 || a.W % 4 || ((size_t)a.H * a.W) % 16 || !a.f_img || !a.f_seg || !a.w_img || !a.w_seg || !a.w_flow ||
         (a.f_depth && !a.w_depth) || (!frames && !a.f_flow))
         return hipErrorInvalidValue;
     if (((uintptr_t)a.f_img | (uintptr_t)a.f_seg | (uintptr_t)a.f_depth | (uintptr_t)a.f_flow | (uintptr_t)a.w_img | (uintptr_t)a.w_seg |
          (uintptr_t)a.w_depth | (uintptr_t)a.w_flow) & 15)
         return hipErrorInvalidValue;
-    if (!flow_fmt_ok(flow_fmt) || (label_fmt != LABELS_F32 && label_fmt != LABELS_U8)) return hipErrorInvalidValue;
+    if (!flow_fmt_ok(flow_fmt) || !depth_fmt_ok(depth_fmt) || (label_fmt != LABELS_F32 && label_fmt != LABELS_U8)) return hipErrorInvalidValue;
     // the job with the most unit pairs decides the pieces per job: a flow plane (four pixels a unit, half as many pairs a row); at
     // most 8, the rest in rounds
     const size_t pairs = (size_t)a.H * ((a.W / 4 + 1) / 2);
     const unsigned gx = (unsigned)std::min<size_t>(8, (pairs + MIRROR_PIECE - 1) / MIRROR_PIECE);
     const dim3 grid(gx, (unsigned)N, GATHER_JOBS);
-    if (frames) window_mirror_as<true>(a, grid, label_fmt, flow_fmt, s);
-    else window_mirror_as<false>(a, grid, label_fmt, flow_fmt, s);
+    if (depth_fmt == DEPTH_F16) {
+        if (frames) window_mirror_as<depth_f16, true>(a, grid, label_fmt, flow_fmt, s);
+        else window_mirror_as<depth_f16, false>(a, grid, label_fmt, flow_fmt, s);
+    } else {
+        if (frames) window_mirror_as<depth_f32, true>(a, grid, label_fmt, flow_fmt, s);
+        else window_mirror_as<depth_f32, false>(a, grid, label_fmt, flow_fmt, s);
+    }
     return hipGetLastError();
 }
 

@@ -86,6 +86,12 @@ constexpr int LABELS_F32 = 0, LABELS_U8 = 1;
 // the instantiation.
 constexpr int FLOW_F32 = 0, FLOW_F16 = 1;
 
+// ---- depth format (davo_set_depth_format, include/davo_hip.h) ----------------------------------------------------------------
+// What the depth planes of a context are made of: float32 (the default) or IEEE binary16, same layout.  The kernels that read raw
+// depth are templated on the element type and widen through depth_fetch4 (input_decode.h); the launchers take the format and pick
+// the instantiation.
+constexpr int DEPTH_F32 = 0, DEPTH_F16 = 1;
+
 // ---- pair selection (davo_set_pairs, include/davo_hip.h) -------------------------------------------------------------------
 // A window's two poses come from two independent evaluations of the PoseNN (davo.py:1456-1457): pair 0 = (tgt, src0), pair 1 =
 // (tgt, src1).  sel 3 runs both: pair image n is pair n & 1 of window n >> 1.  sel 1 / 2 runs pair 0 / 1 alone: pair image n is
@@ -404,7 +410,7 @@ struct SnapArgs {
     const uint8_t* depth;                   // depth sources only (else null): the caller's depth planes, depth_vec units per window ...
     uint8_t* s_depth;                       // ... and the ring slot's copy of them
     int se;                                 // feature-attention variant: record[RANGE_SE] is part of the verdict and of the mirror
-    unsigned depth_vec;                     // 16-byte units of a window's depth planes (float32 always; seg_vec follows the label format)
+    unsigned depth_vec;                     // 16-byte units of a window's depth planes (follows the depth format; seg_vec follows the label format)
 };
 
 }  // namespace davo

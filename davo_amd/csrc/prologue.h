@@ -401,10 +401,11 @@ __global__ __launch_bounds__(256) void se_class_squeeze(const uint8_t* __restric
 // float32 rounding only.  A thread takes four horizontally adjacent pixels (one 16-byte load) per step and adds them as
 // (x + y) + (z + w); then the fixed wave butterfly and a fixed tree over the four waves: one float32 word per record
 // (partial[b][frame][chunk][0]), bitwise the same run after run, no atomics on the sums.  depth is [B][3 file planes: src0, tgt,
-// src1][H][W] float32, 16-byte aligned; H*W is a multiple of 16.  FOLD: the workgroup that delivers the triplet's last record
-// evaluates its three tables (se_squeeze_excite's protocol, pose_tail.h).
-template <bool FOLD>
-__global__ __launch_bounds__(256) void se_depth_squeeze(const float* __restrict__ depth, int HW, Variant v,
+// src1][H][W] in the depth format DT (float or depth_f16, input_decode.h), 16-byte aligned; H*W is a multiple of 16.  A unit comes
+// from one depth_fetch4, so the chunking, the sum's order and every bit are the float32 format's.  FOLD: the workgroup that
+// delivers the triplet's last record evaluates its three tables (se_squeeze_excite's protocol, pose_tail.h).
+template <bool FOLD, typename DT>
+__global__ __launch_bounds__(256) void se_depth_squeeze(const DT* __restrict__ depth, int HW, Variant v,
                                                         unsigned* __restrict__ partial, unsigned* __restrict__ counters,
                                                         const float* __restrict__ w1, const float* __restrict__ b1,
                                                         const float* __restrict__ w2, const float* __restrict__ b2,
@@ -414,13 +415,13 @@ __global__ __launch_bounds__(256) void se_depth_squeeze(const float* __restrict_
     const int frame = (sel == PAIRS_BOTH || blockIdx.y == 0) ? (int)blockIdx.y : 1 + (sel >> 1);
     if (FOLD && range_reset && chunk == 0 && frame == 0 && b == 0 && threadIdx.x == 0) range_reset[RANGE_SNAP] = 0u;   // as se_excite
     const int plane = frame == 0 ? 1 : frame == 1 ? 0 : 2;     // (tgt, src0, src1) -> file order src0, tgt, src1 (davo.py:991-996)
-    const float4* dp = reinterpret_cast<const float4*>(depth + ((size_t)b * 3 + plane) * HW);
+    const DT* dp = depth + ((size_t)b * 3 + plane) * HW;
     const int nunits = HW >> 2;
     const int per = (nunits + SQ_CHUNKS - 1) / SQ_CHUNKS;
     const int beg = chunk * per, end = min(beg + per, nunits);
     float sum = 0.f;
     for (int i = beg + threadIdx.x; i < end; i += 256) {
-        const float4 q = dp[i];
+        const float4 q = depth_fetch4(dp + (size_t)i * 4);
         sum += (q.x + q.y) + (q.z + q.w);
     }
     __shared__ float red[4];
@@ -453,13 +454,13 @@ __global__ __launch_bounds__(256) void se_depth_squeeze(const float* __restrict_
 // v0 variants (rgb only) leave the flow slots zero.
 // LT: the label format, float32 or bytes; a thread's four labels of a plane come from one label_fetch4 (input_decode.h).
 // FT: the flow format, float32 or binary16; a thread's four pixels of flow come from one flow_fetch4 (input_decode.h).
-// DSPLIT (att_source 13, the depth-split flow attention): per 4-pixel group one more float4, of the depth plane of the source frame
-// the label map belongs to (file plane 0 or 2), and each pixel's class is looked up in the near table `tab' or the far table
+// DSPLIT (att_source 13, the depth-split flow attention): per 4-pixel group one more depth_fetch4 (DT: the depth format, float32 or
+// binary16, input_decode.h), of the depth plane of the source frame the label map belongs to (file plane 0 or 2), and each pixel's class is looked up in the near table `tab' or the far table
 // `ds.tab_far' by att_lookup_split (input_decode.h, with DepthSplit); everything else is the same code.  The target's map is ones.
-template <int LD, bool DSPLIT, typename LT, typename FT>
+template <int LD, bool DSPLIT, typename LT, typename FT, typename DT>
 __device__ __forceinline__ void mask_pack_body(const uint8_t* __restrict__ img, const FT* __restrict__ flow,
                                                const LT* __restrict__ seg, const float* __restrict__ tab,
-                                               const Variant& v, int B, int sel, int H, int W, float* __restrict__ out, const DepthSplit& ds) {
+                                               const Variant& v, int B, int sel, int H, int W, float* __restrict__ out, const DepthSplitOf<DT>& ds) {
     const int W4 = W >> 2;
     const long total = (long)B * pairs_per_window(sel) * H * W4;
     const long gid_raw = (long)blockIdx.x * 256 + threadIdx.x;
@@ -492,7 +493,7 @@ __device__ __forceinline__ void mask_pack_body(const uint8_t* __restrict__ img, 
     // -no_segmask (davo.py:1387), the tgt frame unless static_all (davo.py:1394,1411).
     float as[4] = {1.f, 1.f, 1.f, 1.f};
     if (DSPLIT) {
-        const float4 dp = *reinterpret_cast<const float4*>(ds.depth + ((size_t)b * 3 + (s ? 2 : 0)) * H * W + pix);
+        const float4 dp = depth_fetch4(ds.depth + ((size_t)b * 3 + (s ? 2 : 0)) * H * W + pix);
         const float* far_s = ds.tab_far + ((size_t)b * 3 + 1 + s) * NCLS;
         as[0] = att_lookup_split(tab_s, far_s, ds.thr, dp.x, sg.id[0]); as[1] = att_lookup_split(tab_s, far_s, ds.thr, dp.y, sg.id[1]);
         as[2] = att_lookup_split(tab_s, far_s, ds.thr, dp.z, sg.id[2]); as[3] = att_lookup_split(tab_s, far_s, ds.thr, dp.w, sg.id[3]);
@@ -576,10 +577,10 @@ __global__ __launch_bounds__(256) void mask_pack(const uint8_t* __restrict__ img
     mask_pack_body<LD, false>(img, flow, seg, tab, v, B, sel, H, W, out, DepthSplit{});
 }
 
-template <int LD, typename LT, typename FT>
+template <int LD, typename LT, typename FT, typename DT>
 __global__ __launch_bounds__(256) void mask_pack_depthsplit(const uint8_t* __restrict__ img, const FT* __restrict__ flow,
                                                             const LT* __restrict__ seg, const float* __restrict__ tab,
-                                                            Variant v, int B, int sel, int H, int W, float* __restrict__ out, DepthSplit ds) {
+                                                            Variant v, int B, int sel, int H, int W, float* __restrict__ out, DepthSplitOf<DT> ds) {
     mask_pack_body<LD, true>(img, flow, seg, tab, v, B, sel, H, W, out, ds);
 }
 
@@ -824,7 +825,7 @@ __device__ __forceinline__ void snapshot_inputs_if_range_fails(const SnapArgs& a
     const size_t n_img = (size_t)a.img_vec * a.B, n_seg = (size_t)a.seg_vec * a.B, n_flow = (size_t)a.flow_vec_half * a.B;
     for (size_t i = worker; i < n_img; i += nworkers) di[i] = si[i];
     for (size_t i = worker; i < n_seg; i += nworkers) ds[i] = ss[i];
-    if (a.s_depth) {                                           // depth sources: float32 planes, whatever the label format
+    if (a.s_depth) {                                           // depth sources: depth_vec 16-byte vectors of the depth format's planes, whatever the label format
         const uint4* sd = reinterpret_cast<const uint4*>(a.depth);
         uint4* dd = reinterpret_cast<uint4*>(a.s_depth);
         const size_t n_depth = (size_t)a.depth_vec * a.B;

@@ -43,11 +43,12 @@ inline FramePlan frame_plan(int N, int sel, int att_source) {
     p.flow[1] = s1 ? 2 : 1;
     return p;
 }
-// bytes that cross the link for such a batch (label_bytes: 4 or 1 per pixel; flow_bytes: 4 or 2 per component, float32 or binary16)
-inline long long frame_plan_bytes(const FramePlan& p, int N, int H, int W, int label_bytes, int flow_bytes = 4) {
+// bytes that cross the link for such a batch (label_bytes: 4 or 1 per pixel; flow_bytes: 4 or 2 per component, float32 or binary16;
+// depth_bytes: 4 or 2 per pixel, float32 or binary16)
+inline long long frame_plan_bytes(const FramePlan& p, int N, int H, int W, int label_bytes, int flow_bytes = 4, int depth_bytes = 4) {
     const long long HW = (long long)H * W;
     return (p.img[1] - p.img[0]) * HW * 3 + (long long)N * (p.flow[1] - p.flow[0]) * HW * 2 * flow_bytes +
-           (p.seg[1] - p.seg[0]) * HW * label_bytes + (p.depth[1] - p.depth[0]) * HW * 4;
+           (p.seg[1] - p.seg[0]) * HW * label_bytes + (p.depth[1] - p.depth[0]) * HW * depth_bytes;
 }
 
 struct GatherArgs {
@@ -89,8 +90,9 @@ __device__ __forceinline__ void gather_copy(const uint8_t* __restrict__ src, uin
 }
 
 // LT: the label element (float or uint8_t, davo_set_label_format); FT: the flow element (float or flow_f16, davo_set_flow_format) -
-// a flow plane is 2 H W of them, a whole number of 16-byte vectors in either format (H W is a multiple of 16)
-template <typename LT, typename FT>
+// a flow plane is 2 H W of them, a whole number of 16-byte vectors in either format (H W is a multiple of 16); DT: the depth
+// element (float or depth_f16, davo_set_depth_format) - a depth plane is H W of them, a whole number of vectors too
+template <typename LT, typename FT, typename DT>
 __global__ __launch_bounds__(256) void window_gather(GatherArgs a) {
     const size_t n = blockIdx.y, HW = (size_t)a.H * a.W;
     const int job = blockIdx.z;
@@ -108,7 +110,7 @@ __global__ __launch_bounds__(256) void window_gather(GatherArgs a) {
         const int k = (job - 3) % 3;
         if (depth && !a.f_depth) return;
         if (k == 1 ? !(both || (depth ? a.depth_tgt : a.seg_tgt)) : !(a.sel & (k == 0 ? PAIRS_SRC0 : PAIRS_SRC1))) return;
-        const size_t pb = HW * (depth ? sizeof(float) : sizeof(LT));
+        const size_t pb = HW * (depth ? sizeof(DT) : sizeof(LT));
         const unsigned nvec = (unsigned)(pb / 16);
         gather_copy<gather_vec4>((depth ? a.f_depth : a.f_seg) + (n + k) * pb, (depth ? a.w_depth : a.w_seg) + (n * 3 + k) * pb, nvec, nvec, 0);
     } else {                                              // flow plane p: [N][2] -> planes 0, 1 of [B][4]

@@ -3,10 +3,10 @@
 // third of the strip, every flow plane, label map and depth plane on its own; no value changes (the horizontal flow component is
 // NOT negated), plane and frame order stay.  The mirror happens once, where a batch becomes the staging set its forward reads
 // (entry.hip: stage_windows); nothing downstream of the set knows.
-//   window_mirror<LT, FT, false>   window layout: sources and destinations are both window-major.  In place (the host entry points:
-//                                  the staging set after its copies) or from the caller's device buffers into the set.
-//   window_mirror<LT, FT, true>    frame layout: window_gather with mirrored stores - frame-major sources (window_gather.h), the
-//                                  same grid, no launch more than a gather; a flow that is in the set already is mirrored in place.
+//   window_mirror<LT, FT, DT, false>   window layout: sources and destinations are both window-major.  In place (the host entry points:
+//                                      the staging set after its copies) or from the caller's device buffers into the set.
+//   window_mirror<LT, FT, DT, true>    frame layout: window_gather with mirrored stores - frame-major sources (window_gather.h), the
+//                                      same grid, no launch more than a gather; a flow that is in the set already is mirrored in place.
 // A grid of (pieces, window, job), the jobs window_gather's: one third of the strip rows, one label or depth plane, one flow plane.
 // Only what the pair selection and the variant read is touched (frame_plan's / stage_inputs' rule).
 // A row is cut into units of a whole number of pixels; a lane holds unit p of a row and its partner U - 1 - p, reverses the pixels
@@ -15,7 +15,8 @@
 //   strip thirds   3-byte pixels: 16 pixels = 48 bytes (W % 16 == 0), else 4 pixels = three dwords (rows of 3W bytes are dword-aligned)
 //   flow           8-byte pixels: 4 pixels = 32 bytes;  binary16: 4-byte pixels, 4 pixels = 16 bytes
 //   labels         float32: 4 pixels = 16 bytes;  u8: 16 pixels = 16 bytes (W % 16 == 0), else 4 pixels = one dword
-//   depth          4 pixels = 16 bytes
+//   depth          float32: 4 pixels = 16 bytes;  binary16: 8 pixels = 16 bytes (W % 8 == 0), else 4 pixels = 8 bytes (rows of 2W
+//                  bytes are 8-byte aligned, W being a multiple of 4)
 // Four pixels of three bytes are three dwords; their mirror is three byte permutes (v_perm_b32) and one more for the middle dword.
 // Pure streaming, two pairs of units in flight per lane, all loads of a round ahead of its first store; 64-bit offsets.  No
 // floating-point arithmetic at all.
@@ -43,10 +44,10 @@ __host__ __device__ __forceinline__ uint32_t mirror_perm(uint32_t hi, uint32_t l
 #endif
 }
 
-// The pixels of one unit in reverse order.  PX: bytes per pixel (1, 3, 4, 8); K: dwords per unit.
+// The pixels of one unit in reverse order.  PX: bytes per pixel (1, 2, 3, 4, 8); K: dwords per unit.
 template <int PX, int K>
 __host__ __device__ __forceinline__ void mirror_unit(const uint32_t (&in)[K], uint32_t (&out)[K]) {
-    static_assert(PX == 1 || PX == 3 || PX == 4 || PX == 8, "pixel sizes of the input planes");
+    static_assert(PX == 1 || PX == 2 || PX == 3 || PX == 4 || PX == 8, "pixel sizes of the input planes");
     static_assert((K * 4) % PX == 0 && (PX != 3 || K % 3 == 0) && (PX != 8 || K % 2 == 0), "a unit is a whole number of pixels");
     if constexpr (PX == 4) {
 #pragma unroll
@@ -57,6 +58,10 @@ __host__ __device__ __forceinline__ void mirror_unit(const uint32_t (&in)[K], ui
     } else if constexpr (PX == 1) {
 #pragma unroll
         for (int i = 0; i < K; ++i) out[i] = mirror_perm(0u, in[K - 1 - i], 0x00010203u);
+    } else if constexpr (PX == 2) {
+        // two halves b0 b1 | b2 b3 in a dword -> b2 b3 | b0 b1: one byte permute; dwords in reverse order
+#pragma unroll
+        for (int i = 0; i < K; ++i) out[i] = mirror_perm(0u, in[K - 1 - i], 0x01000302u);
     } else {
         // four pixels b0..b11 in (d0, d1, d2) -> b9 b10 b11 b6 | b7 b8 b3 b4 | b5 b0 b1 b2; groups of four pixels in reverse order
 #pragma unroll
@@ -78,6 +83,9 @@ __device__ __forceinline__ void mirror_load(const uint8_t* p, uint32_t (&v)[K]) 
             const gather_vec4 q = reinterpret_cast<const gather_vec4*>(p)[i];
             v[4 * i] = q.x; v[4 * i + 1] = q.y; v[4 * i + 2] = q.z; v[4 * i + 3] = q.w;
         }
+    } else if constexpr (K == 2) {                          // one 8-byte load (binary16 depth rows with W % 8 == 4)
+        const uint2 q = *reinterpret_cast<const uint2*>(p);
+        v[0] = q.x; v[1] = q.y;
     } else {
 #pragma unroll
         for (int i = 0; i < K; ++i) v[i] = reinterpret_cast<const uint32_t*>(p)[i];
@@ -93,6 +101,8 @@ __device__ __forceinline__ void mirror_store(uint8_t* p, const uint32_t (&v)[K])
             q.x = v[4 * i]; q.y = v[4 * i + 1]; q.z = v[4 * i + 2]; q.w = v[4 * i + 3];
             reinterpret_cast<gather_vec4*>(p)[i] = q;
         }
+    } else if constexpr (K == 2) {
+        *reinterpret_cast<uint2*>(p) = make_uint2(v[0], v[1]);
     } else {
 #pragma unroll
         for (int i = 0; i < K; ++i) reinterpret_cast<uint32_t*>(p)[i] = v[i];
@@ -139,6 +149,9 @@ __device__ __forceinline__ void mirror_plane(const uint8_t* src, uint8_t* dst, i
     if constexpr (PX == 1) {
         if (W % 16 == 0) mirror_rows<1, 4>(src, pitch, dst, pitch, H, W / 16);
         else mirror_rows<1, 1>(src, pitch, dst, pitch, H, W / 4);
+    } else if constexpr (PX == 2) {
+        if (W % 8 == 0) mirror_rows<2, 4>(src, pitch, dst, pitch, H, W / 8);
+        else mirror_rows<2, 2>(src, pitch, dst, pitch, H, W / 4);
     } else {
         mirror_rows<PX, PX>(src, pitch, dst, pitch, H, W / 4);      // four pixels: PX dwords
     }
@@ -149,7 +162,7 @@ __device__ __forceinline__ void mirror_plane(const uint8_t* src, uint8_t* dst, i
 // attends the target, so its label map is read - whatever the selection; where it does not, no kernel reads that map (davo_submit's
 // staging does not even copy it) and the mirror leaves it alone.  depth_tgt: a ONE-pair batch reads the target's depth plane
 // (both pairs: every plane, stage_inputs copies them whole).
-template <typename LT, typename FT, bool FRAMES>
+template <typename LT, typename FT, typename DT, bool FRAMES>
 __global__ __launch_bounds__(256) void window_mirror(GatherArgs a) {
     const size_t n = blockIdx.y, HW = (size_t)a.H * a.W;
     const int job = blockIdx.z;
@@ -168,10 +181,10 @@ __global__ __launch_bounds__(256) void window_mirror(GatherArgs a) {
         const int k = (job - 3) % 3;
         if (depth && !a.f_depth) return;
         if (k == 1 ? !(depth ? (both || a.depth_tgt) : a.seg_tgt) : !(a.sel & (k == 0 ? PAIRS_SRC0 : PAIRS_SRC1))) return;
-        const size_t pb = HW * (depth ? sizeof(float) : sizeof(LT));
+        const size_t pb = HW * (depth ? sizeof(DT) : sizeof(LT));
         const uint8_t* src = (depth ? a.f_depth : a.f_seg) + (FRAMES ? n + k : n * 3 + k) * pb;
         uint8_t* dst = (depth ? a.w_depth : a.w_seg) + (n * 3 + k) * pb;
-        if (depth) mirror_plane<4>(src, dst, a.H, a.W);
+        if (depth) mirror_plane<(int)sizeof(DT)>(src, dst, a.H, a.W);
         else mirror_plane<(int)sizeof(LT)>(src, dst, a.H, a.W);
     } else {                                              // flow plane p of planes 0, 1 of [B][4]
         const int p = job - 9;

@@ -14,6 +14,7 @@ import numpy as np
 from . import _lib
 from .labels import LABEL_DTYPES, LABEL_FORMATS, check_label_format, labels_to_u8  # noqa: F401
 from .flow import FLOW_DTYPES, FLOW_FORMATS, check_flow_format, flow_from_f16, flow_to_f16  # noqa: F401
+from .depth import DEPTH_DTYPES, DEPTH_FORMATS, check_depth_format, depth_from_f16, depth_to_f16  # noqa: F401
 from .frames import flip_windows
 from .version import NUM_SEG_CLASSES, att_source_id, parse_version, weight_shapes
 
@@ -115,16 +116,20 @@ class DeviceBuffer:
 class Engine:
     """Thin object wrapper of one ``davo_ctx`` (one GPU, one host thread)."""
 
-    def __init__(self, cfg, img_height, img_width, max_batch, device=0, labels="f32", flow="f32"):
+    def __init__(self, cfg, img_height, img_width, max_batch, device=0, labels="f32", flow="f32", depth="f32"):
         """``labels``: the format of every label map this engine takes - "f32" (the reference's float32 [B,3,H,W,1], the default)
         or "u8" (uint8 class ids, a quarter of the bytes; include/davo_hip.h: davo_set_label_format, davo_amd.labels_to_u8).
         ``flow``: the format of every flow array - "f32" (the default) or "f16" (IEEE binary16 in the same layout, half the
-        bytes; include/davo_hip.h: davo_set_flow_format, davo_amd.flow_to_f16)."""
+        bytes; include/davo_hip.h: davo_set_flow_format, davo_amd.flow_to_f16).
+        ``depth``: the format of every depth array - "f32" (the default) or "f16" (IEEE binary16 in the same layout, half the
+        bytes; include/davo_hip.h: davo_set_depth_format, davo_amd.depth_to_f16).  A variant that reads no depth accepts it."""
         check_label_format(labels)
         check_flow_format(flow)
+        check_depth_format(depth)
         self.cfg, self.H, self.W, self.max_batch, self.device = cfg, img_height, img_width, max_batch, device
         self.labels = "f32"
         self.flow = "f32"
+        self.depth = "f32"
         self._L = _lib.lib()
         self._ctx = ctypes.c_void_p()
         self.host_chunk = 8                       # davo_set_option "host_chunk" as last set through set_option (its default)
@@ -160,6 +165,18 @@ class Engine:
             except Exception:
                 self.close()
                 raise
+        if depth != "f32":
+            try:
+                self.set_depth_format(depth)
+            except Exception:
+                self.close()
+                raise
+
+    def set_depth_format(self, depth):
+        """Select the depth format, "f32" or "f16" (include/davo_hip.h: davo_set_depth_format): before the first call that takes
+        inputs, ValueError afterwards.  From then on every depth array must have that dtype; nothing is converted silently."""
+        self._check(self._L.davo_set_depth_format(self._ctx, DEPTH_FORMATS[check_depth_format(depth)]))
+        self.depth = depth
 
     def set_flow_format(self, flow):
         """Select the flow format, "f32" or "f16" (include/davo_hip.h: davo_set_flow_format): before the first call that takes
@@ -221,16 +238,26 @@ class Engine:
             self._check(self._L.davo_load_weight(self._ctx, name.encode(), a.ctypes.data_as(ctypes.POINTER(ctypes.c_float)), shape, a.ndim))
 
     def _depth_arg(self, depth, shape, names, strict=None):
-        """The depth planes of a batch as the entry points take them (float32 of ``shape``: [B,3,H,W,1] in file order src0, tgt,
-        src1, davo.py:991-996, or the frame layout's [N+2,H,W,1]), or None for a variant that reads none (a depth array handed to
-        such a variant is ignored, as the reference ignores its depth input there).  ``strict``: see _contiguous."""
+        """The depth planes of a batch as the entry points take them (of the engine's depth format and of ``shape``: [B,3,H,W,1]
+        in file order src0, tgt, src1, davo.py:991-996, or the frame layout's [N+2,H,W,1]), or None for a variant that reads none
+        (a depth array handed to such a variant is ignored, as the reference ignores its depth input there).  A float16 array
+        handed to a float32 engine, or anything but float16 to a binary16 engine, is a ValueError.  ``strict``: see _contiguous."""
         if not self.cfg.needs_depth:
             return None
-        if strict and not _is_ready(depth, np.float32):
-            raise ValueError("%s(hold > 0) needs a C-contiguous float32 depth array (a converted copy would not outlive the call)" % strict)
+        if strict and not _is_ready(depth, DEPTH_DTYPES[self.depth]):
+            raise ValueError("%s(hold > 0) needs a C-contiguous %s depth array (a converted copy would not outlive the call)"
+                             % (strict, DEPTH_DTYPES[self.depth]))
         if depth is None:
             raise ValueError("%s and depth inputs are all required for version `%s'" % (names, self.cfg.version))
-        depth = np.ascontiguousarray(depth, np.float32)
+        is_f16 = np.asarray(depth).dtype == np.float16
+        if self.depth == "f16":
+            if not is_f16:
+                raise ValueError("this engine takes float16 depth (depth='f16'), got dtype %s: convert with davo_amd.depth_to_f16" % np.asarray(depth).dtype)
+            depth = np.ascontiguousarray(depth)
+        elif is_f16:
+            raise ValueError("this engine takes float32 depth (depth='f32'), got float16: create it with depth='f16'")
+        else:
+            depth = np.ascontiguousarray(depth, np.float32)
         if depth.shape != shape:
             raise ValueError("depth shape %s != %s" % (depth.shape, shape))
         return depth
@@ -391,6 +418,8 @@ class Engine:
             raise ValueError("d_seg holds %s label maps, this engine takes labels='%s'" % (d_seg.dtype, self.labels))
         if self.cfg.needs_depth and depth is None:
             raise ValueError("%s and depth inputs are all required for version `%s'" % (names, self.cfg.version))
+        if self.cfg.needs_depth and getattr(depth, "dtype", None) is not None and (depth.dtype == np.float16) != (self.depth == "f16"):
+            raise ValueError("depth holds %s depth planes, this engine takes depth='%s'" % (depth.dtype, self.depth))
         ms = ctypes.c_float(0.0)
         self._call(name, n, bufs, depth if depth_slot or self.cfg.needs_depth else None, d_pose, ctypes.byref(ms) if timed else None, depth_slot=depth_slot)
         return ms.value if timed else None
@@ -649,6 +678,7 @@ class DAVO(object):
         self._features = 'full'
         self._labels = "f32"
         self._flow = "f32"
+        self._depth = "f32"
         self._flip = bool(flip)
 
     def use_f16_flow(self):
@@ -658,6 +688,16 @@ class DAVO(object):
         if self.engine is not None:
             raise DavoError("use_f16_flow() must be called before setup_inference")
         self._flow = "f16"
+        return self
+
+    def use_f16_depth(self):
+        """Opt in to binary16 depth planes (include/davo_hip.h: davo_set_depth_format): ``input_depth``, ``inference(inputs=...)``
+        and iterator inputs then carry float16 [B,3,H,W,1] (davo_amd.depth_to_f16 of the float32 planes) and float32 depth is
+        refused.  Before ``setup_inference`` - which also picks the format up by itself from a float16 ``input_depth``.  A
+        variant that reads no depth accepts the call.  Returns self."""
+        if self.engine is not None:
+            raise DavoError("use_f16_depth() must be called before setup_inference")
+        self._depth = "f16"
         return self
 
     def use_u8_labels(self):
@@ -708,7 +748,9 @@ class DAVO(object):
         self.cfg = parse_version(self.version)
         if isinstance(input_flow, np.ndarray) and input_flow.dtype == np.float16:
             self._flow = "f16"                             # a float16 ``input_flow`` selects the binary16 flow format
-        self.engine = Engine(self.cfg, img_height, img_width, batch_size, self.device, labels=self._labels, flow=self._flow)
+        if isinstance(input_depth, np.ndarray) and input_depth.dtype == np.float16:
+            self._depth = "f16"                            # a float16 ``input_depth`` selects the binary16 depth format
+        self.engine = Engine(self.cfg, img_height, img_width, batch_size, self.device, labels=self._labels, flow=self._flow, depth=self._depth)
         if self._weights is not None:
             self.engine.load_weights(self._weights)
         if flip is not None:

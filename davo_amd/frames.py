@@ -6,7 +6,7 @@ A sequence of N windows is N + 2 frames; window n is (src0, tgt, src1) = frames 
 * ``frames`` u8  ``[N+2,H,W,3]``
 * ``flow2``  f32 ``[N,2,H,W,2]``   (float16 for a binary16 engine, davo_amd.flow_to_f16: both conversions keep the dtype) planes (tgt->src0, tgt->src1) of window n - planes 0, 1 of the window layout's ``[B,4,H,W,2]``
 * ``seg``        ``[N+2,H,W,1]``   float32 or uint8 (davo_amd.labels_to_u8)
-* ``depth``  f32 ``[N+2,H,W,1]``   depth-source variants only
+* ``depth``  f32 ``[N+2,H,W,1]``   depth-source variants only (float16 for a binary16-depth engine, davo_amd.depth_to_f16: every conversion keeps the dtype)
 
 The window layout is the reference's (``data_loader.py:537-557``, ``davo.py:978-1004``): strip ``[B,H,3W,3]`` src0|tgt|src1,
 planes ``[B,3,H,W,1]`` in file order src0, tgt, src1.  ``Engine.forward_frames`` / ``submit_frames`` / ``forward_device_frames`` take
@@ -16,6 +16,7 @@ import ctypes
 import numpy as np
 
 from . import _lib
+from .depth import DEPTH_FORMATS, check_depth_format
 from .flow import FLOW_FORMATS, check_flow_format
 from .labels import LABEL_FORMATS, check_label_format
 from .version import att_source_id
@@ -121,22 +122,26 @@ def flip_frames(frames, flow2, seg, depth=None):
     return out if depth is None else out + (planes(np.asarray(depth), "depth"),)
 
 
-def frames_plan(H, W, N, pairs="both", att_source="se_flow", labels="f32", flow="f32"):
+def frames_plan(H, W, N, pairs="both", att_source="se_flow", labels="f32", flow="f32", depth="f32"):
     """What a frame-layout batch of N windows reads (include/davo_hip.h: davo_frames_plan - the function the library's copies and
     its gather kernel are driven by; no GPU needed): ``{'frames', 'seg', 'depth', 'flow': (lo, hi), 'link_bytes': int}`` - frame
     ranges of the pixels, the label maps and the depth planes ((0, 0) where the source reads no depth), the flow planes, and the
     bytes the host entry points send.  ``att_source``: a name of davo_amd.version.ATT_SOURCE / POOLED_ATT_SOURCE or its number.  ``flow``: "f32", or
-    "f16" for a binary16 engine (davo_frames_plan_fmt): half the flow's bytes in 'link_bytes', the same ranges."""
+    "f16" for a binary16 engine (davo_frames_plan_fmt): half the flow's bytes in 'link_bytes', the same ranges.  ``depth``: "f32",
+    or "f16" for a binary16-depth engine (davo_frames_plan_fmt2): half the depth planes' bytes, the same ranges."""
     if pairs not in PAIRS:
         raise ValueError("pairs must be 'both', 'src0' or 'src1', got %r" % (pairs,))
     att = att_source_id(att_source) if isinstance(att_source, str) else int(att_source)
     r = (ctypes.c_int * 8)()
     nbytes = ctypes.c_longlong(0)
     lab = LABEL_FORMATS[check_label_format(labels)]
-    if check_flow_format(flow) == "f32" and att <= 13:         # (davo_frames_plan keeps the range it was published with, 0..13)
+    if check_depth_format(depth) != "f32":
+        rc = _lib.lib().davo_frames_plan_fmt2(int(H), int(W), int(N), PAIRS[pairs], att, lab, FLOW_FORMATS[check_flow_format(flow)],
+                                              DEPTH_FORMATS[depth], r, ctypes.byref(nbytes))
+    elif check_flow_format(flow) == "f32" and att <= 13:         # (davo_frames_plan keeps the range it was published with, 0..13)
         rc = _lib.lib().davo_frames_plan(int(H), int(W), int(N), PAIRS[pairs], att, lab, r, ctypes.byref(nbytes))
     else:
         rc = _lib.lib().davo_frames_plan_fmt(int(H), int(W), int(N), PAIRS[pairs], att, lab, FLOW_FORMATS[flow], r, ctypes.byref(nbytes))
     if rc != 0:
-        raise ValueError("davo_frames_plan(%r) refused its arguments" % ((H, W, N, pairs, att_source, labels, flow),))
+        raise ValueError("davo_frames_plan(%r) refused its arguments" % ((H, W, N, pairs, att_source, labels, flow) + (() if depth == "f32" else (depth,)),))
     return {"frames": (r[0], r[1]), "seg": (r[2], r[3]), "depth": (r[4], r[5]), "flow": (r[6], r[7]), "link_bytes": nbytes.value}

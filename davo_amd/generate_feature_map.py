@@ -97,6 +97,10 @@ def build_parser():
     ap.add_argument("--labels", choices=("f32", "u8"), default="f32",
                     help="u8: the label maps are loaded and handed to the library as uint8 class ids (davo_set_label_format); "
                          "the written files are the same")
+    ap.add_argument("--depth", choices=("f32", "f16"), default="f32",
+                    help="f16: the depth planes of a depth-source version are handed over as IEEE binary16 (include/davo_hip.h: "
+                         "davo_set_depth_format; float32 -monodepth2_depth.npy files are rounded by davo_amd.depth_to_f16, float16 ones "
+                         "read as they are).  The files written are those of a float32 run on the rounded planes")
     ap.add_argument("--flip", action="store_true",
                     help="run the left-right mirrored sequence (include/davo_hip.h: davo_set_flip, each frame mirrored on its own); the "
                          "files go under <output_dir>-flip, as the reference's flip switch appends `-flip' to its output root "
@@ -122,10 +126,11 @@ def main(argv=None):
                          "table to write (a near and a far table are selected per pixel by depth); use "
                          "DAVO.inference(mode='feature') for its attention maps and features" % a.version)
     synthetic = bool(a.synthetic)
+    depth_arg = ("f16" if a.depth == "f16" else True) if cfg.needs_depth else False      # the loaders' ``depth`` argument
     if synthetic:
         from . import synth
         n_frames = a.synthetic
-        load = S.synthetic_window_loader(H, W, depth=cfg.needs_depth, labels=a.labels)
+        load = S.synthetic_window_loader(H, W, depth=depth_arg, labels=a.labels)
         weights = synth.make_weights(a.version)
     else:
         if not a.concat_img_dir or not a.ckpt_file:
@@ -135,7 +140,7 @@ def main(argv=None):
             raise SystemExit("davo_amd.generate_feature_map: sequence %.2d: no directory %s" % (seq, d))
         n_frames = sum(1 for f in os.listdir(d) if f.endswith(".jpg")) + 2 * int((a.seq_length - 1) / 2)       # :83-84
         from .tf_checkpoint import load_weights
-        load = S.kitti_window_loader(a.concat_img_dir, seq, n_frames, H, W, depth=cfg.needs_depth, seg_planes=(0, 1, 2), labels=a.labels)
+        load = S.kitti_window_loader(a.concat_img_dir, seq, n_frames, H, W, depth=depth_arg, seg_planes=(0, 1, 2), labels=a.labels)
         weights = load_weights(a.ckpt_file)
     if n_frames < 3:
         raise SystemExit("davo_amd.generate_feature_map: sequence %.2d has %d frames: a window needs three" % (seq, n_frames))
@@ -147,6 +152,8 @@ def main(argv=None):
     system = DAVO(version=a.version, device=a.device, flip=a.flip).enable_feature_mode(features='heat')
     if a.labels == "u8":
         system.use_u8_labels()
+    if a.depth == "f16":
+        system.use_f16_depth()
     system.setup_inference(H, W, "davo", a.seq_length, a.batch_size)
     system.load_weights(weights)
     poses = np.empty((n_windows, 2, 6), np.float32)

@@ -11,7 +11,9 @@ sequence ``SS`` is
                                            (the binary16 form of davo_amd.flow_to_f16) and converts float32 files by that rule
     <dump>/SS/FFFFFF-seglabel.npy     float32 (3, H, W, 1)   (file order src0, tgt, src1); also accepted: uint8 class ids of
                                            the same shape (what DeepLab writes; the byte form of davo_amd.labels_to_u8)
-    <dump>/SS/FFFFFF-monodepth2_depth.npy  float32 (3, H, W, 1)   (same order; read only for a depth-source variant:
+    <dump>/SS/FFFFFF-monodepth2_depth.npy  float32 (3, H, W, 1)   (a ``depth="f16"`` loader also reads float16 of the same shape as it
+                                           is - the binary16 form of davo_amd.depth_to_f16 - and converts float32 files by that rule;
+                                           same order; read only for a depth-source variant:
                                            test_kitti_pose.py:48,91, data_loader.py:271-274,500-501)
 
 ``ThreadedWindowLoader`` is the same pipeline with a thread pool and a bounded prefetch queue: batches
@@ -27,6 +29,7 @@ from concurrent.futures import ProcessPoolExecutor, ThreadPoolExecutor
 
 import numpy as np
 
+from .depth import DEPTH_DTYPES, check_depth_format, depth_to_f16
 from .flow import FLOW_DTYPES, check_flow_format, flow_to_f16
 from .labels import LABEL_DTYPES, check_label_format, labels_to_u8
 
@@ -58,13 +61,32 @@ def _flow_as_f16(a, path):
     raise ValueError("%s holds %s flow: a flow file is float32 or float16" % (path, a.dtype))
 
 
+def _depth_as_f16(a, path):
+    """A depth file's array as binary16: float16 as it is, float32 by depth_to_f16; any other dtype is an error that names the file."""
+    if a.dtype == np.float16:
+        return a
+    if a.dtype == np.float32:
+        return depth_to_f16(a)
+    raise ValueError("%s holds %s depth: a depth file is float32 or float16" % (path, a.dtype))
+
+
+def depth_mode(depth):
+    """A loader's ``depth`` argument -> the depth format, or None where no depth is read: False / None = none, True or "f32" =
+    float32 planes, "f16" = binary16 planes."""
+    if depth is None or depth is False:
+        return None
+    return "f32" if depth is True else check_depth_format(depth)
+
+
 def load_window(dump_dir, seq, tgt_idx, H, W, depth=False, labels="f32", flow="f32"):
     """One window -> (img u8 [H,3W,3], flow f32 [4,H,W,2], seg f32 [3,H,W,1]); with ``depth`` also the depth planes
     f32 [3,H,W,1] in file order, as a fourth element.  ``labels`` = "u8": seg is uint8 [3,H,W,1] - a uint8 label file as it is,
     a float32 one through labels_to_u8.  ``flow`` = "f16": flow is float16 [4,H,W,2] - a float16 flow file as it is, a float32
-    one through flow_to_f16."""
+    one through flow_to_f16.  ``depth`` = "f16" (instead of True): the depth planes are float16 [3,H,W,1] - a float16 depth file
+    as it is, a float32 one through depth_to_f16."""
     check_label_format(labels)
     flow_fmt = check_flow_format(flow)
+    depth_fmt = depth_mode(depth)
     from PIL import Image
     jpg, flo, sg = window_paths(dump_dir, seq, tgt_idx)
     with Image.open(jpg) as im:
@@ -80,20 +102,24 @@ def load_window(dump_dir, seq, tgt_idx, H, W, depth=False, labels="f32", flow="f
         seg = _labels_as_u8(np.load(sg, mmap_mode="r"), sg).reshape(3, H, W, 1)
     else:
         seg = np.load(sg, mmap_mode="r").astype(np.float32, copy=False).reshape(3, H, W, 1)
-    if depth:
+    if depth_fmt == "f16":
+        dp = depth_path(dump_dir, seq, tgt_idx)
+        return img, flow, seg, _depth_as_f16(np.load(dp, mmap_mode="r"), dp).reshape(3, H, W, 1)
+    if depth_fmt == "f32":
         dep = np.load(depth_path(dump_dir, seq, tgt_idx), mmap_mode="r").astype(np.float32, copy=False).reshape(3, H, W, 1)
         return img, flow, seg, dep
     return img, flow, seg
 
 
-def _read_npy_into(path, dst, planes=None, labels=False, flow16=False):
+def _read_npy_into(path, dst, planes=None, labels=False, flow16=False, depth16=False):
     """Read a C-ordered .npy of dst's dtype and size straight into dst (no intermediate array); anything else
     goes through np.load + cast.  ``planes``: indices along the first axis that are wanted — the others are skipped
     in the file (seek) and left as they are in dst (the path reads flow planes 0,1 and the source frames' label maps only:
     davo.py:978-982,998-1004, so 1.3 of a window's 2.3 MB never have to leave the page cache).  ``labels``: dst is a byte label
     slot - a uint8 file is read straight into it like any file of dst's dtype, a float32 file is converted plane by plane with
     labels_to_u8, any other dtype raises.  ``flow16``: dst is a binary16 flow slot - a float16 file is read straight into it, a
-    float32 file is converted plane by plane with flow_to_f16, any other dtype raises."""
+    float32 file is converted plane by plane with flow_to_f16, any other dtype raises.  ``depth16``: the same for a binary16 depth
+    slot and depth_to_f16."""
     with open(path, "rb") as f:
         major, _ = np.lib.format.read_magic(f)
         shape, fortran, dtype = (np.lib.format.read_array_header_1_0 if major == 1 else np.lib.format.read_array_header_2_0)(f)
@@ -118,6 +144,11 @@ def _read_npy_into(path, dst, planes=None, labels=False, flow16=False):
         a = a.reshape(dst.shape)
         for k in (range(len(dst)) if planes is None else planes):
             dst[k] = _flow_as_f16(a[k], path)
+        return
+    if depth16:                                           # a binary16 depth slot: the file's own halves, or depth_to_f16 of its floats
+        a = a.reshape(dst.shape)
+        for k in (range(len(dst)) if planes is None else planes):
+            dst[k] = _depth_as_f16(a[k], path)
         return
     a = a.astype(dst.dtype, copy=False).reshape(dst.shape)
     if planes is None:
@@ -184,8 +215,10 @@ def load_window_into(dump_dir, seq, tgt_idx, H, W, img, flow, seg, decoder=None,
     img[...] = a
     _read_npy_into(flo, flow, flow_planes, flow16=flow_fmt == "f16")
     _read_npy_into(sg, seg, seg_planes, labels=labels == "u8")
-    if depth is not None:
-        _read_npy_into(depth_path(dump_dir, seq, tgt_idx), depth)
+    if depth is not None:                                 # the slot's dtype says the depth format: float16 = binary16 planes
+        if depth.dtype not in (DEPTH_DTYPES["f32"], DEPTH_DTYPES["f16"]):
+            raise ValueError("a depth slot is float32 or float16, got %s" % depth.dtype)
+        _read_npy_into(depth_path(dump_dir, seq, tgt_idx), depth, depth16=depth.dtype == np.float16)
 
 
 def count_frames(dump_dir, seq, seq_length=3):
@@ -352,7 +385,8 @@ def _segment_batches(segments, B):
     return [(seq, s, min(s + B, hi)) for seq, lo, hi in segments for s in range(lo, hi, B)]
 
 
-def _slot_worker(k, P, names, ctrl_name, B, H, W, dump_dir, segments, flow_planes, seg_planes, chunk, nring, sem, errq, labels="f32", flow_fmt="f32"):
+def _slot_worker(k, P, names, ctrl_name, B, H, W, dump_dir, segments, flow_planes, seg_planes, chunk, nring, sem, errq, labels="f32", flow_fmt="f32",
+                 depth_fmt="f32"):
     """Worker k of P (a fork of the warm fork server): fills its chunks of the batches of ``segments`` (_segment_batches) in order,
     straight into the shared batch buffers, walking on from one segment into the next as ring places free up.  No task queue: which
     chunks are its own follows from k (_chunk_owner); ctrl[0] = number of batches that may be filled
@@ -375,7 +409,7 @@ def _slot_worker(k, P, names, ctrl_name, B, H, W, dump_dir, segments, flow_plane
             segs += t
             ring.append((np.ndarray((B, H, 3 * W, 3), np.uint8, buffer=t[0].buf), np.ndarray((B, 4, H, W, 2), FLOW_DTYPES[flow_fmt], buffer=t[1].buf),
                          np.ndarray((B, 3, H, W, 1), LABEL_DTYPES[labels], buffer=t[2].buf)) +
-                        ((np.ndarray((B, 3, H, W, 1), np.float32, buffer=t[3].buf),) if len(t) == 4 else ()))     # a depth variant's fourth buffer
+                        ((np.ndarray((B, 3, H, W, 1), DEPTH_DTYPES[depth_fmt], buffer=t[3].buf),) if len(t) == 4 else ()))     # a depth variant's fourth buffer
         cpb = -(-B // chunk)                               # chunks per batch (the last one of a batch may be short)
         batches = _segment_batches(segments, B)
         for c in range(len(batches) * cpb):
@@ -443,7 +477,8 @@ class ProcessWindowLoader:
     mapping).  Only the flow planes and label maps the variant consumes are read; the rest of a slot keeps its zeros.  Workers
     are forks of a warm fork server (worker_context): the parent may hold a HIP context, the server never does.
     ``depth``: one more shared, page-locked buffer per ring place for the depth planes of a depth-source variant (all three are
-    read); batches are then (img, flow, seg, depth).
+    read); batches are then (img, flow, seg, depth).  ``depth`` = "f16" (instead of True): that buffer is float16 - half its
+    shared, page-locked bytes - filled from float16 depth files as they are and from float32 ones through depth_to_f16 in the worker.
     ``labels`` = "u8": the label buffers are uint8 - a quarter of their shared, page-locked bytes - filled from uint8 label files
     as they are and from float32 ones through labels_to_u8 in the worker.
     ``flow`` = "f16": the flow buffers are float16 - half their shared, page-locked bytes - filled from float16 flow files as they
@@ -475,7 +510,9 @@ class ProcessWindowLoader:
             raise ValueError("no segment to load")
         seq, lo, hi = self.segments[0]
         self.args = (dump_dir, seq, H, W)
-        self.depth = bool(depth)
+        self.depth_fmt = depth_mode(depth)       # None: no depth buffer
+        self.depth = self.depth_fmt is not None
+        self._depth_bytes = DEPTH_DTYPES[self.depth_fmt or "f32"].itemsize
         self.lo, self.hi, self.B = lo, hi, batch_size
         self._batches = _segment_batches(self.segments, batch_size)
         self._first = np.cumsum([0] + [-(-(b - a) // batch_size) for _, a, b in self.segments])      # a segment's first batch
@@ -488,7 +525,7 @@ class ProcessWindowLoader:
         # fewer batches in flight if not, and a clear error - the caller falls back to the threaded loader - if not even four fit
         self._label_bytes = LABEL_DTYPES[self.labels].itemsize
         self._flow_bytes = FLOW_DTYPES[self.flow].itemsize
-        per_batch = batch_size * (H * 3 * W * 3 + 4 * H * W * 2 * self._flow_bytes + 3 * H * W * self._label_bytes + (3 * H * W * 4 if self.depth else 0))
+        per_batch = batch_size * (H * 3 * W * 3 + 4 * H * W * 2 * self._flow_bytes + 3 * H * W * self._label_bytes + (3 * H * W * self._depth_bytes if self.depth else 0))
         budget = shm_budget_bytes() if shm_budget is None else shm_budget
         want = self.prefetch + self.fill + 2 + self.hold
         self.nring = min(want, budget // per_batch)
@@ -517,7 +554,7 @@ class ProcessWindowLoader:
         from multiprocessing import shared_memory
         dump_dir, seq, H, W = self.args
         B, P = self.B, self.procs
-        sizes = (B * H * 3 * W * 3, B * 4 * H * W * 2 * self._flow_bytes, B * 3 * H * W * self._label_bytes) + ((B * 3 * H * W * 4,) if self.depth else ())
+        sizes = (B * H * 3 * W * 3, B * 4 * H * W * 2 * self._flow_bytes, B * 3 * H * W * self._label_bytes) + ((B * 3 * H * W * self._depth_bytes,) if self.depth else ())
         for _ in range(self.nring):
             trio = [shared_memory.SharedMemory(create=True, size=max(n, 1)) for n in sizes]
             self._segs.append(trio)
@@ -525,7 +562,7 @@ class ProcessWindowLoader:
                      np.ndarray((B, 4, H, W, 2), FLOW_DTYPES[self.flow], buffer=trio[1].buf),
                      np.ndarray((B, 3, H, W, 1), LABEL_DTYPES[self.labels], buffer=trio[2].buf))
             if self.depth:
-                views += (np.ndarray((B, 3, H, W, 1), np.float32, buffer=trio[3].buf),)
+                views += (np.ndarray((B, 3, H, W, 1), DEPTH_DTYPES[self.depth_fmt], buffer=trio[3].buf),)
             self._views.append(views)
         self._ctrl_shm = shared_memory.SharedMemory(create=True, size=8 * (2 + 3 * P))
         self._ctrl = np.ndarray((2 + 3 * P,), np.int64, buffer=self._ctrl_shm.buf)
@@ -536,7 +573,7 @@ class ProcessWindowLoader:
         self._sem, self._errq = ctx.Semaphore(0), ctx.SimpleQueue()
         self._pool = [ctx.Process(target=_slot_worker, daemon=True,
                                   args=(k, P, names, self._ctrl_shm.name, B, H, W, dump_dir, self.segments, self.fp, self.sp,
-                                        self.chunk, self.nring, self._sem, self._errq, self.labels, self.flow)) for k in range(P)]
+                                        self.chunk, self.nring, self._sem, self._errq, self.labels, self.flow, self.depth_fmt or "f32")) for k in range(P)]
         for p in self._pool:                              # forks of the warm server: they attach the buffers and start filling at once
             p.start()
         # Page-locking (hipHostRegister) allocates and pins every page: 0.3 s for the 1.4 GB of a batch-64 ring, which used to sit in
@@ -689,9 +726,10 @@ def kitti_loader(dump_dir, seq, H, W, lo, hi, batch_size, workers=4, prefetch=2,
     """Windows [lo, hi) of a sequence dump; window w has target frame w + 1.  ``decode_procs`` > 0 decodes the
     strips in that many processes (the ``workers`` threads then only wait for them and read the .npy files).
     ``depth``: batches are (img, flow, seg, depth) - the depth files are opened only then.  ``labels`` = "u8": uint8 label batches
-    (load_window).  ``flow`` = "f16": float16 flow batches (load_window)."""
+    (load_window).  ``flow`` = "f16": float16 flow batches (load_window).  ``depth`` = "f16" (instead of True): float16 depth batches."""
     check_label_format(labels)
     flow_fmt = check_flow_format(flow)
+    depth_mode(depth)
     dec = JpegDecodePool(decode_procs) if decode_procs > 0 else None
     return ThreadedWindowLoader(
         lambda w: load_window(dump_dir, seq, w + 1, H, W, depth, labels, flow_fmt), lo, hi, batch_size,
@@ -726,9 +764,12 @@ def write_synthetic_dump(dump_dir, seq, n_frames, H, W, seed=None, quality=None,
     ``scene_like_strip`` at quality 75 (a real dump's file size and decode cost).  ``labels`` = "u8": the ``-seglabel.npy`` files
     hold uint8 class ids, labels_to_u8 of the float maps.  ``flow`` = "f16": the ``-flownet2.npy`` files hold float16,
     flow_to_f16 of the float32 flow; "widened": float32 files of exactly those halves' values (flow_from_f16 of them) - the
-    float32 dump a binary16 run is bit-identical to.  Returns the number of windows written."""
+    float32 dump a binary16 run is bit-identical to.  ``depth`` = "f16" (instead of True): the depth files hold float16,
+    depth_to_f16 of the float32 planes; "widened": float32 files of exactly those halves' values.  Returns the number of windows
+    written."""
     check_label_format(labels)
     flow_fmt = flow if flow == "widened" else check_flow_format(flow)
+    depth_fmt = depth if depth == "widened" else (depth_mode(depth) or "f32")
     from PIL import Image
     from . import synth
     if images not in ("noise", "scene"):
@@ -746,6 +787,8 @@ def write_synthetic_dump(dump_dir, seq, n_frames, H, W, seed=None, quality=None,
         np.save(flo, flow[0] if flow_fmt == "f32" else half if flow_fmt == "f16" else half.astype(np.float32))
         np.save(sg, labels_to_u8(seg[0]) if labels == "u8" else seg[0])
         if depth:
-            np.save(depth_path(dump_dir, seq, w + 1),
-                    synth.make_depth(1, H, W, seed=synth.SEED if seed is None else seed, first_window=w)[0])
+            dep = synth.make_depth(1, H, W, seed=synth.SEED if seed is None else seed, first_window=w)[0]
+            if depth_fmt != "f32":
+                dep = depth_to_f16(dep) if depth_fmt == "f16" else depth_to_f16(dep).astype(np.float32)
+            np.save(depth_path(dump_dir, seq, w + 1), dep)
     return n_frames - 2

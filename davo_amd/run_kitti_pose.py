@@ -146,6 +146,12 @@ def build_parser():
                          "davo_set_flip; the training loader's --data_flip rule, davo_amd.flip_windows) - for a flip-trained checkpoint, or "
                          "to evaluate against kitti_benchmark's poses-flip/NN-flip.txt.  The loaders deliver the dump as it is; the file "
                          "names written are the same NN-pred_kitti_pose.txt")
+    ap.add_argument("--depth", choices=("f32", "f16"), default="f32",
+                    help="f32: the depth planes of a depth-source version cross the link as float32.  f16: as IEEE binary16 "
+                         "(include/davo_hip.h: davo_set_depth_format) - half the depth bytes in the loader's buffers, over the link and in "
+                         "the staging sets; float16 -monodepth2_depth.npy files are read as they are, float32 ones rounded by the "
+                         "loader's workers (davo_amd.depth_to_f16).  The written file is that of a float32 run on the rounded planes, "
+                         "to the byte.  A version that reads no depth ignores the option's files")
     return ap
 
 
@@ -200,6 +206,8 @@ def main(argv=None):
     load = weights = None
     from .version import parse_version
     needs_depth = parse_version(a.version).needs_depth           # a depth source: <dump>/SS/FFFFFF-monodepth2_depth.npy beside the other files
+    if needs_depth and a.depth == "f16":
+        needs_depth = "f16"                                       # the loaders' ``depth`` argument: float16 depth batches
     # this rank's shard of every sequence, in running order: the segments of the one loader
     segments = [(seq, ) + shard_of(n_frames) for seq, n_frames in sequences]
     if not synthetic:
@@ -254,6 +262,8 @@ def main(argv=None):
                 system.use_u8_labels()
             if a.flow == "f16":
                 system.use_f16_flow()
+            if a.depth == "f16":
+                system.use_f16_depth()
             system.setup_inference(H, W, "davo", a.seq_length, a.batch_size, **({"flip": True} if a.flip else {}))
             mark("gpu_context_created")
         finally:
@@ -371,6 +381,8 @@ def main(argv=None):
                 run_wide["labels"] = a.labels
             if a.flow != "f32":
                 run_wide["flow"] = a.flow
+            if a.depth != "f32":
+                run_wide["depth"] = a.depth
             if a.flip:
                 run_wide["flip"] = True
             if len(entries) == 1:          # one sequence: the report it has always had

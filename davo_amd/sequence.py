@@ -417,7 +417,7 @@ class kitti_window_loader:
 
     def __init__(self, concat_img_dir, seq, n_frames, H, W, workers=4, prefetch=2, alloc=None, decode_procs=0, procs=0,
                  pin=None, unpin=None, seg_planes=None, hold=0, depth=False, labels="f32", flow="f32"):
-        self.depth = depth        # a depth-source variant: batches are (img, flow, seg, depth)
+        self.depth = depth        # a depth-source variant: batches are (img, flow, seg, depth); "f16" (instead of True): float16 depth batches
         self.labels = labels      # "u8": every loader below yields uint8 label batches (davo_amd/loader.py)
         self.flow = flow          # "f16": every loader below yields float16 flow batches (davo_amd/loader.py)
         self.dir, self.seq, self.n_frames, self.H, self.W = concat_img_dir, seq, n_frames, H, W
@@ -509,6 +509,7 @@ def synthetic_window_loader(H, W, seed=None, depth=False, labels="f32", flow="f3
     def load(s, e):
         parts = synth.make_inputs(e - s, H, W, seed=synth.SEED if seed is None else seed, first_window=s, labels=labels, flow=flow)
         if depth:
-            parts += (synth.make_depth(e - s, H, W, seed=synth.SEED if seed is None else seed, first_window=s),)
+            parts += (synth.make_depth(e - s, H, W, seed=synth.SEED if seed is None else seed, first_window=s,
+                                       fmt="f16" if depth == "f16" else "f32"),)
         return parts
     return load

@@ -92,12 +92,15 @@ def make_inputs(B, H=128, W=416, seed=SEED, first_window=0, labels="f32", flow="
     return img, (flow_to_f16(flow) if flow_fmt == "f16" else flow), (labels_to_u8(seg) if labels == "u8" else seg)
 
 
-def make_depth(B, H=128, W=416, seed=SEED, first_window=0):
+def make_depth(B, H=128, W=416, seed=SEED, first_window=0, fmt="f32"):
     """Synthetic depth planes f32 ``[B,3,H,W,1]`` (file order src0, tgt, src1; reference ``davo.py:991-996``,
     ``test_kitti_pose.py:48``) in a monodepth2-like range: per plane a smooth field - a coarse 5x9 grid of depths, log-uniform
     in [1.5, 60], interpolated bilinearly, times a per-pixel ripple of +-5 % - so every value lies strictly inside (1, 80).
     Reproducible per window like ``make_inputs`` (streams of their own: the other planes do not move); integer arithmetic plus
-    IEEE add/mul only after the grid's exponentiation, which is float64 ``np.exp2`` of 45 values per plane."""
+    IEEE add/mul only after the grid's exponentiation, which is float64 ``np.exp2`` of 45 values per plane.  ``fmt`` = "f16": the
+    rounded twin of the float32 draw (``davo_amd.depth_to_f16``), float16 [B,3,H,W,1]."""
+    from .depth import check_depth_format, depth_to_f16
+    check_depth_format(fmt)
     depth = np.empty((B, 3, H, W, 1), np.float32)
     gh, gw = 5, 9
     ys = np.linspace(0.0, gh - 1.0, H)
@@ -116,7 +119,7 @@ def make_depth(B, H=128, W=416, seed=SEED, first_window=0):
             top = g[y0][:, x0] * (1.0 - fx) + g[y0][:, x0 + 1] * fx
             bot = g[y0 + 1][:, x0] * (1.0 - fx) + g[y0 + 1][:, x0 + 1] * fx
             depth[b, p, :, :, 0] = ((top * (1.0 - fy) + bot * fy) * (0.95 + 0.1 * rip[p])).astype(np.float32)
-    return depth
+    return depth_to_f16(depth) if fmt == "f16" else depth
 
 
 def make_frames(n_frames, H=128, W=416, seed=SEED, depth=False, labels="f32", flow="f32"):
@@ -125,7 +128,8 @@ def make_frames(n_frames, H=128, W=416, seed=SEED, depth=False, labels="f32", fl
     statistics of ``make_inputs``), seg [n,H,W,1] (8x8 blocks of train ids, 3 % ignore; uint8 with labels="u8"), depth f32
     [n,H,W,1] (the fields of ``make_depth``).  Every frame and every window draws from streams of its own, so no two frames agree
     in any plane, and consecutive windows share their frames by construction - which ``make_inputs``' windows, drawn one by one,
-    do not.  ``flow`` = "f16": flow2 is float16, ``davo_amd.flow_to_f16`` of the float32 draw."""
+    do not.  ``flow`` = "f16": flow2 is float16, ``davo_amd.flow_to_f16`` of the float32 draw.  ``depth`` = "f16" (instead of
+    True): the depth planes are float16, ``davo_amd.depth_to_f16`` of the float32 draw."""
     from .flow import check_flow_format, flow_to_f16
     from .labels import check_label_format, labels_to_u8
     check_label_format(labels)
@@ -148,7 +152,8 @@ def make_frames(n_frames, H=128, W=416, seed=SEED, depth=False, labels="f32", fl
         flow2[w] = (v * 15.384229 + 0.32140523).astype(np.float32).reshape(2, H, W, 2)
     out = (frames, flow_to_f16(flow2) if flow == "f16" else flow2, labels_to_u8(seg) if labels == "u8" else seg)
     if depth:
-        planes = make_depth((n_frames + 2) // 3, H, W, seed=seed, first_window=1000003)      # three planes per draw, all different
+        planes = make_depth((n_frames + 2) // 3, H, W, seed=seed, first_window=1000003,      # three planes per draw, all different
+                            fmt="f16" if depth == "f16" else "f32")
         out += (np.ascontiguousarray(planes.reshape(-1, H, W, 1)[:n_frames]),)
     return out
 

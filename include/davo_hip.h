@@ -127,7 +127,7 @@ int davo_set_posenn_topology(davo_ctx* ctx, int topology);
  * bytes per window instead of 12 H W: a 128x416 window is 1,437,696 B across the link instead of 1,757,184), the staging sets of
  * the streaming slots, the range guard's input snapshots and its re-issues.  Device label maps must be 16-byte aligned in either
  * format (every kernel then loads a 4-pixel unit of labels with one aligned load: H W is a multiple of 16).  A `-no_segmask'
- * context accepts the call and reads no label byte.  The depth planes stay float32.
+ * context accepts the call and reads no label byte.  The depth planes have a format of their own (davo_set_depth_format).
  * Like davo_set_posenn_se this is called right after davo_create: once any call has taken inputs (or a staging set or the
  * snapshot ring exists) it returns DAVO_ERR_INVALID, and so does any other value of fmt.  davo_get_label_format reads it back. */
 enum { DAVO_LABELS_F32 = 0, DAVO_LABELS_U8 = 1 };
@@ -161,6 +161,34 @@ enum { DAVO_FLOW_F32 = 0, DAVO_FLOW_F16 = 1 };
 int davo_set_flow_format(davo_ctx* ctx, int fmt);
 int davo_get_flow_format(const davo_ctx* ctx);
 
+/* Depth format.  The depth planes are a monocular network's estimate (monodepth2), good to a few percent; the reference's dump
+ * stores them as float32 [B,3,H,W,1], which is what every entry point that takes depth takes by default (DAVO_DEPTH_F32).
+ * davo_set_depth_format(ctx, DAVO_DEPTH_F16) makes the context take IEEE binary16 instead, in the same layout: a rounding error of
+ * at most 2^-12 relative; at the depth-split attention's 15 m default threshold a half is 2^-7 m wide.  davo_amd.depth_to_f16 is
+ * the one rule by which float32 depth becomes halves, and it is the flow's: round to nearest even, finite values beyond +-65504
+ * go to +-65504, NaN, infinities and signed zeros are kept.  The kernels read the halves natively: a 4-pixel unit is one aligned
+ * 8-byte load, widened value by value (exact for every binary16 value, subnormals, signed zeros and infinities included; NaN
+ * stays NaN - and a NaN depth is far, as in the float32 format), and every float32 expression, comparison and summation order
+ * behind the widening is the float32 format's.  So for any binary16 array h, a DAVO_DEPTH_F16 context on h and a DAVO_DEPTH_F32
+ * context on (float)h give the same bits in every tensor, in both precisions.
+ * On a DAVO_DEPTH_F16 context the `depth' / `d_depth' argument of EVERY entry point below points at halves (a C caller casts
+ * the pointer): davo_forward_depth, davo_forward_device_depth, davo_submit_depth, davo_calibrate_depth, the three `_frames' forms
+ * ([N+2,H,W,1]), davo_forward_features and davo_forward_heat; and everything the context sizes by a depth plane follows - the
+ * host entry points' copies and their sub-batching, the staging sets and frame buffers of the streaming slots, the frame
+ * layout's gather, the mirror of davo_set_flip, the range guard's input snapshots and its re-issues.  Device depth buffers are
+ * 16-byte aligned, as in the float32 format.  A context whose variant reads no depth accepts the call and still ignores every
+ * depth pointer.
+ * Bytes across the link per window at 128x416, att_source 11, both pairs, byte labels, binary16 flow: the window form sends
+ * 1,011,712 (strip, flow, label maps: above) + 319,488 (three binary16 depth planes; 638,976 as float32) = 1,331,200 instead of
+ * 1,650,688; the frame layout, long batch, 638,976 + 106,496 = 745,472 instead of 851,968.
+ * The ordering rule is the flow format's: called right after davo_create; once any call has taken inputs (or a staging set, a
+ * frame buffer or the snapshot ring exists) it returns DAVO_ERR_INVALID, and so does any other value of fmt.  It is independent
+ * of davo_set_label_format, davo_set_flow_format, davo_set_pairs and davo_set_flip, in any order.  davo_get_depth_format reads
+ * it back. */
+enum { DAVO_DEPTH_F32 = 0, DAVO_DEPTH_F16 = 1 };
+int davo_set_depth_format(davo_ctx* ctx, int fmt);
+int davo_get_depth_format(const davo_ctx* ctx);
+
 /* Replaces tf.train.Saver(tf.trainable_variables()).restore(sess, ckpt)
  * (test_kitti_pose.py:129-131), one tensor at a time, keyed by the TF variable name
  * (e.g. "pose_exp_net/cnv1/weights", "pose_exp_net/pose/rotation/cnv6/biases",
@@ -187,7 +215,9 @@ int davo_forward(davo_ctx* ctx, int B, const uint8_t* img, const float* flow, co
                  float* pose_out);
 
 /* The depth sources (att_source 11, 12) and the depth-split flow attention (13) read a fourth input (davo.py:960, 991-996; test_kitti_pose.py:48, 91):
- *   depth f32  [B,3,H,W,1] (file order src0,tgt,src1 like the label maps; <dump>/SS/FFFFFF-monodepth2_depth.npy),
+ *   depth f32  [B,3,H,W,1] (file order src0,tgt,src1 like the label maps; <dump>/SS/FFFFFF-monodepth2_depth.npy); binary16
+ *              [B,3,H,W,1] behind the same pointer type on a DAVO_DEPTH_F16 context (davo_set_depth_format) - here and for
+ *              every `depth' / `d_depth' argument below,
  * 16-byte aligned where it is a device pointer.  Each entry point that takes inputs has a `_depth' form with that argument
  * behind `seg'; everything said about the three-input form holds for it, the depth planes included: davo_forward_depth copies
  * them with each sub-batch, davo_submit_depth stages all three planes per slot (13 never reads the target's plane), the f16x3 range recovery keeps and re-issues them
@@ -286,7 +316,7 @@ int davo_get_pairs(const davo_ctx* ctx);
  *   flow2    f32   [N,2,H,W,2]   (binary16 on a DAVO_FLOW_F16 context) planes (tgt->src0, tgt->src1) of window n: planes 0, 1 of davo_forward's [B,4,H,W,2], the two the
  *                                path reads
  *   seg            [N+2,H,W,1]   float32, or bytes on a DAVO_LABELS_U8 context (davo_set_label_format)
- *   depth    f32   [N+2,H,W,1]   in the signature: NULL (or anything, ignored) where the variant reads no depth; where it does
+ *   depth    f32   [N+2,H,W,1]   (binary16 on a DAVO_DEPTH_F16 context) in the signature: NULL (or anything, ignored) where the variant reads no depth; where it does
  *                                (att_source 11, 12, 13) a NULL pointer returns DAVO_ERR_INVALID with a message
  *   pose_out f32   [N,2,6]       as davo_forward's
  * Device pointers are 16-byte aligned (DAVO_ERR_INVALID otherwise).
@@ -323,6 +353,8 @@ int davo_get_pairs(const davo_ctx* ctx);
  * pixel and flow plane in *link_bytes; 638,976 per window for the line above with byte labels and binary16 flow);
  * davo_frames_plan means flow_fmt = DAVO_FLOW_F32 and takes att_source 0..13, the range it was published with; the pooled
  * flow-attention sources (14..17), which read what att_source 1 reads, are planned by davo_frames_plan_fmt.
+ * davo_frames_plan_fmt2 is davo_frames_plan_fmt with the depth format as an argument too (DAVO_DEPTH_F32 or DAVO_DEPTH_F16: 4 or
+ * 2 bytes per pixel and depth plane in *link_bytes); davo_frames_plan_fmt means depth_fmt = DAVO_DEPTH_F32.
  * There are no `_frames' forms of davo_calibrate, davo_forward_features and davo_forward_heat. */
 int davo_forward_frames(davo_ctx* ctx, int N, const uint8_t* frames, const float* flow2, const float* seg,
                         const float* depth, float* pose_out);
@@ -332,6 +364,8 @@ int davo_forward_device_frames(davo_ctx* ctx, int N, const void* d_frames, const
                                const void* d_depth, void* d_pose, float* elapsed_ms);
 int davo_frames_plan(int H, int W, int N, int pairs, int att_source, int label_fmt, int* ranges, long long* link_bytes);
 int davo_frames_plan_fmt(int H, int W, int N, int pairs, int att_source, int label_fmt, int flow_fmt, int* ranges, long long* link_bytes);
+int davo_frames_plan_fmt2(int H, int W, int N, int pairs, int att_source, int label_fmt, int flow_fmt, int depth_fmt, int* ranges,
+                          long long* link_bytes);
 
 /* Mirrored inputs.  The reference treats left-right mirrored sequences as data of their own: it trains with --data_flip
  * (data_loader.py:77-84, 142-169), its feature-map driver writes `featuremaps-flip', and it ships mirrored ground truth

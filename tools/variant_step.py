@@ -23,6 +23,12 @@ mirror costs on resident inputs in either layout ("Mirrored
 
     python tools/variant_step.py --batch 32 --rounds 5 --stages 20 --flip off on [--layout frames] <flagship>
 
+`--depth ARM [ARM ...]` (f32 | f16; include/davo_hip.h: davo_set_depth_format) multiplies the arms by the depth format: the f16
+arm's engine takes davo_amd.depth_to_f16 of the same planes.  Both formats of a depth source in one process, alternating
+("Depth planes as binary16"):
+
+    python tools/variant_step.py --batch 32 --rounds 6 --stages 20 <a depth-source version> --depth f32 f16
+
 Under `rocprofv3 --kernel-trace --stats -- python3 tools/variant_step.py ...` it gives the per-kernel table of a variant."""
 import argparse
 import json
@@ -34,7 +40,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 import numpy as np  # noqa: E402
 
-from davo_amd import Engine, synth, parse_version  # noqa: E402
+from davo_amd import Engine, synth, parse_version, depth_to_f16  # noqa: E402
 
 
 def main():
@@ -55,6 +61,8 @@ def main():
                     help="arms of the mirror setting (davo_set_flip): off | on, e.g. --flip off on; every pair arm runs once per flip arm")
     ap.add_argument("--layout", choices=["windows", "frames"], default="windows",
                     help="windows: davo_forward_device; frames: davo_forward_device_frames (the timed step includes the gather)")
+    ap.add_argument("--depth", nargs="+", default=None, choices=["f32", "f16"], metavar="ARM",
+                    help="arms of the depth format (davo_set_depth_format): f32 | f16, e.g. --depth f32 f16; every other arm runs once per depth arm")
     a = ap.parse_args()
     H, W = a.height, a.width
     arms = []
@@ -62,16 +70,16 @@ def main():
         sel, _, b = arm.partition("@")
         if sel not in Engine.PAIRS or (b and not b.isdigit()):
             ap.error("--pairs: `%s' is not both | src0 | src1, optionally @batch" % arm)
-        arms += [(sel, int(b) if b else a.batch, flip == "on") for flip in (a.flip or ["off"])]
-    Bmax = max(b for _, b, _ in arms)
+        arms += [(sel, int(b) if b else a.batch, flip == "on", dfmt) for flip in (a.flip or ["off"]) for dfmt in (a.depth or ["f32"])]
+    Bmax = max(arm[1] for arm in arms)
     frames = synth.make_frames(Bmax + 2, H, W, depth=True) if a.layout == "frames" else None
     img, flow, seg = synth.make_inputs(Bmax, H, W)
     depth = synth.make_depth(Bmax, H, W)           # uploaded for the depth sources only
     runs = []
     for v in a.versions:
         cfg = parse_version(v)
-        for sel, B, flip in arms:
-            e = Engine(cfg, H, W, B)
+        for sel, B, flip, dfmt in arms:
+            e = Engine(cfg, H, W, B, depth=dfmt)
             e.load_weights(synth.make_weights(cfg))
             e.set_precision(a.precision)
             e.set_pairs(sel)
@@ -83,6 +91,7 @@ def main():
                 parts, dep = (img[:B], flow[:B], seg[:B]), depth[:B]
                 e.step = e.forward_device
             bufs = [e.alloc(x.nbytes).upload(x) for x in parts] + [e.alloc(B * 12 * 4)]
+            dep = depth_to_f16(dep) if dfmt == "f16" else dep
             kw = {"depth": e.alloc(dep.nbytes).upload(dep)} if cfg.needs_depth else {}
             for _ in range(a.warmup):
                 e.step(B, *bufs, **kw)
@@ -120,6 +129,8 @@ def main():
                         stage_us_per_round=[{k: round(x, 2) for k, x in r.items()} for r in st])
         if a.pairs:
             line.update(pairs=sel, plan=[e.last_plan(l) for l in range(7)])
+        if a.depth:
+            line.update(depth=e.depth)
         if a.flip or a.layout != "windows":
             line.update(flip=e.flip, layout=a.layout)
         print(json.dumps(line), flush=True)
