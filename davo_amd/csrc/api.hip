@@ -206,56 +206,30 @@ int davo_set_posenn_topology(davo_ctx* c, int topology) {
     return DAVO_OK;
 }
 
-int davo_set_label_format(davo_ctx* c, int fmt) {
+// The three format setters' one body.  kind: "label" | "flow" | "depth" (the setter is davo_set_<kind>_format); field: its member of
+// the context's InputFormat; name0 / name1: the header's names of the values 0 and 1.
+static int set_input_format(davo_ctx* c, const char* kind, int InputFormat::*field, int fmt, const char* name0, const char* name1) {
     if (!c) return DAVO_ERR_INVALID;
-    if (fmt != DAVO_LABELS_F32 && fmt != DAVO_LABELS_U8)
-        return fail(c, DAVO_ERR_INVALID, "label format must be DAVO_LABELS_F32 (0) or DAVO_LABELS_U8 (1), got %d", fmt);
+    InputFormat next = c->fmt;
+    next.*field = fmt;
+    if (!valid(next)) return fail(c, DAVO_ERR_INVALID, "%s format must be %s (0) or %s (1), got %d", kind, name0, name1, fmt);
     // everything sized by plane_bytes() follows the format: it is fixed once inputs were taken or a set of them was allocated
     bool sets = static_cast<bool>(c->host) || static_cast<bool>(c->snaps);
     for (const InputSet& s : c->stream_sets) sets = sets || s.built();
     for (const FrameSet& s : c->frame_sets) sets = sets || s.built();
     if (c->inputs_seen || c->forward_seen || sets)
-        return fail(c, DAVO_ERR_INVALID, "davo_set_label_format must be called before the first call that takes inputs "
-                    "(the staging sets, the range guard's snapshots and every copy are sized by it)");
-    c->label_fmt = fmt;
+        return fail(c, DAVO_ERR_INVALID, "davo_set_%s_format must be called before the first call that takes inputs "
+                    "(the staging sets, the range guard's snapshots and every copy are sized by it)", kind);
+    c->fmt = next;
     return DAVO_OK;
 }
 
-int davo_get_label_format(const davo_ctx* c) { return c ? c->label_fmt : DAVO_ERR_INVALID; }
-
-int davo_set_flow_format(davo_ctx* c, int fmt) {
-    if (!c) return DAVO_ERR_INVALID;
-    if (fmt != DAVO_FLOW_F32 && fmt != DAVO_FLOW_F16)
-        return fail(c, DAVO_ERR_INVALID, "flow format must be DAVO_FLOW_F32 (0) or DAVO_FLOW_F16 (1), got %d", fmt);
-    // the label format's rule: everything sized by plane_bytes() follows the format
-    bool sets = static_cast<bool>(c->host) || static_cast<bool>(c->snaps);
-    for (const InputSet& s : c->stream_sets) sets = sets || s.built();
-    for (const FrameSet& s : c->frame_sets) sets = sets || s.built();
-    if (c->inputs_seen || c->forward_seen || sets)
-        return fail(c, DAVO_ERR_INVALID, "davo_set_flow_format must be called before the first call that takes inputs "
-                    "(the staging sets, the range guard's snapshots and every copy are sized by it)");
-    c->flow_fmt = fmt;
-    return DAVO_OK;
-}
-
-int davo_get_flow_format(const davo_ctx* c) { return c ? c->flow_fmt : DAVO_ERR_INVALID; }
-
-int davo_set_depth_format(davo_ctx* c, int fmt) {
-    if (!c) return DAVO_ERR_INVALID;
-    if (fmt != DAVO_DEPTH_F32 && fmt != DAVO_DEPTH_F16)
-        return fail(c, DAVO_ERR_INVALID, "depth format must be DAVO_DEPTH_F32 (0) or DAVO_DEPTH_F16 (1), got %d", fmt);
-    // the label format's rule: everything sized by plane_bytes() follows the format
-    bool sets = static_cast<bool>(c->host) || static_cast<bool>(c->snaps);
-    for (const InputSet& s : c->stream_sets) sets = sets || s.built();
-    for (const FrameSet& s : c->frame_sets) sets = sets || s.built();
-    if (c->inputs_seen || c->forward_seen || sets)
-        return fail(c, DAVO_ERR_INVALID, "davo_set_depth_format must be called before the first call that takes inputs "
-                    "(the staging sets, the range guard's snapshots and every copy are sized by it)");
-    c->depth_fmt = fmt;
-    return DAVO_OK;
-}
-
-int davo_get_depth_format(const davo_ctx* c) { return c ? c->depth_fmt : DAVO_ERR_INVALID; }
+int davo_set_label_format(davo_ctx* c, int fmt) { return set_input_format(c, "label", &InputFormat::label, fmt, "DAVO_LABELS_F32", "DAVO_LABELS_U8"); }
+int davo_set_flow_format(davo_ctx* c, int fmt) { return set_input_format(c, "flow", &InputFormat::flow, fmt, "DAVO_FLOW_F32", "DAVO_FLOW_F16"); }
+int davo_set_depth_format(davo_ctx* c, int fmt) { return set_input_format(c, "depth", &InputFormat::depth, fmt, "DAVO_DEPTH_F32", "DAVO_DEPTH_F16"); }
+int davo_get_label_format(const davo_ctx* c) { return c ? c->fmt.label : DAVO_ERR_INVALID; }
+int davo_get_flow_format(const davo_ctx* c) { return c ? c->fmt.flow : DAVO_ERR_INVALID; }
+int davo_get_depth_format(const davo_ctx* c) { return c ? c->fmt.depth : DAVO_ERR_INVALID; }
 
 int davo_load_weight(davo_ctx* c, const char* tf_name, const float* data, const int64_t* shape, int ndim) {
     // ndim 0: a scalar variable (the depth threshold); shape may then be null

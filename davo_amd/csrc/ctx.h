@@ -237,9 +237,7 @@ struct davo_ctx {
                                                // channels, B images a batch), pred six columns wide, the unfused two-pass pose head (forward.hip)
     bool opt_patch_cnv1_t = true;              // three-frame PoseNN, f16x3: "patch_cnv1_t" - cnv1 from an LDS-staged 16-channel patch (conv_patch_cnv1t_h3) instead of the implicit GEMM at cin = 16
     bool forward_seen = false;                 // a forward has been issued (davo_set_posenn_se and davo_set_posenn_topology are refused from then on)
-    int label_fmt = davo::LABELS_F32;          // davo_set_label_format: what every `seg' argument points at, and what plane_bytes().seg sizes
-    int flow_fmt = davo::FLOW_F32;             // davo_set_flow_format: what every `flow' argument points at, and what plane_bytes().flow sizes
-    int depth_fmt = davo::DEPTH_F32;           // davo_set_depth_format: what every `depth' argument points at, and what plane_bytes().depth sizes
+    davo::InputFormat fmt;                     // davo_set_{label,flow,depth}_format: what every `seg' / `flow' / `depth' argument points at, and what plane_bytes() sizes
     bool inputs_seen = false;                  // an entry point has taken inputs (davo_set_label_format, davo_set_flow_format and davo_set_depth_format are refused from then on)
     int impl = 0;
     int precision = 1;                         // 0 = FP32 MFMA (bit-exact fmaf chains), 1 = f16x3 split (default)
@@ -345,8 +343,8 @@ inline PlaneBytes plane_bytes(const davo_ctx* c) {
     // seg: [3,H,W,1] in the context's label format, float32 or bytes; depth: [3,H,W,1] in the context's depth format, float32 or binary16 (davo.py:991-996).  H W is a
     // multiple of 16, so every window of every plane starts 16-byte aligned where the block does, in either format.  flow: [4,H,W,2] in
     // the context's flow format, float32 or binary16: a plane of 2 H W halves is still a multiple of 64 bytes
-    return PlaneBytes{HW * 9, HW * 8 * (c->flow_fmt == FLOW_F16 ? 2 : sizeof(float)), HW * 3 * (c->label_fmt == LABELS_U8 ? 1 : sizeof(float)),
-                      HW * 3 * (c->depth_fmt == DEPTH_F16 ? 2 : sizeof(float))};
+    const ElemBytes e = element_bytes(c->fmt);
+    return PlaneBytes{HW * 9, HW * 8 * e.flow, HW * 3 * e.label, HW * 3 * e.depth};
 }
 inline bool needs_depth(const davo_ctx* c) { return att_reads_depth(c->v.att_source); }
 inline bool triplet(const davo_ctx* c) { return c->topology == DAVO_POSENN_TRIPLET; }

@@ -33,7 +33,7 @@ int davo::check_batch(davo_ctx* c, Batch* b, int B, bool out_given, int hold) {
     if (B < 1 || B > c->max_batch) return fail(c, DAVO_ERR_INVALID, "batch %d outside [1,%d]", B, c->max_batch);
     if (hold < 0) return fail(c, DAVO_ERR_INVALID, "hold must be >= 0");
     // a binary16 flow is read in 16-byte units of four pixels (input_decode.h: flow_fetch4): on the device its base is 16-byte aligned
-    if (c->flow_fmt == FLOW_F16 && b->on_device && b->layout == Layout::Windows && ((uintptr_t)b->win.flow & 15))
+    if (c->fmt.flow == FLOW_F16 && b->on_device && b->layout == Layout::Windows && ((uintptr_t)b->win.flow & 15))
         return fail(c, DAVO_ERR_INVALID, "%s: a binary16 device flow buffer (davo_set_flow_format) must be 16-byte aligned", b->fn);
     // flip on: window_mirror reads the caller's device buffers in 16-byte units
     if (c->flip && b->on_device && b->layout == Layout::Windows && (((uintptr_t)b->win.img | (uintptr_t)b->win.flow | (uintptr_t)b->win.seg | (uintptr_t)b->win.depth) & 15))
@@ -167,8 +167,8 @@ int gather_windows(davo_ctx* c, const InputSet& set, const FrameInputs& fr, int 
                        c->H, c->W, sel, p.seg_tgt, p.depth_tgt};
     ProfScope ps(c, s, "window_gather");
     // (the mirrored form leaves out the target's label map where the variant does not attend it: no kernel reads it)
-    if (flip) HIP_TRY(c, launch_window_mirror(a, nb, true, c->label_fmt, c->flow_fmt, c->depth_fmt, s));
-    else HIP_TRY(c, launch_window_gather(a, nb, c->label_fmt, c->flow_fmt, c->depth_fmt, s));
+    if (flip) HIP_TRY(c, launch_window_mirror(a, nb, true, c->fmt, s));
+    else HIP_TRY(c, launch_window_gather(a, nb, c->fmt, s));
     return DAVO_OK;
 }
 
@@ -182,7 +182,7 @@ int mirror_windows(davo_ctx* c, const InputSet& set, const Inputs* from, int b0,
     const GatherArgs a{rd(src.img), rd(src.seg), dst.depth ? rd(src.depth) : nullptr, rd(src.flow), wr(dst.img), wr(dst.seg), wr(dst.depth), wr(dst.flow),
                        c->H, c->W, sel, seg_tgt, att_desc_depth(c->v.att_source)};
     ProfScope ps(c, s, "window_mirror");
-    HIP_TRY(c, launch_window_mirror(a, nb, false, c->label_fmt, c->flow_fmt, c->depth_fmt, s));
+    HIP_TRY(c, launch_window_mirror(a, nb, false, c->fmt, s));
     return DAVO_OK;
 }
 
@@ -365,16 +365,15 @@ int davo_forward_device_frames(davo_ctx* c, int N, const void* d_frames, const v
 }
 
 int davo_frames_plan_fmt2(int H, int W, int N, int pairs, int att_source, int label_fmt, int flow_fmt, int depth_fmt, int* ranges, long long* link_bytes) {
-    if (H < 1 || W < 1 || N < 1 || (pairs != PAIRS_SRC0 && pairs != PAIRS_SRC1 && pairs != PAIRS_BOTH) || att_source < 0 || att_source > ATT_MAX ||
-        (label_fmt != LABELS_F32 && label_fmt != LABELS_U8) || (flow_fmt != FLOW_F32 && flow_fmt != FLOW_F16) ||
-        (depth_fmt != DEPTH_F32 && depth_fmt != DEPTH_F16))
+    const InputFormat fmt{label_fmt, flow_fmt, depth_fmt};
+    if (H < 1 || W < 1 || N < 1 || (pairs != PAIRS_SRC0 && pairs != PAIRS_SRC1 && pairs != PAIRS_BOTH) || att_source < 0 || att_source > ATT_MAX || !valid(fmt))
         return DAVO_ERR_INVALID;
     const FramePlan p = frame_plan(N, pairs, att_source);
     if (ranges) {
         const int r[8] = {p.img[0], p.img[1], p.seg[0], p.seg[1], p.depth[0], p.depth[1], p.flow[0], p.flow[1]};
         memcpy(ranges, r, sizeof r);
     }
-    if (link_bytes) *link_bytes = frame_plan_bytes(p, N, H, W, label_fmt == LABELS_U8 ? 1 : 4, flow_fmt == FLOW_F16 ? 2 : 4, depth_fmt == DEPTH_F16 ? 2 : 4);
+    if (link_bytes) *link_bytes = frame_plan_bytes(p, N, H, W, element_bytes(fmt));
     return DAVO_OK;
 }
 

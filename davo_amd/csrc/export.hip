@@ -60,9 +60,9 @@ int export_features(davo_ctx* c, const Inputs& in, int w0, int nw, int b0, int B
         float* const w_trans = out.feat_trans ? d_fx + l.trans : nullptr;
         if (w_att19 || w_att || w_masked || w_image) {
             ProfScope ps(c, s, "feature_maps");
-            HIP_TRY(c, launch_feature_maps(static_cast<const uint8_t*>(win.img), win.seg, c->label_fmt,
+            HIP_TRY(c, launch_feature_maps(static_cast<const uint8_t*>(win.img), win.seg, c->fmt,
                                            ws.d_tab.get() + (size_t)(w0 + p0) * 3 * NCLS, c->v, np, c->H, c->W, w_att19, w_att, w_masked, w_image, s,
-                                           win.depth, ws.d_tab_far ? ws.d_tab_far.get() + (size_t)(w0 + p0) * 3 * NCLS : nullptr, c->depth_thr, c->depth_fmt));
+                                           win.depth, ws.d_tab_far ? ws.d_tab_far.get() + (size_t)(w0 + p0) * 3 * NCLS : nullptr, c->depth_thr));
         }
         if (w_rot || w_trans) {
             ProfScope ps(c, s, "feature_resize_cnv6");

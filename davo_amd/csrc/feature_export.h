@@ -38,7 +38,7 @@ struct FeatureMapsOut {          // device pointers of one piece of nw windows; 
 // DSPLIT (att_source 13): a source frame's map is mask_pack_depthsplit's select - the frame's own depth plane against the threshold
 // chooses the near table `tab' or the far table `ds.tab_far' per pixel (input_decode.h); depth points at the piece's first window
 // like img and seg.  No single 19-row table was applied there (the reference sets no att_19s, davo.py:1470): o.att_19 is null.
-// LT: the label format, float32 or bytes; DT (DSPLIT only): the depth format, float32 or binary16, read through depth_fetch4
+// LT: the label format, float32 or bytes; DT (DSPLIT only): the depth format, float32 or binary16, read through widen_fetch4
 // (input_decode.h).
 template <bool DSPLIT, typename LT, typename DT>
 __device__ __forceinline__ void feature_maps_body(const uint8_t* __restrict__ img, const LT* __restrict__ seg,
@@ -67,7 +67,7 @@ __device__ __forceinline__ void feature_maps_body(const uint8_t* __restrict__ im
             const LabelIds4 sg = label_fetch4(seg + ((size_t)b * 3 + slot) * HW, pix);
             const float* tab_f = tab + ((size_t)b * 3 + frame) * NCLS;
             if (DSPLIT) {
-                const float4 dp = depth_fetch4(ds.depth + ((size_t)b * 3 + slot) * HW + pix);
+                const float4 dp = widen_fetch4(ds.depth + ((size_t)b * 3 + slot) * HW + pix);
                 const float* far_f = ds.tab_far + ((size_t)b * 3 + frame) * NCLS;
                 a[0] = att_lookup_split(tab_f, far_f, ds.thr, dp.x, sg.id[0]); a[1] = att_lookup_split(tab_f, far_f, ds.thr, dp.y, sg.id[1]);
                 a[2] = att_lookup_split(tab_f, far_f, ds.thr, dp.z, sg.id[2]); a[3] = att_lookup_split(tab_f, far_f, ds.thr, dp.w, sg.id[3]);

@@ -352,7 +352,7 @@ int run_patch_layer(davo_ctx* c, const Run& run, int li, bool f32, const void* x
     c->last_plan[li][0] = ((NB * p.Ho * p.Wo + 127) / 128) * 1000 + t.plan_id; c->last_plan[li][1] = 0; c->last_split[li] = 1;
     const int nblk = p.ntiles < t.per_cu * c->ncu ? p.ntiles : t.per_cu * c->ncu;
     ProfScope ps(c, run.stream, L.label);
-    HIP_TRY(c, launch_patch_layer(li, f32, fused, p, nblk, run.stream, c->label_fmt, c->flow_fmt));
+    HIP_TRY(c, launch_patch_layer(li, f32, fused, p, nblk, run.stream, c->fmt));
     return DAVO_OK;
 }
 
@@ -470,9 +470,8 @@ int forward_device(davo_ctx* c, const Run& run, int B, const Inputs& in, void* d
     for (int i = 0; i < 7; ++i) a[i] = ws.d_act[i].get();
     hipStream_t s = run.stream;
     const uint8_t* const d_img = static_cast<const uint8_t*>(in.img);
-    const void* const d_flow = in.flow;                        // float32 or binary16: c->flow_fmt
-    const int ffmt = c->flow_fmt;
-    const void* const d_seg = in.seg;                          // float32 or bytes: c->label_fmt
+    const void* const d_flow = in.flow;                        // float32 or binary16: c->fmt.flow
+    const void* const d_seg = in.seg;                          // float32 or bytes: c->fmt.label
     auto wdev = [&](const char* n) -> const float* {
         auto it = c->weights.find(n);
         return it == c->weights.end() ? nullptr : it->second.dev.get();
@@ -504,35 +503,35 @@ int forward_device(davo_ctx* c, const Run& run, int B, const Inputs& in, void* d
         if (!ws.d_desc || !se_w1 || !se_b1 || !se_w2 || !se_b2) return fail(c, DAVO_ERR_INVALID, "internal: the pooled attention's descriptor buffer or dense tensors are missing");
         {
             ProfScope ps(c, run.stream, "se_pool_squeeze");
-            HIP_TRY(c, launch_se_pool_squeeze(d_flow, ffmt, B, H, W, v, c->pool, d_partial, sel, s));
+            HIP_TRY(c, launch_se_pool_squeeze(d_flow, c->fmt, B, H, W, v, c->pool, d_partial, sel, s));
         }
         ProfScope ps(c, run.stream, "se_pool_excite");
         HIP_TRY(c, launch_se_pool_excite(d_partial, B, v, c->pool, se_w1, se_b1, se_w2, se_b2, d_tab, ws.d_desc.get(), range_reset, sel, s));
     } else if (att_desc_depth(v.att_source)) {
         // depth sources: one float32 sum per depth plane and chunk, then (or, folded, in the same launch) the excitation
         ProfScope ps(c, run.stream, "se_depth_squeeze");
-        HIP_TRY(c, launch_se_depth_squeeze(fold_excite, in.depth, c->depth_fmt, B, HW, v, reinterpret_cast<unsigned*>(d_partial),
+        HIP_TRY(c, launch_se_depth_squeeze(fold_excite, in.depth, c->fmt, B, HW, v, reinterpret_cast<unsigned*>(d_partial),
                                            d_counters + 1, se_w1, se_b1, se_w2, se_b2, d_tab, range_reset, sel, s));
     } else if (class_table) {
         // segmentation / rgb / seg+flow sources: per-frame histogram, byte or flow sums, then (or, folded, in the same launch) the
         // excitation
         ProfScope ps(c, run.stream, "se_class_squeeze");
-        HIP_TRY(c, launch_se_class_squeeze(fold_excite, d_img, d_flow, ffmt, d_seg, c->label_fmt, B, H, W, v, reinterpret_cast<unsigned*>(d_partial),
+        HIP_TRY(c, launch_se_class_squeeze(fold_excite, d_img, d_flow, d_seg, c->fmt, B, H, W, v, reinterpret_cast<unsigned*>(d_partial),
                                            d_counters + 1, se_w1, se_b1, se_w2, se_b2, d_tab, range_reset, sel, s));
     } else if (fold_excite && depth_split) {
         // the flagship's squeeze; the triplet's last workgroup evaluates the near tables and the far tables from the same sums
         ProfScope ps(c, run.stream, "se_squeeze_partial");
         const float* near_w[4] = {se_w1, se_b1, se_w2, se_b2};
-        HIP_TRY(c, launch_se_squeeze_excite_split(d_flow, ffmt, B, HW, v, d_partial, d_counters + 1, near_w, far_w, d_tab, d_tab_far, range_reset, sel, s));
+        HIP_TRY(c, launch_se_squeeze_excite_split(d_flow, c->fmt, B, HW, v, d_partial, d_counters + 1, near_w, far_w, d_tab, d_tab_far, range_reset, sel, s));
     } else if (fold_excite) {
         // squeeze + excitation in one launch: the workgroup that delivers a triplet's last partial sum evaluates its tables
         ProfScope ps(c, run.stream, "se_squeeze_partial");
-        HIP_TRY(c, launch_se_squeeze_excite(d_flow, ffmt, B, HW, v, d_partial, d_counters + 1,
+        HIP_TRY(c, launch_se_squeeze_excite(d_flow, c->fmt, B, HW, v, d_partial, d_counters + 1,
                                             se_w1, se_b1, se_w2, se_b2,
                                             wdev("pose_exp_net/pose_exp_net/seg_channel_weight/weight"), d_tab, range_reset, sel, s));
     } else if (att_flow_squeeze(v.att_source)) {
         ProfScope ps(c, run.stream, "se_squeeze_partial");
-        HIP_TRY(c, launch_se_squeeze(d_flow, ffmt, B, HW, v, d_partial, sel, s));
+        HIP_TRY(c, launch_se_squeeze(d_flow, c->fmt, B, HW, v, d_partial, sel, s));
     }
     if (!fold_excite && !pooled) {
         ProfScope ps(c, run.stream, "se_excite");
@@ -559,11 +558,11 @@ int forward_device(davo_ctx* c, const Run& run, int B, const Inputs& in, void* d
     c->packed_ld = tri ? 16 : (run.impl == 0 ? 8 : 10);
     if (tri) {
         ProfScope ps(c, run.stream, "mask_pack");
-        HIP_TRY(c, launch_mask_pack3(h3, d_img, d_flow, ffmt, d_seg, c->label_fmt, d_tab, v, B, H, W, d_packed, s));
+        HIP_TRY(c, launch_mask_pack3(h3, d_img, d_flow, d_seg, c->fmt, d_tab, v, B, H, W, d_packed, s));
     } else if (!fused) {
         ProfScope ps(c, run.stream, "mask_pack");
-        HIP_TRY(c, launch_mask_pack(h3 ? 16 : (run.impl == 0 ? 8 : 10), d_img, d_flow, ffmt, d_seg, c->label_fmt, d_tab, v, B, H, W, d_packed, sel, s,
-                                    in.depth, d_tab_far, c->depth_thr, c->depth_fmt));
+        HIP_TRY(c, launch_mask_pack(h3 ? 16 : (run.impl == 0 ? 8 : 10), d_img, d_flow, d_seg, c->fmt, d_tab, v, B, H, W, d_packed, sel, s,
+                                    in.depth, d_tab_far, c->depth_thr));
     }
     const int c6 = v.cnv6_out;
     int rc;

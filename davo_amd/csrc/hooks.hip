@@ -131,8 +131,9 @@ int davo_debug_read(davo_ctx* c, const char* tensor, float* host_out, size_t n_f
     }
     else if (t == "packed") {
         if (!c->packed_valid) {          // fused path: materialise the packed tensor on demand from the last inputs
-            HIP_TRY(c, launch_mask_pack(16, static_cast<const uint8_t*>(c->last_in.img), c->last_in.flow, c->flow_fmt,
-                                        c->last_in.seg, c->label_fmt, ws.d_tab.get(), c->v, c->last_B, c->H, c->W, ws.d_packed.get(), c->last_pairs, last_stream(c)));
+            HIP_TRY(c, launch_mask_pack(16, static_cast<const uint8_t*>(c->last_in.img), c->last_in.flow, c->last_in.seg,
+                                        c->fmt, ws.d_tab.get(), c->v, c->last_B, c->H, c->W, ws.d_packed.get(), c->last_pairs, last_stream(c),
+                                        nullptr, nullptr, 0.f));      // (the depth-split variant never takes the fused path)
             c->packed_valid = true;
         }
         src = ws.d_packed.get(); n = NB * c->H * c->W * c->packed_ld;

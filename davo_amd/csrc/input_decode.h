@@ -37,68 +37,52 @@ __device__ __forceinline__ LabelIds4 label_fetch4(const uint8_t* __restrict__ pl
     return LabelIds4{{label_id((uint8_t)q), label_id((uint8_t)(q >> 8)), label_id((uint8_t)(q >> 16)), label_id((uint8_t)(q >> 24))}};
 }
 
-// The optical flow comes in one of the two formats of davo_set_flow_format (include/davo_hip.h): float32, or IEEE binary16 in the
-// same layout ([B][4][H][W][2], (fx, fy) per pixel).  FT is the element, float or flow_f16.  A reader takes its pixels through one
-// of the fetches below and computes in float32 from there on, so both formats run the same expressions in the same order: a
-// binary16 flow h gives the bits of the float32 flow (float)h.  The widening is v_cvt_f32_f16 per value (two per instruction
-// where the compiler pairs them): exact for every binary16 value - subnormals too (the code objects run with f16/f64 denormals
-// on, the amdgcn default; a half subnormal is a normal float32, so the float32 flush mode does not enter), signed zeros and
-// infinities; a NaN stays a NaN (a signalling one comes out quiet, as from any float conversion).
+// The optical flow and the depth planes each come in one of two formats (davo_set_flow_format, davo_set_depth_format;
+// include/davo_hip.h): float32, or IEEE binary16 in the same layout - flow [B][4][H][W][2], (fx, fy) per pixel; depth [B][3 file
+// planes: src0, tgt, src1][H][W], one value per pixel.  FT / DT is the element, float or in_f16.  A reader takes its values
+// through one of the fetches below and computes in float32 from there on, so both formats run the same expressions in the same
+// order: a binary16 input h gives the bits of the float32 input (float)h.  The widening is v_cvt_f32_f16 per value (two per
+// instruction where the compiler pairs them): exact for every binary16 value - subnormals too (the code objects run with f16/f64
+// denormals on, the amdgcn default; a half subnormal is a normal float32, so the float32 flush mode does not enter), signed zeros
+// and infinities; a NaN stays a NaN (a signalling one comes out quiet, as from any float conversion).
 // Each fetch takes the address of its unit's first element; the callers form it in element arithmetic, the same expression
-// for both formats (a pixel is two elements, a 4-pixel unit eight).
-//   flow_fetch4   a 4-pixel unit (mask_pack, se_class_squeeze): pixels pix .. pix + 3 of one flow plane, pix a multiple of 4.
-//                 float32: two 16-byte loads; binary16: ONE 16-byte load and eight widenings.  Aligned wherever the flow's base is
-//                 16-byte aligned: a plane holds 2 H W elements, H W a multiple of 16.
-//   flow_fetch2   a 2-pixel unit, the step of the SE squeeze's fixed chunking (se_squeeze_partial / se_squeeze_excite: unit i of
-//                 the plane, thread and chunk boundaries fall on units): one 16-byte load, or one 8-byte load and four widenings.
-//                 The squeeze keeps its units, so its summation order is the float32 format's.
-//   flow_fetch1   one pixel (the fused cnv1 patch fill): one 8-byte load, or one 4-byte load and two widenings.
-typedef _Float16 flow_f16;
+// for both formats (a flow pixel is two elements, a depth pixel one).
+//   flow_fetch4   a 4-pixel unit of flow (mask_pack, se_class_squeeze): pixels pix .. pix + 3 of one flow plane, pix a multiple of
+//                 4.  float32: two 16-byte loads; binary16: ONE 16-byte load and eight widenings.  Aligned wherever the flow's base
+//                 is 16-byte aligned: a plane holds 2 H W elements, H W a multiple of 16.
+//   widen_fetch4  four consecutive elements: one 16-byte load, or one 8-byte load and four widenings.  Of flow a 2-pixel unit, the
+//                 step of the SE squeeze's fixed chunking (se_squeeze_partial / se_squeeze_excite: unit i of the plane, thread and
+//                 chunk boundaries fall on units; the squeeze keeps its units, so its summation order is the float32 format's) and
+//                 of se_pool_squeeze.  Of depth pixels pix .. pix + 3 of one plane, pix a multiple of 4 - every reader of raw depth
+//                 goes through it; aligned wherever the planes' base is 16-byte aligned: a plane holds H W elements.
+//   flow_fetch1   one pixel of flow (the fused cnv1 patch fill): one 8-byte load, or one 4-byte load and two widenings.
+typedef _Float16 in_f16;
 struct Flow4 { float v[8]; };                                  // x0 y0 x1 y1 x2 y2 x3 y3
 __device__ __forceinline__ Flow4 flow_fetch4(const float* __restrict__ unit) {
     const float4* p = reinterpret_cast<const float4*>(unit);
     const float4 a = p[0], b = p[1];
     return Flow4{{a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w}};
 }
-__device__ __forceinline__ Flow4 flow_fetch4(const flow_f16* __restrict__ unit) {
-    typedef _Float16 flow_h8 __attribute__((ext_vector_type(8)));
-    const flow_h8 h = *reinterpret_cast<const flow_h8*>(unit);
+__device__ __forceinline__ Flow4 flow_fetch4(const in_f16* __restrict__ unit) {
+    typedef _Float16 in_h8 __attribute__((ext_vector_type(8)));
+    const in_h8 h = *reinterpret_cast<const in_h8*>(unit);
     return Flow4{{(float)h[0], (float)h[1], (float)h[2], (float)h[3], (float)h[4], (float)h[5], (float)h[6], (float)h[7]}};
 }
-__device__ __forceinline__ float4 flow_fetch2(const float* __restrict__ unit) {
+__device__ __forceinline__ float4 widen_fetch4(const float* __restrict__ unit) {
     return *reinterpret_cast<const float4*>(unit);
 }
-__device__ __forceinline__ float4 flow_fetch2(const flow_f16* __restrict__ unit) {
-    typedef _Float16 flow_h4 __attribute__((ext_vector_type(4)));
-    const flow_h4 h = *reinterpret_cast<const flow_h4*>(unit);
+__device__ __forceinline__ float4 widen_fetch4(const in_f16* __restrict__ unit) {
+    typedef _Float16 in_h4 __attribute__((ext_vector_type(4)));
+    const in_h4 h = *reinterpret_cast<const in_h4*>(unit);
     return make_float4((float)h[0], (float)h[1], (float)h[2], (float)h[3]);
 }
 __device__ __forceinline__ float2 flow_fetch1(const float* __restrict__ px) {
     return *reinterpret_cast<const float2*>(px);
 }
-__device__ __forceinline__ float2 flow_fetch1(const flow_f16* __restrict__ px) {
-    typedef _Float16 flow_h2 __attribute__((ext_vector_type(2)));
-    const flow_h2 h = *reinterpret_cast<const flow_h2*>(px);
+__device__ __forceinline__ float2 flow_fetch1(const in_f16* __restrict__ px) {
+    typedef _Float16 in_h2 __attribute__((ext_vector_type(2)));
+    const in_h2 h = *reinterpret_cast<const in_h2*>(px);
     return make_float2((float)h[0], (float)h[1]);
-}
-
-// The depth planes come in one of the two formats of davo_set_depth_format (include/davo_hip.h): float32, or IEEE binary16 in the
-// same layout ([B][3 file planes: src0, tgt, src1][H][W], one value per pixel).  DT is the element, float or depth_f16.  Every
-// reader of raw depth takes four horizontally adjacent pixels through depth_fetch4 and computes in float32 from there on - the
-// same expressions in the same order for both formats, so binary16 planes h give the bits of the float32 planes (float)h.  The
-// widening is the flow fetches' (above): exact for every binary16 value, subnormals, signed zeros and infinities included; a NaN
-// stays a NaN.
-//   depth_fetch4  pixels pix .. pix + 3 of one plane, pix a multiple of 4; the argument is the unit's first element, formed in
-//                 element arithmetic.  float32: one 16-byte load; binary16: ONE 8-byte load and four widenings.  Aligned wherever
-//                 the planes' base is 16-byte aligned: a plane holds H W elements, H W a multiple of 16.
-typedef _Float16 depth_f16;
-__device__ __forceinline__ float4 depth_fetch4(const float* __restrict__ unit) {
-    return *reinterpret_cast<const float4*>(unit);
-}
-__device__ __forceinline__ float4 depth_fetch4(const depth_f16* __restrict__ unit) {
-    typedef _Float16 depth_h4 __attribute__((ext_vector_type(4)));
-    const depth_h4 h = *reinterpret_cast<const depth_h4*>(unit);
-    return make_float4((float)h[0], (float)h[1], (float)h[2], (float)h[3]);
 }
 
 // Depth-split attention (att_source 13, davo.py:1143-1155): near = depth < thr in float32, strict; tf.where sends a NaN depth (the
@@ -108,7 +92,7 @@ __device__ __forceinline__ float att_lookup_split(const float* near19, const flo
 }
 
 // what the depth-split forms of mask_pack (prologue.h) and feature_maps (feature_export.h) take beside the near tables
-// (DT: the depth element, float or depth_f16 - the pointer keeps its element type all the way into the kernel)
+// (DT: the depth element, float or in_f16 - the pointer keeps its element type all the way into the kernel)
 template <typename DT>
 struct DepthSplitOf {
     const DT* depth;             // [B][3 file planes: src0, tgt, src1][H][W] in the depth format DT, 16-byte aligned

@@ -44,61 +44,59 @@ hipError_t launch_layer_h3w64(int layer, const ConvParamsH& p, hipStream_t s);  
 hipError_t launch_h3_generic(int KS, int stride, int tile, const ConvParamsH& p, dim3 grid, hipStream_t s);
 
 // ---- launch_misc.hip: prologue, pose head, cnv1 patch kernel, direct convolution ---------------------
-// d_flow / flow_fmt (here and below): the flow in the format FLOW_F32 or FLOW_F16 (params.h); any other value is an error
-hipError_t launch_se_squeeze(const void* d_flow, int flow_fmt, int B, int HW, const Variant& v, float* d_partial, int sel, hipStream_t s);
+// fmt (here and below): the context's input format (params.h) - what d_flow, d_seg and d_depth point at.  A launcher picks its kernel's
+// element types from it through input_types.h; a value that names no element type of a plane kind the kernel reads is an error
+hipError_t launch_se_squeeze(const void* d_flow, const InputFormat& fmt, int B, int HW, const Variant& v, float* d_partial, int sel, hipStream_t s);
 hipError_t launch_se_excite(const float* d_partial, int B, int HW, const Variant& v, const float* w1, const float* b1,
                             const float* w2, const float* b2, const float* wstatic, float* d_tab, unsigned* d_range_reset, int sel, hipStream_t s);
 // squeeze + excitation in one launch: the last workgroup of each triplet evaluates its tables (prologue.h, pose_tail.h);
 // -> 1 if the parts (x, 0..3) of a 64 x 4 grid ran on one XCD each for every x (what the folded split-K fix-up relies on), 0 if not
 hipError_t xcd_round_robin_probe(hipStream_t s, int* ok);
 // d_counters: one zeroed unsigned per triplet, left at zero
-hipError_t launch_se_squeeze_excite(const void* d_flow, int flow_fmt, int B, int HW, const Variant& v, float* d_partial, unsigned* d_counters,
+hipError_t launch_se_squeeze_excite(const void* d_flow, const InputFormat& fmt, int B, int HW, const Variant& v, float* d_partial, unsigned* d_counters,
                                     const float* w1, const float* b1, const float* w2, const float* b2, const float* wstatic,
                                     float* d_tab, unsigned* d_range_reset, int sel, hipStream_t s);
 // att_source 13: the same launch with both excitations in the last workgroup - near_w / far_w = {bottleneck kernel, bias, recover kernel,
 // bias} of se_flow_near / se_flow_far, d_tab the near tables, d_tab_far the far ones
-hipError_t launch_se_squeeze_excite_split(const void* d_flow, int flow_fmt, int B, int HW, const Variant& v, float* d_partial, unsigned* d_counters,
+hipError_t launch_se_squeeze_excite_split(const void* d_flow, const InputFormat& fmt, int B, int HW, const Variant& v, float* d_partial, unsigned* d_counters,
                                           const float* const near_w[4], const float* const far_w[4], float* d_tab, float* d_tab_far,
                                           unsigned* d_range_reset, int sel, hipStream_t s);
 // segmentation / rgb / seg+flow class-table sources (att_source 4..10): per-frame descriptor records into d_partial (max_batch x 3 x SQ_CHUNKS x SQ_REC words);
 // fold: the triplet's last workgroup evaluates its tables too (d_counters as above), otherwise launch_se_excite follows.
-// d_seg / label_fmt (here and below): the label maps in the format LABELS_F32 or LABELS_U8 (params.h); any other value is an error
-hipError_t launch_se_class_squeeze(bool fold, const uint8_t* d_img, const void* d_flow, int flow_fmt, const void* d_seg, int label_fmt, int B, int H, int W,
+hipError_t launch_se_class_squeeze(bool fold, const uint8_t* d_img, const void* d_flow, const void* d_seg, const InputFormat& fmt, int B, int H, int W,
                                   const Variant& v, unsigned* d_partial, unsigned* d_counters, const float* w1, const float* b1,
                                   const float* w2, const float* b2, float* d_tab, unsigned* d_range_reset, int sel, hipStream_t s);
 // depth sources (att_source 11, 12): one float32 sum per (triplet, frame, chunk) into word 0 of the same records; d_depth is
-// [B][3][H][W] in file order (src0, tgt, src1), 16-byte aligned, in the format depth_fmt: DEPTH_F32 or DEPTH_F16 (params.h; here and
-// below any other value is an error); fold as above
-hipError_t launch_se_depth_squeeze(bool fold, const void* d_depth, int depth_fmt, int B, int HW, const Variant& v, unsigned* d_partial,
+// [B][3][H][W] in file order (src0, tgt, src1), 16-byte aligned, in the format's depth element; fold as above
+hipError_t launch_se_depth_squeeze(bool fold, const void* d_depth, const InputFormat& fmt, int B, int HW, const Variant& v, unsigned* d_partial,
                                    unsigned* d_counters, const float* w1, const float* b1, const float* w2, const float* b2,
                                    float* d_tab, unsigned* d_range_reset, int sel, hipStream_t s);
 // pooled flow-attention variants (att_source 14..17; se_pool.h): window sums into d_partial [B][2][pd.n_items][2], then the excitation
 // (one launch each; "fold_tails" does not apply) -> d_tab [B][3][19] and the descriptor d_desc [B][2][2 pd.n_cells]
-hipError_t launch_se_pool_squeeze(const void* d_flow, int flow_fmt, int B, int H, int W, const Variant& v, const PoolDev& pd, float* d_partial,
+hipError_t launch_se_pool_squeeze(const void* d_flow, const InputFormat& fmt, int B, int H, int W, const Variant& v, const PoolDev& pd, float* d_partial,
                                   int sel, hipStream_t s);
 hipError_t launch_se_pool_excite(const float* d_partial, int B, const Variant& v, const PoolDev& pd, const float* w1, const float* b1,
                                  const float* w2, const float* b2, float* d_tab, float* d_desc, unsigned* d_range_reset, int sel, hipStream_t s);
 // ld: 16 = split-fp16 8-channel layout (f16x3), 8 = float32 8-channel, 10 = the reference's 10-channel layout
-// att_source 13 (the depth-split flow attention) runs the depth-split form: d_depth (16-byte aligned, in the format depth_fmt), the far
-// tables and the threshold are required there and ignored everywhere else
-hipError_t launch_mask_pack(int ld, const uint8_t* d_img, const void* d_flow, int flow_fmt, const void* d_seg, int label_fmt, const float* d_tab,
+// att_source 13 (the depth-split flow attention) runs the depth-split form: d_depth (16-byte aligned, in the format's depth element), the
+// far tables and the threshold are required there and ignored everywhere else (a caller with none passes nullptr, nullptr, 0.f)
+hipError_t launch_mask_pack(int ld, const uint8_t* d_img, const void* d_flow, const void* d_seg, const InputFormat& fmt, const float* d_tab,
                             const Variant& v, int B, int H, int W, float* d_packed, int sel, hipStream_t s,
-                            const void* d_depth = nullptr, const float* d_tab_far = nullptr, float depth_thr = 0.f, int depth_fmt = DEPTH_F32);
+                            const void* d_depth, const float* d_tab_far, float depth_thr);
 // the three-frame PoseNN's packer (prologue.h, mask_pack3): B windows -> [B][H][W][16], float32 or (h3) split-fp16 [16 hi | 16 lo]
-hipError_t launch_mask_pack3(bool h3, const uint8_t* d_img, const void* d_flow, int flow_fmt, const void* d_seg, int label_fmt, const float* d_tab,
+hipError_t launch_mask_pack3(bool h3, const uint8_t* d_img, const void* d_flow, const void* d_seg, const InputFormat& fmt, const float* d_tab,
                              const Variant& v, int B, int H, int W, float* d_packed, hipStream_t s);
 // window_gather.h: N windows of a frame-layout batch into the window-major planes every kernel above reads; every pointer 16-byte
 // aligned; a.f_flow null = the flow planes are in place already (the host entry points copy them there)
 struct GatherArgs;
-hipError_t launch_window_gather(const GatherArgs& a, int N, int label_fmt, int flow_fmt, int depth_fmt, hipStream_t s);
+hipError_t launch_window_gather(const GatherArgs& a, int N, const InputFormat& fmt, hipStream_t s);
 // window_mirror.h: N windows mirrored left-right (davo_set_flip).  frames: the gather above with mirrored stores, a's meaning
 // unchanged; else a.f_* are window-major like a.w_* - the same pointers (in place) or a caller's buffers - and a.f_flow is required.
 // a.seg_tgt: the target's label map is read at all.  Every pointer 16-byte aligned
-hipError_t launch_window_mirror(const GatherArgs& a, int N, bool frames, int label_fmt, int flow_fmt, int depth_fmt, hipStream_t s);
+hipError_t launch_window_mirror(const GatherArgs& a, int N, bool frames, const InputFormat& fmt, hipStream_t s);
 // cnv1 / cnv2 / cnv3 (layer 0..2) from an LDS-staged input patch: conv_patch_cnvN_h3, or conv_patch_cnvN_f32 in float32 mode (f32);
-// fused: conv_patch_cnv1_h3<true, float | uint8_t, float | flow_f16> by label_fmt and flow_fmt (f16x3 cnv1 only; p.seg and p.flow are in those formats)
-hipError_t launch_patch_layer(int layer, bool f32, bool fused, const ConvPatchParams& p, int nblk, hipStream_t s, int label_fmt = LABELS_F32,
-                              int flow_fmt = FLOW_F32);
+// fused: conv_patch_cnv1_h3<true, float | uint8_t, float | in_f16> by fmt's label and flow elements (f16x3 cnv1 only; p.seg and p.flow are in those formats)
+hipError_t launch_patch_layer(int layer, bool f32, bool fused, const ConvPatchParams& p, int nblk, hipStream_t s, const InputFormat& fmt);
 // cnv1 of the three-frame PoseNN from an LDS-staged patch (conv_patch_cnv1t_h3): p.x the 16-channel split-fp16 packed tensor, p.w
 // cp1t::WBYTES of fragments
 hipError_t launch_patch_cnv1t(const ConvPatchParams& p, int nblk, hipStream_t s);
@@ -126,10 +124,9 @@ hipError_t launch_se5_scale(bool h3, const void* d_x, const float* d_scale, int 
 // ---- launch_feature.hip: the feature export (feature_export.h; davo_forward_features) -----------------------------
 // one piece of nw windows: d_img / d_seg / d_tab point at the piece's first window; outputs [3][nw][19], [3][nw][H][W], [3][nw][H][W][3] x 2,
 // frames in the order tgt, src0, src1; a null output is not written
-hipError_t launch_feature_maps(const uint8_t* d_img, const void* d_seg, int label_fmt, const float* d_tab, const Variant& v, int nw, int H, int W,
+hipError_t launch_feature_maps(const uint8_t* d_img, const void* d_seg, const InputFormat& fmt, const float* d_tab, const Variant& v, int nw, int H, int W,
                                float* d_att_19, float* d_attention, float* d_masked, float* d_image, hipStream_t s,
-                               const void* d_depth = nullptr, const float* d_tab_far = nullptr, float depth_thr = 0.f,
-                               int depth_fmt = DEPTH_F32);                                                               // att_source 13: as launch_mask_pack
+                               const void* d_depth, const float* d_tab_far, float depth_thr);      // att_source 13: as launch_mask_pack
 // d_cnv6: the whole stored cnv6 of a both-pairs forward (h3: f16x3 blocked, scaled by 1 / unscale; else float32 NHWC); windows
 // [w0, w0 + nw) of it -> d_rot / d_trans [nw][4 H2][4 W2][c6]; a null head is not computed
 hipError_t launch_feature_resize_cnv6(bool h3, const void* d_cnv6, int w0, int nw, int H2, int W2, int c6, float unscale,

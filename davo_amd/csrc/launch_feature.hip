@@ -1,29 +1,14 @@
 // launch_feature.hip — the feature export kernels (feature_export.h) and their dispatch.
 #include "feature_export.h"
+#include "input_types.h"
 #include "launch.h"
 
 namespace davo {
 
-namespace {
-// the depth-split arguments as the host hands them on (the planes in the format depth_fmt); typed where the kernel is chosen
-struct DepthSplitArgs { const void* depth; const float* tab_far; float thr; };
-template <typename DT>
-DepthSplitOf<DT> depth_split_of(const DepthSplitArgs& a) { return DepthSplitOf<DT>{static_cast<const DT*>(a.depth), a.tab_far, a.thr}; }
-
-template <typename LT>
-void feature_maps_as(const dim3& grid, hipStream_t s, const uint8_t* d_img, const void* d_seg, const float* d_tab, const Variant& v, int nw, int H, int W,
-                     const FeatureMapsOut& o, const DepthSplitArgs* ds, int depth_fmt) {
-    const LT* seg = static_cast<const LT*>(d_seg);
-    if (ds && depth_fmt == DEPTH_F16) hipLaunchKernelGGL((feature_maps_depthsplit<LT, depth_f16>), grid, dim3(256), 0, s, d_img, seg, d_tab, v, nw, H, W, o, depth_split_of<depth_f16>(*ds));
-    else if (ds) hipLaunchKernelGGL((feature_maps_depthsplit<LT, float>), grid, dim3(256), 0, s, d_img, seg, d_tab, v, nw, H, W, o, depth_split_of<float>(*ds));
-    else hipLaunchKernelGGL(feature_maps<LT>, grid, dim3(256), 0, s, d_img, seg, d_tab, v, nw, H, W, o);
-}
-}  // namespace
-
-hipError_t launch_feature_maps(const uint8_t* d_img, const void* d_seg, int label_fmt, const float* d_tab, const Variant& v, int nw, int H, int W,
+hipError_t launch_feature_maps(const uint8_t* d_img, const void* d_seg, const InputFormat& fmt, const float* d_tab, const Variant& v, int nw, int H, int W,
                                float* d_att_19, float* d_attention, float* d_masked, float* d_image, hipStream_t s,
-                               const void* d_depth, const float* d_tab_far, float depth_thr, int depth_fmt) {
-    if ((label_fmt != LABELS_F32 && label_fmt != LABELS_U8) || (depth_fmt != DEPTH_F32 && depth_fmt != DEPTH_F16)) return hipErrorInvalidValue;
+                               const void* d_depth, const float* d_tab_far, float depth_thr) {
+    if (!valid(fmt)) return hipErrorInvalidValue;             // (the plain form reads no depth; a bad depth format is refused all the same)
     if (nw < 1 || H < 16 || W < 16 || H % 4 || W % 4 || !d_img || !d_seg || !d_tab) return hipErrorInvalidValue;
     if (!d_att_19 && !d_attention && !d_masked && !d_image) return hipSuccess;
     const long nthreads = (long)nw * H * (W / 4);             // >= 3 * nw * 19: the att_19 rows fit the first threads
@@ -32,9 +17,17 @@ hipError_t launch_feature_maps(const uint8_t* d_img, const void* d_seg, int labe
     const bool split = v.att_source == ATT_DEPTH_SPLIT;       // two tables per frame: no att_19 rows (api.hip refuses the member)
     if (split && (d_att_19 || !d_depth || ((uintptr_t)d_depth & 15) || !d_tab_far)) return hipErrorInvalidValue;
     const DepthSplitArgs ds{d_depth, d_tab_far, depth_thr};
-    if (label_fmt == LABELS_U8) feature_maps_as<uint8_t>(grid, s, d_img, d_seg, d_tab, v, nw, H, W, o, split ? &ds : nullptr, depth_fmt);
-    else feature_maps_as<float>(grid, s, d_img, d_seg, d_tab, v, nw, H, W, o, split ? &ds : nullptr, depth_fmt);
-    return hipGetLastError();
+    return with_label(fmt, [&](auto L) {
+        using LT = elem_t<decltype(L)>;
+        if (split)
+            return with_depth(fmt, [&](auto D) {
+                using DT = elem_t<decltype(D)>;
+                hipLaunchKernelGGL((feature_maps_depthsplit<LT, DT>), grid, dim3(256), 0, s, d_img, typed(L, d_seg), d_tab, v, nw, H, W, o, depth_split_of<DT>(ds));
+                return hipGetLastError();
+            });
+        hipLaunchKernelGGL(feature_maps<LT>, grid, dim3(256), 0, s, d_img, typed(L, d_seg), d_tab, v, nw, H, W, o);
+        return hipGetLastError();
+    });
 }
 
 hipError_t launch_feature_resize_cnv6(bool h3, const void* d_cnv6, int w0, int nw, int H2, int W2, int c6, float unscale,

@@ -3,10 +3,12 @@
 #include <algorithm>
 #include <mutex>
 #include <set>
+#include <type_traits>
 #include <utility>
 
 #include "conv_patch_h3.h"
 #include "conv_patch_f32.h"
+#include "input_types.h"
 #include "launch.h"
 #include "owned.h"
 #include "posenn_se.h"
@@ -32,21 +34,29 @@ hipError_t ensure_dynamic_lds(const void* kernel, int bytes) {
 }
 
 namespace {
-using flow_f32 = float;
-inline bool flow_fmt_ok(int flow_fmt) { return flow_fmt == FLOW_F32 || flow_fmt == FLOW_F16; }
-using depth_f32 = float;
-inline bool depth_fmt_ok(int depth_fmt) { return depth_fmt == DEPTH_F32 || depth_fmt == DEPTH_F16; }
+// a run-time choice among a kernel's non-type template arguments, as a constant the callable can name (input_types.h does the
+// same for the element types)
+template <typename Fn>
+__attribute__((always_inline)) inline hipError_t with_bool(bool b, Fn&& fn) {
+    return b ? fn(std::true_type{}) : fn(std::false_type{});
+}
+template <typename Fn>
+__attribute__((always_inline)) inline hipError_t with_pack_ld(int ld, Fn&& fn) {
+    if (ld == 16) return fn(std::integral_constant<int, 16>{});
+    if (ld == 8) return fn(std::integral_constant<int, 8>{});
+    if (ld == 10) return fn(std::integral_constant<int, 10>{});
+    return hipErrorInvalidValue;
+}
 }  // namespace
 
-// d_flow / flow_fmt (here and below): the flow in the format FLOW_F32 or FLOW_F16 (params.h); any other value is an error
-hipError_t launch_se_squeeze(const void* d_flow, int flow_fmt, int B, int HW, const Variant& v, float* d_partial, int sel, hipStream_t s) {
-    if (!flow_fmt_ok(flow_fmt)) return hipErrorInvalidValue;
+// fmt (here and below): the context's input format (params.h) - what d_flow, d_seg and d_depth point at; a value that names no
+// element type of a plane kind the kernel reads is an error
+hipError_t launch_se_squeeze(const void* d_flow, const InputFormat& fmt, int B, int HW, const Variant& v, float* d_partial, int sel, hipStream_t s) {
     const dim3 grid(SQ_CHUNKS, pairs_per_window(sel), B);
-    if (flow_fmt == FLOW_F16)
-        hipLaunchKernelGGL(se_squeeze_partial<flow_f16>, grid, dim3(256), 0, s, static_cast<const flow_f16*>(d_flow), HW, v.norm_flow, v.abs_mode, sel, d_partial);
-    else
-        hipLaunchKernelGGL(se_squeeze_partial<flow_f32>, grid, dim3(256), 0, s, static_cast<const float*>(d_flow), HW, v.norm_flow, v.abs_mode, sel, d_partial);
-    return hipGetLastError();
+    return with_flow(fmt, [&](auto F) {
+        hipLaunchKernelGGL(se_squeeze_partial<elem_t<decltype(F)>>, grid, dim3(256), 0, s, typed(F, d_flow), HW, v.norm_flow, v.abs_mode, sel, d_partial);
+        return hipGetLastError();
+    });
 }
 
 hipError_t launch_se_excite(const float* d_partial, int B, int HW, const Variant& v, const float* w1, const float* b1,
@@ -55,102 +65,62 @@ hipError_t launch_se_excite(const float* d_partial, int B, int HW, const Variant
     return hipGetLastError();
 }
 
-hipError_t launch_se_squeeze_excite(const void* d_flow, int flow_fmt, int B, int HW, const Variant& v, float* d_partial, unsigned* d_counters,
+hipError_t launch_se_squeeze_excite(const void* d_flow, const InputFormat& fmt, int B, int HW, const Variant& v, float* d_partial, unsigned* d_counters,
                                     const float* w1, const float* b1, const float* w2, const float* b2, const float* wstatic,
                                     float* d_tab, unsigned* d_range_reset, int sel, hipStream_t s) {
-    if (!flow_fmt_ok(flow_fmt)) return hipErrorInvalidValue;
     const dim3 grid(SQ_CHUNKS, pairs_per_window(sel), B);
-    if (flow_fmt == FLOW_F16)
-        hipLaunchKernelGGL(se_squeeze_excite<flow_f16>, grid, dim3(256), 0, s, static_cast<const flow_f16*>(d_flow), HW, v, d_partial, d_counters, w1, b1, w2, b2,
+    return with_flow(fmt, [&](auto F) {
+        hipLaunchKernelGGL(se_squeeze_excite<elem_t<decltype(F)>>, grid, dim3(256), 0, s, typed(F, d_flow), HW, v, d_partial, d_counters, w1, b1, w2, b2,
                            wstatic, d_tab, d_range_reset, sel);
-    else
-        hipLaunchKernelGGL(se_squeeze_excite<flow_f32>, grid, dim3(256), 0, s, static_cast<const float*>(d_flow), HW, v, d_partial, d_counters, w1, b1, w2, b2,
-                           wstatic, d_tab, d_range_reset, sel);
-    return hipGetLastError();
+        return hipGetLastError();
+    });
 }
 
-hipError_t launch_se_squeeze_excite_split(const void* d_flow, int flow_fmt, int B, int HW, const Variant& v, float* d_partial, unsigned* d_counters,
+hipError_t launch_se_squeeze_excite_split(const void* d_flow, const InputFormat& fmt, int B, int HW, const Variant& v, float* d_partial, unsigned* d_counters,
                                           const float* const near_w[4], const float* const far_w[4], float* d_tab, float* d_tab_far,
                                           unsigned* d_range_reset, int sel, hipStream_t s) {
-    if (v.att_source != ATT_DEPTH_SPLIT || !d_tab_far || !flow_fmt_ok(flow_fmt)) return hipErrorInvalidValue;
+    if (v.att_source != ATT_DEPTH_SPLIT || !d_tab_far) return hipErrorInvalidValue;
     for (int k = 0; k < 4; ++k) if (!near_w[k] || !far_w[k]) return hipErrorInvalidValue;
     const SeFar far{far_w[0], far_w[1], far_w[2], far_w[3], d_tab_far};
     const dim3 grid(SQ_CHUNKS, pairs_per_window(sel), B);
-    if (flow_fmt == FLOW_F16)
-        hipLaunchKernelGGL(se_squeeze_excite_split<flow_f16>, grid, dim3(256), 0, s, static_cast<const flow_f16*>(d_flow), HW, v, d_partial, d_counters,
+    return with_flow(fmt, [&](auto F) {
+        hipLaunchKernelGGL(se_squeeze_excite_split<elem_t<decltype(F)>>, grid, dim3(256), 0, s, typed(F, d_flow), HW, v, d_partial, d_counters,
                            near_w[0], near_w[1], near_w[2], near_w[3], d_tab, d_range_reset, sel, far);
-    else
-        hipLaunchKernelGGL(se_squeeze_excite_split<flow_f32>, grid, dim3(256), 0, s, static_cast<const float*>(d_flow), HW, v, d_partial, d_counters,
-                           near_w[0], near_w[1], near_w[2], near_w[3], d_tab, d_range_reset, sel, far);
-    return hipGetLastError();
+        return hipGetLastError();
+    });
 }
 
-namespace {
-template <typename LT, typename FT>
-void se_class_squeeze_as(bool fold, const dim3& grid, hipStream_t s, const uint8_t* d_img, const void* d_flow_raw, const void* d_seg, int H, int W,
-                         const Variant& v, unsigned* d_partial, unsigned* d_counters, const float* w1, const float* b1,
-                         const float* w2, const float* b2, float* d_tab, unsigned* d_range_reset, int sel) {
-    const LT* seg = static_cast<const LT*>(d_seg);
-    const FT* d_flow = static_cast<const FT*>(d_flow_raw);
-    if (fold)
-        hipLaunchKernelGGL((se_class_squeeze<true, LT, FT>), grid, dim3(256), 0, s, d_img, d_flow, seg, H, W, v, d_partial, d_counters,
-                           w1, b1, w2, b2, d_tab, d_range_reset, sel);
-    else
-        hipLaunchKernelGGL((se_class_squeeze<false, LT, FT>), grid, dim3(256), 0, s, d_img, d_flow, seg, H, W, v, d_partial, d_counters,
-                           w1, b1, w2, b2, d_tab, d_range_reset, sel);
-}
-}  // namespace
-
-hipError_t launch_se_class_squeeze(bool fold, const uint8_t* d_img, const void* d_flow, int flow_fmt, const void* d_seg, int label_fmt, int B, int H, int W,
+hipError_t launch_se_class_squeeze(bool fold, const uint8_t* d_img, const void* d_flow, const void* d_seg, const InputFormat& fmt, int B, int H, int W,
                                   const Variant& v, unsigned* d_partial, unsigned* d_counters, const float* w1, const float* b1,
                                   const float* w2, const float* b2, float* d_tab, unsigned* d_range_reset, int sel, hipStream_t s) {
     const dim3 grid(SQ_CHUNKS, att_se_frames(v.att_source) - (sel == PAIRS_BOTH ? 0 : 1), B);
-    if (!flow_fmt_ok(flow_fmt) || (label_fmt != LABELS_F32 && label_fmt != LABELS_U8)) return hipErrorInvalidValue;
-    const bool u8 = label_fmt == LABELS_U8;
-    if (flow_fmt == FLOW_F16) {
-        if (u8) se_class_squeeze_as<uint8_t, flow_f16>(fold, grid, s, d_img, d_flow, d_seg, H, W, v, d_partial, d_counters, w1, b1, w2, b2, d_tab, d_range_reset, sel);
-        else se_class_squeeze_as<float, flow_f16>(fold, grid, s, d_img, d_flow, d_seg, H, W, v, d_partial, d_counters, w1, b1, w2, b2, d_tab, d_range_reset, sel);
-    } else {
-        if (u8) se_class_squeeze_as<uint8_t, flow_f32>(fold, grid, s, d_img, d_flow, d_seg, H, W, v, d_partial, d_counters, w1, b1, w2, b2, d_tab, d_range_reset, sel);
-        else se_class_squeeze_as<float, flow_f32>(fold, grid, s, d_img, d_flow, d_seg, H, W, v, d_partial, d_counters, w1, b1, w2, b2, d_tab, d_range_reset, sel);
-    }
-    return hipGetLastError();
+    return with_flow(fmt, [&](auto F) { return with_label(fmt, [&](auto L) { return with_bool(fold, [&](auto FOLD) {
+        hipLaunchKernelGGL((se_class_squeeze<decltype(FOLD)::value, elem_t<decltype(L)>, elem_t<decltype(F)>>), grid, dim3(256), 0, s, d_img,
+                           typed(F, d_flow), typed(L, d_seg), H, W, v, d_partial, d_counters, w1, b1, w2, b2, d_tab, d_range_reset, sel);
+        return hipGetLastError();
+    }); }); });
 }
 
-namespace {
-template <typename DT>
-void se_depth_squeeze_as(bool fold, const dim3& grid, hipStream_t s, const void* d_depth_raw, int HW, const Variant& v, unsigned* d_partial,
-                         unsigned* d_counters, const float* w1, const float* b1, const float* w2, const float* b2, float* d_tab,
-                         unsigned* d_range_reset, int sel) {
-    const DT* d_depth = static_cast<const DT*>(d_depth_raw);
-    if (fold)
-        hipLaunchKernelGGL((se_depth_squeeze<true, DT>), grid, dim3(256), 0, s, d_depth, HW, v, d_partial, d_counters, w1, b1, w2, b2, d_tab,
-                           d_range_reset, sel);
-    else
-        hipLaunchKernelGGL((se_depth_squeeze<false, DT>), grid, dim3(256), 0, s, d_depth, HW, v, d_partial, d_counters, w1, b1, w2, b2, d_tab,
-                           d_range_reset, sel);
-}
-}  // namespace
-
-hipError_t launch_se_depth_squeeze(bool fold, const void* d_depth, int depth_fmt, int B, int HW, const Variant& v, unsigned* d_partial,
+hipError_t launch_se_depth_squeeze(bool fold, const void* d_depth, const InputFormat& fmt, int B, int HW, const Variant& v, unsigned* d_partial,
                                    unsigned* d_counters, const float* w1, const float* b1, const float* w2, const float* b2,
                                    float* d_tab, unsigned* d_range_reset, int sel, hipStream_t s) {
-    if (!att_desc_depth(v.att_source) || !d_depth || ((uintptr_t)d_depth & 15) || HW % 16 || !depth_fmt_ok(depth_fmt)) return hipErrorInvalidValue;
+    if (!att_desc_depth(v.att_source) || !d_depth || ((uintptr_t)d_depth & 15) || HW % 16) return hipErrorInvalidValue;
     const dim3 grid(SQ_CHUNKS, 1 + pairs_per_window(sel), B);
-    if (depth_fmt == DEPTH_F16) se_depth_squeeze_as<depth_f16>(fold, grid, s, d_depth, HW, v, d_partial, d_counters, w1, b1, w2, b2, d_tab, d_range_reset, sel);
-    else se_depth_squeeze_as<depth_f32>(fold, grid, s, d_depth, HW, v, d_partial, d_counters, w1, b1, w2, b2, d_tab, d_range_reset, sel);
-    return hipGetLastError();
+    return with_depth(fmt, [&](auto D) { return with_bool(fold, [&](auto FOLD) {
+        hipLaunchKernelGGL((se_depth_squeeze<decltype(FOLD)::value, elem_t<decltype(D)>>), grid, dim3(256), 0, s, typed(D, d_depth), HW, v, d_partial,
+                           d_counters, w1, b1, w2, b2, d_tab, d_range_reset, sel);
+        return hipGetLastError();
+    }); });
 }
 
-hipError_t launch_se_pool_squeeze(const void* d_flow, int flow_fmt, int B, int H, int W, const Variant& v, const PoolDev& pd, float* d_partial,
+hipError_t launch_se_pool_squeeze(const void* d_flow, const InputFormat& fmt, int B, int H, int W, const Variant& v, const PoolDev& pd, float* d_partial,
                                   int sel, hipStream_t s) {
-    if (!att_pooled(v.att_source) || !flow_fmt_ok(flow_fmt) || W % 4 || pd.n_items < 1 || !pd.items || !d_flow || !d_partial) return hipErrorInvalidValue;
+    if (!att_pooled(v.att_source) || W % 4 || pd.n_items < 1 || !pd.items || !d_flow || !d_partial) return hipErrorInvalidValue;
     const dim3 grid(pd.n_items, pairs_per_window(sel), B);
-    if (flow_fmt == FLOW_F16)
-        hipLaunchKernelGGL(se_pool_squeeze<flow_f16>, grid, dim3(256), 0, s, static_cast<const flow_f16*>(d_flow), H, W, v, sel, pd, d_partial);
-    else
-        hipLaunchKernelGGL(se_pool_squeeze<flow_f32>, grid, dim3(256), 0, s, static_cast<const float*>(d_flow), H, W, v, sel, pd, d_partial);
-    return hipGetLastError();
+    return with_flow(fmt, [&](auto F) {
+        hipLaunchKernelGGL(se_pool_squeeze<elem_t<decltype(F)>>, grid, dim3(256), 0, s, typed(F, d_flow), H, W, v, sel, pd, d_partial);
+        return hipGetLastError();
+    });
 }
 
 hipError_t launch_se_pool_excite(const float* d_partial, int B, const Variant& v, const PoolDev& pd, const float* w1, const float* b1,
@@ -166,96 +136,48 @@ hipError_t launch_se_pool_excite(const float* d_partial, int B, const Variant& v
     return hipGetLastError();
 }
 
-namespace {
-// the depth-split arguments as the host hands them on (the planes in the format depth_fmt); typed where the kernel is chosen
-struct DepthSplitArgs { const void* depth; const float* tab_far; float thr; };
-template <typename DT>
-DepthSplitOf<DT> depth_split_of(const DepthSplitArgs& a) { return DepthSplitOf<DT>{static_cast<const DT*>(a.depth), a.tab_far, a.thr}; }
-
-template <typename LT, typename FT, typename DT>
-hipError_t mask_pack_split_as(int ld, const dim3& grid, hipStream_t s, const uint8_t* d_img, const FT* d_flow, const LT* seg, const float* d_tab,
-                              const Variant& v, int B, int sel, int H, int W, float* d_packed, const DepthSplitArgs& args) {
-    const DepthSplitOf<DT> ds = depth_split_of<DT>(args);
-    if (ld == 16) hipLaunchKernelGGL((mask_pack_depthsplit<16, LT, FT, DT>), grid, dim3(256), 0, s, d_img, d_flow, seg, d_tab, v, B, sel, H, W, d_packed, ds);
-    else if (ld == 8) hipLaunchKernelGGL((mask_pack_depthsplit<8, LT, FT, DT>), grid, dim3(256), 0, s, d_img, d_flow, seg, d_tab, v, B, sel, H, W, d_packed, ds);
-    else if (ld == 10) hipLaunchKernelGGL((mask_pack_depthsplit<10, LT, FT, DT>), grid, dim3(256), 0, s, d_img, d_flow, seg, d_tab, v, B, sel, H, W, d_packed, ds);
-    else return hipErrorInvalidValue;
-    return hipGetLastError();
-}
-
-// ds: the depth-split form (null: the plain packer), its planes in the format depth_fmt
-template <typename LT, typename FT>
-hipError_t mask_pack_as(int ld, const dim3& grid, hipStream_t s, const uint8_t* d_img, const void* d_flow_raw, const void* d_seg, const float* d_tab,
-                        const Variant& v, int B, int sel, int H, int W, float* d_packed, const DepthSplitArgs* ds, int depth_fmt) {
-    const LT* seg = static_cast<const LT*>(d_seg);
-    const FT* d_flow = static_cast<const FT*>(d_flow_raw);
-    if (ds) {
-        if (depth_fmt == DEPTH_F16) return mask_pack_split_as<LT, FT, depth_f16>(ld, grid, s, d_img, d_flow, seg, d_tab, v, B, sel, H, W, d_packed, *ds);
-        return mask_pack_split_as<LT, FT, depth_f32>(ld, grid, s, d_img, d_flow, seg, d_tab, v, B, sel, H, W, d_packed, *ds);
-    }
-    if (ld == 16) hipLaunchKernelGGL((mask_pack<16, LT, FT>), grid, dim3(256), 0, s, d_img, d_flow, seg, d_tab, v, B, sel, H, W, d_packed);
-    else if (ld == 8) hipLaunchKernelGGL((mask_pack<8, LT, FT>), grid, dim3(256), 0, s, d_img, d_flow, seg, d_tab, v, B, sel, H, W, d_packed);
-    else if (ld == 10) hipLaunchKernelGGL((mask_pack<10, LT, FT>), grid, dim3(256), 0, s, d_img, d_flow, seg, d_tab, v, B, sel, H, W, d_packed);
-    else return hipErrorInvalidValue;
-    return hipGetLastError();
-}
-}  // namespace
-
-hipError_t launch_mask_pack(int ld, const uint8_t* d_img, const void* d_flow, int flow_fmt, const void* d_seg, int label_fmt, const float* d_tab,
+hipError_t launch_mask_pack(int ld, const uint8_t* d_img, const void* d_flow, const void* d_seg, const InputFormat& fmt, const float* d_tab,
                             const Variant& v, int B, int H, int W, float* d_packed, int sel, hipStream_t s,
-                            const void* d_depth, const float* d_tab_far, float depth_thr, int depth_fmt) {
+                            const void* d_depth, const float* d_tab_far, float depth_thr) {
     const long nthreads = (long)pairs_per_window(sel) * B * H * (W / 4);
     const dim3 grid((unsigned)((nthreads + 255) / 256));
     const bool split = v.att_source == ATT_DEPTH_SPLIT;
     // the depth-split form: a missing plane or table is an error, never the plain packer
     if (split && (!d_depth || ((uintptr_t)d_depth & 15) || !d_tab_far)) return hipErrorInvalidValue;
+    if (!valid(fmt)) return hipErrorInvalidValue;      // (the plain packer reads no depth; a bad depth format is refused all the same)
     const DepthSplitArgs ds{d_depth, d_tab_far, depth_thr};
-    const DepthSplitArgs* const dsp = split ? &ds : nullptr;
-    if (!flow_fmt_ok(flow_fmt) || !depth_fmt_ok(depth_fmt) || (label_fmt != LABELS_F32 && label_fmt != LABELS_U8)) return hipErrorInvalidValue;
-    if (flow_fmt == FLOW_F16) {
-        if (label_fmt == LABELS_U8) return mask_pack_as<uint8_t, flow_f16>(ld, grid, s, d_img, d_flow, d_seg, d_tab, v, B, sel, H, W, d_packed, dsp, depth_fmt);
-        return mask_pack_as<float, flow_f16>(ld, grid, s, d_img, d_flow, d_seg, d_tab, v, B, sel, H, W, d_packed, dsp, depth_fmt);
-    }
-    if (label_fmt == LABELS_U8) return mask_pack_as<uint8_t, flow_f32>(ld, grid, s, d_img, d_flow, d_seg, d_tab, v, B, sel, H, W, d_packed, dsp, depth_fmt);
-    return mask_pack_as<float, flow_f32>(ld, grid, s, d_img, d_flow, d_seg, d_tab, v, B, sel, H, W, d_packed, dsp, depth_fmt);
+    return with_flow(fmt, [&](auto F) { return with_label(fmt, [&](auto L) {
+        using LT = elem_t<decltype(L)>;
+        using FT = elem_t<decltype(F)>;
+        if (split)
+            return with_depth(fmt, [&](auto D) { return with_pack_ld(ld, [&](auto LD) {
+                using DT = elem_t<decltype(D)>;
+                hipLaunchKernelGGL((mask_pack_depthsplit<decltype(LD)::value, LT, FT, DT>), grid, dim3(256), 0, s, d_img, typed(F, d_flow), typed(L, d_seg), d_tab,
+                                   v, B, sel, H, W, d_packed, depth_split_of<DT>(ds));
+                return hipGetLastError();
+            }); });
+        return with_pack_ld(ld, [&](auto LD) {
+            hipLaunchKernelGGL((mask_pack<decltype(LD)::value, LT, FT>), grid, dim3(256), 0, s, d_img, typed(F, d_flow), typed(L, d_seg), d_tab, v, B, sel, H, W,
+                               d_packed);
+            return hipGetLastError();
+        });
+    }); });
 }
 
-namespace {
-template <typename LT, typename FT>
-hipError_t mask_pack3_as(bool h3, const dim3& grid, hipStream_t s, const uint8_t* d_img, const void* d_flow, const void* d_seg, const float* d_tab,
-                         const Variant& v, int B, int H, int W, float* d_packed) {
-    const LT* seg = static_cast<const LT*>(d_seg);
-    const FT* flow = static_cast<const FT*>(d_flow);
-    if (h3) hipLaunchKernelGGL((mask_pack3<true, LT, FT>), grid, dim3(PACK3_THREADS), 0, s, d_img, flow, seg, d_tab, v, B, H, W, d_packed);
-    else hipLaunchKernelGGL((mask_pack3<false, LT, FT>), grid, dim3(PACK3_THREADS), 0, s, d_img, flow, seg, d_tab, v, B, H, W, d_packed);
-    return hipGetLastError();
-}
-}  // namespace
-
-hipError_t launch_mask_pack3(bool h3, const uint8_t* d_img, const void* d_flow, int flow_fmt, const void* d_seg, int label_fmt, const float* d_tab,
+hipError_t launch_mask_pack3(bool h3, const uint8_t* d_img, const void* d_flow, const void* d_seg, const InputFormat& fmt, const float* d_tab,
                              const Variant& v, int B, int H, int W, float* d_packed, hipStream_t s) {
     if (B < 1 || H < 1 || W < 4 || W % 4 || !d_img || !d_flow || !d_seg || !d_tab || !d_packed) return hipErrorInvalidValue;
-    if (!flow_fmt_ok(flow_fmt) || (label_fmt != LABELS_F32 && label_fmt != LABELS_U8)) return hipErrorInvalidValue;
     if (att_reads_depth(v.att_source)) return hipErrorInvalidValue;      // no three-frame form of the depth sources
     const long nthreads = (long)B * H * (W / 4);
     const dim3 grid((unsigned)((nthreads + PACK3_THREADS - 1) / PACK3_THREADS));
-    if (flow_fmt == FLOW_F16) {
-        if (label_fmt == LABELS_U8) return mask_pack3_as<uint8_t, flow_f16>(h3, grid, s, d_img, d_flow, d_seg, d_tab, v, B, H, W, d_packed);
-        return mask_pack3_as<float, flow_f16>(h3, grid, s, d_img, d_flow, d_seg, d_tab, v, B, H, W, d_packed);
-    }
-    if (label_fmt == LABELS_U8) return mask_pack3_as<uint8_t, flow_f32>(h3, grid, s, d_img, d_flow, d_seg, d_tab, v, B, H, W, d_packed);
-    return mask_pack3_as<float, flow_f32>(h3, grid, s, d_img, d_flow, d_seg, d_tab, v, B, H, W, d_packed);
+    return with_flow(fmt, [&](auto F) { return with_label(fmt, [&](auto L) { return with_bool(h3, [&](auto H3) {
+        hipLaunchKernelGGL((mask_pack3<decltype(H3)::value, elem_t<decltype(L)>, elem_t<decltype(F)>>), grid, dim3(PACK3_THREADS), 0, s, d_img,
+                           typed(F, d_flow), typed(L, d_seg), d_tab, v, B, H, W, d_packed);
+        return hipGetLastError();
+    }); }); });
 }
 
-namespace {
-template <typename LT, typename FT>
-void window_gather_as(const GatherArgs& a, const dim3& grid, int depth_fmt, hipStream_t s) {
-    if (depth_fmt == DEPTH_F16) hipLaunchKernelGGL((window_gather<LT, FT, depth_f16>), grid, dim3(256), 0, s, a);
-    else hipLaunchKernelGGL((window_gather<LT, FT, depth_f32>), grid, dim3(256), 0, s, a);
-}
-}  // namespace
-
-hipError_t launch_window_gather(const GatherArgs& a, int N, int label_fmt, int flow_fmt, int depth_fmt, hipStream_t s) {
+hipError_t launch_window_gather(const GatherArgs& a, int N, const InputFormat& fmt, hipStream_t s) {
     if (N < 1 || a.H < 1 || a.W < 4 || a.W % 4 || ((size_t)a.H * a.W) % 16 || !a.f_img || !a.f_seg || !a.w_img || !a.w_seg || !a.w_flow ||
         (a.f_depth && !a.w_depth))
         return hipErrorInvalidValue;
@@ -264,65 +186,44 @@ hipError_t launch_window_gather(const GatherArgs& a, int N, int label_fmt, int f
         return hipErrorInvalidValue;
     // the largest job decides the pieces per job (a flow plane, else a frame or a float32 plane); at most 8, the rest in rounds
     const size_t HW = (size_t)a.H * a.W;
-    if (!flow_fmt_ok(flow_fmt) || !depth_fmt_ok(depth_fmt) || (label_fmt != LABELS_F32 && label_fmt != LABELS_U8)) return hipErrorInvalidValue;
     // (a binary16 flow plane is HW / 4 vectors, no more than a float32 label or depth plane, a binary16 depth plane HW / 8: the max below covers them)
-    const size_t vecs = a.f_flow ? (flow_fmt == FLOW_F16 ? HW / 4 : HW / 2) : (a.W % 16 == 0 ? HW * 3 / 16 : HW * 3 / 4);
+    const size_t vecs = a.f_flow ? HW * 2 * element_bytes(fmt).flow / 16 : (a.W % 16 == 0 ? HW * 3 / 16 : HW * 3 / 4);
     const unsigned gx = (unsigned)std::min<size_t>(8, (std::max(vecs, HW / 4) + GATHER_PIECE - 1) / GATHER_PIECE);
     const dim3 grid(gx, (unsigned)N, GATHER_JOBS);
-    if (flow_fmt == FLOW_F16) {
-        if (label_fmt == LABELS_U8) window_gather_as<uint8_t, flow_f16>(a, grid, depth_fmt, s);
-        else window_gather_as<float, flow_f16>(a, grid, depth_fmt, s);
-    } else {
-        if (label_fmt == LABELS_U8) window_gather_as<uint8_t, flow_f32>(a, grid, depth_fmt, s);
-        else window_gather_as<float, flow_f32>(a, grid, depth_fmt, s);
-    }
-    return hipGetLastError();
+    return with_flow(fmt, [&](auto F) { return with_label(fmt, [&](auto L) { return with_depth(fmt, [&](auto D) {
+        hipLaunchKernelGGL((window_gather<elem_t<decltype(L)>, elem_t<decltype(F)>, elem_t<decltype(D)>>), grid, dim3(256), 0, s, a);
+        return hipGetLastError();
+    }); }); });
 }
 
-namespace {
-template <typename DT, bool FRAMES>
-void window_mirror_as(const GatherArgs& a, const dim3& grid, int label_fmt, int flow_fmt, hipStream_t s) {
-    if (flow_fmt == FLOW_F16) {
-        if (label_fmt == LABELS_U8) hipLaunchKernelGGL((window_mirror<uint8_t, flow_f16, DT, FRAMES>), grid, dim3(256), 0, s, a);
-        else hipLaunchKernelGGL((window_mirror<float, flow_f16, DT, FRAMES>), grid, dim3(256), 0, s, a);
-    } else {
-        if (label_fmt == LABELS_U8) hipLaunchKernelGGL((window_mirror<uint8_t, flow_f32, DT, FRAMES>), grid, dim3(256), 0, s, a);
-        else hipLaunchKernelGGL((window_mirror<float, flow_f32, DT, FRAMES>), grid, dim3(256), 0, s, a);
-    }
-}
-}  // namespace
-
-hipError_t launch_window_mirror(const GatherArgs& a, int N, bool frames, int label_fmt, int flow_fmt, int depth_fmt, hipStream_t s) {
+hipError_t launch_window_mirror(const GatherArgs& a, int N, bool frames, const InputFormat& fmt, hipStream_t s) {
     if (N < 1 || a.H < 1 || a.W < 4 || a.W % 4 || ((size_t)a.H * a.W) % 16 || !a.f_img || !a.f_seg || !a.w_img || !a.w_seg || !a.w_flow ||
         (a.f_depth && !a.w_depth) || (!frames && !a.f_flow))
         return hipErrorInvalidValue;
     if (((uintptr_t)a.f_img | (uintptr_t)a.f_seg | (uintptr_t)a.f_depth | (uintptr_t)a.f_flow | (uintptr_t)a.w_img | (uintptr_t)a.w_seg |
          (uintptr_t)a.w_depth | (uintptr_t)a.w_flow) & 15)
         return hipErrorInvalidValue;
-    if (!flow_fmt_ok(flow_fmt) || !depth_fmt_ok(depth_fmt) || (label_fmt != LABELS_F32 && label_fmt != LABELS_U8)) return hipErrorInvalidValue;
     // the job with the most unit pairs decides the pieces per job: a flow plane (four pixels a unit, half as many pairs a row); at
     // most 8, the rest in rounds
     const size_t pairs = (size_t)a.H * ((a.W / 4 + 1) / 2);
     const unsigned gx = (unsigned)std::min<size_t>(8, (pairs + MIRROR_PIECE - 1) / MIRROR_PIECE);
     const dim3 grid(gx, (unsigned)N, GATHER_JOBS);
-    if (depth_fmt == DEPTH_F16) {
-        if (frames) window_mirror_as<depth_f16, true>(a, grid, label_fmt, flow_fmt, s);
-        else window_mirror_as<depth_f16, false>(a, grid, label_fmt, flow_fmt, s);
-    } else {
-        if (frames) window_mirror_as<depth_f32, true>(a, grid, label_fmt, flow_fmt, s);
-        else window_mirror_as<depth_f32, false>(a, grid, label_fmt, flow_fmt, s);
-    }
-    return hipGetLastError();
+    return with_depth(fmt, [&](auto D) { return with_bool(frames, [&](auto FR) { return with_flow(fmt, [&](auto F) { return with_label(fmt, [&](auto L) {
+        hipLaunchKernelGGL((window_mirror<elem_t<decltype(L)>, elem_t<decltype(F)>, elem_t<decltype(D)>, decltype(FR)::value>), grid, dim3(256), 0, s, a);
+        return hipGetLastError();
+    }); }); }); });
 }
 
-hipError_t launch_patch_layer(int layer, bool f32, bool fused, const ConvPatchParams& p, int nblk, hipStream_t s, int label_fmt, int flow_fmt) {
+hipError_t launch_patch_layer(int layer, bool f32, bool fused, const ConvPatchParams& p, int nblk, hipStream_t s, const InputFormat& fmt) {
     using Kernel = void (*)(ConvPatchParams);
     struct Row { Kernel h3, f32; int threads, lds; };
-    if ((label_fmt != LABELS_F32 && label_fmt != LABELS_U8) || !flow_fmt_ok(flow_fmt)) return hipErrorInvalidValue;
-    static const Kernel cnv1_fused_f32 = conv_patch_cnv1_h3<true, float>, cnv1_fused_u8 = conv_patch_cnv1_h3<true, uint8_t>;
-    static const Kernel cnv1_fused_f32_hf = conv_patch_cnv1_h3<true, float, flow_f16>, cnv1_fused_u8_hf = conv_patch_cnv1_h3<true, uint8_t, flow_f16>;
-    const Kernel cnv1_fused = flow_fmt == FLOW_F16 ? (label_fmt == LABELS_U8 ? cnv1_fused_u8_hf : cnv1_fused_f32_hf)
-                                                   : (label_fmt == LABELS_U8 ? cnv1_fused_u8 : cnv1_fused_f32);
+    // the fused cnv1 of the context's label and flow elements (p.seg and p.flow are in those formats)
+    Kernel cnv1_fused = nullptr;
+    const hipError_t fe = with_flow(fmt, [&](auto F) { return with_label(fmt, [&](auto L) {
+        cnv1_fused = conv_patch_cnv1_h3<true, elem_t<decltype(L)>, elem_t<decltype(F)>>;
+        return hipSuccess;
+    }); });
+    if (fe != hipSuccess) return fe;
     static const Row rows[3] = {{conv_patch_cnv1_h3<false>, conv_patch_cnv1_f32, cp1::THREADS, cp1::LDS_BYTES},
                                 {conv_patch_cnv2_h3, conv_patch_cnv2_f32, cp2::THREADS, cp2::LDS_BYTES},
                                 {conv_patch_cnv3_h3, conv_patch_cnv3_f32, cp3::THREADS, cp3::LDS_BYTES}};

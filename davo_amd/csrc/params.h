@@ -75,22 +75,24 @@ __host__ __device__ inline int att_se_hidden(int a) { return (a == 4 || a == 7 |
 // every plane once, the target's included: its sum enters both source frames' descriptors (davo.py:1109)
 __host__ __device__ inline int att_se_frames(int a) { return (att_tgt_attended(a) || att_desc_depth(a)) ? 3 : 2; }
 
-// ---- label format (davo_set_label_format, include/davo_hip.h) ----------------------------------------------------------------
-// What the label maps of a context are made of: the reference's float32 (the default) or one byte per pixel.  The kernels that read
-// labels are templated on the element type (input_decode.h); the launchers take the format and pick the instantiation.
+// ---- input format (davo_set_label_format / davo_set_flow_format / davo_set_depth_format, include/davo_hip.h) -----------------
+// What the caller's planes of a context are made of.  Labels: the reference's float32 (the default) or one byte per pixel; flow
+// and depth: float32 (the default) or IEEE binary16 in the same layout.  The kernels that read raw inputs are templated on the
+// element types and decode through input_decode.h; the launchers take the InputFormat and pick the instantiation through
+// input_types.h, the one place that turns a format into element types.
 constexpr int LABELS_F32 = 0, LABELS_U8 = 1;
-
-// ---- flow format (davo_set_flow_format, include/davo_hip.h) ------------------------------------------------------------------
-// What the optical flow of a context is made of: float32 (the default) or IEEE binary16, same layout.  The kernels that read raw
-// flow are templated on the element type and widen through the fetches of input_decode.h; the launchers take the format and pick
-// the instantiation.
 constexpr int FLOW_F32 = 0, FLOW_F16 = 1;
-
-// ---- depth format (davo_set_depth_format, include/davo_hip.h) ----------------------------------------------------------------
-// What the depth planes of a context are made of: float32 (the default) or IEEE binary16, same layout.  The kernels that read raw
-// depth are templated on the element type and widen through depth_fetch4 (input_decode.h); the launchers take the format and pick
-// the instantiation.
 constexpr int DEPTH_F32 = 0, DEPTH_F16 = 1;
+struct InputFormat { int label = LABELS_F32, flow = FLOW_F32, depth = DEPTH_F32; };
+inline bool valid(const InputFormat& f) {
+    return (f.label == LABELS_F32 || f.label == LABELS_U8) && (f.flow == FLOW_F32 || f.flow == FLOW_F16) &&
+           (f.depth == DEPTH_F32 || f.depth == DEPTH_F16);
+}
+// bytes of one element of each plane kind (of a valid format)
+struct ElemBytes { int label, flow, depth; };
+inline ElemBytes element_bytes(const InputFormat& f) {
+    return ElemBytes{f.label == LABELS_U8 ? 1 : 4, f.flow == FLOW_F16 ? 2 : 4, f.depth == DEPTH_F16 ? 2 : 4};
+}
 
 // ---- pair selection (davo_set_pairs, include/davo_hip.h) -------------------------------------------------------------------
 // A window's two poses come from two independent evaluations of the PoseNN (davo.py:1456-1457): pair 0 = (tgt, src0), pair 1 =

@@ -28,7 +28,7 @@ __device__ __forceinline__ float wave_sum(float v) {
 // SE squeeze, pass 1: partial[b][s][chunk][2] = sum over the chunk's pixels of t(flow[b][s]).
 // grid (SQ_CHUNKS, selected sources, B), 256 threads; float4 = two pixels x (fx, fy).  Fixed chunking and a
 // fixed reduction tree -> bitwise reproducible run to run.  With one pair selected (sel, params.h) only that source's plane is read.
-// FT: the flow element, float or flow_f16 (input_decode.h); a thread's unit comes from one flow_fetch2.
+// FT: the flow element, float or in_f16 (input_decode.h); a thread's unit comes from one widen_fetch4.
 template <typename FT>
 __global__ __launch_bounds__(256) void se_squeeze_partial(const FT* __restrict__ flow, int HW,
                                                           int norm_flow, int abs_mode, int sel,
@@ -40,7 +40,7 @@ __global__ __launch_bounds__(256) void se_squeeze_partial(const FT* __restrict__
     const int beg = chunk * per, end = min(beg + per, nvec);
     float sx = 0.f, sy = 0.f;
     for (int i = beg + threadIdx.x; i < end; i += 256) {
-        float4 v = flow_fetch2(f + (size_t)i * 4);
+        float4 v = widen_fetch4(f + (size_t)i * 4);
         if (norm_flow) {
             v.x = (v.x - 0.32140523f) / 15.384229f; v.y = (v.y - 0.32140523f) / 15.384229f;
             v.z = (v.z - 0.32140523f) / 15.384229f; v.w = (v.w - 0.32140523f) / 15.384229f;
@@ -234,7 +234,7 @@ __device__ __forceinline__ void se_squeeze_excite_body(const FT* __restrict__ fl
     const int beg = chunk * per, end = min(beg + per, nvec);
     float sx = 0.f, sy = 0.f;
     for (int i = beg + threadIdx.x; i < end; i += 256) {
-        float4 q = flow_fetch2(f + (size_t)i * 4);
+        float4 q = widen_fetch4(f + (size_t)i * 4);
         if (v.norm_flow) {
             q.x = (q.x - 0.32140523f) / 15.384229f; q.y = (q.y - 0.32140523f) / 15.384229f;
             q.z = (q.z - 0.32140523f) / 15.384229f; q.w = (q.w - 0.32140523f) / 15.384229f;
@@ -401,8 +401,8 @@ __global__ __launch_bounds__(256) void se_class_squeeze(const uint8_t* __restric
 // float32 rounding only.  A thread takes four horizontally adjacent pixels (one 16-byte load) per step and adds them as
 // (x + y) + (z + w); then the fixed wave butterfly and a fixed tree over the four waves: one float32 word per record
 // (partial[b][frame][chunk][0]), bitwise the same run after run, no atomics on the sums.  depth is [B][3 file planes: src0, tgt,
-// src1][H][W] in the depth format DT (float or depth_f16, input_decode.h), 16-byte aligned; H*W is a multiple of 16.  A unit comes
-// from one depth_fetch4, so the chunking, the sum's order and every bit are the float32 format's.  FOLD: the workgroup that
+// src1][H][W] in the depth format DT (float or in_f16, input_decode.h), 16-byte aligned; H*W is a multiple of 16.  A unit comes
+// from one widen_fetch4, so the chunking, the sum's order and every bit are the float32 format's.  FOLD: the workgroup that
 // delivers the triplet's last record evaluates its three tables (se_squeeze_excite's protocol, pose_tail.h).
 template <bool FOLD, typename DT>
 __global__ __launch_bounds__(256) void se_depth_squeeze(const DT* __restrict__ depth, int HW, Variant v,
@@ -421,7 +421,7 @@ __global__ __launch_bounds__(256) void se_depth_squeeze(const DT* __restrict__ d
     const int beg = chunk * per, end = min(beg + per, nunits);
     float sum = 0.f;
     for (int i = beg + threadIdx.x; i < end; i += 256) {
-        const float4 q = depth_fetch4(dp + (size_t)i * 4);
+        const float4 q = widen_fetch4(dp + (size_t)i * 4);
         sum += (q.x + q.y) + (q.z + q.w);
     }
     __shared__ float red[4];
@@ -454,7 +454,7 @@ __global__ __launch_bounds__(256) void se_depth_squeeze(const DT* __restrict__ d
 // v0 variants (rgb only) leave the flow slots zero.
 // LT: the label format, float32 or bytes; a thread's four labels of a plane come from one label_fetch4 (input_decode.h).
 // FT: the flow format, float32 or binary16; a thread's four pixels of flow come from one flow_fetch4 (input_decode.h).
-// DSPLIT (att_source 13, the depth-split flow attention): per 4-pixel group one more depth_fetch4 (DT: the depth format, float32 or
+// DSPLIT (att_source 13, the depth-split flow attention): per 4-pixel group one more widen_fetch4 (DT: the depth format, float32 or
 // binary16, input_decode.h), of the depth plane of the source frame the label map belongs to (file plane 0 or 2), and each pixel's class is looked up in the near table `tab' or the far table
 // `ds.tab_far' by att_lookup_split (input_decode.h, with DepthSplit); everything else is the same code.  The target's map is ones.
 template <int LD, bool DSPLIT, typename LT, typename FT, typename DT>
@@ -493,7 +493,7 @@ __device__ __forceinline__ void mask_pack_body(const uint8_t* __restrict__ img, 
     // -no_segmask (davo.py:1387), the tgt frame unless static_all (davo.py:1394,1411).
     float as[4] = {1.f, 1.f, 1.f, 1.f};
     if (DSPLIT) {
-        const float4 dp = depth_fetch4(ds.depth + ((size_t)b * 3 + (s ? 2 : 0)) * H * W + pix);
+        const float4 dp = widen_fetch4(ds.depth + ((size_t)b * 3 + (s ? 2 : 0)) * H * W + pix);
         const float* far_s = ds.tab_far + ((size_t)b * 3 + 1 + s) * NCLS;
         as[0] = att_lookup_split(tab_s, far_s, ds.thr, dp.x, sg.id[0]); as[1] = att_lookup_split(tab_s, far_s, ds.thr, dp.y, sg.id[1]);
         as[2] = att_lookup_split(tab_s, far_s, ds.thr, dp.z, sg.id[2]); as[3] = att_lookup_split(tab_s, far_s, ds.thr, dp.w, sg.id[3]);

@@ -21,7 +21,7 @@
 namespace davo {
 
 // grid (items, selected sources, B), 256 threads.  A row of an item is cut into units: one pixel where the row's first column
-// is odd, then pairs of pixels on even columns (one flow_fetch2: W is a multiple of 4, so an even column is a 16-byte boundary of a
+// is odd, then pairs of pixels on even columns (one widen_fetch4: W is a multiple of 4, so an even column is a 16-byte boundary of a
 // float32 plane, an 8-byte one of a binary16 plane), then one pixel where a column is left over - a pair never straddles a cell
 // edge.  Unit u of the item goes to thread u % 256; a thread adds its units in order, then se_squeeze_partial's fixed tree.
 template <typename FT>
@@ -40,7 +40,7 @@ __global__ __launch_bounds__(256) void se_pool_squeeze(const FT* __restrict__ fl
         const int row = u / nu, k = u - row * nu;
         const size_t rowoff = (size_t)(r.x + row) * W;
         if (k >= head && k < head + npair) {
-            const float4 q = flow_fetch2(f + (rowoff + xa + 2 * (k - head)) * 2);
+            const float4 q = widen_fetch4(f + (rowoff + xa + 2 * (k - head)) * 2);
             sx += se_flow_transform(q.x, 0, v) + se_flow_transform(q.z, 0, v);
             sy += se_flow_transform(q.y, 1, v) + se_flow_transform(q.w, 1, v);
         } else {

@@ -43,12 +43,11 @@ inline FramePlan frame_plan(int N, int sel, int att_source) {
     p.flow[1] = s1 ? 2 : 1;
     return p;
 }
-// bytes that cross the link for such a batch (label_bytes: 4 or 1 per pixel; flow_bytes: 4 or 2 per component, float32 or binary16;
-// depth_bytes: 4 or 2 per pixel, float32 or binary16)
-inline long long frame_plan_bytes(const FramePlan& p, int N, int H, int W, int label_bytes, int flow_bytes = 4, int depth_bytes = 4) {
+// bytes that cross the link for such a batch (e: the element sizes of the batch's input format, params.h)
+inline long long frame_plan_bytes(const FramePlan& p, int N, int H, int W, const ElemBytes& e) {
     const long long HW = (long long)H * W;
-    return (p.img[1] - p.img[0]) * HW * 3 + (long long)N * (p.flow[1] - p.flow[0]) * HW * 2 * flow_bytes +
-           (p.seg[1] - p.seg[0]) * HW * label_bytes + (p.depth[1] - p.depth[0]) * HW * depth_bytes;
+    return (p.img[1] - p.img[0]) * HW * 3 + (long long)N * (p.flow[1] - p.flow[0]) * HW * 2 * e.flow +
+           (p.seg[1] - p.seg[0]) * HW * e.label + (p.depth[1] - p.depth[0]) * HW * e.depth;
 }
 
 struct GatherArgs {
@@ -89,9 +88,9 @@ __device__ __forceinline__ void gather_copy(const uint8_t* __restrict__ src, uin
     }
 }
 
-// LT: the label element (float or uint8_t, davo_set_label_format); FT: the flow element (float or flow_f16, davo_set_flow_format) -
+// LT: the label element (float or uint8_t, davo_set_label_format); FT: the flow element (float or in_f16, davo_set_flow_format) -
 // a flow plane is 2 H W of them, a whole number of 16-byte vectors in either format (H W is a multiple of 16); DT: the depth
-// element (float or depth_f16, davo_set_depth_format) - a depth plane is H W of them, a whole number of vectors too
+// element (float or in_f16, davo_set_depth_format) - a depth plane is H W of them, a whole number of vectors too
 template <typename LT, typename FT, typename DT>
 __global__ __launch_bounds__(256) void window_gather(GatherArgs a) {
     const size_t n = blockIdx.y, HW = (size_t)a.H * a.W;

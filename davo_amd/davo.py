@@ -153,54 +153,50 @@ class Engine:
             except Exception:
                 self.close()
                 raise
-        if labels != "f32":
-            try:
-                self.set_label_format(labels)
-            except Exception:
-                self.close()
-                raise
-        if flow != "f32":
-            try:
-                self.set_flow_format(flow)
-            except Exception:
-                self.close()
-                raise
-        if depth != "f32":
-            try:
-                self.set_depth_format(depth)
-            except Exception:
-                self.close()
-                raise
+        try:
+            for attr, value in (("labels", labels), ("flow", flow), ("depth", depth)):
+                if value != "f32":
+                    self._set_format(attr, value)
+        except Exception:
+            self.close()
+            raise
 
-    def set_depth_format(self, depth):
-        """Select the depth format, "f32" or "f16" (include/davo_hip.h: davo_set_depth_format): before the first call that takes
-        inputs, ValueError afterwards.  From then on every depth array must have that dtype; nothing is converted silently."""
-        self._check(self._L.davo_set_depth_format(self._ctx, DEPTH_FORMATS[check_depth_format(depth)]))
-        self.depth = depth
+    # the engine attribute of each plane kind -> (the C setter, its values, the name check)
+    _FORMATS = {"labels": ("davo_set_label_format", LABEL_FORMATS, check_label_format),
+                "flow": ("davo_set_flow_format", FLOW_FORMATS, check_flow_format),
+                "depth": ("davo_set_depth_format", DEPTH_FORMATS, check_depth_format)}
 
-    def set_flow_format(self, flow):
-        """Select the flow format, "f32" or "f16" (include/davo_hip.h: davo_set_flow_format): before the first call that takes
-        inputs, ValueError afterwards.  From then on every flow array must have that dtype; nothing is converted silently."""
-        self._check(self._L.davo_set_flow_format(self._ctx, FLOW_FORMATS[check_flow_format(flow)]))
-        self.flow = flow
-
-    def _flow_arg(self, flow):
-        """The flow of a batch as the entry points take it: C-contiguous, of the engine's format.  A float16 array handed to a
-        float32 engine, or anything but float16 to a binary16 engine, is a ValueError."""
-        is_f16 = np.asarray(flow).dtype == np.float16
-        if self.flow == "f16":
-            if not is_f16:
-                raise ValueError("this engine takes float16 flow (flow='f16'), got dtype %s: convert with davo_amd.flow_to_f16" % np.asarray(flow).dtype)
-            return np.ascontiguousarray(flow)
-        if is_f16:
-            raise ValueError("this engine takes float32 flow (flow='f32'), got float16: create it with flow='f16'")
-        return np.ascontiguousarray(flow, np.float32)
+    def _set_format(self, attr, value):
+        """The three format setters' one body (include/davo_hip.h: davo_set_label_format / _flow_format / _depth_format): before
+        the first call that takes inputs, ValueError afterwards.  From then on every array of that kind must have the format's
+        dtype; nothing is converted silently."""
+        setter, values, check = self._FORMATS[attr]
+        self._check(getattr(self._L, setter)(self._ctx, values[check(value)]))
+        setattr(self, attr, value)
 
     def set_label_format(self, labels):
-        """Select the label format, "f32" or "u8" (include/davo_hip.h: davo_set_label_format): before the first call that takes
-        inputs, ValueError afterwards.  From then on every label array must have that dtype; nothing is converted silently."""
-        self._check(self._L.davo_set_label_format(self._ctx, LABEL_FORMATS[check_label_format(labels)]))
-        self.labels = labels
+        """Select the label format, "f32" or "u8" (see _set_format)."""
+        self._set_format("labels", labels)
+
+    def set_flow_format(self, flow):
+        """Select the flow format, "f32" or "f16" (see _set_format)."""
+        self._set_format("flow", flow)
+
+    def set_depth_format(self, depth):
+        """Select the depth format, "f32" or "f16" (see _set_format)."""
+        self._set_format("depth", depth)
+
+    def _f16_arg(self, a, noun):
+        """An array of the plane kind ``noun`` ("flow" | "depth") as the entry points take it: C-contiguous, of the engine's format
+        of that kind.  A float16 array handed to a float32 engine, or anything but float16 to a binary16 engine, is a ValueError."""
+        is_f16 = np.asarray(a).dtype == np.float16
+        if getattr(self, noun) == "f16":
+            if not is_f16:
+                raise ValueError("this engine takes float16 %s (%s='f16'), got dtype %s: convert with davo_amd.%s_to_f16" % (noun, noun, np.asarray(a).dtype, noun))
+            return np.ascontiguousarray(a)
+        if is_f16:
+            raise ValueError("this engine takes float32 %s (%s='f32'), got float16: create it with %s='f16'" % (noun, noun, noun))
+        return np.ascontiguousarray(a, np.float32)
 
     def _label_arg(self, seg):
         """The label maps of a batch as the entry points take them: C-contiguous [B,3,H,W,1] of the engine's format.  A byte
@@ -241,7 +237,7 @@ class Engine:
         """The depth planes of a batch as the entry points take them (of the engine's depth format and of ``shape``: [B,3,H,W,1]
         in file order src0, tgt, src1, davo.py:991-996, or the frame layout's [N+2,H,W,1]), or None for a variant that reads none
         (a depth array handed to such a variant is ignored, as the reference ignores its depth input there).  A float16 array
-        handed to a float32 engine, or anything but float16 to a binary16 engine, is a ValueError.  ``strict``: see _contiguous."""
+        handed to a float32 engine, or anything but float16 to a binary16 engine, is a ValueError (_f16_arg).  ``strict``: see _contiguous."""
         if not self.cfg.needs_depth:
             return None
         if strict and not _is_ready(depth, DEPTH_DTYPES[self.depth]):
@@ -249,15 +245,7 @@ class Engine:
                              % (strict, DEPTH_DTYPES[self.depth]))
         if depth is None:
             raise ValueError("%s and depth inputs are all required for version `%s'" % (names, self.cfg.version))
-        is_f16 = np.asarray(depth).dtype == np.float16
-        if self.depth == "f16":
-            if not is_f16:
-                raise ValueError("this engine takes float16 depth (depth='f16'), got dtype %s: convert with davo_amd.depth_to_f16" % np.asarray(depth).dtype)
-            depth = np.ascontiguousarray(depth)
-        elif is_f16:
-            raise ValueError("this engine takes float32 depth (depth='f32'), got float16: create it with depth='f16'")
-        else:
-            depth = np.ascontiguousarray(depth, np.float32)
+        depth = self._f16_arg(depth, "depth")
         if depth.shape != shape:
             raise ValueError("depth shape %s != %s" % (depth.shape, shape))
         return depth
@@ -270,7 +258,7 @@ class Engine:
             if strict:
                 raise ValueError("%s(hold > 0) needs C-contiguous uint8 / %s / %s arrays (a converted copy would not outlive the call)"
                                  % (strict, FLOW_DTYPES[self.flow], LABEL_DTYPES[self.labels]))
-            pixels, flow, seg = np.ascontiguousarray(pixels, np.uint8), self._flow_arg(flow), label_arg(seg)
+            pixels, flow, seg = np.ascontiguousarray(pixels, np.uint8), self._f16_arg(flow, "flow"), label_arg(seg)
         return pixels, flow, seg
 
     def _window_batch(self, img, flow, seg, depth, strict=None, calibration=False):

@@ -43,31 +43,20 @@ def depth_path(dump_dir, seq, tgt_idx):
     return os.path.join(dump_dir, "%.2d" % seq, "%.6d" % tgt_idx) + "-monodepth2_depth.npy"        # test_kitti_pose.py:48
 
 
-def _labels_as_u8(a, path):
-    """A label file's array as bytes: uint8 as it is, float32 by labels_to_u8; any other dtype is an error that names the file."""
-    if a.dtype == np.uint8:
+# A narrow slot format of one plane kind: the dtype its slots hold, the rule that converts a float32 file, the words of the error
+_Narrow = collections.namedtuple("_Narrow", "dtype convert what accepted")
+_LABELS_U8 = _Narrow(np.dtype(np.uint8), labels_to_u8, "labels", "a label file is float32 or uint8")
+_FLOW_F16 = _Narrow(np.dtype(np.float16), flow_to_f16, "flow", "a flow file is float32 or float16")
+_DEPTH_F16 = _Narrow(np.dtype(np.float16), depth_to_f16, "depth", "a depth file is float32 or float16")
+
+
+def _file_as(a, path, narrow):
+    """A file's array in the narrow format: of its dtype as it is, float32 by its rule; any other dtype is an error that names the file."""
+    if a.dtype == narrow.dtype:
         return a
     if a.dtype == np.float32:
-        return labels_to_u8(a)
-    raise ValueError("%s holds %s labels: a label file is float32 or uint8" % (path, a.dtype))
-
-
-def _flow_as_f16(a, path):
-    """A flow file's array as binary16: float16 as it is, float32 by flow_to_f16; any other dtype is an error that names the file."""
-    if a.dtype == np.float16:
-        return a
-    if a.dtype == np.float32:
-        return flow_to_f16(a)
-    raise ValueError("%s holds %s flow: a flow file is float32 or float16" % (path, a.dtype))
-
-
-def _depth_as_f16(a, path):
-    """A depth file's array as binary16: float16 as it is, float32 by depth_to_f16; any other dtype is an error that names the file."""
-    if a.dtype == np.float16:
-        return a
-    if a.dtype == np.float32:
-        return depth_to_f16(a)
-    raise ValueError("%s holds %s depth: a depth file is float32 or float16" % (path, a.dtype))
+        return narrow.convert(a)
+    raise ValueError("%s holds %s %s: %s" % (path, a.dtype, narrow.what, narrow.accepted))
 
 
 def depth_mode(depth):
@@ -95,31 +84,29 @@ def load_window(dump_dir, seq, tgt_idx, H, W, depth=False, labels="f32", flow="f
         raise ValueError("%s is %s, expected %s" % (jpg, img.shape, (H, 3 * W, 3)))
     # memory-mapped: the one copy of these arrays is the worker's write into its slot of the batch buffer
     if flow_fmt == "f16":
-        flow = _flow_as_f16(np.load(flo, mmap_mode="r"), flo).reshape(4, H, W, 2)
+        flow = _file_as(np.load(flo, mmap_mode="r"), flo, _FLOW_F16).reshape(4, H, W, 2)
     else:
         flow = np.load(flo, mmap_mode="r").astype(np.float32, copy=False).reshape(4, H, W, 2)
     if labels == "u8":
-        seg = _labels_as_u8(np.load(sg, mmap_mode="r"), sg).reshape(3, H, W, 1)
+        seg = _file_as(np.load(sg, mmap_mode="r"), sg, _LABELS_U8).reshape(3, H, W, 1)
     else:
         seg = np.load(sg, mmap_mode="r").astype(np.float32, copy=False).reshape(3, H, W, 1)
     if depth_fmt == "f16":
         dp = depth_path(dump_dir, seq, tgt_idx)
-        return img, flow, seg, _depth_as_f16(np.load(dp, mmap_mode="r"), dp).reshape(3, H, W, 1)
+        return img, flow, seg, _file_as(np.load(dp, mmap_mode="r"), dp, _DEPTH_F16).reshape(3, H, W, 1)
     if depth_fmt == "f32":
         dep = np.load(depth_path(dump_dir, seq, tgt_idx), mmap_mode="r").astype(np.float32, copy=False).reshape(3, H, W, 1)
         return img, flow, seg, dep
     return img, flow, seg
 
 
-def _read_npy_into(path, dst, planes=None, labels=False, flow16=False, depth16=False):
+def _read_npy_into(path, dst, planes=None, narrow=None):
     """Read a C-ordered .npy of dst's dtype and size straight into dst (no intermediate array); anything else
     goes through np.load + cast.  ``planes``: indices along the first axis that are wanted — the others are skipped
     in the file (seek) and left as they are in dst (the path reads flow planes 0,1 and the source frames' label maps only:
-    davo.py:978-982,998-1004, so 1.3 of a window's 2.3 MB never have to leave the page cache).  ``labels``: dst is a byte label
-    slot - a uint8 file is read straight into it like any file of dst's dtype, a float32 file is converted plane by plane with
-    labels_to_u8, any other dtype raises.  ``flow16``: dst is a binary16 flow slot - a float16 file is read straight into it, a
-    float32 file is converted plane by plane with flow_to_f16, any other dtype raises.  ``depth16``: the same for a binary16 depth
-    slot and depth_to_f16."""
+    davo.py:978-982,998-1004, so 1.3 of a window's 2.3 MB never have to leave the page cache).  ``narrow``: dst is a slot of that
+    narrow format (_LABELS_U8, _FLOW_F16, _DEPTH_F16) - a file of its dtype is read straight into it like any file of dst's dtype,
+    a float32 file is converted plane by plane with the format's rule, any other dtype raises."""
     with open(path, "rb") as f:
         major, _ = np.lib.format.read_magic(f)
         shape, fortran, dtype = (np.lib.format.read_array_header_1_0 if major == 1 else np.lib.format.read_array_header_2_0)(f)
@@ -135,20 +122,10 @@ def _read_npy_into(path, dst, planes=None, labels=False, flow16=False, depth16=F
                     raise ValueError("%s is truncated" % path)
             return
     a = np.load(path)
-    if labels:                                            # a byte label slot: the file's own bytes, or labels_to_u8 of its floats
+    if narrow is not None:                                # a narrow slot: the file's own elements, or the format's rule on its floats
         a = a.reshape(dst.shape)
         for k in (range(len(dst)) if planes is None else planes):
-            dst[k] = _labels_as_u8(a[k], path)
-        return
-    if flow16:                                            # a binary16 flow slot: the file's own halves, or flow_to_f16 of its floats
-        a = a.reshape(dst.shape)
-        for k in (range(len(dst)) if planes is None else planes):
-            dst[k] = _flow_as_f16(a[k], path)
-        return
-    if depth16:                                           # a binary16 depth slot: the file's own halves, or depth_to_f16 of its floats
-        a = a.reshape(dst.shape)
-        for k in (range(len(dst)) if planes is None else planes):
-            dst[k] = _depth_as_f16(a[k], path)
+            dst[k] = _file_as(a[k], path, narrow)
         return
     a = a.astype(dst.dtype, copy=False).reshape(dst.shape)
     if planes is None:
@@ -213,12 +190,12 @@ def load_window_into(dump_dir, seq, tgt_idx, H, W, img, flow, seg, decoder=None,
     if a.shape != (H, 3 * W, 3):
         raise ValueError("%s is %s, expected %s" % (jpg, a.shape, (H, 3 * W, 3)))
     img[...] = a
-    _read_npy_into(flo, flow, flow_planes, flow16=flow_fmt == "f16")
-    _read_npy_into(sg, seg, seg_planes, labels=labels == "u8")
+    _read_npy_into(flo, flow, flow_planes, _FLOW_F16 if flow_fmt == "f16" else None)
+    _read_npy_into(sg, seg, seg_planes, _LABELS_U8 if labels == "u8" else None)
     if depth is not None:                                 # the slot's dtype says the depth format: float16 = binary16 planes
         if depth.dtype not in (DEPTH_DTYPES["f32"], DEPTH_DTYPES["f16"]):
             raise ValueError("a depth slot is float32 or float16, got %s" % depth.dtype)
-        _read_npy_into(depth_path(dump_dir, seq, tgt_idx), depth, depth16=depth.dtype == np.float16)
+        _read_npy_into(depth_path(dump_dir, seq, tgt_idx), depth, narrow=_DEPTH_F16 if depth.dtype == np.float16 else None)
 
 
 def count_frames(dump_dir, seq, seq_length=3):
