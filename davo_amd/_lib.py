@@ -53,12 +53,14 @@ EXPORTS = (
     "davo_set_flow_format", "davo_get_flow_format", "davo_frames_plan_fmt", "davo_pool_plan",
     "davo_set_flip", "davo_get_flip",
     "davo_set_depth_format", "davo_get_depth_format", "davo_frames_plan_fmt2",
+    "davo_set_posenn_heads",
 )
 COMM_ID_BYTES = 128
 LABELS_F32, LABELS_U8 = 0, 1          # DAVO_LABELS_F32, DAVO_LABELS_U8 (davo_set_label_format)
 FLOW_F32, FLOW_F16 = 0, 1             # DAVO_FLOW_F32, DAVO_FLOW_F16 (davo_set_flow_format)
 DEPTH_F32, DEPTH_F16 = 0, 1           # DAVO_DEPTH_F32, DAVO_DEPTH_F16 (davo_set_depth_format)
 POSENN_PAIRS, POSENN_TRIPLET = 0, 1   # DAVO_POSENN_PAIRS, DAVO_POSENN_TRIPLET (davo_set_posenn_topology)
+POSENN_HEADS_DECOUPLED, POSENN_HEADS_COUPLED = 0, 1   # DAVO_POSENN_HEADS_DECOUPLED, DAVO_POSENN_HEADS_COUPLED (davo_set_posenn_heads)
 
 
 class DavoVariant(ctypes.Structure):
@@ -187,6 +189,7 @@ def _load():
     L.davo_create.argtypes = [ctypes.POINTER(vp), i, i, i, i, ctypes.POINTER(DavoVariant)]
     L.davo_set_posenn_se.argtypes = [vp, i]
     L.davo_set_posenn_topology.argtypes = [vp, i]
+    L.davo_set_posenn_heads.argtypes = [vp, i]
     L.davo_load_weight.argtypes = [vp, ctypes.c_char_p, f32p, ctypes.POINTER(ctypes.c_int64), i]
     L.davo_weights_missing.argtypes = [vp]
     L.davo_forward.argtypes = [vp, i, vp, vp, vp, vp]

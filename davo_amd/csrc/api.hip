@@ -80,7 +80,7 @@ int add_slot(davo_ctx* c) {
     const size_t NB = 2 * (size_t)c->max_batch;
     Slot s;
     HIP_TRY(c, stream_create(&s.stream));
-    for (int i = 0; i < 7; ++i) HIP_TRY(c, dev_alloc(&s.d_act[i], NB * c->act_floats_per_img[i]));
+    for (int i = 0; i < 7; ++i) HIP_TRY(c, dev_alloc(&s.d_act[i], NB * c->slot_floats_per_img[i]));      // the decoupled widths, whatever the heads are now
     HIP_TRY(c, dev_alloc(&s.d_packed, NB * (size_t)c->H * c->W * 10));
     // squeeze partials: se_flow [B][2 sources][SQ_CHUNKS][2] floats, the class-table sources [B][3 frames][SQ_CHUNKS][SQ_REC] words
     // (the pooled flow-attention variants: [B][2 sources][work items][2] floats)
@@ -147,6 +147,7 @@ int davo_create(davo_ctx** out, int device, int H, int W, int max_batch, const d
     for (int i = 0; i < 7; ++i) {
         c->act_ch[i] = ch[i];
         c->act_floats_per_img[i] = px[i] * ch[i];
+        c->slot_floats_per_img[i] = px[i] * ch[i];
     }
     if (att_pooled(c->v.att_source)) { int rc = build_pool_plan(c); if (rc) return rc; }      // the slots' squeeze partials are sized by it
     { int rc = add_slot(c); if (rc) return rc; }
@@ -166,13 +167,15 @@ int davo_set_posenn_se(davo_ctx* c, int mode) {
     if (mode && c->v.att_source != 0)
         return fail(c, DAVO_ERR_INVALID, "the feature-attention PoseNN (`-se_insert') runs with att_source 0 (`-no_segmask') only, got %d", c->v.att_source);
     if (mode && triplet(c)) return fail(c, DAVO_ERR_INVALID, "the three-frame PoseNN (davo_set_posenn_topology) has no feature-attention form");
+    if (mode && coupled(c)) return fail(c, DAVO_ERR_INVALID, "the coupled PoseNN (davo_set_posenn_heads) has no feature-attention form");
     HIP_TRY(c, hipSetDevice(c->device));
     c->posenn_se = mode;
     // the heads read different inputs now: cnv6 becomes one group per head, the grouped path cnv7 runs on (forward.hip)
     const int c6 = c->v.cnv6_out;
     if (mode) init_layer(c->L[5], "cnv6", 3, 1, 2, 256, c6, 2);
+    else if (coupled(c)) init_coupled_head(c->L, c6);      // mode 0 on a coupled context: its own one-group cnv6
     else init_layer(c->L[5], "cnv6", 3, 1, 2, 256, 2 * c6, 1);
-    c->needed = needed_names(c->v, mode);
+    c->needed = needed_names(c->v, mode, coupled(c));
     for (Slot& s : c->slots) {
         if (mode) { int rc = alloc_se_workspace(c, &s); if (rc) return rc; }
         else s.se.reset();
@@ -198,10 +201,50 @@ int davo_set_posenn_topology(davo_ctx* c, int topology) {
         if (c->impl != 0) return fail(c, DAVO_ERR_INVALID, "the three-frame PoseNN has no direct-convolution form: davo_set_impl(ctx, 1) is set");
         if (c->fx_on || c->heat)
             return fail(c, DAVO_ERR_INVALID, "the three-frame PoseNN has no feature or heat export: switch the exports off first");
+        if (coupled(c))
+            return fail(c, DAVO_ERR_INVALID, "the three-frame coupled PoseNN (couple_net_v0_dilation) is not built: davo_set_posenn_heads(ctx, DAVO_POSENN_HEADS_COUPLED) is set");
     }
     c->topology = topology;
     // cnv1 reads 16 packed channels (prologue.h, mask_pack3) instead of 8; every other layer is the same, on B images instead of 2 B
     init_layer(c->L[0], "cnv1", 7, 2, 1, topology == DAVO_POSENN_TRIPLET ? 16 : 8, 16, 1);
+    c->last_slot = 0;
+    return DAVO_OK;
+}
+
+int davo_set_posenn_heads(davo_ctx* c, int heads) {
+    if (!c) return DAVO_ERR_INVALID;
+    if (heads != DAVO_POSENN_HEADS_DECOUPLED && heads != DAVO_POSENN_HEADS_COUPLED)
+        return fail(c, DAVO_ERR_INVALID, "heads must be DAVO_POSENN_HEADS_DECOUPLED (0) or DAVO_POSENN_HEADS_COUPLED (1), got %d", heads);
+    if (!c->weights.empty() || c->forward_seen)
+        return fail(c, DAVO_ERR_INVALID, "davo_set_posenn_heads must be called before the first davo_load_weight and the first forward "
+                    "(it changes the head's variables and the layout of cnv6, cnv7 and pred)");
+    if (heads == DAVO_POSENN_HEADS_COUPLED) {
+        if (triplet(c))
+            return fail(c, DAVO_ERR_INVALID, "the three-frame coupled PoseNN (couple_net_v0_dilation) is not built: davo_set_posenn_topology(ctx, DAVO_POSENN_TRIPLET) is set");
+        if (c->posenn_se)
+            return fail(c, DAVO_ERR_INVALID, "the coupled PoseNN has no feature-attention form: davo_set_posenn_se(ctx, 1) is set");
+        if (c->fx_on || c->heat)
+            return fail(c, DAVO_ERR_INVALID, "the coupled PoseNN has no feature or heat export: switch the exports off first");
+    }
+    c->heads = heads;
+    const int c6 = c->v.cnv6_out;
+    // coupled: cnv6 one GEMM of c6 columns, cnv7 one group over all of them; the activations are [images][H2][W2][c6] and
+    // [images][H3][W3][256].  The slots' buffers were sized for the decoupled widths (2 c6 and 512 channels) and the pose head's partial
+    // sums for two heads of three columns: the coupled tensors must fit them
+    if (heads == DAVO_POSENN_HEADS_COUPLED) init_coupled_head(c->L, c6);
+    else {
+        init_layer(c->L[5], "cnv6", 3, 1, 2, 256, c->posenn_se ? c6 : 2 * c6, c->posenn_se ? 2 : 1);
+        init_layer(c->L[6], "cnv7", 3, 2, 1, c6, 256, 2);
+    }
+    const int ch5 = heads == DAVO_POSENN_HEADS_COUPLED ? c6 : 2 * c6, ch7 = heads == DAVO_POSENN_HEADS_COUPLED ? 256 : 512;
+    const size_t px5 = (size_t)c->H2 * c->W2, px7 = (size_t)c->H3 * c->W3;
+    static_assert(PH_SPLIT * 6 <= 2 * PH_SPLIT * 3, "the slots' pose partials [images][2][PH_SPLIT][3] hold the coupled head's [images][PH_SPLIT][6]");
+    if (px5 * ch5 > c->slot_floats_per_img[5] || px7 * ch7 > c->slot_floats_per_img[6])      // what add_slot allocates, for every slot built before or after this call
+        return fail(c, DAVO_ERR_INVALID, "internal: cnv6 / cnv7 of %d / %d channels do not fit the slots' buffers (%zu / %zu floats per image)", ch5, ch7,
+                    c->slot_floats_per_img[5], c->slot_floats_per_img[6]);
+    c->act_ch[5] = ch5; c->act_floats_per_img[5] = px5 * ch5;
+    c->act_ch[6] = ch7; c->act_floats_per_img[6] = px7 * ch7;
+    c->needed = needed_names(c->v, c->posenn_se, coupled(c));
     c->last_slot = 0;
     return DAVO_OK;
 }

@@ -92,7 +92,9 @@ typedef __attribute__((address_space(3))) void lptr_t;
 // their order per accumulator are unchanged: results are bit-identical to RATE = 0.
 // The kernel body takes its workgroup id as parameters (wg_x of nwg_x, group wg_y) so that conv_igemm_h3_mainrem below can
 // run two tile shapes of one layer in ONE launch; conv_igemm_h3 itself passes blockIdx / gridDim.
-template <int KS, int STRIDE, int WM, int WN, int TM, int TN, int LAYER, bool DMA, bool SMALLC, bool M16 = false, int NSTG = 2, int RATE = 0>
+// NC: pred columns of the fused pose head (y_mode 2): 3 = one head per group; 6 = the coupled network's one head of six columns, a
+// one-group layer whose epilogue forms the products of pred columns 3..5 as a second "virtual head" beside those of columns 0..2
+template <int KS, int STRIDE, int WM, int WN, int TM, int TN, int LAYER, bool DMA, bool SMALLC, bool M16 = false, int NSTG = 2, int RATE = 0, int NC = 3>
 __device__ __forceinline__ void conv_igemm_h3_body(const ConvParamsH& p, const int wg_x, const int nwg_x, const int wg_y) {
     using T = TileH<WM, WN, TM, TN, NSTG>;
     using TX = TileX<WM, WN, TM, TN, NSTG, (RATE > 0 ? RATE : 1)>;
@@ -700,6 +702,11 @@ __device__ __forceinline__ void conv_igemm_h3_body(const ConvParamsH& p, const i
         const int img0 = row0 / p.pose_P;
         const int split_row = (img0 + 1) * p.pose_P - row0;          // tile rows >= split_row: next image
         float q[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+        // NC == 6 (the coupled head, one group): the two image slots times pred columns 3..5, from the same column sums.  pose_w is
+        // [2][Cout][3] there - columns 0..2, then columns 3..5 - and the partial sums take the two-head layout, "head" 1 = columns 3..5,
+        // so pose_tile_sum, pose_from_tiles and pose_from_tiles_tail read component hk = 0..5 where they read head hk / 3's column hk % 3
+        float qb[NC == 6 ? 6 : 1] = {};
+        (void)qb;
 #ifdef DAVO_POSE_DEBUG
         float dbg_v[12];
 #endif
@@ -762,6 +769,12 @@ __device__ __forceinline__ void conv_igemm_h3_body(const ConvParamsH& p, const i
                 q[0] = q01.x; q[1] = q01.y; q[2] = q23.x; q[3] = q23.y; q[4] = q45.x; q[5] = q45.y;
             }
 #endif
+            if constexpr (NC == 6) {      // six more scalar products (docs/F16X3_NUMERICS.md: the build refuses a packed form of them)
+                const float* wpb = wp + (long)p.Cout * 3;
+                const float v0 = n < p.Cout ? wpb[0] : 0.f, v1 = n < p.Cout ? wpb[1] : 0.f, v2 = n < p.Cout ? wpb[2] : 0.f;
+                qb[0] += s0 * v0; qb[1] += s0 * v1; qb[2] += s0 * v2;
+                qb[3] += s1 * v0; qb[4] += s1 * v1; qb[5] += s1 * v2;
+            }
 #ifdef DAVO_POSE_DEBUG
             if constexpr (NCG == 2) { if (jj == 0) { dbg_v[10] = q[4]; dbg_v[11] = q[5]; } dbg_v[jj * 5 + 0] = s0; dbg_v[jj * 5 + 1] = s1; dbg_v[jj * 5 + 2] = w0; dbg_v[jj * 5 + 3] = w1; dbg_v[jj * 5 + 4] = w2; }
 #endif
@@ -787,11 +800,23 @@ __device__ __forceinline__ void conv_igemm_h3_body(const ConvParamsH& p, const i
                 asm volatile("" : "+v"(q[k]));
 #endif
             }
+        if constexpr (NC == 6) {
+#pragma unroll
+            for (int k = 0; k < 6; ++k)
+#pragma unroll
+                for (int o = 32; o > 0; o >>= 1) qb[k] += __shfl_down(qb[k], o, 64);
+        }
         __syncthreads();                                             // every wave is done with the staging slots
-        float* red = reinterpret_cast<float*>(smem_h);               // [waves][6]
+        float* red = reinterpret_cast<float*>(smem_h);               // [waves][6]; NC == 6: columns 3..5 in a second block 64 floats on
         if (lane == 0)
 #pragma unroll
             for (int k = 0; k < 6; ++k) red[wid * 6 + k] = q[k];
+        if constexpr (NC == 6) {
+            static_assert(WM * WN * 6 <= 64 && WM * WN * 64 >= 128, "the second block of wave sums; its six adders are threads 64..69");
+            if (lane == 0)
+#pragma unroll
+                for (int k = 0; k < 6; ++k) red[64 + wid * 6 + k] = qb[k];
+        }
         __syncthreads();
         if (tid < 6) {
             float t = 0.f;
@@ -800,8 +825,18 @@ __device__ __forceinline__ void conv_igemm_h3_body(const ConvParamsH& p, const i
             if (p.pose_counter) { agent_store(dst, t); agent_stores_done(); }      // read by the launch's last workgroup
             else *dst = t;
         }
+        if constexpr (NC == 6) {
+            if (tid >= 64 && tid < 70) {                             // "head" 1 of the partial sums: pred columns 3..5
+                const int k = tid - 64;
+                float t = 0.f;
+                for (int w = 0; w < WM * WN; ++w) t += red[64 + w * 6 + k];
+                float* dst = p.pose_partial + (((long)p.pose_mt + (mtile - p.mtile0)) * p.ntiles_n + ntile) * 6 + k;
+                if (p.pose_counter) { agent_store(dst, t); agent_stores_done(); }
+                else *dst = t;
+            }
+        }
         // the workgroup that finishes last adds the tiles in fixed order and writes the poses (pose_tail.h)
-        if (p.pose_counter && last_workgroup(p.pose_counter, (unsigned)p.pose_total, reinterpret_cast<unsigned*>(red + 64))) pose_from_tiles_tail<WM * WN * 64>(p);
+        if (p.pose_counter && last_workgroup(p.pose_counter, (unsigned)p.pose_total, reinterpret_cast<unsigned*>(red + (NC == 6 ? 128 : 64)))) pose_from_tiles_tail<WM * WN * 64>(p);
         return;
     }
 
@@ -909,10 +944,11 @@ __device__ __forceinline__ void conv_igemm_h3_body(const ConvParamsH& p, const i
     if (p.y_mode == 0 && p.sk_counter) splitk_tail<WM * WN * 64, BMH, BNH>(p, mtile, ntile, reinterpret_cast<unsigned*>(smem_h));
 }
 
-template <int KS, int STRIDE, int WM, int WN, int TM, int TN, int LAYER, bool DMA, bool SMALLC, bool M16 = false, int NSTG = 2, int RATE = 0>
+template <int KS, int STRIDE, int WM, int WN, int TM, int TN, int LAYER, bool DMA, bool SMALLC, bool M16 = false, int NSTG = 2, int RATE = 0, int NC = 3>
 __global__ __launch_bounds__(WM * WN * 64, (WM * WN) >= 8 ? (WM * WN) / 4 : 2)
 void conv_igemm_h3(ConvParamsH p) {
-    conv_igemm_h3_body<KS, STRIDE, WM, WN, TM, TN, LAYER, DMA, SMALLC, M16, NSTG, RATE>(p, blockIdx.x, gridDim.x, blockIdx.y);
+    static_assert(NC == 3 || NC == 6, "pred columns of the fused pose head");
+    conv_igemm_h3_body<KS, STRIDE, WM, WN, TM, TN, LAYER, DMA, SMALLC, M16, NSTG, RATE, NC>(p, blockIdx.x, gridDim.x, blockIdx.y);
 }
 
 // Main launch (256x256 tiles, shared-tap staging) and remainder launch (128x128 tiles, three ring slots) of one layer as ONE

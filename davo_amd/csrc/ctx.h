@@ -235,8 +235,11 @@ struct davo_ctx {
     int posenn_se = 0;                         // davo_set_posenn_se: 0 none | 1 insert - an SE block on cnv5 ahead of each head's cnv6 (posenn_se.h); cnv6 is then a two-group layer
     int topology = DAVO_POSENN_PAIRS;          // davo_set_posenn_topology: DAVO_POSENN_TRIPLET = one (tgt, src0, src1) image per window through cnv1..cnv7 (cnv1 at 16 packed
                                                // channels, B images a batch), pred six columns wide, the unfused two-pass pose head (forward.hip)
+    int heads = DAVO_POSENN_HEADS_DECOUPLED;   // davo_set_posenn_heads: DAVO_POSENN_HEADS_COUPLED = couple_sharednet_v0_dilation - one cnv6 (256 -> c6, one group), one cnv7
+                                               // (c6 -> 256, one group, reads all of cnv6), pred six columns wide: fused into cnv7's f16x3 epilogue (NC = 6), else the
+                                               // two-pass pose head on a stored cnv7 (forward.hip)
     bool opt_patch_cnv1_t = true;              // three-frame PoseNN, f16x3: "patch_cnv1_t" - cnv1 from an LDS-staged 16-channel patch (conv_patch_cnv1t_h3) instead of the implicit GEMM at cin = 16
-    bool forward_seen = false;                 // a forward has been issued (davo_set_posenn_se and davo_set_posenn_topology are refused from then on)
+    bool forward_seen = false;                 // a forward has been issued (davo_set_posenn_se, davo_set_posenn_topology and davo_set_posenn_heads are refused from then on)
     davo::InputFormat fmt;                     // davo_set_{label,flow,depth}_format: what every `seg' / `flow' / `depth' argument points at, and what plane_bytes() sizes
     bool inputs_seen = false;                  // an entry point has taken inputs (davo_set_label_format, davo_set_flow_format and davo_set_depth_format are refused from then on)
     int impl = 0;
@@ -251,6 +254,7 @@ struct davo_ctx {
     bool pred_ready = false;                   // pose head kernels on the device (every mode)
     davo::ConvLayer L[7];                      // cnv1..cnv5, cnv6 (fused), cnv7 (grouped)
     davo::DevMem<float> d_wpred, d_bpred;
+    davo::DevMem<float> d_wpred_halves;        // coupled PoseNN: pred as [2][256][3], columns 0..2 then 3..5 - what cnv7's six-column fused epilogue reads (null otherwise)
     davo::DevMem<uint8_t> d_w1patch;           // cnv1 B fragments for conv_patch_cnv1_h3 (three-frame PoseNN: for conv_patch_cnv1t_h3)
     davo::DevMem<uint8_t> d_w2patch;           // cnv2 B fragments for conv_patch_cnv2_h3
     davo::DevMem<float> d_w1patch_f32, d_w2patch_f32, d_w3patch_f32;      // float32 mode: cnv1 / cnv2 / cnv3 weights in the patch kernels' register order (conv_patch_f32.h)
@@ -259,7 +263,9 @@ struct davo_ctx {
     // geometry
     int H1, W1, H2, W2, H3, W3;
     davo::DevMem<float> d_zeros;
-    size_t act_floats_per_img[7];
+    size_t act_floats_per_img[7];              // the activations as the network stores them (davo_debug_read sizes by these; davo_set_posenn_heads changes [5] and [6])
+    size_t slot_floats_per_img[7];             // what every slot's d_act buffers hold per image: the decoupled widths, fixed by davo_create, so that a slot built
+                                               // at any time (davo_set_inflight) fits whichever heads the context ends up with
     int act_ch[7];
     int pairs = davo::PAIRS_BOTH;              // davo_set_pairs: the pairs of every window the batches issued from now on run
     bool flip = false;                         // davo_set_flip: the batches issued from now on are mirrored left-right where they are staged (window_mirror.h); a batch in
@@ -351,7 +357,8 @@ inline bool triplet(const davo_ctx* c) { return c->topology == DAVO_POSENN_TRIPL
 // images a batch of B windows sends through cnv1..cnv7: one per selected pair, or one per window in the three-frame PoseNN
 inline int batch_images(const davo_ctx* c, int B, int sel) { return triplet(c) ? B : pairs_per_window(sel) * B; }
 // columns of a head's pred, and TF input channels of cnv1 (nets/posenn.py:78,120)
-inline int pred_cols(const davo_ctx* c) { return triplet(c) ? 6 : 3; }
+inline bool coupled(const davo_ctx* c) { return c->heads == DAVO_POSENN_HEADS_COUPLED; }
+inline int pred_cols(const davo_ctx* c) { return (triplet(c) || coupled(c)) ? 6 : 3; }
 inline int cnv1_cin_tf(const davo_ctx* c) { return (triplet(c) ? 3 : 2) * c->v.cin_per_frame; }
 
 // the stream slot i runs on: its own, or the caller's for slot 0 (davo_set_stream)
@@ -379,7 +386,8 @@ int sync_all_slots(davo_ctx* c);
 // ---- weights.hip ----------------------------------------------------------------------------
 void init_layer(ConvLayer& L, const char* label, int KS, int stride, int rate, int cin, int cout, int groups);
 void init_posenn_layers(ConvLayer (&L)[7], int c6);
-std::vector<std::string> needed_names(const Variant& v, int posenn_se = 0);
+void init_coupled_head(ConvLayer (&L)[7], int c6);      // cnv6 and cnv7 of the coupled network, one group each
+std::vector<std::string> needed_names(const Variant& v, int posenn_se = 0, bool coupled = false);
 // TF name of an SE dense tensor of the variant's scope (k: 0 bottleneck_fc/kernel, 1 its bias, 2 recover_fc/kernel, 3 its bias);
 // the se_flow scope's for the variants without SE layers (the kernels do not read them there)
 const char* se_weight_name(int att_source, int k);

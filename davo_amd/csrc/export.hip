@@ -166,6 +166,7 @@ int davo_set_feature_export(davo_ctx* c, int on) {
     { int rc = sync_all_slots(c); if (rc) return rc; }
     if (!on) { c->fx.reset(); c->fx_on = false; return DAVO_OK; }
     if (triplet(c)) return fail(c, DAVO_ERR_INVALID, "the feature export has no three-frame PoseNN form yet (davo_set_posenn_topology): its maps and cnv6 windows are per pair image");
+    if (coupled(c)) return fail(c, DAVO_ERR_INVALID, "the feature export has no coupled PoseNN form yet (davo_set_posenn_heads): its feature maps are one cnv6 per head");
     if (!c->fx) {
         FxBlock fx;
         fx.cap = export_cap(c);
@@ -193,6 +194,7 @@ int davo_set_heat_export(davo_ctx* c, int on) {
     { int rc = sync_all_slots(c); if (rc) return rc; }
     if (!on) { c->heat.reset(); return DAVO_OK; }
     if (triplet(c)) return fail(c, DAVO_ERR_INVALID, "the heat export has no three-frame PoseNN form yet (davo_set_posenn_topology): its cnv6 windows are per pair image");
+    if (coupled(c)) return fail(c, DAVO_ERR_INVALID, "the heat export has no coupled PoseNN form yet (davo_set_posenn_heads): its heat maps are one cnv6 per head");
     if (!c->heat) {
         HeatBlock h;
         h.cap = export_cap(c);

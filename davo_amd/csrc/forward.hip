@@ -11,8 +11,11 @@
 // a pair image to its (window, source frame), every layer in between takes the count.
 // The three-frame PoseNN (davo_set_posenn_topology; nets/posenn.py:69-131) runs ONE image per window: mask_pack3 (16 channels) ->
 // cnv1 (conv_patch_cnv1t_h3, or the implicit GEMM at cin = 16) -> cnv2..cnv7 as above on B images -> the two-pass pose head with six
-// pred columns per head (cnv7 stored; the fused epilogue has three columns).  Host code only: kernels are reached
-// through launch.h.
+// pred columns per head (cnv7 stored; the fused epilogue has three columns).
+// The coupled network (davo_set_posenn_heads; nets/posenn.py:133-187) runs the pair network up to cnv5, then cnv6 as a one-group GEMM
+// of N = cnv6_out, cnv7 as a one-group layer over all of cnv6's channels (256 per pixel) and one head of six columns: f16x3 fuses it
+// into cnv7's epilogue like the flagship's (conv_igemm_h3.h, NC = 6; "fuse_pose", maps of at least 128 pixels), float32 and the small
+// maps store cnv7 and run the two-pass head.  Host code only: kernels are reached through launch.h.
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
@@ -251,7 +254,8 @@ int run_conv_layer_h3(davo_ctx* c, const Run& run, int li, const void* x, int x_
                       bool y_f32, int NB, bool fuse_pose = false, int* pose_bm = nullptr, int* pose_mt = nullptr,
                       int* pose_ntn = nullptr, float* pose_out = nullptr) {
     const ConvLayer& L = c->L[li];
-    const LayerDecision<ConvParamsH> d = decide_layer_h3(L, LayerCall{li, x_ch, Hin, Win, y_ld, y_f32, NB, fuse_pose, pose_out != nullptr}, plan_options(c, li));
+    const bool six = fuse_pose && coupled(c);       // the coupled head's six pred columns: the NC = 6 epilogue, pred as [2][256][3]
+    const LayerDecision<ConvParamsH> d = decide_layer_h3(L, LayerCall{li, x_ch, Hin, Win, y_ld, y_f32, NB, fuse_pose, pose_out != nullptr, six}, plan_options(c, li));
     if (d.err) return fail(c, d.err, "%s", d.msg);
     // scratch before the launches that use it (growing it may synchronise every slot), the device probe before any profiling scope
     float *pose_partial = nullptr, *part = nullptr;
@@ -279,7 +283,7 @@ int run_conv_layer_h3(davo_ctx* c, const Run& run, int li, const void* x, int x_
             p[b].x = static_cast<const uint8_t*>(x); p[b].w = L.d_wh.get(); p[b].bias = L.d_bh.get(); p[b].y = y8;
             p[b].zeros = reinterpret_cast<const uint8_t*>(c->d_zeros.get());
             p[b].range = range;
-            if (fuse_pose) { p[b].pose_w = c->d_wpred.get(); p[b].pose_partial = pose_partial; }
+            if (fuse_pose) { p[b].pose_w = six ? c->d_wpred_halves.get() : c->d_wpred.get(); p[b].pose_partial = pose_partial; }
             if (fuse_pose && pose_out) {      // pose_tail.h
                 p[b].pose_counter = c->slots[run.slot].d_counters.get(); p[b].pose_bias = c->d_bpred.get(); p[b].pose_out = pose_out;
                 p[b].pose_sel = run.pairs;
@@ -428,6 +432,9 @@ int forward_device(davo_ctx* c, const Run& run, int B, const Inputs& in, void* d
     const int sel = run.pairs;
     if (sel != PAIRS_SRC0 && sel != PAIRS_SRC1 && sel != PAIRS_BOTH) return fail(c, DAVO_ERR_INVALID, "internal: pair selection %d", sel);
     const bool tri = triplet(c);       // the three-frame PoseNN: one image per window, both poses from one pass
+    const bool cpl = coupled(c);       // the coupled network: one cnv6, one cnv7 over all of it, one head of six pred columns
+    if (cpl && (tri || c->posenn_se || c->L[5].groups != 1 || c->L[6].groups != 1 || c->L[6].cin != c->v.cnv6_out))
+        return fail(c, DAVO_ERR_INVALID, "internal: the coupled PoseNN runs on the pair topology with one-group cnv6 and cnv7");
     if (tri && (sel != PAIRS_BOTH || run.impl != 0)) return fail(c, DAVO_ERR_INVALID, "internal: the three-frame PoseNN runs both pairs on the MFMA kernels (pairs %d, impl %d)", sel, run.impl);
     if (B < 1 || B > c->max_batch) return fail(c, DAVO_ERR_INVALID, "batch %d outside [1,%d]", B, c->max_batch);
     if (!in.img || !in.flow || !in.seg || !d_pose) return fail(c, DAVO_ERR_INVALID, "null device pointer");
@@ -565,6 +572,7 @@ int forward_device(davo_ctx* c, const Run& run, int B, const Inputs& in, void* d
                                     in.depth, d_tab_far, c->depth_thr));
     }
     const int c6 = v.cnv6_out;
+    const int ch6 = cpl ? c6 : 2 * c6, ch7 = cpl ? 256 : 512;      // channels per pixel of the stored cnv6 and cnv7
     int rc;
     bool pose_fused = false;
     int pose_bm = 0, pose_mt = 0, pose_ntn = 0;
@@ -588,9 +596,10 @@ int forward_device(davo_ctx* c, const Run& run, int B, const Inputs& in, void* d
         if (c->posenn_se) {
             if ((rc = run_posenn_se(c, run, true, a[4], NB))) return rc;
             if ((rc = run_conv_layer_h3(c, run, 5, d_se, 512, c->H2, c->W2, a[5], 2 * c6, false, NB))) return rc;
-        } else if ((rc = run_conv_layer_h3(c, run, 5, a[4], 256, c->H2, c->W2, a[5], 2 * c6, false, NB))) return rc;
-        pose_fused = c->opt_fuse_pose && c->H3 * c->W3 >= 128 && !tri;      // the three-frame PoseNN stores cnv7: the fused epilogue has three columns per head
-        if ((rc = run_conv_layer_h3(c, run, 6, a[5], 2 * c6, c->H2, c->W2, a[6], 512, true, NB, pose_fused, &pose_bm, &pose_mt, &pose_ntn,
+        } else if ((rc = run_conv_layer_h3(c, run, 5, a[4], 256, c->H2, c->W2, a[5], ch6, false, NB))) return rc;
+        // the three-frame PoseNN stores cnv7 (the fused epilogue has three columns per head); the coupled one fuses its six columns (NC = 6)
+        pose_fused = c->opt_fuse_pose && c->H3 * c->W3 >= 128 && !tri;
+        if ((rc = run_conv_layer_h3(c, run, 6, a[5], ch6, c->H2, c->W2, a[6], ch7, true, NB, pose_fused, &pose_bm, &pose_mt, &pose_ntn,
                                     fold_pose ? static_cast<float*>(d_pose) : nullptr))) return rc;
         c->cnv7_valid = !pose_fused;
     } else if (run.impl == 0) {
@@ -605,12 +614,12 @@ int forward_device(davo_ctx* c, const Run& run, int B, const Inputs& in, void* d
         if (c->posenn_se) {
             if ((rc = run_posenn_se(c, run, false, a[4], NB))) return rc;
             if ((rc = run_conv_layer(c, run, 5, d_se, 512, c->H2, c->W2, a[5], 2 * c6, NB))) return rc;
-        } else if ((rc = run_conv_layer(c, run, 5, a[4], 256, c->H2, c->W2, a[5], 2 * c6, NB))) return rc;
+        } else if ((rc = run_conv_layer(c, run, 5, a[4], 256, c->H2, c->W2, a[5], ch6, NB))) return rc;
         // float32 mode, round 4: the pose head in cnv7's epilogue like the f16x3 path's (the 109 MB activation is neither written nor
         // read back, pose_head_partial + pose_finish become pose_from_tiles); tiles of 128 rows must not span more than two images
-        pose_fused = c->opt_fuse_pose && c->H3 * c->W3 >= 128 && c->L[6].npad == 256 && !tri;
+        pose_fused = c->opt_fuse_pose && c->H3 * c->W3 >= 128 && c->L[6].npad == 256 && !tri && !cpl;
         pose_bm = 128; pose_ntn = 8;
-        if ((rc = run_conv_layer(c, run, 6, a[5], 2 * c6, c->H2, c->W2, a[6], 512, NB, pose_fused, &pose_mt))) return rc;
+        if ((rc = run_conv_layer(c, run, 6, a[5], ch6, c->H2, c->W2, a[6], ch7, NB, pose_fused, &pose_mt))) return rc;
         c->cnv7_valid = !pose_fused;
     } else {
         const std::string P = "pose_exp_net/";
@@ -623,7 +632,11 @@ int forward_device(davo_ctx* c, const Run& run, int B, const Inputs& in, void* d
         if ((rc = run_direct(c, run, "cnv5", a[3], NB, c->H2, c->W2, 128, 128, 0, P + "cnv5/weights", P + "cnv5/biases", 3, 256, 1, 8, a[4], 256, 0))) return rc;
         if (c->posenn_se && (rc = run_posenn_se(c, run, false, a[4], NB))) return rc;      // float32 NHWC like the float32 mode's cnv5
         const char* heads[2] = {"rotation", "translation"};
-        for (int h = 0; h < 2; ++h) {
+        if (cpl) {      // the one head: cnv6 from all of cnv5, cnv7 from all of cnv6
+            const std::string hp = P + "pose/";
+            if ((rc = run_direct(c, run, "cnv6", a[4], NB, c->H2, c->W2, 256, 256, 0, hp + "cnv6/weights", hp + "cnv6/biases", 3, c6, 1, 2, a[5], c6, 0))) return rc;
+            if ((rc = run_direct(c, run, "cnv7", a[5], NB, c->H2, c->W2, c6, c6, 0, hp + "cnv7/weights", hp + "cnv7/biases", 3, 256, 2, 1, a[6], 256, 0))) return rc;
+        } else for (int h = 0; h < 2; ++h) {
             const std::string hp = P + "pose/" + heads[h] + "/";
             // feature attention: head h reads its half of the scaled tensor
             const float* x6 = c->posenn_se ? d_se : a[4];
@@ -638,6 +651,8 @@ int forward_device(davo_ctx* c, const Run& run, int B, const Inputs& in, void* d
             HIP_TRY(c, launch_pose_from_tiles(static_cast<const float*>(c->d_pose_tiles.get()) + (size_t)run.slot * c->pose_tiles_floats, NB, c->H3 * c->W3, pose_bm,
                                               pose_mt, pose_ntn, c->d_bpred.get(), static_cast<float*>(d_pose), h3 ? run.snap : SnapArgs{}, sel, s));
             snap_done = true;
+        } else if (cpl) {
+            HIP_TRY(c, launch_pose_head_coupled(a[6], NB, c->H3 * c->W3, c->d_wpred.get(), c->d_bpred.get(), ws.d_pose_partial.get(), static_cast<float*>(d_pose), sel, s));
         } else if (tri) {
             HIP_TRY(c, launch_pose_head6(a[6], B, c->H3 * c->W3, c->d_wpred.get(), c->d_bpred.get(), ws.d_pose_partial.get(), static_cast<float*>(d_pose), s));
         } else {

@@ -111,6 +111,9 @@ hipError_t launch_pose_head(const float* d_c7, int NB, int P, const float* d_wpr
 // ... of the three-frame PoseNN: d_c7 [B][P][512], d_wpred6 [2][256][6], d_bpred6 [2][6], d_partial [B][2][PH_SPLIT][6] -> d_pose [B][2][6]
 hipError_t launch_pose_head6(const float* d_c7, int B, int P, const float* d_wpred6, const float* d_bpred6,
                              float* d_partial, float* d_pose, hipStream_t s);
+// ... of the coupled network: d_c7 [NB][P][256], d_wpred6 [256][6], d_bpred6 [6], d_partial [NB][PH_SPLIT][6] -> d_pose [B][2][6] by pose_store
+hipError_t launch_pose_head_coupled(const float* d_c7, int NB, int P, const float* d_wpred6, const float* d_bpred6,
+                                    float* d_partial, float* d_pose, int sel, hipStream_t s);
 hipError_t launch_conv_direct(const float* x, int N, int Hin, int Win, int cin, int x_ld, int x_coff, const float* w, int KS,
                               int cout, const float* bias, int stride, int rate, int pt, int pl, int Ho, int Wo, int relu,
                               float* y, int y_ld, int y_coff, hipStream_t s);

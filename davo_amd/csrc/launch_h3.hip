@@ -6,6 +6,11 @@ namespace davo {
 
 hipError_t launch_layer_h3(int layer, int tile, const ConvParamsH& p, dim3 grid, hipStream_t s) {
     using namespace h3impl;
+    if (p.y_mode == 2 && p.pose_nc == 6) {
+        // the coupled network's six-column fused pose head: cnv7 alone, on conv_igemm_h3's tiles (conv_igemm_h3s has three columns)
+        if (layer != 6 || is_208(tile)) return hipErrorNotSupported;
+        return launch_tile<3, 2, 7, false, 256, 6>(tile, p, grid, s);
+    }
     if (is_208(tile)) return launch_layer_h3s(layer, p, grid, s);
     switch (layer) {
         case 0: return launch_tile<7, 2, 1, true, 32>(tile, p, grid, s);

@@ -305,6 +305,16 @@ hipError_t launch_pose_head6(const float* d_c7, int B, int P, const float* d_wpr
     return hipGetLastError();
 }
 
+hipError_t launch_pose_head_coupled(const float* d_c7, int NB, int P, const float* d_wpred6, const float* d_bpred6,
+                                    float* d_partial, float* d_pose, int sel, hipStream_t s) {
+    if (NB < 1 || P < 1 || !d_c7 || !d_wpred6 || !d_bpred6 || !d_partial || !d_pose) return hipErrorInvalidValue;
+    hipLaunchKernelGGL((pose_head_partial<6, 1>), dim3(PH_SPLIT, NB, 1), dim3(256), 0, s, d_c7, P, d_wpred6, d_partial);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(pose_finish_coupled, dim3((NB * 6 + 63) / 64), dim3(64), 0, s, d_partial, NB, P, d_bpred6, d_pose, sel);
+    return hipGetLastError();
+}
+
 hipError_t launch_conv_direct(const float* x, int N, int Hin, int Win, int cin, int x_ld, int x_coff, const float* w, int KS,
                               int cout, const float* bias, int stride, int rate, int pt, int pl, int Ho, int Wo, int relu,
                               float* y, int y_ld, int y_coff, hipStream_t s) {

@@ -241,6 +241,8 @@ struct ConvParamsH {
     int pose_sel;           // pair selection of the batch (PAIRS_*)
     int dbg;                // measurement only (DAVO_DBG; results are wrong with any bit set): 1 DMA reads the zero line,
                             // 2 no matrix phase, 4 no wave-half stagger (32x32x16 form), 32 no epilogue, 64 stores fold onto 256 tiles
+    int pose_nc;            // y_mode 2: 6 = the coupled network's six-column head (one group; pose_w [2][Cout][3] = pred columns 0..2 | 3..5, the
+                            // partial sums in the two-head layout); anything else = three columns per group.  Picks the NC = 6 instantiation
 };
 
 constexpr int LDB = 144;        // LDS row: 128 data bytes + 16 pad (conflict-free b128 fragment reads)

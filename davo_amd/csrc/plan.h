@@ -87,7 +87,9 @@ struct LayerGeom {
 };
 // x_ch: channels of the input tensor (f16x3: of the whole blocked tensor; float32: floats per pixel); pose_tail: the launch's last
 // workgroup adds the pose tiles and writes the poses (f16x3 with fuse_pose only)
-struct LayerCall { int li, x_ch, Hin, Win, y_ld; bool y_f32; int NB; bool fuse_pose, pose_tail; };
+// pose_six (f16x3 with fuse_pose, a one-group cnv7): the coupled network's six-column head - the NC = 6 epilogue of conv_igemm_h3.h, its
+// partial sums in the two-head layout, no 208-pixel tile (conv_igemm_h3s.h has the three-column epilogue alone)
+struct LayerCall { int li, x_ch, Hin, Win, y_ld; bool y_f32; int NB; bool fuse_pose, pose_tail; bool pose_six = false; };
 // the context's settings these decisions read (davo_ctx: opt_*, ncu, dev_cus, cu_partition, user_stream, max_batch) and the storage
 // shifts of the layer's input and output (act_shift[li - 1], 0 for cnv1; act_shift[li])
 struct PlanOptions {

@@ -313,7 +313,8 @@ LayerDecision<ConvParamsH> decide_layer_h3(const LayerGeom& L, const LayerCall& 
     std::vector<LaunchH> plan = plan_layer_h3(p.M, L.npad_h, L.groups, L.tile_h, allow_208, o.ncu, others_scale);
     if (fuse_pose) {      // one launch, one tile shape no taller than an image, so a tile touches <= 2 images
         const int P = p.Hout * p.Wout;
-        const int best = plan_single_tile_h3(p.M, L.npad_h, L.groups, P, L.tile_h, allow_208, o.ncu);
+        if (call.pose_six && (li != 6 || L.groups != 1)) { d.err = DAVO_ERR_INVALID; d.msg = "internal: the six-column fused pose head belongs to a one-group cnv7"; return d; }
+        const int best = plan_single_tile_h3(p.M, L.npad_h, L.groups, P, L.tile_h, allow_208 && !call.pose_six, o.ncu);
         if (best < 0) { d.err = DAVO_ERR_INVALID; d.msg = "no tile fits the fused pose head"; return d; }
         plan = {{0, p.M, best}};
         const TileShape ts = tile_shape(best);
@@ -321,8 +322,8 @@ LayerDecision<ConvParamsH> decide_layer_h3(const LayerGeom& L, const LayerCall& 
 #ifdef DAVO_POSE_DEBUG
         d.pose_debug_bytes = (size_t)L.groups * mt * ntn * 512 * 20 * sizeof(float);
 #endif
-        d.pose_floats = (size_t)L.groups * mt * ntn * 6;
-        p.y_mode = 2; p.pose_P = P; p.pose_mt = mt;
+        d.pose_floats = (size_t)(call.pose_six ? 2 : L.groups) * mt * ntn * 6;      // six columns: [2 column halves][mt][ntn][2][3]
+        p.y_mode = 2; p.pose_P = P; p.pose_mt = mt; p.pose_nc = call.pose_six ? 6 : 0;
         if (call.pose_tail) {      // the launch's last workgroup adds the tiles and writes the poses (pose_tail.h)
             p.pose_NB = call.NB; p.pose_bm = ts.bm; p.pose_total = L.groups * mt * ntn;
         }

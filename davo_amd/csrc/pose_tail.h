@@ -52,6 +52,9 @@ __device__ __forceinline__ void pose_store(float* __restrict__ pose, int n, int 
 // slot 0 = the tile's first image, 1 = the next one): entry j = (tile t0 + j / ntn, N tile j % ntn) goes to lane j % 64 (a
 // lane adds its entries in order), then a fixed butterfly over the lanes — the same bits whoever computes it (the
 // pose_from_tiles kernel or the cnv7 launch's last workgroup) and however many lanes hold an entry.  Every lane returns the sum.
+// `head' need not be a head of the network: the coupled network's six-column epilogue (conv_igemm_h3.h, NC = 6) writes the sums of
+// its ONE head's pred columns 0..2 as "head" 0 and of columns 3..5 as "head" 1 of this same layout, so hk = 0..5 here is then the
+// pose component itself.  Anything that changes this layout changes that epilogue's two stores with it.
 template <bool AGENT>
 __device__ __forceinline__ float pose_tile_sum(const float* __restrict__ partial, int n, int hk, int P, int bm, int mtiles, int ntn, int lane) {
     const int head = hk / 3, k = hk - head * 3;

@@ -707,22 +707,25 @@ __global__ __launch_bounds__(PACK3_THREADS) void mask_pack3(const uint8_t* __res
 // adds the PH_SPLIT partials in a fixed order -> bitwise reproducible.
 
 // NC: columns of a head's pred: 3 (one pose per pair image) or 6 (the three-frame PoseNN: both poses of a window from one image,
-// nets/posenn.py:120), wpred [2][256][NC], partial [images][2][PH_SPLIT][NC]; the sums of a column are the same in either form.
-template <int NC>
+// nets/posenn.py:120; the coupled network: all six components from its one head, nets/posenn.py:176-179), wpred [HEADS][256][NC],
+// partial [images][HEADS][PH_SPLIT][NC]; the sums of a column are the same in either form.
+// HEADS: heads side by side in a cnv7 pixel, 256 channels each: 2 (rotation | translation, grid z) or 1 (the coupled network).
+template <int NC, int HEADS = 2>
 __global__ __launch_bounds__(256) void pose_head_partial(const float* __restrict__ c7, int P,
-                                                         const float* __restrict__ wpred /*[2][256][NC]*/,
-                                                         float* __restrict__ partial /*[images][2][PH_SPLIT][NC]*/) {
+                                                         const float* __restrict__ wpred /*[HEADS][256][NC]*/,
+                                                         float* __restrict__ partial /*[images][HEADS][PH_SPLIT][NC]*/) {
+    constexpr int LD = HEADS * 256;        // floats per cnv7 pixel
     const int sp = blockIdx.x, n = blockIdx.y, head = blockIdx.z, c = threadIdx.x;
     const int per = (P + PH_SPLIT - 1) / PH_SPLIT;
     const int p0 = sp * per, p1 = min(p0 + per, P);
-    const float* src = c7 + (size_t)n * P * 512 + head * 256 + c;
+    const float* src = c7 + (size_t)n * P * LD + head * 256 + c;
     float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
     int p = p0;
     for (; p + 4 <= p1; p += 4) {
-        s0 += src[(size_t)p * 512]; s1 += src[(size_t)(p + 1) * 512];
-        s2 += src[(size_t)(p + 2) * 512]; s3 += src[(size_t)(p + 3) * 512];
+        s0 += src[(size_t)p * LD]; s1 += src[(size_t)(p + 1) * LD];
+        s2 += src[(size_t)(p + 2) * LD]; s3 += src[(size_t)(p + 3) * LD];
     }
-    for (; p < p1; ++p) s0 += src[(size_t)p * 512];
+    for (; p < p1; ++p) s0 += src[(size_t)p * LD];
     const float sc = (s0 + s1) + (s2 + s3);
     const float* wp = wpred + ((size_t)head * 256 + c) * NC;
     float v[NC];
@@ -737,7 +740,7 @@ __global__ __launch_bounds__(256) void pose_head_partial(const float* __restrict
     }
     __syncthreads();
     if (c < NC)
-        partial[(((size_t)n * 2 + head) * PH_SPLIT + sp) * NC + c] = (red[c][0] + red[c][1]) + (red[c][2] + red[c][3]);
+        partial[(((size_t)n * HEADS + head) * PH_SPLIT + sp) * NC + c] = (red[c][0] + red[c][1]) + (red[c][2] + red[c][3]);
 }
 
 __global__ __launch_bounds__(64) void pose_finish(const float* __restrict__ partial, int NB, int P,
@@ -767,6 +770,22 @@ __global__ __launch_bounds__(64) void pose_finish6(const float* __restrict__ par
 #pragma unroll
     for (int q = 0; q < PH_SPLIT; ++q) tot += pp[q * 6];
     pose[i] = 0.01f * (tot / (float)P + bpred[head * 6 + col]);
+}
+
+// ... of the coupled network (nets/posenn.py:176-179): pred's six columns ARE the pose of pair image n, unpermuted:
+// pose[pair_pose_row(n, sel)][k] = 0.01 * avg[n][k]; the PH_SPLIT partials in the same fixed order, stored through pose_store (one
+// selected pair: +0.0 into the window's other row)
+__global__ __launch_bounds__(64) void pose_finish_coupled(const float* __restrict__ partial /*[NB][PH_SPLIT][6]*/, int NB, int P,
+                                                          const float* __restrict__ bpred /*[6]*/,
+                                                          float* __restrict__ pose /*[B][2][6]*/, int sel) {
+    const int i = blockIdx.x * 64 + threadIdx.x;           // (n, k)
+    if (i >= NB * 6) return;
+    const int n = i / 6, k = i - n * 6;
+    const float* pp = partial + (size_t)n * PH_SPLIT * 6 + k;
+    float tot = 0.f;
+#pragma unroll
+    for (int s = 0; s < PH_SPLIT; ++s) tot += pp[s * 6];
+    pose_store(pose, n, k, sel, 0.01f * (tot / (float)P + bpred[k]));
 }
 
 // Pose from the per-tile partial sums cnv7's fused epilogue wrote (conv_igemm_h3.h, y_mode 2):

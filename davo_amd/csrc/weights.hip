@@ -99,7 +99,7 @@ bool is_dense_weight(const std::string& nm) {
     return false;
 }
 
-std::vector<std::string> needed_names(const Variant& v, int posenn_se) {
+std::vector<std::string> needed_names(const Variant& v, int posenn_se, bool coupled) {
     std::vector<std::string> n;
     const char* trunk[] = {"cnv1", "cnv2", "cnv3", "cnv4", "cnv5"};
     for (auto l : trunk) {
@@ -108,11 +108,17 @@ std::vector<std::string> needed_names(const Variant& v, int posenn_se) {
     }
     const char* heads[] = {"rotation", "translation"};
     const char* hl[] = {"cnv6", "cnv7", "pred"};
-    for (auto h : heads)
+    if (coupled) {       // one head straight under pose/ (nets/posenn.py:166-176)
         for (auto l : hl) {
-            n.push_back(std::string("pose_exp_net/pose/") + h + "/" + l + "/weights");
-            n.push_back(std::string("pose_exp_net/pose/") + h + "/" + l + "/biases");
+            n.push_back(std::string("pose_exp_net/pose/") + l + "/weights");
+            n.push_back(std::string("pose_exp_net/pose/") + l + "/biases");
         }
+    } else
+        for (auto h : heads)
+            for (auto l : hl) {
+                n.push_back(std::string("pose_exp_net/pose/") + h + "/" + l + "/weights");
+                n.push_back(std::string("pose_exp_net/pose/") + h + "/" + l + "/biases");
+            }
     if (v.att_source == 1 || att_class_table(v.att_source) || att_pooled(v.att_source)) {
         for (int k = 0; k < 4; ++k) n.push_back(se_weight_name(v.att_source, k));
     } else if (v.att_source == ATT_DEPTH_SPLIT) {         // two se_flow MLPs and the threshold; none of se_flow/*_fc
@@ -233,6 +239,18 @@ void init_posenn_layers(ConvLayer (&L)[7], int c6) {
     init_layer(L[6], "cnv7", 3, 2, 1, c6, 256, 2);
 }
 
+// ... of the coupled network (nets/posenn.py:166-176): one cnv6 of c6 columns, one cnv7 that reads all c6 channels
+void init_coupled_head(ConvLayer (&L)[7], int c6) {
+    init_layer(L[5], "cnv6", 3, 1, 2, 256, c6, 1);
+    init_layer(L[6], "cnv7", 3, 2, 1, c6, 256, 1);
+}
+
+// the scopes the head variables live under: rotation/ and translation/, or - coupled - pose/ itself
+static std::vector<std::string> head_scopes(const davo_ctx* c) {
+    if (coupled(c)) return {"pose_exp_net/pose/"};
+    return {"pose_exp_net/pose/rotation/", "pose_exp_net/pose/translation/"};
+}
+
 // cnv1: packed input channel -> TF input channel.  Pairs, v1: [t r,g,b | 0,0 | s r,g,b | fx,fy]; the two zero channels
 // (davo.py:979,1065) are dropped.  v0: [t rgb | s rgb].  Three-frame PoseNN (prologue.h, mask_pack3), v1: TF [t rgb | 0 0 | s0 rgb |
 // f0 | s1 rgb | f1] -> packed [t rgb | s0 rgb | f0 | s1 rgb | f1 | - - -]; v0: TF [t rgb | s0 rgb | s1 rgb], the flow slots empty.
@@ -255,16 +273,24 @@ static int cnv1_chmap(const davo_ctx* c, int chmap[16]) {
 // and uploads 13 MB less in front of its first batch)
 int build_pred_weights(davo_ctx* c) {
     auto W = [&](const std::string& n) -> const HostTensor& { return c->weights.at(n); };
-    const char* heads[2] = {"rotation", "translation"};
-    const int nc = pred_cols(c);
-    std::vector<float> wp(2 * 256 * nc), bp(2 * nc);
-    for (int h = 0; h < 2; ++h) {
-        const std::string p = std::string("pose_exp_net/pose/") + heads[h] + "/pred/";
+    const std::vector<std::string> scopes = head_scopes(c);      // coupled: [256][6] + [6]
+    const int nc = pred_cols(c), nh = (int)scopes.size();
+    std::vector<float> wp(nh * 256 * nc), bp(nh * nc);
+    for (int h = 0; h < nh; ++h) {
+        const std::string p = scopes[h] + "pred/";
         memcpy(wp.data() + h * 256 * nc, W(p + "weights").data.data(), 256 * nc * sizeof(float));
         memcpy(bp.data() + h * nc, W(p + "biases").data.data(), nc * sizeof(float));
     }
     int rc = upload(c, wp, &c->d_wpred); if (rc) return rc;
     rc = upload(c, bp, &c->d_bpred); if (rc) return rc;
+    c->d_wpred_halves.reset();
+    if (coupled(c)) {      // [256][6] -> [2][256][3] for cnv7's six-column fused epilogue (conv_igemm_h3.h, NC = 6)
+        std::vector<float> wh(2 * 256 * 3);
+        for (int h = 0; h < 2; ++h)
+            for (int ch = 0; ch < 256; ++ch)
+                for (int k = 0; k < 3; ++k) wh[(h * 256 + ch) * 3 + k] = wp[ch * 6 + 3 * h + k];
+        rc = upload(c, wh, &c->d_wpred_halves); if (rc) return rc;
+    }
     c->pred_ready = true;
     return DAVO_OK;
 }
@@ -291,24 +317,26 @@ int build_packed_weights(davo_ctx* c) {
         int rc = upload(c, wp, &L.d_w); if (rc) return rc;
         rc = upload(c, bp, &L.d_b); if (rc) return rc;
     }
-    const char* heads[2] = {"rotation", "translation"};
-    {   // cnv6: one GEMM, N = [rotation c6 | translation c6]; feature attention: one group per head like cnv7
+    const std::vector<std::string> scopes = head_scopes(c);
+    const int nh = (int)scopes.size();
+    {   // cnv6: one GEMM, N = [rotation c6 | translation c6]; feature attention: one group per head like cnv7; coupled: the one head
         ConvLayer& L = c->L[5];
         const size_t wstep = L.groups == 2 ? (size_t)L.npad * L.kpad : (size_t)c6 * L.kpad, bstep = L.groups == 2 ? L.npad : c6;
         std::vector<float> wp((size_t)L.groups * L.npad * L.kpad, 0.f), bp((size_t)L.groups * L.npad, 0.f);
-        for (int h = 0; h < 2; ++h) {
-            const std::string p = std::string("pose_exp_net/pose/") + heads[h] + "/cnv6/";
+        for (int h = 0; h < nh; ++h) {
+            const std::string p = scopes[h] + "cnv6/";
             pack_conv_weights(W(p + "weights").data.data(), 3, 256, c6, nullptr, 256, c6, L.kpad, wp.data() + h * wstep);
             memcpy(bp.data() + h * bstep, W(p + "biases").data.data(), c6 * sizeof(float));
         }
         int rc = upload(c, wp, &L.d_w); if (rc) return rc;
         rc = upload(c, bp, &L.d_b); if (rc) return rc;
     }
-    {   // cnv7: two groups (blockIdx.y), group g reads cnv6 channels [g*c6, (g+1)*c6)
+    {   // cnv7: two groups (blockIdx.y), group g reads cnv6 channels [g*c6, (g+1)*c6); coupled: one group over all c6 channels
         ConvLayer& L = c->L[6];
-        std::vector<float> wp((size_t)2 * L.npad * L.kpad, 0.f), bp((size_t)2 * L.npad, 0.f);
-        for (int h = 0; h < 2; ++h) {
-            const std::string p = std::string("pose_exp_net/pose/") + heads[h] + "/cnv7/";
+        if (L.groups != nh) return fail(c, DAVO_ERR_INVALID, "internal: cnv7 has %d groups for %d heads", L.groups, nh);
+        std::vector<float> wp((size_t)nh * L.npad * L.kpad, 0.f), bp((size_t)nh * L.npad, 0.f);
+        for (int h = 0; h < nh; ++h) {
+            const std::string p = scopes[h] + "cnv7/";
             pack_conv_weights(W(p + "weights").data.data(), 3, c6, 256, nullptr, c6, L.npad, L.kpad,
                               wp.data() + (size_t)h * L.npad * L.kpad);
             memcpy(bp.data() + (size_t)h * L.npad, W(p + "biases").data.data(), 256 * sizeof(float));
@@ -364,7 +392,9 @@ int build_packed_weights_h3(davo_ctx* c) {
     int chmap1[16];
     (void)cnv1_chmap(c, chmap1);
     (void)cpf;
-    const char* heads[2] = {"rotation", "translation"};
+    const std::vector<std::string> scopes = head_scopes(c);
+    const int nh = (int)scopes.size();
+    if (c->L[6].groups != nh) return fail(c, DAVO_ERR_INVALID, "internal: cnv7 has %d groups for %d heads", c->L[6].groups, nh);
     for (int li = 0; li < 7; ++li) {
         ConvLayer& L = c->L[li];
         const size_t per_group = (size_t)L.npad_h * L.nchunks_h * 64;
@@ -378,8 +408,8 @@ int build_packed_weights_h3(davo_ctx* c) {
                 const HostTensor& t = W(std::string("pose_exp_net/") + names[li] + "/weights");
                 sc = weight_prescale(t.data.data(), t.data.size());
             } else {
-                for (int h = 0; h < 2; ++h) {
-                    const HostTensor& t = W(std::string("pose_exp_net/pose/") + heads[h] + (li == 5 ? "/cnv6/weights" : "/cnv7/weights"));
+                for (int h = 0; h < nh; ++h) {
+                    const HostTensor& t = W(scopes[h] + (li == 5 ? "cnv6/weights" : "cnv7/weights"));
                     sc = std::fmin(sc, weight_prescale(t.data.data(), t.data.size()));
                 }
             }
@@ -397,13 +427,13 @@ int build_packed_weights_h3(davo_ctx* c) {
             pack(p + "weights", p + "biases", li == 0 ? cnv1_cin_tf(c) : L.cin, L.cout, li == 0 ? chmap1 : nullptr, wp.data(), bp.data());
         } else if (li == 5) {       // rotation | translation stacked along N; feature attention: one group per head
             const size_t wstep = L.groups == 2 ? per_group : (size_t)c6 * L.nchunks_h * 64, bstep = L.groups == 2 ? L.npad_h : c6;
-            for (int h = 0; h < 2; ++h) {
-                const std::string p = std::string("pose_exp_net/pose/") + heads[h] + "/cnv6/";
+            for (int h = 0; h < nh; ++h) {
+                const std::string p = scopes[h] + "cnv6/";
                 pack(p + "weights", p + "biases", 256, c6, nullptr, wp.data() + h * wstep, bp.data() + h * bstep);
             }
         } else {                    // cnv7: one group per head
-            for (int h = 0; h < 2; ++h) {
-                const std::string p = std::string("pose_exp_net/pose/") + heads[h] + "/cnv7/";
+            for (int h = 0; h < nh; ++h) {
+                const std::string p = scopes[h] + "cnv7/";
                 pack(p + "weights", p + "biases", c6, 256, nullptr, wp.data() + (size_t)h * per_group, bp.data() + (size_t)h * L.npad_h);
             }
         }
@@ -483,10 +513,10 @@ int build_packed_weights_h3(davo_ctx* c) {
         c->weight_channel_spread_log2 = 0;
         c->weight_channel_spread_layer.clear();
         const char* lw[6] = {"pose_exp_net/cnv2/weights", "pose_exp_net/cnv3/weights", "pose_exp_net/cnv4/weights", "pose_exp_net/cnv5/weights",
-                             "/cnv6/weights", "/cnv7/weights"};
+                             "cnv6/weights", "cnv7/weights"};
         for (int k = 0; k < 6; ++k) {
-            for (int h = 0; h < (k < 4 ? 1 : 2); ++h) {
-                const std::string name = k < 4 ? std::string(lw[k]) : std::string("pose_exp_net/pose/") + heads[h] + lw[k];
+            for (int h = 0; h < (k < 4 ? 1 : nh); ++h) {
+                const std::string name = k < 4 ? std::string(lw[k]) : scopes[h] + lw[k];
                 const HostTensor& t = W(name);
                 const int64_t taps = t.shape[0] * t.shape[1], cin = t.shape[2], cout = t.shape[3];
                 // Upward spread only (round 4): what matters is a channel whose weights are 2^r LARGER than the typical channel's (its

@@ -153,6 +153,12 @@ class Engine:
             except Exception:
                 self.close()
                 raise
+        if cfg.heads == "coupled":                # `-sharedNN-dilatedCouplePoseNN': likewise before any weight (davo_set_posenn_heads)
+            try:
+                self._check(self._L.davo_set_posenn_heads(self._ctx, _lib.POSENN_HEADS_COUPLED))
+            except Exception:
+                self.close()
+                raise
         try:
             for attr, value in (("labels", labels), ("flow", flow), ("depth", depth)):
                 if value != "f32":

@@ -66,6 +66,10 @@ class VariantConfig:
     posenn: str = "pairs"    # pairs | triplet: decouple_sharednet_v0_dilation on two (tgt, src) images per window, or
                              # decouple_net_v0_dilation on one (tgt, src0, src1) image (davo.py:1038-1040, nets/posenn.py:69-131);
                              # not a davo_variant field: Engine hands it to davo_set_posenn_topology
+    heads: str = "decoupled"  # decoupled | coupled: a rotation and a translation head (cnv6, cnv7, pred of three columns each), or the one head of
+                              # couple_sharednet_v0_dilation (`-sharedNN-dilatedCouplePoseNN', davo.py:1031-1033, nets/posenn.py:133-187): one
+                              # cnv6, one cnv7 that reads all of it, one pred of six columns; not a davo_variant field: Engine hands it to
+                              # davo_set_posenn_heads
 
     @property
     def cin_per_frame(self):
@@ -174,11 +178,12 @@ def parse_version(version):
             raise UnsupportedVariantError("version `%s': `%s' PoseNN mode is not supported." % (v, s))
 
     # -- davo.py:1027-1049: PoseNN type
+    heads = "decoupled"
     if "-sharedNN" in v:
         if "-dilatedPoseNN" in v:
             pass                                        # decouple_sharednet_v0_dilation
         elif "-dilatedCouplePoseNN" in v:
-            raise UnsupportedVariantError("version `%s': couple_sharednet_v0_dilation is not supported." % v)
+            heads = "coupled"                           # couple_sharednet_v0_dilation: the trunk of the above, one six-column head
         elif "-couplePoseNN" in v:
             raise NameError("not support `-sharedNN-couplePoseNN' mode.")      # davo.py:1035
         else:
@@ -294,10 +299,22 @@ def parse_version(version):
             raise UnsupportedVariantError("version `%s': attention source `%s' without `-segmask' would be built and never read; "
                                           "the three-frame network runs an attention source only where it is applied." % (v, att_source))
 
+    if heads == "coupled":
+        # the coupled pair network (nets/posenn.py:133-187): every attention source of the pair network runs in front of it; the
+        # feature-attention block has no coupled form here
+        if posenn_se != "none":
+            raise UnsupportedVariantError("version `%s': `-se_insert' is not supported with the coupled `-sharedNN-dilatedCouplePoseNN' "
+                                          "network (couple_sharednet_v0_dilation)." % v)
+        if att_source != "ones" and not mask_rgb:
+            # the three-frame network's rule, in its words: a graph whose attention nothing applies is not built.  It is also what keeps
+            # `v1-sharedNN-dilatedCouplePoseNN-se_flow' (no `-segmask'), pinned as rejected by tests/test_version.py, raising
+            raise UnsupportedVariantError("version `%s': attention source `%s' without `-segmask' would be built and never read; "
+                                          "the coupled network runs an attention source only where it is applied." % (v, att_source))
+
     return VariantConfig(version=v, major=major, use_flow_info=use_flow_info, cnv6_out=cnv6_out,
                          se_act=se_act, norm_flow=norm_flow, abs_mode=abs_mode,
                          att_source=att_source, mask_rgb=mask_rgb, mask_info=mask_info, posenn_se=posenn_se,
-                         depth_thres_init=depth_thres_init, posenn=posenn)
+                         depth_thres_init=depth_thres_init, posenn=posenn, heads=heads)
 
 
 def weight_shapes(cfg):
@@ -317,8 +334,13 @@ def weight_shapes(cfg):
         "pose_exp_net/cnv4/weights": (3, 3, 64, 128), "pose_exp_net/cnv4/biases": (128,),
         "pose_exp_net/cnv5/weights": (3, 3, 128, 256), "pose_exp_net/cnv5/biases": (256,),
     }
-    for head in ("rotation", "translation"):
-        p = "pose_exp_net/pose/%s/" % head
+    # the head scopes: rotation/ and translation/ with three (three-frame: six) pred columns each, or - coupled - pose/ itself with
+    # six (nets/posenn.py:166-176: no rotation/ or translation/ scope)
+    if cfg.heads == "coupled":
+        head_scopes, npred = ["pose_exp_net/pose/"], 6
+    else:
+        head_scopes = ["pose_exp_net/pose/%s/" % head for head in ("rotation", "translation")]
+    for p in head_scopes:
         sh[p + "cnv6/weights"] = (3, 3, 256, c6)
         sh[p + "cnv6/biases"] = (c6,)
         sh[p + "cnv7/weights"] = (3, 3, c6, 256)

@@ -114,6 +114,34 @@ int davo_set_posenn_se(davo_ctx* ctx, int mode);
 enum { DAVO_POSENN_PAIRS = 0, DAVO_POSENN_TRIPLET = 1 };
 int davo_set_posenn_topology(davo_ctx* ctx, int topology);
 
+/* The PoseNN's heads (davo.py:1027-1049), not part of davo_variant either.  DAVO_POSENN_HEADS_DECOUPLED (the default) is the
+ * rotation head and the translation head of the two decoupled networks.  DAVO_POSENN_HEADS_COUPLED is
+ * `-sharedNN-dilatedCouplePoseNN', couple_sharednet_v0_dilation (nets/posenn.py:133-187): the pair network's trunk cnv1..cnv5, then
+ * ONE cnv6 (3x3, rate 2, 256 -> cnv6_out), ONE cnv7 (3x3, stride 2, reading ALL cnv6_out channels -> 256) and one linear pred of
+ * six columns per pair image n:
+ *   pose[pair_pose_row(n)][k] = 0.01 * mean_{H3,W3}(pred)[n][k],  k = 0..5 unpermuted (rz ry rx tx ty tz).
+ * The trunk's variables keep their names; the head's are pose_exp_net/pose/{cnv6,cnv7,pred}/{weights,biases}: (3,3,256,cnv6_out),
+ * (cnv6_out,), (3,3,cnv6_out,256), (256,), (1,1,256,6), (6,) - there is no rotation/ or translation/ scope, and the variables of
+ * those scopes are refused ("not part of this variant"), as the coupled names are on a decoupled context.
+ * Inputs, their layouts, the [B,2,6] output and everything in front of cnv6 are unchanged: every attention source, both label, flow
+ * and depth formats, davo_set_flip, davo_set_pairs (one selected pair still writes +0.0 into the other row), davo_set_impl(ctx, 1)
+ * and every pose entry point (window, `_depth', device, davo_submit / davo_wait, davo_calibrate, the three `_frames' calls) work as
+ * on the flagship, with the same range recovery.  davo_debug_read sizes "cnv6" as [images,H/4,W/4,cnv6_out] and "cnv7" as
+ * [images,H/8,W/8,256].
+ * Valid only before the first davo_load_weight and the first forward, like its two neighbours: afterwards DAVO_ERR_INVALID.
+ * DAVO_ERR_INVALID as well for a value outside {0, 1}, after davo_set_posenn_topology(ctx, DAVO_POSENN_TRIPLET) (the three-frame
+ * coupled network, couple_net_v0_dilation, is not built), after davo_set_posenn_se(ctx, 1) (the block has no coupled form) and
+ * while a feature or heat export is on (the reference returns (cnv6, cnv6) there; not built).  Symmetrically, on a coupled context
+ * davo_set_posenn_topology(ctx, DAVO_POSENN_TRIPLET), davo_set_posenn_se(ctx, 1), davo_set_feature_export(ctx, 1) and
+ * davo_set_heat_export(ctx, 1) return DAVO_ERR_INVALID.
+ * The pose head.  f16x3 with the option "fuse_pose" 1 (the default), on maps of at least 128 cnv7 pixels per image: the six columns
+ * are fused into cnv7's epilogue like the flagship's three per head (the six-column instantiation of that epilogue; cnv7 is not
+ * stored, davo_debug_read("cnv7") returns DAVO_ERR_NOT_READY, "fold_tails" 1 lets the launch's last workgroup write the poses).
+ * float32 mode, smaller maps and "fuse_pose" 0 keep the two-pass head (pose_head_partial over the stored cnv7, then a fixed-order
+ * finish): a six-column fused epilogue is not built for float32 mode. */
+enum { DAVO_POSENN_HEADS_DECOUPLED = 0, DAVO_POSENN_HEADS_COUPLED = 1 };
+int davo_set_posenn_heads(davo_ctx* ctx, int heads);
+
 /* Label format.  A label map is a class id per pixel, and nothing on the path reads more of it than "class 0..18, or none"; the
  * reference's preprocessing stores it as float32 [B,3,H,W,1] (data_loader.py:313-317), which is what every entry point takes by
  * default (DAVO_LABELS_F32).  davo_set_label_format(ctx, DAVO_LABELS_U8) makes the context take bytes instead: uint8 [B,3,H,W,1],

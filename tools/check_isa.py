@@ -114,8 +114,8 @@ def check(path, kinds=None):
         if m:
             name, in_chunk, saw_barrier = m.group(1), False, False
             kind = next(g for g in m.groups()[1:] if g)      # (round 5: the four-wave kernels of conv_igemm_h3w.h count their waits the same way)
-            # conv_igemm_h3<..., DMA=true, SMALLC, M16=true, NSTG, RATE>: only the 16x16x32 form has the hand-counted loop
-            m16 = kind != "conv_igemm_h3" or re.search(r"Lb1ELb[01]ELb1ELi\dELi\dEEEvNS", name) is not None
+            # conv_igemm_h3<..., DMA=true, SMALLC, M16=true, NSTG, RATE, NC>: only the 16x16x32 form has the hand-counted loop
+            m16 = kind != "conv_igemm_h3" or re.search(r"Lb1ELb[01]ELb1ELi\dELi\dELi\dEEEvNS", name) is not None
             if not m16:
                 name = None
             else:
