@@ -53,7 +53,7 @@ EXPORTS = (
     "davo_set_flow_format", "davo_get_flow_format", "davo_frames_plan_fmt", "davo_pool_plan",
     "davo_set_flip", "davo_get_flip",
     "davo_set_depth_format", "davo_get_depth_format", "davo_frames_plan_fmt2",
-    "davo_set_posenn_heads",
+    "davo_set_posenn_heads", "davo_decide_forward",
 )
 COMM_ID_BYTES = 128
 LABELS_F32, LABELS_U8 = 0, 1          # DAVO_LABELS_F32, DAVO_LABELS_U8 (davo_set_label_format)
@@ -264,6 +264,7 @@ def _load():
     L.davo_pad_class_tile_order.argtypes = [usp, i, i, i, ip]
     L.davo_plan_layer_f32.argtypes = [i] * 4 + [ip, ip, ip]
     L.davo_decide_layer.argtypes = [i] * 7 + [ip, i, ip, i]
+    L.davo_decide_forward.argtypes = [ip, ip, i, ip, i]
     L.davo_comm_preload.argtypes = [ctypes.c_char_p, i]
     L.davo_comm_unique_id.argtypes = [vp, ctypes.c_char_p, i]
     L.davo_comm_init.argtypes = [vp, i, i, vp]

@@ -7,9 +7,10 @@
 //   entry.hip       extern "C": the calls that take a batch (device, streaming and host forward families, both layouts), delivery
 //   export.hip      extern "C": the feature and heat exports (davo_set_*_export, davo_forward_features, davo_forward_heat)
 //   hooks.hip       extern "C": measurement and test hooks (davo_debug_read, davo_conv2d_same, plan and profile calls, memory helpers)
-//   forward.hip     the forward plan of the pose path (which buffers, in what order; the conv layers as plan.hip decides them)
+//   forward.hip     the forward of the pose path, issued: validate, ensure weights, decide_forward (plan.hip), then run_front / run_layers / run_head
 //   range_guard.hip the f16x3 range guard: records, verdicts, calibration, re-issues, tickets (its bookkeeping: range_book.h)
-//   plan.hip        launch planning: tile shapes, whole-round launch splits and every launch decision of a conv layer (pure host logic)
+//   plan.hip        launch planning: tile shapes, whole-round launch splits, every launch decision of a conv layer and the launch sequence of a
+//                   whole forward (decide_forward: front, packer, layer records, head) - pure host logic
 //   weights.hip     weight re-layout: HWIO float32 -> packed f32 / split-fp16 operands
 //   launch_f32.hip  conv_igemm_f32 instantiations + dispatch
 //   launch_h3.hip   conv_igemm_h3 instantiations + dispatch (the f16x3 path, the long compile)

@@ -1,4 +1,7 @@
-// forward.hip — the forward plan of the pose path on one context:
+// forward.hip — the forward of the pose path on one context, issued: forward_device validates, ensures the weights of the mode that
+// runs, asks plan.hip's decide_forward for the launch sequence (a fixed-size record: front, packer, seven layer records, head) and
+// walks it - run_front, run_layers, run_head, which only issue.  Nothing here chooses a kernel or knows the map or channel ladder.
+// The sequence:
 //
 //   se_squeeze_partial (se_class_squeeze for the class-table sources) -> se_excite -> mask_pack -> cnv1..cnv5 -> cnv6 (rotation|translation
 //   fused into one N = 2*cnv6_out GEMM, both read cnv5: nets/posenn.py:222-238)
@@ -92,8 +95,6 @@ int prof_collect(davo_ctx* c) {
 namespace {
 
 constexpr int MAX_WEIGHT_CHANNEL_SPREAD_LOG2 = 14;     // f16x3 per-channel guard (weights.hip)
-constexpr int FOLD_EXCITE_MAX_BATCH = 2;       // auto modes: largest batch that folds the excitation / fuses mask + pack into cnv1
-constexpr int FUSE_PACK_MAX_BATCH = 0;        // measured level at every batch (cnv1 +5 us for mask_pack's 6.7): nowhere by default
 
 // ---- tile orders ------------------------------------------------------------------------------------
 // One cache for every launch's table (davo_ctx::tile_orders): `build' is asked once per key for the order, an empty one meaning
@@ -210,14 +211,19 @@ int launched(davo_ctx* c, int li, int family, hipError_t e) {
     return DAVO_OK;
 }
 
-// FP32-MFMA path.  fuse_pose (cnv7): the pose head runs in the epilogue (conv_igemm.h); *pose_mt receives the layer's M tiles
-int run_conv_layer(davo_ctx* c, const Run& run, int li, const float* x, int x_ld, int Hin, int Win, float* y, int y_ld, int NB, bool fuse_pose = false, int* pose_mt = nullptr) {
+// the tiles a fused cnv7 left its pose sums in: tile height, M tiles, N tiles (pose_from_tiles reads them back)
+struct PoseTiles { int bm = 0, mt = 0, ntn = 0; };
+
+// FP32-MFMA path.  call.fuse_pose (cnv7): the pose head runs in the epilogue (conv_igemm.h) on tiles of 128 rows x 8 N tiles; *tiles receives them
+int run_conv_layer(davo_ctx* c, const Run& run, const LayerCall& call, const float* x, float* y, PoseTiles* tiles) {
+    const int li = call.li, Hin = call.Hin, Win = call.Win, NB = call.NB;
+    const bool fuse_pose = call.fuse_pose;
     const ConvLayer& L = c->L[li];
-    const LayerDecision<ConvParams> d = decide_layer_f32(L, LayerCall{li, x_ld, Hin, Win, y_ld, true, NB, fuse_pose, false}, plan_options(c, li));
+    const LayerDecision<ConvParams> d = decide_layer_f32(L, call, plan_options(c, li));
     if (d.err) return fail(c, d.err, "%s", d.msg);
     float* pose_partial = nullptr;
     if (d.pose_floats) { int rs = slot_scratch(c, run, &c->d_pose_tiles, &c->pose_tiles_floats, d.pose_floats, &pose_partial); if (rs) return rs; }
-    if (fuse_pose && pose_mt) *pose_mt = d.pose_mt;
+    if (fuse_pose) *tiles = PoseTiles{128, d.pose_mt, 8};
     c->last_plan[li][0] = d.plan_code[0]; c->last_plan[li][1] = d.plan_code[1]; c->last_split[li] = d.split;
     const ConvParams& g = d.steps[0].p[0];
     const PadTables* pc = nullptr;
@@ -250,12 +256,12 @@ int run_conv_layer(davo_ctx* c, const Run& run, int li, const float* x, int x_ld
 }
 
 // f16x3 path: x and y are split-fp16 blocked tensors (y float32 when y_f32).  pose_out: the launch's last workgroup writes the poses
-int run_conv_layer_h3(davo_ctx* c, const Run& run, int li, const void* x, int x_ch, int Hin, int Win, void* y, int y_ld,
-                      bool y_f32, int NB, bool fuse_pose = false, int* pose_bm = nullptr, int* pose_mt = nullptr,
-                      int* pose_ntn = nullptr, float* pose_out = nullptr) {
+int run_conv_layer_h3(davo_ctx* c, const Run& run, const LayerCall& call, const void* x, void* y, PoseTiles* tiles, float* pose_out) {
+    const int li = call.li, Hin = call.Hin;
+    const bool fuse_pose = call.fuse_pose;
     const ConvLayer& L = c->L[li];
-    const bool six = fuse_pose && coupled(c);       // the coupled head's six pred columns: the NC = 6 epilogue, pred as [2][256][3]
-    const LayerDecision<ConvParamsH> d = decide_layer_h3(L, LayerCall{li, x_ch, Hin, Win, y_ld, y_f32, NB, fuse_pose, pose_out != nullptr, six}, plan_options(c, li));
+    const bool six = call.pose_six;                 // the coupled head's six pred columns: the NC = 6 epilogue, pred as [2][256][3]
+    const LayerDecision<ConvParamsH> d = decide_layer_h3(L, call, plan_options(c, li));
     if (d.err) return fail(c, d.err, "%s", d.msg);
     // scratch before the launches that use it (growing it may synchronise every slot), the device probe before any profiling scope
     float *pose_partial = nullptr, *part = nullptr;
@@ -267,11 +273,7 @@ int run_conv_layer_h3(davo_ctx* c, const Run& run, int li, const void* x, int x_
         c->xcd_rr = ok;
     }
     const bool fold = d.fold_if_xcd && c->xcd_rr > 0;
-    if (fuse_pose) {
-        if (pose_bm) *pose_bm = d.pose_bm;
-        if (pose_mt) *pose_mt = d.pose_mt;
-        if (pose_ntn) *pose_ntn = d.pose_ntn;
-    }
+    if (fuse_pose) *tiles = PoseTiles{d.pose_bm, d.pose_mt, d.pose_ntn};
     c->last_plan[li][0] = d.plan_code[0]; c->last_plan[li][1] = d.plan_code[1]; c->last_split[li] = d.split;
     uint8_t* const y8 = static_cast<uint8_t*>(y);
     unsigned* const range = run.range ? run.range + li : nullptr;
@@ -319,27 +321,28 @@ int run_conv_layer_h3(davo_ctx* c, const Run& run, int li, const void* x, int x_
 }
 
 // cnv1 / cnv2 / cnv3 (li 0..2) from an LDS-staged input patch: conv_patch_h3.h (x and y split-fp16 blocked) or, f32, conv_patch_f32.h
-// (x and y float32 NHWC).  fused (f16x3 cnv1): the patch is built from the raw inputs (mask + pack fused in); otherwise it is
-// copied from x, for cnv1 the packed tensor.
-struct PatchLayer { int tw, th, per_cu, plan_id; };       // output tile; workgroups per CU, each walks its tiles; id in last_plan
+// (x and y float32 NHWC).  RUN_PATCH_FUSED (f16x3 cnv1): the patch is built from the raw inputs (mask + pack fused in); otherwise it is
+// copied from x, for cnv1 the packed tensor - for RUN_PATCH_CNV1T the three-frame PoseNN's 16-channel one (conv_patch_cnv1t_h3).
+struct PatchLayer { int tw, th, per_cu; };       // output tile; workgroups per CU, each walks its tiles
 constexpr PatchLayer PATCH_LAYERS[3] = {
-    {cp1::TW, cp1::TH, 3, 99},
-    {cp2::TW, cp2::TH, 2, 98},       // f16x3: 120 weight registers per lane; float32: three per CU measured 4 % slower
-    {cp3::TW, cp3::TH, 3, 97}};      // its padding, cp3::RATE on every side, is what SAME padding gives a 3x3 at dilation 2
+    {cp1::TW, cp1::TH, 3},
+    {cp2::TW, cp2::TH, 2},       // f16x3: 120 weight registers per lane; float32: three per CU measured 4 % slower
+    {cp3::TW, cp3::TH, 3}};      // its padding, cp3::RATE on every side, is what SAME padding gives a 3x3 at dilation 2
 
-int run_patch_layer(davo_ctx* c, const Run& run, int li, bool f32, const void* x, void* y, int NB, bool fused = false, const Inputs& in = Inputs{}) {
+int run_patch_layer(davo_ctx* c, const Run& run, int li, const LayerPlan& r, bool f32, const void* x, void* y, int NB, const Inputs& in) {
     const ConvLayer& L = c->L[li];
     const PatchLayer& t = PATCH_LAYERS[li];
+    const bool fused = r.runner == RUN_PATCH_FUSED, cnv1t = r.runner == RUN_PATCH_CNV1T;
+    const int per_cu = cnv1t ? cp1t::PER_CU : t.per_cu;
     const uint8_t* const w_h3[3] = {c->d_w1patch.get(), c->d_w2patch.get(), c->d_w3patch.get()};
     const float* const w_f32[3] = {c->d_w1patch_f32.get(), c->d_w2patch_f32.get(), c->d_w3patch_f32.get()};
-    const int Hin[3] = {c->H, c->H1, c->H2}, Win[3] = {c->W, c->W1, c->W2};
     ConvPatchParams p{};
-    same_pad(Hin[li], L.KS, L.stride, L.rate, &p.Ho, &p.pad_t);
-    same_pad(Win[li], L.KS, L.stride, L.rate, &p.Wo, &p.pad_l);
+    same_pad(r.Hin, L.KS, L.stride, L.rate, &p.Ho, &p.pad_t);
+    same_pad(r.Win, L.KS, L.stride, L.rate, &p.Wo, &p.pad_l);
     p.x = static_cast<const uint8_t*>(x); p.w = f32 ? reinterpret_cast<const uint8_t*>(w_f32[li]) : w_h3[li];
     p.bias = f32 ? L.d_b.get() : L.d_bh.get(); p.y = static_cast<uint8_t*>(y);
     p.zeros = reinterpret_cast<const uint8_t*>(c->d_zeros.get());
-    p.H = Hin[li]; p.W = Win[li];
+    p.H = r.Hin; p.W = r.Win;
     p.tiles_x = (p.Wo + t.tw - 1) / t.tw; p.tiles_y = (p.Ho + t.th - 1) / t.th;
     p.ntiles = NB * p.tiles_x * p.tiles_y;
     if (!f32) {      // stored activations carry 2^act_shift (exact); cnv1's input carries none
@@ -348,94 +351,211 @@ int run_patch_layer(davo_ctx* c, const Run& run, int li, bool f32, const void* x
         p.bias_scale = ldexpf(L.wscale, sin);
         p.range = run.range ? run.range + li : nullptr;
         if (const char* e = tuning_env("DAVO_PDBG")) p.dbg = atoi(e);      // tuning build only
-        if (li == 0) {
+        if (li == 0 && !cnv1t) {
             p.img = static_cast<const uint8_t*>(in.img); p.flow = in.flow;
             p.seg = in.seg; p.tab = c->slots[run.slot].d_tab.get(); p.v = c->v; p.sel = run.pairs;
         }
     }
-    c->last_plan[li][0] = ((NB * p.Ho * p.Wo + 127) / 128) * 1000 + t.plan_id; c->last_plan[li][1] = 0; c->last_split[li] = 1;
-    const int nblk = p.ntiles < t.per_cu * c->ncu ? p.ntiles : t.per_cu * c->ncu;
+    c->last_plan[li][0] = r.plan_code; c->last_plan[li][1] = 0; c->last_split[li] = 1;
+    const int nblk = p.ntiles < per_cu * c->ncu ? p.ntiles : per_cu * c->ncu;
     ProfScope ps(c, run.stream, L.label);
-    HIP_TRY(c, launch_patch_layer(li, f32, fused, p, nblk, run.stream, c->fmt));
+    HIP_TRY(c, launch_patch_layer(li, f32, fused, cnv1t, p, nblk, run.stream, c->fmt));
     return DAVO_OK;
 }
 
-// cnv1 of the three-frame PoseNN from an LDS-staged patch (conv_patch_cnv1t_h3): x the 16-channel split-fp16 packed tensor
-constexpr int PATCH_CNV1T_PLAN_ID = 96;
-int run_patch_cnv1t(davo_ctx* c, const Run& run, const void* x, void* y, int NB) {
-    const ConvLayer& L = c->L[0];
-    ConvPatchParams p{};
-    same_pad(c->H, L.KS, L.stride, L.rate, &p.Ho, &p.pad_t);
-    same_pad(c->W, L.KS, L.stride, L.rate, &p.Wo, &p.pad_l);
-    p.x = static_cast<const uint8_t*>(x); p.w = c->d_w1patch.get(); p.bias = L.d_bh.get(); p.y = static_cast<uint8_t*>(y);
-    p.zeros = reinterpret_cast<const uint8_t*>(c->d_zeros.get());
-    p.H = c->H; p.W = c->W;
-    p.tiles_x = (p.Wo + cp1::TW - 1) / cp1::TW; p.tiles_y = (p.Ho + cp1::TH - 1) / cp1::TH;
-    p.ntiles = NB * p.tiles_x * p.tiles_y;
-    p.out_scale = ldexpf(1.0f / L.wscale, c->act_shift[0]);       // cnv1's input carries no storage scale
-    p.bias_scale = L.wscale;
-    p.range = run.range;                                          // word 0 of the record is cnv1's
-    if (const char* e = tuning_env("DAVO_PDBG")) p.dbg = atoi(e);      // tuning build only
-    c->last_plan[0][0] = ((NB * p.Ho * p.Wo + 127) / 128) * 1000 + PATCH_CNV1T_PLAN_ID; c->last_plan[0][1] = 0; c->last_split[0] = 1;
-    const int nblk = p.ntiles < cp1t::PER_CU * c->ncu ? p.ntiles : cp1t::PER_CU * c->ncu;
-    ProfScope ps(c, run.stream, L.label);
-    HIP_TRY(c, launch_patch_cnv1t(p, nblk, run.stream));
-    return DAVO_OK;
-}
-
-int run_direct(davo_ctx* c, const Run& run, const char* label, const float* x, int N, int Hin, int Win, int cin, int x_ld,
-               int x_coff, const std::string& wname, const std::string& bname, int KS, int cout, int stride,
-               int rate, float* y, int y_ld, int y_coff) {
+// impl 1, group g of layer li: the direct convolution on the raw HWIO weights of the reference's scopes
+int run_direct(davo_ctx* c, const Run& run, int li, const LayerPlan& r, int g, const float* x, float* y, int NB) {
+    static const char* const heads[2] = {"rotation/", "translation/"};
+    const ConvLayer& L = c->L[li];
+    const std::string scope = li < 5 ? std::string("pose_exp_net/") : std::string("pose_exp_net/pose/") + (coupled(c) ? "" : heads[g]);
+    const std::string wname = scope + L.label + "/weights", bname = scope + L.label + "/biases";
     int Ho, Wo, pt, pl;
-    same_pad(Hin, KS, stride, rate, &Ho, &pt);
-    same_pad(Win, KS, stride, rate, &Wo, &pl);
+    same_pad(r.Hin, L.KS, L.stride, L.rate, &Ho, &pt);
+    same_pad(r.Win, L.KS, L.stride, L.rate, &Wo, &pl);
     for (const std::string* n : {&wname, &bname}) {            // impl 1 is the only reader of the raw device copies: made on demand
         HostTensor& t = c->weights.at(*n);
         if (!t.dev) { int rc = upload(c, t.data, &t.dev); if (rc) return rc; }
     }
-    ProfScope ps(c, run.stream, label);
-    HIP_TRY(c, launch_conv_direct(x, N, Hin, Win, cin, x_ld, x_coff, c->weights.at(wname).dev.get(), KS, cout,
-                                  c->weights.at(bname).dev.get(), stride, rate, pt, pl, Ho, Wo, 1, y, y_ld, y_coff, run.stream));
+    ProfScope ps(c, run.stream, L.label);
+    HIP_TRY(c, launch_conv_direct(x, NB, r.Hin, r.Win, r.cin, r.x_ch, r.x_coff[g], c->weights.at(wname).dev.get(), L.KS, r.cout,
+                                  c->weights.at(bname).dev.get(), L.stride, L.rate, pt, pl, Ho, Wo, 1, y, r.y_ld, r.y_coff[g], run.stream));
     return DAVO_OK;
 }
 
-// feature attention (posenn_se.h): cnv5 (x, in the mode's storage) -> the slot's d_se = [x s_r | x s_r s_t], 512 channels of cnv5's geometry
-int run_posenn_se(davo_ctx* c, const Run& run, bool h3, const void* x, int NB) {
-    static const char* const heads[2] = {"rotation", "translation"};
-    static const char* const parts[4] = {"bottleneck_fc/kernel", "bottleneck_fc/bias", "recover_fc/kernel", "recover_fc/bias"};
-    const float* w[8];
-    for (int h = 0; h < 2; ++h)
+// feature attention (posenn_se.h): cnv5 (x, in the mode's storage, P pixels per image) -> the slot's d_se = [x s_r | x s_r s_t], 512 channels of cnv5's geometry
+int run_posenn_se(davo_ctx* c, const Run& run, bool h3, const void* x, int NB, int P) {
+    SeDense w[2];
+    for (int h = 0; h < 2; ++h) {
+        const std::string scope = std::string("pose_exp_net/pose/") + (h ? "translation" : "rotation") + "/cnv5_se_attention/";
+        const float** const slot[4] = {&w[h].w1, &w[h].b1, &w[h].w2, &w[h].b2};
+        const char* const parts[4] = {"bottleneck_fc/kernel", "bottleneck_fc/bias", "recover_fc/kernel", "recover_fc/bias"};
         for (int k = 0; k < 4; ++k) {
-            const auto it = c->weights.find(std::string("pose_exp_net/pose/") + heads[h] + "/cnv5_se_attention/" + parts[k]);
+            const auto it = c->weights.find(scope + parts[k]);
             if (it == c->weights.end() || !it->second.dev) return fail(c, DAVO_ERR_NOT_READY, "feature-attention weights not loaded");
-            w[h * 4 + k] = it->second.dev.get();
+            *slot[k] = it->second.dev.get();
         }
+    }
     if (!c->slots[run.slot].se) return fail(c, DAVO_ERR_INVALID, "internal: no feature-attention workspace");
     const SeWorkspace& ws = *c->slots[run.slot].se;
-    const int P = c->H2 * c->W2;
     {
         ProfScope ps(c, run.stream, "se5_squeeze");
         HIP_TRY(c, launch_se5_squeeze(h3, x, NB, P, ws.d_se_partial.get(), run.stream));
     }
     {
         ProfScope ps(c, run.stream, "se5_excite");
-        HIP_TRY(c, launch_se5_excite(ws.d_se_partial.get(), NB, P, h3 ? ldexpf(1.0f, -c->act_shift[4]) : 1.0f, w, ws.d_se_scale.get(), run.stream));
+        HIP_TRY(c, launch_se5_excite(ws.d_se_partial.get(), NB, P, h3 ? ldexpf(1.0f, -c->act_shift[4]) : 1.0f, w[0], w[1], ws.d_se_scale.get(), run.stream));
     }
     ProfScope ps(c, run.stream, "se5_scale");
     HIP_TRY(c, launch_se5_scale(h3, x, ws.d_se_scale.get(), NB, P, ws.d_se.get(), (h3 && run.range) ? run.range + RANGE_SE : nullptr, run.stream));
     return DAVO_OK;
 }
 
+// ---- the forward: decided in plan.hip (decide_forward), issued here -----------------------------------------------------------------
+// the weights of the mode that really runs, on the device: -> MODE_*; f16x3 falls back to float32 on the weight-spread guard
+int ensure_weights(davo_ctx* c, const Run& run, int* mode, bool* f32_fallback) {
+    if (!c->pred_ready) { int rc = build_pred_weights(c); if (rc) return rc; }
+    bool h3 = run.impl == 0 && run.precision == 1;
+    *f32_fallback = false;
+    if (h3 && !c->packed_h_ready) { int rc = build_packed_weights_h3(c); if (rc) return rc; }
+    if (h3 && c->weight_channel_spread_log2 > MAX_WEIGHT_CHANNEL_SPREAD_LOG2) {
+        // a consumer's per-input-channel weight norms span more than 2^14: per-layer storage scales cannot keep every channel's fp16
+        // pair float32-grade (weights.hip).  The reference's float32 graph has no such limit (nets/posenn.py:205-215): float32 kernels.
+        if (!c->opt_auto_range)
+            return fail(c, DAVO_ERR_RANGE, "`%s': per-input-channel weight norms span 2^%d (> 2^%d): the f16x3 storage cannot hold every channel "
+                        "float32-grade - davo_set_precision(ctx, 0), or leave \"auto_range\" on", c->weight_channel_spread_layer.c_str(),
+                        c->weight_channel_spread_log2, MAX_WEIGHT_CHANNEL_SPREAD_LOG2);
+        h3 = false;
+        *f32_fallback = true;                // counted once per API call by the caller (api.hip)
+        char note[256];
+        snprintf(note, sizeof note, "float32 kernels: per-input-channel weight norms of `%s' span 2^%d (> 2^%d)",
+                 c->weight_channel_spread_layer.c_str(), c->weight_channel_spread_log2, MAX_WEIGHT_CHANNEL_SPREAD_LOG2);
+        c->range_report = note;
+    }
+    if (!h3 && run.impl == 0 && !c->packed_ready) { int rc = build_packed_weights(c); if (rc) return rc; }      // float32 kernels: packed at their first use
+    *mode = h3 ? MODE_H3 : run.impl == 0 ? MODE_F32 : MODE_DIRECT;
+    return DAVO_OK;
+}
+
+// the context's settings and the batch's wishes decide_forward reads; the tuning build's environment is read here
+ForwardOptions forward_options(const davo_ctx* c, const Run& run) {
+    auto env = [](const char* name) { const char* e = tuning_env(name); return e ? atoi(e) : -1; };
+    ForwardOptions o;
+    o.fold_tails = c->opt_fold_tails; o.fuse_pack = c->opt_fuse_pack; o.fuse_pose = c->opt_fuse_pose;
+    o.patch_cnv1_t = c->opt_patch_cnv1_t; o.patch_cnv2 = c->opt_patch_cnv2; o.patch_cnv3 = c->opt_patch_cnv3; o.patch_f32 = c->opt_patch_f32;
+    for (int i = 0; i < 7; ++i) o.forced_tile[i] = c->L[i].tile_h >= 0;
+    o.have_patch_f32[0] = (bool)c->d_w1patch_f32; o.have_patch_f32[1] = (bool)c->d_w2patch_f32; o.have_patch_f32[2] = (bool)c->d_w3patch_f32;
+    o.npad7 = c->L[6].npad;
+    o.zero_record = run.zero_record; o.want_snapshot = run.snap.record != nullptr;
+    o.env_fuse_pack = env("DAVO_FUSE_PACK"); o.env_patch[0] = env("DAVO_CNV1_PATCH"); o.env_patch[1] = env("DAVO_CNV2_PATCH"); o.env_patch[2] = env("DAVO_CNV3_PATCH");
+    return o;
+}
+
+// the attention front and the packer: squeeze, excitation(s), mask + pack
+int run_front(davo_ctx* c, const Run& run, const ForwardPlan& p, int B, const Inputs& in) {
+    const Slot& ws = c->slots[run.slot];
+    const Variant& v = c->v;
+    const int H = c->H, W = c->W, HW = H * W, sel = run.pairs, kind = p.front.kind;
+    const bool fold = p.front.fold_excite;
+    hipStream_t s = run.stream;
+    float *const d_partial = ws.d_partial.get(), *const d_tab = ws.d_tab.get(), *const d_tab_far = ws.d_tab_far.get();
+    unsigned* const d_counters = ws.d_counters.get() + 1;      // [1 + b]: triplet b's squeeze ticket
+    const uint8_t* const d_img = static_cast<const uint8_t*>(in.img);
+    auto wdev = [&](const char* n) -> const float* {
+        auto it = c->weights.find(n);
+        return it == c->weights.end() ? nullptr : it->second.dev.get();
+    };
+    const int a = v.att_source;
+    const SeDense w{wdev(se_weight_name(a, 0)), wdev(se_weight_name(a, 1)), wdev(se_weight_name(a, 2)), wdev(se_weight_name(a, 3))};
+    SeDense far;
+    if (kind == FRONT_FLOW_SPLIT) {
+        far = SeDense{wdev(se_far_weight_name(0)), wdev(se_far_weight_name(1)), wdev(se_far_weight_name(2)), wdev(se_far_weight_name(3))};
+        if (!d_tab_far || !w || !far) return fail(c, DAVO_ERR_INVALID, "internal: the depth-split attention's tables or dense tensors are missing");
+    }
+    if (kind == FRONT_POOLED && (!ws.d_desc || !w)) return fail(c, DAVO_ERR_INVALID, "internal: the pooled attention's descriptor buffer or dense tensors are missing");
+    const float* const wstatic = (kind == FRONT_FLOW || p.front.excite) ? wdev("pose_exp_net/pose_exp_net/seg_channel_weight/weight") : nullptr;
+    auto reset = [&](int label) -> unsigned* { return p.front.reset_at == label ? run.range : nullptr; };      // the launch that zeroes the record's per-batch word
+    if (p.front.squeeze) {
+        const int label = p.launch[0];
+        ProfScope ps(c, s, forward_label(label));
+        if (kind == FRONT_POOLED)             // the window sums of the context's pool plan (se_pool.h)
+            HIP_TRY(c, launch_se_pool_squeeze(in.flow, c->fmt, B, H, W, v, c->pool, d_partial, sel, s));
+        else if (kind == FRONT_DEPTH)         // one float32 sum per depth plane and chunk
+            HIP_TRY(c, launch_se_depth_squeeze(fold, in.depth, c->fmt, B, HW, v, reinterpret_cast<unsigned*>(d_partial), d_counters, w, d_tab, reset(label), sel, s));
+        else if (kind == FRONT_CLASS)         // segmentation / rgb / seg+flow sources: per-frame histogram, byte or flow sums
+            HIP_TRY(c, launch_se_class_squeeze(fold, d_img, in.flow, in.seg, c->fmt, B, H, W, v, reinterpret_cast<unsigned*>(d_partial), d_counters, w, d_tab, reset(label), sel, s));
+        else if (fold && kind == FRONT_FLOW_SPLIT)      // the triplet's last workgroup evaluates the near and the far tables from the same sums
+            HIP_TRY(c, launch_se_squeeze_excite_split(in.flow, c->fmt, B, HW, v, d_partial, d_counters, w, far, d_tab, d_tab_far, reset(label), sel, s));
+        else if (fold)                        // the workgroup that delivers a triplet's last partial sum evaluates its tables
+            HIP_TRY(c, launch_se_squeeze_excite(in.flow, c->fmt, B, HW, v, d_partial, d_counters, w, wstatic, d_tab, reset(label), sel, s));
+        else
+            HIP_TRY(c, launch_se_squeeze(in.flow, c->fmt, B, HW, v, d_partial, sel, s));
+    }
+    if (kind == FRONT_POOLED) {
+        ProfScope ps(c, s, "se_pool_excite");
+        HIP_TRY(c, launch_se_pool_excite(d_partial, B, v, c->pool, w, d_tab, ws.d_desc.get(), reset(LB_SE_POOL_EXCITE), sel, s));
+    }
+    if (p.front.excite) {
+        ProfScope ps(c, s, "se_excite");
+        HIP_TRY(c, launch_se_excite(d_partial, B, HW, v, w, wstatic, d_tab, reset(LB_SE_EXCITE), sel, s));
+    }
+    if (p.front.excite_far) {                 // the same launch again on the far MLP, reading the same partial sums
+        ProfScope ps(c, s, "se_excite_far");
+        HIP_TRY(c, launch_se_excite(d_partial, B, HW, v, far, nullptr, d_tab_far, nullptr, sel, s));
+    }
+    if (p.pack.kind == PACK_NONE) return DAVO_OK;
+    ProfScope ps(c, s, "mask_pack");
+    if (p.pack.kind == PACK_TRIPLET) HIP_TRY(c, launch_mask_pack3(p.mode == MODE_H3, d_img, in.flow, in.seg, c->fmt, d_tab, v, B, H, W, ws.d_packed.get(), s));
+    else HIP_TRY(c, launch_mask_pack(p.pack.ld, d_img, in.flow, in.seg, c->fmt, d_tab, v, B, H, W, ws.d_packed.get(), sel, s, in.depth, d_tab_far, c->depth_thr));
+    return DAVO_OK;
+}
+
+// cnv1..cnv7, each on the runner its record names; impl 1 walks cnv6 and cnv7 once per head
+int run_layers(davo_ctx* c, const Run& run, const ForwardPlan& p, const Inputs& in, float* d_pose, PoseTiles* tiles) {
+    const Slot& ws = c->slots[run.slot];
+    const bool h3 = p.mode == MODE_H3;
+    auto buffer = [&](int b) -> float* { return b == BUF_PACKED ? ws.d_packed.get() : b == BUF_SE ? (ws.se ? ws.se->d_se.get() : nullptr) : ws.d_act[b].get(); };
+    auto run_layer = [&](int li, int g) {
+        const LayerPlan& r = p.layer[li];
+        const float* const x = buffer(r.x_buf);
+        float* const y = ws.d_act[li].get();
+        switch (r.runner) {
+            case RUN_IGEMM_H3: return run_conv_layer_h3(c, run, layer_call(p, li), x, y, tiles, r.pose_tail ? d_pose : nullptr);
+            case RUN_IGEMM_F32: return run_conv_layer(c, run, layer_call(p, li), x, y, tiles);
+            case RUN_DIRECT: return run_direct(c, run, li, r, g, x, y, p.NB);
+            default: return run_patch_layer(c, run, li, r, !h3, x, y, p.NB, in);
+        }
+    };
+    int rc;
+    for (int li = 0; li < 5; ++li)
+        if ((rc = run_layer(li, 0))) return rc;
+    if (p.se5 && (rc = run_posenn_se(c, run, h3, ws.d_act[4].get(), p.NB, p.layer[4].Hout * p.layer[4].Wout))) return rc;
+    for (int g = 0; g < p.layer[5].ngroups; ++g)
+        for (int li = 5; li < 7; ++li)
+            if ((rc = run_layer(li, g))) return rc;
+    return DAVO_OK;
+}
+
+// the poses, unless cnv7's launch wrote them, and the range guard's snapshot where no pose_from_tiles carries it
+int run_head(davo_ctx* c, const Run& run, const ForwardPlan& p, const PoseTiles& t, float* d_pose) {
+    const Slot& ws = c->slots[run.slot];
+    const int P = p.layer[6].Hout * p.layer[6].Wout;
+    if (p.head.kind != HEAD_TAIL) {
+        ProfScope ps(c, run.stream, "pose_head");
+        if (p.head.kind == HEAD_TILES)
+            HIP_TRY(c, launch_pose_from_tiles(static_cast<const float*>(c->d_pose_tiles.get()) + (size_t)run.slot * c->pose_tiles_floats, p.NB, P, t.bm, t.mt, t.ntn,
+                                              c->d_bpred.get(), d_pose, p.mode == MODE_H3 ? run.snap : SnapArgs{}, run.pairs, run.stream));
+        else
+            HIP_TRY(c, launch_pose_head(p.head.cols, p.head.heads, ws.d_act[6].get(), p.NB, P, c->d_wpred.get(), c->d_bpred.get(), ws.d_pose_partial.get(), d_pose,
+                                        run.pairs, run.stream));
+    }
+    if (p.head.snapshot_launch) HIP_TRY(c, launch_range_guard_snapshot(run.snap, run.stream));      // api.hip: tickets
+    return DAVO_OK;
+}
+
 }  // namespace
 
+// validate, ensure weights, decide, issue
 int forward_device(davo_ctx* c, const Run& run, int B, const Inputs& in, void* d_pose, RunResult* res) {
-    const int sel = run.pairs;
-    if (sel != PAIRS_SRC0 && sel != PAIRS_SRC1 && sel != PAIRS_BOTH) return fail(c, DAVO_ERR_INVALID, "internal: pair selection %d", sel);
-    const bool tri = triplet(c);       // the three-frame PoseNN: one image per window, both poses from one pass
-    const bool cpl = coupled(c);       // the coupled network: one cnv6, one cnv7 over all of it, one head of six pred columns
-    if (cpl && (tri || c->posenn_se || c->L[5].groups != 1 || c->L[6].groups != 1 || c->L[6].cin != c->v.cnv6_out))
-        return fail(c, DAVO_ERR_INVALID, "internal: the coupled PoseNN runs on the pair topology with one-group cnv6 and cnv7");
-    if (tri && (sel != PAIRS_BOTH || run.impl != 0)) return fail(c, DAVO_ERR_INVALID, "internal: the three-frame PoseNN runs both pairs on the MFMA kernels (pairs %d, impl %d)", sel, run.impl);
     if (B < 1 || B > c->max_batch) return fail(c, DAVO_ERR_INVALID, "batch %d outside [1,%d]", B, c->max_batch);
     if (!in.img || !in.flow || !in.seg || !d_pose) return fail(c, DAVO_ERR_INVALID, "null device pointer");
     if (needs_depth(c) && (!in.depth || ((uintptr_t)in.depth & 15)))
@@ -447,224 +567,25 @@ int forward_device(davo_ctx* c, const Run& run, int B, const Inputs& in, void* d
     HIP_TRY(c, hipSetDevice(c->device));
     c->forward_seen = true;
     c->last_slot = run.slot;
-    if (!c->pred_ready) { int rc = build_pred_weights(c); if (rc) return rc; }
-    bool h3 = run.impl == 0 && run.precision == 1, f32_fallback = false;
-    if (h3 && !c->packed_h_ready) { int rc = build_packed_weights_h3(c); if (rc) return rc; }
-    if (h3 && c->weight_channel_spread_log2 > MAX_WEIGHT_CHANNEL_SPREAD_LOG2) {
-        // a consumer's per-input-channel weight norms span more than 2^14: per-layer storage scales cannot keep every channel's fp16
-        // pair float32-grade (weights.hip).  The reference's float32 graph has no such limit (nets/posenn.py:205-215): float32 kernels.
-        if (!c->opt_auto_range)
-            return fail(c, DAVO_ERR_RANGE, "`%s': per-input-channel weight norms span 2^%d (> 2^%d): the f16x3 storage cannot hold every channel "
-                        "float32-grade - davo_set_precision(ctx, 0), or leave \"auto_range\" on", c->weight_channel_spread_layer.c_str(),
-                        c->weight_channel_spread_log2, MAX_WEIGHT_CHANNEL_SPREAD_LOG2);
-        h3 = false;
-        f32_fallback = true;                 // counted once per API call by the caller (api.hip)
-        char note[256];
-        snprintf(note, sizeof note, "float32 kernels: per-input-channel weight norms of `%s' span 2^%d (> 2^%d)",
-                 c->weight_channel_spread_layer.c_str(), c->weight_channel_spread_log2, MAX_WEIGHT_CHANNEL_SPREAD_LOG2);
-        c->range_report = note;
-    }
-    if (!h3 && run.impl == 0 && !c->packed_ready) { int rc = build_packed_weights(c); if (rc) return rc; }      // float32 kernels: packed at their first use
-    unsigned* const range_reset = (h3 && run.zero_record) ? run.range : nullptr;
-
-    const int H = c->H, W = c->W, HW = H * W, NB = batch_images(c, B, sel);
-    const Variant& v = c->v;
-    const Slot& ws = c->slots[run.slot];
-    float *const d_partial = ws.d_partial.get(), *const d_tab = ws.d_tab.get(), *const d_packed = ws.d_packed.get();
-    float* const d_se = ws.se ? ws.se->d_se.get() : nullptr;                  // feature attention: cnv6's input (run_posenn_se fills it)
-    unsigned* const d_counters = ws.d_counters.get();
-    float* a[7];
-    for (int i = 0; i < 7; ++i) a[i] = ws.d_act[i].get();
-    hipStream_t s = run.stream;
-    const uint8_t* const d_img = static_cast<const uint8_t*>(in.img);
-    const void* const d_flow = in.flow;                        // float32 or binary16: c->fmt.flow
-    const void* const d_seg = in.seg;                          // float32 or bytes: c->fmt.label
-    auto wdev = [&](const char* n) -> const float* {
-        auto it = c->weights.find(n);
-        return it == c->weights.end() ? nullptr : it->second.dev.get();
-    };
-    // Launches are ~6 us each whatever they do; at batch 1 the path is 11 of them around 0.1 ms of work.  Where a launch can be
-    // folded into its neighbour at less than that, small batches do it (measured per batch: profiles/):
-    //   the excitation MLP in the squeeze launch's last workgroup (costs two memory-side round trips per workgroup: +2 us at
-    //   B = 1, +18 us at B = 32), mask + pack inside cnv1's patch fill (level at B = 32).
-    const bool class_table = att_class_table(v.att_source);
-    const bool fold_excite = (att_flow_squeeze(v.att_source) || class_table) &&
-                             (c->opt_fold_tails >= 1 || (c->opt_fold_tails < 0 && B <= FOLD_EXCITE_MAX_BATCH));
-    const bool fold_pose = c->opt_fold_tails == 1;
-    const float* se_w1 = wdev(se_weight_name(v.att_source, 0));
-    const float* se_b1 = wdev(se_weight_name(v.att_source, 1));
-    const float* se_w2 = wdev(se_weight_name(v.att_source, 2));
-    const float* se_b2 = wdev(se_weight_name(v.att_source, 3));
-    const bool depth_split = v.att_source == ATT_DEPTH_SPLIT;
-    const float* far_w[4] = {nullptr, nullptr, nullptr, nullptr};
-    float* const d_tab_far = ws.d_tab_far.get();
-    if (depth_split) {
-        for (int k = 0; k < 4; ++k) far_w[k] = wdev(se_far_weight_name(k));
-        if (!d_tab_far || !se_w1 || !se_b1 || !se_w2 || !se_b2 || !far_w[0] || !far_w[1] || !far_w[2] || !far_w[3])
-            return fail(c, DAVO_ERR_INVALID, "internal: the depth-split attention's tables or dense tensors are missing");
-    }
-    const bool pooled = att_pooled(v.att_source);
-    if (pooled) {
-        // pooled flow attention (se_pool.h): the window sums of the context's pool plan, then the excitation as a launch of its own
-        // ("fold_tails" does not apply to these sources)
-        if (!ws.d_desc || !se_w1 || !se_b1 || !se_w2 || !se_b2) return fail(c, DAVO_ERR_INVALID, "internal: the pooled attention's descriptor buffer or dense tensors are missing");
-        {
-            ProfScope ps(c, run.stream, "se_pool_squeeze");
-            HIP_TRY(c, launch_se_pool_squeeze(d_flow, c->fmt, B, H, W, v, c->pool, d_partial, sel, s));
-        }
-        ProfScope ps(c, run.stream, "se_pool_excite");
-        HIP_TRY(c, launch_se_pool_excite(d_partial, B, v, c->pool, se_w1, se_b1, se_w2, se_b2, d_tab, ws.d_desc.get(), range_reset, sel, s));
-    } else if (att_desc_depth(v.att_source)) {
-        // depth sources: one float32 sum per depth plane and chunk, then (or, folded, in the same launch) the excitation
-        ProfScope ps(c, run.stream, "se_depth_squeeze");
-        HIP_TRY(c, launch_se_depth_squeeze(fold_excite, in.depth, c->fmt, B, HW, v, reinterpret_cast<unsigned*>(d_partial),
-                                           d_counters + 1, se_w1, se_b1, se_w2, se_b2, d_tab, range_reset, sel, s));
-    } else if (class_table) {
-        // segmentation / rgb / seg+flow sources: per-frame histogram, byte or flow sums, then (or, folded, in the same launch) the
-        // excitation
-        ProfScope ps(c, run.stream, "se_class_squeeze");
-        HIP_TRY(c, launch_se_class_squeeze(fold_excite, d_img, d_flow, d_seg, c->fmt, B, H, W, v, reinterpret_cast<unsigned*>(d_partial),
-                                           d_counters + 1, se_w1, se_b1, se_w2, se_b2, d_tab, range_reset, sel, s));
-    } else if (fold_excite && depth_split) {
-        // the flagship's squeeze; the triplet's last workgroup evaluates the near tables and the far tables from the same sums
-        ProfScope ps(c, run.stream, "se_squeeze_partial");
-        const float* near_w[4] = {se_w1, se_b1, se_w2, se_b2};
-        HIP_TRY(c, launch_se_squeeze_excite_split(d_flow, c->fmt, B, HW, v, d_partial, d_counters + 1, near_w, far_w, d_tab, d_tab_far, range_reset, sel, s));
-    } else if (fold_excite) {
-        // squeeze + excitation in one launch: the workgroup that delivers a triplet's last partial sum evaluates its tables
-        ProfScope ps(c, run.stream, "se_squeeze_partial");
-        HIP_TRY(c, launch_se_squeeze_excite(d_flow, c->fmt, B, HW, v, d_partial, d_counters + 1,
-                                            se_w1, se_b1, se_w2, se_b2,
-                                            wdev("pose_exp_net/pose_exp_net/seg_channel_weight/weight"), d_tab, range_reset, sel, s));
-    } else if (att_flow_squeeze(v.att_source)) {
-        ProfScope ps(c, run.stream, "se_squeeze_partial");
-        HIP_TRY(c, launch_se_squeeze(d_flow, c->fmt, B, HW, v, d_partial, sel, s));
-    }
-    if (!fold_excite && !pooled) {
-        ProfScope ps(c, run.stream, "se_excite");
-        HIP_TRY(c, launch_se_excite(d_partial, B, HW, v, se_w1, se_b1, se_w2, se_b2,
-                                    wdev("pose_exp_net/pose_exp_net/seg_channel_weight/weight"), d_tab, range_reset, sel, s));
-    }
-    if (!fold_excite && depth_split) {
-        // depth-split: the same launch again on the far MLP, reading the same partial sums (a profile entry of its own, so that
-        // "se_excite" is one launch per forward in every variant)
-        ProfScope ps(c, run.stream, "se_excite_far");
-        HIP_TRY(c, launch_se_excite(d_partial, B, HW, v, far_w[0], far_w[1], far_w[2], far_w[3], nullptr, d_tab_far, nullptr, sel, s));
-    }
-    // f16x3, fuse_pack: cnv1 builds its input patch straight from the raw inputs (mask + pack fused in,
-    // the packed tensor never touches HBM).  Measured equal in time to mask_pack + cnv1 (the fused fill is bound
-    // by its byte loads), so the two-kernel form stays the default.  Tuning build: DAVO_FUSE_PACK=1 / DAVO_CNV1_PATCH=0.
-    const char* fe = tuning_env("DAVO_FUSE_PACK");
-    const char* pe = tuning_env("DAVO_CNV1_PATCH");
-    const bool fuse_env = (fe && atoi(fe) == 1) || c->opt_fuse_pack == 1 || (c->opt_fuse_pack < 0 && B <= FUSE_PACK_MAX_BATCH);
-    const bool patch1 = !(pe && atoi(pe) == 0);
-    // (the depth-split attention has no fused fill: its packer is always mask_pack's depth-split form, whatever "fuse_pack" says)
-    const bool fused = h3 && patch1 && fuse_env && !depth_split && !tri;
-    c->packed_valid = !fused;
+    int mode = MODE_H3, rc;
+    bool f32_fallback = false;
+    if ((rc = ensure_weights(c, run, &mode, &f32_fallback))) return rc;
+    const ForwardCall call{c->H, c->W, B, run.pairs, mode, c->v, triplet(c), coupled(c), c->posenn_se, c->L[5].groups, c->L[6].groups, c->L[6].cin};
+    const ForwardPlan p = decide_forward(call, forward_options(c, run));
+    if (p.err) return fail(c, p.err, "%s", p.msg);
+    c->packed_valid = p.pack.packed_valid;
     c->last_in = in;
-    c->packed_ld = tri ? 16 : (run.impl == 0 ? 8 : 10);
-    if (tri) {
-        ProfScope ps(c, run.stream, "mask_pack");
-        HIP_TRY(c, launch_mask_pack3(h3, d_img, d_flow, d_seg, c->fmt, d_tab, v, B, H, W, d_packed, s));
-    } else if (!fused) {
-        ProfScope ps(c, run.stream, "mask_pack");
-        HIP_TRY(c, launch_mask_pack(h3 ? 16 : (run.impl == 0 ? 8 : 10), d_img, d_flow, d_seg, c->fmt, d_tab, v, B, H, W, d_packed, sel, s,
-                                    in.depth, d_tab_far, c->depth_thr));
-    }
-    const int c6 = v.cnv6_out;
-    const int ch6 = cpl ? c6 : 2 * c6, ch7 = cpl ? 256 : 512;      // channels per pixel of the stored cnv6 and cnv7
-    int rc;
-    bool pose_fused = false;
-    int pose_bm = 0, pose_mt = 0, pose_ntn = 0;
+    c->packed_ld = p.pack.packed_ld;
     c->cnv7_valid = true;
-    if (h3) {
-        if (tri) {
-            // cnv1 at 16 packed channels: the LDS-patch kernel ("patch_cnv1_t"), else the implicit GEMM at cin = 16
-            if (c->opt_patch_cnv1_t && c->L[0].tile_h < 0) { if ((rc = run_patch_cnv1t(c, run, d_packed, a[0], NB))) return rc; }
-            else if ((rc = run_conv_layer_h3(c, run, 0, d_packed, 16, H, W, a[0], 16, false, NB))) return rc;
-        }
-        else if (patch1) { if ((rc = run_patch_layer(c, run, 0, false, d_packed, a[0], NB, fused, in))) return rc; }
-        else if ((rc = run_conv_layer_h3(c, run, 0, d_packed, 8, H, W, a[0], 16, false, NB))) return rc;
-        const char* p2e = tuning_env("DAVO_CNV2_PATCH");
-        if (c->opt_patch_cnv2 && c->L[1].tile_h < 0 && !(p2e && atoi(p2e) == 0)) { if ((rc = run_patch_layer(c, run, 1, false, a[0], a[1], NB))) return rc; }
-        else if ((rc = run_conv_layer_h3(c, run, 1, a[0], 16, c->H1, c->W1, a[1], 32, false, NB))) return rc;
-        const char* p3e = tuning_env("DAVO_CNV3_PATCH");
-        if (c->opt_patch_cnv3 && c->L[2].tile_h < 0 && !(p3e && atoi(p3e) == 0)) { if ((rc = run_patch_layer(c, run, 2, false, a[1], a[2], NB))) return rc; }
-        else if ((rc = run_conv_layer_h3(c, run, 2, a[1], 32, c->H2, c->W2, a[2], 64, false, NB))) return rc;
-        if ((rc = run_conv_layer_h3(c, run, 3, a[2], 64, c->H2, c->W2, a[3], 128, false, NB))) return rc;
-        if ((rc = run_conv_layer_h3(c, run, 4, a[3], 128, c->H2, c->W2, a[4], 256, false, NB))) return rc;
-        if (c->posenn_se) {
-            if ((rc = run_posenn_se(c, run, true, a[4], NB))) return rc;
-            if ((rc = run_conv_layer_h3(c, run, 5, d_se, 512, c->H2, c->W2, a[5], 2 * c6, false, NB))) return rc;
-        } else if ((rc = run_conv_layer_h3(c, run, 5, a[4], 256, c->H2, c->W2, a[5], ch6, false, NB))) return rc;
-        // the three-frame PoseNN stores cnv7 (the fused epilogue has three columns per head); the coupled one fuses its six columns (NC = 6)
-        pose_fused = c->opt_fuse_pose && c->H3 * c->W3 >= 128 && !tri;
-        if ((rc = run_conv_layer_h3(c, run, 6, a[5], ch6, c->H2, c->W2, a[6], ch7, true, NB, pose_fused, &pose_bm, &pose_mt, &pose_ntn,
-                                    fold_pose ? static_cast<float*>(d_pose) : nullptr))) return rc;
-        c->cnv7_valid = !pose_fused;
-    } else if (run.impl == 0) {
-        if (c->opt_patch_f32 && c->d_w1patch_f32 && c->packed_ld == 8) { if ((rc = run_patch_layer(c, run, 0, true, d_packed, a[0], NB))) return rc; }
-        else if ((rc = run_conv_layer(c, run, 0, d_packed, tri ? 16 : 8, H, W, a[0], 16, NB))) return rc;      // the three-frame PoseNN: conv_igemm_f32 at cin = 16
-        if (c->opt_patch_f32 && c->d_w2patch_f32) { if ((rc = run_patch_layer(c, run, 1, true, a[0], a[1], NB))) return rc; }
-        else if ((rc = run_conv_layer(c, run, 1, a[0], 16, c->H1, c->W1, a[1], 32, NB))) return rc;
-        if (c->opt_patch_f32 && c->d_w3patch_f32) { if ((rc = run_patch_layer(c, run, 2, true, a[1], a[2], NB))) return rc; }
-        else if ((rc = run_conv_layer(c, run, 2, a[1], 32, c->H2, c->W2, a[2], 64, NB))) return rc;
-        if ((rc = run_conv_layer(c, run, 3, a[2], 64, c->H2, c->W2, a[3], 128, NB))) return rc;
-        if ((rc = run_conv_layer(c, run, 4, a[3], 128, c->H2, c->W2, a[4], 256, NB))) return rc;
-        if (c->posenn_se) {
-            if ((rc = run_posenn_se(c, run, false, a[4], NB))) return rc;
-            if ((rc = run_conv_layer(c, run, 5, d_se, 512, c->H2, c->W2, a[5], 2 * c6, NB))) return rc;
-        } else if ((rc = run_conv_layer(c, run, 5, a[4], 256, c->H2, c->W2, a[5], ch6, NB))) return rc;
-        // float32 mode, round 4: the pose head in cnv7's epilogue like the f16x3 path's (the 109 MB activation is neither written nor
-        // read back, pose_head_partial + pose_finish become pose_from_tiles); tiles of 128 rows must not span more than two images
-        pose_fused = c->opt_fuse_pose && c->H3 * c->W3 >= 128 && c->L[6].npad == 256 && !tri && !cpl;
-        pose_bm = 128; pose_ntn = 8;
-        if ((rc = run_conv_layer(c, run, 6, a[5], ch6, c->H2, c->W2, a[6], ch7, NB, pose_fused, &pose_mt))) return rc;
-        c->cnv7_valid = !pose_fused;
-    } else {
-        const std::string P = "pose_exp_net/";
-        const int c10 = 2 * v.cin_per_frame;
-        if (v.cin_per_frame != 5) return fail(c, DAVO_ERR_INVALID, "impl 1 supports the 10-channel (v1) input only");
-        if ((rc = run_direct(c, run, "cnv1", d_packed, NB, H, W, c10, 10, 0, P + "cnv1/weights", P + "cnv1/biases", 7, 16, 2, 1, a[0], 16, 0))) return rc;
-        if ((rc = run_direct(c, run, "cnv2", a[0], NB, c->H1, c->W1, 16, 16, 0, P + "cnv2/weights", P + "cnv2/biases", 5, 32, 2, 1, a[1], 32, 0))) return rc;
-        if ((rc = run_direct(c, run, "cnv3", a[1], NB, c->H2, c->W2, 32, 32, 0, P + "cnv3/weights", P + "cnv3/biases", 3, 64, 1, 2, a[2], 64, 0))) return rc;
-        if ((rc = run_direct(c, run, "cnv4", a[2], NB, c->H2, c->W2, 64, 64, 0, P + "cnv4/weights", P + "cnv4/biases", 3, 128, 1, 4, a[3], 128, 0))) return rc;
-        if ((rc = run_direct(c, run, "cnv5", a[3], NB, c->H2, c->W2, 128, 128, 0, P + "cnv5/weights", P + "cnv5/biases", 3, 256, 1, 8, a[4], 256, 0))) return rc;
-        if (c->posenn_se && (rc = run_posenn_se(c, run, false, a[4], NB))) return rc;      // float32 NHWC like the float32 mode's cnv5
-        const char* heads[2] = {"rotation", "translation"};
-        if (cpl) {      // the one head: cnv6 from all of cnv5, cnv7 from all of cnv6
-            const std::string hp = P + "pose/";
-            if ((rc = run_direct(c, run, "cnv6", a[4], NB, c->H2, c->W2, 256, 256, 0, hp + "cnv6/weights", hp + "cnv6/biases", 3, c6, 1, 2, a[5], c6, 0))) return rc;
-            if ((rc = run_direct(c, run, "cnv7", a[5], NB, c->H2, c->W2, c6, c6, 0, hp + "cnv7/weights", hp + "cnv7/biases", 3, 256, 2, 1, a[6], 256, 0))) return rc;
-        } else for (int h = 0; h < 2; ++h) {
-            const std::string hp = P + "pose/" + heads[h] + "/";
-            // feature attention: head h reads its half of the scaled tensor
-            const float* x6 = c->posenn_se ? d_se : a[4];
-            if ((rc = run_direct(c, run, "cnv6", x6, NB, c->H2, c->W2, 256, c->posenn_se ? 512 : 256, c->posenn_se ? h * 256 : 0, hp + "cnv6/weights", hp + "cnv6/biases", 3, c6, 1, 2, a[5], 2 * c6, h * c6))) return rc;
-            if ((rc = run_direct(c, run, "cnv7", a[5], NB, c->H2, c->W2, c6, 2 * c6, h * c6, hp + "cnv7/weights", hp + "cnv7/biases", 3, 256, 2, 1, a[6], 512, h * 256))) return rc;
-        }
-    }
-    bool snap_done = false;
-    if (!(pose_fused && fold_pose)) {
-        ProfScope ps(c, run.stream, "pose_head");
-        if (pose_fused) {
-            HIP_TRY(c, launch_pose_from_tiles(static_cast<const float*>(c->d_pose_tiles.get()) + (size_t)run.slot * c->pose_tiles_floats, NB, c->H3 * c->W3, pose_bm,
-                                              pose_mt, pose_ntn, c->d_bpred.get(), static_cast<float*>(d_pose), h3 ? run.snap : SnapArgs{}, sel, s));
-            snap_done = true;
-        } else if (cpl) {
-            HIP_TRY(c, launch_pose_head_coupled(a[6], NB, c->H3 * c->W3, c->d_wpred.get(), c->d_bpred.get(), ws.d_pose_partial.get(), static_cast<float*>(d_pose), sel, s));
-        } else if (tri) {
-            HIP_TRY(c, launch_pose_head6(a[6], B, c->H3 * c->W3, c->d_wpred.get(), c->d_bpred.get(), ws.d_pose_partial.get(), static_cast<float*>(d_pose), s));
-        } else {
-            HIP_TRY(c, launch_pose_head(a[6], NB, c->H3 * c->W3, c->d_wpred.get(), c->d_bpred.get(), ws.d_pose_partial.get(), static_cast<float*>(d_pose), sel, s));
-        }
-    }
-    // the range guard's conditional copy of this batch's inputs (api.hip: tickets) rides in pose_from_tiles; other pose heads get a launch
-    if (h3 && run.snap.record && !snap_done) HIP_TRY(c, launch_range_guard_snapshot(run.snap, s));
+    PoseTiles tiles;
+    if ((rc = run_front(c, run, p, B, in))) return rc;
+    if ((rc = run_layers(c, run, p, in, static_cast<float*>(d_pose), &tiles))) return rc;
+    c->cnv7_valid = p.head.cnv7_valid;
+    if ((rc = run_head(c, run, p, tiles, static_cast<float*>(d_pose)))) return rc;
     c->last_B = B;
-    c->last_pairs = sel;
-    c->last_precision = h3 ? 1 : 0;
-    if (res) *res = RunResult{h3, f32_fallback};
+    c->last_pairs = run.pairs;
+    c->last_precision = mode == MODE_H3 ? 1 : 0;
+    if (res) *res = RunResult{mode == MODE_H3, f32_fallback};
     return DAVO_OK;
 }
 

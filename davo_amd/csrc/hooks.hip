@@ -12,6 +12,15 @@
 
 using namespace davo;
 
+// the seven layers as a context of these settings holds them (api.hip: davo_create and the davo_set_posenn_* calls, "force_tile")
+static void hook_layers(ConvLayer (&L)[7], int cnv6_out, bool posenn_se, bool tri, bool cpl, int force_tile) {
+    init_posenn_layers(L, cnv6_out);
+    if (tri) init_layer(L[0], "cnv1", 7, 2, 1, 16, 16, 1);
+    if (posenn_se) init_layer(L[5], "cnv6", 3, 1, 2, 256, cnv6_out, 2);          // davo_set_posenn_se: one group per head
+    if (cpl) init_coupled_head(L, cnv6_out);
+    for (ConvLayer& l : L) l.tile_h = forced_tile_h(force_tile, l.cout);
+}
+
 extern "C" {
 
 int davo_host_alloc(int device, size_t bytes, void** out) {
@@ -244,10 +253,10 @@ int davo_decide_layer(int precision, int layer, int H, int W, int NB, int cnv6_o
         n_options < 0 || n_options > DAVO_DECIDE_OPTIONS)
         return DAVO_ERR_INVALID;
     PlanOptions o;
-    int force_tile = -1, pose_tail = 0, posenn_se = 0;
+    int force_tile = -1, pose_tail = 0, posenn_se = 0, tri = 0, cpl = 0;
     int* const slot[DAVO_DECIDE_OPTIONS] = {&o.wave128, &o.skip_order, &o.merge_order, &o.pad_classes, &o.merge_rem_f32, nullptr, nullptr, nullptr, nullptr, nullptr,
                                             nullptr, nullptr, nullptr, nullptr, &o.ncu, &o.dev_cus, nullptr, nullptr, &o.max_batch, &o.shift_in, &o.shift_out,
-                                            &force_tile, &pose_tail, &posenn_se};
+                                            &force_tile, &pose_tail, &posenn_se, &tri, &cpl};
     bool* const flag[DAVO_DECIDE_OPTIONS] = {nullptr, nullptr, nullptr, nullptr, nullptr, &o.share_taps, &o.merge_rem, &o.merge_cnv4, &o.tile_208x128, &o.deep_ring,
                                              &o.split_k, &o.fold_fixup, &o.f32_n16, &o.f32_n256, nullptr, nullptr, &o.cu_partition, &o.user_stream};
     for (int i = 0; i < n_options; ++i) {
@@ -255,15 +264,16 @@ int davo_decide_layer(int precision, int layer, int H, int W, int NB, int cnv6_o
         else *flag[i] = options[i] != 0;
     }
     if (o.ncu < 1 || o.dev_cus < 1 || o.max_batch < 1 || force_tile < -1 || force_tile >= NUM_TILES) return DAVO_ERR_INVALID;
-    // the ladder of forward_device: cnv1 reads the 8-channel packed frame pair, cnv2 and cnv3 halve the map, cnv7 stores float32
+    // the layer's input and output as decide_forward lays a forward of NB images out (one pair, or the three-frame PoseNN's NB windows)
     ConvLayer L[7];
-    init_posenn_layers(L, cnv6_out);
-    if (posenn_se) init_layer(L[5], "cnv6", 3, 1, 2, 256, cnv6_out, 2);          // davo_set_posenn_se: one group per head
-    for (ConvLayer& l : L) l.tile_h = forced_tile_h(force_tile, l.cout);
-    const int H1 = (H + 1) / 2, W1 = (W + 1) / 2, H2 = (H1 + 1) / 2, W2 = (W1 + 1) / 2;
-    const int x_ch[7] = {8, 16, 32, 64, 128, posenn_se ? 512 : 256, 2 * cnv6_out}, y_ld[7] = {16, 32, 64, 128, 256, 2 * cnv6_out, 512};
-    const LayerCall call{layer, x_ch[layer], layer == 0 ? H : layer == 1 ? H1 : H2, layer == 0 ? W : layer == 1 ? W1 : W2, y_ld[layer],
-                         precision == 0 || layer == 6, NB, fuse_pose != 0, pose_tail != 0};
+    hook_layers(L, cnv6_out, posenn_se != 0, tri != 0, cpl != 0, force_tile);
+    Variant v{};
+    v.cin_per_frame = 5; v.cnv6_out = cnv6_out;
+    const ForwardPlan fp = decide_forward(ForwardCall{H, W, NB, tri ? PAIRS_BOTH : PAIRS_SRC1, precision == 1 ? MODE_H3 : MODE_F32, v, tri != 0, cpl != 0, posenn_se,
+                                                      L[5].groups, L[6].groups, L[6].cin}, ForwardOptions{});
+    if (fp.err) return fp.err;
+    LayerCall call = layer_call(fp, layer);
+    call.fuse_pose = fuse_pose != 0; call.pose_tail = pose_tail != 0; call.pose_six = fuse_pose && cpl && precision == 1;
     int n = 0;
     auto put = [&](long v) { if (n < out_cap) out[n] = (int)v; ++n; };
     // m_end: one past the step's last output row; deep, family_ok: f16x3 only (the family's own predicate on the step's own block)
@@ -298,6 +308,44 @@ int davo_decide_layer(int precision, int layer, int H, int W, int NB, int cnv6_o
                              : s.family == FAM_H3S        ? is_208(s.tile)
                                                           : !is_208(s.tile);
                   });
+}
+
+int davo_decide_forward(const int* call, const int* options, int n_options, int* out, int out_cap) {
+    if (!call || !out || (n_options > 0 && !options) || n_options < 0 || n_options > DAVO_FORWARD_OPTIONS) return DAVO_ERR_INVALID;
+    const int H = call[0], W = call[1], B = call[2], mode = call[4], cnv6_out = call[6], topology = call[8], heads = call[9], posenn_se = call[10];
+    if (H < 1 || W < 1 || B < 1 || mode < MODE_H3 || mode > MODE_DIRECT || call[5] < 0 || call[5] > ATT_MAX || cnv6_out < 1 ||
+        (topology != DAVO_POSENN_PAIRS && topology != DAVO_POSENN_TRIPLET) || (heads != DAVO_POSENN_HEADS_DECOUPLED && heads != DAVO_POSENN_HEADS_COUPLED))
+        return DAVO_ERR_INVALID;
+    ForwardOptions o;
+    int force_tile = -1, fuse_pose = 1, patch[4] = {1, 1, 1, 1}, zero_record = 0, want_snapshot = 0;
+    int* const slot[DAVO_FORWARD_OPTIONS] = {&o.fold_tails, &o.fuse_pack, &fuse_pose, &patch[0], &patch[1], &patch[2], &patch[3], &force_tile, &zero_record, &want_snapshot};
+    for (int i = 0; i < n_options; ++i) *slot[i] = options[i];
+    if (force_tile < -1 || force_tile >= NUM_TILES) return DAVO_ERR_INVALID;
+    o.fuse_pose = fuse_pose != 0; o.patch_cnv1_t = patch[0] != 0; o.patch_cnv2 = patch[1] != 0; o.patch_cnv3 = patch[2] != 0; o.patch_f32 = patch[3] != 0;
+    o.zero_record = zero_record != 0; o.want_snapshot = want_snapshot != 0;
+    const bool tri = topology == DAVO_POSENN_TRIPLET, cpl = heads == DAVO_POSENN_HEADS_COUPLED;
+    ConvLayer L[7];
+    hook_layers(L, cnv6_out, posenn_se != 0 && !cpl, tri, cpl, force_tile);
+    for (int i = 0; i < 7; ++i) o.forced_tile[i] = L[i].tile_h >= 0;
+    o.have_patch_f32[0] = !tri;                                // weights.hip: the three-frame cnv1 has no float32 patch weights
+    o.npad7 = L[6].npad;
+    Variant v{};
+    v.att_source = call[5]; v.cnv6_out = cnv6_out; v.cin_per_frame = call[7];
+    const ForwardPlan p = decide_forward(ForwardCall{H, W, B, call[3], mode, v, tri, cpl, posenn_se, L[5].groups, L[6].groups, L[6].cin}, o);
+    if (p.err) return p.err;
+    int n = 0;
+    auto put = [&](int x) { if (n < out_cap) out[n] = x; ++n; };
+    for (int x : {p.NB, p.front.kind, (int)p.front.squeeze, (int)p.front.fold_excite, (int)p.front.excite, (int)p.front.excite_far, p.front.reset_at, p.pack.kind,
+                  p.pack.ld, p.pack.packed_ld, (int)p.pack.packed_valid, (int)p.se5, p.head.kind, p.head.cols, p.head.heads, (int)p.head.snapshot_launch,
+                  (int)p.head.cnv7_valid})
+        put(x);
+    for (const LayerPlan& r : p.layer)
+        for (int x : {r.runner, r.label, r.x_buf, r.x_ch, r.Hin, r.Win, r.y_ld, r.Hout, r.Wout, (int)r.y_f32, (int)r.fuse_pose, (int)r.pose_tail, (int)r.pose_six,
+                      r.plan_code, r.ngroups, r.cin, r.cout, r.x_coff[0], r.x_coff[1], r.y_coff[0], r.y_coff[1]})
+            put(x);
+    put(p.nlaunch);
+    for (int i = 0; i < p.nlaunch; ++i) put(p.launch[i]);
+    return n;
 }
 
 int davo_conv2d_same(int device, const float* x, int N, int H, int W, int Cin, const float* w, int k, int Cout,

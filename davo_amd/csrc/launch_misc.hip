@@ -59,56 +59,53 @@ hipError_t launch_se_squeeze(const void* d_flow, const InputFormat& fmt, int B, 
     });
 }
 
-hipError_t launch_se_excite(const float* d_partial, int B, int HW, const Variant& v, const float* w1, const float* b1,
-                            const float* w2, const float* b2, const float* wstatic, float* d_tab, unsigned* d_range_reset, int sel, hipStream_t s) {
-    hipLaunchKernelGGL(se_excite, dim3(B, 3), dim3(64), 0, s, d_partial, HW, v, w1, b1, w2, b2, wstatic, d_tab, d_range_reset, sel);
+hipError_t launch_se_excite(const float* d_partial, int B, int HW, const Variant& v, const SeDense& w, const float* wstatic, float* d_tab,
+                            unsigned* d_range_reset, int sel, hipStream_t s) {
+    hipLaunchKernelGGL(se_excite, dim3(B, 3), dim3(64), 0, s, d_partial, HW, v, w.w1, w.b1, w.w2, w.b2, wstatic, d_tab, d_range_reset, sel);
     return hipGetLastError();
 }
 
 hipError_t launch_se_squeeze_excite(const void* d_flow, const InputFormat& fmt, int B, int HW, const Variant& v, float* d_partial, unsigned* d_counters,
-                                    const float* w1, const float* b1, const float* w2, const float* b2, const float* wstatic,
-                                    float* d_tab, unsigned* d_range_reset, int sel, hipStream_t s) {
+                                    const SeDense& w, const float* wstatic, float* d_tab, unsigned* d_range_reset, int sel, hipStream_t s) {
     const dim3 grid(SQ_CHUNKS, pairs_per_window(sel), B);
     return with_flow(fmt, [&](auto F) {
-        hipLaunchKernelGGL(se_squeeze_excite<elem_t<decltype(F)>>, grid, dim3(256), 0, s, typed(F, d_flow), HW, v, d_partial, d_counters, w1, b1, w2, b2,
+        hipLaunchKernelGGL(se_squeeze_excite<elem_t<decltype(F)>>, grid, dim3(256), 0, s, typed(F, d_flow), HW, v, d_partial, d_counters, w.w1, w.b1, w.w2, w.b2,
                            wstatic, d_tab, d_range_reset, sel);
         return hipGetLastError();
     });
 }
 
 hipError_t launch_se_squeeze_excite_split(const void* d_flow, const InputFormat& fmt, int B, int HW, const Variant& v, float* d_partial, unsigned* d_counters,
-                                          const float* const near_w[4], const float* const far_w[4], float* d_tab, float* d_tab_far,
+                                          const SeDense& near, const SeDense& far_w, float* d_tab, float* d_tab_far,
                                           unsigned* d_range_reset, int sel, hipStream_t s) {
-    if (v.att_source != ATT_DEPTH_SPLIT || !d_tab_far) return hipErrorInvalidValue;
-    for (int k = 0; k < 4; ++k) if (!near_w[k] || !far_w[k]) return hipErrorInvalidValue;
-    const SeFar far{far_w[0], far_w[1], far_w[2], far_w[3], d_tab_far};
+    if (v.att_source != ATT_DEPTH_SPLIT || !d_tab_far || !near || !far_w) return hipErrorInvalidValue;
+    const SeFar far{far_w.w1, far_w.b1, far_w.w2, far_w.b2, d_tab_far};
     const dim3 grid(SQ_CHUNKS, pairs_per_window(sel), B);
     return with_flow(fmt, [&](auto F) {
         hipLaunchKernelGGL(se_squeeze_excite_split<elem_t<decltype(F)>>, grid, dim3(256), 0, s, typed(F, d_flow), HW, v, d_partial, d_counters,
-                           near_w[0], near_w[1], near_w[2], near_w[3], d_tab, d_range_reset, sel, far);
+                           near.w1, near.b1, near.w2, near.b2, d_tab, d_range_reset, sel, far);
         return hipGetLastError();
     });
 }
 
 hipError_t launch_se_class_squeeze(bool fold, const uint8_t* d_img, const void* d_flow, const void* d_seg, const InputFormat& fmt, int B, int H, int W,
-                                  const Variant& v, unsigned* d_partial, unsigned* d_counters, const float* w1, const float* b1,
-                                  const float* w2, const float* b2, float* d_tab, unsigned* d_range_reset, int sel, hipStream_t s) {
+                                  const Variant& v, unsigned* d_partial, unsigned* d_counters, const SeDense& w, float* d_tab,
+                                  unsigned* d_range_reset, int sel, hipStream_t s) {
     const dim3 grid(SQ_CHUNKS, att_se_frames(v.att_source) - (sel == PAIRS_BOTH ? 0 : 1), B);
     return with_flow(fmt, [&](auto F) { return with_label(fmt, [&](auto L) { return with_bool(fold, [&](auto FOLD) {
         hipLaunchKernelGGL((se_class_squeeze<decltype(FOLD)::value, elem_t<decltype(L)>, elem_t<decltype(F)>>), grid, dim3(256), 0, s, d_img,
-                           typed(F, d_flow), typed(L, d_seg), H, W, v, d_partial, d_counters, w1, b1, w2, b2, d_tab, d_range_reset, sel);
+                           typed(F, d_flow), typed(L, d_seg), H, W, v, d_partial, d_counters, w.w1, w.b1, w.w2, w.b2, d_tab, d_range_reset, sel);
         return hipGetLastError();
     }); }); });
 }
 
 hipError_t launch_se_depth_squeeze(bool fold, const void* d_depth, const InputFormat& fmt, int B, int HW, const Variant& v, unsigned* d_partial,
-                                   unsigned* d_counters, const float* w1, const float* b1, const float* w2, const float* b2,
-                                   float* d_tab, unsigned* d_range_reset, int sel, hipStream_t s) {
+                                   unsigned* d_counters, const SeDense& w, float* d_tab, unsigned* d_range_reset, int sel, hipStream_t s) {
     if (!att_desc_depth(v.att_source) || !d_depth || ((uintptr_t)d_depth & 15) || HW % 16) return hipErrorInvalidValue;
     const dim3 grid(SQ_CHUNKS, 1 + pairs_per_window(sel), B);
     return with_depth(fmt, [&](auto D) { return with_bool(fold, [&](auto FOLD) {
         hipLaunchKernelGGL((se_depth_squeeze<decltype(FOLD)::value, elem_t<decltype(D)>>), grid, dim3(256), 0, s, typed(D, d_depth), HW, v, d_partial,
-                           d_counters, w1, b1, w2, b2, d_tab, d_range_reset, sel);
+                           d_counters, w.w1, w.b1, w.w2, w.b2, d_tab, d_range_reset, sel);
         return hipGetLastError();
     }); });
 }
@@ -123,16 +120,15 @@ hipError_t launch_se_pool_squeeze(const void* d_flow, const InputFormat& fmt, in
     });
 }
 
-hipError_t launch_se_pool_excite(const float* d_partial, int B, const Variant& v, const PoolDev& pd, const float* w1, const float* b1,
-                                 const float* w2, const float* b2, float* d_tab, float* d_desc, unsigned* d_range_reset, int sel, hipStream_t s) {
+hipError_t launch_se_pool_excite(const float* d_partial, int B, const Variant& v, const PoolDev& pd, const SeDense& w, float* d_tab, float* d_desc,
+                                 unsigned* d_range_reset, int sel, hipStream_t s) {
     const int a = v.att_source;
-    if (!att_pooled(a) || 2 * pd.n_cells != att_se_in(a) || 2 * pd.n_cells > POOL_MAX_D || !pd.cell_first || !pd.inv_div ||
-        !d_partial || !w1 || !b1 || !w2 || !b2 || !d_tab || !d_desc)
+    if (!att_pooled(a) || 2 * pd.n_cells != att_se_in(a) || 2 * pd.n_cells > POOL_MAX_D || !pd.cell_first || !pd.inv_div || !d_partial || !w || !d_tab || !d_desc)
         return hipErrorInvalidValue;
     if (att_se_hidden(a) == NCLS)
-        hipLaunchKernelGGL(se_pool_excite<NCLS>, dim3(B, 3), dim3(64), 0, s, d_partial, pd, v, w1, b1, w2, b2, d_tab, d_desc, d_range_reset, sel);
+        hipLaunchKernelGGL(se_pool_excite<NCLS>, dim3(B, 3), dim3(64), 0, s, d_partial, pd, v, w.w1, w.b1, w.w2, w.b2, d_tab, d_desc, d_range_reset, sel);
     else
-        hipLaunchKernelGGL(se_pool_excite<8>, dim3(B, 3), dim3(64), 0, s, d_partial, pd, v, w1, b1, w2, b2, d_tab, d_desc, d_range_reset, sel);
+        hipLaunchKernelGGL(se_pool_excite<8>, dim3(B, 3), dim3(64), 0, s, d_partial, pd, v, w.w1, w.b1, w.w2, w.b2, d_tab, d_desc, d_range_reset, sel);
     return hipGetLastError();
 }
 
@@ -214,9 +210,16 @@ hipError_t launch_window_mirror(const GatherArgs& a, int N, bool frames, const I
     }); }); }); });
 }
 
-hipError_t launch_patch_layer(int layer, bool f32, bool fused, const ConvPatchParams& p, int nblk, hipStream_t s, const InputFormat& fmt) {
+hipError_t launch_patch_layer(int layer, bool f32, bool fused, bool cnv1t, const ConvPatchParams& p, int nblk, hipStream_t s, const InputFormat& fmt) {
     using Kernel = void (*)(ConvPatchParams);
     struct Row { Kernel h3, f32; int threads, lds; };
+    if (cnv1t) {
+        if (layer != 0 || f32 || fused || nblk < 1 || !p.x || !p.w || !p.bias || !p.y || !p.zeros || p.ntiles < 1) return hipErrorInvalidValue;
+        const hipError_t e = ensure_dynamic_lds(reinterpret_cast<const void*>(conv_patch_cnv1t_h3), cp1t::LDS_BYTES);
+        if (e != hipSuccess) return e;
+        hipLaunchKernelGGL(conv_patch_cnv1t_h3, dim3(nblk), dim3(cp1::THREADS), cp1t::LDS_BYTES, s, p);
+        return hipGetLastError();
+    }
     // the fused cnv1 of the context's label and flow elements (p.seg and p.flow are in those formats)
     Kernel cnv1_fused = nullptr;
     const hipError_t fe = with_flow(fmt, [&](auto F) { return with_label(fmt, [&](auto L) {
@@ -233,14 +236,6 @@ hipError_t launch_patch_layer(int layer, bool f32, bool fused, const ConvPatchPa
     hipError_t e = ensure_dynamic_lds(reinterpret_cast<const void*>(k), r.lds);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(k, dim3(nblk), dim3(r.threads), r.lds, s, p);
-    return hipGetLastError();
-}
-
-hipError_t launch_patch_cnv1t(const ConvPatchParams& p, int nblk, hipStream_t s) {
-    if (nblk < 1 || !p.x || !p.w || !p.bias || !p.y || !p.zeros || p.ntiles < 1) return hipErrorInvalidValue;
-    hipError_t e = ensure_dynamic_lds(reinterpret_cast<const void*>(conv_patch_cnv1t_h3), cp1t::LDS_BYTES);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(conv_patch_cnv1t_h3, dim3(nblk), dim3(cp1::THREADS), cp1t::LDS_BYTES, s, p);
     return hipGetLastError();
 }
 
@@ -286,32 +281,19 @@ hipError_t launch_range_guard_snapshot(const SnapArgs& snap, hipStream_t s) {
     return hipGetLastError();
 }
 
-hipError_t launch_pose_head(const float* d_c7, int NB, int P, const float* d_wpred, const float* d_bpred,
+hipError_t launch_pose_head(int cols, int heads, const float* d_c7, int NB, int P, const float* d_wpred, const float* d_bpred,
                             float* d_partial, float* d_pose, int sel, hipStream_t s) {
-    hipLaunchKernelGGL(pose_head_partial<3>, dim3(PH_SPLIT, NB, 2), dim3(256), 0, s, d_c7, P, d_wpred, d_partial);
-    hipError_t e = hipGetLastError();
+    if (NB < 1 || P < 1 || !d_c7 || !d_wpred || !d_bpred || !d_partial || !d_pose) return hipErrorInvalidValue;
+    const dim3 grid(PH_SPLIT, NB, heads);
+    if (cols == 3 && heads == 2) hipLaunchKernelGGL(pose_head_partial<3>, grid, dim3(256), 0, s, d_c7, P, d_wpred, d_partial);
+    else if (cols == 6 && heads == 2) hipLaunchKernelGGL(pose_head_partial<6>, grid, dim3(256), 0, s, d_c7, P, d_wpred, d_partial);
+    else if (cols == 6 && heads == 1) hipLaunchKernelGGL((pose_head_partial<6, 1>), grid, dim3(256), 0, s, d_c7, P, d_wpred, d_partial);
+    else return hipErrorInvalidValue;
+    const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(pose_finish, dim3((NB * 6 + 63) / 64), dim3(64), 0, s, d_partial, NB, P, d_bpred, d_pose, sel);
-    return hipGetLastError();
-}
-
-hipError_t launch_pose_head6(const float* d_c7, int B, int P, const float* d_wpred6, const float* d_bpred6,
-                             float* d_partial, float* d_pose, hipStream_t s) {
-    if (B < 1 || P < 1 || !d_c7 || !d_wpred6 || !d_bpred6 || !d_partial || !d_pose) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(pose_head_partial<6>, dim3(PH_SPLIT, B, 2), dim3(256), 0, s, d_c7, P, d_wpred6, d_partial);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(pose_finish6, dim3((B * 12 + 63) / 64), dim3(64), 0, s, d_partial, B, P, d_bpred6, d_pose);
-    return hipGetLastError();
-}
-
-hipError_t launch_pose_head_coupled(const float* d_c7, int NB, int P, const float* d_wpred6, const float* d_bpred6,
-                                    float* d_partial, float* d_pose, int sel, hipStream_t s) {
-    if (NB < 1 || P < 1 || !d_c7 || !d_wpred6 || !d_bpred6 || !d_partial || !d_pose) return hipErrorInvalidValue;
-    hipLaunchKernelGGL((pose_head_partial<6, 1>), dim3(PH_SPLIT, NB, 1), dim3(256), 0, s, d_c7, P, d_wpred6, d_partial);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(pose_finish_coupled, dim3((NB * 6 + 63) / 64), dim3(64), 0, s, d_partial, NB, P, d_bpred6, d_pose, sel);
+    if (cols == 3) hipLaunchKernelGGL(pose_finish, dim3((NB * 6 + 63) / 64), dim3(64), 0, s, d_partial, NB, P, d_bpred, d_pose, sel);
+    else if (heads == 2) hipLaunchKernelGGL(pose_finish6, dim3((NB * 12 + 63) / 64), dim3(64), 0, s, d_partial, NB, P, d_bpred, d_pose);
+    else hipLaunchKernelGGL(pose_finish_coupled, dim3((NB * 6 + 63) / 64), dim3(64), 0, s, d_partial, NB, P, d_bpred, d_pose, sel);
     return hipGetLastError();
 }
 
@@ -332,10 +314,9 @@ hipError_t launch_se5_squeeze(bool h3, const void* d_x, int NB, int P, float* d_
     return hipGetLastError();
 }
 
-hipError_t launch_se5_excite(const float* d_partial, int NB, int P, float unscale, const float* const se_w[8], float* d_scale, hipStream_t s) {
-    if (NB < 1 || P < 1 || !d_partial || !d_scale) return hipErrorInvalidValue;
-    for (int k = 0; k < 8; ++k) if (!se_w[k]) return hipErrorInvalidValue;
-    const Se5Weights w{se_w[0], se_w[1], se_w[2], se_w[3], se_w[4], se_w[5], se_w[6], se_w[7]};
+hipError_t launch_se5_excite(const float* d_partial, int NB, int P, float unscale, const SeDense& rot, const SeDense& trans, float* d_scale, hipStream_t s) {
+    if (NB < 1 || P < 1 || !d_partial || !d_scale || !rot || !trans) return hipErrorInvalidValue;
+    const Se5Weights w{rot.w1, rot.b1, rot.w2, rot.b2, trans.w1, trans.b1, trans.w2, trans.b2};
     hipLaunchKernelGGL(se5_excite, dim3(NB), dim3(256), 0, s, d_partial, P, unscale, w, d_scale);
     return hipGetLastError();
 }

@@ -1,7 +1,8 @@
 // plan.h — launch planning of the convolution layers: which tile shape, how a layer is split
 // into a main launch of whole rounds plus a remainder launch, and which kernel family each launch
-// runs on (LayerDecision, below).  Pure host logic (plan.hip); the test hooks davo_plan_layer and
-// davo_decide_layer (include/davo_hip.h) expose it to the CPU test-suite.
+// runs on (LayerDecision, below), and the launch sequence of a whole forward (ForwardPlan, at the end).
+// Pure host logic (plan.hip); the test hooks davo_plan_layer, davo_decide_layer and davo_decide_forward
+// (include/davo_hip.h) expose it to the CPU test-suite.
 #pragma once
 #include <vector>
 
@@ -146,5 +147,66 @@ ConvParamsH fill_params_h3(const LayerGeom& L, const LayerCall& call, bool share
 ConvParams fill_params_f32(const LayerGeom& L, const LayerCall& call);
 LayerDecision<ConvParamsH> decide_layer_h3(const LayerGeom& L, const LayerCall& call, const PlanOptions& o);
 LayerDecision<ConvParams> decide_layer_f32(const LayerGeom& L, const LayerCall& call, const PlanOptions& o);
+
+// ---- a forward's launches, decided before anything is issued -------------------------------------------------------------------
+// decide_forward is to the whole forward what decide_layer_* are to a layer: a pure function of plain values - no context, no
+// device pointer, no HIP call, no allocation - that returns the launch sequence as one fixed-size record.  forward.hip walks it
+// (run_front, run_layers, run_head: issuing only); davo_decide_forward (hooks.hip) shows it to the CPU test-suite, and
+// davo_decide_layer takes its LayerCall from the same records.  The map ladder H, H/2, H/4, ..., H/8 and the channel ladder
+// 8|16, 16, 32, 64, 128, 256|512, cnv6's width, 256|512 are written down in decide_forward and nowhere else.
+enum { MODE_H3 = 0, MODE_F32 = 1, MODE_DIRECT = 2 };      // the kernels that really run: f16x3, float32 MFMA, impl 1's direct convolution
+struct ForwardCall {
+    int H = 0, W = 0, B = 0, pairs = PAIRS_BOTH, mode = MODE_H3;
+    Variant v{};
+    bool triplet = false, coupled = false;     // davo_set_posenn_topology, davo_set_posenn_heads
+    int posenn_se = 0;                         // davo_set_posenn_se
+    int groups6 = 1, groups7 = 2, cin7 = 0;    // cnv6's and cnv7's groups and cnv7's input channels per group, as the layers were initialised
+};
+// the settings the sequence reads (davo_ctx: opt_*, L[i].tile_h, the float32 patch weights, L[6].npad), the batch's two range-guard
+// wishes (Run::zero_record, Run::snap.record) and the tuning build's DAVO_FUSE_PACK / DAVO_CNV{1,2,3}_PATCH (-1: not set)
+struct ForwardOptions {
+    int fold_tails = -1, fuse_pack = -1;
+    bool fuse_pose = true, patch_cnv1_t = true, patch_cnv2 = true, patch_cnv3 = true, patch_f32 = true;
+    bool forced_tile[7] = {false, false, false, false, false, false, false};
+    bool have_patch_f32[3] = {true, true, true};
+    int npad7 = 256;
+    bool zero_record = false, want_snapshot = false;
+    int env_fuse_pack = -1, env_patch[3] = {-1, -1, -1};
+};
+// the profile labels of a forward's launches, as indices into DAVO_FORWARD_LABELS (include/davo_hip.h; plan.hip holds the two to one length)
+enum { LB_SE_POOL_SQUEEZE = 0, LB_SE_POOL_EXCITE, LB_SE_DEPTH_SQUEEZE, LB_SE_CLASS_SQUEEZE, LB_SE_SQUEEZE_PARTIAL, LB_SE_EXCITE, LB_SE_EXCITE_FAR,
+       LB_MASK_PACK, LB_CNV1, LB_CNV2, LB_CNV3, LB_CNV4, LB_CNV5, LB_SE5_SQUEEZE, LB_SE5_EXCITE, LB_SE5_SCALE, LB_CNV6, LB_CNV7, LB_POSE_HEAD,
+       LB_SNAPSHOT, NUM_LABELS };
+enum { FRONT_FLOW = 0, FRONT_FLOW_SPLIT = 1, FRONT_CLASS = 2, FRONT_DEPTH = 3, FRONT_POOLED = 4 };
+enum { PACK_NONE = 0, PACK_PAIR = 1, PACK_TRIPLET = 2 };      // none: mask + pack run inside cnv1's patch fill
+enum { RUN_PATCH = 0, RUN_PATCH_FUSED = 1, RUN_PATCH_CNV1T = 2, RUN_IGEMM_H3 = 3, RUN_IGEMM_F32 = 4, RUN_DIRECT = 5 };
+enum { BUF_PACKED = -1, BUF_SE = -2 };                        // a layer's input: the packed tensor, the SE-scaled cnv5, else act[i]
+enum { HEAD_TAIL = 0, HEAD_TILES = 1, HEAD_TWO_PASS = 2 };    // the poses come out of cnv7's launch | pose_from_tiles | pose_head_partial + pose_finish
+struct LayerPlan {
+    int runner = RUN_IGEMM_H3, label = LB_CNV1;
+    int x_buf = BUF_PACKED, x_ch = 0, Hin = 0, Win = 0;       // x_ch as LayerCall's: channels of the whole input tensor
+    int y_ld = 0, Hout = 0, Wout = 0;                         // the output is act[layer], y_ld channels per pixel
+    bool y_f32 = false, fuse_pose = false, pose_tail = false, pose_six = false;
+    int plan_code = 0;                                        // patch runners: davo_last_plan's code (the igemm layers' come from decide_layer_*)
+    // impl 1: the layer runs once per group g < ngroups, cin channels from offset x_coff[g] of the input to cout at y_coff[g] of the output
+    int ngroups = 1, cin = 0, cout = 0, x_coff[2] = {0, 0}, y_coff[2] = {0, 0};
+};
+struct ForwardPlan {
+    int err = 0;                               // DAVO_OK, or a davo_status with msg: an internal refusal, nothing is issued
+    char msg[160] = {0};
+    int mode = MODE_H3, NB = 0;                // the call's mode; images through cnv1..cnv7
+    struct { int kind = FRONT_FLOW; bool squeeze = false, fold_excite = false, excite = false, excite_far = false; int reset_at = -1; } front;
+    struct { int kind = PACK_PAIR, ld = 16, packed_ld = 8; bool packed_valid = true; } pack;
+    LayerPlan layer[7];
+    bool se5 = false;                          // feature attention: se5_squeeze, se5_excite, se5_scale between cnv5 and cnv6
+    struct { int kind = HEAD_TWO_PASS, cols = 3, heads = 2; bool snapshot_launch = false, cnv7_valid = true; } head;
+    int nlaunch = 0, launch[24] = {0};         // the launches in issue order (LB_*; a conv layer once, whatever decide_layer_* splits it into)
+};
+ForwardPlan decide_forward(const ForwardCall& call, const ForwardOptions& o);
+const char* forward_label(int label);          // the profile entry of an LB_*
+inline LayerCall layer_call(const ForwardPlan& p, int li) {
+    const LayerPlan& r = p.layer[li];
+    return LayerCall{li, r.x_ch, r.Hin, r.Win, r.y_ld, r.y_f32, p.NB, r.fuse_pose, r.pose_tail, r.pose_six};
+}
 
 }  // namespace davo

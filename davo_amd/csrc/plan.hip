@@ -450,4 +450,130 @@ LayerDecision<ConvParamsH> decide_layer_h3(const LayerGeom& L, const LayerCall& 
     return d;
 }
 
+// ---- the whole forward ------------------------------------------------------------------------------------------------------------
+namespace {
+constexpr int FOLD_EXCITE_MAX_BATCH = 2;       // auto modes: largest batch that folds the excitation / fuses mask + pack into cnv1
+constexpr int FUSE_PACK_MAX_BATCH = 0;         // measured level at every batch (cnv1 +5 us for mask_pack's 6.7): nowhere by default
+constexpr const char* const FORWARD_LABELS[] = DAVO_FORWARD_LABELS;
+static_assert(sizeof FORWARD_LABELS / sizeof *FORWARD_LABELS == NUM_LABELS, "plan.h's LB_* index DAVO_FORWARD_LABELS");
+constexpr int PATCH_PLAN_ID[3] = {99, 98, 97}, PATCH_CNV1T_PLAN_ID = 96;       // davo_last_plan's tile ids of the patch kernels
+
+ForwardPlan refuse(ForwardPlan p, int err, const char* fmt, int a = 0, int b = 0) {
+    p.err = err;
+    snprintf(p.msg, sizeof p.msg, fmt, a, b);
+    return p;
+}
+}  // namespace
+
+const char* forward_label(int label) { return label >= 0 && label < NUM_LABELS ? FORWARD_LABELS[label] : "?"; }
+
+// Launches are ~6 us each whatever they do; at batch 1 the path is 11 of them around 0.1 ms of work.  Where a launch can be folded
+// into its neighbour at less than that, small batches do it (measured per batch: profiles/): the excitation MLP
+// in the squeeze launch's last workgroup (costs two memory-side round trips per workgroup: +2 us at B = 1, +18 us at B = 32), mask +
+// pack inside cnv1's patch fill (level at B = 32).
+ForwardPlan decide_forward(const ForwardCall& call, const ForwardOptions& o) {
+    ForwardPlan p;
+    p.mode = call.mode;
+    const int sel = call.pairs, B = call.B, a = call.v.att_source, c6 = call.v.cnv6_out;
+    const bool tri = call.triplet, cpl = call.coupled, se = call.posenn_se != 0;
+    const bool h3 = call.mode == MODE_H3, direct = call.mode == MODE_DIRECT;
+    if (sel != PAIRS_SRC0 && sel != PAIRS_SRC1 && sel != PAIRS_BOTH) return refuse(p, DAVO_ERR_INVALID, "internal: pair selection %d", sel);
+    if (cpl && (tri || se || call.groups6 != 1 || call.groups7 != 1 || call.cin7 != c6))
+        return refuse(p, DAVO_ERR_INVALID, "internal: the coupled PoseNN runs on the pair topology with one-group cnv6 and cnv7");
+    if (tri && (sel != PAIRS_BOTH || direct))
+        return refuse(p, DAVO_ERR_INVALID, "internal: the three-frame PoseNN runs both pairs on the MFMA kernels (pairs %d, impl %d)", sel, direct ? 1 : 0);
+    if (direct && call.v.cin_per_frame != 5) return refuse(p, DAVO_ERR_INVALID, "impl 1 supports the 10-channel (v1) input only");
+    p.NB = tri ? B : pairs_per_window(sel) * B;        // the three-frame PoseNN: one image per window, both poses from one pass
+    auto launch = [&](int label) { p.launch[p.nlaunch++] = label; };
+
+    // the attention front: squeeze, then (or, folded, in the squeeze launch's last workgroup) the excitation
+    const bool split = a == ATT_DEPTH_SPLIT, pooled = att_pooled(a);
+    const bool fold = (att_flow_squeeze(a) || att_class_table(a)) && (o.fold_tails >= 1 || (o.fold_tails < 0 && B <= FOLD_EXCITE_MAX_BATCH));
+    const bool fold_pose = o.fold_tails == 1;
+    p.front.kind = pooled ? FRONT_POOLED : att_desc_depth(a) ? FRONT_DEPTH : att_class_table(a) ? FRONT_CLASS : split ? FRONT_FLOW_SPLIT : FRONT_FLOW;
+    p.front.squeeze = p.front.kind != FRONT_FLOW || att_flow_squeeze(a);      // (no attention, static tables: the excitation launch alone)
+    p.front.fold_excite = fold;
+    p.front.excite = !fold && !pooled;                 // pooled: se_pool_excite, always a launch of its own ("fold_tails" does not apply)
+    p.front.excite_far = !fold && split;               // the same launch again on the far MLP, under a profile entry of its own
+    const int squeeze_label = pooled ? LB_SE_POOL_SQUEEZE : p.front.kind == FRONT_DEPTH ? LB_SE_DEPTH_SQUEEZE
+                              : p.front.kind == FRONT_CLASS ? LB_SE_CLASS_SQUEEZE : LB_SE_SQUEEZE_PARTIAL;
+    if (p.front.squeeze) launch(squeeze_label);
+    if (pooled) launch(LB_SE_POOL_EXCITE);
+    if (p.front.excite) launch(LB_SE_EXCITE);
+    if (p.front.excite_far) launch(LB_SE_EXCITE_FAR);
+    // the record's per-batch word is zeroed by the launch that evaluates the tables
+    if (h3 && o.zero_record) p.front.reset_at = pooled ? LB_SE_POOL_EXCITE : fold ? squeeze_label : LB_SE_EXCITE;
+
+    // f16x3, fuse_pack: cnv1 builds its input patch straight from the raw inputs (mask + pack fused in, the packed tensor never
+    // touches HBM).  Measured equal in time to mask_pack + cnv1 (the fused fill is bound by its byte loads), so the two-kernel form
+    // stays the default.  The depth-split attention and the three-frame PoseNN have no fused fill, whatever "fuse_pack" says.
+    const bool fuse_wanted = o.env_fuse_pack == 1 || o.fuse_pack == 1 || (o.fuse_pack < 0 && B <= FUSE_PACK_MAX_BATCH);
+    const bool patch1 = o.env_patch[0] != 0;
+    const bool fused = h3 && patch1 && fuse_wanted && !split && !tri;
+    p.pack.kind = tri ? PACK_TRIPLET : fused ? PACK_NONE : PACK_PAIR;
+    p.pack.ld = h3 ? 16 : direct ? 10 : 8;
+    p.pack.packed_ld = tri ? 16 : direct ? 10 : 8;
+    p.pack.packed_valid = !fused;
+    if (p.pack.kind != PACK_NONE) launch(LB_MASK_PACK);
+
+    // the ladders: cnv1 and cnv2 halve the map, cnv3..cnv6 keep it, cnv7 halves it again; channels per pixel of each stored tensor
+    const int H1 = (call.H + 1) / 2, W1 = (call.W + 1) / 2, H2 = (H1 + 1) / 2, W2 = (W1 + 1) / 2, H3 = (H2 + 1) / 2, W3 = (W2 + 1) / 2;
+    const int Hs[8] = {call.H, H1, H2, H2, H2, H2, H2, H3}, Ws[8] = {call.W, W1, W2, W2, W2, W2, W2, W3};
+    const int ch6 = cpl ? c6 : 2 * c6, ch7 = cpl ? 256 : 512;
+    const int packed_ch = direct ? 10 : tri ? 16 : 8;
+    const int ch[8] = {packed_ch, 16, 32, 64, 128, 256, ch6, ch7};
+    const bool big_map = H3 * W3 >= 128;               // the fused head's tiles of 128 rows must not span more than two images
+    // the three-frame PoseNN stores cnv7 (the fused epilogue has three columns per head); the coupled one fuses its six columns in
+    // f16x3 (NC = 6), float32 needs the full 256-column tile
+    const bool pose_fused = !direct && o.fuse_pose && big_map && !tri && (h3 || (o.npad7 == 256 && !cpl));
+    const bool patch_ok[3] = {h3 ? (tri ? o.patch_cnv1_t && !o.forced_tile[0] : patch1) : o.patch_f32 && o.have_patch_f32[0] && p.pack.packed_ld == 8,
+                              h3 ? o.patch_cnv2 && !o.forced_tile[1] && o.env_patch[1] != 0 : o.patch_f32 && o.have_patch_f32[1],
+                              h3 ? o.patch_cnv3 && !o.forced_tile[2] && o.env_patch[2] != 0 : o.patch_f32 && o.have_patch_f32[2]};
+    p.se5 = se;
+    for (int li = 0; li < 7; ++li) {
+        LayerPlan& r = p.layer[li];
+        r.label = li < 5 ? LB_CNV1 + li : li == 5 ? LB_CNV6 : LB_CNV7;
+        r.x_buf = li == 0 ? BUF_PACKED : (li == 5 && se) ? BUF_SE : li - 1;      // feature attention: cnv6 reads [cnv5 s_r | cnv5 s_r s_t]
+        r.x_ch = (li == 5 && se) ? 512 : ch[li];
+        r.Hin = Hs[li]; r.Win = Ws[li]; r.Hout = Hs[li + 1]; r.Wout = Ws[li + 1];
+        r.y_ld = ch[li + 1];
+        r.y_f32 = !h3 || li == 6;
+        if (direct) {
+            // impl 1: cnv6 and cnv7 once per head; with feature attention head g reads its half of the scaled tensor
+            r.runner = RUN_DIRECT;
+            const int heads = (li >= 5 && !cpl) ? 2 : 1;
+            r.ngroups = heads;
+            r.cin = li == 5 ? 256 : li == 6 ? c6 : ch[li];
+            r.cout = li == 5 ? c6 : li == 6 ? 256 : ch[li + 1];
+            for (int g = 0; g < heads; ++g) { r.x_coff[g] = (li == 5 && !se) ? 0 : g * r.cin; r.y_coff[g] = g * r.cout; }
+            continue;
+        }
+        r.runner = h3 ? RUN_IGEMM_H3 : RUN_IGEMM_F32;
+        if (li < 3 && patch_ok[li]) {
+            r.runner = (li == 0 && tri) ? RUN_PATCH_CNV1T : (li == 0 && fused) ? RUN_PATCH_FUSED : RUN_PATCH;
+            r.plan_code = ((p.NB * r.Hout * r.Wout + 127) / 128) * 1000 + (r.runner == RUN_PATCH_CNV1T ? PATCH_CNV1T_PLAN_ID : PATCH_PLAN_ID[li]);
+        }
+        if (li == 6) {
+            r.fuse_pose = pose_fused;
+            r.pose_tail = h3 && fold_pose;             // the launch's last workgroup adds the tiles and writes the poses (pose_tail.h)
+            r.pose_six = h3 && pose_fused && cpl;
+        }
+    }
+    for (int li = 0; li < 5; ++li) launch(p.layer[li].label);
+    if (se) { launch(LB_SE5_SQUEEZE); launch(LB_SE5_EXCITE); launch(LB_SE5_SCALE); }
+    for (int g = 0; g < p.layer[5].ngroups; ++g) { launch(LB_CNV6); launch(LB_CNV7); }
+
+    // the head.  "fold_tails" 1 drops the pose_head launch wherever the head is fused - in float32 too, which has no pose tail in
+    // cnv7 ("Which launches a forward gets": kept as it was found)
+    p.head.kind = (pose_fused && fold_pose) ? HEAD_TAIL : pose_fused ? HEAD_TILES : HEAD_TWO_PASS;
+    p.head.cols = (cpl || tri) ? 6 : 3;
+    p.head.heads = cpl ? 1 : 2;
+    p.head.cnv7_valid = !pose_fused;
+    if (p.head.kind != HEAD_TAIL) launch(LB_POSE_HEAD);
+    // the range guard's conditional copy of the batch's inputs rides in pose_from_tiles; every other head leaves it a launch
+    p.head.snapshot_launch = h3 && o.want_snapshot && p.head.kind != HEAD_TILES;
+    if (p.head.snapshot_launch) launch(LB_SNAPSHOT);
+    return p;
+}
+
 }  // namespace davo

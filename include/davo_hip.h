@@ -835,6 +835,8 @@ int davo_plan_layer_f32(int mtiles, int npad, int groups, int ncu, int* mtile0, 
  *   16 cu_partition    17 a caller's stream is set     18 max_batch (1)
  *   19, 20 storage shifts of the layer's input and output (0)   21 force_tile (-1)
  *   22 the launch's last workgroup writes the poses ("fold_tails" 1; 0)   23 feature attention: cnv6 as one group per head (0)
+ *   24 the three-frame PoseNN: NB windows, cnv1 at 16 packed channels (0)   25 the coupled heads: one-group cnv6 and cnv7 (0)
+ * The layer's input and output (channels, map, storage) are the record davo_decide_forward reports for that layer.
  * out[0] = steps (1 or 2), then DAVO_DECIDE_STEP_INTS per step:
  *   family (0 h3 | 1 h3s | 2 h3w | 3 h3w64 | 4 h3w128 | 5 h3 merged grid | 6 h3 split-K | 7 f32 | 8 f32 n256 | 9 f32 merged grid),
  *   tile (f16x3: the planner's tile id; float32: the N tile's columns, of the remainder for a merged grid), first output row, one past the
@@ -847,11 +849,44 @@ int davo_plan_layer_f32(int mtiles, int npad, int groups, int ncu, int* mtile0, 
  *   channel block.
  * Returns the number of ints the record holds (written up to out_cap), or a negative davo_status (DAVO_ERR_INVALID also where no tile
  * fits the fused pose head). */
-#define DAVO_DECIDE_OPTIONS 24
+#define DAVO_DECIDE_OPTIONS 26
 #define DAVO_DECIDE_STEP_INTS 18
 #define DAVO_DECIDE_TAIL_INTS 12
 int davo_decide_layer(int precision, int layer, int H, int W, int NB, int cnv6_out, int fuse_pose, const int* options, int n_options,
                       int* out, int out_cap);
+
+/* The launch sequence of one forward on its own (no GPU needed; csrc/plan.h: decide_forward): what a forward of B windows of an
+ * H x W frame issues, in order, and what each conv layer reads and writes.
+ * call[DAVO_FORWARD_CALL_INTS]: H, W, B, pair selection (1 src0 | 2 src1 | 3 both), the kernels that run (0 f16x3 | 1 float32 |
+ *   2 impl 1), the variant's att_source, cnv6_out and cin_per_frame, davo_set_posenn_topology's, davo_set_posenn_heads' and
+ *   davo_set_posenn_se's values.
+ * options[i], i < n_options <= DAVO_FORWARD_OPTIONS, in this order; the ones left out keep a new context's values:
+ *    0 fold_tails (-1)   1 fuse_pack (-1)   2 fuse_pose (1)   3 patch_cnv1_t (1)   4 patch_cnv2 (1)   5 patch_cnv3 (1)   6 patch_f32 (1)
+ *    7 force_tile (-1)   8 the batch's first kernel zeroes its range record's per-batch word (a ticketed batch; 0)
+ *    9 the batch's last kernel mirrors the range record and keeps the inputs where it fails (every f16x3 batch of an entry point; 0)
+ * out: DAVO_FORWARD_HEAD_INTS - images through cnv1..cnv7; the attention front: kind (0 flow | 1 flow, depth-split | 2 class table |
+ *   3 depth | 4 pooled), 1 = a squeeze launch, 1 = the excitation folded into it, 1 = se_excite follows, 1 = se_excite_far follows, the
+ *   label of the launch that zeroes the record (-1 none); the packer: 0 none (fused into cnv1) | 1 pair | 2 three-frame, its ld (16 | 8 |
+ *   10), the packed tensor's channels as davo_debug_read sizes it, 1 = it is in memory; 1 = se5_squeeze / se5_excite / se5_scale sit
+ *   between cnv5 and cnv6; the head: 0 written by cnv7's launch | 1 pose_from_tiles | 2 two passes, its pred columns and heads, 1 = the
+ *   range guard's snapshot is a launch of its own, 1 = cnv7 is stored -
+ * then DAVO_FORWARD_LAYER_INTS per layer cnv1..cnv7: runner (0 patch | 1 patch with mask + pack fused in | 2 three-frame cnv1 patch |
+ *   3 f16x3 implicit GEMM | 4 float32 implicit GEMM | 5 direct), label, input buffer (-1 packed | -2 the SE-scaled cnv5 | i = layer i's
+ *   output), its channels, rows and columns, the output's channels per pixel, rows and columns, 1 = float32 output, fuse_pose, pose_tail,
+ *   pose_six, davo_last_plan's code (patch runners; 0 = davo_decide_layer has it), impl 1's groups, input and output channels per group
+ *   and the two groups' input and output channel offsets -
+ * then the number of launches and their labels in issue order, as indices into DAVO_FORWARD_LABELS (a conv layer once, whatever
+ * davo_decide_layer splits it into; the last label has no profile entry).
+ * Returns the number of ints the record holds (written up to out_cap), or a negative davo_status: DAVO_ERR_INVALID for bad arguments
+ * and for every combination the forward itself refuses. */
+#define DAVO_FORWARD_LABELS {"se_pool_squeeze", "se_pool_excite", "se_depth_squeeze", "se_class_squeeze", "se_squeeze_partial", "se_excite", \
+                             "se_excite_far", "mask_pack", "cnv1", "cnv2", "cnv3", "cnv4", "cnv5", "se5_squeeze", "se5_excite", "se5_scale", \
+                             "cnv6", "cnv7", "pose_head", "range_guard_snapshot"}
+#define DAVO_FORWARD_CALL_INTS 11
+#define DAVO_FORWARD_OPTIONS 10
+#define DAVO_FORWARD_HEAD_INTS 17
+#define DAVO_FORWARD_LAYER_INTS 21
+int davo_decide_forward(const int* call, const int* options, int n_options, int* out, int out_cap);
 
 #ifdef __cplusplus
 }

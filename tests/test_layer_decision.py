@@ -10,16 +10,17 @@ import pytest
 from davo_amd import _lib
 
 import cnv6_width_cases as CW
+import forward_plan_cases as FP
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "layer_decisions.json")
 
 # include/davo_hip.h: davo_decide_layer's options, step record and tail
 OPTIONS = ("wave128", "skip_order", "merge_order", "pad_classes", "merge_rem_f32", "share_taps", "merge_rem", "merge_cnv4", "tile_208x128",
            "deep_ring", "split_k", "fold_fixup", "f32_n16", "f32_n256", "ncu", "dev_cus", "cu_partition", "user_stream", "max_batch",
-           "shift_in", "shift_out", "force_tile", "pose_tail", "posenn_se")
+           "shift_in", "shift_out", "force_tile", "pose_tail", "posenn_se", "triplet", "coupled")
 DEFAULTS = dict(wave128=2, skip_order=1, merge_order=-1, pad_classes=7, merge_rem_f32=1, share_taps=1, merge_rem=1, merge_cnv4=0,
                 tile_208x128=0, deep_ring=1, split_k=1, fold_fixup=0, f32_n16=1, f32_n256=0, ncu=256, dev_cus=256, cu_partition=0,
-                user_stream=0, max_batch=1, shift_in=0, shift_out=0, force_tile=-1, pose_tail=0, posenn_se=0)
+                user_stream=0, max_batch=1, shift_in=0, shift_out=0, force_tile=-1, pose_tail=0, posenn_se=0, triplet=0, coupled=0)
 STEP = ("family", "tile", "row0", "m_end", "mtile0", "ntiles_n", "gx", "gy", "n_main", "n_rem", "order", "deep", "rem_label",
         "rem_mtile0", "rem_ntiles_n", "order_kind", "family_ok", "nchunks")
 TAIL = ("code0", "code1", "split", "fold_if_xcd", "pad_classes", "pose_bm", "pose_mt", "pose_ntn", "pose_floats", "splitk_floats",
@@ -58,9 +59,10 @@ def decide(precision, li, H, W, NB, width=128, fuse_pose=0, **options):
     return d
 
 
-def fuses(li, H, W, fuse_pose):
-    """forward_device fuses the pose head into cnv7 where asked and cnv7's map holds a 128-row tile per image."""
-    return li == 6 and bool(fuse_pose) and half(H, 3) * half(W, 3) >= 128
+def fuses(precision, li, H, W, B, fuse_pose, width=128):
+    """Whether the forward fuses the pose head into this layer's launch, as davo_decide_forward reports it for cnv7 of the flagship."""
+    cfg = FP.parse_version(FP.FLOW.replace("-cnv6_128", "-cnv6_%d" % width))
+    return bool(FP.decide_forward(FP.call_of(cfg, H, W, B, precision), fuse_pose=fuse_pose)["layers"][li]["fuse_pose"])
 
 
 def check_structure(d, precision, li, H, W, NB, what, width=128):
@@ -146,7 +148,7 @@ def test_recorded_row(row):
     options = {k: v for k, v in row["options"].items() if k not in NOT_DECISION_OPTIONS}
     for li in decided_layers(row):
         what = (row_id(row), li)
-        d = decide(row["precision"], li, H, W, NB, row["width"], fuses(li, H, W, row["fuse_pose"]), max_batch=row["B"], **options)
+        d = decide(row["precision"], li, H, W, NB, row["width"], fuses(row["precision"], li, H, W, row["B"], row["fuse_pose"], row["width"]), max_batch=row["B"], **options)
         check_structure(d, row["precision"], li, H, W, NB, what, row["width"])
         assert [[c // 1000, c % 1000] for c in (d["code0"], d["code1"]) if c] == row["last_plan"][li], what
         assert d["split"] == row["last_split"][li], what
@@ -167,7 +169,7 @@ def test_structure_with_fewer_compute_units(precision, options):
         for B in Bs:
             for li in range(7):
                 for fuse_pose in (0, 1):
-                    d = decide(precision, li, H, W, 2 * B, 128, fuses(li, H, W, fuse_pose), max_batch=B, **options)
+                    d = decide(precision, li, H, W, 2 * B, 128, fuses(precision, li, H, W, B, fuse_pose), max_batch=B, **options)
                     check_structure(d, precision, li, H, W, 2 * B, (precision, options, H, W, B, li, fuse_pose))
                     assert not d["fold_if_xcd"], (options, H, W, B, li)       # never folded on a share of the device's compute units
 
