@@ -54,7 +54,9 @@ EXPORTS = (
     "davo_set_flip", "davo_get_flip",
     "davo_set_depth_format", "davo_get_depth_format", "davo_frames_plan_fmt2",
     "davo_set_posenn_heads", "davo_decide_forward",
+    "davo_track_begin", "davo_track_push", "davo_track_push_device", "davo_track_frames", "davo_track_end", "davo_track_plan", "davo_track_ring", "davo_track_debug_fill",
 )
+TRACK_TRAJECTORY, TRACK_AS_SET = 0, 1  # DAVO_TRACK_TRAJECTORY, DAVO_TRACK_AS_SET (davo_track_begin)
 COMM_ID_BYTES = 128
 LABELS_F32, LABELS_U8 = 0, 1          # DAVO_LABELS_F32, DAVO_LABELS_U8 (davo_set_label_format)
 FLOW_F32, FLOW_F16 = 0, 1             # DAVO_FLOW_F32, DAVO_FLOW_F16 (davo_set_flow_format)
@@ -253,6 +255,14 @@ def _load():
     L.davo_frames_plan.argtypes = [i] * 6 + [ctypes.POINTER(i), ctypes.POINTER(ctypes.c_longlong)]
     L.davo_frames_plan_fmt.argtypes = [i] * 7 + [ctypes.POINTER(i), ctypes.POINTER(ctypes.c_longlong)]
     L.davo_frames_plan_fmt2.argtypes = [i] * 8 + [ctypes.POINTER(i), ctypes.POINTER(ctypes.c_longlong)]
+    L.davo_track_begin.argtypes = [vp, i, i]
+    L.davo_track_push.argtypes = [vp, vp, vp, vp, vp, vp, i]
+    L.davo_track_push_device.argtypes = [vp, vp, vp, vp, vp, vp, ctypes.POINTER(ctypes.c_float)]
+    L.davo_track_frames.argtypes = [vp]
+    L.davo_track_end.argtypes = [vp]
+    L.davo_track_plan.argtypes = [i] * 8 + [ctypes.POINTER(ctypes.c_longlong)]
+    L.davo_track_debug_fill.argtypes = [vp, i, i]
+    L.davo_track_ring.argtypes = [i, ctypes.c_longlong, ctypes.POINTER(i), ctypes.POINTER(ctypes.c_longlong)]
     L.davo_pool_plan.argtypes = [i] * 3 + [ctypes.POINTER(i), ctypes.POINTER(i), f32p]
     L.davo_debug_read.argtypes = [vp, ctypes.c_char_p, f32p, ctypes.c_size_t]
     L.davo_conv2d_same.argtypes = [i, f32p, i, i, i, i, f32p, i, i, f32p, i, i, i, i, f32p, ctypes.c_char_p, i]

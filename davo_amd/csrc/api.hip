@@ -257,7 +257,7 @@ static int set_input_format(davo_ctx* c, const char* kind, int InputFormat::*fie
     next.*field = fmt;
     if (!valid(next)) return fail(c, DAVO_ERR_INVALID, "%s format must be %s (0) or %s (1), got %d", kind, name0, name1, fmt);
     // everything sized by plane_bytes() follows the format: it is fixed once inputs were taken or a set of them was allocated
-    bool sets = static_cast<bool>(c->host) || static_cast<bool>(c->snaps);
+    bool sets = static_cast<bool>(c->host) || static_cast<bool>(c->snaps) || static_cast<bool>(c->track);
     for (const InputSet& s : c->stream_sets) sets = sets || s.built();
     for (const FrameSet& s : c->frame_sets) sets = sets || s.built();
     if (c->inputs_seen || c->forward_seen || sets)
@@ -374,6 +374,7 @@ int davo_reset_range_state(davo_ctx* c) {
 // the body of davo_calibrate / davo_calibrate_depth: a window batch on the device, no poses wanted
 static int calibrate_entry(davo_ctx* c, int B, Batch b, int* shifts_out) {
     { int rc = check_batch(c, &b, B, true); if (rc) return rc; }
+    { int rc = refuse_while_tracking(c, "davo_calibrate"); if (rc) return rc; }
     c->inputs_seen = true;
     HIP_TRY(c, hipSetDevice(c->device));
     { int rc = judge_all(c); if (rc) return rc; }             // batches issued under the old scales get their verdict first
@@ -457,6 +458,7 @@ static int rebuild_slot_streams(davo_ctx* c, int n) {
 int davo_set_inflight(davo_ctx* c, int n) {
     if (!c || n < 1 || n > MAX_INFLIGHT) return fail(c, DAVO_ERR_INVALID, "inflight must be 1..4");
     if (n > 1 && c->user_stream) return fail(c, DAVO_ERR_INVALID, "in-flight slots use the context's own streams: clear davo_set_stream first");
+    { int rc = refuse_while_tracking(c, "davo_set_inflight"); if (rc) return rc; }      // the session's ring is sized by the slots it began with
     HIP_TRY(c, hipSetDevice(c->device));
     { int rc = deliver_all(c); if (rc) return rc; }
     { int rc = sync_all_slots(c); if (rc) return rc; }

@@ -20,7 +20,7 @@
 //   comm.hip        RCCL communicator behind the C ABI (pose gather of the window-sharded driver)
 // owned.h holds the owner types (device / page-locked memory, streams, events): everything a context allocates is a member of
 // one of them, so `delete ctx' is the whole teardown.  What is built lazily is a named group (HostStaging, PoseRing, RangeRing,
-// Snapshots, FxBlock, SeWorkspace, a Slot), built into a local and moved in complete: a group exists whole or not at all.
+// Snapshots, FxBlock, SeWorkspace, TrackState, a Slot), built into a local and moved in complete: a group exists whole or not at all.
 //
 // A forward's inputs.  forward_device(c, run, B, in, d_pose, &res) reads the context for what lasts (geometry, weights, options,
 // storage scales, the slots' workspaces); what belongs to the batch travels in one argument, `run' (struct Run below): its slot and
@@ -188,6 +188,23 @@ struct HeatBlock {
     int last_np = 0;
 };
 
+// A tracking session (davo_track_begin .. davo_track_end, entry.hip): `lanes' video streams in lockstep, one new frame each per
+// push.  The ring keeps the frames, label maps and (depth variants) depth planes of the last pushes on the device as they were
+// pushed - never mirrored -, R places of `lanes' frames each, in the context's label and depth element types (window_gather.h:
+// track_step says which place a push writes and reads).  Per push index mod R: `uploaded' = its frames are in their place,
+// `gathered' = its windows have been read out of the ring; up_stream / ga_stream the stream each was recorded on.
+struct TrackState {
+    int lanes = 0, policy = 0, R = 0;
+    long long pushed = 0;                        // frames per lane so far
+    DevMem<void> img, seg, depth;                // [R][lanes] frames of each plane kind
+    struct Place {
+        EventOwner uploaded, gathered;
+        hipStream_t up_stream = nullptr, ga_stream = nullptr;
+        bool up = false, ga = false;             // the event has been recorded at all
+    };
+    std::vector<Place> places;                   // R of them
+};
+
 struct Comm;                                     // comm.hip: RCCL communicator state
 
 }  // namespace davo
@@ -309,6 +326,7 @@ struct davo_ctx {
     davo::InputSet stream_sets[davo::MAX_INFLIGHT];     // one staging set per in-flight slot (built by the slot's first davo_submit, davo_submit_frames or davo_forward_device_frames)
     std::optional<davo::PoseRing> pose_ring;   // built by the first davo_submit
     davo::FrameSet frame_sets[davo::MAX_INFLIGHT];      // frame layout: one frame buffer per in-flight slot (built by the slot's first davo_submit_frames; [0] also by davo_forward_frames)
+    std::optional<davo::TrackState> track;     // online tracking: the session's ring and events (davo_track_begin builds it whole, davo_track_end and davo_destroy free it)
     std::deque<davo::StreamJob> jobs;
     unsigned long long n_submitted = 0;
     davo::DevMem<float> d_reissue_pose;        // a re-issued batch writes here first; copied to its own pose buffer unless a later batch has taken that
@@ -354,6 +372,10 @@ inline PlaneBytes plane_bytes(const davo_ctx* c) {
     return PlaneBytes{HW * 9, HW * 8 * e.flow, HW * 3 * e.label, HW * 3 * e.depth};
 }
 inline bool needs_depth(const davo_ctx* c) { return att_reads_depth(c->v.att_source); }
+// the calls a tracking session refuses (davo_set_inflight, the export switches, davo_calibrate): DAVO_OK outside a session
+inline int refuse_while_tracking(davo_ctx* c, const char* fn) {
+    return c->track ? fail(c, DAVO_ERR_INVALID, "%s: a tracking session is open (davo_track_begin): call davo_track_end first", fn) : DAVO_OK;
+}
 inline bool triplet(const davo_ctx* c) { return c->topology == DAVO_POSENN_TRIPLET; }
 // images a batch of B windows sends through cnv1..cnv7: one per selected pair, or one per window in the three-frame PoseNN
 inline int batch_images(const davo_ctx* c, int B, int sel) { return triplet(c) ? B : pairs_per_window(sel) * B; }

@@ -186,6 +186,72 @@ int mirror_windows(davo_ctx* c, const InputSet& set, const Inputs* from, int b0,
     return DAVO_OK;
 }
 
+// ---- tracking: the session's ring (ctx.h: TrackState; window_gather.h: track_step) ---------------------------------------------
+// Both steps of a push run on the stream given, its slot's.  The ring is shared by every slot, so what stream order does for a
+// slot's own staging set events do here, stream to stream and never through the host: the upload waits for the three gathers
+// that read its place, the gather for the two uploads of the earlier places it reads.  An event recorded on the stream that
+// would wait for it is skipped (stream order holds it already): with one slot in flight no wait is issued at all.
+
+// The frames of push t into place t mod R - from the host, or from the caller's device buffers - and, from the host, the flow
+// planes of the selection straight into planes 0, 1 of windows [0, lanes) of `set', as stage_frames puts them (set null: a push
+// that issues no window)
+int track_upload(davo_ctx* c, const FrameInputs& fr, bool on_device, long long t, const InputSet* set, int sel, hipStream_t s) {
+    TrackState& tr = *c->track;
+    const TrackStep st = track_step(t, tr.R);
+    const PlaneBytes f = frame_bytes(c), n = plane_bytes(c);
+    for (const long long u : st.upload_after) {
+        if (u < 0) continue;
+        const TrackState::Place& q = tr.places[u % tr.R];
+        if (q.ga && q.ga_stream != s) HIP_TRY(c, hipStreamWaitEvent(s, q.gathered.get(), 0));
+    }
+    const size_t S = (size_t)tr.lanes, at = (size_t)st.upload_place * S;
+    const hipMemcpyKind kind = on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
+    auto put = [&](const DevMem<void>& d, const void* src, size_t per) {
+        return hipMemcpyAsync(static_cast<uint8_t*>(d.get()) + per * at, src, per * S, kind, s);
+    };
+    HIP_TRY(c, put(tr.img, fr.frames, f.img));
+    HIP_TRY(c, put(tr.seg, fr.seg, f.seg));
+    if (tr.depth) HIP_TRY(c, put(tr.depth, fr.depth, f.depth));
+    if (set && !on_device) {
+        const FramePlan p = frame_plan(1, sel, c->v.att_source);
+        const size_t plane = n.flow / 4, off = plane * p.flow[0], width = plane * (p.flow[1] - p.flow[0]);
+        uint8_t* const d = static_cast<uint8_t*>(set->flow.get()) + off;
+        const uint8_t* const h = static_cast<const uint8_t*>(fr.flow2) + off;
+        if (S == 1) HIP_TRY(c, hipMemcpyAsync(d, h, width, hipMemcpyHostToDevice, s));
+        else HIP_TRY(c, hipMemcpy2DAsync(d, n.flow, h, f.flow, width, S, hipMemcpyHostToDevice, s));
+    }
+    TrackState::Place& me = tr.places[st.upload_place];
+    HIP_TRY(c, hipEventRecord(me.uploaded.get(), s));
+    me.up = true; me.up_stream = s;
+    return DAVO_OK;
+}
+
+// The windows of push t (t >= 2) out of the ring into windows [0, lanes) of `set': the gather launch of the frame layout with the
+// ring's places as frame bases.  d_flow2: the caller's device flow [lanes][2] (null: the flow is in the set already)
+int track_gather(davo_ctx* c, const InputSet& set, const void* d_flow2, long long t, int sel, bool flip, hipStream_t s) {
+    TrackState& tr = *c->track;
+    const TrackStep st = track_step(t, tr.R);
+    for (const long long u : st.gather_after) {
+        const TrackState::Place& q = tr.places[u % tr.R];
+        if (q.up && q.up_stream != s) HIP_TRY(c, hipStreamWaitEvent(s, q.uploaded.get(), 0));
+    }
+    const FramePlan p = frame_plan(tr.lanes, sel, c->v.att_source);
+    auto rd = [](const void* q) { return static_cast<const uint8_t*>(q); };
+    auto wr = [](const DevMem<void>& q) { return static_cast<uint8_t*>(q.get()); };
+    const GatherArgs a{rd(tr.img.get()), rd(tr.seg.get()), rd(tr.depth.get()), rd(d_flow2), wr(set.img), wr(set.seg), wr(set.depth), wr(set.flow),
+                       c->H, c->W, sel, p.seg_tgt, p.depth_tgt,
+                       st.place[0] * tr.lanes, st.place[1] * tr.lanes, st.place[2] * tr.lanes, 1};
+    {
+        ProfScope ps(c, s, "window_gather");
+        if (flip) HIP_TRY(c, launch_window_mirror(a, tr.lanes, true, c->fmt, s));
+        else HIP_TRY(c, launch_window_gather(a, tr.lanes, c->fmt, s));
+    }
+    TrackState::Place& me = tr.places[st.upload_place];
+    HIP_TRY(c, hipEventRecord(me.gathered.get(), s));
+    me.ga = true; me.ga_stream = s;
+    return DAVO_OK;
+}
+
 // ---- the stager: a batch's windows into the staging set its forward reads, a run of windows [b0, b0 + nb) at a time ----------
 // Two steps per run, both on the stream given: stage_upload brings what the windows read onto the device, stage_windows makes the
 // set hold them as windows.  Window layout: stage_inputs, then nothing.  Frame layout: stage_frames into the slot's frame buffer
@@ -195,10 +261,15 @@ int mirror_windows(davo_ctx* c, const InputSet& set, const Inputs* from, int b0,
 // gather launch; the window layout from the host with one window_mirror launch on the set, in place; a window batch on the device
 // gets the slot's staging set after all and is mirrored into it from the caller's buffers, which are never written.
 enum class Path { Device, Submit, Forward };
+// a push of a tracking session (davo_track_push[_device]): a frame-layout batch of `lanes' windows whose frames pass through the
+// session's ring.  t: its index (frames pushed before it); sel: the pair selection the policy gives it
+struct Push { long long t; int sel; };
 struct Stager {
     davo_ctx* c;
     Batch b;
     bool flip = false;                         // the context's setting when the batch was issued
+    int sel = PAIRS_BOTH;                      // the batch's pair selection: the context's, or the push's
+    const Push* push = nullptr;                // a push: b.fr holds ONE new frame per lane, the windows come out of the ring
     const InputSet* set = nullptr;             // the path's staging set of the slot (null: none, see above)
     const FrameSet* fs = nullptr;              // frame layout from the host: the slot's frame buffer
     bool sources_only_seg = false;             // stage_inputs': davo_submit's batches
@@ -208,8 +279,8 @@ struct Stager {
 
 // The stager of batch b in `slot'; builds what the path keeps per slot at its first use, each group whole: davo_forward's staging
 // (slot 0), davo_submit's pose ring and the slot's staging set, the slot's frame buffer for frames that come from the host.
-int acquire_stager(davo_ctx* c, const Batch& b, Path path, int slot, Stager* st) {
-    *st = Stager{c, b, c->flip};
+int acquire_stager(davo_ctx* c, const Batch& b, Path path, int slot, Stager* st, const Push* push = nullptr) {
+    *st = Stager{c, b, c->flip, push ? push->sel : c->pairs, push};
     if (path == Path::Forward) {
         if (!c->host) {
             HostStaging h;
@@ -228,7 +299,7 @@ int acquire_stager(davo_ctx* c, const Batch& b, Path path, int slot, Stager* st)
         if (!c->stream_sets[slot].built()) { int rc = alloc_input_set(c, &c->stream_sets[slot], true); if (rc) return rc; }
         st->set = &c->stream_sets[slot];
     }
-    if (b.layout == Layout::Frames && !b.on_device) {
+    if (b.layout == Layout::Frames && !b.on_device && !push) {      // (a push's frames go into the session's ring)
         { int rc = ensure_frame_set(c, slot); if (rc) return rc; }
         st->fs = &c->frame_sets[slot];
     }
@@ -236,9 +307,10 @@ int acquire_stager(davo_ctx* c, const Batch& b, Path path, int slot, Stager* st)
 }
 
 int stage_upload(Stager* st, int b0, int nb, hipStream_t s) {
+    if (st->push) return track_upload(st->c, st->b.fr, st->b.on_device, st->push->t, st->set, st->sel, s);
     if (st->b.on_device) return DAVO_OK;
-    if (st->fs) return stage_frames(st->c, *st->fs, *st->set, st->b.fr, b0, nb, st->c->pairs, &st->cur, s);
-    return stage_inputs(st->c, *st->set, st->b.win, b0, nb, st->sources_only_seg, st->c->pairs, s);
+    if (st->fs) return stage_frames(st->c, *st->fs, *st->set, st->b.fr, b0, nb, st->sel, &st->cur, s);
+    return stage_inputs(st->c, *st->set, st->b.win, b0, nb, st->sources_only_seg, st->sel, s);
 }
 
 int stage_windows(Stager* st, int b0, int nb, hipStream_t s) {
@@ -246,10 +318,11 @@ int stage_windows(Stager* st, int b0, int nb, hipStream_t s) {
     if (st->b.layout != Layout::Frames) {
         if (!st->flip) return DAVO_OK;
         // the target's label map is read only where the variant attends it (davo_submit's staging does not even copy it otherwise)
-        return mirror_windows(c, *st->set, st->b.on_device ? &st->b.win : nullptr, b0, nb, c->pairs, att_tgt_attended(c->v.att_source), s);
+        return mirror_windows(c, *st->set, st->b.on_device ? &st->b.win : nullptr, b0, nb, st->sel, att_tgt_attended(c->v.att_source), s);
     }
+    if (st->push) return track_gather(c, *st->set, st->b.on_device ? st->b.fr.flow2 : nullptr, st->push->t, st->sel, st->flip, s);
     const FrameInputs dev = st->fs ? FrameInputs{st->fs->img.get(), nullptr, st->fs->seg.get(), st->fs->depth.get()} : st->b.fr;
-    return gather_windows(c, *st->set, dev, b0, nb, c->pairs, st->flip, s);
+    return gather_windows(c, *st->set, dev, b0, nb, st->sel, st->flip, s);
 }
 
 }  // namespace
@@ -295,17 +368,18 @@ int davo::deliver_all(davo_ctx* c) {
 
 // the body of davo_forward_device, davo_forward_device_depth and davo_forward_device_frames: b's pointers are device pointers.  A
 // frame batch runs on the slot's staging set, gathered from them
-static int forward_device_entry(davo_ctx* c, int B, Batch b, void* d_pose, float* elapsed_ms) {
+static int forward_device_entry(davo_ctx* c, int B, Batch b, void* d_pose, float* elapsed_ms, const Push* push = nullptr) {
     { int rc = check_batch(c, &b, B, d_pose != nullptr); if (rc) return rc; }
     c->inputs_seen = true;
     HIP_TRY(c, hipSetDevice(c->device));
     Stager st;
-    { int rc = acquire_stager(c, b, Path::Device, c->next_slot, &st); if (rc) return rc; }
+    { int rc = acquire_stager(c, b, Path::Device, c->next_slot, &st, push); if (rc) return rc; }
     const Inputs in = st.inputs();
     const bool ticketed = c->impl == 0 && c->precision == 1;      // f16x3: the batch gets a record (and a copy of its inputs) of its own
     if (ticketed) { int rc = ticket_reserve(c); if (rc) return rc; }
     // rotate through the in-flight slots: this batch runs on its own stream and workspace
     Run run = make_run(c, c->next_slot);
+    run.pairs = st.sel;
     c->next_slot = (c->next_slot + 1) % c->inflight;
     EventOwner e0, e1;
     // the windows into the slot's staging set, in stream order behind the forward that last read it and ahead of the ticket: the
@@ -315,6 +389,7 @@ static int forward_device_entry(davo_ctx* c, int B, Batch b, void* d_pose, float
         HIP_TRY(c, event_create(&e0));
         HIP_TRY(c, hipEventRecord(e0.get(), run.stream));
     }
+    { int rc = stage_upload(&st, 0, B, run.stream); if (rc) return rc; }       // (a push: its frames into the ring; else nothing, the batch is on the device)
     { int rc = stage_windows(&st, 0, B, run.stream); if (rc) return rc; }
     Ticket t{};
     if (ticketed) { int rc = ticket_begin(c, &run, B, in, &t, st.set != nullptr); if (rc) return rc; }
@@ -413,7 +488,7 @@ int davo_pool_plan(int H, int W, int att_source, int* n_cells, int* rects, float
 // snapshots of a batch all live in context-owned memory.
 
 // the body of davo_submit, davo_submit_depth and davo_submit_frames: b's pointers are host pointers
-static int submit_entry(davo_ctx* c, int B, Batch b, float* pose_out, int hold) {
+static int submit_entry(davo_ctx* c, int B, Batch b, float* pose_out, int hold, const Push* push = nullptr) {
     { int rc = check_batch(c, &b, B, pose_out != nullptr, hold); if (rc) return rc; }
     c->inputs_seen = true;
     HIP_TRY(c, hipSetDevice(c->device));
@@ -426,8 +501,9 @@ static int submit_entry(davo_ctx* c, int B, Batch b, float* pose_out, int hold) 
     if (ticketed) { int rc = ticket_reserve(c); if (rc) return rc; }          // may judge - and re-issue - an older batch: before the slot rotation
     const int slot = c->next_slot, pr = (int)(c->n_submitted % STREAM_POSES);
     Stager st;
-    { int rc = acquire_stager(c, b, Path::Submit, slot, &st); if (rc) return rc; }
+    { int rc = acquire_stager(c, b, Path::Submit, slot, &st, push); if (rc) return rc; }
     Run run = make_run(c, slot);
+    run.pairs = st.sel;
     c->next_slot = (c->next_slot + 1) % c->inflight;
     hipStream_t s = run.stream;
     // H2D on the slot's stream, in order behind the forward that last read this staging set (and, the frame layout, behind the
@@ -483,6 +559,132 @@ int davo_wait(davo_ctx* c, int leave_pending) {
 }
 
 int davo_pending(davo_ctx* c) { return c ? (int)c->jobs.size() : DAVO_ERR_INVALID; }
+
+// ---- online tracking: davo_track_begin / davo_track_push[_device] / davo_track_end ---------------------------------------------
+// A push is a frame-layout batch of `lanes' windows through submit_entry / forward_device_entry above: the same slots, tickets,
+// pose ring, delivery and `hold'.  What differs is where its frames come from (the Stager's two steps: track_upload, track_gather)
+// and who picks its pair selection (the session's policy).  The range guard's copy of a push is of the staging set: a re-issue
+// never reads the ring.
+
+int davo_track_begin(davo_ctx* c, int lanes, int policy) {
+    if (!c) return DAVO_ERR_INVALID;
+    if (c->track) return fail(c, DAVO_ERR_INVALID, "davo_track_begin: a tracking session is open already: call davo_track_end first");
+    if (lanes < 1 || lanes > c->max_batch) return fail(c, DAVO_ERR_INVALID, "davo_track_begin: lanes %d outside [1,%d] (max_batch)", lanes, c->max_batch);
+    if (policy != DAVO_TRACK_TRAJECTORY && policy != DAVO_TRACK_AS_SET)
+        return fail(c, DAVO_ERR_INVALID, "davo_track_begin: policy must be DAVO_TRACK_TRAJECTORY (0) or DAVO_TRACK_AS_SET (1), got %d", policy);
+    if (c->fx_on || c->heat) return fail(c, DAVO_ERR_INVALID, "davo_track_begin: there are no exports under tracking: switch the feature and heat exports off first");
+    HIP_TRY(c, hipSetDevice(c->device));
+    { int rc = deliver_all(c); if (rc) return rc; }
+    TrackState tr;
+    tr.lanes = lanes; tr.policy = policy; tr.R = track_ring_places(c->inflight);
+    const PlaneBytes f = frame_bytes(c);
+    const size_t n = (size_t)tr.R * lanes;
+    HIP_TRY(c, dev_alloc(&tr.img, f.img * n));
+    HIP_TRY(c, dev_alloc(&tr.seg, f.seg * n));
+    if (needs_depth(c)) HIP_TRY(c, dev_alloc(&tr.depth, f.depth * n));
+    tr.places.resize(tr.R);
+    for (TrackState::Place& p : tr.places) {
+        HIP_TRY(c, event_create(&p.uploaded, hipEventDisableTiming));
+        HIP_TRY(c, event_create(&p.gathered, hipEventDisableTiming));
+    }
+    c->track = std::move(tr);
+    return DAVO_OK;
+}
+
+// the selection of the push about to be issued: the three-frame network runs whole windows whatever the policy
+static int push_selection(const davo_ctx* c) {
+    const TrackState& tr = *c->track;
+    if (triplet(c)) return PAIRS_BOTH;
+    if (tr.policy == DAVO_TRACK_AS_SET) return c->pairs;
+    return tr.pushed == 2 ? PAIRS_BOTH : PAIRS_SRC1;       // the session's first window, then tgt->src1 alone
+}
+
+// the body of davo_track_push and davo_track_push_device -> windows issued (0 or lanes) or a negative status
+static int track_push_entry(davo_ctx* c, Batch b, void* pose, int hold, float* elapsed_ms) {
+    if (!c) return DAVO_ERR_INVALID;
+    if (!c->track) return fail(c, DAVO_ERR_INVALID, "%s: no tracking session is open: call davo_track_begin first", b.fn);
+    TrackState& tr = *c->track;
+    const Push push{tr.pushed, push_selection(c)};
+    if (push.t >= 2) {
+        const int rc = b.on_device ? forward_device_entry(c, tr.lanes, b, pose, elapsed_ms, &push)
+                                   : submit_entry(c, tr.lanes, b, static_cast<float*>(pose), hold, &push);
+        if (rc) return rc;
+        ++tr.pushed;
+        return tr.lanes;
+    }
+    // fewer than two earlier frames: the frame goes into the ring and nothing is issued (flow2 and the poses are not read: either may be NULL)
+    if (!b.fr.flow2) b.fr.flow2 = b.fr.frames;
+    { int rc = check_batch(c, &b, tr.lanes, true, hold); if (rc) return rc; }
+    c->inputs_seen = true;
+    HIP_TRY(c, hipSetDevice(c->device));
+    { int rc = track_upload(c, b.fr, b.on_device, push.t, nullptr, push.sel, slot_stream(c, c->next_slot)); if (rc) return rc; }
+    // from the host: the caller's arrays are free on return, whatever `hold' (no submit is counted that a later `hold' could refer to)
+    if (!b.on_device) HIP_TRY(c, hipEventSynchronize(tr.places[push.t % tr.R].uploaded.get()));
+    if (elapsed_ms) *elapsed_ms = 0.f;
+    ++tr.pushed;
+    return 0;
+}
+
+int davo_track_push(davo_ctx* c, const uint8_t* frames, const float* flow2, const float* seg, const float* depth, float* pose_out, int hold) {
+    return track_push_entry(c, frame_batch("davo_track_push", false, frames, flow2, seg, depth), pose_out, hold, nullptr);
+}
+
+int davo_track_push_device(davo_ctx* c, const void* d_frames, const void* d_flow2, const void* d_seg, const void* d_depth, void* d_pose, float* elapsed_ms) {
+    return track_push_entry(c, frame_batch("davo_track_push_device", true, d_frames, d_flow2, d_seg, d_depth), d_pose, 0, elapsed_ms);
+}
+
+int davo_track_frames(const davo_ctx* c) { return c && c->track ? (int)c->track->pushed : DAVO_ERR_INVALID; }
+
+int davo_track_end(davo_ctx* c) {
+    if (!c) return DAVO_ERR_INVALID;
+    if (!c->track) return fail(c, DAVO_ERR_INVALID, "davo_track_end: no tracking session is open");
+    HIP_TRY(c, hipSetDevice(c->device));
+    const int rc = deliver_all(c);
+    // nothing on the device may still touch the ring: every copy into it and every gather out of it has an event
+    for (const TrackState::Place& p : c->track->places) {
+        if (p.up) (void)hipEventSynchronize(p.uploaded.get());
+        if (p.ga) (void)hipEventSynchronize(p.gathered.get());
+    }
+    c->track.reset();
+    return rc;
+}
+
+// test hook: every byte of ring place `place' (its frames, label maps and depth planes) becomes `byte', once nothing in flight
+// touches the ring
+int davo_track_debug_fill(davo_ctx* c, int place, int byte) {
+    if (!c) return DAVO_ERR_INVALID;
+    if (!c->track || place < 0 || place >= c->track->R) return fail(c, DAVO_ERR_INVALID, "davo_track_debug_fill: no session, or place outside [0,R)");
+    HIP_TRY(c, hipSetDevice(c->device));
+    TrackState& tr = *c->track;
+    for (const TrackState::Place& p : tr.places) {
+        if (p.up) HIP_TRY(c, hipEventSynchronize(p.uploaded.get()));
+        if (p.ga) HIP_TRY(c, hipEventSynchronize(p.gathered.get()));
+    }
+    const PlaneBytes f = frame_bytes(c);
+    const size_t S = (size_t)tr.lanes;
+    auto fill = [&](const DevMem<void>& d, size_t per) { return hipMemset(static_cast<uint8_t*>(d.get()) + per * S * place, byte, per * S); };
+    HIP_TRY(c, fill(tr.img, f.img));
+    HIP_TRY(c, fill(tr.seg, f.seg));
+    if (tr.depth) HIP_TRY(c, fill(tr.depth, f.depth));
+    HIP_TRY(c, hipStreamSynchronize(nullptr));               // (api.hip: zero_now)
+    return DAVO_OK;
+}
+
+int davo_track_plan(int H, int W, int lanes, int pairs, int att_source, int label_fmt, int flow_fmt, int depth_fmt, long long* link_bytes) {
+    const InputFormat fmt{label_fmt, flow_fmt, depth_fmt};
+    if (H < 1 || W < 1 || lanes < 1 || (pairs != PAIRS_SRC0 && pairs != PAIRS_SRC1 && pairs != PAIRS_BOTH) || att_source < 0 || att_source > ATT_MAX || !valid(fmt))
+        return DAVO_ERR_INVALID;
+    if (link_bytes) *link_bytes = track_push_bytes(lanes, pairs, att_source, H, W, element_bytes(fmt));
+    return DAVO_OK;
+}
+
+int davo_track_ring(int inflight, long long t, int* places, long long* after) {
+    if (inflight < 1 || inflight > MAX_INFLIGHT || t < 0) return DAVO_ERR_INVALID;
+    const TrackStep s = track_step(t, track_ring_places(inflight));
+    if (places) { places[0] = s.upload_place; for (int k = 0; k < 3; ++k) places[1 + k] = s.place[k]; }
+    if (after) { for (int k = 0; k < 3; ++k) after[k] = s.upload_after[k]; after[3] = s.gather_after[0]; after[4] = s.gather_after[1]; }
+    return s.R;
+}
 
 }  // extern "C"
 

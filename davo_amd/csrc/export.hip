@@ -162,6 +162,7 @@ extern "C" {
 
 int davo_set_feature_export(davo_ctx* c, int on) {
     if (!c) return DAVO_ERR_INVALID;
+    { int rc = refuse_while_tracking(c, "davo_set_feature_export"); if (rc) return rc; }      // exports under tracking are not built
     HIP_TRY(c, hipSetDevice(c->device));
     { int rc = sync_all_slots(c); if (rc) return rc; }
     if (!on) { c->fx.reset(); c->fx_on = false; return DAVO_OK; }
@@ -190,6 +191,7 @@ int davo_forward_features(davo_ctx* c, int B, const uint8_t* img, const float* f
 
 int davo_set_heat_export(davo_ctx* c, int on) {
     if (!c) return DAVO_ERR_INVALID;
+    { int rc = refuse_while_tracking(c, "davo_set_heat_export"); if (rc) return rc; }      // exports under tracking are not built
     HIP_TRY(c, hipSetDevice(c->device));
     { int rc = sync_all_slots(c); if (rc) return rc; }
     if (!on) { c->heat.reset(); return DAVO_OK; }

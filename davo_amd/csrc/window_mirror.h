@@ -171,7 +171,7 @@ __global__ __launch_bounds__(256) void window_mirror(GatherArgs a) {
         const int k = job;
         if (k != 1 && !(a.sel & (k == 0 ? PAIRS_SRC0 : PAIRS_SRC1))) return;
         const size_t third = (size_t)a.W * 3;
-        const uint8_t* src = FRAMES ? a.f_img + (n + k) * HW * 3 : a.f_img + n * HW * 9 + k * third;
+        const uint8_t* src = FRAMES ? a.f_img + a.frame(n, k) * HW * 3 : a.f_img + n * HW * 9 + k * third;
         const size_t src_pitch = FRAMES ? third : third * 3;
         uint8_t* dst = a.w_img + n * HW * 9 + k * third;
         if (a.W % 16 == 0) mirror_rows<3, 12>(src, src_pitch, dst, third * 3, a.H, a.W / 16);
@@ -182,7 +182,7 @@ __global__ __launch_bounds__(256) void window_mirror(GatherArgs a) {
         if (depth && !a.f_depth) return;
         if (k == 1 ? !(depth ? (both || a.depth_tgt) : a.seg_tgt) : !(a.sel & (k == 0 ? PAIRS_SRC0 : PAIRS_SRC1))) return;
         const size_t pb = HW * (depth ? sizeof(DT) : sizeof(LT));
-        const uint8_t* src = (depth ? a.f_depth : a.f_seg) + (FRAMES ? n + k : n * 3 + k) * pb;
+        const uint8_t* src = (depth ? a.f_depth : a.f_seg) + (FRAMES ? a.frame(n, k) : n * 3 + k) * pb;
         uint8_t* dst = (depth ? a.w_depth : a.w_seg) + (n * 3 + k) * pb;
         if (depth) mirror_plane<(int)sizeof(DT)>(src, dst, a.H, a.W);
         else mirror_plane<(int)sizeof(LT)>(src, dst, a.H, a.W);

@@ -7,6 +7,7 @@ yielding ``(img_u8, flow, seg)`` batches (``(img_u8, flow, seg, depth)`` for a d
 through ``load_weights`` — the stand-in for ``tf.train.Saver(...).restore``
 (test_kitti_pose.py:129-131) — keyed by the TF variable names.
 """
+import collections
 import ctypes
 
 import numpy as np
@@ -417,6 +418,67 @@ class Engine:
         ms = ctypes.c_float(0.0)
         self._call(name, n, bufs, depth if depth_slot or self.cfg.needs_depth else None, d_pose, ctypes.byref(ms) if timed else None, depth_slot=depth_slot)
         return ms.value if timed else None
+
+    # ---- online tracking (include/davo_hip.h "Online tracking"; davo_amd/track.py: Tracker) --------------------------
+    TRACK_POLICIES = {"trajectory": _lib.TRACK_TRAJECTORY, "as_set": _lib.TRACK_AS_SET}
+
+    def track_begin(self, lanes=1, policy="trajectory"):
+        """Open a tracking session of ``lanes`` video streams in lockstep (davo_track_begin).  ``policy``: "trajectory" - the
+        first window both pairs, then tgt->src1 alone - or "as_set" - whatever set_pairs holds at each push."""
+        if policy not in self.TRACK_POLICIES:
+            raise ValueError("policy must be 'trajectory' or 'as_set', got %r" % (policy,))
+        self._check(self._L.davo_track_begin(self._ctx, int(lanes), self.TRACK_POLICIES[policy]))
+        self._track_lanes, self._track_held = int(lanes), collections.deque()
+
+    def _track_issued(self, rc):
+        if rc < 0:
+            self._check(rc)
+        return rc
+
+    def track_push(self, frames, flow2, seg, out, hold=0, depth=None):
+        """One new frame per lane (davo_track_push): ``frames`` u8 [S,H,W,3], ``flow2`` [S,2,H,W,2] the flow planes (tgt->src0,
+        tgt->src1) of the window the frame completes, ``seg`` [S,H,W,1], ``depth`` [S,H,W,1] for a depth-source variant, in the
+        engine's formats; ``out`` [S,2,6] and ``hold`` as submit's.  The first two pushes of a session read neither ``flow2`` nor
+        ``out`` (None is fine).  -> windows issued: S, or 0 for those two.  The engine keeps ``out`` and - with ``hold`` - the
+        inputs referenced until the push has been delivered."""
+        S = getattr(self, "_track_lanes", None)
+        if S is None:
+            raise DavoError("track_push: no tracking session is open: call track_begin first")
+        warm = self.track_frames() < 2
+        if warm and flow2 is None:
+            flow2 = np.zeros((S, 2, self.H, self.W, 2), FLOW_DTYPES[self.flow])
+        strict = "track_push" if hold and not warm else None
+        frames, flow2, seg = self._contiguous(frames, flow2, seg, 4, self._frame_label_arg, strict)
+        want = ((S, self.H, self.W, 3), (S, 2, self.H, self.W, 2), (S, self.H, self.W, 1))
+        for name, a, w in zip(("frames", "flow2", "seg"), (frames, flow2, seg), want):
+            if a.shape != w:
+                raise ValueError("%s shape %s != %s" % (name, a.shape, w))
+        depth = self._depth_arg(depth, (S, self.H, self.W, 1), "frames, flow2, seg", strict)
+        if not warm:
+            self._check_out(out, S)
+        n = self._track_issued(self._L.davo_track_push(self._ctx, _ptr(frames), _ptr(flow2), _ptr(seg), _ptr(depth), _ptr(out) if not warm else None, int(hold)))
+        if n:
+            self._track_held.append((out, (frames, flow2, seg, depth) if hold else None))
+            while len(self._track_held) > max(self.pending(), int(hold) + 1):
+                self._track_held.popleft()
+        return n
+
+    def track_push_device(self, d_frames, d_flow2, d_seg, d_pose, timed=False, depth=None):
+        """track_push from DeviceBuffers (davo_track_push_device; 16-byte aligned, never written).  -> (windows issued,
+        milliseconds of the timed form or None)."""
+        ms = ctypes.c_float(0.0)
+        n = self._track_issued(self._L.davo_track_push_device(self._ctx, _ptr(d_frames), _ptr(d_flow2), _ptr(d_seg), _ptr(depth) if self.cfg.needs_depth else None,
+                                                              _ptr(d_pose), ctypes.byref(ms) if timed else None))
+        return n, (ms.value if timed else None)
+
+    def track_frames(self):
+        """Frames pushed per lane in the open session (davo_track_frames)."""
+        return self._track_issued(self._L.davo_track_frames(self._ctx))
+
+    def track_end(self):
+        """Deliver what is pending and free the session's ring (davo_track_end)."""
+        self._check(self._L.davo_track_end(self._ctx))
+        self._track_lanes, self._track_held = None, collections.deque()
 
     def wait(self, leave_pending=0):
         """Deliver submitted batches until at most ``leave_pending`` are outstanding (include/davo_hip.h: davo_wait)."""

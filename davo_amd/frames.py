@@ -122,6 +122,54 @@ def flip_frames(frames, flow2, seg, depth=None):
     return out if depth is None else out + (planes(np.asarray(depth), "depth"),)
 
 
+def track_pushes(frames, flow2, seg, depth=None):
+    """A frame sequence as a tracking session takes it (include/davo_hip.h "Online tracking"; Engine.track_push, Tracker.push):
+    one tuple per frame, ``(frame [1,H,W,3], flow2 [1,2,H,W,2] or None, seg [1,H,W,1], depth [1,H,W,1] or None)`` - push t carries
+    frame t, the flow pair of window t - 2 (None for the first two frames, which complete no window), label map t and depth plane
+    t.  The arrays are views of the arguments (lanes = 1; stack the tuples of S sequences along axis 0 for S lanes)."""
+    frames, flow2, seg = np.asarray(frames), np.asarray(flow2), np.asarray(seg)
+    N = flow2.shape[0]
+    if frames.ndim != 4 or frames.shape[0] != N + 2 or frames.shape[3] != 3:
+        raise ValueError("frames shape %s: expected [N+2,H,W,3] for the %d windows of flow2" % (frames.shape, N))
+    seg = seg[..., None] if seg.ndim == 3 else seg
+    if seg.shape[0] != N + 2 or (depth is not None and np.asarray(depth).shape[0] != N + 2):
+        raise ValueError("seg / depth hold another number of frames than frames' %d" % (N + 2))
+    depth = None if depth is None else np.asarray(depth)
+    return [(frames[t:t + 1], flow2[t - 2:t - 1] if t >= 2 else None, seg[t:t + 1], None if depth is None else depth[t:t + 1])
+            for t in range(N + 2)]
+
+
+def track_pushes_from_windows(img, flow, seg, depth=None):
+    """track_pushes of a batch of CONSECUTIVE windows (frames_from_windows, which names the window and the plane where they are
+    not): B windows -> B + 2 pushes.  ``windows_from_frames`` of the pushes' arrays put back together is the batch again."""
+    return track_pushes(*frames_from_windows(img, flow, seg, depth))
+
+
+def track_plan(H, W, lanes=1, pairs="src1", att_source="se_flow", labels="f32", flow="f32", depth="f32"):
+    """Bytes one push of a tracking session copies across the link (include/davo_hip.h: davo_track_plan; no GPU needed): per lane a
+    frame, a label map, a depth plane where ``att_source`` reads depth, and the flow planes of ``pairs``."""
+    if pairs not in PAIRS:
+        raise ValueError("pairs must be 'both', 'src0' or 'src1', got %r" % (pairs,))
+    att = att_source_id(att_source) if isinstance(att_source, str) else int(att_source)
+    nbytes = ctypes.c_longlong(0)
+    rc = _lib.lib().davo_track_plan(int(H), int(W), int(lanes), PAIRS[pairs], att, LABEL_FORMATS[check_label_format(labels)],
+                                    FLOW_FORMATS[check_flow_format(flow)], DEPTH_FORMATS[check_depth_format(depth)], ctypes.byref(nbytes))
+    if rc != 0:
+        raise ValueError("davo_track_plan(%r) refused its arguments" % ((H, W, lanes, pairs, att_source, labels, flow, depth),))
+    return nbytes.value
+
+
+def track_ring(inflight, t):
+    """The ring rule of a tracking session as the library applies it (include/davo_hip.h: davo_track_ring; no GPU needed), for push
+    ``t`` of a session begun with ``inflight`` slots: ``{'R', 'upload': place, 'read': (3 places, -1 for t < 2), 'upload_after':
+    (3 pushes whose gather the upload waits for, -1 = none), 'gather_after': (2 pushes whose upload the gather waits for)}``."""
+    places, after = (ctypes.c_int * 4)(), (ctypes.c_longlong * 5)()
+    R = _lib.lib().davo_track_ring(int(inflight), int(t), places, after)
+    if R < 0:
+        raise ValueError("davo_track_ring(%r, %r) refused its arguments" % (inflight, t))
+    return {"R": R, "upload": places[0], "read": tuple(places[1:4]), "upload_after": tuple(after[0:3]), "gather_after": tuple(after[3:5])}
+
+
 def frames_plan(H, W, N, pairs="both", att_source="se_flow", labels="f32", flow="f32", depth="f32"):
     """What a frame-layout batch of N windows reads (include/davo_hip.h: davo_frames_plan - the function the library's copies and
     its gather kernel are driven by; no GPU needed): ``{'frames', 'seg', 'depth', 'flow': (lo, hi), 'link_bytes': int}`` - frame

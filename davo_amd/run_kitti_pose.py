@@ -152,12 +152,33 @@ def build_parser():
                          "the staging sets; float16 -monodepth2_depth.npy files are read as they are, float32 ones rounded by the "
                          "loader's workers (davo_amd.depth_to_f16).  The written file is that of a float32 run on the rounded planes, "
                          "to the byte.  A version that reads no depth ignores the option's files")
+    ap.add_argument("--online", action="store_true",
+                    help="feed the dump one frame per push through a tracking session (include/davo_hip.h: davo_track_push; "
+                         "davo_amd.Tracker, one lane): the library keeps the two frames before on the device and every frame crosses the "
+                         "link once.  Runs what --batch_size 1 --pairs trajectory runs - window 0 both pairs, then tgt->src1 alone - and "
+                         "writes its file, byte for byte; combines with --labels, --flow, --depth and --flip.  One GPU, a dump on disk")
     return ap
+
+
+def check_online(ap, a):
+    """--online's refusals, before anything is started"""
+    if not a.online:
+        return
+    if a.gpus > 1:
+        ap.error("--online --gpus %d: a tracking session runs on one GPU (multi-rank tracking is not built)" % a.gpus)
+    if a.synthetic is not None and any(S.parse_frame_counts(a.synthetic, 1)):
+        ap.error("--online --synthetic: the synthetic windows are drawn one by one and share no frames; write a dump of a frame "
+                 "sequence (davo_amd.synth.make_frames, davo_amd.windows_from_frames) and run it with --concat_img_dir")
+    if a.batch_size != 1:
+        ap.error("--online pushes one frame at a time: --batch_size must be 1, got %d" % a.batch_size)
+    if a.emulate_shard or a.force_comm or a.sync_driver:
+        ap.error("--online does not combine with --emulate_shard, --force_comm or --sync_driver")
 
 
 def main(argv=None):
     ap = build_parser()
     a = ap.parse_args(argv)
+    check_online(ap, a)
     # start-up split (wall clock).  Only the first main() of a process can say what the process start cost
     global _FIRST_MAIN
     fresh, _FIRST_MAIN = _FIRST_MAIN, False
@@ -211,6 +232,8 @@ def main(argv=None):
     # this rank's shard of every sequence, in running order: the segments of the one loader
     segments = [(seq, ) + shard_of(n_frames) for seq, n_frames in sequences]
     if not synthetic:
+        if a.online:
+            a.loader_procs = 0                      # windows are read inline, one per push
         if a.loader_procs != 0:
             # the fork server the loader's workers come from starts importing numpy / Pillow now (davo_amd/loader.py: worker_context);
             # it is a spawned interpreter that never touches a GPU, and its 0.2 s of imports pass behind HIP's initialisation
@@ -237,8 +260,9 @@ def main(argv=None):
         # workers need no GPU.  Page-locking the buffers (1.4 GB at batch 64: 0.3 s) follows on the loader's own thread, entry by
         # entry, once the context below exists: HIP serialises hipHostRegister with the context's own allocations, and pinning
         # beside them made the context 0.25 s slower (profiles/r05an_config4_scene_shard_nocomm.json against r05ao).
-        loader_thread = threading.Thread(target=load.prestart_segments, args=(segments, a.batch_size), name="davo-loader-start")
-        loader_thread.start()
+        if not a.online:
+            loader_thread = threading.Thread(target=load.prestart_segments, args=(segments, a.batch_size), name="davo-loader-start")
+            loader_thread.start()
         # ... and the checkpoint is read and parsed (0.06-0.1 s of file and numpy work, no GPU) on a third
         from .tf_checkpoint import load_weights
         ckpt = {}
@@ -297,7 +321,9 @@ def main(argv=None):
         # too - so davo_submit does not wait for its own copy; the threaded loader and the synthetic windows give no such promise
         # (hold = 0).  One stream serves the whole run
         process_loader = not synthetic and load.segment_loader is not None
-        stream = None if a.sync_driver else S.PoseStream(system.engine, hold=1 if process_loader else 0)
+        stream = None if a.sync_driver or a.online else S.PoseStream(system.engine, hold=1 if process_loader else 0)
+        if a.online:
+            system.engine.set_inflight(4)       # the slots PoseStream gives a batch-1 run: the same launch plans
         clock = {}
 
         def source(k, seq, n_frames, lo, hi):
@@ -337,8 +363,12 @@ def main(argv=None):
             return batches
 
         entries = []
-        for seq, traj, poses, timing in S.run_sequences(infer, sequences, source, a.batch_size, rank, world, comm, emulate, stream,
-                                                        before_sequence, a.pairs):
+        if a.online:
+            from .track import run_online
+            results = run_online(system.engine, lambda seq, w: load.load_inline(seq, w, w + 1), sequences, before_sequence)
+        else:
+            results = S.run_sequences(infer, sequences, source, a.batch_size, rank, world, comm, emulate, stream, before_sequence, a.pairs)
+        for seq, traj, poses, timing in results:
             dt = time.perf_counter() - clock["t0"]
             if rank != 0:
                 continue
@@ -385,6 +415,8 @@ def main(argv=None):
                 run_wide["depth"] = a.depth
             if a.flip:
                 run_wide["flip"] = True
+            if a.online:
+                run_wide["online"] = True
             if len(entries) == 1:          # one sequence: the report it has always had
                 report = {k: v for k, v in entries[0].items() if k not in ("seq", "wall_s")}
                 report.update(run_wide)

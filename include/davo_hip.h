@@ -427,6 +427,79 @@ int davo_frames_plan_fmt2(int H, int W, int N, int pairs, int att_source, int la
 int davo_set_flip(davo_ctx* ctx, int on);
 int davo_get_flip(const davo_ctx* ctx);
 
+/* Online tracking.  The `_frames' forms still take a finished piece of a video.  A live caller (one camera, or S simulators in
+ * lockstep) gets one new frame per stream at a time: it would have to keep the last two frames itself, rebuild a three-frame
+ * array for every step and send two of its three frames across the link again.  A tracking session does that on the device:
+ * the caller pushes ONE new frame per lane, the context keeps the frames before it in a ring of its own, and the push yields the
+ * poses of the window the frame completes - window (src0, tgt, src1) = the lane's frames (t - 2, t - 1, t) for push t = 0, 1, ...
+ *   davo_track_begin(ctx, lanes, policy)   opens the session: 1 <= lanes <= max_batch video streams S, the ring (lanes x
+ *            (in-flight slots + 2) frames, label maps and - depth variants - depth planes, in the context's label and depth
+ *            formats) and its events.  Batches pending delivery are delivered first.  A second begin without an end, lanes out
+ *            of range, an unknown policy and a context with an export switched on return DAVO_ERR_INVALID with a message.
+ *   davo_track_push(ctx, frames, flow2, seg, depth, pose_out, hold)   host pointers, one push:
+ *              frames   uint8 [S,H,W,3]      the new frame of every lane
+ *              flow2          [S,2,H,W,2]    the flow planes (tgt->src0, tgt->src1) of the window this frame completes, tgt the
+ *                                            frame pushed before it; the context's flow format
+ *              seg            [S,H,W,1]      the new frame's label map; the context's label format
+ *              depth          [S,H,W,1]      its depth plane, the context's depth format; NULL (or anything) where the variant
+ *                                            reads none, DAVO_ERR_INVALID with a message for NULL where it does
+ *              pose_out f32   [S,2,6]        written at delivery, as davo_submit's
+ *            It is davo_submit_frames on the S windows (lane s, frames t - 2 .. t): streamed like it on the next in-flight slot,
+ *            same bits as davo_forward_frames / davo_forward on those windows under the same selection and batch size, `hold'
+ *            as there (pushes, `_frames' and window submits count alike), range ticket and re-issue (from the library's copy
+ *            of the gathered windows: a re-issue never touches the ring), davo_wait, davo_pending, davo_synchronize.  Returns
+ *            the number of windows issued - S, or 0 for the first two pushes of a session, which only store their frames
+ *            (flow2 and pose_out are not read and may be NULL; the arrays are free on return) - or a negative davo_status.
+ *            What a push copies: a frame, a label map and a depth plane per lane and the flow planes of its selection - at
+ *            128x416, float32, tgt->src1: 159,744 + 425,984 + 212,992 = 798,720 bytes per lane (425,984 with byte labels and
+ *            binary16 flow) against davo_submit_frames' 958,464 (585,728) at N = 1.  Planes the selection does not read may
+ *            hold anything.
+ *   davo_track_push_device(ctx, d_frames, d_flow2, d_seg, d_depth, d_pose, elapsed_ms)   the same from device buffers, 16-byte
+ *            aligned (DAVO_ERR_INVALID otherwise), as davo_forward_device_frames: the frames are copied into the ring and the
+ *            windows gathered on the slot's stream, so the caller's buffers are free once work ordered behind the call on the
+ *            context's stream may run; they are never written.  d_pose [S,2,6] receives the poses in stream order.
+ *   davo_track_frames(ctx)   frames pushed per lane so far (DAVO_ERR_INVALID outside a session).
+ *   davo_track_end(ctx)      delivers what is pending, waits for the ring's last reader and frees the ring and its events
+ *            (davo_destroy does the same for a session left open).  A context that never begins a session allocates nothing
+ *            and launches nothing for it.
+ * Policy - which pairs a push runs (davo_set_pairs explains the selections; an unselected row of pose_out is +0.0):
+ *   DAVO_TRACK_TRAJECTORY   the session's first window runs both pairs, every later push DAVO_PAIRS_SRC1: what a trajectory needs
+ *                           (run_kitti_pose --pairs trajectory).  davo_set_pairs is not read.
+ *   DAVO_TRACK_AS_SET       every push runs the selection davo_set_pairs holds when it is issued.
+ * A three-frame context (davo_set_posenn_topology) runs whole windows under either.
+ * The ring holds frames as pushed, never mirrored: davo_set_flip mirrors inside the gather launch as in the frame layout, no
+ * launch more, and toggling it between pushes applies to the pushes issued after the call.  Nothing of a ring place that no
+ * selected pair reads is read.  (csrc/window_gather.h: the gather kernel takes a frame base per window third; DESIGN.md
+ * section 2 "Online tracking": how uploads and gathers of different slots are ordered, by events and never through the host.)
+ * Between pushes every window and `_frames' call, davo_set_flip, davo_set_pairs, davo_set_stream, davo_wait and
+ * davo_synchronize are legal and leave the ring alone.  REFUSED during a session, with DAVO_ERR_INVALID and a message:
+ * davo_set_inflight (the ring is sized by the slots the session began with), davo_set_feature_export, davo_set_heat_export
+ * (there are no exports under tracking), davo_calibrate[_depth] and the three input format setters.
+ * davo_track_plan is a pure function like davo_frames_plan_fmt2 (no context, no device): *link_bytes receives the bytes one
+ * push of `lanes' lanes copies under selection `pairs' - davo_frames_plan_fmt2's figure for N = 1 per lane less the frames,
+ * label maps and depth planes it sends again.  davo_track_ring is the ring's index rule as a pure function: for push t of a
+ * session begun with `inflight' slots it returns the ring's places R = inflight + 2 (or DAVO_ERR_INVALID); places[4] receives
+ * the place the push uploads into (t mod R) and the three its window reads ((t - 2 + k) mod R; -1 for t < 2); after[5] the pushes
+ * whose gather the upload is ordered behind (t - R, t - R + 1, t - R + 2: the readers of that place; -1 where that push gathered
+ * nothing) and the two whose upload the gather is ordered behind (t - 2, t - 1).  Either pointer may be NULL.
+ * Not built: lanes that start at different times, more than one new frame per lane and push (the `_frames' forms catch up),
+ * exports, multi-rank sessions, and the pose chain itself, which stays with the caller (davo_amd.Tracker does it the reference's
+ * way). */
+enum { DAVO_TRACK_TRAJECTORY = 0, DAVO_TRACK_AS_SET = 1 };
+int davo_track_begin(davo_ctx* ctx, int lanes, int policy);
+int davo_track_push(davo_ctx* ctx, const uint8_t* frames, const float* flow2, const float* seg, const float* depth,
+                    float* pose_out, int hold);
+int davo_track_push_device(davo_ctx* ctx, const void* d_frames, const void* d_flow2, const void* d_seg, const void* d_depth,
+                           void* d_pose, float* elapsed_ms);
+int davo_track_frames(const davo_ctx* ctx);
+int davo_track_end(davo_ctx* ctx);
+int davo_track_plan(int H, int W, int lanes, int pairs, int att_source, int label_fmt, int flow_fmt, int depth_fmt,
+                    long long* link_bytes);
+int davo_track_ring(int inflight, long long t, int* places, long long* after);
+/* Test hook: fills ring place `place' (0 .. R - 1) of the open session - its frames, label maps and depth planes - with `byte',
+ * after waiting for everything in flight that touches the ring.  No forward calls it. */
+int davo_track_debug_fill(davo_ctx* ctx, int place, int byte);
+
 /* The pooled flow-attention variants' window geometry (att_source 14..17) as a function (no context, no device): the cells of the
  * SE descriptor of an H x W frame, in descriptor order (entries 2 i, 2 i + 1 are the x and y means of cell i).  *n_cells receives
  * their number (D / 2; 0 for a source that does not pool); rects, where not NULL, [n][4] = rows [y0, y1) and columns [x0, x1) of
