@@ -54,6 +54,7 @@ EXPORTS = (
     "davo_set_flip", "davo_get_flip",
     "davo_set_depth_format", "davo_get_depth_format", "davo_frames_plan_fmt2",
     "davo_set_posenn_heads", "davo_decide_forward",
+    "davo_get_option", "davo_option_info", "davo_option_store",
     "davo_track_begin", "davo_track_push", "davo_track_push_device", "davo_track_frames", "davo_track_end", "davo_track_plan", "davo_track_ring", "davo_track_debug_fill",
 )
 TRACK_TRAJECTORY, TRACK_AS_SET = 0, 1  # DAVO_TRACK_TRAJECTORY, DAVO_TRACK_AS_SET (davo_track_begin)
@@ -233,6 +234,9 @@ def _load():
     L.davo_last_plan.argtypes = [vp, i, i, ctypes.POINTER(i), ctypes.POINTER(i)]
     L.davo_last_split.argtypes = [vp, i, ctypes.POINTER(i)]
     L.davo_set_option.argtypes = [vp, ctypes.c_char_p, i]
+    L.davo_get_option.argtypes = [vp, ctypes.c_char_p, ctypes.POINTER(i)]
+    L.davo_option_info.argtypes = [i, ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(i)]
+    L.davo_option_store.argtypes = [ctypes.c_char_p, i, ctypes.POINTER(i)]
     L.davo_set_precision.argtypes = [vp, i]
     L.davo_set_impl.argtypes = [vp, i]
     L.davo_set_pairs.argtypes = [vp, i]
@@ -290,3 +294,19 @@ def _load():
             fn.restype = ctypes.c_int
     _lib = L
     return L
+
+
+def option_table():
+    """The launch options as the library holds them (davo_option_info, no GPU needed): [(name, default in stored form)], in the
+    positional order of davo_decide_layer's options 0..13 and then davo_decide_forward's options 0..6."""
+    rows, name, default = [], ctypes.c_char_p(), ctypes.c_int()
+    while lib().davo_option_info(len(rows), ctypes.byref(name), ctypes.byref(default)) == 0:
+        rows.append((name.value.decode(), default.value))
+    return rows
+
+
+def option_store(key, value):
+    """What davo_set_option stores for ``value`` of a launch option (davo_option_store, no GPU needed); None where it refuses the
+    value or ``key`` is no launch option."""
+    stored = ctypes.c_int()
+    return stored.value if lib().davo_option_store(key.encode(), int(value), ctypes.byref(stored)) == 0 else None

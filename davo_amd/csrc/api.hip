@@ -472,32 +472,11 @@ int davo_set_inflight(davo_ctx* c, int n) {
 int davo_set_option(davo_ctx* c, const char* key, int value) {
     if (!c || !key) return DAVO_ERR_INVALID;
     const std::string k = key;
-    if (k == "fuse_pose") c->opt_fuse_pose = value != 0;
-    else if (k == "fuse_pack") c->opt_fuse_pack = value < 0 ? -1 : (value != 0);
-    else if (k == "share_taps") c->opt_share_taps = value != 0;
-    else if (k == "merge_rem") c->opt_merge_rem = value != 0;
-    else if (k == "merge_cnv4") c->opt_merge_cnv4 = value != 0;
-    else if (k == "tile_208x128") c->opt_tile_208x128 = value != 0;
-    else if (k == "merge_order") c->opt_merge_order = value < 0 ? -1 : (value > 2 ? 0 : value);
-    else if (k == "skip_order") c->opt_skip_order = value < 0 ? 0 : (value > 2 ? 2 : value);
-    else if (k == "pad_classes") {
-        // 0 off | 1 the default layers | 8 + mask: the layers of the mask (1 cnv4, 2 cnv5, 4 cnv6)
-        if (value == 0 || value == 1) c->opt_pad_classes = value ? PAD_CLASS_LAYERS : 0;
-        else if (value >= 8 && value <= 15) c->opt_pad_classes = value & 7;
-        else return fail(c, DAVO_ERR_INVALID, "pad_classes must be 0, 1 or 8 + a layer mask (8..15), got %d", value);
+    if (const OptionRow* r = find_option(key)) {                 // a launch option: stored as its table row says (options.h)
+        int stored;
+        if (!option_store(*r, value, &stored)) return fail(c, DAVO_ERR_INVALID, "pad_classes must be 0, 1 or 8 + a layer mask (8..15), got %d", value);
+        c->opt.*r->field = stored;
     }
-    else if (k == "patch_cnv2") c->opt_patch_cnv2 = value != 0;
-    else if (k == "patch_cnv3") c->opt_patch_cnv3 = value != 0;
-    else if (k == "patch_cnv1_t") c->opt_patch_cnv1_t = value != 0;
-    else if (k == "fold_tails") c->opt_fold_tails = value < 0 ? -1 : (value > 2 ? 1 : value);
-    else if (k == "deep_ring") c->opt_deep_ring = value != 0;
-    else if (k == "wave128") c->opt_wave128 = value < 0 ? 0 : (value > 3 ? 3 : value);      // 3: cnv4 on conv_igemm_h3w128 whatever the round count (test hook)
-    else if (k == "split_k") c->opt_split_k = value != 0;
-    else if (k == "fold_fixup") c->opt_fold_fixup = value != 0;
-    else if (k == "f32_n16") c->opt_f32_n16 = value != 0;
-    else if (k == "f32_n256") c->opt_f32_n256 = value != 0;
-    else if (k == "merge_rem_f32") c->opt_merge_rem_f32 = value < 0 ? 0 : (value > 2 ? 2 : value);
-    else if (k == "patch_f32") c->opt_patch_f32 = value != 0;
     else if (k == "auto_range") { int rc = judge_all(c); if (rc) return rc; c->opt_auto_range = value != 0; }
     else if (k == "stable_inputs") { int rc = judge_all(c); if (rc) return rc; c->opt_stable_inputs = value != 0; }
     else if (k == "force_tile") {
@@ -517,6 +496,31 @@ int davo_set_option(davo_ctx* c, const char* key, int value) {
     else if (k == "host_chunk") { if (value < 0) return fail(c, DAVO_ERR_INVALID, "host_chunk must be >= 0"); c->host_chunk = value; }
     else return fail(c, DAVO_ERR_INVALID, "unknown option `%s'", key);
     return DAVO_OK;
+}
+
+int davo_get_option(const davo_ctx* c, const char* key, int* value) {
+    if (!c || !key || !value) return DAVO_ERR_INVALID;
+    const std::string k = key;
+    if (const OptionRow* r = find_option(key)) *value = c->opt.*r->field;
+    else if (k == "auto_range") *value = c->opt_auto_range;
+    else if (k == "stable_inputs") *value = c->opt_stable_inputs;
+    else if (k == "cu_partition") *value = c->cu_partition;
+    else if (k == "profile_stride") *value = c->prof_stride;
+    else if (k == "host_chunk") *value = c->host_chunk;
+    else return DAVO_ERR_INVALID;                                  // unknown, or "force_tile": a value per layer
+    return DAVO_OK;
+}
+
+int davo_option_info(int i, const char** name, int* stored_default) {
+    if (i < 0 || i >= NUM_OPTIONS) return DAVO_ERR_INVALID;
+    if (name) *name = OPTION_TABLE[i].name;
+    if (stored_default) *stored_default = LaunchOptions{}.*OPTION_TABLE[i].field;
+    return DAVO_OK;
+}
+
+int davo_option_store(const char* key, int value, int* stored) {
+    const OptionRow* r = key && stored ? find_option(key) : nullptr;
+    return r && option_store(*r, value, stored) ? DAVO_OK : DAVO_ERR_INVALID;
 }
 
 int davo_set_precision(davo_ctx* c, int precision) {

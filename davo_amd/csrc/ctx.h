@@ -144,7 +144,6 @@ struct PadTables {
     DevMem<unsigned short> tile_taps;
     std::vector<uint16_t> host_taps;
 };
-constexpr int PAD_CLASS_LAYERS = 6;              // "pad_classes" 1: cnv5 | cnv6 (bits: 1 cnv4, 2 cnv5, 4 cnv6).  cnv4 measured level (245.2 -> 243.4 us, inside its run-to-run spread) and stays on the natural order
 
 // ---- what the context builds at a first use, each whole or not at all ------------------------------------------------------------
 // davo_forward's staging (its first call): the input set, the poses on the device and their page-locked bounce buffer, the stream
@@ -217,28 +216,10 @@ struct davo_ctx {
     int ncu = 256;                             // compute units a launch of this context may use (CU-masked slot streams: dev_cus / slots)
     bool cu_partition = false;                 // davo_set_option "cu_partition": slot i's stream is masked to its own share of every XCD's CUs
     hipStream_t user_stream = nullptr;         // davo_set_stream: the caller's stream, which slot 0 then runs on (null: the slot's own)
-    bool opt_fuse_pose = true;                 // f16x3: pose head fused into cnv7's epilogue (davo_set_option)
-    int opt_fuse_pack = -1;                    // f16x3: mask+pack fused into cnv1's patch fill: 0 off | 1 on | -1 where it pays (small batches: one launch fewer)
-    bool opt_patch_cnv2 = true;                // f16x3: cnv2 from an LDS-staged input patch (conv_patch_cnv2_h3) instead of the implicit GEMM
-    bool opt_patch_cnv3 = true;                // f16x3: cnv3 likewise (conv_patch_cnv3_h3)
-    bool opt_merge_rem = true;                 // f16x3: cnv5 / cnv6 main + remainder launches as one grid (conv_igemm_h3_mainrem)
-    int opt_fold_tails = -1;                   // 0 off | 1 both tails | 2 the excitation only | -1 auto: the excitation at small batches (pose_tail.h: what it costs)               // the excitation MLP and the pose head's tile sum run in the last workgroup of the squeeze / cnv7 launch
-    int opt_wave128 = 2;                       // f16x3: cnv5 / cnv6 256x256 tiles on four waves of 128x128 outputs (conv_igemm_h3w.h: -3..5 % per step, bit-identical); 2: their remainder rows on 256x64 tiles too (-1.2 %)
-    bool opt_deep_ring = true;                 // f16x3: launches of at most one workgroup per CU (batch 1..4) run on LDS rings of 3..6 slots
-    int opt_merge_order = -1;                  // merged grids: 0 = short tiles offset inside every XCD, 1 = per XCD, 2 = main tiles (long first) then the remainder; -1 = 2 where a tile order exists, else 0
-    int opt_skip_order = 1;                    // launches whose tiles skip different numbers of padding rows of the filter hand out the long tiles first (tile_order_for, forward.hip): 0 = never, 1 = float32 launches, 2 = the f16x3 merged grids too
+    davo::LaunchOptions opt;                   // the launch options as davo_set_option stored them (options.h: every field, default and rule)
     std::map<std::vector<int>, davo::DevMem<int>> tile_orders;   // device tables of those launches, by (layer, tile rows, tiles, ...); nullptr = uniform
-    int opt_pad_classes = davo::PAD_CLASS_LAYERS;                  // float32: the layers of the mask (1 cnv4, 2 cnv5, 4 cnv6) run on rows sorted by padding class, every tile walks only the taps that are real for its own pixels (pad_classes.h)
     std::map<std::vector<int>, davo::PadTables> pad_tables;   // their device tables, by (layer, pair images, map, padding, rate)
-    bool opt_tile_208x128 = false;             // f16x3: cnv4 may run on the four-wave 208x128 tile (conv_igemm_h3s.h; measured 8 % behind the 128x128 tile at B = 32: off)
-    bool opt_merge_cnv4 = false;               // f16x3: cnv4 as whole rounds of 256x128 tiles + 128x128 remainder tiles in one grid where the batch allows
-    bool opt_share_taps = true;                // f16x3: cnv3..cnv6 stage one pixel patch per filter row for its three taps
-    bool opt_f32_n256 = false;                 // f32 mode experiment: cnv5 / cnv6 on the 128 x 256 tile (eight waves, one workgroup per CU)
-    int opt_merge_rem_f32 = 1;             // f32 mode: cnv4..cnv7 main + remainder launches as one grid (conv_igemm_f32_mainrem)
-    bool opt_f32_n16 = true;                   // f32 mode: cnv1 (16 output channels) on the 128x16 tile / v_mfma_f32_16x16x4_f32 instead of the padded 128x32 one
-    bool opt_fold_fixup = false;               // f16x3 split-K: the part that finishes a tile last adds its partial sums (no splitk_fixup launch); needs xcd_rr > 0.  Measured slower (batch 1: 0.141 against 0.132 ms): off
     int xcd_rr = -1;                           // workgroups (x, y) of a grid whose x extent is a multiple of 8 share an XCD for every y: -1 not probed yet | 0 no | 1 yes
-    bool opt_split_k = true;                   // f16x3: cnv5 / cnv6 launches of at most half a workgroup per CU split their K loop in two (forward.hip)
     davo::GrowBuf d_splitk;                    // split-K partial sums [MAX_INFLIGHT slots][M][2][N] float32
     size_t splitk_floats = 0;                  // ... per slot
     davo::GrowBuf d_pose_tiles;                // per-tile partial sums of the fused pose head, one region per slot likewise
@@ -256,7 +237,6 @@ struct davo_ctx {
     int heads = DAVO_POSENN_HEADS_DECOUPLED;   // davo_set_posenn_heads: DAVO_POSENN_HEADS_COUPLED = couple_sharednet_v0_dilation - one cnv6 (256 -> c6, one group), one cnv7
                                                // (c6 -> 256, one group, reads all of cnv6), pred six columns wide: fused into cnv7's f16x3 epilogue (NC = 6), else the
                                                // two-pass pose head on a stored cnv7 (forward.hip)
-    bool opt_patch_cnv1_t = true;              // three-frame PoseNN, f16x3: "patch_cnv1_t" - cnv1 from an LDS-staged 16-channel patch (conv_patch_cnv1t_h3) instead of the implicit GEMM at cin = 16
     bool forward_seen = false;                 // a forward has been issued (davo_set_posenn_se, davo_set_posenn_topology and davo_set_posenn_heads are refused from then on)
     davo::InputFormat fmt;                     // davo_set_{label,flow,depth}_format: what every `seg' / `flow' / `depth' argument points at, and what plane_bytes() sizes
     bool inputs_seen = false;                  // an entry point has taken inputs (davo_set_label_format, davo_set_flow_format and davo_set_depth_format are refused from then on)
@@ -276,7 +256,6 @@ struct davo_ctx {
     davo::DevMem<uint8_t> d_w1patch;           // cnv1 B fragments for conv_patch_cnv1_h3 (three-frame PoseNN: for conv_patch_cnv1t_h3)
     davo::DevMem<uint8_t> d_w2patch;           // cnv2 B fragments for conv_patch_cnv2_h3
     davo::DevMem<float> d_w1patch_f32, d_w2patch_f32, d_w3patch_f32;      // float32 mode: cnv1 / cnv2 / cnv3 weights in the patch kernels' register order (conv_patch_f32.h)
-    bool opt_patch_f32 = true;                 // float32 mode: cnv1 / cnv2 / cnv3 from an LDS-staged input patch (conv_patch_f32.h) instead of the implicit GEMM
     davo::DevMem<uint8_t> d_w3patch;           // cnv3 B fragments for conv_patch_cnv3_h3
     // geometry
     int H1, W1, H2, W2, H3, W3;

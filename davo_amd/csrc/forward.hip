@@ -101,7 +101,7 @@ constexpr int MAX_WEIGHT_CHANNEL_SPREAD_LOG2 = 14;     // f16x3 per-channel guar
 // that no table is needed, and the table is uploaded.  A table that cannot be put on the device is not fatal: natural order.
 template <class Build>
 const int* cached_tile_order(davo_ctx* c, const std::vector<int>& key, Build build) {
-    if (!c->opt_skip_order) return nullptr;
+    if (!c->opt.skip_order) return nullptr;
     auto it = c->tile_orders.find(key);
     if (it != c->tile_orders.end()) return it->second.get();
     const std::vector<int> order = build();
@@ -194,10 +194,7 @@ int slot_scratch(davo_ctx* c, const Run& run, GrowBuf* buf, size_t* floats, size
 // ---- one conv layer: decided in plan.hip (decide_layer_f32 / decide_layer_h3), issued here ---------------------------------------
 PlanOptions plan_options(const davo_ctx* c, int li) {
     PlanOptions o;
-    o.wave128 = c->opt_wave128; o.skip_order = c->opt_skip_order; o.merge_order = c->opt_merge_order; o.pad_classes = c->opt_pad_classes;
-    o.merge_rem_f32 = c->opt_merge_rem_f32; o.share_taps = c->opt_share_taps; o.merge_rem = c->opt_merge_rem; o.merge_cnv4 = c->opt_merge_cnv4;
-    o.tile_208x128 = c->opt_tile_208x128; o.deep_ring = c->opt_deep_ring; o.split_k = c->opt_split_k; o.fold_fixup = c->opt_fold_fixup;
-    o.f32_n16 = c->opt_f32_n16; o.f32_n256 = c->opt_f32_n256;
+    static_cast<LaunchOptions&>(o) = c->opt;
     o.ncu = c->ncu; o.dev_cus = c->dev_cus; o.cu_partition = c->cu_partition; o.user_stream = c->user_stream != nullptr; o.max_batch = c->max_batch;
     o.shift_in = li == 0 ? 0 : c->act_shift[li - 1]; o.shift_out = c->act_shift[li];
     return o;
@@ -440,8 +437,7 @@ int ensure_weights(davo_ctx* c, const Run& run, int* mode, bool* f32_fallback) {
 ForwardOptions forward_options(const davo_ctx* c, const Run& run) {
     auto env = [](const char* name) { const char* e = tuning_env(name); return e ? atoi(e) : -1; };
     ForwardOptions o;
-    o.fold_tails = c->opt_fold_tails; o.fuse_pack = c->opt_fuse_pack; o.fuse_pose = c->opt_fuse_pose;
-    o.patch_cnv1_t = c->opt_patch_cnv1_t; o.patch_cnv2 = c->opt_patch_cnv2; o.patch_cnv3 = c->opt_patch_cnv3; o.patch_f32 = c->opt_patch_f32;
+    static_cast<LaunchOptions&>(o) = c->opt;
     for (int i = 0; i < 7; ++i) o.forced_tile[i] = c->L[i].tile_h >= 0;
     o.have_patch_f32[0] = (bool)c->d_w1patch_f32; o.have_patch_f32[1] = (bool)c->d_w2patch_f32; o.have_patch_f32[2] = (bool)c->d_w3patch_f32;
     o.npad7 = c->L[6].npad;

@@ -21,6 +21,11 @@ static void hook_layers(ConvLayer (&L)[7], int cnv6_out, bool posenn_se, bool tr
     for (ConvLayer& l : L) l.tile_h = forced_tile_h(force_tile, l.cout);
 }
 
+// davo_decide_layer's options are the option table's first rows (options.h) and twelve values that are no options, davo_decide_forward's
+// the rows behind those and three more: a row added to the table without the header's counts does not compile
+constexpr int LAYER_ROWS = DAVO_DECIDE_OPTIONS - 12, FORWARD_ROWS = DAVO_FORWARD_OPTIONS - 3;
+static_assert(NUM_OPTIONS == LAYER_ROWS + FORWARD_ROWS, "options.h: OPTION_TABLE and include/davo_hip.h: DAVO_DECIDE_OPTIONS, DAVO_FORWARD_OPTIONS");
+
 extern "C" {
 
 int davo_host_alloc(int device, size_t bytes, void** out) {
@@ -253,16 +258,11 @@ int davo_decide_layer(int precision, int layer, int H, int W, int NB, int cnv6_o
         n_options < 0 || n_options > DAVO_DECIDE_OPTIONS)
         return DAVO_ERR_INVALID;
     PlanOptions o;
-    int force_tile = -1, pose_tail = 0, posenn_se = 0, tri = 0, cpl = 0;
-    int* const slot[DAVO_DECIDE_OPTIONS] = {&o.wave128, &o.skip_order, &o.merge_order, &o.pad_classes, &o.merge_rem_f32, nullptr, nullptr, nullptr, nullptr, nullptr,
-                                            nullptr, nullptr, nullptr, nullptr, &o.ncu, &o.dev_cus, nullptr, nullptr, &o.max_batch, &o.shift_in, &o.shift_out,
-                                            &force_tile, &pose_tail, &posenn_se, &tri, &cpl};
-    bool* const flag[DAVO_DECIDE_OPTIONS] = {nullptr, nullptr, nullptr, nullptr, nullptr, &o.share_taps, &o.merge_rem, &o.merge_cnv4, &o.tile_208x128, &o.deep_ring,
-                                             &o.split_k, &o.fold_fixup, &o.f32_n16, &o.f32_n256, nullptr, nullptr, &o.cu_partition, &o.user_stream};
-    for (int i = 0; i < n_options; ++i) {
-        if (slot[i]) *slot[i] = options[i];
-        else *flag[i] = options[i] != 0;
-    }
+    int cu_partition = 0, user_stream = 0, force_tile = -1, pose_tail = 0, posenn_se = 0, tri = 0, cpl = 0;
+    int* const tail[DAVO_DECIDE_OPTIONS - LAYER_ROWS] = {&o.ncu, &o.dev_cus, &cu_partition, &user_stream, &o.max_batch, &o.shift_in, &o.shift_out,
+                                                         &force_tile, &pose_tail, &posenn_se, &tri, &cpl};
+    for (int i = 0; i < n_options; ++i) *(i < LAYER_ROWS ? &(o.*OPTION_TABLE[i].field) : tail[i - LAYER_ROWS]) = options[i];
+    o.cu_partition = cu_partition != 0; o.user_stream = user_stream != 0;
     if (o.ncu < 1 || o.dev_cus < 1 || o.max_batch < 1 || force_tile < -1 || force_tile >= NUM_TILES) return DAVO_ERR_INVALID;
     // the layer's input and output as decide_forward lays a forward of NB images out (one pair, or the three-frame PoseNN's NB windows)
     ConvLayer L[7];
@@ -317,11 +317,10 @@ int davo_decide_forward(const int* call, const int* options, int n_options, int*
         (topology != DAVO_POSENN_PAIRS && topology != DAVO_POSENN_TRIPLET) || (heads != DAVO_POSENN_HEADS_DECOUPLED && heads != DAVO_POSENN_HEADS_COUPLED))
         return DAVO_ERR_INVALID;
     ForwardOptions o;
-    int force_tile = -1, fuse_pose = 1, patch[4] = {1, 1, 1, 1}, zero_record = 0, want_snapshot = 0;
-    int* const slot[DAVO_FORWARD_OPTIONS] = {&o.fold_tails, &o.fuse_pack, &fuse_pose, &patch[0], &patch[1], &patch[2], &patch[3], &force_tile, &zero_record, &want_snapshot};
-    for (int i = 0; i < n_options; ++i) *slot[i] = options[i];
+    int force_tile = -1, zero_record = 0, want_snapshot = 0;
+    int* const tail[DAVO_FORWARD_OPTIONS - FORWARD_ROWS] = {&force_tile, &zero_record, &want_snapshot};
+    for (int i = 0; i < n_options; ++i) *(i < FORWARD_ROWS ? &(o.*OPTION_TABLE[LAYER_ROWS + i].field) : tail[i - FORWARD_ROWS]) = options[i];
     if (force_tile < -1 || force_tile >= NUM_TILES) return DAVO_ERR_INVALID;
-    o.fuse_pose = fuse_pose != 0; o.patch_cnv1_t = patch[0] != 0; o.patch_cnv2 = patch[1] != 0; o.patch_cnv3 = patch[2] != 0; o.patch_f32 = patch[3] != 0;
     o.zero_record = zero_record != 0; o.want_snapshot = want_snapshot != 0;
     const bool tri = topology == DAVO_POSENN_TRIPLET, cpl = heads == DAVO_POSENN_HEADS_COUPLED;
     ConvLayer L[7];

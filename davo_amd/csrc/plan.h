@@ -6,6 +6,7 @@
 #pragma once
 #include <vector>
 
+#include "options.h"
 #include "params.h"
 
 namespace davo {
@@ -91,12 +92,9 @@ struct LayerGeom {
 // pose_six (f16x3 with fuse_pose, a one-group cnv7): the coupled network's six-column head - the NC = 6 epilogue of conv_igemm_h3.h, its
 // partial sums in the two-head layout, no 208-pixel tile (conv_igemm_h3s.h has the three-column epilogue alone)
 struct LayerCall { int li, x_ch, Hin, Win, y_ld; bool y_f32; int NB; bool fuse_pose, pose_tail; bool pose_six = false; };
-// the context's settings these decisions read (davo_ctx: opt_*, ncu, dev_cus, cu_partition, user_stream, max_batch) and the storage
-// shifts of the layer's input and output (act_shift[li - 1], 0 for cnv1; act_shift[li])
-struct PlanOptions {
-    int wave128 = 2, skip_order = 1, merge_order = -1, pad_classes = 7, merge_rem_f32 = 1;
-    bool share_taps = true, merge_rem = true, merge_cnv4 = false, tile_208x128 = false, deep_ring = true, split_k = true, fold_fixup = false;
-    bool f32_n16 = true, f32_n256 = false;
+// the context's settings these decisions read: its launch options (options.h), davo_ctx's ncu, dev_cus, cu_partition, user_stream and
+// max_batch, and the storage shifts of the layer's input and output (act_shift[li - 1], 0 for cnv1; act_shift[li])
+struct PlanOptions : LaunchOptions {
     int ncu = 256, dev_cus = 256;
     bool cu_partition = false, user_stream = false;
     int max_batch = 1, shift_in = 0, shift_out = 0;
@@ -162,11 +160,9 @@ struct ForwardCall {
     int posenn_se = 0;                         // davo_set_posenn_se
     int groups6 = 1, groups7 = 2, cin7 = 0;    // cnv6's and cnv7's groups and cnv7's input channels per group, as the layers were initialised
 };
-// the settings the sequence reads (davo_ctx: opt_*, L[i].tile_h, the float32 patch weights, L[6].npad), the batch's two range-guard
-// wishes (Run::zero_record, Run::snap.record) and the tuning build's DAVO_FUSE_PACK / DAVO_CNV{1,2,3}_PATCH (-1: not set)
-struct ForwardOptions {
-    int fold_tails = -1, fuse_pack = -1;
-    bool fuse_pose = true, patch_cnv1_t = true, patch_cnv2 = true, patch_cnv3 = true, patch_f32 = true;
+// the settings the sequence reads (the context's launch options, L[i].tile_h, the float32 patch weights, L[6].npad), the batch's two
+// range-guard wishes (Run::zero_record, Run::snap.record) and the tuning build's DAVO_FUSE_PACK / DAVO_CNV{1,2,3}_PATCH (-1: not set)
+struct ForwardOptions : LaunchOptions {
     bool forced_tile[7] = {false, false, false, false, false, false, false};
     bool have_patch_f32[3] = {true, true, true};
     int npad7 = 256;

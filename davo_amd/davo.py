@@ -551,6 +551,14 @@ class Engine:
         if key == "host_chunk":
             self.host_chunk = int(value)
 
+    def get_option(self, key):
+        """The value the engine holds for ``key``, as set_option stored it (include/davo_hip.h: davo_get_option)."""
+        v = ctypes.c_int()
+        rc = self._L.davo_get_option(self._ctx, key.encode(), ctypes.byref(v))
+        if rc != 0:
+            raise _PY_ERR.get(rc, DavoError)("option `%s' cannot be read back: unknown, or kept per layer (\"force_tile\")" % key)
+        return v.value
+
     def set_inflight(self, n):
         """Batches kept in flight by forward_device (1..4): n streams + n workspaces, rotated per call."""
         self._check(self._L.davo_set_inflight(self._ctx, int(n)))

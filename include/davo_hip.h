@@ -803,6 +803,19 @@ const char* davo_range_report(const davo_ctx* ctx);
  *   "host_chunk" (default 8): windows per sub-batch; the H2D copy of sub-batch i+1 overlaps the kernels of
  *       sub-batch i when B >= 2*host_chunk.  0 = copy the whole batch, then compute.  Results do not change. */
 int davo_set_option(davo_ctx* ctx, const char* key, int value);
+/* Reading the options back.  The launch options - every key above but "auto_range", "stable_inputs", "cu_partition", "force_tile",
+ * "profile_stride" and "host_chunk" - are one table (csrc/options.h): a row names the option, holds its default and the rule that
+ * turns davo_set_option's value into the one the context stores (switches: value != 0; ranges clamp, with "merge_order" > 2 -> 0,
+ * "fold_tails" > 2 -> 1, "fuse_pack" > 0 -> 1 and every negative auto value -> -1; "pad_classes": 0 -> 0, 1 -> 6, 8 + mask -> mask).
+ *   davo_get_option: *value = the stored value of a launch option, or the current value of "auto_range", "stable_inputs",
+ *     "cu_partition", "profile_stride" or "host_chunk".  "force_tile" is kept per layer and is refused, like an unknown key.
+ *   davo_option_info (no context, no GPU): row i of the table - its name and its default in stored form; DAVO_ERR_INVALID
+ *     for i < 0 and past the last row, which is how a caller finds the end.  Either pointer may be NULL.
+ *   davo_option_store (no context, no GPU): *stored = what davo_set_option(ctx, key, value) would store for a launch option;
+ *     DAVO_ERR_INVALID where it would refuse the value, and for every key that is no launch option. */
+int davo_get_option(const davo_ctx* ctx, const char* key, int* value);
+int davo_option_info(int i, const char** name, int* stored_default);
+int davo_option_store(const char* key, int value, int* stored);
 
 /* ---- multi-GPU: the pose gather of the window-sharded sequence driver, on RCCL ---------------
  * The reference runs one process on one GPU (test_kitti_pose.py:133-149: window loop, then the
@@ -901,8 +914,9 @@ int davo_plan_layer_f32(int mtiles, int npad, int groups, int ncu, int* mtile0, 
 /* Every launch decision of one conv layer on its own (no GPU needed): what a forward of NB pair images of an H x W frame issues for
  * layer 0..6 = cnv1..cnv7 through the implicit-GEMM kernels (csrc/plan.h: decide_layer_h3 for precision 1, decide_layer_f32 for 0),
  * with cnv6_out channels per head.  fuse_pose: the pose head runs in this launch's epilogue (layer 6 where the forward fuses it).
- * options[i], i < n_options <= DAVO_DECIDE_OPTIONS, in this order; the ones left out keep a new context's values:
- *    0 wave128          1 skip_order    2 merge_order   3 pad_classes (mask 1 cnv4 | 2 cnv5 | 4 cnv6)   4 merge_rem_f32
+ * options[i], i < n_options <= DAVO_DECIDE_OPTIONS, in this order; the ones left out keep a new context's values.  Positions 0..13
+ * are davo_option_info's rows 0..13, in stored form (what davo_option_store returns; "pad_classes" is the mask 1 cnv4 | 2 cnv5 | 4 cnv6):
+ *    0 wave128          1 skip_order    2 merge_order   3 pad_classes   4 merge_rem_f32
  *    5 share_taps       6 merge_rem     7 merge_cnv4    8 tile_208x128   9 deep_ring   10 split_k   11 fold_fixup
  *   12 f32_n16         13 f32_n256     14 compute units a launch may use (256)   15 compute units of the device (256)
  *   16 cu_partition    17 a caller's stream is set     18 max_batch (1)
@@ -933,8 +947,9 @@ int davo_decide_layer(int precision, int layer, int H, int W, int NB, int cnv6_o
  * call[DAVO_FORWARD_CALL_INTS]: H, W, B, pair selection (1 src0 | 2 src1 | 3 both), the kernels that run (0 f16x3 | 1 float32 |
  *   2 impl 1), the variant's att_source, cnv6_out and cin_per_frame, davo_set_posenn_topology's, davo_set_posenn_heads' and
  *   davo_set_posenn_se's values.
- * options[i], i < n_options <= DAVO_FORWARD_OPTIONS, in this order; the ones left out keep a new context's values:
- *    0 fold_tails (-1)   1 fuse_pack (-1)   2 fuse_pose (1)   3 patch_cnv1_t (1)   4 patch_cnv2 (1)   5 patch_cnv3 (1)   6 patch_f32 (1)
+ * options[i], i < n_options <= DAVO_FORWARD_OPTIONS, in this order; the ones left out keep a new context's values.  Positions 0..6
+ * are davo_option_info's rows 14..20, in stored form:
+ *    0 fold_tails   1 fuse_pack   2 fuse_pose   3 patch_cnv1_t   4 patch_cnv2   5 patch_cnv3   6 patch_f32
  *    7 force_tile (-1)   8 the batch's first kernel zeroes its range record's per-batch word (a ticketed batch; 0)
  *    9 the batch's last kernel mirrors the range record and keeps the inputs where it fails (every f16x3 batch of an entry point; 0)
  * out: DAVO_FORWARD_HEAD_INTS - images through cnv1..cnv7; the attention front: kind (0 flow | 1 flow, depth-split | 2 class table |

@@ -28,6 +28,11 @@ def test_the_table_is_the_recorded_one():
     assert set(STAGE) == set(FP.labels())
 
 
+def test_the_option_positions_and_defaults_are_the_library_table():
+    """The first seven PLAN_DEFAULTS, as forward_plan_cases.py types them out, are rows 14..20 of the library's option table."""
+    assert FP._lib.option_table()[14:] == list(FP.PLAN_DEFAULTS.items())[:7]
+
+
 def test_the_table_covers_the_rules():
     """Every front kind in both precisions on both sides of the fold boundary, the three PoseNN forms in both precisions and in
     impl 1 where it has one, one pair, each value of the options the sequence reads, both ways the snapshot travels."""

@@ -18,7 +18,7 @@ GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "lay
 OPTIONS = ("wave128", "skip_order", "merge_order", "pad_classes", "merge_rem_f32", "share_taps", "merge_rem", "merge_cnv4", "tile_208x128",
            "deep_ring", "split_k", "fold_fixup", "f32_n16", "f32_n256", "ncu", "dev_cus", "cu_partition", "user_stream", "max_batch",
            "shift_in", "shift_out", "force_tile", "pose_tail", "posenn_se", "triplet", "coupled")
-DEFAULTS = dict(wave128=2, skip_order=1, merge_order=-1, pad_classes=7, merge_rem_f32=1, share_taps=1, merge_rem=1, merge_cnv4=0,
+DEFAULTS = dict(wave128=2, skip_order=1, merge_order=-1, pad_classes=6, merge_rem_f32=1, share_taps=1, merge_rem=1, merge_cnv4=0,
                 tile_208x128=0, deep_ring=1, split_k=1, fold_fixup=0, f32_n16=1, f32_n256=0, ncu=256, dev_cus=256, cu_partition=0,
                 user_stream=0, max_batch=1, shift_in=0, shift_out=0, force_tile=-1, pose_tail=0, posenn_se=0, triplet=0, coupled=0)
 STEP = ("family", "tile", "row0", "m_end", "mtile0", "ntiles_n", "gx", "gy", "n_main", "n_rem", "order", "deep", "rem_label",
@@ -117,6 +117,18 @@ with open(GOLDEN) as f:
     ROWS = json.load(f)["rows"]
 
 
+def test_the_option_positions_and_defaults_are_the_library_table():
+    """OPTIONS[:14] and their DEFAULTS, as typed out above, are rows 0..13 of the library's option table (davo_option_info)."""
+    assert _lib.option_table()[:14] == [(k, DEFAULTS[k]) for k in OPTIONS[:14]]
+
+
+def test_pad_classes_default_leaves_cnv4_on_the_natural_order():
+    """A new context sorts cnv5 and cnv6 by padding class, not cnv4 (mask 6), and that is what the hook decides with no options; mask
+    7 takes cnv4 along.  B = 32 at 128x416 has class tables for all three layers (test_pad_classes_gpu.py)."""
+    assert [decide("f32", li, 128, 416, 64)["pad_classes"] for li in (3, 4, 5)] == [0, 1, 1]
+    assert decide("f32", 3, 128, 416, 64, pad_classes=7)["pad_classes"] == 1
+
+
 def row_id(r):
     return "%s-%s-cnv6_%d-%dx%d-B%d-fuse_pose%d" % (r["group"], r["precision"], r["width"], r["H"], r["W"], r["B"], r["fuse_pose"])
 
@@ -195,3 +207,9 @@ def test_arguments_are_checked():
     assert L.davo_decide_layer(1, 3, 128, 416, 2, 128, 0, None, 0, None, 0) < 0
     n = L.davo_decide_layer(1, 3, 128, 416, 2, 128, 0, None, 0, out, 64)          # no options given: a new context's
     assert n == 1 + out[0] * len(STEP) + len(TAIL)
+    # ... which is the record of DEFAULTS spelt out; so is float32 cnv4's at B = 32, where mask 6 and mask 7 decide differently
+    spelt = (ctypes.c_int * len(OPTIONS))(*[DEFAULTS[k] for k in OPTIONS])
+    for precision, NB in ((1, 2), (0, 64)):
+        full = (ctypes.c_int * 64)()
+        n = L.davo_decide_layer(precision, 3, 128, 416, NB, 128, 0, None, 0, out, 64)
+        assert n > 0 and L.davo_decide_layer(precision, 3, 128, 416, NB, 128, 0, spelt, len(OPTIONS), full, 64) == n and out[:n] == full[:n]

@@ -158,6 +158,34 @@ def test_launch_option(precision, name, B, H, W, options, plan_check, fuse_pose)
     e.close()
 
 
+def test_options_read_back_as_stored():
+    """A context only, no forward: every launch option reads back as the table's default on a new engine and, after set_option, as
+    what davo_option_store says the value is stored as; a refused value leaves the stored one alone."""
+    from davo_amd import _lib
+    table = _lib.option_table()
+    # one value per row that is not its default; the ranges' from outside, so that the stored value differs from the one set
+    values = dict(wave128=7, skip_order=-3, merge_order=5, pad_classes=9, merge_rem_f32=4, fold_tails=3, fuse_pack=5)
+    e = Engine(parse_version(FLAGSHIP_VERSION), 36, 100, 1)
+    try:
+        assert [(k, e.get_option(k)) for k, _ in table] == table
+        for k, default in table:
+            v = values.get(k, 2 if default == 0 else 0)                       # the switches: on as 2, off as 0
+            stored = _lib.option_store(k, v)
+            assert stored is not None and stored != default, (k, v, stored)
+            e.set_option(k, v)
+            assert e.get_option(k) == stored, (k, v)
+        with pytest.raises(ValueError, match=r"pad_classes must be 0, 1 or 8 \+ a layer mask \(8\.\.15\), got 2"):
+            e.set_option("pad_classes", 2)
+        assert e.get_option("pad_classes") == 1
+        assert (e.get_option("auto_range"), e.get_option("stable_inputs"), e.get_option("cu_partition"), e.get_option("profile_stride"),
+                e.get_option("host_chunk")) == (1, 0, 0, 1, 8)
+        for key in ("force_tile", "no_such_option"):
+            with pytest.raises(ValueError, match=key):
+                e.get_option(key)
+    finally:
+        e.close()
+
+
 # ---- float32 siblings to the bit ---------------------------------------------------------------------------------------
 def test_f32_merged_and_unmerged_grids_are_bit_identical():
     """merge_rem_f32 0 (main + remainder launches), 1 (cnv4..cnv6 as one grid, the default) and 2 (cnv7 too), and f32_n256
